@@ -7,13 +7,15 @@ resident in HBM: every rank renders its rows with one HIP kernel launch (float4
 linear-colour buffer + packed 0x00RRGGBB buffer), then -- for N > 1 -- a single
 RCCL gather of the packed rows to rank 0 reassembles the image.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line. `value` comes from the strictly SERIAL loop at N = 1 (one
-frame at a time on one stream; static camera, every table cached); everything else that
-was measured in the same run is reported next to it under its own key:
+frame at a time on one stream; static camera, every table cached). A plain run sets up,
+pre-rolls and warms up, times the K steps, writes the last step's frame if --dump-outputs
+is given, and prints the line. With --full everything else is measured in the same run
+and reported next to it under its own key:
   roofline         HBM roofline of the frame kernel: algorithmic bytes / the kernel's launch
                    duration (HIP events on the launch stream, serial loop) / 8 TB/s
   roofline_valu    the roof that binds (vector-instruction issue)
@@ -24,6 +26,8 @@ was measured in the same run is reported next to it under its own key:
                    setPixelBuff memcpy, what the reference's boundary requires per frame
   cpu_baseline     the CPU oracle timed on this box's cores (all cores and one thread) on a
                    bounded row sample, with GPU-vs-CPU parity checked on those rows
+  clocks, work, fast_mode, grid_order, and at N > 1 per_rank, gather_ms and the gathered
+  frame checked against a single-GPU render
 """
 import argparse
 import json
@@ -44,6 +48,9 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec
 VALU_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: peak fp32 vector
 FLOP_PER_TEST = 17           # the 17-flop discriminant
 EV_EVERY = 4                 # launches between two event-timed ones in the timed loop
+# --dump-outputs: bytes per array (64 MB in all); an array larger than its share is written at a fixed seeded sample of pixels
+DUMP_BUDGET = {"packed": 36_000_000, "rgba": 28_000_000}
+DUMP_SEED = 20261016
 
 
 def parse():
@@ -81,7 +88,33 @@ def parse():
                     help="timed loop: 1 = strictly serial (default at N = 1), 2 = consecutive frames alternate "
                          "between two HIP streams with their own framebuffers (default at N > 1, where frame i's "
                          "gather overlaps frame i+1's kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: clocks, rooflines, work counters, "
+                         "the moving-camera / pipelined / launch-order / fast-mode / update() legs, the CPU baseline with its "
+                         "parity check, and at N > 1 per-rank figures and the gathered frame against a single-GPU render")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's frame to DIR: packed.npy (the packed 0x00RRGGBB words, "
+                         "at N > 1 the frame gathered on rank 0, as float32: exact below 2^24) and rgba.npy (rank 0's float4 "
+                         "frame, float32); an array beyond its share of 64 MB is a seeded sample of pixels, <name>_index.npy "
+                         "holding their row-major indices")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor of shape (rows, width[, channels])} as DIR/<name>.npy in float32 (see --dump-outputs)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        n = t.shape[0] * t.shape[1]
+        per_pixel = t.numel() // n * 4
+        if n * per_pixel > DUMP_BUDGET[name]:
+            m = DUMP_BUDGET[name] // (per_pixel + 8)          # + 8 bytes of its float64 index
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            t = t.reshape(n, -1)[torch.from_numpy(idx).to(t.device)].squeeze(1)
+        a = t.cpu().numpy()
+        if a.dtype == np.int32:          # packed words: unsigned, below 2^24
+            a = a.view(np.uint32)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def cpu_model():
@@ -402,7 +435,7 @@ def main():
         for _ in range(50):
             step_main(k0, None)
             k0 += 1
-        if rank == 0:
+        if rank == 0 and args.full:
             clocks["before"] = read_clocks(fast_only=not args.smi_clocks)
         sync_main(k0)
     # (the pre-roll comes AFTER the clock reading: a query of the power controller disturbs the launches around it)
@@ -413,21 +446,24 @@ def main():
     # (no clock reading inside the timed region: a read of the power controller's tables takes a millisecond or two and was
     # measured to stretch a 20-step loop by 17 %; the clocks are read during untimed launches right before and right after)
     elapsed, k, _ = timed_loop(step_main, args.steps, args.warmup, sync_main, world, k0=k0)
-    kk = k
-    for _ in range(50):
-        step_main(kk, None)
-        kk += 1
-    if rank == 0:
-        clocks["after"] = read_clocks(fast_only=True)
-    sync_main(kk)
-    packed = packed2[(kk - 1) & 1]
-    rgba = rgba2[(kk - 1) & 1]
-    k = kk
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"packed": frame if world > 1 else packed2[(k - 1) & 1], "rgba": rgba2[(k - 1) & 1]})
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    if args.full:
+        kk = k
+        for _ in range(50):
+            step_main(kk, None)
+            kk += 1
+        if rank == 0:
+            clocks["after"] = read_clocks(fast_only=True)
+        sync_main(kk)
+        packed = packed2[(kk - 1) & 1]
+        rgba = rgba2[(kk - 1) & 1]
+        k = kk
     gather_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_g])) if ev_g else 0.0
     # per-rank figures ("report per-GPU kernel times"): every rank's own launch duration and loop time
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = torch.tensor([kernel_ms, elapsed / args.steps * 1e3, float(rows)], dtype=torch.float64, device=coll_dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -437,7 +473,7 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
 
     extras = {}
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         # camera nudged every frame (kernel.cu:1727 `cam.Org.z += 0.1`, back and forth so the view stays
         # the workload's): the eye-cone table is rebuilt on the device for every frame
         def cam_at(j):                 # eight positions 0.1 apart, walked back and forth
@@ -502,41 +538,18 @@ def main():
             scene.render_raw(fds[(k - 1) & 1], main_stream.cuda_stream)
             torch.cuda.synchronize()
 
-    # executed-work statistics from the instrumented kernel variant (untimed)
-    stats = scene.render(w, h, y0=y0, y1=y1, want_stats=True, spp=args.spp, cull=not args.no_cull, tile=args.tile,
-                         interleave=interleave)["stats"]
-    st = torch.tensor([stats[k] for k in rt.STAT_NAMES], dtype=torch.float64, device=coll_dev)
-    if world > 1:
-        dist.all_reduce(st, op=dist.ReduceOp.SUM)
-    stats = dict(zip(rt.STAT_NAMES, [float(v) for v in st.cpu()]))
+    if args.full:
+        # executed-work statistics from the instrumented kernel variant (untimed)
+        stats = scene.render(w, h, y0=y0, y1=y1, want_stats=True, spp=args.spp, cull=not args.no_cull, tile=args.tile,
+                             interleave=interleave)["stats"]
+        st = torch.tensor([stats[k] for k in rt.STAT_NAMES], dtype=torch.float64, device=coll_dev)
+        if world > 1:
+            dist.all_reduce(st, op=dist.ReduceOp.SUM)
+        stats = dict(zip(rt.STAT_NAMES, [float(v) for v in st.cpu()]))
 
     if rank == 0:
         rays = w * h * args.spp
         value = rays / (ms_per_step * 1e-3) / 1e6
-        # algorithmic bytes of one launch: float4 + packed word (+ 24-bit copy for the gather) per pixel-sample
-        band_bytes = rows * w * (16 + 4 + (3 if rgb24 else 0)) * 1.0
-        # the launch's duration: HIP events on its stream. With two frames in flight an event pair spans two
-        # overlapped kernels, so the per-frame time is the honest denominator there.
-        launch_ms = kernel_ms if nfl == 1 else ms_per_step
-        achieved = band_bytes / (launch_ms * 1e-3) / 1e9
-        slots = stats["wave_test_slots"] + stats["cull_tests"]     # lane slots issued for sphere/beam tests
-        valu_tflops = slots * FLOP_PER_TEST / (ms_per_step * 1e-3) / 1e12
-        pmc = committed_pmc(args, world)
-        valu = {}
-        if pmc:
-            try:
-                per_wave = pmc["derived"]["valu_insts_per_wave"]
-                waves = pmc["pmc_avg_per_dispatch"]["SQ_WAVES"]
-                rate = per_wave * waves / (256 * 4) / (launch_ms * 1e-3)      # VALU instructions / s / SIMD
-                valu = {"valu_insts_per_wave_pmc": per_wave, "salu_insts_per_wave_pmc": pmc["derived"].get("salu_insts_per_wave"),
-                        "pmc_file": pmc["file"],
-                        "valu_issue_rate_per_simd_Ginst_s": rate / 1e9, "valu_issue_nominal_per_simd_Ginst_s": 1.2,
-                        "valu_issue_frac_of_nominal": rate / 1.2e9,
-                        "note_issue": "nominal = one wave64 instruction per 2 cycles per SIMD at 2.4 GHz; plain fp32 ops reach "
-                                      "0.95 G/s on this chip, compares/selects/binary64 0.55, transcendentals 0.29 "
-                                      "(profiles/r01_valu_issue_rates.txt)"}
-            except Exception:
-                valu = {}
         out = {
             "metric": "primary_Mrays_per_s", "value": value, "unit": "Mrays/s",
             "frames_per_s": 1e3 / ms_per_step,
@@ -557,54 +570,82 @@ def main():
                        "frames_in_flight": nfl,
                        "outputs": "float4 RGBA + packed 0x00RRGGBB in HBM"},
             "kernel_ms": kernel_ms,
-            "clocks": {**clocks, "nominal_sclk_mhz": 2400,
-                       "note": "read during 50 untimed launches of this workload right before and right after the timed region "
-                               "(an idle GPU reports its idle clock; a read inside the region would stretch it); "
-                               "every fraction of a peak in this line is against the NOMINAL peak (8 TB/s, 157.3 TFLOP/s, "
-                               "2.4 GHz issue), not scaled to the clock read here"},
             "preroll": pre,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc["derived"].get("hbm_traffic_bytes") if pmc else None,
-                         "algorithmic_bytes_per_launch": band_bytes, "launch_ms": launch_ms,
-                         "note": "achieved = algorithmic_bytes_per_launch / launch_ms; launch_ms = mean HIP-event duration of the "
-                                 "frame kernel on its stream in this run's serial loop"
-                                 + ("" if nfl == 1 else " (two frames in flight: time per frame instead)")
-                                 + ". HBM is NOT the binding roof for this path (SURVEY.md F2); see roofline_valu."},
-            "roofline_valu": {"bound": "valu_fp32", "achieved": valu_tflops, "peak": VALU_PEAK_TFLOPS,
-                              "unit": "TFLOP/s", "frac": valu_tflops / VALU_PEAK_TFLOPS,
-                              "executed_test_slots": slots,
-                              "note": "64-lane issue slots of sphere + beam tests x 17 flop / frame time; "
-                                      "excludes ray setup and shading ALU work (most of the instructions)",
-                              **valu},
-            "work": {"hit_fraction": stats["hit_pixels"] / rays, "primary_lane_tests_per_ray": stats["primary_tests"] / rays,
-                     "shadow_lane_tests_per_ray": stats["shadow_tests"] / rays,
-                     "cull_tests_per_ray": stats["cull_tests"] / rays,
-                     "list_overflows": stats["list_overflows"]},
-            **extras,
         }
-        if world == 1 and not args.no_extras and (w, h, args.spp) == (3840, 2160, 1) and not args.no_cull:
-            out["update_end_to_end"] = update_end_to_end(rt, args, packed[:rows])
-        if world == 1 and not args.no_cpu_baseline:
-            torch.cuda.synchronize()
-            g_rgba = rgba.cpu().numpy() if args.spp == 1 else None
-            g_packed = packed[:rows].cpu().numpy().view(np.uint32)
-            cb = cpu_baseline(rt, scene, args, g_rgba, g_packed)
-            brute_tests = cb["tests_per_ray"] * rays
-            out["cpu_baseline"] = cb
-            out["work"]["brute_force_tests_per_ray"] = cb["tests_per_ray"]
-            out["work"]["algorithmic_rate_TFLOPs"] = brute_tests * FLOP_PER_TEST / (ms_per_step * 1e-3) / 1e12
-            out["work"]["executed_over_brute_force"] = slots / brute_tests
-        if world > 1:
-            out["per_rank"] = per_rank
-            out["gather_ms"] = {"root_kernel_end_to_assembled_ms": gather_ms,
-                                "note": "HIP events on the root's frame stream around every 4th frame's exchange: from the end of "
-                                        "the root's own kernel to the gather having delivered every rank's rows and "
-                                        "rt_assemble_rows24 having put them in place (includes waiting for the slowest rank)"}
-            # the assembled frame against a full single-GPU render of the same frame (untimed, rank 0)
-            full = scene.render(w, h, spp=args.spp, cull=not args.no_cull, tile=args.tile, want_rgba=False)["packed"]
-            torch.cuda.synchronize()
-            out["gathered_frame_shape"] = list(frame.shape)
-            out["gathered_frame_equals_single_gpu_render"] = bool(torch.equal(frame.to(full.device), full))
+        if args.full:
+            rays = w * h * args.spp
+            # algorithmic bytes of one launch: float4 + packed word (+ 24-bit copy for the gather) per pixel-sample
+            band_bytes = rows * w * (16 + 4 + (3 if rgb24 else 0)) * 1.0
+            # the launch's duration: HIP events on its stream. With two frames in flight an event pair spans two
+            # overlapped kernels, so the per-frame time is the honest denominator there.
+            launch_ms = kernel_ms if nfl == 1 else ms_per_step
+            achieved = band_bytes / (launch_ms * 1e-3) / 1e9
+            slots = stats["wave_test_slots"] + stats["cull_tests"]     # lane slots issued for sphere/beam tests
+            valu_tflops = slots * FLOP_PER_TEST / (ms_per_step * 1e-3) / 1e12
+            pmc = committed_pmc(args, world)
+            valu = {}
+            if pmc:
+                try:
+                    per_wave = pmc["derived"]["valu_insts_per_wave"]
+                    waves = pmc["pmc_avg_per_dispatch"]["SQ_WAVES"]
+                    rate = per_wave * waves / (256 * 4) / (launch_ms * 1e-3)      # VALU instructions / s / SIMD
+                    valu = {"valu_insts_per_wave_pmc": per_wave, "salu_insts_per_wave_pmc": pmc["derived"].get("salu_insts_per_wave"),
+                            "pmc_file": pmc["file"],
+                            "valu_issue_rate_per_simd_Ginst_s": rate / 1e9, "valu_issue_nominal_per_simd_Ginst_s": 1.2,
+                            "valu_issue_frac_of_nominal": rate / 1.2e9,
+                            "note_issue": "nominal = one wave64 instruction per 2 cycles per SIMD at 2.4 GHz; plain fp32 ops reach "
+                                          "0.95 G/s on this chip, compares/selects/binary64 0.55, transcendentals 0.29 "
+                                          "(profiles/r01_valu_issue_rates.txt)"}
+                except Exception:
+                    valu = {}
+            out.update({
+                "clocks": {**clocks, "nominal_sclk_mhz": 2400,
+                           "note": "read during 50 untimed launches of this workload right before and right after the timed region "
+                                   "(an idle GPU reports its idle clock; a read inside the region would stretch it); "
+                                   "every fraction of a peak in this line is against the NOMINAL peak (8 TB/s, 157.3 TFLOP/s, "
+                                   "2.4 GHz issue), not scaled to the clock read here"},
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": pmc["derived"].get("hbm_traffic_bytes") if pmc else None,
+                             "algorithmic_bytes_per_launch": band_bytes, "launch_ms": launch_ms,
+                             "note": "achieved = algorithmic_bytes_per_launch / launch_ms; launch_ms = mean HIP-event duration of the "
+                                     "frame kernel on its stream in this run's serial loop"
+                                     + ("" if nfl == 1 else " (two frames in flight: time per frame instead)")
+                                     + ". HBM is NOT the binding roof for this path (SURVEY.md F2); see roofline_valu."},
+                "roofline_valu": {"bound": "valu_fp32", "achieved": valu_tflops, "peak": VALU_PEAK_TFLOPS,
+                                  "unit": "TFLOP/s", "frac": valu_tflops / VALU_PEAK_TFLOPS,
+                                  "executed_test_slots": slots,
+                                  "note": "64-lane issue slots of sphere + beam tests x 17 flop / frame time; "
+                                          "excludes ray setup and shading ALU work (most of the instructions)",
+                                  **valu},
+                "work": {"hit_fraction": stats["hit_pixels"] / rays, "primary_lane_tests_per_ray": stats["primary_tests"] / rays,
+                         "shadow_lane_tests_per_ray": stats["shadow_tests"] / rays,
+                         "cull_tests_per_ray": stats["cull_tests"] / rays,
+                         "list_overflows": stats["list_overflows"]},
+                **extras,
+            })
+            if world == 1 and not args.no_extras and (w, h, args.spp) == (3840, 2160, 1) and not args.no_cull:
+                out["update_end_to_end"] = update_end_to_end(rt, args, packed[:rows])
+            if world == 1 and not args.no_cpu_baseline:
+                torch.cuda.synchronize()
+                g_rgba = rgba.cpu().numpy() if args.spp == 1 else None
+                g_packed = packed[:rows].cpu().numpy().view(np.uint32)
+                cb = cpu_baseline(rt, scene, args, g_rgba, g_packed)
+                brute_tests = cb["tests_per_ray"] * rays
+                out["cpu_baseline"] = cb
+                out["work"]["brute_force_tests_per_ray"] = cb["tests_per_ray"]
+                out["work"]["algorithmic_rate_TFLOPs"] = brute_tests * FLOP_PER_TEST / (ms_per_step * 1e-3) / 1e12
+                out["work"]["executed_over_brute_force"] = slots / brute_tests
+            if world > 1:
+                out["per_rank"] = per_rank
+                out["gather_ms"] = {"root_kernel_end_to_assembled_ms": gather_ms,
+                                    "note": "HIP events on the root's frame stream around every 4th frame's exchange: from the end of "
+                                            "the root's own kernel to the gather having delivered every rank's rows and "
+                                            "rt_assemble_rows24 having put them in place (includes waiting for the slowest rank)"}
+                # the assembled frame against a full single-GPU render of the same frame (untimed, rank 0)
+                full = scene.render(w, h, spp=args.spp, cull=not args.no_cull, tile=args.tile, want_rgba=False)["packed"]
+                torch.cuda.synchronize()
+                out["gathered_frame_shape"] = list(frame.shape)
+                out["gathered_frame_equals_single_gpu_render"] = bool(torch.equal(frame.to(full.device), full))
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
