@@ -36,6 +36,7 @@ extern "C" {
 #define RT_MAX_SPP 16
 #define RT_MAX_PLANES 64    /* planes and cubes are tested exhaustively (no culling) */
 #define RT_MAX_CUBES 256
+#define RT_MAX_REFLECT_DEPTH 8  /* rt_launch_opts.reflect_depth: bounces after the primary hit */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -144,7 +145,9 @@ typedef struct rt_object {                                   /* object, kernel.c
     rt_mesh *mesh1;          /* triangle mesh + flat BVH (kernel.cu:1293-1328, 1475-1497);
                                 NULL = no mesh (the reference's bvhbox_count = 0)       */
     rt_sprite *texture;      /* :1240, read at :1643-1655                             */
-    void *mat;               /* unused                                                */
+    void *mat;               /* NULL, or ONE rt_material (material, kernel.cu:213-224) that
+                                rt_launch_raytrace_ex applies to every sphere when
+                                opts->reflect_depth > 0; ignored otherwise                  */
     void **tot_mesh;
     int meshes;
 } rt_object;
@@ -217,6 +220,13 @@ typedef struct rt_launch_opts {
                                 about 2 pixels in 10^5 at C3. Never the
                                 default; culling kernels with the default tile and no mesh only --
                                 otherwise ignored (the launch is exact)                            */
+    int reflect_depth;       /* 0 (default; what a shorter struct_size reads as): no reflections, the
+                                frame exactly as without this field (same kernels, same launches).
+                                1..RT_MAX_REFLECT_DEPTH: mirror reflections off spheres with a non-zero
+                                material reflectivness (rt_scene_set_materials), at most this many
+                                bounces after the primary hit (DESIGN.md "Reflections"). Spheres only;
+                                spp 1; no accumulate, interleave_*, packed24, table_lds or profile
+                                (RT_ERR_UNSUPPORTED); `fast` is ignored (the launch is exact)      */
 } rt_launch_opts;
 
 enum { RT_STAT_PRIMARY_TESTS = 0, /* sphere tests issued for primary rays (per lane) */
@@ -332,6 +342,45 @@ int rt_scene_set_sky(rt_scene *s, const rt_sphere *box, const float *r, const fl
                      const float *b, int w, int h);
 int rt_scene_set_lights(rt_scene *s, const rt_light *lights, int n);
 
+/* material, kernel.cu:213-224 (field names as the reference spells them). Only reflectivness is
+ * implemented; a material with transperancy or roughness != 0 is RT_ERR_UNSUPPORTED. */
+typedef struct rt_material {
+    float reflectivness;     /* k in [0, 1]: the share of a hit's colour taken from its mirror ray */
+    float transperancy;      /* must be 0 */
+    float roughness;         /* must be 0 */
+} rt_material;               /* 12 bytes */
+
+/* One material per sphere of the scene's list (n == the sphere count); NULL / 0 clears them (every
+ * sphere then has k = 0). A reflectivness that is NaN or outside [0, 1]: RT_ERR_INVALID. The
+ * materials survive rt_scene_set_spheres with the same count and are cleared by a different count.
+ *
+ * Semantics of a frame with opts.reflect_depth = D > 0, per pixel (DESIGN.md "Reflections"): R_0 is
+ * the reference's primary ray, w = 1; for b = 0..D, castRay(R_b) over the spheres (sphere::intersect
+ * with all its quirks, first index wins ties). A miss adds w * getFColor(R_b) and stops. A hit on
+ * sphere i with k = material[i].reflectivness adds w * L (L = the reference's three-light sum at
+ * that hit) and stops if k == 0 or b == D; otherwise it adds (w * (1 - k)) * L, then w = w * k and
+ * R_{b+1} = ray(start_O, reflect(R_b.Dir, N)) (kernel.cu:1282-1285 in binary32, start_O = N*0.00001
+ * + new_org as rayTrace forms it). The first term is assigned, later ones added, per channel in
+ * binary32; rgba = (c, 1) and the packed word is rgbToInt(c * 254). A pixel whose primary hit has
+ * k = 0, and every sky pixel, is the frame without reflections bit for bit. */
+int rt_scene_set_materials(rt_scene *s, const rt_material *per_sphere, int n);
+
+/* What the last reflective frame of the scene did (a host wait for that frame): the sphere BVH
+ * (host build, binary64, rebuilt when the spheres change), the queue length entering every
+ * bounce, and -- when rt_scene_set_reflect_timing(s, 1) was called before the frame -- the
+ * device time of every pass (hipEvents: [0] the frame kernel, [1] the primary pass, [1 + b]
+ * bounce b). */
+typedef struct rt_reflect_stats {
+    double bvh_build_ms;     /* host time of the last BVH build                                  */
+    int bvh_nodes, bvh_depth, bvh_leaves;
+    int depth;               /* reflect_depth of the frame                                       */
+    int queue[RT_MAX_REFLECT_DEPTH + 1]; /* queue[b]: rays entering bounce b + 1                 */
+    float pass_ms[RT_MAX_REFLECT_DEPTH + 2];
+    int timed;               /* 1: pass_ms is filled                                              */
+} rt_reflect_stats;
+int rt_scene_set_reflect_timing(rt_scene *s, int on);
+int rt_scene_reflect_stats(rt_scene *s, rt_reflect_stats *out);
+
 typedef struct rt_frame_desc {
     uint32_t struct_size;
     int width, height;
@@ -341,6 +390,9 @@ typedef struct rt_frame_desc {
     rt_launch_opts opts;     /* rgba / band / spp / cull / stats                       */
 } rt_frame_desc;
 
+/* fd->struct_size and fd->opts.struct_size are honoured: a caller built against an older, shorter
+ * rt_frame_desc / rt_launch_opts gets its missing tail fields as 0. (0 in either reads as the
+ * layout before reflect_depth was appended.) */
 int rt_scene_render(rt_scene *s, const rt_frame_desc *fd, void *stream);
 
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
@@ -469,6 +521,21 @@ double rt_debug_sphere_beam_slope(const double lpos[3], const double centre[3], 
 double rt_debug_beam_sine(const double lpos[3], const double start[3], double *sigma, double *frob, double m9[9]);
 /* ... and as the DEVICE builds them (what a scene uses: one wave per sphere, members in list order); needs a GPU */
 int rt_debug_occluder_lists_device(const rt_sphere *spheres, int n, const rt_light *light, int *counts, float *kcaps, int *members, int cap);
+/* The sphere BVH of the reflective frames, built on the host (no GPU needed; tests only). Node j:
+ * lohi[6j..6j+5] = its box (lo xyz, hi xyz: binary32, rounded outward from the binary64 extents of
+ * its spheres), meta[2j] = first child (the second is meta[2j] + 1) or, for a leaf, the first
+ * position in `order`, meta[2j+1] = 0 for an inner node or the leaf's sphere count (1..4). Node 0
+ * is the root; order[] lists the sphere indices leaf by leaf. Returns RT_ERR_CAPACITY if cap is too
+ * small for the tree (2n nodes always suffice). */
+int rt_debug_sphere_bvh(const rt_sphere *spheres, int n, float *lohi, int *meta, int *order, int cap,
+                        int *n_nodes, int *depth);
+/* Host evaluation of the reflective passes' ray casts (the same code the kernels run): for each ray,
+ * nearest hit (hit_index[i], -1 = none, and t[i]) and any-hit (any[i]); use_bvh = 0 walks the whole
+ * list (the brute-force variant). Either output pointer group may be NULL.                       */
+int rt_debug_bvh_cast(const rt_sphere *spheres, int n, const rt_ray *rays, int n_rays, int use_bvh,
+                      int *hit_index, float *t, int *any);
+/* reflect(I, N), kernel.cu:1282-1285, in binary32 as the kernels evaluate it (n vectors).        */
+int rt_debug_reflect(const rt_vec3 *I, const rt_vec3 *N, int n, rt_vec3 *out);
 int rt_debug_occluder_lists_ex(const rt_sphere *spheres, int n, const rt_light *light, int *counts, float *kcaps, int *members, int cap,
                                int *offsets, int *entries_allocated);
 

@@ -30,6 +30,7 @@ except Exception:  # torch is optional for pure-host helpers
 
 RT_MAX_LIGHTS = 8
 RT_MAX_SPP = 16
+RT_MAX_REFLECT_DEPTH = 8
 RT_STATS_COUNT = 24
 STAT_NAMES = ("primary_tests", "shadow_tests", "cull_tests", "hit_pixels", "unshadowed",
               "wave_test_slots", "list_entries", "list_overflows",
@@ -123,7 +124,18 @@ class LaunchOpts(C.Structure):
                 ("accumulate", C.c_int), ("resolve", C.c_int), ("cull", C.c_int), ("tile", C.c_int),
                 ("stats", C.c_void_p), ("force_slow_path", C.c_int), ("profile", C.c_int),
                 ("interleave_count", C.c_int), ("interleave_index", C.c_int), ("interleave_rows", C.c_int),
-                ("packed24", C.c_void_p), ("table_lds", C.c_int), ("fast", C.c_int)]
+                ("packed24", C.c_void_p), ("table_lds", C.c_int), ("fast", C.c_int), ("reflect_depth", C.c_int)]
+
+
+class Material(C.Structure):
+    """rt_material (material, kernel.cu:213-224): only reflectivness is implemented."""
+    _fields_ = [("reflectivness", C.c_float), ("transperancy", C.c_float), ("roughness", C.c_float)]
+
+
+class ReflectStats(C.Structure):
+    _fields_ = [("bvh_build_ms", C.c_double), ("bvh_nodes", C.c_int), ("bvh_depth", C.c_int), ("bvh_leaves", C.c_int),
+                ("depth", C.c_int), ("queue", C.c_int * (RT_MAX_REFLECT_DEPTH + 1)),
+                ("pass_ms", C.c_float * (RT_MAX_REFLECT_DEPTH + 2)), ("timed", C.c_int)]
 
 
 class FrameDesc(C.Structure):
@@ -236,6 +248,12 @@ def load_library():
         "rt_multi_download": (ci, [vp, vp]),
         "rt_config_set_gpus": (ci, [ci]),
         "rt_assemble_rows24": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "rt_scene_set_materials": (ci, [vp, C.POINTER(Material), ci]),
+        "rt_scene_set_reflect_timing": (ci, [vp, ci]),
+        "rt_scene_reflect_stats": (ci, [vp, C.POINTER(ReflectStats)]),
+        "rt_debug_sphere_bvh": (ci, [C.POINTER(Sphere), ci, fp, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(ci), C.POINTER(ci)]),
+        "rt_debug_bvh_cast": (ci, [C.POINTER(Sphere), ci, C.POINTER(Ray), ci, ci, C.POINTER(ci), fp, C.POINTER(ci)]),
+        "rt_debug_reflect": (ci, [C.POINTER(Vec3), C.POINTER(Vec3), ci, C.POINTER(Vec3)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -385,6 +403,34 @@ class Scene:
         _check(self.lib.rt_scene_set_lights(self.handle, lights, n), "rt_scene_set_lights")
         self.lights, self.n_lights = lights, n
 
+    def set_materials(self, reflectivity):
+        """One material per sphere: an array of floats (reflectivness k in [0, 1]) or of Material; None clears them."""
+        if reflectivity is None or len(reflectivity) == 0:
+            _check(self.lib.rt_scene_set_materials(self.handle, None, 0), "rt_scene_set_materials")
+            self.materials = None
+            return
+        n = len(reflectivity)
+        mats = (Material * n)()
+        for i, m in enumerate(reflectivity):
+            if isinstance(m, Material):
+                mats[i] = m
+            else:
+                mats[i].reflectivness = float(m)
+        _check(self.lib.rt_scene_set_materials(self.handle, mats, n), "rt_scene_set_materials")
+        self.materials = mats
+
+    def set_reflect_timing(self, on: bool):
+        _check(self.lib.rt_scene_set_reflect_timing(self.handle, 1 if on else 0), "rt_scene_set_reflect_timing")
+
+    def reflect_stats(self) -> dict:
+        """What the last reflective frame did (waits for it): BVH, queue length per bounce, pass times if timed."""
+        st = ReflectStats()
+        _check(self.lib.rt_scene_reflect_stats(self.handle, C.byref(st)), "rt_scene_reflect_stats")
+        d = st.depth
+        return {"bvh_build_ms": st.bvh_build_ms, "bvh_nodes": st.bvh_nodes, "bvh_depth": st.bvh_depth,
+                "bvh_leaves": st.bvh_leaves, "depth": d, "queue": list(st.queue)[:d],
+                "pass_ms": list(st.pass_ms)[:d + 2] if st.timed else None}
+
     def set_tile_order(self, mode: int):
         """1 (default): launches start their longest tiles first (durations of earlier frames); 0: grid order."""
         _check(self.lib.rt_scene_set_tile_order(self.handle, mode), "rt_scene_set_tile_order")
@@ -400,7 +446,8 @@ class Scene:
 
     def frame_desc(self, width, height, *, pixels=0, rgba=0, cam=None, aspect=None, y0=0, y1=0, spp=1,
                    sample_base=0, sample_total=0, accumulate=False, resolve=0, cull=True, tile=0,
-                   stats=0, force_slow=False, profile=False, interleave=None, packed24=0, table_lds=False, fast=False) -> FrameDesc:
+                   stats=0, force_slow=False, profile=False, interleave=None, packed24=0, table_lds=False, fast=False,
+                   reflect_depth=0) -> FrameDesc:
         fd = FrameDesc()
         fd.struct_size = C.sizeof(FrameDesc)
         fd.width, fd.height = width, height
@@ -424,6 +471,7 @@ class Scene:
         o.packed24 = packed24
         o.table_lds = 1 if table_lds else 0
         o.fast = 1 if fast else 0
+        o.reflect_depth = reflect_depth
         return fd
 
     def render_raw(self, fd: FrameDesc, stream=0):

@@ -227,6 +227,8 @@ struct rt_scene {
     int tile_order_mode = 1;                 // rt_scene_set_tile_order
     hipEvent_t order_built = nullptr;        // the last rebuild; launches on other streams wait for it on the device
     bool order_pending = false;
+    // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
+    RtReflect *refl = nullptr;
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_table_lds = 0, tune_ablate = 0;
 #endif
@@ -324,6 +326,7 @@ extern "C" void rt_scene_destroy(rt_scene *s)
     if (s->table_stream) (void)hipStreamDestroy(s->table_stream);
     if (s->d_raygen) (void)hipFree(s->d_raygen);
     if (s->d_aux) (void)hipFree(s->d_aux);
+    rt_reflect_destroy(s->refl);
     for (hipEvent_t e : s->ring)
         if (e) (void)hipEventDestroy(e);
     delete s;
@@ -608,6 +611,7 @@ int rt_scene_set_spheres_async(rt_scene *s, const rt_sphere *host_spheres, int n
     s->sphere_gen++;
     s->epoch++;
     s->n_blocks = nb;
+    if (s->refl) rt_reflect_spheres_changed(s->refl, s->n_spheres, n);
     s->n_spheres = n;
     return RT_OK;
 }
@@ -1220,7 +1224,10 @@ int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelC
     kc->mode = fd->opts.stats ? (fd->opts.profile ? 3 : 1) : (fd->opts.force_slow_path ? 2 : 0);
     kc->feat = s->n_boxes > 0 ? 2 : ((s->n_planes > 0 || s->n_cubes > 0) ? 1 : 0);
     // the opt-in approximate mode exists for the product configuration only; anything else renders exactly
-    if (fd->opts.fast == 1 && kc->mode == 0 && kc->cull && kc->tile == 8 && kc->feat < 2 && fd->opts.table_lds != 1) kc->mode = 4;
+    // (a reflective frame is exact: `fast` is ignored there -- its L feeds the bounces)
+    if (fd->opts.fast == 1 && fd->opts.reflect_depth == 0 && kc->mode == 0 && kc->cull && kc->tile == 8 && kc->feat < 2 &&
+        fd->opts.table_lds != 1)
+        kc->mode = 4;
     // whole-table LDS staging (north_star's first design, measured slower: DESIGN.md section 3)
     // is opt-in per launch and only when the table fits next to the survivor lists
     kc->table_lds = (fd->opts.table_lds == 1 && s->n_spheres <= kMaxSpheresLds) ? 1 : 0;
@@ -1352,12 +1359,103 @@ static int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, Rt
     return RT_OK;
 }
 
-extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd, void *stream_)
+// The layout before rt_launch_opts.reflect_depth was appended: what struct_size 0 reads as.
+static const size_t kOptsSizeV1 = offsetof(rt_launch_opts, reflect_depth);
+static const size_t kFrameSizeV1 = offsetof(rt_frame_desc, opts) + kOptsSizeV1;
+
+// A frame description as this build lays it out, from a caller's that may be older (shorter): what the caller's
+// struct_size fields do not cover reads as 0.
+void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out)
+{
+    memset(out, 0, sizeof *out);
+    size_t fsz = fd->struct_size ? fd->struct_size : kFrameSizeV1;
+    if (fsz > sizeof *out) fsz = sizeof *out;
+    memcpy(out, fd, fsz);
+    const size_t have = fsz > offsetof(rt_frame_desc, opts) ? fsz - offsetof(rt_frame_desc, opts) : 0;
+    size_t osz = out->opts.struct_size ? out->opts.struct_size : kOptsSizeV1;
+    if (osz > have) osz = have;
+    if (osz < sizeof out->opts) memset(reinterpret_cast<char *>(&out->opts) + osz, 0, sizeof out->opts - osz);
+    out->struct_size = (uint32_t)sizeof *out;
+    out->opts.struct_size = (uint32_t)sizeof out->opts;
+}
+
+int rt_frame_reflect_depth(const rt_frame_desc *fd)
+{
+    if (!fd) return 0;
+    rt_frame_desc f;
+    normalise_frame_desc(fd, &f);
+    return f.opts.reflect_depth;
+}
+
+// What a reflective frame (opts.reflect_depth > 0) does not support; RT_OK when the frame may run.
+static int reflect_supported(const rt_scene *s, const rt_frame_desc *fd)
+{
+    const rt_launch_opts &o = fd->opts;
+    if (o.reflect_depth < 0 || o.reflect_depth > RT_MAX_REFLECT_DEPTH) {
+        rt_set_error("rt_scene_render: reflect_depth %d not in [0, %d]", o.reflect_depth, RT_MAX_REFLECT_DEPTH);
+        return RT_ERR_INVALID;
+    }
+    const char *why = nullptr;
+    if (s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0) why = "planes, cubes or a mesh in the scene";
+    else if (o.spp > 1 || o.sample_base != 0 || o.sample_total > 1) why = "more than one sample per pixel";
+    else if (o.accumulate) why = "accumulate";
+    else if (o.interleave_count > 1 || o.interleave_index != 0 || o.interleave_rows != 0) why = "interleave_*";
+    else if (o.packed24) why = "packed24";
+    else if (o.table_lds) why = "table_lds";
+    else if (o.profile) why = "profile";
+    if (why) {
+        rt_set_error("rt_scene_render: reflect_depth > 0 does not support %s (spheres only, one sample, plain outputs)", why);
+        return RT_ERR_UNSUPPORTED;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_scene_set_materials(rt_scene *s, const rt_material *per_sphere, int n)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_materials: null scene");
+        return RT_ERR_INVALID;
+    }
+    if (!s->refl) s->refl = rt_reflect_create();
+    // frames in flight may read the device copy: rt_reflect_prepare re-uploads it before the next reflective frame,
+    // after those frames (rt_scene_render waits for them when anything changed)
+    return rt_reflect_set_materials(s->refl, per_sphere, n, s->n_spheres);
+}
+
+extern "C" int rt_scene_set_reflect_timing(rt_scene *s, int on)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_reflect_timing: null scene");
+        return RT_ERR_INVALID;
+    }
+    if (!s->refl) s->refl = rt_reflect_create();
+    return rt_reflect_set_timing(s->refl, on);
+}
+
+extern "C" int rt_scene_reflect_stats(rt_scene *s, rt_reflect_stats *out)
+{
+    if (!s || !out) {
+        rt_set_error("rt_scene_reflect_stats: null argument");
+        return RT_ERR_INVALID;
+    }
+    if (!s->refl) s->refl = rt_reflect_create();
+    return rt_reflect_get_stats(s->refl, out);
+}
+
+extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!s || !fd) {
+    if (!s || !fd_in) {
         rt_set_error("rt_scene_render: null scene or frame");
         return RT_ERR_INVALID;
+    }
+    rt_frame_desc fd_local;
+    normalise_frame_desc(fd_in, &fd_local);
+    const rt_frame_desc *fd = &fd_local;
+    const int reflect_depth = fd->opts.reflect_depth;
+    if (reflect_depth != 0) {
+        const int rc = reflect_supported(s, fd);
+        if (rc != RT_OK) return rc;
     }
     {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1394,11 +1492,37 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd, void *strea
     rc = rt_frame_kernel_choice(s, fd, &kc);
     if (rc != RT_OK) return rc;
     if (fc.local_rows == 0) return RT_OK;   // this rank owns no rows of the frame
+    if (reflect_depth > 0) {
+        // the queues, the BVH and the materials are the scene's: after every frame launched so far (a host wait only
+        // when the BVH or the materials change)
+        if (!s->refl) s->refl = rt_reflect_create();
+        if (rt_reflect_needs_upload(s->refl, s->sphere_gen, s->n_spheres)) {
+            rc = rt_scene_quiesce(s);
+            if (rc != RT_OK) return rc;
+        }
+        rc = stream_wait_all_frames(s, stream);
+        if (rc != RT_OK) return rc;
+        float *scratch = nullptr;
+        rc = rt_reflect_prepare(s->refl, s->h_prev.data(), s->n_spheres, s->sphere_gen, fc.width * fc.local_rows,
+                                fc.rgba == nullptr, &scratch, stream);
+        if (rc != RT_OK) return rc;
+        if (!fc.rgba) fc.rgba = scratch;
+        rc = rt_reflect_begin_frame(s->refl, reflect_depth, stream);
+        if (rc != RT_OK) return rc;
+    }
     if (s->tile_order_mode != 0 && !kc.table_lds) {
         rc = rt_scene_prepare_tile_order(s, kc, &fc, stream);
         if (rc != RT_OK) return rc;
     }
+    if (reflect_depth > 0) {
+        rc = rt_reflect_mark_frame_start(s->refl, stream);
+        if (rc != RT_OK) return rc;
+    }
     RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres, kc.tile, kc.cull, kc.mode, kc.table_lds, kc.feat, stream));
+    if (reflect_depth > 0) {
+        rc = rt_reflect_launch(s->refl, &fc, s->d_spheres, s->n_spheres, reflect_depth, kc.cull == 0, stream);
+        if (rc != RT_OK) return rc;
+    }
     return rt_scene_note_launch(s, stream, slot);
 }
 
@@ -1547,6 +1671,15 @@ extern "C" int rt_launch_raytrace_ex(uint32_t *pixels, int width, int height, fl
     if (objs->cube_count > 0 || s->n_cubes > 0) {
         rc = rt_scene_set_cubes(s, objs->d_cubes, objs->cube_count);
         if (rc != RT_OK) return rc;
+    }
+    // the reference's object-wide material (object::mat) on every sphere, for a reflective launch only
+    if (opts && opts->struct_size >= offsetof(rt_launch_opts, reflect_depth) + sizeof(int) && opts->reflect_depth > 0) {
+        {
+            std::vector<rt_material> mats;
+            if (objs->mat) mats.assign((size_t)objs->sphere_count, *static_cast<const rt_material *>(objs->mat));
+            rc = rt_scene_set_materials(s, mats.empty() ? nullptr : mats.data(), (int)mats.size());
+            if (rc != RT_OK) return rc;
+        }
     }
 
     rt_frame_desc fd;

@@ -259,13 +259,17 @@ extern "C" rt_frame_graph *rt_graph_capture(rt_scene *s, const rt_frame_desc *fd
         rt_set_error("rt_graph_capture: the instrumented kernels are not recorded into graphs");
         return nullptr;
     }
+    if (rt_frame_reflect_depth(fd) != 0) {
+        rt_set_error("rt_graph_capture: reflect_depth > 0 is not recorded into graphs (RT_ERR_UNSUPPORTED)");
+        return nullptr;
+    }
     if (rt_dev_prepare() != hipSuccess) {
         rt_set_error("rt_graph_capture: kernel image not loadable on this device");
         return nullptr;
     }
     rt_frame_graph *g = new rt_frame_graph();
     g->scene = s;
-    g->fd = *fd;
+    normalise_frame_desc(fd, &g->fd);   // (a caller's shorter struct ends before the newer fields)
     g->samples = passes;
     g->passes = progressive ? passes : 1;
     g->host_pixels = host_pixels;

@@ -46,3 +46,23 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
                                           const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes);
 extern "C" hipError_t rt_dev_launch_trace(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
                                           int table_in_lds, int feat, hipStream_t stream);
+
+// rt_reflect.hip: mirror reflections (rt_launch_opts.reflect_depth) -- materials, sphere BVH, queues, passes
+struct RtReflect;
+RtReflect *rt_reflect_create();
+void rt_reflect_destroy(RtReflect *r);
+void rt_reflect_spheres_changed(RtReflect *r, int n_old, int n_new);
+int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_spheres);
+bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n);
+int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned long long sphere_gen, int npx,
+                       bool need_rgba, float **rgba_scratch, hipStream_t stream);
+int rt_reflect_begin_frame(RtReflect *r, int depth, hipStream_t stream);
+int rt_reflect_mark_frame_start(RtReflect *r, hipStream_t stream);
+int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute,
+                      hipStream_t stream);
+int rt_reflect_set_timing(RtReflect *r, int on);
+int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out);
+// opts.reflect_depth of a frame description, honouring the struct sizes (0 where the caller's structs end before it)
+int rt_frame_reflect_depth(const rt_frame_desc *fd);
+// a caller's frame description in this build's layout (what its struct_size fields do not cover reads as 0)
+void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out);

@@ -1,0 +1,833 @@
+// rt_reflect.hip -- mirror reflections off spheres (rt_launch_opts.reflect_depth, DESIGN.md "Reflections").
+//
+// A reflective frame runs the frame kernel (rt_trace.inc) as it is, into rgba: that gives every pixel its primary
+// term -- the three-light sum L of its primary hit, or its sky texel. Then, on the same stream and without a host wait:
+//   primary   casts every pixel's primary ray again (nearest hit through the sphere BVH) and ballot-compacts the
+//             pixels whose hit sphere has k = reflectivness > 0 into a queue: {pixel, R_1, w = k, c = (1-k) * L};
+//   bounce b  (b = 1..D, one launch each, a fixed grid that reads the queue length on the device): nearest hit of
+//             R_b through the BVH; a miss adds w * sky; a hit is shaded as the frame kernel shades one (texel, ten
+//             shadow samples per light from the frame kernel's own ShadowChain, any-hit tests through the BVH) and
+//             either adds w * L and ends (k = 0 or b = D) or adds (w * (1-k)) * L and queues R_{b+1} with w * k.
+//             A pixel that ends writes rgba = (c, 1) and its packed word there and then: the pixels that never
+//             entered the queue keep what the frame kernel wrote.
+// The brute-force variant (opts.cull = 0) is the same kernels with the BVH replaced by the whole sphere list.
+//
+// The BVH (host build in binary64, leaves of <= 4 spheres) is exact against the list: its traversal never drops a
+// sphere that sphere::intersect reports as hit, and the nearest hit is the lexicographic minimum of (t, index) --
+// what the reference's strict `t < nt` loop returns. The margin and the pruning rule are derived in DESIGN.md.
+#include "rt_trace.inc"
+#include "rt_internal.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#define RT_BVH_LEAF 4
+#define RT_BVH_STACK 24        // traversal stack entries per lane (LDS, 24 KiB per workgroup); the host refuses a deeper
+                               // tree (a median split of the library's 4 M spheres is 21 deep)
+#define RT_BVH_PAD_REL 1.5e-2  // ray-dependent box padding: RT_BVH_PAD_REL * (L1 distance to the box's far corner + largest
+#define RT_BVH_PAD_ABS 1.0e-16 // radius) + RT_BVH_PAD_ABS: twice the bound 7e-3 derived in DESIGN.md "Reflections" 
+#define RT_REFLECT_BLOCK 256
+#define RT_BOUNCE_GRID 2048    // workgroups of a bounce launch (grid-stride over the queue)
+
+struct BvhNode {   // 48 bytes; children of an inner node are `first` and `first + 1`
+    float lo[3];
+    float rmax;    // largest sphere radius below the node (rounded up)
+    float hi[3];
+    int first;     // inner: first child; leaf: first position in order[] / lsph[]
+    int count;     // 0: inner node; else the leaf's sphere count
+    int axis;      // inner: split axis (the first child holds the lower centres)
+    int pad_[2];
+};
+
+struct QEntry {    // one queued ray: 48 bytes
+    float ox, oy, oz, dx, dy, dz;
+    float w, cr, cg, cb;
+    int pix;       // band-local pixel index
+    int pad_;
+};
+
+struct RtReflectDev {              // the passes' uniforms (by value)
+    const BvhNode *nodes;          // null: walk the whole list (brute force, or a scene the BVH does not cover)
+    const float4 *lsph;            // spheres in leaf order
+    const int *order;              // their list positions
+    const float4 *spheres;         // the list
+    int n;
+    const float *k;                // reflectivness per sphere (null: all 0)
+    int depth;
+};
+
+// ---------------------------------------------------------------------------
+// host & device: sphere::intersect, the BVH walk
+// ---------------------------------------------------------------------------
+// sphere::intersect, kernel.cu:293-354, on a table entry {cx,cy,cz,radius*radius}: the operations of quadratic() and
+// intersect_tail() in rt_trace.inc, in the same order (this file is compiled without contraction, both sides).
+__host__ __device__ __forceinline__ bool rf_intersect(float ox, float oy, float oz, float dx, float dy, float dz,
+                                                      float4 s, float &t)
+{
+    const float ocx = ox - s.x, ocy = oy - s.y, ocz = oz - s.z;
+    const float h = (dx * ocx + dy * ocy) + dz * ocz;
+    const float B = 2.f * h;
+    const float C = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.w;
+    const float A = (dx * dx + dy * dy) + dz * dz;
+    const float disc = B * B - (4.f * A) * C;
+    const float sq = __builtin_sqrtf(disc);
+    const float a2 = 2.f * ((dx * dx + dy * dy) + dz * dz);
+    t = (-B + sq) / a2;
+    if (t == 0.f) return true;
+    if (t >= RT_T_MIN) {
+        const float t2 = (-B - sq) / a2;
+        if (t > t2) t = t2;
+        return true;
+    }
+    return false;
+}
+
+// The traversal's preconditions: a finite origin within 1e15 of the world origin and a direction of
+// squared length in [0.9, 1.1] (every ray here is a unit vector up to rounding). Other rays walk the list.
+__host__ __device__ __forceinline__ bool rf_ray_ok(float ox, float oy, float oz, float dx, float dy, float dz)
+{
+    const double A = ((double)dx * dx + (double)dy * dy) + (double)dz * dz;
+    return __builtin_fabs((double)ox) <= 1e15 && __builtin_fabs((double)oy) <= 1e15 && __builtin_fabs((double)oz) <= 1e15 &&
+           A >= 0.9 && A <= 1.1;   // false for a NaN anywhere
+}
+
+struct RayD {
+    double o[3], inv[3];
+    float d[3];
+};
+
+// The node's box padded for this ray (any sphere of the node that intersect() reports as hit puts its
+// returned t inside [tmin, tmax] of this padded box, and tmax >= 0). Binary64 slab test, unclamped tmin.
+__host__ __device__ __forceinline__ bool rf_node_test(const BvhNode &nd, const RayD &r, double &tmin)
+{
+    double dsum = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const double e0 = __builtin_fabs(r.o[a] - (double)nd.lo[a]), e1 = __builtin_fabs(r.o[a] - (double)nd.hi[a]);
+        dsum += e0 > e1 ? e0 : e1;
+    }
+    const double pad = RT_BVH_PAD_REL * (dsum + (double)nd.rmax) + RT_BVH_PAD_ABS;
+    double t0 = -__builtin_inf(), t1 = __builtin_inf();
+    for (int a = 0; a < 3; ++a) {
+        const double lo = (double)nd.lo[a] - pad, hi = (double)nd.hi[a] + pad;
+        if (r.d[a] == 0.f) {
+            if (r.o[a] < lo || r.o[a] > hi) return false;
+        } else {
+            double ta = (lo - r.o[a]) * r.inv[a], tb = (hi - r.o[a]) * r.inv[a];
+            if (ta > tb) { const double x = ta; ta = tb; tb = x; }
+            t0 = ta > t0 ? ta : t0;
+            t1 = tb < t1 ? tb : t1;
+        }
+    }
+    tmin = t0;
+    return t0 <= t1 && t1 >= 0.0;
+}
+
+// Nearest hit (ANY = false: lexicographic minimum of (t, list index), -1 = none) or any-hit (ANY = true: returns 0 / 1).
+// STK(i) is the lane's i-th stack slot.
+template <bool ANY, class Stack>
+__host__ __device__ __forceinline__ int rf_cast(const RtReflectDev &rd, float ox, float oy, float oz, float dx, float dy,
+                                                float dz, float &t_best, Stack stk)
+{
+    int best = -1;
+    float bt = __builtin_inff();
+    if (!rd.nodes || !rf_ray_ok(ox, oy, oz, dx, dy, dz)) {
+        for (int i = 0; i < rd.n; ++i) {
+            float t;
+            if (rf_intersect(ox, oy, oz, dx, dy, dz, rd.spheres[i], t)) {
+                if (ANY) { t_best = t; return 1; }
+                if (t < bt) { bt = t; best = i; }   // kernel.cu:1335: strict, the first index wins ties
+            }
+        }
+        t_best = bt;
+        return ANY ? 0 : best;
+    }
+    RayD r;
+    r.o[0] = ox; r.o[1] = oy; r.o[2] = oz;
+    r.d[0] = dx; r.d[1] = dy; r.d[2] = dz;
+    r.inv[0] = 1.0 / (double)dx; r.inv[1] = 1.0 / (double)dy; r.inv[2] = 1.0 / (double)dz;
+    int sp = 0;
+    stk(sp++) = 0;
+    while (sp > 0) {
+        const BvhNode nd = rd.nodes[stk(--sp)];
+        double tmin;
+        if (!rf_node_test(nd, r, tmin)) continue;
+        if (!ANY && tmin > (double)bt) continue;   // every hit inside has t >= tmin > bt (unclamped tmin: DESIGN.md)
+        if (nd.count == 0) {
+            // the nearer child last (popped first): the first child holds the lower centres along `axis`
+            const bool up = (nd.axis == 0 ? r.d[0] : (nd.axis == 1 ? r.d[1] : r.d[2])) >= 0.f;   // (no dynamic index: scratch)
+            stk(sp++) = up ? nd.first + 1 : nd.first;
+            stk(sp++) = up ? nd.first : nd.first + 1;
+            continue;
+        }
+        for (int p = nd.first; p < nd.first + nd.count; ++p) {
+            float t;
+            if (rf_intersect(ox, oy, oz, dx, dy, dz, rd.lsph[p], t)) {
+                if (ANY) { t_best = t; return 1; }
+                const int idx = rd.order[p];
+                if (t < bt || (t == bt && idx < best)) { bt = t; best = idx; }
+            }
+        }
+    }
+    t_best = bt;
+    return ANY ? 0 : best;
+}
+
+// reflect(I, N), kernel.cu:1282-1285: sub(I, multiply(multiply(N, dot(I, N)), 2)), the dot product left to right
+__host__ __device__ __forceinline__ void rf_reflect(float ix, float iy, float iz, float nx, float ny, float nz, float &rx,
+                                                    float &ry, float &rz)
+{
+    const float d = (ix * nx + iy * ny) + iz * nz;
+    rx = ix - (nx * d) * 2.f;
+    ry = iy - (ny * d) * 2.f;
+    rz = iz - (nz * d) * 2.f;
+}
+
+// ---------------------------------------------------------------------------
+// device passes
+// ---------------------------------------------------------------------------
+namespace {
+
+struct LdsStack {
+    int *base;   // this workgroup's stack array, slot i of thread tid at base[i * RT_REFLECT_BLOCK + tid]
+    int tid;
+    __device__ int &operator()(int i) const { return base[i * RT_REFLECT_BLOCK + tid]; }
+};
+
+// Append the lanes with `push` set to the queue (one atomic per wave). Every lane of the wave calls it.
+__device__ __forceinline__ void rf_push(bool push, const QEntry &e, QEntry *q, int *count)
+{
+    const lmask m = ballot64(push);
+    if (m == 0) return;
+    const int leader = __builtin_ctzll(m);
+    int b = 0;
+    if ((int)(threadIdx.x & 63u) == leader) b = atomicAdd(count, __popcll(m));
+    const int base = __builtin_amdgcn_readlane(b, leader);
+    if (push) q[base + lane_prefix(m)] = e;
+}
+
+// skybox::getFColor, kernel.cu:1147-1166, as the frame kernel's brute-force instantiation evaluates it
+__device__ __forceinline__ void rf_sky(AuxPtr ax, V3 O, V3 D, float &r, float &g, float &b)
+{
+    const RayK pr = make_ray(O, D);
+    const float4 sk = make_float4(ax->sky_cx, ax->sky_cy, ax->sky_cz, ax->sky_r2);
+    const Quad q = quadratic(pr, sk);
+    float t;
+    intersect_tail(pr, q, t);   // the boolean is ignored there, t is used as left
+    const V3 hp{O.x + D.x * t, O.y + D.y * t, O.z + D.z * t};
+    V3 nrm{hp.x - sk.x, hp.y - sk.y, hp.z - sk.z};
+    normalise_inplace(nrm);
+    const int sky_w = ax->sky_w, sky_h = ax->sky_h;
+    const int ix = f2i((1.f + rtm::atan2f_rt(nrm.z, nrm.x) / 3.1415f) * 0.5f * (float)sky_w);
+    const int iy = f2i(rtm::acosf_rt(nrm.y) / 3.1415f * (float)sky_h);
+    int idx = iy * sky_w + ix;
+    const int last = sky_w * sky_h - 1;
+    idx = idx < 0 ? 0 : (idx > last ? last : idx);   // documented clamp (as the frame kernel)
+    r = ax->sky_r[idx];
+    g = ax->sky_g[idx];
+    b = ax->sky_b[idx];
+}
+
+// The hit point, normal and start_O of castRay's / rayTrace's sphere branch (kernel.cu:1398-1405, 1647)
+__device__ __forceinline__ void rf_hit_frame(V3 O, V3 D, float nt, float4 s, V3 &normal, V3 &start)
+{
+    const V3 new_org{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
+    normal = V3{new_org.x - s.x, new_org.y - s.y, new_org.z - s.z};
+    normalise_inplace(normal);
+    start = V3{normal.x * 0.00001f + new_org.x, normal.y * 0.00001f + new_org.y, normal.z * 0.00001f + new_org.z};
+}
+
+// The three-light sum of rayTrace (kernel.cu:1643-1679) at a sphere hit, with castLightRay's sample construction
+// taken from the frame kernel (ShadowChain, brute-force precision) and its any-hit loop through the BVH.
+// Called by every lane of the wave in uniform control flow; `act` = this lane has a hit to shade.
+__device__ __forceinline__ void rf_shade(const RtFrameConsts &fc, AuxPtr ax, const RtReflectDev &rd, bool act, V3 normal,
+                                         V3 start, LdsStack stk, float &fr, float &fg, float &fb)
+{
+    fr = fg = fb = 0.f;
+    float tr = 0.f, tg = 0.f, tb = 0.f;
+    if (act) {
+        const float tx = (float)((1.0 + rtm::div_by_3p1415((double)rtm::atan2f_rt(normal.z, normal.x))) * 0.5);
+        const float ty = (float)rtm::div_by_3p1415((double)rtm::acosf_rt(normal.y));
+        int ci = f2i(ty * (float)fc.tex_h) * fc.tex_w + f2i(tx * (float)fc.tex_w);
+        const int last = fc.tex_w * fc.tex_h - 1;
+        ci = ci < 0 ? 0 : (ci > last ? last : ci);   // documented clamp (as the frame kernel)
+        tr = fc.tex_r[ci];
+        tg = fc.tex_g[ci];
+        tb = fc.tex_b[ci];
+    }
+    if (!any64(act)) return;
+    if (act) {
+        for (int li = 0; li < fc.n_lights; ++li) {
+            const RtLightDev L = ax->lights[li];
+            ShadowChain<0> chain;
+            chain.begin(V3{L.px, L.py, L.pz}, start);
+            int unshadowed = 0;
+#pragma unroll 1
+            for (int j = 0; j < RT_SHADOW_SAMPLES; ++j) {
+                const V3 d = chain.direction(ax, false, L, start, j);
+                float t;
+                if (!rf_cast<true>(rd, start.x, start.y, start.z, d.x, d.y, d.z, t, stk)) unshadowed += 1;   // kernel.cu:1537-1539
+            }
+            float bsum = brightness_steps(unshadowed);
+            const float a = dot3(normal, chain.toL);                    // kernel.cu:1541
+            bsum = bsum * (a > 0.f ? a : 0.f);
+            fr = fr + bsum * L.r * tr;                                  // kernel.cu:1673-1675
+            fg = fg + bsum * L.g * tg;
+            fb = fb + bsum * L.b * tb;
+        }
+    }
+}
+
+__device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float cr, float cg, float cb)
+{
+    if (fc.rgba) reinterpret_cast<float4 *>(fc.rgba)[pix] = make_float4(cr, cg, cb, 1.f);
+    if (fc.packed && (fc.flags & RT_FLAG_RESOLVE))
+        fc.packed[pix] = rgb_to_int(f2i(cr * 254.f), f2i(cg * 254.f), f2i(cb * 254.f));   // kernel.cu:1682
+}
+
+// The primary pass: every pixel of the band; queues those whose primary hit is reflective.
+__global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtFrameConsts fc, const RtReflectDev rd,
+                                                                       QEntry *q, int *count)
+{
+    __shared__ int stack_lds[RT_BVH_STACK * RT_REFLECT_BLOCK];
+    const LdsStack stk{stack_lds, (int)threadIdx.x};
+    const int npx = fc.width * fc.local_rows;
+    const int pix = (int)(blockIdx.x * RT_REFLECT_BLOCK + threadIdx.x);
+    const bool valid = pix < npx;
+    QEntry e{};
+    bool push = false;
+    if (valid) {
+        const int ly = pix / fc.width, px = pix - ly * fc.width;
+        const int py = fc.y0 + ly;
+        // kernel.cu:1624-1631, as the frame kernel forms it (one sample: sample_base 0 is checked by the host)
+        V3 dir{fc.dx_tab[px], fc.dy_tab[py], fc.eye_nz};
+        normalise_inplace(dir);
+        const float y = dir.y * fc.cos_pitch - dir.z * fc.sin_pitch;
+        float z = dir.y * fc.sin_pitch + dir.z * fc.cos_pitch;
+        const float x = dir.x * fc.cos_yaw + z * fc.sin_yaw;
+        z = -dir.x * fc.sin_yaw + z * fc.cos_yaw;
+        const V3 D{x, y, z};
+        const V3 O{fc.org_x, fc.org_y, fc.org_z};
+        float nt;
+        const int hit = rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk);
+        const float k = (hit >= 0 && rd.k) ? rd.k[hit] : 0.f;
+        if (k > 0.f) {
+            V3 normal, start;
+            rf_hit_frame(O, D, nt, rd.spheres[hit], normal, start);
+            const float4 L = reinterpret_cast<const float4 *>(fc.rgba)[pix];   // the frame kernel's L for this hit
+            const float f = 1.f - k;                                            // (w * (1 - k)) with w = 1
+            e.ox = start.x; e.oy = start.y; e.oz = start.z;
+            rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, e.dx, e.dy, e.dz);
+            e.w = k;                                                            // w * k with w = 1
+            e.cr = f * L.x; e.cg = f * L.y; e.cb = f * L.z;                     // the first term is assigned
+            e.pix = pix;
+            push = true;
+        }
+    }
+    rf_push(push, e, q, count);
+}
+
+// Bounce b (1..depth): a fixed grid walks the queue of the previous pass; its length is read here, on the device.
+__global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFrameConsts fc, const RtReflectDev rd, int b,
+                                                                      const QEntry *qin, const int *count_in, QEntry *qout,
+                                                                      int *count_out)
+{
+    __shared__ int stack_lds[RT_BVH_STACK * RT_REFLECT_BLOCK];
+    const LdsStack stk{stack_lds, (int)threadIdx.x};
+    const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;
+    const int n_in = *count_in;
+    for (int base = (int)blockIdx.x * RT_REFLECT_BLOCK; base < n_in; base += (int)gridDim.x * RT_REFLECT_BLOCK) {
+        const int i = base + (int)threadIdx.x;
+        const bool valid = i < n_in;
+        QEntry e{};
+        if (valid) e = qin[i];
+        const V3 O{e.ox, e.oy, e.oz}, D{e.dx, e.dy, e.dz};
+        float nt = 0.f;
+        const int hit = valid ? rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk) : -1;
+        const bool act = valid && hit >= 0;
+        V3 normal{0.f, 1.f, 0.f}, start{0.f, 0.f, 0.f};
+        if (act) rf_hit_frame(O, D, nt, rd.spheres[hit], normal, start);
+        float Lr, Lg, Lb;
+        rf_shade(fc, ax, rd, act, normal, start, stk, Lr, Lg, Lb);
+        bool push = false;
+        QEntry nx{};
+        if (valid) {
+            float cr = e.cr, cg = e.cg, cb = e.cb;
+            bool done = true;
+            if (!act) {                        // a miss: w * getFColor(R_b), and the pixel is done
+                float sr, sg, sb;
+                rf_sky(ax, O, D, sr, sg, sb);
+                cr = cr + e.w * sr; cg = cg + e.w * sg; cb = cb + e.w * sb;
+            } else {
+                const float k = rd.k ? rd.k[hit] : 0.f;
+                if (k == 0.f || b == rd.depth) {
+                    cr = cr + e.w * Lr; cg = cg + e.w * Lg; cb = cb + e.w * Lb;
+                } else {
+                    const float f = e.w * (1.f - k);
+                    cr = cr + f * Lr; cg = cg + f * Lg; cb = cb + f * Lb;
+                    nx.ox = start.x; nx.oy = start.y; nx.oz = start.z;
+                    rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, nx.dx, nx.dy, nx.dz);
+                    nx.w = e.w * k;
+                    nx.cr = cr; nx.cg = cg; nx.cb = cb;
+                    nx.pix = e.pix;
+                    done = false;
+                    push = true;
+                }
+            }
+            if (done) rf_write(fc, e.pix, cr, cg, cb);
+        }
+        rf_push(push, nx, qout, count_out);
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+struct RtReflect {
+    std::vector<float> k;                 // reflectivness per sphere; empty = all 0
+    std::vector<float> k_dev;             // what the device copy holds (the source of its upload: changed only after
+                                          // the frames that may still read it, in rt_reflect_prepare)
+    bool k_dirty = false;
+    float *d_k = nullptr;
+    size_t cap_k = 0;
+    // the BVH of the sphere list it was built from
+    unsigned long long bvh_gen = ~0ull;
+    int bvh_n = -1;
+    bool bvh_ok = false;                  // false: the list is walked (non-finite or huge data)
+    std::vector<BvhNode> nodes;
+    std::vector<float4> lsph;
+    std::vector<int> order;
+    BvhNode *d_nodes = nullptr;
+    float4 *d_lsph = nullptr;
+    int *d_order = nullptr;
+    size_t cap_nodes = 0, cap_lsph = 0;
+    int depth = 0, leaves = 0;
+    double build_ms = 0.0;
+    // queues and counters
+    QEntry *d_q[2] = {nullptr, nullptr};
+    size_t cap_q = 0;
+    int *d_cnt = nullptr;
+    float4 *d_rgba = nullptr;             // frame-kernel output when the caller gave no rgba
+    size_t cap_rgba = 0;
+    // the last frame
+    int last_depth = 0;
+    bool have_frame = false;
+    int timing = 0;
+    bool timed = false;
+    hipEvent_t ev[RT_MAX_REFLECT_DEPTH + 3] = {};
+    hipEvent_t done = nullptr;            // after the last pass of the last frame (rt_reflect_get_stats waits for it)
+};
+
+static int rf_build_rec(const std::vector<float4> &sph, std::vector<int> &idx, int lo, int hi, int node, int level,
+                        RtReflect *r)
+{
+    r->depth = level > r->depth ? level : r->depth;
+    double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    double clo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, chi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    double rmax = 0.0;
+    for (int p = lo; p < hi; ++p) {
+        const float4 s = sph[idx[p]];
+        const double c[3] = {s.x, s.y, s.z};
+        const double R = std::sqrt((double)s.w);   // intersect() squares the `radius` field: its radius is sqrt(w)
+        rmax = R > rmax ? R : rmax;
+        for (int a = 0; a < 3; ++a) {
+            blo[a] = std::min(blo[a], c[a] - R);
+            bhi[a] = std::max(bhi[a], c[a] + R);
+            clo[a] = std::min(clo[a], c[a]);
+            chi[a] = std::max(chi[a], c[a]);
+        }
+    }
+    BvhNode &nd = r->nodes[node];
+    for (int a = 0; a < 3; ++a) {   // rounded outward to binary32
+        float l = (float)blo[a], h = (float)bhi[a];
+        if ((double)l > blo[a]) l = std::nextafter(l, -HUGE_VALF);
+        if ((double)h < bhi[a]) h = std::nextafter(h, HUGE_VALF);
+        nd.lo[a] = l;
+        nd.hi[a] = h;
+    }
+    float rm = (float)rmax;
+    if ((double)rm < rmax) rm = std::nextafter(rm, HUGE_VALF);
+    nd.rmax = rm;
+    if (hi - lo <= RT_BVH_LEAF) {
+        nd.first = lo;
+        nd.count = hi - lo;
+        nd.axis = 0;
+        r->leaves++;
+        return RT_OK;
+    }
+    int axis = 0;
+    for (int a = 1; a < 3; ++a)
+        if (chi[a] - clo[a] > chi[axis] - clo[axis]) axis = a;
+    const int mid = lo + (hi - lo) / 2;   // median split: depth <= ceil(log2(n / 4)) + 1
+    auto key = [&](int i) { const float4 s = sph[i]; return axis == 0 ? s.x : (axis == 1 ? s.y : s.z); };
+    std::nth_element(idx.begin() + lo, idx.begin() + mid, idx.begin() + hi, [&](int a, int b) {
+        const float ka = key(a), kb = key(b);
+        return ka < kb || (ka == kb && a < b);
+    });
+    const int child = (int)r->nodes.size();
+    r->nodes.resize(r->nodes.size() + 2);
+    BvhNode &nd2 = r->nodes[node];   // (resize may move the array)
+    nd2.first = child;
+    nd2.count = 0;
+    nd2.axis = axis;
+    int rc = rf_build_rec(sph, idx, lo, mid, child, level + 1, r);
+    if (rc != RT_OK) return rc;
+    return rf_build_rec(sph, idx, mid, hi, child + 1, level + 1, r);
+}
+
+// Host build (binary64 extents, binary32 boxes rounded outward). bvh_ok = false when a sphere is non-finite or lies
+// beyond 1e15 (the traversal's derivation assumes neither): every ray then walks the list.
+static int rf_build(RtReflect *r, const float4 *sph, int n)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    r->nodes.clear();
+    r->lsph.clear();
+    r->order.clear();
+    r->depth = 0;
+    r->leaves = 0;
+    r->bvh_ok = n > 0;
+    for (int i = 0; i < n && r->bvh_ok; ++i) {
+        const float4 s = sph[i];
+        const double R = std::sqrt((double)s.w);
+        if (!(std::fabs((double)s.x) + R <= 1e15 && std::fabs((double)s.y) + R <= 1e15 && std::fabs((double)s.z) + R <= 1e15))
+            r->bvh_ok = false;   // (false for NaN / inf too)
+    }
+    if (r->bvh_ok) {
+        std::vector<float4> v(sph, sph + n);
+        std::vector<int> idx((size_t)n);
+        for (int i = 0; i < n; ++i) idx[(size_t)i] = i;
+        r->nodes.reserve((size_t)2 * n);
+        r->nodes.resize(1);
+        int rc = rf_build_rec(v, idx, 0, n, 0, 0, r);
+        if (rc != RT_OK) return rc;
+        if (r->depth + 2 > RT_BVH_STACK) {   // the stack holds at most depth + 1 entries (two pushed per inner node)
+            rt_set_error("reflections: sphere BVH depth %d exceeds the traversal stack (%d)", r->depth, RT_BVH_STACK);
+            return RT_ERR_CAPACITY;
+        }
+        r->order = idx;
+        r->lsph.resize((size_t)n);
+        for (int p = 0; p < n; ++p) r->lsph[(size_t)p] = v[(size_t)idx[(size_t)p]];
+    }
+    r->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
+static RtReflectDev rf_host_view(const RtReflect *r, const float4 *sph, int n, bool use_bvh)
+{
+    RtReflectDev rd{};
+    rd.nodes = (use_bvh && r->bvh_ok) ? r->nodes.data() : nullptr;
+    rd.lsph = r->lsph.data();
+    rd.order = r->order.data();
+    rd.spheres = sph;
+    rd.n = n;
+    return rd;
+}
+
+RtReflect *rt_reflect_create() { return new RtReflect(); }
+
+void rt_reflect_destroy(RtReflect *r)
+{
+    if (!r) return;
+    if (r->d_k) (void)hipFree(r->d_k);
+    if (r->d_nodes) (void)hipFree(r->d_nodes);
+    if (r->d_lsph) (void)hipFree(r->d_lsph);
+    if (r->d_order) (void)hipFree(r->d_order);
+    for (QEntry *q : r->d_q)
+        if (q) (void)hipFree(q);
+    if (r->d_cnt) (void)hipFree(r->d_cnt);
+    if (r->d_rgba) (void)hipFree(r->d_rgba);
+    for (hipEvent_t e : r->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (r->done) (void)hipEventDestroy(r->done);
+    delete r;
+}
+
+// rt_scene_set_spheres: a new count clears the materials (the same count keeps them)
+void rt_reflect_spheres_changed(RtReflect *r, int n_old, int n_new)
+{
+    if (n_old != n_new && !r->k.empty()) {
+        r->k.clear();
+        r->k_dirty = true;
+    }
+}
+
+int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_spheres)
+{
+    if (!m || n == 0) {
+        if (!r->k.empty()) r->k_dirty = true;
+        r->k.clear();
+        return RT_OK;
+    }
+    if (n != n_spheres || n < 0) {
+        rt_set_error("rt_scene_set_materials: %d materials for %d spheres (one per sphere, or NULL / 0)", n, n_spheres);
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) {
+        const float k = m[i].reflectivness;
+        if (!(k >= 0.f && k <= 1.f)) {
+            rt_set_error("rt_scene_set_materials: sphere %d: reflectivness %g is not in [0, 1]", i, (double)k);
+            return RT_ERR_INVALID;
+        }
+        if (m[i].transperancy != 0.f || m[i].roughness != 0.f) {
+            rt_set_error("rt_scene_set_materials: sphere %d: transperancy / roughness are not implemented (only reflectivness)", i);
+            return RT_ERR_UNSUPPORTED;
+        }
+    }
+    std::vector<float> k((size_t)n);
+    for (int i = 0; i < n; ++i) k[(size_t)i] = m[i].reflectivness;
+    if (k != r->k) {   // (the drop-in boundary sets the same materials every frame: no re-upload then)
+        r->k.swap(k);
+        r->k_dirty = true;
+    }
+    return RT_OK;
+}
+
+bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n)
+{
+    return r->k_dirty || r->bvh_gen != sphere_gen || r->bvh_n != n;
+}
+
+// Brings materials and BVH up to date (the caller has waited for every frame that may read them) and makes sure the
+// queues hold `npx` pixels. rgba_scratch: set when the caller has no rgba buffer.
+int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned long long sphere_gen, int npx,
+                       bool need_rgba, float **rgba_scratch, hipStream_t stream)
+{
+    if (r->bvh_gen != sphere_gen || r->bvh_n != n) {
+        const int rc = rf_build(r, h_spheres, n);
+        if (rc != RT_OK) return rc;
+        if (r->bvh_ok) {
+            if (r->nodes.size() > r->cap_nodes) {
+                if (r->d_nodes) RT_HIP(hipFree(r->d_nodes));
+                r->d_nodes = nullptr;
+                r->cap_nodes = 0;
+                RT_HIP(hipMalloc((void **)&r->d_nodes, sizeof(BvhNode) * r->nodes.size()));
+                r->cap_nodes = r->nodes.size();
+            }
+            if ((size_t)n > r->cap_lsph) {
+                if (r->d_lsph) RT_HIP(hipFree(r->d_lsph));
+                if (r->d_order) RT_HIP(hipFree(r->d_order));
+                r->d_lsph = nullptr;
+                r->d_order = nullptr;
+                r->cap_lsph = 0;
+                RT_HIP(hipMalloc((void **)&r->d_lsph, sizeof(float4) * (size_t)n));
+                RT_HIP(hipMalloc((void **)&r->d_order, sizeof(int) * (size_t)n));
+                r->cap_lsph = (size_t)n;
+            }
+            RT_HIP(hipMemcpyAsync(r->d_nodes, r->nodes.data(), sizeof(BvhNode) * r->nodes.size(), hipMemcpyHostToDevice, stream));
+            RT_HIP(hipMemcpyAsync(r->d_lsph, r->lsph.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, stream));
+            RT_HIP(hipMemcpyAsync(r->d_order, r->order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream));
+        }
+        r->bvh_gen = sphere_gen;
+        r->bvh_n = n;
+    }
+    if (r->k_dirty) {
+        r->k_dev = r->k;
+        if (!r->k_dev.empty()) {
+            if (r->k_dev.size() > r->cap_k) {
+                if (r->d_k) RT_HIP(hipFree(r->d_k));
+                r->d_k = nullptr;
+                r->cap_k = 0;
+                RT_HIP(hipMalloc((void **)&r->d_k, sizeof(float) * r->k_dev.size()));
+                r->cap_k = r->k_dev.size();
+            }
+            RT_HIP(hipMemcpyAsync(r->d_k, r->k_dev.data(), sizeof(float) * r->k_dev.size(), hipMemcpyHostToDevice, stream));
+        }
+        r->k_dirty = false;
+    }
+    if ((size_t)npx > r->cap_q) {
+        for (QEntry *&q : r->d_q) {
+            if (q) RT_HIP(hipFree(q));
+            q = nullptr;
+        }
+        r->cap_q = 0;
+        for (QEntry *&q : r->d_q) RT_HIP(hipMalloc((void **)&q, sizeof(QEntry) * (size_t)npx));
+        r->cap_q = (size_t)npx;
+    }
+    if (!r->d_cnt) RT_HIP(hipMalloc((void **)&r->d_cnt, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1)));
+    *rgba_scratch = nullptr;
+    if (need_rgba) {
+        if ((size_t)npx > r->cap_rgba) {
+            if (r->d_rgba) RT_HIP(hipFree(r->d_rgba));
+            r->d_rgba = nullptr;
+            r->cap_rgba = 0;
+            RT_HIP(hipMalloc((void **)&r->d_rgba, sizeof(float4) * (size_t)npx));
+            r->cap_rgba = (size_t)npx;
+        }
+        *rgba_scratch = reinterpret_cast<float *>(r->d_rgba);
+    }
+    return RT_OK;
+}
+
+// timing: an event before the frame kernel (slot 0) and after every pass (slots 1 ..)
+static hipError_t rt_reflect_mark(RtReflect *r, int slot, hipStream_t stream)
+{
+    if (!r->timing) return hipSuccess;
+    if (!r->ev[slot]) {
+        const hipError_t e = hipEventCreate(&r->ev[slot]);
+        if (e != hipSuccess) return e;
+    }
+    return hipEventRecord(r->ev[slot], stream);
+}
+
+int rt_reflect_begin_frame(RtReflect *r, int depth, hipStream_t stream)
+{
+    RT_HIP(hipMemsetAsync(r->d_cnt, 0, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), stream));
+    r->last_depth = depth;
+    r->have_frame = true;
+    r->timed = r->timing != 0;
+    return RT_OK;
+}
+
+// Right before the frame kernel's launch (after anything else the frame enqueues, e.g. the tile-order sort).
+int rt_reflect_mark_frame_start(RtReflect *r, hipStream_t stream)
+{
+    RT_HIP(rt_reflect_mark(r, 0, stream));
+    return RT_OK;
+}
+
+// The passes after the frame kernel (which has written fc->rgba).
+int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute,
+                      hipStream_t stream)
+{
+    RT_HIP(rt_reflect_mark(r, 1, stream));
+    RtReflectDev rd{};
+    rd.nodes = (!brute && r->bvh_ok) ? r->d_nodes : nullptr;
+    rd.lsph = r->d_lsph;
+    rd.order = r->d_order;
+    rd.spheres = d_spheres;
+    rd.n = n;
+    rd.k = r->k_dev.empty() ? nullptr : r->d_k;
+    rd.depth = depth;
+    const int npx = fc->width * fc->local_rows;
+    hipLaunchKernelGGL(rt_reflect_primary, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
+                       stream, *fc, rd, r->d_q[0], r->d_cnt);
+    RT_HIP(hipGetLastError());
+    RT_HIP(rt_reflect_mark(r, 2, stream));
+    for (int b = 1; b <= depth; ++b) {
+        hipLaunchKernelGGL(rt_reflect_bounce, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, rd, b,
+                           r->d_q[(b - 1) & 1], r->d_cnt + (b - 1), r->d_q[b & 1], r->d_cnt + b);
+        RT_HIP(hipGetLastError());
+        RT_HIP(rt_reflect_mark(r, 2 + b, stream));
+    }
+    if (!r->done) RT_HIP(hipEventCreateWithFlags(&r->done, hipEventDisableTiming));
+    RT_HIP(hipEventRecord(r->done, stream));
+    return RT_OK;
+}
+
+int rt_reflect_set_timing(RtReflect *r, int on)
+{
+    r->timing = on ? 1 : 0;
+    return RT_OK;
+}
+
+int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out)
+{
+    memset(out, 0, sizeof *out);
+    out->bvh_build_ms = r->build_ms;
+    out->bvh_nodes = (int)r->nodes.size();
+    out->bvh_depth = r->depth;
+    out->bvh_leaves = r->leaves;
+    if (!r->have_frame) return RT_OK;
+    out->depth = r->last_depth;
+    if (r->done) RT_HIP(hipEventSynchronize(r->done));   // the last frame only, not the whole device
+    RT_HIP(hipMemcpy(out->queue, r->d_cnt, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), hipMemcpyDeviceToHost));
+    if (r->timed) {
+        for (int p = 0; p < r->last_depth + 2; ++p) {
+            float ms = 0.f;
+            RT_HIP(hipEventElapsedTime(&ms, r->ev[p], r->ev[p + 1]));
+            out->pass_ms[p] = ms;
+        }
+        out->timed = 1;
+    }
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// host-only debug entries (tests)
+// ---------------------------------------------------------------------------
+static void pack_list(const rt_sphere *s, int n, std::vector<float4> &v)
+{
+    v.resize((size_t)n);
+    for (int i = 0; i < n; ++i)
+        v[(size_t)i] = make_float4(s[i].orgin.x, s[i].orgin.y, s[i].orgin.z, s[i].radius * s[i].radius);
+}
+
+extern "C" int rt_debug_sphere_bvh(const rt_sphere *spheres, int n, float *lohi, int *meta, int *order, int cap,
+                                   int *n_nodes, int *depth)
+{
+    if (!spheres || n <= 0 || !lohi || !meta || !order || !n_nodes || !depth) {
+        rt_set_error("rt_debug_sphere_bvh: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    std::vector<float4> v;
+    pack_list(spheres, n, v);
+    RtReflect r;
+    const int rc = rf_build(&r, v.data(), n);
+    if (rc != RT_OK) return rc;
+    if (!r.bvh_ok) {
+        rt_set_error("rt_debug_sphere_bvh: the list has non-finite or huge spheres (no BVH: the list is walked)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    if ((int)r.nodes.size() > cap) {
+        rt_set_error("rt_debug_sphere_bvh: %d nodes exceed cap %d", (int)r.nodes.size(), cap);
+        return RT_ERR_CAPACITY;
+    }
+    for (size_t j = 0; j < r.nodes.size(); ++j) {
+        for (int a = 0; a < 3; ++a) {
+            lohi[6 * j + a] = r.nodes[j].lo[a];
+            lohi[6 * j + 3 + a] = r.nodes[j].hi[a];
+        }
+        meta[2 * j] = r.nodes[j].first;
+        meta[2 * j + 1] = r.nodes[j].count;
+    }
+    for (int p = 0; p < n; ++p) order[p] = r.order[(size_t)p];
+    *n_nodes = (int)r.nodes.size();
+    *depth = r.depth;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_bvh_cast(const rt_sphere *spheres, int n, const rt_ray *rays, int n_rays, int use_bvh,
+                                 int *hit_index, float *t, int *any)
+{
+    if (!spheres || n <= 0 || !rays || n_rays < 0) {
+        rt_set_error("rt_debug_bvh_cast: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    std::vector<float4> v;
+    pack_list(spheres, n, v);
+    RtReflect r;
+    int rc = RT_OK;
+    if (use_bvh) rc = rf_build(&r, v.data(), n);
+    if (rc != RT_OK) return rc;
+    const RtReflectDev rd = rf_host_view(&r, v.data(), n, use_bvh != 0);
+    int stack[RT_BVH_STACK];
+    auto stk = [&stack](int i) -> int & { return stack[i]; };
+    for (int i = 0; i < n_rays; ++i) {
+        const rt_ray &ray = rays[i];
+        if (hit_index || t) {
+            float tb;
+            const int h = rf_cast<false>(rd, ray.Org.x, ray.Org.y, ray.Org.z, ray.Dir.x, ray.Dir.y, ray.Dir.z, tb, stk);
+            if (hit_index) hit_index[i] = h;
+            if (t) t[i] = tb;
+        }
+        if (any) {
+            float ta;
+            any[i] = rf_cast<true>(rd, ray.Org.x, ray.Org.y, ray.Org.z, ray.Dir.x, ray.Dir.y, ray.Dir.z, ta, stk);
+        }
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_reflect(const rt_vec3 *I, const rt_vec3 *N, int n, rt_vec3 *out)
+{
+    if (!I || !N || !out || n < 0) {
+        rt_set_error("rt_debug_reflect: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) rf_reflect(I[i].x, I[i].y, I[i].z, N[i].x, N[i].y, N[i].z, out[i].x, out[i].y, out[i].z);
+    return RT_OK;
+}
