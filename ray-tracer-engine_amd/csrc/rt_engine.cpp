@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -124,15 +125,18 @@ extern "C" void rt_managed_free(void *ptr)
 #define RT_CONE_SLOTS 3
 
 struct ConeSlot {
-    float4 *buf = nullptr;
-    size_t cap = 0;                       // float4 units
+    DevArray<float4> buf;
     float org[3] = {0, 0, 0};
     unsigned long long gen = ~0ull;       // sphere_gen the table was built from
     bool valid = false;
     bool used = false;                    // read by some frame since it was built
     unsigned long long last_use = 0;      // ring sequence number of the last frame that read it
-    hipEvent_t built = nullptr;           // the build on the scene's table stream
+    HipEvent built;                       // the build on the scene's table stream
     bool build_pending = false;           // `built` not yet seen complete: readers wait on it (on the device)
+};
+
+struct RtReflectDeleter {
+    void operator()(RtReflect *r) const { rt_reflect_destroy(r); }
 };
 
 #define RT_ORDER_SLOTS 4
@@ -143,10 +147,8 @@ struct ConeSlot {
 struct TileOrder {
     int key[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // tile width, frame width / height, y0, y1, local rows, interleave
                                                   // count / index / rows, and which kernel: cull, mode, samples
-    unsigned *cost = nullptr, *perm = nullptr, *bkey = nullptr, *start = nullptr;   // one allocation: [cap] durations, [cap] order,
-                                                                                      // [nb_cap] block keys, [nb_cap] block starts
-    size_t cap = 0, nb_cap = 0;
-    int n = 0, tiles_x = 0, tiles_y = 0, nb = 0;
+    RtTileOrderBuf buf;                          // empty: the slot has had no layout yet
+    RtTileGrid grid = {};
     float view[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // camera and sphere list the last launch saw
     int same_view = 0;                           // consecutive launches of that view so far
     int since_sort = 0;                          // launches (all of which recorded durations) since the order was sorted / reset
@@ -155,41 +157,35 @@ struct TileOrder {
 };
 
 struct rt_scene {
-    float4 *d_spheres = nullptr;     // [n] list order | [n_pad] Morton order | [n_blocks] block bounds | [n_pad] ints
-    int n_spheres = 0, cap_spheres = 0;
+    DevArray<float4> d_spheres;      // [n] list order | [n_pad] Morton order | [n_blocks] block bounds | [n_pad] ints
+    int n_spheres = 0;
     int n_blocks = 0;
     std::vector<float4> h_prev;      // what was uploaded last (skip identical re-mirrors)
-    float4 *h_stage = nullptr;   // pinned staging for asynchronous re-uploads
-    int cap_stage = 0;
-    hipEvent_t stage_done = nullptr;   // the last upload out of h_stage
+    PinnedArray<float4> h_stage;     // staging for asynchronous re-uploads
+    HipEvent stage_done;             // the last upload out of h_stage
     bool stage_busy = false;
-    float *d_tex[3] = {nullptr, nullptr, nullptr};
+    DevArray<float> d_tex[3];
     int tex_w = 0, tex_h = 0;
-    float *d_sky[3] = {nullptr, nullptr, nullptr};
+    DevArray<float> d_sky[3];
     int sky_w = 0, sky_h = 0;
     float sky_c[3] = {0, 0, 0};
     float sky_radius = 0;        // the sphere's `radius` field (already r*r)
     bool have_sky = false;
     rt_light lights[RT_MAX_LIGHTS];
     int n_lights = 0;
-    RtPlaneDev *d_planes = nullptr;
-    RtCubeDev *d_cubes = nullptr;
+    DevArray<RtPlaneDev> d_planes;
+    DevArray<RtCubeDev> d_cubes;
     int n_planes = 0, n_cubes = 0;
-    RtTriDev *d_tris = nullptr;
-    RtBoxDev *d_boxes = nullptr;
-    int *d_tri_idx = nullptr;
-    float *d_box_spheres = nullptr;
-    float *d_tri9 = nullptr;
-    float *d_tri_bs = nullptr;
-    float *d_tri_nrm = nullptr;
+    DevArray<RtTriDev> d_tris;
+    DevArray<RtBoxDev> d_boxes;
+    DevArray<int> d_tri_idx;
+    DevArray<float> d_box_spheres, d_tri9, d_tri_bs, d_tri_nrm;
     int n_boxes = 0, n_tris = 0, mesh_has_normals = 0;
     // per-light column blocks (see RtFrameAux::lsorted): one allocation, rebuilt when the
     // sphere list or a light's position changes
-    float4 *d_light_tabs = nullptr;
-    size_t cap_light_tabs = 0;           // float4 units
+    DevArray<float4> d_light_tabs;
     // per-light occluder lists (rt_build_occluder_lists): [n_lights][n] headers, then the lights' entry arrays
-    char *d_cand = nullptr;
-    size_t cap_cand = 0;                 // bytes
+    DevArray<char> d_cand;
     size_t cand_ent_off[RT_MAX_LIGHTS] = {};   // byte offset of light i's entries in d_cand (headers: i * n * 16)
     bool cand_valid[RT_MAX_LIGHTS] = {};
     float cand_pos[RT_MAX_LIGHTS][3];    // light position each list set was built for
@@ -203,18 +199,17 @@ struct rt_scene {
     // eye cones for the primary rays (see RtFrameConsts::csorted), one table per recent ray origin
     ConeSlot cones[RT_CONE_SLOTS];
     // dx / dy of the primary rays per column / row and sample (RtFrameConsts::dx_tab)
-    float *d_raygen = nullptr;
-    size_t cap_raygen = 0;               // floats
+    DevArray<float> d_raygen;
     int rg_w = 0, rg_h = 0, rg_total = 0;
     float rg_aspect = 0.f;
     // RtFrameAux as uploaded last
     RtFrameAux h_aux;
-    RtFrameAux *d_aux = nullptr;
+    DevArray<RtFrameAux> d_aux;
     bool aux_valid = false;
     // where the eye-cone builds run: beside the frames, not in front of them
-    hipStream_t table_stream = nullptr;
+    HipStream table_stream;
     // frames in flight
-    hipEvent_t ring[RT_RING] = {};
+    HipEvent ring[RT_RING];
     bool ring_used[RT_RING] = {};
     unsigned long long ring_seq = 0;     // sequence number of the next launch
     // bumped whenever a buffer a recorded graph may point into is rewritten or re-allocated
@@ -225,10 +220,10 @@ struct rt_scene {
     TileOrder orders[RT_ORDER_SLOTS];
     unsigned long long order_clock = 0;      // for least-recently-used replacement
     int tile_order_mode = 1;                 // rt_scene_set_tile_order
-    hipEvent_t order_built = nullptr;        // the last rebuild; launches on other streams wait for it on the device
+    HipEvent order_built;                    // the last rebuild; launches on other streams wait for it on the device
     bool order_pending = false;
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
-    RtReflect *refl = nullptr;
+    std::unique_ptr<RtReflect, RtReflectDeleter> refl;
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_table_lds = 0, tune_ablate = 0;
 #endif
@@ -253,20 +248,12 @@ extern "C" rt_scene *rt_scene_create(void)
     return s;
 }
 
-static void free_planes(float *p[3])
-{
-    for (int i = 0; i < 3; ++i) {
-        if (p[i]) (void)hipFree(p[i]);
-        p[i] = nullptr;
-    }
-}
-
 // Wait (on the host) for every frame launched on this scene so far.
 int rt_scene_quiesce(rt_scene *s)
 {
     for (int i = 0; i < RT_RING; ++i)
-        if (s->ring_used[i]) RT_HIP(hipEventSynchronize(s->ring[i]));
-    if (s->table_stream) RT_HIP(hipStreamSynchronize(s->table_stream));   // a table build still reading the list
+        if (s->ring_used[i]) RT_HIP(hipEventSynchronize(s->ring[i].get()));
+    if (s->table_stream.get()) RT_HIP(hipStreamSynchronize(s->table_stream.get()));   // a table build still reading the list
     return RT_OK;
 }
 
@@ -274,7 +261,7 @@ int rt_scene_quiesce(rt_scene *s)
 static int stream_wait_all_frames(rt_scene *s, hipStream_t stream)
 {
     for (int i = 0; i < RT_RING; ++i)
-        if (s->ring_used[i]) RT_HIP(hipStreamWaitEvent(stream, s->ring[i], 0));
+        if (s->ring_used[i]) RT_HIP(hipStreamWaitEvent(stream, s->ring[i].get(), 0));
     return RT_OK;
 }
 
@@ -283,10 +270,10 @@ static int stream_wait_all_frames(rt_scene *s, hipStream_t stream)
 int rt_scene_note_launch(rt_scene *s, hipStream_t stream, int cone_slot)
 {
     const int k = (int)(s->ring_seq % RT_RING);
-    if (!s->ring[k]) RT_HIP(hipEventCreateWithFlags(&s->ring[k], hipEventDisableTiming));
+    RT_HIP(s->ring[k].create());
     // chain: whoever sees this slot's new event done has also seen the one it replaces
-    if (s->ring_used[k]) RT_HIP(hipStreamWaitEvent(stream, s->ring[k], 0));
-    RT_HIP(hipEventRecord(s->ring[k], stream));
+    if (s->ring_used[k]) RT_HIP(hipStreamWaitEvent(stream, s->ring[k].get(), 0));
+    RT_HIP(hipEventRecord(s->ring[k].get(), stream));
     s->ring_used[k] = true;
     if (cone_slot >= 0) {
         s->cones[cone_slot].used = true;
@@ -299,36 +286,7 @@ int rt_scene_note_launch(rt_scene *s, hipStream_t stream, int cone_slot)
 extern "C" void rt_scene_destroy(rt_scene *s)
 {
     if (!s) return;
-    (void)rt_scene_quiesce(s);
-    if (s->d_spheres) (void)hipFree(s->d_spheres);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    if (s->stage_done) (void)hipEventDestroy(s->stage_done);
-    free_planes(s->d_tex);
-    free_planes(s->d_sky);
-    if (s->d_planes) (void)hipFree(s->d_planes);
-    if (s->d_cubes) (void)hipFree(s->d_cubes);
-    if (s->d_tris) (void)hipFree(s->d_tris);
-    if (s->d_boxes) (void)hipFree(s->d_boxes);
-    if (s->d_tri_idx) (void)hipFree(s->d_tri_idx);
-    if (s->d_box_spheres) (void)hipFree(s->d_box_spheres);
-    if (s->d_tri9) (void)hipFree(s->d_tri9);
-    if (s->d_tri_bs) (void)hipFree(s->d_tri_bs);
-    if (s->d_tri_nrm) (void)hipFree(s->d_tri_nrm);
-    if (s->d_light_tabs) (void)hipFree(s->d_light_tabs);
-    if (s->d_cand) (void)hipFree(s->d_cand);
-    for (TileOrder &o : s->orders)
-        if (o.cost) (void)hipFree(o.cost);
-    if (s->order_built) (void)hipEventDestroy(s->order_built);
-    for (ConeSlot &c : s->cones) {
-        if (c.buf) (void)hipFree(c.buf);
-        if (c.built) (void)hipEventDestroy(c.built);
-    }
-    if (s->table_stream) (void)hipStreamDestroy(s->table_stream);
-    if (s->d_raygen) (void)hipFree(s->d_raygen);
-    if (s->d_aux) (void)hipFree(s->d_aux);
-    rt_reflect_destroy(s->refl);
-    for (hipEvent_t e : s->ring)
-        if (e) (void)hipEventDestroy(e);
+    (void)rt_scene_quiesce(s);   // then nothing reads what the members release
     delete s;
 }
 
@@ -359,7 +317,7 @@ static int build_eye_cones_into(rt_scene *s, const float org[3], float4 *buf, hi
 {
     const int n = s->n_spheres;
     if (((n + 63) & ~63) <= RT_EYE_DEVICE_MAX) {
-        RT_HIP(rt_eye_cones_launch(s->d_spheres, n, org, buf, 1024, stream));
+        RT_HIP(rt_eye_cones_launch(s->d_spheres.get(), n, org, buf, 1024, stream));
         return RT_OK;
     }
     const int n_pad = (n + 63) & ~63, nb = n_pad / RT_BLOCK;
@@ -393,22 +351,16 @@ static int rt_scene_prepare_eye(rt_scene *s, const float org[3], hipStream_t str
     ConeSlot &c = s->cones[v];
     const size_t total = rt_eye_cones_size(s->n_spheres);
     const bool host_build = ((s->n_spheres + 63) & ~63) > RT_EYE_DEVICE_MAX;
-    if (total > c.cap || host_build) {
+    if (total > c.buf.capacity() || host_build) {
         const int rc = rt_scene_quiesce(s);   // nothing may still read the buffer that is freed / overwritten from the host
         if (rc != RT_OK) return rc;
     }
-    if (total > c.cap) {
-        if (c.buf) RT_HIP(hipFree(c.buf));
-        c.buf = nullptr;
-        c.cap = 0;
-        c.valid = false;
-        RT_HIP(hipMalloc((void **)&c.buf, sizeof(float4) * total));
-        c.cap = total;
-        s->epoch++;
-    }
     c.valid = false;
+    bool grew;
+    RT_HIP(c.buf.reserve(total, &grew));
+    if (grew) s->epoch++;
     if (host_build) {
-        const int rc = build_eye_cones_into(s, org, c.buf, stream);
+        const int rc = build_eye_cones_into(s, org, c.buf.get(), stream);
         if (rc != RT_OK) return rc;
         c.build_pending = false;
     } else {
@@ -416,22 +368,23 @@ static int rt_scene_prepare_eye(rt_scene *s, const float org[3], hipStream_t str
         // k's kernel instead of in front of frame k+1's (one small workgroup; a moving camera
         // then costs the frames nothing but an event wait). Ordered, on the device only, after
         // the last frame that read this slot and after a sphere-table upload still in flight.
-        if (!s->table_stream) {
+        if (!s->table_stream.get()) {
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            RT_HIP(hipStreamCreateWithPriority(&s->table_stream, hipStreamNonBlocking, hi));
+            RT_HIP(s->table_stream.create(hipStreamNonBlocking, hi));
         }
-        if (!c.built) RT_HIP(hipEventCreateWithFlags(&c.built, hipEventDisableTiming));
+        const hipStream_t ts = s->table_stream.get();
+        RT_HIP(c.built.create());
         if (c.used) {
-            if (s->ring_seq - c.last_use <= RT_RING) RT_HIP(hipStreamWaitEvent(s->table_stream, s->ring[c.last_use % RT_RING], 0));
+            if (s->ring_seq - c.last_use <= RT_RING) RT_HIP(hipStreamWaitEvent(ts, s->ring[c.last_use % RT_RING].get(), 0));
             else {
-                const int rc = stream_wait_all_frames(s, s->table_stream);
+                const int rc = stream_wait_all_frames(s, ts);
                 if (rc != RT_OK) return rc;
             }
         }
-        if (s->stage_busy) RT_HIP(hipStreamWaitEvent(s->table_stream, s->stage_done, 0));
-        RT_HIP(rt_eye_cones_launch(s->d_spheres, s->n_spheres, org, c.buf, 256, s->table_stream));
-        RT_HIP(hipEventRecord(c.built, s->table_stream));
+        if (s->stage_busy) RT_HIP(hipStreamWaitEvent(ts, s->stage_done.get(), 0));
+        RT_HIP(rt_eye_cones_launch(s->d_spheres.get(), s->n_spheres, org, c.buf.get(), 256, ts));
+        RT_HIP(hipEventRecord(c.built.get(), ts));
         c.build_pending = true;
     }
     memcpy(c.org, org, sizeof c.org);
@@ -478,13 +431,7 @@ static int rt_scene_prepare_lights(rt_scene *s, hipStream_t stream)
     int rc = rt_scene_quiesce(s);
     if (rc != RT_OK) return rc;
     const size_t total = per_light * (size_t)std::max(1, s->n_lights);
-    if (total > s->cap_light_tabs) {
-        if (s->d_light_tabs) RT_HIP(hipFree(s->d_light_tabs));
-        s->d_light_tabs = nullptr;
-        s->cap_light_tabs = 0;
-        RT_HIP(hipMalloc((void **)&s->d_light_tabs, sizeof(float4) * total));
-        s->cap_light_tabs = total;
-    }
+    RT_HIP(s->d_light_tabs.reserve(total));
     std::vector<float4> h(total);
     for (int i = 0; i < s->n_lights; ++i) {
         s->ltab_valid[i] = usable[i];
@@ -493,7 +440,7 @@ static int rt_scene_prepare_lights(rt_scene *s, hipStream_t stream)
             rt_build_light_columns(s->h_prev.data(), n, axis[i], h.data() + per_light * i, h.data() + per_light * i + n_pad);
     }
     for (int i = s->n_lights; i < RT_MAX_LIGHTS; ++i) s->ltab_valid[i] = false;
-    RT_HIP(hipMemcpyAsync(s->d_light_tabs, h.data(), sizeof(float4) * total, hipMemcpyHostToDevice, stream));
+    RT_HIP(hipMemcpyAsync(s->d_light_tabs.get(), h.data(), sizeof(float4) * total, hipMemcpyHostToDevice, stream));
     RT_HIP(hipStreamSynchronize(stream));   // rare (scene or light change): `h` goes out of scope
     s->ltab_gen = s->sphere_gen;
     s->ltab_n_lights = s->n_lights;
@@ -507,7 +454,7 @@ static int rt_scene_prepare_lights(rt_scene *s, hipStream_t stream)
 static int rt_scene_prepare_occluders(rt_scene *s, hipStream_t stream)
 {
     const int n = s->n_spheres;
-    bool want = n >= 64 && n <= kMaxSpheresOccluders && s->h_prev.size() == (size_t)n && s->d_spheres;
+    bool want = n >= 64 && n <= kMaxSpheresOccluders && s->h_prev.size() == (size_t)n && s->d_spheres.get();
 #ifdef RT_TUNING
     if (s->tune_no_light_columns) want = false;
 #endif
@@ -526,22 +473,17 @@ static int rt_scene_prepare_occluders(rt_scene *s, hipStream_t stream)
     if (rc != RT_OK) return rc;
     const size_t hdr_bytes = sizeof(RtCandHdr) * (size_t)n, ent_bytes = sizeof(float4) * (size_t)n * RT_CAND_CAP;
     const size_t bytes = (hdr_bytes + ent_bytes) * (size_t)s->n_lights;
-    if (bytes > s->cap_cand) {
-        if (s->d_cand) RT_HIP(hipFree(s->d_cand));
-        s->d_cand = nullptr;
-        s->cap_cand = 0;
-        RT_HIP(hipMalloc((void **)&s->d_cand, bytes));
-        s->cap_cand = bytes;
-        // a wave reads whole steps of 64 from a slot and masks what lies past the count: let that be zeros, once
-        RT_HIP(hipMemsetAsync(s->d_cand, 0, bytes, stream));
-    }
-    if (s->stage_busy) RT_HIP(hipStreamWaitEvent(stream, s->stage_done, 0));   // the table the build reads may still be on its way
+    bool grew;
+    RT_HIP(s->d_cand.reserve(bytes, &grew));
+    // a wave reads whole steps of 64 from a slot and masks what lies past the count: let that be zeros, once
+    if (grew) RT_HIP(hipMemsetAsync(s->d_cand.get(), 0, bytes, stream));
+    if (s->stage_busy) RT_HIP(hipStreamWaitEvent(stream, s->stage_done.get(), 0));   // the table the build reads may still be on its way
     for (int i = 0; i < s->n_lights; ++i) {
         const float p[3] = {s->lights[i].pos.x, s->lights[i].pos.y, s->lights[i].pos.z};
         memcpy(s->cand_pos[i], p, sizeof p);
         s->cand_ent_off[i] = hdr_bytes * (size_t)s->n_lights + ent_bytes * (size_t)i;
-        RT_HIP(rt_occluder_lists_launch(s->d_spheres, n, p, reinterpret_cast<RtCandHdr *>(s->d_cand + hdr_bytes * (size_t)i),
-                                        reinterpret_cast<float4 *>(s->d_cand + s->cand_ent_off[i]), stream));
+        RT_HIP(rt_occluder_lists_launch(s->d_spheres.get(), n, p, reinterpret_cast<RtCandHdr *>(s->d_cand.get() + hdr_bytes * (size_t)i),
+                                        reinterpret_cast<float4 *>(s->d_cand.get() + s->cand_ent_off[i]), stream));
         s->cand_valid[i] = true;
     }
     for (int i = s->n_lights; i < RT_MAX_LIGHTS; ++i) s->cand_valid[i] = false;
@@ -567,7 +509,7 @@ int rt_scene_set_spheres_async(rt_scene *s, const rt_sphere *host_spheres, int n
     std::vector<float4> packed((size_t)n);
     if (n > 0) {
         pack_spheres(host_spheres, n, packed.data());
-        if (s->n_spheres == n && s->h_prev.size() == (size_t)n && (int)total <= s->cap_spheres &&
+        if (s->n_spheres == n && s->h_prev.size() == (size_t)n && total <= s->d_spheres.capacity() &&
             memcmp(s->h_prev.data(), packed.data(), sizeof(float4) * (size_t)n) == 0)
             return RT_OK;   // unchanged since the last mirror: the device copy is current
     }
@@ -577,32 +519,21 @@ int rt_scene_set_spheres_async(rt_scene *s, const rt_sphere *host_spheres, int n
         const int rc = rt_scene_quiesce(s);
         if (rc != RT_OK) return rc;
     }
-    if ((int)total > s->cap_spheres) {
-        if (s->d_spheres) RT_HIP(hipFree(s->d_spheres));
-        s->d_spheres = nullptr;
-        s->cap_spheres = 0;
-        RT_HIP(hipMalloc((void **)&s->d_spheres, sizeof(float4) * total));
-        s->cap_spheres = (int)total;
-        s->h_prev.clear();
-    }
-    if ((int)total > s->cap_stage) {
-        if (s->stage_busy) RT_HIP(hipEventSynchronize(s->stage_done));
-        if (s->h_stage) RT_HIP(hipHostFree(s->h_stage));
-        s->h_stage = nullptr;
-        s->cap_stage = 0;
-        RT_HIP(hipHostMalloc((void **)&s->h_stage, sizeof(float4) * total, hipHostMallocDefault));
-        s->cap_stage = (int)total;
-    }
+    bool grew;
+    RT_HIP(s->d_spheres.reserve(total, &grew));
+    if (grew) s->h_prev.clear();
+    if (total > s->h_stage.capacity() && s->stage_busy) RT_HIP(hipEventSynchronize(s->stage_done.get()));   // before it is freed
+    RT_HIP(s->h_stage.reserve(total));
     if (n > 0) {
         // the staging buffer is reused: wait for the previous upload to have left it
-        if (!s->stage_done) RT_HIP(hipEventCreateWithFlags(&s->stage_done, hipEventDisableTiming));
-        if (s->stage_busy) RT_HIP(hipEventSynchronize(s->stage_done));
-        float4 *h_orig = s->h_stage, *h_sorted = h_orig + n, *h_blocks = h_sorted + n_pad;
+        RT_HIP(s->stage_done.create());
+        if (s->stage_busy) RT_HIP(hipEventSynchronize(s->stage_done.get()));
+        float4 *h_orig = s->h_stage.get(), *h_sorted = h_orig + n, *h_blocks = h_sorted + n_pad;
         int *h_idx = reinterpret_cast<int *>(h_blocks + nb);
         memcpy(h_orig, packed.data(), sizeof(float4) * (size_t)n);
         rt_build_sorted_blocks(packed.data(), n, h_sorted, h_blocks, h_idx);
-        RT_HIP(hipMemcpyAsync(s->d_spheres, s->h_stage, sizeof(float4) * total, hipMemcpyHostToDevice, stream));
-        RT_HIP(hipEventRecord(s->stage_done, stream));
+        RT_HIP(hipMemcpyAsync(s->d_spheres.get(), s->h_stage.get(), sizeof(float4) * total, hipMemcpyHostToDevice, stream));
+        RT_HIP(hipEventRecord(s->stage_done.get(), stream));
         s->stage_busy = true;
         s->h_prev.swap(packed);
     } else {
@@ -611,7 +542,7 @@ int rt_scene_set_spheres_async(rt_scene *s, const rt_sphere *host_spheres, int n
     s->sphere_gen++;
     s->epoch++;
     s->n_blocks = nb;
-    if (s->refl) rt_reflect_spheres_changed(s->refl, s->n_spheres, n);
+    if (s->refl) rt_reflect_spheres_changed(s->refl.get(), s->n_spheres, n);
     s->n_spheres = n;
     return RT_OK;
 }
@@ -635,12 +566,12 @@ extern "C" int rt_scene_set_planes(rt_scene *s, const rt_plane *host_planes, int
         return RT_ERR_CAPACITY;
     }
     { const int rc = rt_scene_quiesce(s); if (rc != RT_OK) return rc; }
-    if (!s->d_planes) RT_HIP(hipMalloc((void **)&s->d_planes, sizeof(RtPlaneDev) * RT_MAX_PLANES));
+    RT_HIP(s->d_planes.reserve(RT_MAX_PLANES));
     std::vector<RtPlaneDev> tmp(n ? n : 1);
     for (int i = 0; i < n; ++i)
         tmp[i] = RtPlaneDev{host_planes[i].orgin.x, host_planes[i].orgin.y, host_planes[i].orgin.z,
                             host_planes[i].normal.x, host_planes[i].normal.y, host_planes[i].normal.z, 0.f, 0.f};
-    if (n) RT_HIP(hipMemcpy(s->d_planes, tmp.data(), sizeof(RtPlaneDev) * n, hipMemcpyHostToDevice));
+    if (n) RT_HIP(hipMemcpy(s->d_planes.get(), tmp.data(), sizeof(RtPlaneDev) * n, hipMemcpyHostToDevice));
     s->n_planes = n;
     s->epoch++;
     return RT_OK;
@@ -657,14 +588,14 @@ extern "C" int rt_scene_set_cubes(rt_scene *s, const rt_cube *host_cubes, int n)
         return RT_ERR_CAPACITY;
     }
     { const int rc = rt_scene_quiesce(s); if (rc != RT_OK) return rc; }
-    if (!s->d_cubes) RT_HIP(hipMalloc((void **)&s->d_cubes, sizeof(RtCubeDev) * RT_MAX_CUBES));
+    RT_HIP(s->d_cubes.reserve(RT_MAX_CUBES));
     std::vector<RtCubeDev> tmp(n ? n : 1);
     for (int i = 0; i < n; ++i) {
         const rt_cube &c = host_cubes[i];
         tmp[i] = RtCubeDev{c.bounds[0].x, c.bounds[0].y, c.bounds[0].z, c.bounds[1].x, c.bounds[1].y, c.bounds[1].z,
                            c.orgin.x, c.orgin.y, c.orgin.z, 0.f, 0.f, 0.f};
     }
-    if (n) RT_HIP(hipMemcpy(s->d_cubes, tmp.data(), sizeof(RtCubeDev) * n, hipMemcpyHostToDevice));
+    if (n) RT_HIP(hipMemcpy(s->d_cubes.get(), tmp.data(), sizeof(RtCubeDev) * n, hipMemcpyHostToDevice));
     s->n_cubes = n;
     s->epoch++;
     return RT_OK;
@@ -680,17 +611,13 @@ extern "C" int rt_scene_set_mesh(rt_scene *s, const rt_mesh *mesh)
     }
     { const int rc = rt_scene_quiesce(s); if (rc != RT_OK) return rc; }
     s->epoch++;
-    if (s->d_tris) RT_HIP(hipFree(s->d_tris));
-    if (s->d_boxes) RT_HIP(hipFree(s->d_boxes));
-    if (s->d_tri_idx) RT_HIP(hipFree(s->d_tri_idx));
-    if (s->d_box_spheres) RT_HIP(hipFree(s->d_box_spheres));
-    if (s->d_tri9) RT_HIP(hipFree(s->d_tri9));
-    if (s->d_tri_bs) RT_HIP(hipFree(s->d_tri_bs));
-    if (s->d_tri_nrm) RT_HIP(hipFree(s->d_tri_nrm));
-    s->d_tri_nrm = nullptr;
-    s->d_tri9 = nullptr;
-    s->d_tri_bs = nullptr;
-    s->d_tris = nullptr; s->d_boxes = nullptr; s->d_tri_idx = nullptr; s->d_box_spheres = nullptr;
+    RT_HIP(s->d_tris.reset());
+    RT_HIP(s->d_boxes.reset());
+    RT_HIP(s->d_tri_idx.reset());
+    RT_HIP(s->d_box_spheres.reset());
+    RT_HIP(s->d_tri9.reset());
+    RT_HIP(s->d_tri_bs.reset());
+    RT_HIP(s->d_tri_nrm.reset());
     s->n_boxes = s->n_tris = 0;
     if (!mesh || mesh->bvhbox_count == 0) return RT_OK;
     if (mesh->poly_count <= 0 || mesh->bvhbox_count < 0 || !mesh->d_tri_arr || !mesh->d_box) {
@@ -739,9 +666,9 @@ extern "C" int rt_scene_set_mesh(rt_scene *s, const rt_mesh *mesh)
             idx.push_back(b.d_indexes[i]);
         }
     }
-    RT_HIP(hipMalloc((void **)&s->d_tris, sizeof(RtTriDev) * tris.size()));
-    RT_HIP(hipMalloc((void **)&s->d_boxes, sizeof(RtBoxDev) * boxes.size()));
-    RT_HIP(hipMalloc((void **)&s->d_tri_idx, sizeof(int) * (idx.size() ? idx.size() : 1)));
+    RT_HIP(s->d_tris.reserve(tris.size()));
+    RT_HIP(s->d_boxes.reserve(boxes.size()));
+    RT_HIP(s->d_tri_idx.reserve(idx.size() ? idx.size() : 1));
     {   // blocks of RT_BLOCK consecutive leaves (leaf order is kept: it decides ties between triangles),
         // each with a sphere around its members' spheres, appended after the (padded) leaf spheres
         const int nb = mesh->bvhbox_count, nb_pad = (nb + RT_BLOCK - 1) / RT_BLOCK * RT_BLOCK, nblk = nb_pad / RT_BLOCK;
@@ -767,11 +694,11 @@ extern "C" int rt_scene_set_mesh(rt_scene *s, const rt_mesh *mesh)
             o[3] = fin ? rf : INFINITY;
         }
     }
-    RT_HIP(hipMalloc((void **)&s->d_box_spheres, sizeof(float) * bsph.size()));
-    RT_HIP(hipMemcpy(s->d_box_spheres, bsph.data(), sizeof(float) * bsph.size(), hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(s->d_tris, tris.data(), sizeof(RtTriDev) * tris.size(), hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(s->d_boxes, boxes.data(), sizeof(RtBoxDev) * boxes.size(), hipMemcpyHostToDevice));
-    if (!idx.empty()) RT_HIP(hipMemcpy(s->d_tri_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice));
+    RT_HIP(s->d_box_spheres.reserve(bsph.size()));
+    RT_HIP(hipMemcpy(s->d_box_spheres.get(), bsph.data(), sizeof(float) * bsph.size(), hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(s->d_tris.get(), tris.data(), sizeof(RtTriDev) * tris.size(), hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(s->d_boxes.get(), boxes.data(), sizeof(RtBoxDev) * boxes.size(), hipMemcpyHostToDevice));
+    if (!idx.empty()) RT_HIP(hipMemcpy(s->d_tri_idx.get(), idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice));
     {   // vertices per (leaf, triangle) pair, de-indexed and padded by 64 floats so that a full-wave load stays inside
         std::vector<float> t9(idx.size() * 9 + 64, 0.f);
         for (size_t k = 0; k < idx.size(); ++k) {
@@ -779,8 +706,8 @@ extern "C" int rt_scene_set_mesh(rt_scene *s, const rt_mesh *mesh)
             memcpy(&t9[9 * k + 3], tris[idx[k]].p1, 12);
             memcpy(&t9[9 * k + 6], tris[idx[k]].p2, 12);
         }
-        RT_HIP(hipMalloc((void **)&s->d_tri9, sizeof(float) * t9.size()));
-        RT_HIP(hipMemcpy(s->d_tri9, t9.data(), sizeof(float) * t9.size(), hipMemcpyHostToDevice));
+        RT_HIP(s->d_tri9.reserve(t9.size()));
+        RT_HIP(hipMemcpy(s->d_tri9.get(), t9.data(), sizeof(float) * t9.size(), hipMemcpyHostToDevice));
         // bounding sphere of every (leaf, triangle) pair for the per-triangle beam cull (beam_keeps_triangle):
         // centre = centroid, radius = farthest vertex, rounded up; with it the unit normal and kappa, the least
         // |cos| between a ray and the normal for which the cull is valid (slivers and anything non-finite: radius
@@ -821,10 +748,10 @@ extern "C" int rt_scene_set_mesh(rt_scene *s, const rt_mesh *mesh)
                 bn[4 * k + 3] = 2.f;
             }
         }
-        RT_HIP(hipMalloc((void **)&s->d_tri_bs, sizeof(float) * bs.size()));
-        RT_HIP(hipMemcpy(s->d_tri_bs, bs.data(), sizeof(float) * bs.size(), hipMemcpyHostToDevice));
-        RT_HIP(hipMalloc((void **)&s->d_tri_nrm, sizeof(float) * bn.size()));
-        RT_HIP(hipMemcpy(s->d_tri_nrm, bn.data(), sizeof(float) * bn.size(), hipMemcpyHostToDevice));
+        RT_HIP(s->d_tri_bs.reserve(bs.size()));
+        RT_HIP(hipMemcpy(s->d_tri_bs.get(), bs.data(), sizeof(float) * bs.size(), hipMemcpyHostToDevice));
+        RT_HIP(s->d_tri_nrm.reserve(bn.size()));
+        RT_HIP(hipMemcpy(s->d_tri_nrm.get(), bn.data(), sizeof(float) * bn.size(), hipMemcpyHostToDevice));
     }
     s->n_boxes = mesh->bvhbox_count;
     s->n_tris = mesh->poly_count;
@@ -832,14 +759,14 @@ extern "C" int rt_scene_set_mesh(rt_scene *s, const rt_mesh *mesh)
     return RT_OK;
 }
 
-static int upload_planes(float *dst[3], const float *r, const float *g, const float *b, int w, int h)
+static int upload_planes(DevArray<float> dst[3], const float *r, const float *g, const float *b, int w, int h)
 {
     const float *src[3] = {r, g, b};
-    const size_t bytes = sizeof(float) * (size_t)w * (size_t)h;
-    free_planes(dst);
+    const size_t count = (size_t)w * (size_t)h;
+    for (int i = 0; i < 3; ++i) (void)dst[i].reset();
     for (int i = 0; i < 3; ++i) {
-        RT_HIP(hipMalloc((void **)&dst[i], bytes));
-        RT_HIP(hipMemcpy(dst[i], src[i], bytes, hipMemcpyDefault));
+        RT_HIP(dst[i].reserve(count));
+        RT_HIP(hipMemcpy(dst[i].get(), src[i], sizeof(float) * count, hipMemcpyDefault));
     }
     return RT_OK;
 }
@@ -936,19 +863,13 @@ void rt_ray_origin(const rt_frame_desc *fd, float org[3])
 // rebuilds them (host, W + H divisions per sample) after waiting for the frames in flight.
 static int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float aspect, int total)
 {
-    if (s->d_raygen && s->rg_w == width && s->rg_h == height && s->rg_total == total &&
+    if (s->d_raygen.get() && s->rg_w == width && s->rg_h == height && s->rg_total == total &&
         memcmp(&s->rg_aspect, &aspect, sizeof aspect) == 0)
         return RT_OK;
     const int rc = rt_scene_quiesce(s);
     if (rc != RT_OK) return rc;
     const size_t need = (size_t)total * ((size_t)width + (size_t)height);
-    if (need > s->cap_raygen) {
-        if (s->d_raygen) RT_HIP(hipFree(s->d_raygen));
-        s->d_raygen = nullptr;
-        s->cap_raygen = 0;
-        RT_HIP(hipMalloc((void **)&s->d_raygen, sizeof(float) * need));
-        s->cap_raygen = need;
-    }
+    RT_HIP(s->d_raygen.reserve(need));
     std::vector<float> h(need);
     const double aspect_d = (double)aspect;
     const double width_d = (double)(float)width, height_d = (double)(float)height;
@@ -966,7 +887,7 @@ static int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float asp
             dy[y] = (float)((aspect_d * ty_d) * hw_d - 1.0);
         }
     }
-    RT_HIP(hipMemcpy(s->d_raygen, h.data(), sizeof(float) * need, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(s->d_raygen.get(), h.data(), sizeof(float) * need, hipMemcpyHostToDevice));
     s->rg_w = width;
     s->rg_h = height;
     s->rg_total = total;
@@ -1026,31 +947,31 @@ static void rt_build_frame_aux(const rt_scene *s, RtFrameAux *ax)
     {
         const int n_pad = (s->n_spheres + 63) & ~63;
         const size_t per_light = (size_t)n_pad + 2 * (size_t)s->n_blocks;
-        const bool current = s->d_light_tabs && s->ltab_gen == s->sphere_gen && s->ltab_n_lights == s->n_lights;
+        const bool current = s->d_light_tabs.get() && s->ltab_gen == s->sphere_gen && s->ltab_n_lights == s->n_lights;
         for (int i = 0; i < RT_DEV_MAX_LIGHTS; ++i) {
             const bool on = current && i < s->n_lights && s->ltab_valid[i];
-            ax->lsorted[i] = on ? reinterpret_cast<const float *>(s->d_light_tabs + per_light * i) : nullptr;
-            ax->lblocks[i] = on ? reinterpret_cast<const float *>(s->d_light_tabs + per_light * i + n_pad) : nullptr;
-            const bool con = s->d_cand && s->cand_gen == s->sphere_gen && s->cand_n_lights == s->n_lights && i < s->n_lights && s->cand_valid[i];
-            ax->cand_hdr[i] = con ? reinterpret_cast<const RtCandHdr *>(s->d_cand + sizeof(RtCandHdr) * (size_t)s->n_spheres * (size_t)i) : nullptr;
-            ax->cand_ent[i] = con ? reinterpret_cast<const float *>(s->d_cand + s->cand_ent_off[i]) : nullptr;
+            ax->lsorted[i] = on ? reinterpret_cast<const float *>(s->d_light_tabs.get() + per_light * i) : nullptr;
+            ax->lblocks[i] = on ? reinterpret_cast<const float *>(s->d_light_tabs.get() + per_light * i + n_pad) : nullptr;
+            const bool con = s->d_cand.get() && s->cand_gen == s->sphere_gen && s->cand_n_lights == s->n_lights && i < s->n_lights && s->cand_valid[i];
+            ax->cand_hdr[i] = con ? reinterpret_cast<const RtCandHdr *>(s->d_cand.get() + sizeof(RtCandHdr) * (size_t)s->n_spheres * (size_t)i) : nullptr;
+            ax->cand_ent[i] = con ? reinterpret_cast<const float *>(s->d_cand.get() + s->cand_ent_off[i]) : nullptr;
         }
     }
-    ax->sky_r = s->d_sky[0]; ax->sky_g = s->d_sky[1]; ax->sky_b = s->d_sky[2];
+    ax->sky_r = s->d_sky[0].get(); ax->sky_g = s->d_sky[1].get(); ax->sky_b = s->d_sky[2].get();
     ax->sky_w = s->sky_w; ax->sky_h = s->sky_h;
     ax->sky_cx = s->sky_c[0]; ax->sky_cy = s->sky_c[1]; ax->sky_cz = s->sky_c[2];
     ax->sky_r2 = s->sky_radius * s->sky_radius;
     ax->sky_mu_x = texel_margin(s->sky_w, 1.0e-6f);
     ax->sky_mu_y = texel_margin(s->sky_h, 1.0e-6f);
-    ax->planes = s->d_planes;
-    ax->cubes = s->d_cubes;
-    ax->tris = s->d_tris;
-    ax->boxes = s->d_boxes;
-    ax->tri_idx = s->d_tri_idx;
-    ax->box_spheres = s->d_box_spheres;
-    ax->tri9 = s->d_tri9;
-    ax->tri_bs = s->d_tri_bs;
-    ax->tri_nrm = s->d_tri_nrm;
+    ax->planes = s->d_planes.get();
+    ax->cubes = s->d_cubes.get();
+    ax->tris = s->d_tris.get();
+    ax->boxes = s->d_boxes.get();
+    ax->tri_idx = s->d_tri_idx.get();
+    ax->box_spheres = s->d_box_spheres.get();
+    ax->tri9 = s->d_tri9.get();
+    ax->tri_bs = s->d_tri_bs.get();
+    ax->tri_nrm = s->d_tri_nrm.get();
 }
 
 // Bring the device copy of RtFrameAux up to date (a camera move never changes it).
@@ -1061,8 +982,8 @@ static int rt_scene_sync_aux(rt_scene *s)
     if (s->aux_valid && memcmp(&ax, &s->h_aux, sizeof ax) == 0) return RT_OK;
     const int rc = rt_scene_quiesce(s);
     if (rc != RT_OK) return rc;
-    if (!s->d_aux) RT_HIP(hipMalloc((void **)&s->d_aux, sizeof(RtFrameAux)));
-    RT_HIP(hipMemcpy(s->d_aux, &ax, sizeof ax, hipMemcpyHostToDevice));
+    RT_HIP(s->d_aux.reserve(1));
+    RT_HIP(hipMemcpy(s->d_aux.get(), &ax, sizeof ax, hipMemcpyHostToDevice));
     s->h_aux = ax;
     s->aux_valid = true;
     s->epoch++;
@@ -1095,7 +1016,7 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
                      total, RT_MAX_SPP);
         return RT_ERR_INVALID;
     }
-    if ((s->n_spheres > 0 || s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0) && (!s->d_tex[0] || s->tex_w <= 0)) {
+    if ((s->n_spheres > 0 || s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0) && (!s->d_tex[0].get() || s->tex_w <= 0)) {
         rt_set_error("rt_scene_render: scene has primitives but no object texture");
         return RT_ERR_INVALID;
     }
@@ -1157,10 +1078,10 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
 #endif
 
     // kernel.cu:1624-1625 through the raygen tables; :1629-1631: eyePos = (0,0,-1/aspect); dir - eyePos; eyePos + cam.Org
-    const bool rg = s->d_raygen && s->rg_w == fd->width && s->rg_h == fd->height && s->rg_total == total &&
+    const bool rg = s->d_raygen.get() && s->rg_w == fd->width && s->rg_h == fd->height && s->rg_total == total &&
                     memcmp(&s->rg_aspect, &fd->aspect, sizeof(float)) == 0;
-    fc->dx_tab = rg ? s->d_raygen : nullptr;
-    fc->dy_tab = rg ? s->d_raygen + (size_t)total * fd->width : nullptr;
+    fc->dx_tab = rg ? s->d_raygen.get() : nullptr;
+    fc->dy_tab = rg ? s->d_raygen.get() + (size_t)total * fd->width : nullptr;
     const float ez = -1.f / fd->aspect;
     fc->eye_nz = 0.f - ez;
     float org[3];
@@ -1176,13 +1097,13 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
     fc->cos_yaw = rtm::cosf_rt(yawRad);
     fc->sin_yaw = rtm::sinf_rt(yawRad);
 
-    fc->tex_r = s->d_tex[0]; fc->tex_g = s->d_tex[1]; fc->tex_b = s->d_tex[2];
+    fc->tex_r = s->d_tex[0].get(); fc->tex_g = s->d_tex[1].get(); fc->tex_b = s->d_tex[2].get();
     fc->tex_w = s->tex_w; fc->tex_h = s->tex_h;
     fc->tex_mu_x = texel_margin(s->tex_w, 5.0e-7f);   // RT_UV_DELTA of rt_kernels.hip
     fc->tex_mu_y = texel_margin(s->tex_h, 5.0e-7f);
     {
         const int n_pad = (s->n_spheres + 63) & ~63;
-        const float4 *base = s->d_spheres;
+        const float4 *base = s->d_spheres.get();
         fc->sorted = base ? reinterpret_cast<const float *>(base + s->n_spheres) : nullptr;
         fc->blocks = base ? reinterpret_cast<const float *>(base + s->n_spheres + n_pad) : nullptr;
         fc->orig_idx = base ? reinterpret_cast<const int *>(base + s->n_spheres + n_pad + s->n_blocks) : nullptr;
@@ -1192,7 +1113,7 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
         fc->corig = cones ? reinterpret_cast<const int *>(cones + n_pad + 2 * (size_t)s->n_blocks) : nullptr;
         fc->cone_kcap = (float)RT_CONE_KCAP;
     }
-    fc->aux = s->d_aux;
+    fc->aux = s->d_aux.get();
     fc->rgba = o.rgba;
     fc->packed = fd->pixels;
     fc->packed24 = (uint32_t *)o.packed24;
@@ -1281,55 +1202,41 @@ int rt_scene_prepare_static(rt_scene *s, const rt_frame_desc *fd, hipStream_t st
 // afterwards on other streams wait for the sort's event.
 static int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, hipStream_t stream)
 {
-    const int tile_w = kc.tile, th = 64 / tile_w;
-    const int tiles_x = (fc->width + tile_w - 1) / tile_w, tiles_y = (fc->local_rows + th - 1) / th;
-    const int nbx = (tiles_x + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK, nby = (tiles_y + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK;
-    if (tiles_x > 0xffff || tiles_y > 0xffff || (long long)nbx * nby > RT_TILE_ORDER_MAX_BLOCKS) return RT_OK;   // grid order
-    const int n = tiles_x * tiles_y, nb = nbx * nby;
-    const int key[12] = {tile_w, fc->width, fc->height, fc->y0, fc->y1, fc->local_rows, fc->il_count, fc->il_index, fc->il_rows,
+    const RtTileGrid grid = rt_tile_grid(kc.tile, fc->width, fc->local_rows);
+    if (!grid.ok) return RT_OK;   // grid order
+    const int key[12] = {kc.tile, fc->width, fc->height, fc->y0, fc->y1, fc->local_rows, fc->il_count, fc->il_index, fc->il_rows,
                          kc.cull, kc.mode, fc->spp};
     // what the durations depend on from frame to frame: the view and the sphere list
     const float view[8] = {fc->org_x, fc->org_y, fc->org_z, fc->cos_pitch, fc->sin_pitch, fc->cos_yaw, fc->sin_yaw,
                            (float)(s->sphere_gen & 0xffffff)};
     TileOrder *t = nullptr, *lru = &s->orders[0];
     for (TileOrder &o : s->orders) {
-        if (o.cap && memcmp(o.key, key, sizeof key) == 0) t = &o;
+        if (o.buf.cap && memcmp(o.key, key, sizeof key) == 0) t = &o;
         if (o.last_use < lru->last_use) lru = &o;
     }
     if (s->order_pending) {   // an order being sorted (any layout: one event) precedes this launch
-        if (hipEventQuery(s->order_built) == hipSuccess) s->order_pending = false;
-        else RT_HIP(hipStreamWaitEvent(stream, s->order_built, 0));
+        if (hipEventQuery(s->order_built.get()) == hipSuccess) s->order_pending = false;
+        else RT_HIP(hipStreamWaitEvent(stream, s->order_built.get(), 0));
         (void)hipGetLastError();
     }
     if (!t) {                 // a new layout takes the least recently used slot
         t = lru;
         int rc = stream_wait_all_frames(s, stream);   // frames that still write into the slot's old arrays
         if (rc != RT_OK) return rc;
-        if ((size_t)n > t->cap || (size_t)nb > t->nb_cap) {
+        if (!t->buf.fits(grid)) {
             rc = rt_scene_quiesce(s);                  // re-allocation: nothing may still use the old arrays
             if (rc != RT_OK) return rc;
-            if (t->cost) RT_HIP(hipFree(t->cost));
-            t->cost = t->perm = t->bkey = t->start = nullptr;
-            t->cap = t->nb_cap = 0;
-            RT_HIP(hipMalloc((void **)&t->cost, sizeof(unsigned) * (2 * (size_t)n + 2 * (size_t)nb)));
-            t->cap = (size_t)n;
-            t->nb_cap = (size_t)nb;
         }
-        t->perm = t->cost + t->cap;
-        t->bkey = t->perm + t->cap;
-        t->start = t->bkey + t->nb_cap;
-        RT_HIP(hipMemsetAsync(t->cost, 0, sizeof(unsigned) * t->cap, stream));
+        RT_HIP(t->buf.reserve(grid));
+        RT_HIP(hipMemsetAsync(t->buf.cost(), 0, sizeof(unsigned) * t->buf.cap, stream));
         memcpy(t->key, key, sizeof key);
         memcpy(t->view, view, sizeof view);
-        t->n = n;
-        t->nb = nb;
-        t->tiles_x = tiles_x;
-        t->tiles_y = tiles_y;
+        t->grid = grid;
         t->same_view = 0;
         t->since_sort = 0;
         t->have_perm = false;
-        if (!s->order_built) RT_HIP(hipEventCreateWithFlags(&s->order_built, hipEventDisableTiming));
-        RT_HIP(hipEventRecord(s->order_built, stream));   // launches on other streams: after the reset
+        RT_HIP(s->order_built.create());
+        RT_HIP(hipEventRecord(s->order_built.get(), stream));   // launches on other streams: after the reset
         s->order_pending = true;
     } else {
         if (memcmp(t->view, view, sizeof view) != 0) {
@@ -1343,9 +1250,10 @@ static int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, Rt
         if (due && t->since_sort >= 1) {
             int rc = stream_wait_all_frames(s, stream);
             if (rc != RT_OK) return rc;
-            RT_HIP(rt_tile_order_launch(t->cost, t->bkey, t->start, t->perm, t->tiles_x, t->tiles_y, stream));
-            if (!s->order_built) RT_HIP(hipEventCreateWithFlags(&s->order_built, hipEventDisableTiming));
-            RT_HIP(hipEventRecord(s->order_built, stream));
+            RT_HIP(rt_tile_order_launch(t->buf.cost(), t->buf.key(), t->buf.start(), t->buf.perm(), t->grid.tiles_x, t->grid.tiles_y,
+                                        stream));
+            RT_HIP(s->order_built.create());
+            RT_HIP(hipEventRecord(s->order_built.get(), stream));
             s->order_pending = true;
             t->have_perm = true;
             t->since_sort = 0;
@@ -1354,8 +1262,8 @@ static int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, Rt
     t->since_sort++;
     t->same_view++;
     t->last_use = ++s->order_clock;
-    fc->tile_cost = t->cost;
-    fc->tile_perm = t->have_perm ? t->perm : nullptr;
+    fc->tile_cost = t->buf.cost();
+    fc->tile_perm = t->have_perm ? t->buf.perm() : nullptr;
     return RT_OK;
 }
 
@@ -1410,16 +1318,21 @@ static int reflect_supported(const rt_scene *s, const rt_frame_desc *fd)
     return RT_OK;
 }
 
+static RtReflect *scene_reflect(rt_scene *s)   // created on first use
+{
+    if (!s->refl) s->refl.reset(rt_reflect_create());
+    return s->refl.get();
+}
+
 extern "C" int rt_scene_set_materials(rt_scene *s, const rt_material *per_sphere, int n)
 {
     if (!s) {
         rt_set_error("rt_scene_set_materials: null scene");
         return RT_ERR_INVALID;
     }
-    if (!s->refl) s->refl = rt_reflect_create();
     // frames in flight may read the device copy: rt_reflect_prepare re-uploads it before the next reflective frame,
     // after those frames (rt_scene_render waits for them when anything changed)
-    return rt_reflect_set_materials(s->refl, per_sphere, n, s->n_spheres);
+    return rt_reflect_set_materials(scene_reflect(s), per_sphere, n, s->n_spheres);
 }
 
 extern "C" int rt_scene_set_reflect_timing(rt_scene *s, int on)
@@ -1428,8 +1341,7 @@ extern "C" int rt_scene_set_reflect_timing(rt_scene *s, int on)
         rt_set_error("rt_scene_set_reflect_timing: null scene");
         return RT_ERR_INVALID;
     }
-    if (!s->refl) s->refl = rt_reflect_create();
-    return rt_reflect_set_timing(s->refl, on);
+    return rt_reflect_set_timing(scene_reflect(s), on);
 }
 
 extern "C" int rt_scene_reflect_stats(rt_scene *s, rt_reflect_stats *out)
@@ -1438,8 +1350,7 @@ extern "C" int rt_scene_reflect_stats(rt_scene *s, rt_reflect_stats *out)
         rt_set_error("rt_scene_reflect_stats: null argument");
         return RT_ERR_INVALID;
     }
-    if (!s->refl) s->refl = rt_reflect_create();
-    return rt_reflect_get_stats(s->refl, out);
+    return rt_reflect_get_stats(scene_reflect(s), out);
 }
 
 extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *stream_)
@@ -1466,8 +1377,8 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         }
     }
     if (s->stage_busy) {   // a sphere-table upload enqueued on some stream: order this frame after it
-        if (hipEventQuery(s->stage_done) == hipSuccess) s->stage_busy = false;
-        else RT_HIP(hipStreamWaitEvent(stream, s->stage_done, 0));
+        if (hipEventQuery(s->stage_done.get()) == hipSuccess) s->stage_busy = false;
+        else RT_HIP(hipStreamWaitEvent(stream, s->stage_done.get(), 0));
         (void)hipGetLastError();   // hipEventQuery reports "not ready" as an error
     }
     int rc = rt_scene_prepare_static(s, fd, stream);
@@ -1481,12 +1392,12 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     }
     if (slot >= 0 && s->cones[slot].build_pending) {   // the table's build (table stream) precedes its readers
         ConeSlot &c = s->cones[slot];
-        if (hipEventQuery(c.built) == hipSuccess) c.build_pending = false;
-        else RT_HIP(hipStreamWaitEvent(stream, c.built, 0));
+        if (hipEventQuery(c.built.get()) == hipSuccess) c.build_pending = false;
+        else RT_HIP(hipStreamWaitEvent(stream, c.built.get(), 0));
         (void)hipGetLastError();
     }
     RtFrameConsts fc;
-    rc = rt_build_frame_consts(s, fd, slot >= 0 ? s->cones[slot].buf : nullptr, &fc);
+    rc = rt_build_frame_consts(s, fd, slot >= 0 ? s->cones[slot].buf.get() : nullptr, &fc);
     if (rc != RT_OK) return rc;
     RtKernelChoice kc;
     rc = rt_frame_kernel_choice(s, fd, &kc);
@@ -1495,19 +1406,19 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     if (reflect_depth > 0) {
         // the queues, the BVH and the materials are the scene's: after every frame launched so far (a host wait only
         // when the BVH or the materials change)
-        if (!s->refl) s->refl = rt_reflect_create();
-        if (rt_reflect_needs_upload(s->refl, s->sphere_gen, s->n_spheres)) {
+        RtReflect *refl = scene_reflect(s);
+        if (rt_reflect_needs_upload(refl, s->sphere_gen, s->n_spheres)) {
             rc = rt_scene_quiesce(s);
             if (rc != RT_OK) return rc;
         }
         rc = stream_wait_all_frames(s, stream);
         if (rc != RT_OK) return rc;
         float *scratch = nullptr;
-        rc = rt_reflect_prepare(s->refl, s->h_prev.data(), s->n_spheres, s->sphere_gen, fc.width * fc.local_rows,
+        rc = rt_reflect_prepare(refl, s->h_prev.data(), s->n_spheres, s->sphere_gen, fc.width * fc.local_rows,
                                 fc.rgba == nullptr, &scratch, stream);
         if (rc != RT_OK) return rc;
         if (!fc.rgba) fc.rgba = scratch;
-        rc = rt_reflect_begin_frame(s->refl, reflect_depth, stream);
+        rc = rt_reflect_begin_frame(refl, reflect_depth, stream);
         if (rc != RT_OK) return rc;
     }
     if (s->tile_order_mode != 0 && !kc.table_lds) {
@@ -1515,12 +1426,12 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         if (rc != RT_OK) return rc;
     }
     if (reflect_depth > 0) {
-        rc = rt_reflect_mark_frame_start(s->refl, stream);
+        rc = rt_reflect_mark_frame_start(s->refl.get(), stream);
         if (rc != RT_OK) return rc;
     }
-    RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres, kc.tile, kc.cull, kc.mode, kc.table_lds, kc.feat, stream));
+    RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres.get(), kc.tile, kc.cull, kc.mode, kc.table_lds, kc.feat, stream));
     if (reflect_depth > 0) {
-        rc = rt_reflect_launch(s->refl, &fc, s->d_spheres, s->n_spheres, reflect_depth, kc.cull == 0, stream);
+        rc = rt_reflect_launch(s->refl.get(), &fc, s->d_spheres.get(), s->n_spheres, reflect_depth, kc.cull == 0, stream);
         if (rc != RT_OK) return rc;
     }
     return rt_scene_note_launch(s, stream, slot);
@@ -1539,7 +1450,7 @@ extern "C" int rt_scene_set_tile_order(rt_scene *s, int mode)
 }
 
 // For rt_graph.cpp: the scene's buffers a graph node needs.
-const float4 *rt_scene_sphere_table(const rt_scene *s) { return s->d_spheres; }
+const float4 *rt_scene_sphere_table(const rt_scene *s) { return s->d_spheres.get(); }
 int rt_scene_sphere_count(const rt_scene *s) { return s->n_spheres; }
 unsigned long long rt_scene_epoch(const rt_scene *s) { return s->epoch; }
 bool rt_scene_wants_eye_cones(const rt_scene *s, const float org[3]) { return eye_cones_wanted(s, org); }
@@ -1710,35 +1621,28 @@ extern "C" int rt_launch_raytrace(uint32_t *pixels, int width, int height, float
 // ---------------------------------------------------------------------------
 // diagnostics: device evaluation of scalar building blocks (host arrays in/out)
 // ---------------------------------------------------------------------------
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { RT_HIP(hipMalloc((void **)&p, sizeof(T) * (n ? n : 1))); return RT_OK; }
-};
-
 extern "C" int rt_debug_math(int op, const float *a, const float *b, float *out, int n)
 {
     if (n <= 0 || !a || !out || op < 0 || op > 5 || (op == 3 && !b)) return RT_ERR_INVALID;
-    DevBuf<float> da, db, dout;
-    int rc;
-    if ((rc = da.alloc(n)) || (rc = db.alloc(n)) || (rc = dout.alloc(n))) return rc;
-    RT_HIP(hipMemcpy(da.p, a, sizeof(float) * n, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(db.p, b ? b : a, sizeof(float) * n, hipMemcpyHostToDevice));
-    RT_HIP(rt_dev_launch_dbg_math(op, da.p, db.p, dout.p, n, nullptr));
-    RT_HIP(hipMemcpy(out, dout.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+    DevArray<float> da, db, dout;
+    RT_HIP(da.reserve(n));
+    RT_HIP(db.reserve(n));
+    RT_HIP(dout.reserve(n));
+    RT_HIP(hipMemcpy(da.get(), a, sizeof(float) * n, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(db.get(), b ? b : a, sizeof(float) * n, hipMemcpyHostToDevice));
+    RT_HIP(rt_dev_launch_dbg_math(op, da.get(), db.get(), dout.get(), n, nullptr));
+    RT_HIP(hipMemcpy(out, dout.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
 extern "C" int rt_debug_shortcuts(int what, unsigned seed, long long n, unsigned long long out[4])
 {
     if (what < 0 || what > 2 || !out || n < 0) return RT_ERR_INVALID;
-    DevBuf<unsigned long long> d;
-    int rc = d.alloc(4);
-    if (rc != RT_OK) return rc;
-    RT_HIP(hipMemset(d.p, 0, sizeof(unsigned long long) * 4));
-    RT_HIP(rt_dev_launch_dbg_shortcuts(what, seed, n, d.p, nullptr));
-    RT_HIP(hipMemcpy(out, d.p, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost));
+    DevArray<unsigned long long> d;
+    RT_HIP(d.reserve(4));
+    RT_HIP(hipMemset(d.get(), 0, sizeof(unsigned long long) * 4));
+    RT_HIP(rt_dev_launch_dbg_shortcuts(what, seed, n, d.get(), nullptr));
+    RT_HIP(hipMemcpy(out, d.get(), sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1785,14 +1689,15 @@ extern "C" int rt_debug_sphere_beam_slopes(const rt_sphere *spheres, int n, cons
         for (int i = 0; i < n; ++i) host_kbeam[i] = hdr[(size_t)i].kbeam;
     }
     if (device_kbeam) {
-        DevBuf<float4> dtab, dent;
-        DevBuf<RtCandHdr> dhdr;
-        int rc;
-        if ((rc = dtab.alloc((size_t)n)) || (rc = dent.alloc((size_t)n * RT_CAND_CAP)) || (rc = dhdr.alloc((size_t)n))) return rc;
-        RT_HIP(hipMemcpy(dtab.p, tab.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
-        RT_HIP(rt_occluder_lists_launch(dtab.p, n, p, dhdr.p, dent.p, nullptr));
+        DevArray<float4> dtab, dent;
+        DevArray<RtCandHdr> dhdr;
+        RT_HIP(dtab.reserve((size_t)n));
+        RT_HIP(dent.reserve((size_t)n * RT_CAND_CAP));
+        RT_HIP(dhdr.reserve((size_t)n));
+        RT_HIP(hipMemcpy(dtab.get(), tab.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+        RT_HIP(rt_occluder_lists_launch(dtab.get(), n, p, dhdr.get(), dent.get(), nullptr));
         std::vector<RtCandHdr> hdr((size_t)n);
-        RT_HIP(hipMemcpy(hdr.data(), dhdr.p, sizeof(RtCandHdr) * (size_t)n, hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(hdr.data(), dhdr.get(), sizeof(RtCandHdr) * (size_t)n, hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i) device_kbeam[i] = hdr[(size_t)i].kbeam;
     }
     return RT_OK;
@@ -1813,18 +1718,19 @@ extern "C" int rt_debug_occluder_lists_device(const rt_sphere *spheres, int n, c
     if (n <= 0 || !spheres || !light || !counts || !kcaps || (cap > 0 && !members)) return RT_ERR_INVALID;
     std::vector<float4> tab((size_t)n);
     pack_spheres(spheres, n, tab.data());
-    DevBuf<float4> dtab, dent;
-    DevBuf<RtCandHdr> dhdr;
-    int rc;
-    if ((rc = dtab.alloc((size_t)n)) || (rc = dent.alloc((size_t)n * RT_CAND_CAP)) || (rc = dhdr.alloc((size_t)n))) return rc;
-    RT_HIP(hipMemcpy(dtab.p, tab.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
-    RT_HIP(hipMemset(dent.p, 0, sizeof(float4) * (size_t)n * RT_CAND_CAP));
+    DevArray<float4> dtab, dent;
+    DevArray<RtCandHdr> dhdr;
+    RT_HIP(dtab.reserve((size_t)n));
+    RT_HIP(dent.reserve((size_t)n * RT_CAND_CAP));
+    RT_HIP(dhdr.reserve((size_t)n));
+    RT_HIP(hipMemcpy(dtab.get(), tab.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+    RT_HIP(hipMemset(dent.get(), 0, sizeof(float4) * (size_t)n * RT_CAND_CAP));
     const float p[3] = {light->pos.x, light->pos.y, light->pos.z};
-    RT_HIP(rt_occluder_lists_launch(dtab.p, n, p, dhdr.p, dent.p, nullptr));
+    RT_HIP(rt_occluder_lists_launch(dtab.get(), n, p, dhdr.get(), dent.get(), nullptr));
     std::vector<RtCandHdr> hdr((size_t)n);
     std::vector<float4> ent((size_t)n * RT_CAND_CAP);
-    RT_HIP(hipMemcpy(hdr.data(), dhdr.p, sizeof(RtCandHdr) * (size_t)n, hipMemcpyDeviceToHost));
-    RT_HIP(hipMemcpy(ent.data(), dent.p, sizeof(float4) * ent.size(), hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(hdr.data(), dhdr.get(), sizeof(RtCandHdr) * (size_t)n, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(ent.data(), dent.get(), sizeof(float4) * ent.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) {
         counts[i] = hdr[(size_t)i].count;
         kcaps[i] = hdr[(size_t)i].kcap;
@@ -1848,17 +1754,18 @@ extern "C" int rt_debug_intersect(const rt_sphere *spheres, const rt_ray *rays, 
     if (n <= 0 || !spheres || !rays || !hit || !t) return RT_ERR_INVALID;
     std::vector<float4> tab(n);
     pack_spheres(spheres, n, tab.data());
-    DevBuf<float4> dtab;
-    DevBuf<float> drays, dt;
-    DevBuf<int> dhit;
-    int rc;
-    if ((rc = dtab.alloc(n)) || (rc = drays.alloc(6 * (size_t)n)) || (rc = dt.alloc(n)) || (rc = dhit.alloc(n)))
-        return rc;
-    RT_HIP(hipMemcpy(dtab.p, tab.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(drays.p, rays, sizeof(float) * 6 * n, hipMemcpyHostToDevice));
-    RT_HIP(rt_dev_launch_dbg_intersect(dtab.p, drays.p, n, dhit.p, dt.p, nullptr));
-    RT_HIP(hipMemcpy(hit, dhit.p, sizeof(int) * n, hipMemcpyDeviceToHost));
-    RT_HIP(hipMemcpy(t, dt.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+    DevArray<float4> dtab;
+    DevArray<float> drays, dt;
+    DevArray<int> dhit;
+    RT_HIP(dtab.reserve(n));
+    RT_HIP(drays.reserve(6 * (size_t)n));
+    RT_HIP(dt.reserve(n));
+    RT_HIP(dhit.reserve(n));
+    RT_HIP(hipMemcpy(dtab.get(), tab.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(drays.get(), rays, sizeof(float) * 6 * n, hipMemcpyHostToDevice));
+    RT_HIP(rt_dev_launch_dbg_intersect(dtab.get(), drays.get(), n, dhit.get(), dt.get(), nullptr));
+    RT_HIP(hipMemcpy(hit, dhit.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(t, dt.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1872,35 +1779,38 @@ static int debug_light_impl(const rt_sphere *spheres, int n_spheres, const rt_ve
     sc.n_lights = 1;
     RtFrameAux ax;
     rt_build_frame_aux(&sc, &ax);
-    DevBuf<RtFrameAux> dax;
-    int rc = dax.alloc(1);
-    if (rc != RT_OK) return rc;
-    RT_HIP(hipMemcpy(dax.p, &ax, sizeof ax, hipMemcpyHostToDevice));
+    DevArray<RtFrameAux> dax;
+    RT_HIP(dax.reserve(1));
+    RT_HIP(hipMemcpy(dax.get(), &ax, sizeof ax, hipMemcpyHostToDevice));
     RtFrameConsts fc;
     memset(&fc, 0, sizeof fc);
     fc.n_lights = 1;
-    fc.aux = dax.p;
+    fc.aux = dax.get();
     fc.n_spheres = n_spheres;
     std::vector<float4> tab(n_spheres ? n_spheres : 1);
     if (n_spheres) pack_spheres(spheres, n_spheres, tab.data());
-    DevBuf<float4> dtab;
-    DevBuf<float> dstart, dnormal, ddirs, dbright;
-    if ((rc = dtab.alloc(tab.size())) || (rc = dstart.alloc(3 * (size_t)n)) || (rc = dnormal.alloc(3 * (size_t)n)) ||
-        (rc = ddirs.alloc(30 * (size_t)n)) || (rc = dbright.alloc(n)))
-        return rc;
-    RT_HIP(hipMemcpy(dtab.p, tab.data(), sizeof(float4) * tab.size(), hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(dstart.p, start, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(dnormal.p, normal, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-    DevBuf<float> dadirs;
-    DevBuf<int> daok;
-    if (approx_dirs && ((rc = dadirs.alloc(30 * (size_t)n)) || (rc = daok.alloc(10 * (size_t)n)))) return rc;
-    RT_HIP(rt_dev_launch_dbg_light(&fc, dtab.p, dstart.p, dnormal.p, 0, n, ddirs.p, dbright.p, approx_dirs ? dadirs.p : nullptr,
-                                   approx_dirs ? daok.p : nullptr, nullptr));
-    RT_HIP(hipMemcpy(dirs, ddirs.p, sizeof(float) * 30 * n, hipMemcpyDeviceToHost));
-    RT_HIP(hipMemcpy(brightness, dbright.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+    DevArray<float4> dtab;
+    DevArray<float> dstart, dnormal, ddirs, dbright, dadirs;
+    DevArray<int> daok;
+    RT_HIP(dtab.reserve(tab.size()));
+    RT_HIP(dstart.reserve(3 * (size_t)n));
+    RT_HIP(dnormal.reserve(3 * (size_t)n));
+    RT_HIP(ddirs.reserve(30 * (size_t)n));
+    RT_HIP(dbright.reserve(n));
+    RT_HIP(hipMemcpy(dtab.get(), tab.data(), sizeof(float4) * tab.size(), hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(dstart.get(), start, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(dnormal.get(), normal, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
     if (approx_dirs) {
-        RT_HIP(hipMemcpy(approx_dirs, dadirs.p, sizeof(float) * 30 * n, hipMemcpyDeviceToHost));
-        RT_HIP(hipMemcpy(approx_ok, daok.p, sizeof(int) * 10 * n, hipMemcpyDeviceToHost));
+        RT_HIP(dadirs.reserve(30 * (size_t)n));
+        RT_HIP(daok.reserve(10 * (size_t)n));
+    }
+    RT_HIP(rt_dev_launch_dbg_light(&fc, dtab.get(), dstart.get(), dnormal.get(), 0, n, ddirs.get(), dbright.get(), approx_dirs ? dadirs.get() : nullptr,
+                                   approx_dirs ? daok.get() : nullptr, nullptr));
+    RT_HIP(hipMemcpy(dirs, ddirs.get(), sizeof(float) * 30 * n, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(brightness, dbright.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (approx_dirs) {
+        RT_HIP(hipMemcpy(approx_dirs, dadirs.get(), sizeof(float) * 30 * n, hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(approx_ok, daok.get(), sizeof(int) * 10 * n, hipMemcpyDeviceToHost));
     }
     return RT_OK;
 }

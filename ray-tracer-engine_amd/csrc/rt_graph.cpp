@@ -42,14 +42,10 @@ struct rt_frame_graph {
     const float4 *build_tab = nullptr;
     int build_n = 0;
     float build_org[3] = {0, 0, 0};
-    float4 *cones = nullptr;         // the graph's own eye-cone table
-    size_t cones_cap = 0;            // float4 units
+    DevArray<float4> cones;          // the graph's own eye-cone table
     bool cones_on_device = false;    // built by the graph's build node (else by the host at (re)build time)
     unsigned long long epoch = 0;    // rt_scene_epoch() the nodes were built against
-    // launch order of the passes' tiles (rt_scene_set_tile_order): [n] durations, [n] order, [nb] block keys, [nb] block starts
-    unsigned *order_buf = nullptr;
-    size_t order_cap = 0;            // unsigneds
-    unsigned *o_cost = nullptr, *o_perm = nullptr, *o_key = nullptr, *o_start = nullptr;
+    RtTileOrderBuf order;            // launch order of the passes' tiles (rt_scene_set_tile_order)
     bool order_on = false;
 };
 
@@ -88,11 +84,11 @@ static int fill_arguments(rt_frame_graph *g, bool with_cones)
     rt_ray_origin(&g->fd, g->build_org);
     for (int p = 0; p < g->passes; ++p) {
         const rt_frame_desc fd = pass_desc(g, p);
-        const int rc = rt_build_frame_consts(g->scene, &fd, with_cones ? g->cones : nullptr, &g->fc[p]);
+        const int rc = rt_build_frame_consts(g->scene, &fd, with_cones ? g->cones.get() : nullptr, &g->fc[p]);
         if (rc != RT_OK) return rc;
         if (g->order_on) {
-            g->fc[p].tile_perm = g->o_perm;
-            g->fc[p].tile_cost = g->o_cost;
+            g->fc[p].tile_perm = g->order.perm();
+            g->fc[p].tile_cost = g->order.cost();
         }
     }
     return RT_OK;
@@ -118,21 +114,14 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
     const bool want_cones = g->fd.opts.cull != 0 && rt_scene_wants_eye_cones(s, org);
     g->cones_on_device = want_cones && ((n + 63) & ~63) <= RT_EYE_DEVICE_MAX;
     if (want_cones) {
-        const size_t total = rt_eye_cones_size(n);
-        if (total > g->cones_cap) {
-            if (g->cones) RT_HIP(hipFree(g->cones));
-            g->cones = nullptr;
-            g->cones_cap = 0;
-            RT_HIP(hipMalloc((void **)&g->cones, sizeof(float4) * total));
-            g->cones_cap = total;
-        }
+        RT_HIP(g->cones.reserve(rt_eye_cones_size(n)));
         if (!g->cones_on_device) {   // list too long for the device builder: host build, blocking upload
-            const int rc = rt_scene_build_eye_cones_host(s, org, g->cones, stream);
+            const int rc = rt_scene_build_eye_cones_host(s, org, g->cones.get(), stream);
             if (rc != RT_OK) return rc;
         }
     }
     // the passes' launch order: all passes render the same rows with the same tile shape
-    int tiles_x = 0, tiles_y = 0;
+    RtTileGrid tg;
     g->order_on = false;
     {
         const rt_frame_desc fd0 = pass_desc(g, 0);
@@ -141,24 +130,10 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
         int rc0 = rt_frame_kernel_choice(s, &fd0, &kc0);
         if (rc0 == RT_OK) rc0 = rt_build_frame_consts(s, &fd0, nullptr, &fc0);
         if (rc0 != RT_OK) return rc0;
-        tiles_x = (fc0.width + kc0.tile - 1) / kc0.tile;
-        tiles_y = (fc0.local_rows + 64 / kc0.tile - 1) / (64 / kc0.tile);
-        const long long nb = (long long)((tiles_x + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK) * ((tiles_y + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK);
-        if (rt_scene_tile_order_mode(s) != 0 && !kc0.table_lds && fc0.local_rows > 0 && tiles_x <= 0xffff && tiles_y <= 0xffff &&
-            nb <= RT_TILE_ORDER_MAX_BLOCKS) {
-            const size_t n = (size_t)tiles_x * (size_t)tiles_y, need = 2 * n + 2 * (size_t)nb;
-            if (need > g->order_cap) {
-                if (g->order_buf) RT_HIP(hipFree(g->order_buf));
-                g->order_buf = nullptr;
-                g->order_cap = 0;
-                RT_HIP(hipMalloc((void **)&g->order_buf, sizeof(unsigned) * need));
-                g->order_cap = need;
-            }
-            g->o_cost = g->order_buf;
-            g->o_perm = g->o_cost + n;
-            g->o_key = g->o_perm + n;
-            g->o_start = g->o_key + nb;
-            RT_HIP(hipMemset(g->o_cost, 0, sizeof(unsigned) * n));   // no durations yet: the first replay sorts zeros (any order)
+        tg = rt_tile_grid(kc0.tile, fc0.width, fc0.local_rows);
+        if (rt_scene_tile_order_mode(s) != 0 && !kc0.table_lds && tg.ok) {
+            RT_HIP(g->order.reserve(tg));
+            RT_HIP(hipMemset(g->order.cost(), 0, sizeof(unsigned) * tg.n));   // no durations yet: the first replay sorts zeros (any order)
             g->order_on = true;
         }
     }
@@ -177,7 +152,8 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
         rt_eye_cones_kernel_config(n, 1024, &func, &g->build_params.gridDim, &g->build_params.blockDim, &lds);
         g->build_params.func = const_cast<void *>(func);
         g->build_params.sharedMemBytes = lds;
-        void *args[] = {&g->build_tab, &g->build_n, &g->build_org[0], &g->build_org[1], &g->build_org[2], &g->cones};
+        float4 *cones = g->cones.get();
+        void *args[] = {&g->build_tab, &g->build_n, &g->build_org[0], &g->build_org[1], &g->build_org[2], &cones};
         g->build_params.kernelParams = args;
         RT_HIP(hipGraphAddKernelNode(&g->build_node, g->graph, nullptr, 0, &g->build_params));
         g->build_params.kernelParams = nullptr;   // `args` is a local: re-pointed on every update
@@ -186,13 +162,12 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
     if (g->order_on) {   // keys -> sort -> expand, from the durations of the previous replay
         const void *func[3];
         dim3 grid[3], block[3];
-        rt_tile_order_kernel_configs(tiles_x, tiles_y, func, grid, block);
-        int nbx = (tiles_x + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK, nby = (tiles_y + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK;
-        int n = tiles_x * tiles_y;
-        const unsigned *c_cost = g->o_cost, *c_key = g->o_key, *c_start = g->o_start;
-        void *a0[] = {&c_cost, &g->o_key, &nbx, &tiles_x, &tiles_y};
-        void *a1[] = {&c_key, &g->o_start, &nbx, &nby, &tiles_x, &tiles_y};
-        void *a2[] = {&c_start, &g->o_perm, &n, &tiles_x, &nbx};
+        rt_tile_order_kernel_configs(tg.tiles_x, tg.tiles_y, func, grid, block);
+        const unsigned *c_cost = g->order.cost(), *c_key = g->order.key(), *c_start = g->order.start();
+        unsigned *key = g->order.key(), *start = g->order.start(), *perm = g->order.perm();
+        void *a0[] = {&c_cost, &key, &tg.nbx, &tg.tiles_x, &tg.tiles_y};
+        void *a1[] = {&c_key, &start, &tg.nbx, &tg.nby, &tg.tiles_x, &tg.tiles_y};
+        void *a2[] = {&c_start, &perm, &tg.n, &tg.tiles_x, &tg.nbx};
         void **args[3] = {a0, a1, a2};
         for (int k = 0; k < 3; ++k) {
             hipKernelNodeParams kp;
@@ -284,7 +259,8 @@ extern "C" rt_frame_graph *rt_graph_capture(rt_scene *s, const rt_frame_desc *fd
 static int update_nodes(rt_frame_graph *g)
 {
     if (g->build_node) {
-        void *args[] = {&g->build_tab, &g->build_n, &g->build_org[0], &g->build_org[1], &g->build_org[2], &g->cones};
+        float4 *cones = g->cones.get();
+        void *args[] = {&g->build_tab, &g->build_n, &g->build_org[0], &g->build_org[1], &g->build_org[2], &cones};
         g->build_params.kernelParams = args;
         const hipError_t e = hipGraphExecKernelNodeSetParams(g->exec, g->build_node, &g->build_params);
         g->build_params.kernelParams = nullptr;
@@ -338,7 +314,5 @@ extern "C" void rt_graph_destroy(rt_frame_graph *g)
     if (!g) return;
     if (g->scene) (void)rt_scene_quiesce(g->scene);
     release_graph(g);
-    if (g->cones) (void)hipFree(g->cones);
-    if (g->order_buf) (void)hipFree(g->order_buf);
     delete g;
 }

@@ -15,6 +15,75 @@ int rt_hip_fail(hipError_t e, const char *expr, const char *file, int line);
         if (rt_e_ != hipSuccess) return rt_hip_fail(rt_e_, #expr, __FILE__, __LINE__); \
     } while (0)
 
+// Owners of the host side's device buffers, pinned buffers, events and streams: each releases its resource when it is
+// destroyed or reset. None of them waits for the device: whoever releases something a frame in flight may still use
+// waits first, at the call site. They can be moved from but not assigned to (no release hides in an assignment), and
+// nothing with static storage duration holds one (it would be released after the HIP runtime has gone).
+template <typename T, bool Pinned>
+class HipArray {
+public:
+    HipArray() = default;
+    HipArray(HipArray &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    ~HipArray() { (void)reset(); }
+    T *get() const { return p_; }
+    size_t capacity() const { return cap_; }   // elements
+    // Room for n elements: re-allocates only when n exceeds the capacity, and then keeps none of the old contents.
+    // *grew (if given): whether it re-allocated.
+    hipError_t reserve(size_t n, bool *grew = nullptr)
+    {
+        if (grew) *grew = false;
+        if (n <= cap_) return hipSuccess;
+        hipError_t e = reset();
+        if (e == hipSuccess)
+            e = Pinned ? hipHostMalloc((void **)&p_, sizeof(T) * n, hipHostMallocDefault) : hipMalloc((void **)&p_, sizeof(T) * n);
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            return e;
+        }
+        cap_ = n;
+        if (grew) *grew = true;
+        return hipSuccess;
+    }
+    hipError_t reset()
+    {
+        T *p = p_;
+        p_ = nullptr;
+        cap_ = 0;
+        return p ? (Pinned ? hipHostFree(p) : hipFree(p)) : hipSuccess;
+    }
+
+private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
+template <typename T> using DevArray = HipArray<T, false>;      // hipMalloc
+template <typename T> using PinnedArray = HipArray<T, true>;    // hipHostMalloc
+
+// An event or stream, made by the first create() (later calls do nothing).
+template <typename H, hipError_t (*Destroy)(H)>
+class HipHandle {
+public:
+    HipHandle() = default;
+    HipHandle(HipHandle &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    ~HipHandle() { reset(); }
+    H get() const { return h_; }
+    void reset()
+    {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+
+protected:
+    H h_ = nullptr;
+};
+struct HipEvent : HipHandle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return h_ ? hipSuccess : hipEventCreateWithFlags(&h_, flags); }
+};
+struct HipStream : HipHandle<hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags) { return h_ ? hipSuccess : hipStreamCreateWithFlags(&h_, flags); }
+    hipError_t create(unsigned flags, int priority) { return h_ ? hipSuccess : hipStreamCreateWithPriority(&h_, flags, priority); }
+};
+
 struct rt_scene;
 
 // which instantiation of the frame kernel renders a frame (rt_kernels.hip: TW, CULL, MODE, TABLDS, FEAT)

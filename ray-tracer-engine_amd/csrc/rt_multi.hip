@@ -87,13 +87,15 @@ struct Rccl {
 };
 Rccl g_rccl;
 
+// The buffers, streams and events of Dev and rt_multi are released by hand, each with its own device current
+// (release_buffers, rt_multi_destroy), never by their destructors under whichever device is current then.
 struct Dev {
     int device = 0;
     rt_scene *scene = nullptr;
-    hipStream_t stream = nullptr;          // this device's frames: kernel, then its part of the gather
-    unsigned *send[2] = {nullptr, nullptr}; // peers: the rows rendered, 3 bytes per pixel, two frames deep
+    HipStream stream;                      // this device's frames: kernel, then its part of the gather
+    DevArray<unsigned> send[2];            // peers: the rows rendered, 3 bytes per pixel, two frames deep
     ncclComm_t comm = nullptr;
-    hipEvent_t rendered[2] = {nullptr, nullptr};
+    HipEvent rendered[2];
 };
 
 }  // namespace
@@ -103,11 +105,11 @@ struct rt_multi {
     int transport = RT_MULTI_RCCL;
     std::vector<Dev> dev;
     // root (dev[0]) side
-    hipStream_t copy_stream[2] = {nullptr, nullptr};   // peer-copy transport: pulls run beside the root's kernel
-    unsigned *recv[2] = {nullptr, nullptr};            // n slots of slot_rows rows, two frames deep
-    uint32_t *frame[2] = {nullptr, nullptr};           // assembled frames when the caller passes no buffer
-    hipEvent_t assembled[2] = {nullptr, nullptr};      // scatter of buffer set b done: the set may be re-used
-    hipEvent_t pulled[2] = {nullptr, nullptr};
+    HipStream copy_stream[2];                          // peer-copy transport: pulls run beside the root's kernel
+    DevArray<unsigned> recv[2];                        // n slots of slot_rows rows, two frames deep
+    DevArray<uint32_t> frame[2];                       // assembled frames when the caller passes no buffer
+    HipEvent assembled[2];                             // scatter of buffer set b done: the set may be re-used
+    HipEvent pulled[2];
     bool set_used[2] = {false, false};
     int width = 0, height = 0, slot_rows = 0;
     unsigned long long frames = 0;
@@ -130,19 +132,14 @@ static int release_buffers(rt_multi *m)
 {
     for (int d = 0; d < m->n; ++d) {
         RT_HIP(hipSetDevice(m->dev[d].device));
-        RT_HIP(hipStreamSynchronize(m->dev[d].stream));
-        for (int b = 0; b < 2; ++b) {
-            if (m->dev[d].send[b]) RT_HIP(hipFree(m->dev[d].send[b]));
-            m->dev[d].send[b] = nullptr;
-        }
+        RT_HIP(hipStreamSynchronize(m->dev[d].stream.get()));
+        for (DevArray<unsigned> &buf : m->dev[d].send) RT_HIP(buf.reset());
     }
     RT_HIP(hipSetDevice(m->dev[0].device));
     for (int b = 0; b < 2; ++b) {
-        if (m->copy_stream[b]) RT_HIP(hipStreamSynchronize(m->copy_stream[b]));
-        if (m->recv[b]) RT_HIP(hipFree(m->recv[b]));
-        if (m->frame[b]) RT_HIP(hipFree(m->frame[b]));
-        m->recv[b] = nullptr;
-        m->frame[b] = nullptr;
+        if (m->copy_stream[b].get()) RT_HIP(hipStreamSynchronize(m->copy_stream[b].get()));
+        RT_HIP(m->recv[b].reset());
+        RT_HIP(m->frame[b].reset());
         m->set_used[b] = false;
     }
     m->width = m->height = m->slot_rows = 0;
@@ -157,15 +154,14 @@ extern "C" void rt_multi_destroy(rt_multi *m)
         (void)hipSetDevice(d.device);
         if (d.comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(d.comm);
         if (d.scene) rt_scene_destroy(d.scene);
-        if (d.stream) (void)hipStreamDestroy(d.stream);
-        for (hipEvent_t e : d.rendered)
-            if (e) (void)hipEventDestroy(e);
+        d.stream.reset();
+        for (HipEvent &e : d.rendered) e.reset();
     }
     if (!m->dev.empty()) (void)hipSetDevice(m->dev[0].device);
     for (int b = 0; b < 2; ++b) {
-        if (m->copy_stream[b]) (void)hipStreamDestroy(m->copy_stream[b]);
-        if (m->assembled[b]) (void)hipEventDestroy(m->assembled[b]);
-        if (m->pulled[b]) (void)hipEventDestroy(m->pulled[b]);
+        m->copy_stream[b].reset();
+        m->assembled[b].reset();
+        m->pulled[b].reset();
     }
     delete m;
 }
@@ -199,28 +195,29 @@ static int rccl_bring_up(rt_multi *m, const int *devices)
     RT_NCCL(g_rccl.CommInitAll(comms.data(), n, devices));
     for (int i = 0; i < n; ++i) m->dev[i].comm = comms[i];
     const size_t slot = 256;
-    std::vector<unsigned char *> bufs((size_t)n, nullptr);
+    std::vector<DevArray<unsigned char>> bufs((size_t)n);
     int rc = RT_OK;
     auto body = [&]() -> int {
         for (int i = 0; i < n; ++i) {
             RT_HIP(hipSetDevice(devices[i]));
-            RT_HIP(hipMalloc((void **)&bufs[(size_t)i], i == 0 ? slot * (size_t)n : slot));
-            if (i == 0) RT_HIP(hipMemsetAsync(bufs[0], 0, slot * (size_t)n, m->dev[0].stream));
-            RT_HIP(hipMemsetAsync(bufs[(size_t)i], 0x40 + i, slot, m->dev[i].stream));
+            RT_HIP(bufs[(size_t)i].reserve(i == 0 ? slot * (size_t)n : slot));
+            if (i == 0) RT_HIP(hipMemsetAsync(bufs[0].get(), 0, slot * (size_t)n, m->dev[0].stream.get()));
+            RT_HIP(hipMemsetAsync(bufs[(size_t)i].get(), 0x40 + i, slot, m->dev[i].stream.get()));
         }
         RT_NCCL(g_rccl.GroupStart());
         for (int i = 0; i < n; ++i) {
             RT_HIP(hipSetDevice(devices[i]));
-            RT_NCCL(g_rccl.Gather(bufs[(size_t)i], i == 0 ? (void *)bufs[0] : nullptr, slot, ncclUint8, 0, m->dev[i].comm, m->dev[i].stream));
+            RT_NCCL(g_rccl.Gather(bufs[(size_t)i].get(), i == 0 ? (void *)bufs[0].get() : nullptr, slot, ncclUint8, 0, m->dev[i].comm,
+                                  m->dev[i].stream.get()));
         }
         RT_NCCL(g_rccl.GroupEnd());
         for (int i = 0; i < n; ++i) {
             RT_HIP(hipSetDevice(devices[i]));
-            RT_HIP(hipStreamSynchronize(m->dev[i].stream));
+            RT_HIP(hipStreamSynchronize(m->dev[i].stream.get()));
         }
         std::vector<unsigned char> host(slot * (size_t)n);
         RT_HIP(hipSetDevice(devices[0]));
-        RT_HIP(hipMemcpy(host.data(), bufs[0], host.size(), hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(host.data(), bufs[0].get(), host.size(), hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i)
             for (size_t k = 0; k < slot; ++k)
                 if (host[slot * (size_t)i + k] != (unsigned char)(0x40 + i)) {
@@ -232,9 +229,9 @@ static int rccl_bring_up(rt_multi *m, const int *devices)
     };
     rc = body();
     for (int i = 0; i < n; ++i)
-        if (bufs[(size_t)i]) {
+        if (bufs[(size_t)i].get()) {
             (void)hipSetDevice(devices[i]);
-            (void)hipFree(bufs[(size_t)i]);
+            (void)bufs[(size_t)i].reset();
         }
     (void)hipSetDevice(devices[0]);
     return rc;
@@ -266,8 +263,8 @@ static int create_impl(rt_multi *m, const int *devices, int n, int transport)
         d.device = devices[i];
         RT_HIP(hipSetDevice(d.device));
         d.scene = rt_scene_create();
-        RT_HIP(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-        for (hipEvent_t &e : d.rendered) RT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        RT_HIP(d.stream.create(hipStreamNonBlocking));
+        for (HipEvent &e : d.rendered) RT_HIP(e.create());
         if (transport == RT_MULTI_PEER_COPY) {
             const int prc = enable_peer(devices[0], d.device);
             if (prc != RT_OK) return prc;
@@ -275,9 +272,9 @@ static int create_impl(rt_multi *m, const int *devices, int n, int transport)
     }
     RT_HIP(hipSetDevice(devices[0]));
     for (int b = 0; b < 2; ++b) {
-        RT_HIP(hipStreamCreateWithFlags(&m->copy_stream[b], hipStreamNonBlocking));
-        RT_HIP(hipEventCreateWithFlags(&m->assembled[b], hipEventDisableTiming));
-        RT_HIP(hipEventCreateWithFlags(&m->pulled[b], hipEventDisableTiming));
+        RT_HIP(m->copy_stream[b].create(hipStreamNonBlocking));
+        RT_HIP(m->assembled[b].create());
+        RT_HIP(m->pulled[b].create());
     }
     if (transport == RT_MULTI_RCCL) {
         const int rc = rccl_bring_up(m, devices);
@@ -378,13 +375,13 @@ static int ensure_buffers(rt_multi *m, int width, int height)
     const int slot_rows = ((blocks + m->n - 1) / m->n) * RT_MULTI_BLOCK;   // the largest share, whole blocks
     const size_t slot_bytes = (size_t)slot_rows * (size_t)width * 3;
     RT_HIP(hipSetDevice(m->dev[0].device));
-    for (int b = 0; b < 2; ++b) {
-        RT_HIP(hipMalloc((void **)&m->recv[b], slot_bytes * (size_t)m->n));
-        RT_HIP(hipMalloc((void **)&m->frame[b], sizeof(uint32_t) * (size_t)width * (size_t)height));
+    for (int b = 0; b < 2; ++b) {   // (slot_bytes: whole words, slot_rows being a multiple of 16)
+        RT_HIP(m->recv[b].reserve(slot_bytes * (size_t)m->n / sizeof(unsigned)));
+        RT_HIP(m->frame[b].reserve((size_t)width * (size_t)height));
     }
     for (int d = 1; d < m->n; ++d) {
         RT_HIP(hipSetDevice(m->dev[d].device));
-        for (int b = 0; b < 2; ++b) RT_HIP(hipMalloc((void **)&m->dev[d].send[b], slot_bytes));
+        for (DevArray<unsigned> &buf : m->dev[d].send) RT_HIP(buf.reserve(slot_bytes / sizeof(unsigned)));
     }
     RT_HIP(hipSetDevice(m->dev[0].device));
     m->width = width;
@@ -426,7 +423,7 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
         if (rc != RT_OK) return rc;
         const int b = (int)(m->frames & 1);
         RT_HIP(hipSetDevice(m->dev[0].device));
-        if (m->set_used[b]) RT_HIP(hipStreamWaitEvent(m->dev[0].stream, m->assembled[b], 0));
+        if (m->set_used[b]) RT_HIP(hipStreamWaitEvent(m->dev[0].stream.get(), m->assembled[b].get(), 0));
         rt_frame_desc f = *fd;
         f.opts.y0 = y0;
         f.opts.y1 = y1;
@@ -434,11 +431,11 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
         f.opts.rgba = nullptr;
         f.opts.packed24 = nullptr;
         f.opts.stats = nullptr;
-        uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[b];
+        uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[b].get();
         f.pixels = out + (size_t)y0 * (size_t)w;
-        rc = rt_scene_render(m->dev[0].scene, &f, m->dev[0].stream);
+        rc = rt_scene_render(m->dev[0].scene, &f, m->dev[0].stream.get());
         if (rc != RT_OK) return rc;
-        RT_HIP(hipEventRecord(m->assembled[b], m->dev[0].stream));
+        RT_HIP(hipEventRecord(m->assembled[b].get(), m->dev[0].stream.get()));
         m->set_used[b] = true;
         m->last = out;
         m->last_set = b;
@@ -462,7 +459,7 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
         Dev &dv = m->dev[d];
         RT_HIP(hipSetDevice(dv.device));
         // buffer set b was last read by the scatter of frame (frames - 2): wait for it on the device
-        if (m->set_used[b]) RT_HIP(hipStreamWaitEvent(dv.stream, m->assembled[b], 0));
+        if (m->set_used[b]) RT_HIP(hipStreamWaitEvent(dv.stream.get(), m->assembled[b].get(), 0));
         rt_frame_desc f = *fd;
         f.pixels = nullptr;
         f.opts.rgba = nullptr;
@@ -472,50 +469,50 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
         f.opts.interleave_count = n;
         f.opts.interleave_index = d;
         f.opts.interleave_rows = RT_MULTI_BLOCK;
-        f.opts.packed24 = d == 0 ? (void *)m->recv[b] : (void *)dv.send[b];
+        f.opts.packed24 = d == 0 ? (void *)m->recv[b].get() : (void *)dv.send[b].get();
         if (n == 1) f.opts.interleave_count = f.opts.interleave_index = f.opts.interleave_rows = 0;   // (a band as it is)
         if (rows_of(hb, d, n) > 0) {
-            rc = rt_scene_render(dv.scene, &f, dv.stream);
+            rc = rt_scene_render(dv.scene, &f, dv.stream.get());
             if (rc != RT_OK) return rc;
         }
-        RT_HIP(hipEventRecord(dv.rendered[b], dv.stream));
+        RT_HIP(hipEventRecord(dv.rendered[b].get(), dv.stream.get()));
     }
     // the frame's single exchange
-    hipStream_t assemble_on = root.stream;
+    hipStream_t assemble_on = root.stream.get();
     if (m->transport == RT_MULTI_RCCL) {
         RT_NCCL(g_rccl.GroupStart());
         for (int d = 0; d < n; ++d) {
             Dev &dv = m->dev[d];
             RT_HIP(hipSetDevice(dv.device));
             // in place on the root: its send buffer is its own slot of the receive buffer
-            const void *src = d == 0 ? (const void *)m->recv[b] : (const void *)dv.send[b];
-            RT_NCCL(g_rccl.Gather(src, d == 0 ? (void *)m->recv[b] : nullptr, slot_bytes, ncclUint8, 0, dv.comm, dv.stream));
+            const void *src = d == 0 ? (const void *)m->recv[b].get() : (const void *)dv.send[b].get();
+            RT_NCCL(g_rccl.Gather(src, d == 0 ? (void *)m->recv[b].get() : nullptr, slot_bytes, ncclUint8, 0, dv.comm, dv.stream.get()));
         }
         RT_NCCL(g_rccl.GroupEnd());
         m->gathers++;
     } else {
         // the root pulls: one asynchronous peer copy per peer, all on the set's copy stream (SDMA engines)
         RT_HIP(hipSetDevice(root.device));
-        assemble_on = m->copy_stream[b];
-        for (int d = 0; d < n; ++d) RT_HIP(hipStreamWaitEvent(assemble_on, m->dev[d].rendered[b], 0));
+        assemble_on = m->copy_stream[b].get();
+        for (int d = 0; d < n; ++d) RT_HIP(hipStreamWaitEvent(assemble_on, m->dev[d].rendered[b].get(), 0));
         for (int d = 1; d < n; ++d) {
             const size_t bytes = (size_t)rows_of(hb, d, n) * (size_t)w * 3;
             if (!bytes) continue;
-            char *dst = (char *)m->recv[b] + slot_bytes * (size_t)d;
+            char *dst = (char *)m->recv[b].get() + slot_bytes * (size_t)d;
             if (m->dev[d].device == root.device)   // the same device twice (one-GPU rehearsal of the path)
-                RT_HIP(hipMemcpyAsync(dst, m->dev[d].send[b], bytes, hipMemcpyDeviceToDevice, assemble_on));
+                RT_HIP(hipMemcpyAsync(dst, m->dev[d].send[b].get(), bytes, hipMemcpyDeviceToDevice, assemble_on));
             else
-                RT_HIP(hipMemcpyPeerAsync(dst, root.device, m->dev[d].send[b], m->dev[d].device, bytes, assemble_on));
+                RT_HIP(hipMemcpyPeerAsync(dst, root.device, m->dev[d].send[b].get(), m->dev[d].device, bytes, assemble_on));
         }
     }
     // rows home, 24 -> 32 bits
     RT_HIP(hipSetDevice(root.device));
-    uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[b];
+    uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[b].get();
     const long long threads = (long long)(w / 4) * hb;
-    hipLaunchKernelGGL(rt_scatter_rows24, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, assemble_on, m->recv[b],
+    hipLaunchKernelGGL(rt_scatter_rows24, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, assemble_on, m->recv[b].get(),
                        reinterpret_cast<uint4 *>(out + (size_t)y0 * (size_t)w), w, hb, n, slot_rows);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(m->assembled[b], assemble_on));
+    RT_HIP(hipEventRecord(m->assembled[b].get(), assemble_on));
     m->set_used[b] = true;
     m->last = out;
     m->last_set = b;
@@ -532,7 +529,7 @@ extern "C" int rt_multi_stream_wait(rt_multi *m, void *stream)
         return RT_ERR_INVALID;
     }
     RT_HIP(hipSetDevice(m->dev[0].device));
-    RT_HIP(hipStreamWaitEvent((hipStream_t)stream, m->assembled[m->last_set], 0));
+    RT_HIP(hipStreamWaitEvent((hipStream_t)stream, m->assembled[m->last_set].get(), 0));
     return RT_OK;
 }
 
@@ -562,10 +559,10 @@ extern "C" int rt_multi_sync(rt_multi *m)
     if (!m) return RT_ERR_INVALID;
     for (Dev &d : m->dev) {
         RT_HIP(hipSetDevice(d.device));
-        RT_HIP(hipStreamSynchronize(d.stream));
+        RT_HIP(hipStreamSynchronize(d.stream.get()));
     }
     RT_HIP(hipSetDevice(m->dev[0].device));
-    for (int b = 0; b < 2; ++b) RT_HIP(hipStreamSynchronize(m->copy_stream[b]));
+    for (int b = 0; b < 2; ++b) RT_HIP(hipStreamSynchronize(m->copy_stream[b].get()));
     return RT_OK;
 }
 

@@ -392,8 +392,7 @@ struct RtReflect {
     std::vector<float> k_dev;             // what the device copy holds (the source of its upload: changed only after
                                           // the frames that may still read it, in rt_reflect_prepare)
     bool k_dirty = false;
-    float *d_k = nullptr;
-    size_t cap_k = 0;
+    DevArray<float> d_k;
     // the BVH of the sphere list it was built from
     unsigned long long bvh_gen = ~0ull;
     int bvh_n = -1;
@@ -401,25 +400,22 @@ struct RtReflect {
     std::vector<BvhNode> nodes;
     std::vector<float4> lsph;
     std::vector<int> order;
-    BvhNode *d_nodes = nullptr;
-    float4 *d_lsph = nullptr;
-    int *d_order = nullptr;
-    size_t cap_nodes = 0, cap_lsph = 0;
+    DevArray<BvhNode> d_nodes;
+    DevArray<float4> d_lsph;
+    DevArray<int> d_order;
     int depth = 0, leaves = 0;
     double build_ms = 0.0;
     // queues and counters
-    QEntry *d_q[2] = {nullptr, nullptr};
-    size_t cap_q = 0;
-    int *d_cnt = nullptr;
-    float4 *d_rgba = nullptr;             // frame-kernel output when the caller gave no rgba
-    size_t cap_rgba = 0;
+    DevArray<QEntry> d_q[2];
+    DevArray<int> d_cnt;
+    DevArray<float4> d_rgba;              // frame-kernel output when the caller gave no rgba
     // the last frame
     int last_depth = 0;
     bool have_frame = false;
     int timing = 0;
     bool timed = false;
-    hipEvent_t ev[RT_MAX_REFLECT_DEPTH + 3] = {};
-    hipEvent_t done = nullptr;            // after the last pass of the last frame (rt_reflect_get_stats waits for it)
+    HipEvent ev[RT_MAX_REFLECT_DEPTH + 3];
+    HipEvent done;                        // after the last pass of the last frame (rt_reflect_get_stats waits for it)
 };
 
 static int rf_build_rec(const std::vector<float4> &sph, std::vector<int> &idx, int lo, int hi, int node, int level,
@@ -529,22 +525,8 @@ static RtReflectDev rf_host_view(const RtReflect *r, const float4 *sph, int n, b
 
 RtReflect *rt_reflect_create() { return new RtReflect(); }
 
-void rt_reflect_destroy(RtReflect *r)
-{
-    if (!r) return;
-    if (r->d_k) (void)hipFree(r->d_k);
-    if (r->d_nodes) (void)hipFree(r->d_nodes);
-    if (r->d_lsph) (void)hipFree(r->d_lsph);
-    if (r->d_order) (void)hipFree(r->d_order);
-    for (QEntry *q : r->d_q)
-        if (q) (void)hipFree(q);
-    if (r->d_cnt) (void)hipFree(r->d_cnt);
-    if (r->d_rgba) (void)hipFree(r->d_rgba);
-    for (hipEvent_t e : r->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (r->done) (void)hipEventDestroy(r->done);
-    delete r;
-}
+// (the scene has waited for its frames, which include the passes)
+void rt_reflect_destroy(RtReflect *r) { delete r; }
 
 // rt_scene_set_spheres: a new count clears the materials (the same count keeps them)
 void rt_reflect_spheres_changed(RtReflect *r, int n_old, int n_new)
@@ -600,26 +582,12 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
         const int rc = rf_build(r, h_spheres, n);
         if (rc != RT_OK) return rc;
         if (r->bvh_ok) {
-            if (r->nodes.size() > r->cap_nodes) {
-                if (r->d_nodes) RT_HIP(hipFree(r->d_nodes));
-                r->d_nodes = nullptr;
-                r->cap_nodes = 0;
-                RT_HIP(hipMalloc((void **)&r->d_nodes, sizeof(BvhNode) * r->nodes.size()));
-                r->cap_nodes = r->nodes.size();
-            }
-            if ((size_t)n > r->cap_lsph) {
-                if (r->d_lsph) RT_HIP(hipFree(r->d_lsph));
-                if (r->d_order) RT_HIP(hipFree(r->d_order));
-                r->d_lsph = nullptr;
-                r->d_order = nullptr;
-                r->cap_lsph = 0;
-                RT_HIP(hipMalloc((void **)&r->d_lsph, sizeof(float4) * (size_t)n));
-                RT_HIP(hipMalloc((void **)&r->d_order, sizeof(int) * (size_t)n));
-                r->cap_lsph = (size_t)n;
-            }
-            RT_HIP(hipMemcpyAsync(r->d_nodes, r->nodes.data(), sizeof(BvhNode) * r->nodes.size(), hipMemcpyHostToDevice, stream));
-            RT_HIP(hipMemcpyAsync(r->d_lsph, r->lsph.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, stream));
-            RT_HIP(hipMemcpyAsync(r->d_order, r->order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream));
+            RT_HIP(r->d_nodes.reserve(r->nodes.size()));
+            RT_HIP(r->d_lsph.reserve((size_t)n));
+            RT_HIP(r->d_order.reserve((size_t)n));
+            RT_HIP(hipMemcpyAsync(r->d_nodes.get(), r->nodes.data(), sizeof(BvhNode) * r->nodes.size(), hipMemcpyHostToDevice, stream));
+            RT_HIP(hipMemcpyAsync(r->d_lsph.get(), r->lsph.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, stream));
+            RT_HIP(hipMemcpyAsync(r->d_order.get(), r->order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream));
         }
         r->bvh_gen = sphere_gen;
         r->bvh_n = n;
@@ -627,37 +595,17 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
     if (r->k_dirty) {
         r->k_dev = r->k;
         if (!r->k_dev.empty()) {
-            if (r->k_dev.size() > r->cap_k) {
-                if (r->d_k) RT_HIP(hipFree(r->d_k));
-                r->d_k = nullptr;
-                r->cap_k = 0;
-                RT_HIP(hipMalloc((void **)&r->d_k, sizeof(float) * r->k_dev.size()));
-                r->cap_k = r->k_dev.size();
-            }
-            RT_HIP(hipMemcpyAsync(r->d_k, r->k_dev.data(), sizeof(float) * r->k_dev.size(), hipMemcpyHostToDevice, stream));
+            RT_HIP(r->d_k.reserve(r->k_dev.size()));
+            RT_HIP(hipMemcpyAsync(r->d_k.get(), r->k_dev.data(), sizeof(float) * r->k_dev.size(), hipMemcpyHostToDevice, stream));
         }
         r->k_dirty = false;
     }
-    if ((size_t)npx > r->cap_q) {
-        for (QEntry *&q : r->d_q) {
-            if (q) RT_HIP(hipFree(q));
-            q = nullptr;
-        }
-        r->cap_q = 0;
-        for (QEntry *&q : r->d_q) RT_HIP(hipMalloc((void **)&q, sizeof(QEntry) * (size_t)npx));
-        r->cap_q = (size_t)npx;
-    }
-    if (!r->d_cnt) RT_HIP(hipMalloc((void **)&r->d_cnt, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1)));
+    for (DevArray<QEntry> &q : r->d_q) RT_HIP(q.reserve((size_t)npx));
+    RT_HIP(r->d_cnt.reserve(RT_MAX_REFLECT_DEPTH + 1));
     *rgba_scratch = nullptr;
     if (need_rgba) {
-        if ((size_t)npx > r->cap_rgba) {
-            if (r->d_rgba) RT_HIP(hipFree(r->d_rgba));
-            r->d_rgba = nullptr;
-            r->cap_rgba = 0;
-            RT_HIP(hipMalloc((void **)&r->d_rgba, sizeof(float4) * (size_t)npx));
-            r->cap_rgba = (size_t)npx;
-        }
-        *rgba_scratch = reinterpret_cast<float *>(r->d_rgba);
+        RT_HIP(r->d_rgba.reserve((size_t)npx));
+        *rgba_scratch = reinterpret_cast<float *>(r->d_rgba.get());
     }
     return RT_OK;
 }
@@ -666,16 +614,13 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
 static hipError_t rt_reflect_mark(RtReflect *r, int slot, hipStream_t stream)
 {
     if (!r->timing) return hipSuccess;
-    if (!r->ev[slot]) {
-        const hipError_t e = hipEventCreate(&r->ev[slot]);
-        if (e != hipSuccess) return e;
-    }
-    return hipEventRecord(r->ev[slot], stream);
+    const hipError_t e = r->ev[slot].create(hipEventDefault);
+    return e != hipSuccess ? e : hipEventRecord(r->ev[slot].get(), stream);
 }
 
 int rt_reflect_begin_frame(RtReflect *r, int depth, hipStream_t stream)
 {
-    RT_HIP(hipMemsetAsync(r->d_cnt, 0, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), stream));
+    RT_HIP(hipMemsetAsync(r->d_cnt.get(), 0, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), stream));
     r->last_depth = depth;
     r->have_frame = true;
     r->timed = r->timing != 0;
@@ -695,26 +640,26 @@ int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_sph
 {
     RT_HIP(rt_reflect_mark(r, 1, stream));
     RtReflectDev rd{};
-    rd.nodes = (!brute && r->bvh_ok) ? r->d_nodes : nullptr;
-    rd.lsph = r->d_lsph;
-    rd.order = r->d_order;
+    rd.nodes = (!brute && r->bvh_ok) ? r->d_nodes.get() : nullptr;
+    rd.lsph = r->d_lsph.get();
+    rd.order = r->d_order.get();
     rd.spheres = d_spheres;
     rd.n = n;
-    rd.k = r->k_dev.empty() ? nullptr : r->d_k;
+    rd.k = r->k_dev.empty() ? nullptr : r->d_k.get();
     rd.depth = depth;
     const int npx = fc->width * fc->local_rows;
     hipLaunchKernelGGL(rt_reflect_primary, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
-                       stream, *fc, rd, r->d_q[0], r->d_cnt);
+                       stream, *fc, rd, r->d_q[0].get(), r->d_cnt.get());
     RT_HIP(hipGetLastError());
     RT_HIP(rt_reflect_mark(r, 2, stream));
     for (int b = 1; b <= depth; ++b) {
         hipLaunchKernelGGL(rt_reflect_bounce, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, rd, b,
-                           r->d_q[(b - 1) & 1], r->d_cnt + (b - 1), r->d_q[b & 1], r->d_cnt + b);
+                           r->d_q[(b - 1) & 1].get(), r->d_cnt.get() + (b - 1), r->d_q[b & 1].get(), r->d_cnt.get() + b);
         RT_HIP(hipGetLastError());
         RT_HIP(rt_reflect_mark(r, 2 + b, stream));
     }
-    if (!r->done) RT_HIP(hipEventCreateWithFlags(&r->done, hipEventDisableTiming));
-    RT_HIP(hipEventRecord(r->done, stream));
+    RT_HIP(r->done.create());
+    RT_HIP(hipEventRecord(r->done.get(), stream));
     return RT_OK;
 }
 
@@ -733,12 +678,12 @@ int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out)
     out->bvh_leaves = r->leaves;
     if (!r->have_frame) return RT_OK;
     out->depth = r->last_depth;
-    if (r->done) RT_HIP(hipEventSynchronize(r->done));   // the last frame only, not the whole device
-    RT_HIP(hipMemcpy(out->queue, r->d_cnt, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), hipMemcpyDeviceToHost));
+    if (r->done.get()) RT_HIP(hipEventSynchronize(r->done.get()));   // the last frame only, not the whole device
+    RT_HIP(hipMemcpy(out->queue, r->d_cnt.get(), sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), hipMemcpyDeviceToHost));
     if (r->timed) {
         for (int p = 0; p < r->last_depth + 2; ++p) {
             float ms = 0.f;
-            RT_HIP(hipEventElapsedTime(&ms, r->ev[p], r->ev[p + 1]));
+            RT_HIP(hipEventElapsedTime(&ms, r->ev[p].get(), r->ev[p + 1].get()));
             out->pass_ms[p] = ms;
         }
         out->timed = 1;

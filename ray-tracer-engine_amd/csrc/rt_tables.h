@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "rt_internal.h"
+
 // Largest beam slope the eye cones are valid for (RtFrameConsts::cone_kcap): tiles whose own
 // beam is wider (tiny resolutions) fall back to the 3-D blocks.
 #define RT_CONE_KCAP 0.1
@@ -44,4 +46,48 @@ void rt_eye_cones_kernel_config(int n, int threads, const void **func, dim3 *gri
 #define RT_TILE_ORDER_MAX_BLOCKS 4096
 hipError_t rt_tile_order_launch(const unsigned *cost, unsigned *key, unsigned *start, unsigned *perm, int tiles_x, int tiles_y,
                                 hipStream_t stream);
+
+// The tiles of a launch (tile_w x 64 / tile_w pixels over width x rows) and their blocks; ok: the launch has tiles and
+// the kernels above can order them (else it keeps grid order).
+struct RtTileGrid {
+    int tiles_x, tiles_y, nbx, nby, n, nb;
+    bool ok;
+};
+inline RtTileGrid rt_tile_grid(int tile_w, int width, int rows)
+{
+    RtTileGrid g;
+    const int th = 64 / tile_w;
+    g.tiles_x = (width + tile_w - 1) / tile_w;
+    g.tiles_y = (rows + th - 1) / th;
+    g.nbx = (g.tiles_x + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK;
+    g.nby = (g.tiles_y + RT_TILE_ORDER_BLOCK - 1) / RT_TILE_ORDER_BLOCK;
+    g.ok = g.tiles_x > 0 && g.tiles_y > 0 && g.tiles_x <= 0xffff && g.tiles_y <= 0xffff &&
+           (long long)g.nbx * g.nby <= RT_TILE_ORDER_MAX_BLOCKS;
+    g.n = g.ok ? g.tiles_x * g.tiles_y : 0;
+    g.nb = g.ok ? g.nbx * g.nby : 0;
+    return g;
+}
+// The arrays of rt_tile_order_launch in one allocation: [cap] durations | [cap] order | [nb_cap] block keys |
+// [nb_cap] block starts.
+struct RtTileOrderBuf {
+    DevArray<unsigned> mem;
+    size_t cap = 0, nb_cap = 0;
+    unsigned *cost() const { return mem.get(); }
+    unsigned *perm() const { return mem.get() + cap; }
+    unsigned *key() const { return mem.get() + 2 * cap; }
+    unsigned *start() const { return mem.get() + 2 * cap + nb_cap; }
+    bool fits(const RtTileGrid &g) const { return (size_t)g.n <= cap && (size_t)g.nb <= nb_cap; }
+    // Room for grid g: re-allocates only when it does not fit, and then keeps none of the old contents.
+    hipError_t reserve(const RtTileGrid &g)
+    {
+        if (fits(g)) return hipSuccess;
+        cap = nb_cap = 0;
+        hipError_t e = mem.reset();
+        if (e == hipSuccess) e = mem.reserve(2 * (size_t)g.n + 2 * (size_t)g.nb);
+        if (e != hipSuccess) return e;
+        cap = (size_t)g.n;
+        nb_cap = (size_t)g.nb;
+        return hipSuccess;
+    }
+};
 void rt_tile_order_kernel_configs(int tiles_x, int tiles_y, const void *func[3], dim3 grid[3], dim3 block[3]);
