@@ -203,11 +203,11 @@ typedef struct rt_launch_opts {
                                 word without its zero top byte), width*rows*3 bytes, band-local
                                 like `pixels`; needs width % 4 == 0. What a multi-GPU rank
                                 sends to the root: a quarter less than the 32-bit words      */
-    int table_lds;           /* 1: each 256-thread workgroup stages the WHOLE sphere table in LDS
-                                (north_star's first design) instead of reading it from global
-                                memory / L2 and keeping only the tiles' survivor lists in LDS.
-                                Same pixels; measured slower, so opt-in.
-                                Default tile only; ignored when the table does not fit          */
+    int table_lds;           /* kept for the layout; selects no kernel. It once staged the whole
+                                sphere table in LDS per workgroup, which measured slower in every
+                                round and was removed: 1 renders with the
+                                default kernel, exactly as 0. 1 still keeps the launch exact
+                                (`fast` ignored), and a frame with reflect_depth > 0 refuses it  */
     int fast;                /* 1: opt-in APPROXIMATE mode. Everything that enters a pixel continuously
                                 (primary hit, normal, toL) stays exact; the ten shadow-sample
                                 directions of a light are built once per light in binary32 with
@@ -402,7 +402,7 @@ int rt_scene_render(rt_scene *s, const rt_frame_desc *fd, void *stream);
  * keeps changing. A launch then ends with its cheap tiles instead of draining the SIMDs behind a few expensive ones
  * (C3: 0.38 -> 0.35 ms per frame, an eighth of the frame 0.085 -> 0.071 ms; a moving camera 0.398 -> 0.381 ms).
  * 0: grid order. Scheduling only: the pixels are the same bits either way. A frame graph sorts its own order at the
- * head of every replay (from the durations of the previous one); table_lds launches always run in grid order.     */
+ * head of every replay (from the durations of the previous one).                                                  */
 int rt_scene_set_tile_order(rt_scene *s, int mode);
 
 /* hipGraph-captured frame loop (config C4): `passes` samples per pixel + resolve + optional async copy of the packed

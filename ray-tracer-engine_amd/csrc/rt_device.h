@@ -70,9 +70,6 @@
 #ifndef RT_MIN_WAVES_MESH_MULTI
 #define RT_MIN_WAVES_MESH_MULTI 4 // ... with a sample loop or work counters on top: 128 registers, no spill
 #endif
-#ifndef RT_WAVES_PER_WG
-#define RT_WAVES_PER_WG 4         // wave tiles per workgroup when the table is staged in LDS (1, 2 or 4)
-#endif
 #ifndef RT_BLOCK
 #define RT_BLOCK 16             // spheres per block of the Morton-ordered table (divides 64)
 #endif

@@ -225,11 +225,10 @@ struct rt_scene {
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
     std::unique_ptr<RtReflect, RtReflectDeleter> refl;
 #ifdef RT_TUNING
-    int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_table_lds = 0, tune_ablate = 0;
+    int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
 #endif
 };
 
-static const int kMaxSpheresLds = (160 * 1024 - RT_WAVES_PER_WG * (RT_LIST_CAP * 20 + 16 * 4 + 64 * 4 + RT_BOX_CAP * 4)) / 16;
 static const int kMaxSpheres = 1 << 22;
 static const int kMaxSpheresOccluders = 8192;    // the per-sphere occluder lists take n * 128 entries (2 KiB per sphere) per light
 
@@ -242,7 +241,6 @@ extern "C" rt_scene *rt_scene_create(void)
     // the product library reads no environment
     if (const char *e = getenv("RT_NO_EYE_CONES")) s->tune_no_eye_cones = atoi(e);
     if (const char *e = getenv("RT_NO_LIGHT_COLUMNS")) s->tune_no_light_columns = atoi(e);
-    if (const char *e = getenv("RT_TABLE_LDS")) s->tune_table_lds = atoi(e);
     if (const char *e = getenv("RT_ABLATE")) s->tune_ablate = atoi(e);
 #endif
     return s;
@@ -1136,7 +1134,7 @@ static int tile_from_opts(const rt_launch_opts &o, int *tile)
     return RT_OK;
 }
 
-// Which instantiation renders this frame (rt_kernels.hip: MODE, FEAT, TABLDS).
+// Which instantiation renders this frame (rt_kernels.hip: TW, CULL, MODE, FEAT).
 int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelChoice *kc)
 {
     int rc = tile_from_opts(fd->opts, &kc->tile);
@@ -1145,16 +1143,12 @@ int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelC
     kc->mode = fd->opts.stats ? (fd->opts.profile ? 3 : 1) : (fd->opts.force_slow_path ? 2 : 0);
     kc->feat = s->n_boxes > 0 ? 2 : ((s->n_planes > 0 || s->n_cubes > 0) ? 1 : 0);
     // the opt-in approximate mode exists for the product configuration only; anything else renders exactly
-    // (a reflective frame is exact: `fast` is ignored there -- its L feeds the bounces)
+    // (a reflective frame is exact: `fast` is ignored there -- its L feeds the bounces; and so is
+    // a launch with the table_lds field set: include/rt_engine.h)
     if (fd->opts.fast == 1 && fd->opts.reflect_depth == 0 && kc->mode == 0 && kc->cull && kc->tile == 8 && kc->feat < 2 &&
         fd->opts.table_lds != 1)
         kc->mode = 4;
-    // whole-table LDS staging (north_star's first design, measured slower: DESIGN.md section 3)
-    // is opt-in per launch and only when the table fits next to the survivor lists
-    kc->table_lds = (fd->opts.table_lds == 1 && s->n_spheres <= kMaxSpheresLds) ? 1 : 0;
-#ifdef RT_TUNING
-    if (s->tune_table_lds && s->n_spheres <= kMaxSpheresLds) kc->table_lds = 1;
-#else
+#ifndef RT_TUNING
     if (kc->mode == 3) {
         rt_set_error("rt_scene_render: opts.profile (phase stamps) needs a tuning build of the library (make EXTRA=-DRT_TUNING)");
         return RT_ERR_UNSUPPORTED;
@@ -1421,7 +1415,7 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         rc = rt_reflect_begin_frame(refl, reflect_depth, stream);
         if (rc != RT_OK) return rc;
     }
-    if (s->tile_order_mode != 0 && !kc.table_lds) {
+    if (s->tile_order_mode != 0) {
         rc = rt_scene_prepare_tile_order(s, kc, &fc, stream);
         if (rc != RT_OK) return rc;
     }
@@ -1429,7 +1423,7 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         rc = rt_reflect_mark_frame_start(s->refl.get(), stream);
         if (rc != RT_OK) return rc;
     }
-    RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres.get(), kc.tile, kc.cull, kc.mode, kc.table_lds, kc.feat, stream));
+    RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres.get(), kc.tile, kc.cull, kc.mode, kc.feat, stream));
     if (reflect_depth > 0) {
         rc = rt_reflect_launch(s->refl.get(), &fc, s->d_spheres.get(), s->n_spheres, reflect_depth, kc.cull == 0, stream);
         if (rc != RT_OK) return rc;

@@ -131,7 +131,7 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
         if (rc0 == RT_OK) rc0 = rt_build_frame_consts(s, &fd0, nullptr, &fc0);
         if (rc0 != RT_OK) return rc0;
         tg = rt_tile_grid(kc0.tile, fc0.width, fc0.local_rows);
-        if (rt_scene_tile_order_mode(s) != 0 && !kc0.table_lds && tg.ok) {
+        if (rt_scene_tile_order_mode(s) != 0 && tg.ok) {
             RT_HIP(g->order.reserve(tg));
             RT_HIP(hipMemset(g->order.cost(), 0, sizeof(unsigned) * tg.n));   // no durations yet: the first replay sorts zeros (any order)
             g->order_on = true;
@@ -191,7 +191,7 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
         memset(&kp, 0, sizeof kp);
         const void *func;
         unsigned lds;
-        RT_HIP(rt_dev_trace_config(&g->fc[p], kc.tile, kc.cull, kc.mode, kc.table_lds, kc.feat, &func, &kp.gridDim, &kp.blockDim, &lds));
+        RT_HIP(rt_dev_trace_config(&g->fc[p], kc.tile, kc.cull, kc.mode, kc.feat, &func, &kp.gridDim, &kp.blockDim, &lds));
         kp.func = const_cast<void *>(func);
         kp.sharedMemBytes = lds;
         void *args[] = {&g->fc[p], &g->spheres};
@@ -236,10 +236,6 @@ extern "C" rt_frame_graph *rt_graph_capture(rt_scene *s, const rt_frame_desc *fd
     }
     if (rt_frame_reflect_depth(fd) != 0) {
         rt_set_error("rt_graph_capture: reflect_depth > 0 is not recorded into graphs (RT_ERR_UNSUPPORTED)");
-        return nullptr;
-    }
-    if (rt_dev_prepare() != hipSuccess) {
-        rt_set_error("rt_graph_capture: kernel image not loadable on this device");
         return nullptr;
     }
     rt_frame_graph *g = new rt_frame_graph();

@@ -86,9 +86,9 @@ struct HipStream : HipHandle<hipStream_t, hipStreamDestroy> {
 
 struct rt_scene;
 
-// which instantiation of the frame kernel renders a frame (rt_kernels.hip: TW, CULL, MODE, TABLDS, FEAT)
+// which instantiation of the frame kernel renders a frame (rt_kernels.hip: TW, CULL, MODE, FEAT)
 struct RtKernelChoice {
-    int tile, cull, mode, table_lds, feat;
+    int tile, cull, mode, feat;
 };
 
 int rt_scene_set_spheres_async(rt_scene *s, const rt_sphere *host_spheres, int n, hipStream_t stream);
@@ -110,11 +110,10 @@ int rt_scene_tile_order_mode(const rt_scene *s);   // rt_scene_set_tile_order
 int rt_scene_build_eye_cones_host(rt_scene *s, const float org[3], float4 *buf, hipStream_t stream);
 
 // launchers of rt_kernels.hip
-extern "C" hipError_t rt_dev_prepare(void);
-extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int table_in_lds, int feat,
+extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int feat,
                                           const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes);
 extern "C" hipError_t rt_dev_launch_trace(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
-                                          int table_in_lds, int feat, hipStream_t stream);
+                                          int feat, hipStream_t stream);
 
 // rt_reflect.hip: mirror reflections (rt_launch_opts.reflect_depth) -- materials, sphere BVH, queues, passes
 struct RtReflect;

@@ -197,82 +197,51 @@ __global__ void rt_dbg_shortcuts(int what, unsigned seed, long long n, unsigned 
 
 RtTraceFn rt_trace_fn_cull8(int mode, int feat, int multi)
 {
-    return multi ? trace_fn_mode_feat<8, true, false, true>(mode, feat) : trace_fn_mode_feat<8, true, false, false>(mode, feat);
+    return multi ? trace_fn_mode_feat<8, true, true>(mode, feat) : trace_fn_mode_feat<8, true, false>(mode, feat);
 }
 
 
 // ---------------------------------------------------------------------------
 // host-side launchers (called from rt_engine.cpp / rt_graph.cpp)
 // ---------------------------------------------------------------------------
-// The instantiations that exist: trace_exists() in rt_trace.inc. Tile widths other than 8 and whole-table LDS
-// staging are tuning / test dimensions: TABLDS exists for the default tile only (other tiles read the table from
-// global memory whatever was asked), and MODE 3 (phase stamps) exists in RT_TUNING builds only.
-// Everything but the default tile's culling kernels lives in the other translation units.
-static RtTraceFn trace_fn(int tile_w, int cull, int mode, int table_in_lds, int feat, int multi)
+// The instantiations that exist: trace_exists() in rt_trace.inc. Tile widths other than 8 are test dimensions, and
+// MODE 3 (phase stamps) exists in RT_TUNING builds only. Everything but the default tile's culling kernels lives in
+// the other translation units.
+static RtTraceFn trace_fn(int tile_w, int cull, int mode, int feat, int multi)
 {
-    if (tile_w == 8) {
-        if (table_in_lds) return rt_trace_fn_lds(cull, mode, feat, multi);
-        return cull ? rt_trace_fn_cull8(mode, feat, multi) : rt_trace_fn_brute8(mode, feat, multi);
-    }
+    if (tile_w == 8) return cull ? rt_trace_fn_cull8(mode, feat, multi) : rt_trace_fn_brute8(mode, feat, multi);
     if (tile_w == 16 || tile_w == 32 || tile_w == 64) return rt_trace_fn_tiles(tile_w, cull, mode, feat);   // sample loop always
     return nullptr;
 }
 
-// Raise the dynamic-LDS limit of the instantiations that stage the whole table (a single
-// workgroup may use the whole 160 KiB). Not a stream operation: it runs once, outside any
-// stream capture or graph construction.
-extern "C" hipError_t rt_dev_prepare(void)
+// Everything a launch of the frame kernel needs besides its two arguments: one 64-thread
+// workgroup per tile. hipErrorNotSupported: no such instantiation.
+extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int feat,
+                                          const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes)
 {
-    static unsigned long long done = 0;   // one bit per device: function attributes belong to a device's code object
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorNoDevice;
-    if (dev < 64 && ((done >> dev) & 1ull)) return hipSuccess;
-    for (int cull = 0; cull < 2; ++cull)
-        for (int mode = 0; mode < 5; ++mode)
-            for (int feat = 0; feat < 3; ++feat)
-                for (int multi = 0; multi < 2; ++multi) {
-                    const RtTraceFn fn = trace_fn(8, cull, mode, 1, feat, multi);
-                    if (!fn) continue;
-                    const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (e != hipSuccess) return e;
-                }
-    if (dev < 64) done |= 1ull << dev;
+    const RtTraceFn fn = trace_fn(tile_w, cull, mode, feat, fc->spp > 1 ? 1 : 0);
+    if (!fn) return hipErrorNotSupported;
+    *lds_bytes = (unsigned)(RT_LIST_CAP * sizeof(float4) +   // survivor list
+                            RT_LIST_CAP * sizeof(int) +      // list positions (primary order)
+                            16 * sizeof(float) +             // brightness table
+                            64 * sizeof(int) +               // marked blocks of a culling pass
+                            16 * sizeof(double) +            // atan(k/8)
+                            192 * sizeof(float) +            // texel colours per pixel
+                            (feat == 2 ? (RT_BOX_CAP + 128) * sizeof(int) : 0));
+    const int th = 64 / tile_w;
+    *grid = dim3((fc->width + tile_w - 1) / tile_w, (fc->local_rows + th - 1) / th);
+    *block = dim3(64);
+    *func = (const void *)fn;
     return hipSuccess;
 }
 
-// Everything a launch of the frame kernel needs besides its two arguments. table_in_lds is
-// honoured for the default tile only. hipErrorNotSupported: no such instantiation.
-extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int table_in_lds, int feat,
-                                          const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes)
-{
-    if (tile_w != 8 || (feat == 2 && fc->spp > 1)) table_in_lds = 0;
-    const RtTraceFn fn = trace_fn(tile_w, cull, mode, table_in_lds, feat, fc->spp > 1 ? 1 : 0);
-    if (!fn) return hipErrorNotSupported;
-    const int n_pad = (fc->n_spheres + 63) & ~63;
-    const int wpw = table_in_lds ? RT_WAVES_PER_WG : 1;   // as WPW in the kernel
-    *lds_bytes = (unsigned)((size_t)((table_in_lds ? n_pad : 0) + wpw * RT_LIST_CAP) * sizeof(float4) +
-                            (size_t)wpw * RT_LIST_CAP * sizeof(int) +   // list positions (primary order)
-                            (size_t)wpw * 16 * sizeof(float) +          // brightness table per wave
-                            (size_t)wpw * 64 * sizeof(int) +            // marked blocks of a culling pass
-                            (size_t)wpw * 16 * sizeof(double) +         // atan(k/8) per wave
-                            (size_t)wpw * 192 * sizeof(float) +         // texel colours per pixel
-                            (feat == 2 ? (size_t)wpw * (RT_BOX_CAP + 128) * sizeof(int) : 0));
-    const int th = 64 / tile_w;
-    const int wgx = (tile_w <= 16 && wpw >= 2) ? 2 : 1;
-    const int wgy = wpw / wgx;
-    *grid = dim3((fc->width + tile_w * wgx - 1) / (tile_w * wgx), (fc->local_rows + th * wgy - 1) / (th * wgy));
-    *block = dim3(64 * wpw);
-    *func = (const void *)fn;
-    return rt_dev_prepare();
-}
-
 extern "C" hipError_t rt_dev_launch_trace(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
-                                          int table_in_lds, int feat, hipStream_t stream)
+                                          int feat, hipStream_t stream)
 {
     const void *func = nullptr;
     dim3 grid, block;
     unsigned lds_bytes = 0;
-    const hipError_t ce = rt_dev_trace_config(fc, tile_w, cull, mode, table_in_lds, feat, &func, &grid, &block, &lds_bytes);
+    const hipError_t ce = rt_dev_trace_config(fc, tile_w, cull, mode, feat, &func, &grid, &block, &lds_bytes);
     if (ce != hipSuccess) return ce;
     hipLaunchKernelGGL((RtTraceFn)func, grid, block, lds_bytes, stream, *fc, spheres);
     return hipGetLastError();

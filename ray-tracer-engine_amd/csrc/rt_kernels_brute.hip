@@ -4,5 +4,5 @@
 
 RtTraceFn rt_trace_fn_brute8(int mode, int feat, int multi)
 {
-    return multi ? trace_fn_mode_feat<8, false, false, true>(mode, feat) : trace_fn_mode_feat<8, false, false, false>(mode, feat);
+    return multi ? trace_fn_mode_feat<8, false, true>(mode, feat) : trace_fn_mode_feat<8, false, false>(mode, feat);
 }

@@ -5,7 +5,7 @@
 template <int TW>
 static RtTraceFn tiles_tw(int cull, int mode, int feat)
 {
-    return cull ? trace_fn_mode_feat<TW, true, false, true>(mode, feat) : trace_fn_mode_feat<TW, false, false, true>(mode, feat);
+    return cull ? trace_fn_mode_feat<TW, true, true>(mode, feat) : trace_fn_mode_feat<TW, false, true>(mode, feat);
 }
 
 RtTraceFn rt_trace_fn_tiles(int tile_w, int cull, int mode, int feat)

@@ -8,8 +8,7 @@
 //
 //   * one wave64 owns a TW x (64/TW) pixel tile and is its own workgroup; the sphere
 //     tables {cx,cy,cz,radius^2} stay in global memory (L2-resident) and only the
-//     tile's culled lists live in LDS (staging the whole table per 256-thread
-//     workgroup is the opt-in rt_launch_opts.table_lds: measured slower);
+//     tile's culled lists live in LDS;
 //   * per tile the wave cooperatively culls the table against a conservative
 //     bound of the tile's rays (a cone for the primary rays, a cone-capped beam
 //     for each light's shadow rays), ballot-compacts the survivors IN LIST
@@ -28,8 +27,8 @@
 //
 // This file is the DEVICE side of the frame kernel, included by the translation units that instantiate it
 // (rt_kernels.hip: default tile, tables in global memory, culling kernels + the diagnostics; rt_kernels_brute.hip:
-// the same tile, brute-force loops; rt_kernels_lds.hip: whole-table LDS staging; rt_kernels_tiles.hip: the other
-// tile shapes) -- one code object, compiled in parallel.
+// the same tile, brute-force loops; rt_kernels_tiles.hip: the other tile shapes) -- one code object, compiled in
+// parallel.
 #pragma once
 // wins ties (kernel.cu:1335) resolve identically: the output is bit-identical
 // to the brute-force loops (template CULL=false), which tests check.
@@ -648,27 +647,11 @@ __device__ __forceinline__ lmask beam_keeps_column(const Beam &b, float4 blkA, f
     return LM(!(reach < 0.f)) & LM(!(d2 > rad * rad * 1.001f));   // NaN / inf bounds keep the block
 }
 
-// The sphere table is either the workgroup's LDS copy (TABLDS, up to a few
-// thousand spheres) or read straight from global memory (any N; coalesced 16 B
-// per lane, L2-resident), in which case LDS only holds the survivor lists.
-template <bool TABLDS>
-__device__ __forceinline__ float4 table_at(const float4 *lds_tab, const float4 *__restrict__ gl_tab, int i)
-{
-    if constexpr (TABLDS) return lds_tab[i];
-    else return gl_tab[i];
-}
 // An entry of the list being walked: the wave's survivor list, or the whole table.
-template <bool TABLDS>
-__device__ __forceinline__ float4 entry_at(bool use_list, const float4 *list, const float4 *lds_tab,
-                                           const float4 *__restrict__ gl_tab, int e)
+__device__ __forceinline__ float4 entry_at(bool use_list, const float4 *list, const float4 *__restrict__ gl_tab, int e)
 {
-    if constexpr (TABLDS) {
-        const float4 *p = use_list ? list : lds_tab;
-        return p[e];
-    } else {
-        if (use_list) return list[e];
-        return gl_tab[e];
-    }
+    if (use_list) return list[e];
+    return gl_tab[e];
 }
 
 // The member test of the culling loop: beam_keeps(), and with OCCL the question whether the
@@ -715,8 +698,8 @@ __device__ __forceinline__ lmask beam_member_test(const Beam &b, float4 s, lmask
 // RT_LIST_CAP tells the caller to walk the whole table instead.
 // BLOCKS selects the first level: 0 = cubes of the 3-D order (fc.sorted/fc.blocks), 1 = a
 // light's columns, 2 = eye cones (the last two: csorted/cblocks/corig, read from global memory).
-template <int STATS, bool TABLDS, bool OCCL, bool ORDERED, int BLOCKS = 0, typename FC = RtFrameConsts>
-__device__ __forceinline__ int build_list2(const float4 *tab, const FC &fc, int n, float4 *list, int *keys,
+template <int STATS, bool OCCL, bool ORDERED, int BLOCKS = 0, typename FC = RtFrameConsts>
+__device__ __forceinline__ int build_list2(const FC &fc, int n, float4 *list, int *keys,
                                            int *blist, const Beam &b, int lane, unsigned long long &n_cull,
                                            const float4 *__restrict__ csorted = nullptr,
                                            const float4 *__restrict__ cblocks = nullptr,
@@ -767,7 +750,7 @@ __device__ __forceinline__ int build_list2(const float4 *tab, const FC &fc, int 
             const int nslot = t + G + grp;
             const int nxt = (nslot < marked) ? blist[nslot] : -1;
             const int i = (cur < 0 ? 0 : cur) * RT_BLOCK + sub;   // inside the padded table
-            const float4 s = table_at<TABLDS && !COLUMNS>(tab, gsorted, i);
+            const float4 s = gsorted[i];
             const lmask m = beam_member_test<OCCL>(b, s, LM(cur >= 0) & LM(i < n), blk);
             const int pos = count + lane_prefix(m);
             if (lane_in(m) && pos < RT_LIST_CAP) {
@@ -1254,8 +1237,8 @@ __device__ __forceinline__ PreSure<N> presure_test(V3 o, const V3 (&dq)[N], floa
 // the live scalars of primitives that are not there.
 // MULTI: the launch may take several samples per pixel (rt_launch_opts.spp > 1). The
 // one-sample kernel has no sample loop: 74 -> 22 spilled scalars and 15 fewer vector registers.
-template <int TW, bool CULL, int MODE, bool TABLDS, int FEAT = 0, bool MULTI = true>
-__global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? (MODE == 1 ? 3 : (MULTI || TABLDS) ? RT_MIN_WAVES_MESH_MULTI : RT_MIN_WAVES_MESH) : (MODE == 1) ? 4 : (!MULTI && !TABLDS) ? RT_MIN_WAVES_ONE_SAMPLE : RT_MIN_WAVES_PER_SIMD) void rt_trace_tiles(const RtFrameConsts fc,
+template <int TW, bool CULL, int MODE, int FEAT = 0, bool MULTI = true>
+__global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_WAVES_MESH_MULTI : RT_MIN_WAVES_MESH) : (MODE == 1) ? 4 : !MULTI ? RT_MIN_WAVES_ONE_SAMPLE : RT_MIN_WAVES_PER_SIMD) void rt_trace_tiles(const RtFrameConsts fc,
                                                                      const float4 *__restrict__ spheres)
 {
     constexpr int STATS = (MODE == 1) ? 1 : (MODE == 3) ? 2 : 0;
@@ -1283,47 +1266,32 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
     constexpr int LEAN_SHADOW_TAIL = FAST ? 2 : 0;
 #endif
     constexpr int TH = 64 / TW;
-    // Waves per workgroup: RT_WAVES_PER_WG share one staged table (TABLDS); with the table left
-    // in global memory nothing is shared, and one-wave workgroups fill the SIMDs best
-    // (0.68 vs 0.71 ms at C3) and need no barrier.
-    constexpr int WPW = TABLDS ? RT_WAVES_PER_WG : 1;
-    constexpr int WGX = (TW <= 16 && WPW >= 2) ? 2 : 1;   // wave tiles per workgroup in x
+    // One wave per workgroup: with the tables in global memory nothing is shared between waves, and one-wave
+    // workgroups fill the SIMDs best (0.68 vs 0.71 ms at C3) and need no barrier.
     extern __shared__ float4 lds[];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;   // always 0 (one-wave workgroups); kept for code generation only: the
+                                         // wave's LDS and the tile rows below say why
     const int n = fc.n_spheres;
-    const int n_pad = (n + 63) & ~63;
     const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;   // lights, sample constants, sky, planes/cubes, mesh (device memory)
 
-    // ---- stage the sphere table into LDS (coalesced 16 B/lane) ----
-    float4 *tab = lds;
-    if constexpr (TABLDS) {
-        // the culling kernels stage the Morton-ordered copy (whole blocks, n_pad entries);
-        // the brute-force kernels stage the list as it is
-        const float4 *src = CULL ? reinterpret_cast<const float4 *>(fc.sorted) : spheres;
-        for (int i = tid; i < (CULL ? n_pad : n); i += 64 * WPW) tab[i] = src[i];
-        __syncthreads();
-    }
-    float4 *mylist = lds + (TABLDS ? n_pad : 0) + wave * RT_LIST_CAP;
-    int *mykeys = reinterpret_cast<int *>(lds + (TABLDS ? n_pad : 0) + WPW * RT_LIST_CAP) + wave * RT_LIST_CAP;
+    // The wave's LDS, in the order rt_dev_trace_config sizes it. The `wave` terms are zero, but with them the compiler
+    // holds these addresses in registers; as plain constants it re-materialises them inside the loops, and the
+    // product kernel's code grows by 8 %.
+    float4 *mylist = lds + wave * RT_LIST_CAP;
+    int *mykeys = reinterpret_cast<int *>(lds + RT_LIST_CAP) + wave * RT_LIST_CAP;   // list positions (primary order)
     // b after n float+=double steps of 0.1 (brightness_steps), one 16-entry copy per wave: a
     // per-lane n then costs one LDS read instead of a ten-deep select chain per light
-    float *mybtab = reinterpret_cast<float *>(lds + (TABLDS ? n_pad : 0) + WPW * RT_LIST_CAP) +
-                    WPW * RT_LIST_CAP + wave * 16;
+    float *mybtab = reinterpret_cast<float *>(lds + RT_LIST_CAP) + RT_LIST_CAP + wave * 16;
     // marked blocks of one culling pass (at most 64 at a time)
-    int *myblks = reinterpret_cast<int *>(lds + (TABLDS ? n_pad : 0) + WPW * RT_LIST_CAP) +
-                  WPW * (RT_LIST_CAP + 16) + wave * 64;
+    int *myblks = reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16) + wave * 64;
     // rtm::atan_eighth(0..8) for the binary64 arctangent (one LDS read instead of a select chain)
-    double *myatan = reinterpret_cast<double *>(reinterpret_cast<int *>(lds + (TABLDS ? n_pad : 0) + WPW * RT_LIST_CAP) +
-                                                WPW * (RT_LIST_CAP + 16 + 64)) + wave * 16;
+    double *myatan = reinterpret_cast<double *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64)) + wave * 16;
     // the pixels' texel colours wait here for the shading at the end of a light (three registers that are live across
     // the whole light loop for one use per lit light; the compiler put them in scratch memory -- 0.4 GB per frame)
-    float *mytex = reinterpret_cast<float *>(reinterpret_cast<int *>(lds + (TABLDS ? n_pad : 0) + WPW * RT_LIST_CAP) +
-                                             WPW * (RT_LIST_CAP + 16 + 64 + 32)) + wave * 192;
-    int *myboxes = reinterpret_cast<int *>(lds + (TABLDS ? n_pad : 0) + WPW * RT_LIST_CAP) +
-                   WPW * (RT_LIST_CAP + 16 + 64 + 32 + 192) + wave * (RT_BOX_CAP + 128);   // + marked leaf blocks + 64 staged floats
+    float *mytex = reinterpret_cast<float *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32)) + wave * 192;
+    int *myboxes = reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192) + wave * (RT_BOX_CAP + 128);   // + marked leaf blocks + 64 staged floats
     float *mytri = reinterpret_cast<float *>(myboxes + RT_BOX_CAP + 64);   // staged vertices of a leaf (MESH launches only)
     if (lane < 16) {
         mybtab[lane] = kBrightnessSteps[lane];   // same values as brightness_steps()
@@ -1331,30 +1299,29 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
     }
     wave_lds_sync();
 
-    // which tile: the workgroup's own, or (one-wave workgroups) the one the frame's tile order puts at this place
+    // which tile: the workgroup's own, or the one the frame's tile order puts at this place
     unsigned blk_x = blockIdx.x, blk_y = blockIdx.y;
     unsigned t_start = 0;
-    const unsigned tiles_x = (unsigned)(fc.width + TW - 1) / (unsigned)TW;   // = gridDim.x of a one-wave-workgroup launch
-    if (!TABLDS) {
-        if (fc.tile_perm) {
-            const unsigned p = fc.tile_perm[blockIdx.y * tiles_x + blockIdx.x];
-            blk_x = p & 0xffffu;
-            blk_y = p >> 16;
-        }
-        if (fc.tile_cost) t_start = (unsigned)__builtin_amdgcn_s_memtime();
+    const unsigned tiles_x = (unsigned)(fc.width + TW - 1) / (unsigned)TW;   // = gridDim.x
+    if (fc.tile_perm) {
+        const unsigned p = fc.tile_perm[blockIdx.y * tiles_x + blockIdx.x];
+        blk_x = p & 0xffffu;
+        blk_y = p >> 16;
     }
-    const int tile_x = (blk_x * WGX + (wave % WGX)) * TW;
+    if (fc.tile_cost) t_start = (unsigned)__builtin_amdgcn_s_memtime();
+    const int tile_x = blk_x * TW;
     // local row -> global row: a contiguous band, or row blocks dealt round-robin
     // to the ranks of a multi-GPU frame (il_rows is a multiple of the tile rows a
     // workgroup covers, so a tile never straddles two blocks)
-    const int ly = (blk_y * (WPW / WGX) + (wave / WGX)) * TH + (lane / TW);
+    // (`+ wave` adds 0; without it the 64x1-tile kernels compile to different code, the others do not change)
+    const int ly = (blk_y + wave) * TH + (lane / TW);
     const int px = tile_x + (lane % TW);
     // (il_rows is a power of two -- the host checks -- and il_count = 1, il_index = 0 for a contiguous band: shifts and a
     // mask, where a division by a run-time il_rows is thirty vector instructions at the head of every wave)
     const int il_sh = __builtin_ctz((unsigned)fc.il_rows);
     const int py = fc.y0 + ((((ly >> il_sh) * fc.il_count + fc.il_index) << il_sh) | (ly & (fc.il_rows - 1)));   // blocks are dealt from the band's first row
     const lmask valid_m = LM(px < fc.width) & LM(ly < fc.local_rows) & LM(py < fc.y1);
-    if (valid_m == 0) return;   // wave-uniform; after the only workgroup barrier
+    if (valid_m == 0) return;   // wave-uniform
     const bool valid = lane_in(valid_m);
 
     unsigned long long st_primary = 0, st_shadow = 0, st_cull = 0, st_slots = 0, st_entries = 0,
@@ -1435,10 +1402,10 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
                 // eye cones when the scene has them and the tile's beam is within their slope limit
                 const float4 *csorted = reinterpret_cast<const float4 *>(fc.csorted);
                 const int c = (csorted && b.k <= fc.cone_kcap)
-                                  ? build_list2<STATS, TABLDS, false, true, 2>(tab, fc, n, mylist, mykeys, myblks, b, lane, st_cull,
+                                  ? build_list2<STATS, false, true, 2>(fc, n, mylist, mykeys, myblks, b, lane, st_cull,
                                                                               csorted, reinterpret_cast<const float4 *>(fc.cblocks),
                                                                               fc.corig)
-                                  : build_list2<STATS, TABLDS, false, true>(tab, fc, n, mylist, mykeys, myblks, b, lane, st_cull);
+                                  : build_list2<STATS, false, true>(fc, n, mylist, mykeys, myblks, b, lane, st_cull);
                 if (c <= RT_LIST_CAP) {
                     p_use_list = true;
                     pcount = c;
@@ -1512,11 +1479,10 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
                 }
             }
         }
-        // without a list the table is walked in list order: from global memory in the culling
-        // kernels (their LDS copy is Morton-ordered), from LDS in the brute-force ones
+        // without a list the table is walked in list order, from global memory
         auto primary_entry = [&](int e) -> float4 {
             if (CULL) return p_use_list ? mylist[e] : spheres[e];
-            return entry_at<TABLDS>(false, mylist, tab, spheres, e);
+            return spheres[e];
         };
         // A culled list comes front to back (build_list2): entry e carries its list position in
         // mykeys[e] and a lower bound of its t in the block-list slot e. `holder` is the list
@@ -1895,10 +1861,10 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
                         if (!(uniform(b.k) <= ch.kcap)) cand_n = -1;   // (also for a NaN)
                         const int cb = cand_n >= 0 ? build_list_cand<STATS>(reinterpret_cast<const float4 *>(ax->cand_ent[li]) + cand_off, cand_n,
                                                                             mylist, b, lane, st_cull, may_skip)
-                                     : lsorted ? build_list2<STATS, TABLDS, true, false, 1>(
-                                                     tab, *kl, n, mylist, mykeys, myblks, b, lane, st_cull, lsorted,
+                                     : lsorted ? build_list2<STATS, true, false, 1>(
+                                                     *kl, n, mylist, mykeys, myblks, b, lane, st_cull, lsorted,
                                                      reinterpret_cast<const float4 *>(ax->lblocks[li]), nullptr, may_skip)
-                                               : build_list2<STATS, TABLDS, true, false>(tab, *kl, n, mylist, mykeys, myblks, b,
+                                               : build_list2<STATS, true, false>(*kl, n, mylist, mykeys, myblks, b,
                                                                                          lane, st_cull, nullptr, nullptr, nullptr, may_skip);
                         const int c = cb & 0x3fffffff;
                         if (may_skip && (cb & 0x40000000)) {
@@ -2116,7 +2082,7 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
                         // (no entry kept in flight: at 7 waves per SIMD the LDS latency is covered by the other
                         // waves, and the four registers are what lets the kernel run at 7)
                         for (int e = 0; e < scount_j; ++e) {
-                            const float4 cur = entry_at<TABLDS>(s_use_list, mylist, tab, gtab, e);
+                            const float4 cur = entry_at(s_use_list, mylist, gtab, e);
                             shadow_test<LEAN_SHADOW_TAIL>(sr, cur, shadowed, force_slow);
                             if (STATS == 1) { st_shadow += __popcll(ballot64(lit)); st_slots += 64; }
                             if (all64(shadowed)) break;
@@ -2221,18 +2187,16 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
     // scratch slot -- across the light loop, whose register peak is what the seven-waves-per-SIMD budget is cut to.
     unsigned wb_x = blockIdx.x, wb_y = blockIdx.y;
     const unsigned wb_tiles_x = (unsigned)(kargs->width + TW - 1) / (unsigned)TW;
-    if (!TABLDS) {
-        const uint32_t *perm = kargs->tile_perm;
-        if (perm) {
-            const unsigned p = perm[blockIdx.y * wb_tiles_x + blockIdx.x];
-            wb_x = p & 0xffffu;
-            wb_y = p >> 16;
-        }
+    const uint32_t *perm = kargs->tile_perm;
+    if (perm) {
+        const unsigned p = perm[blockIdx.y * wb_tiles_x + blockIdx.x];
+        wb_x = p & 0xffffu;
+        wb_y = p >> 16;
     }
     int wb_lane = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(wb_lane));
-    const int wb_px = (int)((wb_x * WGX + (wave % WGX)) * TW) + (wb_lane % TW);
-    const int wb_ly = (int)((wb_y * (WPW / WGX) + (wave / WGX)) * TH) + (wb_lane / TW);
+    const int wb_px = (int)(wb_x * TW) + (wb_lane % TW);
+    const int wb_ly = (int)((wb_y + wave) * TH) + (wb_lane / TW);
     const unsigned out_idx = (unsigned)wb_ly * (unsigned)kargs->width + (unsigned)wb_px;   // band-local pixel index
     if (valid) {
         const size_t o = out_idx;
@@ -2276,7 +2240,7 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
         if (valid && i < 3) o_packed24[(size_t)(out_idx >> 2) * 3 + (size_t)i] = w24;
     }
 
-    if (!TABLDS && o_cost) {   // this tile's wave duration, for the order of later frames (a plain store: an atomic maximum
+    if (o_cost) {   // this tile's wave duration, for the order of later frames (a plain store: an atomic maximum
         // per block of tiles here, 256 waves ending together on one address, slowed the whole launch down by 3 %)
         const unsigned dt = (unsigned)__builtin_amdgcn_s_memtime() - t_start;
         if (wb_lane == 0) o_cost[wb_y * wb_tiles_x + wb_x] = dt;
@@ -2336,20 +2300,18 @@ __global__ __launch_bounds__(64 * (TABLDS ? RT_WAVES_PER_WG : 1), (FEAT == 2) ? 
 
 typedef void (*RtTraceFn)(const RtFrameConsts, const float4 *);
 
-// Which (mode, feat) exist for a tile / cull / TABLDS / MULTI combination. The default tile has them all; the other
-// tile widths are test dimensions of the exact kernels (modes 0 and 2 on sphere scenes, mode 0 with cubes / planes /
-// a mesh, the work counters on sphere scenes only), and whole-table LDS staging has no work-counter build: what no
-// test, tool or bench launches is not compiled (34 of 130 instantiations less: build time and code-object size,
-// profiles/r03_build_and_first_launch.json). A missing combination makes the launch fail with hipErrorNotSupported.
-template <int TW, bool CULL, bool TABLDS, bool MULTI, int MODE, int FEAT>
+// Which (mode, feat) exist for a tile / cull / MULTI combination. The default tile has them all; the other tile
+// widths are test dimensions of the exact kernels (modes 0 and 2 on sphere scenes, mode 0 with cubes / planes / a
+// mesh, the work counters on sphere scenes only): what no test, tool or bench launches is not compiled (build time
+// and code-object size, profiles/r03_build_and_first_launch.json). A missing combination makes the launch fail with
+// hipErrorNotSupported.
+template <int TW, bool CULL, bool MULTI, int MODE, int FEAT>
 static constexpr bool trace_exists()
 {
 #ifdef RT_QUICK   // kernel experiments (tools/variants.sh): the product instantiation and its brute-force twin only
-    if (TW != 8 || TABLDS || FEAT != 0 || (MODE != 0 && MODE != 1) || (MULTI && MODE != 0)) return false;
+    if (TW != 8 || FEAT != 0 || (MODE != 0 && MODE != 1) || (MULTI && MODE != 0)) return false;
 #endif
-    if (FEAT == 2 && TABLDS && MULTI) return false;              // mesh + whole-table staging + sample loop
-    if (MODE == 4) return TW == 8 && CULL && !TABLDS && FEAT < 2;  // fast mode: the product configuration only
-    if (MODE == 1 && TABLDS) return false;
+    if (MODE == 4) return TW == 8 && CULL && FEAT < 2;   // fast mode: the product configuration only
     if (TW != 8 && FEAT >= 1 && MODE != 0) return false;
 #ifndef RT_TUNING
     if (MODE == 3) return false;
@@ -2357,33 +2319,33 @@ static constexpr bool trace_exists()
     return true;
 }
 
-template <int TW, bool CULL, bool TABLDS, bool MULTI, int MODE, int FEAT>
+template <int TW, bool CULL, bool MULTI, int MODE, int FEAT>
 static RtTraceFn trace_fn_one()
 {
-    if constexpr (trace_exists<TW, CULL, TABLDS, MULTI, MODE, FEAT>()) return rt_trace_tiles<TW, CULL, MODE, TABLDS, FEAT, MULTI>;
+    if constexpr (trace_exists<TW, CULL, MULTI, MODE, FEAT>()) return rt_trace_tiles<TW, CULL, MODE, FEAT, MULTI>;
     else return nullptr;
 }
 
-template <int TW, bool CULL, bool TABLDS, bool MULTI, int MODE>
+template <int TW, bool CULL, bool MULTI, int MODE>
 static RtTraceFn trace_fn_feat(int feat)
 {
     switch (feat) {
-    case 0: return trace_fn_one<TW, CULL, TABLDS, MULTI, MODE, 0>();
-    case 1: return trace_fn_one<TW, CULL, TABLDS, MULTI, MODE, 1>();
-    case 2: return trace_fn_one<TW, CULL, TABLDS, MULTI, MODE, 2>();
+    case 0: return trace_fn_one<TW, CULL, MULTI, MODE, 0>();
+    case 1: return trace_fn_one<TW, CULL, MULTI, MODE, 1>();
+    case 2: return trace_fn_one<TW, CULL, MULTI, MODE, 2>();
     default: return nullptr;
     }
 }
 
-template <int TW, bool CULL, bool TABLDS, bool MULTI>
+template <int TW, bool CULL, bool MULTI>
 static RtTraceFn trace_fn_mode_feat(int mode, int feat)
 {
     switch (mode) {
-    case 0: return trace_fn_feat<TW, CULL, TABLDS, MULTI, 0>(feat);
-    case 1: return trace_fn_feat<TW, CULL, TABLDS, MULTI, 1>(feat);
-    case 2: return trace_fn_feat<TW, CULL, TABLDS, MULTI, 2>(feat);
-    case 3: return trace_fn_feat<TW, CULL, TABLDS, MULTI, 3>(feat);
-    case 4: return trace_fn_feat<TW, CULL, TABLDS, MULTI, 4>(feat);
+    case 0: return trace_fn_feat<TW, CULL, MULTI, 0>(feat);
+    case 1: return trace_fn_feat<TW, CULL, MULTI, 1>(feat);
+    case 2: return trace_fn_feat<TW, CULL, MULTI, 2>(feat);
+    case 3: return trace_fn_feat<TW, CULL, MULTI, 3>(feat);
+    case 4: return trace_fn_feat<TW, CULL, MULTI, 4>(feat);
     default: return nullptr;
     }
 }
@@ -2393,5 +2355,4 @@ static RtTraceFn trace_fn_mode_feat(int mode, int feat)
 // the parts of the instantiation table (one translation unit each)
 RtTraceFn rt_trace_fn_cull8(int mode, int feat, int multi);                 // rt_kernels.hip
 RtTraceFn rt_trace_fn_brute8(int mode, int feat, int multi);                // rt_kernels_brute.hip
-RtTraceFn rt_trace_fn_lds(int cull, int mode, int feat, int multi);         // rt_kernels_lds.hip
 RtTraceFn rt_trace_fn_tiles(int tile_w, int cull, int mode, int feat);      // rt_kernels_tiles.hip

@@ -188,9 +188,9 @@ def test_random_seeds_and_counts(rt, gpu, n, seed):
 
 
 def test_table_in_global_memory_matches_lds_staging(rt, gpu):
-    """By default the kernel reads the table from global memory and keeps only
-    the tiles' survivor lists in LDS; rt_launch_opts.table_lds stages the whole table per
-    workgroup instead (north_star's first design). Neither mode may change a bit."""
+    """The kernel reads the table from global memory and keeps only the tiles'
+    survivor lists in LDS. rt_launch_opts.table_lds, which once staged the whole table
+    per workgroup, is still accepted and renders the default kernel's bits."""
     import torch
     from scenes import Inputs
     for n in (100, 1024):
@@ -209,8 +209,8 @@ def test_table_in_global_memory_matches_lds_staging(rt, gpu):
 
 
 def test_large_sphere_counts(rt, gpu):
-    """Maximum sizes: 9000 and 20000 spheres (global-memory table; 9000 also with
-    the table staged in LDS, which it still fits) equal the brute-force loops. The
+    """Maximum sizes: 9000 and 20000 spheres (9000 also with table_lds set, which
+    renders the default kernel's bits) equal the brute-force loops. The
     oracle agrees on a tiny frame. 9000 spheres are beyond the device-side eye-cone
     builder (RT_EYE_DEVICE_MAX), so this is also the host-built table."""
     import torch

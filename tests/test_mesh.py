@@ -137,7 +137,7 @@ def _render_both(rt, inp, mesh, w, h, **kw):
     pm = rt.mesh_from_obj_text(mesh)
     sc.set_mesh(pm)
     # every way a mesh scene can be launched: culled / brute force, the four tile shapes, all shortcuts
-    # off, with the work counters, whole-table LDS staging
+    # off, with the work counters, with table_lds set (accepted, renders the default kernel)
     for opts in (dict(cull=True), dict(cull=False), dict(cull=True, tile=16), dict(cull=True, tile=32), dict(cull=False, tile=64),
                  dict(cull=True, force_slow=True), dict(cull=True, want_stats=True), dict(cull=True, table_lds=True)) + tuple(kw.get("more", ())):
         out = sc.render(w, h, cam=inp.cam, **opts)

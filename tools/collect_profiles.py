@@ -6,7 +6,6 @@ src = os.path.join("gpurun_out", tag)
 line = [l for l in open(os.path.join(src, "bench.json")).read().strip().splitlines() if l.startswith("{")][-1]
 json.dump(json.loads(line), open(f"profiles/{name}_bench_c3_n1.json", "w"), indent=1)
 subprocess.check_call([sys.executable, "tools/summarize_profile.py", tag, f"{name}_c3_frame_kernel"], stdout=subprocess.DEVNULL)
-subprocess.check_call([sys.executable, "tools/summarize_profile.py", tag + "_tablds", f"{name}_c3_table_lds"], stdout=subprocess.DEVNULL)
 for f in ("other_configs", "mesh_scenes", "fast_mode", "host_overhead_single_stream", "host_overhead_two_streams",
           "multi_one_gpu_rehearsal", "build_and_first_launch", "bench_driver_flags", "bench_n2_gloo_one_gpu"):
     s = open(os.path.join(src, f + ".json")).read()

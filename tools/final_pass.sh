@@ -9,7 +9,6 @@ export TMPDIR=/tmp
 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 echo "bench done"; tail -c 600 $OUT/bench.json
 bash tools/profile_gpu.sh $TAG > $OUT/profile.log 2>&1 || exit 2
-FLAGS="--table-lds" bash tools/profile_gpu.sh ${TAG}_tablds > $OUT/profile_tablds.log 2>&1 || exit 3
 echo "profiles done"
 python3 tools/bench_configs.py > $OUT/other_configs.json 2> $OUT/other_configs.err || exit 4
 python3 tools/bench_mesh.py > $OUT/mesh_scenes.json 2>/dev/null || exit 5

@@ -33,6 +33,6 @@ for k in range(6):
 print(json.dumps({"library": os.path.basename(so), "library_bytes": os.path.getsize(so),
                   "torch_cuda_init_s": t_torch, "dlopen_ms": t_dlopen * 1e3, "scene_upload_ms": t_scene * 1e3,
                   "first_frame_ms": times[0], "second_frame_ms": times[1], "later_frames_ms": times[2:],
-                  "build": {"wall_s": a.build_wall_s, "cpu_s": a.build_cpu_s, "how": "make -j8, four translation units of the frame kernel"},
+                  "build": {"wall_s": a.build_wall_s, "cpu_s": a.build_cpu_s, "how": "make -j8, three translation units of the frame kernel"},
                   "note": "C3 frame (3840x2160, 1024 spheres) incl. allocation of its output tensor and a host synchronise; the first "
                           "frame carries the code-object load, the eye-cone / light-column table builds and the raygen tables"}))

@@ -5,7 +5,7 @@
 set -u
 TAG=${1:-r1}
 shift || true
-# flags for every run of the profile (e.g. FLAGS="--table-lds"); the trace run takes 20 steps, the counter runs 3
+# flags for every run of the profile (e.g. FLAGS="--tile 16"); the trace run takes 20 steps, the counter runs 3
 FLAGS=${FLAGS:-}
 BENCH_ARGS="--steps 20 --warmup 3 --no-cpu-baseline --no-extras $FLAGS"
 export TMPDIR=/tmp

@@ -22,7 +22,7 @@ tex, sky = rt.synth_texture(0), rt.synth_texture(1)
 bad = []
 t0 = time.time()
 frames = pixels = 0
-kinds = {"tile": {}, "spp4": 0, "table_lds": 0, "mesh": 0, "prims": 0}
+kinds = {"tile": {}, "spp4": 0, "mesh": 0, "prims": 0}
 for k in range(a.scenes):
     seed = a.seed0 + k
     rng = np.random.default_rng(seed)
@@ -69,17 +69,15 @@ for k in range(a.scenes):
         has_mesh = True
     tile = 8 if has_mesh else int(rng.choice([8, 8, 8, 16, 32, 64]))
     spp = 4 if rng.random() < 0.15 else 1
-    tlds = bool(tile == 8 and rng.random() < 0.1)
     kinds["tile"][tile] = kinds["tile"].get(tile, 0) + 1
     kinds["spp4"] += spp == 4
-    kinds["table_lds"] += tlds
     kinds["mesh"] += has_mesh
     for view in range(2):
         if view == 1:   # the reference moves its camera every frame: nudge it, as checkKey does
             cam.Org.z += 0.1
             cam.Org.x -= 0.1
             cam.Camyaw += 1.0
-        x = sc.render(a.width, a.height, cam=cam, cull=True, tile=tile, spp=spp, table_lds=tlds)
+        x = sc.render(a.width, a.height, cam=cam, cull=True, tile=tile, spp=spp)
         y = sc.render(a.width, a.height, cam=cam, cull=False, spp=spp)
         torch.cuda.synchronize()
         frames += 1
