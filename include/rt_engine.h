@@ -395,6 +395,66 @@ typedef struct rt_frame_desc {
  * layout before reflect_depth was appended.) */
 int rt_scene_render(rt_scene *s, const rt_frame_desc *fd, void *stream);
 
+/* ------------------------------------------------------------------ *
+ * Ray queries: what a caller's rays hit, whether they   *
+ * are blocked, and the colour the frame would give them.               *
+ * ------------------------------------------------------------------ */
+enum { RT_HIT_NONE = -1, RT_HIT_TRIANGLE = 0, RT_HIT_SPHERE = 1, RT_HIT_PLANE = 2, RT_HIT_CUBE = 3 };   /* castRay's hit_type */
+
+/* castRay's outputs (kernel.cu:1287-1431) for one ray; 64 bytes. A miss: t = +inf, kind = index = -1, the rest 0. */
+typedef struct rt_hit {
+    float t;                 /* nt (a sphere reached from inside: its negative near root); +inf on a miss          */
+    int kind;                /* RT_HIT_*                                                                          */
+    int index;               /* position in the scene's list; triangle: index into the mesh's triangle array      */
+    float u, v;              /* nu, nv of a triangle hit, else 0                                                  */
+    float tx, ty;            /* texture coordinates as castRay forms them (plane: 0.5, 0.5)                       */
+    rt_vec3 normal;          /* as castRay forms it (plane: as stored, not normalised; triangle: interpolated when
+                                the mesh has vertex normals)                                                      */
+    rt_vec3 new_org;         /* as castRay forms it (triangle: the hit point displaced by the whole normal)       */
+    uint32_t pad_[3];
+} rt_hit;
+
+#define RT_MAX_QUERY_RAYS (1 << 26)
+enum { RT_QUERY_NEAREST = 0, RT_QUERY_OCCLUDED = 1, RT_QUERY_SHADE = 2 };
+typedef struct rt_ray_query {
+    uint32_t struct_size;    /* sizeof(rt_ray_query); 0 reads as this layout. Fields past a caller's size read as 0 */
+    int mode;                /* RT_QUERY_*                                                                        */
+    int n;                   /* rays, 0 <= n <= RT_MAX_QUERY_RAYS; 0: nothing is done                             */
+    int cull;                /* -1 (default) or 1: spheres through the scene's sphere BVH; 0: the whole lists. The
+                                results are the same bits either way                                              */
+    const rt_ray *rays;      /* device, n rays, used as given (directions are not normalised)                     */
+    rt_hit *hits;            /* device, n records: required for NEAREST, optional for SHADE (the primary hit)     */
+    int *occluded;           /* device, n words: required for OCCLUDED                                            */
+    float *rgba;             /* device, float4 per ray (SHADE): (c, 1)                                            */
+    uint32_t *packed;        /* device, word per ray (SHADE): rgbToInt(c * 254). SHADE needs rgba or packed       */
+} rt_ray_query;              /* rgba must be 16-byte aligned (one float4 store per ray), the other pointers 4-byte
+                                aligned; RT_ERR_INVALID otherwise                                                 */
+
+/* One query over n rays, one thread per ray, on `stream` (asynchronous; NULL = the null stream).
+ *  NEAREST   castRay as the frame kernel evaluates it: mesh leaves (a leaf's triangles only if its own box passes
+ *            cube::intersect), then spheres, cubes, planes; every comparison is the strict t < nt, so the first
+ *            primitive found wins a tie, also across kinds. sphere::intersect, cube::intersect and Moller-Trumbore
+ *            keep their quirks (negative near root from inside, the min/max macros' NaN behaviour, t >= 1e-7f).
+ *  OCCLUDED  castLightRay's per-sample test (kernel.cu:1475-1536): 1 if any triangle (behind its leaf's box), sphere,
+ *            plane or cube reports a hit, at any distance (the reference has no limit), else 0.
+ *  SHADE     rayTrace's pixel body (kernel.cu:1633-1690) for the given ray: on a hit the texel (the frame's clamp)
+ *            and the three-light sum with castLightRay from start_O = N*0.00001 + new_org, occluders of every kind;
+ *            on a miss getFColor (the frame's clamp). Shading the frame's own primary rays
+ *            (rt_scene_primary_rays) gives the frame's rgba and packed words bit for bit. Not a frame path: about
+ *            thirty shadow traversals per hit.
+ * Null or invalid arguments (a bad mode, n out of range, rays NULL with n > 0, a missing required output) return
+ * RT_ERR_INVALID and write nothing; SHADE also needs the scene's texture (when it has primitives) and sky. A stream
+ * that is being captured is refused (RT_ERR_UNSUPPORTED). A query is ordered after the scene's pending uploads and
+ * counts as a frame in flight for the scene's update rules; the host waits only when the sphere BVH (shared with
+ * reflective frames) must be rebuilt. */
+int rt_scene_trace_rays(rt_scene *s, const rt_ray_query *q, void *stream);
+
+/* The reference's primary rays (kernel.cu:1624-1631) of fd's band (opts.y0 / y1; band-local pixel order, row y0
+ * first), formed exactly as the frame kernel forms them at one sample: rays_dev holds width * (y1 - y0) rays
+ * (device). fd's outputs, samples, interleave and reflection fields are ignored; the scene needs what a frame
+ * needs (texture, sky). */
+int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd, rt_ray *rays_dev, void *stream);
+
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
  * tile first -- the frame kernel records every tile's wave duration, and from the previous launch's durations the
  * blocks are sorted on the device (three small kernels, ~15 us): after 1, 2, 4, 8, 16, 32, 64, 96, ... launches of an

@@ -138,6 +138,24 @@ class ReflectStats(C.Structure):
                 ("pass_ms", C.c_float * (RT_MAX_REFLECT_DEPTH + 2)), ("timed", C.c_int)]
 
 
+RT_HIT_NONE, RT_HIT_TRIANGLE, RT_HIT_SPHERE, RT_HIT_PLANE, RT_HIT_CUBE = -1, 0, 1, 2, 3
+RT_QUERY_NEAREST, RT_QUERY_OCCLUDED, RT_QUERY_SHADE = 0, 1, 2
+RT_MAX_QUERY_RAYS = 1 << 26
+_QUERY_MODES = {"nearest": RT_QUERY_NEAREST, "occluded": RT_QUERY_OCCLUDED, "shade": RT_QUERY_SHADE}
+
+
+class Hit(C.Structure):
+    """rt_hit: castRay's outputs for one ray (64 bytes)."""
+    _fields_ = [("t", C.c_float), ("kind", C.c_int), ("index", C.c_int), ("u", C.c_float), ("v", C.c_float),
+                ("tx", C.c_float), ("ty", C.c_float), ("normal", Vec3), ("new_org", Vec3), ("pad_", C.c_uint32 * 3)]
+
+
+class RayQuery(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int), ("n", C.c_int), ("cull", C.c_int),
+                ("rays", C.c_void_p), ("hits", C.c_void_p), ("occluded", C.c_void_p), ("rgba", C.c_void_p),
+                ("packed", C.c_void_p)]
+
+
 class FrameDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
                 ("aspect", C.c_float), ("cam", Camera), ("pixels", C.c_void_p), ("opts", LaunchOpts)]
@@ -254,6 +272,8 @@ def load_library():
         "rt_debug_sphere_bvh": (ci, [C.POINTER(Sphere), ci, fp, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(ci), C.POINTER(ci)]),
         "rt_debug_bvh_cast": (ci, [C.POINTER(Sphere), ci, C.POINTER(Ray), ci, ci, C.POINTER(ci), fp, C.POINTER(ci)]),
         "rt_debug_reflect": (ci, [C.POINTER(Vec3), C.POINTER(Vec3), ci, C.POINTER(Vec3)]),
+        "rt_scene_trace_rays": (ci, [vp, C.POINTER(RayQuery), vp]),
+        "rt_scene_primary_rays": (ci, [vp, C.POINTER(FrameDesc), vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -502,3 +522,72 @@ class Scene:
         if want_stats:
             out["stats"] = dict(zip(STAT_NAMES, stats.cpu().tolist()))
         return out
+
+    # ---------------------------------------------------------------- ray queries
+    def query(self, mode, n, *, rays=0, hits=0, occluded=0, rgba=0, packed=0, cull=-1) -> RayQuery:
+        q = RayQuery()
+        q.struct_size = C.sizeof(RayQuery)
+        q.mode = _QUERY_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        q.n, q.cull = n, cull
+        q.rays, q.hits, q.occluded, q.rgba, q.packed = rays, hits, occluded, rgba, packed
+        return q
+
+    def trace_rays_raw(self, q: RayQuery, stream=0) -> int:
+        """rt_scene_trace_rays as is: returns the status."""
+        return self.lib.rt_scene_trace_rays(self.handle, C.byref(q), stream)
+
+    def trace_rays(self, rays, mode="nearest", cull=True, stream=None):
+        """Cast a CUDA float32 tensor of rays, shape (n, 6) = Org, Dir (directions used as given). Returns a dict of
+        tensors: nearest -> t, kind, index, uv, txy, normal, new_org (castRay's hit record; kind -1 / t = inf on a
+        miss); occluded -> occluded (int32 0/1, castLightRay's any-hit); shade -> rgba (n, 4), packed (n,) int32 (the
+        colour rayTrace gives the ray: the frame's pixel for its own primary ray)."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError("no GPU visible: the ray queries have no CPU fallback")
+        if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6):
+            raise RtError("rays must be a CUDA float32 tensor of shape (n, 6)")
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        m = _QUERY_MODES[mode]
+        st = torch.cuda.current_stream() if stream is None else stream
+        out = {}
+        kw = {}
+        if m == RT_QUERY_NEAREST:
+            hits = torch.empty((n, 16), dtype=torch.int32, device=rays.device)
+            kw["hits"] = hits.data_ptr()
+        elif m == RT_QUERY_OCCLUDED:
+            occ = torch.empty(n, dtype=torch.int32, device=rays.device)
+            kw["occluded"] = occ.data_ptr()
+        else:
+            rgba = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            packed = torch.empty(n, dtype=torch.int32, device=rays.device)
+            kw["rgba"], kw["packed"] = rgba.data_ptr(), packed.data_ptr()
+        q = self.query(m, n, rays=rays.data_ptr(), cull=1 if cull else 0, **kw)
+        _check(self.trace_rays_raw(q, st.cuda_stream), "rt_scene_trace_rays")
+        if m == RT_QUERY_NEAREST:
+            f = hits.view(torch.float32)
+            out = {"t": f[:, 0], "kind": hits[:, 1], "index": hits[:, 2], "uv": f[:, 3:5], "txy": f[:, 5:7],
+                   "normal": f[:, 7:10], "new_org": f[:, 10:13]}
+        elif m == RT_QUERY_OCCLUDED:
+            out = {"occluded": occ}
+        else:
+            out = {"rgba": rgba, "packed": packed}
+        return out
+
+    def primary_rays(self, width, height, *, y0=0, y1=0, cam=None, aspect=None, stream=None):
+        """The reference's primary rays of rows [y0, y1) as the frame kernel forms them: (rows, width, 6) CUDA float32."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError("no GPU visible: the ray queries have no CPU fallback")
+        rows = (y1 if y1 else height) - y0
+        rays = torch.empty((rows, width, 6), dtype=torch.float32, device="cuda")
+        fd = self.frame_desc(width, height, cam=cam, aspect=aspect, y0=y0, y1=y1)
+        st = torch.cuda.current_stream() if stream is None else stream
+        _check(self.lib.rt_scene_primary_rays(self.handle, C.byref(fd), rays.data_ptr(), st.cuda_stream),
+               "rt_scene_primary_rays")
+        return rays
+
+    def pick(self, width, height, x, y, **kw):
+        """What is under pixel (x, y) of a width x height frame: (kind, index), kind RT_HIT_* (-1: sky)."""
+        hit = self.trace_rays(self.primary_rays(width, height, y0=y, y1=y + 1, **kw)[0, x:x + 1], "nearest")
+        return int(hit["kind"][0]), int(hit["index"][0])

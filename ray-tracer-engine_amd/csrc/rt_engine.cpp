@@ -1347,6 +1347,27 @@ extern "C" int rt_scene_reflect_stats(rt_scene *s, rt_reflect_stats *out)
     return rt_reflect_get_stats(scene_reflect(s), out);
 }
 
+// A sphere-table upload enqueued on some stream: order what `stream` does next after it.
+static hipError_t order_after_upload(rt_scene *s, hipStream_t stream)
+{
+    if (s->stage_busy) {
+        if (hipEventQuery(s->stage_done.get()) == hipSuccess) s->stage_busy = false;
+        else {
+            const hipError_t e = hipStreamWaitEvent(stream, s->stage_done.get(), 0);
+            if (e != hipSuccess) return e;
+        }
+        (void)hipGetLastError();   // hipEventQuery reports "not ready" as an error
+    }
+    return hipSuccess;
+}
+
+static bool stream_capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream) (void)hipStreamIsCapturing(stream, &cs);
+    return cs != hipStreamCaptureStatusNone;
+}
+
 extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
@@ -1370,11 +1391,7 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
             return RT_ERR_UNSUPPORTED;
         }
     }
-    if (s->stage_busy) {   // a sphere-table upload enqueued on some stream: order this frame after it
-        if (hipEventQuery(s->stage_done.get()) == hipSuccess) s->stage_busy = false;
-        else RT_HIP(hipStreamWaitEvent(stream, s->stage_done.get(), 0));
-        (void)hipGetLastError();   // hipEventQuery reports "not ready" as an error
-    }
+    RT_HIP(order_after_upload(s, stream));
     int rc = rt_scene_prepare_static(s, fd, stream);
     if (rc != RT_OK) return rc;
     int slot = -1;
@@ -1429,6 +1446,110 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         if (rc != RT_OK) return rc;
     }
     return rt_scene_note_launch(s, stream, slot);
+}
+
+// ---------------------------------------------------------------------------
+// ray queries (rt_query.hip)
+// ---------------------------------------------------------------------------
+extern "C" int rt_scene_trace_rays(rt_scene *s, const rt_ray_query *q_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !q_in) {
+        rt_set_error("rt_scene_trace_rays: null scene or query");
+        return RT_ERR_INVALID;
+    }
+    rt_ray_query q;   // in this build's layout: what the caller's struct_size does not cover reads as 0
+    memset(&q, 0, sizeof q);
+    size_t sz = q_in->struct_size ? q_in->struct_size : sizeof q;
+    if (sz > sizeof q) sz = sizeof q;
+    memcpy(&q, q_in, sz);
+    q.struct_size = (uint32_t)sizeof q;
+    const char *bad = nullptr;
+    if (q.mode != RT_QUERY_NEAREST && q.mode != RT_QUERY_OCCLUDED && q.mode != RT_QUERY_SHADE) bad = "mode is not an RT_QUERY_* value";
+    else if (q.n < 0 || q.n > RT_MAX_QUERY_RAYS) bad = "n is not in [0, RT_MAX_QUERY_RAYS]";
+    else if (q.cull < -1 || q.cull > 1) bad = "cull is not -1, 0 or 1";
+    else if (q.n > 0 && !q.rays) bad = "rays is NULL";
+    else if (q.mode == RT_QUERY_NEAREST && !q.hits) bad = "NEAREST needs hits";
+    else if (q.mode == RT_QUERY_OCCLUDED && !q.occluded) bad = "OCCLUDED needs occluded";
+    else if (q.mode == RT_QUERY_SHADE && !q.rgba && !q.packed) bad = "SHADE needs rgba or packed";
+    else if ((((uintptr_t)q.rays | (uintptr_t)q.hits | (uintptr_t)q.occluded | (uintptr_t)q.packed) & 3u) || ((uintptr_t)q.rgba & 15u))
+        bad = "rgba must be 16-byte aligned (one float4 store per ray), the other pointers 4-byte aligned";
+    else if (q.mode == RT_QUERY_SHADE && !s->have_sky) bad = "SHADE needs the scene's sky";
+    else if (q.mode == RT_QUERY_SHADE && (s->n_spheres > 0 || s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0) &&
+             (!s->d_tex[0].get() || s->tex_w <= 0))
+        bad = "SHADE needs the scene's texture";
+    if (bad) {
+        rt_set_error("rt_scene_trace_rays: %s (mode %d, n %d, cull %d)", bad, q.mode, q.n, q.cull);
+        return RT_ERR_INVALID;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_trace_rays: the stream is being captured (queries are not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    if (q.n == 0) return RT_OK;
+    RT_HIP(order_after_upload(s, stream));
+    int rc = rt_scene_sync_aux(s);
+    if (rc != RT_OK) return rc;
+    const RtSphereBvh *bvh = nullptr;
+    if (q.cull != 0 && s->n_spheres > 0) {
+        // the BVH is shared with reflective frames: rebuilt (after a host wait for every reader) only when the list
+        // changed, and read after whatever frame uploaded it last
+        RtSphereBvh *b = rt_reflect_bvh(scene_reflect(s));
+        if (rt_sphere_bvh_stale(b, s->sphere_gen, s->n_spheres)) {
+            rc = rt_scene_quiesce(s);
+            if (rc != RT_OK) return rc;
+            rc = rt_sphere_bvh_update(b, s->h_prev.data(), s->n_spheres, s->sphere_gen, stream);
+            if (rc != RT_OK) return rc;
+        }
+        rc = stream_wait_all_frames(s, stream);
+        if (rc != RT_OK) return rc;
+        bvh = b;
+    }
+    RtFrameConsts fc;
+    memset(&fc, 0, sizeof fc);
+    fc.n_spheres = s->n_spheres;
+    fc.n_lights = s->n_lights;
+    fc.n_planes = s->n_planes;
+    fc.n_cubes = s->n_cubes;
+    fc.n_boxes = s->n_boxes;
+    fc.flags = s->mesh_has_normals ? RT_FLAG_MESH_NORMALS : 0;
+    fc.tex_r = s->d_tex[0].get(); fc.tex_g = s->d_tex[1].get(); fc.tex_b = s->d_tex[2].get();
+    fc.tex_w = s->tex_w; fc.tex_h = s->tex_h;
+    fc.aux = s->d_aux.get();
+    rc = rt_query_launch(&fc, bvh, s->d_spheres.get(), s->n_spheres, &q, stream);
+    if (rc != RT_OK) return rc;
+    return rt_scene_note_launch(s, stream, -1);   // a query in flight counts as a frame
+}
+
+extern "C" int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd_in, rt_ray *rays_dev, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !fd_in || !rays_dev) {
+        rt_set_error("rt_scene_primary_rays: null scene, frame or ray buffer");
+        return RT_ERR_INVALID;
+    }
+    rt_frame_desc fd;
+    normalise_frame_desc(fd_in, &fd);
+    // one sample, a contiguous band; the frame's outputs are not used (rt_build_frame_consts wants one: the rays)
+    rt_launch_opts &o = fd.opts;
+    o.spp = 1; o.sample_base = 0; o.sample_total = 0; o.accumulate = 0; o.reflect_depth = 0;
+    o.interleave_count = 0; o.interleave_index = 0; o.interleave_rows = 0;
+    o.rgba = nullptr; o.packed24 = nullptr; o.stats = nullptr;
+    fd.pixels = reinterpret_cast<uint32_t *>(rays_dev);
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_primary_rays: the stream is being captured");
+        return RT_ERR_UNSUPPORTED;
+    }
+    RtFrameConsts fc;
+    int rc = rt_build_frame_consts(s, &fd, nullptr, &fc);   // validates size, band, texture and sky first
+    if (rc != RT_OK) return rc;
+    rc = rt_scene_prepare_raygen(s, fd.width, fd.height, fd.aspect, 1);
+    if (rc != RT_OK) return rc;
+    rc = rt_build_frame_consts(s, &fd, nullptr, &fc);       // now with the raygen tables
+    if (rc != RT_OK) return rc;
+    rc = rt_query_launch_primary(&fc, rays_dev, stream);
+    if (rc != RT_OK) return rc;
+    return rt_scene_note_launch(s, stream, -1);   // it reads the raygen tables
 }
 
 int rt_scene_tile_order_mode(const rt_scene *s) { return s->tile_order_mode; }

@@ -130,6 +130,17 @@ int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_sph
                       hipStream_t stream);
 int rt_reflect_set_timing(RtReflect *r, int on);
 int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out);
+// the scene's sphere BVH (rt_bvh.h), shared by reflective frames and ray queries
+struct RtSphereBvh;
+RtSphereBvh *rt_reflect_bvh(RtReflect *r);
+bool rt_sphere_bvh_stale(const RtSphereBvh *b, unsigned long long sphere_gen, int n);
+int rt_sphere_bvh_update(RtSphereBvh *b, const float4 *h_spheres, int n, unsigned long long sphere_gen, hipStream_t stream);
+
+// rt_query.hip: ray queries (q: validated, in this build's layout; bvh: null or current -- the list is walked then)
+int rt_query_launch(const RtFrameConsts *fc, const RtSphereBvh *bvh, const float4 *d_spheres, int n_spheres,
+                    const rt_ray_query *q, hipStream_t stream);
+int rt_query_launch_primary(const RtFrameConsts *fc, rt_ray *rays, hipStream_t stream);
+
 // opts.reflect_depth of a frame description, honouring the struct sizes (0 where the caller's structs end before it)
 int rt_frame_reflect_depth(const rt_frame_desc *fd);
 // a caller's frame description in this build's layout (what its struct_size fields do not cover reads as 0)

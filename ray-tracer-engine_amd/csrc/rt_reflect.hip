@@ -12,11 +12,8 @@
 //             entered the queue keep what the frame kernel wrote.
 // The brute-force variant (opts.cull = 0) is the same kernels with the BVH replaced by the whole sphere list.
 //
-// The BVH (host build in binary64, leaves of <= 4 spheres) is exact against the list: its traversal never drops a
-// sphere that sphere::intersect reports as hit, and the nearest hit is the lexicographic minimum of (t, index) --
-// what the reference's strict `t < nt` loop returns. The margin and the pruning rule are derived in DESIGN.md.
-#include "rt_trace.inc"
-#include "rt_internal.h"
+// The BVH and the per-ray pieces the ray queries share are in rt_bvh.h.
+#include "rt_bvh.h"
 
 #include <algorithm>
 #include <chrono>
@@ -24,23 +21,8 @@
 #include <cstring>
 #include <vector>
 
-#define RT_BVH_LEAF 4
-#define RT_BVH_STACK 24        // traversal stack entries per lane (LDS, 24 KiB per workgroup); the host refuses a deeper
-                               // tree (a median split of the library's 4 M spheres is 21 deep)
-#define RT_BVH_PAD_REL 1.5e-2  // ray-dependent box padding: RT_BVH_PAD_REL * (L1 distance to the box's far corner + largest
-#define RT_BVH_PAD_ABS 1.0e-16 // radius) + RT_BVH_PAD_ABS: twice the bound 7e-3 derived in DESIGN.md "Reflections" 
-#define RT_REFLECT_BLOCK 256
+#define RT_REFLECT_BLOCK RT_BVH_BLOCK
 #define RT_BOUNCE_GRID 2048    // workgroups of a bounce launch (grid-stride over the queue)
-
-struct BvhNode {   // 48 bytes; children of an inner node are `first` and `first + 1`
-    float lo[3];
-    float rmax;    // largest sphere radius below the node (rounded up)
-    float hi[3];
-    int first;     // inner: first child; leaf: first position in order[] / lsph[]
-    int count;     // 0: inner node; else the leaf's sphere count
-    int axis;      // inner: split axis (the first child holds the lower centres)
-    int pad_[2];
-};
 
 struct QEntry {    // one queued ray: 48 bytes
     float ox, oy, oz, dx, dy, dz;
@@ -48,132 +30,6 @@ struct QEntry {    // one queued ray: 48 bytes
     int pix;       // band-local pixel index
     int pad_;
 };
-
-struct RtReflectDev {              // the passes' uniforms (by value)
-    const BvhNode *nodes;          // null: walk the whole list (brute force, or a scene the BVH does not cover)
-    const float4 *lsph;            // spheres in leaf order
-    const int *order;              // their list positions
-    const float4 *spheres;         // the list
-    int n;
-    const float *k;                // reflectivness per sphere (null: all 0)
-    int depth;
-};
-
-// ---------------------------------------------------------------------------
-// host & device: sphere::intersect, the BVH walk
-// ---------------------------------------------------------------------------
-// sphere::intersect, kernel.cu:293-354, on a table entry {cx,cy,cz,radius*radius}: the operations of quadratic() and
-// intersect_tail() in rt_trace.inc, in the same order (this file is compiled without contraction, both sides).
-__host__ __device__ __forceinline__ bool rf_intersect(float ox, float oy, float oz, float dx, float dy, float dz,
-                                                      float4 s, float &t)
-{
-    const float ocx = ox - s.x, ocy = oy - s.y, ocz = oz - s.z;
-    const float h = (dx * ocx + dy * ocy) + dz * ocz;
-    const float B = 2.f * h;
-    const float C = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.w;
-    const float A = (dx * dx + dy * dy) + dz * dz;
-    const float disc = B * B - (4.f * A) * C;
-    const float sq = __builtin_sqrtf(disc);
-    const float a2 = 2.f * ((dx * dx + dy * dy) + dz * dz);
-    t = (-B + sq) / a2;
-    if (t == 0.f) return true;
-    if (t >= RT_T_MIN) {
-        const float t2 = (-B - sq) / a2;
-        if (t > t2) t = t2;
-        return true;
-    }
-    return false;
-}
-
-// The traversal's preconditions: a finite origin within 1e15 of the world origin and a direction of
-// squared length in [0.9, 1.1] (every ray here is a unit vector up to rounding). Other rays walk the list.
-__host__ __device__ __forceinline__ bool rf_ray_ok(float ox, float oy, float oz, float dx, float dy, float dz)
-{
-    const double A = ((double)dx * dx + (double)dy * dy) + (double)dz * dz;
-    return __builtin_fabs((double)ox) <= 1e15 && __builtin_fabs((double)oy) <= 1e15 && __builtin_fabs((double)oz) <= 1e15 &&
-           A >= 0.9 && A <= 1.1;   // false for a NaN anywhere
-}
-
-struct RayD {
-    double o[3], inv[3];
-    float d[3];
-};
-
-// The node's box padded for this ray (any sphere of the node that intersect() reports as hit puts its
-// returned t inside [tmin, tmax] of this padded box, and tmax >= 0). Binary64 slab test, unclamped tmin.
-__host__ __device__ __forceinline__ bool rf_node_test(const BvhNode &nd, const RayD &r, double &tmin)
-{
-    double dsum = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        const double e0 = __builtin_fabs(r.o[a] - (double)nd.lo[a]), e1 = __builtin_fabs(r.o[a] - (double)nd.hi[a]);
-        dsum += e0 > e1 ? e0 : e1;
-    }
-    const double pad = RT_BVH_PAD_REL * (dsum + (double)nd.rmax) + RT_BVH_PAD_ABS;
-    double t0 = -__builtin_inf(), t1 = __builtin_inf();
-    for (int a = 0; a < 3; ++a) {
-        const double lo = (double)nd.lo[a] - pad, hi = (double)nd.hi[a] + pad;
-        if (r.d[a] == 0.f) {
-            if (r.o[a] < lo || r.o[a] > hi) return false;
-        } else {
-            double ta = (lo - r.o[a]) * r.inv[a], tb = (hi - r.o[a]) * r.inv[a];
-            if (ta > tb) { const double x = ta; ta = tb; tb = x; }
-            t0 = ta > t0 ? ta : t0;
-            t1 = tb < t1 ? tb : t1;
-        }
-    }
-    tmin = t0;
-    return t0 <= t1 && t1 >= 0.0;
-}
-
-// Nearest hit (ANY = false: lexicographic minimum of (t, list index), -1 = none) or any-hit (ANY = true: returns 0 / 1).
-// STK(i) is the lane's i-th stack slot.
-template <bool ANY, class Stack>
-__host__ __device__ __forceinline__ int rf_cast(const RtReflectDev &rd, float ox, float oy, float oz, float dx, float dy,
-                                                float dz, float &t_best, Stack stk)
-{
-    int best = -1;
-    float bt = __builtin_inff();
-    if (!rd.nodes || !rf_ray_ok(ox, oy, oz, dx, dy, dz)) {
-        for (int i = 0; i < rd.n; ++i) {
-            float t;
-            if (rf_intersect(ox, oy, oz, dx, dy, dz, rd.spheres[i], t)) {
-                if (ANY) { t_best = t; return 1; }
-                if (t < bt) { bt = t; best = i; }   // kernel.cu:1335: strict, the first index wins ties
-            }
-        }
-        t_best = bt;
-        return ANY ? 0 : best;
-    }
-    RayD r;
-    r.o[0] = ox; r.o[1] = oy; r.o[2] = oz;
-    r.d[0] = dx; r.d[1] = dy; r.d[2] = dz;
-    r.inv[0] = 1.0 / (double)dx; r.inv[1] = 1.0 / (double)dy; r.inv[2] = 1.0 / (double)dz;
-    int sp = 0;
-    stk(sp++) = 0;
-    while (sp > 0) {
-        const BvhNode nd = rd.nodes[stk(--sp)];
-        double tmin;
-        if (!rf_node_test(nd, r, tmin)) continue;
-        if (!ANY && tmin > (double)bt) continue;   // every hit inside has t >= tmin > bt (unclamped tmin: DESIGN.md)
-        if (nd.count == 0) {
-            // the nearer child last (popped first): the first child holds the lower centres along `axis`
-            const bool up = (nd.axis == 0 ? r.d[0] : (nd.axis == 1 ? r.d[1] : r.d[2])) >= 0.f;   // (no dynamic index: scratch)
-            stk(sp++) = up ? nd.first + 1 : nd.first;
-            stk(sp++) = up ? nd.first : nd.first + 1;
-            continue;
-        }
-        for (int p = nd.first; p < nd.first + nd.count; ++p) {
-            float t;
-            if (rf_intersect(ox, oy, oz, dx, dy, dz, rd.lsph[p], t)) {
-                if (ANY) { t_best = t; return 1; }
-                const int idx = rd.order[p];
-                if (t < bt || (t == bt && idx < best)) { bt = t; best = idx; }
-            }
-        }
-    }
-    t_best = bt;
-    return ANY ? 0 : best;
-}
 
 // reflect(I, N), kernel.cu:1282-1285: sub(I, multiply(multiply(N, dot(I, N)), 2)), the dot product left to right
 __host__ __device__ __forceinline__ void rf_reflect(float ix, float iy, float iz, float nx, float ny, float nz, float &rx,
@@ -190,12 +46,6 @@ __host__ __device__ __forceinline__ void rf_reflect(float ix, float iy, float iz
 // ---------------------------------------------------------------------------
 namespace {
 
-struct LdsStack {
-    int *base;   // this workgroup's stack array, slot i of thread tid at base[i * RT_REFLECT_BLOCK + tid]
-    int tid;
-    __device__ int &operator()(int i) const { return base[i * RT_REFLECT_BLOCK + tid]; }
-};
-
 // Append the lanes with `push` set to the queue (one atomic per wave). Every lane of the wave calls it.
 __device__ __forceinline__ void rf_push(bool push, const QEntry &e, QEntry *q, int *count)
 {
@@ -206,37 +56,6 @@ __device__ __forceinline__ void rf_push(bool push, const QEntry &e, QEntry *q, i
     if ((int)(threadIdx.x & 63u) == leader) b = atomicAdd(count, __popcll(m));
     const int base = __builtin_amdgcn_readlane(b, leader);
     if (push) q[base + lane_prefix(m)] = e;
-}
-
-// skybox::getFColor, kernel.cu:1147-1166, as the frame kernel's brute-force instantiation evaluates it
-__device__ __forceinline__ void rf_sky(AuxPtr ax, V3 O, V3 D, float &r, float &g, float &b)
-{
-    const RayK pr = make_ray(O, D);
-    const float4 sk = make_float4(ax->sky_cx, ax->sky_cy, ax->sky_cz, ax->sky_r2);
-    const Quad q = quadratic(pr, sk);
-    float t;
-    intersect_tail(pr, q, t);   // the boolean is ignored there, t is used as left
-    const V3 hp{O.x + D.x * t, O.y + D.y * t, O.z + D.z * t};
-    V3 nrm{hp.x - sk.x, hp.y - sk.y, hp.z - sk.z};
-    normalise_inplace(nrm);
-    const int sky_w = ax->sky_w, sky_h = ax->sky_h;
-    const int ix = f2i((1.f + rtm::atan2f_rt(nrm.z, nrm.x) / 3.1415f) * 0.5f * (float)sky_w);
-    const int iy = f2i(rtm::acosf_rt(nrm.y) / 3.1415f * (float)sky_h);
-    int idx = iy * sky_w + ix;
-    const int last = sky_w * sky_h - 1;
-    idx = idx < 0 ? 0 : (idx > last ? last : idx);   // documented clamp (as the frame kernel)
-    r = ax->sky_r[idx];
-    g = ax->sky_g[idx];
-    b = ax->sky_b[idx];
-}
-
-// The hit point, normal and start_O of castRay's / rayTrace's sphere branch (kernel.cu:1398-1405, 1647)
-__device__ __forceinline__ void rf_hit_frame(V3 O, V3 D, float nt, float4 s, V3 &normal, V3 &start)
-{
-    const V3 new_org{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
-    normal = V3{new_org.x - s.x, new_org.y - s.y, new_org.z - s.z};
-    normalise_inplace(normal);
-    start = V3{normal.x * 0.00001f + new_org.x, normal.y * 0.00001f + new_org.y, normal.z * 0.00001f + new_org.z};
 }
 
 // The three-light sum of rayTrace (kernel.cu:1643-1679) at a sphere hit, with castLightRay's sample construction
@@ -299,16 +118,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
     QEntry e{};
     bool push = false;
     if (valid) {
-        const int ly = pix / fc.width, px = pix - ly * fc.width;
-        const int py = fc.y0 + ly;
-        // kernel.cu:1624-1631, as the frame kernel forms it (one sample: sample_base 0 is checked by the host)
-        V3 dir{fc.dx_tab[px], fc.dy_tab[py], fc.eye_nz};
-        normalise_inplace(dir);
-        const float y = dir.y * fc.cos_pitch - dir.z * fc.sin_pitch;
-        float z = dir.y * fc.sin_pitch + dir.z * fc.cos_pitch;
-        const float x = dir.x * fc.cos_yaw + z * fc.sin_yaw;
-        z = -dir.x * fc.sin_yaw + z * fc.cos_yaw;
-        const V3 D{x, y, z};
+        const V3 D = rf_primary_dir(fc, pix);   // one sample: sample_base 0 is checked by the host
         const V3 O{fc.org_x, fc.org_y, fc.org_z};
         float nt;
         const int hit = rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk);
@@ -393,18 +203,7 @@ struct RtReflect {
                                           // the frames that may still read it, in rt_reflect_prepare)
     bool k_dirty = false;
     DevArray<float> d_k;
-    // the BVH of the sphere list it was built from
-    unsigned long long bvh_gen = ~0ull;
-    int bvh_n = -1;
-    bool bvh_ok = false;                  // false: the list is walked (non-finite or huge data)
-    std::vector<BvhNode> nodes;
-    std::vector<float4> lsph;
-    std::vector<int> order;
-    DevArray<BvhNode> d_nodes;
-    DevArray<float4> d_lsph;
-    DevArray<int> d_order;
-    int depth = 0, leaves = 0;
-    double build_ms = 0.0;
+    RtSphereBvh bvh;                      // the sphere BVH (shared with the ray queries)
     // queues and counters
     DevArray<QEntry> d_q[2];
     DevArray<int> d_cnt;
@@ -419,7 +218,7 @@ struct RtReflect {
 };
 
 static int rf_build_rec(const std::vector<float4> &sph, std::vector<int> &idx, int lo, int hi, int node, int level,
-                        RtReflect *r)
+                        RtSphereBvh *r)
 {
     r->depth = level > r->depth ? level : r->depth;
     double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
@@ -475,9 +274,9 @@ static int rf_build_rec(const std::vector<float4> &sph, std::vector<int> &idx, i
     return rf_build_rec(sph, idx, mid, hi, child + 1, level + 1, r);
 }
 
-// Host build (binary64 extents, binary32 boxes rounded outward). bvh_ok = false when a sphere is non-finite or lies
+// Host build (binary64 extents, binary32 boxes rounded outward). ok = false when a sphere is non-finite or lies
 // beyond 1e15 (the traversal's derivation assumes neither): every ray then walks the list.
-static int rf_build(RtReflect *r, const float4 *sph, int n)
+static int rf_build(RtSphereBvh *r, const float4 *sph, int n)
 {
     const auto t0 = std::chrono::steady_clock::now();
     r->nodes.clear();
@@ -485,14 +284,14 @@ static int rf_build(RtReflect *r, const float4 *sph, int n)
     r->order.clear();
     r->depth = 0;
     r->leaves = 0;
-    r->bvh_ok = n > 0;
-    for (int i = 0; i < n && r->bvh_ok; ++i) {
+    r->ok = n > 0;
+    for (int i = 0; i < n && r->ok; ++i) {
         const float4 s = sph[i];
         const double R = std::sqrt((double)s.w);
         if (!(std::fabs((double)s.x) + R <= 1e15 && std::fabs((double)s.y) + R <= 1e15 && std::fabs((double)s.z) + R <= 1e15))
-            r->bvh_ok = false;   // (false for NaN / inf too)
+            r->ok = false;   // (false for NaN / inf too)
     }
-    if (r->bvh_ok) {
+    if (r->ok) {
         std::vector<float4> v(sph, sph + n);
         std::vector<int> idx((size_t)n);
         for (int i = 0; i < n; ++i) idx[(size_t)i] = i;
@@ -512,10 +311,30 @@ static int rf_build(RtReflect *r, const float4 *sph, int n)
     return RT_OK;
 }
 
-static RtReflectDev rf_host_view(const RtReflect *r, const float4 *sph, int n, bool use_bvh)
+bool rt_sphere_bvh_stale(const RtSphereBvh *b, unsigned long long sphere_gen, int n) { return b->gen != sphere_gen || b->n != n; }
+
+int rt_sphere_bvh_update(RtSphereBvh *b, const float4 *h_spheres, int n, unsigned long long sphere_gen, hipStream_t stream)
+{
+    if (!rt_sphere_bvh_stale(b, sphere_gen, n)) return RT_OK;
+    const int rc = rf_build(b, h_spheres, n);
+    if (rc != RT_OK) return rc;
+    if (b->ok) {
+        RT_HIP(b->d_nodes.reserve(b->nodes.size()));
+        RT_HIP(b->d_lsph.reserve((size_t)n));
+        RT_HIP(b->d_order.reserve((size_t)n));
+        RT_HIP(hipMemcpyAsync(b->d_nodes.get(), b->nodes.data(), sizeof(BvhNode) * b->nodes.size(), hipMemcpyHostToDevice, stream));
+        RT_HIP(hipMemcpyAsync(b->d_lsph.get(), b->lsph.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, stream));
+        RT_HIP(hipMemcpyAsync(b->d_order.get(), b->order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream));
+    }
+    b->gen = sphere_gen;
+    b->n = n;
+    return RT_OK;
+}
+
+static RtReflectDev rf_host_view(const RtSphereBvh *r, const float4 *sph, int n, bool use_bvh)
 {
     RtReflectDev rd{};
-    rd.nodes = (use_bvh && r->bvh_ok) ? r->nodes.data() : nullptr;
+    rd.nodes = (use_bvh && r->ok) ? r->nodes.data() : nullptr;
     rd.lsph = r->lsph.data();
     rd.order = r->order.data();
     rd.spheres = sph;
@@ -524,6 +343,8 @@ static RtReflectDev rf_host_view(const RtReflect *r, const float4 *sph, int n, b
 }
 
 RtReflect *rt_reflect_create() { return new RtReflect(); }
+
+RtSphereBvh *rt_reflect_bvh(RtReflect *r) { return &r->bvh; }
 
 // (the scene has waited for its frames, which include the passes)
 void rt_reflect_destroy(RtReflect *r) { delete r; }
@@ -570,7 +391,7 @@ int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_sp
 
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n)
 {
-    return r->k_dirty || r->bvh_gen != sphere_gen || r->bvh_n != n;
+    return r->k_dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
 }
 
 // Brings materials and BVH up to date (the caller has waited for every frame that may read them) and makes sure the
@@ -578,19 +399,9 @@ bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, 
 int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned long long sphere_gen, int npx,
                        bool need_rgba, float **rgba_scratch, hipStream_t stream)
 {
-    if (r->bvh_gen != sphere_gen || r->bvh_n != n) {
-        const int rc = rf_build(r, h_spheres, n);
+    {
+        const int rc = rt_sphere_bvh_update(&r->bvh, h_spheres, n, sphere_gen, stream);
         if (rc != RT_OK) return rc;
-        if (r->bvh_ok) {
-            RT_HIP(r->d_nodes.reserve(r->nodes.size()));
-            RT_HIP(r->d_lsph.reserve((size_t)n));
-            RT_HIP(r->d_order.reserve((size_t)n));
-            RT_HIP(hipMemcpyAsync(r->d_nodes.get(), r->nodes.data(), sizeof(BvhNode) * r->nodes.size(), hipMemcpyHostToDevice, stream));
-            RT_HIP(hipMemcpyAsync(r->d_lsph.get(), r->lsph.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, stream));
-            RT_HIP(hipMemcpyAsync(r->d_order.get(), r->order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream));
-        }
-        r->bvh_gen = sphere_gen;
-        r->bvh_n = n;
     }
     if (r->k_dirty) {
         r->k_dev = r->k;
@@ -640,9 +451,9 @@ int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_sph
 {
     RT_HIP(rt_reflect_mark(r, 1, stream));
     RtReflectDev rd{};
-    rd.nodes = (!brute && r->bvh_ok) ? r->d_nodes.get() : nullptr;
-    rd.lsph = r->d_lsph.get();
-    rd.order = r->d_order.get();
+    rd.nodes = (!brute && r->bvh.ok) ? r->bvh.d_nodes.get() : nullptr;
+    rd.lsph = r->bvh.d_lsph.get();
+    rd.order = r->bvh.d_order.get();
     rd.spheres = d_spheres;
     rd.n = n;
     rd.k = r->k_dev.empty() ? nullptr : r->d_k.get();
@@ -672,10 +483,10 @@ int rt_reflect_set_timing(RtReflect *r, int on)
 int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out)
 {
     memset(out, 0, sizeof *out);
-    out->bvh_build_ms = r->build_ms;
-    out->bvh_nodes = (int)r->nodes.size();
-    out->bvh_depth = r->depth;
-    out->bvh_leaves = r->leaves;
+    out->bvh_build_ms = r->bvh.build_ms;
+    out->bvh_nodes = (int)r->bvh.nodes.size();
+    out->bvh_depth = r->bvh.depth;
+    out->bvh_leaves = r->bvh.leaves;
     if (!r->have_frame) return RT_OK;
     out->depth = r->last_depth;
     if (r->done.get()) RT_HIP(hipEventSynchronize(r->done.get()));   // the last frame only, not the whole device
@@ -710,10 +521,10 @@ extern "C" int rt_debug_sphere_bvh(const rt_sphere *spheres, int n, float *lohi,
     }
     std::vector<float4> v;
     pack_list(spheres, n, v);
-    RtReflect r;
+    RtSphereBvh r;
     const int rc = rf_build(&r, v.data(), n);
     if (rc != RT_OK) return rc;
-    if (!r.bvh_ok) {
+    if (!r.ok) {
         rt_set_error("rt_debug_sphere_bvh: the list has non-finite or huge spheres (no BVH: the list is walked)");
         return RT_ERR_UNSUPPORTED;
     }
@@ -744,7 +555,7 @@ extern "C" int rt_debug_bvh_cast(const rt_sphere *spheres, int n, const rt_ray *
     }
     std::vector<float4> v;
     pack_list(spheres, n, v);
-    RtReflect r;
+    RtSphereBvh r;
     int rc = RT_OK;
     if (use_bvh) rc = rf_build(&r, v.data(), n);
     if (rc != RT_OK) return rc;
