@@ -343,7 +343,8 @@ int rt_scene_set_sky(rt_scene *s, const rt_sphere *box, const float *r, const fl
 int rt_scene_set_lights(rt_scene *s, const rt_light *lights, int n);
 
 /* material, kernel.cu:213-224 (field names as the reference spells them). Only reflectivness is
- * implemented; a material with transperancy or roughness != 0 is RT_ERR_UNSUPPORTED. */
+ * implemented here; a material with transperancy or roughness != 0 is RT_ERR_UNSUPPORTED
+ * (transparency is set through rt_material_ex, which carries an index of refraction). */
 typedef struct rt_material {
     float reflectivness;     /* k in [0, 1]: the share of a hit's colour taken from its mirror ray */
     float transperancy;      /* must be 0 */
@@ -364,6 +365,46 @@ typedef struct rt_material {
  * binary32; rgba = (c, 1) and the packed word is rgbToInt(c * 254). A pixel whose primary hit has
  * k = 0, and every sky pixel, is the frame without reflections bit for bit. */
 int rt_scene_set_materials(rt_scene *s, const rt_material *per_sphere, int n);
+
+/* A material with transparency (DESIGN.md "Refraction"). The old rt_material has no index of
+ * refraction, so it keeps refusing transperancy != 0; this one carries it. */
+typedef struct rt_material_ex {
+    float reflectivness;     /* k in [0, 1]                                                        */
+    float transperancy;      /* tau in [0, 1]: the share of a hit's colour taken from the ray that
+                                passes through the sphere                                          */
+    float roughness;         /* must be 0 (RT_ERR_UNSUPPORTED)                                     */
+    float ior;               /* index of refraction, finite, in [1, 4], where tau > 0; ignored (may
+                                be 0) where tau == 0                                               */
+} rt_material_ex;            /* 16 bytes */
+
+/* One material per sphere (n == the sphere count); NULL / 0 clears them. The same per-sphere table
+ * as rt_scene_set_materials: the last call of either wins, and a call to rt_scene_set_materials
+ * sets every tau to 0. It survives rt_scene_set_spheres with the same count and is cleared by a
+ * different count. A NaN or out-of-range k, tau or ior (ior only where tau > 0): RT_ERR_INVALID;
+ * roughness != 0, or k > 0 together with tau > 0 on one sphere: RT_ERR_UNSUPPORTED (one
+ * continuation per hit). Nothing changes on an error.
+ *
+ * Semantics: the per-pixel loop of rt_scene_set_materials, binary32, no contraction, correctly
+ * rounded division and sqrt, dot products left to right. At a hit on sphere i with tau > 0 and
+ * b < D: new_org, N, start_O and L as for a mirror hit; the term is (w * (1 - tau)) * L, then
+ * w = w * tau. refract(I, n, eta) for n facing against I: c = -dot(I, n),
+ * q = 1 - (eta*eta) * (1 - c*c), s = sqrt(q > 0 ? q : 0) (no total internal reflection), result
+ * I*eta + n*(eta*c - s), not renormalised. R_{b+1}:
+ *   1. dot(D, N) >= 0 (a silhouette hit, or intersect()'s t == 0 case): R_{b+1} = ray(start_O, D).
+ *   2. Else T = refract(D, N, 1/ior), P = N*(-0.00001f) + new_org, t1 = the FAR root of
+ *      sphere::intersect for (P, T) against sphere i, (-B + sqrt(disc)) / a2, before its min.
+ *   3. !(t1 > 0) (NaN, degenerate tiny spheres): R_{b+1} = ray(start_O, D).
+ *   4. Else Q = P + T*t1, M = normalise(Q - c_i), U = refract(T, -M, ior),
+ *      R_{b+1} = ray(M*0.00001f + Q, U).
+ * A hit with b == D, or with tau == 0 and k == 0, ends the pixel with w * L. A pass through a glass
+ * sphere is one bounce of reflect_depth. A ray that starts inside a sphere meets it at
+ * intersect()'s negative near root, behind its origin, where dot(D, N) < 0: it takes rule 2 there.
+ * Two consequences: the chord P..Q is not tested against other spheres (a sphere that overlaps a
+ * glass sphere's interior is not seen from inside it), and glass casts full shadows (castLightRay
+ * is unchanged). No Fresnel weighting, tint, attenuation or caustics. A scene where no sphere has
+ * tau > 0 renders exactly as with rt_scene_set_materials. The drop-in boundary (object::mat) stays
+ * mirror-only. */
+int rt_scene_set_materials_ex(rt_scene *s, const rt_material_ex *per_sphere, int n);
 
 /* What the last reflective frame of the scene did (a host wait for that frame): the sphere BVH
  * (host build, binary64, rebuilt when the spheres change), the queue length entering every
@@ -596,6 +637,14 @@ int rt_debug_bvh_cast(const rt_sphere *spheres, int n, const rt_ray *rays, int n
                       int *hit_index, float *t, int *any);
 /* reflect(I, N), kernel.cu:1282-1285, in binary32 as the kernels evaluate it (n vectors).        */
 int rt_debug_reflect(const rt_vec3 *I, const rt_vec3 *N, int n, rt_vec3 *out);
+/* refract(I, N, eta) of rt_scene_set_materials_ex, in binary32 as the kernels evaluate it.       */
+int rt_debug_refract(const rt_vec3 *I, const rt_vec3 *N, const float *eta, int n, rt_vec3 *out);
+/* The glass step of rt_scene_set_materials_ex for rays[i] hitting `sphere` with ior[i] (the same
+ * code the kernels run, from sphere::intersect's hit to R_{b+1}): out[i] = R_{b+1}; entered[i] = 1
+ * when the ray passed through the sphere (rule 4), 0 when it leaves undeviated (rules 1 and 3),
+ * -1 when intersect() reports no hit (out[i] = rays[i]).                                          */
+int rt_debug_transmit(const rt_sphere *sphere, const float *ior, const rt_ray *rays, int n,
+                      rt_ray *out, int *entered);
 int rt_debug_occluder_lists_ex(const rt_sphere *spheres, int n, const rt_light *light, int *counts, float *kcaps, int *members, int cap,
                                int *offsets, int *entries_allocated);
 

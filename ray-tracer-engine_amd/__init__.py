@@ -132,6 +132,11 @@ class Material(C.Structure):
     _fields_ = [("reflectivness", C.c_float), ("transperancy", C.c_float), ("roughness", C.c_float)]
 
 
+class MaterialEx(C.Structure):
+    """rt_material_ex: a material with transparency and an index of refraction (16 bytes)."""
+    _fields_ = [("reflectivness", C.c_float), ("transperancy", C.c_float), ("roughness", C.c_float), ("ior", C.c_float)]
+
+
 class ReflectStats(C.Structure):
     _fields_ = [("bvh_build_ms", C.c_double), ("bvh_nodes", C.c_int), ("bvh_depth", C.c_int), ("bvh_leaves", C.c_int),
                 ("depth", C.c_int), ("queue", C.c_int * (RT_MAX_REFLECT_DEPTH + 1)),
@@ -272,6 +277,9 @@ def load_library():
         "rt_debug_sphere_bvh": (ci, [C.POINTER(Sphere), ci, fp, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(ci), C.POINTER(ci)]),
         "rt_debug_bvh_cast": (ci, [C.POINTER(Sphere), ci, C.POINTER(Ray), ci, ci, C.POINTER(ci), fp, C.POINTER(ci)]),
         "rt_debug_reflect": (ci, [C.POINTER(Vec3), C.POINTER(Vec3), ci, C.POINTER(Vec3)]),
+        "rt_scene_set_materials_ex": (ci, [vp, C.POINTER(MaterialEx), ci]),
+        "rt_debug_refract": (ci, [C.POINTER(Vec3), C.POINTER(Vec3), fp, ci, C.POINTER(Vec3)]),
+        "rt_debug_transmit": (ci, [C.POINTER(Sphere), fp, C.POINTER(Ray), ci, C.POINTER(Ray), C.POINTER(ci)]),
         "rt_scene_trace_rays": (ci, [vp, C.POINTER(RayQuery), vp]),
         "rt_scene_primary_rays": (ci, [vp, C.POINTER(FrameDesc), vp, vp]),
     }
@@ -437,6 +445,29 @@ class Scene:
             else:
                 mats[i].reflectivness = float(m)
         _check(self.lib.rt_scene_set_materials(self.handle, mats, n), "rt_scene_set_materials")
+        self.materials = mats
+
+    def set_materials_ex(self, reflectivity=None, transparency=None, ior=None):
+        """One rt_material_ex per sphere: per-sphere arrays of reflectivness k, transperancy tau and ior (a missing array
+        is all 0), or a list of MaterialEx as the first argument; all None (or empty) clears the materials."""
+        if reflectivity is not None and len(reflectivity) > 0 and isinstance(reflectivity[0], MaterialEx):
+            n = len(reflectivity)
+            mats = (MaterialEx * n)(*reflectivity)
+        else:
+            given = [a for a in (reflectivity, transparency, ior) if a is not None]
+            if not given or all(len(a) == 0 for a in given):
+                _check(self.lib.rt_scene_set_materials_ex(self.handle, None, 0), "rt_scene_set_materials_ex")
+                self.materials = None
+                return
+            n = len(given[0])
+            if any(len(a) != n for a in given):
+                raise RtError("set_materials_ex: reflectivity, transparency and ior differ in length")
+            mats = (MaterialEx * n)()
+            for field, a in (("reflectivness", reflectivity), ("transperancy", transparency), ("ior", ior)):
+                if a is not None:
+                    for i, v in enumerate(a):
+                        setattr(mats[i], field, float(v))
+        _check(self.lib.rt_scene_set_materials_ex(self.handle, mats, n), "rt_scene_set_materials_ex")
         self.materials = mats
 
     def set_reflect_timing(self, on: bool):

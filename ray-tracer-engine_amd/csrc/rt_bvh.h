@@ -37,6 +37,7 @@ struct RtReflectDev {              // the passes' uniforms (by value)
     int n;
     const float *k;                // reflectivness per sphere (null: all 0)
     int depth;
+    const float2 *glass;           // (transperancy, ior) per sphere (null: no sphere has transperancy > 0)
 };
 
 // ---------------------------------------------------------------------------
@@ -185,13 +186,29 @@ __device__ __forceinline__ void rf_sky(AuxPtr ax, V3 O, V3 D, float &r, float &g
     b = ax->sky_b[idx];
 }
 
-// The hit point, normal and start_O of castRay's / rayTrace's sphere branch (kernel.cu:1398-1405, 1647)
-__device__ __forceinline__ void rf_hit_frame(V3 O, V3 D, float nt, float4 s, V3 &normal, V3 &start)
+// normalise_inplace (rt_trace.inc) for host and device: the same operations (the host debug entries run them)
+__host__ __device__ __forceinline__ void rf_normalise(V3 &v)
 {
-    const V3 new_org{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
+    const float l = __builtin_sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+    if (l != 0.f) {
+        v.x = v.x / l;
+        v.y = v.y / l;
+        v.z = v.z / l;
+    }
+}
+
+// The hit point, normal and start_O of castRay's / rayTrace's sphere branch (kernel.cu:1398-1405, 1647)
+__host__ __device__ __forceinline__ void rf_hit_frame(V3 O, V3 D, float nt, float4 s, V3 &normal, V3 &start, V3 &new_org)
+{
+    new_org = V3{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
     normal = V3{new_org.x - s.x, new_org.y - s.y, new_org.z - s.z};
-    normalise_inplace(normal);
+    rf_normalise(normal);
     start = V3{normal.x * 0.00001f + new_org.x, normal.y * 0.00001f + new_org.y, normal.z * 0.00001f + new_org.z};
+}
+__host__ __device__ __forceinline__ void rf_hit_frame(V3 O, V3 D, float nt, float4 s, V3 &normal, V3 &start)
+{
+    V3 new_org;
+    rf_hit_frame(O, D, nt, s, normal, start, new_org);
 }
 
 // The direction of the primary ray of band-local pixel `pix` (kernel.cu:1624-1631), as the frame kernel forms it at one

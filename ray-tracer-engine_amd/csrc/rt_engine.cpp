@@ -1329,6 +1329,16 @@ extern "C" int rt_scene_set_materials(rt_scene *s, const rt_material *per_sphere
     return rt_reflect_set_materials(scene_reflect(s), per_sphere, n, s->n_spheres);
 }
 
+extern "C" int rt_scene_set_materials_ex(rt_scene *s, const rt_material_ex *per_sphere, int n)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_materials_ex: null scene");
+        return RT_ERR_INVALID;
+    }
+    // (as rt_scene_set_materials: the next reflective frame uploads after the frames in flight)
+    return rt_reflect_set_materials_ex(scene_reflect(s), per_sphere, n, s->n_spheres);
+}
+
 extern "C" int rt_scene_set_reflect_timing(rt_scene *s, int on)
 {
     if (!s) {

@@ -10,6 +10,9 @@
 //             either adds w * L and ends (k = 0 or b = D) or adds (w * (1-k)) * L and queues R_{b+1} with w * k.
 //             A pixel that ends writes rgba = (c, 1) and its packed word there and then: the pixels that never
 //             entered the queue keep what the frame kernel wrote.
+// Glass (transperancy tau > 0, DESIGN.md "Refraction") is one more kind of continuation: the term is (w * (1-tau)) * L,
+// w becomes w * tau and R_{b+1} is the ray that passed through the sphere (rf_transmit). Both passes are templates on
+// GLASS; the host launches GLASS = true only when some sphere has tau > 0, so mirror-only frames run today's code.
 // The brute-force variant (opts.cull = 0) is the same kernels with the BVH replaced by the whole sphere list.
 //
 // The BVH and the per-ray pieces the ray queries share are in rt_bvh.h.
@@ -39,6 +42,59 @@ __host__ __device__ __forceinline__ void rf_reflect(float ix, float iy, float iz
     rx = ix - (nx * d) * 2.f;
     ry = iy - (ny * d) * 2.f;
     rz = iz - (nz * d) * 2.f;
+}
+
+// refract(I, n, eta) for a normal n that faces against I: c = -dot(I, n) (left to right), q = 1 - (eta*eta) * (1 - c*c),
+// s = sqrt(max(q, 0)) -- a negative radicand is taken as 0, no total internal reflection -- and I*eta + n*(eta*c - s),
+// per component, not renormalised
+__host__ __device__ __forceinline__ void rf_refract(float ix, float iy, float iz, float nx, float ny, float nz, float eta,
+                                                    float &rx, float &ry, float &rz)
+{
+    const float c = -((ix * nx + iy * ny) + iz * nz);
+    const float q = 1.f - (eta * eta) * (1.f - c * c);
+    const float sq = __builtin_sqrtf(q > 0.f ? q : 0.f);
+    const float f = eta * c - sq;
+    rx = ix * eta + nx * f;
+    ry = iy * eta + ny * f;
+    rz = iz * eta + nz * f;
+}
+
+// The far root of sphere::intersect for (P, T) against s: rf_intersect's operations up to (-B + sqrt(disc)) / a2, before
+// its min (from inside, intersect() returns the negative near root)
+__host__ __device__ __forceinline__ float rf_far_root(V3 P, V3 T, float4 s)
+{
+    const float ocx = P.x - s.x, ocy = P.y - s.y, ocz = P.z - s.z;
+    const float h = (T.x * ocx + T.y * ocy) + T.z * ocz;
+    const float B = 2.f * h;
+    const float C = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.w;
+    const float A = (T.x * T.x + T.y * T.y) + T.z * T.z;
+    const float disc = B * B - (4.f * A) * C;
+    const float sq = __builtin_sqrtf(disc);
+    const float a2 = 2.f * ((T.x * T.x + T.y * T.y) + T.z * T.z);
+    return (-B + sq) / a2;
+}
+
+// The glass continuation of a hit on sphere s (DESIGN.md "Refraction"): D = the ray's direction, normal / start /
+// new_org = the hit frame (rf_hit_frame). Writes R_{b+1} and returns 1 when the ray passed through the sphere (rule 4),
+// 0 when it leaves undeviated from start_O (rule 1: dot(D, N) >= 0; rule 3: no positive far root from inside).
+// The chord is not tested against other spheres.
+__host__ __device__ __forceinline__ int rf_transmit(V3 D, V3 normal, V3 start, V3 new_org, float4 s, float ior, V3 &ro,
+                                                    V3 &rd)
+{
+    ro = start;
+    rd = D;
+    if ((D.x * normal.x + D.y * normal.y) + D.z * normal.z >= 0.f) return 0;   // rule 1
+    V3 T;
+    rf_refract(D.x, D.y, D.z, normal.x, normal.y, normal.z, 1.f / ior, T.x, T.y, T.z);
+    const V3 P{normal.x * -0.00001f + new_org.x, normal.y * -0.00001f + new_org.y, normal.z * -0.00001f + new_org.z};
+    const float t1 = rf_far_root(P, T, s);
+    if (!(t1 > 0.f)) return 0;                                                   // rule 3 (NaN included)
+    const V3 Q{P.x + T.x * t1, P.y + T.y * t1, P.z + T.z * t1};
+    V3 M{Q.x - s.x, Q.y - s.y, Q.z - s.z};
+    rf_normalise(M);
+    rf_refract(T.x, T.y, T.z, -M.x, -M.y, -M.z, ior, rd.x, rd.y, rd.z);
+    ro = V3{M.x * 0.00001f + Q.x, M.y * 0.00001f + Q.y, M.z * 0.00001f + Q.z};
+    return 1;
 }
 
 // ---------------------------------------------------------------------------
@@ -106,7 +162,8 @@ __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float
         fc.packed[pix] = rgb_to_int(f2i(cr * 254.f), f2i(cg * 254.f), f2i(cb * 254.f));   // kernel.cu:1682
 }
 
-// The primary pass: every pixel of the band; queues those whose primary hit is reflective.
+// The primary pass: every pixel of the band; queues those whose primary hit is reflective (or, GLASS, transparent).
+template <bool GLASS>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtFrameConsts fc, const RtReflectDev rd,
                                                                        QEntry *q, int *count)
 {
@@ -122,14 +179,27 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
         const V3 O{fc.org_x, fc.org_y, fc.org_z};
         float nt;
         const int hit = rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk);
-        const float k = (hit >= 0 && rd.k) ? rd.k[hit] : 0.f;
+        float k = (hit >= 0 && rd.k) ? rd.k[hit] : 0.f;
+        float2 g = make_float2(0.f, 0.f);                                       // (tau, ior)
+        if (GLASS && hit >= 0) {
+            g = rd.glass[hit];
+            if (g.x > 0.f) k = g.x;                                             // (k > 0 and tau > 0 are never both set)
+        }
         if (k > 0.f) {
-            V3 normal, start;
-            rf_hit_frame(O, D, nt, rd.spheres[hit], normal, start);
+            const float4 s = rd.spheres[hit];
+            V3 normal, start, new_org;
+            rf_hit_frame(O, D, nt, s, normal, start, new_org);
             const float4 L = reinterpret_cast<const float4 *>(fc.rgba)[pix];   // the frame kernel's L for this hit
             const float f = 1.f - k;                                            // (w * (1 - k)) with w = 1
-            e.ox = start.x; e.oy = start.y; e.oz = start.z;
-            rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, e.dx, e.dy, e.dz);
+            if (GLASS && g.x > 0.f) {
+                V3 ro, rdir;
+                rf_transmit(D, normal, start, new_org, s, g.y, ro, rdir);
+                e.ox = ro.x; e.oy = ro.y; e.oz = ro.z;
+                e.dx = rdir.x; e.dy = rdir.y; e.dz = rdir.z;
+            } else {
+                e.ox = start.x; e.oy = start.y; e.oz = start.z;
+                rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, e.dx, e.dy, e.dz);
+            }
             e.w = k;                                                            // w * k with w = 1
             e.cr = f * L.x; e.cg = f * L.y; e.cb = f * L.z;                     // the first term is assigned
             e.pix = pix;
@@ -140,6 +210,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
 }
 
 // Bounce b (1..depth): a fixed grid walks the queue of the previous pass; its length is read here, on the device.
+template <bool GLASS>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFrameConsts fc, const RtReflectDev rd, int b,
                                                                       const QEntry *qin, const int *count_in, QEntry *qout,
                                                                       int *count_out)
@@ -171,14 +242,28 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
                 rf_sky(ax, O, D, sr, sg, sb);
                 cr = cr + e.w * sr; cg = cg + e.w * sg; cb = cb + e.w * sb;
             } else {
-                const float k = rd.k ? rd.k[hit] : 0.f;
+                float k = rd.k ? rd.k[hit] : 0.f;
+                float2 g = make_float2(0.f, 0.f);   // (tau, ior)
+                if (GLASS) {
+                    g = rd.glass[hit];
+                    if (g.x > 0.f) k = g.x;         // (k > 0 and tau > 0 are never both set)
+                }
                 if (k == 0.f || b == rd.depth) {
                     cr = cr + e.w * Lr; cg = cg + e.w * Lg; cb = cb + e.w * Lb;
                 } else {
                     const float f = e.w * (1.f - k);
                     cr = cr + f * Lr; cg = cg + f * Lg; cb = cb + f * Lb;
-                    nx.ox = start.x; nx.oy = start.y; nx.oz = start.z;
-                    rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, nx.dx, nx.dy, nx.dz);
+                    if (GLASS && g.x > 0.f) {
+                        // new_org again from O, D, nt (rf_hit_frame's operations): cheaper than keeping it across rf_shade
+                        const V3 new_org{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
+                        V3 ro, rdir;
+                        rf_transmit(D, normal, start, new_org, rd.spheres[hit], g.y, ro, rdir);
+                        nx.ox = ro.x; nx.oy = ro.y; nx.oz = ro.z;
+                        nx.dx = rdir.x; nx.dy = rdir.y; nx.dz = rdir.z;
+                    } else {
+                        nx.ox = start.x; nx.oy = start.y; nx.oz = start.z;
+                        rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, nx.dx, nx.dy, nx.dz);
+                    }
                     nx.w = e.w * k;
                     nx.cr = cr; nx.cg = cg; nx.cb = cb;
                     nx.pix = e.pix;
@@ -203,6 +288,10 @@ struct RtReflect {
                                           // the frames that may still read it, in rt_reflect_prepare)
     bool k_dirty = false;
     DevArray<float> d_k;
+    std::vector<float> glass;             // (transperancy, ior) per sphere, interleaved; empty = no sphere has tau > 0
+    std::vector<float> glass_dev;         // what d_glass holds (as k_dev)
+    bool glass_dirty = false;
+    DevArray<float2> d_glass;
     RtSphereBvh bvh;                      // the sphere BVH (shared with the ray queries)
     // queues and counters
     DevArray<QEntry> d_q[2];
@@ -356,6 +445,17 @@ void rt_reflect_spheres_changed(RtReflect *r, int n_old, int n_new)
         r->k.clear();
         r->k_dirty = true;
     }
+    if (n_old != n_new && !r->glass.empty()) {
+        r->glass.clear();
+        r->glass_dirty = true;
+    }
+}
+
+// the old entry sets every transperancy to 0
+static void rf_clear_glass(RtReflect *r)
+{
+    if (!r->glass.empty()) r->glass_dirty = true;
+    r->glass.clear();
 }
 
 int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_spheres)
@@ -363,6 +463,7 @@ int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_sp
     if (!m || n == 0) {
         if (!r->k.empty()) r->k_dirty = true;
         r->k.clear();
+        rf_clear_glass(r);
         return RT_OK;
     }
     if (n != n_spheres || n < 0) {
@@ -386,12 +487,72 @@ int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_sp
         r->k.swap(k);
         r->k_dirty = true;
     }
+    rf_clear_glass(r);
+    return RT_OK;
+}
+
+int rt_reflect_set_materials_ex(RtReflect *r, const rt_material_ex *m, int n, int n_spheres)
+{
+    if (!m || n == 0) {
+        if (!r->k.empty()) r->k_dirty = true;
+        r->k.clear();
+        rf_clear_glass(r);
+        return RT_OK;
+    }
+    if (n != n_spheres || n < 0) {
+        rt_set_error("rt_scene_set_materials_ex: %d materials for %d spheres (one per sphere, or NULL / 0)", n, n_spheres);
+        return RT_ERR_INVALID;
+    }
+    bool any_glass = false;
+    for (int i = 0; i < n; ++i) {   // every value first, then what is not implemented: nothing changes on an error
+        const float k = m[i].reflectivness, tau = m[i].transperancy, ior = m[i].ior;
+        if (!(k >= 0.f && k <= 1.f) || !(tau >= 0.f && tau <= 1.f)) {
+            rt_set_error("rt_scene_set_materials_ex: sphere %d: reflectivness %g / transperancy %g is not in [0, 1]", i,
+                         (double)k, (double)tau);
+            return RT_ERR_INVALID;
+        }
+        if (tau > 0.f && !(ior >= 1.f && ior <= 4.f)) {
+            rt_set_error("rt_scene_set_materials_ex: sphere %d: ior %g is not in [1, 4]", i, (double)ior);
+            return RT_ERR_INVALID;
+        }
+        any_glass = any_glass || tau > 0.f;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (m[i].roughness != 0.f) {
+            rt_set_error("rt_scene_set_materials_ex: sphere %d: roughness is not implemented", i);
+            return RT_ERR_UNSUPPORTED;
+        }
+        if (m[i].reflectivness > 0.f && m[i].transperancy > 0.f) {
+            rt_set_error("rt_scene_set_materials_ex: sphere %d: reflectivness and transperancy both > 0 (one continuation "
+                         "per hit: a sphere is a mirror or glass)", i);
+            return RT_ERR_UNSUPPORTED;
+        }
+    }
+    std::vector<float> k((size_t)n);
+    for (int i = 0; i < n; ++i) k[(size_t)i] = m[i].reflectivness;
+    if (k != r->k) {
+        r->k.swap(k);
+        r->k_dirty = true;
+    }
+    std::vector<float> glass;
+    if (any_glass) {
+        glass.resize((size_t)2 * n);
+        for (int i = 0; i < n; ++i) {
+            const float tau = m[i].transperancy;
+            glass[(size_t)2 * i] = tau;
+            glass[(size_t)2 * i + 1] = tau > 0.f ? m[i].ior : 0.f;   // (ignored where tau == 0)
+        }
+    }
+    if (glass != r->glass) {
+        r->glass.swap(glass);
+        r->glass_dirty = true;
+    }
     return RT_OK;
 }
 
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n)
 {
-    return r->k_dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
+    return r->k_dirty || r->glass_dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
 }
 
 // Brings materials and BVH up to date (the caller has waited for every frame that may read them) and makes sure the
@@ -410,6 +571,15 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
             RT_HIP(hipMemcpyAsync(r->d_k.get(), r->k_dev.data(), sizeof(float) * r->k_dev.size(), hipMemcpyHostToDevice, stream));
         }
         r->k_dirty = false;
+    }
+    if (r->glass_dirty) {
+        r->glass_dev = r->glass;
+        if (!r->glass_dev.empty()) {
+            RT_HIP(r->d_glass.reserve(r->glass_dev.size() / 2));
+            RT_HIP(hipMemcpyAsync(r->d_glass.get(), r->glass_dev.data(), sizeof(float) * r->glass_dev.size(),
+                                  hipMemcpyHostToDevice, stream));
+        }
+        r->glass_dirty = false;
     }
     for (DevArray<QEntry> &q : r->d_q) RT_HIP(q.reserve((size_t)npx));
     RT_HIP(r->d_cnt.reserve(RT_MAX_REFLECT_DEPTH + 1));
@@ -458,13 +628,15 @@ int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_sph
     rd.n = n;
     rd.k = r->k_dev.empty() ? nullptr : r->d_k.get();
     rd.depth = depth;
+    rd.glass = r->glass_dev.empty() ? nullptr : r->d_glass.get();
+    const bool glass = rd.glass != nullptr;   // mirror-only frames run the GLASS = false instantiations (today's code)
     const int npx = fc->width * fc->local_rows;
-    hipLaunchKernelGGL(rt_reflect_primary, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
+    hipLaunchKernelGGL(glass ? rt_reflect_primary<true> : rt_reflect_primary<false>, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
                        stream, *fc, rd, r->d_q[0].get(), r->d_cnt.get());
     RT_HIP(hipGetLastError());
     RT_HIP(rt_reflect_mark(r, 2, stream));
     for (int b = 1; b <= depth; ++b) {
-        hipLaunchKernelGGL(rt_reflect_bounce, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, rd, b,
+        hipLaunchKernelGGL(glass ? rt_reflect_bounce<true> : rt_reflect_bounce<false>, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, rd, b,
                            r->d_q[(b - 1) & 1].get(), r->d_cnt.get() + (b - 1), r->d_q[b & 1].get(), r->d_cnt.get() + b);
         RT_HIP(hipGetLastError());
         RT_HIP(rt_reflect_mark(r, 2 + b, stream));
@@ -585,5 +757,42 @@ extern "C" int rt_debug_reflect(const rt_vec3 *I, const rt_vec3 *N, int n, rt_ve
         return RT_ERR_INVALID;
     }
     for (int i = 0; i < n; ++i) rf_reflect(I[i].x, I[i].y, I[i].z, N[i].x, N[i].y, N[i].z, out[i].x, out[i].y, out[i].z);
+    return RT_OK;
+}
+
+extern "C" int rt_debug_refract(const rt_vec3 *I, const rt_vec3 *N, const float *eta, int n, rt_vec3 *out)
+{
+    if (!I || !N || !eta || !out || n < 0) {
+        rt_set_error("rt_debug_refract: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i)
+        rf_refract(I[i].x, I[i].y, I[i].z, N[i].x, N[i].y, N[i].z, eta[i], out[i].x, out[i].y, out[i].z);
+    return RT_OK;
+}
+
+extern "C" int rt_debug_transmit(const rt_sphere *sphere, const float *ior, const rt_ray *rays, int n, rt_ray *out,
+                                 int *entered)
+{
+    if (!sphere || !ior || !rays || !out || !entered || n < 0) {
+        rt_set_error("rt_debug_transmit: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    std::vector<float4> v;
+    pack_list(sphere, 1, v);
+    for (int i = 0; i < n; ++i) {
+        const V3 O{rays[i].Org.x, rays[i].Org.y, rays[i].Org.z}, D{rays[i].Dir.x, rays[i].Dir.y, rays[i].Dir.z};
+        out[i] = rays[i];
+        float t;
+        if (!rf_intersect(O.x, O.y, O.z, D.x, D.y, D.z, v[0], t)) {
+            entered[i] = -1;
+            continue;
+        }
+        V3 normal, start, new_org, ro, rd;
+        rf_hit_frame(O, D, t, v[0], normal, start, new_org);
+        entered[i] = rf_transmit(D, normal, start, new_org, v[0], ior[i], ro, rd);
+        out[i].Org.x = ro.x; out[i].Org.y = ro.y; out[i].Org.z = ro.z;
+        out[i].Dir.x = rd.x; out[i].Dir.y = rd.y; out[i].Dir.z = rd.z;
+    }
     return RT_OK;
 }
