@@ -514,8 +514,9 @@ typedef struct rt_frame_graph rt_frame_graph;
 rt_frame_graph *rt_graph_capture(rt_scene *s, const rt_frame_desc *fd, int passes,
                                  uint32_t *host_pixels /* pinned, may be NULL */, void *stream);
 /* Replays the frame. If the scene's tables were rewritten since the graph was built (another
- * sphere list, lights, textures, or a direct render at another resolution) the graph is
- * rebuilt first -- it never replays against tables it was not built for.                     */
+ * sphere list, other lights -- also when nothing rendered since rt_scene_set_lights; the same
+ * lights set again do not count --, textures, or a direct render at another resolution) the
+ * graph is rebuilt first -- it never replays against tables it was not built for.             */
 int rt_graph_launch(rt_frame_graph *g, void *stream);
 /* A camera move (kernel.cu:1716-1759 moves `cam` every frame): the kernel nodes' by-value
  * uniforms are replaced with hipGraphExecKernelNodeSetParams and the eye-cone table is rebuilt

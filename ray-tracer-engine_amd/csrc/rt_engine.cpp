@@ -817,8 +817,12 @@ extern "C" int rt_scene_set_lights(rt_scene *s, const rt_light *lights, int n)
         rt_set_error("rt_scene_set_lights: light_size %d > RT_MAX_LIGHTS %d", n, RT_MAX_LIGHTS);
         return RT_ERR_CAPACITY;
     }
+    // a frame graph holds the lights (its uniforms, RtFrameAux, the tables keyed on them): other lights rebuild it. The
+    // drop-in boundary sets the same lights every frame, which must not.
+    const bool same = n == s->n_lights && (n == 0 || memcmp(s->lights, lights, sizeof(rt_light) * (size_t)n) == 0);
     for (int i = 0; i < n; ++i) s->lights[i] = lights[i];
     s->n_lights = n;
+    if (!same) s->epoch++;
     return RT_OK;
 }
 

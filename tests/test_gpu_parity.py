@@ -340,8 +340,8 @@ def test_graph_replay_equals_direct_launch(rt, gpu, passes):
 def test_graph_never_replays_against_tables_of_another_frame(rt, gpu):
     """A graph built for camera A keeps rendering camera A after direct renders of the same
     scene with camera B (which builds other eye cones), at another resolution (other raygen
-    tables), with a light moved (other column tables: the graph then follows the scene) and
-    with another sphere list."""
+    tables), with a light moved (other column tables: the graph then follows the scene, from
+    the first replay after set_lights on) and with another sphere list."""
     import torch
     lib = rt.load_library()
     w, h, n = 160, 90, 1024
@@ -374,9 +374,11 @@ def test_graph_never_replays_against_tables_of_another_frame(rt, gpu):
     lights = rt.default_lights()
     lights[0].pos.x = 25.0
     scene.set_lights(lights, 3)
+    got_first = replay()                                 # directly after set_lights: no render in between
     _, want_l, _ = _render(scene, w, h, cam=cam_a)       # rebuilds the light tables in place
     got = replay()
     assert np.array_equal(got, want_l) and not np.array_equal(got, want_a)
+    assert np.array_equal(got_first, want_l)
     sph = rt.generate_spheres(n, 7)
     scene.set_spheres(sph, n)
     got = replay()
