@@ -257,8 +257,10 @@ void rt_build_light_columns(const float4 *tab, int n, const float u_f[3], float4
 // slope kcap around u from a ball around S: a short list per (S, light), built here once per scene, of which a tile
 // then only has to cull the members against its own, much thinner beam (rt_trace.inc: build_list_cand) instead of
 // walking the light's column blocks. Conservative by the same member test the kernel applies (beam_member_test) with
-// the ball of S (radius R_S 1.001 + 1e-3: the starts lie 1e-5 above the surface, give or take the rounding of the hit
-// point) as the ray origins; kcap = the slope every group on S uses (kbeam, rt_sphere_beam_slope below) plus 0.1 %, or,
+// the ball of S (radius R_S 1.001 + 1e-3) as the ray origins. Most starts lie in it (1e-5 above the surface), but not
+// all: a start is a float hit point, and at a grazing primary ray the rounding of the discriminant moves it along the ray
+// by up to ~1e-3 of the camera's distance (tests/test_margins_cpu.py). So the kernel CHECKS that every start of a group
+// lies in this ball before it takes the list or kbeam (rt_trace.inc, at the group's formation; tests/test_margins_gpu.py); kcap = the slope every group on S uses (kbeam, rt_sphere_beam_slope below) plus 0.1 %, or,
 // for a sphere without one, 1.15 x the largest slope the kernel's own bound yields at 14 points of S; the kernel checks
 // its beam's slope against kcap before using the list. Built on the device (rt_occluder_lists_kernel); the host builder
 // is the same member test in a plain loop, for the tests.

@@ -1722,6 +1722,19 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 g_az = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, start.z), glead));
                 const float ox = start.x - g_ax, oy = start.y - g_ay, oz = start.z - g_az;
                 g_r2 = uniform(wave_max(inc ? __builtin_fmaf(ox, ox, __builtin_fmaf(oy, oy, oz * oz)) : 0.f));
+                // The sphere's occluder lists and its kbeam (rt_tables.hip) hold for starts inside the ball of radius
+                // R 1.001 + 1e-3 around its centre. A start is a float hit point: at a grazing primary ray the rounding of
+                // the discriminant moves it along the ray by up to ~1e-3 of the camera's distance, far outside that ball
+                // (tests/test_margins_cpu.py). So the ball is checked, every start of the group against it, in float
+                // with 1e-5 relative to spare (|start - c|^2 and the radius carry a few ulp each); a group that has a
+                // start outside takes neither the list nor kbeam and culls as a group on a plane does.
+                if (g_sphere >= 0) {
+                    const float4 sc = spheres[g_sphere];
+                    const float cx = start.x - sc.x, cy = start.y - sc.y, cz = start.z - sc.z;
+                    const float ball = __builtin_amdgcn_sqrtf(sc.w) * 1.001f + 1.0e-3f;
+                    const float far2 = uniform(wave_max(inc ? __builtin_fmaf(cx, cx, __builtin_fmaf(cy, cy, cz * cz)) : 0.f));
+                    if (!(far2 <= ball * ball * 0.99999f)) g_sphere = -1;   // (also for a NaN)
+                }
             }
             for (int li = 0; li < fc.n_lights; ++li) {
                 const RtLightDev L = ax->lights[li];

@@ -1,5 +1,7 @@
 """Shared test inputs: the reference's default scene at the BASELINE.json
 configs, as inputs for both the HIP path and the oracle."""
+import ctypes as C
+
 import numpy as np
 
 
@@ -94,3 +96,76 @@ def mixed_oracle_render(inp, oracle, width, height, **kw):
     return oracle.render(inp.spheres, inp.n, inp.tex, inp.sky, inp.sky_box, inp.lights, inp.n_lights, inp.cam,
                          width, height, inp.aspect, cubes=inp.cubes, n_cubes=inp.n_cubes, planes=inp.planes,
                          n_planes=inp.n_planes, nthreads=kw.get("nthreads", 8))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+class Scn:
+    """Free-form scene: explicit spheres (x,y,z,ctor_r), lights, camera, textures."""
+
+    def __init__(self, rt, spheres, lights=None, cam=None, tex=None, sky=None, sky_size=10000.0, aspect=None,
+                 planes=(), cubes=()):
+        self.rt = rt
+        lib = rt.load_library()
+        self.n = len(spheres)
+        self.spheres = (rt.Sphere * max(self.n, 1))()
+        for i, (x, y, z, r) in enumerate(spheres):
+            lib.rt_sphere_init(C.byref(self.spheres[i]), float(x), float(y), float(z), float(r))
+        self.n_planes, self.n_cubes = len(planes), len(cubes)
+        self.planes = (rt.Plane * max(self.n_planes, 1))()
+        for i, v in enumerate(planes):
+            lib.rt_plane_init(C.byref(self.planes[i]), *[float(x) for x in v])
+        self.cubes = (rt.Cube * max(self.n_cubes, 1))()
+        for i, v in enumerate(cubes):
+            lib.rt_cube_init(C.byref(self.cubes[i]), *[float(x) for x in v])
+        if lights is None:
+            self.lights, self.n_lights = rt.default_lights(), 3
+        else:
+            self.n_lights = len(lights)
+            self.lights = (rt.Light * max(self.n_lights, 1))()
+            for i, (p, size, r, g, b) in enumerate(lights):
+                self.lights[i] = rt.Light(rt.Vec3(*[float(v) for v in p]), size, r, g, b)
+        self.cam = cam if cam is not None else rt.default_camera()
+        self.tex = tex if tex is not None else rt.synth_texture(0)
+        self.sky = sky if sky is not None else rt.synth_texture(1)
+        self.sky_box = rt.sky_sphere(sky_size)
+        self.aspect = rt.default_aspect() if aspect is None else aspect
+
+    def scene(self):
+        s = self.rt.Scene()
+        s.set_spheres(self.spheres, self.n)
+        s.set_texture(self.tex)
+        s.set_sky(self.sky_box, self.sky)
+        s.set_lights(self.lights, self.n_lights)
+        if getattr(self, "n_planes", 0):
+            s.set_planes(self.planes, self.n_planes)
+        if getattr(self, "n_cubes", 0):
+            s.set_cubes(self.cubes, self.n_cubes)
+        return s
+
+    def check(self, w, h, tiles=(8,), spp=1, nthreads=16):
+        import oracle_py
+        import torch
+        acc = None
+        lib = self.rt.load_library()
+        for k in range(spp):
+            ox, oy = C.c_double(), C.c_double()
+            assert lib.rt_sample_offset(k, spp, C.byref(ox), C.byref(oy)) == 0
+            rgba, packed, cnt = oracle_py.render(self.spheres, self.n, self.tex, self.sky, self.sky_box, self.lights,
+                                                 self.n_lights, self.cam, w, h, self.aspect,
+                                                 off=(ox.value, oy.value), nthreads=nthreads,
+                                                 cubes=getattr(self, "cubes", None), n_cubes=getattr(self, "n_cubes", 0),
+                                                 planes=getattr(self, "planes", None), n_planes=getattr(self, "n_planes", 0))
+            acc = rgba if acc is None else (acc + rgba).astype(np.float32)
+        sc = self.scene()
+        for tile in tiles:
+            for cull in (True, False):
+                out = sc.render(w, h, cull=cull, tile=tile, spp=spp, cam=self.cam, aspect=self.aspect)
+                torch.cuda.synchronize()
+                got = out["rgba"].cpu().numpy()
+                assert np.array_equal(_bits(got), _bits(acc)), (tile, cull, int((_bits(got) != _bits(acc)).any(axis=2).sum()))
+                if spp == 1:
+                    assert np.array_equal(out["packed"].cpu().numpy().view(np.uint32), packed), (tile, cull)
+        return cnt
