@@ -429,6 +429,26 @@ typedef struct rt_frame_desc {
     rt_camera cam;
     uint32_t *pixels;        /* device, band-local (row y0 first); may be NULL        */
     rt_launch_opts opts;     /* rgba / band / spp / cull / stats                       */
+    /* G-buffer outputs, appended after `opts` (rt_launch_opts keeps its layout): per-pixel
+       guides of the frame's own primary ray, written by the frame kernel itself. Each is NULL (what a shorter struct_size reads as: the frame exactly as without
+       these fields) or a device buffer in the row layout of `pixels` / `rgba` (band-local, compact rows
+       under interleave_*). Any subset may be set; unset buffers are not touched; a set one is always
+       overwritten (also with `accumulate`). On a hit they hold castRay's values, as rt_hit does for the
+       pixel's ray from rt_scene_primary_rays; on a miss (sky) the values in brackets.                   */
+    float *aov_depth;        /* float: castRay's nt -- negative for a sphere reached from inside     [+inf] */
+    float *aov_normal;       /* float4, 16-byte aligned: castRay's normal (x, y, z, 0) -- a plane's as
+                                stored, a triangle's interpolated when the mesh has normals       [0, 0, 0, 0] */
+    int *aov_id;             /* int2, 8-byte aligned: (kind, index) as rt_hit -- RT_HIT_*, the list position,
+                                for a triangle its position in the mesh's triangle array          [-1, -1] */
+    float *aov_albedo;       /* float4, 16-byte aligned: the texel the frame multiplies the light sum by,
+                                (r, g, b, 1) with the frame's clamp          [the sky texel (r, g, b, 1) = rgba] */
+    /* The guides describe the pixel centre's primary ray; with reflect_depth > 0 they are those of the
+       primary hit. A frame that sets any of them: one sample (spp <= 1, sample_total <= 1), tile 0 or 8, no
+       stats, profile or force_slow_path (RT_ERR_UNSUPPORTED otherwise); `fast` is ignored (the launch is
+       exact); cull 0 and 1, every kind of primitive, bands, interleave_*, packed24 and accumulate work.
+       A misaligned pointer: RT_ERR_INVALID. Either refusal writes nothing. The drop-in rt_launch_raytrace_ex has
+       none (its rt_launch_opts does not carry them); rt_multi_render refuses them (RT_ERR_UNSUPPORTED) and
+       rt_graph_capture returns NULL with the field's name in rt_last_error().                              */
 } rt_frame_desc;
 
 /* fd->struct_size and fd->opts.struct_size are honoured: a caller built against an older, shorter

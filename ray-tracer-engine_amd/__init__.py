@@ -127,6 +127,11 @@ class LaunchOpts(C.Structure):
                 ("packed24", C.c_void_p), ("table_lds", C.c_int), ("fast", C.c_int), ("reflect_depth", C.c_int)]
 
 
+# G-buffer outputs (rt_frame_desc.aov_*): name -> (dtype name, components per pixel)
+AOV_NAMES = ("depth", "normal", "id", "albedo")
+_AOV_LAYOUT = {"depth": ("float32", 1), "normal": ("float32", 4), "id": ("int32", 2), "albedo": ("float32", 4)}
+
+
 class Material(C.Structure):
     """rt_material (material, kernel.cu:213-224): only reflectivness is implemented."""
     _fields_ = [("reflectivness", C.c_float), ("transperancy", C.c_float), ("roughness", C.c_float)]
@@ -163,7 +168,8 @@ class RayQuery(C.Structure):
 
 class FrameDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
-                ("aspect", C.c_float), ("cam", Camera), ("pixels", C.c_void_p), ("opts", LaunchOpts)]
+                ("aspect", C.c_float), ("cam", Camera), ("pixels", C.c_void_p), ("opts", LaunchOpts),
+                ("aov_depth", C.c_void_p), ("aov_normal", C.c_void_p), ("aov_id", C.c_void_p), ("aov_albedo", C.c_void_p)]
 
 
 _lib = None
@@ -498,7 +504,7 @@ class Scene:
     def frame_desc(self, width, height, *, pixels=0, rgba=0, cam=None, aspect=None, y0=0, y1=0, spp=1,
                    sample_base=0, sample_total=0, accumulate=False, resolve=0, cull=True, tile=0,
                    stats=0, force_slow=False, profile=False, interleave=None, packed24=0, table_lds=False, fast=False,
-                   reflect_depth=0) -> FrameDesc:
+                   reflect_depth=0, aov_depth=0, aov_normal=0, aov_id=0, aov_albedo=0) -> FrameDesc:
         fd = FrameDesc()
         fd.struct_size = C.sizeof(FrameDesc)
         fd.width, fd.height = width, height
@@ -523,14 +529,23 @@ class Scene:
         o.table_lds = 1 if table_lds else 0
         o.fast = 1 if fast else 0
         o.reflect_depth = reflect_depth
+        fd.aov_depth, fd.aov_normal, fd.aov_id, fd.aov_albedo = aov_depth, aov_normal, aov_id, aov_albedo
         return fd
 
     def render_raw(self, fd: FrameDesc, stream=0):
         _check(self.lib.rt_scene_render(self.handle, C.byref(fd), stream), "rt_scene_render")
 
-    def render(self, width, height, *, y0=0, y1=0, want_rgba=True, want_stats=False, want_packed24=False, stream=None, **kw):
+    def render(self, width, height, *, y0=0, y1=0, want_rgba=True, want_stats=False, want_packed24=False, stream=None,
+               aov=(), **kw):
         """Render rows [y0,y1) into fresh torch CUDA tensors and return
-        {'packed': int32 [rows, W], 'rgba': float32 [rows, W, 4], 'stats': dict}."""
+        {'packed': int32 [rows, W], 'rgba': float32 [rows, W, 4], 'stats': dict}. `aov`: names out of AOV_NAMES
+        ("depth", "normal", "id", "albedo"); out['aov'] then maps each to its G-buffer of the frame's primary rays:
+        depth float32 [rows, W], normal float32 [rows, W, 4], id int32 [rows, W, 2] (kind, index), albedo float32
+        [rows, W, 4] (rt_frame_desc.aov_*)."""
+        aov = (aov,) if isinstance(aov, str) else tuple(aov or ())
+        for name in aov:
+            if name not in _AOV_LAYOUT:
+                raise RtError(f"unknown G-buffer output {name!r} (one of {AOV_NAMES})")
         import torch
         if not torch.cuda.is_available():
             raise RtError("no GPU visible: the ray-tracing path has no CPU fallback")
@@ -543,11 +558,19 @@ class Scene:
         stats = torch.zeros(RT_STATS_COUNT, dtype=torch.int64, device="cuda") if want_stats else None
         st = torch.cuda.current_stream() if stream is None else stream
         p24 = torch.zeros((rows, width * 3 // 4), dtype=torch.int32, device="cuda") if want_packed24 else None
+        aovs = {}
+        for name in aov:
+            dt, comps = _AOV_LAYOUT[name]
+            shape = (rows, width) if comps == 1 else (rows, width, comps)
+            aovs[name] = torch.empty(shape, dtype=getattr(torch, dt), device="cuda")
         fd = self.frame_desc(width, height, pixels=packed.data_ptr(), rgba=rgba.data_ptr() if want_rgba else 0,
                              y0=y0, y1=y1, stats=stats.data_ptr() if want_stats else 0,
-                             packed24=p24.data_ptr() if want_packed24 else 0, **kw)
+                             packed24=p24.data_ptr() if want_packed24 else 0,
+                             **{f"aov_{k}": v.data_ptr() for k, v in aovs.items()}, **kw)
         self.render_raw(fd, st.cuda_stream)
         out = {"packed": packed, "rgba": rgba}
+        if aov:
+            out["aov"] = aovs
         if want_packed24:
             out["packed24"] = p24     # [rows, 3*width/4] int32: bytes B,G,R per pixel (rt_launch_opts.packed24)
         if want_stats:

@@ -243,4 +243,11 @@ struct RtFrameConsts {
     // null. Scheduling only: every tile is rendered exactly once, by the same instructions.
     const unsigned *tile_perm;
     unsigned *tile_cost;
+
+    // G-buffer outputs (rt_frame_desc.aov_*; MODE 5 of the frame kernel only), band-local like `rgba`, may be null:
+    // read from the kernel-argument segment where they are stored, after the primary hit's texel fetch
+    float *aov_depth;           // float per pixel
+    float *aov_normal;          // float4 per pixel
+    int *aov_id;                // int2 per pixel
+    float *aov_albedo;          // float4 per pixel
 };

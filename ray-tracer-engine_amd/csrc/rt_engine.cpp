@@ -1032,8 +1032,8 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
             const int b = o.interleave_rows > 0 ? o.interleave_rows : 16;
             owns_rows = b > 0 && (long long)o.interleave_index * b < (y1 - y0);
         }
-        if (owns_rows && !fd->pixels && !o.rgba && !o.packed24) {
-            rt_set_error("rt_scene_render: no output buffer (pixels, opts.rgba and opts.packed24 are all null)");
+        if (owns_rows && !fd->pixels && !o.rgba && !o.packed24 && !rt_fd_aov_field(fd)) {
+            rt_set_error("rt_scene_render: no output buffer (pixels, opts.rgba, opts.packed24 and aov_* are all null)");
             return RT_ERR_INVALID;
         }
     }
@@ -1124,6 +1124,10 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
         return RT_ERR_INVALID;
     }
     fc->stats = (unsigned long long *)o.stats;
+    fc->aov_depth = fd->aov_depth;
+    fc->aov_normal = fd->aov_normal;
+    fc->aov_id = fd->aov_id;
+    fc->aov_albedo = fd->aov_albedo;
     return RT_OK;
 }
 
@@ -1162,6 +1166,9 @@ int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelC
         rt_set_error("rt_scene_render: stats and force_slow_path exclude each other");
         return RT_ERR_UNSUPPORTED;
     }
+    // the G-buffer kernel: the product kernel plus its stores (aov_supported has refused what it does not cover;
+    // `fast` is ignored, as for reflective frames)
+    if (rt_fd_aov_field(fd)) kc->mode = 5;
     return RT_OK;
 }
 
@@ -1285,6 +1292,47 @@ void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out)
     out->opts.struct_size = (uint32_t)sizeof out->opts;
 }
 
+const char *rt_fd_aov_field(const rt_frame_desc *fd)
+{
+    if (fd->aov_depth) return "aov_depth";
+    if (fd->aov_normal) return "aov_normal";
+    if (fd->aov_id) return "aov_id";
+    if (fd->aov_albedo) return "aov_albedo";
+    return nullptr;
+}
+
+const char *rt_frame_aov_field(const rt_frame_desc *fd)
+{
+    if (!fd) return nullptr;
+    rt_frame_desc f;
+    normalise_frame_desc(fd, &f);
+    return rt_fd_aov_field(&f);
+}
+
+// What a frame with G-buffer outputs (fd->aov_*) does not support; RT_OK when the frame may run (or sets none).
+static int aov_supported(const rt_frame_desc *fd)
+{
+    const rt_launch_opts &o = fd->opts;
+    const char *field = rt_fd_aov_field(fd);
+    if (!field) return RT_OK;
+    if (((uintptr_t)fd->aov_depth & 3u) || ((uintptr_t)fd->aov_normal & 15u) || ((uintptr_t)fd->aov_id & 7u) ||
+        ((uintptr_t)fd->aov_albedo & 15u)) {
+        rt_set_error("rt_scene_render: aov_normal and aov_albedo must be 16-byte aligned, aov_id 8-byte, aov_depth 4-byte");
+        return RT_ERR_INVALID;
+    }
+    const char *why = nullptr;
+    if (o.spp > 1 || o.sample_total > 1) why = "more than one sample per pixel";
+    else if (o.tile != 0 && o.tile != 8) why = "a tile other than 8";
+    else if (o.stats) why = "stats";
+    else if (o.profile) why = "profile";
+    else if (o.force_slow_path) why = "force_slow_path";
+    if (why) {
+        rt_set_error("rt_scene_render: %s (G-buffer outputs) does not support %s (one sample, the product kernel)", field, why);
+        return RT_ERR_UNSUPPORTED;
+    }
+    return RT_OK;
+}
+
 int rt_frame_reflect_depth(const rt_frame_desc *fd)
 {
     if (!fd) return 0;
@@ -1395,6 +1443,10 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     const int reflect_depth = fd->opts.reflect_depth;
     if (reflect_depth != 0) {
         const int rc = reflect_supported(s, fd);
+        if (rc != RT_OK) return rc;
+    }
+    {
+        const int rc = aov_supported(fd);
         if (rc != RT_OK) return rc;
     }
     {
@@ -1549,6 +1601,7 @@ extern "C" int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd_in, rt
     o.spp = 1; o.sample_base = 0; o.sample_total = 0; o.accumulate = 0; o.reflect_depth = 0;
     o.interleave_count = 0; o.interleave_index = 0; o.interleave_rows = 0;
     o.rgba = nullptr; o.packed24 = nullptr; o.stats = nullptr;
+    fd.aov_depth = nullptr; fd.aov_normal = nullptr; fd.aov_id = nullptr; fd.aov_albedo = nullptr;
     fd.pixels = reinterpret_cast<uint32_t *>(rays_dev);
     if (stream_capturing(stream)) {
         rt_set_error("rt_scene_primary_rays: the stream is being captured");

@@ -238,6 +238,10 @@ extern "C" rt_frame_graph *rt_graph_capture(rt_scene *s, const rt_frame_desc *fd
         rt_set_error("rt_graph_capture: reflect_depth > 0 is not recorded into graphs (RT_ERR_UNSUPPORTED)");
         return nullptr;
     }
+    if (const char *aov = rt_frame_aov_field(fd)) {
+        rt_set_error("rt_graph_capture: %s (G-buffer outputs) is not recorded into graphs (RT_ERR_UNSUPPORTED)", aov);
+        return nullptr;
+    }
     rt_frame_graph *g = new rt_frame_graph();
     g->scene = s;
     normalise_frame_desc(fd, &g->fd);   // (a caller's shorter struct ends before the newer fields)

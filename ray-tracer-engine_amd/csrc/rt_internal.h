@@ -144,5 +144,9 @@ int rt_query_launch_primary(const RtFrameConsts *fc, rt_ray *rays, hipStream_t s
 
 // opts.reflect_depth of a frame description, honouring the struct sizes (0 where the caller's structs end before it)
 int rt_frame_reflect_depth(const rt_frame_desc *fd);
+// the first G-buffer output (aov_*) a frame sets, by field name, or null: of a frame description in this build's
+// layout, and of a caller's (honouring its struct sizes)
+const char *rt_fd_aov_field(const rt_frame_desc *fd);
+const char *rt_frame_aov_field(const rt_frame_desc *fd);
 // a caller's frame description in this build's layout (what its struct_size fields do not cover reads as 0)
 void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out);

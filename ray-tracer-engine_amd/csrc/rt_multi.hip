@@ -406,6 +406,10 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
         rt_set_error("rt_multi_render: reflect_depth > 0 is not supported across devices");
         return RT_ERR_UNSUPPORTED;
     }
+    if (const char *aov = rt_frame_aov_field(fd)) {
+        rt_set_error("rt_multi_render: %s (G-buffer outputs) is not supported across devices", aov);
+        return RT_ERR_UNSUPPORTED;
+    }
     const int w = fd->width, h = fd->height, n = m->n;
     int y0 = fd->opts.y0, y1 = fd->opts.y1;
     if (y0 == 0 && y1 == 0) y1 = h;

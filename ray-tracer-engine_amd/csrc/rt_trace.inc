@@ -1230,7 +1230,8 @@ __device__ __forceinline__ PreSure<N> presure_test(V3 o, const V3 (&dq)[N], floa
 // ---------------------------------------------------------------------------
 // MODE: 0 = product kernel, 1 = work counters, 2 = every exactness-preserving shortcut off
 // (rt_launch_opts.force_slow_path: tests), 3 = per-phase cycle stamps (s_memtime; RT_TUNING
-// builds only, run time never quoted).
+// builds only, run time never quoted), 4 = opt-in approximate arithmetic (rt_launch_opts.fast),
+// 5 = the product kernel plus the G-buffer stores (rt_frame_desc.aov_*; one sample, default tile).
 // FEAT: 0 = spheres only (the reference's default scene and every BASELINE config), 1 = with
 // the cube / plane branches of castRay and castLightRay, 2 = with those and the triangle mesh.
 // Each is its own instantiation so that the sphere-only kernel carries neither the code nor
@@ -1244,6 +1245,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
     constexpr int STATS = (MODE == 1) ? 1 : (MODE == 3) ? 2 : 0;
     constexpr bool force_slow = (MODE == 2);
     constexpr bool FAST = (MODE == 4);    // rt_launch_opts.fast: approximate arithmetic, never the default
+    constexpr bool AOV = (MODE == 5);     // rt_frame_desc.aov_*: MODE 0 plus the G-buffer stores after the texel fetch
     constexpr bool MESH = (FEAT == 2);
     constexpr bool PRIMS = (FEAT >= 1);   // cubes and planes may be present
     // the culling kernels take every exactness-preserving shortcut (lean normalise/sqrt, fast
@@ -1431,6 +1433,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         float hcx = 0.f, hcy = 0.f, hcz = 0.f;   // centre of the closest sphere
         int hkind = 1;                           // 0 triangle, 1 sphere, 2 plane, 3 cube (kernel.cu:1376)
         int htri = 0;
+        int hprim = 0;                           // list position of the closest plane or cube (AOV only)
         if (MESH) {
             // triangles through the flat list of leaf boxes, kernel.cu:1293-1328 (before
             // the spheres, as there): a lane tests a leaf's triangles iff its ray hits the box
@@ -1533,6 +1536,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     nt = t;
                     hkind = 3;
                     hcx = c.cx; hcy = c.cy; hcz = c.cz;
+                    if (AOV) hprim = i;
                 }
             }
         }
@@ -1543,6 +1547,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 nt = t;
                 hkind = 2;
                 hcx = p.nx; hcy = p.ny; hcz = p.nz;
+                if (AOV) hprim = i;
             }
         }
         phase(2);
@@ -1671,6 +1676,37 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             fr = ax->sky_r[sky_idx];
             fg = ax->sky_g[sky_idx];
             fb = ax->sky_b[sky_idx];
+        }
+        if (AOV) {
+            // ================= G-buffer (rt_frame_desc.aov_*, DESIGN.md 6e) =================
+            // Every value is live here and nothing new is held across the light loop below, whose register peak is
+            // what the budget is cut to: the output pointers come from the kernel-argument segment at this point,
+            // and the pixel's place is formed again as the write-back forms it.
+            FcPtr ka = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ka));
+            float *const o_depth = ka->aov_depth, *const o_normal = ka->aov_normal, *const o_albedo = ka->aov_albedo;
+            int *const o_id = ka->aov_id;
+            unsigned a_x = blockIdx.x, a_y = blockIdx.y;
+            const unsigned a_tiles_x = (unsigned)(ka->width + TW - 1) / (unsigned)TW;
+            if (ka->tile_perm) {
+                const unsigned p = ka->tile_perm[blockIdx.y * a_tiles_x + blockIdx.x];
+                a_x = p & 0xffffu;
+                a_y = p >> 16;
+            }
+            const size_t o = (size_t)((unsigned)((a_y + wave) * TH + lane / TW) * (unsigned)ka->width + (unsigned)(a_x * TW + lane % TW));
+            if (valid) {
+                if (o_depth) o_depth[o] = nt;   // +inf on a miss
+                if (o_normal)
+                    reinterpret_cast<float4 *>(o_normal)[o] = hit ? make_float4(normal.x, normal.y, normal.z, 0.f)
+                                                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (o_id) {
+                    int idx = -1;
+                    if (hit) idx = (MESH && hkind == 0) ? ax->tri_idx[htri] : (PRIMS && hkind >= 2) ? hprim : holder;
+                    reinterpret_cast<int2 *>(o_id)[o] = make_int2(hit ? hkind : -1, idx);
+                }
+                if (o_albedo)
+                    reinterpret_cast<float4 *>(o_albedo)[o] = hit ? make_float4(tr, tg, tb, 1.f) : make_float4(fr, fg, fb, 1.f);
+            }
         }
         if (hit_m != 0 && !RT_ABL(16)) {
             // A tile that straddles a silhouette sees several spheres at different
@@ -2325,6 +2361,7 @@ static constexpr bool trace_exists()
     if (TW != 8 || FEAT != 0 || (MODE != 0 && MODE != 1) || (MULTI && MODE != 0)) return false;
 #endif
     if (MODE == 4) return TW == 8 && CULL && FEAT < 2;   // fast mode: the product configuration only
+    if (MODE == 5) return TW == 8 && !MULTI;             // G-buffer: the one-sample kernels of the default tile
     if (TW != 8 && FEAT >= 1 && MODE != 0) return false;
 #ifndef RT_TUNING
     if (MODE == 3) return false;
@@ -2359,6 +2396,7 @@ static RtTraceFn trace_fn_mode_feat(int mode, int feat)
     case 2: return trace_fn_feat<TW, CULL, MULTI, 2>(feat);
     case 3: return trace_fn_feat<TW, CULL, MULTI, 3>(feat);
     case 4: return trace_fn_feat<TW, CULL, MULTI, 4>(feat);
+    case 5: return trace_fn_feat<TW, CULL, MULTI, 5>(feat);
     default: return nullptr;
     }
 }
