@@ -516,6 +516,64 @@ int rt_scene_trace_rays(rt_scene *s, const rt_ray_query *q, void *stream);
  * needs (texture, sky). */
 int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd, rt_ray *rays_dev, void *stream);
 
+/* ------------------------------------------------------------------ *
+ * G-buffer-guided denoiser: an edge-avoiding a-trous    *
+ * wavelet filter over a rendered frame, steered by the frame's guides. *
+ * ------------------------------------------------------------------ */
+#define RT_DENOISE_MAX_ITERATIONS 6
+#define RT_DENOISE_MAX_NORMAL_SHIFT 8
+#define RT_DENOISE_MAX_SIZE 32768   /* width and height */
+typedef struct rt_denoise_desc {
+    uint32_t struct_size;    /* sizeof(rt_denoise_desc); 0 reads as this layout. Fields past a caller's size read as 0 */
+    int width, height;       /* of every buffer below: rows of `width` pixels, as a frame or a band wrote them         */
+    const float *rgba_in;    /* device, float4 per pixel, 16-byte aligned: the colour to filter (rt_launch_opts.rgba)  */
+    const float *depth;      /* device, the four guides in the rt_frame_desc.aov_* layouts: float, 4-byte aligned      */
+    const float *normal;     /*   float4, 16-byte aligned                                                              */
+    const float *albedo;     /*   float4, 16-byte aligned; may be NULL only with demodulate = 0                        */
+    const int *id;           /*   int2 (kind, index), 8-byte aligned                                                   */
+    float *rgba_out;         /* device, float4 per pixel, 16-byte aligned: (filtered colour, 1); may equal rgba_in     */
+    uint32_t *pixels;        /* NULL, or device: the packed framebuffer of the result, rgbToInt(c * 254) as the frame  */
+    int iterations;          /* 1 .. RT_DENOISE_MAX_ITERATIONS; iteration i has its taps 2^i pixels apart   [4]        */
+    int normal_shift;        /* 0 .. RT_DENOISE_MAX_NORMAL_SHIFT: the normal weight is max(0, N.N')^(2^shift) [5]      */
+    float sigma_depth;       /* finite, > 0: relative depth difference at which the depth weight is 1/2     [0.05]     */
+    float sigma_colour;      /* finite; > 0: luminance difference at which the colour weight is 1/2; <= 0: off [0]     */
+    int demodulate;          /* non-zero: filter colour / albedo and multiply the albedo back (direct light only) [1]  */
+    int variant;             /* 0: the product kernels; 1: the plain one-thread-per-pixel yardstick (every tap from the
+                                caller's arrays); 2: the product kernels without LDS staging (measurement). The results
+                                are the same bits in all three                                                         */
+} rt_denoise_desc;
+
+/* The defaults in brackets above; sizes and pointers 0. */
+void rt_denoise_desc_init(rt_denoise_desc *d);
+
+/* Filters rgba_in into rgba_out (and `pixels`) on `stream` (a hipStream_t; NULL = the null stream): `iterations`
+ * passes of a 5 x 5 B3-spline kernel {1, 4, 6, 4, 1} / 16 with holes, whose taps are weighted by how well their
+ * guides agree with the centre's -- same object (id), similar normal, similar depth and, optionally, similar
+ * luminance (DESIGN.md 6f gives every formula; binary32, + - * / only, so the result is defined to the bit and
+ * variants 0, 1 and 2 return the same bits). A pixel with kind < 0 (sky) keeps its input bits in rgba_out, packs its
+ * input colour into `pixels` and contributes to no other pixel; so does a pixel none of whose neighbours agree with
+ * it, up to the demodulation round trip. Taps outside the buffer are skipped: a band is filtered as the buffer it is,
+ * so bands filtered apart differ from the whole frame within 2 * (2^iterations - 1) rows of a cut.
+ * demodulate = 1 assumes colour = light x albedo (frames with reflect_depth = 0); reflective frames pass 0. The
+ * guides are those of one sample per pixel: a caller may filter an spp > 1 colour with the 1-spp guides of the same
+ * camera.
+ * The call enqueues its kernels and returns; there is no host wait (a call that is larger than any before it
+ * allocates). rgba_out and `pixels` must not overlap the inputs, except that rgba_out may be rgba_in itself. The
+ * scratch (two irradiance buffers and the packed guides, 52 bytes per pixel) belongs to the scene and grows on
+ * demand: calls of one scene on different streams are ordered on the device, one after the other (an event, no host
+ * wait); ordering the call after the frame that writes its inputs is the caller's (the same stream, or an event).
+ * Before anything is enqueued, and with nothing written: NULL or misaligned pointers, sizes <= 0 or above
+ * RT_DENOISE_MAX_SIZE, iterations, normal_shift or variant out of range, a sigma_depth that is not finite and > 0, a
+ * sigma_colour that is not finite -> RT_ERR_INVALID; a stream that is being captured -> RT_ERR_UNSUPPORTED
+ * (rt_last_error() says so). */
+int rt_scene_denoise(rt_scene *s, const rt_denoise_desc *d, void *stream);
+
+/* Device time of every launch of the scene's later denoise calls (hipEvents around each; off by default).
+ * rt_scene_denoise_times waits for the last call and fills ms[0 .. *n - 1]: variants 0 and 2: [0] the pack pass,
+ * [1 + i] iteration i; variant 1: [i] iteration i. cap: room in ms. */
+int rt_scene_set_denoise_timing(rt_scene *s, int on);
+int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n);
+
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
  * tile first -- the frame kernel records every tile's wave duration, and from the previous launch's durations the
  * blocks are sorted on the device (three small kernels, ~15 us): after 1, 2, 4, 8, 16, 32, 64, 96, ... launches of an
@@ -609,6 +667,9 @@ int rt_set_soft_errors(int on);  /* 1: rt_check() records + returns instead of e
  * comparison with the CPU oracle (tests only; all pointers are HOST arrays).
  * op: 0 cosf, 1 sinf, 2 acosf, 3 atan2f(a,b)                                    */
 int rt_debug_math(int op, const float *a, const float *b, float *out, int n);
+/* A float4 copy kernel over n16 float4s (16-byte aligned, disjoint device buffers): the copy the denoiser's traffic
+ * floor is measured with (tools/bench_denoise.py). */
+int rt_debug_copy16(const void *src, void *dst, size_t n16, void *stream);
 /* sphere::intersect on the device: hit[i], t[i] for rays[i] vs spheres[i].      */
 int rt_debug_intersect(const rt_sphere *spheres, const rt_ray *rays, int n, int *hit, float *t);
 /* The 10 shadow-sample directions of castLightRay (kernel.cu:1442-1468) and its

@@ -172,6 +172,18 @@ class FrameDesc(C.Structure):
                 ("aov_depth", C.c_void_p), ("aov_normal", C.c_void_p), ("aov_id", C.c_void_p), ("aov_albedo", C.c_void_p)]
 
 
+class DenoiseDesc(C.Structure):
+    """rt_denoise_desc."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
+                ("rgba_in", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p),
+                ("id", C.c_void_p), ("rgba_out", C.c_void_p), ("pixels", C.c_void_p),
+                ("iterations", C.c_int), ("normal_shift", C.c_int), ("sigma_depth", C.c_float),
+                ("sigma_colour", C.c_float), ("demodulate", C.c_int), ("variant", C.c_int)]
+
+
+RT_DENOISE_MAX_ITERATIONS = 6
+RT_DENOISE_MAX_NORMAL_SHIFT = 8
+
 _lib = None
 
 
@@ -288,6 +300,11 @@ def load_library():
         "rt_debug_transmit": (ci, [C.POINTER(Sphere), fp, C.POINTER(Ray), ci, C.POINTER(Ray), C.POINTER(ci)]),
         "rt_scene_trace_rays": (ci, [vp, C.POINTER(RayQuery), vp]),
         "rt_scene_primary_rays": (ci, [vp, C.POINTER(FrameDesc), vp, vp]),
+        "rt_denoise_desc_init": (None, [C.POINTER(DenoiseDesc)]),
+        "rt_scene_denoise": (ci, [vp, C.POINTER(DenoiseDesc), vp]),
+        "rt_scene_set_denoise_timing": (ci, [vp, ci]),
+        "rt_scene_denoise_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
+        "rt_debug_copy16": (ci, [vp, vp, C.c_size_t, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -645,3 +662,63 @@ class Scene:
         """What is under pixel (x, y) of a width x height frame: (kind, index), kind RT_HIT_* (-1: sky)."""
         hit = self.trace_rays(self.primary_rays(width, height, y0=y, y1=y + 1, **kw)[0, x:x + 1], "nearest")
         return int(hit["kind"][0]), int(hit["index"][0])
+
+    # ---------------------------------------------------------------- the denoiser (DESIGN.md 6f)
+    def denoise_desc(self, width, height, *, rgba_in=0, depth=0, normal=0, albedo=0, id=0, rgba_out=0, pixels=0,
+                     iterations=None, normal_shift=None, sigma_depth=None, sigma_colour=None, demodulate=None,
+                     variant=0) -> DenoiseDesc:
+        """rt_denoise_desc with rt_denoise_desc_init's defaults where an argument is None."""
+        d = DenoiseDesc()
+        self.lib.rt_denoise_desc_init(C.byref(d))
+        d.width, d.height = width, height
+        d.rgba_in, d.depth, d.normal, d.albedo, d.id = rgba_in, depth, normal, albedo, id
+        d.rgba_out, d.pixels = rgba_out, pixels
+        for k, v in (("iterations", iterations), ("normal_shift", normal_shift), ("sigma_depth", sigma_depth),
+                     ("sigma_colour", sigma_colour), ("variant", variant)):
+            if v is not None:
+                setattr(d, k, v)
+        if demodulate is not None:
+            d.demodulate = 1 if demodulate else 0
+        return d
+
+    def denoise_raw(self, d: DenoiseDesc, stream=0) -> int:
+        """rt_scene_denoise as is: returns the status."""
+        return self.lib.rt_scene_denoise(self.handle, C.byref(d), stream)
+
+    def denoise(self, frame, *, iterations=None, normal_shift=None, sigma_depth=None, sigma_colour=None,
+                demodulate=None, want_packed=True, variant=0, stream=None):
+        """Filter a frame that render(..., aov=("depth", "normal", "id", "albedo")) returned with the edge-avoiding
+        a-trous filter of rt_scene_denoise (None: the default of rt_denoise_desc_init; demodulate=False needs no
+        albedo). Returns {'rgba': float32 [rows, W, 4], 'packed': int32 [rows, W] or None} as new tensors; the frame's
+        own tensors are not written. Enqueued on `stream` (default: the current stream); no host wait."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError("no GPU visible: the denoiser has no CPU fallback")
+        rgba, aov = frame.get("rgba"), frame.get("aov") or {}
+        need = ("depth", "normal", "id") + (() if demodulate is not None and not demodulate else ("albedo",))
+        if rgba is None or any(k not in aov for k in need):
+            raise RtError(f"denoise needs the frame's rgba and the G-buffer outputs {need}: render with want_rgba=True "
+                          f"and aov={AOV_NAMES}")
+        rows, width = rgba.shape[0], rgba.shape[1]
+        out = torch.empty_like(rgba)
+        packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
+        st = torch.cuda.current_stream() if stream is None else stream
+        d = self.denoise_desc(width, rows, rgba_in=rgba.data_ptr(), depth=aov["depth"].data_ptr(),
+                              normal=aov["normal"].data_ptr(), albedo=aov["albedo"].data_ptr() if "albedo" in aov else 0,
+                              id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
+                              pixels=packed.data_ptr() if want_packed else 0, iterations=iterations,
+                              normal_shift=normal_shift, sigma_depth=sigma_depth, sigma_colour=sigma_colour,
+                              demodulate=demodulate, variant=variant)
+        _check(self.denoise_raw(d, st.cuda_stream), "rt_scene_denoise")
+        return {"rgba": out, "packed": packed}
+
+    def set_denoise_timing(self, on: bool):
+        _check(self.lib.rt_scene_set_denoise_timing(self.handle, 1 if on else 0), "rt_scene_set_denoise_timing")
+
+    def denoise_times(self):
+        """Device ms of every launch of the last timed denoise call (waits for it): variants 0 and 2: the pack pass, then
+        the iterations; variant 1: the iterations."""
+        ms = (C.c_float * (RT_DENOISE_MAX_ITERATIONS + 1))()
+        n = C.c_int()
+        _check(self.lib.rt_scene_denoise_times(self.handle, ms, len(ms), C.byref(n)), "rt_scene_denoise_times")
+        return list(ms)[: n.value]

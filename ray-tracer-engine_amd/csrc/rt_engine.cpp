@@ -224,6 +224,15 @@ struct rt_scene {
     bool order_pending = false;
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
     std::unique_ptr<RtReflect, RtReflectDeleter> refl;
+    // the denoiser's scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand; `dn_done`
+    // orders the scene's denoise calls on the device, whatever their streams
+    DevArray<float4> dn_col[2], dn_guide;
+    DevArray<int> dn_key;
+    HipEvent dn_done;
+    bool dn_used = false;
+    HipEvent dn_ev[RT_DENOISE_MAX_ITERATIONS + 2];   // rt_scene_set_denoise_timing
+    bool dn_timing = false;
+    int dn_timed = 0;                                // events the last timed call recorded
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
 #endif
@@ -252,6 +261,7 @@ int rt_scene_quiesce(rt_scene *s)
     for (int i = 0; i < RT_RING; ++i)
         if (s->ring_used[i]) RT_HIP(hipEventSynchronize(s->ring[i].get()));
     if (s->table_stream.get()) RT_HIP(hipStreamSynchronize(s->table_stream.get()));   // a table build still reading the list
+    if (s->dn_used) RT_HIP(hipEventSynchronize(s->dn_done.get()));                     // a denoise call still using the scratch
     return RT_OK;
 }
 
@@ -1617,6 +1627,113 @@ extern "C" int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd_in, rt
     rc = rt_query_launch_primary(&fc, rays_dev, stream);
     if (rc != RT_OK) return rc;
     return rt_scene_note_launch(s, stream, -1);   // it reads the raygen tables
+}
+
+// ---------------------------------------------------------------------------
+// the G-buffer-guided denoiser (rt_denoise.hip)
+// ---------------------------------------------------------------------------
+extern "C" void rt_denoise_desc_init(rt_denoise_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->iterations = 4;
+    d->normal_shift = 5;
+    d->sigma_depth = 0.05f;
+    d->sigma_colour = 0.f;
+    d->demodulate = 1;
+}
+
+extern "C" int rt_scene_denoise(rt_scene *s, const rt_denoise_desc *d_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_denoise: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_denoise_desc d;   // in this build's layout: what the caller's struct_size does not cover reads as 0
+    memset(&d, 0, sizeof d);
+    size_t sz = d_in->struct_size ? d_in->struct_size : sizeof d;
+    if (sz > sizeof d) sz = sizeof d;
+    memcpy(&d, d_in, sz);
+    d.struct_size = (uint32_t)sizeof d;
+    const char *bad = nullptr;
+    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
+        bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
+    else if (!d.rgba_in || !d.depth || !d.normal || !d.id || !d.rgba_out) bad = "rgba_in, depth, normal, id and rgba_out must not be NULL";
+    else if (d.demodulate && !d.albedo) bad = "demodulate needs albedo";
+    else if ((((uintptr_t)d.rgba_in | (uintptr_t)d.normal | (uintptr_t)d.albedo | (uintptr_t)d.rgba_out) & 15u) ||
+             ((uintptr_t)d.id & 7u) || (((uintptr_t)d.depth | (uintptr_t)d.pixels) & 3u))
+        bad = "rgba_in, normal, albedo and rgba_out must be 16-byte aligned, id 8-byte, depth and pixels 4-byte";
+    else if (d.iterations < 1 || d.iterations > RT_DENOISE_MAX_ITERATIONS) bad = "iterations is not in [1, RT_DENOISE_MAX_ITERATIONS]";
+    else if (d.normal_shift < 0 || d.normal_shift > RT_DENOISE_MAX_NORMAL_SHIFT) bad = "normal_shift is not in [0, RT_DENOISE_MAX_NORMAL_SHIFT]";
+    else if (!(d.sigma_depth > 0.f) || !std::isfinite(d.sigma_depth)) bad = "sigma_depth is not finite and > 0";
+    else if (!std::isfinite(d.sigma_colour)) bad = "sigma_colour is not finite";
+    else if (d.variant < 0 || d.variant > 2) bad = "variant is not 0, 1 or 2";
+    if (bad) {
+        rt_set_error("rt_scene_denoise: %s (%d x %d, iterations %d, normal_shift %d, variant %d)", bad, d.width, d.height,
+                     d.iterations, d.normal_shift, d.variant);
+        return RT_ERR_INVALID;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_denoise: the stream is being captured (the denoiser is not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    const size_t npx = (size_t)d.width * d.height;
+    if (npx > s->dn_col[0].capacity() || npx > s->dn_col[1].capacity() ||
+        (d.variant != 1 && (npx > s->dn_guide.capacity() || npx > s->dn_key.capacity()))) {
+        // growing releases the old buffers: after the host has seen the last call that used them end
+        if (s->dn_used) RT_HIP(hipEventSynchronize(s->dn_done.get()));
+        RT_HIP(s->dn_col[0].reserve(npx));
+        RT_HIP(s->dn_col[1].reserve(npx));
+        if (d.variant != 1) {
+            RT_HIP(s->dn_guide.reserve(npx));
+            RT_HIP(s->dn_key.reserve(npx));
+        }
+    }
+    RT_HIP(s->dn_done.create());
+    if (s->dn_used) RT_HIP(hipStreamWaitEvent(stream, s->dn_done.get(), 0));   // one scratch: one call at a time
+    hipEvent_t ev[RT_DENOISE_MAX_ITERATIONS + 2];
+    s->dn_timed = 0;
+    if (s->dn_timing) {
+        for (int i = 0; i < RT_DENOISE_MAX_ITERATIONS + 2; ++i) {
+            RT_HIP(s->dn_ev[i].create(hipEventDefault));
+            ev[i] = s->dn_ev[i].get();
+        }
+    }
+    const int rc = rt_denoise_launch(&d, s->dn_col[0].get(), s->dn_col[1].get(), s->dn_guide.get(), s->dn_key.get(),
+                                     s->dn_timing ? ev : nullptr, stream);
+    // also after a launch that failed half way: what was enqueued uses the scratch
+    RT_HIP(hipEventRecord(s->dn_done.get(), stream));
+    s->dn_used = true;
+    if (rc == RT_OK && s->dn_timing) s->dn_timed = d.iterations + (d.variant == 1 ? 1 : 2);
+    return rc;
+}
+
+extern "C" int rt_scene_set_denoise_timing(rt_scene *s, int on)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_denoise_timing: null scene");
+        return RT_ERR_INVALID;
+    }
+    s->dn_timing = on != 0;
+    return RT_OK;
+}
+
+extern "C" int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    if (!s || !ms || !n || cap < 0) {
+        rt_set_error("rt_scene_denoise_times: null argument");
+        return RT_ERR_INVALID;
+    }
+    *n = 0;
+    if (s->dn_timed < 2) return RT_OK;
+    RT_HIP(hipEventSynchronize(s->dn_done.get()));
+    for (int i = 0; i + 1 < s->dn_timed && i < cap; ++i) {
+        RT_HIP(hipEventElapsedTime(&ms[i], s->dn_ev[i].get(), s->dn_ev[i + 1].get()));
+        *n = i + 1;
+    }
+    return RT_OK;
 }
 
 int rt_scene_tile_order_mode(const rt_scene *s) { return s->tile_order_mode; }

@@ -150,3 +150,8 @@ const char *rt_fd_aov_field(const rt_frame_desc *fd);
 const char *rt_frame_aov_field(const rt_frame_desc *fd);
 // a caller's frame description in this build's layout (what its struct_size fields do not cover reads as 0)
 void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out);
+
+// rt_denoise.hip: the G-buffer-guided denoiser (d: validated, in this build's layout; the scene's scratch, room for
+// width * height pixels each; ev: null, or iterations + 2 timing events)
+int rt_denoise_launch(const rt_denoise_desc *d, float4 *col0, float4 *col1, float4 *guide, int *key, hipEvent_t *ev,
+                      hipStream_t stream);
