@@ -584,6 +584,31 @@ int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n);
  * head of every replay (from the durations of the previous one).                                                  */
 int rt_scene_set_tile_order(rt_scene *s, int mode);
 
+/* Per-view candidate lists of the primary rays. 1 (default): for every view (ray origin, rotation, frame size, aspect)
+ * the frame is cut into blocks of pixels (64 x 64 at full-HD and above, smaller at small frames) and the spheres the
+ * primary rays of each block can hit are listed front to back once, on the device, beside the previous frame; the
+ * tiles of every frame of that view walk their block's list instead of each culling and ordering the sphere table for
+ * itself. A resting camera builds once, a moving one once per frame. Only where the scene has eye cones (64 spheres
+ * or more) and whole tiles nest in the blocks; a block with more than 64 candidates leaves its tiles on the old
+ * path. 0: every tile culls for itself. The pixels are the same bits either way. A frame graph builds its own lists. */
+int rt_scene_set_view_lists(rt_scene *s, int mode);
+typedef struct rt_view_lists_info {
+    int read;                  /* 1: the last launch on the scene read view lists (else everything below is 0) */
+    int block_w, block_h;      /* pixels */
+    int blocks_x, blocks_y, blocks;
+    int overflowed;            /* blocks with more than 64 candidates (their tiles cull for themselves) */
+    int not_built;             /* blocks without a usable cone (likewise) */
+    int longest;               /* longest list */
+    float mean;                /* mean list length */
+} rt_view_lists_info;
+/* Waits for the lists' build. slots (optional, room for `cap` 16-byte records): a copy of the lists, per block 97
+ * records: {count, flags, 0, 0} (ints), 64 entries {x, y, z, radius^2}, 64 list positions (ints), 64 bounds (floats). */
+int rt_scene_view_lists_info(rt_scene *s, rt_view_lists_info *out, float *slots, size_t cap);
+/* The host builder's lists for a sphere list and a frame (no device involved; tests). beams (optional): per block the
+ * cone's unit axis and slope (-1: no usable cone). */
+int rt_debug_view_lists_host(const rt_sphere *spheres, int n, const rt_frame_desc *fd, rt_view_lists_info *out,
+                             float *slots, size_t cap, float *beams);
+
 /* hipGraph-captured frame loop (config C4): `passes` samples per pixel + resolve + optional async copy of the packed
  * frame to pinned host memory, recorded once and replayed per frame. passes > 0: the samples are taken by ONE kernel
  * node (the sample loop runs inside the kernel); passes < 0: |passes| progressive one-sample nodes, each adding into

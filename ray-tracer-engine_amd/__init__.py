@@ -181,6 +181,16 @@ class DenoiseDesc(C.Structure):
                 ("sigma_colour", C.c_float), ("demodulate", C.c_int), ("variant", C.c_int)]
 
 
+class ViewListsInfo(C.Structure):
+    """rt_view_lists_info."""
+    _fields_ = [("read", C.c_int), ("block_w", C.c_int), ("block_h", C.c_int), ("blocks_x", C.c_int), ("blocks_y", C.c_int),
+                ("blocks", C.c_int), ("overflowed", C.c_int), ("not_built", C.c_int), ("longest", C.c_int), ("mean", C.c_float)]
+
+
+RT_VIEW_CAP = 64
+RT_VIEW_SLOT = 1 + RT_VIEW_CAP + RT_VIEW_CAP // 4 + RT_VIEW_CAP // 4    # 16-byte records per block
+RT_VIEW_OVERFLOW, RT_VIEW_NOT_BUILT = 1, 2
+
 RT_DENOISE_MAX_ITERATIONS = 6
 RT_DENOISE_MAX_NORMAL_SHIFT = 8
 
@@ -249,6 +259,9 @@ def load_library():
         "rt_scene_set_sky": (ci, [vp, C.POINTER(Sphere), fp, fp, fp, ci, ci]),
         "rt_scene_set_lights": (ci, [vp, C.POINTER(Light), ci]),
         "rt_scene_set_tile_order": (ci, [vp, ci]),
+        "rt_scene_set_view_lists": (ci, [vp, ci]),
+        "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
+        "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
         "rt_scene_render": (ci, [vp, C.POINTER(FrameDesc), vp]),
         "rt_graph_capture": (vp, [vp, C.POINTER(FrameDesc), ci, vp, vp]),
         "rt_graph_launch": (ci, [vp, vp]),
@@ -392,6 +405,43 @@ def interleaved_rows(height: int, rank: int, world: int, block: int = 16):
     return rows
 
 
+def _view_info_dict(info) -> dict:
+    return {k: getattr(info, k) for k, _ in ViewListsInfo._fields_}
+
+
+def unpack_view_lists(buf, blocks):
+    """Per block of a view-list table (float32 [blocks * RT_VIEW_SLOT, 4]): (count, flags, entries float32 [count, 4],
+    positions int32 [count], bounds float32 [count])."""
+    out = []
+    slots = np.ascontiguousarray(buf, dtype=np.float32).reshape(blocks, RT_VIEW_SLOT, 4)
+    for b in range(blocks):
+        count, flags = (int(v) for v in slots[b, 0].view(np.int32)[:2])
+        pos = slots[b, 1 + RT_VIEW_CAP:1 + RT_VIEW_CAP + RT_VIEW_CAP // 4].reshape(-1).view(np.int32)[:count].copy()
+        lbs = slots[b, 1 + RT_VIEW_CAP + RT_VIEW_CAP // 4:].reshape(-1)[:count].copy()
+        out.append((count, flags, slots[b, 1:1 + count].copy(), pos, lbs))
+    return out
+
+
+def view_lists_host(spheres, n, fd, want_lists=True, want_beams=False) -> dict:
+    """The host builder's view lists for a sphere list and a frame description (no GPU): the summary of
+    Scene.view_lists_info plus 'lists' and 'beams' (float32 [blocks, 4]: unit axis, slope or -1)."""
+    lib = load_library()
+    info = ViewListsInfo()
+    _check(lib.rt_debug_view_lists_host(spheres, n, C.byref(fd), C.byref(info), None, 0, None), "rt_debug_view_lists_host")
+    buf = np.zeros((info.blocks * RT_VIEW_SLOT, 4), dtype=np.float32) if want_lists else None
+    beams = np.zeros((info.blocks, 4), dtype=np.float32) if want_beams else None
+    if want_lists or want_beams:
+        _check(lib.rt_debug_view_lists_host(spheres, n, C.byref(fd), C.byref(info), _fptr(buf) if want_lists else None,
+                                            buf.shape[0] if want_lists else 0, _fptr(beams) if want_beams else None),
+               "rt_debug_view_lists_host")
+    d = _view_info_dict(info)
+    if want_lists:
+        d["lists"] = unpack_view_lists(buf, info.blocks)
+    if want_beams:
+        d["beams"] = beams
+    return d
+
+
 class Scene:
     """Device-resident scene (rt_scene). Keeps the host arrays it was built from
     so tests can hand exactly the same inputs to the oracle."""
@@ -508,6 +558,22 @@ class Scene:
     def set_tile_order(self, mode: int):
         """1 (default): launches start their longest tiles first (durations of earlier frames); 0: grid order."""
         _check(self.lib.rt_scene_set_tile_order(self.handle, mode), "rt_scene_set_tile_order")
+
+    def set_view_lists(self, mode: int):
+        """1 (default): the tiles of a frame walk their block's per-view candidate list; 0: every tile culls for itself."""
+        _check(self.lib.rt_scene_set_view_lists(self.handle, mode), "rt_scene_set_view_lists")
+
+    def view_lists_info(self, want_lists: bool = False) -> dict:
+        """What the last launch read (waits for the lists' build): read, block size, blocks, overflowed and not-built
+        blocks, longest and mean list; with want_lists also 'lists' (see unpack_view_lists)."""
+        info = ViewListsInfo()
+        _check(self.lib.rt_scene_view_lists_info(self.handle, C.byref(info), None, 0), "rt_scene_view_lists_info")
+        d = _view_info_dict(info)
+        if want_lists and info.read:
+            buf = np.zeros((info.blocks * RT_VIEW_SLOT, 4), dtype=np.float32)
+            _check(self.lib.rt_scene_view_lists_info(self.handle, C.byref(info), _fptr(buf), buf.shape[0]), "rt_scene_view_lists_info")
+            d["lists"] = unpack_view_lists(buf, info.blocks)
+        return d
 
     @classmethod
     def default(cls, n_spheres: int = 1024, seed: int = 1) -> "Scene":

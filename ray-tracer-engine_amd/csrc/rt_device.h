@@ -74,6 +74,10 @@
 #define RT_BLOCK 16             // spheres per block of the Morton-ordered table (divides 64)
 #endif
 #define RT_BOX_CAP 128          // leaf-box list capacity per wave (ints in LDS, mesh scenes only)
+#define RT_VIEW_CAP 64          // longest view list kept (what one wave orders front to back in one step)
+#define RT_VIEW_SLOT (1 + RT_VIEW_CAP + RT_VIEW_CAP / 4 + RT_VIEW_CAP / 4)   // float4 per block: header, entries, positions, bounds
+#define RT_VIEW_OVERFLOW 1      // header flags: more than RT_VIEW_CAP survivors -- the tile culls for itself
+#define RT_VIEW_NOT_BUILT 2     // ... the block has no usable cone (degenerate or too wide) -- likewise
 
 // Smallest binary32 >= 0.0001 (binary64): `t >= 0.0001` (kernel.cu:342) compares
 // the widened float with the double literal, which is equivalent to a float
@@ -228,6 +232,16 @@ struct RtFrameConsts {
     const int *corig;
 
     const RtFrameAux *aux;      // device memory, see above
+
+    // View lists (rt_tables.hip: rt_view_lists_kernel): for every block of 2^bw x 2^bh pixels of the frame, the spheres
+    // any primary ray of the block can hit, already ordered front to back -- what build_list2<ORDERED> yields for the
+    // block's own cone, built once per view instead of once per tile and frame. Block (px >> bw, py >> bh) owns the
+    // slot of RT_VIEW_SLOT float4 at view_lists + (by * view_nbx + bx) * RT_VIEW_SLOT: a header {count, flags, -, -}
+    // (ints), RT_VIEW_CAP entries {x, y, z, r^2}, their list positions (ints) and their lower bounds of t (floats).
+    // Null: the launch has none (or its tiles do not nest in the blocks) and every tile culls for itself.
+    const float *view_lists;
+    int view_nbx;               // blocks per row of blocks
+    int view_shift;             // bw | bh << 8
 
     // outputs
     float *rgba;                // float4 per pixel, band-local, may be null

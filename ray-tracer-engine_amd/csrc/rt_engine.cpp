@@ -135,6 +135,21 @@ struct ConeSlot {
     bool build_pending = false;           // `built` not yet seen complete: readers wait on it (on the device)
 };
 
+// View lists (RtFrameConsts::view_lists, rt_tables.hip): one table per recent view, built on the table stream after the
+// eye-cone table it reads and handed over exactly as that one is -- after the slot's last reader through the frame ring,
+// before its first reader through `built`; a camera move costs no host wait.
+#define RT_VIEW_SLOTS 4
+struct ViewSlot {
+    DevArray<float4> buf;
+    unsigned key[18] = {};                // compared by bits: sphere_gen, origin, rotation, eye_nz, aspect, frame size, sample total, block shape
+    bool valid = false;
+    bool used = false;
+    unsigned long long last_use = 0;
+    HipEvent built;
+    bool build_pending = false;
+    int nbx = 0, nby = 0, bw = 0, bh = 0;
+};
+
 struct RtReflectDeleter {
     void operator()(RtReflect *r) const { rt_reflect_destroy(r); }
 };
@@ -220,6 +235,10 @@ struct rt_scene {
     TileOrder orders[RT_ORDER_SLOTS];
     unsigned long long order_clock = 0;      // for least-recently-used replacement
     int tile_order_mode = 1;                 // rt_scene_set_tile_order
+    // per-view candidate lists of the primary rays
+    ViewSlot views[RT_VIEW_SLOTS];
+    int view_lists_mode = 1;                 // rt_scene_set_view_lists
+    int view_last = -1;                      // the slot the last launch read, -1: it read none
     HipEvent order_built;                    // the last rebuild; launches on other streams wait for it on the device
     bool order_pending = false;
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
@@ -1002,6 +1021,17 @@ static int rt_scene_sync_aux(rt_scene *s)
     return RT_OK;
 }
 
+// camera::rotateDir, kernel.cu:249-250
+static void view_rotation(const rt_frame_desc *fd, RtFrameConsts *fc)
+{
+    const float yawRad = (float)(fd->cam.Camyaw * (3.1415 / 180));
+    const float pitchRad = (float)(fd->cam.Campitch * (3.1415 / 180));
+    fc->cos_pitch = rtm::cosf_rt(pitchRad);
+    fc->sin_pitch = rtm::sinf_rt(pitchRad);
+    fc->cos_yaw = rtm::cosf_rt(yawRad);
+    fc->sin_yaw = rtm::sinf_rt(yawRad);
+}
+
 // The by-value frame uniforms. Pure host computation: no device call, the scene is not
 // changed. `cones`: the eye-cone table the frame reads (its org must be the frame's), or null.
 int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const float4 *cones, RtFrameConsts *fc)
@@ -1101,13 +1131,7 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
     fc->org_x = org[0];
     fc->org_y = org[1];
     fc->org_z = org[2];
-    // camera::rotateDir, kernel.cu:249-250
-    const float yawRad = (float)(fd->cam.Camyaw * (3.1415 / 180));
-    const float pitchRad = (float)(fd->cam.Campitch * (3.1415 / 180));
-    fc->cos_pitch = rtm::cosf_rt(pitchRad);
-    fc->sin_pitch = rtm::sinf_rt(pitchRad);
-    fc->cos_yaw = rtm::cosf_rt(yawRad);
-    fc->sin_yaw = rtm::sinf_rt(yawRad);
+    view_rotation(fd, fc);
 
     fc->tex_r = s->d_tex[0].get(); fc->tex_g = s->d_tex[1].get(); fc->tex_b = s->d_tex[2].get();
     fc->tex_w = s->tex_w; fc->tex_h = s->tex_h;
@@ -1279,6 +1303,109 @@ static int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, Rt
     t->last_use = ++s->order_clock;
     fc->tile_cost = t->buf.cost();
     fc->tile_perm = t->have_perm ? t->buf.perm() : nullptr;
+    return RT_OK;
+}
+
+// The view of a frame as the view-list builders take it (block shape by rt_view_block_shape; tab, cones, out left null).
+static void view_params_from_consts(const RtFrameConsts &fc, float aspect, RtViewParams *p)
+{
+    memset(p, 0, sizeof *p);
+    p->n = fc.n_spheres;
+    p->n_blocks = fc.n_blocks;
+    p->org[0] = fc.org_x; p->org[1] = fc.org_y; p->org[2] = fc.org_z;
+    p->cos_pitch = fc.cos_pitch; p->sin_pitch = fc.sin_pitch; p->cos_yaw = fc.cos_yaw; p->sin_yaw = fc.sin_yaw;
+    p->eye_nz = fc.eye_nz;
+    p->aspect = aspect;
+    p->width = fc.width;
+    p->height = fc.height;
+    rt_view_block_shape(fc.width, fc.height, &p->bw, &p->bh);
+    p->nbx = (fc.width + (1 << p->bw) - 1) >> p->bw;
+    p->nby = (fc.height + (1 << p->bh) - 1) >> p->bh;
+}
+
+// Do whole tiles of this launch nest in the view's blocks? Tiles start at multiples of their width and, counted from
+// the band's first row y0 (interleaved row blocks are multiples of 16 rows from there), of their height.
+static bool view_tiles_nest(const RtViewParams &p, const RtFrameConsts &fc, int tile_w)
+{
+    const int th = 64 / tile_w;
+    return (1 << p.bw) >= tile_w && (1 << p.bh) >= th && fc.y0 % th == 0;
+}
+
+// The view lists of a culled frame whose eye-cone table is cones[cone_slot]: finds or builds them and points fc at them.
+// Leaves fc without lists (every tile culls for itself) when the switch is off or the launch's tiles do not nest.
+static int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelChoice &kc, int cone_slot, RtFrameConsts *fc,
+                                 hipStream_t stream, int *view_out)
+{
+    *view_out = -1;
+    if (!s->view_lists_mode || cone_slot < 0 || !kc.cull || kc.mode == 2) return RT_OK;
+    RtViewParams p;
+    view_params_from_consts(*fc, fd->aspect, &p);
+    if (!view_tiles_nest(p, *fc, kc.tile)) return RT_OK;
+    unsigned key[18];
+    {
+        const float f[10] = {p.org[0], p.org[1], p.org[2], p.cos_pitch, p.sin_pitch, p.cos_yaw, p.sin_yaw, p.eye_nz, p.aspect, fc->sample_total};
+        memcpy(key, f, sizeof f);
+        key[10] = (unsigned)s->sphere_gen; key[11] = (unsigned)(s->sphere_gen >> 32);
+        key[12] = (unsigned)p.width; key[13] = (unsigned)p.height; key[14] = (unsigned)p.bw; key[15] = (unsigned)p.bh;
+        key[16] = (unsigned)p.n; key[17] = 0;
+    }
+    int v = -1;
+    for (int i = 0; i < RT_VIEW_SLOTS; ++i)
+        if (s->views[i].valid && memcmp(s->views[i].key, key, sizeof key) == 0) v = i;
+    if (v < 0) {
+        // victim: a slot that holds nothing, else the one read longest ago
+        v = 0;
+        for (int i = 1; i < RT_VIEW_SLOTS; ++i) {
+            const ViewSlot &c = s->views[i], &b = s->views[v];
+            if (b.valid && (!c.valid || !c.used || (b.used && c.last_use < b.last_use))) v = i;
+        }
+        ViewSlot &c = s->views[v];
+        const size_t total = rt_view_lists_size(p.nbx, p.nby);
+        c.valid = false;
+        if (total > c.buf.capacity()) {
+            const int rc = rt_scene_quiesce(s);   // nothing may still read the buffer that is freed
+            if (rc != RT_OK) return rc;
+            RT_HIP(c.buf.reserve(total));
+            s->epoch++;
+        }
+        if (!s->table_stream.get()) {
+            int lo = 0, hi = 0;
+            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+            RT_HIP(s->table_stream.create(hipStreamNonBlocking, hi));
+        }
+        // on the table stream: behind the build of the eye-cone table it reads (same stream, or finished on the host),
+        // after the last frame that read this slot and after a sphere-table upload still in flight
+        const hipStream_t ts = s->table_stream.get();
+        RT_HIP(c.built.create());
+        if (c.used) {
+            if (s->ring_seq - c.last_use <= RT_RING) RT_HIP(hipStreamWaitEvent(ts, s->ring[c.last_use % RT_RING].get(), 0));
+            else {
+                const int rc = stream_wait_all_frames(s, ts);
+                if (rc != RT_OK) return rc;
+            }
+        }
+        if (s->stage_busy) RT_HIP(hipStreamWaitEvent(ts, s->stage_done.get(), 0));
+        p.tab = s->d_spheres.get();
+        p.cones = s->cones[cone_slot].buf.get();
+        p.out = c.buf.get();
+        RT_HIP(rt_view_lists_launch(p, ts));
+        RT_HIP(hipEventRecord(c.built.get(), ts));
+        c.build_pending = true;
+        memcpy(c.key, key, sizeof key);
+        c.nbx = p.nbx; c.nby = p.nby; c.bw = p.bw; c.bh = p.bh;
+        c.valid = true;
+        c.used = false;
+    }
+    ViewSlot &c = s->views[v];
+    if (c.build_pending) {   // the build precedes its readers
+        if (hipEventQuery(c.built.get()) == hipSuccess) c.build_pending = false;
+        else RT_HIP(hipStreamWaitEvent(stream, c.built.get(), 0));
+        (void)hipGetLastError();
+    }
+    fc->view_lists = reinterpret_cast<const float *>(c.buf.get());
+    fc->view_nbx = c.nbx;
+    fc->view_shift = c.bw | (c.bh << 8);
+    *view_out = v;
     return RT_OK;
 }
 
@@ -1490,6 +1617,9 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     rc = rt_frame_kernel_choice(s, fd, &kc);
     if (rc != RT_OK) return rc;
     if (fc.local_rows == 0) return RT_OK;   // this rank owns no rows of the frame
+    int view = -1;
+    rc = rt_scene_prepare_view(s, fd, kc, slot, &fc, stream, &view);
+    if (rc != RT_OK) return rc;
     if (reflect_depth > 0) {
         // the queues, the BVH and the materials are the scene's: after every frame launched so far (a host wait only
         // when the BVH or the materials change)
@@ -1520,6 +1650,11 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     if (reflect_depth > 0) {
         rc = rt_reflect_launch(s->refl.get(), &fc, s->d_spheres.get(), s->n_spheres, reflect_depth, kc.cull == 0, stream);
         if (rc != RT_OK) return rc;
+    }
+    s->view_last = view;
+    if (view >= 0) {
+        s->views[view].used = true;
+        s->views[view].last_use = s->ring_seq;   // the ring slot this launch is about to take
     }
     return rt_scene_note_launch(s, stream, slot);
 }
@@ -1752,6 +1887,116 @@ extern "C" int rt_scene_set_tile_order(rt_scene *s, int mode)
 const float4 *rt_scene_sphere_table(const rt_scene *s) { return s->d_spheres.get(); }
 int rt_scene_sphere_count(const rt_scene *s) { return s->n_spheres; }
 unsigned long long rt_scene_epoch(const rt_scene *s) { return s->epoch; }
+int rt_scene_view_lists_mode(const rt_scene *s) { return s->view_lists_mode; }
+
+extern "C" int rt_scene_set_view_lists(rt_scene *s, int mode)
+{
+    if (!s || (mode != 0 && mode != 1)) {
+        rt_set_error("rt_scene_set_view_lists: null scene or mode %d not in {0, 1}", mode);
+        return RT_ERR_INVALID;
+    }
+    s->view_lists_mode = mode;
+    return RT_OK;
+}
+
+static void view_lists_summary(const float4 *slots, int blocks, rt_view_lists_info *out)
+{
+    long long sum = 0;
+    for (int b = 0; b < blocks; ++b) {
+        int hdr[4];
+        memcpy(hdr, slots + (size_t)b * RT_VIEW_SLOT, sizeof hdr);
+        if (hdr[1] & RT_VIEW_OVERFLOW) out->overflowed++;
+        if (hdr[1] & RT_VIEW_NOT_BUILT) out->not_built++;
+        if (hdr[0] > out->longest) out->longest = hdr[0];
+        sum += hdr[0];
+    }
+    out->blocks = blocks;
+    out->mean = blocks > 0 ? (float)((double)sum / blocks) : 0.f;
+}
+
+// What the last launch on this scene read (waits for that view's build); out->read = 0: it read no lists. `slots`
+// (optional, `cap` float4): a copy of the lists themselves.
+extern "C" int rt_scene_view_lists_info(rt_scene *s, rt_view_lists_info *out, float *slots, size_t cap)
+{
+    if (!s || !out) {
+        rt_set_error("rt_scene_view_lists_info: null argument");
+        return RT_ERR_INVALID;
+    }
+    memset(out, 0, sizeof *out);
+    if (s->view_last < 0) return RT_OK;
+    const ViewSlot &c = s->views[s->view_last];
+    RT_HIP(hipEventSynchronize(c.built.get()));
+    const size_t total = rt_view_lists_size(c.nbx, c.nby);
+    std::vector<float4> h(total);
+    RT_HIP(hipMemcpy(h.data(), c.buf.get(), sizeof(float4) * total, hipMemcpyDeviceToHost));
+    out->read = 1;
+    out->block_w = 1 << c.bw; out->block_h = 1 << c.bh;
+    out->blocks_x = c.nbx; out->blocks_y = c.nby;
+    view_lists_summary(h.data(), c.nbx * c.nby, out);
+    if (slots) {
+        if (cap < total) {
+            rt_set_error("rt_scene_view_lists_info: room for %zu float4, the lists take %zu", cap, total);
+            return RT_ERR_INVALID;
+        }
+        memcpy(slots, h.data(), sizeof(float4) * total);
+    }
+    return RT_OK;
+}
+
+// The host builder for a sphere list and a frame description, no device involved (tests): the summary, and into `slots`
+// (optional, `cap` float4) the lists. beams (optional): {ux, uy, uz, k or -1} per block.
+extern "C" int rt_debug_view_lists_host(const rt_sphere *spheres, int n, const rt_frame_desc *fd_in, rt_view_lists_info *out,
+                                        float *slots, size_t cap, float *beams)
+{
+    if (!spheres || n < 1 || !fd_in || !out) {
+        rt_set_error("rt_debug_view_lists_host: bad argument");
+        return RT_ERR_INVALID;
+    }
+    rt_frame_desc fd;
+    normalise_frame_desc(fd_in, &fd);
+    RtFrameConsts fc;
+    memset(&fc, 0, sizeof fc);
+    fc.n_spheres = n;
+    fc.width = fd.width; fc.height = fd.height;
+    fc.eye_nz = 0.f - (-1.f / fd.aspect);
+    float org[3];
+    rt_ray_origin(&fd, org);
+    fc.org_x = org[0]; fc.org_y = org[1]; fc.org_z = org[2];
+    view_rotation(&fd, &fc);
+    RtViewParams p;
+    view_params_from_consts(fc, fd.aspect, &p);
+    std::vector<float4> tab((size_t)n);
+    pack_spheres(spheres, n, tab.data());
+    const size_t total = rt_view_lists_size(p.nbx, p.nby);
+    std::vector<float4> h(total);
+    p.out = h.data();
+    rt_build_view_lists_host(tab.data(), p, h.data());
+    memset(out, 0, sizeof *out);
+    out->block_w = 1 << p.bw; out->block_h = 1 << p.bh;
+    out->blocks_x = p.nbx; out->blocks_y = p.nby;
+    view_lists_summary(h.data(), p.nbx * p.nby, out);
+    if (slots) {
+        if (cap < total) {
+            rt_set_error("rt_debug_view_lists_host: room for %zu float4, the lists take %zu", cap, total);
+            return RT_ERR_INVALID;
+        }
+        memcpy(slots, h.data(), sizeof(float4) * total);
+    }
+    if (beams)
+        for (int b = 0; b < p.nbx * p.nby; ++b) {
+            const RtViewBeam vb = rt_view_block_beam(p, b % p.nbx, b / p.nbx);
+            beams[4 * b + 0] = vb.ux; beams[4 * b + 1] = vb.uy; beams[4 * b + 2] = vb.uz; beams[4 * b + 3] = vb.ok ? vb.k : -1.f;
+        }
+    return RT_OK;
+}
+
+// for a graph's own lists (rt_graph.cpp)
+int rt_view_params_for_frame(const rt_scene *s, const RtFrameConsts *fc, float aspect, int tile_w, int cull, int mode, RtViewParams *p)
+{
+    view_params_from_consts(*fc, aspect, p);
+    return s->view_lists_mode && cull && mode != 2 && view_tiles_nest(*p, *fc, tile_w);
+}
+
 bool rt_scene_wants_eye_cones(const rt_scene *s, const float org[3]) { return eye_cones_wanted(s, org); }
 int rt_scene_build_eye_cones_host(rt_scene *s, const float org[3], float4 *buf, hipStream_t stream)
 {

@@ -3,7 +3,7 @@
 // malloc -> H2D -> launch -> sync -> free sequence (/root/reference/kernel.cu:1762-1792)
 // with a graph built once:
 //
-//   [eye-cone build]  ->  [tile order: keys, sort, expand]  ->  [sample pass 0] -> ... -> [sample pass p-1]  ->  [copy to the present buffer]
+//   [eye-cone build]  ->  [view-list build]  ->  [tile order: keys, sort, expand]  ->  [sample pass 0] -> ... -> [sample pass p-1]  ->  [copy to the present buffer]
 //
 // (the tile order -- blocks of 16 x 16 tiles, longest tile first, DESIGN.md section 4d -- is sorted at the head of every
 // replay from the wave durations the passes of the previous replay recorded into the graph's own arrays)
@@ -32,6 +32,11 @@ struct rt_frame_graph {
     hipGraphExec_t exec = nullptr;
     // nodes whose parameters follow the camera
     hipGraphNode_t build_node = nullptr;
+    hipGraphNode_t view_node = nullptr;      // the graph's own view lists (RtFrameConsts::view_lists), built after the cones
+    hipKernelNodeParams view_kparams;
+    RtViewParams view_params;
+    DevArray<float4> views;
+    bool views_on = false;
     hipGraphNode_t pass_node[RT_MAX_SPP] = {};
     bool pass_live[RT_MAX_SPP] = {};
     hipKernelNodeParams pass_params[RT_MAX_SPP];
@@ -56,6 +61,7 @@ static void release_graph(rt_frame_graph *g)
     g->exec = nullptr;
     g->graph = nullptr;
     g->build_node = nullptr;
+    g->view_node = nullptr;
     for (int p = 0; p < RT_MAX_SPP; ++p) g->pass_live[p] = false;
 }
 
@@ -89,6 +95,24 @@ static int fill_arguments(rt_frame_graph *g, bool with_cones)
         if (g->order_on) {
             g->fc[p].tile_perm = g->order.perm();
             g->fc[p].tile_cost = g->order.cost();
+        }
+    }
+    if (g->views_on) {   // one view for all passes: the same camera, frame and block shape
+        const int nbx = g->view_params.nbx, nby = g->view_params.nby;
+        RtViewParams vp;
+        (void)rt_view_params_for_frame(g->scene, &g->fc[0], g->fd.aspect, 8, 1, 0, &vp);
+        if (vp.nbx != nbx || vp.nby != nby) {
+            rt_set_error("rt_graph: the view lists' geometry changed under a recorded graph");
+            return RT_ERR_INVALID;
+        }
+        vp.tab = rt_scene_sphere_table(g->scene);
+        vp.cones = g->cones.get();
+        vp.out = g->views.get();
+        g->view_params = vp;
+        for (int p = 0; p < g->passes; ++p) {
+            g->fc[p].view_lists = reinterpret_cast<const float *>(g->views.get());
+            g->fc[p].view_nbx = vp.nbx;
+            g->fc[p].view_shift = vp.bw | (vp.bh << 8);
         }
     }
     return RT_OK;
@@ -130,6 +154,9 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
         int rc0 = rt_frame_kernel_choice(s, &fd0, &kc0);
         if (rc0 == RT_OK) rc0 = rt_build_frame_consts(s, &fd0, nullptr, &fc0);
         if (rc0 != RT_OK) return rc0;
+        // the graph's own view lists: where it has its own eye cones and the passes' tiles nest in the blocks
+        g->views_on = want_cones && rt_view_params_for_frame(s, &fc0, g->fd.aspect, kc0.tile, kc0.cull, kc0.mode, &g->view_params) != 0;
+        if (g->views_on) RT_HIP(g->views.reserve(rt_view_lists_size(g->view_params.nbx, g->view_params.nby)));
         tg = rt_tile_grid(kc0.tile, fc0.width, fc0.local_rows);
         if (rt_scene_tile_order_mode(s) != 0 && tg.ok) {
             RT_HIP(g->order.reserve(tg));
@@ -158,6 +185,17 @@ static int build_graph(rt_frame_graph *g, hipStream_t stream)
         RT_HIP(hipGraphAddKernelNode(&g->build_node, g->graph, nullptr, 0, &g->build_params));
         g->build_params.kernelParams = nullptr;   // `args` is a local: re-pointed on every update
         prev = g->build_node;
+    }
+    if (g->views_on) {   // after the cone table it reads (a host-built one is already there)
+        memset(&g->view_kparams, 0, sizeof g->view_kparams);
+        const void *func;
+        rt_view_lists_kernel_config(g->view_params, &func, &g->view_kparams.gridDim, &g->view_kparams.blockDim);
+        g->view_kparams.func = const_cast<void *>(func);
+        void *args[] = {&g->view_params};
+        g->view_kparams.kernelParams = args;
+        RT_HIP(hipGraphAddKernelNode(&g->view_node, g->graph, prev ? &prev : nullptr, prev ? 1 : 0, &g->view_kparams));
+        g->view_kparams.kernelParams = nullptr;
+        prev = g->view_node;
     }
     if (g->order_on) {   // keys -> sort -> expand, from the durations of the previous replay
         const void *func[3];
@@ -264,6 +302,13 @@ static int update_nodes(rt_frame_graph *g)
         g->build_params.kernelParams = args;
         const hipError_t e = hipGraphExecKernelNodeSetParams(g->exec, g->build_node, &g->build_params);
         g->build_params.kernelParams = nullptr;
+        RT_HIP(e);
+    }
+    if (g->view_node) {
+        void *args[] = {&g->view_params};
+        g->view_kparams.kernelParams = args;
+        const hipError_t e = hipGraphExecKernelNodeSetParams(g->exec, g->view_node, &g->view_kparams);
+        g->view_kparams.kernelParams = nullptr;
         RT_HIP(e);
     }
     for (int p = 0; p < g->passes; ++p) {

@@ -107,6 +107,10 @@ int rt_scene_sphere_count(const rt_scene *s);
 unsigned long long rt_scene_epoch(const rt_scene *s);
 bool rt_scene_wants_eye_cones(const rt_scene *s, const float org[3]);
 int rt_scene_tile_order_mode(const rt_scene *s);   // rt_scene_set_tile_order
+// The view (block shape included) of a frame with uniforms fc, for the view-list builders; returns whether a launch of
+// that tile width / cull / mode reads view lists at all (rt_scene_set_view_lists, nesting tiles).
+struct RtViewParams;
+int rt_view_params_for_frame(const rt_scene *s, const RtFrameConsts *fc, float aspect, int tile_w, int cull, int mode, RtViewParams *p);
 int rt_scene_build_eye_cones_host(rt_scene *s, const float org[3], float4 *buf, hipStream_t stream);
 
 // launchers of rt_kernels.hip

@@ -36,6 +36,37 @@ hipError_t rt_eye_cones_launch(const float4 *tab, int n, const float org[3], flo
 // (const float4 *tab, int n, float ox, float oy, float oz, float4 *out).
 void rt_eye_cones_kernel_config(int n, int threads, const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes);
 
+// View lists (RtFrameConsts::view_lists): one view -- ray origin, rotation, eye_nz, frame size and aspect -- cut into
+// blocks of 2^bw x 2^bh pixels; per block the front-to-back list of the spheres a primary ray of the block can hit.
+// `cones`: the eye-cone table of the same origin (rt_eye_cones_launch) or null; `tab`: the scene's sphere allocation
+// ([n] list order | Morton order | blocks | positions, rt_scene::d_spheres).
+struct RtViewParams {
+    const float4 *tab;
+    const float4 *cones;
+    int n, n_blocks;
+    float org[3];
+    float cos_pitch, sin_pitch, cos_yaw, sin_yaw;
+    float eye_nz, aspect;
+    int width, height;
+    int bw, bh;                // log2 of the block's width and height in pixels
+    int nbx, nby;
+    float4 *out;               // nbx * nby slots of RT_VIEW_SLOT float4
+};
+// The block's cone as the builders hand it to the member test: unit axis and slope (ok = false: no usable cone).
+struct RtViewBeam {
+    float ux, uy, uz, k;
+    bool ok;
+};
+RtViewBeam rt_view_block_beam(const RtViewParams &p, int bx, int by);
+// Block size for a frame: 64 x 64 pixels, halved (down to a tile, 8 x 8) while the frame has fewer than 256 blocks.
+void rt_view_block_shape(int width, int height, int *bw, int *bh);
+inline size_t rt_view_lists_size(int nbx, int nby) { return (size_t)nbx * (size_t)nby * RT_VIEW_SLOT; }   // float4 units
+hipError_t rt_view_lists_launch(const RtViewParams &p, hipStream_t stream);
+// The same launch as a graph kernel node; the argument is (RtViewParams p).
+void rt_view_lists_kernel_config(const RtViewParams &p, const void **func, dim3 *grid, dim3 *block);
+// Host restatement: the member test over the whole list-order table `tab` (n entries), no block level.
+void rt_build_view_lists_host(const float4 *tab, const RtViewParams &p, float4 *out);
+
 // Order of the tiles of a launch (RtFrameConsts::tile_perm): blocks of RT_TILE_ORDER_BLOCK x RT_TILE_ORDER_BLOCK tiles,
 // the block with the longest tile first (cost[tile]: wave durations of the previous launch, shader clocks; 0 = never
 // rendered), tiles row-major inside a block; perm[] = (tile_y << 16) | tile_x. Three small kernels on `stream` (the

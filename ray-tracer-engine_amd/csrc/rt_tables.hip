@@ -11,17 +11,21 @@
 //                                                                 workgroup, bitonic sort in LDS; the
 //                                                                 host version is the fallback for
 //                                                                 lists beyond RT_EYE_DEVICE_MAX
+//   view lists            per block of the frame: the primary     DEVICE (rt_view_lists_launch), once per view:
+//                         rays' candidates, front to back         one wave per block, the frame kernel's own cull
 // The reference moves its camera every frame (checkKey, kernel.cu:1716-1759): that must not
 // cost a host-side sort, a blocking upload and a device synchronisation per frame.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <utility>
 #include <vector>
 
 #include "rt_device.h"
 #include "rt_tables.h"
+#include "rt_trace.inc"   // the view lists are built by the frame kernel's own cull (build_list2)
 
 // ---------------------------------------------------------------------------
 // shared host / device pieces
@@ -804,6 +808,199 @@ hipError_t rt_eye_cones_launch(const float4 *tab, int n, const float org[3], flo
     rt_eye_cones_kernel_config(n, threads, &func, &grid, &block, &lds);
     hipLaunchKernelGGL(rt_eye_cones_kernel, grid, block, lds, stream, tab, n, org[0], org[1], org[2], out);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// View lists. The primary cull of a tile -- its beam, the two-level cull, the front-to-back order -- depends on the
+// sphere list and the view, not on the frame: the sort key is a function of the sphere and the ray origin, and the
+// survivors of a block of 64 x 64 pixels are a quarter more than those of one of its 8 x 8 tiles. So the cull is done
+// once per VIEW and block, by the frame kernel's own build_list2<ORDERED> (same block tests, same member test and
+// paddings, same bounds, non-finite bounds first) for the block's cone, one wave per block, and the tiles of every
+// frame of that view read the result (rt_trace.inc). A block with more than RT_VIEW_CAP survivors or without a usable
+// cone says so in its header and its tiles cull for themselves, as before.
+//   The block's cone. A primary ray of pixel (x, y) and sample offset (ox, oy) in [0,1)^2 has, before normalise and
+// rotateDir, the direction (dx(x + ox), dy(y + oy), eye_nz) with dx, dy the affine, increasing binary64 expressions of
+// rt_scene_prepare_raygen narrowed to binary32 (monotone): it lies in the rectangle of the image plane spanned by the
+// block's pixel EDGES x0, x0 + BW, y0, y0 + BH, whatever the sample. The rays within an angle theta < 90 degrees of an
+// axis meet the image plane in a convex region (a conic section's inside), so the angle from the axis is quasi-convex
+// on the plane and over the rectangle largest at a corner. Axis = the normalised sum of the four corner directions,
+// rounded to binary32 as the kernel will use it; the deviation is measured from that rounded axis, in binary64, and
+// its sine padded as the tile's own beam pads it (x 1.01 + 1e-5), which also covers what separates the kernel's rays
+// from these expressions: dx, dy rounded to binary32 (6e-8 relative), its binary32 normalise and rotation (a few 1e-7
+// in the direction) and the axis' length (1 +- 1e-7).
+// ---------------------------------------------------------------------------
+RT_HDI void view_corner_dir(const RtViewParams &p, double xe, double ye, double d[3])
+{
+    const double aspect_d = (double)p.aspect, width_d = (double)(float)p.width, height_d = (double)(float)p.height;
+    const double hw_d = (double)((float)p.height / (float)p.width);
+    const double dx = aspect_d * ((2.0 * xe) / width_d) - 1.0, dy = (aspect_d * ((2.0 * ye) / height_d)) * hw_d - 1.0;
+    const double dz = (double)p.eye_nz;
+    const double l = sqrt(dx * dx + dy * dy + dz * dz);
+    const double nx = dx / l, ny = dy / l, nz = dz / l;
+    // camera::rotateDir, kernel.cu:252-257
+    const double y = ny * (double)p.cos_pitch - nz * (double)p.sin_pitch;
+    double z = ny * (double)p.sin_pitch + nz * (double)p.cos_pitch;
+    const double x = nx * (double)p.cos_yaw + z * (double)p.sin_yaw;
+    z = -nx * (double)p.sin_yaw + z * (double)p.cos_yaw;
+    d[0] = x; d[1] = y; d[2] = z;
+}
+
+RT_HDI RtViewBeam view_block_beam_hd(const RtViewParams &p, int bx, int by)
+{
+    RtViewBeam b;
+    b.ux = b.uy = b.uz = b.k = 0.f;
+    b.ok = false;
+    const int x0 = bx << p.bw, y0 = by << p.bh;
+    const int x1 = (x0 + (1 << p.bw) < p.width) ? x0 + (1 << p.bw) : p.width, y1 = (y0 + (1 << p.bh) < p.height) ? y0 + (1 << p.bh) : p.height;
+    double c[4][3], m[3] = {0, 0, 0};
+    for (int i = 0; i < 4; ++i) {
+        view_corner_dir(p, (double)((i & 1) ? x1 : x0), (double)((i & 2) ? y1 : y0), c[i]);
+        for (int k = 0; k < 3; ++k) m[k] += c[i][k];
+    }
+    const double ml = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+    if (!(ml > 1e-9) || !fin_d(ml)) return b;
+    b.ux = (float)(m[0] / ml); b.uy = (float)(m[1] / ml); b.uz = (float)(m[2] / ml);
+    const double u[3] = {b.ux, b.uy, b.uz};
+    double s2 = 0;
+    bool ahead = true;
+    for (int i = 0; i < 4; ++i) {
+        const double cx = c[i][1] * u[2] - c[i][2] * u[1], cy = c[i][2] * u[0] - c[i][0] * u[2], cz = c[i][0] * u[1] - c[i][1] * u[0];
+        const double q = cx * cx + cy * cy + cz * cz;
+        s2 = (q > s2 || q != q) ? q : s2;
+        ahead = ahead && (c[i][0] * u[0] + c[i][1] * u[1] + c[i][2] * u[2] > 0.0);
+    }
+    if (!ahead || !(s2 < 0.25)) return b;      // NaN or a block too wide to bound: its tiles cull for themselves
+    const double sn = sqrt(s2) * 1.01 + 1.0e-5;
+    b.k = (float)(sn / sqrt(1.0 - sn * sn) * 1.000001);
+    b.ok = true;
+    return b;
+}
+
+RtViewBeam rt_view_block_beam(const RtViewParams &p, int bx, int by) { return view_block_beam_hd(p, bx, by); }
+
+// 64 x 64 pixels hold every tile shape and make a list a quarter longer than a tile's own at the BASELINE sizes; the
+// builder's work is one whole-table cull per block, so small frames, whose blocks would be few and wide (at 160 x 90 a
+// 64-pixel block spans 40 degrees), get smaller ones: halved while the frame has fewer than 256 blocks, down to a tile.
+void rt_view_block_shape(int width, int height, int *bw, int *bh)
+{
+    int s = 6;
+    while (s > 3 && (long long)((width + (1 << s) - 1) >> s) * ((height + (1 << s) - 1) >> s) < 256) --s;
+    *bw = s;
+    *bh = s;
+}
+
+namespace {
+struct ViewTables {   // what build_list2 reads of the frame uniforms
+    const float *sorted, *blocks;
+    const int *orig_idx;
+    int n_blocks;
+};
+}
+
+__global__ __launch_bounds__(64) void rt_view_lists_kernel(const RtViewParams p)
+{
+    __shared__ float4 list[RT_LIST_CAP];
+    __shared__ int keys[RT_LIST_CAP];
+    __shared__ int blist[64];
+    const int lane = threadIdx.x & 63;
+    const int blk = blockIdx.x, bx = blk % p.nbx, by = blk / p.nbx;
+    const RtViewBeam vb = view_block_beam_hd(p, bx, by);
+    int count = 0, flags = RT_VIEW_NOT_BUILT;
+    if (vb.ok) {
+        Beam b;
+        b.ax = p.org[0]; b.ay = p.org[1]; b.az = p.org[2];
+        b.ux = vb.ux; b.uy = vb.uy; b.uz = vb.uz;
+        b.k = vb.k;
+        b.smin = 0.f; b.smax = 0.f;
+        b.r0 = 1.0e-4f;            // as the tile's own beam
+        const int n_pad = (p.n + 63) & ~63;
+        ViewTables t;
+        t.sorted = reinterpret_cast<const float *>(p.tab + p.n);
+        t.blocks = reinterpret_cast<const float *>(p.tab + p.n + n_pad);
+        t.orig_idx = reinterpret_cast<const int *>(p.tab + p.n + n_pad + p.n_blocks);
+        t.n_blocks = p.n_blocks;
+        unsigned long long unused = 0;
+        const int c = (p.cones && b.k <= (float)RT_CONE_KCAP)
+                          ? build_list2<0, false, true, 2>(t, p.n, list, keys, blist, b, lane, unused, p.cones, p.cones + n_pad,
+                                                           reinterpret_cast<const int *>(p.cones + n_pad + 2 * (size_t)p.n_blocks))
+                          : build_list2<0, false, true>(t, p.n, list, keys, blist, b, lane, unused);
+        flags = (c > RT_VIEW_CAP) ? RT_VIEW_OVERFLOW : 0;
+        count = (c > RT_VIEW_CAP) ? 0 : c;
+    }
+    float4 *slot = p.out + (size_t)blk * RT_VIEW_SLOT;
+    if (lane < count) {
+        slot[1 + lane] = list[lane];
+        reinterpret_cast<int *>(slot + 1 + RT_VIEW_CAP)[lane] = keys[lane];
+        // (a list of one is not ordered: it has no bounds, and the walk reads none)
+        reinterpret_cast<float *>(slot + 1 + RT_VIEW_CAP + RT_VIEW_CAP / 4)[lane] = count > 1 ? reinterpret_cast<const float *>(blist)[lane] : 0.f;
+    }
+    if (lane == 0) *reinterpret_cast<int4 *>(slot) = make_int4(count, flags, 0, 0);
+}
+
+void rt_view_lists_kernel_config(const RtViewParams &p, const void **func, dim3 *grid, dim3 *block)
+{
+    *func = (const void *)rt_view_lists_kernel;
+    *grid = dim3((unsigned)(p.nbx * p.nby));
+    *block = dim3(64);
+}
+
+hipError_t rt_view_lists_launch(const RtViewParams &p, hipStream_t stream)
+{
+    if (p.n < 1 || p.nbx < 1 || p.nby < 1 || !p.tab || !p.out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_view_lists_kernel, dim3((unsigned)(p.nbx * p.nby)), dim3(64), 0, stream, p);
+    return hipGetLastError();
+}
+
+// The host restatement: beam_member_test and the bound of build_list2 in the same binary32 operations (this file is
+// compiled without contraction on both sides; the device's square root may differ from sqrtf in the last place), over
+// the whole list -- the block level only ever drops what the member test drops.
+static bool view_member_host(const RtViewBeam &b, const float org[3], float4 s)
+{
+    const float vx = s.x - org[0], vy = s.y - org[1], vz = s.z - org[2];
+    const float vv = fmaf(vx, vx, fmaf(vy, vy, vz * vz));
+    const float sa = fmaf(vx, b.ux, fmaf(vy, b.uy, vz * b.uz));
+    const float d2 = fmaxf(fmaf(-sa, sa, vv), 0.f);
+    const float pad = fmaf(RT_PAD_REL, vv, RT_PAD_ABS);
+    const float rc = sqrtf(s.w + pad) * 1.0001f;
+    const float reach = sa + rc - 0.f;
+    const float rad = fmaf(b.k, fmaxf(reach, 0.f), 1.0e-4f) + rc;
+    return reach >= 0.f && d2 <= rad * rad * 1.0005f;
+}
+
+static float view_bound_host(const float org[3], float4 e)
+{
+    const float vx = e.x - org[0], vy = e.y - org[1], vz = e.z - org[2];
+    const float vv = fmaf(vx, vx, fmaf(vy, vy, vz * vz));
+    const float dist = sqrtf(vv), rr = sqrtf(e.w);
+    const float slack = fmaf(1.5e-3f, dist + rr, 1.0e-3f);
+    const float lb = (vv > e.w * 1.001f + 1.0e-6f) ? (dist - rr) - slack : -(dist + rr) - slack;
+    return (lb == lb) ? lb : -INFINITY;
+}
+
+void rt_build_view_lists_host(const float4 *tab, const RtViewParams &p, float4 *out)
+{
+    std::vector<std::pair<float, int>> keep;
+    for (int blk = 0; blk < p.nbx * p.nby; ++blk) {
+        float4 *slot = out + (size_t)blk * RT_VIEW_SLOT;
+        for (int i = 0; i < RT_VIEW_SLOT; ++i) slot[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        const RtViewBeam b = view_block_beam_hd(p, blk % p.nbx, blk / p.nbx);
+        int count = 0, flags = RT_VIEW_NOT_BUILT;
+        if (b.ok) {
+            keep.clear();
+            for (int i = 0; i < p.n; ++i)
+                if (view_member_host(b, p.org, tab[i])) keep.push_back({view_bound_host(p.org, tab[i]), i});
+            flags = (int)keep.size() > RT_VIEW_CAP ? RT_VIEW_OVERFLOW : 0;
+            count = flags ? 0 : (int)keep.size();
+            if (!flags) std::stable_sort(keep.begin(), keep.end(), [](const std::pair<float, int> &a, const std::pair<float, int> &c) { return a.first < c.first; });
+        }
+        for (int e = 0; e < count; ++e) {
+            slot[1 + e] = tab[keep[e].second];
+            reinterpret_cast<int *>(slot + 1 + RT_VIEW_CAP)[e] = keep[e].second;
+            reinterpret_cast<float *>(slot + 1 + RT_VIEW_CAP + RT_VIEW_CAP / 4)[e] = count > 1 ? keep[e].first : 0.f;
+        }
+        int hdr[4] = {count, flags, 0, 0};
+        memcpy(slot, hdr, sizeof hdr);
+    }
 }
 
 // ---------------------------------------------------------------------------

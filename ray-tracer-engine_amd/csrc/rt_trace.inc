@@ -55,7 +55,9 @@ namespace {
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const RtFrameAux __attribute__((address_space(4))) *AuxPtr;
 typedef const RtFrameConsts __attribute__((address_space(4))) *FcPtr;
+typedef const int __attribute__((address_space(4))) *ConstIntPtr;
 #else
+typedef const int *ConstIntPtr;
 typedef const RtFrameAux *AuxPtr;   // host pass over this translation unit (device functions are only parsed there)
 typedef const RtFrameConsts *FcPtr;
 #endif
@@ -1351,8 +1353,35 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 
     float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f;
 
+    // The view list of the block of the frame this tile lies in (RtFrameConsts::view_lists), by the tile's frame
+    // coordinates alone: what the primary cull below would compute, built once per view (rt_tables.hip).
+    constexpr bool VIEW = CULL && !force_slow;
+    const float4 *vslot = nullptr;
+    if (VIEW && fc.view_lists) {
+        const int ly0 = (int)blk_y * TH;
+        const int py0 = fc.y0 + ((((ly0 >> il_sh) * fc.il_count + fc.il_index) << il_sh) | (ly0 & (fc.il_rows - 1)));
+        const int vblk = __builtin_amdgcn_readfirstlane((py0 >> (fc.view_shift >> 8)) * fc.view_nbx + (tile_x >> (fc.view_shift & 255)));
+        vslot = reinterpret_cast<const float4 *>(fc.view_lists) + (size_t)vblk * RT_VIEW_SLOT;
+    }
+
     const int n_samples = MULTI ? fc.spp : 1;
     for (int sample = 0; sample < n_samples; ++sample) {
+        // header (a scalar load) and this lane's entry of the block's list: asked for here, ahead of the ray
+        // arithmetic, and consumed after it. The slot is whole whatever its count, so the entry does not wait for the
+        // header. A multi-sample launch fetches the list again for every sample (the light loop re-uses its LDS).
+        int v_count = 0;
+        bool v_use = false;
+        float4 v_ent = make_float4(0.f, 0.f, 0.f, 0.f);
+        int v_key = 0;
+        float v_lb = 0.f;
+        if (VIEW && vslot) {
+            const ConstIntPtr vh = (ConstIntPtr)(uintptr_t)vslot;
+            v_count = vh[0];
+            v_use = vh[1] == 0;
+            v_ent = vslot[1 + lane];
+            v_key = reinterpret_cast<const int *>(vslot + 1 + RT_VIEW_CAP)[lane];
+            v_lb = reinterpret_cast<const float *>(vslot + 1 + RT_VIEW_CAP + RT_VIEW_CAP / 4)[lane];
+        }
         // ================= primary ray, kernel.cu:1624-1631 =================
         // dx, dy of kernel.cu:1624-1625 (binary64 expressions of the column resp. the row) come
         // from the frame's tables, evaluated by the host with the reference's operations; lanes
@@ -1383,24 +1412,39 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         Beam pbeam;                // the tile's primary beam, kept for the per-triangle cull of the mesh leaves
         bool pbeam_ok = false;
         if (CULL) {
-            // cone around the tile's mean direction, apex at the (shared) origin
-            float sx = D.x, sy = D.y, sz = D.z;
-            wave_sum3(sx, sy, sz);
-            const float inv = __builtin_amdgcn_rsqf(__builtin_fmaf(sx, sx, __builtin_fmaf(sy, sy, sz * sz)));
             Beam b;
-            b.ux = uniform(sx * inv); b.uy = uniform(sy * inv); b.uz = uniform(sz * inv);
-            const float cx = D.y * b.uz - D.z * b.uy, cy = D.z * b.ux - D.x * b.uz, cz = D.x * b.uy - D.y * b.ux;
-            float s2 = wave_max(__builtin_fmaf(cx, cx, __builtin_fmaf(cy, cy, cz * cz)));
-            s2 = uniform(s2);
-            // s2 is sin^2 of the largest deviation (|D| = 1 up to rounding)
-            const bool ok = (s2 < 0.25f);   // NaN or a degenerate tile: do not cull
-            const float sn = __builtin_amdgcn_sqrtf(s2) * 1.01f + 1.0e-5f;
-            b.k = sn * __builtin_amdgcn_rsqf(1.f - sn * sn);
-            b.ax = O.x; b.ay = O.y; b.az = O.z;
-            b.smin = 0.f;
-            b.smax = 0.f;
-            b.r0 = 1.0e-4f;
-            if (ok) {
+            bool ok = false;
+            if (!v_use || MESH) {
+                // cone around the tile's mean direction, apex at the (shared) origin
+                float sx = D.x, sy = D.y, sz = D.z;
+                wave_sum3(sx, sy, sz);
+                const float inv = __builtin_amdgcn_rsqf(__builtin_fmaf(sx, sx, __builtin_fmaf(sy, sy, sz * sz)));
+                b.ux = uniform(sx * inv); b.uy = uniform(sy * inv); b.uz = uniform(sz * inv);
+                const float cx = D.y * b.uz - D.z * b.uy, cy = D.z * b.ux - D.x * b.uz, cz = D.x * b.uy - D.y * b.ux;
+                float s2 = wave_max(__builtin_fmaf(cx, cx, __builtin_fmaf(cy, cy, cz * cz)));
+                s2 = uniform(s2);
+                // s2 is sin^2 of the largest deviation (|D| = 1 up to rounding)
+                ok = (s2 < 0.25f);   // NaN or a degenerate tile: do not cull
+                const float sn = __builtin_amdgcn_sqrtf(s2) * 1.01f + 1.0e-5f;
+                b.k = sn * __builtin_amdgcn_rsqf(1.f - sn * sn);
+                b.ax = O.x; b.ay = O.y; b.az = O.z;
+                b.smin = 0.f;
+                b.smax = 0.f;
+                b.r0 = 1.0e-4f;
+            }
+            if (v_use) {
+                // the block's list as it stands: a superset of what this tile's own cull would keep, in the order and
+                // with the positions and bounds the walk below expects (no block pass, no member step, no sort)
+                // (filtering it first with the tile's own beam -- one member test, ballot compaction -- costs the beam
+                // it was meant to save: 0.202 against 0.194 ms at C3, profiles/view_lists_ab.json)
+                mylist[lane] = v_ent;
+                mykeys[lane] = v_key;
+                reinterpret_cast<float *>(myblks)[lane] = v_lb;
+                wave_lds_sync();
+                p_use_list = true;
+                pcount = v_count;
+                if (STATS == 1) st_entries += (unsigned long long)v_count;
+            } else if (ok) {
                 // eye cones when the scene has them and the tile's beam is within their slope limit
                 const float4 *csorted = reinterpret_cast<const float4 *>(fc.csorted);
                 const int c = (csorted && b.k <= fc.cone_kcap)
@@ -1415,16 +1459,16 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     st_overflow += 1;
                 }
                 if (STATS == 1) st_entries += (unsigned long long)(c <= RT_LIST_CAP ? c : n);
-                if (MESH) {
-                    const int cb = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_BOX_CAP, b, lane);
-                    if (cb <= RT_BOX_CAP) {
-                        pb_use_list = true;
-                        pbcount = cb;
-                    }
-                    pbeam = b;
-                    pbeam_ok = !force_slow;
-                    if (STATS == 1) sm_plisted += (unsigned long long)pbcount;
+            }
+            if (MESH && ok) {
+                const int cb = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_BOX_CAP, b, lane);
+                if (cb <= RT_BOX_CAP) {
+                    pb_use_list = true;
+                    pbcount = cb;
                 }
+                pbeam = b;
+                pbeam_ok = !force_slow;
+                if (STATS == 1) sm_plisted += (unsigned long long)pbcount;
             }
         }
 
