@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "../../include/rt_engine.h"
 #include "rt_device.h"
 
@@ -84,7 +86,44 @@ struct HipStream : HipHandle<hipStream_t, hipStreamDestroy> {
     hipError_t create(unsigned flags, int priority) { return h_ ? hipSuccess : hipStreamCreateWithPriority(&h_, flags, priority); }
 };
 
+// An event that may still be pending: recorded on one stream, and whatever must follow it -- on any stream, or on the
+// host -- asks this owner instead of keeping a flag beside the event. Once the event has been seen complete nobody
+// waits on it again.
+class HipPendingEvent {
+public:
+    hipError_t record(hipStream_t stream)   // created on first use
+    {
+        hipError_t e = ev_.create();
+        if (e == hipSuccess) e = hipEventRecord(ev_.get(), stream);
+        if (e == hipSuccess) pending_ = true;
+        return e;
+    }
+    // What `stream` does next follows the last record(): a device-side wait, and none once the event is complete.
+    hipError_t order(hipStream_t stream)
+    {
+        if (!pending_) return hipSuccess;
+        if (hipEventQuery(ev_.get()) == hipSuccess) {
+            pending_ = false;
+            return hipSuccess;
+        }
+        (void)hipGetLastError();   // "not ready" is reported as an error
+        return hipStreamWaitEvent(stream, ev_.get(), 0);
+    }
+    hipError_t host_wait()
+    {
+        const hipError_t e = pending_ ? hipEventSynchronize(ev_.get()) : hipSuccess;
+        if (e == hipSuccess) pending_ = false;
+        return e;
+    }
+    bool pending() const { return pending_; }
+
+private:
+    HipEvent ev_;
+    bool pending_ = false;
+};
+
 struct rt_scene;
+struct RtTableSlot;   // rt_scene.h
 
 // which instantiation of the frame kernel renders a frame (rt_kernels.hip: TW, CULL, MODE, FEAT)
 struct RtKernelChoice {
@@ -98,9 +137,10 @@ int rt_scene_prepare_static(rt_scene *s, const rt_frame_desc *fd, hipStream_t st
 int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const float4 *cones, RtFrameConsts *fc);
 int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelChoice *kc);
 void rt_ray_origin(const rt_frame_desc *fd, float org[3]);
-// frames in flight (rt_engine.cpp): host wait for all of them; bookkeeping after a launch
+// frames in flight (rt_scene.cpp): host wait for all of them; bookkeeping after a launch that read the scene's cached
+// eye-cone table `cones` and view lists `views` (null: it read none of its own)
 int rt_scene_quiesce(rt_scene *s);
-int rt_scene_note_launch(rt_scene *s, hipStream_t stream, int cone_slot);
+int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, RtTableSlot *views);
 // what a graph node needs from the scene
 const float4 *rt_scene_sphere_table(const rt_scene *s);
 int rt_scene_sphere_count(const rt_scene *s);
@@ -112,6 +152,21 @@ int rt_scene_tile_order_mode(const rt_scene *s);   // rt_scene_set_tile_order
 struct RtViewParams;
 int rt_view_params_for_frame(const rt_scene *s, const RtFrameConsts *fc, float aspect, int tile_w, int cull, int mode, RtViewParams *p);
 int rt_scene_build_eye_cones_host(rt_scene *s, const float org[3], float4 *buf, hipStream_t stream);
+
+// rt_shim.cpp: memManager::operator delete on something the shim has mirrored
+void rt_shim_forget(const void *ptr);
+
+// rt_mesh.cpp: the reference-layout mesh (triangles, leaf boxes with their own index arrays) flattened into the arrays
+// the device reads -- pure host computation, validation of the leaves included
+struct RtFlatMesh {
+    std::vector<RtTriDev> tris;
+    std::vector<RtBoxDev> boxes;     // {bounds, start, len} into idx
+    std::vector<int> idx;
+    std::vector<float> box_spheres;  // leaf spheres, padded to RT_BLOCK, then one per block of leaves
+    std::vector<float> tri9;         // vertices per (leaf, triangle) pair, padded by 64 floats
+    std::vector<float> tri_bs, tri_nrm;   // per pair: bounding sphere; unit normal and kappa
+};
+int rt_mesh_flatten(const rt_mesh *mesh, RtFlatMesh *out);
 
 // launchers of rt_kernels.hip
 extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int feat,

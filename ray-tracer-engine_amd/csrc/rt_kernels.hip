@@ -202,7 +202,7 @@ RtTraceFn rt_trace_fn_cull8(int mode, int feat, int multi)
 
 
 // ---------------------------------------------------------------------------
-// host-side launchers (called from rt_engine.cpp / rt_graph.cpp)
+// host-side launchers (called from rt_render.cpp / rt_debug.cpp / rt_graph.cpp)
 // ---------------------------------------------------------------------------
 // The instantiations that exist: trace_exists() in rt_trace.inc. Tile widths other than 8 are test dimensions, and
 // MODE 3 (phase stamps) exists in RT_TUNING builds only. Everything but the default tile's culling kernels lives in

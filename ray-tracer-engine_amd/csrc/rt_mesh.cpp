@@ -13,9 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rt_engine.h"
+#include <algorithm>
 
-void rt_set_error(const char *fmt, ...);
+#include "rt_internal.h"
 
 namespace {
 
@@ -327,4 +327,129 @@ extern "C" void rt_mesh_free(rt_mesh *m)
     free(m->h_tri_arr);
     free(m->indexes);
     free(m);
+}
+
+// The mesh as the device reads it (RtFlatMesh, rt_internal.h): triangles, leaf boxes {bounds, start, len} with one
+// shared index array, and the spheres, normals and kappa the beam culls test. No GPU needed.
+int rt_mesh_flatten(const rt_mesh *mesh, RtFlatMesh *out)
+{
+    std::vector<RtTriDev> &tris = out->tris;
+    std::vector<RtBoxDev> &boxes = out->boxes;
+    std::vector<int> &idx = out->idx;
+    std::vector<float> &bsph = out->box_spheres, &t9 = out->tri9, &bs = out->tri_bs, &bn = out->tri_nrm;
+    tris.assign((size_t)mesh->poly_count, RtTriDev{});
+    for (int i = 0; i < mesh->poly_count; ++i) {
+        const rt_triangle &t = mesh->d_tri_arr[i];
+        RtTriDev &d = tris[i];
+        memset(&d, 0, sizeof d);
+        memcpy(d.p0, &t.points[0], 12); memcpy(d.p1, &t.points[1], 12); memcpy(d.p2, &t.points[2], 12);
+        memcpy(d.n, &t.normal, 12);
+        memcpy(d.vn, t.vecNormal, 36);
+        memcpy(d.vt, t.vt, 24);
+    }
+    boxes.assign((size_t)mesh->bvhbox_count, RtBoxDev{});
+    bsph.assign((size_t)mesh->bvhbox_count * 4, 0.f);   // bounding sphere of each leaf (for beam culling)
+    idx.clear();
+    for (int j = 0; j < mesh->bvhbox_count; ++j) {
+        const rt_bvhbox &b = mesh->d_box[j];
+        const rt_cube *c = b.d_bvhbox ? b.d_bvhbox : b.bvhbox;
+        if (!c || !b.d_indexes || b.length < 0) {
+            rt_set_error("rt_scene_set_mesh: leaf %d is incomplete", j);
+            return RT_ERR_INVALID;
+        }
+        RtBoxDev &d = boxes[j];
+        d.lo[0] = c->bounds[0].x; d.lo[1] = c->bounds[0].y; d.lo[2] = c->bounds[0].z;
+        d.hi[0] = c->bounds[1].x; d.hi[1] = c->bounds[1].y; d.hi[2] = c->bounds[1].z;
+        {
+            const double cx = 0.5 * ((double)d.lo[0] + d.hi[0]), cy = 0.5 * ((double)d.lo[1] + d.hi[1]),
+                         cz = 0.5 * ((double)d.lo[2] + d.hi[2]);
+            const double hx = 0.5 * std::fabs((double)d.hi[0] - d.lo[0]), hy = 0.5 * std::fabs((double)d.hi[1] - d.lo[1]),
+                         hz = 0.5 * std::fabs((double)d.hi[2] - d.lo[2]);
+            bsph[4 * j + 0] = (float)cx; bsph[4 * j + 1] = (float)cy; bsph[4 * j + 2] = (float)cz;
+            bsph[4 * j + 3] = (float)((hx * hx + hy * hy + hz * hz) * 1.001 + 1e-6);   // radius^2, rounded up
+        }
+        d.start = (int)idx.size();
+        d.len = b.length;
+        for (int i = 0; i < b.length; ++i) {
+            if (b.d_indexes[i] < 0 || b.d_indexes[i] >= mesh->poly_count) {
+                rt_set_error("rt_scene_set_mesh: leaf %d references triangle %d of %d", j, b.d_indexes[i], mesh->poly_count);
+                return RT_ERR_INVALID;
+            }
+            idx.push_back(b.d_indexes[i]);
+        }
+    }
+    {   // blocks of RT_BLOCK consecutive leaves (leaf order is kept: it decides ties between triangles),
+        // each with a sphere around its members' spheres, appended after the (padded) leaf spheres
+        const int nb = mesh->bvhbox_count, nb_pad = (nb + RT_BLOCK - 1) / RT_BLOCK * RT_BLOCK, nblk = nb_pad / RT_BLOCK;
+        bsph.resize((size_t)(nb_pad + nblk) * 4, 0.f);
+        for (int j = nb; j < nb_pad; ++j) bsph[4 * (size_t)j + 3] = -1.f;
+        for (int k = 0; k < nblk; ++k) {
+            const int j0 = k * RT_BLOCK, j1 = std::min(nb, j0 + RT_BLOCK);
+            double cx = 0, cy = 0, cz = 0;
+            for (int j = j0; j < j1; ++j) { cx += bsph[4 * (size_t)j]; cy += bsph[4 * (size_t)j + 1]; cz += bsph[4 * (size_t)j + 2]; }
+            const double inv = 1.0 / std::max(1, j1 - j0);
+            const float cf[3] = {(float)(cx * inv), (float)(cy * inv), (float)(cz * inv)};
+            double r = 0;
+            for (int j = j0; j < j1; ++j) {
+                const double dx = bsph[4 * (size_t)j] - (double)cf[0], dy = bsph[4 * (size_t)j + 1] - (double)cf[1],
+                             dz = bsph[4 * (size_t)j + 2] - (double)cf[2];
+                const double d = std::sqrt(dx * dx + dy * dy + dz * dz) + std::sqrt(std::max(0.0, (double)bsph[4 * (size_t)j + 3]));
+                r = (d > r || d != d) ? d : r;   // a NaN sticks
+            }
+            float rf = (float)(r * 1.001 + 1e-3);
+            const bool fin = std::isfinite(cf[0]) && std::isfinite(cf[1]) && std::isfinite(cf[2]) && rf == rf;
+            float *o = &bsph[4 * (size_t)(nb_pad + k)];
+            o[0] = fin ? cf[0] : 0.f; o[1] = fin ? cf[1] : 0.f; o[2] = fin ? cf[2] : 0.f;
+            o[3] = fin ? rf : INFINITY;
+        }
+    }
+    {   // vertices per (leaf, triangle) pair, de-indexed and padded by 64 floats so that a full-wave load stays inside
+        t9.assign(idx.size() * 9 + 64, 0.f);
+        for (size_t k = 0; k < idx.size(); ++k) {
+            memcpy(&t9[9 * k + 0], tris[idx[k]].p0, 12);
+            memcpy(&t9[9 * k + 3], tris[idx[k]].p1, 12);
+            memcpy(&t9[9 * k + 6], tris[idx[k]].p2, 12);
+        }
+        // bounding sphere of every (leaf, triangle) pair for the per-triangle beam cull (beam_keeps_triangle):
+        // centre = centroid, radius = farthest vertex, rounded up; with it the unit normal and kappa, the least
+        // |cos| between a ray and the normal for which the cull is valid (slivers and anything non-finite: radius
+        // +inf, normal 0, kappa 2 -- never culled)
+        bs.assign(idx.size() * 4 + 4 * 64, 0.f);
+        bn.assign(idx.size() * 4 + 4 * 64, 0.f);   // unit normals (zero = "always edge-on" for degenerate ones)
+        for (size_t k = 0; k < idx.size(); ++k) {
+            const float *p = &t9[9 * k];
+            double c[3], r = 0, e[3][3], len[3];
+            for (int a = 0; a < 3; ++a) c[a] = ((double)p[a] + p[3 + a] + p[6 + a]) / 3.0;
+            for (int v = 0; v < 3; ++v) {
+                double d2 = 0;
+                for (int a = 0; a < 3; ++a) d2 += ((double)p[3 * v + a] - c[a]) * ((double)p[3 * v + a] - c[a]);
+                r = std::max(r, std::sqrt(d2));
+            }
+            for (int v = 0; v < 3; ++v) {   // edge v: from vertex v to vertex (v+1)%3
+                len[v] = 0;
+                for (int a = 0; a < 3; ++a) {
+                    e[v][a] = (double)p[3 * ((v + 1) % 3) + a] - p[3 * v + a];
+                    len[v] += e[v][a] * e[v][a];
+                }
+                len[v] = std::sqrt(len[v]);
+            }
+            const double cx = e[0][1] * e[1][2] - e[0][2] * e[1][1], cy = e[0][2] * e[1][0] - e[0][0] * e[1][2],
+                         cz = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+            const double area2 = std::sqrt(cx * cx + cy * cy + cz * cz);   // |e0 x e1| = twice the area
+            double min_sin = INFINITY;
+            for (int v = 0; v < 3; ++v) min_sin = std::min(min_sin, area2 / (len[v] * len[(v + 2) % 3]));
+            // kappa = 3e-3 / (smallest corner sine), see beam_keeps_triangle; >= 1 means "never culled"
+            const bool good = std::isfinite(r) && std::isfinite(c[0] + c[1] + c[2]) && min_sin > 3.0e-3 && min_sin == min_sin &&
+                              area2 > 0 && std::isfinite(area2);
+            bs[4 * k + 0] = (float)c[0]; bs[4 * k + 1] = (float)c[1]; bs[4 * k + 2] = (float)c[2];
+            bs[4 * k + 3] = good ? (float)(r * 1.001 + 1e-6) : INFINITY;
+            if (good) {
+                bn[4 * k + 0] = (float)(cx / area2); bn[4 * k + 1] = (float)(cy / area2); bn[4 * k + 2] = (float)(cz / area2);
+                bn[4 * k + 3] = (float)(3.0e-3 / min_sin * 1.001);
+            } else {
+                bn[4 * k + 3] = 2.f;
+            }
+        }
+    }
+    return RT_OK;
 }

@@ -1,0 +1,202 @@
+// rt_scene.h -- struct rt_scene and what its own translation units share (rt_scene.cpp, rt_scene_tables.cpp,
+// rt_render.cpp, rt_shim.cpp, rt_debug.cpp). Everything else goes through the functions of rt_internal.h.
+//
+// Frames in flight and the buffers they read. A frame is asynchronous work on the caller's stream; the scene's device
+// buffers may be read by frames on several streams at once (two frames in flight, a replaying graph). Whoever is about
+// to overwrite or free such a buffer first waits for the frames launched so far -- not for the whole device:
+//   * every launch records an event into a ring of RT_RING slots; before a slot is re-used the launching stream waits
+//     on the event it held, so "the ring's events are done" implies "every earlier frame is done";
+//   * rare mutations (sphere list, lights, textures, resolution) wait on the host for the ring (rt_scene_quiesce) and
+//     then change the buffers in place;
+//   * the per-frame mutations, the eye-cone table and the view lists of a moving camera, never wait on the host: each
+//     rotates through a few RtTableSlot buffers and is handed over by the four functions below.
+//
+// The hand-over of a cached table (rt_scene_begin_build / end_build / order_reader / note_launch). The contract:
+//   (a) builds run on the scene's table stream, never on the frame's -- beside frame k's kernel, not in front of frame
+//       k+1's. The exception is the host build of an eye-cone table beyond RT_EYE_DEVICE_MAX, which quiesces, uploads
+//       blocking on the caller's stream and leaves nothing pending;
+//   (b) a view-list build follows the cone build it reads because both are on the table stream, or because the host
+//       build has finished;
+//   (c) a reader waits on the build event on the device only; the host never waits for a build, except in
+//       rt_scene_view_lists_info;
+//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's event;
+//   (e) the tile order keeps one event for all layouts; a new layout or a re-sort first makes the launching stream
+//       wait for every ring event;
+//   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
+//       scratch;
+//   (g) whatever rewrites or re-allocates a buffer a recorded graph may point into bumps `epoch`, and nothing else
+//       does: of the hand-over functions only an rt_scene_begin_build whose buffer re-allocates.
+#pragma once
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "rt_internal.h"
+#include "rt_tables.h"
+
+#define RT_RING 4
+#define RT_CONE_SLOTS 3
+#define RT_VIEW_SLOTS 4
+
+// One cached device table of a few: built on the table stream after the slot's last reader (through the frame ring),
+// read after `built` (on the device).
+struct RtTableSlot {
+    DevArray<float4> buf;
+    bool valid = false;
+    bool used = false;                    // read by some launch since it was built
+    unsigned long long last_use = 0;      // ring sequence number of the last launch that read it
+    HipPendingEvent built;                // the build on the scene's table stream
+};
+struct ConeSlot : RtTableSlot {
+    float org[3] = {0, 0, 0};
+    unsigned long long gen = ~0ull;       // sphere_gen the table was built from
+};
+// View lists (RtFrameConsts::view_lists, rt_tables.hip): one table per recent view, built after the eye-cone table it reads.
+struct ViewSlot : RtTableSlot {
+    unsigned key[18] = {};                // compared by bits: sphere_gen, origin, rotation, eye_nz, aspect, frame size, sample total, block shape
+    int nbx = 0, nby = 0, bw = 0, bh = 0;
+};
+
+// The slot a new table replaces: a free one (is_free: it holds nothing a frame could ask for) before an occupied one;
+// among occupied ones a never-read one before a read one; then the least recently read.
+template <typename Slot, size_t N, typename IsFree>
+Slot &rt_slot_victim(Slot (&slots)[N], IsFree is_free)
+{
+    Slot *v = &slots[0];
+    for (Slot &c : slots) {
+        const bool c_free = is_free(c), v_free = is_free(*v);
+        if ((c_free && !v_free) || (c_free == v_free && (!c.used || (v->used && c.last_use < v->last_use)))) v = &c;
+    }
+    return *v;
+}
+
+struct RtReflectDeleter {
+    void operator()(RtReflect *r) const { rt_reflect_destroy(r); }
+};
+
+#define RT_ORDER_SLOTS 4
+#define RT_ORDER_EVERY 32            // an unchanged view: the order is sorted again from fresh durations every so many launches
+#ifndef RT_ORDER_MOVING
+#define RT_ORDER_MOVING 3            // a view that keeps changing: every so many
+#endif
+struct TileOrder {
+    int key[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // tile width, frame width / height, y0, y1, local rows, interleave
+                                                  // count / index / rows, and which kernel: cull, mode, samples
+    RtTileOrderBuf buf;                          // empty: the slot has had no layout yet
+    RtTileGrid grid = {};
+    float view[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // camera and sphere list the last launch saw
+    int same_view = 0;                           // consecutive launches of that view so far
+    int since_sort = 0;                          // launches (all of which recorded durations) since the order was sorted / reset
+    bool have_perm = false;
+    unsigned long long last_use = 0;
+};
+
+struct rt_scene {
+    DevArray<float4> d_spheres;      // [n] list order | [n_pad] Morton order | [n_blocks] block bounds | [n_pad] ints
+    int n_spheres = 0;
+    int n_blocks = 0;
+    std::vector<float4> h_prev;      // what was uploaded last (skip identical re-mirrors)
+    PinnedArray<float4> h_stage;     // staging for asynchronous re-uploads
+    HipPendingEvent stage_done;      // the last upload out of h_stage
+    DevArray<float> d_tex[3];
+    int tex_w = 0, tex_h = 0;
+    DevArray<float> d_sky[3];
+    int sky_w = 0, sky_h = 0;
+    float sky_c[3] = {0, 0, 0};
+    float sky_radius = 0;        // the sphere's `radius` field (already r*r)
+    bool have_sky = false;
+    rt_light lights[RT_MAX_LIGHTS];
+    int n_lights = 0;
+    DevArray<RtPlaneDev> d_planes;
+    DevArray<RtCubeDev> d_cubes;
+    int n_planes = 0, n_cubes = 0;
+    DevArray<RtTriDev> d_tris;
+    DevArray<RtBoxDev> d_boxes;
+    DevArray<int> d_tri_idx;
+    DevArray<float> d_box_spheres, d_tri9, d_tri_bs, d_tri_nrm;
+    int n_boxes = 0, n_tris = 0, mesh_has_normals = 0;
+    // per-light column blocks (see RtFrameAux::lsorted): one allocation, rebuilt when the
+    // sphere list or a light's position changes
+    DevArray<float4> d_light_tabs;
+    // per-light occluder lists (rt_build_occluder_lists): [n_lights][n] headers, then the lights' entry arrays
+    DevArray<char> d_cand;
+    size_t cand_ent_off[RT_MAX_LIGHTS] = {};   // byte offset of light i's entries in d_cand (headers: i * n * 16)
+    bool cand_valid[RT_MAX_LIGHTS] = {};
+    float cand_pos[RT_MAX_LIGHTS][3];    // light position each list set was built for
+    unsigned long long cand_gen = ~0ull;
+    int cand_n_lights = 0;
+    unsigned long long sphere_gen = 0;   // bumped whenever the mirrored sphere list changes
+    unsigned long long ltab_gen = ~0ull; // sphere_gen the light tables were built from
+    int ltab_n_lights = 0;
+    float ltab_axis[RT_MAX_LIGHTS][3];   // axis each table was built for
+    bool ltab_valid[RT_MAX_LIGHTS] = {};
+    // eye cones for the primary rays (see RtFrameConsts::csorted), one table per recent ray origin
+    ConeSlot cones[RT_CONE_SLOTS];
+    // dx / dy of the primary rays per column / row and sample (RtFrameConsts::dx_tab)
+    DevArray<float> d_raygen;
+    int rg_w = 0, rg_h = 0, rg_total = 0;
+    float rg_aspect = 0.f;
+    // RtFrameAux as uploaded last
+    RtFrameAux h_aux;
+    DevArray<RtFrameAux> d_aux;
+    bool aux_valid = false;
+    // where the slots' builds run: beside the frames, not in front of them
+    HipStream table_stream;
+    // frames in flight
+    HipEvent ring[RT_RING];
+    bool ring_used[RT_RING] = {};
+    unsigned long long ring_seq = 0;     // sequence number of the next launch
+    // bumped whenever a buffer a recorded graph may point into is rewritten or re-allocated
+    unsigned long long epoch = 0;
+    // order of the tiles within a launch (RtFrameConsts::tile_perm / tile_cost, rt_tables.hip): per launch
+    // layout (which rows of which frame, tile shape) the tiles' wave durations as the frame kernel records
+    // them and, rebuilt from those every RT_ORDER_EVERY launches, the order that starts the longest first
+    TileOrder orders[RT_ORDER_SLOTS];
+    unsigned long long order_clock = 0;      // for least-recently-used replacement
+    int tile_order_mode = 1;                 // rt_scene_set_tile_order
+    HipPendingEvent order_built;             // the last rebuild; launches on other streams wait for it on the device
+    // per-view candidate lists of the primary rays
+    ViewSlot views[RT_VIEW_SLOTS];
+    int view_lists_mode = 1;                 // rt_scene_set_view_lists
+    int view_last = -1;                      // the slot the last launch read, -1: it read none
+    // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
+    std::unique_ptr<RtReflect, RtReflectDeleter> refl;
+    // the denoiser's scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand; `dn_done`
+    // orders the scene's denoise calls on the device, whatever their streams
+    DevArray<float4> dn_col[2], dn_guide;
+    DevArray<int> dn_key;
+    HipPendingEvent dn_done;
+    HipEvent dn_ev[RT_DENOISE_MAX_ITERATIONS + 2];   // rt_scene_set_denoise_timing
+    bool dn_timing = false;
+    int dn_timed = 0;                                // events the last timed call recorded
+#ifdef RT_TUNING
+    int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
+#endif
+};
+
+// rt_scene.cpp
+int rt_scene_wait_all_frames(rt_scene *s, hipStream_t stream);   // `stream` waits for every frame launched so far (no host wait)
+// Begin a build into slot c of `total` float4: quiesces before the buffer is freed (it grows; epoch++) or written from
+// the host (on_host); otherwise orders the table stream after the slot's last reader and an upload in flight, and the
+// caller launches the build there. End it: records the build. A reader's stream: ordered behind the build.
+int rt_scene_begin_build(rt_scene *s, RtTableSlot &c, size_t total, bool on_host);
+int rt_scene_end_build(rt_scene *s, RtTableSlot &c, bool on_host);
+inline hipError_t rt_scene_order_reader(RtTableSlot &c, hipStream_t stream) { return c.built.order(stream); }
+RtReflect *rt_scene_reflect(rt_scene *s);   // created on first use
+void rt_pack_spheres(const rt_sphere *src, int n, float4 *dst);
+// rt_scene_tables.cpp: each finds or builds what the frame reads; the slot index comes back (-1: the frame reads none)
+int rt_scene_prepare_eye(rt_scene *s, const float org[3], hipStream_t stream, int *slot_out);
+int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelChoice &kc, int cone_slot, RtFrameConsts *fc,
+                          hipStream_t stream, int *view_out);
+int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, hipStream_t stream);
+int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float aspect, int total);
+void rt_build_frame_aux(const rt_scene *s, RtFrameAux *ax);
+int rt_scene_sync_aux(rt_scene *s);
+void rt_view_params_from_consts(const RtFrameConsts &fc, float aspect, RtViewParams *p);
+void rt_view_lists_summary(const float4 *slots, int blocks, rt_view_lists_info *out);
+// rt_render.cpp
+void rt_view_rotation(const rt_frame_desc *fd, RtFrameConsts *fc);
+
+// margin of the fast texel-index path for a texture dimension of `size` texels (rt_kernels.hip:
+// sure_texel): approximation error RT_UV_DELTA plus the rounding of the two float products
+inline float rt_texel_margin(int size, float delta) { return (float)size * (delta + 0x1.0p-22f) * 1.01f; }

@@ -11,6 +11,9 @@
 // Longest list (padded to 64) the one-workgroup device builder sorts in LDS (8 B per key).
 #define RT_EYE_DEVICE_MAX 8192
 
+// A sphere count padded to whole waves of 64: the length of every Morton-, column- and cone-ordered table.
+inline int rt_pad64(int n) { return (n + 63) & ~63; }
+
 void rt_build_sorted_blocks(const float4 *tab, int n, float4 *sorted, float4 *blocks, int *orig);
 void rt_build_light_columns(const float4 *tab, int n, const float u[3], float4 *sorted, float4 *blocks);
 // Per sphere S of the table and one light: the entries a shadow ray from S's surface towards the light can hit
