@@ -224,7 +224,8 @@ typedef struct rt_launch_opts {
                                 frame exactly as without this field (same kernels, same launches).
                                 1..RT_MAX_REFLECT_DEPTH: mirror reflections off spheres with a non-zero
                                 material reflectivness (rt_scene_set_materials), at most this many
-                                bounces after the primary hit (DESIGN.md "Reflections"). Spheres only;
+                                bounces after the primary hit (DESIGN.md "Reflections"). Spheres only
+                                unless rt_scene_set_reflect_scope(s, RT_REFLECT_SCENE);
                                 spp 1; no accumulate, interleave_*, packed24, table_lds or profile
                                 (RT_ERR_UNSUPPORTED); `fast` is ignored (the launch is exact)      */
 } rt_launch_opts;
@@ -754,6 +755,48 @@ int rt_debug_transmit(const rt_sphere *sphere, const float *ior, const rt_ray *r
                       rt_ray *out, int *entered);
 int rt_debug_occluder_lists_ex(const rt_sphere *spheres, int n, const rt_light *light, int *counts, float *kcaps, int *members, int cap,
                                int *offsets, int *entries_allocated);
+
+/* ------------------------------------------------------------------ *
+ * Reflective frames over the whole scene.              *
+ * ------------------------------------------------------------------ */
+/* The scope of a frame with opts.reflect_depth > 0. RT_REFLECT_SPHERES (the default): spheres only,
+ * exactly as before this switch existed -- a scene that holds a plane, a cube or a mesh is
+ * RT_ERR_UNSUPPORTED and nothing is written. RT_REFLECT_SCENE lifts that one refusal. Any other value:
+ * RT_ERR_INVALID. A host-side switch, read when a frame is launched: no wait, no device needed.
+ *
+ * Semantics under RT_REFLECT_SCENE: the per-pixel loop of rt_scene_set_materials / _ex with three
+ * substitutions.
+ *   Nearest hit. castRay(R_b) is castRay over the whole scene, as RT_QUERY_NEAREST defines it: mesh
+ *     leaves behind their boxes, then spheres, then cubes, then planes, the strict `t < nt` across
+ *     kinds, every primitive test with its quirks (a cube's negative tmin from inside, a plane hit only
+ *     for denom < 0, Moller-Trumbore's t >= 1e-7f).
+ *   Hit frame. N, new_org, the texel and start_O = N*0.00001 + new_org are as rt_hit / castRay form
+ *     them for that kind: a plane's normal as stored (not normalised), a cube's the normalised
+ *     hit - centre, a triangle's new_org displaced by the whole normal, texture coordinates as castRay's
+ *     ((0.5, 0.5) for a plane). reflect(R_b.Dir, N) takes that N as it is. Two consequences: a plane
+ *     whose stored normal is not a unit vector is not a mirror (the reflected direction is neither the
+ *     mirror direction nor a unit vector), and a ray reflected off a cube near an edge -- where
+ *     hit - centre points away from the face's own normal -- may re-enter the same cube.
+ *   Light. L is the three-light sum with castLightRay's any-hit over every kind (RT_QUERY_OCCLUDED).
+ * Everything else is unchanged: k comes from the hit primitive's table (below; a triangle always has
+ * k = 0), weights and the order of additions are as before, glass rules 1..4 apply at glass spheres
+ * (glass stays a sphere property; the chord stays untested, now also against planes, cubes and
+ * triangles). A sky pixel, and a pixel whose primary hit has k = 0 and tau = 0, is the plain frame
+ * bit for bit. A scene with no spheres at all is legal. rt_reflect_stats.queue[b] counts rays of every
+ * kind of hit.
+ * Still RT_ERR_UNSUPPORTED under either scope, with nothing written: spp > 1, accumulate,
+ * interleave_*, packed24, table_lds, profile, rt_graph_capture and rt_multi_render. The drop-in
+ * boundary (rt_launch_raytrace_ex, object::mat) keeps the spheres-only scope. */
+enum { RT_REFLECT_SPHERES = 0, RT_REFLECT_SCENE = 1 };
+int rt_scene_set_reflect_scope(rt_scene *s, int scope);
+/* One material per plane / per cube of the scene's list, under rt_scene_set_materials' rules per list:
+ * n must equal the list's count (RT_ERR_INVALID); NULL / 0 clears the table (every k = 0) and always
+ * succeeds; the table survives rt_scene_set_planes / rt_scene_set_cubes with the same count and is
+ * cleared by a different count; a NaN k or a k outside [0, 1] is RT_ERR_INVALID; transperancy or
+ * roughness != 0 is RT_ERR_UNSUPPORTED (the values are checked before the count). Nothing changes on
+ * an error. The tables may be set under either scope; only frames under RT_REFLECT_SCENE read them. */
+int rt_scene_set_plane_materials(rt_scene *s, const rt_material *per_plane, int n);
+int rt_scene_set_cube_materials(rt_scene *s, const rt_material *per_cube, int n);
 
 #ifdef __cplusplus
 }

@@ -152,6 +152,8 @@ RT_HIT_NONE, RT_HIT_TRIANGLE, RT_HIT_SPHERE, RT_HIT_PLANE, RT_HIT_CUBE = -1, 0, 
 RT_QUERY_NEAREST, RT_QUERY_OCCLUDED, RT_QUERY_SHADE = 0, 1, 2
 RT_MAX_QUERY_RAYS = 1 << 26
 _QUERY_MODES = {"nearest": RT_QUERY_NEAREST, "occluded": RT_QUERY_OCCLUDED, "shade": RT_QUERY_SHADE}
+RT_REFLECT_SPHERES, RT_REFLECT_SCENE = 0, 1     # rt_scene_set_reflect_scope
+_REFLECT_SCOPES = {"spheres": RT_REFLECT_SPHERES, "scene": RT_REFLECT_SCENE}
 
 
 class Hit(C.Structure):
@@ -318,6 +320,9 @@ def load_library():
         "rt_scene_set_denoise_timing": (ci, [vp, ci]),
         "rt_scene_denoise_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_debug_copy16": (ci, [vp, vp, C.c_size_t, vp]),
+        "rt_scene_set_reflect_scope": (ci, [vp, ci]),
+        "rt_scene_set_plane_materials": (ci, [vp, C.POINTER(Material), ci]),
+        "rt_scene_set_cube_materials": (ci, [vp, C.POINTER(Material), ci]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -542,6 +547,37 @@ class Scene:
                         setattr(mats[i], field, float(v))
         _check(self.lib.rt_scene_set_materials_ex(self.handle, mats, n), "rt_scene_set_materials_ex")
         self.materials = mats
+
+    def set_reflect_scope(self, scope):
+        """"spheres" (default): reflective frames refuse planes, cubes and a mesh; "scene": they cast, shade and
+        reflect over every kind of primitive. Also takes RT_REFLECT_SPHERES / RT_REFLECT_SCENE."""
+        if isinstance(scope, str):
+            if scope not in _REFLECT_SCOPES:
+                raise RtError(f"unknown reflect scope {scope!r} (one of {tuple(_REFLECT_SCOPES)})")
+            scope = _REFLECT_SCOPES[scope]
+        _check(self.lib.rt_scene_set_reflect_scope(self.handle, int(scope)), "rt_scene_set_reflect_scope")
+
+    def _set_kind_materials(self, entry, reflectivity):
+        fn = getattr(self.lib, entry)
+        if reflectivity is None or len(reflectivity) == 0:
+            _check(fn(self.handle, None, 0), entry)
+            return
+        n = len(reflectivity)
+        mats = (Material * n)()
+        for i, m in enumerate(reflectivity):
+            if isinstance(m, Material):
+                mats[i] = m
+            else:
+                mats[i].reflectivness = float(m)
+        _check(fn(self.handle, mats, n), entry)
+
+    def set_plane_materials(self, reflectivity):
+        """One material per plane (floats k in [0, 1], or Material); None clears them. Read under the "scene" scope."""
+        self._set_kind_materials("rt_scene_set_plane_materials", reflectivity)
+
+    def set_cube_materials(self, reflectivity):
+        """One material per cube (floats k in [0, 1], or Material); None clears them. Read under the "scene" scope."""
+        self._set_kind_materials("rt_scene_set_cube_materials", reflectivity)
 
     def set_reflect_timing(self, on: bool):
         _check(self.lib.rt_scene_set_reflect_timing(self.handle, 1 if on else 0), "rt_scene_set_reflect_timing")

@@ -181,6 +181,10 @@ void rt_reflect_destroy(RtReflect *r);
 void rt_reflect_spheres_changed(RtReflect *r, int n_old, int n_new);
 int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_spheres);
 int rt_reflect_set_materials_ex(RtReflect *r, const rt_material_ex *m, int n, int n_spheres);
+int rt_reflect_set_kind_materials(RtReflect *r, int which, const rt_material *m, int n, int n_list);   // which: 0 planes, 1 cubes
+void rt_reflect_kind_list_changed(RtReflect *r, int which, int n_old, int n_new);
+int rt_reflect_set_scope(RtReflect *r, int scope);
+int rt_reflect_scope(const RtReflect *r);
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n);
 int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned long long sphere_gen, int npx,
                        bool need_rgba, float **rgba_scratch, hipStream_t stream);

@@ -14,9 +14,14 @@
 // w becomes w * tau and R_{b+1} is the ray that passed through the sphere (rf_transmit). Both passes are templates on
 // GLASS; the host launches GLASS = true only when some sphere has tau > 0, so mirror-only frames run today's code.
 // The brute-force variant (opts.cull = 0) is the same kernels with the BVH replaced by the whole sphere list.
+// Whole scenes (rt_scene_set_reflect_scope(RT_REFLECT_SCENE)) are a second template parameter, KINDS:
+// the nearest hit is castRay over every kind of primitive (q_nearest), the hit frame is castRay's record for that kind
+// (q_hit_record), k comes from the hit primitive's table (a triangle has k = 0) and L is shaded with castLightRay's
+// any-hit over every kind (q_shade_hit) -- the ray queries' own functions. The host launches KINDS = true only when
+// the scope is the scene and the scene holds a plane, a cube or a mesh: every other frame runs today's code.
 //
-// The BVH and the per-ray pieces the ray queries share are in rt_bvh.h.
-#include "rt_bvh.h"
+// The BVH and the per-ray pieces the ray queries share are in rt_bvh.h, the all-kinds casts in rt_cast.h.
+#include "rt_cast.h"
 
 #include <algorithm>
 #include <chrono>
@@ -32,6 +37,12 @@ struct QEntry {    // one queued ray: 48 bytes
     float w, cr, cg, cb;
     int pix;       // band-local pixel index
     int pad_;
+};
+
+// The KINDS passes' tables beside RtReflectDev's per-sphere ones (the last kernel argument)
+struct RtKindsDev {
+    const float *k_plane;          // reflectivness per plane (null: all 0)
+    const float *k_cube;           // reflectivness per cube (null: all 0)
 };
 
 // reflect(I, N), kernel.cu:1282-1285: sub(I, multiply(multiply(N, dot(I, N)), 2)), the dot product left to right
@@ -155,6 +166,24 @@ __device__ __forceinline__ void rf_shade(const RtFrameConsts &fc, AuxPtr ax, con
     }
 }
 
+// rf_shade for a hit of any kind: rayTrace's pixel body at castRay's record h (q_shade_hit), under the same contract
+__device__ __forceinline__ void rf_shade_kinds(const RtFrameConsts &fc, AuxPtr ax, const RtReflectDev &rd, bool act,
+                                               const rt_hit &h, LdsStack stk, float &fr, float &fg, float &fb)
+{
+    fr = fg = fb = 0.f;
+    if (!any64(act)) return;
+    if (act) q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
+}
+
+// k of the hit primitive: its kind's table at its list position; a triangle has none
+__device__ __forceinline__ float rf_kind_k(const RtReflectDev &rd, const RtKindsDev &kd, int kind, int pos)
+{
+    if (kind == RT_HIT_SPHERE) return rd.k ? rd.k[pos] : 0.f;
+    if (kind == RT_HIT_PLANE) return kd.k_plane ? kd.k_plane[pos] : 0.f;
+    if (kind == RT_HIT_CUBE) return kd.k_cube ? kd.k_cube[pos] : 0.f;
+    return 0.f;
+}
+
 __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float cr, float cg, float cb)
 {
     if (fc.rgba) reinterpret_cast<float4 *>(fc.rgba)[pix] = make_float4(cr, cg, cb, 1.f);
@@ -163,9 +192,10 @@ __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float
 }
 
 // The primary pass: every pixel of the band; queues those whose primary hit is reflective (or, GLASS, transparent).
-template <bool GLASS>
+// KINDS: the hit is castRay's over every kind (the frame kernel's own hit, as the G-buffers show for NEAREST).
+template <bool GLASS, bool KINDS>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtFrameConsts fc, const RtReflectDev rd,
-                                                                       QEntry *q, int *count)
+                                                                       QEntry *q, int *count, const RtKindsDev kd)
 {
     __shared__ int stack_lds[RT_BVH_STACK * RT_REFLECT_BLOCK];
     const LdsStack stk{stack_lds, (int)threadIdx.x};
@@ -178,17 +208,33 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
         const V3 D = rf_primary_dir(fc, pix);   // one sample: sample_base 0 is checked by the host
         const V3 O{fc.org_x, fc.org_y, fc.org_z};
         float nt;
-        const int hit = rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk);
-        float k = (hit >= 0 && rd.k) ? rd.k[hit] : 0.f;
+        int hit, kind = RT_HIT_SPHERE;                                          // hit: the list position within its kind
+        float k;
+        if constexpr (KINDS) {
+            nt = q_nearest(fc, (AuxPtr)(uintptr_t)fc.aux, rd, O, D, stk, kind, hit);
+            k = rf_kind_k(rd, kd, kind, hit);
+        } else {
+            hit = rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk);
+            k = (hit >= 0 && rd.k) ? rd.k[hit] : 0.f;
+        }
         float2 g = make_float2(0.f, 0.f);                                       // (tau, ior)
-        if (GLASS && hit >= 0) {
+        if (GLASS && hit >= 0 && kind == RT_HIT_SPHERE) {
             g = rd.glass[hit];
             if (g.x > 0.f) k = g.x;                                             // (k > 0 and tau > 0 are never both set)
         }
         if (k > 0.f) {
-            const float4 s = rd.spheres[hit];
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);                         // the hit sphere (glass reads it)
             V3 normal, start, new_org;
-            rf_hit_frame(O, D, nt, s, normal, start, new_org);
+            if constexpr (KINDS) {
+                const rt_hit h = q_hit_record(fc, (AuxPtr)(uintptr_t)fc.aux, rd, O, D, nt, kind, hit);
+                normal = V3{h.normal.x, h.normal.y, h.normal.z};
+                new_org = V3{h.new_org.x, h.new_org.y, h.new_org.z};
+                start = V3{normal.x * 0.00001f + new_org.x, normal.y * 0.00001f + new_org.y, normal.z * 0.00001f + new_org.z};
+                if (GLASS && g.x > 0.f) s = rd.spheres[hit];
+            } else {
+                s = rd.spheres[hit];
+                rf_hit_frame(O, D, nt, s, normal, start, new_org);
+            }
             const float4 L = reinterpret_cast<const float4 *>(fc.rgba)[pix];   // the frame kernel's L for this hit
             const float f = 1.f - k;                                            // (w * (1 - k)) with w = 1
             if (GLASS && g.x > 0.f) {
@@ -210,10 +256,10 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
 }
 
 // Bounce b (1..depth): a fixed grid walks the queue of the previous pass; its length is read here, on the device.
-template <bool GLASS>
+template <bool GLASS, bool KINDS>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFrameConsts fc, const RtReflectDev rd, int b,
                                                                       const QEntry *qin, const int *count_in, QEntry *qout,
-                                                                      int *count_out)
+                                                                      int *count_out, const RtKindsDev kd)
 {
     __shared__ int stack_lds[RT_BVH_STACK * RT_REFLECT_BLOCK];
     const LdsStack stk{stack_lds, (int)threadIdx.x};
@@ -226,12 +272,27 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
         if (valid) e = qin[i];
         const V3 O{e.ox, e.oy, e.oz}, D{e.dx, e.dy, e.dz};
         float nt = 0.f;
-        const int hit = valid ? rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk) : -1;
-        const bool act = valid && hit >= 0;
+        int hit = -1, kind = RT_HIT_SPHERE;   // hit: the list position within its kind
+        bool act;
         V3 normal{0.f, 1.f, 0.f}, start{0.f, 0.f, 0.f};
-        if (act) rf_hit_frame(O, D, nt, rd.spheres[hit], normal, start);
         float Lr, Lg, Lb;
-        rf_shade(fc, ax, rd, act, normal, start, stk, Lr, Lg, Lb);
+        if constexpr (KINDS) {
+            if (valid) nt = q_nearest(fc, ax, rd, O, D, stk, kind, hit);
+            act = valid && kind >= 0;
+            rt_hit h{};
+            if (act) {
+                h = q_hit_record(fc, ax, rd, O, D, nt, kind, hit);
+                normal = V3{h.normal.x, h.normal.y, h.normal.z};
+                start = V3{normal.x * 0.00001f + h.new_org.x, normal.y * 0.00001f + h.new_org.y,
+                           normal.z * 0.00001f + h.new_org.z};
+            }
+            rf_shade_kinds(fc, ax, rd, act, h, stk, Lr, Lg, Lb);
+        } else {
+            hit = valid ? rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk) : -1;
+            act = valid && hit >= 0;
+            if (act) rf_hit_frame(O, D, nt, rd.spheres[hit], normal, start);
+            rf_shade(fc, ax, rd, act, normal, start, stk, Lr, Lg, Lb);
+        }
         bool push = false;
         QEntry nx{};
         if (valid) {
@@ -242,9 +303,11 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
                 rf_sky(ax, O, D, sr, sg, sb);
                 cr = cr + e.w * sr; cg = cg + e.w * sg; cb = cb + e.w * sb;
             } else {
-                float k = rd.k ? rd.k[hit] : 0.f;
+                float k;
+                if constexpr (KINDS) k = rf_kind_k(rd, kd, kind, hit);
+                else k = rd.k ? rd.k[hit] : 0.f;
                 float2 g = make_float2(0.f, 0.f);   // (tau, ior)
-                if (GLASS) {
+                if (GLASS && kind == RT_HIT_SPHERE) {
                     g = rd.glass[hit];
                     if (g.x > 0.f) k = g.x;         // (k > 0 and tau > 0 are never both set)
                 }
@@ -282,6 +345,19 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+// A per-plane or per-cube reflectivness table: d_k's protocol (the device copy changes only in rt_reflect_prepare)
+struct RtKTable {
+    std::vector<float> k;                 // empty = all 0
+    std::vector<float> k_dev;             // what the device copy holds
+    bool dirty = false;
+    DevArray<float> d_k;
+    void clear()
+    {
+        if (!k.empty()) dirty = true;
+        k.clear();
+    }
+};
+
 struct RtReflect {
     std::vector<float> k;                 // reflectivness per sphere; empty = all 0
     std::vector<float> k_dev;             // what the device copy holds (the source of its upload: changed only after
@@ -292,6 +368,8 @@ struct RtReflect {
     std::vector<float> glass_dev;         // what d_glass holds (as k_dev)
     bool glass_dirty = false;
     DevArray<float2> d_glass;
+    int scope = RT_REFLECT_SPHERES;       // rt_scene_set_reflect_scope
+    RtKTable plane_k, cube_k;             // read only by frames under RT_REFLECT_SCENE
     RtSphereBvh bvh;                      // the sphere BVH (shared with the ray queries)
     // queues and counters
     DevArray<QEntry> d_q[2];
@@ -550,9 +628,66 @@ int rt_reflect_set_materials_ex(RtReflect *r, const rt_material_ex *m, int n, in
     return RT_OK;
 }
 
+// rt_scene_set_plane_materials / rt_scene_set_cube_materials (which = 0 / 1): rt_reflect_set_materials' rules for a
+// list of n_list entries, except that the values are checked before the count
+int rt_reflect_set_kind_materials(RtReflect *r, int which, const rt_material *m, int n, int n_list)
+{
+    const char *fn = which == 0 ? "rt_scene_set_plane_materials" : "rt_scene_set_cube_materials";
+    const char *what = which == 0 ? "plane" : "cube";
+    RtKTable &t = which == 0 ? r->plane_k : r->cube_k;
+    if (!m || n == 0) {
+        t.clear();
+        return RT_OK;
+    }
+    for (int i = 0; i < n; ++i) {   // every value first, then what is not implemented, then the count
+        const float k = m[i].reflectivness;
+        if (!(k >= 0.f && k <= 1.f)) {
+            rt_set_error("%s: %s %d: reflectivness %g is not in [0, 1]", fn, what, i, (double)k);
+            return RT_ERR_INVALID;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        if (m[i].transperancy != 0.f || m[i].roughness != 0.f) {
+            rt_set_error("%s: %s %d: transperancy / roughness are not implemented (only reflectivness; glass is a sphere "
+                         "property)", fn, what, i);
+            return RT_ERR_UNSUPPORTED;
+        }
+    }
+    if (n != n_list) {
+        rt_set_error("%s: %d materials for %d %ss (one per %s, or NULL / 0)", fn, n, n_list, what, what);
+        return RT_ERR_INVALID;
+    }
+    std::vector<float> k((size_t)n);
+    for (int i = 0; i < n; ++i) k[(size_t)i] = m[i].reflectivness;
+    if (k != t.k) {
+        t.k.swap(k);
+        t.dirty = true;
+    }
+    return RT_OK;
+}
+
+// rt_scene_set_planes / rt_scene_set_cubes: a new count clears the list's materials (the same count keeps them)
+void rt_reflect_kind_list_changed(RtReflect *r, int which, int n_old, int n_new)
+{
+    if (n_old != n_new) (which == 0 ? r->plane_k : r->cube_k).clear();
+}
+
+int rt_reflect_set_scope(RtReflect *r, int scope)
+{
+    if (scope != RT_REFLECT_SPHERES && scope != RT_REFLECT_SCENE) {
+        rt_set_error("rt_scene_set_reflect_scope: scope %d is not RT_REFLECT_SPHERES or RT_REFLECT_SCENE", scope);
+        return RT_ERR_INVALID;
+    }
+    r->scope = scope;
+    return RT_OK;
+}
+
+int rt_reflect_scope(const RtReflect *r) { return r->scope; }
+
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n)
 {
-    return r->k_dirty || r->glass_dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
+    // (the plane and cube tables count under either scope: the upload is due whenever they changed)
+    return r->k_dirty || r->glass_dirty || r->plane_k.dirty || r->cube_k.dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
 }
 
 // Brings materials and BVH up to date (the caller has waited for every frame that may read them) and makes sure the
@@ -580,6 +715,15 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
                                   hipMemcpyHostToDevice, stream));
         }
         r->glass_dirty = false;
+    }
+    for (RtKTable *t : {&r->plane_k, &r->cube_k}) {
+        if (!t->dirty) continue;
+        t->k_dev = t->k;
+        if (!t->k_dev.empty()) {
+            RT_HIP(t->d_k.reserve(t->k_dev.size()));
+            RT_HIP(hipMemcpyAsync(t->d_k.get(), t->k_dev.data(), sizeof(float) * t->k_dev.size(), hipMemcpyHostToDevice, stream));
+        }
+        t->dirty = false;
     }
     for (DevArray<QEntry> &q : r->d_q) RT_HIP(q.reserve((size_t)npx));
     RT_HIP(r->d_cnt.reserve(RT_MAX_REFLECT_DEPTH + 1));
@@ -630,14 +774,24 @@ int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_sph
     rd.depth = depth;
     rd.glass = r->glass_dev.empty() ? nullptr : r->d_glass.get();
     const bool glass = rd.glass != nullptr;   // mirror-only frames run the GLASS = false instantiations (today's code)
+    // KINDS only where the scope is the scene and there is something besides spheres: every frame that rendered before
+    // the scope existed runs the KINDS = false instantiations
+    const bool kinds = r->scope == RT_REFLECT_SCENE && (fc->n_planes > 0 || fc->n_cubes > 0 || fc->n_boxes > 0);
+    RtKindsDev kd{};
+    kd.k_plane = (kinds && !r->plane_k.k_dev.empty()) ? r->plane_k.d_k.get() : nullptr;
+    kd.k_cube = (kinds && !r->cube_k.k_dev.empty()) ? r->cube_k.d_k.get() : nullptr;
+    const auto primary = kinds ? (glass ? rt_reflect_primary<true, true> : rt_reflect_primary<false, true>)
+                               : (glass ? rt_reflect_primary<true, false> : rt_reflect_primary<false, false>);
+    const auto bounce = kinds ? (glass ? rt_reflect_bounce<true, true> : rt_reflect_bounce<false, true>)
+                              : (glass ? rt_reflect_bounce<true, false> : rt_reflect_bounce<false, false>);
     const int npx = fc->width * fc->local_rows;
-    hipLaunchKernelGGL(glass ? rt_reflect_primary<true> : rt_reflect_primary<false>, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
-                       stream, *fc, rd, r->d_q[0].get(), r->d_cnt.get());
+    hipLaunchKernelGGL(primary, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
+                       stream, *fc, rd, r->d_q[0].get(), r->d_cnt.get(), kd);
     RT_HIP(hipGetLastError());
     RT_HIP(rt_reflect_mark(r, 2, stream));
     for (int b = 1; b <= depth; ++b) {
-        hipLaunchKernelGGL(glass ? rt_reflect_bounce<true> : rt_reflect_bounce<false>, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, rd, b,
-                           r->d_q[(b - 1) & 1].get(), r->d_cnt.get() + (b - 1), r->d_q[b & 1].get(), r->d_cnt.get() + b);
+        hipLaunchKernelGGL(bounce, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, rd, b,
+                           r->d_q[(b - 1) & 1].get(), r->d_cnt.get() + (b - 1), r->d_q[b & 1].get(), r->d_cnt.get() + b, kd);
         RT_HIP(hipGetLastError());
         RT_HIP(rt_reflect_mark(r, 2 + b, stream));
     }

@@ -296,7 +296,9 @@ static int reflect_supported(const rt_scene *s, const rt_frame_desc *fd)
         return RT_ERR_INVALID;
     }
     const char *why = nullptr;
-    if (s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0) why = "planes, cubes or a mesh in the scene";
+    const bool spheres_only = !s->refl || rt_reflect_scope(s->refl.get()) == RT_REFLECT_SPHERES;
+    if (spheres_only && (s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0))
+        why = "planes, cubes or a mesh in the scene (rt_scene_set_reflect_scope(RT_REFLECT_SCENE) lifts this)";
     else if (o.spp > 1 || o.sample_base != 0 || o.sample_total > 1) why = "more than one sample per pixel";
     else if (o.accumulate) why = "accumulate";
     else if (o.interleave_count > 1 || o.interleave_index != 0 || o.interleave_rows != 0) why = "interleave_*";
@@ -304,7 +306,7 @@ static int reflect_supported(const rt_scene *s, const rt_frame_desc *fd)
     else if (o.table_lds) why = "table_lds";
     else if (o.profile) why = "profile";
     if (why) {
-        rt_set_error("rt_scene_render: reflect_depth > 0 does not support %s (spheres only, one sample, plain outputs)", why);
+        rt_set_error("rt_scene_render: reflect_depth > 0 does not support %s (one sample, plain outputs)", why);
         return RT_ERR_UNSUPPORTED;
     }
     return RT_OK;

@@ -187,6 +187,7 @@ extern "C" int rt_scene_set_planes(rt_scene *s, const rt_plane *host_planes, int
         tmp[i] = RtPlaneDev{host_planes[i].orgin.x, host_planes[i].orgin.y, host_planes[i].orgin.z,
                             host_planes[i].normal.x, host_planes[i].normal.y, host_planes[i].normal.z, 0.f, 0.f};
     if (n) RT_HIP(hipMemcpy(s->d_planes.get(), tmp.data(), sizeof(RtPlaneDev) * n, hipMemcpyHostToDevice));
+    if (s->refl) rt_reflect_kind_list_changed(s->refl.get(), 0, s->n_planes, n);
     s->n_planes = n;
     s->epoch++;
     return RT_OK;
@@ -211,6 +212,7 @@ extern "C" int rt_scene_set_cubes(rt_scene *s, const rt_cube *host_cubes, int n)
                            c.orgin.x, c.orgin.y, c.orgin.z, 0.f, 0.f, 0.f};
     }
     if (n) RT_HIP(hipMemcpy(s->d_cubes.get(), tmp.data(), sizeof(RtCubeDev) * n, hipMemcpyHostToDevice));
+    if (s->refl) rt_reflect_kind_list_changed(s->refl.get(), 1, s->n_cubes, n);
     s->n_cubes = n;
     s->epoch++;
     return RT_OK;
@@ -355,6 +357,35 @@ extern "C" int rt_scene_set_materials_ex(rt_scene *s, const rt_material_ex *per_
     }
     // (as rt_scene_set_materials: the next reflective frame uploads after the frames in flight)
     return rt_reflect_set_materials_ex(rt_scene_reflect(s), per_sphere, n, s->n_spheres);
+}
+
+// The scope of reflective frames: a host-side switch, read when a frame is launched
+extern "C" int rt_scene_set_reflect_scope(rt_scene *s, int scope)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_reflect_scope: null scene");
+        return RT_ERR_INVALID;
+    }
+    return rt_reflect_set_scope(rt_scene_reflect(s), scope);
+}
+
+extern "C" int rt_scene_set_plane_materials(rt_scene *s, const rt_material *per_plane, int n)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_plane_materials: null scene");
+        return RT_ERR_INVALID;
+    }
+    // (as rt_scene_set_materials: the next reflective frame uploads after the frames in flight)
+    return rt_reflect_set_kind_materials(rt_scene_reflect(s), 0, per_plane, n, s->n_planes);
+}
+
+extern "C" int rt_scene_set_cube_materials(rt_scene *s, const rt_material *per_cube, int n)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_cube_materials: null scene");
+        return RT_ERR_INVALID;
+    }
+    return rt_reflect_set_kind_materials(rt_scene_reflect(s), 1, per_cube, n, s->n_cubes);
 }
 
 extern "C" int rt_scene_set_reflect_timing(rt_scene *s, int on)

@@ -3,9 +3,12 @@
 ms per frame (BVH and brute-force variants), the time of every pass (hipEvents), the queue length per bounce, the
 BVH build time, and the same frame with reflect_depth = 0. Prints one JSON line.
 
-  python3 tools/bench_reflect.py [--iters 20] [--depth 3]
+--floor: the whole-scene scope (rt_scene_set_reflect_scope) on C3's spheres plus the reference's plane
+(kernel.cu:1187) with k = 0.3: the same figures for the all-kinds passes. --out also writes the JSON to a file.
+
+  python3 tools/bench_reflect.py [--iters 20] [--depth 3] [--floor] [--out FILE]
 """
-import argparse, json, os, sys
+import argparse, ctypes, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import torch
@@ -29,14 +32,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--depth", type=int, default=3)
+    ap.add_argument("--floor", action="store_true", help="add the reference's plane (k = 0.3) under the scene scope")
+    ap.add_argument("--out", default="", help="also write the JSON line to this file")
     a = ap.parse_args()
     rt = rt_amd.load()
     w, h, n = 3840, 2160, 1024
     scene = rt.Scene.default(n)
     scene.set_materials([0.5 if i % 4 == 0 else 0.0 for i in range(n)])
+    if a.floor:
+        planes = (rt.Plane * 1)()
+        rt.load_library().rt_plane_init(ctypes.byref(planes[0]), 0.0, -4.0, 0.0, 0.0, 1.0, 0.0)
+        scene.set_planes(planes, 1)
+        scene.set_plane_materials([0.3])
+        scene.set_reflect_scope("scene")
     rgba = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
     pk = torch.empty((h, w), dtype=torch.int32, device="cuda")
-    out = {"config": f"{w}x{h}_n{n}_k0.5_every4th_depth{a.depth}", "iters": a.iters}
+    out = {"config": f"{w}x{h}_n{n}_k0.5_every4th_depth{a.depth}" + ("_floor_k0.3_scope_scene" if a.floor else ""),
+           "iters": a.iters}
     fd0 = scene.frame_desc(w, h, pixels=pk.data_ptr(), rgba=rgba.data_ptr())
     out["plain_ms"] = time_frames(scene, fd0, a.iters)
     fd = scene.frame_desc(w, h, pixels=pk.data_ptr(), rgba=rgba.data_ptr(), reflect_depth=a.depth)
@@ -53,6 +65,10 @@ def main():
     out["bvh"] = {k: stats[k] for k in ("bvh_build_ms", "bvh_nodes", "bvh_depth", "bvh_leaves")}
     out["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
