@@ -225,8 +225,10 @@ typedef struct rt_launch_opts {
                                 1..RT_MAX_REFLECT_DEPTH: mirror reflections off spheres with a non-zero
                                 material reflectivness (rt_scene_set_materials), at most this many
                                 bounces after the primary hit (DESIGN.md "Reflections"). Spheres only
-                                unless rt_scene_set_reflect_scope(s, RT_REFLECT_SCENE);
-                                spp 1; no accumulate, interleave_*, packed24, table_lds or profile
+                                unless rt_scene_set_reflect_scope(s, RT_REFLECT_SCENE); under the
+                                default sampling mode spp 1 and no accumulate
+                                (rt_scene_set_reflect_samples(s, RT_REFLECT_SAMPLES_MANY) lifts both);
+                                no interleave_*, packed24, table_lds or profile
                                 (RT_ERR_UNSUPPORTED); `fast` is ignored (the launch is exact)      */
 } rt_launch_opts;
 
@@ -411,7 +413,9 @@ int rt_scene_set_materials_ex(rt_scene *s, const rt_material_ex *per_sphere, int
  * (host build, binary64, rebuilt when the spheres change), the queue length entering every
  * bounce, and -- when rt_scene_set_reflect_timing(s, 1) was called before the frame -- the
  * device time of every pass (hipEvents: [0] the frame kernel, [1] the primary pass, [1 + b]
- * bounce b). */
+ * bounce b). A supersampled frame (rt_scene_set_reflect_samples): queue[b] is summed over the
+ * call's samples, pass_ms over its groups of samples ([0]: the frame kernel's launches), and the
+ * resolve passes are counted in the last bounce's slot. */
 typedef struct rt_reflect_stats {
     double bvh_build_ms;     /* host time of the last BVH build                                  */
     int bvh_nodes, bvh_depth, bvh_leaves;
@@ -784,9 +788,10 @@ int rt_debug_occluder_lists_ex(const rt_sphere *spheres, int n, const rt_light *
  * triangles). A sky pixel, and a pixel whose primary hit has k = 0 and tau = 0, is the plain frame
  * bit for bit. A scene with no spheres at all is legal. rt_reflect_stats.queue[b] counts rays of every
  * kind of hit.
- * Still RT_ERR_UNSUPPORTED under either scope, with nothing written: spp > 1, accumulate,
- * interleave_*, packed24, table_lds, profile, rt_graph_capture and rt_multi_render. The drop-in
- * boundary (rt_launch_raytrace_ex, object::mat) keeps the spheres-only scope. */
+ * Still RT_ERR_UNSUPPORTED under either scope, with nothing written: under the default sampling mode
+ * (rt_scene_set_reflect_samples below) spp > 1 and accumulate; under either mode interleave_*,
+ * packed24, table_lds, profile, rt_graph_capture and rt_multi_render. The drop-in boundary
+ * (rt_launch_raytrace_ex, object::mat) keeps the spheres-only scope. */
 enum { RT_REFLECT_SPHERES = 0, RT_REFLECT_SCENE = 1 };
 int rt_scene_set_reflect_scope(rt_scene *s, int scope);
 /* One material per plane / per cube of the scene's list, under rt_scene_set_materials' rules per list:
@@ -797,6 +802,44 @@ int rt_scene_set_reflect_scope(rt_scene *s, int scope);
  * an error. The tables may be set under either scope; only frames under RT_REFLECT_SCENE read them. */
 int rt_scene_set_plane_materials(rt_scene *s, const rt_material *per_plane, int n);
 int rt_scene_set_cube_materials(rt_scene *s, const rt_material *per_cube, int n);
+
+/* ------------------------------------------------------------------ *
+ * Supersampled reflective frames.                      *
+ * ------------------------------------------------------------------ */
+/* How a frame with opts.reflect_depth > 0 samples a pixel. RT_REFLECT_SAMPLES_ONE (the default): one
+ * sample, exactly as before this switch existed -- spp > 1, sample_base != 0, sample_total > 1 and
+ * accumulate are RT_ERR_UNSUPPORTED and nothing is written. RT_REFLECT_SAMPLES_MANY lifts those
+ * refusals: the frame takes spp 1..RT_MAX_SPP, sample_base, sample_total, accumulate and resolve = -1
+ * with the plain frame's range checks and errors. Any other value: RT_ERR_INVALID, the mode unchanged.
+ * A host-side switch, read when a frame is launched: no wait, no device needed.
+ *
+ * The result, to the bit. n = spp (0 reads as 1), total = sample_total > 0 ? sample_total : n,
+ * base = sample_base.
+ *   Per sample k = base .. base + n - 1, ascending: R_0^k is the primary ray the plain frame forms
+ *     for sample k of total (rt_sample_offset(k, total)), and c_k the colour the per-pixel loop of
+ *     rt_scene_set_materials / _ex / rt_scene_set_reflect_scope gives that ray: w = 1, depth D, the
+ *     scene's scope and tables, the first term assigned and later ones added.
+ *   Sum. S = +0, then S = S + c_k per channel in binary32, in ascending k (as the plain frame sums
+ *     its samples).
+ *   Without accumulate rgba = (S, (float)n); with it rgba = (old.xyz + S, old.w + (float)n).
+ *   With pixels set and resolve != -1: m = total == 1 ? v : v / (float)total for each channel v of
+ *     the rgba just formed, and the word is rgbToInt(f2i(m.r*254), f2i(m.g*254), f2i(m.b*254));
+ *     resolve = -1 leaves pixels untouched.
+ * Consequences: a pixel none of whose samples has a primary hit with k > 0 or tau > 0 is the plain
+ * frame with the same sample fields bit for bit (rgba with .w, and the packed word). One call with
+ * spp = 4 equals four one-sample accumulate calls in ascending k (resolve = -1 until the last) bit
+ * for bit. A 2 + 2 split is old + (c_2 + c_3), which is NOT the four-in-one sum ((c_0 + c_1) + c_2)
+ * + c_3 -- as for plain frames. A request a one-sample frame serves (one sample, total 1, base 0, no
+ * accumulate, resolve != -1) runs exactly as under RT_REFLECT_SAMPLES_ONE: same launches, same bits.
+ * Still RT_ERR_UNSUPPORTED under either mode, with nothing written: interleave_*, packed24, table_lds,
+ * profile, rt_graph_capture, rt_multi_render, and G-buffer outputs (aov_*) with more than one sample.
+ * `fast` stays ignored, cull = 0 stays the whole-list variant, row bands work. The samples of a call
+ * are processed in groups of four on scene-owned scratch (about 112 bytes per pixel-sample of a group,
+ * plus 16 per pixel when there are several groups); a group whose pixel-samples exceed the queues'
+ * index range is RT_ERR_CAPACITY. The drop-in boundary (rt_launch_raytrace_ex) keeps
+ * RT_REFLECT_SAMPLES_ONE. */
+enum { RT_REFLECT_SAMPLES_ONE = 0, RT_REFLECT_SAMPLES_MANY = 1 };
+int rt_scene_set_reflect_samples(rt_scene *s, int mode);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,8 @@ RT_MAX_QUERY_RAYS = 1 << 26
 _QUERY_MODES = {"nearest": RT_QUERY_NEAREST, "occluded": RT_QUERY_OCCLUDED, "shade": RT_QUERY_SHADE}
 RT_REFLECT_SPHERES, RT_REFLECT_SCENE = 0, 1     # rt_scene_set_reflect_scope
 _REFLECT_SCOPES = {"spheres": RT_REFLECT_SPHERES, "scene": RT_REFLECT_SCENE}
+RT_REFLECT_SAMPLES_ONE, RT_REFLECT_SAMPLES_MANY = 0, 1     # rt_scene_set_reflect_samples
+_REFLECT_SAMPLES = {"one": RT_REFLECT_SAMPLES_ONE, "many": RT_REFLECT_SAMPLES_MANY}
 
 
 class Hit(C.Structure):
@@ -321,6 +323,7 @@ def load_library():
         "rt_scene_denoise_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_debug_copy16": (ci, [vp, vp, C.c_size_t, vp]),
         "rt_scene_set_reflect_scope": (ci, [vp, ci]),
+        "rt_scene_set_reflect_samples": (ci, [vp, ci]),
         "rt_scene_set_plane_materials": (ci, [vp, C.POINTER(Material), ci]),
         "rt_scene_set_cube_materials": (ci, [vp, C.POINTER(Material), ci]),
     }
@@ -556,6 +559,16 @@ class Scene:
                 raise RtError(f"unknown reflect scope {scope!r} (one of {tuple(_REFLECT_SCOPES)})")
             scope = _REFLECT_SCOPES[scope]
         _check(self.lib.rt_scene_set_reflect_scope(self.handle, int(scope)), "rt_scene_set_reflect_scope")
+
+    def set_reflect_samples(self, mode):
+        """"one" (default): reflective frames take one sample per pixel and refuse spp > 1, sample ranges and
+        accumulate; "many": they take spp, sample_base, sample_total, accumulate and resolve=-1 as plain frames do
+        (DESIGN.md 6h). Also takes RT_REFLECT_SAMPLES_ONE / RT_REFLECT_SAMPLES_MANY."""
+        if isinstance(mode, str):
+            if mode not in _REFLECT_SAMPLES:
+                raise RtError(f"unknown reflect sampling mode {mode!r} (one of {tuple(_REFLECT_SAMPLES)})")
+            mode = _REFLECT_SAMPLES[mode]
+        _check(self.lib.rt_scene_set_reflect_samples(self.handle, int(mode)), "rt_scene_set_reflect_samples")
 
     def _set_kind_materials(self, entry, reflectivity):
         fn = getattr(self.lib, entry)

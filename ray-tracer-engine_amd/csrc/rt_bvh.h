@@ -211,13 +211,14 @@ __host__ __device__ __forceinline__ void rf_hit_frame(V3 O, V3 D, float nt, floa
     rf_hit_frame(O, D, nt, s, normal, start, new_org);
 }
 
-// The direction of the primary ray of band-local pixel `pix` (kernel.cu:1624-1631), as the frame kernel forms it at one
-// sample; its origin is {fc.org_x, fc.org_y, fc.org_z}
-__device__ __forceinline__ V3 rf_primary_dir(const RtFrameConsts &fc, int pix)
+// The direction of the primary ray of band-local pixel `pix` (kernel.cu:1624-1631), as the frame kernel forms it for
+// sample `sidx` of the tables' total (row sidx of dx_tab / dy_tab; 0: the only sample of a one-sample frame); its origin
+// is {fc.org_x, fc.org_y, fc.org_z}
+__device__ __forceinline__ V3 rf_primary_dir(const RtFrameConsts &fc, int pix, int sidx = 0)
 {
     const int ly = pix / fc.width, px = pix - ly * fc.width;
     const int py = fc.y0 + ly;
-    V3 dir{fc.dx_tab[px], fc.dy_tab[py], fc.eye_nz};
+    V3 dir{fc.dx_tab[sidx * fc.width + px], fc.dy_tab[sidx * fc.height + py], fc.eye_nz};
     normalise_inplace(dir);
     const float y = dir.y * fc.cos_pitch - dir.z * fc.sin_pitch;
     float z = dir.y * fc.sin_pitch + dir.z * fc.cos_pitch;

@@ -185,13 +185,26 @@ int rt_reflect_set_kind_materials(RtReflect *r, int which, const rt_material *m,
 void rt_reflect_kind_list_changed(RtReflect *r, int which, int n_old, int n_new);
 int rt_reflect_set_scope(RtReflect *r, int scope);
 int rt_reflect_scope(const RtReflect *r);
+int rt_reflect_set_samples(RtReflect *r, int mode);
+int rt_reflect_samples(const RtReflect *r);
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n);
 int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned long long sphere_gen, int npx,
                        bool need_rgba, float **rgba_scratch, hipStream_t stream);
-int rt_reflect_begin_frame(RtReflect *r, int depth, hipStream_t stream);
+// the scratch of a supersampled frame (rt_scene_set_reflect_samples): the pixel-samples of its largest group, which the
+// queues and the slab must hold; the pixels of the running sum (0: one group, no sum); whether a buffer would be
+// re-allocated for it
+struct RtSamplesPlan {
+    int entries, sum_px;
+    bool grows;
+};
+int rt_reflect_samples_plan(const RtReflect *r, int n, int npx, RtSamplesPlan *plan);
+int rt_reflect_prepare_samples(RtReflect *r, const RtSamplesPlan *plan);
+int rt_reflect_begin_frame(RtReflect *r, int depth, int samples, hipStream_t stream);
 int rt_reflect_mark_frame_start(RtReflect *r, hipStream_t stream);
 int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute,
                       hipStream_t stream);
+int rt_reflect_launch_samples(RtReflect *r, const RtFrameConsts *fc, const RtFrameConsts *out, const RtKernelChoice *kc,
+                              const float4 *d_spheres, int n, int depth, hipStream_t stream);
 int rt_reflect_set_timing(RtReflect *r, int on);
 int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out);
 // the scene's sphere BVH (rt_bvh.h), shared by reflective frames and ray queries

@@ -20,6 +20,12 @@
 // any-hit over every kind (q_shade_hit) -- the ray queries' own functions. The host launches KINDS = true only when
 // the scope is the scene and the scene holds a plane, a cube or a mesh: every other frame runs today's code.
 //
+// Supersampled frames (rt_scene_set_reflect_samples(RT_REFLECT_SAMPLES_MANY)) run the same passes over
+// groups of at most RT_REFLECT_SAMPLE_GROUP samples: the frame kernel once per sample into a slab of a scene-owned
+// [G][npx] buffer, the primary pass's SAMPLES = true instantiation over all G * npx pixel-samples (a queue entry's `pix`
+// is then the slab index), the bounces as they are with the slab as their rgba, and rt_reflect_resolve, which sums a
+// pixel's slab entries in ascending sample order and is the only pass that touches the caller's outputs.
+//
 // The BVH and the per-ray pieces the ray queries share are in rt_bvh.h, the all-kinds casts in rt_cast.h.
 #include "rt_cast.h"
 
@@ -31,11 +37,13 @@
 
 #define RT_REFLECT_BLOCK RT_BVH_BLOCK
 #define RT_BOUNCE_GRID 2048    // workgroups of a bounce launch (grid-stride over the queue)
+#define RT_REFLECT_SAMPLE_GROUP 4   // samples of a supersampled frame that share one run of the passes (bounds the scratch)
+#define RT_REFLECT_MAX_GROUPS ((RT_MAX_SPP + RT_REFLECT_SAMPLE_GROUP - 1) / RT_REFLECT_SAMPLE_GROUP)
 
 struct QEntry {    // one queued ray: 48 bytes
     float ox, oy, oz, dx, dy, dz;
     float w, cr, cg, cb;
-    int pix;       // band-local pixel index
+    int pix;       // band-local pixel index (a supersampled frame: sample slot * band pixels + that)
     int pad_;
 };
 
@@ -193,19 +201,28 @@ __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float
 
 // The primary pass: every pixel of the band; queues those whose primary hit is reflective (or, GLASS, transparent).
 // KINDS: the hit is castRay's over every kind (the frame kernel's own hit, as the G-buffers show for NEAREST).
-template <bool GLASS, bool KINDS>
+// SAMPLES: a group of fc.spp samples, the first of them sample fc.sample_base of the raygen tables' total. Thread i is
+// pixel i % npx at sample fc.sample_base + i / npx; fc.rgba is the group's slab [fc.spp][npx], where the frame kernel
+// has left that sample's L at [i], and the queue entry's pix is i.
+template <bool GLASS, bool KINDS, bool SAMPLES>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtFrameConsts fc, const RtReflectDev rd,
                                                                        QEntry *q, int *count, const RtKindsDev kd)
 {
     __shared__ int stack_lds[RT_BVH_STACK * RT_REFLECT_BLOCK];
     const LdsStack stk{stack_lds, (int)threadIdx.x};
     const int npx = fc.width * fc.local_rows;
-    const int pix = (int)(blockIdx.x * RT_REFLECT_BLOCK + threadIdx.x);
-    const bool valid = pix < npx;
+    const int pix = (int)(blockIdx.x * RT_REFLECT_BLOCK + threadIdx.x);   // SAMPLES: the slab index i
+    const bool valid = pix < (SAMPLES ? fc.spp * npx : npx);               // (the host has checked that it fits an int)
     QEntry e{};
     bool push = false;
     if (valid) {
-        const V3 D = rf_primary_dir(fc, pix);   // one sample: sample_base 0 is checked by the host
+        V3 D;
+        if constexpr (SAMPLES) {
+            const int j = pix / npx;
+            D = rf_primary_dir(fc, pix - j * npx, fc.sample_base + j);
+        } else {
+            D = rf_primary_dir(fc, pix);   // one sample: sample_base 0 is checked by the host
+        }
         const V3 O{fc.org_x, fc.org_y, fc.org_z};
         float nt;
         int hit, kind = RT_HIT_SPHERE;                                          // hit: the list position within its kind
@@ -340,6 +357,53 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
     }
 }
 
+// The resolve pass of a supersampled frame, one thread per band pixel: S = (the earlier groups' sum, or +0) + the
+// group's g slab entries of the pixel in ascending sample order, per channel in binary32 (the frame kernel's
+// acc = 0.f; acc = acc + fr). Not the last group: S goes to `sum`. The last group: the frame kernel's write-back for
+// `n_samples` samples of `total` -- accumulate, rgba = (S, n_samples), the packed word of S / total.
+__global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_resolve(const float4 *slab, int npx, int g, float4 *sum,
+                                                                       int first, int last, float4 *rgba, uint32_t *packed,
+                                                                       int flags, float n_samples, float total)
+{
+    const int pix = (int)(blockIdx.x * RT_REFLECT_BLOCK + threadIdx.x);
+    if (pix >= npx) return;
+    float r = 0.f, gr = 0.f, b = 0.f;
+    if (!first) {
+        const float4 s = sum[pix];
+        r = s.x; gr = s.y; b = s.z;
+    }
+    for (int j = 0; j < g; ++j) {
+        const float4 c = slab[(size_t)j * (size_t)npx + (size_t)pix];
+        r = r + c.x;
+        gr = gr + c.y;
+        b = b + c.z;
+    }
+    if (!last) {
+        sum[pix] = make_float4(r, gr, b, 0.f);
+        return;
+    }
+    float w = n_samples;
+    if (rgba) {
+        if (flags & RT_FLAG_ACCUMULATE) {
+            const float4 old = rgba[pix];
+            r = old.x + r;
+            gr = old.y + gr;
+            b = old.z + b;
+            w = old.w + w;
+        }
+        rgba[pix] = make_float4(r, gr, b, w);
+    }
+    if (packed && (flags & RT_FLAG_RESOLVE)) {
+        float mr = r, mg = gr, mb = b;
+        if (total != 1.f) {
+            mr = r / total;
+            mg = gr / total;
+            mb = b / total;
+        }
+        packed[pix] = rgb_to_int(f2i(mr * 254.f), f2i(mg * 254.f), f2i(mb * 254.f));
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -369,13 +433,19 @@ struct RtReflect {
     bool glass_dirty = false;
     DevArray<float2> d_glass;
     int scope = RT_REFLECT_SPHERES;       // rt_scene_set_reflect_scope
+    int samples = RT_REFLECT_SAMPLES_ONE; // rt_scene_set_reflect_samples
     RtKTable plane_k, cube_k;             // read only by frames under RT_REFLECT_SCENE
     RtSphereBvh bvh;                      // the sphere BVH (shared with the ray queries)
     // queues and counters
     DevArray<QEntry> d_q[2];
     DevArray<int> d_cnt;
     DevArray<float4> d_rgba;              // frame-kernel output when the caller gave no rgba
+    // supersampled frames: the group's per-sample colours [G][npx] and, when there are several groups, their running sum
+    DevArray<float4> d_slab, d_sum;
+    HipEvent sev[RT_REFLECT_MAX_GROUPS][RT_MAX_REFLECT_DEPTH + 4];   // per group: rt_reflect_launch_samples
     // the last frame
+    int last_groups = 1;                  // runs of the passes (a supersampled frame: its groups), one counter row each
+    bool last_samples = false;            // it was a supersampled frame (timed through sev)
     int last_depth = 0;
     bool have_frame = false;
     int timing = 0;
@@ -684,6 +754,18 @@ int rt_reflect_set_scope(RtReflect *r, int scope)
 
 int rt_reflect_scope(const RtReflect *r) { return r->scope; }
 
+int rt_reflect_set_samples(RtReflect *r, int mode)
+{
+    if (mode != RT_REFLECT_SAMPLES_ONE && mode != RT_REFLECT_SAMPLES_MANY) {
+        rt_set_error("rt_scene_set_reflect_samples: mode %d is not RT_REFLECT_SAMPLES_ONE or RT_REFLECT_SAMPLES_MANY", mode);
+        return RT_ERR_INVALID;
+    }
+    r->samples = mode;
+    return RT_OK;
+}
+
+int rt_reflect_samples(const RtReflect *r) { return r->samples; }
+
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n)
 {
     // (the plane and cube tables count under either scope: the upload is due whenever they changed)
@@ -691,7 +773,8 @@ bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, 
 }
 
 // Brings materials and BVH up to date (the caller has waited for every frame that may read them) and makes sure the
-// queues hold `npx` pixels. rgba_scratch: set when the caller has no rgba buffer.
+// queues hold `npx` pixels (a supersampled frame: the pixel-samples of a group). rgba_scratch: set when the caller has
+// no rgba buffer.
 int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned long long sphere_gen, int npx,
                        bool need_rgba, float **rgba_scratch, hipStream_t stream)
 {
@@ -726,12 +809,38 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
         t->dirty = false;
     }
     for (DevArray<QEntry> &q : r->d_q) RT_HIP(q.reserve((size_t)npx));
-    RT_HIP(r->d_cnt.reserve(RT_MAX_REFLECT_DEPTH + 1));
+    RT_HIP(r->d_cnt.reserve(RT_REFLECT_MAX_GROUPS * (RT_MAX_REFLECT_DEPTH + 1)));   // one row per group
     *rgba_scratch = nullptr;
     if (need_rgba) {
         RT_HIP(r->d_rgba.reserve((size_t)npx));
         *rgba_scratch = reinterpret_cast<float *>(r->d_rgba.get());
     }
+    return RT_OK;
+}
+
+// The scratch of a supersampled frame of `n` samples over `npx` band pixels (RtSamplesPlan, rt_internal.h).
+// RT_ERR_CAPACITY when a group's pixel-samples do not fit the int of QEntry::pix (and of the bounces' grid stride).
+int rt_reflect_samples_plan(const RtReflect *r, int n, int npx, RtSamplesPlan *plan)
+{
+    const int g = std::min(n, RT_REFLECT_SAMPLE_GROUP);
+    const long long e = (long long)g * npx;
+    if (e > 0x7fffffffLL - (long long)RT_BOUNCE_GRID * RT_REFLECT_BLOCK) {
+        rt_set_error("rt_scene_render: %d samples of %d pixels per pass exceed the reflective queues' index range", g, npx);
+        return RT_ERR_CAPACITY;
+    }
+    plan->entries = (int)e;
+    plan->sum_px = n > g ? npx : 0;
+    plan->grows = (size_t)e > r->d_slab.capacity() || (size_t)e > r->d_q[0].capacity() || (size_t)e > r->d_q[1].capacity() ||
+                  (size_t)plan->sum_px > r->d_sum.capacity();
+    return RT_OK;
+}
+
+// The slab and the running sum of a plan: after rt_reflect_prepare (the queues) and under its protocol -- after the
+// frames in flight, and after a host wait when it re-allocates
+int rt_reflect_prepare_samples(RtReflect *r, const RtSamplesPlan *plan)
+{
+    RT_HIP(r->d_slab.reserve((size_t)plan->entries));
+    if (plan->sum_px > 0) RT_HIP(r->d_sum.reserve((size_t)plan->sum_px));
     return RT_OK;
 }
 
@@ -743,9 +852,12 @@ static hipError_t rt_reflect_mark(RtReflect *r, int slot, hipStream_t stream)
     return e != hipSuccess ? e : hipEventRecord(r->ev[slot].get(), stream);
 }
 
-int rt_reflect_begin_frame(RtReflect *r, int depth, hipStream_t stream)
+// samples: 0 for a one-sample frame, else the samples of a supersampled one (rt_reflect_launch_samples)
+int rt_reflect_begin_frame(RtReflect *r, int depth, int samples, hipStream_t stream)
 {
-    RT_HIP(hipMemsetAsync(r->d_cnt.get(), 0, sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), stream));
+    r->last_samples = samples > 0;
+    r->last_groups = samples > 0 ? (samples + RT_REFLECT_SAMPLE_GROUP - 1) / RT_REFLECT_SAMPLE_GROUP : 1;
+    RT_HIP(hipMemsetAsync(r->d_cnt.get(), 0, sizeof(int) * (size_t)r->last_groups * (RT_MAX_REFLECT_DEPTH + 1), stream));
     r->last_depth = depth;
     r->have_frame = true;
     r->timed = r->timing != 0;
@@ -759,12 +871,17 @@ int rt_reflect_mark_frame_start(RtReflect *r, hipStream_t stream)
     return RT_OK;
 }
 
-// The passes after the frame kernel (which has written fc->rgba).
-int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute,
-                      hipStream_t stream)
+// What the passes of a frame read and which instantiations run them
+struct RfPasses {
+    RtReflectDev rd;
+    RtKindsDev kd;
+    bool glass, kinds;
+};
+
+static RfPasses rf_passes(const RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute)
 {
-    RT_HIP(rt_reflect_mark(r, 1, stream));
-    RtReflectDev rd{};
+    RfPasses p{};
+    RtReflectDev &rd = p.rd;
     rd.nodes = (!brute && r->bvh.ok) ? r->bvh.d_nodes.get() : nullptr;
     rd.lsph = r->bvh.d_lsph.get();
     rd.order = r->bvh.d_order.get();
@@ -773,27 +890,92 @@ int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_sph
     rd.k = r->k_dev.empty() ? nullptr : r->d_k.get();
     rd.depth = depth;
     rd.glass = r->glass_dev.empty() ? nullptr : r->d_glass.get();
-    const bool glass = rd.glass != nullptr;   // mirror-only frames run the GLASS = false instantiations (today's code)
+    p.glass = rd.glass != nullptr;   // mirror-only frames run the GLASS = false instantiations (today's code)
     // KINDS only where the scope is the scene and there is something besides spheres: every frame that rendered before
     // the scope existed runs the KINDS = false instantiations
-    const bool kinds = r->scope == RT_REFLECT_SCENE && (fc->n_planes > 0 || fc->n_cubes > 0 || fc->n_boxes > 0);
-    RtKindsDev kd{};
-    kd.k_plane = (kinds && !r->plane_k.k_dev.empty()) ? r->plane_k.d_k.get() : nullptr;
-    kd.k_cube = (kinds && !r->cube_k.k_dev.empty()) ? r->cube_k.d_k.get() : nullptr;
-    const auto primary = kinds ? (glass ? rt_reflect_primary<true, true> : rt_reflect_primary<false, true>)
-                               : (glass ? rt_reflect_primary<true, false> : rt_reflect_primary<false, false>);
-    const auto bounce = kinds ? (glass ? rt_reflect_bounce<true, true> : rt_reflect_bounce<false, true>)
-                              : (glass ? rt_reflect_bounce<true, false> : rt_reflect_bounce<false, false>);
-    const int npx = fc->width * fc->local_rows;
-    hipLaunchKernelGGL(primary, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
-                       stream, *fc, rd, r->d_q[0].get(), r->d_cnt.get(), kd);
+    p.kinds = r->scope == RT_REFLECT_SCENE && (fc->n_planes > 0 || fc->n_cubes > 0 || fc->n_boxes > 0);
+    p.kd.k_plane = (p.kinds && !r->plane_k.k_dev.empty()) ? r->plane_k.d_k.get() : nullptr;
+    p.kd.k_cube = (p.kinds && !r->cube_k.k_dev.empty()) ? r->cube_k.d_k.get() : nullptr;
+    return p;
+}
+
+// The primary pass over `threads` pixels (SAMPLES: pixel-samples) and the `depth` bounces, with the counter row `cnt`;
+// mark(slot) after the primary pass (2) and after bounce b (2 + b)
+template <bool SAMPLES, typename Mark>
+static int rf_run_passes(RtReflect *r, const RfPasses &p, const RtFrameConsts *fc, int threads, int depth, int *cnt,
+                         hipStream_t stream, Mark mark)
+{
+    const auto primary = p.kinds ? (p.glass ? rt_reflect_primary<true, true, SAMPLES> : rt_reflect_primary<false, true, SAMPLES>)
+                                 : (p.glass ? rt_reflect_primary<true, false, SAMPLES> : rt_reflect_primary<false, false, SAMPLES>);
+    const auto bounce = p.kinds ? (p.glass ? rt_reflect_bounce<true, true> : rt_reflect_bounce<false, true>)
+                                : (p.glass ? rt_reflect_bounce<true, false> : rt_reflect_bounce<false, false>);
+    hipLaunchKernelGGL(primary, dim3((threads + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
+                       stream, *fc, p.rd, r->d_q[0].get(), cnt, p.kd);
     RT_HIP(hipGetLastError());
-    RT_HIP(rt_reflect_mark(r, 2, stream));
+    RT_HIP(mark(2));
     for (int b = 1; b <= depth; ++b) {
-        hipLaunchKernelGGL(bounce, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, rd, b,
-                           r->d_q[(b - 1) & 1].get(), r->d_cnt.get() + (b - 1), r->d_q[b & 1].get(), r->d_cnt.get() + b, kd);
+        hipLaunchKernelGGL(bounce, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, p.rd, b,
+                           r->d_q[(b - 1) & 1].get(), cnt + (b - 1), r->d_q[b & 1].get(), cnt + b, p.kd);
         RT_HIP(hipGetLastError());
-        RT_HIP(rt_reflect_mark(r, 2 + b, stream));
+        RT_HIP(mark(2 + b));
+    }
+    return RT_OK;
+}
+
+// The passes after the frame kernel (which has written fc->rgba).
+int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute,
+                      hipStream_t stream)
+{
+    RT_HIP(rt_reflect_mark(r, 1, stream));
+    const RfPasses p = rf_passes(r, fc, d_spheres, n, depth, brute);
+    const int rc = rf_run_passes<false>(r, p, fc, fc->width * fc->local_rows, depth, r->d_cnt.get(), stream,
+                                        [&](int slot) { return rt_reflect_mark(r, slot, stream); });
+    if (rc != RT_OK) return rc;
+    RT_HIP(r->done.create());
+    RT_HIP(hipEventRecord(r->done.get(), stream));
+    return RT_OK;
+}
+
+// A supersampled frame, after rt_reflect_prepare_samples and rt_reflect_begin_frame. `fc`: the uniforms
+// of one sample of the frame -- spp 1, no accumulate, no resolve, no packed output; its rgba and sample_base are set
+// here. `out`: the caller's frame (rgba, packed, flags, spp, sample_base, sample_total), which only the resolve pass of
+// the last group touches. Per group of at most RT_REFLECT_SAMPLE_GROUP samples: the frame kernel per sample into its
+// slab, the primary pass over the group, the bounces, the resolve pass.
+int rt_reflect_launch_samples(RtReflect *r, const RtFrameConsts *fc, const RtFrameConsts *out, const RtKernelChoice *kc,
+                              const float4 *d_spheres, int n, int depth, hipStream_t stream)
+{
+    const int npx = fc->width * fc->local_rows;
+    const int n_samples = out->spp, groups = r->last_groups;
+    float4 *const slab = r->d_slab.get();
+    for (int gi = 0; gi < groups; ++gi) {
+        const int k0 = out->sample_base + gi * RT_REFLECT_SAMPLE_GROUP;
+        const int g = std::min(RT_REFLECT_SAMPLE_GROUP, n_samples - gi * RT_REFLECT_SAMPLE_GROUP);
+        HipEvent *ev = r->sev[gi];
+        const auto mark = [&](int slot) {
+            if (!r->timing) return hipSuccess;
+            const hipError_t e = ev[slot].create(hipEventDefault);
+            return e != hipSuccess ? e : hipEventRecord(ev[slot].get(), stream);
+        };
+        RT_HIP(mark(0));
+        RtFrameConsts f = *fc;
+        for (int j = 0; j < g; ++j) {
+            f.sample_base = k0 + j;
+            f.rgba = reinterpret_cast<float *>(slab + (size_t)j * (size_t)npx);
+            RT_HIP(rt_dev_launch_trace(&f, d_spheres, kc->tile, kc->cull, kc->mode, kc->feat, stream));
+        }
+        RT_HIP(mark(1));
+        // the passes' view of the group: g samples from k0, the slab as their rgba, nothing packed
+        f.spp = g;
+        f.sample_base = k0;
+        f.rgba = reinterpret_cast<float *>(slab);
+        const RfPasses p = rf_passes(r, &f, d_spheres, n, depth, kc->cull == 0);
+        const int rc = rf_run_passes<true>(r, p, &f, g * npx, depth, r->d_cnt.get() + gi * (RT_MAX_REFLECT_DEPTH + 1), stream, mark);
+        if (rc != RT_OK) return rc;
+        hipLaunchKernelGGL(rt_reflect_resolve, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
+                           stream, slab, npx, g, r->d_sum.get(), gi == 0 ? 1 : 0, gi == groups - 1 ? 1 : 0,
+                           reinterpret_cast<float4 *>(out->rgba), out->packed, out->flags, (float)n_samples, out->sample_total);
+        RT_HIP(hipGetLastError());
+        RT_HIP(mark(depth + 3));
     }
     RT_HIP(r->done.create());
     RT_HIP(hipEventRecord(r->done.get(), stream));
@@ -816,12 +998,20 @@ int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out)
     if (!r->have_frame) return RT_OK;
     out->depth = r->last_depth;
     if (r->done.get()) RT_HIP(hipEventSynchronize(r->done.get()));   // the last frame only, not the whole device
-    RT_HIP(hipMemcpy(out->queue, r->d_cnt.get(), sizeof(int) * (RT_MAX_REFLECT_DEPTH + 1), hipMemcpyDeviceToHost));
+    // (a supersampled frame: queue[] and pass_ms[] are summed over its groups, the resolve passes counted in the last
+    // bounce's slot)
+    int cnt[RT_REFLECT_MAX_GROUPS][RT_MAX_REFLECT_DEPTH + 1];
+    RT_HIP(hipMemcpy(cnt, r->d_cnt.get(), sizeof(int) * (size_t)r->last_groups * (RT_MAX_REFLECT_DEPTH + 1), hipMemcpyDeviceToHost));
+    for (int g = 0; g < r->last_groups; ++g)
+        for (int b = 0; b <= RT_MAX_REFLECT_DEPTH; ++b) out->queue[b] += cnt[g][b];
     if (r->timed) {
-        for (int p = 0; p < r->last_depth + 2; ++p) {
-            float ms = 0.f;
-            RT_HIP(hipEventElapsedTime(&ms, r->ev[p].get(), r->ev[p + 1].get()));
-            out->pass_ms[p] = ms;
+        for (int g = 0; g < r->last_groups; ++g) {
+            const HipEvent *ev = r->last_samples ? r->sev[g] : r->ev;
+            for (int p = 0; p < r->last_depth + (r->last_samples ? 3 : 2); ++p) {
+                float ms = 0.f;
+                RT_HIP(hipEventElapsedTime(&ms, ev[p].get(), ev[p + 1].get()));
+                out->pass_ms[std::min(p, r->last_depth + 1)] += ms;
+            }
         }
         out->timed = 1;
     }

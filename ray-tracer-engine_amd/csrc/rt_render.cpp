@@ -297,16 +297,19 @@ static int reflect_supported(const rt_scene *s, const rt_frame_desc *fd)
     }
     const char *why = nullptr;
     const bool spheres_only = !s->refl || rt_reflect_scope(s->refl.get()) == RT_REFLECT_SPHERES;
+    const bool many = s->refl && rt_reflect_samples(s->refl.get()) == RT_REFLECT_SAMPLES_MANY;
     if (spheres_only && (s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0))
         why = "planes, cubes or a mesh in the scene (rt_scene_set_reflect_scope(RT_REFLECT_SCENE) lifts this)";
-    else if (o.spp > 1 || o.sample_base != 0 || o.sample_total > 1) why = "more than one sample per pixel";
-    else if (o.accumulate) why = "accumulate";
+    else if (!many && (o.spp > 1 || o.sample_base != 0 || o.sample_total > 1))
+        why = "more than one sample per pixel (rt_scene_set_reflect_samples(RT_REFLECT_SAMPLES_MANY) lifts this)";
+    else if (!many && o.accumulate) why = "accumulate (rt_scene_set_reflect_samples(RT_REFLECT_SAMPLES_MANY) lifts this)";
     else if (o.interleave_count > 1 || o.interleave_index != 0 || o.interleave_rows != 0) why = "interleave_*";
     else if (o.packed24) why = "packed24";
     else if (o.table_lds) why = "table_lds";
     else if (o.profile) why = "profile";
     if (why) {
-        rt_set_error("rt_scene_render: reflect_depth > 0 does not support %s (one sample, plain outputs)", why);
+        rt_set_error("rt_scene_render: reflect_depth > 0 does not support %s (%s, plain outputs)", why,
+                     many ? "samples through spp / accumulate" : "one sample");
         return RT_ERR_UNSUPPORTED;
     }
     return RT_OK;
@@ -360,6 +363,22 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     rc = rt_frame_kernel_choice(s, fd, &kc);
     if (rc != RT_OK) return rc;
     if (fc.local_rows == 0) return RT_OK;   // this rank owns no rows of the frame
+    // A supersampled reflective frame (rt_scene_set_reflect_samples): anything but the request a
+    // one-sample frame serves, which runs as it always has. `out` keeps the caller's outputs and sample range for the
+    // resolve pass; fc becomes one sample of the frame, which the frame kernel renders into the scene's scratch.
+    const rt_launch_opts &o = fd->opts;
+    const bool samples = reflect_depth > 0 && s->refl && rt_reflect_samples(s->refl.get()) == RT_REFLECT_SAMPLES_MANY &&
+                         !(fc.spp == 1 && fc.sample_total == 1.f && o.sample_base == 0 && !o.accumulate && o.resolve != -1);
+    const RtFrameConsts out = fc;
+    const int npx = fc.width * fc.local_rows;
+    RtSamplesPlan plan{npx, 0, false};   // the queues hold the band's pixels, or the pixel-samples of a group
+    if (samples) {
+        rc = rt_reflect_samples_plan(s->refl.get(), out.spp, npx, &plan);   // (too large: refused before anything is built)
+        if (rc != RT_OK) return rc;
+        fc.spp = 1;
+        fc.flags &= ~(RT_FLAG_ACCUMULATE | RT_FLAG_RESOLVE);
+        fc.packed = nullptr;
+    }
     int view = -1;
     rc = rt_scene_prepare_view(s, fd, kc, slot, &fc, stream, &view);
     if (rc != RT_OK) return rc;
@@ -367,32 +386,43 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         // the queues, the BVH and the materials are the scene's: after every frame launched so far (a host wait only
         // when the BVH or the materials change)
         RtReflect *refl = rt_scene_reflect(s);
-        if (rt_reflect_needs_upload(refl, s->sphere_gen, s->n_spheres)) {
+        // (a host wait too when the samples' scratch is re-allocated)
+        if (plan.grows || rt_reflect_needs_upload(refl, s->sphere_gen, s->n_spheres)) {
             rc = rt_scene_quiesce(s);
             if (rc != RT_OK) return rc;
         }
         rc = rt_scene_wait_all_frames(s, stream);
         if (rc != RT_OK) return rc;
         float *scratch = nullptr;
-        rc = rt_reflect_prepare(refl, s->h_prev.data(), s->n_spheres, s->sphere_gen, fc.width * fc.local_rows,
-                                fc.rgba == nullptr, &scratch, stream);
+        rc = rt_reflect_prepare(refl, s->h_prev.data(), s->n_spheres, s->sphere_gen, plan.entries, !samples && fc.rgba == nullptr,
+                                &scratch, stream);
         if (rc != RT_OK) return rc;
-        if (!fc.rgba) fc.rgba = scratch;
-        rc = rt_reflect_begin_frame(refl, reflect_depth, stream);
+        if (samples) {
+            rc = rt_reflect_prepare_samples(refl, &plan);
+            if (rc != RT_OK) return rc;
+        } else if (!fc.rgba) {
+            fc.rgba = scratch;
+        }
+        rc = rt_reflect_begin_frame(refl, reflect_depth, samples ? out.spp : 0, stream);
         if (rc != RT_OK) return rc;
     }
     if (s->tile_order_mode != 0) {
         rc = rt_scene_prepare_tile_order(s, kc, &fc, stream);
         if (rc != RT_OK) return rc;
     }
-    if (reflect_depth > 0) {
-        rc = rt_reflect_mark_frame_start(s->refl.get(), stream);
+    if (samples) {   // the frame kernel per sample, the passes per group, the resolve pass
+        rc = rt_reflect_launch_samples(s->refl.get(), &fc, &out, &kc, s->d_spheres.get(), s->n_spheres, reflect_depth, stream);
         if (rc != RT_OK) return rc;
-    }
-    RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres.get(), kc.tile, kc.cull, kc.mode, kc.feat, stream));
-    if (reflect_depth > 0) {
-        rc = rt_reflect_launch(s->refl.get(), &fc, s->d_spheres.get(), s->n_spheres, reflect_depth, kc.cull == 0, stream);
-        if (rc != RT_OK) return rc;
+    } else {
+        if (reflect_depth > 0) {
+            rc = rt_reflect_mark_frame_start(s->refl.get(), stream);
+            if (rc != RT_OK) return rc;
+        }
+        RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres.get(), kc.tile, kc.cull, kc.mode, kc.feat, stream));
+        if (reflect_depth > 0) {
+            rc = rt_reflect_launch(s->refl.get(), &fc, s->d_spheres.get(), s->n_spheres, reflect_depth, kc.cull == 0, stream);
+            if (rc != RT_OK) return rc;
+        }
     }
     s->view_last = view;
     return rt_scene_note_launch(s, stream, slot >= 0 ? &s->cones[slot] : nullptr, view >= 0 ? &s->views[view] : nullptr);

@@ -369,6 +369,16 @@ extern "C" int rt_scene_set_reflect_scope(rt_scene *s, int scope)
     return rt_reflect_set_scope(rt_scene_reflect(s), scope);
 }
 
+// How reflective frames sample a pixel: a host-side switch, read when a frame is launched
+extern "C" int rt_scene_set_reflect_samples(rt_scene *s, int mode)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_reflect_samples: null scene");
+        return RT_ERR_INVALID;
+    }
+    return rt_reflect_set_samples(rt_scene_reflect(s), mode);
+}
+
 extern "C" int rt_scene_set_plane_materials(rt_scene *s, const rt_material *per_plane, int n)
 {
     if (!s) {
