@@ -579,6 +579,72 @@ int rt_scene_denoise(rt_scene *s, const rt_denoise_desc *d, void *stream);
 int rt_scene_set_denoise_timing(rt_scene *s, int on);
 int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n);
 
+/* ------------------------------------------------------------------ *
+ * Temporal accumulation: a frame's history, reprojected *
+ * into the current view by the frame's own G-buffer.                   *
+ * ------------------------------------------------------------------ */
+#define RT_TEMPORAL_MAX_HISTORY 256
+typedef struct rt_temporal_desc {
+    uint32_t struct_size;        /* sizeof(rt_temporal_desc); 0 reads as this layout. Fields past a caller's size read as 0 */
+    int width, height;           /* of every buffer below: whole frames, rows of `width` pixels                            */
+    float aspect;                /* the view the current buffers were rendered with (rt_frame_desc.aspect / cam)           */
+    rt_camera cam;
+    float prev_aspect;           /* the view the prev_* buffers were rendered with                                         */
+    rt_camera prev_cam;
+    const float *rgba_in;        /* device, float4, 16-byte aligned: the current colour (may be a jittered sample's)       */
+    const float *depth;          /* device, the current guides in the rt_frame_desc.aov_* layouts: float, 4-byte aligned   */
+    const float *normal;         /*   float4, 16-byte aligned                                                              */
+    const int *id;               /*   int2 (kind, index), 8-byte aligned                                                   */
+    const float *prev_rgba;      /* device, float4: (accumulated colour, history length n) -- a former rgba_out            */
+    const float *prev_depth;     /* device: the guides of the frame that former call accumulated, same layouts             */
+    const float *prev_normal;
+    const int *prev_id;
+    const float *prev_moments;   /* NULL, or device, float2, 8-byte aligned: a former moments_out                          */
+    float *rgba_out;             /* device, float4, 16-byte aligned: (new accumulated colour, new n)                       */
+    float *moments_out;          /* NULL, or device, float2, 8-byte aligned: running means of (luma, luma^2); needs
+                                    prev_moments unless `reset`                                                            */
+    uint32_t *pixels;            /* NULL, or device: the packed framebuffer of rgba_out's colour, rgbToInt(c * 254)        */
+    int reset;                   /* non-zero: no history is read (every prev_* may be NULL): rgba_out = (colour, 1)        */
+    int max_history;             /* 1 .. RT_TEMPORAL_MAX_HISTORY: n stops growing there (weight 1 / n of a new frame) [32] */
+    float depth_tolerance;       /* finite, > 0: relative, on squared distances to the previous eye               [0.02]   */
+    float normal_cos_min;        /* in [0, 1]: smallest cosine between the two normals                            [0.9]    */
+    int variant;                 /* 0: the product kernel; 1: the plain one-thread-per-pixel yardstick. The same bits      */
+} rt_temporal_desc;
+
+/* The defaults in brackets above (the interface's own choices, not measurements); sizes, views and pointers 0. */
+void rt_temporal_desc_init(rt_temporal_desc *d);
+
+/* Blends the current colour into the history on `stream` (a hipStream_t; NULL = the null stream). Per pixel: its
+ * world point (its primary ray, formed as rt_scene_primary_rays forms it, times `depth`) is taken into the previous
+ * view; the four previous pixels around where it lands are kept if they show the same surface -- equal id, a distance
+ * to the previous eye that agrees with prev_depth within depth_tolerance, a normal within normal_cos_min -- and
+ * blended bilinearly into a history (colour H, length n_prev); the result is H + (c - H) / n with
+ * n = min(n_prev + 1, max_history), and the luminance moments likewise. A pixel without history -- `reset`, sky, a
+ * depth that is not finite and > 0, a point behind the previous eye or outside its frame, no agreeing tap -- gets
+ * (c, 1). With cam / aspect equal to prev_cam / prev_aspect byte for byte the only tap is the pixel itself with
+ * weight 1: a standing camera gives the exact running mean. DESIGN.md 6i gives every formula; binary32, + - * / and
+ * compares only, so the result is defined to the bit and both variants return the same bits.
+ * The scene is assumed static between the two frames: there are no motion vectors, a moved object is rejected by
+ * its depth or only by chance. A caller that moves objects or lights passes `reset`.
+ * The call enqueues one kernel and returns; there is no host wait (the first call of a size or aspect uploads that
+ * view's ray tables). The pass gathers: no output may overlap an input. Calls of one scene on different streams are
+ * ordered on the device, one after the other (an event); ordering the call after the frames that wrote its inputs is
+ * the caller's. Before anything is enqueued, and with nothing written: NULL or misaligned pointers (float4 buffers
+ * 16 bytes, id and moments 8, depth and pixels 4), sizes <= 0 or above RT_DENOISE_MAX_SIZE, max_history, variant,
+ * depth_tolerance or normal_cos_min out of range or not finite, an aspect that is not finite and > 0, missing prev_*
+ * without `reset`, moments_out without prev_moments unless `reset`, an output that overlaps an input or another
+ * output -> RT_ERR_INVALID; a stream that is being captured -> RT_ERR_UNSUPPORTED. */
+int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d, void *stream);
+
+/* What the kernels get as uniforms for a view, pure host code: out[0..2] the origin of every primary ray
+ * (eyePos + cam.Org), out[3..6] cos_pitch, sin_pitch, cos_yaw, sin_yaw of camera::rotateDir. */
+int rt_view_terms(int width, int height, float aspect, const rt_camera *cam, float out[7]);
+
+/* Device time of the scene's later temporal calls (hipEvents around the launch; off by default).
+ * rt_scene_temporal_times waits for the last call and fills ms[0 .. *n - 1] (one launch: *n <= 1). cap: room in ms. */
+int rt_scene_set_temporal_timing(rt_scene *s, int on);
+int rt_scene_temporal_times(rt_scene *s, float *ms, int cap, int *n);
+
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
  * tile first -- the frame kernel records every tile's wave duration, and from the previous launch's durations the
  * blocks are sorted on the device (three small kernels, ~15 us): after 1, 2, 4, 8, 16, 32, 64, 96, ... launches of an

@@ -185,6 +185,18 @@ class DenoiseDesc(C.Structure):
                 ("sigma_colour", C.c_float), ("demodulate", C.c_int), ("variant", C.c_int)]
 
 
+class TemporalDesc(C.Structure):
+    """rt_temporal_desc."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
+                ("aspect", C.c_float), ("cam", Camera), ("prev_aspect", C.c_float), ("prev_cam", Camera),
+                ("rgba_in", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p),
+                ("prev_rgba", C.c_void_p), ("prev_depth", C.c_void_p), ("prev_normal", C.c_void_p),
+                ("prev_id", C.c_void_p), ("prev_moments", C.c_void_p),
+                ("rgba_out", C.c_void_p), ("moments_out", C.c_void_p), ("pixels", C.c_void_p),
+                ("reset", C.c_int), ("max_history", C.c_int), ("depth_tolerance", C.c_float),
+                ("normal_cos_min", C.c_float), ("variant", C.c_int)]
+
+
 class ViewListsInfo(C.Structure):
     """rt_view_lists_info."""
     _fields_ = [("read", C.c_int), ("block_w", C.c_int), ("block_h", C.c_int), ("blocks_x", C.c_int), ("blocks_y", C.c_int),
@@ -197,6 +209,7 @@ RT_VIEW_OVERFLOW, RT_VIEW_NOT_BUILT = 1, 2
 
 RT_DENOISE_MAX_ITERATIONS = 6
 RT_DENOISE_MAX_NORMAL_SHIFT = 8
+RT_TEMPORAL_MAX_HISTORY = 256
 
 _lib = None
 
@@ -322,6 +335,11 @@ def load_library():
         "rt_scene_set_denoise_timing": (ci, [vp, ci]),
         "rt_scene_denoise_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_debug_copy16": (ci, [vp, vp, C.c_size_t, vp]),
+        "rt_temporal_desc_init": (None, [C.POINTER(TemporalDesc)]),
+        "rt_scene_temporal": (ci, [vp, C.POINTER(TemporalDesc), vp]),
+        "rt_view_terms": (ci, [ci, ci, cf, C.POINTER(Camera), fp]),
+        "rt_scene_set_temporal_timing": (ci, [vp, ci]),
+        "rt_scene_temporal_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_scene_set_reflect_scope": (ci, [vp, ci]),
         "rt_scene_set_reflect_samples": (ci, [vp, ci]),
         "rt_scene_set_plane_materials": (ci, [vp, C.POINTER(Material), ci]),
@@ -347,6 +365,21 @@ def _fptr(a):
 # ----------------------------------------------------------------------------
 # default scene of the reference (kernel.cu:1189-1192, 1695-1712, 261, 1701)
 # ----------------------------------------------------------------------------
+def view_terms(width, height, aspect, cam):
+    """rt_view_terms: the origin of a view's primary rays, then cos_pitch, sin_pitch, cos_yaw, sin_yaw (7 float32)."""
+    import numpy as np
+    out = np.zeros(7, dtype=np.float32)
+    cam = _copy_camera(cam)
+    _check(load_library().rt_view_terms(width, height, aspect, C.byref(cam), _fptr(out)), "rt_view_terms")
+    return out
+
+
+def _copy_camera(cam) -> Camera:
+    c = Camera()
+    C.memmove(C.byref(c), C.byref(cam), C.sizeof(Camera))
+    return c
+
+
 def default_camera() -> Camera:
     return Camera(Vec3(4, 3, 10), Vec3(0, 0, 1), 0.0, 180.0, -20.0)
 
@@ -826,6 +859,95 @@ class Scene:
                               demodulate=demodulate, variant=variant)
         _check(self.denoise_raw(d, st.cuda_stream), "rt_scene_denoise")
         return {"rgba": out, "packed": packed}
+
+    # ---------------------------------------------------------------- temporal accumulation
+    def temporal_desc(self, width, height, *, cam=None, aspect=None, prev_cam=None, prev_aspect=None, rgba_in=0, depth=0,
+                      normal=0, id=0, prev_rgba=0, prev_depth=0, prev_normal=0, prev_id=0, prev_moments=0, rgba_out=0,
+                      moments_out=0, pixels=0, reset=False, max_history=None, depth_tolerance=None, normal_cos_min=None,
+                      variant=0) -> TemporalDesc:
+        """rt_temporal_desc with rt_temporal_desc_init's defaults where an argument is None (cam / aspect: the
+        default view; prev_cam / prev_aspect: the current ones)."""
+        d = TemporalDesc()
+        self.lib.rt_temporal_desc_init(C.byref(d))
+        d.width, d.height = width, height
+        d.aspect = default_aspect() if aspect is None else aspect
+        d.cam = _copy_camera(cam if cam is not None else default_camera())
+        d.prev_aspect = d.aspect if prev_aspect is None else prev_aspect
+        d.prev_cam = _copy_camera(prev_cam if prev_cam is not None else d.cam)
+        d.rgba_in, d.depth, d.normal, d.id = rgba_in, depth, normal, id
+        d.prev_rgba, d.prev_depth, d.prev_normal, d.prev_id = prev_rgba, prev_depth, prev_normal, prev_id
+        d.prev_moments = prev_moments
+        d.rgba_out, d.moments_out, d.pixels = rgba_out, moments_out, pixels
+        d.reset = 1 if reset else 0
+        for k, v in (("max_history", max_history), ("depth_tolerance", depth_tolerance),
+                     ("normal_cos_min", normal_cos_min), ("variant", variant)):
+            if v is not None:
+                setattr(d, k, v)
+        return d
+
+    def temporal_raw(self, d: TemporalDesc, stream=0) -> int:
+        """rt_scene_temporal as is: returns the status."""
+        return self.lib.rt_scene_temporal(self.handle, C.byref(d), stream)
+
+    def temporal(self, frame, history=None, *, cam=None, aspect=None, colour=None, max_history=None,
+                 depth_tolerance=None, normal_cos_min=None, want_moments=True, want_packed=True, variant=0, stream=None):
+        """Blend a frame that render(..., aov=("depth", "normal", "id")) returned with camera `cam` and `aspect` into
+        `history`, what the previous call returned (None: no history is read -- the first frame, or after objects or
+        lights moved). `colour`: an rgba tensor to accumulate instead of the frame's own, from another render of the
+        same view (a jittered sample_base = k, sample_total = m frame, which cannot carry guides). Returns the new
+        history {'rgba': float32 [rows, W, 4] (accumulated colour, history length), 'moments': float32 [rows, W, 2]
+        or None, 'packed': int32 [rows, W] or None, 'depth', 'normal', 'id': the frame's guide tensors (not copied),
+        'cam', 'aspect'} as new tensors; neither the frame's nor the history's tensors are written. Enqueued on
+        `stream` (default: the current stream); no host wait."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError("no GPU visible: temporal accumulation has no CPU fallback")
+        aov = frame.get("aov") or {}
+        rgba = frame.get("rgba") if colour is None else colour
+        need = ("depth", "normal", "id")
+        if rgba is None or any(k not in aov for k in need):
+            raise RtError(f"temporal needs the frame's rgba (or colour=) and the G-buffer outputs {need}: render with "
+                          f"want_rgba=True and aov={need}")
+        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
+        if tuple(rgba.shape) != (rows, width, 4) or rgba.dtype != torch.float32 or not rgba.is_cuda:
+            raise RtError("temporal: the colour must be a CUDA float32 tensor of the guides' shape [rows, W, 4]")
+        rgba = rgba.contiguous()
+        if history is not None:
+            if tuple(history["rgba"].shape) != (rows, width, 4):
+                raise RtError("temporal: the history is of another size (pass history=None after a resize)")
+            if want_moments and history.get("moments") is None:
+                raise RtError("temporal: want_moments needs a history with moments")
+        cam = _copy_camera(cam if cam is not None else default_camera())
+        aspect = default_aspect() if aspect is None else aspect
+        out = torch.empty_like(rgba)
+        moments = torch.empty((rows, width, 2), dtype=torch.float32, device=rgba.device) if want_moments else None
+        packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
+        st = torch.cuda.current_stream() if stream is None else stream
+        prev = {}
+        if history is not None:
+            prev = dict(prev_cam=history["cam"], prev_aspect=history["aspect"], prev_rgba=history["rgba"].data_ptr(),
+                        prev_depth=history["depth"].data_ptr(), prev_normal=history["normal"].data_ptr(),
+                        prev_id=history["id"].data_ptr(),
+                        prev_moments=history["moments"].data_ptr() if history.get("moments") is not None else 0)
+        d = self.temporal_desc(width, rows, cam=cam, aspect=aspect, rgba_in=rgba.data_ptr(),
+                               depth=aov["depth"].data_ptr(), normal=aov["normal"].data_ptr(), id=aov["id"].data_ptr(),
+                               rgba_out=out.data_ptr(), moments_out=moments.data_ptr() if want_moments else 0,
+                               pixels=packed.data_ptr() if want_packed else 0, reset=history is None,
+                               max_history=max_history, depth_tolerance=depth_tolerance, normal_cos_min=normal_cos_min,
+                               variant=variant, **prev)
+        _check(self.temporal_raw(d, st.cuda_stream), "rt_scene_temporal")
+        return {"rgba": out, "moments": moments, "packed": packed, "depth": aov["depth"], "normal": aov["normal"],
+                "id": aov["id"], "cam": cam, "aspect": aspect}
+
+    def set_temporal_timing(self, on: bool):
+        _check(self.lib.rt_scene_set_temporal_timing(self.handle, 1 if on else 0), "rt_scene_set_temporal_timing")
+
+    def temporal_times(self):
+        """Device ms of the last timed temporal call's launch (waits for it): a list of at most one value."""
+        ms = (C.c_float * 1)()
+        n = C.c_int()
+        _check(self.lib.rt_scene_temporal_times(self.handle, ms, len(ms), C.byref(n)), "rt_scene_temporal_times")
+        return list(ms)[: n.value]
 
     def set_denoise_timing(self, on: bool):
         _check(self.lib.rt_scene_set_denoise_timing(self.handle, 1 if on else 0), "rt_scene_set_denoise_timing")

@@ -231,3 +231,9 @@ void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out);
 // width * height pixels each; ev: null, or iterations + 2 timing events)
 int rt_denoise_launch(const rt_denoise_desc *d, float4 *col0, float4 *col1, float4 *guide, int *key, hipEvent_t *ev,
                       hipStream_t stream);
+
+// rt_temporal.hip: temporal accumulation (d: validated, in this build's layout; dx_tab / dy_tab: the current view's ray
+// tables at one sample; view[7] / prev_view[7]: rt_view_terms of the two views; same_view: they are the same bytes;
+// ev: null, or two timing events)
+int rt_temporal_launch(const rt_temporal_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
+                       const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream);

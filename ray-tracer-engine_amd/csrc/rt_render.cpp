@@ -1,5 +1,5 @@
 // rt_render.cpp -- what a launch does: a caller's descriptions in this build's layout, the by-value frame uniforms,
-// the kernel choice, and the entry points that enqueue work on the scene -- frames, ray queries, the denoiser.
+// the kernel choice, and the entry points that enqueue work on the scene -- frames, ray queries, the denoiser, temporal accumulation.
 //
 // Reference interface replaced here:
 //   rayTrace<<<...>>> launch     /root/reference/kernel.cu:1615, 1780-1783
@@ -627,5 +627,151 @@ extern "C" int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n)
         RT_HIP(hipEventElapsedTime(&ms[i], s->dn_ev[i].get(), s->dn_ev[i + 1].get()));
         *n = i + 1;
     }
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// temporal accumulation (rt_temporal.hip)
+// ---------------------------------------------------------------------------
+extern "C" void rt_temporal_desc_init(rt_temporal_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->max_history = 32;
+    d->depth_tolerance = 0.02f;
+    d->normal_cos_min = 0.9f;
+}
+
+extern "C" int rt_view_terms(int width, int height, float aspect, const rt_camera *cam, float out[7])
+{
+    if (!cam || !out || width <= 0 || height <= 0) {
+        rt_set_error("rt_view_terms: null camera or output, or a size <= 0");
+        return RT_ERR_INVALID;
+    }
+    rt_frame_desc fd;
+    memset(&fd, 0, sizeof fd);
+    fd.width = width; fd.height = height;
+    fd.aspect = aspect;
+    fd.cam = *cam;
+    RtFrameConsts fc;
+    rt_ray_origin(&fd, out);
+    rt_view_rotation(&fd, &fc);
+    out[3] = fc.cos_pitch; out[4] = fc.sin_pitch; out[5] = fc.cos_yaw; out[6] = fc.sin_yaw;
+    return RT_OK;
+}
+
+extern "C" int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_temporal: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_temporal_desc d;
+    as_built(d_in, &d);
+    const bool reset = d.reset != 0;
+    struct Range {
+        uintptr_t p;
+        size_t bytes;
+    };
+    const char *bad = nullptr;
+    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
+        bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
+    else if (!d.rgba_in || !d.depth || !d.normal || !d.id || !d.rgba_out) bad = "rgba_in, depth, normal, id and rgba_out must not be NULL";
+    else if (!reset && (!d.prev_rgba || !d.prev_depth || !d.prev_normal || !d.prev_id))
+        bad = "prev_rgba, prev_depth, prev_normal and prev_id must not be NULL without reset";
+    else if (!reset && d.moments_out && !d.prev_moments) bad = "moments_out needs prev_moments without reset";
+    else if ((((uintptr_t)d.rgba_in | (uintptr_t)d.normal | (uintptr_t)d.rgba_out) & 15u) ||
+             (((uintptr_t)d.id | (uintptr_t)d.moments_out) & 7u) || (((uintptr_t)d.depth | (uintptr_t)d.pixels) & 3u) ||
+             (!reset && ((((uintptr_t)d.prev_rgba | (uintptr_t)d.prev_normal) & 15u) ||
+                         (((uintptr_t)d.prev_id | (uintptr_t)d.prev_moments) & 7u) || ((uintptr_t)d.prev_depth & 3u))))
+        bad = "rgba and normal buffers must be 16-byte aligned, id and moments 8-byte, depth and pixels 4-byte";
+    else if (d.max_history < 1 || d.max_history > RT_TEMPORAL_MAX_HISTORY) bad = "max_history is not in [1, RT_TEMPORAL_MAX_HISTORY]";
+    else if (!(d.depth_tolerance > 0.f) || !std::isfinite(d.depth_tolerance)) bad = "depth_tolerance is not finite and > 0";
+    else if (!(d.normal_cos_min >= 0.f && d.normal_cos_min <= 1.f)) bad = "normal_cos_min is not in [0, 1]";
+    else if (d.variant < 0 || d.variant > 1) bad = "variant is not 0 or 1";
+    else if (!(d.aspect > 0.f) || !std::isfinite(d.aspect) || (!reset && (!(d.prev_aspect > 0.f) || !std::isfinite(d.prev_aspect))))
+        bad = "aspect and prev_aspect must be finite and > 0";
+    else {
+        // the pass gathers: an output that overlaps an input (or another output) would be read after it was written
+        const size_t npx = (size_t)d.width * d.height;
+        const Range outs[3] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.moments_out, npx * 8}, {(uintptr_t)d.pixels, npx * 4}};
+        const Range ins[9] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16},
+                              {(uintptr_t)d.id, npx * 8},
+                              {reset ? 0 : (uintptr_t)d.prev_rgba, npx * 16}, {reset ? 0 : (uintptr_t)d.prev_depth, npx * 4},
+                              {reset ? 0 : (uintptr_t)d.prev_normal, npx * 16}, {reset ? 0 : (uintptr_t)d.prev_id, npx * 8},
+                              {reset ? 0 : (uintptr_t)d.prev_moments, npx * 8}};
+        auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
+        for (int i = 0; i < 3 && !bad; ++i) {
+            for (const Range &in : ins)
+                if (overlap(outs[i], in)) bad = "an output buffer overlaps an input (the pass gathers: it cannot run in place)";
+            for (int j = i + 1; j < 3; ++j)
+                if (overlap(outs[i], outs[j])) bad = "two output buffers overlap";
+        }
+    }
+    if (bad) {
+        rt_set_error("rt_scene_temporal: %s (%d x %d, max_history %d, variant %d)", bad, d.width, d.height, d.max_history, d.variant);
+        return RT_ERR_INVALID;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_temporal: the stream is being captured (the pass is not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    float view[7], prev_view[7];
+    rt_view_terms(d.width, d.height, d.aspect, &d.cam, view);
+    const bool same_view = !reset && memcmp(&d.cam, &d.prev_cam, sizeof d.cam) == 0 && memcmp(&d.aspect, &d.prev_aspect, sizeof d.aspect) == 0;
+    if (reset) memcpy(prev_view, view, sizeof view);
+    else rt_view_terms(d.width, d.height, d.prev_aspect, &d.prev_cam, prev_view);
+    const bool need_rays = !reset && !same_view;
+    if (need_rays && !(s->tp_raygen.get() && s->tp_w == d.width && s->tp_h == d.height &&
+                       memcmp(&s->tp_aspect, &d.aspect, sizeof d.aspect) == 0)) {
+        // another size or aspect: new tables, after the host has seen the last call that read the old ones end
+        RT_HIP(s->tp_done.host_wait());
+        const size_t need = (size_t)d.width + (size_t)d.height;
+        s->tp_w = s->tp_h = 0;
+        RT_HIP(s->tp_raygen.reserve(need));
+        std::vector<float> h(need);
+        rt_raygen_fill(d.width, d.height, d.aspect, 1, h.data());
+        RT_HIP(hipMemcpy(s->tp_raygen.get(), h.data(), sizeof(float) * need, hipMemcpyHostToDevice));
+        s->tp_w = d.width; s->tp_h = d.height; s->tp_aspect = d.aspect;
+    }
+    RT_HIP(s->tp_done.order(stream));
+    hipEvent_t ev[2];
+    s->tp_timed = 0;
+    if (s->tp_timing) {
+        for (int i = 0; i < 2; ++i) {
+            RT_HIP(s->tp_ev[i].create(hipEventDefault));
+            ev[i] = s->tp_ev[i].get();
+        }
+    }
+    const int rc = rt_temporal_launch(&d, need_rays ? s->tp_raygen.get() : nullptr, need_rays ? s->tp_raygen.get() + d.width : nullptr,
+                                      view, prev_view, same_view, s->tp_timing ? ev : nullptr, stream);
+    RT_HIP(s->tp_done.record(stream));
+    if (rc == RT_OK && s->tp_timing) s->tp_timed = 2;
+    return rc;
+}
+
+extern "C" int rt_scene_set_temporal_timing(rt_scene *s, int on)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_temporal_timing: null scene");
+        return RT_ERR_INVALID;
+    }
+    s->tp_timing = on != 0;
+    return RT_OK;
+}
+
+extern "C" int rt_scene_temporal_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    if (!s || !ms || !n || cap < 0) {
+        rt_set_error("rt_scene_temporal_times: null argument");
+        return RT_ERR_INVALID;
+    }
+    *n = 0;
+    if (s->tp_timed < 2 || cap < 1) return RT_OK;
+    RT_HIP(s->tp_done.host_wait());
+    RT_HIP(hipEventElapsedTime(&ms[0], s->tp_ev[0].get(), s->tp_ev[1].get()));
+    *n = 1;
     return RT_OK;
 }

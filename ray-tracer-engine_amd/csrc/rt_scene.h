@@ -19,7 +19,7 @@
 //       build has finished;
 //   (c) a reader waits on the build event on the device only; the host never waits for a build, except in
 //       rt_scene_view_lists_info;
-//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's event;
+//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's and the temporal pass's events;
 //   (e) the tile order keeps one event for all layouts; a new layout or a re-sort first makes the launching stream
 //       wait for every ring event;
 //   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
@@ -169,6 +169,15 @@ struct rt_scene {
     HipEvent dn_ev[RT_DENOISE_MAX_ITERATIONS + 2];   // rt_scene_set_denoise_timing
     bool dn_timing = false;
     int dn_timed = 0;                                // events the last timed call recorded
+    // temporal accumulation (rt_temporal.hip): the ray tables of the view its last call reprojected from (its own, so
+    // that a call of another size does not rebuild the frames' d_raygen); `tp_done` orders the scene's temporal calls
+    DevArray<float> tp_raygen;                       // dx[width], dy[height] at one sample
+    int tp_w = 0, tp_h = 0;
+    float tp_aspect = 0.f;
+    HipPendingEvent tp_done;
+    HipEvent tp_ev[2];                               // rt_scene_set_temporal_timing
+    bool tp_timing = false;
+    int tp_timed = 0;
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
 #endif
@@ -190,6 +199,7 @@ int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelCh
                           hipStream_t stream, int *view_out);
 int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, hipStream_t stream);
 int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float aspect, int total);
+void rt_raygen_fill(int width, int height, float aspect, int total, float *h);   // the tables' values (host)
 void rt_build_frame_aux(const rt_scene *s, RtFrameAux *ax);
 int rt_scene_sync_aux(rt_scene *s);
 void rt_view_params_from_consts(const RtFrameConsts &fc, float aspect, RtViewParams *p);

@@ -165,6 +165,27 @@ static int rt_scene_prepare_occluders(rt_scene *s, hipStream_t stream)
     return RT_OK;
 }
 
+// dx / dy of the primary rays per column / row and sample (kernel.cu:1624-1625): h[total * width] then h[total * height]
+void rt_raygen_fill(int width, int height, float aspect, int total, float *h)
+{
+    const double aspect_d = (double)aspect;
+    const double width_d = (double)(float)width, height_d = (double)(float)height;
+    const double hw_d = (double)((float)height / (float)width);
+    for (int k = 0; k < total; ++k) {
+        double ox, oy;
+        rt_sample_offset(k, total, &ox, &oy);
+        float *dx = h + (size_t)k * width, *dy = h + (size_t)total * width + (size_t)k * height;
+        for (int x = 0; x < width; ++x) {
+            const double tx_d = (2.0 * ((double)x + ox)) / width_d;
+            dx[x] = (float)(aspect_d * tx_d - 1.0);
+        }
+        for (int y = 0; y < height; ++y) {
+            const double ty_d = (2.0 * ((double)y + oy)) / height_d;
+            dy[y] = (float)((aspect_d * ty_d) * hw_d - 1.0);
+        }
+    }
+}
+
 // dx and dy of kernel.cu:1624-1625 for every column, row and sample of a frame:
 //   dx = aspect*(2*(x+0.5)/(float)width) - 1,  dy = aspect*(2*(y+0.5)/(float)height)*((float)height/width) - 1
 // binary64 expressions (the literal 0.5) narrowed to float on assignment. They depend on the
@@ -180,22 +201,7 @@ int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float aspect, in
     const size_t need = (size_t)total * ((size_t)width + (size_t)height);
     RT_HIP(s->d_raygen.reserve(need));
     std::vector<float> h(need);
-    const double aspect_d = (double)aspect;
-    const double width_d = (double)(float)width, height_d = (double)(float)height;
-    const double hw_d = (double)((float)height / (float)width);
-    for (int k = 0; k < total; ++k) {
-        double ox, oy;
-        rt_sample_offset(k, total, &ox, &oy);
-        float *dx = h.data() + (size_t)k * width, *dy = h.data() + (size_t)total * width + (size_t)k * height;
-        for (int x = 0; x < width; ++x) {
-            const double tx_d = (2.0 * ((double)x + ox)) / width_d;
-            dx[x] = (float)(aspect_d * tx_d - 1.0);
-        }
-        for (int y = 0; y < height; ++y) {
-            const double ty_d = (2.0 * ((double)y + oy)) / height_d;
-            dy[y] = (float)((aspect_d * ty_d) * hw_d - 1.0);
-        }
-    }
+    rt_raygen_fill(width, height, aspect, total, h.data());
     RT_HIP(hipMemcpy(s->d_raygen.get(), h.data(), sizeof(float) * need, hipMemcpyHostToDevice));
     s->rg_w = width;
     s->rg_h = height;
