@@ -800,6 +800,15 @@ double rt_debug_sphere_beam_slope(const double lpos[3], const double centre[3], 
 double rt_debug_beam_sine(const double lpos[3], const double start[3], double *sigma, double *frob, double m9[9]);
 /* ... and as the DEVICE builds them (what a scene uses: one wave per sphere, members in list order); needs a GPU */
 int rt_debug_occluder_lists_device(const rt_sphere *spheres, int n, const rt_light *light, int *counts, float *kcaps, int *members, int cap);
+/* The tile order of rt_scene_set_tile_order as the DEVICE sorts it, for a grid of tiles_x x tiles_y tiles and their
+ * durations cost[tiles_x * tiles_y] (row-major; needs a GPU; tests only). Blocks of 16 x 16 tiles, nbx = ceil(tiles_x / 16)
+ * per row of blocks: key[nb] = the longest tile of every block, start[nb] = where each block's tiles start in the order,
+ * perm[tiles_x * tiles_y] = the order, (tile_y << 16) | tile_x. One launch of the three kernels on a stream of the
+ * call's own, which it waits for. via_configs != 0: the kernels are launched from the functions and geometries a frame
+ * graph makes its kernel nodes from. A grid the library keeps in grid order (a coordinate above 0xffff, more than 4096
+ * blocks): RT_ERR_UNSUPPORTED, nothing is launched or written.                                                      */
+int rt_debug_tile_order(const unsigned *cost, int tiles_x, int tiles_y, int via_configs, unsigned *key, unsigned *start,
+                        unsigned *perm);
 /* The sphere BVH of the reflective frames, built on the host (no GPU needed; tests only). Node j:
  * lohi[6j..6j+5] = its box (lo xyz, hi xyz: binary32, rounded outward from the binary64 extents of
  * its spheres), meta[2j] = first child (the second is meta[2j] + 1) or, for a leaf, the first

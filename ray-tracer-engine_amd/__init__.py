@@ -279,6 +279,7 @@ def load_library():
         "rt_scene_set_view_lists": (ci, [vp, ci]),
         "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
         "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
+        "rt_debug_tile_order": (ci, [C.POINTER(C.c_uint), ci, ci, ci, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
         "rt_scene_render": (ci, [vp, C.POINTER(FrameDesc), vp]),
         "rt_graph_capture": (vp, [vp, C.POINTER(FrameDesc), ci, vp, vp]),
         "rt_graph_launch": (ci, [vp, vp]),
@@ -481,6 +482,20 @@ def view_lists_host(spheres, n, fd, want_lists=True, want_beams=False) -> dict:
     if want_beams:
         d["beams"] = beams
     return d
+
+
+def debug_tile_order(cost, tiles_x, tiles_y, via_configs=False):
+    """rt_debug_tile_order as is: (status, key uint32 [nb], start uint32 [nb], perm uint32 [tiles_x * tiles_y]) as the
+    device sorts the tile durations cost (uint32, row-major); the arrays hold 0xffffffff where nothing was written."""
+    cost = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+    n = max(tiles_x, 0) * max(tiles_y, 0)
+    if cost.size != n:
+        raise RtError(f"debug_tile_order: {cost.size} durations for {tiles_x} x {tiles_y} tiles")
+    nb = -(-max(tiles_x, 0) // 16) * -(-max(tiles_y, 0) // 16)
+    key, start, perm = (np.full(k, 0xffffffff, dtype=np.uint32) for k in (nb, nb, n))
+    up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint))
+    rc = load_library().rt_debug_tile_order(up(cost), tiles_x, tiles_y, 1 if via_configs else 0, up(key), up(start), up(perm))
+    return rc, key, start, perm
 
 
 class Scene:

@@ -1,5 +1,7 @@
 // rt_debug.cpp -- diagnostics for the tests (rt_debug_*): device evaluation of scalar building blocks and the host
 // restatements of the table builders, host arrays in and out.
+#include <limits.h>
+
 #include "rt_scene.h"
 
 // launchers defined in rt_kernels.hip
@@ -223,6 +225,66 @@ extern "C" int rt_debug_light_prepass(const rt_vec3 *start, const rt_light *ligh
     std::vector<rt_vec3> normal((size_t)n, rt_vec3{0.f, 1.f, 0.f});
     std::vector<float> bright((size_t)n);
     return debug_light_impl(nullptr, 0, start, normal.data(), light, n, dirs, bright.data(), approx_dirs, approx_ok);
+}
+
+// The tile order of a grid of tiles_x x tiles_y tiles as the DEVICE sorts it from cost[] (rt_tile_order_launch: what a
+// scene's launches use), downloaded: key[nb], start[nb], perm[n]. via_configs != 0: the same three kernels launched from
+// the functions and geometries of rt_tile_order_kernel_configs, as a frame graph's kernel nodes are. A grid that
+// rt_tile_grid does not accept: RT_ERR_UNSUPPORTED, nothing launched.
+extern "C" int rt_debug_tile_order(const unsigned *cost, int tiles_x, int tiles_y, int via_configs, unsigned *key, unsigned *start,
+                                   unsigned *perm)
+{
+    // The argument and grid checks come before the first HIP call: a refusal needs no device, and
+    // tests/test_tile_order_cpu.py relies on that on machines without one.
+    if (!cost || !key || !start || !perm || tiles_x <= 0 || tiles_y <= 0) {
+        rt_set_error("rt_debug_tile_order: bad argument");
+        return RT_ERR_INVALID;
+    }
+    const int tile_w = 8, tile_h = 64 / tile_w;
+    if (tiles_x > INT_MAX / tile_w || tiles_y > INT_MAX / tile_h) {
+        rt_set_error("rt_debug_tile_order: %d x %d tiles cannot be ordered", tiles_x, tiles_y);
+        return RT_ERR_UNSUPPORTED;
+    }
+    const RtTileGrid g = rt_tile_grid(tile_w, tile_w * tiles_x, tile_h * tiles_y);
+    if (!g.ok || g.tiles_x != tiles_x || g.tiles_y != tiles_y) {
+        rt_set_error("rt_debug_tile_order: %d x %d tiles cannot be ordered", tiles_x, tiles_y);
+        return RT_ERR_UNSUPPORTED;
+    }
+    RtTileOrderBuf buf;
+    HipStream stream;
+    RT_HIP(buf.reserve(g));
+    RT_HIP(stream.create(hipStreamNonBlocking));
+    // everything on `stream`, a non-blocking one: the null stream's work is not ordered against it
+    RT_HIP(hipMemcpyAsync(buf.cost(), cost, sizeof(unsigned) * (size_t)g.n, hipMemcpyHostToDevice, stream.get()));
+    // known contents where the kernels must write: an entry of perm[] they leave out is no tile
+    RT_HIP(hipMemsetAsync(buf.perm(), 0xff, sizeof(unsigned) * (size_t)g.n, stream.get()));
+    RT_HIP(hipMemsetAsync(buf.key(), 0xa5, sizeof(unsigned) * (size_t)g.nb, stream.get()));
+    RT_HIP(hipMemsetAsync(buf.start(), 0, sizeof(unsigned) * (size_t)g.nb, stream.get()));     // in range: the third kernel indexes perm[] by it
+    if (!via_configs) {
+        RT_HIP(rt_tile_order_launch(buf.cost(), buf.key(), buf.start(), buf.perm(), g.tiles_x, g.tiles_y, stream.get()));
+    } else {
+        // What this path tests is the functions, grids and blocks of rt_tile_order_kernel_configs. The argument lists
+        // below are this function's own, written from the comment at rt_tile_order_kernel_configs; the lists
+        // rt_graph.cpp builds for its kernel nodes are not exercised here (graph replays are: test_gpu_parity.py).
+        const void *func[3];
+        dim3 grid[3], block[3];
+        rt_tile_order_kernel_configs(g.tiles_x, g.tiles_y, func, grid, block);
+        const unsigned *d_cost = buf.cost();
+        unsigned *d_key = buf.key(), *d_start = buf.start(), *d_perm = buf.perm();
+        const unsigned *d_key_in = d_key, *d_start_in = d_start;
+        int tx = g.tiles_x, ty = g.tiles_y, nbx = g.nbx, nby = g.nby, n = g.n;
+        void *keys_args[] = {&d_cost, &d_key, &nbx, &tx, &ty};
+        void *sort_args[] = {&d_key_in, &d_start, &nbx, &nby, &tx, &ty};
+        void *expand_args[] = {&d_start_in, &d_perm, &n, &tx, &nbx};
+        RT_HIP(hipLaunchKernel(func[0], grid[0], block[0], keys_args, 0, stream.get()));
+        RT_HIP(hipLaunchKernel(func[1], grid[1], block[1], sort_args, 0, stream.get()));
+        RT_HIP(hipLaunchKernel(func[2], grid[2], block[2], expand_args, 0, stream.get()));
+    }
+    RT_HIP(hipStreamSynchronize(stream.get()));
+    RT_HIP(hipMemcpy(key, buf.key(), sizeof(unsigned) * (size_t)g.nb, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(start, buf.start(), sizeof(unsigned) * (size_t)g.nb, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(perm, buf.perm(), sizeof(unsigned) * (size_t)g.n, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 // The host builder for a sphere list and a frame description, no device involved (tests): the summary, and into `slots`
