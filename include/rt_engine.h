@@ -645,6 +645,65 @@ int rt_view_terms(int width, int height, float aspect, const rt_camera *cam, flo
 int rt_scene_set_temporal_timing(rt_scene *s, int on);
 int rt_scene_temporal_times(rt_scene *s, float *ms, int cap, int *n);
 
+/* ------------------------------------------------------------------ *
+ * Variance-guided denoiser: rt_scene_denoise's filter   *
+ * with a luminance threshold per pixel, scaled by the variance that    *
+ * rt_scene_temporal's moments (or the neighbourhood) show there.       *
+ * ------------------------------------------------------------------ */
+typedef struct rt_vdenoise_desc {
+    uint32_t struct_size;    /* sizeof(rt_vdenoise_desc); 0 reads as this layout. Fields past a caller's size read as 0 */
+    int width, height;       /* as rt_denoise_desc, field for field, down to `pixels`                                   */
+    const float *rgba_in;    /* device, float4, 16-byte aligned: the colour to filter; with `moments`, w is the history
+                                length n that rt_scene_temporal wrote beside them                                       */
+    const float *depth;
+    const float *normal;
+    const float *albedo;     /*   may be NULL only with demodulate = 0                                                  */
+    const int *id;
+    float *rgba_out;         /* device, float4, 16-byte aligned: (filtered colour, 1); may equal rgba_in                */
+    uint32_t *pixels;        /* NULL, or device: the packed framebuffer of the result                                   */
+    const float *moments;    /* NULL, or device, float2, 8-byte aligned: a moments_out of rt_scene_temporal     [NULL]  */
+    float *variance_out;     /* NULL, or device, float, 4-byte aligned: the variance after the last iteration, in the
+                                filter's domain (of the demodulated luminance when demodulating); 0 for sky     [NULL]  */
+    int iterations;          /* 1 .. RT_DENOISE_MAX_ITERATIONS                                                  [4]     */
+    int normal_shift;        /* 0 .. RT_DENOISE_MAX_NORMAL_SHIFT                                                [5]     */
+    float sigma_depth;       /* finite, > 0                                                                     [0.05]  */
+    float sigma_colour;      /* finite, 0 .. 2^20: the luminance threshold in standard deviations               [4]     */
+    float sigma_floor;       /* finite, > 0: the luminance threshold where the variance is 0                    [2^-6]  */
+    int min_history;         /* 1 .. RT_TEMPORAL_MAX_HISTORY: a pixel whose n is below it (or every pixel, without
+                                `moments`) takes its variance from its 7 x 7 neighbourhood                      [4]     */
+    float spatial_boost;     /* finite, >= 0: factor on that spatial estimate                                   [4]     */
+    int demodulate;          /* as rt_denoise_desc                                                              [1]     */
+    int variant;             /* 0: the product kernels; 1: the plain one-thread-per-pixel yardstick; 2: the product
+                                kernels with the direct kernel instead of the LDS-staged one at step 16 (measurement:
+                                DESIGN.md 6j). The same bits in all three                                               */
+} rt_vdenoise_desc;
+
+/* The defaults in brackets above (the interface's own choices -- those of the SVGF filter this stage restates -- not
+ * measurements); sizes and pointers 0. */
+void rt_vdenoise_desc_init(rt_vdenoise_desc *d);
+
+/* rt_scene_denoise with a per-pixel colour weight: e_c = S / (S + g g), S(p) = sigma_colour^2 * (the 3 x 3 mean of the
+ * variance around p) + sigma_floor^2. The variance of a pixel starts as max(m2 - m1 m1, 0) of `moments` (divided by
+ * the squared luminance of the albedo when demodulating) where rgba_in.w >= min_history, elsewhere as spatial_boost
+ * times the variance of the luminance over the agreeing pixels of its 7 x 7 neighbourhood; every iteration carries it
+ * along as sum(w w v) / (sum w)^2. Where the history has converged the threshold is sigma_floor and edges the history
+ * resolved stay; where it is short the threshold opens and the noise is filtered. DESIGN.md 6j gives every formula;
+ * binary32, + - * / and compares only: defined to the bit, all variants return the same bits, and with a variance of 0
+ * (or sigma_colour = 0) the result is rt_scene_denoise's with sigma_colour = sigma_floor.
+ * Host behaviour is rt_scene_denoise's: the call enqueues and returns; the scratch is the scene's denoise scratch and
+ * two variance arrays (60 bytes per pixel), so calls of this entry point and of rt_scene_denoise on one scene, on
+ * whatever streams, are ordered on the device by one event. rgba_out may be rgba_in itself; no other output may overlap
+ * an input or another output. Before anything is enqueued, and with nothing written: what rt_scene_denoise refuses,
+ * misaligned moments or variance_out, sigma_colour, sigma_floor, min_history or spatial_boost out of range or not
+ * finite, an overlap -> RT_ERR_INVALID; a stream that is being captured -> RT_ERR_UNSUPPORTED. */
+int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d, void *stream);
+
+/* Device time of every launch of the scene's later variance-guided calls (off by default). rt_scene_vdenoise_times
+ * waits for the last call and fills ms[0 .. *n - 1]: variants 0 and 2: [0] the pack pass, [1] the spatial-estimate
+ * pass, [2 + i] iteration i; variant 1: [0] the initial variance, [1 + i] iteration i. cap: room in ms. */
+int rt_scene_set_vdenoise_timing(rt_scene *s, int on);
+int rt_scene_vdenoise_times(rt_scene *s, float *ms, int cap, int *n);
+
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
  * tile first -- the frame kernel records every tile's wave duration, and from the previous launch's durations the
  * blocks are sorted on the device (three small kernels, ~15 us): after 1, 2, 4, 8, 16, 32, 64, 96, ... launches of an

@@ -185,6 +185,17 @@ class DenoiseDesc(C.Structure):
                 ("sigma_colour", C.c_float), ("demodulate", C.c_int), ("variant", C.c_int)]
 
 
+class VDenoiseDesc(C.Structure):
+    """rt_vdenoise_desc."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
+                ("rgba_in", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p),
+                ("id", C.c_void_p), ("rgba_out", C.c_void_p), ("pixels", C.c_void_p),
+                ("moments", C.c_void_p), ("variance_out", C.c_void_p),
+                ("iterations", C.c_int), ("normal_shift", C.c_int), ("sigma_depth", C.c_float),
+                ("sigma_colour", C.c_float), ("sigma_floor", C.c_float), ("min_history", C.c_int),
+                ("spatial_boost", C.c_float), ("demodulate", C.c_int), ("variant", C.c_int)]
+
+
 class TemporalDesc(C.Structure):
     """rt_temporal_desc."""
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
@@ -335,6 +346,10 @@ def load_library():
         "rt_scene_denoise": (ci, [vp, C.POINTER(DenoiseDesc), vp]),
         "rt_scene_set_denoise_timing": (ci, [vp, ci]),
         "rt_scene_denoise_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
+        "rt_vdenoise_desc_init": (None, [C.POINTER(VDenoiseDesc)]),
+        "rt_scene_denoise_variance": (ci, [vp, C.POINTER(VDenoiseDesc), vp]),
+        "rt_scene_set_vdenoise_timing": (ci, [vp, ci]),
+        "rt_scene_vdenoise_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_debug_copy16": (ci, [vp, vp, C.c_size_t, vp]),
         "rt_temporal_desc_init": (None, [C.POINTER(TemporalDesc)]),
         "rt_scene_temporal": (ci, [vp, C.POINTER(TemporalDesc), vp]),
@@ -874,6 +889,81 @@ class Scene:
                               demodulate=demodulate, variant=variant)
         _check(self.denoise_raw(d, st.cuda_stream), "rt_scene_denoise")
         return {"rgba": out, "packed": packed}
+
+    # ---------------------------------------------------------------- the variance-guided denoiser
+    def vdenoise_desc(self, width, height, *, rgba_in=0, depth=0, normal=0, albedo=0, id=0, rgba_out=0, pixels=0,
+                      moments=0, variance_out=0, iterations=None, normal_shift=None, sigma_depth=None, sigma_colour=None,
+                      sigma_floor=None, min_history=None, spatial_boost=None, demodulate=None, variant=0) -> VDenoiseDesc:
+        """rt_vdenoise_desc with rt_vdenoise_desc_init's defaults where an argument is None."""
+        d = VDenoiseDesc()
+        self.lib.rt_vdenoise_desc_init(C.byref(d))
+        d.width, d.height = width, height
+        d.rgba_in, d.depth, d.normal, d.albedo, d.id = rgba_in, depth, normal, albedo, id
+        d.rgba_out, d.pixels, d.moments, d.variance_out = rgba_out, pixels, moments, variance_out
+        for k, v in (("iterations", iterations), ("normal_shift", normal_shift), ("sigma_depth", sigma_depth),
+                     ("sigma_colour", sigma_colour), ("sigma_floor", sigma_floor), ("min_history", min_history),
+                     ("spatial_boost", spatial_boost), ("variant", variant)):
+            if v is not None:
+                setattr(d, k, v)
+        if demodulate is not None:
+            d.demodulate = 1 if demodulate else 0
+        return d
+
+    def denoise_variance_raw(self, d: VDenoiseDesc, stream=0) -> int:
+        """rt_scene_denoise_variance as is: returns the status."""
+        return self.lib.rt_scene_denoise_variance(self.handle, C.byref(d), stream)
+
+    def denoise_variance(self, frame, history=None, *, iterations=None, normal_shift=None, sigma_depth=None,
+                         sigma_colour=None, sigma_floor=None, min_history=None, spatial_boost=None, demodulate=None,
+                         want_packed=True, want_variance=True, variant=0, stream=None):
+        """Filter with the variance-guided a-trous filter of rt_scene_denoise_variance. The guides and the albedo are
+        those of `frame` (render(..., aov=("depth", "normal", "id", "albedo"))). With `history` (what Scene.temporal
+        returned for that frame) the colour, its history length and the luminance moments come from it; without, the
+        colour is the frame's own and every pixel's variance is the spatial estimate. None: the default of
+        rt_vdenoise_desc_init. Returns {'rgba': float32 [rows, W, 4], 'packed': int32 [rows, W] or None, 'variance':
+        float32 [rows, W] or None} as new tensors; neither the frame's nor the history's tensors are written.
+        Enqueued on `stream` (default: the current stream); no host wait."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError("no GPU visible: the denoiser has no CPU fallback")
+        aov = frame.get("aov") or {}
+        rgba = frame.get("rgba") if history is None else history.get("rgba")
+        moments = None if history is None else history.get("moments")
+        need = ("depth", "normal", "id") + (() if demodulate is not None and not demodulate else ("albedo",))
+        if rgba is None or any(k not in aov for k in need):
+            raise RtError(f"denoise_variance needs a colour (the frame's rgba or the history's) and the G-buffer outputs "
+                          f"{need}: render with want_rgba=True and aov={AOV_NAMES}")
+        if history is not None and moments is None:
+            raise RtError("denoise_variance: the history carries no moments (Scene.temporal(..., want_moments=True))")
+        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
+        if tuple(rgba.shape) != (rows, width, 4):
+            raise RtError("denoise_variance: the colour is not of the guides' shape [rows, W, 4]")
+        out = torch.empty_like(rgba)
+        packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
+        variance = torch.empty((rows, width), dtype=torch.float32, device=rgba.device) if want_variance else None
+        st = torch.cuda.current_stream() if stream is None else stream
+        d = self.vdenoise_desc(width, rows, rgba_in=rgba.data_ptr(), depth=aov["depth"].data_ptr(),
+                               normal=aov["normal"].data_ptr(), albedo=aov["albedo"].data_ptr() if "albedo" in aov else 0,
+                               id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
+                               pixels=packed.data_ptr() if want_packed else 0,
+                               moments=moments.data_ptr() if moments is not None else 0,
+                               variance_out=variance.data_ptr() if want_variance else 0, iterations=iterations,
+                               normal_shift=normal_shift, sigma_depth=sigma_depth, sigma_colour=sigma_colour,
+                               sigma_floor=sigma_floor, min_history=min_history, spatial_boost=spatial_boost,
+                               demodulate=demodulate, variant=variant)
+        _check(self.denoise_variance_raw(d, st.cuda_stream), "rt_scene_denoise_variance")
+        return {"rgba": out, "packed": packed, "variance": variance}
+
+    def set_vdenoise_timing(self, on: bool):
+        _check(self.lib.rt_scene_set_vdenoise_timing(self.handle, 1 if on else 0), "rt_scene_set_vdenoise_timing")
+
+    def vdenoise_times(self):
+        """Device ms of every launch of the last timed variance-guided call (waits for it): variants 0 and 2: the pack
+        pass, the spatial-estimate pass, then the iterations; variant 1: the initial variance, then the iterations."""
+        ms = (C.c_float * (RT_DENOISE_MAX_ITERATIONS + 2))()
+        n = C.c_int()
+        _check(self.lib.rt_scene_vdenoise_times(self.handle, ms, len(ms), C.byref(n)), "rt_scene_vdenoise_times")
+        return list(ms)[: n.value]
 
     # ---------------------------------------------------------------- temporal accumulation (DESIGN.md 6i)
     def temporal_desc(self, width, height, *, cam=None, aspect=None, prev_cam=None, prev_aspect=None, rgba_in=0, depth=0,

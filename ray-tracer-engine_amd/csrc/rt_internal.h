@@ -232,6 +232,11 @@ void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out);
 int rt_denoise_launch(const rt_denoise_desc *d, float4 *col0, float4 *col1, float4 *guide, int *key, hipEvent_t *ev,
                       hipStream_t stream);
 
+// rt_vdenoise.hip: the variance-guided denoiser (d: validated, in this build's layout; the scene's scratch, room for
+// width * height pixels each; lds16: step 16 runs the LDS-staged kernel; ev: null, or iterations + 3 timing events)
+int rt_vdenoise_launch(const rt_vdenoise_desc *d, float4 *col0, float4 *col1, float4 *guide, int *key, float *var0,
+                       float *var1, bool lds16, hipEvent_t *ev, hipStream_t stream);
+
 // rt_temporal.hip: temporal accumulation (d: validated, in this build's layout; dx_tab / dy_tab: the current view's ray
 // tables at one sample; view[7] / prev_view[7]: rt_view_terms of the two views; same_view: they are the same bytes;
 // ev: null, or two timing events)

@@ -631,6 +631,140 @@ extern "C" int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n)
 }
 
 // ---------------------------------------------------------------------------
+// the variance-guided denoiser (rt_vdenoise.hip)
+// ---------------------------------------------------------------------------
+// Which kernel runs step 16 in variant 0 (variant 2 runs the other): the LDS-staged one (61 440 B), by the measurement
+// of DESIGN.md 6j -- equal to the direct one at 3840 x 2160 (0.425 against 0.423 ms), 1.32 times faster at 960 x 540.
+static const bool kVdenoiseLds16 = true;
+
+extern "C" void rt_vdenoise_desc_init(rt_vdenoise_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->iterations = 4;
+    d->normal_shift = 5;
+    d->sigma_depth = 0.05f;
+    d->sigma_colour = 4.f;
+    d->sigma_floor = 0.015625f;
+    d->min_history = 4;
+    d->spatial_boost = 4.f;
+    d->demodulate = 1;
+}
+
+extern "C" int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_denoise_variance: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_vdenoise_desc d;
+    as_built(d_in, &d);
+    struct Range {
+        uintptr_t p;
+        size_t bytes;
+    };
+    const char *bad = nullptr;
+    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
+        bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
+    else if (!d.rgba_in || !d.depth || !d.normal || !d.id || !d.rgba_out) bad = "rgba_in, depth, normal, id and rgba_out must not be NULL";
+    else if (d.demodulate && !d.albedo) bad = "demodulate needs albedo";
+    else if ((((uintptr_t)d.rgba_in | (uintptr_t)d.normal | (uintptr_t)d.albedo | (uintptr_t)d.rgba_out) & 15u) ||
+             (((uintptr_t)d.id | (uintptr_t)d.moments) & 7u) ||
+             (((uintptr_t)d.depth | (uintptr_t)d.pixels | (uintptr_t)d.variance_out) & 3u))
+        bad = "rgba_in, normal, albedo and rgba_out must be 16-byte aligned, id and moments 8-byte, depth, pixels and variance_out 4-byte";
+    else if (d.iterations < 1 || d.iterations > RT_DENOISE_MAX_ITERATIONS) bad = "iterations is not in [1, RT_DENOISE_MAX_ITERATIONS]";
+    else if (d.normal_shift < 0 || d.normal_shift > RT_DENOISE_MAX_NORMAL_SHIFT) bad = "normal_shift is not in [0, RT_DENOISE_MAX_NORMAL_SHIFT]";
+    else if (!(d.sigma_depth > 0.f) || !std::isfinite(d.sigma_depth)) bad = "sigma_depth is not finite and > 0";
+    else if (!(d.sigma_colour >= 0.f && d.sigma_colour <= 1048576.f)) bad = "sigma_colour is not in [0, 2^20]";
+    else if (!(d.sigma_floor > 0.f) || !std::isfinite(d.sigma_floor)) bad = "sigma_floor is not finite and > 0";
+    else if (d.min_history < 1 || d.min_history > RT_TEMPORAL_MAX_HISTORY) bad = "min_history is not in [1, RT_TEMPORAL_MAX_HISTORY]";
+    else if (!(d.spatial_boost >= 0.f) || !std::isfinite(d.spatial_boost)) bad = "spatial_boost is not finite and >= 0";
+    else if (d.variant < 0 || d.variant > 2) bad = "variant is not 0, 1 or 2";
+    else {
+        const size_t npx = (size_t)d.width * d.height;
+        const Range outs[3] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.pixels, npx * 4}, {(uintptr_t)d.variance_out, npx * 4}};
+        const Range ins[6] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16},
+                              {(uintptr_t)d.albedo, npx * 16}, {(uintptr_t)d.id, npx * 8}, {(uintptr_t)d.moments, npx * 8}};
+        auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
+        for (int i = 0; i < 3 && !bad; ++i) {
+            for (int k = 0; k < 6; ++k)
+                if (overlap(outs[i], ins[k]) && !(i == 0 && k == 0 && d.rgba_out == d.rgba_in))
+                    bad = "an output buffer overlaps an input (only rgba_out may be rgba_in itself)";
+            for (int j = i + 1; j < 3; ++j)
+                if (overlap(outs[i], outs[j])) bad = "two output buffers overlap";
+        }
+    }
+    if (bad) {
+        rt_set_error("rt_scene_denoise_variance: %s (%d x %d, iterations %d, normal_shift %d, min_history %d, variant %d)", bad,
+                     d.width, d.height, d.iterations, d.normal_shift, d.min_history, d.variant);
+        return RT_ERR_INVALID;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_denoise_variance: the stream is being captured (the denoiser is not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    const size_t npx = (size_t)d.width * d.height;
+    if (npx > s->dn_col[0].capacity() || npx > s->dn_col[1].capacity() || npx > s->vd_var[0].capacity() ||
+        npx > s->vd_var[1].capacity() || (d.variant != 1 && (npx > s->dn_guide.capacity() || npx > s->dn_key.capacity()))) {
+        // growing releases the old buffers: after the host has seen the last call that used them end
+        RT_HIP(s->dn_done.host_wait());
+        RT_HIP(s->dn_col[0].reserve(npx));
+        RT_HIP(s->dn_col[1].reserve(npx));
+        RT_HIP(s->vd_var[0].reserve(npx));
+        RT_HIP(s->vd_var[1].reserve(npx));
+        if (d.variant != 1) {
+            RT_HIP(s->dn_guide.reserve(npx));
+            RT_HIP(s->dn_key.reserve(npx));
+        }
+    }
+    RT_HIP(s->dn_done.order(stream));   // one scratch, shared with rt_scene_denoise: one call at a time
+    constexpr int kEvents = RT_DENOISE_MAX_ITERATIONS + 3;
+    hipEvent_t ev[kEvents];
+    s->vd_timed = 0;
+    if (s->vd_timing) {
+        for (int i = 0; i < kEvents; ++i) {
+            RT_HIP(s->vd_ev[i].create(hipEventDefault));
+            ev[i] = s->vd_ev[i].get();
+        }
+    }
+    const bool lds16 = (d.variant == 2) != kVdenoiseLds16;
+    const int rc = rt_vdenoise_launch(&d, s->dn_col[0].get(), s->dn_col[1].get(), s->dn_guide.get(), s->dn_key.get(),
+                                      s->vd_var[0].get(), s->vd_var[1].get(), lds16, s->vd_timing ? ev : nullptr, stream);
+    // also after a launch that failed half way: what was enqueued uses the scratch
+    RT_HIP(s->dn_done.record(stream));
+    if (rc == RT_OK && s->vd_timing) s->vd_timed = d.iterations + (d.variant == 1 ? 2 : 3);
+    return rc;
+}
+
+extern "C" int rt_scene_set_vdenoise_timing(rt_scene *s, int on)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_vdenoise_timing: null scene");
+        return RT_ERR_INVALID;
+    }
+    s->vd_timing = on != 0;
+    return RT_OK;
+}
+
+extern "C" int rt_scene_vdenoise_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    if (!s || !ms || !n || cap < 0) {
+        rt_set_error("rt_scene_vdenoise_times: null argument");
+        return RT_ERR_INVALID;
+    }
+    *n = 0;
+    if (s->vd_timed < 2) return RT_OK;
+    RT_HIP(s->dn_done.host_wait());
+    for (int i = 0; i + 1 < s->vd_timed && i < cap; ++i) {
+        RT_HIP(hipEventElapsedTime(&ms[i], s->vd_ev[i].get(), s->vd_ev[i + 1].get()));
+        *n = i + 1;
+    }
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
 // temporal accumulation (rt_temporal.hip)
 // ---------------------------------------------------------------------------
 extern "C" void rt_temporal_desc_init(rt_temporal_desc *d)

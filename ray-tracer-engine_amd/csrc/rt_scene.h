@@ -169,6 +169,11 @@ struct rt_scene {
     HipEvent dn_ev[RT_DENOISE_MAX_ITERATIONS + 2];   // rt_scene_set_denoise_timing
     bool dn_timing = false;
     int dn_timed = 0;                                // events the last timed call recorded
+    // the variance-guided denoiser (rt_vdenoise.hip) uses the scratch above and `dn_done`, plus two variance arrays
+    DevArray<float> vd_var[2];
+    HipEvent vd_ev[RT_DENOISE_MAX_ITERATIONS + 3];   // rt_scene_set_vdenoise_timing
+    bool vd_timing = false;
+    int vd_timed = 0;
     // temporal accumulation (rt_temporal.hip): the ray tables of the view its last call reprojected from (its own, so
     // that a call of another size does not rebuild the frames' d_raygen); `tp_done` orders the scene's temporal calls
     DevArray<float> tp_raygen;                       // dx[width], dy[height] at one sample
