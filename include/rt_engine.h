@@ -625,7 +625,8 @@ void rt_temporal_desc_init(rt_temporal_desc *d);
  * weight 1: a standing camera gives the exact running mean. DESIGN.md 6i gives every formula; binary32, + - * / and
  * compares only, so the result is defined to the bit and both variants return the same bits.
  * The scene is assumed static between the two frames: there are no motion vectors, a moved object is rejected by
- * its depth or only by chance. A caller that moves objects or lights passes `reset`.
+ * its depth or only by chance. A caller that moves objects or lights passes `reset`, or calls
+ * rt_scene_temporal_motion below, which takes a displacement per sphere and cube and clamps the history.
  * The call enqueues one kernel and returns; there is no host wait (the first call of a size or aspect uploads that
  * view's ray tables). The pass gathers: no output may overlap an input. Calls of one scene on different streams are
  * ordered on the device, one after the other (an event); ordering the call after the frames that wrote its inputs is
@@ -635,6 +636,66 @@ void rt_temporal_desc_init(rt_temporal_desc *d);
  * without `reset`, moments_out without prev_moments unless `reset`, an output that overlaps an input or another
  * output -> RT_ERR_INVALID; a stream that is being captured -> RT_ERR_UNSUPPORTED. */
 int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d, void *stream);
+
+/* Temporal accumulation over moving spheres and cubes, with a history clamp. Every field of
+ * rt_temporal_desc, in the same order and with the same meaning, then the motion and the clamp. */
+typedef struct rt_tmotion_desc {
+    uint32_t struct_size;        /* sizeof(rt_tmotion_desc); 0 reads as this layout. Fields past a caller's size read as 0 */
+    int width, height;
+    float aspect;
+    rt_camera cam;
+    float prev_aspect;
+    rt_camera prev_cam;
+    const float *rgba_in;
+    const float *depth;
+    const float *normal;
+    const int *id;
+    const float *prev_rgba;
+    const float *prev_depth;
+    const float *prev_normal;
+    const int *prev_id;
+    const float *prev_moments;
+    float *rgba_out;
+    float *moments_out;
+    uint32_t *pixels;
+    int reset;
+    int max_history;             /*                                                                                 [32]   */
+    float depth_tolerance;       /*                                                                                 [0.02] */
+    float normal_cos_min;        /*                                                                                 [0.9]  */
+    int variant;                 /* 0: the product kernel; 1: the plain one-thread-per-pixel yardstick. The same bits      */
+    const float *sphere_motion;  /* NULL, or device, float4 per sphere, 16-byte aligned: .xyz = the sphere's centre now
+                                    minus its centre in the frame the history was accumulated over; .w is ignored [NULL]   */
+    int n_sphere_motion;         /* spheres the array covers; a sphere at or past it did not move (0 with NULL)     [0]    */
+    const float *cube_motion;    /* the same per cube: a translation of both corners                                [NULL] */
+    int n_cube_motion;           /*                                                                                 [0]    */
+    int clamp;                   /* non-zero: the reprojected history is clamped to the colour box of the current
+                                    frame's 3 x 3 neighbourhood                                                     [1]    */
+    float clamp_slack;           /* finite, in [0, 16]: each side of the box is widened by this share of its extent [0.25] */
+    int clamp_history;           /* 1 .. RT_TEMPORAL_MAX_HISTORY: where the clamp changed the history colour, the
+                                    history length counts as at most this                                           [4]    */
+} rt_tmotion_desc;
+
+/* The defaults in brackets above (the interface's own choices, not measurements); sizes, views and pointers 0. */
+void rt_tmotion_desc_init(rt_tmotion_desc *d);
+
+/* rt_scene_temporal for scenes whose spheres and cubes move by translation and whose lights move. Per pixel, the
+ * displacement m of the object its id names (spheres and cubes inside their tables; planes, triangles and everything
+ * else: 0) is taken out of the world point before that goes into the previous view, so the depth test compares
+ * prev_depth with where the surface point was; a displacement that is not finite leaves the pixel at (c, 1). With
+ * identical views a pixel whose m is zero takes rt_scene_temporal's single tap (a standing camera keeps the exact
+ * running mean on everything that did not move); a mover goes through the reprojection. With `clamp`, the
+ * reprojected history colour H is clamped per channel to [lo - e, hi + e], lo / hi the minimum / maximum of rgba_in
+ * over the 3 x 3 pixels around the pixel that lie inside the buffer and e = (hi - lo) * clamp_slack; where that
+ * changed H the history length is cut to clamp_history before the blend (a shadow that travelled over a pixel is
+ * forgotten within a few frames). DESIGN.md 6k gives every formula; both variants return the same bits, and with both
+ * counts 0 and clamp = 0 they are rt_scene_temporal's. Rotation and scaling, moving planes and meshes and per-pixel
+ * motion vectors are out of scope; lights carry no motion of their own: the clamp answers a moved light, and `reset`
+ * remains. The host side is rt_scene_temporal's: one kernel, no host wait but the ray-table upload of a new size or
+ * aspect, ordered with every temporal call of the scene, timed by rt_scene_set_temporal_timing. Refused with
+ * RT_ERR_INVALID before anything is enqueued: everything rt_scene_temporal refuses, a negative count, a count > 0
+ * with a NULL array, a motion array that is not 16-byte aligned, clamp_slack not finite or outside [0, 16],
+ * clamp_history out of range, an output that overlaps a motion array; a capturing stream: RT_ERR_UNSUPPORTED. */
+int rt_scene_temporal_motion(rt_scene *s, const rt_tmotion_desc *d, void *stream);
 
 /* What the kernels get as uniforms for a view, pure host code: out[0..2] the origin of every primary ray
  * (eyePos + cam.Org), out[3..6] cos_pitch, sin_pitch, cos_yaw, sin_yaw of camera::rotateDir. */

@@ -208,6 +208,13 @@ class TemporalDesc(C.Structure):
                 ("normal_cos_min", C.c_float), ("variant", C.c_int)]
 
 
+class TMotionDesc(C.Structure):
+    """rt_tmotion_desc: rt_temporal_desc's fields, then the motion and the clamp."""
+    _fields_ = TemporalDesc._fields_ + [("sphere_motion", C.c_void_p), ("n_sphere_motion", C.c_int),
+                                        ("cube_motion", C.c_void_p), ("n_cube_motion", C.c_int),
+                                        ("clamp", C.c_int), ("clamp_slack", C.c_float), ("clamp_history", C.c_int)]
+
+
 class ViewListsInfo(C.Structure):
     """rt_view_lists_info."""
     _fields_ = [("read", C.c_int), ("block_w", C.c_int), ("block_h", C.c_int), ("blocks_x", C.c_int), ("blocks_y", C.c_int),
@@ -354,6 +361,8 @@ def load_library():
         "rt_temporal_desc_init": (None, [C.POINTER(TemporalDesc)]),
         "rt_scene_temporal": (ci, [vp, C.POINTER(TemporalDesc), vp]),
         "rt_view_terms": (ci, [ci, ci, cf, C.POINTER(Camera), fp]),
+        "rt_tmotion_desc_init": (None, [C.POINTER(TMotionDesc)]),
+        "rt_scene_temporal_motion": (ci, [vp, C.POINTER(TMotionDesc), vp]),
         "rt_scene_set_temporal_timing": (ci, [vp, ci]),
         "rt_scene_temporal_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_scene_set_reflect_scope": (ci, [vp, ci]),
@@ -998,7 +1007,7 @@ class Scene:
                  depth_tolerance=None, normal_cos_min=None, want_moments=True, want_packed=True, variant=0, stream=None):
         """Blend a frame that render(..., aov=("depth", "normal", "id")) returned with camera `cam` and `aspect` into
         `history`, what the previous call returned (None: no history is read -- the first frame, or after objects or
-        lights moved). `colour`: an rgba tensor to accumulate instead of the frame's own, from another render of the
+        lights moved, which temporal_motion below follows instead). `colour`: an rgba tensor to accumulate instead of the frame's own, from another render of the
         same view (a jittered sample_base = k, sample_total = m frame, which cannot carry guides). Returns the new
         history {'rgba': float32 [rows, W, 4] (accumulated colour, history length), 'moments': float32 [rows, W, 2]
         or None, 'packed': int32 [rows, W] or None, 'depth', 'normal', 'id': the frame's guide tensors (not copied),
@@ -1043,6 +1052,127 @@ class Scene:
         _check(self.temporal_raw(d, st.cuda_stream), "rt_scene_temporal")
         return {"rgba": out, "moments": moments, "packed": packed, "depth": aov["depth"], "normal": aov["normal"],
                 "id": aov["id"], "cam": cam, "aspect": aspect}
+
+    # ------------------------------------------- temporal accumulation over moving objects
+    def temporal_motion_desc(self, width, height, *, sphere_motion=0, n_sphere_motion=0, cube_motion=0, n_cube_motion=0,
+                             clamp=None, clamp_slack=None, clamp_history=None, **kw) -> TMotionDesc:
+        """rt_tmotion_desc: temporal_desc's arguments, then the motion arrays (device addresses) and the clamp, with
+        rt_tmotion_desc_init's defaults where an argument is None."""
+        t = self.temporal_desc(width, height, **kw)
+        d = TMotionDesc()
+        self.lib.rt_tmotion_desc_init(C.byref(d))
+        for k, _ in TemporalDesc._fields_[1:]:
+            setattr(d, k, getattr(t, k))
+        d.sphere_motion, d.n_sphere_motion = sphere_motion, n_sphere_motion
+        d.cube_motion, d.n_cube_motion = cube_motion, n_cube_motion
+        if clamp is not None:
+            d.clamp = 1 if clamp else 0
+        for k, v in (("clamp_slack", clamp_slack), ("clamp_history", clamp_history)):
+            if v is not None:
+                setattr(d, k, v)
+        return d
+
+    def temporal_motion_raw(self, d: TMotionDesc, stream=0) -> int:
+        """rt_scene_temporal_motion as is: returns the status."""
+        return self.lib.rt_scene_temporal_motion(self.handle, C.byref(d), stream)
+
+    def _object_origins(self):
+        """Host copies, float32 [n, 3]: the sphere centres and each cube's bounds[0] as the scene holds them now."""
+        sp = np.zeros((self.n_spheres or 0, 3), dtype=np.float32)
+        for i in range(sp.shape[0]):
+            o = self.spheres[i].orgin
+            sp[i] = (o.x, o.y, o.z)
+        cu = np.zeros((getattr(self, "n_cubes", 0) or 0, 3), dtype=np.float32)
+        for i in range(cu.shape[0]):
+            o = self.cubes[i].bounds[0]
+            cu[i] = (o.x, o.y, o.z)
+        return sp, cu
+
+    def temporal_motion(self, frame, history=None, *, cam=None, aspect=None, colour=None, sphere_motion=None,
+                        cube_motion=None, clamp=None, clamp_slack=None, clamp_history=None, max_history=None,
+                        depth_tolerance=None, normal_cos_min=None, want_moments=True, want_packed=True, variant=0,
+                        stream=None):
+        """Scene.temporal for a scene whose spheres and cubes were moved (set_spheres / set_cubes) and whose lights may
+        have moved since `history` was made. The returned history is temporal's dict plus 'spheres' and 'cubes': host
+        copies, float32 [n, 3], of the sphere centres and of each cube's bounds[0] at the time of this call. With
+        sphere_motion / cube_motion None the displacements are now - history[...] in binary32 (a history from
+        Scene.temporal carries no positions: nothing moved); an object count that differs from the history's raises
+        RtError: start over with history=None. An explicit displacement array -- numpy [n, 3] or [n, 4], or a CUDA
+        float32 tensor [n, 4] -- overrides the inferred one. clamp / clamp_slack / clamp_history: rt_tmotion_desc's
+        (None: its defaults). Enqueued on `stream` (default: the current stream); inferred or numpy displacements
+        are uploaded first, which is the only host wait."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError("no GPU visible: temporal accumulation has no CPU fallback")
+        aov = frame.get("aov") or {}
+        rgba = frame.get("rgba") if colour is None else colour
+        need = ("depth", "normal", "id")
+        if rgba is None or any(k not in aov for k in need):
+            raise RtError(f"temporal_motion needs the frame's rgba (or colour=) and the G-buffer outputs {need}: render "
+                          f"with want_rgba=True and aov={need}")
+        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
+        if tuple(rgba.shape) != (rows, width, 4) or rgba.dtype != torch.float32 or not rgba.is_cuda:
+            raise RtError("temporal_motion: the colour must be a CUDA float32 tensor of the guides' shape [rows, W, 4]")
+        rgba = rgba.contiguous()
+        now = dict(zip(("spheres", "cubes"), self._object_origins()))
+        if history is not None:
+            if tuple(history["rgba"].shape) != (rows, width, 4):
+                raise RtError("temporal_motion: the history is of another size (pass history=None after a resize)")
+            if want_moments and history.get("moments") is None:
+                raise RtError("temporal_motion: want_moments needs a history with moments")
+            for k in ("spheres", "cubes"):
+                if history.get(k) is not None and history[k].shape != now[k].shape:
+                    raise RtError(f"temporal_motion: the scene has {now[k].shape[0]} {k}, the history {history[k].shape[0]} "
+                                  "(pass history=None after adding or removing objects)")
+        cam = _copy_camera(cam if cam is not None else default_camera())
+        aspect = default_aspect() if aspect is None else aspect
+        st = torch.cuda.current_stream() if stream is None else stream
+        motion = {}
+        with torch.cuda.stream(st):
+            out = torch.empty_like(rgba)
+            moments = torch.empty((rows, width, 2), dtype=torch.float32, device=rgba.device) if want_moments else None
+            packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
+            for k, given in (("spheres", sphere_motion), ("cubes", cube_motion)):
+                m = given
+                if m is None and history is not None and history.get(k) is not None:
+                    m = (now[k] - history[k]).astype(np.float32)
+                    if not m.any():
+                        m = None                                   # nothing moved: no table
+                if m is None or history is None:
+                    continue
+                if not torch.is_tensor(m):
+                    m = np.asarray(m, dtype=np.float32)
+                    if m.ndim != 2 or m.shape[1] not in (3, 4):
+                        raise RtError("temporal_motion: a displacement array is [n, 3] or [n, 4]")
+                    m4 = np.zeros((m.shape[0], 4), dtype=np.float32)
+                    m4[:, :m.shape[1]] = m
+                    m = torch.from_numpy(m4).to(rgba.device)
+                if m.dtype != torch.float32 or not m.is_cuda or m.ndim != 2 or m.shape[1] != 4 or not m.is_contiguous():
+                    raise RtError("temporal_motion: a displacement tensor must be a contiguous CUDA float32 [n, 4]")
+                if m.shape[0]:
+                    motion[k] = m
+        prev = {}
+        if history is not None:
+            prev = dict(prev_cam=history["cam"], prev_aspect=history["aspect"], prev_rgba=history["rgba"].data_ptr(),
+                        prev_depth=history["depth"].data_ptr(), prev_normal=history["normal"].data_ptr(),
+                        prev_id=history["id"].data_ptr(),
+                        prev_moments=history["moments"].data_ptr() if history.get("moments") is not None else 0)
+        sm, cm = motion.get("spheres"), motion.get("cubes")
+        d = self.temporal_motion_desc(width, rows, cam=cam, aspect=aspect, rgba_in=rgba.data_ptr(),
+                                      depth=aov["depth"].data_ptr(), normal=aov["normal"].data_ptr(),
+                                      id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
+                                      moments_out=moments.data_ptr() if want_moments else 0,
+                                      pixels=packed.data_ptr() if want_packed else 0, reset=history is None,
+                                      max_history=max_history, depth_tolerance=depth_tolerance,
+                                      normal_cos_min=normal_cos_min, variant=variant,
+                                      sphere_motion=sm.data_ptr() if sm is not None else 0,
+                                      n_sphere_motion=sm.shape[0] if sm is not None else 0,
+                                      cube_motion=cm.data_ptr() if cm is not None else 0,
+                                      n_cube_motion=cm.shape[0] if cm is not None else 0,
+                                      clamp=clamp, clamp_slack=clamp_slack, clamp_history=clamp_history, **prev)
+        _check(self.temporal_motion_raw(d, st.cuda_stream), "rt_scene_temporal_motion")
+        return {"rgba": out, "moments": moments, "packed": packed, "depth": aov["depth"], "normal": aov["normal"],
+                "id": aov["id"], "cam": cam, "aspect": aspect, "spheres": now["spheres"], "cubes": now["cubes"]}
 
     def set_temporal_timing(self, on: bool):
         _check(self.lib.rt_scene_set_temporal_timing(self.handle, 1 if on else 0), "rt_scene_set_temporal_timing")

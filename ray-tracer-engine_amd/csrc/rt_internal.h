@@ -242,3 +242,7 @@ int rt_vdenoise_launch(const rt_vdenoise_desc *d, float4 *col0, float4 *col1, fl
 // ev: null, or two timing events)
 int rt_temporal_launch(const rt_temporal_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
                        const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream);
+// the same for rt_scene_temporal_motion; dx_tab / dy_tab are needed with identical views too once an
+// object moved
+int rt_tmotion_launch(const rt_tmotion_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
+                      const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream);

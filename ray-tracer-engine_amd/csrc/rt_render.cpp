@@ -765,7 +765,7 @@ extern "C" int rt_scene_vdenoise_times(rt_scene *s, float *ms, int cap, int *n)
 }
 
 // ---------------------------------------------------------------------------
-// temporal accumulation (rt_temporal.hip, DESIGN.md 6i)
+// temporal accumulation (rt_temporal.hip, DESIGN.md 6i and 6k)
 // ---------------------------------------------------------------------------
 extern "C" void rt_temporal_desc_init(rt_temporal_desc *d)
 {
@@ -795,15 +795,16 @@ extern "C" int rt_view_terms(int width, int height, float aspect, const rt_camer
     return RT_OK;
 }
 
-extern "C" int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d_in, void *stream_)
+// rt_tmotion_desc repeats rt_temporal_desc's fields: one description, one set of checks and one host path serve both
+static_assert(offsetof(rt_tmotion_desc, variant) == offsetof(rt_temporal_desc, variant) &&
+                  offsetof(rt_tmotion_desc, rgba_in) == offsetof(rt_temporal_desc, rgba_in) &&
+                  offsetof(rt_tmotion_desc, pixels) == offsetof(rt_temporal_desc, pixels),
+              "rt_tmotion_desc must begin with rt_temporal_desc's fields");
+constexpr size_t kTemporalShared = offsetof(rt_temporal_desc, variant) + sizeof(int);
+
+// Both temporal entries. d: in this build's layout; motion: rt_scene_temporal_motion (`name` for the messages).
+static int temporal_call(rt_scene *s, const rt_tmotion_desc &d, bool motion, const char *name, hipStream_t stream)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!s || !d_in) {
-        rt_set_error("rt_scene_temporal: null scene or description");
-        return RT_ERR_INVALID;
-    }
-    rt_temporal_desc d;
-    as_built(d_in, &d);
     const bool reset = d.reset != 0;
     struct Range {
         uintptr_t p;
@@ -827,15 +828,23 @@ extern "C" int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d_in, void
     else if (d.variant < 0 || d.variant > 1) bad = "variant is not 0 or 1";
     else if (!(d.aspect > 0.f) || !std::isfinite(d.aspect) || (!reset && (!(d.prev_aspect > 0.f) || !std::isfinite(d.prev_aspect))))
         bad = "aspect and prev_aspect must be finite and > 0";
+    else if (motion && (d.n_sphere_motion < 0 || d.n_cube_motion < 0)) bad = "n_sphere_motion and n_cube_motion must not be negative";
+    else if (motion && ((d.n_sphere_motion > 0 && !d.sphere_motion) || (d.n_cube_motion > 0 && !d.cube_motion)))
+        bad = "a motion count > 0 needs its array";
+    else if (motion && (((uintptr_t)d.sphere_motion | (uintptr_t)d.cube_motion) & 15u)) bad = "sphere_motion and cube_motion must be 16-byte aligned";
+    else if (motion && !(d.clamp_slack >= 0.f && d.clamp_slack <= 16.f)) bad = "clamp_slack is not in [0, 16]";
+    else if (motion && (d.clamp_history < 1 || d.clamp_history > RT_TEMPORAL_MAX_HISTORY)) bad = "clamp_history is not in [1, RT_TEMPORAL_MAX_HISTORY]";
     else {
         // the pass gathers: an output that overlaps an input (or another output) would be read after it was written
         const size_t npx = (size_t)d.width * d.height;
         const Range outs[3] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.moments_out, npx * 8}, {(uintptr_t)d.pixels, npx * 4}};
-        const Range ins[9] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16},
-                              {(uintptr_t)d.id, npx * 8},
-                              {reset ? 0 : (uintptr_t)d.prev_rgba, npx * 16}, {reset ? 0 : (uintptr_t)d.prev_depth, npx * 4},
-                              {reset ? 0 : (uintptr_t)d.prev_normal, npx * 16}, {reset ? 0 : (uintptr_t)d.prev_id, npx * 8},
-                              {reset ? 0 : (uintptr_t)d.prev_moments, npx * 8}};
+        const Range ins[11] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16},
+                               {(uintptr_t)d.id, npx * 8},
+                               {reset ? 0 : (uintptr_t)d.prev_rgba, npx * 16}, {reset ? 0 : (uintptr_t)d.prev_depth, npx * 4},
+                               {reset ? 0 : (uintptr_t)d.prev_normal, npx * 16}, {reset ? 0 : (uintptr_t)d.prev_id, npx * 8},
+                               {reset ? 0 : (uintptr_t)d.prev_moments, npx * 8},
+                               {d.n_sphere_motion > 0 ? (uintptr_t)d.sphere_motion : 0, (size_t)d.n_sphere_motion * 16},
+                               {d.n_cube_motion > 0 ? (uintptr_t)d.cube_motion : 0, (size_t)d.n_cube_motion * 16}};
         auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
         for (int i = 0; i < 3 && !bad; ++i) {
             for (const Range &in : ins)
@@ -845,11 +854,11 @@ extern "C" int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d_in, void
         }
     }
     if (bad) {
-        rt_set_error("rt_scene_temporal: %s (%d x %d, max_history %d, variant %d)", bad, d.width, d.height, d.max_history, d.variant);
+        rt_set_error("%s: %s (%d x %d, max_history %d, variant %d)", name, bad, d.width, d.height, d.max_history, d.variant);
         return RT_ERR_INVALID;
     }
     if (stream_capturing(stream)) {
-        rt_set_error("rt_scene_temporal: the stream is being captured (the pass is not recorded into graphs)");
+        rt_set_error("%s: the stream is being captured (the pass is not recorded into graphs)", name);
         return RT_ERR_UNSUPPORTED;
     }
     float view[7], prev_view[7];
@@ -857,7 +866,8 @@ extern "C" int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d_in, void
     const bool same_view = !reset && memcmp(&d.cam, &d.prev_cam, sizeof d.cam) == 0 && memcmp(&d.aspect, &d.prev_aspect, sizeof d.aspect) == 0;
     if (reset) memcpy(prev_view, view, sizeof view);
     else rt_view_terms(d.width, d.height, d.prev_aspect, &d.prev_cam, prev_view);
-    const bool need_rays = !reset && !same_view;
+    // with identical views only a pixel of a moved object is reprojected
+    const bool need_rays = !reset && (!same_view || d.n_sphere_motion > 0 || d.n_cube_motion > 0);
     if (need_rays && !(s->tp_raygen.get() && s->tp_w == d.width && s->tp_h == d.height &&
                        memcmp(&s->tp_aspect, &d.aspect, sizeof d.aspect) == 0)) {
         // another size or aspect: new tables, after the host has seen the last call that read the old ones end
@@ -879,11 +889,59 @@ extern "C" int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d_in, void
             ev[i] = s->tp_ev[i].get();
         }
     }
-    const int rc = rt_temporal_launch(&d, need_rays ? s->tp_raygen.get() : nullptr, need_rays ? s->tp_raygen.get() + d.width : nullptr,
-                                      view, prev_view, same_view, s->tp_timing ? ev : nullptr, stream);
+    const float *dx_tab = need_rays ? s->tp_raygen.get() : nullptr, *dy_tab = need_rays ? s->tp_raygen.get() + d.width : nullptr;
+    int rc;
+    if (motion) {
+        rc = rt_tmotion_launch(&d, dx_tab, dy_tab, view, prev_view, same_view, s->tp_timing ? ev : nullptr, stream);
+    } else {
+        rt_temporal_desc td;
+        memset(&td, 0, sizeof td);
+        memcpy(&td, &d, kTemporalShared);
+        td.struct_size = (uint32_t)sizeof td;
+        rc = rt_temporal_launch(&td, dx_tab, dy_tab, view, prev_view, same_view, s->tp_timing ? ev : nullptr, stream);
+    }
     RT_HIP(s->tp_done.record(stream));
     if (rc == RT_OK && s->tp_timing) s->tp_timed = 2;
     return rc;
+}
+
+extern "C" int rt_scene_temporal(rt_scene *s, const rt_temporal_desc *d_in, void *stream_)
+{
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_temporal: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_temporal_desc td;
+    as_built(d_in, &td);
+    rt_tmotion_desc d;
+    memset(&d, 0, sizeof d);
+    memcpy(&d, &td, kTemporalShared);      // no motion, no clamp
+    d.struct_size = (uint32_t)sizeof d;
+    return temporal_call(s, d, false, "rt_scene_temporal", (hipStream_t)stream_);
+}
+
+extern "C" void rt_tmotion_desc_init(rt_tmotion_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->max_history = 32;
+    d->depth_tolerance = 0.02f;
+    d->normal_cos_min = 0.9f;
+    d->clamp = 1;
+    d->clamp_slack = 0.25f;
+    d->clamp_history = 4;
+}
+
+extern "C" int rt_scene_temporal_motion(rt_scene *s, const rt_tmotion_desc *d_in, void *stream_)
+{
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_temporal_motion: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_tmotion_desc d;
+    as_built(d_in, &d);
+    return temporal_call(s, d, true, "rt_scene_temporal_motion", (hipStream_t)stream_);
 }
 
 extern "C" int rt_scene_set_temporal_timing(rt_scene *s, int on)

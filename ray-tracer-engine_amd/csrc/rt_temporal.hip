@@ -14,6 +14,8 @@
 //   grid's width padded to a multiple of eight tiles: the tiles below one another then run on one XCD (tile b runs on
 //   XCD b % 8; the eight L2s are not shared) and the frame is still streamed row band by row band. With `reset` or
 //   identical views there is one tap or none and nothing to exchange: variant 0 launches tp_plain.
+// rt_scene_temporal_motion adds tm_plain / tm_product below: the same pass with a displacement per
+//   sphere and cube and a clamp of the history to the current neighbourhood's colour box.
 //   What was measured and not kept: 64 x 8 tiles walked column segment by column segment per XCD
 //   (slower than the yardstick: the frame is no longer streamed), other tile shapes in row-major order (the
 //   yardstick's time at 3840 x 2160), a packed record per previous pixel (a pass of its own costs more than it saves).
@@ -78,9 +80,8 @@ __device__ __forceinline__ void tp_write_new(const TpArgs &a, size_t p, float4 c
     tp_write(a, p, c.x, c.y, c.z, 1.f, y, y * y);
 }
 
-// The pixel's primary ray as rt_scene_primary_rays forms it (rf_primary_dir), its world point, and where that lands in
-// the previous view: false if it has no history for reasons of geometry. qq: squared distance to the previous eye.
-__device__ __forceinline__ bool tp_project(const TpArgs &a, int x, int y, float t, float &fx, float &fy, float &qq)
+// The pixel's primary ray as rt_scene_primary_rays forms it (rf_primary_dir) and its world point.
+__device__ __forceinline__ V3 tp_world(const TpArgs &a, int x, int y, float t)
 {
     RtFrameConsts fc;
     fc.width = a.w; fc.height = a.h; fc.y0 = 0;
@@ -88,7 +89,14 @@ __device__ __forceinline__ bool tp_project(const TpArgs &a, int x, int y, float 
     fc.eye_nz = a.eye_nz;
     fc.cos_pitch = a.cp; fc.sin_pitch = a.sp; fc.cos_yaw = a.cy; fc.sin_yaw = a.sy;
     const V3 D = rf_primary_dir(fc, y * a.w + x);
-    const float px = a.ox + D.x * t, py = a.oy + D.y * t, pz = a.oz + D.z * t;
+    V3 P;
+    P.x = a.ox + D.x * t; P.y = a.oy + D.y * t; P.z = a.oz + D.z * t;
+    return P;
+}
+// Where a world point lands in the previous view: false if it has no history for reasons of geometry. qq: squared
+// distance to the previous eye.
+__device__ __forceinline__ bool tp_into_prev(const TpArgs &a, float px, float py, float pz, float &fx, float &fy, float &qq)
+{
     const float qx = px - a.pox, qy = py - a.poy, qz = pz - a.poz;
     qq = (qx * qx + qy * qy) + qz * qz;
     const float vx = qx * a.pcy - qz * a.psy;
@@ -102,6 +110,11 @@ __device__ __forceinline__ bool tp_project(const TpArgs &a, int x, int y, float 
     fx = ((dx + 1.f) / a.pa) * half - 0.5f;
     fy = ((dy + 1.f) / a.pa) * half - 0.5f;
     return fx >= -1.f && fx <= (float)a.w && fy >= -1.f && fy <= (float)a.h;
+}
+__device__ __forceinline__ bool tp_project(const TpArgs &a, int x, int y, float t, float &fx, float &fy, float &qq)
+{
+    const V3 P = tp_world(a, x, y, t);
+    return tp_into_prev(a, P.x, P.y, P.z, fx, fy, qq);
 }
 // floor of a value in [-1, 32768]: truncation, corrected for negative values
 __device__ __forceinline__ int tp_floor(float f)
@@ -314,6 +327,269 @@ __global__ __launch_bounds__(TP_TW * TP_TH) void tp_product(const TpArgs a)
     tp_finish(a, p, c, s);
 }
 
+// ---------------------------------------------------------------------------
+// rt_scene_temporal_motion: the pass above with a displacement per sphere and cube taken out of the
+// world point before it goes into the previous view, and the history clamped to the colour box of the current frame's
+// 3 x 3 neighbourhood. tm_plain is the yardstick (the nine colours read straight from rgba_in); tm_product keeps
+// tp_product's tile and next-lane exchange and stages the tile's rgba_in with a one-pixel halo in LDS (66 x 6 float4:
+// a wave reads 64 consecutive 16-byte slots of one row, which ds_read_b128 serves without a bank conflict).
+// ---------------------------------------------------------------------------
+constexpr int TM_LW = TP_TW + 2, TM_LH = TP_TH + 2;        // the staged tile with its halo
+constexpr int TM_HALO = 2 * TM_LW + 2 * TP_TH;             // its border: two rows, two columns of TP_TH
+
+struct TmArgs {                        // by value
+    TpArgs t;
+    const float4 *smot, *cmot;         // a displacement per sphere / cube (null with a count of 0)
+    int nsm, ncm, clamp;
+    float slack, clamp_n;              // clamp_slack, (float)clamp_history
+};
+
+// The key of a float in the total order of the bit patterns, and min / max in that order: independent of the order in
+// which the nine values are visited (equal keys are equal bits).
+__device__ __forceinline__ uint32_t tm_key(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float tm_min(float a, float b) { return tm_key(a) <= tm_key(b) ? a : b; }
+__device__ __forceinline__ float tm_max(float a, float b) { return tm_key(a) >= tm_key(b) ? a : b; }
+
+struct TmBox {
+    float lo[3], hi[3];
+};
+// nb(dx, dy): rgba_in at the pixel's neighbour, coordinates clamped to the buffer
+template <class Nb>
+__device__ __forceinline__ TmBox tm_box(const Nb &nb)
+{
+    const float4 c = nb(0, 0);
+    TmBox b = {{c.x, c.y, c.z}, {c.x, c.y, c.z}};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        if (k == 4) continue;
+        const float4 v = nb(k % 3 - 1, k / 3 - 1);
+        b.lo[0] = tm_min(b.lo[0], v.x); b.hi[0] = tm_max(b.hi[0], v.x);
+        b.lo[1] = tm_min(b.lo[1], v.y); b.hi[1] = tm_max(b.hi[1], v.y);
+        b.lo[2] = tm_min(b.lo[2], v.z); b.hi[2] = tm_max(b.hi[2], v.z);
+    }
+    return b;
+}
+struct TmNbGlobal {
+    const float4 *in;
+    int w, h, x, y;
+    __device__ __forceinline__ float4 operator()(int dx, int dy) const
+    {
+        int qx = x + dx, qy = y + dy;
+        qx = qx < 0 ? 0 : (qx >= w ? w - 1 : qx);
+        qy = qy < 0 ? 0 : (qy >= h ? h - 1 : qy);
+        return in[(size_t)qy * w + qx];
+    }
+};
+struct TmNbLds {
+    const float4 *centre;              // the pixel's own slot in the staged tile
+    __device__ __forceinline__ float4 operator()(int dx, int dy) const { return centre[dy * TM_LW + dx]; }
+};
+
+// the displacement of the object a pixel shows: planes, triangles and indices outside the table do not move
+__device__ __forceinline__ float4 tm_motion(const TmArgs &a, int2 id)
+{
+    if (id.x == RT_HIT_SPHERE && (unsigned)id.y < (unsigned)a.nsm) return a.smot[id.y];
+    if (id.x == RT_HIT_CUBE && (unsigned)id.y < (unsigned)a.ncm) return a.cmot[id.y];
+    return make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ bool tm_static(float4 m) { return m.x == 0.f && m.y == 0.f && m.z == 0.f; }
+
+// tp_begin with the colour already read
+__device__ __forceinline__ bool tm_begin(const TpArgs &a, size_t p, float4 c, int2 &id, float &t)
+{
+    id = a.id[p];
+    t = a.depth[p];
+    if (id.x < 0 || !(t > 0.f) || !(t < __builtin_inff())) {
+        tp_write_new(a, p, c);
+        return false;
+    }
+    return true;
+}
+
+// tp_finish with the history clamped to the box
+template <class Nb>
+__device__ __forceinline__ void tm_finish(const TmArgs &a, size_t p, float4 c, const TpSum &s, const Nb &nb)
+{
+    const TpArgs &t = a.t;
+    if (!(s.w > 0.f)) {
+        tp_write_new(t, p, c);
+        return;
+    }
+    float h[3] = {s.r / s.w, s.g / s.w, s.b / s.w};
+    float nh = s.n / s.w;
+    if (a.clamp) {
+        const TmBox b = tm_box(nb);
+        bool clamped = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float e = (b.hi[k] - b.lo[k]) * a.slack;
+            const float lo = b.lo[k] - e, hi = b.hi[k] + e;
+            if (h[k] < lo) {
+                h[k] = lo;
+                clamped = true;
+            } else if (h[k] > hi) {
+                h[k] = hi;
+                clamped = true;
+            }
+        }
+        if (clamped && nh > a.clamp_n) nh = a.clamp_n;
+    }
+    float n = nh + 1.f;
+    if (!(n < t.max_n)) n = t.max_n;
+    const float al = 1.f / n;
+    const float r = h[0] + (c.x - h[0]) * al, g = h[1] + (c.y - h[1]) * al, bl = h[2] + (c.z - h[2]) * al;
+    float m1 = 0.f, m2 = 0.f;
+    if (t.moments_out) {
+        const float h1 = s.m1 / s.w, h2 = s.m2 / s.w;
+        const float y = tp_luma(c.x, c.y, c.z);
+        m1 = h1 + (y - h1) * al;
+        m2 = h2 + (y * y - h2) * al;
+    }
+    tp_write(t, p, r, g, bl, n, m1, m2);
+}
+
+// identical views, a static pixel: the only tap is the pixel itself with weight 1
+__device__ __forceinline__ TpSum tm_single_tap(const TpArgs &a, size_t p, int2 id, float t)
+{
+    TpSum s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float2 pm = (a.moments_out && a.prev_moments) ? a.prev_moments[p] : make_float2(0.f, 0.f);
+    tp_tap(a, id, a.normal[p], t * t, 1.f, a.prev_id[p], a.prev_depth[p], a.prev_normal[p], a.prev_rgba[p], pm, s);
+    return s;
+}
+
+__global__ __launch_bounds__(TP_ROW) void tm_plain(const TmArgs a)
+{
+    const TpArgs &ta = a.t;
+    const int x = (int)blockIdx.x * TP_ROW + (int)threadIdx.x, y = (int)blockIdx.y;
+    if (x >= ta.w) return;
+    const size_t p = (size_t)y * ta.w + x;
+    const float4 c = ta.rgba_in[p];
+    int2 id;
+    float t;
+    if (!tm_begin(ta, p, c, id, t)) return;
+    const TmNbGlobal nb = {ta.rgba_in, ta.w, ta.h, x, y};
+    const float4 m = tm_motion(a, id);
+    if (ta.same_view && tm_static(m)) {
+        tm_finish(a, p, c, tm_single_tap(ta, p, id, t), nb);
+        return;
+    }
+    const V3 P = tp_world(ta, x, y, t);
+    float fx, fy, qq;
+    if (!tp_into_prev(ta, P.x - m.x, P.y - m.y, P.z - m.z, fx, fy, qq)) {
+        tp_write_new(ta, p, c);
+        return;
+    }
+    const int x0 = tp_floor(fx), y0 = tp_floor(fy);
+    const float ax = fx - (float)x0, ay = fy - (float)y0;
+    const float4 n = ta.normal[p];
+    const bool moments = ta.moments_out && ta.prev_moments;
+    TpSum s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < 4; ++k) {
+        const int tx = x0 + (k & 1), ty = y0 + (k >> 1);
+        if (tx < 0 || tx >= ta.w || ty < 0 || ty >= ta.h) continue;
+        const size_t q = (size_t)ty * ta.w + tx;
+        const int2 pid = ta.prev_id[q];
+        if (pid.x != id.x || pid.y != id.y) continue;
+        tp_tap(ta, id, n, qq, tp_weight(k, ax, ay), pid, ta.prev_depth[q], ta.prev_normal[q], ta.prev_rgba[q],
+               moments ? ta.prev_moments[q] : make_float2(0.f, 0.f), s);
+    }
+    tm_finish(a, p, c, s, nb);
+}
+
+// tp_product's tile, order and exchange. Every lane of a tile that touches the frame stages a colour (its own, or the
+// frame's nearest for a lane past the right or bottom edge) and the first TM_HALO lanes one halo slot each; nobody
+// leaves before the barrier and the exchange. The barrier stands right behind the staging: holding it back until every
+// lane's tap loads were issued keeps 110 registers alive instead of 75 and took 1.38 x rt_scene_temporal's time at
+// 3840 x 2160 against this form's 1.16. With identical views static lanes take the single tap and sit the exchange out; movers
+// go through the reprojection.
+template <bool MOMENTS>
+__global__ __launch_bounds__(TP_TW * TP_TH) void tm_product(const TmArgs a)
+{
+    __shared__ float4 tile[TM_LH * TM_LW];
+    const TpArgs &ta = a.t;
+    const int nsegp = (((ta.w + TP_TW - 1) / TP_TW + 7) >> 3) << 3;
+    const int b = (int)blockIdx.x;
+    const int tyi = b / nsegp, seg = b - tyi * nsegp;
+    if (seg * TP_TW >= ta.w) return;               // a tile of the padding: the whole workgroup
+    const int lx = (int)threadIdx.x & (TP_TW - 1), ly = (int)threadIdx.x / TP_TW;
+    const int x = seg * TP_TW + lx, y = tyi * TP_TH + ly;
+    const bool inside = x < ta.w && y < ta.h;
+    const size_t p = (size_t)(y < ta.h ? y : ta.h - 1) * ta.w + (x < ta.w ? x : ta.w - 1);     // its own if inside
+    const float4 c = ta.rgba_in[p];
+    if (a.clamp) {
+        tile[(ly + 1) * TM_LW + lx + 1] = c;
+        const int i = (int)threadIdx.x;
+        if (i < TM_HALO) {
+            int hx, hy;
+            if (i < 2 * TM_LW) {
+                hx = i < TM_LW ? i : i - TM_LW;
+                hy = i < TM_LW ? 0 : TM_LH - 1;
+            } else {
+                const int j = i - 2 * TM_LW;
+                hx = j < TP_TH ? 0 : TM_LW - 1;
+                hy = 1 + (j < TP_TH ? j : j - TP_TH);
+            }
+            int gx = seg * TP_TW - 1 + hx, gy = tyi * TP_TH - 1 + hy;
+            gx = gx < 0 ? 0 : (gx >= ta.w ? ta.w - 1 : gx);
+            gy = gy < 0 ? 0 : (gy >= ta.h ? ta.h - 1 : gy);
+            tile[hy * TM_LW + hx] = ta.rgba_in[(size_t)gy * ta.w + gx];
+        }
+        __syncthreads();
+    }
+    const TmNbLds nb = {&tile[(ly + 1) * TM_LW + lx + 1]};
+    int2 id = make_int2(-1, 0);
+    float t = 0.f;
+    bool live = false;
+    float fx = 0.f, fy = 0.f, qq = 0.f;
+    if (inside && tm_begin(ta, p, c, id, t)) {
+        const float4 m = tm_motion(a, id);
+        if (ta.same_view && tm_static(m)) {
+            tm_finish(a, p, c, tm_single_tap(ta, p, id, t), nb);
+        } else {
+            const V3 P = tp_world(ta, x, y, t);
+            live = tp_into_prev(ta, P.x - m.x, P.y - m.y, P.z - m.z, fx, fy, qq);
+            if (!live) tp_write_new(ta, p, c);
+        }
+    }
+    int x0 = 0, y0 = 0;
+    int ql[2] = {-1, -1}, qr[2] = {-2, -2};        // the pixels a live lane loads / wants from the next lane
+    TpRec L[2] = {}, R[2] = {};
+    float4 n = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) {
+        x0 = tp_floor(fx); y0 = tp_floor(fy);
+        n = ta.normal[p];
+        const int cx0 = x0 < 0 ? 0 : (x0 >= ta.w ? ta.w - 1 : x0), cx1 = x0 + 1 >= ta.w ? ta.w - 1 : x0 + 1;   // x0 + 1 >= 0
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int ty = y0 + r, cy = ty < 0 ? 0 : (ty >= ta.h ? ta.h - 1 : ty);
+            ql[r] = cy * ta.w + cx0;
+            qr[r] = cy * ta.w + cx1;
+            L[r] = tp_load<MOMENTS>(ta, ql[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int nq = __shfl_down(ql[r], 1);      // the last lane gets its own
+        R[r] = tp_next_lane<MOMENTS>(L[r]);
+        if (live && nq != qr[r]) R[r] = tp_load<MOMENTS>(ta, qr[r]);
+    }
+    if (!live) return;
+    const float ax = fx - (float)x0, ay = fy - (float)y0;
+    TpSum s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int tx = x0 + (k & 1), ty = y0 + (k >> 1);
+        if (tx < 0 || tx >= ta.w || ty < 0 || ty >= ta.h) continue;
+        const TpRec &q = (k & 1) ? R[k >> 1] : L[k >> 1];
+        tp_tap(ta, id, n, qq, tp_weight(k, ax, ay), q.id, q.t, q.n, q.c, q.m, s);
+    }
+    tm_finish(a, p, c, s, nb);
+}
+
 }   // namespace
 
 #define TP_HIP(expr)                                                         \
@@ -322,8 +598,10 @@ __global__ __launch_bounds__(TP_TW * TP_TH) void tp_product(const TpArgs a)
         if (tp_e_ != hipSuccess) return rt_hip_fail(tp_e_, #expr, __FILE__, __LINE__); \
     } while (0)
 
-int rt_temporal_launch(const rt_temporal_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
-                       const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream)
+// the description's prefix that both entries share (rt_tmotion_desc repeats rt_temporal_desc's fields)
+template <class Desc>
+static TpArgs tp_args(const Desc *d, const float *dx_tab, const float *dy_tab, const float view[7], const float prev_view[7],
+                      bool same_view)
 {
     TpArgs a = {};
     a.w = d->width; a.h = d->height;
@@ -351,15 +629,55 @@ int rt_temporal_launch(const rt_temporal_desc *d, const float *dx_tab, const flo
     a.rgba_out = (float4 *)d->rgba_out;
     a.moments_out = (float2 *)d->moments_out;
     a.pixels = d->pixels;
+    return a;
+}
+
+static int tp_launch(const TpArgs &a, int variant, hipEvent_t *ev, hipStream_t stream)
+{
     if (ev) TP_HIP(hipEventRecord(ev[0], stream));
     // reset and identical views read no neighbour: the product is then the plain kernel
-    if (d->variant == 1 || a.reset || a.same_view) {
+    if (variant == 1 || a.reset || a.same_view) {
         hipLaunchKernelGGL(tp_plain, dim3((a.w + TP_ROW - 1) / TP_ROW, a.h), dim3(TP_ROW), 0, stream, a);
     } else {
         const int nseg8 = ((a.w + TP_TW - 1) / TP_TW + 7) >> 3, nty = (a.h + TP_TH - 1) / TP_TH;
         const dim3 grid((unsigned)((size_t)nseg8 * 8 * nty)), block(TP_TW * TP_TH);
         if (a.moments_out && a.prev_moments) hipLaunchKernelGGL(tp_product<true>, grid, block, 0, stream, a);
         else hipLaunchKernelGGL(tp_product<false>, grid, block, 0, stream, a);
+    }
+    TP_HIP(hipGetLastError());
+    if (ev) TP_HIP(hipEventRecord(ev[1], stream));
+    return RT_OK;
+}
+
+int rt_temporal_launch(const rt_temporal_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
+                       const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream)
+{
+    return tp_launch(tp_args(d, dx_tab, dy_tab, view, prev_view, same_view), d->variant, ev, stream);
+}
+
+int rt_tmotion_launch(const rt_tmotion_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
+                      const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream)
+{
+    TmArgs a = {};
+    a.t = tp_args(d, dx_tab, dy_tab, view, prev_view, same_view);
+    a.nsm = d->sphere_motion ? d->n_sphere_motion : 0;
+    a.ncm = d->cube_motion ? d->n_cube_motion : 0;
+    a.smot = a.nsm ? (const float4 *)d->sphere_motion : nullptr;
+    a.cmot = a.ncm ? (const float4 *)d->cube_motion : nullptr;
+    a.clamp = d->clamp != 0;
+    a.slack = d->clamp_slack;
+    a.clamp_n = (float)d->clamp_history;
+    // nothing moves and nothing is clamped, or no history is read: rt_scene_temporal's kernels compute it
+    if (a.t.reset || (a.nsm == 0 && a.ncm == 0 && !a.clamp)) return tp_launch(a.t, d->variant, ev, stream);
+    const TpArgs &t = a.t;
+    if (ev) TP_HIP(hipEventRecord(ev[0], stream));
+    if (d->variant == 1) {
+        hipLaunchKernelGGL(tm_plain, dim3((t.w + TP_ROW - 1) / TP_ROW, t.h), dim3(TP_ROW), 0, stream, a);
+    } else {
+        const int nseg8 = ((t.w + TP_TW - 1) / TP_TW + 7) >> 3, nty = (t.h + TP_TH - 1) / TP_TH;
+        const dim3 grid((unsigned)((size_t)nseg8 * 8 * nty)), block(TP_TW * TP_TH);
+        if (t.moments_out && t.prev_moments) hipLaunchKernelGGL(tm_product<true>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(tm_product<false>, grid, block, 0, stream, a);
     }
     TP_HIP(hipGetLastError());
     if (ev) TP_HIP(hipEventRecord(ev[1], stream));
