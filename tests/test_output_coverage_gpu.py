@@ -11,6 +11,7 @@ import pytest
 
 import denoise_ref as R
 import meshes
+import vdenoise_ref as V
 from arena import PATTERNS, Run, as_bytes, assert_pair, run_twice, same_bytes
 from scenes import Inputs, mixed_scene
 
@@ -18,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 # bytes per pixel and required alignment of the per-pixel outputs (include/rt_engine.h)
 LAYOUT = {"pixels": (4, 4), "rgba": (16, 16), "packed24": (3, 4), "depth": (4, 4), "normal": (16, 16), "id": (8, 8),
-          "albedo": (16, 16), "moments": (8, 8), "host": (4, 4), "rays": (24, 4)}
+          "albedo": (16, 16), "moments": (8, 8), "host": (4, 4), "rays": (24, 4), "variance": (4, 4)}
 AOV = ("depth", "normal", "id", "albedo")
 GUIDES = ("depth", "normal", "id")
 
@@ -348,6 +349,9 @@ def test_primary_rays_of_a_band(rt, scene):
 
 # ----------------------------------------------------------------------------- denoise and temporal
 SIZES = [(64, 1), (1, 64), (5, 5), (65, 9), (161, 91)]
+# Beyond the first group of eight: 17 tile columns of 64 for the two temporal product kernels, whose grid
+# is padded to a multiple of eight columns; 9 row segments of 256 for vd_iter_direct, which walks them in groups of eight.
+WIDE_TEMPORAL, WIDE_DENOISE = (1088, 5), (2100, 3)
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -403,7 +407,128 @@ def test_denoise(rt, scene, w, h):
     assert np.array_equal(as_bytes(frame["rgba"]), before)
 
 
-@pytest.mark.parametrize("w,h", SIZES)
+def _accumulated(rt, scene, w, h, ks):
+    """The frame of the last of the cameras `ks` with every G-buffer output, and Scene.temporal's history over them."""
+    hist = None
+    for k in ks:
+        frame = scene.render(w, h, cam=_camera(rt, k), aov=AOV)
+        hist = scene.temporal(frame, hist, cam=_camera(rt, k))
+    return frame, hist
+
+
+@pytest.mark.parametrize("w,h", SIZES + [WIDE_DENOISE])
+def test_denoise_variance(rt, scene, w, h):
+    """rt_scene_denoise_variance into arenas for rgba_out, pixels and variance_out, with a history of two cameras and
+    without. The passes go through six scratch arrays of the scene's (two of irradiance, the packed guides and keys,
+    two of variance) and leave parts of them unwritten by design: the pack pass stores no guide and no key for a sky
+    pixel, the spatial pass leaves per workgroup. As in test_denoise no arena can stand for them, so every call follows
+    a decoy call of the same size -- two iterations of the product kernels, which write all six -- on the frame and
+    history of a camera 2.4 degrees and 0.28 units away: its valid pixels differ from the real call's in both
+    directions (on CPU frames 70 and 65 of 585 pixels at 65 x 9, 1 271 and 1 727 of 6 300 at 2100 x 3), so that stale
+    guides, keys and variances are plausible values exactly where the real call has sky; and the result is compared
+    with the restatement, not only with another run of the library."""
+    import torch
+    frame, hist = _accumulated(rt, scene, w, h, (0, 1))
+    decoy = _accumulated(rt, scene, w, h, (4, 5))
+    torch.cuda.synchronize()
+    a = frame["aov"]
+    valid, decoy_valid = ((f["aov"]["id"][..., 0] >= 0).cpu().numpy() for f in (frame, decoy[0]))
+    if w * h >= 65 * 9:
+        assert (valid & ~decoy_valid).any() and (~valid & decoy_valid).any() and valid.any() and not valid.all()
+    ins = [frame["rgba"], hist["rgba"], hist["moments"], a["depth"], a["normal"], a["albedo"], a["id"]]
+    before = [as_bytes(t).copy() for t in ins]
+    guides = [a[k].cpu().numpy() for k in ("depth", "normal", "albedo", "id")]
+    names = ("rgba", "pixels", "variance")
+
+    def dirty_the_scratch():
+        scene.denoise_variance(*decoy, iterations=2, variant=0)
+
+    for iterations in (1, 5, 6):
+        for history in (hist, None):
+            src = frame["rgba"] if history is None else history["rgba"]
+            moments = None if history is None else history["moments"]
+            ref = dict(zip(names, V.denoise_variance(src.cpu().numpy(), *guides, None if moments is None else moments.cpu().numpy(),
+                                                     iterations=iterations)))
+            for variant in (0, 1, 2):
+                def call(p, unset=(), in_place=False):
+                    dirty_the_scratch()
+                    g = lambda k: 0 if k in unset else p[k]
+                    d = scene.vdenoise_desc(w, h, rgba_in=p["rgba"] if in_place else src.data_ptr(), depth=a["depth"].data_ptr(),
+                                            normal=a["normal"].data_ptr(), albedo=a["albedo"].data_ptr(), id=a["id"].data_ptr(),
+                                            moments=0 if moments is None else moments.data_ptr(), rgba_out=p["rgba"],
+                                            pixels=g("pixels"), variance_out=g("variance"), iterations=iterations, variant=variant)
+                    assert scene.denoise_variance_raw(d, _stream()) == 0, scene.lib.rt_last_error()
+                what = f"iterations {iterations} variant {variant} history {history is not None}"
+                got = run_twice(call, _outs(w * h, names), what)
+                out = scene.denoise_variance(frame, history, iterations=iterations, variant=variant)
+                want = dict(rgba=out["rgba"], pixels=out["packed"], variance=out["variance"])
+                for k in names:
+                    same_bytes(got[k], want[k], f"{what} {k}")
+                    same_bytes(got[k], ref[k], f"{what} {k} against the restatement")
+                for unset in ("pixels", "variance"):
+                    got = run_twice(lambda p: call(p, (unset,)), _outs(w * h, names, untouched=(unset,)), f"{what} without {unset}")
+                    for k in names:
+                        if k != unset:
+                            same_bytes(got[k], want[k], f"{what} without {unset}: {k}")
+                # in place: rgba_out is rgba_in
+                outs = _outs(w * h, names)
+                outs["rgba"]["prefill"] = as_bytes(src).tobytes()
+                got = run_twice(lambda p: call(p, in_place=True), outs, what + " in place")
+                for k in names:
+                    same_bytes(got[k], want[k], f"{what} in place {k}")
+    for t, b in zip(ins, before):
+        assert np.array_equal(as_bytes(t), b)
+
+
+@pytest.mark.parametrize("w,h", SIZES + [WIDE_TEMPORAL])
+def test_temporal_motion(rt, scene, w, h):
+    """rt_scene_temporal_motion into arenas for rgba_out, moments_out and pixels, with every second sphere that the
+    frames show displaced: under the moved view every hit pixel is reprojected; under the identical view the movers go
+    through tm_product's reprojection and exchange while the static lanes of the same waves take the single tap."""
+    import torch
+    cams = [_camera(rt, 0), _camera(rt, 1)]
+    frames = [scene.render(w, h, cam=c, aov=GUIDES) for c in cams]
+    hist = scene.temporal(frames[0], None, cam=cams[0])
+    torch.cuda.synchronize()
+    ids = np.stack([f["aov"]["id"].cpu().numpy() for f in frames])
+    shown = np.unique(ids[..., 1][ids[..., 0] == 1])             # RT_HIT_SPHERE
+    assert shown.size > 0
+    table = np.zeros((256, 4), dtype=np.float32)
+    moves = np.array([(0.0, 0.05, 0.0), (-0.04, 0.02, 0.05), (0.03, 0.0, -0.03)], dtype=np.float32)
+    table[shown[::2], :3] = moves[np.arange(shown[::2].size) % 3]
+    mover = (ids[..., 0] == 1) & np.isin(ids[..., 1], shown[::2])
+    if w * h >= 65 * 9:
+        assert mover[0].any() and mover[1].any() and ((ids[..., 0] >= 0) & ~mover)[0].any()
+    if w > 512:             # movers and static hits in tiles beyond the first group of eight, in both frames
+        assert mover[:, :, 512:].any(axis=(1, 2)).all() and ((ids[..., 0] >= 0) & ~mover)[:, :, 512:].any(axis=(1, 2)).all()
+    sm = torch.from_numpy(table).cuda()
+    names = ("rgba", "moments", "pixels")
+    for variant in (0, 1):
+        for clamp in (True, False):
+            for i, view in ((1, "moved"), (0, "identical")):
+                def call(p, unset=()):
+                    f = frames[i]["aov"]
+                    g = lambda k: 0 if k in unset else p[k]
+                    d = scene.temporal_motion_desc(
+                        w, h, cam=cams[i], rgba_in=frames[i]["rgba"].data_ptr(), depth=f["depth"].data_ptr(),
+                        normal=f["normal"].data_ptr(), id=f["id"].data_ptr(), prev_cam=hist["cam"], prev_aspect=hist["aspect"],
+                        prev_rgba=hist["rgba"].data_ptr(), prev_depth=hist["depth"].data_ptr(),
+                        prev_normal=hist["normal"].data_ptr(), prev_id=hist["id"].data_ptr(),
+                        prev_moments=hist["moments"].data_ptr(), rgba_out=p["rgba"], moments_out=g("moments"),
+                        pixels=g("pixels"), variant=variant, clamp=clamp, sphere_motion=sm.data_ptr(), n_sphere_motion=256)
+                    assert scene.temporal_motion_raw(d, _stream()) == 0, scene.lib.rt_last_error()
+                what = f"variant {variant} clamp {clamp} {view} view"
+                want = scene.temporal_motion(frames[i], hist, cam=cams[i], sphere_motion=sm, clamp=clamp, variant=variant)
+                got = run_twice(call, _outs(w * h, names), what)
+                for k, t in (("rgba", want["rgba"]), ("moments", want["moments"]), ("pixels", want["packed"])):
+                    same_bytes(got[k], t, f"{what} {k}")
+                # the MOMENTS = false instantiation
+                got = run_twice(lambda p: call(p, ("moments", "pixels")), _outs(w * h, names, untouched=("moments", "pixels")),
+                                what + " rgba only")
+                same_bytes(got["rgba"], want["rgba"], what + " rgba only")
+
+
+@pytest.mark.parametrize("w,h", SIZES + [WIDE_TEMPORAL])
 def test_temporal(rt, scene, w, h):
     import torch
     cams = [_camera(rt, 0), _camera(rt, 1)]

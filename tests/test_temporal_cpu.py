@@ -48,6 +48,22 @@ class View:
         return T.temporal(self.cur, hist, self.O, self.D, self.terms, prev.terms, prev.aspect, same, details=True, **kw)
 
 
+# The wide path: the GPU tests' path with the yaw turned to 170, for buffers of more than eight tile
+# columns (tp_product / tm_product pad their grid to a multiple of eight 64-pixel columns) and of more than eight
+# 256-pixel row segments (vd_iter_direct). With yaw 180 columns 512 .. 575 of a 576 x 36 frame show no sphere at all.
+WIDE_CAMS = ((4, 3, 10, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.7, 3.1, 10.1, 166, -21))
+WIDE_BLOCK = 64                 # a tile column of the two temporal product kernels
+WIDE_FIRST = 8                  # the first tile column outside the first group of eight
+WIDE_HISTORY_FLOOR = 0.1        # of every such column's pixels, in the moved-camera step
+WIDE_SEGMENT = 2048             # the first column of vd_iter_direct's second group of eight row segments
+WIDE_HIT_FLOOR = 0.3            # of the pixels from there on, for the second camera
+
+
+def block_shares(mask, first=WIDE_FIRST):
+    """The share of `mask` [H, W] in every 64-column block from block `first` on."""
+    return [float(mask[:, x:x + WIDE_BLOCK].mean()) for x in range(first * WIDE_BLOCK, mask.shape[1], WIDE_BLOCK)]
+
+
 def _pair(rt, oracle, inp, w, h):
     """The default camera, then the same camera half a unit to the side."""
     return View(rt, oracle, inp, _cam(rt, 4, 3, 10, 180, -20), w, h), View(rt, oracle, inp, _cam(rt, 4.5, 3, 10, 180, -20), w, h)
@@ -119,6 +135,29 @@ def test_a_sideways_step(request, scene):
     assert np.array_equal(_bits(out[~has]), _bits(c[~has]))
     Y = R.luma(c)
     assert np.array_equal(_bits(r["moments"][~has]), _bits(np.stack([Y, (Y * Y).astype(f32)], axis=-1)[~has]))
+
+
+def test_the_wide_inputs_show_spheres_beyond_the_first_group_of_eight(rt, oracle):
+    """Conditions on the inputs of the wide GPU tests (test_temporal_gpu, test_tmotion_gpu, test_vdenoise_gpu), from
+    the restatement alone, so that those tests cannot pass on sky: 256 spheres, the first two cameras of WIDE_CAMS.
+    The restatement's values -- 576 x 36: 9 tile columns, hit share 0.70, has_history share 0.57, 0.84 in column 8;
+    1088 x 36: 17 tile columns, hit share 0.70, has_history share 0.46, the smallest of columns 8 .. 16 is column 12
+    with 0.17; 2100 x 36: 9 row segments of 256, hit share 0.68 and 0.59 in columns >= 2048. The floors (0.1 of a
+    column's pixels with history, 0.3 of the pixels hit) lie below the smallest of these by a factor of 1.7 at least."""
+    inp = Inputs(rt, 256)
+    for w, tiles in ((576, 9), (1088, 17)):
+        assert -(-w // WIDE_BLOCK) == tiles and ((tiles + 7) >> 3) << 3 > 8            # nsegp = 16, 24
+        a, b = (View(rt, oracle, inp, _cam(rt, *c), w, 36) for c in WIDE_CAMS[:2])
+        r = b.onto(a.onto(None, a), a)
+        shares = block_shares(r["has_history"])
+        print(w, "hit share", (b.cur["id"][..., 0] >= 0).mean(), "has_history share", r["has_history"].mean(), "columns 8 ..:", shares)
+        assert len(shares) == tiles - WIDE_FIRST and min(shares) >= WIDE_HISTORY_FLOOR, (w, shares)
+    w = 2100
+    assert (-(-w // 256) + 7) >> 3 == 2                                                # nseg8
+    b = View(rt, oracle, inp, _cam(rt, *WIDE_CAMS[1]), w, 36)
+    hit = b.cur["id"][..., 0] >= 0
+    print(w, "hit share", hit.mean(), "in columns >= 2048:", hit[:, WIDE_SEGMENT:].mean())
+    assert hit[:, WIDE_SEGMENT:].mean() >= WIDE_HIT_FLOOR
 
 
 def test_a_camera_turned_round_has_no_history(rt, oracle, spheres):

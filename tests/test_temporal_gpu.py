@@ -7,6 +7,7 @@ import pytest
 import meshes
 import temporal_ref as T
 from scenes import Inputs, mixed_scene
+from test_temporal_cpu import WIDE_CAMS, WIDE_HISTORY_FLOOR, block_shares
 
 pytestmark = pytest.mark.gpu
 
@@ -146,6 +147,33 @@ def test_sizes_that_are_no_multiple_of_the_tiles(rt, gpu, w, h):
         y0, x0 = min(max(cy - h // 2, 0), 91 - h), min(max(cx - w // 2, 0), 322 - w)
         res = _chain(rt, sc, inp, 322, 91, cams, crop=(slice(y0, y0 + h), slice(x0, x0 + w)))
         assert res[2]["has_history"].any()              # the repeated camera
+    finally:
+        sc.close()
+
+
+def _wide_path(rt):
+    """_path with the yaw turned to 170 (test_temporal_cpu.WIDE_CAMS)."""
+    return [_cam(rt, *c) for c in WIDE_CAMS]
+
+
+@pytest.mark.parametrize("w,h", [(576, 36), (1088, 36)])
+def test_more_than_eight_tile_columns(rt, gpu, w, h):
+    """tp_product pads its grid's width to a multiple of eight 64-pixel tile columns (nsegp) and finds its tile by
+    b / nsegp and b - tyi * nsegp: at every width up to 512 nsegp is 8. 576 has 9 columns (nsegp = 16), 1088 has 17
+    (nsegp = 24); frames rendered at the size itself, along the path with the yaw turned to 170, where the columns
+    from 8 on show spheres that keep history over the camera step. Measured with the restatement on CPU frames
+    (test_temporal_cpu): has_history share 0.84 in column 8 of 576; 0.17 in column 12 of 1088, the smallest of columns
+    8 .. 16. The floor of 0.1 is asserted here on the restatement's has_history of the device's frames."""
+    inp = Inputs(rt, 256)
+    sc = _scene(rt, inp)
+    try:
+        res = _chain(rt, sc, inp, w, h, _wide_path(rt))
+        shares = block_shares(res[1]["has_history"])
+        print(w, "has_history share of tile columns 8 ..:", shares)
+        assert len(shares) == -(-w // 64) - 8 and min(shares) >= WIDE_HISTORY_FLOOR, shares
+        assert not res[0]["has_history"].any()
+        hit = res[2]["id"][..., 0] >= 0
+        assert res[2]["has_history"][hit].all()                         # the repeated camera
     finally:
         sc.close()
 

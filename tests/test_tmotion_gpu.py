@@ -8,7 +8,7 @@ import pytest
 import meshes
 import tmotion_ref as M
 from scenes import Inputs, mixed_scene
-from test_temporal_gpu import GUIDES, SENTINEL, _bits, _cam, _crop, _cur, _hist_np, _path, _scene
+from test_temporal_gpu import GUIDES, SENTINEL, _bits, _cam, _crop, _cur, _hist_np, _path, _scene, _wide_path
 from test_tmotion_cpu import move_cube, move_spheres
 
 pytestmark = pytest.mark.gpu
@@ -54,9 +54,9 @@ def _step(rt, sc, frame, hist, cam, aspect, sm=None, cm=None, colour=None, **kw)
     return a, want
 
 
-def _visible(frame, kind, k, skip=()):
-    """The k objects of `kind` that cover most pixels of the frame (fewer if fewer are seen)."""
-    ids = frame["aov"]["id"].cpu().numpy()
+def _visible(frame, kind, k, skip=(), x0=0):
+    """The k objects of `kind` that cover most pixels of the frame's columns from x0 on (fewer if fewer are seen)."""
+    ids = frame["aov"]["id"].cpu().numpy()[:, x0:]
     idx, cnt = np.unique(ids[..., 1][ids[..., 0] == kind], return_counts=True)
     order = [int(i) for i in idx[np.argsort(-cnt, kind="stable")] if int(i) not in skip]
     return order[:k]
@@ -65,17 +65,22 @@ def _visible(frame, kind, k, skip=()):
 MOVES = [(0.0, 0.2, 0.0), (-0.15, 0.1, 0.2), (0.1, 0.0, -0.1), (0.05, -0.1, 0.1)]
 
 
-def _walk(rt, sc, inp, w, h, crop=None, cube=None, **kw):
+def _walk(rt, sc, inp, w, h, crop=None, cube=None, cams=None, movers=4, x0=0, **kw):
     """A camera translation with four spheres (and `cube`) displaced, the same camera again with other displacements,
     a yaw step; every step with the clamp on and off from the same history. Returns the restatement's results with
-    the clamp on."""
-    cams = _path(rt)
+    the clamp on. cams: another path of that form; movers, x0: that many spheres per step, those that cover most of
+    the columns from x0 on."""
+    cams = _path(rt) if cams is None else cams
     hist, res, moved = None, [], []
     frame = None
     for k, cam in enumerate(cams):
         sm = cm = None
         if k in (1, 2) and frame is not None:
-            pick = _visible(frame, M.RT_HIT_SPHERE, 4, skip=moved)
+            # x0: what the coming camera sees there before the move, a sphere moved at the step before included (the
+            # few spheres such columns show can leave them once displaced) -- `moved` may then name a sphere twice
+            if x0:
+                frame = sc.render(w, h, cam=cam, aspect=inp.aspect, aov=GUIDES)
+            pick = _visible(frame, M.RT_HIT_SPHERE, movers, skip=() if x0 else moved, x0=x0)
             moved += pick
             sm = move_spheres(inp, {i: MOVES[(j + k) % 4] for j, i in enumerate(pick)})
             sc.set_spheres(inp.spheres, inp.n)
@@ -87,7 +92,7 @@ def _walk(rt, sc, inp, w, h, crop=None, cube=None, **kw):
             frame = _crop(frame, *crop)
         _step(rt, sc, frame, hist, cam, inp.aspect, sm, cm, clamp=False, **kw)
         hist, want = _step(rt, sc, frame, hist, cam, inp.aspect, sm, cm, clamp=True, **kw)
-        want["moved"] = list(moved)
+        want["moved"], want["picked"] = list(moved), list(pick) if sm is not None else []
         res.append(want)
     return res
 
@@ -141,6 +146,34 @@ def test_sizes_that_are_no_multiple_of_the_tiles(rt, gpu, w, h):
         y0, x0 = min(max(cy - h // 2, 0), 91 - h), min(max(cx - w // 2, 0), 322 - w)
         res = _walk(rt, sc, inp, 322, 91, crop=(slice(y0, y0 + h), slice(x0, x0 + w)))
         assert res[2]["has_history"].any()              # the repeated camera
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("w,h,movers", [(576, 36, 1), (1088, 36, 2)])
+def test_more_than_eight_tile_columns(rt, gpu, w, h, movers):
+    """tm_product has tp_product's grid, padded to a multiple of eight 64-pixel tile columns, and leaves in the tiles
+    of the padding; at every width up to 512 the padded width is 8 columns. Here 9 and 17 columns (16 and 24 padded),
+    along test_temporal_gpu's wide path, and the displaced spheres are picked among those seen in columns >= 512, so
+    that movers -- the reprojection with a displacement, the exchange between lanes, the clamp's staged tile -- run in
+    tiles of the second and third group under the moved and under the repeated camera. On CPU frames of the first two
+    cameras (test_temporal_cpu.View) columns >= 512 of 576 x 36 show two spheres, of 333 and 1 850 pixels under the
+    second camera, and the larger one fills them once displaced, which is why one sphere is displaced per step there
+    and the same sphere may be displaced again; with the restatement, 2 304 and 11 131 mover pixels in the camera step."""
+    inp = Inputs(rt, 256)
+    sc = _scene(rt, inp)
+    try:
+        res = _walk(rt, sc, inp, w, h, cams=_wide_path(rt), movers=movers, x0=512)
+        for k in (1, 2):
+            r, ids = res[k], res[k]["id"]
+            assert len(r["picked"]) == movers, (k, r["picked"])
+            mover = (ids[..., 0] == M.RT_HIT_SPHERE) & np.isin(ids[..., 1], r["picked"])
+            mover[:, :512] = False
+            assert mover.sum() > 20 and not r["static"][mover].any(), (k, int(mover.sum()))
+            print(w, "step", k, "mover pixels in columns >= 512:", int(mover.sum()), "with history:",
+                  int(r["has_history"][mover].sum()))
+        assert res[2]["has_history"][mover].any()              # the repeated camera: movers keep history
+        assert res[1]["has_history"][:, 512:].mean() > 0.1     # and so does the moved camera there
     finally:
         sc.close()
 

@@ -9,6 +9,7 @@ import denoise_ref as R
 import meshes
 import vdenoise_ref as V
 from scenes import Inputs, mixed_scene
+from test_temporal_cpu import WIDE_CAMS, WIDE_HIT_FLOOR, WIDE_SEGMENT
 
 pytestmark = pytest.mark.gpu
 
@@ -44,11 +45,14 @@ def _scene(rt, inp, mesh=None):
     return sc
 
 
-def _accumulate(rt, sc, inp, w, h):
-    """The last frame of the path and the history accumulated along it."""
+def _accumulate(rt, sc, inp, w, h, cams=None, colour=None):
+    """The last frame of the path (cams: of another one) and the history accumulated along it. colour(frame, k): what
+    is accumulated for frame k instead of the frame's own colour; the last frame then carries it as its rgba."""
     hist = None
-    for cam in _path(rt):
+    for k, cam in enumerate(_path(rt) if cams is None else cams):
         frame = sc.render(w, h, cam=cam, aspect=inp.aspect, aov=ALL)
+        if colour is not None:
+            frame = dict(frame, rgba=colour(frame, k))
         hist = sc.temporal(frame, hist, cam=cam, aspect=inp.aspect)
     return frame, hist
 
@@ -187,6 +191,58 @@ def test_960x540(rt, gpu):
         _check(sc, frame, hist, iterations=2)
         _check(sc, frame, hist, iterations=6, ref=False)
         _check(sc, frame, None, iterations=5, ref=False)
+    finally:
+        sc.close()
+
+
+def _ambient(frame, k):
+    """The frame's colour with an ambient term on every hit pixel: the albedo times a factor of the normal (0.05 ..
+    0.35) that also changes from frame to frame, so that no hit pixel is black and a held camera has temporal variance."""
+    import torch
+    a = frame["aov"]
+    shade = (0.2 + 0.15 * a["normal"][..., 1:2]) * (0.75 + 0.125 * ((5 * k) % 4))
+    c = frame["rgba"].clone()
+    c[..., :3] = torch.where(a["id"][..., :1] >= 0, c[..., :3] + shade * a["albedo"][..., :3], c[..., :3])
+    return c
+
+
+@pytest.mark.parametrize("colour", [None, _ambient], ids=["lights", "ambient"])
+def test_more_than_eight_row_segments(rt, gpu, colour):
+    """vd_iter_direct maps blockIdx.x to a 256-pixel row segment in groups of eight, seg = ((b >> 3) % nseg8) * 8 +
+    (b & 7): nseg8 is 1 at every width up to 2048. 2100 x 36 has 9 segments (nseg8 = 2), rendered at the size itself
+    along test_temporal_cpu's wide path (yaw 170) with the second camera held for four frames: on CPU frames the second
+    camera hits 0.68 of the pixels and 0.59 of columns >= 2048, and there 0.22 of the pixels keep history over the
+    camera step (0.38 of the valid ones). Those arrive with n = 5 and the others with n = 4, so min_history = 5 splits
+    the valid pixels there into temporal and spatial initial variances (measured on the device's history: 0.380 and
+    0.620 of the valid pixels there); each class is asserted to be 5 % of them at least. Iteration 5 puts
+    vd_iter_direct<true> at step 16 in one of variants 0 / 2; iteration 6 puts <false> at step 16 there and <true> at
+    step 32 in both.
+    No light reaches what columns >= 1920 show: every hit pixel there is black in the frame itself ("lights"), its
+    irradiance and variance 0 whatever the weights. "ambient" accumulates the same frames with an ambient term, so that
+    those columns carry colours and variances a wrong tap would change. On CPU frames the largest albedo channel of
+    every hit pixel there is 0.353 at least and its normal's y lies in [-0.81, 0.02], so the ambient term is 0.02 at
+    least in that channel (asserted below on the device's albedo as > 0); a filtered pixel is a mean of such values
+    with weights >= 0 and a centre weight > 0, which is why every hit pixel of the result there must be non-black."""
+    inp = Inputs(rt, 256)
+    sc = _scene(rt, inp)
+    try:
+        w, h, min_history = 2100, 36, 5
+        cams = [_cam(rt, *WIDE_CAMS[0])] + [_cam(rt, *WIDE_CAMS[1])] * 4
+        frame, hist = _accumulate(rt, sc, inp, w, h, cams, colour)
+        there = (slice(None), slice(WIDE_SEGMENT, None))
+        hit, long_, short = (m[there] for m in _classes(frame, hist, min_history))
+        shares = hit.mean(), long_.sum() / hit.sum(), short.sum() / hit.sum()
+        print("columns >= 2048: hit share, long and short share of the hit pixels:", shares)
+        assert shares[0] >= WIDE_HIT_FLOOR and shares[1] >= 0.05 and shares[2] >= 0.05, shares
+        for n in (5, 6):
+            with_history = _check(sc, frame, hist, iterations=n, min_history=min_history)
+            without = _check(sc, frame, None, iterations=n)
+            if colour is not None:
+                assert (frame["aov"]["albedo"].cpu().numpy()[there][hit][:, :3].max(axis=-1) > 0).all()
+                rgba, var = with_history[0][there].view(np.float32), with_history[2][there].view(np.float32)
+                assert (rgba[hit][:, :3].max(axis=-1) > 0).all() and (var[long_] > 0).any() and (var[short] > 0).any()
+                assert (with_history[0][there][hit] != _bits(hist["rgba"])[there][hit]).any()       # filtered there
+                assert (with_history[0][there] != without[0][there]).any()
     finally:
         sc.close()
 
