@@ -117,6 +117,8 @@ def load(libm: bool = False):
     lib.oracle_mesh_triangles.argtypes = [C.c_void_p]
     lib.oracle_mesh_box.restype = ci
     lib.oracle_mesh_box.argtypes = [C.c_void_p, ci, C.POINTER(cf), C.POINTER(cf), C.POINTER(C.POINTER(ci)), C.POINTER(ci)]
+    lib.oracle_mesh_split_leaves.restype = ci
+    lib.oracle_mesh_split_leaves.argtypes = [C.c_void_p, ci]
     lib.oracle_triangle_intersect.restype = ci
     lib.oracle_triangle_intersect.argtypes = [C.POINTER(OTriangle), C.POINTER(ORay), C.POINTER(cf), C.POINTER(cf), C.POINTER(cf)]
     lib.oracle_msvc_srand.restype = None
@@ -197,6 +199,16 @@ class Mesh:
         pc, bc, hn = C.c_int(), C.c_int(), C.c_int()
         self.lib.oracle_mesh_counts(self.handle, C.byref(pc), C.byref(bc), C.byref(hn))
         self.poly_count, self.bvhbox_count, self.has_normals = pc.value, bc.value, bool(hn.value)
+
+    def split_leaves(self, max_len: int):
+        """Every leaf becomes consecutive leaves of at most max_len triangles (oracle_mesh_split_leaves): a mesh
+        with more leaves than the loader's ten passes can make. Returns self."""
+        if self.lib.oracle_mesh_split_leaves(self.handle, max_len) != 0:
+            raise ValueError("oracle_mesh_split_leaves refused max_len = %r" % (max_len,))
+        bc = C.c_int()
+        self.lib.oracle_mesh_counts(self.handle, None, C.byref(bc), None)
+        self.bvhbox_count = bc.value
+        return self
 
     def triangles(self):
         ptr = self.lib.oracle_mesh_triangles(self.handle)

@@ -112,6 +112,9 @@ void oracle_mesh_free(o_mesh *m);
 int oracle_mesh_counts(const o_mesh *m, int *poly_count, int *bvhbox_count, int *has_normals);
 const o_triangle *oracle_mesh_triangles(const o_mesh *m);
 int oracle_mesh_box(const o_mesh *m, int j, float bounds[6], float orgin[3], const int **indexes, int *length);
+/* test aid: replace every leaf by consecutive leaves of at most max_len triangles (same order, bounds by
+ * createBvhMesh's rule) -- more leaves than the ten passes can make. Returns 0 on success. */
+int oracle_mesh_split_leaves(o_mesh *m, int max_len);
 int oracle_triangle_intersect(const o_triangle *tri, const o_ray *r, float *t, float *u, float *v); /* :1024-1059 */
 /* MSVC rand() replay + scene generator (kernel.cu:1189-1192). */
 void oracle_msvc_srand(unsigned int seed);

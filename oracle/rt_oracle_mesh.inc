@@ -291,6 +291,32 @@ int oracle_mesh_box(const o_mesh *m, int j, float bounds[6], float orgin[3], con
     return 0;
 }
 
+/* Test aid, not a restatement: every leaf becomes consecutive leaves of at most max_len triangles, in the same
+ * order, each with the bounds createBvhMesh gives a leaf of those triangles (first vertex of its first and last
+ * triangle, grown by getMinMaxP). A mesh of more leaves than the ten passes can make (2^10), which a caller may
+ * still hand to the product. The new leaves point into the old index arrays. */
+int oracle_mesh_split_leaves(o_mesh *m, int max_len)
+{
+    if (!m || max_len < 1) return 1;
+    const o_triangle *T = m->tris;
+    vecbuf out;
+    vb_init(&out, sizeof(bvhbox_t));
+    for (int j = 0; j < m->bvhbox_count; j++) {
+        const bvhbox_t *b = &m->boxes[j];
+        for (int c0 = 0; c0 < b->length; c0 += max_len) {
+            int *idx = b->indexes + c0;
+            int len = b->length - c0 < max_len ? b->length - c0 : max_len;
+            vec3d low = T[idx[0]].points[0], high = T[idx[len - 1]].points[0];
+            for (int z = 0; z < len; z++) getMinMaxP(&T[idx[z]], &low, &high);
+            *(bvhbox_t *)vb_push(&out) = make_box(low, high, idx, len);
+        }
+    }
+    free(m->boxes);
+    m->boxes = (bvhbox_t *)out.p;
+    m->bvhbox_count = out.n;
+    return 0;
+}
+
 /* mesh::rayIntersect (Moller-Trumbore), kernel.cu:1024-1059 */
 static int rayIntersect(const ray *r, const o_triangle *tri, float *t, float *u, float *v)
 {

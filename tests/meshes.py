@@ -35,6 +35,62 @@ def uv_sphere_obj(cx=4.0, cy=2.0, cz=5.0, r=1.6, n_lat=10, n_lon=16, quads=True)
     return "\n".join(lines) + "\n"
 
 
+FAN_SIZES = (150, 63, 127, 64, 126, 70, 5, 1)
+
+
+def fan_hub(k, x0=0.0, y0=0.0, z0=6.0, pitch=1.6, dz=0.45):
+    """Hub of fan k: a 3-wide grid in x and y, every fan a step farther in z. The first six take their places down
+    the columns of the first two rows: that is the order in which the loader's cuts (y, x, z, ...) leave them, so
+    leaf k is fan k (asserted on the CPU, tests/test_mesh_large_cpu.py)."""
+    slot = (k % 2) * 3 + k // 2 if k < 6 else k
+    return (x0 + pitch * (slot % 3), y0 + pitch * (slot // 3), z0 + dz * k)
+
+
+def fans_obj(sizes=FAN_SIZES, normals=False, rim=0.7, **grid):
+    """One triangle fan per entry of `sizes`, every triangle (hub, rim i, rim i + 1): the loader's split sorts
+    triangles by their FIRST vertex, so a fan is never cut and becomes one leaf of exactly its length, the triangles
+    in the order written. The fans face -z (hub raised towards the viewer: a shallow cone) and their rims wave and zigzag
+    in z, so that no two neighbouring triangles are coplanar. Every run of 63 triangles -- what a tile takes at a time --
+    shares an equal part of the circle among its members (a member's part at most a sixth before the parts are
+    scaled to the whole): the one triangle at position 63 of a fan of 64, or 126 of 127, is wide and shows in a
+    small frame. `normals`: vn lines and a//c faces (per-vertex normals, no vt)."""
+    lines = ["# triangle fans of %s" % (list(sizes),)]
+    faces = []
+    nv = nn = 0
+    for k, n in enumerate(sizes):
+        hx, hy, hz = fan_hub(k, **grid)
+        chunks = (n + 62) // 63
+        wts = [min(1.0 / (chunks * min(63, n - i // 63 * 63)), 1.0 / 6) for i in range(n)]
+        span = 2 * math.pi * (1.0 if n >= 3 else n / 3.0)
+        lines.append("v %.6f %.6f %.6f" % (hx, hy, hz - 0.25))
+        hub = nv = nv + 1
+        first = nv + 1
+        acc = 0.0
+        for i in range(n + 1):
+            th = span * acc / sum(wts) + 0.3 * k
+            r = rim * (1 + 0.06 * math.sin(5 * th))
+            step = span * wts[min(i, n - 1)] / sum(wts)
+            zig = 0.05 * rim * step * (1 if i % 2 else -1)     # a crease at every spoke, whatever the waves do there
+            lines.append("v %.6f %.6f %.6f" % (hx + r * math.cos(th), hy + r * math.sin(th),
+                                               hz + 0.09 * math.sin(7 * th + k) + 0.04 * math.cos(31 * th) + zig))
+            nv += 1
+            acc += wts[i] if i < n else 0
+        if normals:
+            # the hub's normal and one per rim vertex, leaning outwards: interpolated normals differ across a triangle
+            lines.append("vn 0 0 -1")
+            nn += 1
+            hub_n = nn
+            for i in range(n + 1):
+                th = span * i / max(n, 1)
+                lines.append("vn %.6f %.6f %.6f" % (0.5 * math.cos(th), 0.5 * math.sin(th), -1.0))
+                nn += 1
+            for i in range(n):
+                faces.append("f %d//%d %d//%d %d//%d" % (hub, hub_n, first + i, hub_n + 1 + i, first + i + 1, hub_n + 2 + i))
+        else:
+            faces += ["f %d %d %d" % (hub, first + i, first + i + 1) for i in range(n)]
+    return "\n".join(lines + faces) + "\n"
+
+
 def box_obj_no_normals(x0=1.0, y0=0.0, z0=6.0, s=1.5):
     """A box as 12 bare-index triangles (no vn / vt): the loader's third branch."""
     v = [(x0, y0, z0), (x0 + s, y0, z0), (x0 + s, y0 + s, z0), (x0, y0 + s, z0),

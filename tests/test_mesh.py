@@ -15,6 +15,11 @@ OBJS = {
     "box_bare_indices": meshes.box_obj_no_normals(),
     "normals_only_quad": meshes.normals_only_obj(),
     "with_blank_and_comment_lines": "# c\n\nv 0 0 0\nv 1 0 0\n\nv 0 1 0\r\nf 1 2 3\n",
+    # large enough for the size-dependent paths of the frame kernel (tests/test_mesh_large_*.py): loader only here
+    "fans": meshes.fans_obj(),
+    "fans_normals": meshes.fans_obj(normals=True),
+    "uv_sphere_24x40": meshes.uv_sphere_obj(n_lat=24, n_lon=40),
+    "uv_sphere_40x64": meshes.uv_sphere_obj(n_lat=40, n_lon=64),
 }
 
 
