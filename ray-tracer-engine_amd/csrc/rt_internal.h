@@ -227,14 +227,18 @@ const char *rt_frame_aov_field(const rt_frame_desc *fd);
 // a caller's frame description in this build's layout (what its struct_size fields do not cover reads as 0)
 void normalise_frame_desc(const rt_frame_desc *fd, rt_frame_desc *out);
 
-// rt_denoise.hip: the G-buffer-guided denoiser (d: validated, in this build's layout; the scene's scratch, room for
-// width * height pixels each; ev: null, or iterations + 2 timing events)
-int rt_denoise_launch(const rt_denoise_desc *d, float4 *col0, float4 *col1, float4 *guide, int *key, hipEvent_t *ev,
+// rt_denoise.hip: the two a-trous denoisers, one set of kernels. Both public descriptions in one layout:
+// rt_vdenoise_desc's fields, which rt_denoise_desc's are among, and which filter. `plain`: rt_scene_denoise's (a uniform
+// colour threshold sigma_colour, none if it is <= 0; moments, variance_out, sigma_floor, min_history and spatial_boost
+// are not read).
+struct RtAtrousDesc : rt_vdenoise_desc {
+    bool plain;
+};
+// d: validated; the scene's scratch, room for width * height pixels each; ev: null, or iterations + 2 timing events
+int rt_denoise_launch(const RtAtrousDesc *d, float4 *col0, float4 *col1, float4 *guide, int *key, hipEvent_t *ev,
                       hipStream_t stream);
-
-// rt_vdenoise.hip: the variance-guided denoiser (d: validated, in this build's layout; the scene's scratch, room for
-// width * height pixels each; lds16: step 16 runs the LDS-staged kernel; ev: null, or iterations + 3 timing events)
-int rt_vdenoise_launch(const rt_vdenoise_desc *d, float4 *col0, float4 *col1, float4 *guide, int *key, float *var0,
+// the variance-guided one: lds16: step 16 runs the LDS-staged kernel; ev: null, or iterations + 3 timing events
+int rt_vdenoise_launch(const RtAtrousDesc *d, float4 *col0, float4 *col1, float4 *guide, int *key, float *var0,
                        float *var1, bool lds16, hipEvent_t *ev, hipStream_t stream);
 
 // rt_temporal.hip: temporal accumulation (d: validated, in this build's layout; dx_tab / dy_tab: the current view's ray

@@ -530,8 +530,14 @@ extern "C" int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd_in, rt
 }
 
 // ---------------------------------------------------------------------------
-// the G-buffer-guided denoiser (rt_denoise.hip)
+// the two a-trous denoisers (rt_denoise.hip): the G-buffer-guided one and the variance-guided one
+// (DESIGN.md 6j). One host path, denoise_call; each keeps its own timing state
 // ---------------------------------------------------------------------------
+// Which kernel runs step 16 in the variance-guided variant 0 (variant 2 runs the other): the LDS-staged one (61 440 B),
+// by the measurement of DESIGN.md 6j -- equal to the direct one at 3840 x 2160 (0.425 against 0.423 ms), 1.32 times
+// faster at 960 x 540.
+static const bool kVdenoiseLds16 = true;
+
 extern "C" void rt_denoise_desc_init(rt_denoise_desc *d)
 {
     if (!d) return;
@@ -543,99 +549,6 @@ extern "C" void rt_denoise_desc_init(rt_denoise_desc *d)
     d->sigma_colour = 0.f;
     d->demodulate = 1;
 }
-
-extern "C" int rt_scene_denoise(rt_scene *s, const rt_denoise_desc *d_in, void *stream_)
-{
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!s || !d_in) {
-        rt_set_error("rt_scene_denoise: null scene or description");
-        return RT_ERR_INVALID;
-    }
-    rt_denoise_desc d;
-    as_built(d_in, &d);
-    const char *bad = nullptr;
-    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
-        bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
-    else if (!d.rgba_in || !d.depth || !d.normal || !d.id || !d.rgba_out) bad = "rgba_in, depth, normal, id and rgba_out must not be NULL";
-    else if (d.demodulate && !d.albedo) bad = "demodulate needs albedo";
-    else if ((((uintptr_t)d.rgba_in | (uintptr_t)d.normal | (uintptr_t)d.albedo | (uintptr_t)d.rgba_out) & 15u) ||
-             ((uintptr_t)d.id & 7u) || (((uintptr_t)d.depth | (uintptr_t)d.pixels) & 3u))
-        bad = "rgba_in, normal, albedo and rgba_out must be 16-byte aligned, id 8-byte, depth and pixels 4-byte";
-    else if (d.iterations < 1 || d.iterations > RT_DENOISE_MAX_ITERATIONS) bad = "iterations is not in [1, RT_DENOISE_MAX_ITERATIONS]";
-    else if (d.normal_shift < 0 || d.normal_shift > RT_DENOISE_MAX_NORMAL_SHIFT) bad = "normal_shift is not in [0, RT_DENOISE_MAX_NORMAL_SHIFT]";
-    else if (!(d.sigma_depth > 0.f) || !std::isfinite(d.sigma_depth)) bad = "sigma_depth is not finite and > 0";
-    else if (!std::isfinite(d.sigma_colour)) bad = "sigma_colour is not finite";
-    else if (d.variant < 0 || d.variant > 2) bad = "variant is not 0, 1 or 2";
-    if (bad) {
-        rt_set_error("rt_scene_denoise: %s (%d x %d, iterations %d, normal_shift %d, variant %d)", bad, d.width, d.height,
-                     d.iterations, d.normal_shift, d.variant);
-        return RT_ERR_INVALID;
-    }
-    if (stream_capturing(stream)) {
-        rt_set_error("rt_scene_denoise: the stream is being captured (the denoiser is not recorded into graphs)");
-        return RT_ERR_UNSUPPORTED;
-    }
-    const size_t npx = (size_t)d.width * d.height;
-    if (npx > s->dn_col[0].capacity() || npx > s->dn_col[1].capacity() ||
-        (d.variant != 1 && (npx > s->dn_guide.capacity() || npx > s->dn_key.capacity()))) {
-        // growing releases the old buffers: after the host has seen the last call that used them end
-        RT_HIP(s->dn_done.host_wait());
-        RT_HIP(s->dn_col[0].reserve(npx));
-        RT_HIP(s->dn_col[1].reserve(npx));
-        if (d.variant != 1) {
-            RT_HIP(s->dn_guide.reserve(npx));
-            RT_HIP(s->dn_key.reserve(npx));
-        }
-    }
-    RT_HIP(s->dn_done.order(stream));   // one scratch: one call at a time
-    hipEvent_t ev[RT_DENOISE_MAX_ITERATIONS + 2];
-    s->dn_timed = 0;
-    if (s->dn_timing) {
-        for (int i = 0; i < RT_DENOISE_MAX_ITERATIONS + 2; ++i) {
-            RT_HIP(s->dn_ev[i].create(hipEventDefault));
-            ev[i] = s->dn_ev[i].get();
-        }
-    }
-    const int rc = rt_denoise_launch(&d, s->dn_col[0].get(), s->dn_col[1].get(), s->dn_guide.get(), s->dn_key.get(),
-                                     s->dn_timing ? ev : nullptr, stream);
-    // also after a launch that failed half way: what was enqueued uses the scratch
-    RT_HIP(s->dn_done.record(stream));
-    if (rc == RT_OK && s->dn_timing) s->dn_timed = d.iterations + (d.variant == 1 ? 1 : 2);
-    return rc;
-}
-
-extern "C" int rt_scene_set_denoise_timing(rt_scene *s, int on)
-{
-    if (!s) {
-        rt_set_error("rt_scene_set_denoise_timing: null scene");
-        return RT_ERR_INVALID;
-    }
-    s->dn_timing = on != 0;
-    return RT_OK;
-}
-
-extern "C" int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n)
-{
-    if (!s || !ms || !n || cap < 0) {
-        rt_set_error("rt_scene_denoise_times: null argument");
-        return RT_ERR_INVALID;
-    }
-    *n = 0;
-    if (s->dn_timed < 2) return RT_OK;
-    RT_HIP(s->dn_done.host_wait());
-    for (int i = 0; i + 1 < s->dn_timed && i < cap; ++i) {
-        RT_HIP(hipEventElapsedTime(&ms[i], s->dn_ev[i].get(), s->dn_ev[i + 1].get()));
-        *n = i + 1;
-    }
-    return RT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// the variance-guided denoiser (rt_vdenoise.hip)
-// ---------------------------------------------------------------------------
-// Which kernel runs step 16 in variant 0 (variant 2 runs the other): the LDS-staged one (61 440 B), by the measurement
-// of DESIGN.md 6j -- equal to the direct one at 3840 x 2160 (0.425 against 0.423 ms), 1.32 times faster at 960 x 540.
-static const bool kVdenoiseLds16 = true;
 
 extern "C" void rt_vdenoise_desc_init(rt_vdenoise_desc *d)
 {
@@ -652,15 +565,31 @@ extern "C" void rt_vdenoise_desc_init(rt_vdenoise_desc *d)
     d->demodulate = 1;
 }
 
-extern "C" int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d_in, void *stream_)
+// What the two public descriptions share, field by field (their layouts part after `pixels`); the rest is 0.
+template <typename D>
+static RtAtrousDesc atrous_desc(const D &d, bool plain)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!s || !d_in) {
-        rt_set_error("rt_scene_denoise_variance: null scene or description");
-        return RT_ERR_INVALID;
-    }
-    rt_vdenoise_desc d;
-    as_built(d_in, &d);
+    RtAtrousDesc a = {};
+    a.struct_size = (uint32_t)sizeof(rt_vdenoise_desc);
+    a.width = d.width; a.height = d.height;
+    a.rgba_in = d.rgba_in;
+    a.depth = d.depth; a.normal = d.normal; a.albedo = d.albedo; a.id = d.id;
+    a.rgba_out = d.rgba_out;
+    a.pixels = d.pixels;
+    a.iterations = d.iterations;
+    a.normal_shift = d.normal_shift;
+    a.sigma_depth = d.sigma_depth;
+    a.sigma_colour = d.sigma_colour;
+    a.demodulate = d.demodulate;
+    a.variant = d.variant;
+    a.plain = plain;
+    return a;
+}
+
+// Both denoise entries. d: in this build's layout (`name` for the messages). Only rt_scene_denoise_variance checks its
+// buffers for overlaps.
+static int denoise_call(rt_scene *s, const RtAtrousDesc &d, const char *name, hipStream_t stream)
+{
     struct Range {
         uintptr_t p;
         size_t bytes;
@@ -673,16 +602,18 @@ extern "C" int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d_
     else if ((((uintptr_t)d.rgba_in | (uintptr_t)d.normal | (uintptr_t)d.albedo | (uintptr_t)d.rgba_out) & 15u) ||
              (((uintptr_t)d.id | (uintptr_t)d.moments) & 7u) ||
              (((uintptr_t)d.depth | (uintptr_t)d.pixels | (uintptr_t)d.variance_out) & 3u))
-        bad = "rgba_in, normal, albedo and rgba_out must be 16-byte aligned, id and moments 8-byte, depth, pixels and variance_out 4-byte";
+        bad = d.plain ? "rgba_in, normal, albedo and rgba_out must be 16-byte aligned, id 8-byte, depth and pixels 4-byte"
+                      : "rgba_in, normal, albedo and rgba_out must be 16-byte aligned, id and moments 8-byte, depth, pixels and variance_out 4-byte";
     else if (d.iterations < 1 || d.iterations > RT_DENOISE_MAX_ITERATIONS) bad = "iterations is not in [1, RT_DENOISE_MAX_ITERATIONS]";
     else if (d.normal_shift < 0 || d.normal_shift > RT_DENOISE_MAX_NORMAL_SHIFT) bad = "normal_shift is not in [0, RT_DENOISE_MAX_NORMAL_SHIFT]";
     else if (!(d.sigma_depth > 0.f) || !std::isfinite(d.sigma_depth)) bad = "sigma_depth is not finite and > 0";
-    else if (!(d.sigma_colour >= 0.f && d.sigma_colour <= 1048576.f)) bad = "sigma_colour is not in [0, 2^20]";
-    else if (!(d.sigma_floor > 0.f) || !std::isfinite(d.sigma_floor)) bad = "sigma_floor is not finite and > 0";
-    else if (d.min_history < 1 || d.min_history > RT_TEMPORAL_MAX_HISTORY) bad = "min_history is not in [1, RT_TEMPORAL_MAX_HISTORY]";
-    else if (!(d.spatial_boost >= 0.f) || !std::isfinite(d.spatial_boost)) bad = "spatial_boost is not finite and >= 0";
+    else if (d.plain && !std::isfinite(d.sigma_colour)) bad = "sigma_colour is not finite";
+    else if (!d.plain && !(d.sigma_colour >= 0.f && d.sigma_colour <= 1048576.f)) bad = "sigma_colour is not in [0, 2^20]";
+    else if (!d.plain && (!(d.sigma_floor > 0.f) || !std::isfinite(d.sigma_floor))) bad = "sigma_floor is not finite and > 0";
+    else if (!d.plain && (d.min_history < 1 || d.min_history > RT_TEMPORAL_MAX_HISTORY)) bad = "min_history is not in [1, RT_TEMPORAL_MAX_HISTORY]";
+    else if (!d.plain && (!(d.spatial_boost >= 0.f) || !std::isfinite(d.spatial_boost))) bad = "spatial_boost is not finite and >= 0";
     else if (d.variant < 0 || d.variant > 2) bad = "variant is not 0, 1 or 2";
-    else {
+    else if (!d.plain) {
         const size_t npx = (size_t)d.width * d.height;
         const Range outs[3] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.pixels, npx * 4}, {(uintptr_t)d.variance_out, npx * 4}};
         const Range ins[6] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16},
@@ -697,71 +628,135 @@ extern "C" int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d_
         }
     }
     if (bad) {
-        rt_set_error("rt_scene_denoise_variance: %s (%d x %d, iterations %d, normal_shift %d, min_history %d, variant %d)", bad,
-                     d.width, d.height, d.iterations, d.normal_shift, d.min_history, d.variant);
+        if (d.plain)
+            rt_set_error("%s: %s (%d x %d, iterations %d, normal_shift %d, variant %d)", name, bad, d.width, d.height, d.iterations,
+                         d.normal_shift, d.variant);
+        else
+            rt_set_error("%s: %s (%d x %d, iterations %d, normal_shift %d, min_history %d, variant %d)", name, bad, d.width,
+                         d.height, d.iterations, d.normal_shift, d.min_history, d.variant);
         return RT_ERR_INVALID;
     }
     if (stream_capturing(stream)) {
-        rt_set_error("rt_scene_denoise_variance: the stream is being captured (the denoiser is not recorded into graphs)");
+        rt_set_error("%s: the stream is being captured (the denoiser is not recorded into graphs)", name);
         return RT_ERR_UNSUPPORTED;
     }
     const size_t npx = (size_t)d.width * d.height;
-    if (npx > s->dn_col[0].capacity() || npx > s->dn_col[1].capacity() || npx > s->vd_var[0].capacity() ||
-        npx > s->vd_var[1].capacity() || (d.variant != 1 && (npx > s->dn_guide.capacity() || npx > s->dn_key.capacity()))) {
+    if (npx > s->dn_col[0].capacity() || npx > s->dn_col[1].capacity() ||
+        (!d.plain && (npx > s->vd_var[0].capacity() || npx > s->vd_var[1].capacity())) ||
+        (d.variant != 1 && (npx > s->dn_guide.capacity() || npx > s->dn_key.capacity()))) {
         // growing releases the old buffers: after the host has seen the last call that used them end
         RT_HIP(s->dn_done.host_wait());
         RT_HIP(s->dn_col[0].reserve(npx));
         RT_HIP(s->dn_col[1].reserve(npx));
-        RT_HIP(s->vd_var[0].reserve(npx));
-        RT_HIP(s->vd_var[1].reserve(npx));
+        if (!d.plain) {
+            RT_HIP(s->vd_var[0].reserve(npx));
+            RT_HIP(s->vd_var[1].reserve(npx));
+        }
         if (d.variant != 1) {
             RT_HIP(s->dn_guide.reserve(npx));
             RT_HIP(s->dn_key.reserve(npx));
         }
     }
-    RT_HIP(s->dn_done.order(stream));   // one scratch, shared with rt_scene_denoise: one call at a time
-    constexpr int kEvents = RT_DENOISE_MAX_ITERATIONS + 3;
-    hipEvent_t ev[kEvents];
-    s->vd_timed = 0;
-    if (s->vd_timing) {
-        for (int i = 0; i < kEvents; ++i) {
-            RT_HIP(s->vd_ev[i].create(hipEventDefault));
-            ev[i] = s->vd_ev[i].get();
+    RT_HIP(s->dn_done.order(stream));   // one scratch for both entries: one call at a time
+    // each entry has its timing state: rt_scene_denoise_times reports the last plain call, whatever came after it
+    HipEvent *const timer = d.plain ? s->dn_ev : s->vd_ev;
+    const bool timing = d.plain ? s->dn_timing : s->vd_timing;
+    int &timed = d.plain ? s->dn_timed : s->vd_timed;
+    // events beside one per iteration: before the first launch, after the pack (not in variant 1), after the variance's
+    // spatial estimate / v_0
+    const int extra = d.plain ? 2 : 3;
+    hipEvent_t ev[RT_DENOISE_MAX_ITERATIONS + 3];
+    timed = 0;
+    if (timing) {
+        for (int i = 0; i < RT_DENOISE_MAX_ITERATIONS + extra; ++i) {
+            RT_HIP(timer[i].create(hipEventDefault));
+            ev[i] = timer[i].get();
         }
     }
-    const bool lds16 = (d.variant == 2) != kVdenoiseLds16;
-    const int rc = rt_vdenoise_launch(&d, s->dn_col[0].get(), s->dn_col[1].get(), s->dn_guide.get(), s->dn_key.get(),
-                                      s->vd_var[0].get(), s->vd_var[1].get(), lds16, s->vd_timing ? ev : nullptr, stream);
+    const int rc = d.plain ? rt_denoise_launch(&d, s->dn_col[0].get(), s->dn_col[1].get(), s->dn_guide.get(), s->dn_key.get(),
+                                               timing ? ev : nullptr, stream)
+                           : rt_vdenoise_launch(&d, s->dn_col[0].get(), s->dn_col[1].get(), s->dn_guide.get(), s->dn_key.get(),
+                                                s->vd_var[0].get(), s->vd_var[1].get(), (d.variant == 2) != kVdenoiseLds16,
+                                                timing ? ev : nullptr, stream);
     // also after a launch that failed half way: what was enqueued uses the scratch
     RT_HIP(s->dn_done.record(stream));
-    if (rc == RT_OK && s->vd_timing) s->vd_timed = d.iterations + (d.variant == 1 ? 2 : 3);
+    if (rc == RT_OK && timing) timed = d.iterations + extra - (d.variant == 1 ? 1 : 0);
     return rc;
+}
+
+extern "C" int rt_scene_denoise(rt_scene *s, const rt_denoise_desc *d_in, void *stream_)
+{
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_denoise: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_denoise_desc d;
+    as_built(d_in, &d);
+    return denoise_call(s, atrous_desc(d, true), "rt_scene_denoise", (hipStream_t)stream_);
+}
+
+extern "C" int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d_in, void *stream_)
+{
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_denoise_variance: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_vdenoise_desc d;
+    as_built(d_in, &d);
+    RtAtrousDesc a = atrous_desc(d, false);
+    a.moments = d.moments;
+    a.variance_out = d.variance_out;
+    a.sigma_floor = d.sigma_floor;
+    a.min_history = d.min_history;
+    a.spatial_boost = d.spatial_boost;
+    return denoise_call(s, a, "rt_scene_denoise_variance", (hipStream_t)stream_);
+}
+
+static int denoise_set_timing(rt_scene *s, const char *name, bool rt_scene::*timing, int on)
+{
+    if (!s) {
+        rt_set_error("%s: null scene", name);
+        return RT_ERR_INVALID;
+    }
+    s->*timing = on != 0;
+    return RT_OK;
+}
+
+// ms[i]: between events i and i + 1 of the `timed` events the entry's last timed call recorded
+static int denoise_times(rt_scene *s, const char *name, const HipEvent *ev, int timed, float *ms, int cap, int *n)
+{
+    if (!s || !ms || !n || cap < 0) {
+        rt_set_error("%s: null argument", name);
+        return RT_ERR_INVALID;
+    }
+    *n = 0;
+    if (timed < 2) return RT_OK;
+    RT_HIP(s->dn_done.host_wait());
+    for (int i = 0; i + 1 < timed && i < cap; ++i) {
+        RT_HIP(hipEventElapsedTime(&ms[i], ev[i].get(), ev[i + 1].get()));
+        *n = i + 1;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_scene_set_denoise_timing(rt_scene *s, int on)
+{
+    return denoise_set_timing(s, "rt_scene_set_denoise_timing", &rt_scene::dn_timing, on);
+}
+
+extern "C" int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    return denoise_times(s, "rt_scene_denoise_times", s ? s->dn_ev : nullptr, s ? s->dn_timed : 0, ms, cap, n);
 }
 
 extern "C" int rt_scene_set_vdenoise_timing(rt_scene *s, int on)
 {
-    if (!s) {
-        rt_set_error("rt_scene_set_vdenoise_timing: null scene");
-        return RT_ERR_INVALID;
-    }
-    s->vd_timing = on != 0;
-    return RT_OK;
+    return denoise_set_timing(s, "rt_scene_set_vdenoise_timing", &rt_scene::vd_timing, on);
 }
 
 extern "C" int rt_scene_vdenoise_times(rt_scene *s, float *ms, int cap, int *n)
 {
-    if (!s || !ms || !n || cap < 0) {
-        rt_set_error("rt_scene_vdenoise_times: null argument");
-        return RT_ERR_INVALID;
-    }
-    *n = 0;
-    if (s->vd_timed < 2) return RT_OK;
-    RT_HIP(s->dn_done.host_wait());
-    for (int i = 0; i + 1 < s->vd_timed && i < cap; ++i) {
-        RT_HIP(hipEventElapsedTime(&ms[i], s->vd_ev[i].get(), s->vd_ev[i + 1].get()));
-        *n = i + 1;
-    }
-    return RT_OK;
+    return denoise_times(s, "rt_scene_vdenoise_times", s ? s->vd_ev : nullptr, s ? s->vd_timed : 0, ms, cap, n);
 }
 
 // ---------------------------------------------------------------------------

@@ -161,7 +161,7 @@ struct rt_scene {
     int view_last = -1;                      // the slot the last launch read, -1: it read none
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
     std::unique_ptr<RtReflect, RtReflectDeleter> refl;
-    // the denoiser's scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand; `dn_done`
+    // the two denoisers' scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand; `dn_done`
     // orders the scene's denoise calls on the device, whatever their streams
     DevArray<float4> dn_col[2], dn_guide;
     DevArray<int> dn_key;
@@ -169,7 +169,7 @@ struct rt_scene {
     HipEvent dn_ev[RT_DENOISE_MAX_ITERATIONS + 2];   // rt_scene_set_denoise_timing
     bool dn_timing = false;
     int dn_timed = 0;                                // events the last timed call recorded
-    // the variance-guided denoiser (rt_vdenoise.hip) uses the scratch above and `dn_done`, plus two variance arrays
+    // the variance-guided denoiser uses the scratch above and `dn_done`, plus two variance arrays and timing state of its own
     DevArray<float> vd_var[2];
     HipEvent vd_ev[RT_DENOISE_MAX_ITERATIONS + 3];   // rt_scene_set_vdenoise_timing
     bool vd_timing = false;

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "rt_cast.h"
+#include "rt_filter.h"
 #include "rt_internal.h"
 
 namespace {
@@ -56,27 +57,16 @@ struct TpSum {
     float r, g, b, n, m1, m2, w;
 };
 
-__device__ __forceinline__ float tp_luma(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-// float -> int as the frame kernel's f2i and rgbToInt (kernel.cu:547-556), the denoiser's pack
-__device__ __forceinline__ uint32_t tp_pack_colour(float r, float g, float b)
-{
-    int ir = (int)(r * 254.f), ig = (int)(g * 254.f), ib = (int)(b * 254.f);
-    if (ir > 255) ir = 255;
-    if (ig > 255) ig = 255;
-    if (ib > 255) ib = 255;
-    return (uint32_t)(((ir & 0xff) << 16) + ((ig & 0xff) << 8) + (ib & 0xff));
-}
-
 __device__ __forceinline__ void tp_write(const TpArgs &a, size_t p, float r, float g, float b, float n, float m1, float m2)
 {
     a.rgba_out[p] = make_float4(r, g, b, n);
     if (a.moments_out) a.moments_out[p] = make_float2(m1, m2);
-    if (a.pixels) a.pixels[p] = tp_pack_colour(r, g, b);
+    if (a.pixels) a.pixels[p] = im_pack_colour(r, g, b);
 }
 // a pixel without history: (c, 1), moments (Y, Y Y)
 __device__ __forceinline__ void tp_write_new(const TpArgs &a, size_t p, float4 c)
 {
-    const float y = tp_luma(c.x, c.y, c.z);
+    const float y = im_luma(c.x, c.y, c.z);
     tp_write(a, p, c.x, c.y, c.z, 1.f, y, y * y);
 }
 
@@ -159,7 +149,7 @@ __device__ __forceinline__ void tp_finish(const TpArgs &a, size_t p, float4 c, c
     float m1 = 0.f, m2 = 0.f;
     if (a.moments_out) {
         const float h1 = s.m1 / s.w, h2 = s.m2 / s.w;
-        const float y = tp_luma(c.x, c.y, c.z);
+        const float y = im_luma(c.x, c.y, c.z);
         m1 = h1 + (y - h1) * al;
         m2 = h2 + (y * y - h2) * al;
     }
@@ -445,7 +435,7 @@ __device__ __forceinline__ void tm_finish(const TmArgs &a, size_t p, float4 c, c
     float m1 = 0.f, m2 = 0.f;
     if (t.moments_out) {
         const float h1 = s.m1 / s.w, h2 = s.m2 / s.w;
-        const float y = tp_luma(c.x, c.y, c.z);
+        const float y = im_luma(c.x, c.y, c.z);
         m1 = h1 + (y - h1) * al;
         m2 = h2 + (y * y - h2) * al;
     }

@@ -350,7 +350,7 @@ def test_primary_rays_of_a_band(rt, scene):
 # ----------------------------------------------------------------------------- denoise and temporal
 SIZES = [(64, 1), (1, 64), (5, 5), (65, 9), (161, 91)]
 # Beyond the first group of eight: 17 tile columns of 64 for the two temporal product kernels, whose grid
-# is padded to a multiple of eight columns; 9 row segments of 256 for vd_iter_direct, which walks them in groups of eight.
+# is padded to a multiple of eight columns; 9 row segments of 256 for dn_iter_direct, which walks them in groups of eight.
 WIDE_TEMPORAL, WIDE_DENOISE = (1088, 5), (2100, 3)
 
 

@@ -50,12 +50,12 @@ class View:
 
 # The wide path: the GPU tests' path with the yaw turned to 170, for buffers of more than eight tile
 # columns (tp_product / tm_product pad their grid to a multiple of eight 64-pixel columns) and of more than eight
-# 256-pixel row segments (vd_iter_direct). With yaw 180 columns 512 .. 575 of a 576 x 36 frame show no sphere at all.
+# 256-pixel row segments (dn_iter_direct). With yaw 180 columns 512 .. 575 of a 576 x 36 frame show no sphere at all.
 WIDE_CAMS = ((4, 3, 10, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.7, 3.1, 10.1, 166, -21))
 WIDE_BLOCK = 64                 # a tile column of the two temporal product kernels
 WIDE_FIRST = 8                  # the first tile column outside the first group of eight
 WIDE_HISTORY_FLOOR = 0.1        # of every such column's pixels, in the moved-camera step
-WIDE_SEGMENT = 2048             # the first column of vd_iter_direct's second group of eight row segments
+WIDE_SEGMENT = 2048             # the first column of dn_iter_direct's second group of eight row segments
 WIDE_HIT_FLOOR = 0.3            # of the pixels from there on, for the second camera
 
 

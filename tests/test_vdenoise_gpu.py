@@ -208,15 +208,15 @@ def _ambient(frame, k):
 
 @pytest.mark.parametrize("colour", [None, _ambient], ids=["lights", "ambient"])
 def test_more_than_eight_row_segments(rt, gpu, colour):
-    """vd_iter_direct maps blockIdx.x to a 256-pixel row segment in groups of eight, seg = ((b >> 3) % nseg8) * 8 +
+    """dn_iter_direct maps blockIdx.x to a 256-pixel row segment in groups of eight, seg = ((b >> 3) % nseg8) * 8 +
     (b & 7): nseg8 is 1 at every width up to 2048. 2100 x 36 has 9 segments (nseg8 = 2), rendered at the size itself
     along test_temporal_cpu's wide path (yaw 170) with the second camera held for four frames: on CPU frames the second
     camera hits 0.68 of the pixels and 0.59 of columns >= 2048, and there 0.22 of the pixels keep history over the
     camera step (0.38 of the valid ones). Those arrive with n = 5 and the others with n = 4, so min_history = 5 splits
     the valid pixels there into temporal and spatial initial variances (measured on the device's history: 0.380 and
     0.620 of the valid pixels there); each class is asserted to be 5 % of them at least. Iteration 5 puts
-    vd_iter_direct<true> at step 16 in one of variants 0 / 2; iteration 6 puts <false> at step 16 there and <true> at
-    step 32 in both.
+    its LAST = true instantiation at step 16 in one of variants 0 / 2; iteration 6 puts LAST = false at step 16 there and
+    LAST = true at step 32 in both.
     No light reaches what columns >= 1920 show: every hit pixel there is black in the frame itself ("lights"), its
     irradiance and variance 0 whatever the weights. "ambient" accumulates the same frames with an ambient term, so that
     those columns carry colours and variances a wrong tap would change. On CPU frames the largest albedo channel of
