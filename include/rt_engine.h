@@ -765,6 +765,71 @@ int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d, void *stre
 int rt_scene_set_vdenoise_timing(rt_scene *s, int on);
 int rt_scene_vdenoise_times(rt_scene *s, float *ms, int cap, int *n);
 
+/* ------------------------------------------------------------------ *
+ * Guided upsampling: a colour rendered at a lower       *
+ * resolution brought to full resolution, steered by both frames'       *
+ * guides.                                                              *
+ * ------------------------------------------------------------------ */
+typedef struct rt_upsample_desc {
+    uint32_t struct_size;         /* sizeof(rt_upsample_desc); 0 reads as this layout. Fields past a caller's size read as 0 */
+    int width, height;            /* full resolution ("hi"), W x H: of depth .. source                                      */
+    int lo_width, lo_height;      /* low resolution ("lo"), w x h, w <= W and h <= H: of rgba_lo .. id_lo                   */
+    const float *rgba_lo;         /* device, float4, 16-byte aligned: the colour to upsample                                */
+    const float *depth_lo;        /* device, the lo frame's guides in the rt_frame_desc.aov_* layouts: float, 4-byte aligned */
+    const float *normal_lo;       /*   float4, 16-byte aligned                                                              */
+    const float *albedo_lo;       /*   float4, 16-byte aligned; may be NULL only with demodulate = 0                        */
+    const int *id_lo;             /*   int2 (kind, index), 8-byte aligned                                                   */
+    const float *depth;           /* device, the hi frame's guides, same layouts                                            */
+    const float *normal;
+    const float *albedo;          /*   may be NULL only with demodulate = 0                                                 */
+    const int *id;
+    const float *base;            /* NULL, or device, float4, 16-byte aligned, W x H: what a pixel that is not upsampled
+                                     takes, all four words (the plain frame); may be rgba_out itself                [NULL]  */
+    float *rgba_out;              /* device, float4, 16-byte aligned, W x H                                                 */
+    uint32_t *pixels;             /* NULL, or device: the packed framebuffer of rgba_out, rgbToInt(c * 254)                 */
+    uint8_t *source;              /* NULL, or device, a byte per hi pixel: 1 upsampled, 0 sky or not selected, 2 selected
+                                     but without a counting tap                                                             */
+    const uint8_t *sphere_select; /* NULL, or device, a byte per sphere: non-zero = its pixels are upsampled         [NULL] */
+    int n_sphere_select;          /* spheres the table covers; an index at or past it reads as 0                     [0]    */
+    const uint8_t *plane_select;  /* the same per plane                                                                     */
+    int n_plane_select;
+    const uint8_t *cube_select;   /* the same per cube (a triangle always reads as 0)                                       */
+    int n_cube_select;
+    int use_tables;               /* 0: every hit pixel is selected, the tables are not read; else only those named  [0]    */
+    int normal_shift;             /* 0 .. RT_DENOISE_MAX_NORMAL_SHIFT: as rt_denoise_desc                            [5]    */
+    float sigma_depth;            /* finite, > 0: as rt_denoise_desc                                                 [0.05] */
+    int demodulate;               /* non-zero: upsample colour / albedo_lo and multiply the hi albedo back           [1]    */
+    int variant;                  /* 0: the product kernel, one thread per hi pixel; 1: at the exact 2 x ratio a second
+                                     implementation (a lane per 2 x 2 quad, neighbouring lo columns from neighbouring
+                                     lanes; slower, kept for the cross-check), else the same kernel. The same bits          */
+} rt_upsample_desc;
+
+/* The defaults in brackets above; sizes and pointers 0. */
+void rt_upsample_desc_init(rt_upsample_desc *d);
+
+/* Brings rgba_lo to W x H on `stream` (a hipStream_t; NULL = the null stream). A hi pixel is selected if it shows an
+ * object (kind >= 0) and, with use_tables, its object's table entry is non-zero. A selected pixel takes the weighted
+ * mean of the four lo pixels around its centre ((x + 0.5) w / W - 0.5), each weighted by its bilinear factor times
+ * rt_scene_denoise's normal and depth factors with the hi pixel as the centre, and counted only if it shows the same
+ * object; demodulated, the lo colours are divided by albedo_lo first and the mean is multiplied by the hi albedo.
+ * Every other pixel -- sky, not selected, no counting tap -- takes base's four words, or without base the plain
+ * bilinear mean of rgba_lo. DESIGN.md 6l gives every formula; binary32, + - * / and compares only, so the result is
+ * defined to the bit and both variants return the same bits.
+ * The call enqueues one kernel and returns; there is no host wait. Calls of one scene on different streams are ordered
+ * on the device, one after the other (an event); ordering the call after the frames that wrote its inputs is the
+ * caller's. Before anything is enqueued, and with nothing written: NULL or misaligned required pointers (float4
+ * buffers 16 bytes, id 8, depth and pixels 4), sizes <= 0 or above RT_DENOISE_MAX_SIZE, lo_width > width or
+ * lo_height > height, normal_shift or variant out of range, a sigma_depth that is not finite and > 0, demodulate
+ * without both albedos, a negative count, a count > 0 with a NULL table, an output that overlaps an input or another
+ * output (only rgba_out may be base itself: a pixel reads only its own base pixel) -> RT_ERR_INVALID; a stream that
+ * is being captured -> RT_ERR_UNSUPPORTED. */
+int rt_scene_upsample(rt_scene *s, const rt_upsample_desc *d, void *stream);
+
+/* Device time of the scene's later upsample calls (hipEvents around the launch; off by default).
+ * rt_scene_upsample_times waits for the last call and fills ms[0 .. *n - 1] (one launch: *n <= 1). cap: room in ms. */
+int rt_scene_set_upsample_timing(rt_scene *s, int on);
+int rt_scene_upsample_times(rt_scene *s, float *ms, int cap, int *n);
+
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
  * tile first -- the frame kernel records every tile's wave duration, and from the previous launch's durations the
  * blocks are sorted on the device (three small kernels, ~15 us): after 1, 2, 4, 8, 16, 32, 64, 96, ... launches of an

@@ -215,6 +215,21 @@ class TMotionDesc(C.Structure):
                                         ("clamp", C.c_int), ("clamp_slack", C.c_float), ("clamp_history", C.c_int)]
 
 
+class UpsampleDesc(C.Structure):
+    """rt_upsample_desc."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
+                ("lo_width", C.c_int), ("lo_height", C.c_int),
+                ("rgba_lo", C.c_void_p), ("depth_lo", C.c_void_p), ("normal_lo", C.c_void_p), ("albedo_lo", C.c_void_p),
+                ("id_lo", C.c_void_p),
+                ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("id", C.c_void_p),
+                ("base", C.c_void_p), ("rgba_out", C.c_void_p), ("pixels", C.c_void_p), ("source", C.c_void_p),
+                ("sphere_select", C.c_void_p), ("n_sphere_select", C.c_int),
+                ("plane_select", C.c_void_p), ("n_plane_select", C.c_int),
+                ("cube_select", C.c_void_p), ("n_cube_select", C.c_int),
+                ("use_tables", C.c_int), ("normal_shift", C.c_int), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int), ("variant", C.c_int)]
+
+
 class ViewListsInfo(C.Structure):
     """rt_view_lists_info."""
     _fields_ = [("read", C.c_int), ("block_w", C.c_int), ("block_h", C.c_int), ("blocks_x", C.c_int), ("blocks_y", C.c_int),
@@ -365,6 +380,10 @@ def load_library():
         "rt_scene_temporal_motion": (ci, [vp, C.POINTER(TMotionDesc), vp]),
         "rt_scene_set_temporal_timing": (ci, [vp, ci]),
         "rt_scene_temporal_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
+        "rt_upsample_desc_init": (None, [C.POINTER(UpsampleDesc)]),
+        "rt_scene_upsample": (ci, [vp, C.POINTER(UpsampleDesc), vp]),
+        "rt_scene_set_upsample_timing": (ci, [vp, ci]),
+        "rt_scene_upsample_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_scene_set_reflect_scope": (ci, [vp, ci]),
         "rt_scene_set_reflect_samples": (ci, [vp, ci]),
         "rt_scene_set_plane_materials": (ci, [vp, C.POINTER(Material), ci]),
@@ -540,6 +559,7 @@ class Scene:
         self.n_lights = 0
         self.planes, self.n_planes = None, 0
         self.cubes, self.n_cubes = None, 0
+        self.materials = self.plane_materials = self.cube_materials = None
 
     def close(self):
         if self.handle:
@@ -646,7 +666,7 @@ class Scene:
         fn = getattr(self.lib, entry)
         if reflectivity is None or len(reflectivity) == 0:
             _check(fn(self.handle, None, 0), entry)
-            return
+            return None
         n = len(reflectivity)
         mats = (Material * n)()
         for i, m in enumerate(reflectivity):
@@ -655,14 +675,15 @@ class Scene:
             else:
                 mats[i].reflectivness = float(m)
         _check(fn(self.handle, mats, n), entry)
+        return mats
 
     def set_plane_materials(self, reflectivity):
         """One material per plane (floats k in [0, 1], or Material); None clears them. Read under the "scene" scope."""
-        self._set_kind_materials("rt_scene_set_plane_materials", reflectivity)
+        self.plane_materials = self._set_kind_materials("rt_scene_set_plane_materials", reflectivity)
 
     def set_cube_materials(self, reflectivity):
         """One material per cube (floats k in [0, 1], or Material); None clears them. Read under the "scene" scope."""
-        self._set_kind_materials("rt_scene_set_cube_materials", reflectivity)
+        self.cube_materials = self._set_kind_materials("rt_scene_set_cube_materials", reflectivity)
 
     def set_reflect_timing(self, on: bool):
         _check(self.lib.rt_scene_set_reflect_timing(self.handle, 1 if on else 0), "rt_scene_set_reflect_timing")
@@ -1173,6 +1194,133 @@ class Scene:
         _check(self.temporal_motion_raw(d, st.cuda_stream), "rt_scene_temporal_motion")
         return {"rgba": out, "moments": moments, "packed": packed, "depth": aov["depth"], "normal": aov["normal"],
                 "id": aov["id"], "cam": cam, "aspect": aspect, "spheres": now["spheres"], "cubes": now["cubes"]}
+
+    # ---------------------------------------------------------------- guided upsampling
+    def upsample_desc(self, width, height, lo_width, lo_height, *, rgba_lo=0, depth_lo=0, normal_lo=0, albedo_lo=0,
+                      id_lo=0, depth=0, normal=0, albedo=0, id=0, base=0, rgba_out=0, pixels=0, source=0,
+                      sphere_select=0, n_sphere_select=0, plane_select=0, n_plane_select=0, cube_select=0,
+                      n_cube_select=0, use_tables=False, normal_shift=None, sigma_depth=None, demodulate=None,
+                      variant=0) -> UpsampleDesc:
+        """rt_upsample_desc with rt_upsample_desc_init's defaults where an argument is None."""
+        d = UpsampleDesc()
+        self.lib.rt_upsample_desc_init(C.byref(d))
+        d.width, d.height, d.lo_width, d.lo_height = width, height, lo_width, lo_height
+        d.rgba_lo, d.depth_lo, d.normal_lo, d.albedo_lo, d.id_lo = rgba_lo, depth_lo, normal_lo, albedo_lo, id_lo
+        d.depth, d.normal, d.albedo, d.id, d.base = depth, normal, albedo, id, base
+        d.rgba_out, d.pixels, d.source = rgba_out, pixels, source
+        d.sphere_select, d.n_sphere_select = sphere_select, n_sphere_select
+        d.plane_select, d.n_plane_select = plane_select, n_plane_select
+        d.cube_select, d.n_cube_select = cube_select, n_cube_select
+        d.use_tables = 1 if use_tables else 0
+        for k, v in (("normal_shift", normal_shift), ("sigma_depth", sigma_depth), ("variant", variant)):
+            if v is not None:
+                setattr(d, k, v)
+        if demodulate is not None:
+            d.demodulate = 1 if demodulate else 0
+        return d
+
+    def upsample_raw(self, d: UpsampleDesc, stream=0) -> int:
+        """rt_scene_upsample as is: returns the status."""
+        return self.lib.rt_scene_upsample(self.handle, C.byref(d), stream)
+
+    def upsample(self, hi, lo, *, colour=None, base=True, select=None, normal_shift=None, sigma_depth=None,
+                 demodulate=None, want_packed=True, want_source=True, variant=0, stream=None):
+        """Bring a low-resolution colour to the resolution of `hi`. `hi` and `lo` are frames of one view as
+        render(..., aov=("depth", "normal", "id", "albedo")) returned them (demodulate=False needs no albedo).
+        `colour`: an rgba tensor of lo's size to upsample instead of lo["rgba"]. `base`: True passes hi["rgba"] (what
+        a pixel that is not upsampled takes), False or None none (the plain bilinear mean), or a tensor of hi's size.
+        `select`: None = every hit pixel is upsampled; or a dict with any of "sphere", "plane", "cube", each a sequence
+        (or uint8 CUDA tensor) with a non-zero entry per object whose pixels are. Returns {'rgba': float32
+        [H, W, 4], 'packed': int32 [H, W] or None, 'source': uint8 [H, W] or None} as new tensors; no input is
+        written. Enqueued on `stream` (default: the current stream); no host wait."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError("no GPU visible: the upsampler has no CPU fallback")
+        ha, la = hi.get("aov") or {}, lo.get("aov") or {}
+        rgba_lo = lo.get("rgba") if colour is None else colour
+        demod = demodulate is None or bool(demodulate)
+        need = ("depth", "normal", "id") + (("albedo",) if demod else ())
+        if rgba_lo is None or any(k not in ha or k not in la for k in need):
+            raise RtError(f"upsample needs lo's rgba (or colour=) and the G-buffer outputs {need} of both frames: render "
+                          f"with want_rgba=True and aov={AOV_NAMES}")
+        H, W = ha["depth"].shape[0], ha["depth"].shape[1]
+        h, w = la["depth"].shape[0], la["depth"].shape[1]
+        if tuple(rgba_lo.shape) != (h, w, 4) or rgba_lo.dtype != torch.float32 or not rgba_lo.is_cuda:
+            raise RtError("upsample: the colour must be a CUDA float32 tensor of lo's guides' shape [h, w, 4]")
+        rgba_lo = rgba_lo.contiguous()
+        if base is True:
+            base = hi.get("rgba")
+            if base is None:
+                raise RtError("upsample: base=True needs hi's rgba")
+        elif base is False:
+            base = None
+        if base is not None:
+            if tuple(base.shape) != (H, W, 4) or base.dtype != torch.float32 or not base.is_cuda:
+                raise RtError("upsample: base must be a CUDA float32 tensor of hi's shape [H, W, 4]")
+            base = base.contiguous()
+        dev = rgba_lo.device
+        tables, keep = {}, []
+        if select is not None:
+            for kind in ("sphere", "plane", "cube"):
+                t = select.get(kind)
+                if t is None or len(t) == 0:
+                    continue
+                if not isinstance(t, torch.Tensor):
+                    t = torch.tensor([1 if v else 0 for v in t], dtype=torch.uint8)
+                t = t.to(device=dev, dtype=torch.uint8).contiguous()
+                keep.append(t)
+                tables[f"{kind}_select"], tables[f"n_{kind}_select"] = t.data_ptr(), t.numel()
+        out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+        packed = torch.empty((H, W), dtype=torch.int32, device=dev) if want_packed else None
+        source = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_source else None
+        st = torch.cuda.current_stream() if stream is None else stream
+        d = self.upsample_desc(W, H, w, h, rgba_lo=rgba_lo.data_ptr(), depth_lo=la["depth"].data_ptr(),
+                               normal_lo=la["normal"].data_ptr(), albedo_lo=la["albedo"].data_ptr() if demod else 0,
+                               id_lo=la["id"].data_ptr(), depth=ha["depth"].data_ptr(), normal=ha["normal"].data_ptr(),
+                               albedo=ha["albedo"].data_ptr() if demod else 0, id=ha["id"].data_ptr(),
+                               base=base.data_ptr() if base is not None else 0, rgba_out=out.data_ptr(),
+                               pixels=packed.data_ptr() if want_packed else 0,
+                               source=source.data_ptr() if want_source else 0, use_tables=select is not None,
+                               normal_shift=normal_shift, sigma_depth=sigma_depth, demodulate=demod, variant=variant,
+                               **tables)
+        _check(self.upsample_raw(d, st.cuda_stream), "rt_scene_upsample")
+        for t in keep:                    # the tables stay allocated until the stream has run the pass
+            t.record_stream(st)
+        return {"rgba": out, "packed": packed, "source": source}
+
+    def upsample_select(self):
+        """The tables render_upscaled passes: per kind, 1 where the object's material has k > 0 or tau > 0."""
+        def table(mats):
+            return [1 if (m.reflectivness > 0 or m.transperancy > 0) else 0 for m in mats] if mats is not None else []
+        return {"sphere": table(self.materials), "plane": table(self.plane_materials), "cube": table(self.cube_materials)}
+
+    def render_upscaled(self, width, height, factor=2, reflect_depth=1, *, variant=0, want_parts=False, **kw):
+        """A reflective frame traced at reduced resolution: the plain frame (reflect_depth = 0) with guides at
+        width x height, the reflective frame with guides at width // factor x height // factor with the same camera
+        and aspect, and rt_scene_upsample without demodulation, the plain frame as base and tables built from the
+        materials -- every pixel that shows neither mirror nor glass is the full-resolution frame's, bit for bit.
+        `kw` goes to both renders (cam, aspect, cull, ...). Returns upsample's dict; with want_parts also 'hi' and
+        'lo', the two frames."""
+        if factor < 1 or width // factor < 1 or height // factor < 1:
+            raise RtError("render_upscaled: factor must be >= 1 and leave a low-resolution frame of at least 1 x 1")
+        guides = ("depth", "normal", "id")
+        hi = self.render(width, height, aov=guides, **kw)
+        lo = self.render(width // factor, height // factor, aov=guides, reflect_depth=reflect_depth, **kw)
+        out = self.upsample(hi, lo, base=True, select=self.upsample_select(), demodulate=False, variant=variant,
+                            stream=kw.get("stream"))
+        if want_parts:
+            out["hi"], out["lo"] = hi, lo
+        return out
+
+    def set_upsample_timing(self, on: bool):
+        _check(self.lib.rt_scene_set_upsample_timing(self.handle, 1 if on else 0), "rt_scene_set_upsample_timing")
+
+    def upsample_times(self):
+        """Device ms of the last timed upsample call (waits for it): a list of at most one."""
+        ms = (C.c_float * 1)()
+        n = C.c_int(0)
+        _check(self.lib.rt_scene_upsample_times(self.handle, ms, 1, C.byref(n)), "rt_scene_upsample_times")
+        return list(ms)[: n.value]
 
     def set_temporal_timing(self, on: bool):
         _check(self.lib.rt_scene_set_temporal_timing(self.handle, 1 if on else 0), "rt_scene_set_temporal_timing")

@@ -250,3 +250,6 @@ int rt_temporal_launch(const rt_temporal_desc *d, const float *dx_tab, const flo
 // object moved
 int rt_tmotion_launch(const rt_tmotion_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
                       const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream);
+
+// rt_upsample.hip: guided upsampling (d: validated, in this build's layout; ev: null, or two timing events)
+int rt_upsample_launch(const rt_upsample_desc *d, hipEvent_t *ev, hipStream_t stream);

@@ -962,3 +962,116 @@ extern "C" int rt_scene_temporal_times(rt_scene *s, float *ms, int cap, int *n)
     *n = 1;
     return RT_OK;
 }
+
+// ---------------------------------------------------------------------------
+// guided upsampling (rt_upsample.hip)
+// ---------------------------------------------------------------------------
+extern "C" void rt_upsample_desc_init(rt_upsample_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->normal_shift = 5;
+    d->sigma_depth = 0.05f;
+    d->demodulate = 1;
+}
+
+extern "C" int rt_scene_upsample(rt_scene *s, const rt_upsample_desc *d_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_upsample: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_upsample_desc d;
+    as_built(d_in, &d);
+    struct Range {
+        uintptr_t p;
+        size_t bytes;
+    };
+    const char *bad = nullptr;
+    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE ||
+        d.lo_width <= 0 || d.lo_height <= 0)
+        bad = "the sizes must be in [1, RT_DENOISE_MAX_SIZE]";
+    else if (d.lo_width > d.width || d.lo_height > d.height) bad = "the lo size must not exceed the hi size";
+    else if (!d.rgba_lo || !d.depth_lo || !d.normal_lo || !d.id_lo || !d.depth || !d.normal || !d.id || !d.rgba_out)
+        bad = "rgba_lo, depth_lo, normal_lo, id_lo, depth, normal, id and rgba_out must not be NULL";
+    else if (d.demodulate && (!d.albedo || !d.albedo_lo)) bad = "demodulate needs albedo and albedo_lo";
+    else if ((((uintptr_t)d.rgba_lo | (uintptr_t)d.normal_lo | (uintptr_t)d.albedo_lo | (uintptr_t)d.normal | (uintptr_t)d.albedo |
+               (uintptr_t)d.base | (uintptr_t)d.rgba_out) & 15u) ||
+             (((uintptr_t)d.id_lo | (uintptr_t)d.id) & 7u) ||
+             (((uintptr_t)d.depth_lo | (uintptr_t)d.depth | (uintptr_t)d.pixels) & 3u))
+        bad = "rgba, normal, albedo and base buffers must be 16-byte aligned, id 8-byte, depth and pixels 4-byte";
+    else if (d.normal_shift < 0 || d.normal_shift > RT_DENOISE_MAX_NORMAL_SHIFT) bad = "normal_shift is not in [0, RT_DENOISE_MAX_NORMAL_SHIFT]";
+    else if (!(d.sigma_depth > 0.f) || !std::isfinite(d.sigma_depth)) bad = "sigma_depth is not finite and > 0";
+    else if (d.variant < 0 || d.variant > 1) bad = "variant is not 0 or 1";
+    else if (d.n_sphere_select < 0 || d.n_plane_select < 0 || d.n_cube_select < 0) bad = "a table's count must not be negative";
+    else if ((d.n_sphere_select > 0 && !d.sphere_select) || (d.n_plane_select > 0 && !d.plane_select) ||
+             (d.n_cube_select > 0 && !d.cube_select))
+        bad = "a count > 0 needs its table";
+    else {
+        const size_t npx = (size_t)d.width * d.height, nlo = (size_t)d.lo_width * d.lo_height;
+        const Range outs[3] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.pixels, npx * 4}, {(uintptr_t)d.source, npx}};
+        const Range ins[13] = {{(uintptr_t)d.rgba_lo, nlo * 16}, {(uintptr_t)d.depth_lo, nlo * 4}, {(uintptr_t)d.normal_lo, nlo * 16},
+                               {(uintptr_t)d.albedo_lo, nlo * 16}, {(uintptr_t)d.id_lo, nlo * 8},
+                               {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16}, {(uintptr_t)d.albedo, npx * 16},
+                               {(uintptr_t)d.id, npx * 8}, {(uintptr_t)d.base, npx * 16},
+                               {d.n_sphere_select > 0 ? (uintptr_t)d.sphere_select : 0, (size_t)d.n_sphere_select},
+                               {d.n_plane_select > 0 ? (uintptr_t)d.plane_select : 0, (size_t)d.n_plane_select},
+                               {d.n_cube_select > 0 ? (uintptr_t)d.cube_select : 0, (size_t)d.n_cube_select}};
+        auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
+        for (int i = 0; i < 3 && !bad; ++i) {
+            for (int k = 0; k < 13; ++k)
+                if (overlap(outs[i], ins[k]) && !(i == 0 && k == 9 && d.rgba_out == d.base))
+                    bad = "an output buffer overlaps an input (only rgba_out may be base itself)";
+            for (int j = i + 1; j < 3; ++j)
+                if (overlap(outs[i], outs[j])) bad = "two output buffers overlap";
+        }
+    }
+    if (bad) {
+        rt_set_error("rt_scene_upsample: %s (%d x %d from %d x %d, normal_shift %d, variant %d)", bad, d.width, d.height,
+                     d.lo_width, d.lo_height, d.normal_shift, d.variant);
+        return RT_ERR_INVALID;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_upsample: the stream is being captured (the pass is not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    RT_HIP(s->up_done.order(stream));
+    hipEvent_t ev[2];
+    s->up_timed = 0;
+    if (s->up_timing) {
+        for (int i = 0; i < 2; ++i) {
+            RT_HIP(s->up_ev[i].create(hipEventDefault));
+            ev[i] = s->up_ev[i].get();
+        }
+    }
+    const int rc = rt_upsample_launch(&d, s->up_timing ? ev : nullptr, stream);
+    RT_HIP(s->up_done.record(stream));
+    if (rc == RT_OK && s->up_timing) s->up_timed = 2;
+    return rc;
+}
+
+extern "C" int rt_scene_set_upsample_timing(rt_scene *s, int on)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_upsample_timing: null scene");
+        return RT_ERR_INVALID;
+    }
+    s->up_timing = on != 0;
+    return RT_OK;
+}
+
+extern "C" int rt_scene_upsample_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    if (!s || !ms || !n || cap < 0) {
+        rt_set_error("rt_scene_upsample_times: null argument");
+        return RT_ERR_INVALID;
+    }
+    *n = 0;
+    if (s->up_timed < 2 || cap < 1) return RT_OK;
+    RT_HIP(s->up_done.host_wait());
+    RT_HIP(hipEventElapsedTime(&ms[0], s->up_ev[0].get(), s->up_ev[1].get()));
+    *n = 1;
+    return RT_OK;
+}

@@ -31,6 +31,7 @@ int rt_scene_quiesce(rt_scene *s)
     if (s->table_stream.get()) RT_HIP(hipStreamSynchronize(s->table_stream.get()));   // a table build still reading the list
     RT_HIP(s->dn_done.host_wait());                                                    // a denoise call still using the scratch
     RT_HIP(s->tp_done.host_wait());                                                    // a temporal call still reading its ray tables
+    RT_HIP(s->up_done.host_wait());                                                    // an upsample call in flight
     return RT_OK;
 }
 

@@ -19,7 +19,7 @@
 //       build has finished;
 //   (c) a reader waits on the build event on the device only; the host never waits for a build, except in
 //       rt_scene_view_lists_info;
-//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's and the temporal pass's events;
+//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's, the temporal pass's and the upsampler's events;
 //   (e) the tile order keeps one event for all layouts; a new layout or a re-sort first makes the launching stream
 //       wait for every ring event;
 //   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
@@ -183,6 +183,11 @@ struct rt_scene {
     HipEvent tp_ev[2];                               // rt_scene_set_temporal_timing
     bool tp_timing = false;
     int tp_timed = 0;
+    // guided upsampling (rt_upsample.hip): no scratch; `up_done` orders the scene's upsample calls
+    HipPendingEvent up_done;
+    HipEvent up_ev[2];                               // rt_scene_set_upsample_timing
+    bool up_timing = false;
+    int up_timed = 0;
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
 #endif
