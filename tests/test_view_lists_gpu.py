@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from scenes import Inputs, Scn
+from view_margins import assert_lists_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -57,19 +58,7 @@ def test_device_builder_equals_host_builder(rt, gpu, w, h, n):
     dev = scene.view_lists_info(want_lists=True)
     assert dev["read"] == 1
     host = rt.view_lists_host(inp.spheres, n, scene.frame_desc(w, h))
-    for k in ("block_w", "block_h", "blocks_x", "blocks_y", "blocks", "overflowed", "not_built", "longest"):
-        assert dev[k] == host[k], (k, dev[k], host[k])
-    for b, (d, hst) in enumerate(zip(dev["lists"], host["lists"])):
-        assert d[0] == hst[0] and d[1] == hst[1], (b, d[:2], hst[:2])
-        assert set(d[3].tolist()) == set(hst[3].tolist()), b                      # the same spheres
-        assert np.array_equal(d[2], inp_table(inp)[d[3]]), b                      # each with its own list position
-        if d[0] > 1:
-            assert (np.diff(d[4]) >= 0).all(), b                                  # front to back
-            # the same order up to equal bounds: every sphere's bound agrees (the device's square root may differ
-            # from sqrtf in the last place)
-            hb = dict(zip(hst[3].tolist(), hst[4].tolist()))
-            for p, lb in zip(d[3].tolist(), d[4].tolist()):
-                assert abs(lb - hb[p]) <= 1e-5 * (1 + abs(lb)), (b, p, lb, hb[p])
+    assert_lists_equal(dev, host, inp_table(inp))
 
 
 _TABS = {}
