@@ -574,14 +574,20 @@ class Scene:
 
     def set_spheres(self, spheres, n):
         _check(self.lib.rt_scene_set_spheres(self.handle, spheres, n), "rt_scene_set_spheres")
+        if n != self.n_spheres:           # the library cleared the materials: so does their host mirror (upsample_select)
+            self.materials = None
         self.spheres, self.n_spheres = spheres, n
 
     def set_planes(self, planes, n):
         _check(self.lib.rt_scene_set_planes(self.handle, planes, n), "rt_scene_set_planes")
+        if n != self.n_planes:
+            self.plane_materials = None
         self.planes, self.n_planes = planes, n
 
     def set_cubes(self, cubes, n):
         _check(self.lib.rt_scene_set_cubes(self.handle, cubes, n), "rt_scene_set_cubes")
+        if n != self.n_cubes:
+            self.cube_materials = None
         self.cubes, self.n_cubes = cubes, n
 
     def set_mesh(self, mesh):

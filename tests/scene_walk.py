@@ -5,7 +5,15 @@ tests/test_scene_state_gpu.py walks one scene through such a sequence and compar
 built from the walk's current state alone; tests/test_scene_walk_cpu.py checks the generator and the model.
 
 The materials follow DESIGN.md section 6d: one per sphere; rt_scene_set_spheres with the same count keeps them, another
-count clears them; the old entry (set_materials) sets every transparency to 0; NULL / 0 clears them."""
+count clears them; the old entry (set_materials) sets every transparency to 0; NULL / 0 clears them. The plane and cube
+materials follow the same rule per list (rt_engine.h: they "survive rt_scene_set_planes / rt_scene_set_cubes with the same
+count and are cleared by a different count"); the reflect scope, the sampling mode and the view-list mode are switches
+that survive everything.
+
+Two vocabularies: generate(seed, steps) is the first suite's (MUTATIONS, OUTPUTS; its sequences are pinned by digest in
+tests/test_scene_walk_cpu.py), generate(seed, steps, vocabulary=2) adds the scope, the sampling mode, the view lists, the
+plane and cube materials, plane and cube lists of several counts, G-buffer outputs, supersampled reflective frames,
+refused requests, the post passes and temporal accumulation (MUTATIONS_2, OUTPUTS_2; seeds WALK_SEEDS_2)."""
 import random
 from dataclasses import dataclass, replace
 
@@ -34,29 +42,70 @@ WALK_STEPS = 60
 MUTATIONS = ("spheres", "lights", "texture", "planes", "cubes", "mesh", "materials", "tile_order")
 OUTPUTS = ("render", "query", "graph")
 
+# the second vocabulary
+WALK_SEEDS_2 = (17, 25, 149, 262, 1103, 1205)    # chosen so that tests/test_scene_walk_cpu.py's conditions hold
+MUTATIONS_2 = MUTATIONS + ("scope", "samples", "view_lists", "plane_materials", "cube_materials")
+OUTPUTS_2 = OUTPUTS + ("refused", "pass", "temporal")
+AOV = ("depth", "normal", "id", "albedo")
+GUIDES = ("depth", "normal", "id")
+# plane and cube lists (count, variant), derived from scenes.mixed_scene's (2 planes, 5 cubes): variant 0 is the first
+# `count` primitives as they are, variant 1 the same with one primitive translated. None: no such primitives.
+PLANE_SPECS = ((2, 0), (2, 1), (1, 0), (1, 1))
+CUBE_SPECS = ((5, 0), (5, 1), (4, 0), (4, 1))
+PLANE_MOVE = (0.0, -0.5, 0.0)            # added to the last plane's point
+CUBE_MOVE = (0.25, 0.5, -0.25)           # added to cube 1's centre and bounds
+KIND_K = (0.0, 0.25, 0.5, 1.0)
+
 
 @dataclass(frozen=True)
 class State:
     """What a fresh scene is built from. spheres: (count, seed, shift) -- rt_generate_spheres(count, seed) with `shift`
     added to every centre's y; lights: 7-tuples (pos, size, r, g, b); texture: 0 the stand-in, 1 a darker variant;
     mats: None, or (kind, seed) with kind "k" (old entry: mirrors only) or "ex" (mirrors and glass) -- the arrays are
-    material_arrays(kind, seed, count)."""
+    material_arrays(kind, seed, count). planes / cubes: None (or False), or a spec (count, variant) out of PLANE_SPECS /
+    CUBE_SPECS (True, the first vocabulary's "on": the first spec); mesh: 0 (or False) none, 1 (or True) the mesh, 2 the
+    same mesh elsewhere; plane_mats / cube_mats: None, or the seed of kind_k(seed, count)."""
     spheres: tuple = (256, 1, 0.0)
     lights: tuple = DEFAULT_LIGHTS
     texture: int = 0
-    planes: bool = False
-    cubes: bool = False
-    mesh: bool = False
+    planes: tuple = None
+    cubes: tuple = None
+    mesh: int = 0
     mats: tuple = None
     tile_order: int = 1
+    scope: str = "spheres"               # "spheres" / "scene"
+    samples: str = "one"                 # "one" / "many"
+    view_lists: int = 1
+    plane_mats: int = None
+    cube_mats: int = None
 
     @property
     def n(self):
         return self.spheres[0]
 
+    @property
+    def n_planes(self):
+        return spec_of(self.planes, PLANE_SPECS)[0]
+
+    @property
+    def n_cubes(self):
+        return spec_of(self.cubes, CUBE_SPECS)[0]
+
     def reflect_ok(self):
-        """Reflective frames take spheres only."""
-        return not (self.planes or self.cubes or self.mesh)
+        """Reflective frames take every primitive under the scene scope, spheres only under the other."""
+        return self.scope == "scene" or not (self.planes or self.cubes or self.mesh)
+
+
+def spec_of(value, specs):
+    """(count, variant) of a State's planes / cubes field: the first vocabulary's booleans mean the whole list."""
+    if not value:
+        return (0, 0)
+    return specs[0] if value is True else tuple(value)
+
+
+def kind_k(seed, n):
+    """k per plane or cube, float32, out of KIND_K."""
+    return np.random.default_rng(2000 + seed).choice(np.float32(KIND_K), n).astype(np.float32)
 
 
 def material_arrays(kind, seed, n):
@@ -84,10 +133,20 @@ def apply(state, op):
         return replace(state, lights=op["lights"])
     if kind == "texture":
         return replace(state, texture=op["texture"])
-    if kind in ("planes", "cubes", "mesh", "tile_order"):
+    if kind in ("planes", "cubes"):
+        specs, mats = (PLANE_SPECS, "plane_mats") if kind == "planes" else (CUBE_SPECS, "cube_mats")
+        same = spec_of(op[kind], specs)[0] == spec_of(getattr(state, kind), specs)[0]
+        return replace(state, **{kind: op[kind], mats: getattr(state, mats) if same else None})   # as the spheres' table
+    if kind in ("mesh", "tile_order", "scope", "samples", "view_lists"):
         return replace(state, **{kind: op[kind]})
     if kind == "materials":
         return replace(state, mats=op["mats"])                   # "k" is the old entry: it clears the glass
+    if kind == "plane_materials":
+        return replace(state, plane_mats=op["seed"])
+    if kind == "cube_materials":
+        return replace(state, cube_mats=op["seed"])
+    if kind == "temporal" and op.get("mutation"):                # the change between the step's two frames
+        return apply(state, op["mutation"])
     return state
 
 
@@ -163,8 +222,11 @@ def _graph_op(rng, state):
     return {"op": "graph", "cam": rng.randrange(len(CAMERAS)) if rng.random() < 0.4 else None}
 
 
-def generate(seed, steps):
-    """`steps` operations on one scene that starts as State(). Deterministic per seed."""
+def generate(seed, steps, vocabulary=1):
+    """`steps` operations on one scene that starts as State(). Deterministic per seed. vocabulary 1: the first suite's
+    operations, exactly as they were; 2: those of generate_2."""
+    if vocabulary == 2:
+        return generate_2(seed, steps)
     rng = random.Random(seed)
     state = State()
     ops = []
@@ -199,14 +261,249 @@ def generate(seed, steps):
     return ops
 
 
+# ------------------------------------------------------------------------------------------------ the second vocabulary
+def _kind_list_op(rng, state, kind):
+    """planes / cubes: on, off, the same count with one primitive moved, or another count."""
+    specs = PLANE_SPECS if kind == "planes" else CUBE_SPECS
+    cur = getattr(state, kind)
+    if not cur:
+        return {"op": kind, "how": "on", kind: rng.choice(specs)}
+    count, variant = spec_of(cur, specs)
+    how = rng.choice(("off", "same_count_moved", "same_count_moved", "other_count", "other_count"))
+    if how == "off":
+        return {"op": kind, "how": how, kind: None}
+    if how == "same_count_moved":
+        return {"op": kind, "how": how, kind: (count, 1 - variant)}
+    return {"op": kind, "how": how, kind: rng.choice([s for s in specs if s[0] != count])}
+
+
+def _kind_materials_op(rng, state, kind):
+    n = state.n_planes if kind == "plane_materials" else state.n_cubes
+    if n == 0 or rng.random() < 0.2:
+        return {"op": kind, "how": "clear", "seed": None}
+    return {"op": kind, "how": "set", "seed": rng.randrange(1, 50)}
+
+
+def _stream_fields(rng):
+    return {"stream": rng.randrange(2), "defer": rng.random() < 0.35}
+
+
+def _render_op_2(rng, state):
+    """The first vocabulary's frame plus guides, and under the "many" mode more than one sample of a reflective frame:
+    spp 2, 4 or 5 (two groups), a sample range, or two accumulating calls (the first with resolve = -1). Guides go
+    with one sample only (rt_engine.h refuses them otherwise)."""
+    w, h = rng.choice(SIZES)
+    band = (0, 0)
+    if rng.random() < 0.3:
+        y0 = rng.randrange(0, h - 4)
+        band = (y0, rng.randrange(y0 + 1, h + 1))
+    depth = rng.randrange(1, 4) if state.reflect_ok() and rng.random() < 0.55 else 0
+    spp, base, total, split = 1, 0, 0, None
+    if depth and state.samples == "many" and rng.random() < 0.75:
+        spp = rng.choice((2, 4, 5))
+        how = rng.choice(("plain", "range", "split"))
+        if how == "range":
+            total = spp + rng.randrange(1, 4)
+            base = rng.randrange(0, total - spp + 1)
+        elif how == "split":
+            split = rng.randrange(1, spp)            # the first call's samples; the second takes the others
+    elif not depth:
+        spp = rng.choice((1, 1, 2, 4))
+    aov = ()
+    if spp == 1 and rng.random() < 0.5:
+        aov = tuple(a for a in AOV if rng.random() < 0.6)
+    op = {"op": "render", "cam": rng.randrange(len(CAMERAS)), "size": (w, h), "aspect": rng.choice(ASPECTS),
+          "spp": spp, "cull": int(rng.random() < 0.75), "band": band, "depth": depth, "aov": aov,
+          "sample_base": base, "sample_total": total, "split": split}
+    op.update(_stream_fields(rng))
+    return op
+
+
+def _refused_op(rng, state):
+    """A request rt_engine.h names RT_ERR_UNSUPPORTED for the state, or None if the state allows none: a reflective
+    frame over a plane, a cube or a mesh under the spheres scope; under the "one" mode a reflective frame with spp 2, a
+    sample range or accumulate."""
+    w, h = rng.choice(SIZES)
+    op = {"op": "refused", "cam": rng.randrange(len(CAMERAS)), "size": (w, h), "depth": rng.randrange(1, 4),
+          "stream": rng.randrange(2)}
+    if not state.reflect_ok():
+        return dict(op, why="scope", request={})
+    if state.samples == "one":
+        return dict(op, why="samples", request=rng.choice(({"spp": 2}, {"sample_base": 1, "sample_total": 2},
+                                                           {"accumulate": True}, {"spp": 4, "sample_total": 8})))
+    return None
+
+
+def _pass_op(rng, state):
+    w, h = rng.choice(SIZES)
+    what = rng.choice(("denoise", "vdenoise", "upsample", "upsample", "render_upscaled", "render_upscaled"))
+    if what == "render_upscaled" and not state.reflect_ok():
+        what = "upsample"
+    op = {"op": "pass", "what": what, "cam": rng.randrange(len(CAMERAS)), "size": (w, h), "aspect": rng.choice(ASPECTS),
+          "variant": rng.randrange(3 if what in ("denoise", "vdenoise") else 2)}
+    if what == "denoise":
+        op["shrink"] = rng.choice((1, 1, 2, 3))               # the pass at size // shrink
+    elif what == "vdenoise":
+        op["history"] = rng.random() < 0.6
+        op["shrink"] = rng.choice((1, 2))
+    else:
+        op["factor"] = rng.choice((2, 3))                     # 2 divides every SIZES entry; 3 does not divide 64 x 36 and 40 x 90
+        op["depth"] = rng.randrange(1, 3) if state.reflect_ok() else 0
+    op.update(_stream_fields(rng))
+    return op
+
+
+def _temporal_op(rng, state):
+    """Two frames from two cameras accumulated one onto the other; or, with a same-count move of the spheres or the
+    cubes between the frames, temporal_motion with the history made before the move."""
+    w, h = rng.choice(SIZES)
+    a, b = rng.sample(range(len(CAMERAS)), 2)                # two views: the history is reprojected
+    op = {"op": "temporal", "form": "camera", "cams": (a, b), "size": (w, h),
+          "aspect": rng.choice(ASPECTS), "variant": rng.randrange(2), "mutation": None}
+    forms = ["camera"]
+    if 0 < state.n <= 1024:
+        forms.append("motion_spheres")
+    if state.cubes:
+        forms.append("motion_cubes")
+    form = rng.choice(forms)
+    if form == "motion_spheres":
+        n, seed, shift = state.spheres
+        op["mutation"] = {"op": "spheres", "how": "same_count", "spheres": (n, seed, round(shift + rng.choice((-0.5, 0.25)), 2))}
+    elif form == "motion_cubes":
+        count, variant = spec_of(state.cubes, CUBE_SPECS)
+        op["mutation"] = {"op": "cubes", "how": "same_count_moved", "cubes": (count, 1 - variant)}
+    op["form"] = form
+    op.update(_stream_fields(rng))
+    return op
+
+
+def generate_2(seed, steps):
+    """`steps` operations of the second vocabulary on one scene that starts as State(). Deterministic per seed."""
+    rng = random.Random(1000003 * 2 + seed)
+    state = State()
+    ops = []
+    while len(ops) < steps:
+        r = rng.random()
+        if r < 0.46:
+            kind = rng.choice(("spheres", "spheres", "spheres", "lights", "lights", "texture", "planes", "planes", "cubes",
+                               "cubes", "mesh", "materials", "materials", "tile_order", "scope", "scope", "samples",
+                               "samples", "view_lists", "view_lists", "plane_materials", "cube_materials", "cube_materials"))
+            if kind == "spheres":
+                op = _spheres_op(rng, state)
+            elif kind == "lights":
+                op = _lights_op(rng, state.lights)
+            elif kind == "texture":
+                op = {"op": "texture", "texture": 1 - state.texture}
+            elif kind in ("planes", "cubes"):
+                op = _kind_list_op(rng, state, kind)
+            elif kind == "mesh":
+                op = {"op": "mesh", "mesh": rng.choice([m for m in (0, 1, 2) if m != int(state.mesh)])}
+            elif kind == "materials":
+                op = _materials_op(rng, state)
+            elif kind == "tile_order":
+                op = {"op": "tile_order", "tile_order": 1 - state.tile_order}
+            elif kind == "scope":
+                op = {"op": "scope", "scope": "scene" if state.scope == "spheres" else "spheres"}
+            elif kind == "samples":
+                op = {"op": "samples", "samples": "many" if state.samples == "one" else "one"}
+            elif kind == "view_lists":
+                op = {"op": "view_lists", "view_lists": 1 - state.view_lists}
+            else:
+                op = _kind_materials_op(rng, state, kind)
+            state = apply(state, op)
+            ops.append(op)
+            # an output right after the change, before any render: graph replays and queries read the scene as is
+            if rng.random() < 0.45 and len(ops) < steps:
+                ops.append(_graph_op(rng, state) if rng.random() < 0.5 else _query_op(rng, state))
+        elif r < 0.70:
+            ops.append(_render_op_2(rng, state))
+        elif r < 0.75:
+            ops.append(_query_op(rng, state))
+        elif r < 0.81:
+            ops.append(_graph_op(rng, state))
+        elif r < 0.86:
+            op = _refused_op(rng, state)
+            if op is not None:
+                ops.append(op)
+        elif r < 0.95:
+            ops.append(_pass_op(rng, state))
+        else:
+            op = _temporal_op(rng, state)
+            state = apply(state, op)
+            ops.append(op)
+    return ops
+
+
+def _transitions_2(seen, state, op, prev, cleared):
+    """The second vocabulary's labels of one step; `cleared` is the set of material tables a count change has cleared
+    and nothing has set again."""
+    k = op["op"]
+    if k in ("planes", "cubes") and "how" in op:
+        seen.add("%s:%s" % (k, op["how"]))
+        table = "plane_mats" if k == "planes" else "cube_mats"
+        if getattr(state, table) is not None:
+            kept = getattr(apply(state, op), table) is not None
+            seen.add("kind_materials:kept" if kept else "kind_materials:cleared_by_count")
+            if not kept:
+                cleared.add(table)
+    elif k == "spheres" and state.mats is not None and op["spheres"][0] != state.n:
+        cleared.add("mats")
+    elif k in ("materials", "plane_materials", "cube_materials"):
+        cleared.discard({"materials": "mats", "plane_materials": "plane_mats", "cube_materials": "cube_mats"}[k])
+        if k != "materials":
+            seen.add("%s:%s" % (k, op["how"]))
+    elif k == "scope":
+        seen.add("scope:to_" + op["scope"])
+    elif k == "samples":
+        seen.add("samples:to_" + op["samples"])
+    elif k == "view_lists":
+        seen.add("view_lists:" + ("on" if op["view_lists"] else "off"))
+    elif k == "render" and "aov" in op:
+        if op["depth"] and state.scope == "scene":
+            seen.add("render:scene_scope_depth>0")
+            if state.mesh:
+                seen.add("render:scene_scope_with_mesh")
+        if op["depth"] and op["spp"] > 4:
+            seen.add("render:many_two_groups")
+        if op["split"]:
+            seen.add("render:many_accumulate_split")
+        if op["sample_total"]:
+            seen.add("render:many_sample_range")
+        if op["aov"]:
+            seen.add("render:aov_reflective" if op["depth"] else "render:aov")
+    elif k == "refused":
+        seen.add("refused:" + op["why"])
+    elif k == "pass":
+        what = op["what"]
+        if what == "denoise":
+            seen.add("pass:denoise")
+        elif what == "vdenoise":
+            seen.add("pass:vdenoise_history" if op["history"] else "pass:vdenoise")
+        elif what == "upsample":
+            w, h = op["size"]
+            exact = w % op["factor"] == 0 and h % op["factor"] == 0
+            seen.add("pass:upsample_exact%d" % op["factor"] if exact else "pass:upsample_other_ratio")
+        else:
+            seen.add("pass:render_upscaled")
+            if cleared:
+                seen.add("render_upscaled_after:materials_cleared_by_count")
+    elif k == "temporal":
+        seen.add("temporal:" + op["form"])
+    if prev is not None and prev["op"] in ("pass", "temporal") and prev["defer"] and prev["stream"] == 1 \
+            and k in MUTATIONS_2:
+        seen.add("pass_deferred_then_mutation")
+
+
 def transitions(ops):
     """Labels of what each step exercises (for the coverage test): the set over the whole walk."""
     seen = set()
     state = State()
     prev = None
+    cleared = set()
     for op in ops:
         k = op["op"]
         seen.add(k)
+        _transitions_2(seen, state, op, prev, cleared)
         if k == "spheres":
             n0, m = state.n, op["spheres"][0]
             seen.add("spheres:" + op["how"])
@@ -237,7 +534,7 @@ def transitions(ops):
             seen.add("graph:set_camera")
         elif k == "query":
             seen.add("query:" + op["rays"])
-        if prev is not None and prev["op"] in MUTATIONS and k in ("graph", "query"):
+        if prev is not None and prev["op"] in MUTATIONS_2 and k in ("graph", "query"):
             seen.add("%s_after:%s" % (k, prev["op"]))
         state = apply(state, op)
         prev = op
@@ -294,11 +591,72 @@ def planes_cubes(rt):
     return _cache["mixed"]
 
 
-def mesh(rt):
-    if "mesh" not in _cache:
-        from meshes import uv_sphere_obj
-        _cache["mesh"] = rt.mesh_from_obj_text(uv_sphere_obj(cx=3.0, cy=1.0, cz=4.0, r=1.2, n_lat=6, n_lon=10))
-    return _cache["mesh"]
+def plane_list(rt, value):
+    """(array, count) of a State's planes field."""
+    count, variant = spec_of(value, PLANE_SPECS)
+    if ("planes", count, variant) not in _cache:
+        import ctypes as C
+        src = planes_cubes(rt)[0]
+        arr = (rt.Plane * max(count, 1))()
+        C.memmove(arr, src, C.sizeof(rt.Plane) * count)
+        if variant:
+            o = arr[count - 1].orgin
+            o.x, o.y, o.z = (float(np.float32(v) + np.float32(d)) for v, d in zip((o.x, o.y, o.z), PLANE_MOVE))
+        _cache[("planes", count, variant)] = arr
+    return _cache[("planes", count, variant)], count
+
+
+def cube_list(rt, value):
+    """(array, count) of a State's cubes field."""
+    count, variant = spec_of(value, CUBE_SPECS)
+    if ("cubes", count, variant) not in _cache:
+        import ctypes as C
+        src = planes_cubes(rt)[2]
+        arr = (rt.Cube * max(count, 1))()
+        C.memmove(arr, src, C.sizeof(rt.Cube) * count)
+        if variant:
+            for o in (arr[1].orgin, arr[1].bounds[0], arr[1].bounds[1]):
+                o.x, o.y, o.z = (float(np.float32(v) + np.float32(d)) for v, d in zip((o.x, o.y, o.z), CUBE_MOVE))
+        _cache[("cubes", count, variant)] = arr
+    return _cache[("cubes", count, variant)], count
+
+
+MESH_AT = {1: (3.0, 1.0, 4.0), 2: (5.5, 1.5, 5.0)}
+
+
+def mesh_text(variant):
+    from meshes import uv_sphere_obj
+    cx, cy, cz = MESH_AT[int(variant)]
+    return uv_sphere_obj(cx=cx, cy=cy, cz=cz, r=1.2, n_lat=6, n_lon=10)
+
+
+def mesh(rt, variant=1):
+    if ("mesh", int(variant)) not in _cache:
+        _cache[("mesh", int(variant))] = rt.mesh_from_obj_text(mesh_text(variant))
+    return _cache[("mesh", int(variant))]
+
+
+def origins(rt, state):
+    """The sphere centres and each cube's bounds[0] of `state`, float32 [n, 3]: what displacements are formed from."""
+    sp = sphere_array(rt, state.spheres)
+    cu, n_c = cube_list(rt, state.cubes)
+    a = np.array([[sp[i].orgin.x, sp[i].orgin.y, sp[i].orgin.z] for i in range(state.n)], dtype=np.float32).reshape(-1, 3)
+    b = np.array([[cu[i].bounds[0].x, cu[i].bounds[0].y, cu[i].bounds[0].z] for i in range(n_c)], dtype=np.float32)
+    return a, b.reshape(-1, 3)
+
+
+def motion_tables(rt, before, after):
+    """The displacement tables [n, 4] of the objects between two states of equal counts, binary32 (an empty table
+    where nothing moved: nothing is to be inferred)."""
+    out = []
+    for a, b in zip(origins(rt, before), origins(rt, after)):
+        assert a.shape == b.shape
+        d = (b - a).astype(np.float32)
+        m = np.zeros((a.shape[0] if d.any() else 0, 4), dtype=np.float32)
+        if d.any():
+            m[:, :3] = d
+        out.append(m)
+    return out
 
 
 def set_materials(scene, state_mats, n, old_entry=None):
@@ -325,36 +683,53 @@ def apply_to_scene(rt, scene, op, state):
     elif k == "texture":
         scene.set_texture(texture_planes(rt, op["texture"]))
     elif k == "planes":
-        p, n_p, _, _ = planes_cubes(rt)
-        scene.set_planes(p, n_p if op["planes"] else 0)
+        scene.set_planes(*plane_list(rt, op["planes"]))
     elif k == "cubes":
-        _, _, c, n_c = planes_cubes(rt)
-        scene.set_cubes(c, n_c if op["cubes"] else 0)
+        scene.set_cubes(*cube_list(rt, op["cubes"]))
     elif k == "mesh":
-        scene.set_mesh(mesh(rt) if op["mesh"] else None)
+        scene.set_mesh(mesh(rt, op["mesh"]) if op["mesh"] else None)
     elif k == "materials":
         set_materials(scene, op["mats"], state.n)
     elif k == "tile_order":
         scene.set_tile_order(op["tile_order"])
+    elif k == "scope":
+        scene.set_reflect_scope(op["scope"])
+    elif k == "samples":
+        scene.set_reflect_samples(op["samples"])
+    elif k == "view_lists":
+        scene.set_view_lists(op["view_lists"])
+    elif k == "plane_materials":
+        scene.set_plane_materials(None if op["seed"] is None else kind_k(op["seed"], state.n_planes))
+    elif k == "cube_materials":
+        scene.set_cube_materials(None if op["seed"] is None else kind_k(op["seed"], state.n_cubes))
 
 
 def fresh_scene(rt, state):
     """A new scene holding `state`, its setters called in one canonical order."""
     s = rt.Scene()
     s.set_spheres(sphere_array(rt, state.spheres), state.n)
-    p, n_p, c, n_c = planes_cubes(rt)
     if state.planes:
-        s.set_planes(p, n_p)
+        s.set_planes(*plane_list(rt, state.planes))
     if state.cubes:
-        s.set_cubes(c, n_c)
+        s.set_cubes(*cube_list(rt, state.cubes))
     if state.mesh:
-        s.set_mesh(mesh(rt))
+        s.set_mesh(mesh(rt, state.mesh))
     s.set_texture(texture_planes(rt, state.texture))
     box, sky_planes = sky(rt)
     s.set_sky(box, sky_planes)
     s.set_lights(light_array(rt, state.lights), len(state.lights))
     if state.mats is not None:
         set_materials(s, state.mats, state.n)
+    if state.plane_mats is not None:
+        s.set_plane_materials(kind_k(state.plane_mats, state.n_planes))
+    if state.cube_mats is not None:
+        s.set_cube_materials(kind_k(state.cube_mats, state.n_cubes))
+    if state.scope != "spheres":
+        s.set_reflect_scope(state.scope)
+    if state.samples != "one":
+        s.set_reflect_samples(state.samples)
+    if not state.view_lists:
+        s.set_view_lists(0)
     s.set_tile_order(state.tile_order)
     return s
 
@@ -362,10 +737,10 @@ def fresh_scene(rt, state):
 def oracle_frame(oracle, rt, state, cam, w, h, aspect=None, y0=0, y1=None):
     """The CPU oracle's frame of `state` (no mesh, no materials)."""
     assert not state.mesh and state.mats is None
-    p, n_p, c, n_c = planes_cubes(rt)
+    p, n_p = plane_list(rt, state.planes)
+    c, n_c = cube_list(rt, state.cubes)
     box, sky_planes = sky(rt)
     return oracle.render(sphere_array(rt, state.spheres), state.n, texture_planes(rt, state.texture), sky_planes, box,
                          light_array(rt, state.lights), len(state.lights), cam, w, h,
                          rt.default_aspect() if aspect is None else aspect, y0=y0, y1=y1, nthreads=8,
-                         cubes=c if state.cubes else None, n_cubes=n_c if state.cubes else 0,
-                         planes=p if state.planes else None, n_planes=n_p if state.planes else 0)
+                         cubes=c if n_c else None, n_cubes=n_c, planes=p if n_p else None, n_planes=n_p)

@@ -3,7 +3,14 @@ occluder lists, raygen tables, RtFrameAux, the sphere table, tile orders, the sp
 reused while a hand-written key says it is current. Here one scene goes through sequences of changes -- targeted
 transitions first, then seeded random walks (tests/scene_walk.py) -- and every output (rgba bits, packed, every rt_hit
 field, occlusion, reflect queue lengths) is compared with a fresh scene built from the current state alone. A few
-checkpoints compare with the oracle or the reflection composers directly, so that the check is not circular."""
+checkpoints compare with the oracle or the reflection composers directly, so that the check is not circular.
+
+The caches that came later are covered by tests/test_scene_state2_gpu.py with this file's helpers and the second
+vocabulary of tests/scene_walk.py: the reflect scope with the plane and cube material tables, the supersampling scratch
+and its per-group events, the view-list slots and their switch (also under a recorded graph), G-buffer outputs, the
+denoisers' shared scratch, temporal accumulation's raygen table, temporal_motion's host copies, guided upsampling and
+the wrapper's host mirrors of the material tables (Scene.upsample_select). The six walks of this file stay as they
+were, op for op (their digests are pinned in tests/test_scene_walk_cpu.py)."""
 import ctypes as C
 
 import numpy as np

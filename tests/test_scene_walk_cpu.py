@@ -1,9 +1,13 @@
 """The operation sequences of tests/test_scene_state_gpu.py (no GPU): deterministic per seed, within the library's rules,
-and covering every transition the state tests are there for. The state model's materials rule is DESIGN.md 6d's."""
+and covering every transition the state tests are there for. The state model's materials rule is DESIGN.md 6d's; the
+rules of the plane and cube materials, the scope and the sampling mode are rt_engine.h's. The first vocabulary's
+sequences are pinned by digest; the second vocabulary's walks must reach REQUIRED_2 and keep refusals rare."""
+import hashlib
+
 import numpy as np
 
 import scene_walk as sw
-from scene_walk import WALK_SEEDS, WALK_STEPS
+from scene_walk import WALK_SEEDS, WALK_SEEDS_2, WALK_STEPS
 
 # what the walks must reach over the GPU test's seeds
 REQUIRED = {
@@ -100,3 +104,203 @@ def test_materials_kept_and_cleared_as_design_6d_says():
     # the ex arrays carry glass, and the k arrays of both kinds of one seed are the same mirrors
     k_ex, tau_ex, _ = sw.material_arrays("ex", 3, 64)
     assert tau_ex.any() and np.array_equal(k_ex, k)
+
+
+# ------------------------------------------------------------------------------------------------ the second vocabulary
+# sha256 of repr(generate(seed, 60)) as the module gave it before it had a second vocabulary
+OLD_WALKS = {
+    1: "3d583f709ee6ab650e7cf81cfef6f64c694b067a1b942ce258fd4a2d5c6cad38",
+    2: "f15aa82666891577da7f8378c6bbff54ea7e3900f4df5715876fdf65a872ac82",
+    97: "e677782c7f7fc5b7020803a38da34d06f8b8fff74db3f0d78f2921161d609d3d",
+    13: "6f0ffb8bd36167a58bc3653b26ffe5a7014142e3244137b089020a0bc7b9467e",
+    22: "37f55e6d86995fc40dbc26ab3cda83134fe8f2f1cc4f879bb211d7048f4aaf0d",
+    29: "d93a939dec5b823120daea69f5a3568156a049b60e43b1aaf225ce7d9d588303",
+}
+
+REQUIRED_2 = {
+    *sw.MUTATIONS_2, *sw.OUTPUTS_2,
+    "scope:to_scene", "scope:to_spheres", "samples:to_many", "samples:to_one", "view_lists:off", "view_lists:on",
+    "planes:on", "planes:off", "planes:other_count", "planes:same_count_moved",
+    "cubes:on", "cubes:off", "cubes:other_count", "cubes:same_count_moved",
+    "plane_materials:set", "cube_materials:set", "cube_materials:clear",
+    "kind_materials:kept", "kind_materials:cleared_by_count",
+    "render:scene_scope_depth>0", "render:scene_scope_with_mesh", "render:many_two_groups",
+    "render:many_accumulate_split", "render:many_sample_range", "render:aov", "render:aov_reflective",
+    "refused:scope", "refused:samples",
+    "pass:denoise", "pass:vdenoise", "pass:vdenoise_history", "pass:upsample_exact2", "pass:upsample_exact3",
+    "pass:upsample_other_ratio",
+    "pass:render_upscaled",
+    "temporal:camera", "temporal:motion_spheres", "temporal:motion_cubes",
+    "pass_deferred_then_mutation", "graph_after:view_lists", "render_upscaled_after:materials_cleared_by_count",
+}
+GROUPS = ("scope:", "samples:", "pass:", "temporal:")
+
+
+def test_the_first_walks_are_what_they_were():
+    assert set(OLD_WALKS) == set(WALK_SEEDS) and WALK_STEPS == 60
+    for seed, digest in OLD_WALKS.items():
+        assert hashlib.sha256(repr(sw.generate(seed, 60)).encode()).hexdigest() == digest, seed
+        assert sw.generate(seed, 60, vocabulary=1) == sw.generate(seed, 60)
+
+
+def test_second_generator_is_deterministic_per_seed():
+    for seed in WALK_SEEDS_2:
+        ops = sw.generate(seed, WALK_STEPS, vocabulary=2)
+        assert ops == sw.generate(seed, WALK_STEPS, vocabulary=2) == sw.generate_2(seed, WALK_STEPS)
+        assert len(ops) == WALK_STEPS and all(op["op"] in sw.MUTATIONS_2 + sw.OUTPUTS_2 for op in ops)
+    assert sw.generate(WALK_SEEDS_2[0], WALK_STEPS, vocabulary=2) != sw.generate(WALK_SEEDS_2[1], WALK_STEPS, vocabulary=2)
+
+
+def test_second_walks_cover_every_transition():
+    walks = {label: 0 for label in REQUIRED_2}
+    for seed in WALK_SEEDS_2:
+        one = sw.transitions(sw.generate(seed, WALK_STEPS, vocabulary=2))
+        for g in GROUPS:                              # every single walk: the scope, the samples, a pass, temporal
+            assert any(label.startswith(g) for label in one), (seed, g)
+        for label in one & REQUIRED_2:
+            walks[label] += 1
+    thin = sorted(label for label, n in walks.items() if n < 2)   # no transition rests on one walk alone
+    assert not thin, thin
+
+
+def test_refusals_are_the_headers_and_rare():
+    """A refused step asks for what rt_engine.h names RT_ERR_UNSUPPORTED in the step's state, and nothing else is
+    refused: at most a quarter of a walk's output steps."""
+    for seed in WALK_SEEDS_2:
+        state = sw.State()
+        outputs = refused = 0
+        for i, op in enumerate(sw.generate(seed, WALK_STEPS, vocabulary=2)):
+            where = "seed %d step %d: %s" % (seed, i, op)
+            if op["op"] in sw.OUTPUTS_2:
+                outputs += 1
+            if op["op"] == "refused":
+                refused += 1
+                assert 1 <= op["depth"] <= 3, where
+                if op["why"] == "scope":
+                    assert state.scope == "spheres" and (state.planes or state.cubes or state.mesh), where
+                    assert op["request"] == {}, where
+                else:
+                    assert op["why"] == "samples" and state.samples == "one" and state.reflect_ok(), where
+                    r = op["request"]
+                    assert r.get("spp", 1) > 1 or r.get("sample_base", 0) != 0 or r.get("sample_total", 0) > 1 \
+                        or r.get("accumulate"), where
+                    n, total = r.get("spp", 1), r.get("sample_total", 0) or r.get("spp", 1)
+                    assert 0 <= r.get("sample_base", 0) and r.get("sample_base", 0) + n <= total <= 16, where
+            state = sw.apply(state, op)
+        assert refused >= 1 and 4 * refused <= outputs, (seed, refused, outputs)
+
+
+def test_second_walks_respect_the_library_rules():
+    for seed in WALK_SEEDS_2:
+        state = sw.State()
+        for i, op in enumerate(sw.generate(seed, WALK_STEPS, vocabulary=2)):
+            where = "seed %d step %d: %s" % (seed, i, op)
+            k = op["op"]
+            if k == "render":
+                w, h = op["size"]
+                y0, y1 = op["band"]
+                assert (w, h) in sw.SIZES and (op["band"] == (0, 0) or 0 <= y0 < y1 <= h), where
+                n, base, total = op["spp"], op["sample_base"], op["sample_total"]
+                assert n in (1, 2, 4, 5) and 0 <= op["depth"] <= 3, where
+                assert total == 0 or (0 <= base and base + n <= total <= 16), where
+                if op["depth"]:
+                    assert state.reflect_ok(), where
+                    if n > 1 or total or op["split"]:
+                        assert state.samples == "many", where
+                else:
+                    assert n in (1, 2, 4) and not total and not op["split"], where
+                if op["split"]:
+                    assert 1 <= op["split"] < n and not total, where
+                if op["aov"]:                         # guides: one sample
+                    assert n == 1 and total == 0 and not op["split"] and set(op["aov"]) <= set(sw.AOV), where
+            elif k == "pass":
+                assert op["what"] in ("denoise", "vdenoise", "upsample", "render_upscaled"), where
+                if op["what"] == "render_upscaled" or op.get("depth"):
+                    assert state.reflect_ok(), where
+                if op["what"] in ("upsample", "render_upscaled"):
+                    assert op["factor"] in (2, 3) and min(op["size"]) // op["factor"] >= 1, where
+                    if op["factor"] == 2:             # "exact2" is what it says at every size of the pool
+                        assert not (op["size"][0] % 2 or op["size"][1] % 2), where
+            elif k == "temporal":
+                m = op["mutation"]
+                assert (m is None) == (op["form"] == "camera"), where
+                a, b = op["cams"]                     # two views: the second frame reprojects the first's history
+                assert a != b and sw.CAMERAS[a] != sw.CAMERAS[b], where
+                if m is not None:                     # the counts stay: the history's displacements are defined
+                    after = sw.apply(state, m)
+                    assert (after.n, after.n_cubes) == (state.n, state.n_cubes) and after != state, where
+                    assert m["how"] in ("same_count", "same_count_moved"), where
+            elif k in ("planes", "cubes"):
+                specs = sw.PLANE_SPECS if k == "planes" else sw.CUBE_SPECS
+                assert op[k] is None or op[k] in specs, where
+                old, new = sw.spec_of(getattr(state, k), specs), sw.spec_of(op[k], specs)
+                assert {"on": old[0] == 0 < new[0], "off": new[0] == 0 < old[0],
+                        "same_count_moved": old[0] == new[0] > 0 and old != new,
+                        "other_count": 0 < old[0] != new[0] > 0}[op["how"]], where
+            elif k in ("plane_materials", "cube_materials") and op["seed"] is not None:
+                n = state.n_planes if k == "plane_materials" else state.n_cubes
+                assert n > 0 and set(sw.kind_k(op["seed"], n).tolist()) <= set(sw.KIND_K), where
+            elif k == "materials" and op["mats"] is not None:
+                assert state.n > 0, where
+            state = sw.apply(state, op)
+
+
+def test_kind_tables_scope_and_samples_follow_the_header():
+    """rt_engine.h: the plane / cube tables survive set_planes / set_cubes with the same count and are cleared by a
+    different count; the scope and the sampling mode survive everything."""
+    s = sw.State(planes=(2, 0), cubes=(5, 0), scope="scene", samples="many", view_lists=0)
+    s = sw.apply(s, {"op": "plane_materials", "seed": 3})
+    s = sw.apply(s, {"op": "cube_materials", "seed": 4})
+    moved = sw.apply(s, {"op": "cubes", "cubes": (5, 1)})
+    assert (moved.cube_mats, moved.plane_mats) == (4, 3)                                  # same count: kept
+    fewer = sw.apply(moved, {"op": "cubes", "cubes": (4, 1)})
+    assert fewer.cube_mats is None and fewer.plane_mats == 3                              # another count: that table only
+    assert sw.apply(fewer, {"op": "cubes", "cubes": (5, 1)}).cube_mats is None            # and it does not come back
+    assert sw.apply(s, {"op": "cubes", "cubes": None}).cube_mats is None
+    assert sw.apply(s, {"op": "planes", "planes": (2, 1)}).plane_mats == 3
+    assert sw.apply(s, {"op": "planes", "planes": (1, 0)}).plane_mats is None
+    assert sw.apply(s, {"op": "planes", "planes": True}).plane_mats == 3                  # the first vocabulary's "on": 2 planes
+    assert sw.apply(s, {"op": "plane_materials", "seed": None}).plane_mats is None
+    assert sw.apply(s, {"op": "spheres", "spheres": (65, 1, 0.0)}).cube_mats == 4         # the spheres' count is no key
+    ops = [{"op": "spheres", "spheres": (8, 2, 0.0)}, {"op": "planes", "planes": None}, {"op": "cubes", "cubes": (4, 0)},
+           {"op": "mesh", "mesh": 2}, {"op": "materials", "mats": None}, {"op": "lights", "lights": sw.DEFAULT_LIGHTS[:1]},
+           {"op": "cube_materials", "seed": None}, {"op": "tile_order", "tile_order": 0}]
+    for op in ops:
+        s = sw.apply(s, op)
+        assert (s.scope, s.samples, s.view_lists) == ("scene", "many", 0), op
+    # reflect_ok: the scene scope, or nothing but spheres
+    assert s.reflect_ok() and not sw.apply(s, {"op": "scope", "scope": "spheres"}).reflect_ok()
+    for field, value in (("planes", (1, 0)), ("cubes", (4, 1)), ("mesh", 1), ("mesh", 2)):
+        assert not sw.State(**{field: value}).reflect_ok() and sw.State(scope="scene", **{field: value}).reflect_ok()
+    assert sw.State().reflect_ok()
+    # a temporal step carries its mutation into the state
+    t = {"op": "temporal", "mutation": {"op": "spheres", "spheres": (256, 1, 0.25)}}
+    assert sw.apply(sw.State(), t).spheres == (256, 1, 0.25)
+    assert sw.apply(sw.State(), {"op": "temporal", "mutation": None}) == sw.State()
+
+
+def test_the_variants_of_the_lists(rt):
+    """The plane and cube lists of a spec: the first `count` primitives of the mixed scene, one of them translated in
+    variant 1; the displacement tables are the difference of the two states' origins in binary32."""
+    full_p, n_p, full_c, n_c = sw.planes_cubes(rt)
+    assert (n_p, n_c) == (sw.PLANE_SPECS[0][0], sw.CUBE_SPECS[0][0])
+    raw = lambda arr, i: bytes(arr[i])
+    for count, variant in sw.CUBE_SPECS:
+        arr, n = sw.cube_list(rt, (count, variant))
+        assert n == count
+        for i in range(count):
+            assert (raw(arr, i) == raw(full_c, i)) == (not (variant and i == 1)), (count, variant, i)
+    for count, variant in sw.PLANE_SPECS:
+        arr, n = sw.plane_list(rt, (count, variant))
+        assert n == count
+        for i in range(count):
+            assert (raw(arr, i) == raw(full_p, i)) == (not (variant and i == count - 1)), (count, variant, i)
+    a, b = sw.State(spheres=(8, 1, 0.0), cubes=(5, 0)), sw.State(spheres=(8, 1, 0.25), cubes=(5, 1))
+    sm, cm = sw.motion_tables(rt, a, b)
+    # (fl(y + 0.25) - y is 0.25 up to the rounding of the sum)
+    assert sm.shape == (8, 4) and not sm[:, [0, 2, 3]].any() and np.abs(sm[:, 1] - 0.25).max() < 1e-6
+    assert cm.shape == (5, 4) and np.abs(cm[1, :3] - np.float32(sw.CUBE_MOVE)).max() < 1e-6 and not cm[[0, 2, 3, 4]].any()
+    oa, ob = sw.origins(rt, a), sw.origins(rt, b)
+    assert np.array_equal(sm[:, :3], ob[0] - oa[0]) and np.array_equal(cm[:, :3], ob[1] - oa[1])
+    sm, cm = sw.motion_tables(rt, a, sw.State(spheres=(8, 1, 0.0), cubes=(5, 1)))
+    assert sm.shape == (0, 4) and cm.shape == (5, 4)
