@@ -241,15 +241,12 @@ int rt_denoise_launch(const RtAtrousDesc *d, float4 *col0, float4 *col1, float4 
 int rt_vdenoise_launch(const RtAtrousDesc *d, float4 *col0, float4 *col1, float4 *guide, int *key, float *var0,
                        float *var1, bool lds16, hipEvent_t *ev, hipStream_t stream);
 
-// rt_temporal.hip: temporal accumulation (d: validated, in this build's layout; dx_tab / dy_tab: the current view's ray
-// tables at one sample; view[7] / prev_view[7]: rt_view_terms of the two views; same_view: they are the same bytes;
-// ev: null, or two timing events)
-int rt_temporal_launch(const rt_temporal_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
+// rt_temporal.hip: temporal accumulation, both entries (d: validated, in this build's layout, for
+// rt_scene_temporal with no motion table and no clamp; dx_tab / dy_tab: the current view's ray tables at one sample,
+// needed with identical views too once an object moved; view[7] / prev_view[7]: rt_view_terms of the two views;
+// same_view: they are the same bytes; ev: null, or two timing events)
+int rt_temporal_launch(const rt_tmotion_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
                        const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream);
-// the same for rt_scene_temporal_motion; dx_tab / dy_tab are needed with identical views too once an
-// object moved
-int rt_tmotion_launch(const rt_tmotion_desc *d, const float *dx_tab, const float *dy_tab, const float view[7],
-                      const float prev_view[7], bool same_view, hipEvent_t *ev, hipStream_t stream);
 
 // rt_upsample.hip: guided upsampling (d: validated, in this build's layout; ev: null, or two timing events)
 int rt_upsample_launch(const rt_upsample_desc *d, hipEvent_t *ev, hipStream_t stream);

@@ -529,6 +529,28 @@ extern "C" int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd_in, rt
     return rt_scene_note_launch(s, stream, nullptr, nullptr);   // it reads the raygen tables
 }
 
+// A buffer that a post pass reads or writes (p: 0 if the call does not use it).
+struct Range {
+    uintptr_t p;
+    size_t bytes;
+};
+// What the post passes refuse: `in_message` if an output overlaps an input, but for outs[0] being ins[alias] itself
+// (alias < 0: no input may be written in place), or that two outputs overlap; null if neither.
+template <size_t NOUT, size_t NIN>
+static const char *overlap_message(const Range (&outs)[NOUT], const Range (&ins)[NIN], int alias, const char *in_message)
+{
+    auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
+    for (size_t i = 0; i < NOUT; ++i) {
+        const char *bad = nullptr;
+        for (size_t k = 0; k < NIN; ++k)
+            if (overlap(outs[i], ins[k]) && !(i == 0 && (int)k == alias && outs[0].p == ins[k].p)) bad = in_message;
+        for (size_t j = i + 1; j < NOUT; ++j)
+            if (overlap(outs[i], outs[j])) bad = "two output buffers overlap";
+        if (bad) return bad;
+    }
+    return nullptr;
+}
+
 // ---------------------------------------------------------------------------
 // the two a-trous denoisers (rt_denoise.hip): the G-buffer-guided one and the variance-guided one
 // (DESIGN.md 6j). One host path, denoise_call; each keeps its own timing state
@@ -590,10 +612,6 @@ static RtAtrousDesc atrous_desc(const D &d, bool plain)
 // buffers for overlaps.
 static int denoise_call(rt_scene *s, const RtAtrousDesc &d, const char *name, hipStream_t stream)
 {
-    struct Range {
-        uintptr_t p;
-        size_t bytes;
-    };
     const char *bad = nullptr;
     if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
         bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
@@ -618,14 +636,7 @@ static int denoise_call(rt_scene *s, const RtAtrousDesc &d, const char *name, hi
         const Range outs[3] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.pixels, npx * 4}, {(uintptr_t)d.variance_out, npx * 4}};
         const Range ins[6] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16},
                               {(uintptr_t)d.albedo, npx * 16}, {(uintptr_t)d.id, npx * 8}, {(uintptr_t)d.moments, npx * 8}};
-        auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
-        for (int i = 0; i < 3 && !bad; ++i) {
-            for (int k = 0; k < 6; ++k)
-                if (overlap(outs[i], ins[k]) && !(i == 0 && k == 0 && d.rgba_out == d.rgba_in))
-                    bad = "an output buffer overlaps an input (only rgba_out may be rgba_in itself)";
-            for (int j = i + 1; j < 3; ++j)
-                if (overlap(outs[i], outs[j])) bad = "two output buffers overlap";
-        }
+        bad = overlap_message(outs, ins, 0, "an output buffer overlaps an input (only rgba_out may be rgba_in itself)");
     }
     if (bad) {
         if (d.plain)
@@ -712,7 +723,8 @@ extern "C" int rt_scene_denoise_variance(rt_scene *s, const rt_vdenoise_desc *d_
     return denoise_call(s, a, "rt_scene_denoise_variance", (hipStream_t)stream_);
 }
 
-static int denoise_set_timing(rt_scene *s, const char *name, bool rt_scene::*timing, int on)
+// The timing switch and the timings of every post pass (`name` for the messages).
+static int pass_set_timing(rt_scene *s, const char *name, bool rt_scene::*timing, int on)
 {
     if (!s) {
         rt_set_error("%s: null scene", name);
@@ -722,16 +734,18 @@ static int denoise_set_timing(rt_scene *s, const char *name, bool rt_scene::*tim
     return RT_OK;
 }
 
-// ms[i]: between events i and i + 1 of the `timed` events the entry's last timed call recorded
-static int denoise_times(rt_scene *s, const char *name, const HipEvent *ev, int timed, float *ms, int cap, int *n)
+// ms[i]: between events i and i + 1 of the `timed` events the entry's last timed call recorded; done: what that call
+// recorded behind its work
+static int pass_times(rt_scene *s, const char *name, HipPendingEvent rt_scene::*done, const HipEvent *ev, int timed, float *ms,
+                      int cap, int *n)
 {
     if (!s || !ms || !n || cap < 0) {
         rt_set_error("%s: null argument", name);
         return RT_ERR_INVALID;
     }
     *n = 0;
-    if (timed < 2) return RT_OK;
-    RT_HIP(s->dn_done.host_wait());
+    if (timed < 2 || cap < 1) return RT_OK;
+    RT_HIP((s->*done).host_wait());
     for (int i = 0; i + 1 < timed && i < cap; ++i) {
         RT_HIP(hipEventElapsedTime(&ms[i], ev[i].get(), ev[i + 1].get()));
         *n = i + 1;
@@ -741,22 +755,22 @@ static int denoise_times(rt_scene *s, const char *name, const HipEvent *ev, int 
 
 extern "C" int rt_scene_set_denoise_timing(rt_scene *s, int on)
 {
-    return denoise_set_timing(s, "rt_scene_set_denoise_timing", &rt_scene::dn_timing, on);
+    return pass_set_timing(s, "rt_scene_set_denoise_timing", &rt_scene::dn_timing, on);
 }
 
 extern "C" int rt_scene_denoise_times(rt_scene *s, float *ms, int cap, int *n)
 {
-    return denoise_times(s, "rt_scene_denoise_times", s ? s->dn_ev : nullptr, s ? s->dn_timed : 0, ms, cap, n);
+    return pass_times(s, "rt_scene_denoise_times", &rt_scene::dn_done, s ? s->dn_ev : nullptr, s ? s->dn_timed : 0, ms, cap, n);
 }
 
 extern "C" int rt_scene_set_vdenoise_timing(rt_scene *s, int on)
 {
-    return denoise_set_timing(s, "rt_scene_set_vdenoise_timing", &rt_scene::vd_timing, on);
+    return pass_set_timing(s, "rt_scene_set_vdenoise_timing", &rt_scene::vd_timing, on);
 }
 
 extern "C" int rt_scene_vdenoise_times(rt_scene *s, float *ms, int cap, int *n)
 {
-    return denoise_times(s, "rt_scene_vdenoise_times", s ? s->vd_ev : nullptr, s ? s->vd_timed : 0, ms, cap, n);
+    return pass_times(s, "rt_scene_vdenoise_times", &rt_scene::dn_done, s ? s->vd_ev : nullptr, s ? s->vd_timed : 0, ms, cap, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -801,10 +815,6 @@ constexpr size_t kTemporalShared = offsetof(rt_temporal_desc, variant) + sizeof(
 static int temporal_call(rt_scene *s, const rt_tmotion_desc &d, bool motion, const char *name, hipStream_t stream)
 {
     const bool reset = d.reset != 0;
-    struct Range {
-        uintptr_t p;
-        size_t bytes;
-    };
     const char *bad = nullptr;
     if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
         bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
@@ -840,13 +850,7 @@ static int temporal_call(rt_scene *s, const rt_tmotion_desc &d, bool motion, con
                                {reset ? 0 : (uintptr_t)d.prev_moments, npx * 8},
                                {d.n_sphere_motion > 0 ? (uintptr_t)d.sphere_motion : 0, (size_t)d.n_sphere_motion * 16},
                                {d.n_cube_motion > 0 ? (uintptr_t)d.cube_motion : 0, (size_t)d.n_cube_motion * 16}};
-        auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
-        for (int i = 0; i < 3 && !bad; ++i) {
-            for (const Range &in : ins)
-                if (overlap(outs[i], in)) bad = "an output buffer overlaps an input (the pass gathers: it cannot run in place)";
-            for (int j = i + 1; j < 3; ++j)
-                if (overlap(outs[i], outs[j])) bad = "two output buffers overlap";
-        }
+        bad = overlap_message(outs, ins, -1, "an output buffer overlaps an input (the pass gathers: it cannot run in place)");
     }
     if (bad) {
         rt_set_error("%s: %s (%d x %d, max_history %d, variant %d)", name, bad, d.width, d.height, d.max_history, d.variant);
@@ -885,16 +889,7 @@ static int temporal_call(rt_scene *s, const rt_tmotion_desc &d, bool motion, con
         }
     }
     const float *dx_tab = need_rays ? s->tp_raygen.get() : nullptr, *dy_tab = need_rays ? s->tp_raygen.get() + d.width : nullptr;
-    int rc;
-    if (motion) {
-        rc = rt_tmotion_launch(&d, dx_tab, dy_tab, view, prev_view, same_view, s->tp_timing ? ev : nullptr, stream);
-    } else {
-        rt_temporal_desc td;
-        memset(&td, 0, sizeof td);
-        memcpy(&td, &d, kTemporalShared);
-        td.struct_size = (uint32_t)sizeof td;
-        rc = rt_temporal_launch(&td, dx_tab, dy_tab, view, prev_view, same_view, s->tp_timing ? ev : nullptr, stream);
-    }
+    const int rc = rt_temporal_launch(&d, dx_tab, dy_tab, view, prev_view, same_view, s->tp_timing ? ev : nullptr, stream);
     RT_HIP(s->tp_done.record(stream));
     if (rc == RT_OK && s->tp_timing) s->tp_timed = 2;
     return rc;
@@ -941,26 +936,12 @@ extern "C" int rt_scene_temporal_motion(rt_scene *s, const rt_tmotion_desc *d_in
 
 extern "C" int rt_scene_set_temporal_timing(rt_scene *s, int on)
 {
-    if (!s) {
-        rt_set_error("rt_scene_set_temporal_timing: null scene");
-        return RT_ERR_INVALID;
-    }
-    s->tp_timing = on != 0;
-    return RT_OK;
+    return pass_set_timing(s, "rt_scene_set_temporal_timing", &rt_scene::tp_timing, on);
 }
 
 extern "C" int rt_scene_temporal_times(rt_scene *s, float *ms, int cap, int *n)
 {
-    if (!s || !ms || !n || cap < 0) {
-        rt_set_error("rt_scene_temporal_times: null argument");
-        return RT_ERR_INVALID;
-    }
-    *n = 0;
-    if (s->tp_timed < 2 || cap < 1) return RT_OK;
-    RT_HIP(s->tp_done.host_wait());
-    RT_HIP(hipEventElapsedTime(&ms[0], s->tp_ev[0].get(), s->tp_ev[1].get()));
-    *n = 1;
-    return RT_OK;
+    return pass_times(s, "rt_scene_temporal_times", &rt_scene::tp_done, s ? s->tp_ev : nullptr, s ? s->tp_timed : 0, ms, cap, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -985,10 +966,6 @@ extern "C" int rt_scene_upsample(rt_scene *s, const rt_upsample_desc *d_in, void
     }
     rt_upsample_desc d;
     as_built(d_in, &d);
-    struct Range {
-        uintptr_t p;
-        size_t bytes;
-    };
     const char *bad = nullptr;
     if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE ||
         d.lo_width <= 0 || d.lo_height <= 0)
@@ -1019,14 +996,7 @@ extern "C" int rt_scene_upsample(rt_scene *s, const rt_upsample_desc *d_in, void
                                {d.n_sphere_select > 0 ? (uintptr_t)d.sphere_select : 0, (size_t)d.n_sphere_select},
                                {d.n_plane_select > 0 ? (uintptr_t)d.plane_select : 0, (size_t)d.n_plane_select},
                                {d.n_cube_select > 0 ? (uintptr_t)d.cube_select : 0, (size_t)d.n_cube_select}};
-        auto overlap = [](const Range &a, const Range &b) { return a.p && b.p && a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
-        for (int i = 0; i < 3 && !bad; ++i) {
-            for (int k = 0; k < 13; ++k)
-                if (overlap(outs[i], ins[k]) && !(i == 0 && k == 9 && d.rgba_out == d.base))
-                    bad = "an output buffer overlaps an input (only rgba_out may be base itself)";
-            for (int j = i + 1; j < 3; ++j)
-                if (overlap(outs[i], outs[j])) bad = "two output buffers overlap";
-        }
+        bad = overlap_message(outs, ins, 9, "an output buffer overlaps an input (only rgba_out may be base itself)");
     }
     if (bad) {
         rt_set_error("rt_scene_upsample: %s (%d x %d from %d x %d, normal_shift %d, variant %d)", bad, d.width, d.height,
@@ -1054,24 +1024,10 @@ extern "C" int rt_scene_upsample(rt_scene *s, const rt_upsample_desc *d_in, void
 
 extern "C" int rt_scene_set_upsample_timing(rt_scene *s, int on)
 {
-    if (!s) {
-        rt_set_error("rt_scene_set_upsample_timing: null scene");
-        return RT_ERR_INVALID;
-    }
-    s->up_timing = on != 0;
-    return RT_OK;
+    return pass_set_timing(s, "rt_scene_set_upsample_timing", &rt_scene::up_timing, on);
 }
 
 extern "C" int rt_scene_upsample_times(rt_scene *s, float *ms, int cap, int *n)
 {
-    if (!s || !ms || !n || cap < 0) {
-        rt_set_error("rt_scene_upsample_times: null argument");
-        return RT_ERR_INVALID;
-    }
-    *n = 0;
-    if (s->up_timed < 2 || cap < 1) return RT_OK;
-    RT_HIP(s->up_done.host_wait());
-    RT_HIP(hipEventElapsedTime(&ms[0], s->up_ev[0].get(), s->up_ev[1].get()));
-    *n = 1;
-    return RT_OK;
+    return pass_times(s, "rt_scene_upsample_times", &rt_scene::up_done, s ? s->up_ev : nullptr, s ? s->up_timed : 0, ms, cap, n);
 }

@@ -484,7 +484,7 @@ def test_denoise_variance(rt, scene, w, h):
 def test_temporal_motion(rt, scene, w, h):
     """rt_scene_temporal_motion into arenas for rgba_out, moments_out and pixels, with every second sphere that the
     frames show displaced: under the moved view every hit pixel is reprojected; under the identical view the movers go
-    through tm_product's reprojection and exchange while the static lanes of the same waves take the single tap."""
+    through tp_product<MOTION>'s reprojection and exchange while the static lanes of the same waves take the single tap."""
     import torch
     cams = [_camera(rt, 0), _camera(rt, 1)]
     frames = [scene.render(w, h, cam=c, aov=GUIDES) for c in cams]

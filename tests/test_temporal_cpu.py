@@ -49,7 +49,7 @@ class View:
 
 
 # The wide path: the GPU tests' path with the yaw turned to 170, for buffers of more than eight tile
-# columns (tp_product / tm_product pad their grid to a multiple of eight 64-pixel columns) and of more than eight
+# columns (tp_product pads its grid to a multiple of eight 64-pixel columns, with MOTION too) and of more than eight
 # 256-pixel row segments (dn_iter_direct). With yaw 180 columns 512 .. 575 of a 576 x 36 frame show no sphere at all.
 WIDE_CAMS = ((4, 3, 10, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.7, 3.1, 10.1, 166, -21))
 WIDE_BLOCK = 64                 # a tile column of the two temporal product kernels

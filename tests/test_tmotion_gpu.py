@@ -152,7 +152,7 @@ def test_sizes_that_are_no_multiple_of_the_tiles(rt, gpu, w, h):
 
 @pytest.mark.parametrize("w,h,movers", [(576, 36, 1), (1088, 36, 2)])
 def test_more_than_eight_tile_columns(rt, gpu, w, h, movers):
-    """tm_product has tp_product's grid, padded to a multiple of eight 64-pixel tile columns, and leaves in the tiles
+    """With MOTION tp_product keeps its grid, padded to a multiple of eight 64-pixel tile columns, and leaves in the tiles
     of the padding; at every width up to 512 the padded width is 8 columns. Here 9 and 17 columns (16 and 24 padded),
     along test_temporal_gpu's wide path, and the displaced spheres are picked among those seen in columns >= 512, so
     that movers -- the reprojection with a displacement, the exchange between lanes, the clamp's staged tile -- run in
