@@ -877,27 +877,124 @@ class Scene:
         hit = self.trace_rays(self.primary_rays(width, height, y0=y, y1=y + 1, **kw)[0, x:x + 1], "nearest")
         return int(hit["kind"][0]), int(hit["index"][0])
 
+    # ---------------------------------------------------------------- what the post passes below share
+    def _desc(self, cls, init, plain, optional=None, flags=None):
+        """A `cls` after self.lib.<init>: `plain` assigned as it is, `optional` where not None, `flags` (where not
+        None) as 0 / 1."""
+        d = cls()
+        getattr(self.lib, init)(C.byref(d))
+        for k, v in plain.items():
+            setattr(d, k, v)
+        for k, v in (optional or {}).items():
+            if v is not None:
+                setattr(d, k, v)
+        for k, v in (flags or {}).items():
+            if v is not None:
+                setattr(d, k, 1 if v else 0)
+        return d
+
+    @staticmethod
+    def _need_gpu(what):
+        """torch, or RtError where no GPU is visible."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RtError(f"no GPU visible: {what} has no CPU fallback")
+        return torch
+
+    @staticmethod
+    def _guides(frame, colour, need, message):
+        """The frame's G-buffer outputs, or RtError(message) without a colour or one of the guides `need`."""
+        aov = frame.get("aov") or {}
+        if colour is None or any(k not in aov for k in need):
+            raise RtError(message)
+        return aov
+
+    @staticmethod
+    def _cuda_colour(torch, name, rgba, rows, width):
+        if tuple(rgba.shape) != (rows, width, 4) or rgba.dtype != torch.float32 or not rgba.is_cuda:
+            raise RtError(f"{name}: the colour must be a CUDA float32 tensor of the guides' shape [rows, W, 4]")
+        return rgba.contiguous()
+
+    @staticmethod
+    def _stream(torch, stream):
+        return torch.cuda.current_stream() if stream is None else stream
+
+    @staticmethod
+    def _new(torch, want, like, shape, dtype):
+        """A new tensor on `like`'s device, or None."""
+        return torch.empty(shape, dtype=dtype, device=like.device) if want else None
+
+    @staticmethod
+    def _ptr(t):
+        return t.data_ptr() if t is not None else 0
+
+    @classmethod
+    def _prev(cls, history):
+        """temporal_desc's prev_* of a history."""
+        if history is None:
+            return {}
+        return dict(prev_cam=history["cam"], prev_aspect=history["aspect"], prev_rgba=history["rgba"].data_ptr(),
+                    prev_depth=history["depth"].data_ptr(), prev_normal=history["normal"].data_ptr(),
+                    prev_id=history["id"].data_ptr(), prev_moments=cls._ptr(history.get("moments")))
+
+    def _set_pass_timing(self, name, on):
+        fn = f"rt_scene_set_{name}_timing"
+        _check(getattr(self.lib, fn)(self.handle, 1 if on else 0), fn)
+
+    def _pass_times(self, name, cap):
+        fn = f"rt_scene_{name}_times"
+        ms = (C.c_float * cap)()
+        n = C.c_int()
+        _check(getattr(self.lib, fn)(self.handle, ms, cap, C.byref(n)), fn)
+        return list(ms)[: n.value]
+
     # ---------------------------------------------------------------- the denoiser (DESIGN.md 6f)
     def denoise_desc(self, width, height, *, rgba_in=0, depth=0, normal=0, albedo=0, id=0, rgba_out=0, pixels=0,
                      iterations=None, normal_shift=None, sigma_depth=None, sigma_colour=None, demodulate=None,
                      variant=0) -> DenoiseDesc:
         """rt_denoise_desc with rt_denoise_desc_init's defaults where an argument is None."""
-        d = DenoiseDesc()
-        self.lib.rt_denoise_desc_init(C.byref(d))
-        d.width, d.height = width, height
-        d.rgba_in, d.depth, d.normal, d.albedo, d.id = rgba_in, depth, normal, albedo, id
-        d.rgba_out, d.pixels = rgba_out, pixels
-        for k, v in (("iterations", iterations), ("normal_shift", normal_shift), ("sigma_depth", sigma_depth),
-                     ("sigma_colour", sigma_colour), ("variant", variant)):
-            if v is not None:
-                setattr(d, k, v)
-        if demodulate is not None:
-            d.demodulate = 1 if demodulate else 0
-        return d
+        return self._desc(DenoiseDesc, "rt_denoise_desc_init",
+                          dict(width=width, height=height, rgba_in=rgba_in, depth=depth, normal=normal, albedo=albedo,
+                               id=id, rgba_out=rgba_out, pixels=pixels),
+                          dict(iterations=iterations, normal_shift=normal_shift, sigma_depth=sigma_depth,
+                               sigma_colour=sigma_colour, variant=variant),
+                          dict(demodulate=demodulate))
 
     def denoise_raw(self, d: DenoiseDesc, stream=0) -> int:
         """rt_scene_denoise as is: returns the status."""
         return self.lib.rt_scene_denoise(self.handle, C.byref(d), stream)
+
+    def _denoise(self, variance, frame, history, want_packed, want_variance, stream, **knobs):
+        """denoise (variance False: no history, rows and width from the colour as it is) and denoise_variance."""
+        torch = self._need_gpu("the denoiser")
+        rgba = frame.get("rgba") if history is None else history.get("rgba")
+        moments = None if history is None else history.get("moments")
+        demodulate = knobs["demodulate"]
+        need = ("depth", "normal", "id") + (() if demodulate is not None and not demodulate else ("albedo",))
+        colour = "a colour (the frame's rgba or the history's)" if variance else "the frame's rgba"
+        aov = self._guides(frame, rgba, need, f"{'denoise_variance' if variance else 'denoise'} needs {colour} and the "
+                           f"G-buffer outputs {need}: render with want_rgba=True and aov={AOV_NAMES}")
+        if variance:
+            if history is not None and moments is None:
+                raise RtError("denoise_variance: the history carries no moments (Scene.temporal(..., want_moments=True))")
+            rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
+            if tuple(rgba.shape) != (rows, width, 4):
+                raise RtError("denoise_variance: the colour is not of the guides' shape [rows, W, 4]")
+        else:
+            rows, width = rgba.shape[0], rgba.shape[1]
+        out = torch.empty_like(rgba)
+        packed = self._new(torch, want_packed, rgba, (rows, width), torch.int32)
+        var = self._new(torch, want_variance, rgba, (rows, width), torch.float32)
+        st = self._stream(torch, stream)
+        args = dict(rgba_in=rgba.data_ptr(), depth=aov["depth"].data_ptr(), normal=aov["normal"].data_ptr(),
+                    albedo=self._ptr(aov.get("albedo")), id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
+                    pixels=self._ptr(packed), **knobs)
+        if variance:
+            d = self.vdenoise_desc(width, rows, moments=self._ptr(moments), variance_out=self._ptr(var), **args)
+            _check(self.denoise_variance_raw(d, st.cuda_stream), "rt_scene_denoise_variance")
+            return {"rgba": out, "packed": packed, "variance": var}
+        _check(self.denoise_raw(self.denoise_desc(width, rows, **args), st.cuda_stream), "rt_scene_denoise")
+        return {"rgba": out, "packed": packed}
 
     def denoise(self, frame, *, iterations=None, normal_shift=None, sigma_depth=None, sigma_colour=None,
                 demodulate=None, want_packed=True, variant=0, stream=None):
@@ -905,45 +1002,22 @@ class Scene:
         a-trous filter of rt_scene_denoise (None: the default of rt_denoise_desc_init; demodulate=False needs no
         albedo). Returns {'rgba': float32 [rows, W, 4], 'packed': int32 [rows, W] or None} as new tensors; the frame's
         own tensors are not written. Enqueued on `stream` (default: the current stream); no host wait."""
-        import torch
-        if not torch.cuda.is_available():
-            raise RtError("no GPU visible: the denoiser has no CPU fallback")
-        rgba, aov = frame.get("rgba"), frame.get("aov") or {}
-        need = ("depth", "normal", "id") + (() if demodulate is not None and not demodulate else ("albedo",))
-        if rgba is None or any(k not in aov for k in need):
-            raise RtError(f"denoise needs the frame's rgba and the G-buffer outputs {need}: render with want_rgba=True "
-                          f"and aov={AOV_NAMES}")
-        rows, width = rgba.shape[0], rgba.shape[1]
-        out = torch.empty_like(rgba)
-        packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
-        st = torch.cuda.current_stream() if stream is None else stream
-        d = self.denoise_desc(width, rows, rgba_in=rgba.data_ptr(), depth=aov["depth"].data_ptr(),
-                              normal=aov["normal"].data_ptr(), albedo=aov["albedo"].data_ptr() if "albedo" in aov else 0,
-                              id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
-                              pixels=packed.data_ptr() if want_packed else 0, iterations=iterations,
-                              normal_shift=normal_shift, sigma_depth=sigma_depth, sigma_colour=sigma_colour,
-                              demodulate=demodulate, variant=variant)
-        _check(self.denoise_raw(d, st.cuda_stream), "rt_scene_denoise")
-        return {"rgba": out, "packed": packed}
+        return self._denoise(False, frame, None, want_packed, False, stream, iterations=iterations,
+                             normal_shift=normal_shift, sigma_depth=sigma_depth, sigma_colour=sigma_colour,
+                             demodulate=demodulate, variant=variant)
 
     # ---------------------------------------------------------------- the variance-guided denoiser (DESIGN.md 6j)
     def vdenoise_desc(self, width, height, *, rgba_in=0, depth=0, normal=0, albedo=0, id=0, rgba_out=0, pixels=0,
                       moments=0, variance_out=0, iterations=None, normal_shift=None, sigma_depth=None, sigma_colour=None,
                       sigma_floor=None, min_history=None, spatial_boost=None, demodulate=None, variant=0) -> VDenoiseDesc:
         """rt_vdenoise_desc with rt_vdenoise_desc_init's defaults where an argument is None."""
-        d = VDenoiseDesc()
-        self.lib.rt_vdenoise_desc_init(C.byref(d))
-        d.width, d.height = width, height
-        d.rgba_in, d.depth, d.normal, d.albedo, d.id = rgba_in, depth, normal, albedo, id
-        d.rgba_out, d.pixels, d.moments, d.variance_out = rgba_out, pixels, moments, variance_out
-        for k, v in (("iterations", iterations), ("normal_shift", normal_shift), ("sigma_depth", sigma_depth),
-                     ("sigma_colour", sigma_colour), ("sigma_floor", sigma_floor), ("min_history", min_history),
-                     ("spatial_boost", spatial_boost), ("variant", variant)):
-            if v is not None:
-                setattr(d, k, v)
-        if demodulate is not None:
-            d.demodulate = 1 if demodulate else 0
-        return d
+        return self._desc(VDenoiseDesc, "rt_vdenoise_desc_init",
+                          dict(width=width, height=height, rgba_in=rgba_in, depth=depth, normal=normal, albedo=albedo,
+                               id=id, rgba_out=rgba_out, pixels=pixels, moments=moments, variance_out=variance_out),
+                          dict(iterations=iterations, normal_shift=normal_shift, sigma_depth=sigma_depth,
+                               sigma_colour=sigma_colour, sigma_floor=sigma_floor, min_history=min_history,
+                               spatial_boost=spatial_boost, variant=variant),
+                          dict(demodulate=demodulate))
 
     def denoise_variance_raw(self, d: VDenoiseDesc, stream=0) -> int:
         """rt_scene_denoise_variance as is: returns the status."""
@@ -959,47 +1033,18 @@ class Scene:
         rt_vdenoise_desc_init. Returns {'rgba': float32 [rows, W, 4], 'packed': int32 [rows, W] or None, 'variance':
         float32 [rows, W] or None} as new tensors; neither the frame's nor the history's tensors are written.
         Enqueued on `stream` (default: the current stream); no host wait."""
-        import torch
-        if not torch.cuda.is_available():
-            raise RtError("no GPU visible: the denoiser has no CPU fallback")
-        aov = frame.get("aov") or {}
-        rgba = frame.get("rgba") if history is None else history.get("rgba")
-        moments = None if history is None else history.get("moments")
-        need = ("depth", "normal", "id") + (() if demodulate is not None and not demodulate else ("albedo",))
-        if rgba is None or any(k not in aov for k in need):
-            raise RtError(f"denoise_variance needs a colour (the frame's rgba or the history's) and the G-buffer outputs "
-                          f"{need}: render with want_rgba=True and aov={AOV_NAMES}")
-        if history is not None and moments is None:
-            raise RtError("denoise_variance: the history carries no moments (Scene.temporal(..., want_moments=True))")
-        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
-        if tuple(rgba.shape) != (rows, width, 4):
-            raise RtError("denoise_variance: the colour is not of the guides' shape [rows, W, 4]")
-        out = torch.empty_like(rgba)
-        packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
-        variance = torch.empty((rows, width), dtype=torch.float32, device=rgba.device) if want_variance else None
-        st = torch.cuda.current_stream() if stream is None else stream
-        d = self.vdenoise_desc(width, rows, rgba_in=rgba.data_ptr(), depth=aov["depth"].data_ptr(),
-                               normal=aov["normal"].data_ptr(), albedo=aov["albedo"].data_ptr() if "albedo" in aov else 0,
-                               id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
-                               pixels=packed.data_ptr() if want_packed else 0,
-                               moments=moments.data_ptr() if moments is not None else 0,
-                               variance_out=variance.data_ptr() if want_variance else 0, iterations=iterations,
-                               normal_shift=normal_shift, sigma_depth=sigma_depth, sigma_colour=sigma_colour,
-                               sigma_floor=sigma_floor, min_history=min_history, spatial_boost=spatial_boost,
-                               demodulate=demodulate, variant=variant)
-        _check(self.denoise_variance_raw(d, st.cuda_stream), "rt_scene_denoise_variance")
-        return {"rgba": out, "packed": packed, "variance": variance}
+        return self._denoise(True, frame, history, want_packed, want_variance, stream, iterations=iterations,
+                             normal_shift=normal_shift, sigma_depth=sigma_depth, sigma_colour=sigma_colour,
+                             sigma_floor=sigma_floor, min_history=min_history, spatial_boost=spatial_boost,
+                             demodulate=demodulate, variant=variant)
 
     def set_vdenoise_timing(self, on: bool):
-        _check(self.lib.rt_scene_set_vdenoise_timing(self.handle, 1 if on else 0), "rt_scene_set_vdenoise_timing")
+        self._set_pass_timing("vdenoise", on)
 
     def vdenoise_times(self):
         """Device ms of every launch of the last timed variance-guided call (waits for it): variants 0 and 2: the pack
         pass, the spatial-estimate pass, then the iterations; variant 1: the initial variance, then the iterations."""
-        ms = (C.c_float * (RT_DENOISE_MAX_ITERATIONS + 2))()
-        n = C.c_int()
-        _check(self.lib.rt_scene_vdenoise_times(self.handle, ms, len(ms), C.byref(n)), "rt_scene_vdenoise_times")
-        return list(ms)[: n.value]
+        return self._pass_times("vdenoise", RT_DENOISE_MAX_ITERATIONS + 2)
 
     # ---------------------------------------------------------------- temporal accumulation (DESIGN.md 6i)
     def temporal_desc(self, width, height, *, cam=None, aspect=None, prev_cam=None, prev_aspect=None, rgba_in=0, depth=0,
@@ -1008,27 +1053,66 @@ class Scene:
                       variant=0) -> TemporalDesc:
         """rt_temporal_desc with rt_temporal_desc_init's defaults where an argument is None (cam / aspect: the
         default view; prev_cam / prev_aspect: the current ones)."""
-        d = TemporalDesc()
-        self.lib.rt_temporal_desc_init(C.byref(d))
-        d.width, d.height = width, height
-        d.aspect = default_aspect() if aspect is None else aspect
-        d.cam = _copy_camera(cam if cam is not None else default_camera())
-        d.prev_aspect = d.aspect if prev_aspect is None else prev_aspect
-        d.prev_cam = _copy_camera(prev_cam if prev_cam is not None else d.cam)
-        d.rgba_in, d.depth, d.normal, d.id = rgba_in, depth, normal, id
-        d.prev_rgba, d.prev_depth, d.prev_normal, d.prev_id = prev_rgba, prev_depth, prev_normal, prev_id
-        d.prev_moments = prev_moments
-        d.rgba_out, d.moments_out, d.pixels = rgba_out, moments_out, pixels
-        d.reset = 1 if reset else 0
-        for k, v in (("max_history", max_history), ("depth_tolerance", depth_tolerance),
-                     ("normal_cos_min", normal_cos_min), ("variant", variant)):
-            if v is not None:
-                setattr(d, k, v)
-        return d
+        aspect = default_aspect() if aspect is None else aspect
+        cam = _copy_camera(cam if cam is not None else default_camera())
+        return self._desc(TemporalDesc, "rt_temporal_desc_init",
+                          dict(width=width, height=height, aspect=aspect, cam=cam,
+                               prev_aspect=aspect if prev_aspect is None else prev_aspect,
+                               prev_cam=_copy_camera(prev_cam if prev_cam is not None else cam),
+                               rgba_in=rgba_in, depth=depth, normal=normal, id=id, prev_rgba=prev_rgba,
+                               prev_depth=prev_depth, prev_normal=prev_normal, prev_id=prev_id, prev_moments=prev_moments,
+                               rgba_out=rgba_out, moments_out=moments_out, pixels=pixels),
+                          dict(max_history=max_history, depth_tolerance=depth_tolerance, normal_cos_min=normal_cos_min,
+                               variant=variant),
+                          dict(reset=bool(reset)))
 
     def temporal_raw(self, d: TemporalDesc, stream=0) -> int:
         """rt_scene_temporal as is: returns the status."""
         return self.lib.rt_scene_temporal(self.handle, C.byref(d), stream)
+
+    def _temporal(self, motion, frame, history, cam, aspect, colour, want_moments, want_packed, stream, **knobs):
+        """temporal (motion None) and temporal_motion (motion: (sphere_motion, cube_motion, the clamp's arguments))."""
+        import contextlib
+        torch = self._need_gpu("temporal accumulation")
+        name = "temporal" if motion is None else "temporal_motion"
+        rgba = frame.get("rgba") if colour is None else colour
+        need = ("depth", "normal", "id")
+        aov = self._guides(frame, rgba, need, f"{name} needs the frame's rgba (or colour=) and the G-buffer outputs "
+                           f"{need}: render with want_rgba=True and aov={need}")
+        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
+        rgba = self._cuda_colour(torch, name, rgba, rows, width)
+        now = {} if motion is None else dict(zip(("spheres", "cubes"), self._object_origins()))
+        if history is not None:
+            if tuple(history["rgba"].shape) != (rows, width, 4):
+                raise RtError(f"{name}: the history is of another size (pass history=None after a resize)")
+            if want_moments and history.get("moments") is None:
+                raise RtError(f"{name}: want_moments needs a history with moments")
+            for k in now:
+                if history.get(k) is not None and history[k].shape != now[k].shape:
+                    raise RtError(f"temporal_motion: the scene has {now[k].shape[0]} {k}, the history {history[k].shape[0]} "
+                                  "(pass history=None after adding or removing objects)")
+        cam = _copy_camera(cam if cam is not None else default_camera())
+        aspect = default_aspect() if aspect is None else aspect
+        st = self._stream(torch, stream)
+        # temporal_motion allocates (and uploads its tables) on `stream`, temporal on the current stream
+        with torch.cuda.stream(st) if motion is not None else contextlib.nullcontext():
+            out = torch.empty_like(rgba)
+            moments = self._new(torch, want_moments, rgba, (rows, width, 2), torch.float32)
+            packed = self._new(torch, want_packed, rgba, (rows, width), torch.int32)
+            tables = {} if motion is None else self._motion_tables(torch, history, now, rgba.device, *motion[:2])
+        args = dict(cam=cam, aspect=aspect, rgba_in=rgba.data_ptr(), depth=aov["depth"].data_ptr(),
+                    normal=aov["normal"].data_ptr(), id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
+                    moments_out=self._ptr(moments), pixels=self._ptr(packed), reset=history is None,
+                    **knobs, **self._prev(history))
+        if motion is None:
+            _check(self.temporal_raw(self.temporal_desc(width, rows, **args), st.cuda_stream), "rt_scene_temporal")
+        else:
+            for k, m in tables.items():
+                args[k], args["n_" + k] = m.data_ptr(), m.shape[0]
+            d = self.temporal_motion_desc(width, rows, **args, **motion[2])
+            _check(self.temporal_motion_raw(d, st.cuda_stream), "rt_scene_temporal_motion")
+        return {"rgba": out, "moments": moments, "packed": packed, "depth": aov["depth"], "normal": aov["normal"],
+                "id": aov["id"], "cam": cam, "aspect": aspect, **now}
 
     def temporal(self, frame, history=None, *, cam=None, aspect=None, colour=None, max_history=None,
                  depth_tolerance=None, normal_cos_min=None, want_moments=True, want_packed=True, variant=0, stream=None):
@@ -1040,45 +1124,9 @@ class Scene:
         or None, 'packed': int32 [rows, W] or None, 'depth', 'normal', 'id': the frame's guide tensors (not copied),
         'cam', 'aspect'} as new tensors; neither the frame's nor the history's tensors are written. Enqueued on
         `stream` (default: the current stream); no host wait."""
-        import torch
-        if not torch.cuda.is_available():
-            raise RtError("no GPU visible: temporal accumulation has no CPU fallback")
-        aov = frame.get("aov") or {}
-        rgba = frame.get("rgba") if colour is None else colour
-        need = ("depth", "normal", "id")
-        if rgba is None or any(k not in aov for k in need):
-            raise RtError(f"temporal needs the frame's rgba (or colour=) and the G-buffer outputs {need}: render with "
-                          f"want_rgba=True and aov={need}")
-        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
-        if tuple(rgba.shape) != (rows, width, 4) or rgba.dtype != torch.float32 or not rgba.is_cuda:
-            raise RtError("temporal: the colour must be a CUDA float32 tensor of the guides' shape [rows, W, 4]")
-        rgba = rgba.contiguous()
-        if history is not None:
-            if tuple(history["rgba"].shape) != (rows, width, 4):
-                raise RtError("temporal: the history is of another size (pass history=None after a resize)")
-            if want_moments and history.get("moments") is None:
-                raise RtError("temporal: want_moments needs a history with moments")
-        cam = _copy_camera(cam if cam is not None else default_camera())
-        aspect = default_aspect() if aspect is None else aspect
-        out = torch.empty_like(rgba)
-        moments = torch.empty((rows, width, 2), dtype=torch.float32, device=rgba.device) if want_moments else None
-        packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
-        st = torch.cuda.current_stream() if stream is None else stream
-        prev = {}
-        if history is not None:
-            prev = dict(prev_cam=history["cam"], prev_aspect=history["aspect"], prev_rgba=history["rgba"].data_ptr(),
-                        prev_depth=history["depth"].data_ptr(), prev_normal=history["normal"].data_ptr(),
-                        prev_id=history["id"].data_ptr(),
-                        prev_moments=history["moments"].data_ptr() if history.get("moments") is not None else 0)
-        d = self.temporal_desc(width, rows, cam=cam, aspect=aspect, rgba_in=rgba.data_ptr(),
-                               depth=aov["depth"].data_ptr(), normal=aov["normal"].data_ptr(), id=aov["id"].data_ptr(),
-                               rgba_out=out.data_ptr(), moments_out=moments.data_ptr() if want_moments else 0,
-                               pixels=packed.data_ptr() if want_packed else 0, reset=history is None,
-                               max_history=max_history, depth_tolerance=depth_tolerance, normal_cos_min=normal_cos_min,
-                               variant=variant, **prev)
-        _check(self.temporal_raw(d, st.cuda_stream), "rt_scene_temporal")
-        return {"rgba": out, "moments": moments, "packed": packed, "depth": aov["depth"], "normal": aov["normal"],
-                "id": aov["id"], "cam": cam, "aspect": aspect}
+        return self._temporal(None, frame, history, cam, aspect, colour, want_moments, want_packed, stream,
+                              max_history=max_history, depth_tolerance=depth_tolerance, normal_cos_min=normal_cos_min,
+                              variant=variant)
 
     # ------------------------------------------- temporal accumulation over moving objects (DESIGN.md 6k)
     def temporal_motion_desc(self, width, height, *, sphere_motion=0, n_sphere_motion=0, cube_motion=0, n_cube_motion=0,
@@ -1086,18 +1134,10 @@ class Scene:
         """rt_tmotion_desc: temporal_desc's arguments, then the motion arrays (device addresses) and the clamp, with
         rt_tmotion_desc_init's defaults where an argument is None."""
         t = self.temporal_desc(width, height, **kw)
-        d = TMotionDesc()
-        self.lib.rt_tmotion_desc_init(C.byref(d))
-        for k, _ in TemporalDesc._fields_[1:]:
-            setattr(d, k, getattr(t, k))
-        d.sphere_motion, d.n_sphere_motion = sphere_motion, n_sphere_motion
-        d.cube_motion, d.n_cube_motion = cube_motion, n_cube_motion
-        if clamp is not None:
-            d.clamp = 1 if clamp else 0
-        for k, v in (("clamp_slack", clamp_slack), ("clamp_history", clamp_history)):
-            if v is not None:
-                setattr(d, k, v)
-        return d
+        return self._desc(TMotionDesc, "rt_tmotion_desc_init",
+                          dict({k: getattr(t, k) for k, _ in TemporalDesc._fields_[1:]}, sphere_motion=sphere_motion,
+                               n_sphere_motion=n_sphere_motion, cube_motion=cube_motion, n_cube_motion=n_cube_motion),
+                          dict(clamp_slack=clamp_slack, clamp_history=clamp_history), dict(clamp=clamp))
 
     def temporal_motion_raw(self, d: TMotionDesc, stream=0) -> int:
         """rt_scene_temporal_motion as is: returns the status."""
@@ -1115,6 +1155,31 @@ class Scene:
             cu[i] = (o.x, o.y, o.z)
         return sp, cu
 
+    @staticmethod
+    def _motion_tables(torch, history, now, device, sphere_motion, cube_motion):
+        """{'sphere_motion', 'cube_motion': CUDA float32 [n, 4]}: per kind the displacements given, else those inferred
+        from the positions the history carries; no entry without a history, where nothing moved or for an empty table."""
+        tables = {}
+        for k, arg, m in (("spheres", "sphere_motion", sphere_motion), ("cubes", "cube_motion", cube_motion)):
+            if m is None and history is not None and history.get(k) is not None:
+                m = (now[k] - history[k]).astype(np.float32)
+                if not m.any():
+                    m = None                                   # nothing moved: no table
+            if m is None or history is None:
+                continue
+            if not torch.is_tensor(m):
+                m = np.asarray(m, dtype=np.float32)
+                if m.ndim != 2 or m.shape[1] not in (3, 4):
+                    raise RtError("temporal_motion: a displacement array is [n, 3] or [n, 4]")
+                m4 = np.zeros((m.shape[0], 4), dtype=np.float32)
+                m4[:, :m.shape[1]] = m
+                m = torch.from_numpy(m4).to(device)
+            if m.dtype != torch.float32 or not m.is_cuda or m.ndim != 2 or m.shape[1] != 4 or not m.is_contiguous():
+                raise RtError("temporal_motion: a displacement tensor must be a contiguous CUDA float32 [n, 4]")
+            if m.shape[0]:
+                tables[arg] = m
+        return tables
+
     def temporal_motion(self, frame, history=None, *, cam=None, aspect=None, colour=None, sphere_motion=None,
                         cube_motion=None, clamp=None, clamp_slack=None, clamp_history=None, max_history=None,
                         depth_tolerance=None, normal_cos_min=None, want_moments=True, want_packed=True, variant=0,
@@ -1128,78 +1193,10 @@ class Scene:
         float32 tensor [n, 4] -- overrides the inferred one. clamp / clamp_slack / clamp_history: rt_tmotion_desc's
         (None: its defaults). Enqueued on `stream` (default: the current stream); inferred or numpy displacements
         are uploaded first, which is the only host wait."""
-        import torch
-        if not torch.cuda.is_available():
-            raise RtError("no GPU visible: temporal accumulation has no CPU fallback")
-        aov = frame.get("aov") or {}
-        rgba = frame.get("rgba") if colour is None else colour
-        need = ("depth", "normal", "id")
-        if rgba is None or any(k not in aov for k in need):
-            raise RtError(f"temporal_motion needs the frame's rgba (or colour=) and the G-buffer outputs {need}: render "
-                          f"with want_rgba=True and aov={need}")
-        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
-        if tuple(rgba.shape) != (rows, width, 4) or rgba.dtype != torch.float32 or not rgba.is_cuda:
-            raise RtError("temporal_motion: the colour must be a CUDA float32 tensor of the guides' shape [rows, W, 4]")
-        rgba = rgba.contiguous()
-        now = dict(zip(("spheres", "cubes"), self._object_origins()))
-        if history is not None:
-            if tuple(history["rgba"].shape) != (rows, width, 4):
-                raise RtError("temporal_motion: the history is of another size (pass history=None after a resize)")
-            if want_moments and history.get("moments") is None:
-                raise RtError("temporal_motion: want_moments needs a history with moments")
-            for k in ("spheres", "cubes"):
-                if history.get(k) is not None and history[k].shape != now[k].shape:
-                    raise RtError(f"temporal_motion: the scene has {now[k].shape[0]} {k}, the history {history[k].shape[0]} "
-                                  "(pass history=None after adding or removing objects)")
-        cam = _copy_camera(cam if cam is not None else default_camera())
-        aspect = default_aspect() if aspect is None else aspect
-        st = torch.cuda.current_stream() if stream is None else stream
-        motion = {}
-        with torch.cuda.stream(st):
-            out = torch.empty_like(rgba)
-            moments = torch.empty((rows, width, 2), dtype=torch.float32, device=rgba.device) if want_moments else None
-            packed = torch.empty((rows, width), dtype=torch.int32, device=rgba.device) if want_packed else None
-            for k, given in (("spheres", sphere_motion), ("cubes", cube_motion)):
-                m = given
-                if m is None and history is not None and history.get(k) is not None:
-                    m = (now[k] - history[k]).astype(np.float32)
-                    if not m.any():
-                        m = None                                   # nothing moved: no table
-                if m is None or history is None:
-                    continue
-                if not torch.is_tensor(m):
-                    m = np.asarray(m, dtype=np.float32)
-                    if m.ndim != 2 or m.shape[1] not in (3, 4):
-                        raise RtError("temporal_motion: a displacement array is [n, 3] or [n, 4]")
-                    m4 = np.zeros((m.shape[0], 4), dtype=np.float32)
-                    m4[:, :m.shape[1]] = m
-                    m = torch.from_numpy(m4).to(rgba.device)
-                if m.dtype != torch.float32 or not m.is_cuda or m.ndim != 2 or m.shape[1] != 4 or not m.is_contiguous():
-                    raise RtError("temporal_motion: a displacement tensor must be a contiguous CUDA float32 [n, 4]")
-                if m.shape[0]:
-                    motion[k] = m
-        prev = {}
-        if history is not None:
-            prev = dict(prev_cam=history["cam"], prev_aspect=history["aspect"], prev_rgba=history["rgba"].data_ptr(),
-                        prev_depth=history["depth"].data_ptr(), prev_normal=history["normal"].data_ptr(),
-                        prev_id=history["id"].data_ptr(),
-                        prev_moments=history["moments"].data_ptr() if history.get("moments") is not None else 0)
-        sm, cm = motion.get("spheres"), motion.get("cubes")
-        d = self.temporal_motion_desc(width, rows, cam=cam, aspect=aspect, rgba_in=rgba.data_ptr(),
-                                      depth=aov["depth"].data_ptr(), normal=aov["normal"].data_ptr(),
-                                      id=aov["id"].data_ptr(), rgba_out=out.data_ptr(),
-                                      moments_out=moments.data_ptr() if want_moments else 0,
-                                      pixels=packed.data_ptr() if want_packed else 0, reset=history is None,
-                                      max_history=max_history, depth_tolerance=depth_tolerance,
-                                      normal_cos_min=normal_cos_min, variant=variant,
-                                      sphere_motion=sm.data_ptr() if sm is not None else 0,
-                                      n_sphere_motion=sm.shape[0] if sm is not None else 0,
-                                      cube_motion=cm.data_ptr() if cm is not None else 0,
-                                      n_cube_motion=cm.shape[0] if cm is not None else 0,
-                                      clamp=clamp, clamp_slack=clamp_slack, clamp_history=clamp_history, **prev)
-        _check(self.temporal_motion_raw(d, st.cuda_stream), "rt_scene_temporal_motion")
-        return {"rgba": out, "moments": moments, "packed": packed, "depth": aov["depth"], "normal": aov["normal"],
-                "id": aov["id"], "cam": cam, "aspect": aspect, "spheres": now["spheres"], "cubes": now["cubes"]}
+        motion = (sphere_motion, cube_motion, dict(clamp=clamp, clamp_slack=clamp_slack, clamp_history=clamp_history))
+        return self._temporal(motion, frame, history, cam, aspect, colour, want_moments, want_packed, stream,
+                              max_history=max_history, depth_tolerance=depth_tolerance, normal_cos_min=normal_cos_min,
+                              variant=variant)
 
     # ---------------------------------------------------------------- guided upsampling (DESIGN.md 6l)
     def upsample_desc(self, width, height, lo_width, lo_height, *, rgba_lo=0, depth_lo=0, normal_lo=0, albedo_lo=0,
@@ -1208,22 +1205,15 @@ class Scene:
                       n_cube_select=0, use_tables=False, normal_shift=None, sigma_depth=None, demodulate=None,
                       variant=0) -> UpsampleDesc:
         """rt_upsample_desc with rt_upsample_desc_init's defaults where an argument is None."""
-        d = UpsampleDesc()
-        self.lib.rt_upsample_desc_init(C.byref(d))
-        d.width, d.height, d.lo_width, d.lo_height = width, height, lo_width, lo_height
-        d.rgba_lo, d.depth_lo, d.normal_lo, d.albedo_lo, d.id_lo = rgba_lo, depth_lo, normal_lo, albedo_lo, id_lo
-        d.depth, d.normal, d.albedo, d.id, d.base = depth, normal, albedo, id, base
-        d.rgba_out, d.pixels, d.source = rgba_out, pixels, source
-        d.sphere_select, d.n_sphere_select = sphere_select, n_sphere_select
-        d.plane_select, d.n_plane_select = plane_select, n_plane_select
-        d.cube_select, d.n_cube_select = cube_select, n_cube_select
-        d.use_tables = 1 if use_tables else 0
-        for k, v in (("normal_shift", normal_shift), ("sigma_depth", sigma_depth), ("variant", variant)):
-            if v is not None:
-                setattr(d, k, v)
-        if demodulate is not None:
-            d.demodulate = 1 if demodulate else 0
-        return d
+        return self._desc(UpsampleDesc, "rt_upsample_desc_init",
+                          dict(width=width, height=height, lo_width=lo_width, lo_height=lo_height, rgba_lo=rgba_lo,
+                               depth_lo=depth_lo, normal_lo=normal_lo, albedo_lo=albedo_lo, id_lo=id_lo, depth=depth,
+                               normal=normal, albedo=albedo, id=id, base=base, rgba_out=rgba_out, pixels=pixels,
+                               source=source, sphere_select=sphere_select, n_sphere_select=n_sphere_select,
+                               plane_select=plane_select, n_plane_select=n_plane_select, cube_select=cube_select,
+                               n_cube_select=n_cube_select),
+                          dict(normal_shift=normal_shift, sigma_depth=sigma_depth, variant=variant),
+                          dict(use_tables=bool(use_tables), demodulate=demodulate))
 
     def upsample_raw(self, d: UpsampleDesc, stream=0) -> int:
         """rt_scene_upsample as is: returns the status."""
@@ -1239,9 +1229,7 @@ class Scene:
         (or uint8 CUDA tensor) with a non-zero entry per object whose pixels are. Returns {'rgba': float32
         [H, W, 4], 'packed': int32 [H, W] or None, 'source': uint8 [H, W] or None} as new tensors; no input is
         written. Enqueued on `stream` (default: the current stream); no host wait."""
-        import torch
-        if not torch.cuda.is_available():
-            raise RtError("no GPU visible: the upsampler has no CPU fallback")
+        torch = self._need_gpu("the upsampler")
         ha, la = hi.get("aov") or {}, lo.get("aov") or {}
         rgba_lo = lo.get("rgba") if colour is None else colour
         demod = demodulate is None or bool(demodulate)
@@ -1277,16 +1265,15 @@ class Scene:
                 keep.append(t)
                 tables[f"{kind}_select"], tables[f"n_{kind}_select"] = t.data_ptr(), t.numel()
         out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
-        packed = torch.empty((H, W), dtype=torch.int32, device=dev) if want_packed else None
-        source = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_source else None
-        st = torch.cuda.current_stream() if stream is None else stream
+        packed = self._new(torch, want_packed, rgba_lo, (H, W), torch.int32)
+        source = self._new(torch, want_source, rgba_lo, (H, W), torch.uint8)
+        st = self._stream(torch, stream)
         d = self.upsample_desc(W, H, w, h, rgba_lo=rgba_lo.data_ptr(), depth_lo=la["depth"].data_ptr(),
                                normal_lo=la["normal"].data_ptr(), albedo_lo=la["albedo"].data_ptr() if demod else 0,
                                id_lo=la["id"].data_ptr(), depth=ha["depth"].data_ptr(), normal=ha["normal"].data_ptr(),
                                albedo=ha["albedo"].data_ptr() if demod else 0, id=ha["id"].data_ptr(),
-                               base=base.data_ptr() if base is not None else 0, rgba_out=out.data_ptr(),
-                               pixels=packed.data_ptr() if want_packed else 0,
-                               source=source.data_ptr() if want_source else 0, use_tables=select is not None,
+                               base=self._ptr(base), rgba_out=out.data_ptr(), pixels=self._ptr(packed),
+                               source=self._ptr(source), use_tables=select is not None,
                                normal_shift=normal_shift, sigma_depth=sigma_depth, demodulate=demod, variant=variant,
                                **tables)
         _check(self.upsample_raw(d, st.cuda_stream), "rt_scene_upsample")
@@ -1319,32 +1306,23 @@ class Scene:
         return out
 
     def set_upsample_timing(self, on: bool):
-        _check(self.lib.rt_scene_set_upsample_timing(self.handle, 1 if on else 0), "rt_scene_set_upsample_timing")
+        self._set_pass_timing("upsample", on)
 
     def upsample_times(self):
         """Device ms of the last timed upsample call (waits for it): a list of at most one."""
-        ms = (C.c_float * 1)()
-        n = C.c_int(0)
-        _check(self.lib.rt_scene_upsample_times(self.handle, ms, 1, C.byref(n)), "rt_scene_upsample_times")
-        return list(ms)[: n.value]
+        return self._pass_times("upsample", 1)
 
     def set_temporal_timing(self, on: bool):
-        _check(self.lib.rt_scene_set_temporal_timing(self.handle, 1 if on else 0), "rt_scene_set_temporal_timing")
+        self._set_pass_timing("temporal", on)
 
     def temporal_times(self):
         """Device ms of the last timed temporal call's launch (waits for it): a list of at most one value."""
-        ms = (C.c_float * 1)()
-        n = C.c_int()
-        _check(self.lib.rt_scene_temporal_times(self.handle, ms, len(ms), C.byref(n)), "rt_scene_temporal_times")
-        return list(ms)[: n.value]
+        return self._pass_times("temporal", 1)
 
     def set_denoise_timing(self, on: bool):
-        _check(self.lib.rt_scene_set_denoise_timing(self.handle, 1 if on else 0), "rt_scene_set_denoise_timing")
+        self._set_pass_timing("denoise", on)
 
     def denoise_times(self):
         """Device ms of every launch of the last timed denoise call (waits for it): variants 0 and 2: the pack pass, then
         the iterations; variant 1: the iterations."""
-        ms = (C.c_float * (RT_DENOISE_MAX_ITERATIONS + 1))()
-        n = C.c_int()
-        _check(self.lib.rt_scene_denoise_times(self.handle, ms, len(ms), C.byref(n)), "rt_scene_denoise_times")
-        return list(ms)[: n.value]
+        return self._pass_times("denoise", RT_DENOISE_MAX_ITERATIONS + 1)

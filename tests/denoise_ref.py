@@ -59,19 +59,44 @@ def _shifted(a, oy, ox, fill):
     return b
 
 
+def _guides(depth, normal, ids, sigma_depth):
+    """(kind, index, N, z, zden^2) of the guides: every triangle has index 0; zden = sigma_depth max(|z|, 2^-10)."""
+    kind, index = ids[..., 0], np.where(ids[..., 0] == RT_HIT_TRIANGLE, 0, ids[..., 1])
+    N = normal[..., :3].astype(f32)
+    z = depth.astype(f32)
+    with np.errstate(all="ignore"):
+        zden = (f32(sigma_depth) * _max(np.abs(z), TINY)).astype(f32)
+        zden2 = (zden * zden).astype(f32)
+    return kind, index, N, z, zden2
+
+
+def _geometry(N, z, zden2, kind, index, oy, ox, normal_shift):
+    """(ok, e_n, e_z) of the tap at offset (oy, ox): ok = inside, valid and e_id; e_z = 1 / (1 + (dz / zden)^2) in the
+    form zden^2 / (zden^2 + dz^2)."""
+    h, w = z.shape
+    ok = _shifted(np.ones((h, w), dtype=bool), oy, ox, False)
+    kq = _shifted(kind, oy, ox, -1)
+    iq = _shifted(index, oy, ox, -1)
+    ok &= (kq >= 0) & (kq == kind) & (iq == index)
+    Nq = _shifted(N, oy, ox, 0)
+    zq = _shifted(z, oy, ox, 0)
+    dot = ((N[..., 0] * Nq[..., 0] + N[..., 1] * Nq[..., 1]).astype(f32) + N[..., 2] * Nq[..., 2]).astype(f32)
+    m = np.where(dot > 0, dot, f32(0)).astype(f32)
+    for _ in range(normal_shift):
+        m = (m * m).astype(f32)
+    dz = (zq - z).astype(f32)
+    ez = (zden2 / (zden2 + (dz * dz).astype(f32)).astype(f32)).astype(f32)
+    return ok, m, ez
+
+
 def iterate(I, depth, normal, ids, step, normal_shift, sigma_depth, sigma_colour):
     """One iteration: I [H, W, 3] float32 -> I' (pixels that are not valid keep I)."""
     h, w = depth.shape
-    kind, index = ids[..., 0], np.where(ids[..., 0] == RT_HIT_TRIANGLE, 0, ids[..., 1])
+    kind, index, N, z, zden2 = _guides(depth, normal, ids, sigma_depth)
     valid = kind >= 0
-    N = normal[..., :3].astype(f32)
-    z = depth.astype(f32)
-    sd, sc = f32(sigma_depth), f32(sigma_colour)
+    sc = f32(sigma_colour)
     use_colour = bool(sc > 0)
-    inside = np.ones((h, w), dtype=bool)
     with np.errstate(all="ignore"):
-        zden = (sd * _max(np.abs(z), TINY)).astype(f32)
-        zden2 = (zden * zden).astype(f32)
         sc2 = f32(sc * sc)
         Yp = luma(I) if use_colour else None
         acc = np.zeros((h, w, 3), dtype=f32)
@@ -84,21 +109,10 @@ def iterate(I, depth, normal, ids, step, normal_shift, sigma_depth, sigma_colour
                     wt = np.full((h, w), H5[2] * H5[2], dtype=f32)
                     ok = np.ones((h, w), dtype=bool)
                 else:
-                    ok = _shifted(inside, oy, ox, False)
-                    kq = _shifted(kind, oy, ox, -1)
-                    iq = _shifted(index, oy, ox, -1)
-                    ok &= (kq >= 0) & (kq == kind) & (iq == index)
-                    Nq = _shifted(N, oy, ox, 0)
-                    zq = _shifted(z, oy, ox, 0)
-                    dot = ((N[..., 0] * Nq[..., 0] + N[..., 1] * Nq[..., 1]).astype(f32) + N[..., 2] * Nq[..., 2]).astype(f32)
-                    m = np.where(dot > 0, dot, f32(0)).astype(f32)
-                    for _ in range(normal_shift):
-                        m = (m * m).astype(f32)
+                    ok, m, ez = _geometry(N, z, zden2, kind, index, oy, ox, normal_shift)
                     wt = ((H5[dx + 2] * H5[dy + 2]) * m).astype(f32)
-                    # e_z = 1 / (1 + (dz / zden)^2) in the form zden^2 / (zden^2 + dz^2), e_c likewise
-                    dz = (zq - z).astype(f32)
-                    wt = (wt * (zden2 / (zden2 + (dz * dz).astype(f32)).astype(f32)).astype(f32)).astype(f32)
-                    if use_colour:
+                    wt = (wt * ez).astype(f32)
+                    if use_colour:                                  # e_c in e_z's form
                         dl = (luma(Iq) - Yp).astype(f32)
                         wt = (wt * (sc2 / (sc2 + (dl * dl).astype(f32)).astype(f32)).astype(f32)).astype(f32)
                     ok &= (wt > 0) & (wt < np.inf)

@@ -10,16 +10,13 @@ import numpy as np
 import pytest
 
 import denoise_ref as R
+from postpass import bits as _bits
 from scenes import Inputs, mixed_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 _FIELDS = ("struct_size", "width", "height", "rgba_in", "depth", "normal", "albedo", "id", "rgba_out", "pixels",
            "iterations", "normal_shift", "sigma_depth", "sigma_colour", "demodulate", "variant")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

@@ -8,18 +8,13 @@ import pytest
 
 import denoise_ref as R
 import meshes
+from postpass import ALL, SENTINEL, crop as _crop, scene as _scene, tensor_bits as _bits
 from scenes import Inputs, mixed_scene
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-ALL = ("depth", "normal", "id", "albedo")
-SENTINEL = 0x5a5a5a5a
 VARIANTS = (0, 1, 2)
-
-
-def _bits(t):
-    return t.contiguous().cpu().numpy().view(np.uint32)
 
 
 def _np(frame):
@@ -29,20 +24,8 @@ def _np(frame):
             a["id"].cpu().numpy())
 
 
-def _crop(frame, rows, cols):
-    """Rows and columns of a frame as a frame of its own (contiguous tensors)."""
-    cut = lambda t: t[rows, cols].contiguous()
-    return {"rgba": cut(frame["rgba"]), "packed": cut(frame["packed"]), "aov": {k: cut(v) for k, v in frame["aov"].items()}}
-
-
 def _render(rt, inp, w, h, mesh=None, **kw):
-    sc = inp.scene()
-    if getattr(inp, "n_planes", 0):
-        sc.set_planes(inp.planes, inp.n_planes)
-    if getattr(inp, "n_cubes", 0):
-        sc.set_cubes(inp.cubes, inp.n_cubes)
-    if mesh is not None:
-        sc.set_mesh(rt.mesh_from_obj_text(mesh))
+    sc = _scene(rt, inp, mesh)
     return sc, sc.render(w, h, cam=inp.cam, aspect=inp.aspect, aov=ALL, **kw)
 
 

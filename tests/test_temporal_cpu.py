@@ -12,56 +12,14 @@ import pytest
 
 import denoise_ref as R
 import temporal_ref as T
+# WIDE_HIT_FLOOR and WIDE_SEGMENT: for the suites that take the wide path's constants from this module
+from postpass import (TEMPORAL_FIELDS, WIDE_BLOCK, WIDE_CAMS, WIDE_FIRST, WIDE_HIT_FLOOR, WIDE_HISTORY_FLOOR,  # noqa: F401
+                      WIDE_SEGMENT, View, bits as _bits, block_shares, cam as _cam)
 from scenes import Inputs, mixed_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-_FIELDS = ("struct_size", "width", "height", "aspect", "cam", "prev_aspect", "prev_cam", "rgba_in", "depth", "normal",
-           "id", "prev_rgba", "prev_depth", "prev_normal", "prev_id", "prev_moments", "rgba_out", "moments_out", "pixels",
-           "reset", "max_history", "depth_tolerance", "normal_cos_min", "variant")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _cam(rt, x, y, z, yaw, pitch):
-    return rt.Camera(rt.Vec3(x, y, z), rt.Vec3(0, 0, 1), 0.0, yaw, pitch)
-
-
-class View:
-    """One camera's frame of a scene, formed on the CPU: the restatement's `cur`, the rays and the view terms."""
-
-    def __init__(self, rt, oracle, inp, cam, w, h):
-        from test_reflect_cpu import Composer
-        inp.cam = cam
-        rgba, depth, normal, _, ids = R.oracle_inputs(rt, oracle, inp, w, h)
-        comp = Composer(oracle, None, inp.spheres, inp.n, inp.tex, inp.sky, inp.sky_box, inp.lights, inp.n_lights, cam,
-                        inp.aspect)
-        self.O, self.D = comp.primary(w, h, 0, h)
-        self.cur = dict(rgba=rgba, depth=depth, normal=normal, id=ids)
-        self.terms = rt.view_terms(w, h, inp.aspect, cam)
-        self.aspect, self.cam, self.w, self.h = inp.aspect, cam, w, h
-
-    def onto(self, hist, prev, same=False, **kw):
-        """This view's frame blended into `hist`, which was accumulated in the view `prev`."""
-        return T.temporal(self.cur, hist, self.O, self.D, self.terms, prev.terms, prev.aspect, same, details=True, **kw)
-
-
-# The wide path (DESIGN.md 2): the GPU tests' path with the yaw turned to 170, for buffers of more than eight tile
-# columns (tp_product pads its grid to a multiple of eight 64-pixel columns, with MOTION too) and of more than eight
-# 256-pixel row segments (dn_iter_direct). With yaw 180 columns 512 .. 575 of a 576 x 36 frame show no sphere at all.
-WIDE_CAMS = ((4, 3, 10, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.5, 3.1, 10.2, 170, -20), (4.7, 3.1, 10.1, 166, -21))
-WIDE_BLOCK = 64                 # a tile column of the two temporal product kernels
-WIDE_FIRST = 8                  # the first tile column outside the first group of eight
-WIDE_HISTORY_FLOOR = 0.1        # of every such column's pixels, in the moved-camera step
-WIDE_SEGMENT = 2048             # the first column of dn_iter_direct's second group of eight row segments
-WIDE_HIT_FLOOR = 0.3            # of the pixels from there on, for the second camera
-
-
-def block_shares(mask, first=WIDE_FIRST):
-    """The share of `mask` [H, W] in every 64-column block from block `first` on."""
-    return [float(mask[:, x:x + WIDE_BLOCK].mean()) for x in range(first * WIDE_BLOCK, mask.shape[1], WIDE_BLOCK)]
+_FIELDS = TEMPORAL_FIELDS
 
 
 def _pair(rt, oracle, inp, w, h):

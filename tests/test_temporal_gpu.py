@@ -6,56 +6,13 @@ import pytest
 
 import meshes
 import temporal_ref as T
+from postpass import (GUIDES, SENTINEL, WIDE_HISTORY_FLOOR, block_shares, cam as _cam, crop as _crop, cur as _cur,
+                      hist_np as _hist_np, path as _path, scene as _scene, tensor_bits as _bits, wide_path as _wide_path)
 from scenes import Inputs, mixed_scene
-from test_temporal_cpu import WIDE_CAMS, WIDE_HISTORY_FLOOR, block_shares
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-GUIDES = ("depth", "normal", "id")
-SENTINEL = 0x5a5a5a5a
-
-
-def _bits(t):
-    return t.contiguous().cpu().numpy().view(np.uint32)
-
-
-def _cam(rt, x, y, z, yaw, pitch):
-    return rt.Camera(rt.Vec3(x, y, z), rt.Vec3(0, 0, 1), 0.0, yaw, pitch)
-
-
-def _path(rt):
-    """A translation, the same camera again, then a yaw step with a translation."""
-    return [_cam(rt, 4, 3, 10, 180, -20), _cam(rt, 4.5, 3.1, 10.2, 180, -20), _cam(rt, 4.5, 3.1, 10.2, 180, -20),
-            _cam(rt, 4.7, 3.1, 10.1, 176, -21)]
-
-
-def _scene(rt, inp, mesh=None):
-    sc = inp.scene()
-    if getattr(inp, "n_planes", 0):
-        sc.set_planes(inp.planes, inp.n_planes)
-    if getattr(inp, "n_cubes", 0):
-        sc.set_cubes(inp.cubes, inp.n_cubes)
-    if mesh is not None:
-        sc.set_mesh(rt.mesh_from_obj_text(mesh))
-    return sc
-
-
-def _crop(frame, rows, cols):
-    cut = lambda t: t[rows, cols].contiguous()
-    return {"rgba": cut(frame["rgba"]), "packed": cut(frame["packed"]), "aov": {k: cut(v) for k, v in frame["aov"].items()}}
-
-
-def _cur(frame, colour=None):
-    a = frame["aov"]
-    return dict(rgba=(frame["rgba"] if colour is None else colour).cpu().numpy(), depth=a["depth"].cpu().numpy(),
-                normal=a["normal"].cpu().numpy(), id=a["id"].cpu().numpy())
-
-
-def _hist_np(h):
-    return None if h is None else dict(rgba=h["rgba"].cpu().numpy(), depth=h["depth"].cpu().numpy(),
-                                       normal=h["normal"].cpu().numpy(), id=h["id"].cpu().numpy(),
-                                       moments=None if h["moments"] is None else h["moments"].cpu().numpy())
 
 
 def _step(rt, sc, frame, hist, cam, aspect, colour=None, ref=True, **kw):
@@ -149,11 +106,6 @@ def test_sizes_that_are_no_multiple_of_the_tiles(rt, gpu, w, h):
         assert res[2]["has_history"].any()              # the repeated camera
     finally:
         sc.close()
-
-
-def _wide_path(rt):
-    """_path with the yaw turned to 170 (test_temporal_cpu.WIDE_CAMS)."""
-    return [_cam(rt, *c) for c in WIDE_CAMS]
 
 
 @pytest.mark.parametrize("w,h", [(576, 36), (1088, 36)])

@@ -10,47 +10,18 @@ import numpy as np
 import pytest
 
 import tmotion_ref as M
+from postpass import TEMPORAL_FIELDS, View, bits as _bits, cam as _cam, move_cube, move_spheres
 from scenes import Inputs, mixed_scene
-from test_temporal_cpu import View, _cam, _FIELDS as _TEMPORAL_FIELDS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-_FIELDS = _TEMPORAL_FIELDS + ("sphere_motion", "n_sphere_motion", "cube_motion", "n_cube_motion", "clamp", "clamp_slack",
+_FIELDS = TEMPORAL_FIELDS + ("sphere_motion", "n_sphere_motion", "cube_motion", "n_cube_motion", "clamp", "clamp_slack",
                               "clamp_history")
 CAM0, CAM1 = (4, 3, 10, 180, -20), (4.5, 3.1, 10.2, 180, -20)
 SPHERE_MOVES = {21: (0, 0.2, 0), 207: (-0.15, 0.1, 0.2), 100: (0.1, 0, -0.1), 150: (0, -0.1, 0.1)}
 # A box in mid-frame and a move that changes the depth of each of its faces, chosen with the restatement alone: it
 # keeps 0.968 of the box's pixels with the displacement and none without.
 CUBE, CUBE_MOVE = 1, (-0.1, 0.1, 0.15)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def move_spheres(inp, moves):
-    """Moves spheres of `inp` in binary32; returns the displacement table [n, 4] (now - before)."""
-    tab = np.zeros((inp.n, 4), dtype=f32)
-    for i, d in moves.items():
-        o = inp.spheres[i].orgin
-        before = np.array([o.x, o.y, o.z], dtype=f32)
-        now = (before + np.array(d, dtype=f32)).astype(f32)
-        o.x, o.y, o.z = (float(v) for v in now)
-        tab[i, :3] = (now - before).astype(f32)
-    return tab
-
-
-def move_cube(rt, inp, i, d):
-    lib = rt.load_library()
-    tab = np.zeros((inp.n_cubes, 4), dtype=f32)
-    b = inp.cubes[i].bounds
-    lo = np.array([b[0].x, b[0].y, b[0].z], dtype=f32)
-    hi = np.array([b[1].x, b[1].y, b[1].z], dtype=f32)
-    d = np.array(d, dtype=f32)
-    nlo, nhi = (lo + d).astype(f32), (hi + d).astype(f32)
-    lib.rt_cube_init(C.byref(inp.cubes[i]), *[float(v) for v in nlo], *[float(v) for v in nhi])
-    tab[i, :3] = (nlo - lo).astype(f32)
-    return tab
 
 
 def run(v, hist, prev, same, **kw):
@@ -277,7 +248,7 @@ def test_the_box_does_not_depend_on_the_order(light):
 def test_desc_layout_and_defaults(rt, tmp_path):
     src = tmp_path / "layout.c"
     body = "".join(f'    printf("%zu\\n", offsetof(rt_tmotion_desc, {f}));\n' for f in _FIELDS)
-    body += "".join(f'    printf("%zu\\n", offsetof(rt_temporal_desc, {f}));\n' for f in _TEMPORAL_FIELDS)
+    body += "".join(f'    printf("%zu\\n", offsetof(rt_temporal_desc, {f}));\n' for f in TEMPORAL_FIELDS)
     src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rt_engine.h"\nint main(void) {\n'
                    f'    printf("%zu\\n", sizeof(rt_tmotion_desc));\n{body}    return 0;\n}}\n')
     exe = tmp_path / "layout"
@@ -287,7 +258,7 @@ def test_desc_layout_and_defaults(rt, tmp_path):
     assert C.sizeof(rt.TMotionDesc) == want[0]
     assert [getattr(rt.TMotionDesc, f).offset for f in _FIELDS] == want[1:1 + n]
     assert [f for f, _ in rt.TMotionDesc._fields_] == list(_FIELDS)
-    assert want[1:1 + len(_TEMPORAL_FIELDS)] == want[1 + n:]              # rt_temporal_desc's fields, in place
+    assert want[1:1 + len(TEMPORAL_FIELDS)] == want[1 + n:]              # rt_temporal_desc's fields, in place
     lib = rt.load_library()
     d = rt.TMotionDesc()
     C.memset(C.byref(d), 0xff, C.sizeof(d))

@@ -7,9 +7,9 @@ import pytest
 
 import meshes
 import tmotion_ref as M
+from postpass import (GUIDES, SENTINEL, crop as _crop, cur as _cur, hist_np as _hist_np, move_cube,
+                      move_spheres, path as _path, scene as _scene, tensor_bits as _bits, wide_path as _wide_path)
 from scenes import Inputs, mixed_scene
-from test_temporal_gpu import GUIDES, SENTINEL, _bits, _cam, _crop, _cur, _hist_np, _path, _scene, _wide_path
-from test_tmotion_cpu import move_cube, move_spheres
 
 pytestmark = pytest.mark.gpu
 

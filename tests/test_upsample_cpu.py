@@ -12,6 +12,7 @@ import pytest
 
 import denoise_ref as R
 import upsample_ref as U
+from postpass import bits as _bits, mae, mirror_k
 from scenes import Inputs, mixed_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,22 +23,9 @@ _FIELDS = ("struct_size", "width", "height", "lo_width", "lo_height", "rgba_lo",
            "normal_shift", "sigma_depth", "demodulate", "variant")
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def frame(rt, oracle, inp, w, h):
     rgba, depth, normal, albedo, ids = R.oracle_inputs(rt, oracle, inp, w, h)
     return dict(rgba=rgba, depth=depth, normal=normal, albedo=albedo, id=ids)
-
-
-def mae(a, b, mask=None):
-    d = np.abs(a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64))
-    return float(d[mask].mean() if mask is not None else d.mean())
-
-
-def mirror_k(n):
-    return np.array([0.5 if i % 4 == 0 else 0.0 for i in range(n)], dtype=np.float32)
 
 
 @pytest.fixture(scope="module")

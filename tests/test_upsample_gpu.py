@@ -10,31 +10,14 @@ import pytest
 import denoise_ref as R
 import meshes
 import upsample_ref as U
+from postpass import ALL, SENTINEL, mae, mirror_k, scene as _scene, tensor_bits as _bits
 from scenes import Inputs, mixed_scene
-from test_upsample_cpu import mae, mirror_k
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-ALL = ("depth", "normal", "id", "albedo")
-SENTINEL = 0x5a5a5a5a
 SIZES = [(2, 2, 1, 1), (64, 2, 32, 1), (2, 64, 1, 32), (128, 16, 64, 8), (130, 18, 65, 9), (256, 32, 64, 8),
          (96, 54, 32, 18), (96, 54, 64, 36), (161, 91, 81, 46), (64, 8, 64, 8), (960, 540, 480, 270)]
-
-
-def _bits(t):
-    return t.contiguous().cpu().numpy().view(np.uint32)
-
-
-def _scene(rt, inp, mesh=None):
-    sc = inp.scene()
-    if getattr(inp, "n_planes", 0):
-        sc.set_planes(inp.planes, inp.n_planes)
-    if getattr(inp, "n_cubes", 0):
-        sc.set_cubes(inp.cubes, inp.n_cubes)
-    if mesh is not None:
-        sc.set_mesh(rt.mesh_from_obj_text(mesh))
-    return sc
 
 
 def _pair(sc, inp, W, H, w, h, **kw):

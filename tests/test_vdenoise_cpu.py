@@ -11,6 +11,7 @@ import pytest
 
 import denoise_ref as R
 import vdenoise_ref as V
+from postpass import bits as _bits
 from scenes import Inputs, mixed_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,10 +19,6 @@ f32 = np.float32
 _FIELDS = ("struct_size", "width", "height", "rgba_in", "depth", "normal", "albedo", "id", "rgba_out", "pixels",
            "moments", "variance_out", "iterations", "normal_shift", "sigma_depth", "sigma_colour", "sigma_floor",
            "min_history", "spatial_boost", "demodulate", "variant")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

@@ -8,23 +8,14 @@ import pytest
 import denoise_ref as R
 import meshes
 import vdenoise_ref as V
+from postpass import (ALL, SENTINEL, WIDE_CAMS, WIDE_HIT_FLOOR, WIDE_SEGMENT, cam as _cam, crop, scene as _scene,
+                      tensor_bits as _bits)
 from scenes import Inputs, mixed_scene
-from test_temporal_cpu import WIDE_CAMS, WIDE_HIT_FLOOR, WIDE_SEGMENT
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-ALL = ("depth", "normal", "id", "albedo")
-SENTINEL = 0x5a5a5a5a
 VARIANTS = (0, 1, 2)
-
-
-def _bits(t):
-    return t.contiguous().cpu().numpy().view(np.uint32)
-
-
-def _cam(rt, x, y, z, yaw, pitch):
-    return rt.Camera(rt.Vec3(x, y, z), rt.Vec3(0, 0, 1), 0.0, yaw, pitch)
 
 
 def _path(rt):
@@ -32,17 +23,6 @@ def _path(rt):
     the repeated camera held for three more frames: a pixel that keeps its history throughout arrives with n = 6, one
     that the yaw step disoccludes with n = 1."""
     return [_cam(rt, 4, 3, 10, 180, -20)] + [_cam(rt, 4.5, 3.1, 10.2, 180, -20)] * 4 + [_cam(rt, 4.7, 3.1, 10.1, 176, -21)]
-
-
-def _scene(rt, inp, mesh=None):
-    sc = inp.scene()
-    if getattr(inp, "n_planes", 0):
-        sc.set_planes(inp.planes, inp.n_planes)
-    if getattr(inp, "n_cubes", 0):
-        sc.set_cubes(inp.cubes, inp.n_cubes)
-    if mesh is not None:
-        sc.set_mesh(rt.mesh_from_obj_text(mesh))
-    return sc
 
 
 def _accumulate(rt, sc, inp, w, h, cams=None, colour=None):
@@ -58,9 +38,7 @@ def _accumulate(rt, sc, inp, w, h, cams=None, colour=None):
 
 
 def _crop(frame, hist, rows, cols):
-    cut = lambda t: t[rows, cols].contiguous()
-    return ({"rgba": cut(frame["rgba"]), "packed": cut(frame["packed"]), "aov": {k: cut(v) for k, v in frame["aov"].items()}},
-            {"rgba": cut(hist["rgba"]), "moments": cut(hist["moments"])})
+    return crop(frame, rows, cols), {k: hist[k][rows, cols].contiguous() for k in ("rgba", "moments")}
 
 
 def _np(frame, hist):

@@ -18,38 +18,10 @@ DEFAULTS = dict(iterations=4, normal_shift=5, sigma_depth=0.05, sigma_colour=4.0
                 spatial_boost=4.0, demodulate=True)
 
 
-def _guides(depth, normal, ids, sigma_depth):
-    kind, index = ids[..., 0], np.where(ids[..., 0] == R.RT_HIT_TRIANGLE, 0, ids[..., 1])
-    N = normal[..., :3].astype(f32)
-    z = depth.astype(f32)
-    with np.errstate(all="ignore"):
-        zden = (f32(sigma_depth) * R._max(np.abs(z), R.TINY)).astype(f32)
-        zden2 = (zden * zden).astype(f32)
-    return kind, index, N, z, zden2
-
-
-def _geometry(N, z, zden2, kind, index, oy, ox, normal_shift):
-    """(ok, e_n, e_z) of the tap at offset (oy, ox): ok = inside, valid and e_id."""
-    h, w = z.shape
-    ok = R._shifted(np.ones((h, w), dtype=bool), oy, ox, False)
-    kq = R._shifted(kind, oy, ox, -1)
-    iq = R._shifted(index, oy, ox, -1)
-    ok &= (kq >= 0) & (kq == kind) & (iq == index)
-    Nq = R._shifted(N, oy, ox, 0)
-    zq = R._shifted(z, oy, ox, 0)
-    dot = ((N[..., 0] * Nq[..., 0] + N[..., 1] * Nq[..., 1]).astype(f32) + N[..., 2] * Nq[..., 2]).astype(f32)
-    m = np.where(dot > 0, dot, f32(0)).astype(f32)
-    for _ in range(normal_shift):
-        m = (m * m).astype(f32)
-    dz = (zq - z).astype(f32)
-    ez = (zden2 / (zden2 + (dz * dz).astype(f32)).astype(f32)).astype(f32)
-    return ok, m, ez
-
-
 def spatial_variance(I0, depth, normal, ids, normal_shift, sigma_depth, spatial_boost):
     """t * spatial_boost of every pixel from its 7 x 7 neighbourhood (before the clamp)."""
     h, w = depth.shape
-    kind, index, N, z, zden2 = _guides(depth, normal, ids, sigma_depth)
+    kind, index, N, z, zden2 = R._guides(depth, normal, ids, sigma_depth)
     with np.errstate(all="ignore"):
         Y = R.luma(I0)
         W = np.zeros((h, w), dtype=f32)
@@ -62,7 +34,7 @@ def spatial_variance(I0, depth, normal, ids, normal_shift, sigma_depth, spatial_
                     wt = np.ones((h, w), dtype=f32)
                     ok = np.ones((h, w), dtype=bool)
                 else:
-                    ok, m, ez = _geometry(N, z, zden2, kind, index, dy, dx, normal_shift)
+                    ok, m, ez = R._geometry(N, z, zden2, kind, index, dy, dx, normal_shift)
                     wt = (m * ez).astype(f32)
                     ok &= (wt > 0) & (wt < np.inf)
                 W = np.where(ok, (W + wt).astype(f32), W)
@@ -114,7 +86,7 @@ def mean3(v, valid):
 def iterate(I, v, depth, normal, ids, step, normal_shift, sigma_depth, sigma_colour, sigma_floor, want_taps=False):
     """One iteration: (I [H, W, 3], v [H, W]) -> (I', v'); pixels that are not valid keep I and have v' = 0."""
     h, w = depth.shape
-    kind, index, N, z, zden2 = _guides(depth, normal, ids, sigma_depth)
+    kind, index, N, z, zden2 = R._guides(depth, normal, ids, sigma_depth)
     valid = kind >= 0
     sc, sf = f32(sigma_colour), f32(sigma_floor)
     with np.errstate(all="ignore"):
@@ -134,7 +106,7 @@ def iterate(I, v, depth, normal, ids, step, normal_shift, sigma_depth, sigma_col
                     wt = np.full((h, w), R.H5[2] * R.H5[2], dtype=f32)
                     ok = np.ones((h, w), dtype=bool)
                 else:
-                    ok, m, ez = _geometry(N, z, zden2, kind, index, oy, ox, normal_shift)
+                    ok, m, ez = R._geometry(N, z, zden2, kind, index, oy, ox, normal_shift)
                     wt = ((R.H5[dx + 2] * R.H5[dy + 2]) * m).astype(f32)
                     wt = (wt * ez).astype(f32)
                     dl = (R.luma(Iq) - Yp).astype(f32)

@@ -15,32 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
 import torch
 import rt_amd
-from _settle import settle
+from _timing import copy_floor, time_ms
 
 ALL = ("depth", "normal", "id", "albedo")
 PACK_BYTES, ITER_BYTES, LAST_BYTES = 96, 52, 72      # per pixel, read + written
-
-
-def time_ms(step, iters, reps):
-    settle(step, torch.cuda.synchronize, window=max(1, iters))
-    runs = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        runs.append(e0.elapsed_time(e1) / iters)
-    return statistics.median(runs)
-
-
-def copy_floor(lib, npx, bytes_per_px, iters, reps, st):
-    """ms of a float4 copy that reads and writes bytes_per_px * npx bytes in all (half read, half written)."""
-    n16 = npx * bytes_per_px // 2 // 16
-    src = torch.empty(n16 * 4, dtype=torch.float32, device="cuda").normal_()
-    dst = torch.empty_like(src)
-    return time_ms(lambda: lib.rt_debug_copy16(src.data_ptr(), dst.data_ptr(), n16, st), iters, reps)
 
 
 def denoise_cases(rt, scene, w, h, iters, reps):
@@ -70,9 +48,9 @@ def denoise_cases(rt, scene, w, h, iters, reps):
             r["launches"] = (["pack"] if variant != 1 else []) + [f"step{1 << i}" for i in range(n)]
             res[f"iterations{n}_variant{variant}"] = r
     npx = w * h
-    floor = {"pack_ms": copy_floor(scene.lib, npx, PACK_BYTES, iters, reps, st),
-             "iteration_ms": copy_floor(scene.lib, npx, ITER_BYTES, iters, reps, st),
-             "last_iteration_ms": copy_floor(scene.lib, npx, LAST_BYTES, iters, reps, st)}
+    floor = {"pack_ms": copy_floor(scene.lib, npx * PACK_BYTES, iters, reps, st),
+             "iteration_ms": copy_floor(scene.lib, npx * ITER_BYTES, iters, reps, st),
+             "last_iteration_ms": copy_floor(scene.lib, npx * LAST_BYTES, iters, reps, st)}
     floor["default_call_ms"] = floor["pack_ms"] + 3 * floor["iteration_ms"] + floor["last_iteration_ms"]
     res["traffic_floor"] = floor
     d4 = res["iterations4_variant0"]

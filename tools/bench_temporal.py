@@ -16,32 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
 import torch
 import rt_amd
-from _settle import settle
+from _timing import copier, interleaved_ms
 
 GUIDES = ("depth", "normal", "id")
 CUR_BYTES, PREV_BYTES, MOMENT_BYTES, OUT_BYTES = 44, 44, 8, 20      # per pixel; + 8 of moments written
-
-
-def timed(step, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        step()
-    e1.record()
-    return e0, e1
-
-
-def interleaved_ms(steps, iters, reps):
-    """{name: median ms per call}: every repetition times each of `steps` once, one after the other."""
-    for s in steps.values():
-        settle(s, torch.cuda.synchronize, window=max(1, iters))
-    runs = {k: [] for k in steps}
-    for _ in range(reps):
-        ev = {k: timed(s, iters) for k, s in steps.items()}
-        torch.cuda.synchronize()
-        for k, (e0, e1) in ev.items():
-            runs[k].append(e0.elapsed_time(e1) / iters)
-    return {k: statistics.median(v) for k, v in runs.items()}
 
 
 def cases(rt, scene, w, h, iters, reps, step_len):
@@ -82,28 +60,18 @@ def cases(rt, scene, w, h, iters, reps, step_len):
             state["k"] += 1
         return step
 
-    npx = w * h
-
-    def copier(bytes_per_px):
-        n16 = npx * bytes_per_px // 2 // 16
-        src = torch.empty(n16 * 4, dtype=torch.float32, device="cuda").normal_()
-        dst = torch.empty_like(src)
-        return lambda: scene.lib.rt_debug_copy16(src.data_ptr(), dst.data_ptr(), n16, st)
-
     full = CUR_BYTES + PREV_BYTES + MOMENT_BYTES + OUT_BYTES + 8
     bare = CUR_BYTES + PREV_BYTES + OUT_BYTES
-    res = {"moving": interleaved_ms({"variant0_ms": stepper(descs(0, True)), "variant1_ms": stepper(descs(1, True)),
-                                     "copy_floor_ms": copier(full)}, iters, reps),
-           "moving_no_moments": interleaved_ms({"variant0_ms": stepper(descs(0, False)), "variant1_ms": stepper(descs(1, False)),
-                                                "copy_floor_ms": copier(bare)}, iters, reps),
-           "standing": interleaved_ms({"variant0_ms": stepper(descs(0, True, standing=True)),
-                                       "variant1_ms": stepper(descs(1, True, standing=True)), "copy_floor_ms": copier(full)},
-                                      iters, reps),
-           "reset": interleaved_ms({"variant0_ms": stepper(descs(0, True, reset=True)),
-                                    "variant1_ms": stepper(descs(1, True, reset=True)),
-                                    "copy_floor_ms": copier(16 + OUT_BYTES + 8)}, iters, reps)}
-    res["traffic_floor_bytes_per_pixel"] = {"moving": full, "moving_no_moments": bare, "standing": full, "reset": 16 + OUT_BYTES + 8}
-    for k in ("moving", "moving_no_moments", "standing", "reset"):
+    floor = {"moving": full, "moving_no_moments": bare, "standing": full, "reset": 16 + OUT_BYTES + 8}
+    kw = {"moving": dict(), "moving_no_moments": dict(), "standing": dict(standing=True), "reset": dict(reset=True)}
+    res = {}
+    for k, bytes_per_px in floor.items():
+        moments = k != "moving_no_moments"
+        res[k], _ = interleaved_ms({"variant0_ms": stepper(descs(0, moments, **kw[k])),
+                                    "variant1_ms": stepper(descs(1, moments, **kw[k])),
+                                    "copy_floor_ms": copier(scene.lib, w * h * bytes_per_px, st)}, iters, reps)
+    res["traffic_floor_bytes_per_pixel"] = floor
+    for k in floor:
         r = res[k]
         r["variant1_over_variant0"] = r["variant1_ms"] / r["variant0_ms"]
         r["variant0_over_floor"] = r["variant0_ms"] / r["copy_floor_ms"]

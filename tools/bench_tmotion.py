@@ -22,34 +22,11 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
 import numpy as np
 import torch
 import rt_amd
-from _settle import settle
+from _timing import copier, interleaved_ms
 
 GUIDES = ("depth", "normal", "id")
 BYTES = 44 + 44 + 8 + 20 + 8            # current inputs, previous colour and guides, previous moments, outputs
 MOVE = (0.01, 0.005, -0.01)             # per frame, every 16th sphere
-
-
-def timed(step, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        step()
-    e1.record()
-    return e0, e1
-
-
-def interleaved_ms(steps, iters, reps):
-    """({name: median ms per call}, {name: host ms per call of the pre-roll's last window})."""
-    pre = {}
-    for k, s in steps.items():
-        pre[k] = settle(s, torch.cuda.synchronize, window=max(1, iters))[-1] * 1e3
-    runs = {k: [] for k in steps}
-    for _ in range(reps):
-        ev = {k: timed(s, iters) for k, s in steps.items()}
-        torch.cuda.synchronize()
-        for k, (e0, e1) in ev.items():
-            runs[k].append(e0.elapsed_time(e1) / iters)
-    return {k: statistics.median(v) for k, v in runs.items()}, pre
 
 
 def cases(rt, scene, w, h, iters, reps, step_len):
@@ -110,15 +87,12 @@ def cases(rt, scene, w, h, iters, reps, step_len):
             state["k"] += 1
         return step
 
-    n16 = w * h * BYTES // 2 // 16
-    src = torch.empty(n16 * 4, dtype=torch.float32, device="cuda").normal_()
-    dst = torch.empty_like(src)
     steps = {"temporal_v0_ms": stepper("temporal", descs("temporal", 0)),
              "motion_v0_ms": stepper("motion", descs("motion", 0)),
              "motion_v1_ms": stepper("motion", descs("motion", 1)),
              "noclamp_v0_ms": stepper("motion", descs("motion", 0, clamp=False)),
              "zero_v0_ms": stepper("motion", descs("motion", 0, zero=True)),
-             "copy_floor_ms": lambda: scene.lib.rt_debug_copy16(src.data_ptr(), dst.data_ptr(), n16, st)}
+             "copy_floor_ms": copier(scene.lib, w * h * BYTES, st)}
     res, pre = interleaved_ms(steps, iters, reps)
     res["preroll_last_window_host_ms"] = pre
     res["motion_v0_over_temporal_v0"] = res["motion_v0_ms"] / res["temporal_v0_ms"]

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
 import torch
 import rt_amd
-from bench_denoise import time_ms
+from _timing import copy_floor, time_ms
 
 GUIDES = ("depth", "normal", "id")
 
@@ -99,12 +99,8 @@ def main():
         r["selected_share"] = float((source != 0).float().mean())
         r["upsampled_share"] = float((source == 1).float().mean())
         r["selected_without_a_tap"] = int((source == 2).sum())
-        nbytes = moved_bytes(source, factor)
-        n16 = nbytes // 2 // 16
-        src = torch.empty(n16 * 4, dtype=torch.float32, device="cuda").normal_()
-        dst = torch.empty_like(src)
-        r["moved_bytes"] = nbytes
-        r["copy_floor_ms"] = time_ms(lambda: scene.lib.rt_debug_copy16(src.data_ptr(), dst.data_ptr(), n16, st), a.iters, a.reps)
+        r["moved_bytes"] = moved_bytes(source, factor)
+        r["copy_floor_ms"] = copy_floor(scene.lib, r["moved_bytes"], a.iters, a.reps, st)
         r["variant0_over_copy"] = r["upsample_variant0_ms"] / r["copy_floor_ms"]
         r["variant1_over_variant0"] = r["upsample_variant1_ms"] / r["upsample_variant0_ms"]
         r["pipeline_over_full_frame"] = r["pipeline_ms"] / out["reflective_frame_full_ms"]

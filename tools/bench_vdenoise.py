@@ -17,32 +17,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
 import torch
 import rt_amd
-from _settle import settle
+from _timing import copier, interleaved_ms
 
 ALL = ("depth", "normal", "id", "albedo")
 PACK_BYTES, SPATIAL_BYTES, ITER_BYTES, LAST_BYTES = 108, 44, 60, 80      # per pixel, read + written
-
-
-def timed(step, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        step()
-    e1.record()
-    return e0, e1
-
-
-def interleaved_ms(steps, iters, reps):
-    """{name: median ms per call}: every repetition times each of `steps` once, one after the other."""
-    for s in steps.values():
-        settle(s, torch.cuda.synchronize, window=max(1, iters))
-    runs = {k: [] for k in steps}
-    for _ in range(reps):
-        ev = {k: timed(s, iters) for k, s in steps.items()}
-        torch.cuda.synchronize()
-        for k, (e0, e1) in ev.items():
-            runs[k].append(e0.elapsed_time(e1) / iters)
-    return {k: statistics.median(v) for k, v in runs.items()}
 
 
 def moving_history(rt, scene, w, h, step_len):
@@ -104,7 +82,7 @@ def cases(rt, scene, w, h, iters, reps, step_len):
         steps = {"variant0_moments": vd_step(n, 0, True), "variant1_moments": vd_step(n, 1, True),
                  "variant2_moments": vd_step(n, 2, True), "variant0_null": vd_step(n, 0, False),
                  "variant1_null": vd_step(n, 1, False), "rt_scene_denoise": dn_step(n)}
-        r = {"call_ms": interleaved_ms(steps, iters, reps), "launch_ms": {}}
+        r = {"call_ms": interleaved_ms(steps, iters, reps)[0], "launch_ms": {}}
         for k, s in steps.items():
             if k == "rt_scene_denoise":
                 r["launch_ms"][k] = launches(s, scene.denoise_times, scene.set_denoise_timing)
@@ -122,16 +100,8 @@ def cases(rt, scene, w, h, iters, reps, step_len):
     res["launches"] = {"variants 0 and 2": ["pack", "spatial"] + [f"step{1 << i}" for i in range(6)],
                        "variant 1": ["initial variance"] + [f"step{1 << i}" for i in range(6)],
                        "rt_scene_denoise": ["pack"] + [f"step{1 << i}" for i in range(6)]}
-    npx = w * h
-
-    def copier(bytes_per_px):
-        n16 = npx * bytes_per_px // 2 // 16
-        src = torch.empty(n16 * 4, dtype=torch.float32, device="cuda").normal_()
-        dst = torch.empty_like(src)
-        return lambda: scene.lib.rt_debug_copy16(src.data_ptr(), dst.data_ptr(), n16, st)
-    res["traffic_floor"] = interleaved_ms({"pack_ms": copier(PACK_BYTES), "spatial_dense_ms": copier(SPATIAL_BYTES),
-                                           "iteration_ms": copier(ITER_BYTES), "last_iteration_ms": copier(LAST_BYTES)},
-                                          iters, reps)
+    floors = {"pack_ms": PACK_BYTES, "spatial_dense_ms": SPATIAL_BYTES, "iteration_ms": ITER_BYTES, "last_iteration_ms": LAST_BYTES}
+    res["traffic_floor"], _ = interleaved_ms({k: copier(scene.lib, w * h * b, st) for k, b in floors.items()}, iters, reps)
     r6 = res["iterations6"]["launch_ms"]
     res["step16"] = {"variant0_ms": r6["variant0_moments"][6], "variant2_ms": r6["variant2_moments"][6]}
     res["spatial_pass_ms"] = {"sparse (moving camera, moments)": r6["variant0_moments"][1], "dense (moments = NULL)": r6["variant0_null"][1]}
