@@ -347,11 +347,12 @@ int rt_scene_set_lights(rt_scene *s, const rt_light *lights, int n);
 
 /* material, kernel.cu:213-224 (field names as the reference spells them). Only reflectivness is
  * implemented here; a material with transperancy or roughness != 0 is RT_ERR_UNSUPPORTED
- * (transparency is set through rt_material_ex, which carries an index of refraction). */
+ * (transparency is set through rt_material_ex, which carries an index of refraction; roughness
+ * through rt_scene_set_roughness, below "Glossy reflections"). */
 typedef struct rt_material {
     float reflectivness;     /* k in [0, 1]: the share of a hit's colour taken from its mirror ray */
     float transperancy;      /* must be 0 */
-    float roughness;         /* must be 0 */
+    float roughness;         /* must be 0 (set it with rt_scene_set_roughness) */
 } rt_material;               /* 12 bytes */
 
 /* One material per sphere of the scene's list (n == the sphere count); NULL / 0 clears them (every
@@ -375,7 +376,7 @@ typedef struct rt_material_ex {
     float reflectivness;     /* k in [0, 1]                                                        */
     float transperancy;      /* tau in [0, 1]: the share of a hit's colour taken from the ray that
                                 passes through the sphere                                          */
-    float roughness;         /* must be 0 (RT_ERR_UNSUPPORTED)                                     */
+    float roughness;         /* must be 0 (RT_ERR_UNSUPPORTED; rt_scene_set_roughness sets it)     */
     float ior;               /* index of refraction, finite, in [1, 4], where tau > 0; ignored (may
                                 be 0) where tau == 0                                               */
 } rt_material_ex;            /* 16 bytes */
@@ -1017,6 +1018,16 @@ int rt_debug_refract(const rt_vec3 *I, const rt_vec3 *N, const float *eta, int n
  * -1 when intersect() reports no hit (out[i] = rays[i]).                                          */
 int rt_debug_transmit(const rt_sphere *sphere, const float *ior, const rt_ray *rays, int n,
                       rt_ray *out, int *entered);
+/* rf_gloss of rt_scene_set_roughness (the same code the kernels run) for n tuples (R, N, rho, key, b):
+ * out[i] = the continuation; what[i] (may be NULL) = 0 nothing drawn (rho == 0), else 1, | 2 when the
+ * halved fourth draw was taken, | 4 when R' was rejected and out[i] = R.                            */
+int rt_debug_gloss(const rt_vec3 *R, const rt_vec3 *N, const float *rho, const unsigned *key, const int *b, int n,
+                   rt_vec3 *out, int *what);
+/* key(px, py, s, seed) of rt_scene_set_roughness for n tuples.                                      */
+int rt_debug_gloss_key(const unsigned *px, const unsigned *py, const unsigned *s, const unsigned *seed, int n,
+                       unsigned *key);
+/* sizeof of the reflective passes' queue entry (48; its last word carries the glossy key).          */
+int rt_debug_reflect_entry_size(void);
 int rt_debug_occluder_lists_ex(const rt_sphere *spheres, int n, const rt_light *light, int *counts, float *kcaps, int *members, int cap,
                                int *offsets, int *entries_allocated);
 
@@ -1062,6 +1073,49 @@ int rt_scene_set_reflect_scope(rt_scene *s, int scope);
  * an error. The tables may be set under either scope; only frames under RT_REFLECT_SCENE read them. */
 int rt_scene_set_plane_materials(rt_scene *s, const rt_material *per_plane, int n);
 int rt_scene_set_cube_materials(rt_scene *s, const rt_material *per_cube, int n);
+
+/* ------------------------------------------------------------------ *
+ * Glossy reflections.                                  *
+ * ------------------------------------------------------------------ */
+/* Roughness per primitive of one kind: kind = RT_HIT_SPHERE, RT_HIT_PLANE or RT_HIT_CUBE (anything
+ * else: RT_ERR_INVALID; a triangle has roughness 0), one value in [0, 1] per primitive of that
+ * kind's list. NULL or n == 0 clears the kind's table (every rho = 0) and always succeeds. A count
+ * other than the list's, a NaN or a value outside [0, 1]: RT_ERR_INVALID, and nothing changes on an
+ * error. A table follows its kind's k table: it survives rt_scene_set_spheres / _planes / _cubes with
+ * the same count and is cleared by a different count; the plane and cube tables may be set under
+ * either scope and are read only under RT_REFLECT_SCENE.
+ *
+ * Roughness has an entry of its own, and rt_material / rt_material_ex keep refusing a non-zero
+ * roughness field: those structs describe a surface that one ray continues deterministically, and
+ * callers (the drop-in boundary among them) rely on a frame that is a function of the scene alone.
+ * A rough surface makes the frame a function of the sample index and of a seed as well, which only
+ * a caller that asked for it by name should get.
+ *
+ * Semantics: the per-pixel loop of rt_scene_set_materials under either scope, with one change. At a
+ * hit b (0: the primary hit) that continues as a mirror (k > 0, b < D, not glass) on a primitive
+ * with rho > 0, R_{b+1}'s direction is not R = reflect(R_b.Dir, N) but gloss(R, N, rho, key, b).
+ * All integer arithmetic is uint32 and wraps:
+ *   mix(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *   key = mix(mix(mix(mix(seed) ^ s) ^ py) ^ px)    px, py: the pixel in the full frame (py counts
+ *         from row 0 of the frame, not from opts.y0); s: the absolute sample index, sample_base + j
+ *         under RT_REFLECT_SAMPLES_MANY and 0 under the default mode; seed: rt_scene_set_gloss_seed
+ *   draw(key, b, t), axis a = 0, 1, 2:  h = mix(key + 0x9e3779b9 * ((b*4 + t)*3 + a + 1)),
+ *         u_a = float(h >> 8) * 2^-23 - 1            (exact, in [-1, 1))
+ *   u = the first of the draws t = 0, 1, 2, 3 with (ux*ux + uy*uy) + uz*uz <= 1; if none, draw 3
+ *       with every component multiplied by 0.5f
+ *   G = (R.x + rho*ux, R.y + rho*uy, R.z + rho*uz), R' = normalise(G) (G as it is where its length
+ *       is 0); the continuation is R' if dot(R', N) * dot(R, N) > 0 (both dots left to right; a NaN
+ *       fails), else R unchanged.
+ * binary32, no contraction, correctly rounded division and sqrt. rho == 0 draws nothing: a scene
+ * whose tables hold no value > 0 renders exactly as without them. Roughness on a glass sphere
+ * (tau > 0) or on a surface with k == 0 is accepted and has no effect. The multiplicity of a glossy
+ * lobe comes from spp and accumulate under RT_REFLECT_SAMPLES_MANY, or from one sample per frame
+ * with a new seed (or sample_base) accumulated by rt_scene_temporal. What a reflective frame
+ * refuses, and rt_reflect_stats, are unchanged. */
+int rt_scene_set_roughness(rt_scene *s, int kind, const float *rho, int n);
+/* The seed of the glossy draws (default 0, any value): a host-side value, read when a frame is
+ * launched: no wait, no device needed. */
+int rt_scene_set_gloss_seed(rt_scene *s, unsigned seed);
 
 /* ------------------------------------------------------------------ *
  * Supersampled reflective frames.                      *

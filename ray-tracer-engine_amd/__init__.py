@@ -156,6 +156,7 @@ RT_REFLECT_SPHERES, RT_REFLECT_SCENE = 0, 1     # rt_scene_set_reflect_scope
 _REFLECT_SCOPES = {"spheres": RT_REFLECT_SPHERES, "scene": RT_REFLECT_SCENE}
 RT_REFLECT_SAMPLES_ONE, RT_REFLECT_SAMPLES_MANY = 0, 1     # rt_scene_set_reflect_samples
 _REFLECT_SAMPLES = {"one": RT_REFLECT_SAMPLES_ONE, "many": RT_REFLECT_SAMPLES_MANY}
+_ROUGH_KINDS = {"sphere": RT_HIT_SPHERE, "plane": RT_HIT_PLANE, "cube": RT_HIT_CUBE}   # Scene.set_roughness
 
 
 class Hit(C.Structure):
@@ -388,6 +389,12 @@ def load_library():
         "rt_scene_set_reflect_samples": (ci, [vp, ci]),
         "rt_scene_set_plane_materials": (ci, [vp, C.POINTER(Material), ci]),
         "rt_scene_set_cube_materials": (ci, [vp, C.POINTER(Material), ci]),
+        "rt_scene_set_roughness": (ci, [vp, ci, fp, ci]),
+        "rt_scene_set_gloss_seed": (ci, [vp, C.c_uint]),
+        "rt_debug_gloss": (ci, [C.POINTER(Vec3), C.POINTER(Vec3), fp, C.POINTER(C.c_uint), C.POINTER(ci), ci,
+                                C.POINTER(Vec3), C.POINTER(ci)]),
+        "rt_debug_gloss_key": (ci, [C.POINTER(C.c_uint)] * 4 + [ci, C.POINTER(C.c_uint)]),
+        "rt_debug_reflect_entry_size": (ci, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -690,6 +697,26 @@ class Scene:
     def set_cube_materials(self, reflectivity):
         """One material per cube (floats k in [0, 1], or Material); None clears them. Read under the "scene" scope."""
         self.cube_materials = self._set_kind_materials("rt_scene_set_cube_materials", reflectivity)
+
+    def set_roughness(self, kind, values):
+        """Roughness per primitive of one kind ("sphere", "plane" or "cube"; also RT_HIT_SPHERE / _PLANE / _CUBE): one
+        float in [0, 1] per primitive of that list; None (or empty) clears the kind's table. The mirror continuation of
+        a hit with roughness > 0 is jittered inside a ball of that radius; the draws are a function of
+        the pixel, the sample index and set_gloss_seed. The plane and cube tables are read under the "scene" scope."""
+        if isinstance(kind, str):
+            if kind not in _ROUGH_KINDS:
+                raise RtError(f"unknown roughness kind {kind!r} (one of {tuple(_ROUGH_KINDS)})")
+            kind = _ROUGH_KINDS[kind]
+        if values is None or len(values) == 0:
+            _check(self.lib.rt_scene_set_roughness(self.handle, int(kind), None, 0), "rt_scene_set_roughness")
+            return
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        _check(self.lib.rt_scene_set_roughness(self.handle, int(kind), _fptr(v), v.shape[0]), "rt_scene_set_roughness")
+
+    def set_gloss_seed(self, seed: int):
+        """The seed of the glossy draws (default 0; taken modulo 2^32). One sample per frame with set_gloss_seed(frame)
+        into Scene.temporal(colour=...) accumulates a glossy lobe over frames."""
+        _check(self.lib.rt_scene_set_gloss_seed(self.handle, int(seed) & 0xffffffff), "rt_scene_set_gloss_seed")
 
     def set_reflect_timing(self, on: bool):
         _check(self.lib.rt_scene_set_reflect_timing(self.handle, 1 if on else 0), "rt_scene_set_reflect_timing")

@@ -38,6 +38,7 @@ struct RtReflectDev {              // the passes' uniforms (by value)
     const float *k;                // reflectivness per sphere (null: all 0)
     int depth;
     const float2 *glass;           // (transperancy, ior) per sphere (null: no sphere has transperancy > 0)
+    const float *rough;            // roughness per sphere (null: all 0); read by the GLOSS passes only
 };
 
 // ---------------------------------------------------------------------------

@@ -26,6 +26,12 @@
 // is then the slab index), the bounces as they are with the slab as their rgba, and rt_reflect_resolve, which sums a
 // pixel's slab entries in ascending sample order and is the only pass that touches the caller's outputs.
 //
+// Glossy reflections (rt_scene_set_roughness) are a last template parameter, GLOSS: the mirror continuation
+// of a hit whose roughness is > 0 is rf_gloss's -- the mirror direction plus roughness times a point of the unit ball,
+// drawn by an integer hash of the pixel, the sample, the hit's index and the scene's seed, renormalised. The primary
+// pass forms the pixel-sample's key and the queue entry carries it. The host launches GLOSS = true only when a
+// roughness table the frame reads holds a value > 0: every other frame runs today's code.
+//
 // The BVH and the per-ray pieces the ray queries share are in rt_bvh.h, the all-kinds casts in rt_cast.h.
 #include "rt_cast.h"
 
@@ -44,13 +50,17 @@ struct QEntry {    // one queued ray: 48 bytes
     float ox, oy, oz, dx, dy, dz;
     float w, cr, cg, cb;
     int pix;       // band-local pixel index (a supersampled frame: sample slot * band pixels + that)
-    int pad_;
+    int pad_;      // GLOSS: the pixel-sample's key (rf_gloss_key), formed by the primary pass and passed on unchanged
 };
+static_assert(sizeof(QEntry) == 48, "QEntry is 48 bytes");
 
-// The KINDS passes' tables beside RtReflectDev's per-sphere ones (the last kernel argument)
+// The KINDS passes' tables beside RtReflectDev's per-sphere ones, and the GLOSS passes' seed (the last kernel argument)
 struct RtKindsDev {
     const float *k_plane;          // reflectivness per plane (null: all 0)
     const float *k_cube;           // reflectivness per cube (null: all 0)
+    const float *rough_plane;      // roughness per plane (null: all 0)
+    const float *rough_cube;       // roughness per cube (null: all 0)
+    uint32_t gloss_seed;           // rt_scene_set_gloss_seed
 };
 
 // reflect(I, N), kernel.cu:1282-1285: sub(I, multiply(multiply(N, dot(I, N)), 2)), the dot product left to right
@@ -61,6 +71,64 @@ __host__ __device__ __forceinline__ void rf_reflect(float ix, float iy, float iz
     rx = ix - (nx * d) * 2.f;
     ry = iy - (ny * d) * 2.f;
     rz = iz - (nz * d) * 2.f;
+}
+
+// Glossy reflection: the integer mixer of the draws, uint32 throughout (wrapping)
+__host__ __device__ __forceinline__ uint32_t rf_mix(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// The key of pixel (px, py) of the full frame at absolute sample s under the scene's seed
+__host__ __device__ __forceinline__ uint32_t rf_gloss_key(uint32_t px, uint32_t py, uint32_t s, uint32_t seed)
+{
+    return rf_mix(rf_mix(rf_mix(rf_mix(seed) ^ s) ^ py) ^ px);
+}
+
+// Component a of draw t for hit b under `key`: 24 bits of the mixed counter as an exact value of [-1, 1)
+__host__ __device__ __forceinline__ float rf_gloss_draw(uint32_t key, uint32_t b, uint32_t t, uint32_t a)
+{
+    const uint32_t h = rf_mix(key + 0x9e3779b9u * ((b * 4u + t) * 3u + a + 1u));
+    return (float)(h >> 8) * 1.1920928955078125e-07f - 1.f;   // 2^-23
+}
+
+// The glossy continuation of a hit with mirror direction R, normal N and roughness rho: u = the first of the draws
+// t = 0..3 inside the unit ball (none: draw 3 halved), R' = normalise(R + rho * u), which is taken if it leaves the
+// surface on R's side (dot(R', N) * dot(R, N) > 0, NaN fails) and else R. rho == 0 draws nothing and gives R.
+// Returns what happened: 0 nothing drawn; 1 perturbed; | 2 the halved draw; | 4 R' rejected (the output is R).
+__host__ __device__ __forceinline__ int rf_gloss(V3 R, V3 N, float rho, uint32_t key, uint32_t b, V3 &out)
+{
+    out = R;
+    if (rho == 0.f) return 0;
+    int what = 1 | 2;
+    float ux = 0.f, uy = 0.f, uz = 0.f;
+#pragma unroll 1
+    for (uint32_t t = 0; t < 4u; ++t) {
+        ux = rf_gloss_draw(key, b, t, 0u);
+        uy = rf_gloss_draw(key, b, t, 1u);
+        uz = rf_gloss_draw(key, b, t, 2u);
+        if ((ux * ux + uy * uy) + uz * uz <= 1.f) {
+            what = 1;
+            break;
+        }
+    }
+    if (what & 2) {
+        ux = ux * 0.5f;
+        uy = uy * 0.5f;
+        uz = uz * 0.5f;
+    }
+    V3 G{R.x + rho * ux, R.y + rho * uy, R.z + rho * uz};
+    rf_normalise(G);
+    const float dg = (G.x * N.x + G.y * N.y) + G.z * N.z;
+    const float dr = (R.x * N.x + R.y * N.y) + R.z * N.z;
+    if (dg * dr > 0.f) out = G;
+    else what |= 4;
+    return what;
 }
 
 // refract(I, n, eta) for a normal n that faces against I: c = -dot(I, n) (left to right), q = 1 - (eta*eta) * (1 - c*c),
@@ -192,6 +260,15 @@ __device__ __forceinline__ float rf_kind_k(const RtReflectDev &rd, const RtKinds
     return 0.f;
 }
 
+// roughness of the hit primitive, as rf_kind_k
+__device__ __forceinline__ float rf_kind_rough(const RtReflectDev &rd, const RtKindsDev &kd, int kind, int pos)
+{
+    if (kind == RT_HIT_SPHERE) return rd.rough ? rd.rough[pos] : 0.f;
+    if (kind == RT_HIT_PLANE) return kd.rough_plane ? kd.rough_plane[pos] : 0.f;
+    if (kind == RT_HIT_CUBE) return kd.rough_cube ? kd.rough_cube[pos] : 0.f;
+    return 0.f;
+}
+
 __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float cr, float cg, float cb)
 {
     if (fc.rgba) reinterpret_cast<float4 *>(fc.rgba)[pix] = make_float4(cr, cg, cb, 1.f);
@@ -204,7 +281,9 @@ __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float
 // SAMPLES: a group of fc.spp samples, the first of them sample fc.sample_base of the raygen tables' total. Thread i is
 // pixel i % npx at sample fc.sample_base + i / npx; fc.rgba is the group's slab [fc.spp][npx], where the frame kernel
 // has left that sample's L at [i], and the queue entry's pix is i.
-template <bool GLASS, bool KINDS, bool SAMPLES>
+// GLOSS: some roughness table the frame reads holds a value > 0. Every queued entry carries the key of its
+// pixel-sample, and the mirror continuation of a hit whose roughness is > 0 is rf_gloss's (hit 0 here, hit b in bounce b).
+template <bool GLASS, bool KINDS, bool SAMPLES, bool GLOSS>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtFrameConsts fc, const RtReflectDev rd,
                                                                        QEntry *q, int *count, const RtKindsDev kd)
 {
@@ -263,6 +342,23 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
                 e.ox = start.x; e.oy = start.y; e.oz = start.z;
                 rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, e.dx, e.dy, e.dz);
             }
+            if constexpr (GLOSS) {
+                // the pixel in the full frame (rows count from row 0 of the frame) and the absolute sample index
+                const int sj = SAMPLES ? pix / npx : 0;
+                const int lp = pix - sj * npx;
+                const int ly = lp / fc.width;
+                const uint32_t key = rf_gloss_key((uint32_t)(lp - ly * fc.width), (uint32_t)(fc.y0 + ly),
+                                                  (uint32_t)(SAMPLES ? fc.sample_base + sj : 0), kd.gloss_seed);
+                e.pad_ = (int)key;
+                if (!(GLASS && g.x > 0.f)) {
+                    const float rho = KINDS ? rf_kind_rough(rd, kd, kind, hit) : (rd.rough ? rd.rough[hit] : 0.f);
+                    if (rho > 0.f) {
+                        V3 Rg;
+                        rf_gloss(V3{e.dx, e.dy, e.dz}, normal, rho, key, 0u, Rg);
+                        e.dx = Rg.x; e.dy = Rg.y; e.dz = Rg.z;
+                    }
+                }
+            }
             e.w = k;                                                            // w * k with w = 1
             e.cr = f * L.x; e.cg = f * L.y; e.cb = f * L.z;                     // the first term is assigned
             e.pix = pix;
@@ -273,7 +369,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
 }
 
 // Bounce b (1..depth): a fixed grid walks the queue of the previous pass; its length is read here, on the device.
-template <bool GLASS, bool KINDS>
+template <bool GLASS, bool KINDS, bool GLOSS>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFrameConsts fc, const RtReflectDev rd, int b,
                                                                       const QEntry *qin, const int *count_in, QEntry *qout,
                                                                       int *count_out, const RtKindsDev kd)
@@ -343,7 +439,16 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
                     } else {
                         nx.ox = start.x; nx.oy = start.y; nx.oz = start.z;
                         rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, nx.dx, nx.dy, nx.dz);
+                        if constexpr (GLOSS) {
+                            const float rho = KINDS ? rf_kind_rough(rd, kd, kind, hit) : (rd.rough ? rd.rough[hit] : 0.f);
+                            if (rho > 0.f) {
+                                V3 Rg;
+                                rf_gloss(V3{nx.dx, nx.dy, nx.dz}, normal, rho, (uint32_t)e.pad_, (uint32_t)b, Rg);
+                                nx.dx = Rg.x; nx.dy = Rg.y; nx.dz = Rg.z;
+                            }
+                        }
                     }
+                    if constexpr (GLOSS) nx.pad_ = e.pad_;
                     nx.w = e.w * k;
                     nx.cr = cr; nx.cg = cg; nx.cb = cb;
                     nx.pix = e.pix;
@@ -409,17 +514,20 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_resolve(const flo
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// A per-plane or per-cube reflectivness table: d_k's protocol (the device copy changes only in rt_reflect_prepare)
+// A per-plane or per-cube reflectivness table, or a roughness table of any kind: d_k's protocol (the device copy
+// changes only in rt_reflect_prepare)
 struct RtKTable {
     std::vector<float> k;                 // empty = all 0
     std::vector<float> k_dev;             // what the device copy holds
     bool dirty = false;
+    bool pos_dev = false;                 // k_dev holds a value > 0 (the roughness tables: whether GLOSS is needed)
     DevArray<float> d_k;
     void clear()
     {
         if (!k.empty()) dirty = true;
         k.clear();
     }
+    const float *dev() const { return k_dev.empty() ? nullptr : d_k.get(); }
 };
 
 struct RtReflect {
@@ -435,6 +543,8 @@ struct RtReflect {
     int scope = RT_REFLECT_SPHERES;       // rt_scene_set_reflect_scope
     int samples = RT_REFLECT_SAMPLES_ONE; // rt_scene_set_reflect_samples
     RtKTable plane_k, cube_k;             // read only by frames under RT_REFLECT_SCENE
+    RtKTable rough_sphere, rough_plane, rough_cube;   // rt_scene_set_roughness (the last two: as plane_k, cube_k)
+    unsigned gloss_seed = 0;              // rt_scene_set_gloss_seed: a host-side value, read when a frame is launched
     RtSphereBvh bvh;                      // the sphere BVH (shared with the ray queries)
     // queues and counters
     DevArray<QEntry> d_q[2];
@@ -597,6 +707,7 @@ void rt_reflect_spheres_changed(RtReflect *r, int n_old, int n_new)
         r->glass.clear();
         r->glass_dirty = true;
     }
+    if (n_old != n_new) r->rough_sphere.clear();
 }
 
 // the old entry sets every transperancy to 0
@@ -739,7 +850,47 @@ int rt_reflect_set_kind_materials(RtReflect *r, int which, const rt_material *m,
 // rt_scene_set_planes / rt_scene_set_cubes: a new count clears the list's materials (the same count keeps them)
 void rt_reflect_kind_list_changed(RtReflect *r, int which, int n_old, int n_new)
 {
-    if (n_old != n_new) (which == 0 ? r->plane_k : r->cube_k).clear();
+    if (n_old != n_new) {
+        (which == 0 ? r->plane_k : r->cube_k).clear();
+        (which == 0 ? r->rough_plane : r->rough_cube).clear();
+    }
+}
+
+// rt_scene_set_roughness: one value in [0, 1] per primitive of `kind`'s list of n_list entries, or NULL / 0 to clear
+int rt_reflect_set_roughness(RtReflect *r, int kind, const float *rho, int n, int n_list)
+{
+    if (kind != RT_HIT_SPHERE && kind != RT_HIT_PLANE && kind != RT_HIT_CUBE) {
+        rt_set_error("rt_scene_set_roughness: kind %d is not RT_HIT_SPHERE, RT_HIT_PLANE or RT_HIT_CUBE", kind);
+        return RT_ERR_INVALID;
+    }
+    const char *what = kind == RT_HIT_SPHERE ? "sphere" : (kind == RT_HIT_PLANE ? "plane" : "cube");
+    RtKTable &t = kind == RT_HIT_SPHERE ? r->rough_sphere : (kind == RT_HIT_PLANE ? r->rough_plane : r->rough_cube);
+    if (!rho || n == 0) {
+        t.clear();
+        return RT_OK;
+    }
+    if (n != n_list || n < 0) {
+        rt_set_error("rt_scene_set_roughness: %d values for %d %ss (one per %s, or NULL / 0)", n, n_list, what, what);
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!(rho[i] >= 0.f && rho[i] <= 1.f)) {
+            rt_set_error("rt_scene_set_roughness: %s %d: roughness %g is not in [0, 1]", what, i, (double)rho[i]);
+            return RT_ERR_INVALID;
+        }
+    }
+    std::vector<float> v(rho, rho + n);
+    if (v != t.k) {
+        t.k.swap(v);
+        t.dirty = true;
+    }
+    return RT_OK;
+}
+
+int rt_reflect_set_gloss_seed(RtReflect *r, unsigned seed)
+{
+    r->gloss_seed = seed;
+    return RT_OK;
 }
 
 int rt_reflect_set_scope(RtReflect *r, int scope)
@@ -769,7 +920,8 @@ int rt_reflect_samples(const RtReflect *r) { return r->samples; }
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n)
 {
     // (the plane and cube tables count under either scope: the upload is due whenever they changed)
-    return r->k_dirty || r->glass_dirty || r->plane_k.dirty || r->cube_k.dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
+    return r->k_dirty || r->glass_dirty || r->plane_k.dirty || r->cube_k.dirty || r->rough_sphere.dirty ||
+           r->rough_plane.dirty || r->rough_cube.dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
 }
 
 // Brings materials and BVH up to date (the caller has waited for every frame that may read them) and makes sure the
@@ -799,9 +951,10 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
         }
         r->glass_dirty = false;
     }
-    for (RtKTable *t : {&r->plane_k, &r->cube_k}) {
+    for (RtKTable *t : {&r->plane_k, &r->cube_k, &r->rough_sphere, &r->rough_plane, &r->rough_cube}) {
         if (!t->dirty) continue;
         t->k_dev = t->k;
+        t->pos_dev = std::any_of(t->k_dev.begin(), t->k_dev.end(), [](float v) { return v > 0.f; });
         if (!t->k_dev.empty()) {
             RT_HIP(t->d_k.reserve(t->k_dev.size()));
             RT_HIP(hipMemcpyAsync(t->d_k.get(), t->k_dev.data(), sizeof(float) * t->k_dev.size(), hipMemcpyHostToDevice, stream));
@@ -875,7 +1028,7 @@ int rt_reflect_mark_frame_start(RtReflect *r, hipStream_t stream)
 struct RfPasses {
     RtReflectDev rd;
     RtKindsDev kd;
-    bool glass, kinds;
+    bool glass, kinds, gloss;
 };
 
 static RfPasses rf_passes(const RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute)
@@ -896,7 +1049,30 @@ static RfPasses rf_passes(const RtReflect *r, const RtFrameConsts *fc, const flo
     p.kinds = r->scope == RT_REFLECT_SCENE && (fc->n_planes > 0 || fc->n_cubes > 0 || fc->n_boxes > 0);
     p.kd.k_plane = (p.kinds && !r->plane_k.k_dev.empty()) ? r->plane_k.d_k.get() : nullptr;
     p.kd.k_cube = (p.kinds && !r->cube_k.k_dev.empty()) ? r->cube_k.d_k.get() : nullptr;
+    // GLOSS only where a roughness table that this frame's scope reads holds a value > 0: every other frame runs the
+    // GLOSS = false instantiations with the arguments it had before roughness existed (no table, seed 0)
+    p.gloss = r->rough_sphere.pos_dev || (p.kinds && (r->rough_plane.pos_dev || r->rough_cube.pos_dev));
+    if (p.gloss) {
+        rd.rough = r->rough_sphere.dev();
+        p.kd.rough_plane = p.kinds ? r->rough_plane.dev() : nullptr;
+        p.kd.rough_cube = p.kinds ? r->rough_cube.dev() : nullptr;
+        p.kd.gloss_seed = r->gloss_seed;
+    }
     return p;
+}
+
+// The instantiations of the two passes for a frame's (glass, kinds), at compile-time SAMPLES and GLOSS
+template <bool SAMPLES, bool GLOSS>
+static auto rf_primary_kernel(const RfPasses &p)
+{
+    return p.kinds ? (p.glass ? rt_reflect_primary<true, true, SAMPLES, GLOSS> : rt_reflect_primary<false, true, SAMPLES, GLOSS>)
+                   : (p.glass ? rt_reflect_primary<true, false, SAMPLES, GLOSS> : rt_reflect_primary<false, false, SAMPLES, GLOSS>);
+}
+template <bool GLOSS>
+static auto rf_bounce_kernel(const RfPasses &p)
+{
+    return p.kinds ? (p.glass ? rt_reflect_bounce<true, true, GLOSS> : rt_reflect_bounce<false, true, GLOSS>)
+                   : (p.glass ? rt_reflect_bounce<true, false, GLOSS> : rt_reflect_bounce<false, false, GLOSS>);
 }
 
 // The primary pass over `threads` pixels (SAMPLES: pixel-samples) and the `depth` bounces, with the counter row `cnt`;
@@ -905,10 +1081,8 @@ template <bool SAMPLES, typename Mark>
 static int rf_run_passes(RtReflect *r, const RfPasses &p, const RtFrameConsts *fc, int threads, int depth, int *cnt,
                          hipStream_t stream, Mark mark)
 {
-    const auto primary = p.kinds ? (p.glass ? rt_reflect_primary<true, true, SAMPLES> : rt_reflect_primary<false, true, SAMPLES>)
-                                 : (p.glass ? rt_reflect_primary<true, false, SAMPLES> : rt_reflect_primary<false, false, SAMPLES>);
-    const auto bounce = p.kinds ? (p.glass ? rt_reflect_bounce<true, true> : rt_reflect_bounce<false, true>)
-                                : (p.glass ? rt_reflect_bounce<true, false> : rt_reflect_bounce<false, false>);
+    const auto primary = p.gloss ? rf_primary_kernel<SAMPLES, true>(p) : rf_primary_kernel<SAMPLES, false>(p);
+    const auto bounce = p.gloss ? rf_bounce_kernel<true>(p) : rf_bounce_kernel<false>(p);
     hipLaunchKernelGGL(primary, dim3((threads + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
                        stream, *fc, p.rd, r->d_q[0].get(), cnt, p.kd);
     RT_HIP(hipGetLastError());
@@ -1103,6 +1277,35 @@ extern "C" int rt_debug_reflect(const rt_vec3 *I, const rt_vec3 *N, int n, rt_ve
     for (int i = 0; i < n; ++i) rf_reflect(I[i].x, I[i].y, I[i].z, N[i].x, N[i].y, N[i].z, out[i].x, out[i].y, out[i].z);
     return RT_OK;
 }
+
+extern "C" int rt_debug_gloss(const rt_vec3 *R, const rt_vec3 *N, const float *rho, const unsigned *key, const int *b, int n,
+                              rt_vec3 *out, int *what)
+{
+    if (!R || !N || !rho || !key || !b || !out || n < 0) {
+        rt_set_error("rt_debug_gloss: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) {
+        V3 o;
+        const int w = rf_gloss(V3{R[i].x, R[i].y, R[i].z}, V3{N[i].x, N[i].y, N[i].z}, rho[i], key[i], (uint32_t)b[i], o);
+        out[i].x = o.x; out[i].y = o.y; out[i].z = o.z;
+        if (what) what[i] = w;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_gloss_key(const unsigned *px, const unsigned *py, const unsigned *s, const unsigned *seed, int n,
+                                  unsigned *key)
+{
+    if (!px || !py || !s || !seed || !key || n < 0) {
+        rt_set_error("rt_debug_gloss_key: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) key[i] = rf_gloss_key(px[i], py[i], s[i], seed[i]);
+    return RT_OK;
+}
+
+extern "C" int rt_debug_reflect_entry_size(void) { return (int)sizeof(QEntry); }
 
 extern "C" int rt_debug_refract(const rt_vec3 *I, const rt_vec3 *N, const float *eta, int n, rt_vec3 *out)
 {

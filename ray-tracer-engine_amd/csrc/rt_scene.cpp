@@ -400,6 +400,28 @@ extern "C" int rt_scene_set_cube_materials(rt_scene *s, const rt_material *per_c
     return rt_reflect_set_kind_materials(rt_scene_reflect(s), 1, per_cube, n, s->n_cubes);
 }
 
+// Roughness per primitive of one kind: tables of their own beside the k tables, under the same protocol
+extern "C" int rt_scene_set_roughness(rt_scene *s, int kind, const float *rho, int n)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_roughness: null scene");
+        return RT_ERR_INVALID;
+    }
+    const int n_list = kind == RT_HIT_SPHERE ? s->n_spheres : (kind == RT_HIT_PLANE ? s->n_planes : s->n_cubes);
+    // (as rt_scene_set_materials: the next reflective frame uploads after the frames in flight)
+    return rt_reflect_set_roughness(rt_scene_reflect(s), kind, rho, n, n_list);
+}
+
+// The seed of the glossy draws: a host-side value, read when a frame is launched
+extern "C" int rt_scene_set_gloss_seed(rt_scene *s, unsigned seed)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_gloss_seed: null scene");
+        return RT_ERR_INVALID;
+    }
+    return rt_reflect_set_gloss_seed(rt_scene_reflect(s), seed);
+}
+
 extern "C" int rt_scene_set_reflect_timing(rt_scene *s, int on)
 {
     if (!s) {

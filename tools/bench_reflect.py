@@ -13,7 +13,10 @@ reflective frame); per round ms per N samples, then median, min and max over the
 queue lengths of each, and the shader clock read while merged frames are in flight. The default of 1 runs exactly as
 described above.
 
-  python3 tools/bench_reflect.py [--iters 20] [--depth 3] [--floor] [--spp N --rounds 5] [--out FILE]
+--rough RHO (RHO > 0): glossy mirrors (rt_scene_set_roughness): that roughness on the mirrors the tool
+creates -- every fourth sphere and, with --floor, the plane. Combines with --floor and --spp; 0 sets no table.
+
+  python3 tools/bench_reflect.py [--iters 20] [--depth 3] [--floor] [--rough RHO] [--spp N --rounds 5] [--out FILE]
 """
 import argparse, ctypes, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,6 +106,7 @@ def main():
     ap.add_argument("--depth", type=int, default=3)
     ap.add_argument("--floor", action="store_true", help="add the reference's plane (k = 0.3) under the scene scope")
     ap.add_argument("--spp", type=int, default=1, help="> 1: the supersampled frame, three ways (see above)")
+    ap.add_argument("--rough", type=float, default=0.0, help="> 0: this roughness on the mirrors (see above)")
     ap.add_argument("--rounds", type=int, default=5, help="with --spp: rounds of the interleaved comparison")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     a = ap.parse_args()
@@ -116,9 +120,14 @@ def main():
         scene.set_planes(planes, 1)
         scene.set_plane_materials([0.3])
         scene.set_reflect_scope("scene")
+    if a.rough > 0:
+        scene.set_roughness("sphere", [a.rough if i % 4 == 0 else 0.0 for i in range(n)])
+        if a.floor:
+            scene.set_roughness("plane", [a.rough])
     rgba = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
     pk = torch.empty((h, w), dtype=torch.int32, device="cuda")
-    out = {"config": f"{w}x{h}_n{n}_k0.5_every4th_depth{a.depth}" + ("_floor_k0.3_scope_scene" if a.floor else ""),
+    out = {"config": f"{w}x{h}_n{n}_k0.5_every4th_depth{a.depth}" + ("_floor_k0.3_scope_scene" if a.floor else "") +
+           (f"_rough{a.rough:g}" if a.rough > 0 else ""),
            "iters": a.iters}
     if a.spp > 1:
         out["config"] += f"_spp{a.spp}"
