@@ -246,4 +246,5 @@ struct RtSphereBvh {
     double build_ms = 0.0;
 };
 // rt_sphere_bvh_stale: whether rt_sphere_bvh_update would rebuild it (the caller must first wait for every reader of the
-// device arrays); rt_sphere_bvh_update: rebuild and upload on `stream` when stale (rt_internal.h)
+// device arrays); rt_sphere_bvh_update: rebuild and upload on `stream` when stale (rt_sphere_bvh.cpp, declared in
+// rt_internal.h)

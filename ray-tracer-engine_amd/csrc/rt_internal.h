@@ -174,7 +174,12 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
 extern "C" hipError_t rt_dev_launch_trace(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
                                           int feat, hipStream_t stream);
 
-// rt_reflect.hip: mirror reflections (rt_launch_opts.reflect_depth) -- materials, sphere BVH, queues, passes
+// rt_sphere_bvh.cpp: the scene's sphere BVH (rt_bvh.h), shared by reflective frames and ray queries
+struct RtSphereBvh;
+bool rt_sphere_bvh_stale(const RtSphereBvh *b, unsigned long long sphere_gen, int n);
+int rt_sphere_bvh_update(RtSphereBvh *b, const float4 *h_spheres, int n, unsigned long long sphere_gen, hipStream_t stream);
+
+// rt_reflect.hip: mirror reflections (rt_launch_opts.reflect_depth) -- materials, queues, passes; it owns the scene's BVH
 struct RtReflect;
 RtReflect *rt_reflect_create();
 void rt_reflect_destroy(RtReflect *r);
@@ -209,11 +214,7 @@ int rt_reflect_launch_samples(RtReflect *r, const RtFrameConsts *fc, const RtFra
                               const float4 *d_spheres, int n, int depth, hipStream_t stream);
 int rt_reflect_set_timing(RtReflect *r, int on);
 int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out);
-// the scene's sphere BVH (rt_bvh.h), shared by reflective frames and ray queries
-struct RtSphereBvh;
 RtSphereBvh *rt_reflect_bvh(RtReflect *r);
-bool rt_sphere_bvh_stale(const RtSphereBvh *b, unsigned long long sphere_gen, int n);
-int rt_sphere_bvh_update(RtSphereBvh *b, const float4 *h_spheres, int n, unsigned long long sphere_gen, hipStream_t stream);
 
 // rt_query.hip: ray queries (q: validated, in this build's layout; bvh: null or current -- the list is walked then)
 int rt_query_launch(const RtFrameConsts *fc, const RtSphereBvh *bvh, const float4 *d_spheres, int n_spheres,

@@ -32,12 +32,11 @@
 // pass forms the pixel-sample's key and the queue entry carries it. The host launches GLOSS = true only when a
 // roughness table the frame reads holds a value > 0: every other frame runs today's code.
 //
-// The BVH and the per-ray pieces the ray queries share are in rt_bvh.h, the all-kinds casts in rt_cast.h.
+// The BVH and the per-ray pieces the ray queries share are in rt_bvh.h, the BVH's host build and its debug entries in
+// rt_sphere_bvh.cpp, the all-kinds casts in rt_cast.h.
 #include "rt_cast.h"
 
 #include <algorithm>
-#include <chrono>
-#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -251,22 +250,41 @@ __device__ __forceinline__ void rf_shade_kinds(const RtFrameConsts &fc, AuxPtr a
     if (act) q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
 }
 
-// k of the hit primitive: its kind's table at its list position; a triangle has none
-__device__ __forceinline__ float rf_kind_k(const RtReflectDev &rd, const RtKindsDev &kd, int kind, int pos)
+// k or roughness of the hit primitive: its kind's table (null: all 0) at its list position; a triangle has none
+__device__ __forceinline__ float rf_kind_value(const float *sphere, const float *plane, const float *cube, int kind, int pos)
 {
-    if (kind == RT_HIT_SPHERE) return rd.k ? rd.k[pos] : 0.f;
-    if (kind == RT_HIT_PLANE) return kd.k_plane ? kd.k_plane[pos] : 0.f;
-    if (kind == RT_HIT_CUBE) return kd.k_cube ? kd.k_cube[pos] : 0.f;
+    if (kind == RT_HIT_SPHERE) return sphere ? sphere[pos] : 0.f;
+    if (kind == RT_HIT_PLANE) return plane ? plane[pos] : 0.f;
+    if (kind == RT_HIT_CUBE) return cube ? cube[pos] : 0.f;
     return 0.f;
 }
 
-// roughness of the hit primitive, as rf_kind_k
-__device__ __forceinline__ float rf_kind_rough(const RtReflectDev &rd, const RtKindsDev &kd, int kind, int pos)
+// The continuation of hit b (0: the primary hit) at list position `hit` of `kind`, into e's origin, direction and pad_:
+// glass (g = (tau, ior) with tau > 0; s = the hit sphere) goes through rf_transmit, anything else takes the mirror
+// direction from start, which GLOSS perturbs where the hit's roughness is > 0. GLOSS passes the key on.
+template <bool GLASS, bool KINDS, bool GLOSS>
+__device__ __forceinline__ void rf_continue(const RtReflectDev &rd, const RtKindsDev &kd, int kind, int hit, float2 g, V3 D,
+                                            V3 normal, V3 start, V3 new_org, float4 s, uint32_t key, int b, QEntry &e)
 {
-    if (kind == RT_HIT_SPHERE) return rd.rough ? rd.rough[pos] : 0.f;
-    if (kind == RT_HIT_PLANE) return kd.rough_plane ? kd.rough_plane[pos] : 0.f;
-    if (kind == RT_HIT_CUBE) return kd.rough_cube ? kd.rough_cube[pos] : 0.f;
-    return 0.f;
+    if (GLASS && g.x > 0.f) {
+        V3 ro, rdir;
+        rf_transmit(D, normal, start, new_org, s, g.y, ro, rdir);
+        e.ox = ro.x; e.oy = ro.y; e.oz = ro.z;
+        e.dx = rdir.x; e.dy = rdir.y; e.dz = rdir.z;
+    } else {
+        e.ox = start.x; e.oy = start.y; e.oz = start.z;
+        rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, e.dx, e.dy, e.dz);
+        if constexpr (GLOSS) {
+            const float rho = KINDS ? rf_kind_value(rd.rough, kd.rough_plane, kd.rough_cube, kind, hit)
+                                    : (rd.rough ? rd.rough[hit] : 0.f);
+            if (rho > 0.f) {
+                V3 Rg;
+                rf_gloss(V3{e.dx, e.dy, e.dz}, normal, rho, key, (uint32_t)b, Rg);
+                e.dx = Rg.x; e.dy = Rg.y; e.dz = Rg.z;
+            }
+        }
+    }
+    if constexpr (GLOSS) e.pad_ = (int)key;
 }
 
 __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float cr, float cg, float cb)
@@ -308,7 +326,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
         float k;
         if constexpr (KINDS) {
             nt = q_nearest(fc, (AuxPtr)(uintptr_t)fc.aux, rd, O, D, stk, kind, hit);
-            k = rf_kind_k(rd, kd, kind, hit);
+            k = rf_kind_value(rd.k, kd.k_plane, kd.k_cube, kind, hit);
         } else {
             hit = rf_cast<false>(rd, O.x, O.y, O.z, D.x, D.y, D.z, nt, stk);
             k = (hit >= 0 && rd.k) ? rd.k[hit] : 0.f;
@@ -333,32 +351,16 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
             }
             const float4 L = reinterpret_cast<const float4 *>(fc.rgba)[pix];   // the frame kernel's L for this hit
             const float f = 1.f - k;                                            // (w * (1 - k)) with w = 1
-            if (GLASS && g.x > 0.f) {
-                V3 ro, rdir;
-                rf_transmit(D, normal, start, new_org, s, g.y, ro, rdir);
-                e.ox = ro.x; e.oy = ro.y; e.oz = ro.z;
-                e.dx = rdir.x; e.dy = rdir.y; e.dz = rdir.z;
-            } else {
-                e.ox = start.x; e.oy = start.y; e.oz = start.z;
-                rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, e.dx, e.dy, e.dz);
-            }
+            uint32_t key = 0u;
             if constexpr (GLOSS) {
                 // the pixel in the full frame (rows count from row 0 of the frame) and the absolute sample index
                 const int sj = SAMPLES ? pix / npx : 0;
                 const int lp = pix - sj * npx;
                 const int ly = lp / fc.width;
-                const uint32_t key = rf_gloss_key((uint32_t)(lp - ly * fc.width), (uint32_t)(fc.y0 + ly),
-                                                  (uint32_t)(SAMPLES ? fc.sample_base + sj : 0), kd.gloss_seed);
-                e.pad_ = (int)key;
-                if (!(GLASS && g.x > 0.f)) {
-                    const float rho = KINDS ? rf_kind_rough(rd, kd, kind, hit) : (rd.rough ? rd.rough[hit] : 0.f);
-                    if (rho > 0.f) {
-                        V3 Rg;
-                        rf_gloss(V3{e.dx, e.dy, e.dz}, normal, rho, key, 0u, Rg);
-                        e.dx = Rg.x; e.dy = Rg.y; e.dz = Rg.z;
-                    }
-                }
+                key = rf_gloss_key((uint32_t)(lp - ly * fc.width), (uint32_t)(fc.y0 + ly),
+                                   (uint32_t)(SAMPLES ? fc.sample_base + sj : 0), kd.gloss_seed);
             }
+            rf_continue<GLASS, KINDS, GLOSS>(rd, kd, kind, hit, g, D, normal, start, new_org, s, key, 0, e);
             e.w = k;                                                            // w * k with w = 1
             e.cr = f * L.x; e.cg = f * L.y; e.cb = f * L.z;                     // the first term is assigned
             e.pix = pix;
@@ -417,7 +419,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
                 cr = cr + e.w * sr; cg = cg + e.w * sg; cb = cb + e.w * sb;
             } else {
                 float k;
-                if constexpr (KINDS) k = rf_kind_k(rd, kd, kind, hit);
+                if constexpr (KINDS) k = rf_kind_value(rd.k, kd.k_plane, kd.k_cube, kind, hit);
                 else k = rd.k ? rd.k[hit] : 0.f;
                 float2 g = make_float2(0.f, 0.f);   // (tau, ior)
                 if (GLASS && kind == RT_HIT_SPHERE) {
@@ -429,26 +431,14 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
                 } else {
                     const float f = e.w * (1.f - k);
                     cr = cr + f * Lr; cg = cg + f * Lg; cb = cb + f * Lb;
+                    V3 new_org{0.f, 0.f, 0.f};
+                    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);   // the hit sphere (glass reads it)
                     if (GLASS && g.x > 0.f) {
                         // new_org again from O, D, nt (rf_hit_frame's operations): cheaper than keeping it across rf_shade
-                        const V3 new_org{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
-                        V3 ro, rdir;
-                        rf_transmit(D, normal, start, new_org, rd.spheres[hit], g.y, ro, rdir);
-                        nx.ox = ro.x; nx.oy = ro.y; nx.oz = ro.z;
-                        nx.dx = rdir.x; nx.dy = rdir.y; nx.dz = rdir.z;
-                    } else {
-                        nx.ox = start.x; nx.oy = start.y; nx.oz = start.z;
-                        rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, nx.dx, nx.dy, nx.dz);
-                        if constexpr (GLOSS) {
-                            const float rho = KINDS ? rf_kind_rough(rd, kd, kind, hit) : (rd.rough ? rd.rough[hit] : 0.f);
-                            if (rho > 0.f) {
-                                V3 Rg;
-                                rf_gloss(V3{nx.dx, nx.dy, nx.dz}, normal, rho, (uint32_t)e.pad_, (uint32_t)b, Rg);
-                                nx.dx = Rg.x; nx.dy = Rg.y; nx.dz = Rg.z;
-                            }
-                        }
+                        new_org = V3{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
+                        s = rd.spheres[hit];
                     }
-                    if constexpr (GLOSS) nx.pad_ = e.pad_;
+                    rf_continue<GLASS, KINDS, GLOSS>(rd, kd, kind, hit, g, D, normal, start, new_org, s, (uint32_t)e.pad_, b, nx);
                     nx.w = e.w * k;
                     nx.cr = cr; nx.cg = cg; nx.cb = cb;
                     nx.pix = e.pix;
@@ -514,36 +504,55 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_resolve(const flo
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// A per-plane or per-cube reflectivness table, or a roughness table of any kind: d_k's protocol (the device copy
-// changes only in rt_reflect_prepare)
-struct RtKTable {
-    std::vector<float> k;                 // empty = all 0
-    std::vector<float> k_dev;             // what the device copy holds
-    bool dirty = false;
-    bool pos_dev = false;                 // k_dev holds a value > 0 (the roughness tables: whether GLOSS is needed)
-    DevArray<float> d_k;
+// One per-primitive table of the passes (reflectivness or roughness of a kind, or the spheres' glass pairs): what the
+// host last set, and a device copy that changes only in upload() -- in rt_reflect_prepare, after the frames that may
+// still read it. The passes are chosen and pointed by what the device holds (v_dev, pos_dev, dev()), never by v.
+namespace {
+struct RfTable {
+    std::vector<float> v;                 // empty = all 0
+    std::vector<float> v_dev;             // what the device copy holds
+    bool dirty = false;                   // v changed since the last upload
+    bool pos_dev = false;                 // v_dev holds a value > 0 (the roughness tables: whether GLOSS is needed)
+    DevArray<float> d;
+    void set(std::vector<float> nv)       // (the drop-in boundary sets the same materials every frame: no re-upload then)
+    {
+        if (nv == v) return;
+        v.swap(nv);
+        dirty = true;
+    }
     void clear()
     {
-        if (!k.empty()) dirty = true;
-        k.clear();
+        if (!v.empty()) dirty = true;
+        v.clear();
     }
-    const float *dev() const { return k_dev.empty() ? nullptr : d_k.get(); }
+    hipError_t upload(hipStream_t stream)
+    {
+        if (!dirty) return hipSuccess;
+        v_dev = v;
+        pos_dev = std::any_of(v_dev.begin(), v_dev.end(), [](float x) { return x > 0.f; });
+        if (!v_dev.empty()) {
+            hipError_t e = d.reserve(v_dev.size());
+            if (e == hipSuccess) e = hipMemcpyAsync(d.get(), v_dev.data(), sizeof(float) * v_dev.size(), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess) return e;
+        }
+        dirty = false;
+        return hipSuccess;
+    }
+    const float *dev() const { return v_dev.empty() ? nullptr : d.get(); }
 };
+}  // namespace
+
+// The tables: reflectivness and roughness by kind (RT_HIT_SPHERE + i: sphere, plane, cube), and the spheres' glass
+enum { RF_K = 0, RF_ROUGH = 3, RF_GLASS = 6, RF_TABLES = 7 };
+static_assert(RT_HIT_PLANE == RT_HIT_SPHERE + 1 && RT_HIT_CUBE == RT_HIT_SPHERE + 2, "the tables are indexed by kind");
 
 struct RtReflect {
-    std::vector<float> k;                 // reflectivness per sphere; empty = all 0
-    std::vector<float> k_dev;             // what the device copy holds (the source of its upload: changed only after
-                                          // the frames that may still read it, in rt_reflect_prepare)
-    bool k_dirty = false;
-    DevArray<float> d_k;
-    std::vector<float> glass;             // (transperancy, ior) per sphere, interleaved; empty = no sphere has tau > 0
-    std::vector<float> glass_dev;         // what d_glass holds (as k_dev)
-    bool glass_dirty = false;
-    DevArray<float2> d_glass;
+    // tab[RF_K + i], tab[RF_ROUGH + i]: one value per primitive of kind i; the plane and cube tables are read only by
+    // frames under RT_REFLECT_SCENE. tab[RF_GLASS]: (transperancy, ior) per sphere, interleaved; empty = no sphere has
+    // tau > 0 (the device reads it as float2)
+    RfTable tab[RF_TABLES];
     int scope = RT_REFLECT_SPHERES;       // rt_scene_set_reflect_scope
     int samples = RT_REFLECT_SAMPLES_ONE; // rt_scene_set_reflect_samples
-    RtKTable plane_k, cube_k;             // read only by frames under RT_REFLECT_SCENE
-    RtKTable rough_sphere, rough_plane, rough_cube;   // rt_scene_set_roughness (the last two: as plane_k, cube_k)
     unsigned gloss_seed = 0;              // rt_scene_set_gloss_seed: a host-side value, read when a frame is launched
     RtSphereBvh bvh;                      // the sphere BVH (shared with the ray queries)
     // queues and counters
@@ -552,142 +561,16 @@ struct RtReflect {
     DevArray<float4> d_rgba;              // frame-kernel output when the caller gave no rgba
     // supersampled frames: the group's per-sample colours [G][npx] and, when there are several groups, their running sum
     DevArray<float4> d_slab, d_sum;
-    HipEvent sev[RT_REFLECT_MAX_GROUPS][RT_MAX_REFLECT_DEPTH + 4];   // per group: rt_reflect_launch_samples
     // the last frame
     int last_groups = 1;                  // runs of the passes (a supersampled frame: its groups), one counter row each
-    bool last_samples = false;            // it was a supersampled frame (timed through sev)
+    bool last_samples = false;            // it was a supersampled frame (its groups end with a resolve pass)
     int last_depth = 0;
     bool have_frame = false;
     int timing = 0;
     bool timed = false;
-    HipEvent ev[RT_MAX_REFLECT_DEPTH + 3];
+    HipEvent ev[RT_REFLECT_MAX_GROUPS][RT_MAX_REFLECT_DEPTH + 4];   // a row per group (a one-sample frame: row 0), rf_mark
     HipEvent done;                        // after the last pass of the last frame (rt_reflect_get_stats waits for it)
 };
-
-static int rf_build_rec(const std::vector<float4> &sph, std::vector<int> &idx, int lo, int hi, int node, int level,
-                        RtSphereBvh *r)
-{
-    r->depth = level > r->depth ? level : r->depth;
-    double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    double clo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, chi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    double rmax = 0.0;
-    for (int p = lo; p < hi; ++p) {
-        const float4 s = sph[idx[p]];
-        const double c[3] = {s.x, s.y, s.z};
-        const double R = std::sqrt((double)s.w);   // intersect() squares the `radius` field: its radius is sqrt(w)
-        rmax = R > rmax ? R : rmax;
-        for (int a = 0; a < 3; ++a) {
-            blo[a] = std::min(blo[a], c[a] - R);
-            bhi[a] = std::max(bhi[a], c[a] + R);
-            clo[a] = std::min(clo[a], c[a]);
-            chi[a] = std::max(chi[a], c[a]);
-        }
-    }
-    BvhNode &nd = r->nodes[node];
-    for (int a = 0; a < 3; ++a) {   // rounded outward to binary32
-        float l = (float)blo[a], h = (float)bhi[a];
-        if ((double)l > blo[a]) l = std::nextafter(l, -HUGE_VALF);
-        if ((double)h < bhi[a]) h = std::nextafter(h, HUGE_VALF);
-        nd.lo[a] = l;
-        nd.hi[a] = h;
-    }
-    float rm = (float)rmax;
-    if ((double)rm < rmax) rm = std::nextafter(rm, HUGE_VALF);
-    nd.rmax = rm;
-    if (hi - lo <= RT_BVH_LEAF) {
-        nd.first = lo;
-        nd.count = hi - lo;
-        nd.axis = 0;
-        r->leaves++;
-        return RT_OK;
-    }
-    int axis = 0;
-    for (int a = 1; a < 3; ++a)
-        if (chi[a] - clo[a] > chi[axis] - clo[axis]) axis = a;
-    const int mid = lo + (hi - lo) / 2;   // median split: depth <= ceil(log2(n / 4)) + 1
-    auto key = [&](int i) { const float4 s = sph[i]; return axis == 0 ? s.x : (axis == 1 ? s.y : s.z); };
-    std::nth_element(idx.begin() + lo, idx.begin() + mid, idx.begin() + hi, [&](int a, int b) {
-        const float ka = key(a), kb = key(b);
-        return ka < kb || (ka == kb && a < b);
-    });
-    const int child = (int)r->nodes.size();
-    r->nodes.resize(r->nodes.size() + 2);
-    BvhNode &nd2 = r->nodes[node];   // (resize may move the array)
-    nd2.first = child;
-    nd2.count = 0;
-    nd2.axis = axis;
-    int rc = rf_build_rec(sph, idx, lo, mid, child, level + 1, r);
-    if (rc != RT_OK) return rc;
-    return rf_build_rec(sph, idx, mid, hi, child + 1, level + 1, r);
-}
-
-// Host build (binary64 extents, binary32 boxes rounded outward). ok = false when a sphere is non-finite or lies
-// beyond 1e15 (the traversal's derivation assumes neither): every ray then walks the list.
-static int rf_build(RtSphereBvh *r, const float4 *sph, int n)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    r->nodes.clear();
-    r->lsph.clear();
-    r->order.clear();
-    r->depth = 0;
-    r->leaves = 0;
-    r->ok = n > 0;
-    for (int i = 0; i < n && r->ok; ++i) {
-        const float4 s = sph[i];
-        const double R = std::sqrt((double)s.w);
-        if (!(std::fabs((double)s.x) + R <= 1e15 && std::fabs((double)s.y) + R <= 1e15 && std::fabs((double)s.z) + R <= 1e15))
-            r->ok = false;   // (false for NaN / inf too)
-    }
-    if (r->ok) {
-        std::vector<float4> v(sph, sph + n);
-        std::vector<int> idx((size_t)n);
-        for (int i = 0; i < n; ++i) idx[(size_t)i] = i;
-        r->nodes.reserve((size_t)2 * n);
-        r->nodes.resize(1);
-        int rc = rf_build_rec(v, idx, 0, n, 0, 0, r);
-        if (rc != RT_OK) return rc;
-        if (r->depth + 2 > RT_BVH_STACK) {   // the stack holds at most depth + 1 entries (two pushed per inner node)
-            rt_set_error("reflections: sphere BVH depth %d exceeds the traversal stack (%d)", r->depth, RT_BVH_STACK);
-            return RT_ERR_CAPACITY;
-        }
-        r->order = idx;
-        r->lsph.resize((size_t)n);
-        for (int p = 0; p < n; ++p) r->lsph[(size_t)p] = v[(size_t)idx[(size_t)p]];
-    }
-    r->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return RT_OK;
-}
-
-bool rt_sphere_bvh_stale(const RtSphereBvh *b, unsigned long long sphere_gen, int n) { return b->gen != sphere_gen || b->n != n; }
-
-int rt_sphere_bvh_update(RtSphereBvh *b, const float4 *h_spheres, int n, unsigned long long sphere_gen, hipStream_t stream)
-{
-    if (!rt_sphere_bvh_stale(b, sphere_gen, n)) return RT_OK;
-    const int rc = rf_build(b, h_spheres, n);
-    if (rc != RT_OK) return rc;
-    if (b->ok) {
-        RT_HIP(b->d_nodes.reserve(b->nodes.size()));
-        RT_HIP(b->d_lsph.reserve((size_t)n));
-        RT_HIP(b->d_order.reserve((size_t)n));
-        RT_HIP(hipMemcpyAsync(b->d_nodes.get(), b->nodes.data(), sizeof(BvhNode) * b->nodes.size(), hipMemcpyHostToDevice, stream));
-        RT_HIP(hipMemcpyAsync(b->d_lsph.get(), b->lsph.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, stream));
-        RT_HIP(hipMemcpyAsync(b->d_order.get(), b->order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream));
-    }
-    b->gen = sphere_gen;
-    b->n = n;
-    return RT_OK;
-}
-
-static RtReflectDev rf_host_view(const RtSphereBvh *r, const float4 *sph, int n, bool use_bvh)
-{
-    RtReflectDev rd{};
-    rd.nodes = (use_bvh && r->ok) ? r->nodes.data() : nullptr;
-    rd.lsph = r->lsph.data();
-    rd.order = r->order.data();
-    rd.spheres = sph;
-    rd.n = n;
-    return rd;
-}
 
 RtReflect *rt_reflect_create() { return new RtReflect(); }
 
@@ -699,30 +582,34 @@ void rt_reflect_destroy(RtReflect *r) { delete r; }
 // rt_scene_set_spheres: a new count clears the materials (the same count keeps them)
 void rt_reflect_spheres_changed(RtReflect *r, int n_old, int n_new)
 {
-    if (n_old != n_new && !r->k.empty()) {
-        r->k.clear();
-        r->k_dirty = true;
-    }
-    if (n_old != n_new && !r->glass.empty()) {
-        r->glass.clear();
-        r->glass_dirty = true;
-    }
-    if (n_old != n_new) r->rough_sphere.clear();
+    if (n_old == n_new) return;
+    for (int t : {RF_K, RF_GLASS, RF_ROUGH}) r->tab[t].clear();
+}
+
+// rt_scene_set_planes / rt_scene_set_cubes (which = 0 / 1): a new count clears the list's materials (the same count
+// keeps them)
+void rt_reflect_kind_list_changed(RtReflect *r, int which, int n_old, int n_new)
+{
+    if (n_old == n_new) return;
+    for (int t : {RF_K, RF_ROUGH}) r->tab[t + 1 + which].clear();
+}
+
+// The setters below share their head -- NULL / 0 clears the entry's tables -- and their commit, RfTable::set; on a
+// refusal nothing has changed. Each keeps its own checks in its own order.
+template <typename M>
+static std::vector<float> rf_reflectivness(const M *m, int n)
+{
+    std::vector<float> k((size_t)n);
+    for (int i = 0; i < n; ++i) k[(size_t)i] = m[i].reflectivness;
+    return k;
 }
 
 // the old entry sets every transperancy to 0
-static void rf_clear_glass(RtReflect *r)
-{
-    if (!r->glass.empty()) r->glass_dirty = true;
-    r->glass.clear();
-}
-
 int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_spheres)
 {
     if (!m || n == 0) {
-        if (!r->k.empty()) r->k_dirty = true;
-        r->k.clear();
-        rf_clear_glass(r);
+        r->tab[RF_K].clear();
+        r->tab[RF_GLASS].clear();
         return RT_OK;
     }
     if (n != n_spheres || n < 0) {
@@ -740,22 +627,16 @@ int rt_reflect_set_materials(RtReflect *r, const rt_material *m, int n, int n_sp
             return RT_ERR_UNSUPPORTED;
         }
     }
-    std::vector<float> k((size_t)n);
-    for (int i = 0; i < n; ++i) k[(size_t)i] = m[i].reflectivness;
-    if (k != r->k) {   // (the drop-in boundary sets the same materials every frame: no re-upload then)
-        r->k.swap(k);
-        r->k_dirty = true;
-    }
-    rf_clear_glass(r);
+    r->tab[RF_K].set(rf_reflectivness(m, n));
+    r->tab[RF_GLASS].clear();
     return RT_OK;
 }
 
 int rt_reflect_set_materials_ex(RtReflect *r, const rt_material_ex *m, int n, int n_spheres)
 {
     if (!m || n == 0) {
-        if (!r->k.empty()) r->k_dirty = true;
-        r->k.clear();
-        rf_clear_glass(r);
+        r->tab[RF_K].clear();
+        r->tab[RF_GLASS].clear();
         return RT_OK;
     }
     if (n != n_spheres || n < 0) {
@@ -787,12 +668,6 @@ int rt_reflect_set_materials_ex(RtReflect *r, const rt_material_ex *m, int n, in
             return RT_ERR_UNSUPPORTED;
         }
     }
-    std::vector<float> k((size_t)n);
-    for (int i = 0; i < n; ++i) k[(size_t)i] = m[i].reflectivness;
-    if (k != r->k) {
-        r->k.swap(k);
-        r->k_dirty = true;
-    }
     std::vector<float> glass;
     if (any_glass) {
         glass.resize((size_t)2 * n);
@@ -802,10 +677,8 @@ int rt_reflect_set_materials_ex(RtReflect *r, const rt_material_ex *m, int n, in
             glass[(size_t)2 * i + 1] = tau > 0.f ? m[i].ior : 0.f;   // (ignored where tau == 0)
         }
     }
-    if (glass != r->glass) {
-        r->glass.swap(glass);
-        r->glass_dirty = true;
-    }
+    r->tab[RF_K].set(rf_reflectivness(m, n));
+    r->tab[RF_GLASS].set(std::move(glass));
     return RT_OK;
 }
 
@@ -815,7 +688,7 @@ int rt_reflect_set_kind_materials(RtReflect *r, int which, const rt_material *m,
 {
     const char *fn = which == 0 ? "rt_scene_set_plane_materials" : "rt_scene_set_cube_materials";
     const char *what = which == 0 ? "plane" : "cube";
-    RtKTable &t = which == 0 ? r->plane_k : r->cube_k;
+    RfTable &t = r->tab[RF_K + 1 + which];
     if (!m || n == 0) {
         t.clear();
         return RT_OK;
@@ -838,22 +711,8 @@ int rt_reflect_set_kind_materials(RtReflect *r, int which, const rt_material *m,
         rt_set_error("%s: %d materials for %d %ss (one per %s, or NULL / 0)", fn, n, n_list, what, what);
         return RT_ERR_INVALID;
     }
-    std::vector<float> k((size_t)n);
-    for (int i = 0; i < n; ++i) k[(size_t)i] = m[i].reflectivness;
-    if (k != t.k) {
-        t.k.swap(k);
-        t.dirty = true;
-    }
+    t.set(rf_reflectivness(m, n));
     return RT_OK;
-}
-
-// rt_scene_set_planes / rt_scene_set_cubes: a new count clears the list's materials (the same count keeps them)
-void rt_reflect_kind_list_changed(RtReflect *r, int which, int n_old, int n_new)
-{
-    if (n_old != n_new) {
-        (which == 0 ? r->plane_k : r->cube_k).clear();
-        (which == 0 ? r->rough_plane : r->rough_cube).clear();
-    }
 }
 
 // rt_scene_set_roughness: one value in [0, 1] per primitive of `kind`'s list of n_list entries, or NULL / 0 to clear
@@ -864,7 +723,7 @@ int rt_reflect_set_roughness(RtReflect *r, int kind, const float *rho, int n, in
         return RT_ERR_INVALID;
     }
     const char *what = kind == RT_HIT_SPHERE ? "sphere" : (kind == RT_HIT_PLANE ? "plane" : "cube");
-    RtKTable &t = kind == RT_HIT_SPHERE ? r->rough_sphere : (kind == RT_HIT_PLANE ? r->rough_plane : r->rough_cube);
+    RfTable &t = r->tab[RF_ROUGH + kind - RT_HIT_SPHERE];
     if (!rho || n == 0) {
         t.clear();
         return RT_OK;
@@ -879,11 +738,7 @@ int rt_reflect_set_roughness(RtReflect *r, int kind, const float *rho, int n, in
             return RT_ERR_INVALID;
         }
     }
-    std::vector<float> v(rho, rho + n);
-    if (v != t.k) {
-        t.k.swap(v);
-        t.dirty = true;
-    }
+    t.set(std::vector<float>(rho, rho + n));
     return RT_OK;
 }
 
@@ -920,8 +775,8 @@ int rt_reflect_samples(const RtReflect *r) { return r->samples; }
 bool rt_reflect_needs_upload(const RtReflect *r, unsigned long long sphere_gen, int n)
 {
     // (the plane and cube tables count under either scope: the upload is due whenever they changed)
-    return r->k_dirty || r->glass_dirty || r->plane_k.dirty || r->cube_k.dirty || r->rough_sphere.dirty ||
-           r->rough_plane.dirty || r->rough_cube.dirty || rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
+    return std::any_of(r->tab, r->tab + RF_TABLES, [](const RfTable &t) { return t.dirty; }) ||
+           rt_sphere_bvh_stale(&r->bvh, sphere_gen, n);
 }
 
 // Brings materials and BVH up to date (the caller has waited for every frame that may read them) and makes sure the
@@ -934,33 +789,7 @@ int rt_reflect_prepare(RtReflect *r, const float4 *h_spheres, int n, unsigned lo
         const int rc = rt_sphere_bvh_update(&r->bvh, h_spheres, n, sphere_gen, stream);
         if (rc != RT_OK) return rc;
     }
-    if (r->k_dirty) {
-        r->k_dev = r->k;
-        if (!r->k_dev.empty()) {
-            RT_HIP(r->d_k.reserve(r->k_dev.size()));
-            RT_HIP(hipMemcpyAsync(r->d_k.get(), r->k_dev.data(), sizeof(float) * r->k_dev.size(), hipMemcpyHostToDevice, stream));
-        }
-        r->k_dirty = false;
-    }
-    if (r->glass_dirty) {
-        r->glass_dev = r->glass;
-        if (!r->glass_dev.empty()) {
-            RT_HIP(r->d_glass.reserve(r->glass_dev.size() / 2));
-            RT_HIP(hipMemcpyAsync(r->d_glass.get(), r->glass_dev.data(), sizeof(float) * r->glass_dev.size(),
-                                  hipMemcpyHostToDevice, stream));
-        }
-        r->glass_dirty = false;
-    }
-    for (RtKTable *t : {&r->plane_k, &r->cube_k, &r->rough_sphere, &r->rough_plane, &r->rough_cube}) {
-        if (!t->dirty) continue;
-        t->k_dev = t->k;
-        t->pos_dev = std::any_of(t->k_dev.begin(), t->k_dev.end(), [](float v) { return v > 0.f; });
-        if (!t->k_dev.empty()) {
-            RT_HIP(t->d_k.reserve(t->k_dev.size()));
-            RT_HIP(hipMemcpyAsync(t->d_k.get(), t->k_dev.data(), sizeof(float) * t->k_dev.size(), hipMemcpyHostToDevice, stream));
-        }
-        t->dirty = false;
-    }
+    for (RfTable &t : r->tab) RT_HIP(t.upload(stream));
     for (DevArray<QEntry> &q : r->d_q) RT_HIP(q.reserve((size_t)npx));
     RT_HIP(r->d_cnt.reserve(RT_REFLECT_MAX_GROUPS * (RT_MAX_REFLECT_DEPTH + 1)));   // one row per group
     *rgba_scratch = nullptr;
@@ -997,12 +826,14 @@ int rt_reflect_prepare_samples(RtReflect *r, const RtSamplesPlan *plan)
     return RT_OK;
 }
 
-// timing: an event before the frame kernel (slot 0) and after every pass (slots 1 ..)
-static hipError_t rt_reflect_mark(RtReflect *r, int slot, hipStream_t stream)
+// timing, per group (a one-sample frame: group 0): an event before the frame kernel(s) (slot 0), after them (1), after
+// the primary pass (2), after bounce b (2 + b) and, a supersampled frame, after the resolve pass (depth + 3)
+static hipError_t rf_mark(RtReflect *r, int group, int slot, hipStream_t stream)
 {
     if (!r->timing) return hipSuccess;
-    const hipError_t e = r->ev[slot].create(hipEventDefault);
-    return e != hipSuccess ? e : hipEventRecord(r->ev[slot].get(), stream);
+    HipEvent &ev = r->ev[group][slot];
+    const hipError_t e = ev.create(hipEventDefault);
+    return e != hipSuccess ? e : hipEventRecord(ev.get(), stream);
 }
 
 // samples: 0 for a one-sample frame, else the samples of a supersampled one (rt_reflect_launch_samples)
@@ -1020,7 +851,7 @@ int rt_reflect_begin_frame(RtReflect *r, int depth, int samples, hipStream_t str
 // Right before the frame kernel's launch (after anything else the frame enqueues, e.g. the tile-order sort).
 int rt_reflect_mark_frame_start(RtReflect *r, hipStream_t stream)
 {
-    RT_HIP(rt_reflect_mark(r, 0, stream));
+    RT_HIP(rf_mark(r, 0, 0, stream));
     return RT_OK;
 }
 
@@ -1040,22 +871,23 @@ static RfPasses rf_passes(const RtReflect *r, const RtFrameConsts *fc, const flo
     rd.order = r->bvh.d_order.get();
     rd.spheres = d_spheres;
     rd.n = n;
-    rd.k = r->k_dev.empty() ? nullptr : r->d_k.get();
+    const RfTable *k = r->tab + RF_K, *rough = r->tab + RF_ROUGH;   // [0] sphere, [1] plane, [2] cube
+    rd.k = k[0].dev();
     rd.depth = depth;
-    rd.glass = r->glass_dev.empty() ? nullptr : r->d_glass.get();
+    rd.glass = reinterpret_cast<const float2 *>(r->tab[RF_GLASS].dev());
     p.glass = rd.glass != nullptr;   // mirror-only frames run the GLASS = false instantiations (today's code)
     // KINDS only where the scope is the scene and there is something besides spheres: every frame that rendered before
     // the scope existed runs the KINDS = false instantiations
     p.kinds = r->scope == RT_REFLECT_SCENE && (fc->n_planes > 0 || fc->n_cubes > 0 || fc->n_boxes > 0);
-    p.kd.k_plane = (p.kinds && !r->plane_k.k_dev.empty()) ? r->plane_k.d_k.get() : nullptr;
-    p.kd.k_cube = (p.kinds && !r->cube_k.k_dev.empty()) ? r->cube_k.d_k.get() : nullptr;
+    p.kd.k_plane = p.kinds ? k[1].dev() : nullptr;
+    p.kd.k_cube = p.kinds ? k[2].dev() : nullptr;
     // GLOSS only where a roughness table that this frame's scope reads holds a value > 0: every other frame runs the
     // GLOSS = false instantiations with the arguments it had before roughness existed (no table, seed 0)
-    p.gloss = r->rough_sphere.pos_dev || (p.kinds && (r->rough_plane.pos_dev || r->rough_cube.pos_dev));
+    p.gloss = rough[0].pos_dev || (p.kinds && (rough[1].pos_dev || rough[2].pos_dev));
     if (p.gloss) {
-        rd.rough = r->rough_sphere.dev();
-        p.kd.rough_plane = p.kinds ? r->rough_plane.dev() : nullptr;
-        p.kd.rough_cube = p.kinds ? r->rough_cube.dev() : nullptr;
+        rd.rough = rough[0].dev();
+        p.kd.rough_plane = p.kinds ? rough[1].dev() : nullptr;
+        p.kd.rough_cube = p.kinds ? rough[2].dev() : nullptr;
         p.kd.gloss_seed = r->gloss_seed;
     }
     return p;
@@ -1075,23 +907,24 @@ static auto rf_bounce_kernel(const RfPasses &p)
                    : (p.glass ? rt_reflect_bounce<true, false, GLOSS> : rt_reflect_bounce<false, false, GLOSS>);
 }
 
-// The primary pass over `threads` pixels (SAMPLES: pixel-samples) and the `depth` bounces, with the counter row `cnt`;
-// mark(slot) after the primary pass (2) and after bounce b (2 + b)
-template <bool SAMPLES, typename Mark>
-static int rf_run_passes(RtReflect *r, const RfPasses &p, const RtFrameConsts *fc, int threads, int depth, int *cnt,
-                         hipStream_t stream, Mark mark)
+// The primary pass over `threads` pixels (SAMPLES: pixel-samples) and the `depth` bounces of group `group`, with its
+// counter row and its row of events
+template <bool SAMPLES>
+static int rf_run_passes(RtReflect *r, const RfPasses &p, const RtFrameConsts *fc, int threads, int depth, int group,
+                         hipStream_t stream)
 {
+    int *const cnt = r->d_cnt.get() + group * (RT_MAX_REFLECT_DEPTH + 1);
     const auto primary = p.gloss ? rf_primary_kernel<SAMPLES, true>(p) : rf_primary_kernel<SAMPLES, false>(p);
     const auto bounce = p.gloss ? rf_bounce_kernel<true>(p) : rf_bounce_kernel<false>(p);
     hipLaunchKernelGGL(primary, dim3((threads + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
                        stream, *fc, p.rd, r->d_q[0].get(), cnt, p.kd);
     RT_HIP(hipGetLastError());
-    RT_HIP(mark(2));
+    RT_HIP(rf_mark(r, group, 2, stream));
     for (int b = 1; b <= depth; ++b) {
         hipLaunchKernelGGL(bounce, dim3(RT_BOUNCE_GRID), dim3(RT_REFLECT_BLOCK), 0, stream, *fc, p.rd, b,
                            r->d_q[(b - 1) & 1].get(), cnt + (b - 1), r->d_q[b & 1].get(), cnt + b, p.kd);
         RT_HIP(hipGetLastError());
-        RT_HIP(mark(2 + b));
+        RT_HIP(rf_mark(r, group, 2 + b, stream));
     }
     return RT_OK;
 }
@@ -1100,10 +933,9 @@ static int rf_run_passes(RtReflect *r, const RfPasses &p, const RtFrameConsts *f
 int rt_reflect_launch(RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute,
                       hipStream_t stream)
 {
-    RT_HIP(rt_reflect_mark(r, 1, stream));
+    RT_HIP(rf_mark(r, 0, 1, stream));
     const RfPasses p = rf_passes(r, fc, d_spheres, n, depth, brute);
-    const int rc = rf_run_passes<false>(r, p, fc, fc->width * fc->local_rows, depth, r->d_cnt.get(), stream,
-                                        [&](int slot) { return rt_reflect_mark(r, slot, stream); });
+    const int rc = rf_run_passes<false>(r, p, fc, fc->width * fc->local_rows, depth, 0, stream);
     if (rc != RT_OK) return rc;
     RT_HIP(r->done.create());
     RT_HIP(hipEventRecord(r->done.get(), stream));
@@ -1124,32 +956,26 @@ int rt_reflect_launch_samples(RtReflect *r, const RtFrameConsts *fc, const RtFra
     for (int gi = 0; gi < groups; ++gi) {
         const int k0 = out->sample_base + gi * RT_REFLECT_SAMPLE_GROUP;
         const int g = std::min(RT_REFLECT_SAMPLE_GROUP, n_samples - gi * RT_REFLECT_SAMPLE_GROUP);
-        HipEvent *ev = r->sev[gi];
-        const auto mark = [&](int slot) {
-            if (!r->timing) return hipSuccess;
-            const hipError_t e = ev[slot].create(hipEventDefault);
-            return e != hipSuccess ? e : hipEventRecord(ev[slot].get(), stream);
-        };
-        RT_HIP(mark(0));
+        RT_HIP(rf_mark(r, gi, 0, stream));
         RtFrameConsts f = *fc;
         for (int j = 0; j < g; ++j) {
             f.sample_base = k0 + j;
             f.rgba = reinterpret_cast<float *>(slab + (size_t)j * (size_t)npx);
             RT_HIP(rt_dev_launch_trace(&f, d_spheres, kc->tile, kc->cull, kc->mode, kc->feat, stream));
         }
-        RT_HIP(mark(1));
+        RT_HIP(rf_mark(r, gi, 1, stream));
         // the passes' view of the group: g samples from k0, the slab as their rgba, nothing packed
         f.spp = g;
         f.sample_base = k0;
         f.rgba = reinterpret_cast<float *>(slab);
         const RfPasses p = rf_passes(r, &f, d_spheres, n, depth, kc->cull == 0);
-        const int rc = rf_run_passes<true>(r, p, &f, g * npx, depth, r->d_cnt.get() + gi * (RT_MAX_REFLECT_DEPTH + 1), stream, mark);
+        const int rc = rf_run_passes<true>(r, p, &f, g * npx, depth, gi, stream);
         if (rc != RT_OK) return rc;
         hipLaunchKernelGGL(rt_reflect_resolve, dim3((npx + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
                            stream, slab, npx, g, r->d_sum.get(), gi == 0 ? 1 : 0, gi == groups - 1 ? 1 : 0,
                            reinterpret_cast<float4 *>(out->rgba), out->packed, out->flags, (float)n_samples, out->sample_total);
         RT_HIP(hipGetLastError());
-        RT_HIP(mark(depth + 3));
+        RT_HIP(rf_mark(r, gi, depth + 3, stream));
     }
     RT_HIP(r->done.create());
     RT_HIP(hipEventRecord(r->done.get(), stream));
@@ -1180,7 +1006,7 @@ int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out)
         for (int b = 0; b <= RT_MAX_REFLECT_DEPTH; ++b) out->queue[b] += cnt[g][b];
     if (r->timed) {
         for (int g = 0; g < r->last_groups; ++g) {
-            const HipEvent *ev = r->last_samples ? r->sev[g] : r->ev;
+            const HipEvent *ev = r->ev[g];
             for (int p = 0; p < r->last_depth + (r->last_samples ? 3 : 2); ++p) {
                 float ms = 0.f;
                 RT_HIP(hipEventElapsedTime(&ms, ev[p].get(), ev[p + 1].get()));
@@ -1195,79 +1021,6 @@ int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out)
 // ---------------------------------------------------------------------------
 // host-only debug entries (tests)
 // ---------------------------------------------------------------------------
-static void pack_list(const rt_sphere *s, int n, std::vector<float4> &v)
-{
-    v.resize((size_t)n);
-    for (int i = 0; i < n; ++i)
-        v[(size_t)i] = make_float4(s[i].orgin.x, s[i].orgin.y, s[i].orgin.z, s[i].radius * s[i].radius);
-}
-
-extern "C" int rt_debug_sphere_bvh(const rt_sphere *spheres, int n, float *lohi, int *meta, int *order, int cap,
-                                   int *n_nodes, int *depth)
-{
-    if (!spheres || n <= 0 || !lohi || !meta || !order || !n_nodes || !depth) {
-        rt_set_error("rt_debug_sphere_bvh: invalid argument");
-        return RT_ERR_INVALID;
-    }
-    std::vector<float4> v;
-    pack_list(spheres, n, v);
-    RtSphereBvh r;
-    const int rc = rf_build(&r, v.data(), n);
-    if (rc != RT_OK) return rc;
-    if (!r.ok) {
-        rt_set_error("rt_debug_sphere_bvh: the list has non-finite or huge spheres (no BVH: the list is walked)");
-        return RT_ERR_UNSUPPORTED;
-    }
-    if ((int)r.nodes.size() > cap) {
-        rt_set_error("rt_debug_sphere_bvh: %d nodes exceed cap %d", (int)r.nodes.size(), cap);
-        return RT_ERR_CAPACITY;
-    }
-    for (size_t j = 0; j < r.nodes.size(); ++j) {
-        for (int a = 0; a < 3; ++a) {
-            lohi[6 * j + a] = r.nodes[j].lo[a];
-            lohi[6 * j + 3 + a] = r.nodes[j].hi[a];
-        }
-        meta[2 * j] = r.nodes[j].first;
-        meta[2 * j + 1] = r.nodes[j].count;
-    }
-    for (int p = 0; p < n; ++p) order[p] = r.order[(size_t)p];
-    *n_nodes = (int)r.nodes.size();
-    *depth = r.depth;
-    return RT_OK;
-}
-
-extern "C" int rt_debug_bvh_cast(const rt_sphere *spheres, int n, const rt_ray *rays, int n_rays, int use_bvh,
-                                 int *hit_index, float *t, int *any)
-{
-    if (!spheres || n <= 0 || !rays || n_rays < 0) {
-        rt_set_error("rt_debug_bvh_cast: invalid argument");
-        return RT_ERR_INVALID;
-    }
-    std::vector<float4> v;
-    pack_list(spheres, n, v);
-    RtSphereBvh r;
-    int rc = RT_OK;
-    if (use_bvh) rc = rf_build(&r, v.data(), n);
-    if (rc != RT_OK) return rc;
-    const RtReflectDev rd = rf_host_view(&r, v.data(), n, use_bvh != 0);
-    int stack[RT_BVH_STACK];
-    auto stk = [&stack](int i) -> int & { return stack[i]; };
-    for (int i = 0; i < n_rays; ++i) {
-        const rt_ray &ray = rays[i];
-        if (hit_index || t) {
-            float tb;
-            const int h = rf_cast<false>(rd, ray.Org.x, ray.Org.y, ray.Org.z, ray.Dir.x, ray.Dir.y, ray.Dir.z, tb, stk);
-            if (hit_index) hit_index[i] = h;
-            if (t) t[i] = tb;
-        }
-        if (any) {
-            float ta;
-            any[i] = rf_cast<true>(rd, ray.Org.x, ray.Org.y, ray.Org.z, ray.Dir.x, ray.Dir.y, ray.Dir.z, ta, stk);
-        }
-    }
-    return RT_OK;
-}
-
 extern "C" int rt_debug_reflect(const rt_vec3 *I, const rt_vec3 *N, int n, rt_vec3 *out)
 {
     if (!I || !N || !out || n < 0) {
@@ -1325,8 +1078,7 @@ extern "C" int rt_debug_transmit(const rt_sphere *sphere, const float *ior, cons
         rt_set_error("rt_debug_transmit: invalid argument");
         return RT_ERR_INVALID;
     }
-    std::vector<float4> v;
-    pack_list(sphere, 1, v);
+    const float4 v[1] = {make_float4(sphere->orgin.x, sphere->orgin.y, sphere->orgin.z, sphere->radius * sphere->radius)};
     for (int i = 0; i < n; ++i) {
         const V3 O{rays[i].Org.x, rays[i].Org.y, rays[i].Org.z}, D{rays[i].Dir.x, rays[i].Dir.y, rays[i].Dir.z};
         out[i] = rays[i];

@@ -321,3 +321,30 @@ def test_scratch_life_cycle(rt, oracle, gpu):
     _check(a, _ref2(rt, oracle, 5), "first")
     _check(b, _ref1(rt, oracle), "second")
     assert _same(c, a) and c[2] == a[2]
+
+
+# ----------------------------------------------------------------------------- 10. timed frames
+def test_timed_frames_are_the_untimed_ones(rt, gpu):
+    """Timing on: pass_ms has depth + 2 finite entries >= 0 with a sum > 0, for a one-sample frame (one row of events, no
+    resolve slot) and for 5 samples (two groups, 4 + 1: the second row and the resolve slot), and the queue and both
+    outputs are those of the same frame with timing off, where pass_ms is None. Nothing about how long a pass takes."""
+    w, h, n, depth = 32, 16, 8, 2                    # more than one bounce, a queue that is not empty
+    sc = Inputs(rt, n).scene()
+    sc.set_materials(_k_by_index(n))
+    _many(sc)
+    for spp in (1, 5):
+        sc.set_reflect_timing(False)
+        plain = _render(sc, w, h, reflect_depth=depth, spp=spp)
+        assert sc.reflect_stats()["pass_ms"] is None, spp
+        assert plain[2][0] > 0 and len(plain[2]) == depth, (spp, plain[2])
+        sc.set_reflect_timing(True)
+        timed = _render(sc, w, h, reflect_depth=depth, spp=spp)
+        ms = sc.reflect_stats()["pass_ms"]
+        assert ms is not None and len(ms) == depth + 2, (spp, ms)
+        assert all(np.isfinite(t) and t >= 0 for t in ms), (spp, ms)
+        assert sum(ms) > 0, (spp, ms)
+        assert timed[2] == plain[2], (spp, timed[2], plain[2])
+        assert _same(timed, plain), spp
+    sc.set_reflect_timing(False)
+    _render(sc, w, h, reflect_depth=depth, spp=5)
+    assert sc.reflect_stats()["pass_ms"] is None      # off again after timed frames
