@@ -1028,6 +1028,16 @@ int rt_debug_gloss_key(const unsigned *px, const unsigned *py, const unsigned *s
                        unsigned *key);
 /* sizeof of the reflective passes' queue entry (48; its last word carries the glossy key).          */
 int rt_debug_reflect_entry_size(void);
+/* F(c, ior) of rt_scene_set_glass_model(RT_GLASS_FRESNEL), in binary32 as the kernels evaluate it.  */
+int rt_debug_fresnel(const float *c, const float *ior, int n, float *F);
+/* The glass hit of the Fresnel model for rays[i] hitting `sphere` with ior[i], rho[i], key[i], b[i]
+ * (the same code the kernels run, from sphere::intersect's hit to R_{b+1}): out[i] = R_{b+1};
+ * choice[i] = 1 rule 1 (nothing drawn), 2 reflected, 3 through the sphere (rule 4), 4 rule 3, -1 when
+ * intersect() reports no hit (out[i] = rays[i]). F, u, what may be NULL: the reflectance, the draw
+ * (both 0 where nothing was drawn) and rt_debug_gloss's `what` of the perturbation.               */
+int rt_debug_glass_choice(const rt_sphere *sphere, const float *ior, const float *rho, const unsigned *key,
+                          const int *b, const rt_ray *rays, int n, rt_ray *out, int *choice, float *F, float *u,
+                          int *what);
 int rt_debug_occluder_lists_ex(const rt_sphere *spheres, int n, const rt_light *light, int *counts, float *kcaps, int *members, int cap,
                                int *offsets, int *entries_allocated);
 
@@ -1108,7 +1118,8 @@ int rt_scene_set_cube_materials(rt_scene *s, const rt_material *per_cube, int n)
  *       fails), else R unchanged.
  * binary32, no contraction, correctly rounded division and sqrt. rho == 0 draws nothing: a scene
  * whose tables hold no value > 0 renders exactly as without them. Roughness on a glass sphere
- * (tau > 0) or on a surface with k == 0 is accepted and has no effect. The multiplicity of a glossy
+ * (tau > 0) or on a surface with k == 0 is accepted and has no effect (a glass sphere: under
+ * RT_GLASS_PLAIN; under RT_GLASS_FRESNEL, below, it frosts the glass). The multiplicity of a glossy
  * lobe comes from spp and accumulate under RT_REFLECT_SAMPLES_MANY, or from one sample per frame
  * with a new seed (or sample_base) accumulated by rt_scene_temporal. What a reflective frame
  * refuses, and rt_reflect_stats, are unchanged. */
@@ -1116,6 +1127,39 @@ int rt_scene_set_roughness(rt_scene *s, int kind, const float *rho, int n);
 /* The seed of the glossy draws (default 0, any value): a host-side value, read when a frame is
  * launched: no wait, no device needed. */
 int rt_scene_set_gloss_seed(rt_scene *s, unsigned seed);
+
+/* ------------------------------------------------------------------ *
+ * Fresnel glass.                                       *
+ * ------------------------------------------------------------------ */
+/* How a glass sphere (rt_scene_set_materials_ex, transperancy > 0) continues a ray. RT_GLASS_PLAIN
+ * (the default): always through the sphere, as described there. RT_GLASS_FRESNEL: a hit reflects
+ * with the dielectric reflectance F of its angle and index, and goes through otherwise -- one ray
+ * per hit, chosen by a hashed draw, its weight unchanged. Any other value: RT_ERR_INVALID, and
+ * nothing changes. A host-side value like the gloss seed, read when a frame is launched: no wait, no
+ * device needed; it survives rt_scene_set_spheres and rt_scene_set_materials*, and has no effect on
+ * a frame without glass or with reflect_depth 0.
+ *
+ * Semantics under RT_GLASS_FRESNEL: the per-pixel loop of rt_scene_set_materials_ex with one change.
+ * The colour term of a glass hit and its weight are as there ((w * (1 - tau)) * L, then w = w * tau);
+ * at a continuing glass hit b on sphere i, with D, N, start_O, new_org as there and mix, key, gloss
+ * of rt_scene_set_roughness:
+ *   1. dot(D, N) >= 0 (rule 1): the ray leaves undeviated from start_O; nothing is drawn.
+ *   2. c = -dot(D, N); eta = 1 / ior; q = 1 - (eta*eta) * (1 - c*c); ct = sqrt(q > 0 ? q : 0);
+ *      rs = (c - ior*ct) / (c + ior*ct); rp = (ct - ior*c) / (ct + ior*c);
+ *      F = (rs*rs + rp*rp) * 0.5f        (the unpolarised reflectance, not Schlick's approximation)
+ *   3. h = mix(mix(key ^ 0x46726573) + 0x9e3779b9 * (b + 1)); u = float(h >> 8) * 2^-24, in [0, 1)
+ *   4. u < F (a NaN F fails): R_{b+1} = ray(start_O, reflect(D, N)), its direction replaced by
+ *      gloss(R, N, rho_i, key, b) where sphere i's roughness is > 0 -- what a mirror hit would do.
+ *   5. otherwise the glass step as it is (rules 3 and 4); where the ray went through (rule 4) and
+ *      rho_i > 0, its direction U is replaced by gloss(U, M, rho_i, key, b), M the exit normal.
+ * binary32, no contraction, correctly rounded division and sqrt, dot products left to right. Under
+ * this model roughness on a glass sphere is frosted glass; under RT_GLASS_PLAIN it has no effect.
+ * Internal reflection along the chord is not modelled: a pass through the sphere is one bounce.
+ * The multiplicity of the two branches comes from spp, accumulate and rt_scene_temporal, as for
+ * glossy reflections. What a reflective frame refuses (k > 0 with tau > 0 on one sphere included)
+ * and rt_reflect_stats are unchanged. */
+enum { RT_GLASS_PLAIN = 0, RT_GLASS_FRESNEL = 1 };
+int rt_scene_set_glass_model(rt_scene *s, int model);
 
 /* ------------------------------------------------------------------ *
  * Supersampled reflective frames.                      *

@@ -157,6 +157,8 @@ _REFLECT_SCOPES = {"spheres": RT_REFLECT_SPHERES, "scene": RT_REFLECT_SCENE}
 RT_REFLECT_SAMPLES_ONE, RT_REFLECT_SAMPLES_MANY = 0, 1     # rt_scene_set_reflect_samples
 _REFLECT_SAMPLES = {"one": RT_REFLECT_SAMPLES_ONE, "many": RT_REFLECT_SAMPLES_MANY}
 _ROUGH_KINDS = {"sphere": RT_HIT_SPHERE, "plane": RT_HIT_PLANE, "cube": RT_HIT_CUBE}   # Scene.set_roughness
+RT_GLASS_PLAIN, RT_GLASS_FRESNEL = 0, 1     # rt_scene_set_glass_model
+_GLASS_MODELS = {"plain": RT_GLASS_PLAIN, "fresnel": RT_GLASS_FRESNEL}
 
 
 class Hit(C.Structure):
@@ -395,6 +397,10 @@ def load_library():
                                 C.POINTER(Vec3), C.POINTER(ci)]),
         "rt_debug_gloss_key": (ci, [C.POINTER(C.c_uint)] * 4 + [ci, C.POINTER(C.c_uint)]),
         "rt_debug_reflect_entry_size": (ci, []),
+        "rt_scene_set_glass_model": (ci, [vp, ci]),
+        "rt_debug_fresnel": (ci, [fp, fp, ci, fp]),
+        "rt_debug_glass_choice": (ci, [C.POINTER(Sphere), fp, fp, C.POINTER(C.c_uint), C.POINTER(ci), C.POINTER(Ray), ci,
+                                       C.POINTER(Ray), C.POINTER(ci), fp, fp, C.POINTER(ci)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -717,6 +723,17 @@ class Scene:
         """The seed of the glossy draws (default 0; taken modulo 2^32). One sample per frame with set_gloss_seed(frame)
         into Scene.temporal(colour=...) accumulates a glossy lobe over frames."""
         _check(self.lib.rt_scene_set_gloss_seed(self.handle, int(seed) & 0xffffffff), "rt_scene_set_gloss_seed")
+
+    def set_glass_model(self, model):
+        """How a glass sphere continues a ray: "plain" (the default: always through the sphere) or "fresnel" -- a hit
+        reflects with the dielectric reflectance of its angle and index and goes through otherwise, by a draw of the
+        pixel, the sample index and set_gloss_seed; roughness on a glass sphere then frosts it. Also
+        takes RT_GLASS_PLAIN / RT_GLASS_FRESNEL."""
+        if isinstance(model, str):
+            if model not in _GLASS_MODELS:
+                raise RtError(f"unknown glass model {model!r} (one of {tuple(_GLASS_MODELS)})")
+            model = _GLASS_MODELS[model]
+        _check(self.lib.rt_scene_set_glass_model(self.handle, int(model)), "rt_scene_set_glass_model")
 
     def set_reflect_timing(self, on: bool):
         _check(self.lib.rt_scene_set_reflect_timing(self.handle, 1 if on else 0), "rt_scene_set_reflect_timing")

@@ -190,6 +190,7 @@ int rt_reflect_set_kind_materials(RtReflect *r, int which, const rt_material *m,
 void rt_reflect_kind_list_changed(RtReflect *r, int which, int n_old, int n_new);
 int rt_reflect_set_roughness(RtReflect *r, int kind, const float *rho, int n, int n_list);   // kind: RT_HIT_SPHERE / PLANE / CUBE
 int rt_reflect_set_gloss_seed(RtReflect *r, unsigned seed);
+int rt_reflect_set_glass_model(RtReflect *r, int model);   // RT_GLASS_PLAIN / RT_GLASS_FRESNEL
 int rt_reflect_set_scope(RtReflect *r, int scope);
 int rt_reflect_scope(const RtReflect *r);
 int rt_reflect_set_samples(RtReflect *r, int mode);

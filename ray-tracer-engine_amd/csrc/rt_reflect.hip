@@ -32,6 +32,11 @@
 // pass forms the pixel-sample's key and the queue entry carries it. The host launches GLOSS = true only when a
 // roughness table the frame reads holds a value > 0: every other frame runs today's code.
 //
+// Fresnel glass (rt_scene_set_glass_model(RT_GLASS_FRESNEL)) is a template parameter of its own, FRESNEL: a
+// glass hit is reflected with probability rf_fresnel and transmitted otherwise, by one more draw of the same key, and
+// roughness on a glass sphere perturbs whichever ray it takes (rf_fresnel_continue). The host launches FRESNEL = true
+// (with GLASS and GLOSS, for the key) only under that model in a frame with glass: every other frame runs today's code.
+//
 // The BVH and the per-ray pieces the ray queries share are in rt_bvh.h, the BVH's host build and its debug entries in
 // rt_sphere_bvh.cpp, the all-kinds casts in rt_cast.h.
 #include "rt_cast.h"
@@ -163,12 +168,13 @@ __host__ __device__ __forceinline__ float rf_far_root(V3 P, V3 T, float4 s)
 // The glass continuation of a hit on sphere s (DESIGN.md "Refraction"): D = the ray's direction, normal / start /
 // new_org = the hit frame (rf_hit_frame). Writes R_{b+1} and returns 1 when the ray passed through the sphere (rule 4),
 // 0 when it leaves undeviated from start_O (rule 1: dot(D, N) >= 0; rule 3: no positive far root from inside).
-// The chord is not tested against other spheres.
+// The chord is not tested against other spheres. M: the exit normal of rule 4 (else the hit's normal).
 __host__ __device__ __forceinline__ int rf_transmit(V3 D, V3 normal, V3 start, V3 new_org, float4 s, float ior, V3 &ro,
-                                                    V3 &rd)
+                                                    V3 &rd, V3 &M)
 {
     ro = start;
     rd = D;
+    M = normal;
     if ((D.x * normal.x + D.y * normal.y) + D.z * normal.z >= 0.f) return 0;   // rule 1
     V3 T;
     rf_refract(D.x, D.y, D.z, normal.x, normal.y, normal.z, 1.f / ior, T.x, T.y, T.z);
@@ -176,11 +182,84 @@ __host__ __device__ __forceinline__ int rf_transmit(V3 D, V3 normal, V3 start, V
     const float t1 = rf_far_root(P, T, s);
     if (!(t1 > 0.f)) return 0;                                                   // rule 3 (NaN included)
     const V3 Q{P.x + T.x * t1, P.y + T.y * t1, P.z + T.z * t1};
-    V3 M{Q.x - s.x, Q.y - s.y, Q.z - s.z};
+    M = V3{Q.x - s.x, Q.y - s.y, Q.z - s.z};
     rf_normalise(M);
     rf_refract(T.x, T.y, T.z, -M.x, -M.y, -M.z, ior, rd.x, rd.y, rd.z);
     ro = V3{M.x * 0.00001f + Q.x, M.y * 0.00001f + Q.y, M.z * 0.00001f + Q.z};
     return 1;
+}
+
+__host__ __device__ __forceinline__ int rf_transmit(V3 D, V3 normal, V3 start, V3 new_org, float4 s, float ior, V3 &ro,
+                                                    V3 &rd)
+{
+    V3 M;
+    return rf_transmit(D, normal, start, new_org, s, ior, ro, rd, M);
+}
+
+// Fresnel glass (rt_scene_set_glass_model(RT_GLASS_FRESNEL)): the unpolarised reflectance of a dielectric
+// of index ior at cosine c = -dot(D, N) of the incidence angle. The radicand is rf_refract's (eta = 1 / ior), clamped alike.
+__host__ __device__ __forceinline__ float rf_fresnel(float c, float ior)
+{
+    const float eta = 1.f / ior;
+    const float q = 1.f - (eta * eta) * (1.f - c * c);
+    const float ct = __builtin_sqrtf(q > 0.f ? q : 0.f);
+    const float rs = (c - ior * ct) / (c + ior * ct);
+    const float rp = (ct - ior * c) / (ct + ior * c);
+    return (rs * rs + rp * rp) * 0.5f;
+}
+
+// The draw of hit b under `key` that a Fresnel glass hit compares with its reflectance: 24 bits as an exact value of
+// [0, 1). The inner mix with a constant keeps the stream apart from rf_gloss_draw's of the same key and b.
+__host__ __device__ __forceinline__ float rf_fresnel_draw(uint32_t key, uint32_t b)
+{
+    const uint32_t h = rf_mix(rf_mix(key ^ 0x46726573u) + 0x9e3779b9u * (b + 1u));
+    return (float)(h >> 8) * 5.9604644775390625e-08f;   // 2^-24
+}
+
+// What rf_fresnel_continue did: a mirror hit; a glass hit that left by rule 1 (nothing drawn), was reflected (u < F),
+// went through the sphere (rule 4) or left by rule 3
+enum { RF_MIRROR = 0, RF_RULE1 = 1, RF_REFLECTED = 2, RF_THROUGH = 3, RF_RULE3 = 4 };
+
+// The continuation of hit b under the Fresnel model, of a mirror (glass = false) or of glass of index ior on sphere s:
+// a glass hit with dot(D, N) < 0 is reflected with probability F = rf_fresnel and transmitted (rf_transmit) otherwise,
+// by the draw u (a NaN F transmits). The mirror ray -- a mirror's or a reflected glass hit's -- is perturbed by rf_gloss
+// against N where rho > 0, and so is the exit direction of a ray that went through, against the exit normal M. The
+// branches are exclusive: one rf_gloss serves them all. F, u: 0 where nothing was drawn; what: rf_gloss's result.
+__host__ __device__ __forceinline__ int rf_fresnel_continue(bool glass, V3 D, V3 normal, V3 start, V3 new_org, float4 s,
+                                                            float ior, float rho, uint32_t key, uint32_t b, V3 &ro, V3 &rd,
+                                                            float &F, float &u, int &what)
+{
+    int choice = RF_MIRROR;
+    bool mirror = !glass;
+    V3 gn = normal;   // the normal rf_gloss keeps the perturbed ray on the side of
+    F = u = 0.f;
+    ro = start;
+    rd = D;
+    if (glass) {
+        const float dn = (D.x * normal.x + D.y * normal.y) + D.z * normal.z;
+        if (dn >= 0.f) {                                                         // rule 1, as rf_transmit
+            choice = RF_RULE1;
+            rho = 0.f;
+        } else {
+            F = rf_fresnel(-dn, ior);
+            u = rf_fresnel_draw(key, b);
+            if (u < F) {
+                choice = RF_REFLECTED;
+                mirror = true;
+            } else {
+                choice = rf_transmit(D, normal, start, new_org, s, ior, ro, rd, gn) ? RF_THROUGH : RF_RULE3;
+                if (choice == RF_RULE3) rho = 0.f;
+            }
+        }
+    }
+    if (mirror) rf_reflect(D.x, D.y, D.z, normal.x, normal.y, normal.z, rd.x, rd.y, rd.z);
+    what = 0;
+    if (rho > 0.f) {
+        V3 G;
+        what = rf_gloss(rd, gn, rho, key, b, G);
+        rd = G;
+    }
+    return choice;
 }
 
 // ---------------------------------------------------------------------------
@@ -262,10 +341,24 @@ __device__ __forceinline__ float rf_kind_value(const float *sphere, const float 
 // The continuation of hit b (0: the primary hit) at list position `hit` of `kind`, into e's origin, direction and pad_:
 // glass (g = (tau, ior) with tau > 0; s = the hit sphere) goes through rf_transmit, anything else takes the mirror
 // direction from start, which GLOSS perturbs where the hit's roughness is > 0. GLOSS passes the key on.
-template <bool GLASS, bool KINDS, bool GLOSS>
+// FRESNEL (with GLASS and GLOSS): every continuation is rf_fresnel_continue's.
+template <bool GLASS, bool KINDS, bool GLOSS, bool FRESNEL>
 __device__ __forceinline__ void rf_continue(const RtReflectDev &rd, const RtKindsDev &kd, int kind, int hit, float2 g, V3 D,
                                             V3 normal, V3 start, V3 new_org, float4 s, uint32_t key, int b, QEntry &e)
 {
+    static_assert(!FRESNEL || (GLASS && GLOSS), "the Fresnel model needs glass and the key");
+    if constexpr (FRESNEL) {
+        const float rho = KINDS ? rf_kind_value(rd.rough, kd.rough_plane, kd.rough_cube, kind, hit)
+                                : (rd.rough ? rd.rough[hit] : 0.f);
+        V3 ro, rdir;
+        float F, u;
+        int what;
+        rf_fresnel_continue(g.x > 0.f, D, normal, start, new_org, s, g.y, rho, key, (uint32_t)b, ro, rdir, F, u, what);
+        e.ox = ro.x; e.oy = ro.y; e.oz = ro.z;
+        e.dx = rdir.x; e.dy = rdir.y; e.dz = rdir.z;
+        e.pad_ = (int)key;
+        return;
+    }
     if (GLASS && g.x > 0.f) {
         V3 ro, rdir;
         rf_transmit(D, normal, start, new_org, s, g.y, ro, rdir);
@@ -301,7 +394,9 @@ __device__ __forceinline__ void rf_write(const RtFrameConsts &fc, int pix, float
 // has left that sample's L at [i], and the queue entry's pix is i.
 // GLOSS: some roughness table the frame reads holds a value > 0. Every queued entry carries the key of its
 // pixel-sample, and the mirror continuation of a hit whose roughness is > 0 is rf_gloss's (hit 0 here, hit b in bounce b).
-template <bool GLASS, bool KINDS, bool SAMPLES, bool GLOSS>
+// FRESNEL: the glass model is RT_GLASS_FRESNEL and the frame has glass; a glass hit draws between the
+// mirror ray and rf_transmit's, so the passes need the key: FRESNEL comes with GLASS and GLOSS only.
+template <bool GLASS, bool KINDS, bool SAMPLES, bool GLOSS, bool FRESNEL>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtFrameConsts fc, const RtReflectDev rd,
                                                                        QEntry *q, int *count, const RtKindsDev kd)
 {
@@ -360,7 +455,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
                 key = rf_gloss_key((uint32_t)(lp - ly * fc.width), (uint32_t)(fc.y0 + ly),
                                    (uint32_t)(SAMPLES ? fc.sample_base + sj : 0), kd.gloss_seed);
             }
-            rf_continue<GLASS, KINDS, GLOSS>(rd, kd, kind, hit, g, D, normal, start, new_org, s, key, 0, e);
+            rf_continue<GLASS, KINDS, GLOSS, FRESNEL>(rd, kd, kind, hit, g, D, normal, start, new_org, s, key, 0, e);
             e.w = k;                                                            // w * k with w = 1
             e.cr = f * L.x; e.cg = f * L.y; e.cb = f * L.z;                     // the first term is assigned
             e.pix = pix;
@@ -371,7 +466,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_primary(const RtF
 }
 
 // Bounce b (1..depth): a fixed grid walks the queue of the previous pass; its length is read here, on the device.
-template <bool GLASS, bool KINDS, bool GLOSS>
+template <bool GLASS, bool KINDS, bool GLOSS, bool FRESNEL>
 __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFrameConsts fc, const RtReflectDev rd, int b,
                                                                       const QEntry *qin, const int *count_in, QEntry *qout,
                                                                       int *count_out, const RtKindsDev kd)
@@ -438,7 +533,7 @@ __global__ __launch_bounds__(RT_REFLECT_BLOCK) void rt_reflect_bounce(const RtFr
                         new_org = V3{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
                         s = rd.spheres[hit];
                     }
-                    rf_continue<GLASS, KINDS, GLOSS>(rd, kd, kind, hit, g, D, normal, start, new_org, s, (uint32_t)e.pad_, b, nx);
+                    rf_continue<GLASS, KINDS, GLOSS, FRESNEL>(rd, kd, kind, hit, g, D, normal, start, new_org, s, (uint32_t)e.pad_, b, nx);
                     nx.w = e.w * k;
                     nx.cr = cr; nx.cg = cg; nx.cb = cb;
                     nx.pix = e.pix;
@@ -554,6 +649,7 @@ struct RtReflect {
     int scope = RT_REFLECT_SPHERES;       // rt_scene_set_reflect_scope
     int samples = RT_REFLECT_SAMPLES_ONE; // rt_scene_set_reflect_samples
     unsigned gloss_seed = 0;              // rt_scene_set_gloss_seed: a host-side value, read when a frame is launched
+    int glass_model = RT_GLASS_PLAIN;     // rt_scene_set_glass_model: likewise
     RtSphereBvh bvh;                      // the sphere BVH (shared with the ray queries)
     // queues and counters
     DevArray<QEntry> d_q[2];
@@ -748,6 +844,16 @@ int rt_reflect_set_gloss_seed(RtReflect *r, unsigned seed)
     return RT_OK;
 }
 
+int rt_reflect_set_glass_model(RtReflect *r, int model)
+{
+    if (model != RT_GLASS_PLAIN && model != RT_GLASS_FRESNEL) {
+        rt_set_error("rt_scene_set_glass_model: model %d is not RT_GLASS_PLAIN or RT_GLASS_FRESNEL", model);
+        return RT_ERR_INVALID;
+    }
+    r->glass_model = model;
+    return RT_OK;
+}
+
 int rt_reflect_set_scope(RtReflect *r, int scope)
 {
     if (scope != RT_REFLECT_SPHERES && scope != RT_REFLECT_SCENE) {
@@ -859,7 +965,7 @@ int rt_reflect_mark_frame_start(RtReflect *r, hipStream_t stream)
 struct RfPasses {
     RtReflectDev rd;
     RtKindsDev kd;
-    bool glass, kinds, gloss;
+    bool glass, kinds, gloss, fresnel;
 };
 
 static RfPasses rf_passes(const RtReflect *r, const RtFrameConsts *fc, const float4 *d_spheres, int n, int depth, bool brute)
@@ -884,6 +990,10 @@ static RfPasses rf_passes(const RtReflect *r, const RtFrameConsts *fc, const flo
     // GLOSS only where a roughness table that this frame's scope reads holds a value > 0: every other frame runs the
     // GLOSS = false instantiations with the arguments it had before roughness existed (no table, seed 0)
     p.gloss = rough[0].pos_dev || (p.kinds && (rough[1].pos_dev || rough[2].pos_dev));
+    // FRESNEL only under that model in a frame with glass; its draw needs the key, so it takes GLOSS along, with or
+    // without a roughness table
+    p.fresnel = p.glass && r->glass_model == RT_GLASS_FRESNEL;
+    p.gloss = p.gloss || p.fresnel;
     if (p.gloss) {
         rd.rough = rough[0].dev();
         p.kd.rough_plane = p.kinds ? rough[1].dev() : nullptr;
@@ -893,18 +1003,23 @@ static RfPasses rf_passes(const RtReflect *r, const RtFrameConsts *fc, const flo
     return p;
 }
 
-// The instantiations of the two passes for a frame's (glass, kinds), at compile-time SAMPLES and GLOSS
+// The instantiations of the two passes for a frame's (glass, kinds, fresnel), at compile-time SAMPLES and GLOSS
 template <bool SAMPLES, bool GLOSS>
 static auto rf_primary_kernel(const RfPasses &p)
 {
-    return p.kinds ? (p.glass ? rt_reflect_primary<true, true, SAMPLES, GLOSS> : rt_reflect_primary<false, true, SAMPLES, GLOSS>)
-                   : (p.glass ? rt_reflect_primary<true, false, SAMPLES, GLOSS> : rt_reflect_primary<false, false, SAMPLES, GLOSS>);
+    if constexpr (GLOSS)   // (FRESNEL comes with GLASS and GLOSS only)
+        if (p.fresnel)
+            return p.kinds ? rt_reflect_primary<true, true, SAMPLES, true, true> : rt_reflect_primary<true, false, SAMPLES, true, true>;
+    return p.kinds ? (p.glass ? rt_reflect_primary<true, true, SAMPLES, GLOSS, false> : rt_reflect_primary<false, true, SAMPLES, GLOSS, false>)
+                   : (p.glass ? rt_reflect_primary<true, false, SAMPLES, GLOSS, false> : rt_reflect_primary<false, false, SAMPLES, GLOSS, false>);
 }
 template <bool GLOSS>
 static auto rf_bounce_kernel(const RfPasses &p)
 {
-    return p.kinds ? (p.glass ? rt_reflect_bounce<true, true, GLOSS> : rt_reflect_bounce<false, true, GLOSS>)
-                   : (p.glass ? rt_reflect_bounce<true, false, GLOSS> : rt_reflect_bounce<false, false, GLOSS>);
+    if constexpr (GLOSS)
+        if (p.fresnel) return p.kinds ? rt_reflect_bounce<true, true, true, true> : rt_reflect_bounce<true, false, true, true>;
+    return p.kinds ? (p.glass ? rt_reflect_bounce<true, true, GLOSS, false> : rt_reflect_bounce<false, true, GLOSS, false>)
+                   : (p.glass ? rt_reflect_bounce<true, false, GLOSS, false> : rt_reflect_bounce<false, false, GLOSS, false>);
 }
 
 // The primary pass over `threads` pixels (SAMPLES: pixel-samples) and the `depth` bounces of group `group`, with its
@@ -1092,6 +1207,47 @@ extern "C" int rt_debug_transmit(const rt_sphere *sphere, const float *ior, cons
         entered[i] = rf_transmit(D, normal, start, new_org, v[0], ior[i], ro, rd);
         out[i].Org.x = ro.x; out[i].Org.y = ro.y; out[i].Org.z = ro.z;
         out[i].Dir.x = rd.x; out[i].Dir.y = rd.y; out[i].Dir.z = rd.z;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_fresnel(const float *c, const float *ior, int n, float *F)
+{
+    if (!c || !ior || !F || n < 0) {
+        rt_set_error("rt_debug_fresnel: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) F[i] = rf_fresnel(c[i], ior[i]);
+    return RT_OK;
+}
+
+extern "C" int rt_debug_glass_choice(const rt_sphere *sphere, const float *ior, const float *rho, const unsigned *key,
+                                     const int *b, const rt_ray *rays, int n, rt_ray *out, int *choice, float *F, float *u,
+                                     int *what)
+{
+    if (!sphere || !ior || !rho || !key || !b || !rays || !out || !choice || n < 0) {
+        rt_set_error("rt_debug_glass_choice: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    const float4 v[1] = {make_float4(sphere->orgin.x, sphere->orgin.y, sphere->orgin.z, sphere->radius * sphere->radius)};
+    for (int i = 0; i < n; ++i) {
+        const V3 O{rays[i].Org.x, rays[i].Org.y, rays[i].Org.z}, D{rays[i].Dir.x, rays[i].Dir.y, rays[i].Dir.z};
+        out[i] = rays[i];
+        float t, Fi = 0.f, ui = 0.f;
+        int wi = 0;
+        if (!rf_intersect(O.x, O.y, O.z, D.x, D.y, D.z, v[0], t)) {
+            choice[i] = -1;
+        } else {
+            V3 normal, start, new_org, ro, rd;
+            rf_hit_frame(O, D, t, v[0], normal, start, new_org);
+            choice[i] = rf_fresnel_continue(true, D, normal, start, new_org, v[0], ior[i], rho[i], key[i], (uint32_t)b[i], ro,
+                                            rd, Fi, ui, wi);
+            out[i].Org.x = ro.x; out[i].Org.y = ro.y; out[i].Org.z = ro.z;
+            out[i].Dir.x = rd.x; out[i].Dir.y = rd.y; out[i].Dir.z = rd.z;
+        }
+        if (F) F[i] = Fi;
+        if (u) u[i] = ui;
+        if (what) what[i] = wi;
     }
     return RT_OK;
 }

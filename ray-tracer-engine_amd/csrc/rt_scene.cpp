@@ -422,6 +422,16 @@ extern "C" int rt_scene_set_gloss_seed(rt_scene *s, unsigned seed)
     return rt_reflect_set_gloss_seed(rt_scene_reflect(s), seed);
 }
 
+// How glass continues a ray: a host-side value, read when a frame is launched
+extern "C" int rt_scene_set_glass_model(rt_scene *s, int model)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_glass_model: null scene");
+        return RT_ERR_INVALID;
+    }
+    return rt_reflect_set_glass_model(rt_scene_reflect(s), model);
+}
+
 extern "C" int rt_scene_set_reflect_timing(rt_scene *s, int on)
 {
     if (!s) {

@@ -8,7 +8,12 @@ shader clock read while frames are in flight. With --ab-root DIR (a checkout of 
 the mirror configuration is also timed alternately in fresh processes of that tree and of this one, --ab-rounds times
 each, so that the two libraries see the same machine state. Prints one JSON line (and writes it to --out).
 
-  python3 tools/bench_refract.py [--iters 20] [--depth 3] [--ab-root DIR --ab-rounds 5] [--out file.json]
+--fresnel: Fresnel glass (rt_scene_set_glass_model) instead: the glass configuration under the plain model,
+under the Fresnel model, and under the Fresnel model with roughness 0.1 on the glass spheres -- ms per frame, the time
+of every pass and the queue lengths of each. With --ab-root the configuration timed alternately is then the glass one
+under the plain model (rt_scene_set_materials_ex and render_raw only: what the other tree has as well).
+
+  python3 tools/bench_refract.py [--iters 20] [--depth 3] [--fresnel] [--ab-root DIR --ab-rounds 5] [--out file.json]
 """
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,16 +48,19 @@ def time_frames(torch, settle, scene, fd, iters):
     return e0.elapsed_time(e1) / iters
 
 
-def mirror_child(root, iters, depth):
+def mirror_child(root, iters, depth, kind="mirror"):
     """Time the mirror configuration with the package of `root` (only set_materials and render_raw: the API every
-    commit since reflections has). Prints {"ms": ...}."""
+    commit since reflections has), or (--fresnel) the glass one (set_materials_ex). Prints {"ms": ...}."""
     sys.path[:0] = [root, os.path.join(ROOT, "tools")]
     import torch
     import rt_amd
     from _settle import settle
     rt = rt_amd.load()
     scene = rt.Scene.default(N)
-    scene.set_materials(materials("mirror")[0])
+    if kind == "mirror":
+        scene.set_materials(materials("mirror")[0])
+    else:
+        scene.set_materials_ex(*materials(kind))
     rgba = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
     pk = torch.empty((H, W), dtype=torch.int32, device="cuda")
     fd = scene.frame_desc(W, H, pixels=pk.data_ptr(), rgba=rgba.data_ptr(), reflect_depth=depth)
@@ -63,13 +71,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--depth", type=int, default=3)
+    ap.add_argument("--fresnel", action="store_true", help="the glass configuration under the Fresnel model (see above)")
     ap.add_argument("--ab-root", default="")
     ap.add_argument("--ab-rounds", type=int, default=5)
     ap.add_argument("--out", default="")
     ap.add_argument("--mirror-child", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.mirror_child:
-        mirror_child(a.mirror_child, a.iters, a.depth)
+        mirror_child(a.mirror_child, a.iters, a.depth, "glass" if a.fresnel else "mirror")
         return
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
     import torch
@@ -86,12 +95,19 @@ def main():
     fd = scene.frame_desc(W, H, pixels=pk.data_ptr(), rgba=rgba.data_ptr(), reflect_depth=a.depth)
     fdb = scene.frame_desc(W, H, pixels=pk.data_ptr(), rgba=rgba.data_ptr(), reflect_depth=a.depth, cull=False)
     names = ["frame_kernel", "primary"] + [f"bounce{b}" for b in range(1, a.depth + 1)]
-    for kind in ("glass", "mirror", "mix"):
+    # (--fresnel: the glass configuration three times over -- model, roughness on the glass spheres)
+    cases = ([("glass_plain", "glass", "plain", 0.0), ("glass_fresnel", "glass", "fresnel", 0.0),
+              ("glass_fresnel_rough0.1", "glass", "fresnel", 0.1)] if a.fresnel
+             else [(kind, kind, None, 0.0) for kind in ("glass", "mirror", "mix")])
+    for name, kind, model, rho in cases:
         k, tau, ior = materials(kind)
         if kind == "mirror":
             scene.set_materials(k)
         else:
             scene.set_materials_ex(k, tau, ior)
+        if model is not None:
+            scene.set_glass_model(model)
+            scene.set_roughness("sphere", [rho if t > 0 else 0.0 for t in tau] if rho > 0 else None)
         r = {"ms": time_frames(torch, settle, scene, fd, a.iters)}
         # the clock under this workload: read while a window of frames is in flight
         for _ in range(5):
@@ -106,7 +122,7 @@ def main():
         scene.set_reflect_timing(False)
         r["pass_ms"] = dict(zip(names, stats["pass_ms"] or []))
         r["queue_per_bounce"] = stats["queue"]
-        out[kind] = r
+        out[name] = r
     out["clocks_end"] = read_clocks()
     if a.ab_root:
         del scene, rgba, pk
@@ -117,7 +133,7 @@ def main():
                 env = dict(os.environ)
                 env.pop("RT_ENGINE_LIB", None)
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mirror-child", root, "--iters",
-                                    str(a.iters), "--depth", str(a.depth)], capture_output=True, text=True, env=env,
+                                    str(a.iters), "--depth", str(a.depth)] + (["--fresnel"] if a.fresnel else []), capture_output=True, text=True, env=env,
                                    timeout=600)
                 if p.returncode != 0:
                     raise SystemExit(f"mirror child for {root} failed ({p.returncode}): {p.stderr[-2000:]}")
@@ -127,7 +143,7 @@ def main():
             ab[key.replace("_ms", "_median_ms")] = v[len(v) // 2]
             ab[key.replace("_ms", "_spread_ms")] = v[-1] - v[0]
         ab["this_over_parent"] = ab["this_median_ms"] / ab["parent_median_ms"]
-        out["mirror_ab"] = ab
+        out["glass_plain_ab" if a.fresnel else "mirror_ab"] = ab
     line = json.dumps(out)
     print(line)
     if a.out:
