@@ -1199,6 +1199,83 @@ int rt_scene_set_glass_model(rt_scene *s, int model);
 enum { RT_REFLECT_SAMPLES_ONE = 0, RT_REFLECT_SAMPLES_MANY = 1 };
 int rt_scene_set_reflect_samples(rt_scene *s, int mode);
 
+/* ------------------------------------------------------------------ *
+ * One-bounce global illumination: a hashed diffuse     *
+ * gather pass over a frame's G-buffer.                                *
+ * ------------------------------------------------------------------ */
+#define RT_INDIRECT_MAX_RAYS 16
+typedef struct rt_indirect_desc {
+    uint32_t struct_size;     /* sizeof(rt_indirect_desc); 0 reads as this layout; fields past a caller's size read as 0 */
+    int width, height;        /* whole frames, rows of `width` pixels (as rt_temporal_desc)                             */
+    float aspect;             /* the view the guides were rendered with (rt_frame_desc.aspect / cam)                    */
+    rt_camera cam;
+    const float *depth;       /* device, the four guides in the rt_frame_desc.aov_* layouts and alignments              */
+    const float *normal;
+    const int   *id;
+    const float *albedo;      /* NULL: the factor is 1 (the output is the irradiance term itself)                       */
+    const float *rgba_in;     /* NULL, or device, float4, 16-byte aligned: the colour the indirect term is added to     */
+    float *rgba_out;          /* device, float4, 16-byte aligned; may equal rgba_in, overlaps nothing else              */
+    uint32_t *pixels;         /* NULL, or device: the packed word of rgba_out's colour, rgbToInt(c * 254)               */
+    int rays;                 /* 1 .. RT_INDIRECT_MAX_RAYS: gather rays per pixel                               [1]     */
+    int ray_base;             /* >= 0, ray_base + rays <= 1 << 24: index of the call's first ray                [0]     */
+    uint32_t seed;            /*                                                                                [0]     */
+    float strength;           /* finite, >= 0: factor on the indirect term                                      [1]     */
+    int cull;                 /* -1 or 1: the sphere BVH; 0: the whole lists; the same bits                     [-1]    */
+    int variant;              /* 0: the product kernels; 1: the plain one-thread-per-pixel yardstick; the same bits [0] */
+} rt_indirect_desc;
+
+/* The defaults in brackets above; sizes, view and pointers 0. */
+void rt_indirect_desc_init(rt_indirect_desc *d);
+
+/* Adds every surface pixel's one-bounce indirect diffuse light to a colour, on `stream` (a hipStream_t; NULL = the
+ * null stream). p = y * width + x; all arithmetic binary32, no contraction, correctly rounded division and sqrt, dot
+ * products left to right; mix, key as rt_scene_set_roughness defines them:
+ *   1. A pixel is dead if id[p].kind < 0, depth[p] is not finite, or nn = (n.x*n.x + n.y*n.y) + n.z*n.z of the normal
+ *      guide is 0 or not finite. A dead pixel casts nothing; its rgba_out is rgba_in[p]'s bits ((0, 0, 0, 1) without
+ *      rgba_in) and its packed word the pack of that colour.
+ *   2. O = the origin of the view's primary rays, D = the pixel's primary direction as rt_scene_primary_rays forms it,
+ *      P = O + D * depth per component (a negative depth -- a sphere seen from inside -- as it is), n = normalise(normal
+ *      guide), negated if dot(n, D) > 0, start = n * 0.00001f + P.
+ *   3. For j = 0 .. rays - 1: key = key(x, y, ray_base + j, seed); kg = mix(key ^ 0x47497261);
+ *      draw(t, a) = float(mix(kg + 0x9e3779b9 * (t*2 + a + 1)) >> 8) * 2^-23 - 1. For t = 0 .. 5: x1 = draw(t, 0),
+ *      x2 = draw(t, 1), s = x1*x1 + x2*x2; the first t with s < 1 gives r = sqrt(1 - s) and the point of the unit sphere
+ *      u = ((2*x1)*r, (2*x2)*r, 1 - 2*s) (Marsaglia); no such t: u = 0. G = normalise(n + u), or n unless
+ *      dot(G, n) > 0. c_j = the colour RT_QUERY_SHADE gives ray(start, G): direct light at what it hits, getFColor on
+ *      a miss.
+ *   4. S = 0.f; S = S + c_j in ascending j; E = S / (float)rays.
+ *   5. I = strength * E, then I = I * albedo.rgb where albedo is given.
+ *   6. rgba_out = (rgba_in.rgb + I, rgba_in.a), or (I, 1) without rgba_in; pixels = rgbToInt(f2i(c * 254) ...) of it.
+ * normalise(n + point of the unit sphere) is cosine-distributed about n, and the light model carries no 1 / pi: the
+ * Lambert estimator under that density is albedo x radiance, unweighted. Distinct (ray_base + j) are distinct samples:
+ * a caller accumulates over frames with ray_base = the frame number (rt_scene_temporal), or filters the term
+ * (rt_scene_denoise); at 4K the intended use is the pass at half resolution and rt_scene_upsample (README).
+ * One bounce; the guides are the primary hit's, so what a mirror or glass shows gets the light of the mirror's own
+ * surface point (a caller scales by 1 - k through the id guide); no importance sampling; whole frames only.
+ * Host behaviour is rt_scene_trace_rays': ordered after pending uploads, counted as a frame in flight, a host wait
+ * only when the shared sphere BVH must be rebuilt, the scratch grows (variant 0: 256 bytes per pixel, plus 16 with
+ * more than 4 rays; it belongs to the scene) or a view of another size or aspect needs its ray tables. Calls of one
+ * scene on different streams are ordered on the device by an event; ordering the call after the frame that wrote its
+ * inputs is the caller's. Before anything is enqueued, and with nothing written: NULL or misaligned required pointers,
+ * sizes <= 0 or above RT_DENOISE_MAX_SIZE, an aspect that is not finite and > 0, rays, ray_base, cull or variant out
+ * of range, a strength that is not finite and >= 0, an output that overlaps an input other than rgba_out == rgba_in,
+ * a scene without sky, or with primitives and no texture -> RT_ERR_INVALID; a frame whose pixels times 4 rays exceed
+ * the queue's index range -> RT_ERR_CAPACITY; a stream that is being captured -> RT_ERR_UNSUPPORTED. */
+int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d, void *stream);
+
+/* Device time of every launch of the scene's later indirect calls (hipEvents around each; off by default).
+ * rt_scene_indirect_times waits for the last call and fills ms[0 .. *n - 1]: variant 1: [0] the kernel; variant 0: per
+ * group of at most 4 rays [3g] the cast pass, [3g + 1] the shade pass, [3g + 2] the resolve pass. cap: room in ms. */
+int rt_scene_set_indirect_timing(rt_scene *s, int on);
+int rt_scene_indirect_times(rt_scene *s, float *ms, int cap, int *n);
+
+/* The gather direction of step 3 (the same code the kernels run, no GPU needed; tests only) for `count` pairs
+ * (n[i], key[i]), n as step 2 leaves it: G[i]; tries[i] (may be NULL) = the pairs drawn until one qualified, 1 .. 6,
+ * or 0 when none did (u = 0). */
+int rt_debug_indirect_dir(const rt_vec3 *n, const unsigned *key, int count, rt_vec3 *G, int *tries);
+/* The queue lengths of the scene's last variant-0 indirect call, one per group of rays (waits for the call; tests and
+ * tools): counts[0 .. *n - 1], the gather rays that hit something. cap: room in counts. */
+int rt_debug_indirect_counts(rt_scene *s, int *counts, int cap, int *n);
+
 #ifdef __cplusplus
 }
 #endif

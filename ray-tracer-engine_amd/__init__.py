@@ -233,6 +233,19 @@ class UpsampleDesc(C.Structure):
                 ("demodulate", C.c_int), ("variant", C.c_int)]
 
 
+class IndirectDesc(C.Structure):
+    """rt_indirect_desc."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
+                ("aspect", C.c_float), ("cam", Camera),
+                ("depth", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p), ("albedo", C.c_void_p),
+                ("rgba_in", C.c_void_p), ("rgba_out", C.c_void_p), ("pixels", C.c_void_p),
+                ("rays", C.c_int), ("ray_base", C.c_int), ("seed", C.c_uint32), ("strength", C.c_float),
+                ("cull", C.c_int), ("variant", C.c_int)]
+
+
+RT_INDIRECT_MAX_RAYS = 16
+
+
 class ViewListsInfo(C.Structure):
     """rt_view_lists_info."""
     _fields_ = [("read", C.c_int), ("block_w", C.c_int), ("block_h", C.c_int), ("blocks_x", C.c_int), ("blocks_y", C.c_int),
@@ -401,6 +414,12 @@ def load_library():
         "rt_debug_fresnel": (ci, [fp, fp, ci, fp]),
         "rt_debug_glass_choice": (ci, [C.POINTER(Sphere), fp, fp, C.POINTER(C.c_uint), C.POINTER(ci), C.POINTER(Ray), ci,
                                        C.POINTER(Ray), C.POINTER(ci), fp, fp, C.POINTER(ci)]),
+        "rt_indirect_desc_init": (None, [C.POINTER(IndirectDesc)]),
+        "rt_scene_indirect": (ci, [vp, C.POINTER(IndirectDesc), vp]),
+        "rt_scene_set_indirect_timing": (ci, [vp, ci]),
+        "rt_scene_indirect_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
+        "rt_debug_indirect_dir": (ci, [C.POINTER(Vec3), C.POINTER(C.c_uint), ci, C.POINTER(Vec3), C.POINTER(ci)]),
+        "rt_debug_indirect_counts": (ci, [vp, C.POINTER(ci), ci, C.POINTER(ci)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -1370,3 +1389,74 @@ class Scene:
         """Device ms of every launch of the last timed denoise call (waits for it): variants 0 and 2: the pack pass, then
         the iterations; variant 1: the iterations."""
         return self._pass_times("denoise", RT_DENOISE_MAX_ITERATIONS + 1)
+
+    # ---------------------------------------------------------------- one-bounce global illumination (DESIGN.md 6o)
+    def indirect_desc(self, width, height, *, cam=None, aspect=None, depth=0, normal=0, id=0, albedo=0, rgba_in=0,
+                      rgba_out=0, pixels=0, rays=None, ray_base=None, seed=None, strength=None, cull=None,
+                      variant=0) -> IndirectDesc:
+        """rt_indirect_desc with rt_indirect_desc_init's defaults where an argument is None (cam / aspect: the default
+        view)."""
+        return self._desc(IndirectDesc, "rt_indirect_desc_init",
+                          dict(width=width, height=height, aspect=default_aspect() if aspect is None else aspect,
+                               cam=_copy_camera(cam if cam is not None else default_camera()), depth=depth, normal=normal,
+                               id=id, albedo=albedo, rgba_in=rgba_in, rgba_out=rgba_out, pixels=pixels),
+                          dict(rays=rays, ray_base=ray_base, seed=seed, strength=strength, cull=cull, variant=variant))
+
+    def indirect_raw(self, d: IndirectDesc, stream=0) -> int:
+        """rt_scene_indirect as is: returns the status."""
+        return self.lib.rt_scene_indirect(self.handle, C.byref(d), stream)
+
+    def indirect(self, frame, *, cam=None, aspect=None, colour="frame", rays=None, ray_base=None, seed=None,
+                 strength=None, modulate=True, cull=True, variant=0, want_packed=False, stream=None):
+        """Add one-bounce indirect diffuse light to a frame that render(..., aov=("depth", "normal", "id", "albedo"))
+        returned with camera `cam` and `aspect`: per surface pixel `rays` hashed cosine-distributed gather rays (ray
+        indices ray_base .. ray_base + rays - 1 under `seed`), each shaded as trace_rays(..., "shade") shades it, their
+        mean times `strength` and -- with `modulate` -- the pixel's albedo. `colour`: "frame" adds the term to
+        frame["rgba"], None returns the term alone, or a CUDA float32 tensor of the guides' shape to add it to.
+        modulate=False needs no albedo. None: the default of rt_indirect_desc_init. Returns {'rgba': float32
+        [rows, W, 4], and with want_packed 'packed': int32 [rows, W]} as new tensors; no input is written. Enqueued on
+        `stream` (default: the current stream)."""
+        torch = self._need_gpu("the indirect pass")
+        need = ("depth", "normal", "id") + (("albedo",) if modulate else ())
+        aov = frame.get("aov") or {}
+        if any(k not in aov for k in need):
+            raise RtError(f"indirect needs the G-buffer outputs {need}: render with aov={AOV_NAMES}")
+        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
+        if isinstance(colour, str):
+            if colour != "frame":
+                raise RtError('indirect: colour is "frame", None or a tensor')
+            colour = frame.get("rgba")
+            if colour is None:
+                raise RtError('indirect: colour="frame" needs the frame\'s rgba (render with want_rgba=True)')
+        if colour is not None:
+            colour = self._cuda_colour(torch, "indirect", colour, rows, width)
+        like = aov["depth"]
+        out = torch.empty((rows, width, 4), dtype=torch.float32, device=like.device)
+        packed = self._new(torch, want_packed, like, (rows, width), torch.int32)
+        st = self._stream(torch, stream)
+        d = self.indirect_desc(width, rows, cam=cam, aspect=aspect, depth=aov["depth"].data_ptr(),
+                               normal=aov["normal"].data_ptr(), id=aov["id"].data_ptr(),
+                               albedo=aov["albedo"].data_ptr() if modulate else 0, rgba_in=self._ptr(colour),
+                               rgba_out=out.data_ptr(), pixels=self._ptr(packed), rays=rays, ray_base=ray_base, seed=seed,
+                               strength=strength, cull=1 if cull else 0, variant=variant)
+        _check(self.indirect_raw(d, st.cuda_stream), "rt_scene_indirect")
+        res = {"rgba": out}
+        if want_packed:
+            res["packed"] = packed
+        return res
+
+    def set_indirect_timing(self, on: bool):
+        self._set_pass_timing("indirect", on)
+
+    def indirect_times(self):
+        """Device ms of every launch of the last timed indirect call (waits for it): variant 1: the kernel; variant 0:
+        per group of at most 4 rays the cast, shade and resolve passes."""
+        return self._pass_times("indirect", 3 * ((RT_INDIRECT_MAX_RAYS + 3) // 4))
+
+    def indirect_counts(self):
+        """The queue lengths of the last variant-0 indirect call (waits for it), one per group of rays: the gather rays
+        that hit something."""
+        cnt = (C.c_int * 4)()
+        n = C.c_int()
+        _check(self.lib.rt_debug_indirect_counts(self.handle, cnt, 4, C.byref(n)), "rt_debug_indirect_counts")
+        return list(cnt)[: n.value]

@@ -76,6 +76,24 @@ __host__ __device__ __forceinline__ bool rf_ray_ok(float ox, float oy, float oz,
            A >= 0.9 && A <= 1.1;   // false for a NaN anywhere
 }
 
+// The integer mixer of every hashed draw (glossy reflections; the indirect pass, 6o): uint32 throughout
+// (wrapping)
+__host__ __device__ __forceinline__ uint32_t rf_mix(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// The key of pixel (px, py) of the full frame at absolute sample s under the scene's seed
+__host__ __device__ __forceinline__ uint32_t rf_gloss_key(uint32_t px, uint32_t py, uint32_t s, uint32_t seed)
+{
+    return rf_mix(rf_mix(rf_mix(rf_mix(seed) ^ s) ^ py) ^ px);
+}
+
 struct RayD {
     double o[3], inv[3];
     float d[3];

@@ -254,3 +254,20 @@ int rt_temporal_launch(const rt_tmotion_desc *d, const float *dx_tab, const floa
 
 // rt_upsample.hip: guided upsampling (d: validated, in this build's layout; ev: null, or two timing events)
 int rt_upsample_launch(const rt_upsample_desc *d, hipEvent_t *ev, hipStream_t stream);
+
+// rt_indirect.hip: the indirect pass. The product's scratch, all the scene's: per slot of a group of at
+// most RT_INDIRECT_GROUP rays a colour (slab) and a queue entry of RT_INDIRECT_ENTRY_F4 float4, a running sum per pixel
+// when there are several groups, and a counter per group.
+#define RT_INDIRECT_GROUP 4
+#define RT_INDIRECT_MAX_GROUPS ((RT_INDIRECT_MAX_RAYS + RT_INDIRECT_GROUP - 1) / RT_INDIRECT_GROUP)
+#define RT_INDIRECT_ENTRY_F4 3
+#define RT_INDIRECT_MAX_EVENTS (1 + 3 * RT_INDIRECT_MAX_GROUPS)
+struct RtIndirectScratch {
+    float4 *slab, *queue, *sum;
+    int *count;
+};
+bool rt_indirect_wavefront(int variant);   // whether `variant` runs the wavefront passes (and needs the scratch)
+// d: validated, in this build's layout; fc: the view's uniforms (whole frame, one sample, the pass's own ray tables);
+// bvh: null or current; ev: null, or RT_INDIRECT_MAX_EVENTS timing events, of which *n_ev are recorded
+int rt_indirect_launch(const rt_indirect_desc *d, const RtFrameConsts *fc, const RtSphereBvh *bvh, const float4 *d_spheres,
+                       int n_spheres, const RtIndirectScratch *scratch, hipEvent_t *ev, int *n_ev, hipStream_t stream);

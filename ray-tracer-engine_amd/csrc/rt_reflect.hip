@@ -77,23 +77,7 @@ __host__ __device__ __forceinline__ void rf_reflect(float ix, float iy, float iz
     rz = iz - (nz * d) * 2.f;
 }
 
-// Glossy reflection: the integer mixer of the draws, uint32 throughout (wrapping)
-__host__ __device__ __forceinline__ uint32_t rf_mix(uint32_t x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// The key of pixel (px, py) of the full frame at absolute sample s under the scene's seed
-__host__ __device__ __forceinline__ uint32_t rf_gloss_key(uint32_t px, uint32_t py, uint32_t s, uint32_t seed)
-{
-    return rf_mix(rf_mix(rf_mix(rf_mix(seed) ^ s) ^ py) ^ px);
-}
-
+// Glossy reflection: the integer mixer of the draws and the key are rf_mix and rf_gloss_key of rt_bvh.h.
 // Component a of draw t for hit b under `key`: 24 bits of the mixed counter as an exact value of [-1, 1)
 __host__ __device__ __forceinline__ float rf_gloss_draw(uint32_t key, uint32_t b, uint32_t t, uint32_t a)
 {

@@ -1031,3 +1031,164 @@ extern "C" int rt_scene_upsample_times(rt_scene *s, float *ms, int cap, int *n)
 {
     return pass_times(s, "rt_scene_upsample_times", &rt_scene::up_done, s ? s->up_ev : nullptr, s ? s->up_timed : 0, ms, cap, n);
 }
+
+// ---------------------------------------------------------------------------
+// one-bounce global illumination (rt_indirect.hip)
+// ---------------------------------------------------------------------------
+extern "C" void rt_indirect_desc_init(rt_indirect_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->rays = 1;
+    d->strength = 1.f;
+    d->cull = -1;
+}
+
+extern "C" int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_indirect: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_indirect_desc d;
+    as_built(d_in, &d);
+    const char *bad = nullptr;
+    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
+        bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
+    else if (!(d.aspect > 0.f) || !std::isfinite(d.aspect)) bad = "aspect is not finite and > 0";
+    else if (!d.depth || !d.normal || !d.id || !d.rgba_out) bad = "depth, normal, id and rgba_out must not be NULL";
+    else if ((((uintptr_t)d.normal | (uintptr_t)d.albedo | (uintptr_t)d.rgba_in | (uintptr_t)d.rgba_out) & 15u) ||
+             ((uintptr_t)d.id & 7u) || (((uintptr_t)d.depth | (uintptr_t)d.pixels) & 3u))
+        bad = "normal, albedo, rgba_in and rgba_out must be 16-byte aligned, id 8-byte, depth and pixels 4-byte";
+    else if (d.rays < 1 || d.rays > RT_INDIRECT_MAX_RAYS) bad = "rays is not in [1, RT_INDIRECT_MAX_RAYS]";
+    else if (d.ray_base < 0 || d.ray_base > (1 << 24) - d.rays) bad = "ray_base is negative, or ray_base + rays exceeds 1 << 24";
+    else if (!(d.strength >= 0.f) || !std::isfinite(d.strength)) bad = "strength is not finite and >= 0";
+    else if (d.cull < -1 || d.cull > 1) bad = "cull is not -1, 0 or 1";
+    else if (d.variant < 0 || d.variant > 1) bad = "variant is not 0 or 1";
+    else {
+        const size_t npx = (size_t)d.width * d.height;
+        const Range outs[2] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.pixels, npx * 4}};
+        const Range ins[5] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.depth, npx * 4}, {(uintptr_t)d.normal, npx * 16},
+                              {(uintptr_t)d.id, npx * 8}, {(uintptr_t)d.albedo, npx * 16}};
+        bad = overlap_message(outs, ins, 0, "an output buffer overlaps an input (only rgba_out may be rgba_in itself)");
+    }
+    if (!bad) {   // SHADE's own conditions
+        if (!s->have_sky) bad = "the scene has no sky";
+        else if ((s->n_spheres > 0 || s->n_planes > 0 || s->n_cubes > 0 || s->n_boxes > 0) && (!s->d_tex[0].get() || s->tex_w <= 0))
+            bad = "the scene has primitives but no texture";
+    }
+    if (bad) {
+        rt_set_error("rt_scene_indirect: %s (%d x %d)", bad, d.width, d.height);
+        return RT_ERR_INVALID;
+    }
+    const bool wavefront = rt_indirect_wavefront(d.variant);
+    const size_t npx = (size_t)d.width * d.height;
+    const size_t slots = (size_t)std::min(d.rays, RT_INDIRECT_GROUP) * npx;   // of the largest group
+    if (wavefront && slots > (size_t)0x7fffffff - (size_t)2048 * 256) {
+        rt_set_error("rt_scene_indirect: %d rays of %d x %d pixels per pass exceed the queue's index range",
+                     std::min(d.rays, RT_INDIRECT_GROUP), d.width, d.height);
+        return RT_ERR_CAPACITY;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_indirect: the stream is being captured (the pass is not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    RT_HIP(s->stage_done.order(stream));
+    int rc = rt_scene_sync_aux(s);
+    if (rc != RT_OK) return rc;
+    const RtSphereBvh *bvh = nullptr;
+    if (d.cull != 0 && s->n_spheres > 0) {   // the shared BVH, as rt_scene_trace_rays handles it
+        RtSphereBvh *b = rt_reflect_bvh(rt_scene_reflect(s));
+        if (rt_sphere_bvh_stale(b, s->sphere_gen, s->n_spheres)) {
+            rc = rt_scene_quiesce(s);
+            if (rc != RT_OK) return rc;
+            rc = rt_sphere_bvh_update(b, s->h_prev.data(), s->n_spheres, s->sphere_gen, stream);
+            if (rc != RT_OK) return rc;
+        }
+        rc = rt_scene_wait_all_frames(s, stream);
+        if (rc != RT_OK) return rc;
+        bvh = b;
+    }
+    // the view's ray tables at one sample: the pass's own, so that a call at another size than the frames' (half
+    // resolution) does not rebuild theirs. Another size or aspect: after the host has seen the last call end
+    if (!(s->ind_raygen.get() && s->ind_w == d.width && s->ind_h == d.height && memcmp(&s->ind_aspect, &d.aspect, sizeof d.aspect) == 0)) {
+        RT_HIP(s->ind_done.host_wait());
+        const size_t need = (size_t)d.width + (size_t)d.height;
+        s->ind_w = s->ind_h = 0;
+        RT_HIP(s->ind_raygen.reserve(need));
+        std::vector<float> h(need);
+        rt_raygen_fill(d.width, d.height, d.aspect, 1, h.data());
+        RT_HIP(hipMemcpy(s->ind_raygen.get(), h.data(), sizeof(float) * need, hipMemcpyHostToDevice));
+        s->ind_w = d.width; s->ind_h = d.height; s->ind_aspect = d.aspect;
+    }
+    const int groups = (d.rays + RT_INDIRECT_GROUP - 1) / RT_INDIRECT_GROUP;
+    if (wavefront) {
+        const size_t sum_px = groups > 1 ? npx : 0;
+        if (slots > s->ind_slab.capacity() || slots * RT_INDIRECT_ENTRY_F4 > s->ind_queue.capacity() || sum_px > s->ind_sum.capacity() ||
+            (size_t)RT_INDIRECT_MAX_GROUPS > s->ind_count.capacity()) {
+            // growing releases the old buffers: after the host has seen the last call that used them end
+            RT_HIP(s->ind_done.host_wait());
+            RT_HIP(s->ind_slab.reserve(slots));
+            RT_HIP(s->ind_queue.reserve(slots * RT_INDIRECT_ENTRY_F4));
+            RT_HIP(s->ind_sum.reserve(sum_px));
+            RT_HIP(s->ind_count.reserve(RT_INDIRECT_MAX_GROUPS));
+        }
+    }
+    rt_frame_desc fd;
+    memset(&fd, 0, sizeof fd);
+    fd.struct_size = (uint32_t)sizeof fd;
+    fd.opts.struct_size = (uint32_t)sizeof fd.opts;
+    fd.width = d.width; fd.height = d.height;
+    fd.aspect = d.aspect;
+    fd.cam = d.cam;
+    fd.pixels = reinterpret_cast<uint32_t *>(d.rgba_out);   // (rt_build_frame_consts wants an output; the kernels read none of fc's)
+    RtFrameConsts fc;
+    rc = rt_build_frame_consts(s, &fd, nullptr, &fc);
+    if (rc != RT_OK) return rc;
+    fc.dx_tab = s->ind_raygen.get();
+    fc.dy_tab = s->ind_raygen.get() + d.width;
+    fc.packed = nullptr;
+    RT_HIP(s->ind_done.order(stream));   // one scratch: one call at a time
+    hipEvent_t ev[RT_INDIRECT_MAX_EVENTS];
+    s->ind_timed = 0;
+    if (s->ind_timing) {
+        for (int i = 0; i < RT_INDIRECT_MAX_EVENTS; ++i) {
+            RT_HIP(s->ind_ev[i].create(hipEventDefault));
+            ev[i] = s->ind_ev[i].get();
+        }
+    }
+    const RtIndirectScratch scratch{s->ind_slab.get(), s->ind_queue.get(), s->ind_sum.get(), s->ind_count.get()};
+    int n_ev = 0;
+    rc = rt_indirect_launch(&d, &fc, bvh, s->d_spheres.get(), s->n_spheres, &scratch, s->ind_timing ? ev : nullptr, &n_ev, stream);
+    // also after a launch that failed half way: what was enqueued uses the scratch
+    RT_HIP(s->ind_done.record(stream));
+    if (rc != RT_OK) return rc;
+    if (s->ind_timing) s->ind_timed = n_ev;
+    s->ind_groups = wavefront ? groups : 0;
+    return rt_scene_note_launch(s, stream, nullptr, nullptr);   // the pass in flight counts as a frame
+}
+
+extern "C" int rt_scene_set_indirect_timing(rt_scene *s, int on)
+{
+    return pass_set_timing(s, "rt_scene_set_indirect_timing", &rt_scene::ind_timing, on);
+}
+
+extern "C" int rt_scene_indirect_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    return pass_times(s, "rt_scene_indirect_times", &rt_scene::ind_done, s ? s->ind_ev : nullptr, s ? s->ind_timed : 0, ms, cap, n);
+}
+
+extern "C" int rt_debug_indirect_counts(rt_scene *s, int *counts, int cap, int *n)
+{
+    if (!s || !counts || !n || cap < 0) {
+        rt_set_error("rt_debug_indirect_counts: null argument");
+        return RT_ERR_INVALID;
+    }
+    *n = std::min(cap, s->ind_groups);
+    if (*n == 0) return RT_OK;
+    RT_HIP(s->ind_done.host_wait());
+    RT_HIP(hipMemcpy(counts, s->ind_count.get(), sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost));
+    return RT_OK;
+}

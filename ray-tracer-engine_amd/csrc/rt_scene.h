@@ -19,7 +19,8 @@
 //       build has finished;
 //   (c) a reader waits on the build event on the device only; the host never waits for a build, except in
 //       rt_scene_view_lists_info;
-//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's, the temporal pass's and the upsampler's events;
+//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's, the temporal pass's, the upsampler's
+//       and the indirect pass's events;
 //   (e) the tile order keeps one event for all layouts; a new layout or a re-sort first makes the launching stream
 //       wait for every ring event;
 //   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
@@ -188,6 +189,18 @@ struct rt_scene {
     HipEvent up_ev[2];                               // rt_scene_set_upsample_timing
     bool up_timing = false;
     int up_timed = 0;
+    // the indirect pass (rt_indirect.hip): ray tables of its own, as the temporal pass has, and the product's scratch,
+    // grown on demand; `ind_done` orders the scene's indirect calls
+    DevArray<float> ind_raygen;                      // dx[width], dy[height] at one sample
+    int ind_w = 0, ind_h = 0;
+    float ind_aspect = 0.f;
+    DevArray<float4> ind_slab, ind_queue, ind_sum;
+    DevArray<int> ind_count;
+    int ind_groups = 0;                              // groups of the last variant-0 call (rt_debug_indirect_counts)
+    HipPendingEvent ind_done;
+    HipEvent ind_ev[RT_INDIRECT_MAX_EVENTS];         // rt_scene_set_indirect_timing
+    bool ind_timing = false;
+    int ind_timed = 0;
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
 #endif
