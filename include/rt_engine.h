@@ -1276,6 +1276,57 @@ int rt_debug_indirect_dir(const rt_vec3 *n, const unsigned *key, int count, rt_v
  * tools): counts[0 .. *n - 1], the gather rays that hit something. cap: room in counts. */
 int rt_debug_indirect_counts(rt_scene *s, int *counts, int cap, int *n);
 
+/* ------------------------------------------------------------------ *
+ * Multi-bounce global illumination: diffuse paths in   *
+ * the gather pass.                                                    *
+ * ------------------------------------------------------------------ */
+#define RT_INDIRECT_MAX_BOUNCES 4
+typedef struct rt_indirect_paths_opts {
+    uint32_t struct_size;   /* sizeof; 0 reads as this layout; fields past a caller's size read as their defaults */
+    int bounces;            /* 1 .. RT_INDIRECT_MAX_BOUNCES: surface hits a gather path may shade            [2] */
+} rt_indirect_paths_opts;
+
+/* The defaults in brackets above. */
+void rt_indirect_paths_opts_init(rt_indirect_paths_opts *o);
+
+/* rt_scene_indirect whose gather rays are diffuse paths of at most `bounces` shaded surface hits. `d` is
+ * rt_scene_indirect's description, every field with its meaning, checks and error texts; o == NULL: the defaults.
+ * Steps 1, 2, 4, 5 and 6 of rt_scene_indirect hold unchanged and so does the arithmetic; only c_j of step 3 changes.
+ * For gather ray j of a live pixel (x, y), with B = bounces:
+ *   O_0 = start, D_0 = G as step 3 forms them, key_0 = key(x, y, ray_base + j, seed). For b = 0 .. B - 1:
+ *   (a) the nearest hit of ray(O_b, D_b) as RT_QUERY_NEAREST finds it;
+ *   (b) a miss: term = getFColor(O_b, D_b); the path ends after (d);
+ *   (c) a hit: h_b = castRay's record, term = what RT_QUERY_SHADE gives the hit: direct light times the hit's texel;
+ *   (d) b == 0: L = 0.f + term per channel (what rt_scene_indirect stores); b >= 1: L = L + T_b * term;
+ *   (e) b == B - 1: the path ends;
+ *   (f) a_b = the texel (c) read for h_b (the same index expression and clamp); T_1 = a_0, T_{b+1} = T_b * a_b per
+ *       channel;
+ *   (g) n = h_b.normal, nn = (n.x*n.x + n.y*n.y) + n.z*n.z; nn 0 or not finite: the path ends (the dead rule of
+ *       step 1). n = normalise(n), negated if dot(n, D_b) > 0; P = O_b + D_b * t_b per component (the record's own hit
+ *       point, not new_org; a negative t as it is); O_{b+1} = n * 0.00001f + P; key_{b+1} = mix(key_b ^ 0x426f756e);
+ *       D_{b+1} = step 3's direction for n under key_{b+1}.
+ *   c_j = L.
+ * Every continuation draw has the cosine density about n and the model carries no 1 / pi, so a bounce weighs the texel
+ * alone, as step 5 does. Mirrors and glass met by a gather ray count as diffuse surfaces with their texel, as SHADE
+ * treats them. No Russian roulette: a path ends by a miss, a dead normal or the budget only.
+ * bounces == 1 issues exactly the launches of rt_scene_indirect and gives its bits. Both entries share one host path:
+ * the same ordering, the same refusals (under this entry's name), one scratch. Variant 0 with bounces > 1 takes 576
+ * bytes of scratch per pixel (per slot of a group of 4 rays a 16-byte colour and two queue entries of 64 bytes: origin,
+ * direction, hit, slot, throughput and key), 16 more per pixel with more than 4 rays, and 64 bytes of counters.
+ * bounces out of range -> RT_ERR_INVALID, naming the field, with nothing written. */
+int rt_scene_indirect_paths(rt_scene *s, const rt_indirect_desc *d, const rt_indirect_paths_opts *o, void *stream);
+
+/* rt_scene_set_indirect_timing / rt_scene_indirect_times serve this entry too. With bounces > 1: variant 1: [0] the
+ * kernel; variant 0: per group of at most 4 rays the cast pass, `bounces` shade-and-continue passes and the resolve
+ * pass, (2 + bounces) intervals a group. */
+
+/* The queue lengths of the scene's last variant-0 rt_scene_indirect_paths call with bounces > 1 (waits for the call;
+ * tests and tools): counts[group * bounces + b] = the entries that entered bounce b's shade pass. *n = groups *
+ * bounces, at most cap; 0 after any other indirect call (and rt_debug_indirect_counts gives 0 after such a call). */
+int rt_debug_indirect_path_counts(rt_scene *s, int *counts, int cap, int *n);
+/* key_b of (g) for `count` keys key_0 (the same code the kernels run, no GPU needed; tests only): out[i]. b >= 0. */
+int rt_debug_indirect_path_key(const unsigned *key, int count, int b, unsigned *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,14 @@ class IndirectDesc(C.Structure):
 RT_INDIRECT_MAX_RAYS = 16
 
 
+class IndirectPathsOpts(C.Structure):
+    """rt_indirect_paths_opts."""
+    _fields_ = [("struct_size", C.c_uint32), ("bounces", C.c_int)]
+
+
+RT_INDIRECT_MAX_BOUNCES = 4
+
+
 class ViewListsInfo(C.Structure):
     """rt_view_lists_info."""
     _fields_ = [("read", C.c_int), ("block_w", C.c_int), ("block_h", C.c_int), ("blocks_x", C.c_int), ("blocks_y", C.c_int),
@@ -420,6 +428,10 @@ def load_library():
         "rt_scene_indirect_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
         "rt_debug_indirect_dir": (ci, [C.POINTER(Vec3), C.POINTER(C.c_uint), ci, C.POINTER(Vec3), C.POINTER(ci)]),
         "rt_debug_indirect_counts": (ci, [vp, C.POINTER(ci), ci, C.POINTER(ci)]),
+        "rt_indirect_paths_opts_init": (None, [C.POINTER(IndirectPathsOpts)]),
+        "rt_scene_indirect_paths": (ci, [vp, C.POINTER(IndirectDesc), C.POINTER(IndirectPathsOpts), vp]),
+        "rt_debug_indirect_path_counts": (ci, [vp, C.POINTER(ci), ci, C.POINTER(ci)]),
+        "rt_debug_indirect_path_key": (ci, [C.POINTER(C.c_uint), ci, ci, C.POINTER(C.c_uint)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -1460,3 +1472,66 @@ class Scene:
         n = C.c_int()
         _check(self.lib.rt_debug_indirect_counts(self.handle, cnt, 4, C.byref(n)), "rt_debug_indirect_counts")
         return list(cnt)[: n.value]
+
+    # ---------------------------------------------------------------- multi-bounce global illumination
+    def indirect_paths_opts(self, bounces=None) -> IndirectPathsOpts:
+        """rt_indirect_paths_opts with rt_indirect_paths_opts_init's default where `bounces` is None."""
+        return self._desc(IndirectPathsOpts, "rt_indirect_paths_opts_init", {}, dict(bounces=bounces))
+
+    def indirect_paths_raw(self, d: IndirectDesc, o: IndirectPathsOpts = None, stream=0) -> int:
+        """rt_scene_indirect_paths as is (o None: NULL, the defaults): returns the status."""
+        self._paths_bounces = o.bounces if o is not None else self.indirect_paths_opts().bounces   # for indirect_path_counts
+        return self.lib.rt_scene_indirect_paths(self.handle, C.byref(d), C.byref(o) if o is not None else None, stream)
+
+    def indirect_paths(self, frame, *, bounces=None, cam=None, aspect=None, colour="frame", rays=None, ray_base=None,
+                       seed=None, strength=None, modulate=True, cull=True, variant=0, want_packed=False, stream=None):
+        """Scene.indirect whose gather rays are diffuse paths of at most `bounces` shaded surface hits (1 ..
+        RT_INDIRECT_MAX_BOUNCES; None: the default of rt_indirect_paths_opts_init, 2): a hit lit directly spawns the
+        next cosine-distributed ray with the hit's texel as its weight. Every other keyword as indirect's, the same
+        dict returned; bounces=1 is indirect itself, launch for launch."""
+        torch = self._need_gpu("the indirect pass")
+        need = ("depth", "normal", "id") + (("albedo",) if modulate else ())
+        aov = frame.get("aov") or {}
+        if any(k not in aov for k in need):
+            raise RtError(f"indirect_paths needs the G-buffer outputs {need}: render with aov={AOV_NAMES}")
+        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
+        if isinstance(colour, str):
+            if colour != "frame":
+                raise RtError('indirect_paths: colour is "frame", None or a tensor')
+            colour = frame.get("rgba")
+            if colour is None:
+                raise RtError('indirect_paths: colour="frame" needs the frame\'s rgba (render with want_rgba=True)')
+        if colour is not None:
+            colour = self._cuda_colour(torch, "indirect_paths", colour, rows, width)
+        like = aov["depth"]
+        out = torch.empty((rows, width, 4), dtype=torch.float32, device=like.device)
+        packed = self._new(torch, want_packed, like, (rows, width), torch.int32)
+        st = self._stream(torch, stream)
+        d = self.indirect_desc(width, rows, cam=cam, aspect=aspect, depth=aov["depth"].data_ptr(),
+                               normal=aov["normal"].data_ptr(), id=aov["id"].data_ptr(),
+                               albedo=aov["albedo"].data_ptr() if modulate else 0, rgba_in=self._ptr(colour),
+                               rgba_out=out.data_ptr(), pixels=self._ptr(packed), rays=rays, ray_base=ray_base, seed=seed,
+                               strength=strength, cull=1 if cull else 0, variant=variant)
+        _check(self.indirect_paths_raw(d, self.indirect_paths_opts(bounces), st.cuda_stream), "rt_scene_indirect_paths")
+        res = {"rgba": out}
+        if want_packed:
+            res["packed"] = packed
+        return res
+
+    def indirect_path_counts(self):
+        """The queue lengths of the last variant-0 indirect_paths call with bounces > 1 (waits for it): per group of
+        rays a list with, per bounce, the paths that entered its shade pass. [] after any other indirect call."""
+        cap = ((RT_INDIRECT_MAX_RAYS + 3) // 4) * RT_INDIRECT_MAX_BOUNCES
+        cnt = (C.c_int * cap)()
+        n = C.c_int()
+        _check(self.lib.rt_debug_indirect_path_counts(self.handle, cnt, cap, C.byref(n)), "rt_debug_indirect_path_counts")
+        b = getattr(self, "_paths_bounces", 0)    # the C entry reports counts[group * bounces + b]
+        if n.value == 0 or b < 1 or n.value % b:
+            return []
+        return [list(cnt)[g:g + b] for g in range(0, n.value, b)]
+
+    def indirect_paths_times(self):
+        """Device ms of every launch of the last timed indirect or indirect_paths call (set_indirect_timing; waits for
+        it): variant 1: the kernel; variant 0: per group of at most 4 rays the cast pass, the shade pass (bounces = 1)
+        or one shade-and-continue pass per bounce, and the resolve pass."""
+        return self._pass_times("indirect", (2 + RT_INDIRECT_MAX_BOUNCES) * ((RT_INDIRECT_MAX_RAYS + 3) // 4))

@@ -183,4 +183,14 @@ __device__ __forceinline__ void q_shade_hit(const RtFrameConsts &fc, AuxPtr ax, 
     }
 }
 
+// The texel q_shade_hit reads for h: its index expression and its documented clamp, restated for the callers that need
+// the texel beside the shaded colour (the paths of rt_indirect.hip)
+__device__ __forceinline__ void q_hit_texel(const RtFrameConsts &fc, const rt_hit &h, float &tr, float &tg, float &tb)
+{
+    int ci = f2i(h.ty * (float)fc.tex_h) * fc.tex_w + f2i(h.tx * (float)fc.tex_w);
+    const int last = fc.tex_w * fc.tex_h - 1;
+    ci = ci < 0 ? 0 : (ci > last ? last : ci);
+    tr = fc.tex_r[ci]; tg = fc.tex_g[ci]; tb = fc.tex_b[ci];
+}
+
 }  // namespace

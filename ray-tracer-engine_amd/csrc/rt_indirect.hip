@@ -17,6 +17,16 @@
 //   No float atomics: the order of the sum is the slab's. The queue holds as many entries as the group has slots.
 // Which of the two rt_indirect_desc.variant 0 names is kIndirectWavefrontIsProduct below, by the measurement of
 // DESIGN.md 6o. The brute-force variant (cull = 0) is the same kernels with the BVH replaced by the whole sphere list.
+//
+// Paths (rt_scene_indirect_paths with bounces > 1): a gather ray's hit spawns the next ray with a
+// throughput. Again two implementations, the same bits:
+//   plain       rt_indirect_paths_plain: the plain kernel with the loop over the bounces inside the loop over the rays;
+//   wavefront   per group the cast pass as it is (queue 0), then per bounce b one shade-and-continue pass over queue b
+//               on the shade pass's fixed grid: it shades the entry, adds the term to the entry's slot of the slab
+//               (one writer per slot and pass: the order of the sum is the order of the launches) and -- unless b is
+//               the last -- forms the next ray and casts it: a miss adds throughput x sky to the slot at once, a hit is
+//               ballot-compacted into queue b + 1 with its throughput and key. Two queues ping-pong; a pass pushes at
+//               most one entry per entry it read, so no queue outgrows the group's slots. Then the resolve pass as it is.
 #include "rt_cast.h"
 
 #include <algorithm>
@@ -26,6 +36,8 @@
 
 // variant 0 runs the wavefront passes and variant 1 the plain kernel (true), or the other way round (false)
 static const bool kIndirectWavefrontIsProduct = true;
+// the same choice for calls with bounces > 1, by the measurement of DESIGN.md 6p
+static const bool kIndirectPathsWavefrontIsProduct = true;
 
 struct RtIndirectDev {             // a call's arguments (by value)
     const float *depth;
@@ -68,6 +80,13 @@ __host__ __device__ __forceinline__ int rf_indirect_dir(V3 n, uint32_t key, V3 &
     return tries;
 }
 
+// key_b of a path from its key_0: key_{b+1} = mix(key_b ^ 0x426f756e)
+__host__ __device__ __forceinline__ uint32_t rf_indirect_path_key(uint32_t key, int b)
+{
+    for (int i = 0; i < b; ++i) key = rf_mix(key ^ 0x426f756eu);
+    return key;
+}
+
 namespace {
 
 __device__ __forceinline__ bool ind_finite(float v) { return __builtin_fabsf(v) <= 3.4028234663852886e38f; }   // NaN: false
@@ -96,6 +115,31 @@ __device__ __forceinline__ V3 ind_ray_dir(const RtFrameConsts &fc, const RtIndir
     V3 G;
     rf_indirect_dir(n, rf_gloss_key((uint32_t)x, (uint32_t)y, (uint32_t)(d.ray_base + j), d.seed), G);
     return G;
+}
+
+// key_0 of the path that ray j of pixel p starts: the key of ind_ray_dir
+__device__ __forceinline__ uint32_t ind_ray_key(const RtFrameConsts &fc, const RtIndirectDev &d, int p, int j)
+{
+    const int y = p / fc.width, x = p - y * fc.width;
+    return rf_gloss_key((uint32_t)x, (uint32_t)y, (uint32_t)(d.ray_base + j), d.seed);
+}
+
+// Step (g) of a path at the hit h of ray(O, D) under `key`: false if the hit's normal is dead; else O, D and key become
+// the next ray's
+__device__ __forceinline__ bool ind_next_ray(const rt_hit &h, V3 &O, V3 &D, uint32_t &key)
+{
+    V3 n{h.normal.x, h.normal.y, h.normal.z};
+    const float nn = (n.x * n.x + n.y * n.y) + n.z * n.z;
+    if (nn == 0.f || !ind_finite(nn)) return false;
+    rf_normalise(n);
+    if ((n.x * D.x + n.y * D.y) + n.z * D.z > 0.f) n = V3{-n.x, -n.y, -n.z};
+    const V3 P{O.x + D.x * h.t, O.y + D.y * h.t, O.z + D.z * h.t};
+    O = V3{n.x * 0.00001f + P.x, n.y * 0.00001f + P.y, n.z * 0.00001f + P.z};
+    key = rf_indirect_path_key(key, 1);
+    V3 G;
+    rf_indirect_dir(n, key, G);
+    D = G;
+    return true;
 }
 
 __device__ __forceinline__ void ind_store(const RtIndirectDev &d, int p, float4 c)
@@ -159,6 +203,60 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_plain(const RtF
         sr = sr + (0.f + fr);   // (what RT_QUERY_SHADE stores for the ray: the sum over one sample starts at 0)
         sg = sg + (0.f + fg);
         sb = sb + (0.f + fb);
+    }
+    ind_finish(d, p, sr, sg, sb);
+}
+
+// The plain kernel of a call with bounces > 1: per ray the loop of DESIGN.md 6p
+__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_paths_plain(const RtFrameConsts fc, const RtReflectDev rd,
+                                                                           const RtIndirectDev d, int bounces)
+{
+    __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
+    const LdsStack stk{stack_lds, (int)threadIdx.x};
+    const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;
+    const int p = (int)(blockIdx.x * RT_INDIRECT_BLOCK + threadIdx.x);
+    if (p >= fc.width * fc.height) return;
+    V3 n, start;
+    if (!ind_pixel(fc, d, p, n, start)) {
+        ind_store_dead(d, p);
+        return;
+    }
+    float sr = 0.f, sg = 0.f, sb = 0.f;
+#pragma unroll 1
+    for (int j = 0; j < d.rays; ++j) {
+        V3 O = start, D = ind_ray_dir(fc, d, p, j, n);
+        uint32_t key = ind_ray_key(fc, d, p, j);
+        float lr = 0.f, lg = 0.f, lb = 0.f, tr = 1.f, tg = 1.f, tb = 1.f;
+#pragma unroll 1
+        for (int b = 0;; ++b) {
+            int kind, pos;
+            const float nt = q_nearest(fc, ax, rd, O, D, stk, kind, pos);
+            float fr, fg, fb;
+            rt_hit h{};
+            if (kind >= 0) {
+                h = q_hit_record(fc, ax, rd, O, D, nt, kind, pos);
+                q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
+            } else {
+                rf_sky(ax, O, D, fr, fg, fb);
+            }
+            if (b == 0) {
+                lr = 0.f + fr; lg = 0.f + fg; lb = 0.f + fb;
+            } else {
+                lr = lr + tr * fr; lg = lg + tg * fg; lb = lb + tb * fb;
+            }
+            if (kind < 0 || b == bounces - 1) break;
+            float ar, ag, ab;
+            q_hit_texel(fc, h, ar, ag, ab);
+            if (b == 0) {
+                tr = ar; tg = ag; tb = ab;
+            } else {
+                tr = tr * ar; tg = tg * ag; tb = tb * ab;
+            }
+            if (!ind_next_ray(h, O, D, key)) break;
+        }
+        sr = sr + lr;
+        sg = sg + lg;
+        sb = sb + lb;
     }
     ind_finish(d, p, sr, sg, sb);
 }
@@ -229,6 +327,88 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_shade(const RtF
     }
 }
 
+// The shade-and-continue pass of bounce b over queue b: a fixed grid, the queue's length read here.
+// FIRST: b == 0, the entries are the cast pass's (no throughput; the key is the slot's); LAST: b == bounces - 1, nothing
+// continues. Every lane of a wave makes every trip of the loop (its bounds are uniform) and reaches the ballot: a lane
+// without an entry is inactive by `act`, never by leaving.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_paths_pass(const RtFrameConsts fc, const RtReflectDev rd,
+                                                                          const RtIndirectDev d, int j0, const float4 *q_in,
+                                                                          const int *count_in, float4 *q_out, int *count_out,
+                                                                          float4 *slab)
+{
+    __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
+    const LdsStack stk{stack_lds, (int)threadIdx.x};
+    const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;
+    const int n_in = *count_in;
+    constexpr int kIn = FIRST ? RT_INDIRECT_ENTRY_F4 : RT_INDIRECT_PATH_ENTRY_F4;
+    for (int base = (int)blockIdx.x * RT_INDIRECT_BLOCK; base < n_in; base += (int)gridDim.x * RT_INDIRECT_BLOCK) {
+        const int i = base + (int)threadIdx.x;
+        const bool act = i < n_in;
+        bool push = false;
+        V3 O{0.f, 0.f, 0.f}, D{0.f, 0.f, 0.f};
+        float nt = 0.f, tr = 0.f, tg = 0.f, tb = 0.f;
+        int kind = -1, pos = -1, slot = 0;
+        uint32_t key = 0;
+        if (act) {
+            const float4 *e = q_in + (size_t)kIn * (size_t)i;
+            const float4 e0 = e[0], e1 = e[1], e2 = e[2];
+            O = V3{e0.x, e0.y, e0.z};
+            D = V3{e1.x, e1.y, e1.z};
+            slot = __float_as_int(e2.y);
+            const rt_hit h = q_hit_record(fc, ax, rd, O, D, e0.w, __float_as_int(e1.w), __float_as_int(e2.x));
+            float fr, fg, fb;
+            q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
+            float lr, lg, lb;
+            if (FIRST) {
+                lr = 0.f + fr; lg = 0.f + fg; lb = 0.f + fb;
+                const int npx = fc.width * fc.height, j = slot / npx;
+                key = ind_ray_key(fc, d, slot - j * npx, j0 + j);
+            } else {
+                const float4 e3 = e[3], s = slab[slot];
+                tr = e3.x; tg = e3.y; tb = e3.z;
+                key = (uint32_t)__float_as_int(e3.w);
+                lr = s.x + tr * fr; lg = s.y + tg * fg; lb = s.z + tb * fb;
+            }
+            if (!LAST) {
+                float ar, ag, ab;
+                q_hit_texel(fc, h, ar, ag, ab);
+                if (FIRST) {
+                    tr = ar; tg = ag; tb = ab;
+                } else {
+                    tr = tr * ar; tg = tg * ag; tb = tb * ab;
+                }
+                if (ind_next_ray(h, O, D, key)) {
+                    nt = q_nearest(fc, ax, rd, O, D, stk, kind, pos);
+                    if (kind >= 0) {
+                        push = true;
+                    } else {   // the next bounce's miss, at once
+                        rf_sky(ax, O, D, fr, fg, fb);
+                        lr = lr + tr * fr; lg = lg + tg * fg; lb = lb + tb * fb;
+                    }
+                }
+            }
+            slab[slot] = make_float4(lr, lg, lb, 0.f);
+        }
+        if (!LAST) {   // append the wave's continuing paths (one atomic per wave; every lane of the wave is here)
+            const lmask m = ballot64(push);
+            if (m != 0) {
+                const int leader = __builtin_ctzll(m);
+                int b = 0;
+                if ((int)(threadIdx.x & 63u) == leader) b = atomicAdd(count_out, __popcll(m));
+                const int at = __builtin_amdgcn_readlane(b, leader);
+                if (push) {
+                    float4 *o = q_out + (size_t)RT_INDIRECT_PATH_ENTRY_F4 * (size_t)(at + lane_prefix(m));
+                    o[0] = make_float4(O.x, O.y, O.z, nt);
+                    o[1] = make_float4(D.x, D.y, D.z, __int_as_float(kind));
+                    o[2] = make_float4(__int_as_float(pos), __int_as_float(slot), 0.f, 0.f);
+                    o[3] = make_float4(tr, tg, tb, __int_as_float((int)key));
+                }
+            }
+        }
+    }
+}
+
 // The resolve pass of a group of g rays, one thread per pixel: S = (the earlier groups' sum, or +0) + the pixel's g
 // slots in ascending ray order. Not the last group: S goes to `sum`. The last group: steps 4 to 6, and the dead pixels.
 __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_resolve(const RtIndirectDev d, int npx, int g,
@@ -266,8 +446,9 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_resolve(const R
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-int rt_indirect_launch(const rt_indirect_desc *d, const RtFrameConsts *fc, const RtSphereBvh *bvh, const float4 *d_spheres,
-                       int n_spheres, const RtIndirectScratch *scratch, hipEvent_t *ev, int *n_ev, hipStream_t stream)
+int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameConsts *fc, const RtSphereBvh *bvh,
+                       const float4 *d_spheres, int n_spheres, const RtIndirectScratch *scratch, hipEvent_t *ev, int *n_ev,
+                       hipStream_t stream)
 {
     RtReflectDev rd{};
     rd.nodes = (bvh && bvh->ok) ? bvh->d_nodes.get() : nullptr;
@@ -287,26 +468,45 @@ int rt_indirect_launch(const rt_indirect_desc *d, const RtFrameConsts *fc, const
     };
     *n_ev = 0;
     RT_HIP(mark());
-    if (!rt_indirect_wavefront(d->variant)) {
-        hipLaunchKernelGGL(rt_indirect_plain, px_grid, block, 0, stream, *fc, rd, dd);
+    if (!rt_indirect_wavefront(d->variant, bounces)) {
+        if (bounces > 1) hipLaunchKernelGGL(rt_indirect_paths_plain, px_grid, block, 0, stream, *fc, rd, dd, bounces);
+        else hipLaunchKernelGGL(rt_indirect_plain, px_grid, block, 0, stream, *fc, rd, dd);
         RT_HIP(hipGetLastError());
         RT_HIP(mark());
         *n_ev = marks;
         return RT_OK;
     }
     const int groups = (d->rays + RT_INDIRECT_GROUP - 1) / RT_INDIRECT_GROUP;
-    RT_HIP(hipMemsetAsync(scratch->count, 0, sizeof(int) * (size_t)groups, stream));
+    RT_HIP(hipMemsetAsync(scratch->count, 0, sizeof(int) * (size_t)groups * (size_t)bounces, stream));
     for (int gi = 0; gi < groups; ++gi) {
         const int j0 = gi * RT_INDIRECT_GROUP, g = std::min(RT_INDIRECT_GROUP, d->rays - j0);
         const unsigned slot_blocks = (unsigned)(((long long)g * npx + RT_INDIRECT_BLOCK - 1) / RT_INDIRECT_BLOCK);
+        int *count = scratch->count + gi * bounces;   // one per bounce
+        const dim3 shade_grid(std::min<unsigned>(RT_INDIRECT_GRID, slot_blocks));
         hipLaunchKernelGGL(rt_indirect_cast, dim3(slot_blocks), block, 0, stream, *fc, rd, dd, j0, g, scratch->slab,
-                           scratch->queue, scratch->count + gi);
+                           scratch->queue, count);
         RT_HIP(hipGetLastError());
         RT_HIP(mark());
-        hipLaunchKernelGGL(rt_indirect_shade, dim3(std::min<unsigned>(RT_INDIRECT_GRID, slot_blocks)), block, 0, stream, *fc,
-                           rd, scratch->queue, scratch->count + gi, scratch->slab);
-        RT_HIP(hipGetLastError());
-        RT_HIP(mark());
+        if (bounces == 1) {
+            hipLaunchKernelGGL(rt_indirect_shade, shade_grid, block, 0, stream, *fc, rd, scratch->queue, count, scratch->slab);
+            RT_HIP(hipGetLastError());
+            RT_HIP(mark());
+        }
+        for (int b = 0; bounces > 1 && b < bounces; ++b) {   // queue b -> queue b + 1: the two buffers in turn
+            const float4 *q_in = (b & 1) ? scratch->queue2 : scratch->queue;
+            float4 *q_out = (b & 1) ? scratch->queue : scratch->queue2;
+            if (b == 0)
+                hipLaunchKernelGGL((rt_indirect_paths_pass<true, false>), shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in,
+                                   count, q_out, count + 1, scratch->slab);
+            else if (b < bounces - 1)
+                hipLaunchKernelGGL((rt_indirect_paths_pass<false, false>), shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in,
+                                   count + b, q_out, count + b + 1, scratch->slab);
+            else
+                hipLaunchKernelGGL((rt_indirect_paths_pass<false, true>), shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in,
+                                   count + b, (float4 *)nullptr, (int *)nullptr, scratch->slab);
+            RT_HIP(hipGetLastError());
+            RT_HIP(mark());
+        }
         hipLaunchKernelGGL(rt_indirect_resolve, px_grid, block, 0, stream, dd, npx, g, scratch->slab, scratch->sum,
                            gi == 0 ? 1 : 0, gi == groups - 1 ? 1 : 0);
         RT_HIP(hipGetLastError());
@@ -316,7 +516,10 @@ int rt_indirect_launch(const rt_indirect_desc *d, const RtFrameConsts *fc, const
     return RT_OK;
 }
 
-bool rt_indirect_wavefront(int variant) { return (variant == 0) == kIndirectWavefrontIsProduct; }
+bool rt_indirect_wavefront(int variant, int bounces)
+{
+    return (variant == 0) == (bounces > 1 ? kIndirectPathsWavefrontIsProduct : kIndirectWavefrontIsProduct);
+}
 
 // ---------------------------------------------------------------------------
 // host-only debug entry (tests)
@@ -333,5 +536,15 @@ extern "C" int rt_debug_indirect_dir(const rt_vec3 *n, const unsigned *key, int 
         G[i].x = o.x; G[i].y = o.y; G[i].z = o.z;
         if (tries) tries[i] = t;
     }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_indirect_path_key(const unsigned *key, int count, int b, unsigned *out)
+{
+    if (!key || !out || count < 0 || b < 0) {
+        rt_set_error("rt_debug_indirect_path_key: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < count; ++i) out[i] = rf_indirect_path_key(key[i], b);
     return RT_OK;
 }

@@ -261,13 +261,21 @@ int rt_upsample_launch(const rt_upsample_desc *d, hipEvent_t *ev, hipStream_t st
 #define RT_INDIRECT_GROUP 4
 #define RT_INDIRECT_MAX_GROUPS ((RT_INDIRECT_MAX_RAYS + RT_INDIRECT_GROUP - 1) / RT_INDIRECT_GROUP)
 #define RT_INDIRECT_ENTRY_F4 3
-#define RT_INDIRECT_MAX_EVENTS (1 + 3 * RT_INDIRECT_MAX_GROUPS)
+// Paths (rt_scene_indirect_paths with bounces > 1): the entries of the queues after the first carry the
+// throughput and the key in a fourth float4; two queues of that width ping-pong, and there is a counter per (group, bounce).
+#define RT_INDIRECT_PATH_ENTRY_F4 4
+#define RT_INDIRECT_MAX_COUNTS (RT_INDIRECT_MAX_GROUPS * RT_INDIRECT_MAX_BOUNCES)
+#define RT_INDIRECT_MAX_EVENTS (1 + (2 + RT_INDIRECT_MAX_BOUNCES) * RT_INDIRECT_MAX_GROUPS)
 struct RtIndirectScratch {
     float4 *slab, *queue, *sum;
     int *count;
+    float4 *queue2;   // paths only
 };
-bool rt_indirect_wavefront(int variant);   // whether `variant` runs the wavefront passes (and needs the scratch)
+// whether `variant` runs the wavefront passes (and needs the scratch) in a call of `bounces`
+bool rt_indirect_wavefront(int variant, int bounces = 1);
 // d: validated, in this build's layout; fc: the view's uniforms (whole frame, one sample, the pass's own ray tables);
-// bvh: null or current; ev: null, or RT_INDIRECT_MAX_EVENTS timing events, of which *n_ev are recorded
-int rt_indirect_launch(const rt_indirect_desc *d, const RtFrameConsts *fc, const RtSphereBvh *bvh, const float4 *d_spheres,
-                       int n_spheres, const RtIndirectScratch *scratch, hipEvent_t *ev, int *n_ev, hipStream_t stream);
+// bvh: null or current; ev: null, or RT_INDIRECT_MAX_EVENTS timing events, of which *n_ev are recorded; bounces: 1 is
+// rt_scene_indirect itself
+int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameConsts *fc, const RtSphereBvh *bvh,
+                       const float4 *d_spheres, int n_spheres, const RtIndirectScratch *scratch, hipEvent_t *ev, int *n_ev,
+                       hipStream_t stream);

@@ -1045,11 +1045,11 @@ extern "C" void rt_indirect_desc_init(rt_indirect_desc *d)
     d->cull = -1;
 }
 
-extern "C" int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d_in, void *stream_)
+// The host path of both entries: `name` is the entry's, bounces == 1 is rt_scene_indirect itself
+static int indirect_call(rt_scene *s, const rt_indirect_desc *d_in, int bounces, const char *name, hipStream_t stream)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (!s || !d_in) {
-        rt_set_error("rt_scene_indirect: null scene or description");
+        rt_set_error("%s: null scene or description", name);
         return RT_ERR_INVALID;
     }
     rt_indirect_desc d;
@@ -1080,19 +1080,19 @@ extern "C" int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d_in, void
             bad = "the scene has primitives but no texture";
     }
     if (bad) {
-        rt_set_error("rt_scene_indirect: %s (%d x %d)", bad, d.width, d.height);
+        rt_set_error("%s: %s (%d x %d)", name, bad, d.width, d.height);
         return RT_ERR_INVALID;
     }
-    const bool wavefront = rt_indirect_wavefront(d.variant);
+    const bool wavefront = rt_indirect_wavefront(d.variant, bounces);
     const size_t npx = (size_t)d.width * d.height;
     const size_t slots = (size_t)std::min(d.rays, RT_INDIRECT_GROUP) * npx;   // of the largest group
     if (wavefront && slots > (size_t)0x7fffffff - (size_t)2048 * 256) {
-        rt_set_error("rt_scene_indirect: %d rays of %d x %d pixels per pass exceed the queue's index range",
+        rt_set_error("%s: %d rays of %d x %d pixels per pass exceed the queue's index range", name,
                      std::min(d.rays, RT_INDIRECT_GROUP), d.width, d.height);
         return RT_ERR_CAPACITY;
     }
     if (stream_capturing(stream)) {
-        rt_set_error("rt_scene_indirect: the stream is being captured (the pass is not recorded into graphs)");
+        rt_set_error("%s: the stream is being captured (the pass is not recorded into graphs)", name);
         return RT_ERR_UNSUPPORTED;
     }
     RT_HIP(s->stage_done.order(stream));
@@ -1126,14 +1126,17 @@ extern "C" int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d_in, void
     const int groups = (d.rays + RT_INDIRECT_GROUP - 1) / RT_INDIRECT_GROUP;
     if (wavefront) {
         const size_t sum_px = groups > 1 ? npx : 0;
-        if (slots > s->ind_slab.capacity() || slots * RT_INDIRECT_ENTRY_F4 > s->ind_queue.capacity() || sum_px > s->ind_sum.capacity() ||
-            (size_t)RT_INDIRECT_MAX_GROUPS > s->ind_count.capacity()) {
+        // paths: two queues of the wider entry, which ping-pong
+        const size_t q1 = slots * (bounces > 1 ? RT_INDIRECT_PATH_ENTRY_F4 : RT_INDIRECT_ENTRY_F4), q2 = bounces > 1 ? q1 : 0;
+        if (slots > s->ind_slab.capacity() || q1 > s->ind_queue.capacity() || q2 > s->ind_queue2.capacity() ||
+            sum_px > s->ind_sum.capacity() || (size_t)RT_INDIRECT_MAX_COUNTS > s->ind_count.capacity()) {
             // growing releases the old buffers: after the host has seen the last call that used them end
             RT_HIP(s->ind_done.host_wait());
             RT_HIP(s->ind_slab.reserve(slots));
-            RT_HIP(s->ind_queue.reserve(slots * RT_INDIRECT_ENTRY_F4));
+            RT_HIP(s->ind_queue.reserve(q1));
+            RT_HIP(s->ind_queue2.reserve(q2));
             RT_HIP(s->ind_sum.reserve(sum_px));
-            RT_HIP(s->ind_count.reserve(RT_INDIRECT_MAX_GROUPS));
+            RT_HIP(s->ind_count.reserve(RT_INDIRECT_MAX_COUNTS));
         }
     }
     rt_frame_desc fd;
@@ -1159,15 +1162,44 @@ extern "C" int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d_in, void
             ev[i] = s->ind_ev[i].get();
         }
     }
-    const RtIndirectScratch scratch{s->ind_slab.get(), s->ind_queue.get(), s->ind_sum.get(), s->ind_count.get()};
+    const RtIndirectScratch scratch{s->ind_slab.get(), s->ind_queue.get(), s->ind_sum.get(), s->ind_count.get(), s->ind_queue2.get()};
     int n_ev = 0;
-    rc = rt_indirect_launch(&d, &fc, bvh, s->d_spheres.get(), s->n_spheres, &scratch, s->ind_timing ? ev : nullptr, &n_ev, stream);
+    rc = rt_indirect_launch(&d, bounces, &fc, bvh, s->d_spheres.get(), s->n_spheres, &scratch, s->ind_timing ? ev : nullptr, &n_ev, stream);
     // also after a launch that failed half way: what was enqueued uses the scratch
     RT_HIP(s->ind_done.record(stream));
     if (rc != RT_OK) return rc;
     if (s->ind_timing) s->ind_timed = n_ev;
-    s->ind_groups = wavefront ? groups : 0;
+    s->ind_groups = wavefront && bounces == 1 ? groups : 0;
+    s->ind_path_counts = wavefront && bounces > 1 ? groups * bounces : 0;
     return rt_scene_note_launch(s, stream, nullptr, nullptr);   // the pass in flight counts as a frame
+}
+
+extern "C" int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d, void *stream)
+{
+    return indirect_call(s, d, 1, "rt_scene_indirect", (hipStream_t)stream);
+}
+
+extern "C" void rt_indirect_paths_opts_init(rt_indirect_paths_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->struct_size = (uint32_t)sizeof *o;
+    o->bounces = 2;
+}
+
+extern "C" int rt_scene_indirect_paths(rt_scene *s, const rt_indirect_desc *d, const rt_indirect_paths_opts *o_in, void *stream)
+{
+    rt_indirect_paths_opts o;
+    rt_indirect_paths_opts_init(&o);
+    if (o_in) {   // fields past the caller's size keep their defaults
+        const size_t have = o_in->struct_size ? std::min((size_t)o_in->struct_size, sizeof o) : sizeof o;
+        if (have >= offsetof(rt_indirect_paths_opts, bounces) + sizeof o.bounces) o.bounces = o_in->bounces;
+    }
+    if (o.bounces < 1 || o.bounces > RT_INDIRECT_MAX_BOUNCES) {
+        rt_set_error("rt_scene_indirect_paths: bounces is not in [1, RT_INDIRECT_MAX_BOUNCES] (%d)", o.bounces);
+        return RT_ERR_INVALID;
+    }
+    return indirect_call(s, d, o.bounces, "rt_scene_indirect_paths", (hipStream_t)stream);
 }
 
 extern "C" int rt_scene_set_indirect_timing(rt_scene *s, int on)
@@ -1187,6 +1219,19 @@ extern "C" int rt_debug_indirect_counts(rt_scene *s, int *counts, int cap, int *
         return RT_ERR_INVALID;
     }
     *n = std::min(cap, s->ind_groups);
+    if (*n == 0) return RT_OK;
+    RT_HIP(s->ind_done.host_wait());
+    RT_HIP(hipMemcpy(counts, s->ind_count.get(), sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_debug_indirect_path_counts(rt_scene *s, int *counts, int cap, int *n)
+{
+    if (!s || !counts || !n || cap < 0) {
+        rt_set_error("rt_debug_indirect_path_counts: null argument");
+        return RT_ERR_INVALID;
+    }
+    *n = std::min(cap, s->ind_path_counts);
     if (*n == 0) return RT_OK;
     RT_HIP(s->ind_done.host_wait());
     RT_HIP(hipMemcpy(counts, s->ind_count.get(), sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost));

@@ -7,6 +7,13 @@ trace_rays(shade) of the same view's primary rays, and the frame with its four g
 it to --out (an existing "existing_paths" entry of that file is kept: tools/bench_reflect.py and bench.py fill it).
 
   python3 tools/bench_indirect.py [--iters 2] [--rounds 5] [--out profiles/indirect_c3.json]
+
+With --bounces N the diffuse paths instead (rt_scene_indirect_paths): one ray per pixel at both sizes,
+bounces 1 .. N, the two variants alternating as above, every launch of one call, the queue length entering each bounce;
+and bounces = 1 through the new entry against rt_scene_indirect, alternating. The default --out is then
+profiles/indirect_paths_c3.json.
+
+  python3 tools/bench_indirect.py --bounces 3
 """
 import argparse, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,13 +76,106 @@ def indirect_cases(rt, scene, w, h, iters, rounds):
     return res
 
 
+def _stats(runs):
+    return {"call_ms_rounds": runs, "call_ms_median": statistics.median(runs), "call_ms_min": min(runs), "call_ms_max": max(runs)}
+
+
+def paths_cases(rt, scene, w, h, max_bounces, iters, rounds):
+    st = torch.cuda.current_stream().cuda_stream
+    frame = scene.render(w, h, aov=ALL)
+    a = frame["aov"]
+    out = torch.empty_like(frame["rgba"])
+    packed = torch.empty_like(frame["packed"])
+    res = {"live_pixels": int((a["id"][..., 0] >= 0).sum())}
+
+    def desc(variant):
+        return scene.indirect_desc(w, h, depth=a["depth"].data_ptr(), normal=a["normal"].data_ptr(), id=a["id"].data_ptr(),
+                                   albedo=a["albedo"].data_ptr(), rgba_in=frame["rgba"].data_ptr(), rgba_out=out.data_ptr(),
+                                   pixels=packed.data_ptr(), rays=1, variant=variant)
+
+    def alternate(steps):
+        for s in steps.values():
+            settle(s, torch.cuda.synchronize, window=iters, max_windows=8)
+        runs = {k: [] for k in steps}
+        for _ in range(rounds):
+            for k, s in steps.items():
+                e0, e1 = timed(s, iters)
+                torch.cuda.synchronize()
+                runs[k].append(e0.elapsed_time(e1) / iters)
+        return runs
+
+    for bounces in range(1, max_bounces + 1):
+        o = scene.indirect_paths_opts(bounces)
+        steps = {}
+        for variant in (0, 1):
+            def step(d=desc(variant)):
+                if scene.indirect_paths_raw(d, o, st) != 0:
+                    raise rt.RtError("rt_scene_indirect_paths failed")
+            steps[variant] = step
+        runs = alternate(steps)
+        r = {}
+        scene.set_indirect_timing(True)
+        for variant in (0, 1):
+            steps[variant]()
+            r[f"variant{variant}"] = {**_stats(runs[variant]), "launch_ms": scene.indirect_paths_times(),
+                                      "queue": scene.indirect_path_counts() if bounces > 1 else [scene.indirect_counts()]}
+        scene.set_indirect_timing(False)
+        r["variant0_median_below_variant1_min"] = r["variant0"]["call_ms_median"] < r["variant1"]["call_ms_min"]
+        r["variant1_median_below_variant0_min"] = r["variant1"]["call_ms_median"] < r["variant0"]["call_ms_min"]
+        res[f"bounces{bounces}"] = r
+    # bounces = 1 through the new entry against rt_scene_indirect: the same launches
+    o1, d0 = scene.indirect_paths_opts(1), desc(0)
+
+    def old():
+        if scene.indirect_raw(d0, st) != 0:
+            raise rt.RtError("rt_scene_indirect failed")
+
+    def new():
+        if scene.indirect_paths_raw(d0, o1, st) != 0:
+            raise rt.RtError("rt_scene_indirect_paths failed")
+    runs = alternate({"rt_scene_indirect": old, "rt_scene_indirect_paths": new})
+    e = {k: _stats(v) for k, v in runs.items()}
+    a_, b_ = e["rt_scene_indirect"], e["rt_scene_indirect_paths"]
+    e["medians_inside_each_others_range"] = (b_["call_ms_min"] <= a_["call_ms_median"] <= b_["call_ms_max"] and
+                                             a_["call_ms_min"] <= b_["call_ms_median"] <= a_["call_ms_max"])
+    res["one_bounce_entries"] = e
+    return res
+
+
+def paths_main(rt, a):
+    out = {"iters": a.iters, "rounds": a.rounds, "rays": 1,
+           "statistic": "call_ms_rounds: hipEvent ms per call of --iters calls, the two variants alternating per round "
+                        "(settled clocks); launch_ms: the hipEvent time of each launch of one call "
+                        "(rt_scene_indirect_times); queue: per group, the entries that entered each bounce's shade pass",
+           "variants": "0: the product (wavefront: cast, one shade-and-continue pass per bounce, resolve); "
+                       "1: the plain one-thread-per-pixel yardstick"}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            old = json.load(f)
+        if "existing_paths" in old:
+            out["existing_paths"] = old["existing_paths"]
+    scene = rt.Scene.default(1024)
+    for w, h in ((3840, 2160), (1920, 1080)):
+        out[f"n1024_{w}x{h}"] = paths_cases(rt, scene, w, h, a.bounces, a.iters, a.rounds)
+    scene.close()
+    out["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(out))
+    with open(a.out, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "indirect_c3.json"))
+    ap.add_argument("--bounces", type=int, default=0, help="N: time the diffuse paths with bounces 1 .. N instead")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
     rt = rt_amd.load()
+    if a.bounces:
+        a.out = a.out or os.path.join(ROOT, "profiles", "indirect_paths_c3.json")
+        return paths_main(rt, a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "indirect_c3.json")
     out = {"iters": a.iters, "rounds": a.rounds,
            "statistic": "call_ms_rounds: hipEvent ms per call of --iters calls, the two variants alternating per round "
                         "(settled clocks); pass_ms: the hipEvent time of each launch of one call (rt_scene_indirect_times)",
