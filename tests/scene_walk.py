@@ -13,7 +13,15 @@ that survive everything.
 Two vocabularies: generate(seed, steps) is the first suite's (MUTATIONS, OUTPUTS; its sequences are pinned by digest in
 tests/test_scene_walk_cpu.py), generate(seed, steps, vocabulary=2) adds the scope, the sampling mode, the view lists, the
 plane and cube materials, plane and cube lists of several counts, G-buffer outputs, supersampled reflective frames,
-refused requests, the post passes and temporal accumulation (MUTATIONS_2, OUTPUTS_2; seeds WALK_SEEDS_2)."""
+refused requests, the post passes and temporal accumulation (MUTATIONS_2, OUTPUTS_2; seeds WALK_SEEDS_2).
+
+generate(seed, steps, vocabulary=3) adds what came after that: the three roughness tables (rt_engine.h, "Glossy
+reflections": a table follows its kind's k table -- it survives the list set with the same count and is cleared by
+another count; the material entries do not touch it), the gloss seed and the glass model ("Fresnel glass"; both survive
+everything), and the two gather passes as an output of their own, "gather": rt_scene_indirect / rt_scene_indirect_paths
+over guides the scene renders itself, at full or half size, on either stream (MUTATIONS_3, OUTPUTS_3; seeds
+WALK_SEEDS_3, which together reach every label of REQUIRED_3). The first two vocabularies' sequences stay what they
+were; both are pinned by digest."""
 import random
 from dataclasses import dataclass, replace
 
@@ -56,6 +64,31 @@ PLANE_MOVE = (0.0, -0.5, 0.0)            # added to the last plane's point
 CUBE_MOVE = (0.25, 0.5, -0.25)           # added to cube 1's centre and bounds
 KIND_K = (0.0, 0.25, 0.5, 1.0)
 
+# the third vocabulary
+WALK_SEEDS_3 = (700, 1235, 2191, 4727, 6182, 7125)   # every label of REQUIRED_3 is on two of these walks at the least
+MUTATIONS_3 = MUTATIONS_2 + ("roughness", "gloss_seed", "glass_model")
+OUTPUTS_3 = OUTPUTS_2 + ("gather",)
+ROUGHNESS = (0.0, 0.0, 0.2, 0.6, 1.0)    # (two zeros: some primitives of a rough table stay sharp)
+ROUGH_KINDS = ("spheres", "planes", "cubes")
+GLOSS_SEEDS = (0, 1, 5, 0xffffffff)
+GATHER_RAYS = (1, 2, 4, 5, 9)            # groups of 4: one group, a whole group, two groups, three groups
+V3_OPS = ("roughness", "gloss_seed", "glass_model", "gather")
+# what the third vocabulary's walks must reach over WALK_SEEDS_3 (the labels of _transitions_3)
+REQUIRED_3 = frozenset(
+    MUTATIONS_3 + OUTPUTS_3
+    + tuple("roughness:%s:%s" % (k, how) for k in ("spheres", "planes", "cubes")
+            for how in ("set", "clear", "kept", "cleared_by_count"))
+    + ("gloss_seed", "glass_model:to_fresnel", "glass_model:to_plain",
+       "render:glossy", "render:glossy_scene_scope", "render:glossy_many", "render:fresnel", "render:frosted",
+       "pass:render_upscaled_glossy", "temporal:glossy",
+       "gather:indirect", "gather:paths1", "gather:paths2", "gather:paths3", "gather:paths4",
+       "gather:two_groups", "gather:three_groups", "gather:variant1", "gather:cull0", "gather:half_size",
+       "gather:mesh", "gather:above_8192", "gather:grows", "gather:smaller", "gather:second_queue_appears",
+       "gather_after:spheres:count", "gather_after:spheres:same_count", "gather_after:lights", "gather_after:texture",
+       "gather_after:planes", "gather_after:cubes", "gather_after:mesh",
+       "bvh_first_user:gather", "bvh_first_user:query", "bvh_first_user:render",
+       "gather_deferred_then_mutation"))
+
 
 @dataclass(frozen=True)
 class State:
@@ -64,7 +97,8 @@ class State:
     mats: None, or (kind, seed) with kind "k" (old entry: mirrors only) or "ex" (mirrors and glass) -- the arrays are
     material_arrays(kind, seed, count). planes / cubes: None (or False), or a spec (count, variant) out of PLANE_SPECS /
     CUBE_SPECS (True, the first vocabulary's "on": the first spec); mesh: 0 (or False) none, 1 (or True) the mesh, 2 the
-    same mesh elsewhere; plane_mats / cube_mats: None, or the seed of kind_k(seed, count)."""
+    same mesh elsewhere; plane_mats / cube_mats: None, or the seed of kind_k(seed, count); rough_spheres / rough_planes / rough_cubes: None, or
+    the seed of roughness(seed, count); gloss_seed: rt_scene_set_gloss_seed's; glass_model: "plain" / "fresnel"."""
     spheres: tuple = (256, 1, 0.0)
     lights: tuple = DEFAULT_LIGHTS
     texture: int = 0
@@ -78,6 +112,11 @@ class State:
     view_lists: int = 1
     plane_mats: int = None
     cube_mats: int = None
+    rough_spheres: int = None
+    rough_planes: int = None
+    rough_cubes: int = None
+    gloss_seed: int = 0
+    glass_model: str = "plain"
 
     @property
     def n(self):
@@ -90,6 +129,14 @@ class State:
     @property
     def n_cubes(self):
         return spec_of(self.cubes, CUBE_SPECS)[0]
+
+    def count_of(self, kind):
+        """The length of the list of `kind` (out of ROUGH_KINDS)."""
+        return {"spheres": self.n, "planes": self.n_planes, "cubes": self.n_cubes}[kind]
+
+    def rough(self):
+        """The kinds that have a roughness table."""
+        return tuple(k for k in ROUGH_KINDS if getattr(self, "rough_" + k) is not None)
 
     def reflect_ok(self):
         """Reflective frames take every primitive under the scene scope, spheres only under the other."""
@@ -106,6 +153,11 @@ def spec_of(value, specs):
 def kind_k(seed, n):
     """k per plane or cube, float32, out of KIND_K."""
     return np.random.default_rng(2000 + seed).choice(np.float32(KIND_K), n).astype(np.float32)
+
+
+def roughness(seed, n):
+    """rho per primitive of one kind, float32, out of ROUGHNESS."""
+    return np.random.default_rng(3000 + seed).choice(np.float32(ROUGHNESS), n).astype(np.float32)
 
 
 def material_arrays(kind, seed, n):
@@ -127,8 +179,9 @@ def apply(state, op):
     kind = op["op"]
     if kind == "spheres":
         sp = op["spheres"]
-        mats = state.mats if sp[0] == state.n else None          # another count clears the materials
-        return replace(state, spheres=sp, mats=mats)
+        same = sp[0] == state.n                                  # another count clears the materials and the roughness
+        return replace(state, spheres=sp, mats=state.mats if same else None,
+                       rough_spheres=state.rough_spheres if same else None)
     if kind == "lights":
         return replace(state, lights=op["lights"])
     if kind == "texture":
@@ -136,8 +189,10 @@ def apply(state, op):
     if kind in ("planes", "cubes"):
         specs, mats = (PLANE_SPECS, "plane_mats") if kind == "planes" else (CUBE_SPECS, "cube_mats")
         same = spec_of(op[kind], specs)[0] == spec_of(getattr(state, kind), specs)[0]
-        return replace(state, **{kind: op[kind], mats: getattr(state, mats) if same else None})   # as the spheres' table
-    if kind in ("mesh", "tile_order", "scope", "samples", "view_lists"):
+        rough = "rough_" + kind
+        return replace(state, **{kind: op[kind], mats: getattr(state, mats) if same else None,   # as the spheres' tables
+                                 rough: getattr(state, rough) if same else None})
+    if kind in ("mesh", "tile_order", "scope", "samples", "view_lists", "gloss_seed", "glass_model"):
         return replace(state, **{kind: op[kind]})
     if kind == "materials":
         return replace(state, mats=op["mats"])                   # "k" is the old entry: it clears the glass
@@ -145,6 +200,8 @@ def apply(state, op):
         return replace(state, plane_mats=op["seed"])
     if kind == "cube_materials":
         return replace(state, cube_mats=op["seed"])
+    if kind == "roughness":
+        return replace(state, **{"rough_" + op["kind"]: op["seed"]})
     if kind == "temporal" and op.get("mutation"):                # the change between the step's two frames
         return apply(state, op["mutation"])
     return state
@@ -224,9 +281,11 @@ def _graph_op(rng, state):
 
 def generate(seed, steps, vocabulary=1):
     """`steps` operations on one scene that starts as State(). Deterministic per seed. vocabulary 1: the first suite's
-    operations, exactly as they were; 2: those of generate_2."""
+    operations, exactly as they were; 2: those of generate_2; 3: those of generate_3."""
     if vocabulary == 2:
         return generate_2(seed, steps)
+    if vocabulary == 3:
+        return generate_3(seed, steps)
     rng = random.Random(seed)
     state = State()
     ops = []
@@ -434,6 +493,238 @@ def generate_2(seed, steps):
     return ops
 
 
+# ------------------------------------------------------------------------------------------------ the third vocabulary
+def _roughness_op(rng, state):
+    """A table of a kind that has primitives set (a new seed) or cleared; None where the scene has no such kind."""
+    kinds = [k for k in ROUGH_KINDS if state.count_of(k) > 0]
+    if not kinds:
+        return None
+    kind = rng.choice(kinds)
+    cur = getattr(state, "rough_" + kind)
+    if cur is not None and rng.random() < 0.3:
+        return {"op": "roughness", "kind": kind, "how": "clear", "seed": None}
+    return {"op": "roughness", "kind": kind, "how": "set", "seed": rng.choice([s for s in range(1, 50) if s != cur])}
+
+
+def _gather_op(rng, state):
+    """One gather pass over guides the scene renders for it (reflect_depth 0, all four G-buffer outputs): entry
+    "indirect", or "paths" with 1 .. 4 bounces (1 issues the other entry's launches). shrink 2: the guides and the pass
+    at half the size, the result lifted onto a full-size frame by upsample(base=True, demodulate=True). Above 1024
+    spheres at most 2 rays and 2 bounces."""
+    w, h = rng.choice(SIZES)
+    entry = rng.choice(("indirect", "paths", "paths"))
+    bounces = rng.randrange(1, 5) if entry == "paths" else 1
+    rays = rng.choice(GATHER_RAYS)
+    if state.n > 1024:
+        rays, bounces = rng.choice((1, 2)), min(bounces, 2)
+    op = {"op": "gather", "entry": entry, "bounces": bounces, "rays": rays, "ray_base": rng.choice((0, 3)),
+          "seed": rng.randrange(1 << 32), "strength": rng.choice((0.75, 1.0)), "cull": int(rng.random() < 0.75),
+          "variant": int(rng.random() >= 0.75), "size": (w, h), "shrink": rng.choice((1, 1, 2)),
+          "cam": rng.randrange(len(CAMERAS)), "aspect": rng.choice(ASPECTS), "colour": rng.choice(("frame", None)),
+          "modulate": rng.random() < 0.7}
+    op.update(_stream_fields(rng))
+    return op
+
+
+def gather_scratch(op):
+    """What a gather asks of the scene's scratch, as rt_scene_indirect / _paths state it: (slots of the slab, float4 of
+    the first queue, float4 of the second queue, pixels of the running sum); None for the yardstick variant, which
+    takes none."""
+    if op["variant"]:
+        return None
+    w, h = op["size"]
+    npx = (w // op["shrink"]) * (h // op["shrink"])
+    slots = min(op["rays"], 4) * npx
+    paths = op["bounces"] > 1
+    q = slots * (4 if paths else 3)
+    return (slots, q, q if paths else 0, npx if op["rays"] > 4 else 0)
+
+
+def generate_3(seed, steps):
+    """`steps` operations of the third vocabulary on one scene that starts as State(). Deterministic per seed."""
+    rng = random.Random(1000003 * 3 + seed)
+    state = State()
+    ops = []
+    while len(ops) < steps:
+        r = rng.random()
+        if r < 0.47:
+            kind = rng.choice(("spheres", "spheres", "spheres", "lights", "lights", "texture", "planes", "planes", "planes",
+                               "cubes", "cubes", "cubes", "mesh", "mesh", "materials", "materials", "materials", "tile_order",
+                               "scope", "scope", "scope", "samples", "samples", "view_lists", "plane_materials",
+                               "plane_materials", "cube_materials", "cube_materials", "roughness", "roughness", "roughness",
+                               "roughness", "roughness", "roughness", "gloss_seed", "glass_model", "glass_model"))
+            if kind == "spheres":
+                op = _spheres_op(rng, state)
+            elif kind == "lights":
+                op = _lights_op(rng, state.lights)
+            elif kind == "texture":
+                op = {"op": "texture", "texture": 1 - state.texture}
+            elif kind in ("planes", "cubes"):
+                op = _kind_list_op(rng, state, kind)
+            elif kind == "mesh":
+                op = {"op": "mesh", "mesh": rng.choice([m for m in (0, 1, 2) if m != int(state.mesh)])}
+            elif kind == "materials":
+                op = _materials_op(rng, state)
+            elif kind == "tile_order":
+                op = {"op": "tile_order", "tile_order": 1 - state.tile_order}
+            elif kind == "scope":
+                op = {"op": "scope", "scope": "scene" if state.scope == "spheres" else "spheres"}
+            elif kind == "samples":
+                op = {"op": "samples", "samples": "many" if state.samples == "one" else "one"}
+            elif kind == "view_lists":
+                op = {"op": "view_lists", "view_lists": 1 - state.view_lists}
+            elif kind == "roughness":
+                op = _roughness_op(rng, state)
+                if op is None:
+                    continue
+            elif kind == "gloss_seed":
+                op = {"op": "gloss_seed", "gloss_seed": rng.choice([g for g in GLOSS_SEEDS if g != state.gloss_seed])}
+            elif kind == "glass_model":
+                op = {"op": "glass_model", "glass_model": "fresnel" if state.glass_model == "plain" else "plain"}
+            else:
+                op = _kind_materials_op(rng, state, kind)
+            state = apply(state, op)
+            ops.append(op)
+            # an output right after the change, before any render: gathers, graph replays and queries read the scene as is
+            if rng.random() < 0.5 and len(ops) < steps:
+                q = rng.random()
+                ops.append(_gather_op(rng, state) if q < 0.6 else _graph_op(rng, state) if q < 0.8 else _query_op(rng, state))
+        elif r < 0.67:
+            ops.append(_render_op_2(rng, state))
+        elif r < 0.70:
+            ops.append(_query_op(rng, state))
+        elif r < 0.73:
+            ops.append(_graph_op(rng, state))
+        elif r < 0.76:
+            op = _refused_op(rng, state)
+            if op is not None:
+                ops.append(op)
+        elif r < 0.83:
+            ops.append(_pass_op(rng, state))
+        elif r < 0.87:
+            op = _temporal_op(rng, state)
+            state = apply(state, op)
+            ops.append(op)
+        else:
+            ops.append(_gather_op(rng, state))
+    return ops
+
+
+def _glossy(mats, rough, n, seeds_k):
+    """Whether some primitive of a list of n is a mirror (k > 0) with roughness > 0."""
+    if mats is None or rough is None or n == 0:
+        return False
+    return bool(((seeds_k(mats, n) > 0) & (roughness(rough, n) > 0)).any())
+
+
+def _sphere_k(mats, n):
+    return material_arrays(mats[0], mats[1], n)[0]
+
+
+def _frame_kinds(state, depth):
+    """What a frame of `depth` bounces in `state` exercises of the glossy and Fresnel paths: a set out of "glossy",
+    "glossy_scene_scope", "fresnel", "frosted"."""
+    out = set()
+    if not depth:
+        return out
+    if _glossy(state.mats, state.rough_spheres, state.n, _sphere_k):
+        out.add("glossy")
+    if state.scope == "scene" and (_glossy(state.plane_mats, state.rough_planes, state.n_planes, kind_k) or
+                                   _glossy(state.cube_mats, state.rough_cubes, state.n_cubes, kind_k)):
+        out.add("glossy_scene_scope")
+    if state.glass_model == "fresnel" and state.mats is not None and state.mats[0] == "ex" and state.n:
+        tau = material_arrays(*state.mats, state.n)[1]
+        if (tau > 0).any():
+            out.add("fresnel")
+            if state.rough_spheres is not None and ((tau > 0) & (roughness(state.rough_spheres, state.n) > 0)).any():
+                out.add("frosted")
+    return out
+
+
+def _transitions_3(seen, state, op, prev, track):
+    """The third vocabulary's labels of one step. `track` follows the walk: "since" the mutations since the last
+    output, "bvh" whether the spheres changed since the shared BVH's last user, "scratch" the largest request per
+    scratch buffer so far, "one_bounce" the largest one-bounce request of slots, "second" whether a second queue exists."""
+    k = op["op"]
+    if k == "roughness":
+        seen.add("roughness:%s:%s" % (op["kind"], op["how"]))
+    elif k == "gloss_seed":
+        seen.add("gloss_seed")
+    elif k == "glass_model":
+        seen.add("glass_model:to_" + op["glass_model"])
+    elif k in ROUGH_KINDS and getattr(state, "rough_" + k) is not None:
+        kept = getattr(apply(state, op), "rough_" + k) is not None
+        seen.add("roughness:%s:%s" % (k, "kept" if kept else "cleared_by_count"))
+    elif k == "render":
+        kinds = _frame_kinds(state, op["depth"])
+        seen.update("render:" + f for f in kinds)
+        if kinds & {"glossy", "glossy_scene_scope"} and op["spp"] > 1 and state.samples == "many":
+            seen.add("render:glossy_many")
+    elif k == "pass" and op["what"] == "render_upscaled" and state.rough():
+        seen.add("pass:render_upscaled_glossy")
+    elif k == "temporal" and state.rough():
+        seen.add("temporal:glossy")
+    elif k == "gather":
+        seen.add("gather:indirect" if op["entry"] == "indirect" else "gather:paths%d" % op["bounces"])
+        if op["rays"] > 4:
+            seen.add("gather:two_groups")
+        if op["rays"] > 8:
+            seen.add("gather:three_groups")
+        if op["variant"]:
+            seen.add("gather:variant1")
+        if not op["cull"]:
+            seen.add("gather:cull0")
+        if op["shrink"] == 2:
+            seen.add("gather:half_size")
+        if state.mesh:
+            seen.add("gather:mesh")
+        if state.n > 8192:
+            seen.add("gather:above_8192")
+        need = gather_scratch(op)
+        if need is not None:
+            have = track.get("scratch")
+            if have is not None:
+                if any(a > b for a, b in zip(need, have)):
+                    seen.add("gather:grows")
+                elif need[0] < have[0]:
+                    seen.add("gather:smaller")
+            if op["bounces"] > 1:
+                if not track.get("second") and track.get("one_bounce", 0) >= need[0]:
+                    seen.add("gather:second_queue_appears")     # only the second queue is new
+                track["second"] = True
+            else:
+                track["one_bounce"] = max(track.get("one_bounce", 0), need[0])
+            track["scratch"] = need if have is None else tuple(max(a, b) for a, b in zip(need, have))
+        for m in track.get("since", ()):
+            seen.add("gather_after:" + m)
+    # the shared sphere BVH: who reads it first after a change of the spheres
+    if k == "spheres" and op["how"] != "same_list" or k == "temporal" and op["form"] == "motion_spheres":
+        track["bvh"] = True
+    elif track.get("bvh") and state.n > 0:
+        user = None
+        if k == "gather" and op["cull"]:
+            user = "gather"
+        elif k == "query" and op["cull"]:
+            user = "query"
+        elif k == "render" and op["depth"] and op["cull"]:
+            user = "render"
+        elif k == "pass" and op.get("depth"):
+            user = "pass"
+        if user:
+            seen.add("bvh_first_user:" + user)
+            track["bvh"] = False
+    # the mutations no output has read yet
+    if k in MUTATIONS_3:
+        since = track.setdefault("since", [])
+        name = "spheres:" + op["how"] if k == "spheres" else k
+        if name not in since:
+            since.append(name)
+    else:
+        track["since"] = []
+    if prev is not None and prev["op"] == "gather" and prev["defer"] and prev["stream"] == 1 and k in MUTATIONS_3:
+        seen.add("gather_deferred_then_mutation")
+
+
 def _transitions_2(seen, state, op, prev, cleared):
     """The second vocabulary's labels of one step; `cleared` is the set of material tables a count change has cleared
     and nothing has set again."""
@@ -500,10 +791,14 @@ def transitions(ops):
     state = State()
     prev = None
     cleared = set()
+    third = any(op["op"] in V3_OPS for op in ops)        # the first two vocabularies' label sets stay what they are
+    track = {}
     for op in ops:
         k = op["op"]
         seen.add(k)
         _transitions_2(seen, state, op, prev, cleared)
+        if third:
+            _transitions_3(seen, state, op, prev, track)
         if k == "spheres":
             n0, m = state.n, op["spheres"][0]
             seen.add("spheres:" + op["how"])
@@ -672,6 +967,11 @@ def set_materials(scene, state_mats, n, old_entry=None):
         scene.set_materials_ex(reflectivity=k, transparency=tau, ior=ior)
 
 
+def set_roughness(scene, kind, seed, n):
+    """Put roughness(seed, n) on the table of `kind` (out of ROUGH_KINDS) of `scene`; a seed of None clears it."""
+    scene.set_roughness(kind[:-1], None if seed is None else roughness(seed, n))
+
+
 def apply_to_scene(rt, scene, op, state):
     """Carry a mutation out on a live scene whose state is `state` (before the op)."""
     k = op["op"]
@@ -702,6 +1002,12 @@ def apply_to_scene(rt, scene, op, state):
         scene.set_plane_materials(None if op["seed"] is None else kind_k(op["seed"], state.n_planes))
     elif k == "cube_materials":
         scene.set_cube_materials(None if op["seed"] is None else kind_k(op["seed"], state.n_cubes))
+    elif k == "roughness":
+        set_roughness(scene, op["kind"], op["seed"], state.count_of(op["kind"]))
+    elif k == "gloss_seed":
+        scene.set_gloss_seed(op["gloss_seed"])
+    elif k == "glass_model":
+        scene.set_glass_model(op["glass_model"])
 
 
 def fresh_scene(rt, state):
@@ -724,6 +1030,12 @@ def fresh_scene(rt, state):
         s.set_plane_materials(kind_k(state.plane_mats, state.n_planes))
     if state.cube_mats is not None:
         s.set_cube_materials(kind_k(state.cube_mats, state.n_cubes))
+    for kind in state.rough():
+        set_roughness(s, kind, getattr(state, "rough_" + kind), state.count_of(kind))
+    if state.gloss_seed:
+        s.set_gloss_seed(state.gloss_seed)
+    if state.glass_model != "plain":
+        s.set_glass_model(state.glass_model)
     if state.scope != "spheres":
         s.set_reflect_scope(state.scope)
     if state.samples != "one":

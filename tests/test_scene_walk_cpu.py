@@ -1,7 +1,10 @@
 """The operation sequences of tests/test_scene_state_gpu.py (no GPU): deterministic per seed, within the library's rules,
 and covering every transition the state tests are there for. The state model's materials rule is DESIGN.md 6d's; the
 rules of the plane and cube materials, the scope and the sampling mode are rt_engine.h's. The first vocabulary's
-sequences are pinned by digest; the second vocabulary's walks must reach REQUIRED_2 and keep refusals rare."""
+sequences are pinned by digest; the second vocabulary's walks must reach REQUIRED_2 and keep refusals rare. The third
+vocabulary (roughness, gloss seed, glass model, the gather passes; tests/test_scene_state3_gpu.py) is pinned by digest
+like the other two, its walks must reach sw.REQUIRED_3, and its model follows rt_engine.h's "Glossy reflections" and
+"Fresnel glass"."""
 import hashlib
 
 import numpy as np
@@ -304,3 +307,211 @@ def test_the_variants_of_the_lists(rt):
     assert np.array_equal(sm[:, :3], ob[0] - oa[0]) and np.array_equal(cm[:, :3], ob[1] - oa[1])
     sm, cm = sw.motion_tables(rt, a, sw.State(spheres=(8, 1, 0.0), cubes=(5, 1)))
     assert sm.shape == (0, 4) and cm.shape == (5, 4)
+
+
+# ------------------------------------------------------------------------------------------------ the third vocabulary
+# sha256 of repr(generate(seed, 60, vocabulary=2)) as the module gave it before it had a third vocabulary
+OLD_WALKS_2 = {
+    17: "d4334273a920017e50326952f9ae5c0e91306ed31189d12818c2384175b63685",
+    25: "cfd83cc728f8c839ef5bc3675cab48abbfc5a6ac67d51147f144b62044afeaea",
+    149: "5e5f3501c3549d10c7b25185bd2b993d52d1cd7d59b10e16476cde57c6ad9f30",
+    262: "d32dac465741cc577c062918528afaf09a9a1289ae4f834897299622ffef0ff5",
+    1103: "b9a187c545009a3cff6a989a7b7fd7f4bfaaaf4a986a8b335f5f03aecc60f29c",
+    1205: "3d127c39f3e101cba9a6bed29489eaa19e2cbc76c5b18fe7d542cede33ecba76",
+}
+# sha256 of repr(generate(seed, 60, vocabulary=3)): the walks tests/test_scene_state3_gpu.py was run with
+WALKS_3 = {
+    700: "edd8f71a064d5167313cbf0243fee0f38d3b2f1f7ec1a548cb17c8ea0d1ea9fd",
+    1235: "0e8cd3157a17396348cd47aa6be42df35a35131928736890f83744a658563956",
+    2191: "84a2712781267b4c6b104055a48342cdddfe7c9519afa746609b227585feb8fc",
+    4727: "9453bba134da01d13a21ae40e3cc158640132fb74f284b1910e084877f7e28e5",
+    6182: "faa7e6a30f8f2acf4357c406501a58fec4cfb13c93c3e2f3b6bf783eb390ee17",
+    7125: "a540f888fe951eeea6e6cbd1ef71ef781bcd09ed4e7c6e265c95aa83d4d5026f",
+}
+
+
+def _digest(ops):
+    return hashlib.sha256(repr(ops).encode()).hexdigest()
+
+
+def test_the_second_walks_are_what_they_were():
+    assert set(OLD_WALKS_2) == set(WALK_SEEDS_2) and WALK_STEPS == 60
+    for seed, digest in OLD_WALKS_2.items():
+        assert _digest(sw.generate(seed, 60, vocabulary=2)) == digest, seed
+    # and the label sets of the first two vocabularies carry nothing of the third
+    for seeds, v in ((WALK_SEEDS, 1), (WALK_SEEDS_2, 2)):
+        for seed in seeds:
+            new = {t for t in sw.transitions(sw.generate(seed, 60, vocabulary=v))
+                   if t.split(":")[0] in ("roughness", "gather", "gather_after", "bvh_first_user", "gloss_seed", "glass_model")}
+            assert not new, (v, seed, new)
+
+
+def test_third_generator_is_deterministic_and_pinned():
+    assert set(WALKS_3) == set(sw.WALK_SEEDS_3) and len(sw.WALK_SEEDS_3) == 6
+    assert sw.MUTATIONS_3 == sw.MUTATIONS_2 + ("roughness", "gloss_seed", "glass_model")
+    assert sw.OUTPUTS_3 == sw.OUTPUTS_2 + ("gather",)
+    for seed, digest in WALKS_3.items():
+        ops = sw.generate(seed, WALK_STEPS, vocabulary=3)
+        assert ops == sw.generate(seed, WALK_STEPS, vocabulary=3) == sw.generate_3(seed, WALK_STEPS)
+        assert len(ops) == WALK_STEPS and all(op["op"] in sw.MUTATIONS_3 + sw.OUTPUTS_3 for op in ops)
+        assert _digest(ops) == digest, seed
+    assert sw.generate(sw.WALK_SEEDS_3[0], WALK_STEPS, vocabulary=3) != sw.generate(sw.WALK_SEEDS_3[1], WALK_STEPS, vocabulary=3)
+
+
+def test_third_walks_cover_every_transition():
+    assert len(sw.REQUIRED_3) == 70 and set(sw.MUTATIONS_3 + sw.OUTPUTS_3) <= sw.REQUIRED_3
+    walks = {label: 0 for label in sw.REQUIRED_3}
+    for seed in sw.WALK_SEEDS_3:
+        one = sw.transitions(sw.generate(seed, WALK_STEPS, vocabulary=3))
+        assert "gather" in one and any(t.startswith("gather_after:") for t in one), seed     # every single walk
+        for label in one & sw.REQUIRED_3:
+            walks[label] += 1
+    missing = sorted(label for label, n in walks.items() if n == 0)
+    assert not missing, missing
+    thin = sorted(label for label, n in walks.items() if n < 2)   # no transition rests on one walk alone
+    assert not thin, thin
+
+
+def test_third_walks_respect_the_library_rules():
+    """Every walk replayed against apply: the second vocabulary's rules for what it shares, and the new steps within
+    what rt_engine.h accepts -- a roughness table only for a kind with primitives, its values in [0, 1], a gather with
+    rays in 1 .. RT_INDIRECT_MAX_RAYS and bounces in 1 .. RT_INDIRECT_MAX_BOUNCES, bounded above 1024 spheres;
+    refusals are the header's and at most a quarter of a walk's output steps."""
+    refused_all = 0
+    for seed in sw.WALK_SEEDS_3:
+        state = sw.State()
+        outputs = refused = 0
+        for i, op in enumerate(sw.generate(seed, WALK_STEPS, vocabulary=3)):
+            where = "seed %d step %d: %s" % (seed, i, op)
+            k = op["op"]
+            outputs += k in sw.OUTPUTS_3
+            if k == "roughness":
+                n = state.count_of(op["kind"])
+                assert op["kind"] in sw.ROUGH_KINDS and n > 0, where
+                assert (op["how"], op["seed"] is None) in (("set", False), ("clear", True)), where
+                if op["seed"] is not None:
+                    rho = sw.roughness(op["seed"], n)
+                    assert rho.dtype == np.float32 and rho.shape == (n,) and set(rho.tolist()) <= set(np.float32(sw.ROUGHNESS).tolist()), where
+                    assert op["seed"] != getattr(state, "rough_" + op["kind"]), where
+                else:
+                    assert getattr(state, "rough_" + op["kind"]) is not None, where
+            elif k == "gloss_seed":
+                assert op["gloss_seed"] in sw.GLOSS_SEEDS and op["gloss_seed"] != state.gloss_seed, where
+            elif k == "glass_model":
+                assert op["glass_model"] in ("plain", "fresnel") and op["glass_model"] != state.glass_model, where
+            elif k == "gather":
+                assert op["entry"] in ("indirect", "paths") and 1 <= op["rays"] <= 16 and 1 <= op["bounces"] <= 4, where
+                assert op["entry"] == "paths" or op["bounces"] == 1, where
+                assert op["rays"] in sw.GATHER_RAYS and op["ray_base"] in (0, 3) and op["strength"] in (0.75, 1.0), where
+                assert 0 <= op["seed"] < 1 << 32 and op["cull"] in (0, 1) and op["variant"] in (0, 1), where
+                assert op["size"] in sw.SIZES and op["shrink"] in (1, 2) and op["aspect"] in sw.ASPECTS, where
+                assert not (op["size"][0] % op["shrink"] or op["size"][1] % op["shrink"]), where
+                assert op["colour"] in ("frame", None) and op["modulate"] in (True, False), where
+                assert op["stream"] in (0, 1) and op["defer"] in (True, False), where
+                if state.n > 1024:
+                    assert op["rays"] <= 2 and op["bounces"] <= 2, where
+            elif k == "refused":
+                refused += 1
+                assert 1 <= op["depth"] <= 3, where
+                if op["why"] == "scope":
+                    assert state.scope == "spheres" and (state.planes or state.cubes or state.mesh), where
+                    assert op["request"] == {}, where
+                else:
+                    assert op["why"] == "samples" and state.samples == "one" and state.reflect_ok(), where
+                    r = op["request"]
+                    assert r.get("spp", 1) > 1 or r.get("sample_base", 0) != 0 or r.get("sample_total", 0) > 1 \
+                        or r.get("accumulate"), where
+            elif k == "render":
+                assert (op["depth"] == 0 or state.reflect_ok()) and op["size"] in sw.SIZES, where
+                if op["depth"] and (op["spp"] > 1 or op["sample_total"] or op["split"]):
+                    assert state.samples == "many", where
+                if op["aov"]:
+                    assert op["spp"] == 1 and not op["sample_total"] and not op["split"], where
+            elif k == "pass":
+                if op["what"] == "render_upscaled" or op.get("depth"):
+                    assert state.reflect_ok(), where
+            elif k == "temporal" and op["mutation"] is not None:
+                after = sw.apply(state, op["mutation"])
+                assert (after.n, after.n_cubes) == (state.n, state.n_cubes) and after != state, where
+            elif k in ("plane_materials", "cube_materials") and op["seed"] is not None:
+                assert (state.n_planes if k == "plane_materials" else state.n_cubes) > 0, where
+            elif k == "materials" and op["mats"] is not None:
+                assert state.n > 0, where
+            elif k == "spheres":
+                assert op["spheres"][0] in sw.SPHERE_COUNTS, where
+            state = sw.apply(state, op)
+            # a table never outlives its list, nor has another length than it
+            for kind in sw.ROUGH_KINDS:
+                assert getattr(state, "rough_" + kind) is None or state.count_of(kind) > 0, where
+        assert 4 * refused <= outputs, (seed, refused, outputs)
+        refused_all += refused
+    assert refused_all >= 1
+
+
+def test_roughness_seed_and_model_follow_the_header():
+    """rt_engine.h, "Glossy reflections": a table follows its kind's k table -- it survives the list set with the same
+    count and is cleared by a different count; the material entries do not touch it. The gloss seed and the glass
+    model ("Fresnel glass") survive everything."""
+    s = sw.State(spheres=(64, 1, 0.0), planes=(2, 0), cubes=(5, 0), gloss_seed=5, glass_model="fresnel")
+    assert s.rough() == ()
+    for kind, seed in (("spheres", 3), ("planes", 4), ("cubes", 6)):
+        s = sw.apply(s, {"op": "roughness", "kind": kind, "how": "set", "seed": seed})
+    assert (s.rough_spheres, s.rough_planes, s.rough_cubes) == (3, 4, 6) and s.rough() == sw.ROUGH_KINDS
+    tables = lambda st: (st.rough_spheres, st.rough_planes, st.rough_cubes)
+    # the same count keeps the kind's table, another count clears that table only, and it does not come back
+    for kind, same, other, at in (("spheres", (64, 2, 0.5), (65, 1, 0.0), 0), ("planes", (2, 1), (1, 0), 1),
+                                  ("cubes", (5, 1), (4, 1), 2)):
+        kept = sw.apply(s, {"op": kind, kind: same})
+        assert tables(kept) == (3, 4, 6), kind
+        gone = sw.apply(kept, {"op": kind, kind: other})
+        assert tables(gone) == tuple(None if i == at else v for i, v in enumerate((3, 4, 6))), kind
+        back = sw.apply(gone, {"op": kind, kind: same})
+        assert tables(back) == tables(gone), kind
+        if kind != "spheres":                                      # the list removed: another count
+            assert tables(sw.apply(s, {"op": kind, kind: None}))[at] is None
+    assert sw.apply(s, {"op": "planes", "planes": True}).rough_planes == 4      # the first vocabulary's "on": 2 planes
+    # the k tables go with their lists as before, and with the roughness: one count change clears both
+    m = sw.apply(sw.apply(s, {"op": "materials", "mats": ("ex", 3)}), {"op": "cube_materials", "seed": 4})
+    gone = sw.apply(m, {"op": "spheres", "spheres": (63, 1, 0.0)})
+    assert (gone.mats, gone.rough_spheres, gone.cube_mats, gone.rough_cubes) == (None, None, 4, 6)
+    again = sw.apply(gone, {"op": "materials", "mats": ("ex", 3)})
+    assert again.rough_spheres is None                              # the materials set again: the roughness stays cleared
+    # the material entries do not touch a table; clearing one table leaves the others
+    for op in ({"op": "materials", "mats": ("k", 9)}, {"op": "materials", "mats": ("ex", 9)}, {"op": "materials", "mats": None},
+               {"op": "plane_materials", "seed": 2}, {"op": "plane_materials", "seed": None},
+               {"op": "cube_materials", "seed": 2}, {"op": "cube_materials", "seed": None}):
+        assert tables(sw.apply(m, op)) == (3, 4, 6), op
+    assert tables(sw.apply(s, {"op": "roughness", "kind": "planes", "how": "clear", "seed": None})) == (3, None, 6)
+    # the seed and the model survive every other op, outputs included
+    ops = [{"op": "spheres", "spheres": (8, 2, 0.0)}, {"op": "planes", "planes": None}, {"op": "cubes", "cubes": (4, 0)},
+           {"op": "mesh", "mesh": 2}, {"op": "materials", "mats": ("ex", 2)}, {"op": "materials", "mats": None},
+           {"op": "lights", "lights": sw.DEFAULT_LIGHTS[:1]}, {"op": "texture", "texture": 1},
+           {"op": "cube_materials", "seed": 3}, {"op": "plane_materials", "seed": None}, {"op": "tile_order", "tile_order": 0},
+           {"op": "scope", "scope": "scene"}, {"op": "samples", "samples": "many"}, {"op": "view_lists", "view_lists": 0},
+           {"op": "roughness", "kind": "cubes", "how": "set", "seed": 8},
+           {"op": "roughness", "kind": "spheres", "how": "clear", "seed": None},
+           {"op": "temporal", "mutation": {"op": "spheres", "spheres": (8, 2, 0.25)}}, {"op": "gather"}, {"op": "render"}]
+    t = s
+    for op in ops:
+        t = sw.apply(t, op)
+        assert (t.gloss_seed, t.glass_model) == (5, "fresnel"), op
+    assert sw.apply(t, {"op": "gloss_seed", "gloss_seed": 0xffffffff}).gloss_seed == 0xffffffff
+    u = sw.apply(t, {"op": "glass_model", "glass_model": "plain"})
+    assert (u.glass_model, u.gloss_seed) == ("plain", 5)
+    # the defaults leave a state of the first two vocabularies what it was
+    assert sw.State() == sw.State(rough_spheres=None, rough_planes=None, rough_cubes=None, gloss_seed=0, glass_model="plain")
+    # the helper: float32 out of ROUGHNESS, some primitives sharp and some rough
+    rho = sw.roughness(3, 64)
+    assert rho.dtype == np.float32 and (rho == 0).any() and (rho > 0).any() and rho.max() <= 1
+
+
+def test_gather_scratch_is_the_headers():
+    """rt_engine.h: variant 0 takes 256 bytes per pixel at four rays (576 with bounces > 1), 16 more per pixel with
+    more than 4 rays; the yardstick variant none."""
+    op = dict(size=(64, 36), shrink=1, rays=4, bounces=1, variant=0)
+    bytes_of = lambda need: 16 * (need[0] + need[1] + need[2] + need[3])
+    assert bytes_of(sw.gather_scratch(op)) == 256 * 64 * 36
+    assert bytes_of(sw.gather_scratch(dict(op, bounces=3))) == 576 * 64 * 36
+    assert bytes_of(sw.gather_scratch(dict(op, rays=9))) == (256 + 16) * 64 * 36
+    assert bytes_of(sw.gather_scratch(dict(op, rays=2, shrink=2))) == 128 * 32 * 18
+    assert sw.gather_scratch(dict(op, variant=1)) is None
