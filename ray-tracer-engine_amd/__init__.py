@@ -1428,20 +1428,26 @@ class Scene:
         modulate=False needs no albedo. None: the default of rt_indirect_desc_init. Returns {'rgba': float32
         [rows, W, 4], and with want_packed 'packed': int32 [rows, W]} as new tensors; no input is written. Enqueued on
         `stream` (default: the current stream)."""
+        return self._indirect("indirect", lambda d, st: _check(self.indirect_raw(d, st), "rt_scene_indirect"), frame, cam,
+                              aspect, colour, rays, ray_base, seed, strength, modulate, cull, variant, want_packed, stream)
+
+    def _indirect(self, name, call, frame, cam, aspect, colour, rays, ray_base, seed, strength, modulate, cull, variant,
+                  want_packed, stream):
+        """The body of indirect and indirect_paths: `name` is the method's, call(d, stream) runs its entry."""
         torch = self._need_gpu("the indirect pass")
         need = ("depth", "normal", "id") + (("albedo",) if modulate else ())
         aov = frame.get("aov") or {}
         if any(k not in aov for k in need):
-            raise RtError(f"indirect needs the G-buffer outputs {need}: render with aov={AOV_NAMES}")
+            raise RtError(f"{name} needs the G-buffer outputs {need}: render with aov={AOV_NAMES}")
         rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
         if isinstance(colour, str):
             if colour != "frame":
-                raise RtError('indirect: colour is "frame", None or a tensor')
+                raise RtError(f'{name}: colour is "frame", None or a tensor')
             colour = frame.get("rgba")
             if colour is None:
-                raise RtError('indirect: colour="frame" needs the frame\'s rgba (render with want_rgba=True)')
+                raise RtError(f'{name}: colour="frame" needs the frame\'s rgba (render with want_rgba=True)')
         if colour is not None:
-            colour = self._cuda_colour(torch, "indirect", colour, rows, width)
+            colour = self._cuda_colour(torch, name, colour, rows, width)
         like = aov["depth"]
         out = torch.empty((rows, width, 4), dtype=torch.float32, device=like.device)
         packed = self._new(torch, want_packed, like, (rows, width), torch.int32)
@@ -1451,7 +1457,7 @@ class Scene:
                                albedo=aov["albedo"].data_ptr() if modulate else 0, rgba_in=self._ptr(colour),
                                rgba_out=out.data_ptr(), pixels=self._ptr(packed), rays=rays, ray_base=ray_base, seed=seed,
                                strength=strength, cull=1 if cull else 0, variant=variant)
-        _check(self.indirect_raw(d, st.cuda_stream), "rt_scene_indirect")
+        call(d, st.cuda_stream)
         res = {"rgba": out}
         if want_packed:
             res["packed"] = packed
@@ -1468,9 +1474,12 @@ class Scene:
     def indirect_counts(self):
         """The queue lengths of the last variant-0 indirect call (waits for it), one per group of rays: the gather rays
         that hit something."""
-        cnt = (C.c_int * 4)()
+        return self._indirect_counts("rt_debug_indirect_counts", 4)
+
+    def _indirect_counts(self, fn, cap):
+        cnt = (C.c_int * cap)()
         n = C.c_int()
-        _check(self.lib.rt_debug_indirect_counts(self.handle, cnt, 4, C.byref(n)), "rt_debug_indirect_counts")
+        _check(getattr(self.lib, fn)(self.handle, cnt, cap, C.byref(n)), fn)
         return list(cnt)[: n.value]
 
     # ---------------------------------------------------------------- multi-bounce global illumination (DESIGN.md 6p)
@@ -1489,46 +1498,19 @@ class Scene:
         RT_INDIRECT_MAX_BOUNCES; None: the default of rt_indirect_paths_opts_init, 2): a hit lit directly spawns the
         next cosine-distributed ray with the hit's texel as its weight. Every other keyword as indirect's, the same
         dict returned; bounces=1 is indirect itself, launch for launch."""
-        torch = self._need_gpu("the indirect pass")
-        need = ("depth", "normal", "id") + (("albedo",) if modulate else ())
-        aov = frame.get("aov") or {}
-        if any(k not in aov for k in need):
-            raise RtError(f"indirect_paths needs the G-buffer outputs {need}: render with aov={AOV_NAMES}")
-        rows, width = aov["depth"].shape[0], aov["depth"].shape[1]
-        if isinstance(colour, str):
-            if colour != "frame":
-                raise RtError('indirect_paths: colour is "frame", None or a tensor')
-            colour = frame.get("rgba")
-            if colour is None:
-                raise RtError('indirect_paths: colour="frame" needs the frame\'s rgba (render with want_rgba=True)')
-        if colour is not None:
-            colour = self._cuda_colour(torch, "indirect_paths", colour, rows, width)
-        like = aov["depth"]
-        out = torch.empty((rows, width, 4), dtype=torch.float32, device=like.device)
-        packed = self._new(torch, want_packed, like, (rows, width), torch.int32)
-        st = self._stream(torch, stream)
-        d = self.indirect_desc(width, rows, cam=cam, aspect=aspect, depth=aov["depth"].data_ptr(),
-                               normal=aov["normal"].data_ptr(), id=aov["id"].data_ptr(),
-                               albedo=aov["albedo"].data_ptr() if modulate else 0, rgba_in=self._ptr(colour),
-                               rgba_out=out.data_ptr(), pixels=self._ptr(packed), rays=rays, ray_base=ray_base, seed=seed,
-                               strength=strength, cull=1 if cull else 0, variant=variant)
-        _check(self.indirect_paths_raw(d, self.indirect_paths_opts(bounces), st.cuda_stream), "rt_scene_indirect_paths")
-        res = {"rgba": out}
-        if want_packed:
-            res["packed"] = packed
-        return res
+        def call(d, st):
+            _check(self.indirect_paths_raw(d, self.indirect_paths_opts(bounces), st), "rt_scene_indirect_paths")
+        return self._indirect("indirect_paths", call, frame, cam, aspect, colour, rays, ray_base, seed, strength, modulate,
+                              cull, variant, want_packed, stream)
 
     def indirect_path_counts(self):
         """The queue lengths of the last variant-0 indirect_paths call with bounces > 1 (waits for it): per group of
         rays a list with, per bounce, the paths that entered its shade pass. [] after any other indirect call."""
-        cap = ((RT_INDIRECT_MAX_RAYS + 3) // 4) * RT_INDIRECT_MAX_BOUNCES
-        cnt = (C.c_int * cap)()
-        n = C.c_int()
-        _check(self.lib.rt_debug_indirect_path_counts(self.handle, cnt, cap, C.byref(n)), "rt_debug_indirect_path_counts")
+        cnt = self._indirect_counts("rt_debug_indirect_path_counts", ((RT_INDIRECT_MAX_RAYS + 3) // 4) * RT_INDIRECT_MAX_BOUNCES)
         b = getattr(self, "_paths_bounces", 0)    # the C entry reports counts[group * bounces + b]
-        if n.value == 0 or b < 1 or n.value % b:
+        if not cnt or b < 1 or len(cnt) % b:
             return []
-        return [list(cnt)[g:g + b] for g in range(0, n.value, b)]
+        return [cnt[g:g + b] for g in range(0, len(cnt), b)]
 
     def indirect_paths_times(self):
         """Device ms of every launch of the last timed indirect or indirect_paths call (set_indirect_timing; waits for

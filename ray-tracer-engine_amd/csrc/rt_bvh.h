@@ -183,6 +183,21 @@ struct LdsStack {
     __device__ int &operator()(int i) const { return base[i * RT_BVH_BLOCK + tid]; }
 };
 
+// Append the wave's lanes with `push` set to a queue whose length is *count (one atomic per wave, the first such
+// lane's): returns the lane's index in the queue, 0 without `push`. The ballot and the readlane are the wave's: every
+// lane of the wave reaches the call, and in a loop a lane without an entry is switched off by its flag, never by
+// leaving the loop.
+__device__ __forceinline__ int rf_wave_append(bool push, int *count)
+{
+    const lmask m = ballot64(push);
+    if (m == 0) return 0;
+    const int leader = __builtin_ctzll(m);
+    int b = 0;
+    if ((int)(threadIdx.x & 63u) == leader) b = atomicAdd(count, __popcll(m));
+    const int base = __builtin_amdgcn_readlane(b, leader);
+    return push ? base + lane_prefix(m) : 0;
+}
+
 // skybox::getFColor, kernel.cu:1147-1166, as the frame kernel's brute-force instantiation evaluates it
 __device__ __forceinline__ void rf_sky(AuxPtr ax, V3 O, V3 D, float &r, float &g, float &b)
 {

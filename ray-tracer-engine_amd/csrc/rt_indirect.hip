@@ -1,32 +1,29 @@
-// rt_indirect.hip -- one-bounce global illumination (rt_scene_indirect): a hashed diffuse gather pass.
+// rt_indirect.hip -- global illumination (rt_scene_indirect; rt_scene_indirect_paths, 6p): a hashed
+// diffuse gather pass with a bounce budget.
 //
 // Every surface pixel of a frame's G-buffer casts `rays` cosine-distributed gather rays from its surface point; each
-// is shaded exactly as a RT_QUERY_SHADE ray (rt_query.hip): direct light at what it hits through the casts of
-// rt_cast.h, getFColor on a miss. Their mean times the pixel's albedo is added to the frame's colour.
+// is a diffuse path of at most `bounces` shaded hits. A hit is shaded exactly as a RT_QUERY_SHADE ray (rt_query.hip):
+// direct light through the casts of rt_cast.h; a miss is getFColor and ends the path. Unless the budget is spent, a hit
+// spawns the next ray with the hit's texel in its throughput. The mean of the paths times the pixel's albedo is added
+// to the frame's colour. bounces == 1 is rt_scene_indirect: the path is the gather ray.
 //
 // Two implementations, the same bits:
-//   plain       one thread per pixel, 256-thread workgroups, loops over the rays: q_nearest, q_hit_record, then
-//               q_shade_hit or rf_sky, and the sum, the albedo and the outputs in the same thread;
-//   wavefront   per group of at most RT_INDIRECT_GROUP rays three passes in the shape of the reflective passes:
+//   plain       one thread per pixel, 256-thread workgroups: a loop over the rays, in it the loop over the bounces
+//               (q_nearest, q_hit_record, then q_shade_hit or rf_sky), then the sum, the albedo and the outputs;
+//   wavefront   per group of at most RT_INDIRECT_GROUP rays, in the shape of the reflective passes:
 //     cast      over the group's (pixel, ray) slots: forms the ray and finds its nearest hit; a miss writes its sky
-//               colour to the slot of a slab, a hit is ballot-compacted into a queue (one atomic per wave);
-//     shade     a fixed grid over the queue, whose length it reads on the device: full waves of hits, each shaded and
-//               written to its slot;
+//               colour to the slot of a slab, a hit is appended to queue 0 (one atomic per wave);
+//     shade     once per bounce b, a fixed grid over queue b, whose length it reads on the device: shades the entry,
+//               adds the term to the entry's slot (one writer per slot and pass: the order of the sum is the order of
+//               the launches) and -- unless b is the last -- forms the next ray and casts it: a miss adds throughput x
+//               sky to the slot at once, a hit is appended to queue b + 1 with its throughput and key. Two buffers
+//               ping-pong; a pass pushes at most one entry per entry it read, so no queue outgrows the group's slots;
 //     resolve   per pixel: the earlier groups' running sum plus the group's slots in ascending ray order, and -- the
 //               last group -- the mean, the albedo and the outputs. Dead pixels are written here.
-//   No float atomics: the order of the sum is the slab's. The queue holds as many entries as the group has slots.
-// Which of the two rt_indirect_desc.variant 0 names is kIndirectWavefrontIsProduct below, by the measurement of
-// DESIGN.md 6o. The brute-force variant (cull = 0) is the same kernels with the BVH replaced by the whole sphere list.
-//
-// Paths (rt_scene_indirect_paths with bounces > 1): a gather ray's hit spawns the next ray with a
-// throughput. Again two implementations, the same bits:
-//   plain       rt_indirect_paths_plain: the plain kernel with the loop over the bounces inside the loop over the rays;
-//   wavefront   per group the cast pass as it is (queue 0), then per bounce b one shade-and-continue pass over queue b
-//               on the shade pass's fixed grid: it shades the entry, adds the term to the entry's slot of the slab
-//               (one writer per slot and pass: the order of the sum is the order of the launches) and -- unless b is
-//               the last -- forms the next ray and casts it: a miss adds throughput x sky to the slot at once, a hit is
-//               ballot-compacted into queue b + 1 with its throughput and key. Two queues ping-pong; a pass pushes at
-//               most one entry per entry it read, so no queue outgrows the group's slots. Then the resolve pass as it is.
+//   No float atomics: the order of the sum is the slab's.
+// Which of the two rt_indirect_desc.variant 0 names is kIndirectWavefrontIsProduct (bounces == 1, the measurement of
+// DESIGN.md 6o) or kIndirectPathsWavefrontIsProduct (bounces > 1, that of 6p) below. The brute-force variant (cull = 0)
+// is the same kernels with the BVH replaced by the whole sphere list.
 #include "rt_cast.h"
 
 #include <algorithm>
@@ -91,37 +88,47 @@ namespace {
 
 __device__ __forceinline__ bool ind_finite(float v) { return __builtin_fabsf(v) <= 3.4028234663852886e38f; }   // NaN: false
 
-// Steps 1 and 2 for pixel p: false if it is dead; else its normal and the start of its gather rays
-__device__ __forceinline__ bool ind_pixel(const RtFrameConsts &fc, const RtIndirectDev &d, int p, V3 &n, V3 &start)
+// Step 1 for pixel p, the one statement of the dead-pixel rule: false if it is dead; else `live` gets its depth and
+// normal as the G-buffer holds them. (A continuation, not a flag handed back with the values: the rule stays one branch
+// at the head of its caller, and the plain kernels keep their registers to the digit.)
+template <class F>
+__device__ __forceinline__ bool ind_if_live(const RtIndirectDev &d, int p, F live)
 {
     const int kind = d.id[p].x;
     const float depth = d.depth[p];
     const float4 ng = d.normal[p];
     const float nn = (ng.x * ng.x + ng.y * ng.y) + ng.z * ng.z;
     if (kind < 0 || !ind_finite(depth) || nn == 0.f || !ind_finite(nn)) return false;
-    const V3 D = rf_primary_dir(fc, p);
-    const V3 P{fc.org_x + D.x * depth, fc.org_y + D.y * depth, fc.org_z + D.z * depth};
-    n = V3{ng.x, ng.y, ng.z};
-    rf_normalise(n);
-    if ((n.x * D.x + n.y * D.y) + n.z * D.z > 0.f) n = V3{-n.x, -n.y, -n.z};
-    start = V3{n.x * 0.00001f + P.x, n.y * 0.00001f + P.y, n.z * 0.00001f + P.z};
+    live(depth, ng);
     return true;
 }
 
-// The direction of ray j (counted from the call's first) of pixel p
-__device__ __forceinline__ V3 ind_ray_dir(const RtFrameConsts &fc, const RtIndirectDev &d, int p, int j, V3 n)
+// Steps 1 and 2 for pixel p: false if it is dead; else its normal and the start of its gather rays
+__device__ __forceinline__ bool ind_pixel(const RtFrameConsts &fc, const RtIndirectDev &d, int p, V3 &n, V3 &start)
 {
-    const int y = p / fc.width, x = p - y * fc.width;
-    V3 G;
-    rf_indirect_dir(n, rf_gloss_key((uint32_t)x, (uint32_t)y, (uint32_t)(d.ray_base + j), d.seed), G);
-    return G;
+    return ind_if_live(d, p, [&](float depth, float4 ng) {
+        const V3 D = rf_primary_dir(fc, p);
+        const V3 P{fc.org_x + D.x * depth, fc.org_y + D.y * depth, fc.org_z + D.z * depth};
+        n = V3{ng.x, ng.y, ng.z};
+        rf_normalise(n);
+        if ((n.x * D.x + n.y * D.y) + n.z * D.z > 0.f) n = V3{-n.x, -n.y, -n.z};
+        start = V3{n.x * 0.00001f + P.x, n.y * 0.00001f + P.y, n.z * 0.00001f + P.z};
+    });
 }
 
-// key_0 of the path that ray j of pixel p starts: the key of ind_ray_dir
+// key_0 of the path that ray j (counted from the call's first) of pixel p starts
 __device__ __forceinline__ uint32_t ind_ray_key(const RtFrameConsts &fc, const RtIndirectDev &d, int p, int j)
 {
     const int y = p / fc.width, x = p - y * fc.width;
     return rf_gloss_key((uint32_t)x, (uint32_t)y, (uint32_t)(d.ray_base + j), d.seed);
+}
+
+// The direction of that ray: step 3 under its key
+__device__ __forceinline__ V3 ind_ray_dir(const RtFrameConsts &fc, const RtIndirectDev &d, int p, int j, V3 n)
+{
+    V3 G;
+    rf_indirect_dir(n, ind_ray_key(fc, d, p, j), G);
+    return G;
 }
 
 // Step (g) of a path at the hit h of ray(O, D) under `key`: false if the hit's normal is dead; else O, D and key become
@@ -173,44 +180,13 @@ __device__ __forceinline__ void ind_finish(const RtIndirectDev &d, int p, float 
     ind_store(d, p, c);
 }
 
-// The plain kernel: everything for pixel p in one thread
+// The plain kernel: everything for pixel p in one thread, per ray the loop of DESIGN.md 6p. ONE: the budget is the
+// constant 1 and the loop over the bounces a single trip (6o's sr = sr + (0.f + fr))
+template <bool ONE>
 __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_plain(const RtFrameConsts fc, const RtReflectDev rd,
-                                                                     const RtIndirectDev d)
+                                                                     const RtIndirectDev d, int budget)
 {
-    __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
-    const LdsStack stk{stack_lds, (int)threadIdx.x};
-    const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;
-    const int p = (int)(blockIdx.x * RT_INDIRECT_BLOCK + threadIdx.x);
-    if (p >= fc.width * fc.height) return;
-    V3 n, start;
-    if (!ind_pixel(fc, d, p, n, start)) {
-        ind_store_dead(d, p);
-        return;
-    }
-    float sr = 0.f, sg = 0.f, sb = 0.f;
-#pragma unroll 1
-    for (int j = 0; j < d.rays; ++j) {
-        const V3 G = ind_ray_dir(fc, d, p, j, n);
-        int kind, pos;
-        const float nt = q_nearest(fc, ax, rd, start, G, stk, kind, pos);
-        float fr, fg, fb;
-        if (kind >= 0) {
-            const rt_hit h = q_hit_record(fc, ax, rd, start, G, nt, kind, pos);
-            q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
-        } else {
-            rf_sky(ax, start, G, fr, fg, fb);
-        }
-        sr = sr + (0.f + fr);   // (what RT_QUERY_SHADE stores for the ray: the sum over one sample starts at 0)
-        sg = sg + (0.f + fg);
-        sb = sb + (0.f + fb);
-    }
-    ind_finish(d, p, sr, sg, sb);
-}
-
-// The plain kernel of a call with bounces > 1: per ray the loop of DESIGN.md 6p
-__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_paths_plain(const RtFrameConsts fc, const RtReflectDev rd,
-                                                                           const RtIndirectDev d, int bounces)
-{
+    const int bounces = ONE ? 1 : budget;
     __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
     const LdsStack stk{stack_lds, (int)threadIdx.x};
     const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;
@@ -291,51 +267,25 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_cast(const RtFr
             }
         }
     }
-    // append the wave's hits (one atomic per wave; every lane of the wave is here)
-    const lmask m = ballot64(push);
-    if (m == 0) return;
-    const int leader = __builtin_ctzll(m);
-    int b = 0;
-    if ((int)(threadIdx.x & 63u) == leader) b = atomicAdd(count, __popcll(m));
-    const int base = __builtin_amdgcn_readlane(b, leader);
+    const int at = rf_wave_append(push, count);   // (every lane of the wave is here)
     if (push) {
-        float4 *e = queue + (size_t)RT_INDIRECT_ENTRY_F4 * (size_t)(base + lane_prefix(m));
+        float4 *e = queue + (size_t)RT_INDIRECT_ENTRY_F4 * (size_t)at;
         e[0] = make_float4(start.x, start.y, start.z, nt);
         e[1] = make_float4(G.x, G.y, G.z, __int_as_float(kind));
         e[2] = make_float4(__int_as_float(pos), __int_as_float(i), 0.f, 0.f);
     }
 }
 
-// The shade pass: a fixed grid walks the queue, whose length is read here, on the device
-__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_shade(const RtFrameConsts fc, const RtReflectDev rd,
-                                                                     const float4 *queue, const int *count, float4 *slab)
-{
-    __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
-    const LdsStack stk{stack_lds, (int)threadIdx.x};
-    const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;
-    const int n_in = *count;
-    for (int base = (int)blockIdx.x * RT_INDIRECT_BLOCK; base < n_in; base += (int)gridDim.x * RT_INDIRECT_BLOCK) {
-        const int i = base + (int)threadIdx.x;
-        if (i >= n_in) continue;
-        const float4 *e = queue + (size_t)RT_INDIRECT_ENTRY_F4 * (size_t)i;
-        const float4 e0 = e[0], e1 = e[1], e2 = e[2];
-        const V3 O{e0.x, e0.y, e0.z}, D{e1.x, e1.y, e1.z};
-        const rt_hit h = q_hit_record(fc, ax, rd, O, D, e0.w, __float_as_int(e1.w), __float_as_int(e2.x));
-        float fr, fg, fb;
-        q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
-        slab[__float_as_int(e2.y)] = make_float4(0.f + fr, 0.f + fg, 0.f + fb, 0.f);
-    }
-}
-
-// The shade-and-continue pass of bounce b over queue b: a fixed grid, the queue's length read here.
+// The shade pass of bounce b over queue b: a fixed grid, the queue's length read here, on the device.
 // FIRST: b == 0, the entries are the cast pass's (no throughput; the key is the slot's); LAST: b == bounces - 1, nothing
-// continues. Every lane of a wave makes every trip of the loop (its bounds are uniform) and reaches the ballot: a lane
-// without an entry is inactive by `act`, never by leaving.
+// continues (q_out and count_out are null). <true, true> is the shade pass of DESIGN.md 6o. Every lane of a wave makes
+// every trip of the loop (its bounds are uniform) and reaches rf_wave_append: a lane without an entry is inactive by
+// `act`, never by leaving.
 template <bool FIRST, bool LAST>
-__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_paths_pass(const RtFrameConsts fc, const RtReflectDev rd,
-                                                                          const RtIndirectDev d, int j0, const float4 *q_in,
-                                                                          const int *count_in, float4 *q_out, int *count_out,
-                                                                          float4 *slab)
+__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_shade(const RtFrameConsts fc, const RtReflectDev rd,
+                                                                     const RtIndirectDev d, int j0, const float4 *q_in,
+                                                                     const int *count_in, float4 *q_out, int *count_out,
+                                                                     float4 *slab)
 {
     __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
     const LdsStack stk{stack_lds, (int)threadIdx.x};
@@ -390,20 +340,14 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_paths_pass(cons
             }
             slab[slot] = make_float4(lr, lg, lb, 0.f);
         }
-        if (!LAST) {   // append the wave's continuing paths (one atomic per wave; every lane of the wave is here)
-            const lmask m = ballot64(push);
-            if (m != 0) {
-                const int leader = __builtin_ctzll(m);
-                int b = 0;
-                if ((int)(threadIdx.x & 63u) == leader) b = atomicAdd(count_out, __popcll(m));
-                const int at = __builtin_amdgcn_readlane(b, leader);
-                if (push) {
-                    float4 *o = q_out + (size_t)RT_INDIRECT_PATH_ENTRY_F4 * (size_t)(at + lane_prefix(m));
-                    o[0] = make_float4(O.x, O.y, O.z, nt);
-                    o[1] = make_float4(D.x, D.y, D.z, __int_as_float(kind));
-                    o[2] = make_float4(__int_as_float(pos), __int_as_float(slot), 0.f, 0.f);
-                    o[3] = make_float4(tr, tg, tb, __int_as_float((int)key));
-                }
+        if (!LAST) {   // append the wave's continuing paths
+            const int at = rf_wave_append(push, count_out);
+            if (push) {
+                float4 *o = q_out + (size_t)RT_INDIRECT_PATH_ENTRY_F4 * (size_t)at;
+                o[0] = make_float4(O.x, O.y, O.z, nt);
+                o[1] = make_float4(D.x, D.y, D.z, __int_as_float(kind));
+                o[2] = make_float4(__int_as_float(pos), __int_as_float(slot), 0.f, 0.f);
+                o[3] = make_float4(tr, tg, tb, __int_as_float((int)key));
             }
         }
     }
@@ -416,10 +360,7 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_resolve(const R
 {
     const int p = (int)(blockIdx.x * RT_INDIRECT_BLOCK + threadIdx.x);
     if (p >= npx) return;
-    const float depth = d.depth[p];
-    const float4 ng = d.normal[p];
-    const float nn = (ng.x * ng.x + ng.y * ng.y) + ng.z * ng.z;
-    if (d.id[p].x < 0 || !ind_finite(depth) || nn == 0.f || !ind_finite(nn)) {   // dead, as ind_pixel
+    if (!ind_if_live(d, p, [](float, float4) {})) {
         if (last) ind_store_dead(d, p);
         return;
     }
@@ -469,8 +410,8 @@ int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameCons
     *n_ev = 0;
     RT_HIP(mark());
     if (!rt_indirect_wavefront(d->variant, bounces)) {
-        if (bounces > 1) hipLaunchKernelGGL(rt_indirect_paths_plain, px_grid, block, 0, stream, *fc, rd, dd, bounces);
-        else hipLaunchKernelGGL(rt_indirect_plain, px_grid, block, 0, stream, *fc, rd, dd);
+        hipLaunchKernelGGL(bounces == 1 ? rt_indirect_plain<true> : rt_indirect_plain<false>, px_grid, block, 0, stream, *fc, rd,
+                           dd, bounces);
         RT_HIP(hipGetLastError());
         RT_HIP(mark());
         *n_ev = marks;
@@ -487,23 +428,14 @@ int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameCons
                            scratch->queue, count);
         RT_HIP(hipGetLastError());
         RT_HIP(mark());
-        if (bounces == 1) {
-            hipLaunchKernelGGL(rt_indirect_shade, shade_grid, block, 0, stream, *fc, rd, scratch->queue, count, scratch->slab);
-            RT_HIP(hipGetLastError());
-            RT_HIP(mark());
-        }
-        for (int b = 0; bounces > 1 && b < bounces; ++b) {   // queue b -> queue b + 1: the two buffers in turn
+        for (int b = 0; b < bounces; ++b) {   // queue b -> queue b + 1: the two buffers in turn
+            const bool first = b == 0, last = b == bounces - 1;
             const float4 *q_in = (b & 1) ? scratch->queue2 : scratch->queue;
-            float4 *q_out = (b & 1) ? scratch->queue : scratch->queue2;
-            if (b == 0)
-                hipLaunchKernelGGL((rt_indirect_paths_pass<true, false>), shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in,
-                                   count, q_out, count + 1, scratch->slab);
-            else if (b < bounces - 1)
-                hipLaunchKernelGGL((rt_indirect_paths_pass<false, false>), shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in,
-                                   count + b, q_out, count + b + 1, scratch->slab);
-            else
-                hipLaunchKernelGGL((rt_indirect_paths_pass<false, true>), shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in,
-                                   count + b, (float4 *)nullptr, (int *)nullptr, scratch->slab);
+            float4 *q_out = last ? nullptr : (b & 1) ? scratch->queue : scratch->queue2;
+            const auto shade = first ? (last ? rt_indirect_shade<true, true> : rt_indirect_shade<true, false>)
+                                     : (last ? rt_indirect_shade<false, true> : rt_indirect_shade<false, false>);
+            hipLaunchKernelGGL(shade, shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in, count + b, q_out,
+                               last ? nullptr : count + b + 1, scratch->slab);
             RT_HIP(hipGetLastError());
             RT_HIP(mark());
         }

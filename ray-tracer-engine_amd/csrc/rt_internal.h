@@ -255,21 +255,20 @@ int rt_temporal_launch(const rt_tmotion_desc *d, const float *dx_tab, const floa
 // rt_upsample.hip: guided upsampling (d: validated, in this build's layout; ev: null, or two timing events)
 int rt_upsample_launch(const rt_upsample_desc *d, hipEvent_t *ev, hipStream_t stream);
 
-// rt_indirect.hip: the indirect pass. The product's scratch, all the scene's: per slot of a group of at
-// most RT_INDIRECT_GROUP rays a colour (slab) and a queue entry of RT_INDIRECT_ENTRY_F4 float4, a running sum per pixel
-// when there are several groups, and a counter per group.
+// rt_indirect.hip: the indirect pass. The product's scratch, all the scene's: per slot of a group of
+// at most RT_INDIRECT_GROUP rays a colour (slab) and a queue entry, a running sum per pixel when there are several
+// groups, and a counter per (group, bounce). Queue 0's entries are RT_INDIRECT_ENTRY_F4 float4; those of the later
+// queues (bounces > 1) carry the throughput and the key in a fourth, and two buffers of that width ping-pong.
 #define RT_INDIRECT_GROUP 4
 #define RT_INDIRECT_MAX_GROUPS ((RT_INDIRECT_MAX_RAYS + RT_INDIRECT_GROUP - 1) / RT_INDIRECT_GROUP)
 #define RT_INDIRECT_ENTRY_F4 3
-// Paths (rt_scene_indirect_paths with bounces > 1): the entries of the queues after the first carry the
-// throughput and the key in a fourth float4; two queues of that width ping-pong, and there is a counter per (group, bounce).
 #define RT_INDIRECT_PATH_ENTRY_F4 4
 #define RT_INDIRECT_MAX_COUNTS (RT_INDIRECT_MAX_GROUPS * RT_INDIRECT_MAX_BOUNCES)
 #define RT_INDIRECT_MAX_EVENTS (1 + (2 + RT_INDIRECT_MAX_BOUNCES) * RT_INDIRECT_MAX_GROUPS)
 struct RtIndirectScratch {
     float4 *slab, *queue, *sum;
     int *count;
-    float4 *queue2;   // paths only
+    float4 *queue2;   // bounces > 1 only
 };
 // whether `variant` runs the wavefront passes (and needs the scratch) in a call of `bounces`
 bool rt_indirect_wavefront(int variant, int bounces = 1);

@@ -251,7 +251,8 @@ __host__ __device__ __forceinline__ int rf_fresnel_continue(bool glass, V3 D, V3
 // ---------------------------------------------------------------------------
 namespace {
 
-// Append the lanes with `push` set to the queue (one atomic per wave). Every lane of the wave calls it.
+// Append the lanes with `push` set to the queue (one atomic per wave). Every lane of the wave calls it. (The sequence of
+// rf_wave_append, rt_bvh.h, written out: through the helper four bounce kernels spill 2 to 4 more scalar registers.)
 __device__ __forceinline__ void rf_push(bool push, const QEntry &e, QEntry *q, int *count)
 {
     const lmask m = ballot64(push);

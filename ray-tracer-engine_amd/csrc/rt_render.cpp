@@ -1033,7 +1033,7 @@ extern "C" int rt_scene_upsample_times(rt_scene *s, float *ms, int cap, int *n)
 }
 
 // ---------------------------------------------------------------------------
-// one-bounce global illumination (rt_indirect.hip)
+// global illumination with a bounce budget (rt_indirect.hip)
 // ---------------------------------------------------------------------------
 extern "C" void rt_indirect_desc_init(rt_indirect_desc *d)
 {
@@ -1169,8 +1169,8 @@ static int indirect_call(rt_scene *s, const rt_indirect_desc *d_in, int bounces,
     RT_HIP(s->ind_done.record(stream));
     if (rc != RT_OK) return rc;
     if (s->ind_timing) s->ind_timed = n_ev;
-    s->ind_groups = wavefront && bounces == 1 ? groups : 0;
-    s->ind_path_counts = wavefront && bounces > 1 ? groups * bounces : 0;
+    s->ind_counts = wavefront ? groups * bounces : 0;
+    s->ind_bounces = bounces;
     return rt_scene_note_launch(s, stream, nullptr, nullptr);   // the pass in flight counts as a frame
 }
 
@@ -1212,28 +1212,26 @@ extern "C" int rt_scene_indirect_times(rt_scene *s, float *ms, int cap, int *n)
     return pass_times(s, "rt_scene_indirect_times", &rt_scene::ind_done, s ? s->ind_ev : nullptr, s ? s->ind_timed : 0, ms, cap, n);
 }
 
-extern "C" int rt_debug_indirect_counts(rt_scene *s, int *counts, int cap, int *n)
+// The last call's counters, if it was of the entry's kind (paths: bounces > 1); else none
+static int indirect_counts(rt_scene *s, const char *name, bool paths, int *counts, int cap, int *n)
 {
     if (!s || !counts || !n || cap < 0) {
-        rt_set_error("rt_debug_indirect_counts: null argument");
+        rt_set_error("%s: null argument", name);
         return RT_ERR_INVALID;
     }
-    *n = std::min(cap, s->ind_groups);
+    *n = (s->ind_bounces > 1) == paths ? std::min(cap, s->ind_counts) : 0;
     if (*n == 0) return RT_OK;
     RT_HIP(s->ind_done.host_wait());
     RT_HIP(hipMemcpy(counts, s->ind_count.get(), sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
+extern "C" int rt_debug_indirect_counts(rt_scene *s, int *counts, int cap, int *n)
+{
+    return indirect_counts(s, "rt_debug_indirect_counts", false, counts, cap, n);
+}
+
 extern "C" int rt_debug_indirect_path_counts(rt_scene *s, int *counts, int cap, int *n)
 {
-    if (!s || !counts || !n || cap < 0) {
-        rt_set_error("rt_debug_indirect_path_counts: null argument");
-        return RT_ERR_INVALID;
-    }
-    *n = std::min(cap, s->ind_path_counts);
-    if (*n == 0) return RT_OK;
-    RT_HIP(s->ind_done.host_wait());
-    RT_HIP(hipMemcpy(counts, s->ind_count.get(), sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return indirect_counts(s, "rt_debug_indirect_path_counts", true, counts, cap, n);
 }

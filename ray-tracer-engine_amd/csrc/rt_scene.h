@@ -196,9 +196,8 @@ struct rt_scene {
     float ind_aspect = 0.f;
     DevArray<float4> ind_slab, ind_queue, ind_sum;
     DevArray<int> ind_count;
-    DevArray<float4> ind_queue2;                     // paths (bounces > 1): the second of the two queues
-    int ind_groups = 0;                              // groups of the last variant-0 call (rt_debug_indirect_counts)
-    int ind_path_counts = 0;                         // groups * bounces of the last wavefront call with bounces > 1
+    DevArray<float4> ind_queue2;                     // bounces > 1: the second of the two queues
+    int ind_counts = 0, ind_bounces = 1;             // the last call's counters (groups * bounces; plain: 0) and bounces
     HipPendingEvent ind_done;
     HipEvent ind_ev[RT_INDIRECT_MAX_EVENTS];         // rt_scene_set_indirect_timing
     bool ind_timing = false;

@@ -311,6 +311,24 @@ def test_tails_and_empty_queues(rt, gpu, w, h):
         b = _paths(sc, room, frame, bounces=3, rays=rays, variant=1)
         torch.cuda.synchronize()
         G1._same_outputs(a, b, (w, h, rays))
+        # two bounces: the first shade pass runs straight into the last, no middle pass
+        a = _paths(sc, room, frame, bounces=2, rays=rays, variant=0)
+        assert sc.indirect_path_counts() == [[min(4, rays - j0) * w * h] * 2 for j0 in range(0, rays, 4)]
+        b = _paths(sc, room, frame, bounces=2, rays=rays, variant=1)
+        torch.cuda.synchronize()
+        G1._same_outputs(a, b, (w, h, rays, 2))
+        # one bounce: the only shade pass is first and last at once; both entries, both variants
+        a = _paths(sc, room, frame, bounces=1, rays=rays, variant=0)
+        assert sc.indirect_counts() == [min(4, rays - j0) * w * h for j0 in range(0, rays, 4)]
+        assert sc.indirect_path_counts() == []
+        b = _paths(sc, room, frame, bounces=1, rays=rays, variant=1)
+        c = G1._call(sc, room, frame, rays=rays, variant=0)
+        assert sc.indirect_counts() == [min(4, rays - j0) * w * h for j0 in range(0, rays, 4)]
+        assert sc.indirect_path_counts() == []
+        d = G1._call(sc, room, frame, rays=rays, variant=1)
+        torch.cuda.synchronize()
+        for other, what in ((b, "variants"), (c, "entries"), (d, "entries and variants")):
+            G1._same_outputs(a, other, (w, h, rays, 1, what))
     # a sky-only view: nothing is cast at any bounce, the output is the input
     inp = Inputs(rt, 8)
     sky = inp.scene()
@@ -323,6 +341,20 @@ def test_tails_and_empty_queues(rt, gpu, w, h):
         assert np.array_equal(P.tensor_bits(out["rgba"]), P.tensor_bits(frame["rgba"]))
         if variant == 0:
             assert sky.indirect_path_counts() == [[0, 0, 0]]
+    for bounces in (2, 1):
+        for variant, passes in ((0, 2 + bounces), (1, 1)):
+            outs = [_paths(sky, inp, frame, bounces=bounces, variant=variant)]
+            assert len(sky.indirect_paths_times()) == passes
+            if variant == 0:
+                assert sky.indirect_path_counts() == ([[0, 0]] if bounces == 2 else [])
+                assert sky.indirect_counts() == ([] if bounces == 2 else [0])
+            if bounces == 1:
+                outs.append(G1._call(sky, inp, frame, variant=variant))
+                assert len(sky.indirect_times()) == passes
+                if variant == 0:
+                    assert sky.indirect_counts() == [0] and sky.indirect_path_counts() == []
+            for out in outs:
+                assert np.array_equal(P.tensor_bits(out["rgba"]), P.tensor_bits(frame["rgba"]))
 
 
 def test_every_output_element_is_written(rt, gpu):

@@ -24,41 +24,67 @@ from _settle import settle
 from _timing import time_ms, timed
 
 ALL = ("depth", "normal", "id", "albedo")
+CALL = "call_ms_rounds: hipEvent ms per call of --iters calls, the two variants alternating per round (settled clocks); "
 
 
-def indirect_cases(rt, scene, w, h, iters, rounds):
-    st = torch.cuda.current_stream().cuda_stream
-    frame = scene.render(w, h, aov=ALL)
-    a = frame["aov"]
-    out = torch.empty_like(frame["rgba"])
-    packed = torch.empty_like(frame["packed"])
-    dead = float((a["id"][..., 0] < 0).float().mean())
-    res = {"dead_pixel_share": dead, "live_pixels": int((a["id"][..., 0] >= 0).sum())}
+class View:
+    """A frame of `scene` with its guides, the outputs of the calls on it, and the steps that make one call."""
+
+    def __init__(self, rt, scene, w, h):
+        self.rt, self.scene, self.w, self.h = rt, scene, w, h
+        self.st = torch.cuda.current_stream().cuda_stream
+        self.frame = scene.render(w, h, aov=ALL)
+        self.aov = self.frame["aov"]
+        self.out = torch.empty_like(self.frame["rgba"])
+        self.packed = torch.empty_like(self.frame["packed"])
+        self.live = int((self.aov["id"][..., 0] >= 0).sum())
+
+    def step(self, rays, variant, bounces=None):
+        """One call of variant `variant`: rt_scene_indirect, or with `bounces` rt_scene_indirect_paths."""
+        a, scene, st = self.aov, self.scene, self.st
+        d = scene.indirect_desc(self.w, self.h, depth=a["depth"].data_ptr(), normal=a["normal"].data_ptr(), id=a["id"].data_ptr(),
+                                albedo=a["albedo"].data_ptr(), rgba_in=self.frame["rgba"].data_ptr(), rgba_out=self.out.data_ptr(),
+                                pixels=self.packed.data_ptr(), rays=rays, variant=variant)
+        o = scene.indirect_paths_opts(bounces) if bounces else None
+        name = "rt_scene_indirect_paths" if bounces else "rt_scene_indirect"
+
+        def step():
+            if (scene.indirect_paths_raw(d, o, st) if bounces else scene.indirect_raw(d, st)) != 0:
+                raise self.rt.RtError(name + " failed")
+        return step
+
+
+def alternate(steps, iters, rounds):
+    """ms per call of every step of `steps`: settled, then `rounds` rounds of `iters` calls each, the steps in turn."""
+    for s in steps.values():
+        settle(s, torch.cuda.synchronize, window=iters, max_windows=8)
+    runs = {k: [] for k in steps}
+    for _ in range(rounds):
+        for k, s in steps.items():
+            e0, e1 = timed(s, iters)
+            torch.cuda.synchronize()
+            runs[k].append(e0.elapsed_time(e1) / iters)
+    return runs
+
+
+def _stats(runs, with_max=True):
+    s = {"call_ms_rounds": runs, "call_ms_median": statistics.median(runs), "call_ms_min": min(runs)}
+    if with_max:
+        s["call_ms_max"] = max(runs)
+    return s
+
+
+def indirect_cases(v, iters, rounds):
+    scene, a = v.scene, v.aov
+    res = {"dead_pixel_share": float((a["id"][..., 0] < 0).float().mean()), "live_pixels": v.live}
     for rays in (1, 4):
-        steps = {}
-        for variant in (0, 1):
-            d = scene.indirect_desc(w, h, depth=a["depth"].data_ptr(), normal=a["normal"].data_ptr(), id=a["id"].data_ptr(),
-                                    albedo=a["albedo"].data_ptr(), rgba_in=frame["rgba"].data_ptr(), rgba_out=out.data_ptr(),
-                                    pixels=packed.data_ptr(), rays=rays, variant=variant)
-
-            def step(d=d):
-                if scene.indirect_raw(d, st) != 0:
-                    raise rt.RtError("rt_scene_indirect failed")
-            steps[variant] = step
-        for s in steps.values():
-            settle(s, torch.cuda.synchronize, window=iters, max_windows=8)
-        runs = {0: [], 1: []}
-        for _ in range(rounds):
-            for variant in (0, 1):
-                e0, e1 = timed(steps[variant], iters)
-                torch.cuda.synchronize()
-                runs[variant].append(e0.elapsed_time(e1) / iters)
+        steps = {variant: v.step(rays, variant) for variant in (0, 1)}
+        runs = alternate(steps, iters, rounds)
         r = {}
         scene.set_indirect_timing(True)
         for variant in (0, 1):
             steps[variant]()
-            r[f"variant{variant}"] = {"call_ms_rounds": runs[variant], "call_ms_median": statistics.median(runs[variant]),
-                                      "call_ms_min": min(runs[variant]), "pass_ms": scene.indirect_times(),
+            r[f"variant{variant}"] = {**_stats(runs[variant], with_max=False), "pass_ms": scene.indirect_times(),
                                       "queue": scene.indirect_counts()}
         scene.set_indirect_timing(False)
         r["passes"] = "variant 0: per group of at most 4 rays cast, shade, resolve; variant 1: the kernel"
@@ -66,53 +92,23 @@ def indirect_cases(rt, scene, w, h, iters, rounds):
         r["variant1_over_variant0"] = r["variant1"]["call_ms_median"] / r["variant0"]["call_ms_median"]
         res[f"rays{rays}"] = r
     # for scale: SHADE of the view's own primary rays, and the frame with its guides
+    w, h = v.w, v.h
     rays_t = scene.primary_rays(w, h).reshape(-1, 6)
     rgba = torch.empty((w * h, 4), dtype=torch.float32, device="cuda")
     q = scene.query("shade", w * h, rays=rays_t.data_ptr(), rgba=rgba.data_ptr())
-    res["trace_rays_shade_primary_ms"] = time_ms(lambda: scene.trace_rays_raw(q, st), iters, rounds)
-    bufs = {k: torch.empty_like(v) for k, v in a.items()}
-    fd = scene.frame_desc(w, h, pixels=packed.data_ptr(), rgba=out.data_ptr(), **{f"aov_{k}": v.data_ptr() for k, v in bufs.items()})
-    res["frame_all4_guides_ms"] = time_ms(lambda: scene.render_raw(fd, st), 20, rounds)
+    res["trace_rays_shade_primary_ms"] = time_ms(lambda: scene.trace_rays_raw(q, v.st), iters, rounds)
+    bufs = {k: torch.empty_like(t) for k, t in a.items()}
+    fd = scene.frame_desc(w, h, pixels=v.packed.data_ptr(), rgba=v.out.data_ptr(), **{f"aov_{k}": t.data_ptr() for k, t in bufs.items()})
+    res["frame_all4_guides_ms"] = time_ms(lambda: scene.render_raw(fd, v.st), 20, rounds)
     return res
 
 
-def _stats(runs):
-    return {"call_ms_rounds": runs, "call_ms_median": statistics.median(runs), "call_ms_min": min(runs), "call_ms_max": max(runs)}
-
-
-def paths_cases(rt, scene, w, h, max_bounces, iters, rounds):
-    st = torch.cuda.current_stream().cuda_stream
-    frame = scene.render(w, h, aov=ALL)
-    a = frame["aov"]
-    out = torch.empty_like(frame["rgba"])
-    packed = torch.empty_like(frame["packed"])
-    res = {"live_pixels": int((a["id"][..., 0] >= 0).sum())}
-
-    def desc(variant):
-        return scene.indirect_desc(w, h, depth=a["depth"].data_ptr(), normal=a["normal"].data_ptr(), id=a["id"].data_ptr(),
-                                   albedo=a["albedo"].data_ptr(), rgba_in=frame["rgba"].data_ptr(), rgba_out=out.data_ptr(),
-                                   pixels=packed.data_ptr(), rays=1, variant=variant)
-
-    def alternate(steps):
-        for s in steps.values():
-            settle(s, torch.cuda.synchronize, window=iters, max_windows=8)
-        runs = {k: [] for k in steps}
-        for _ in range(rounds):
-            for k, s in steps.items():
-                e0, e1 = timed(s, iters)
-                torch.cuda.synchronize()
-                runs[k].append(e0.elapsed_time(e1) / iters)
-        return runs
-
+def paths_cases(v, max_bounces, iters, rounds):
+    scene = v.scene
+    res = {"live_pixels": v.live}
     for bounces in range(1, max_bounces + 1):
-        o = scene.indirect_paths_opts(bounces)
-        steps = {}
-        for variant in (0, 1):
-            def step(d=desc(variant)):
-                if scene.indirect_paths_raw(d, o, st) != 0:
-                    raise rt.RtError("rt_scene_indirect_paths failed")
-            steps[variant] = step
-        runs = alternate(steps)
+        steps = {variant: v.step(1, variant, bounces) for variant in (0, 1)}
+        runs = alternate(steps, iters, rounds)
         r = {}
         scene.set_indirect_timing(True)
         for variant in (0, 1):
@@ -124,44 +120,13 @@ def paths_cases(rt, scene, w, h, max_bounces, iters, rounds):
         r["variant1_median_below_variant0_min"] = r["variant1"]["call_ms_median"] < r["variant0"]["call_ms_min"]
         res[f"bounces{bounces}"] = r
     # bounces = 1 through the new entry against rt_scene_indirect: the same launches
-    o1, d0 = scene.indirect_paths_opts(1), desc(0)
-
-    def old():
-        if scene.indirect_raw(d0, st) != 0:
-            raise rt.RtError("rt_scene_indirect failed")
-
-    def new():
-        if scene.indirect_paths_raw(d0, o1, st) != 0:
-            raise rt.RtError("rt_scene_indirect_paths failed")
-    runs = alternate({"rt_scene_indirect": old, "rt_scene_indirect_paths": new})
-    e = {k: _stats(v) for k, v in runs.items()}
+    runs = alternate({"rt_scene_indirect": v.step(1, 0), "rt_scene_indirect_paths": v.step(1, 0, 1)}, iters, rounds)
+    e = {k: _stats(r) for k, r in runs.items()}
     a_, b_ = e["rt_scene_indirect"], e["rt_scene_indirect_paths"]
     e["medians_inside_each_others_range"] = (b_["call_ms_min"] <= a_["call_ms_median"] <= b_["call_ms_max"] and
                                              a_["call_ms_min"] <= b_["call_ms_median"] <= a_["call_ms_max"])
     res["one_bounce_entries"] = e
     return res
-
-
-def paths_main(rt, a):
-    out = {"iters": a.iters, "rounds": a.rounds, "rays": 1,
-           "statistic": "call_ms_rounds: hipEvent ms per call of --iters calls, the two variants alternating per round "
-                        "(settled clocks); launch_ms: the hipEvent time of each launch of one call "
-                        "(rt_scene_indirect_times); queue: per group, the entries that entered each bounce's shade pass",
-           "variants": "0: the product (wavefront: cast, one shade-and-continue pass per bounce, resolve); "
-                       "1: the plain one-thread-per-pixel yardstick"}
-    if os.path.exists(a.out):
-        with open(a.out) as f:
-            old = json.load(f)
-        if "existing_paths" in old:
-            out["existing_paths"] = old["existing_paths"]
-    scene = rt.Scene.default(1024)
-    for w, h in ((3840, 2160), (1920, 1080)):
-        out[f"n1024_{w}x{h}"] = paths_cases(rt, scene, w, h, a.bounces, a.iters, a.rounds)
-    scene.close()
-    out["device"] = torch.cuda.get_device_name(0)
-    print(json.dumps(out))
-    with open(a.out, "w") as f:
-        f.write(json.dumps(out, indent=1) + "\n")
 
 
 def main():
@@ -172,15 +137,19 @@ def main():
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     rt = rt_amd.load()
+    out = {"iters": a.iters, "rounds": a.rounds}
     if a.bounces:
         a.out = a.out or os.path.join(ROOT, "profiles", "indirect_paths_c3.json")
-        return paths_main(rt, a)
-    a.out = a.out or os.path.join(ROOT, "profiles", "indirect_c3.json")
-    out = {"iters": a.iters, "rounds": a.rounds,
-           "statistic": "call_ms_rounds: hipEvent ms per call of --iters calls, the two variants alternating per round "
-                        "(settled clocks); pass_ms: the hipEvent time of each launch of one call (rt_scene_indirect_times)",
-           "variants": "0: the product (wavefront passes: cast, shade over the compacted queue, resolve); "
-                       "1: the plain one-thread-per-pixel yardstick"}
+        out.update({"rays": 1,
+                    "statistic": CALL + "launch_ms: the hipEvent time of each launch of one call (rt_scene_indirect_times); "
+                                 "queue: per group, the entries that entered each bounce's shade pass",
+                    "variants": "0: the product (wavefront: cast, one shade-and-continue pass per bounce, resolve); "
+                                "1: the plain one-thread-per-pixel yardstick"})
+    else:
+        a.out = a.out or os.path.join(ROOT, "profiles", "indirect_c3.json")
+        out.update({"statistic": CALL + "pass_ms: the hipEvent time of each launch of one call (rt_scene_indirect_times)",
+                    "variants": "0: the product (wavefront passes: cast, shade over the compacted queue, resolve); "
+                                "1: the plain one-thread-per-pixel yardstick"})
     if os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
@@ -188,7 +157,8 @@ def main():
             out["existing_paths"] = old["existing_paths"]
     scene = rt.Scene.default(1024)
     for w, h in ((3840, 2160), (1920, 1080)):
-        out[f"n1024_{w}x{h}"] = indirect_cases(rt, scene, w, h, a.iters, a.rounds)
+        v = View(rt, scene, w, h)
+        out[f"n1024_{w}x{h}"] = paths_cases(v, a.bounces, a.iters, a.rounds) if a.bounces else indirect_cases(v, a.iters, a.rounds)
     scene.close()
     out["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
