@@ -432,6 +432,7 @@ def load_library():
         "rt_scene_indirect_paths": (ci, [vp, C.POINTER(IndirectDesc), C.POINTER(IndirectPathsOpts), vp]),
         "rt_debug_indirect_path_counts": (ci, [vp, C.POINTER(ci), ci, C.POINTER(ci)]),
         "rt_debug_indirect_path_key": (ci, [C.POINTER(C.c_uint), ci, ci, C.POINTER(C.c_uint)]),
+        "rt_debug_reflect_dispatch": (ci, [vp, C.POINTER(ci), ci]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly

@@ -215,6 +215,8 @@ int rt_reflect_launch_samples(RtReflect *r, const RtFrameConsts *fc, const RtFra
                               const float4 *d_spheres, int n, int depth, hipStream_t stream);
 int rt_reflect_set_timing(RtReflect *r, int on);
 int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out);
+enum { RT_REFLECT_DISPATCH_FIELDS = 7 };
+void rt_reflect_dispatch(const RtReflect *r, int out[RT_REFLECT_DISPATCH_FIELDS]);   // r may be null
 RtSphereBvh *rt_reflect_bvh(RtReflect *r);
 
 // rt_query.hip: ray queries (q: validated, in this build's layout; bvh: null or current -- the list is walked then)

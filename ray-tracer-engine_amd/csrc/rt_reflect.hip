@@ -647,6 +647,12 @@ struct RtReflect {
     bool last_samples = false;            // it was a supersampled frame (its groups end with a resolve pass)
     int last_depth = 0;
     bool have_frame = false;
+    // what rf_run_passes launched last (rt_debug_reflect_dispatch): the instantiation's flags, whether the passes
+    // walked the sphere BVH, and how many groups of the frame have run; groups = 0 before any reflective frame
+    struct {
+        bool glass, kinds, samples, gloss, fresnel, bvh;
+        int groups;
+    } dispatch = {};
     int timing = 0;
     bool timed = false;
     HipEvent ev[RT_REFLECT_MAX_GROUPS][RT_MAX_REFLECT_DEPTH + 4];   // a row per group (a one-sample frame: row 0), rf_mark
@@ -1016,6 +1022,7 @@ static int rf_run_passes(RtReflect *r, const RfPasses &p, const RtFrameConsts *f
     int *const cnt = r->d_cnt.get() + group * (RT_MAX_REFLECT_DEPTH + 1);
     const auto primary = p.gloss ? rf_primary_kernel<SAMPLES, true>(p) : rf_primary_kernel<SAMPLES, false>(p);
     const auto bounce = p.gloss ? rf_bounce_kernel<true>(p) : rf_bounce_kernel<false>(p);
+    r->dispatch = {p.glass, p.kinds, SAMPLES, p.gloss, p.fresnel, p.rd.nodes != nullptr, group + 1};
     hipLaunchKernelGGL(primary, dim3((threads + RT_REFLECT_BLOCK - 1) / RT_REFLECT_BLOCK), dim3(RT_REFLECT_BLOCK), 0,
                        stream, *fc, p.rd, r->d_q[0].get(), cnt, p.kd);
     RT_HIP(hipGetLastError());
@@ -1116,6 +1123,21 @@ int rt_reflect_get_stats(RtReflect *r, rt_reflect_stats *out)
         out->timed = 1;
     }
     return RT_OK;
+}
+
+// rt_debug_reflect_dispatch: out = {glass, kinds, samples, gloss, fresnel, bvh, groups} as rf_run_passes launched the
+// last reflective frame; r null or no such frame yet: the flags -1 and groups 0
+void rt_reflect_dispatch(const RtReflect *r, int out[RT_REFLECT_DISPATCH_FIELDS])
+{
+    static_assert(RT_REFLECT_DISPATCH_FIELDS == 7, "six flags and the group count");
+    if (!r || r->dispatch.groups == 0) {
+        std::fill(out, out + RT_REFLECT_DISPATCH_FIELDS - 1, -1);
+        out[RT_REFLECT_DISPATCH_FIELDS - 1] = 0;
+        return;
+    }
+    const auto &d = r->dispatch;
+    const int v[RT_REFLECT_DISPATCH_FIELDS] = {d.glass, d.kinds, d.samples, d.gloss, d.fresnel, d.bvh, d.groups};
+    std::copy(v, v + RT_REFLECT_DISPATCH_FIELDS, out);
 }
 
 // ---------------------------------------------------------------------------

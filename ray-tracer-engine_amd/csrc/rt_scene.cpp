@@ -451,6 +451,20 @@ extern "C" int rt_scene_reflect_stats(rt_scene *s, rt_reflect_stats *out)
     return rt_reflect_get_stats(rt_scene_reflect(s), out);
 }
 
+// Tests only (not in include/rt_engine.h): which instantiations of the reflective passes the scene's most recent
+// reflective frame launched. out[0 .. 4]: GLASS, KINDS, SAMPLES, GLOSS, FRESNEL of rt_reflect_primary (0 / 1); out[5]:
+// 1 the passes walked the sphere BVH, 0 the whole list; out[6]: the frame's sample groups (a one-sample frame: 1).
+// Before any reflective frame: the flags -1 and 0 groups. Host state only: it waits for nothing.
+extern "C" int rt_debug_reflect_dispatch(rt_scene *s, int *out, int cap)
+{
+    if (!s || !out || cap < RT_REFLECT_DISPATCH_FIELDS) {
+        rt_set_error("rt_debug_reflect_dispatch: null argument or room for fewer than %d ints", RT_REFLECT_DISPATCH_FIELDS);
+        return RT_ERR_INVALID;
+    }
+    rt_reflect_dispatch(s->refl.get(), out);
+    return RT_OK;
+}
+
 int rt_scene_tile_order_mode(const rt_scene *s) { return s->tile_order_mode; }
 
 extern "C" int rt_scene_set_tile_order(rt_scene *s, int mode)
