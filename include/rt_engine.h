@@ -1327,6 +1327,38 @@ int rt_debug_indirect_path_counts(rt_scene *s, int *counts, int cap, int *n);
 /* key_b of (g) for `count` keys key_0 (the same code the kernels run, no GPU needed; tests only): out[i]. b >= 0. */
 int rt_debug_indirect_path_key(const unsigned *key, int count, int b, unsigned *out);
 
+/* ------------------------------------------------------------------ *
+ * Emissive surfaces: spheres, planes and cubes that     *
+ * light the gather paths of the two indirect entries.                  *
+ * ------------------------------------------------------------------ */
+/* Emission per primitive of one kind, under rt_scene_set_roughness' protocol: kind = RT_HIT_SPHERE, RT_HIT_PLANE or
+ * RT_HIT_CUBE (anything else, RT_HIT_TRIANGLE included: RT_ERR_INVALID, naming the kind; a triangle emits nothing);
+ * rgb holds 3 * n floats, one colour per primitive of that kind's list, n the list's count. NULL or n == 0 clears the
+ * kind's table and always succeeds. A value that is not finite and >= 0 (the message names the kind, the primitive,
+ * the channel and the value; the values are checked before the count), or another count than the list's:
+ * RT_ERR_INVALID, and nothing changes on an error. A table behaves as the
+ * roughness table when its list is set again: it survives rt_scene_set_spheres / _planes / _cubes with the same count
+ * and is cleared by a different count.
+ *
+ * Host-side state, read when an indirect call is launched: no wait, no device needed here. The scene's next
+ * rt_scene_indirect / rt_scene_indirect_paths call uploads a table that changed (16 bytes per primitive) on its own
+ * stream, ordered on the device after the scene's indirect calls in flight; only a table that grows waits on the host
+ * for them. rt_indirect_desc and rt_indirect_paths_opts are unchanged.
+ *
+ * Semantics: steps 1 to 6 of rt_scene_indirect and (a) to (g) of rt_scene_indirect_paths with one change. The colour
+ * RT_QUERY_SHADE gives a gather hit (c_j of step 3; `term` of (c)) becomes term + e per channel in binary32, e the
+ * table entry of the hit record's (kind, index); e = 0 for a triangle and for a kind without a table. Everything after
+ * uses that sum as it used the term: 0.f + term at bounce 0, L + T_b * term later, the order of the sums, steps 4 to 6.
+ * The texel throughput of an emitter is its texel, as for any surface; a miss is getFColor; dead pixels, keys and
+ * directions are unchanged, so emission changes no path and no queue length. Without a table (never set, or every
+ * kind cleared) a call launches the kernels it launched before emission existed and gives their bits; an all-zero
+ * table gives the same bits through the other instantiations.
+ * Emission is found by the cosine-distributed gather rays alone: no emitter is sampled directly, so a small bright one
+ * is noisy (rt_scene_temporal and the denoisers are the remedy). The frame kernel, RT_QUERY_SHADE, the ray queries and
+ * the reflective passes do not read the tables: an emitter seen by the primary ray is the caller's to add from the id
+ * guide (Scene.emission_term in the Python wrapper), one seen in a mirror or through glass is not shown. */
+int rt_scene_set_emission(rt_scene *s, int kind, const float *rgb, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -413,6 +413,7 @@ def load_library():
         "rt_scene_set_plane_materials": (ci, [vp, C.POINTER(Material), ci]),
         "rt_scene_set_cube_materials": (ci, [vp, C.POINTER(Material), ci]),
         "rt_scene_set_roughness": (ci, [vp, ci, fp, ci]),
+        "rt_scene_set_emission": (ci, [vp, ci, fp, ci]),
         "rt_scene_set_gloss_seed": (ci, [vp, C.c_uint]),
         "rt_debug_gloss": (ci, [C.POINTER(Vec3), C.POINTER(Vec3), fp, C.POINTER(C.c_uint), C.POINTER(ci), ci,
                                 C.POINTER(Vec3), C.POINTER(ci)]),
@@ -605,6 +606,7 @@ class Scene:
         self.planes, self.n_planes = None, 0
         self.cubes, self.n_cubes = None, 0
         self.materials = self.plane_materials = self.cube_materials = None
+        self.emission = {}                # set_emission's host mirror: {RT_HIT_*: float32 [n, 3]} (emission_term)
 
     def close(self):
         if self.handle:
@@ -621,18 +623,21 @@ class Scene:
         _check(self.lib.rt_scene_set_spheres(self.handle, spheres, n), "rt_scene_set_spheres")
         if n != self.n_spheres:           # the library cleared the materials: so does their host mirror (upsample_select)
             self.materials = None
+            self.emission.pop(RT_HIT_SPHERE, None)
         self.spheres, self.n_spheres = spheres, n
 
     def set_planes(self, planes, n):
         _check(self.lib.rt_scene_set_planes(self.handle, planes, n), "rt_scene_set_planes")
         if n != self.n_planes:
             self.plane_materials = None
+            self.emission.pop(RT_HIT_PLANE, None)
         self.planes, self.n_planes = planes, n
 
     def set_cubes(self, cubes, n):
         _check(self.lib.rt_scene_set_cubes(self.handle, cubes, n), "rt_scene_set_cubes")
         if n != self.n_cubes:
             self.cube_materials = None
+            self.emission.pop(RT_HIT_CUBE, None)
         self.cubes, self.n_cubes = cubes, n
 
     def set_mesh(self, mesh):
@@ -750,6 +755,42 @@ class Scene:
             return
         v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
         _check(self.lib.rt_scene_set_roughness(self.handle, int(kind), _fptr(v), v.shape[0]), "rt_scene_set_roughness")
+
+    def set_emission(self, kind, values):
+        """Emission per primitive of one kind ("sphere", "plane" or "cube"; also RT_HIT_SPHERE / _PLANE / _CUBE): an
+        [n, 3] array, one finite colour >= 0 per primitive of that list; None (or empty) clears the kind's table. A gather
+        hit of indirect / indirect_paths on an emitter adds its colour to what the hit is shaded with (DESIGN.md 6q);
+        nothing else reads the tables -- emission_term is what the primary ray sees. Host state: the next indirect call
+        uploads it. A list set again with another count clears its table."""
+        if isinstance(kind, str):
+            if kind not in _ROUGH_KINDS:
+                raise RtError(f"unknown emission kind {kind!r} (one of {tuple(_ROUGH_KINDS)})")
+            kind = _ROUGH_KINDS[kind]
+        if values is None or len(values) == 0:
+            _check(self.lib.rt_scene_set_emission(self.handle, int(kind), None, 0), "rt_scene_set_emission")
+            self.emission.pop(int(kind), None)
+            return
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise RtError(f"set_emission: values must have shape [n, 3], not {tuple(v.shape)}")
+        _check(self.lib.rt_scene_set_emission(self.handle, int(kind), _fptr(v), v.shape[0]), "rt_scene_set_emission")
+        self.emission[int(kind)] = v.copy()
+
+    def emission_term(self, frame):
+        """What the primary ray itself sees of an emitter: float32 [rows, W, 4] on the device of frame["aov"]["id"], rgb
+        the set_emission entry of the id guide's (kind, index), a = 0; zero for sky, triangles and kinds without a
+        table. Plain indexing, no kernel. The caller adds it after the denoiser, so that an emitter glows in the picture
+        -- outside the pass, where the demodulated upsample of a half-resolution pipeline would divide it by albedo."""
+        import torch
+        ids = (frame.get("aov") or {}).get("id")
+        if ids is None:
+            raise RtError(f"emission_term needs the G-buffer output 'id': render with aov={AOV_NAMES}")
+        kind, index = ids[..., 0].long(), ids[..., 1].long()
+        out = torch.zeros(tuple(ids.shape[:2]) + (4,), dtype=torch.float32, device=ids.device)
+        for k, v in self.emission.items():
+            m = kind == k
+            out[..., :3][m] = torch.from_numpy(v).to(ids.device)[index[m]]
+        return out
 
     def set_gloss_seed(self, seed: int):
         """The seed of the glossy draws (default 0; taken modulo 2^32). One sample per frame with set_gloss_seed(frame)

@@ -21,6 +21,10 @@
 //     resolve   per pixel: the earlier groups' running sum plus the group's slots in ascending ray order, and -- the
 //               last group -- the mean, the albedo and the outputs. Dead pixels are written here.
 //   No float atomics: the order of the sum is the slab's.
+// Emissive surfaces (rt_scene_set_emission) are a template parameter of the two kernels that shade a hit,
+// EMIT: the colour q_shade_hit gives a hit gets the hit primitive's table entry added (ind_emit). The tables are an
+// argument of the EMIT = true instantiations alone, which the host launches only when some kind has a table: every
+// other call runs the EMIT = false ones, with the arguments they had before emission existed.
 // Which of the two rt_indirect_desc.variant 0 names is kIndirectWavefrontIsProduct (bounces == 1, the measurement of
 // DESIGN.md 6o) or kIndirectPathsWavefrontIsProduct (bounces > 1, that of 6p) below. The brute-force variant (cull = 0)
 // is the same kernels with the BVH replaced by the whole sphere list.
@@ -180,12 +184,28 @@ __device__ __forceinline__ void ind_finish(const RtIndirectDev &d, int p, float 
     ind_store(d, p, c);
 }
 
-// The plain kernel: everything for pixel p in one thread, per ray the loop of DESIGN.md 6p. ONE: the budget is the
-// constant 1 and the loop over the bounces a single trip (6o's sr = sr + (0.f + fr))
-template <bool ONE>
-__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_plain(const RtFrameConsts fc, const RtReflectDev rd,
-                                                                     const RtIndirectDev d, int budget)
+// What a gather hit emits: h's colour plus the entry of its (kind, index) in its kind's table; a triangle
+// and a kind without a table emit nothing. The kind differs from lane to lane: one 16-byte vector load. Without tables
+// (the EMIT = false instantiations pass none) the colour is q_shade_hit's.
+__device__ __forceinline__ void ind_emit(const rt_hit &, float &, float &, float &) {}
+__device__ __forceinline__ void ind_emit(const rt_hit &h, float &fr, float &fg, float &fb, const RtEmitDev &em)
 {
+    const float4 *t = h.kind == RT_HIT_SPHERE ? em.sphere : (h.kind == RT_HIT_PLANE ? em.plane : (h.kind == RT_HIT_CUBE ? em.cube : nullptr));
+    if (!t) return;
+    const float4 e = t[h.index];
+    fr = fr + e.x;
+    fg = fg + e.y;
+    fb = fb + e.z;
+}
+
+// The plain kernel: everything for pixel p in one thread, per ray the loop of DESIGN.md 6p. ONE: the budget is the
+// constant 1 and the loop over the bounces a single trip (6o's sr = sr + (0.f + fr)). EMIT: `em` is the emission tables
+// (one RtEmitDev; without EMIT no argument at all)
+template <bool ONE, bool EMIT, class... Em>
+__global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_plain(const RtFrameConsts fc, const RtReflectDev rd,
+                                                                     const RtIndirectDev d, int budget, const Em... em)
+{
+    static_assert(sizeof...(Em) == (EMIT ? 1 : 0), "the tables go to the EMIT instantiations alone");
     const int bounces = ONE ? 1 : budget;
     __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
     const LdsStack stk{stack_lds, (int)threadIdx.x};
@@ -212,6 +232,7 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_plain(const RtF
             if (kind >= 0) {
                 h = q_hit_record(fc, ax, rd, O, D, nt, kind, pos);
                 q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
+                ind_emit(h, fr, fg, fb, em...);
             } else {
                 rf_sky(ax, O, D, fr, fg, fb);
             }
@@ -280,13 +301,14 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_cast(const RtFr
 // FIRST: b == 0, the entries are the cast pass's (no throughput; the key is the slot's); LAST: b == bounces - 1, nothing
 // continues (q_out and count_out are null). <true, true> is the shade pass of DESIGN.md 6o. Every lane of a wave makes
 // every trip of the loop (its bounds are uniform) and reaches rf_wave_append: a lane without an entry is inactive by
-// `act`, never by leaving.
-template <bool FIRST, bool LAST>
+// `act`, never by leaving. EMIT: as the plain kernel's.
+template <bool FIRST, bool LAST, bool EMIT, class... Em>
 __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_shade(const RtFrameConsts fc, const RtReflectDev rd,
                                                                      const RtIndirectDev d, int j0, const float4 *q_in,
                                                                      const int *count_in, float4 *q_out, int *count_out,
-                                                                     float4 *slab)
+                                                                     float4 *slab, const Em... em)
 {
+    static_assert(sizeof...(Em) == (EMIT ? 1 : 0), "the tables go to the EMIT instantiations alone");
     __shared__ int stack_lds[RT_BVH_STACK * RT_INDIRECT_BLOCK];
     const LdsStack stk{stack_lds, (int)threadIdx.x};
     const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;
@@ -309,6 +331,7 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_shade(const RtF
             const rt_hit h = q_hit_record(fc, ax, rd, O, D, e0.w, __float_as_int(e1.w), __float_as_int(e2.x));
             float fr, fg, fb;
             q_shade_hit(fc, ax, rd, h, stk, fr, fg, fb);
+            ind_emit(h, fr, fg, fb, em...);
             float lr, lg, lb;
             if (FIRST) {
                 lr = 0.f + fr; lg = 0.f + fg; lb = 0.f + fb;
@@ -388,8 +411,8 @@ __global__ __launch_bounds__(RT_INDIRECT_BLOCK) void rt_indirect_resolve(const R
 // host side
 // ---------------------------------------------------------------------------
 int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameConsts *fc, const RtSphereBvh *bvh,
-                       const float4 *d_spheres, int n_spheres, const RtIndirectScratch *scratch, hipEvent_t *ev, int *n_ev,
-                       hipStream_t stream)
+                       const float4 *d_spheres, int n_spheres, const RtEmitDev *emit, const RtIndirectScratch *scratch,
+                       hipEvent_t *ev, int *n_ev, hipStream_t stream)
 {
     RtReflectDev rd{};
     rd.nodes = (bvh && bvh->ok) ? bvh->d_nodes.get() : nullptr;
@@ -410,8 +433,13 @@ int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameCons
     *n_ev = 0;
     RT_HIP(mark());
     if (!rt_indirect_wavefront(d->variant, bounces)) {
-        hipLaunchKernelGGL(bounces == 1 ? rt_indirect_plain<true> : rt_indirect_plain<false>, px_grid, block, 0, stream, *fc, rd,
-                           dd, bounces);
+        if (emit) {
+            const auto plain = bounces == 1 ? rt_indirect_plain<true, true, RtEmitDev> : rt_indirect_plain<false, true, RtEmitDev>;
+            hipLaunchKernelGGL(plain, px_grid, block, 0, stream, *fc, rd, dd, bounces, *emit);
+        } else {
+            const auto plain = bounces == 1 ? rt_indirect_plain<true, false> : rt_indirect_plain<false, false>;
+            hipLaunchKernelGGL(plain, px_grid, block, 0, stream, *fc, rd, dd, bounces);
+        }
         RT_HIP(hipGetLastError());
         RT_HIP(mark());
         *n_ev = marks;
@@ -432,10 +460,18 @@ int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameCons
             const bool first = b == 0, last = b == bounces - 1;
             const float4 *q_in = (b & 1) ? scratch->queue2 : scratch->queue;
             float4 *q_out = last ? nullptr : (b & 1) ? scratch->queue : scratch->queue2;
-            const auto shade = first ? (last ? rt_indirect_shade<true, true> : rt_indirect_shade<true, false>)
-                                     : (last ? rt_indirect_shade<false, true> : rt_indirect_shade<false, false>);
-            hipLaunchKernelGGL(shade, shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in, count + b, q_out,
-                               last ? nullptr : count + b + 1, scratch->slab);
+            int *const count_out = last ? nullptr : count + b + 1;
+            if (emit) {
+                const auto shade = first ? (last ? rt_indirect_shade<true, true, true, RtEmitDev> : rt_indirect_shade<true, false, true, RtEmitDev>)
+                                         : (last ? rt_indirect_shade<false, true, true, RtEmitDev> : rt_indirect_shade<false, false, true, RtEmitDev>);
+                hipLaunchKernelGGL(shade, shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in, count + b, q_out, count_out,
+                                   scratch->slab, *emit);
+            } else {
+                const auto shade = first ? (last ? rt_indirect_shade<true, true, false> : rt_indirect_shade<true, false, false>)
+                                         : (last ? rt_indirect_shade<false, true, false> : rt_indirect_shade<false, false, false>);
+                hipLaunchKernelGGL(shade, shade_grid, block, 0, stream, *fc, rd, dd, j0, q_in, count + b, q_out, count_out,
+                                   scratch->slab);
+            }
             RT_HIP(hipGetLastError());
             RT_HIP(mark());
         }

@@ -272,11 +272,16 @@ struct RtIndirectScratch {
     int *count;
     float4 *queue2;   // bounces > 1 only
 };
+// Emission per primitive of a kind (rt_scene_set_emission): (r, g, b, 0) at the list position; null: the
+// kind has no table
+struct RtEmitDev {
+    const float4 *sphere, *plane, *cube;
+};
 // whether `variant` runs the wavefront passes (and needs the scratch) in a call of `bounces`
 bool rt_indirect_wavefront(int variant, int bounces = 1);
 // d: validated, in this build's layout; fc: the view's uniforms (whole frame, one sample, the pass's own ray tables);
 // bvh: null or current; ev: null, or RT_INDIRECT_MAX_EVENTS timing events, of which *n_ev are recorded; bounces: 1 is
-// rt_scene_indirect itself
+// rt_scene_indirect itself; emit: null (no kind has a table: today's instantiations), or the tables, one of them at least
 int rt_indirect_launch(const rt_indirect_desc *d, int bounces, const RtFrameConsts *fc, const RtSphereBvh *bvh,
-                       const float4 *d_spheres, int n_spheres, const RtIndirectScratch *scratch, hipEvent_t *ev, int *n_ev,
-                       hipStream_t stream);
+                       const float4 *d_spheres, int n_spheres, const RtEmitDev *emit, const RtIndirectScratch *scratch,
+                       hipEvent_t *ev, int *n_ev, hipStream_t stream);

@@ -1154,6 +1154,23 @@ static int indirect_call(rt_scene *s, const rt_indirect_desc *d_in, int bounces,
     fc.dy_tab = s->ind_raygen.get() + d.width;
     fc.packed = nullptr;
     RT_HIP(s->ind_done.order(stream));   // one scratch: one call at a time
+    // the emission tables that changed: on this stream, so behind every indirect call in flight and ahead of this one
+    // (a table that grows releases the old buffer: after the host has seen those calls end)
+    RtEmitDev emit{};
+    for (RtEmitTable &t : s->emit) {
+        if (!t.dirty) continue;
+        if (t.v.size() > t.d.capacity()) RT_HIP(s->ind_done.host_wait());
+        t.v_dev = t.v;
+        if (!t.v_dev.empty()) {
+            RT_HIP(t.d.reserve(t.v_dev.size()));
+            RT_HIP(hipMemcpyAsync(t.d.get(), t.v_dev.data(), sizeof(float4) * t.v_dev.size(), hipMemcpyHostToDevice, stream));
+        }
+        t.dirty = false;
+    }
+    emit.sphere = s->emit[0].dev();
+    emit.plane = s->emit[1].dev();
+    emit.cube = s->emit[2].dev();
+    const bool any_emit = emit.sphere || emit.plane || emit.cube;
     hipEvent_t ev[RT_INDIRECT_MAX_EVENTS];
     s->ind_timed = 0;
     if (s->ind_timing) {
@@ -1164,7 +1181,8 @@ static int indirect_call(rt_scene *s, const rt_indirect_desc *d_in, int bounces,
     }
     const RtIndirectScratch scratch{s->ind_slab.get(), s->ind_queue.get(), s->ind_sum.get(), s->ind_count.get(), s->ind_queue2.get()};
     int n_ev = 0;
-    rc = rt_indirect_launch(&d, bounces, &fc, bvh, s->d_spheres.get(), s->n_spheres, &scratch, s->ind_timing ? ev : nullptr, &n_ev, stream);
+    rc = rt_indirect_launch(&d, bounces, &fc, bvh, s->d_spheres.get(), s->n_spheres, any_emit ? &emit : nullptr, &scratch,
+                            s->ind_timing ? ev : nullptr, &n_ev, stream);
     // also after a launch that failed half way: what was enqueued uses the scratch
     RT_HIP(s->ind_done.record(stream));
     if (rc != RT_OK) return rc;

@@ -3,6 +3,7 @@
 //
 // Reference interfaces replaced here:
 //   object / sprite / skybox     /root/reference/kernel.cu:1116-1244, sprite.h:11-47
+#include <cmath>
 #include <cstdlib>
 
 #include "rt_scene.h"
@@ -106,6 +107,16 @@ extern "C" void rt_scene_destroy(rt_scene *s)
     delete s;
 }
 
+// rt_scene_set_spheres / _planes / _cubes: a new count clears the list's emission table, the same count keeps it (as
+// the roughness table, rt_reflect_spheres_changed)
+static void emit_list_changed(rt_scene *s, int kind, int n_old, int n_new)
+{
+    RtEmitTable &t = s->emit[kind - RT_HIT_SPHERE];
+    if (n_old == n_new) return;
+    if (!t.v.empty()) t.dirty = true;
+    t.v.clear();
+}
+
 // {cx, cy, cz, radius*radius}: the only four numbers sphere::intersect reads
 // (kernel.cu:332-334); radius*radius is the same binary32 product either way.
 void rt_pack_spheres(const rt_sphere *src, int n, float4 *dst)
@@ -161,6 +172,7 @@ int rt_scene_set_spheres_async(rt_scene *s, const rt_sphere *host_spheres, int n
     s->epoch++;
     s->n_blocks = nb;
     if (s->refl) rt_reflect_spheres_changed(s->refl.get(), s->n_spheres, n);
+    emit_list_changed(s, RT_HIT_SPHERE, s->n_spheres, n);
     s->n_spheres = n;
     return RT_OK;
 }
@@ -191,6 +203,7 @@ extern "C" int rt_scene_set_planes(rt_scene *s, const rt_plane *host_planes, int
                             host_planes[i].normal.x, host_planes[i].normal.y, host_planes[i].normal.z, 0.f, 0.f};
     if (n) RT_HIP(hipMemcpy(s->d_planes.get(), tmp.data(), sizeof(RtPlaneDev) * n, hipMemcpyHostToDevice));
     if (s->refl) rt_reflect_kind_list_changed(s->refl.get(), 0, s->n_planes, n);
+    emit_list_changed(s, RT_HIT_PLANE, s->n_planes, n);
     s->n_planes = n;
     s->epoch++;
     return RT_OK;
@@ -216,6 +229,7 @@ extern "C" int rt_scene_set_cubes(rt_scene *s, const rt_cube *host_cubes, int n)
     }
     if (n) RT_HIP(hipMemcpy(s->d_cubes.get(), tmp.data(), sizeof(RtCubeDev) * n, hipMemcpyHostToDevice));
     if (s->refl) rt_reflect_kind_list_changed(s->refl.get(), 1, s->n_cubes, n);
+    emit_list_changed(s, RT_HIT_CUBE, s->n_cubes, n);
     s->n_cubes = n;
     s->epoch++;
     return RT_OK;
@@ -411,6 +425,50 @@ extern "C" int rt_scene_set_roughness(rt_scene *s, int kind, const float *rho, i
     const int n_list = kind == RT_HIT_SPHERE ? s->n_spheres : (kind == RT_HIT_PLANE ? s->n_planes : s->n_cubes);
     // (as rt_scene_set_materials: the next reflective frame uploads after the frames in flight)
     return rt_reflect_set_roughness(rt_scene_reflect(s), kind, rho, n, n_list);
+}
+
+// Emission per primitive of one kind: host state under rt_scene_set_roughness' protocol; the next indirect
+// call uploads it (rt_render.cpp, indirect_call)
+extern "C" int rt_scene_set_emission(rt_scene *s, int kind, const float *rgb, int n)
+{
+    if (!s) {
+        rt_set_error("rt_scene_set_emission: null scene");
+        return RT_ERR_INVALID;
+    }
+    if (kind != RT_HIT_SPHERE && kind != RT_HIT_PLANE && kind != RT_HIT_CUBE) {
+        rt_set_error("rt_scene_set_emission: kind %d is not RT_HIT_SPHERE, RT_HIT_PLANE or RT_HIT_CUBE", kind);
+        return RT_ERR_INVALID;
+    }
+    const char *what = kind == RT_HIT_SPHERE ? "sphere" : (kind == RT_HIT_PLANE ? "plane" : "cube");
+    const int n_list = kind == RT_HIT_SPHERE ? s->n_spheres : (kind == RT_HIT_PLANE ? s->n_planes : s->n_cubes);
+    RtEmitTable &t = s->emit[kind - RT_HIT_SPHERE];
+    if (!rgb || n == 0) {
+        if (!t.v.empty()) t.dirty = true;
+        t.v.clear();
+        return RT_OK;
+    }
+    // every value first, then the count (rt_reflect_set_kind_materials' order: a value's refusal does not depend on the
+    // scene's lists)
+    for (int i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) {
+            const float e = rgb[3 * (size_t)i + c];
+            if (!(e >= 0.f) || !std::isfinite(e)) {
+                rt_set_error("rt_scene_set_emission: %s %d: emission.%c %g is not finite and >= 0", what, i, "rgb"[c], (double)e);
+                return RT_ERR_INVALID;
+            }
+        }
+    }
+    if (n != n_list) {
+        rt_set_error("rt_scene_set_emission: %d colours for %d %ss (one per %s, or NULL / 0)", n, n_list, what, what);
+        return RT_ERR_INVALID;
+    }
+    std::vector<float4> v((size_t)n);
+    for (int i = 0; i < n; ++i) v[(size_t)i] = make_float4(rgb[3 * (size_t)i], rgb[3 * (size_t)i + 1], rgb[3 * (size_t)i + 2], 0.f);
+    // (the same table again: no re-upload)
+    if (v.size() == t.v.size() && memcmp(v.data(), t.v.data(), sizeof(float4) * v.size()) == 0) return RT_OK;
+    t.v.swap(v);
+    t.dirty = true;
+    return RT_OK;
 }
 
 // The seed of the glossy draws: a host-side value, read when a frame is launched

@@ -92,6 +92,17 @@ struct TileOrder {
     unsigned long long last_use = 0;
 };
 
+// One kind's emission table: what the host last set, and a device copy that changes only in an indirect call, behind
+// the calls that may still read it (the protocol of rt_reflect.hip's RfTable, with `ind_done` for the frame ring).
+// The passes are pointed by what the device holds (v_dev), never by v.
+struct RtEmitTable {
+    std::vector<float4> v;               // (r, g, b, 0) per primitive; empty = no table
+    std::vector<float4> v_dev;           // what the device copy holds
+    bool dirty = false;                  // v changed since the last upload
+    DevArray<float4> d;
+    const float4 *dev() const { return v_dev.empty() ? nullptr : d.get(); }
+};
+
 struct rt_scene {
     DevArray<float4> d_spheres;      // [n] list order | [n_pad] Morton order | [n_blocks] block bounds | [n_pad] ints
     int n_spheres = 0;
@@ -202,6 +213,9 @@ struct rt_scene {
     HipEvent ind_ev[RT_INDIRECT_MAX_EVENTS];         // rt_scene_set_indirect_timing
     bool ind_timing = false;
     int ind_timed = 0;
+    // emission per primitive of a kind (rt_scene_set_emission; [kind - RT_HIT_SPHERE]): host state, which
+    // the next indirect call uploads on its stream behind `ind_done` -- the indirect calls are the tables' only readers
+    RtEmitTable emit[3];
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
 #endif

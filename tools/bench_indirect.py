@@ -14,6 +14,13 @@ and bounces = 1 through the new entry against rt_scene_indirect, alternating. Th
 profiles/indirect_paths_c3.json.
 
   python3 tools/bench_indirect.py --bounces 3
+
+With --emit K emissive surfaces (rt_scene_set_emission): every K-th sphere of a second, otherwise equal
+scene emits; the product (variant 0) at one ray per pixel and bounces 1 and 2 at both sizes, the scene without tables and
+the scene with them alternating as above, with the queue lengths of both. The default --out is then
+profiles/indirect_emit_c3.json (its "parent_ab" and "existing_paths" entries are kept).
+
+  python3 tools/bench_indirect.py --emit 16
 """
 import argparse, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,16 +136,40 @@ def paths_cases(v, max_bounces, iters, rounds):
     return res
 
 
+def emit_cases(views, iters, rounds):
+    """views: {"no_tables": View, "tables": View} of two scenes that differ in the emission tables alone."""
+    res = {"live_pixels": views["no_tables"].live}
+    for bounces in (1, 2):
+        steps = {k: v.step(1, 0, bounces) for k, v in views.items()}
+        runs = alternate(steps, iters, rounds)
+        r = {}
+        for k, v in views.items():
+            steps[k]()
+            r[k] = {**_stats(runs[k]), "queue": v.scene.indirect_path_counts() if bounces > 1 else [v.scene.indirect_counts()]}
+        a_, b_ = r["no_tables"], r["tables"]
+        r["tables_over_no_tables"] = b_["call_ms_median"] / a_["call_ms_median"]
+        r["tables_median_inside_no_tables_range"] = a_["call_ms_min"] <= b_["call_ms_median"] <= a_["call_ms_max"]
+        r["same_queues"] = a_["queue"] == b_["queue"]
+        res[f"bounces{bounces}"] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--bounces", type=int, default=0, help="N: time the diffuse paths with bounces 1 .. N instead")
+    ap.add_argument("--emit", type=int, default=0, help="K: time the product with every K-th sphere emissive against no tables")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     rt = rt_amd.load()
     out = {"iters": a.iters, "rounds": a.rounds}
-    if a.bounces:
+    if a.emit:
+        a.out = a.out or os.path.join(ROOT, "profiles", "indirect_emit_c3.json")
+        out.update({"rays": 1, "emit_every": a.emit, "variant": 0,
+                    "statistic": CALL.replace("the two variants", "the scene without tables and the scene with them") +
+                                 "queue: per group, the entries that entered each bounce's shade pass"})
+    elif a.bounces:
         a.out = a.out or os.path.join(ROOT, "profiles", "indirect_paths_c3.json")
         out.update({"rays": 1,
                     "statistic": CALL + "launch_ms: the hipEvent time of each launch of one call (rt_scene_indirect_times); "
@@ -153,13 +184,26 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
-        if "existing_paths" in old:
-            out["existing_paths"] = old["existing_paths"]
+        for k in ("existing_paths", "parent_ab"):
+            if k in old:
+                out[k] = old[k]
     scene = rt.Scene.default(1024)
+    lit = None
+    if a.emit:
+        import numpy as np
+        lit = rt.Scene.default(1024)
+        e = np.zeros((1024, 3), dtype=np.float32)
+        e[::a.emit] = (1.0, 0.75, 0.5)
+        lit.set_emission("sphere", e)
     for w, h in ((3840, 2160), (1920, 1080)):
         v = View(rt, scene, w, h)
-        out[f"n1024_{w}x{h}"] = paths_cases(v, a.bounces, a.iters, a.rounds) if a.bounces else indirect_cases(v, a.iters, a.rounds)
+        if a.emit:
+            out[f"n1024_{w}x{h}"] = emit_cases({"no_tables": v, "tables": View(rt, lit, w, h)}, a.iters, a.rounds)
+        else:
+            out[f"n1024_{w}x{h}"] = paths_cases(v, a.bounces, a.iters, a.rounds) if a.bounces else indirect_cases(v, a.iters, a.rounds)
     scene.close()
+    if lit is not None:
+        lit.close()
     out["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
     with open(a.out, "w") as f:
