@@ -866,6 +866,29 @@ int rt_scene_view_lists_info(rt_scene *s, rt_view_lists_info *out, float *slots,
 int rt_debug_view_lists_host(const rt_sphere *spheres, int n, const rt_frame_desc *fd, rt_view_lists_info *out,
                              float *slots, size_t cap, float *beams);
 
+/* Light verdicts of a resting view. 1 (default): the second launch in a row with bit-identical inputs (camera, frame
+ * size, rows, tile shape, interleave, sphere list, lights, textures; the output buffers and the stream may differ)
+ * also writes, per tile, which lights it found to add nothing to any pixel of the tile (all pixels facing away, a full
+ * occluder, every shadow sample of every pixel shadowed) and which it found clear of every occluder; the launches
+ * after it skip the former and take the latter's brightness without looking for occluders. A launch with other inputs
+ * does neither, so a moving camera renders as it did. One-sample frames of sphere scenes (no cubes, planes or mesh;
+ * not stats, force_slow_path, fast, G-buffer or reflective frames; not frame graphs or rt_multi). 0: every launch
+ * evaluates every light. The pixels are the same bits either way: what is skipped is what the same code skipped, or
+ * ran to no effect, on the same inputs.                                                                             */
+int rt_scene_set_light_verdicts(rt_scene *s, int mode);
+typedef struct rt_light_verdicts_info {
+    int state;                 /* what the last frame launch on the scene did: 0 nothing, 1 wrote a table, 2 read one */
+    int slot;                  /* which of the scene's tables (-1: none) */
+    int tiles_x, tiles_y;      /* the table: one 64-bit word per tile of the launch, row by row */
+    int unwritten;             /* tiles the writing launch left untouched: words still all ones, which a reader evaluates
+                                  (0 as long as the launch's grid is cut to its rows, so that every tile has a pixel) */
+    long long nothing, clear;  /* (group, light) entries with code 1 resp. 2 over the whole table */
+} rt_light_verdicts_info;
+/* Tests and profiles; waits for the launch that wrote the table. words (optional, room for `cap` words): a copy of the
+ * table, two bits per (group, light) at 16 * group + 2 * light for the tile's first 4 groups and the first 8 lights:
+ * 0 evaluate, 1 adds nothing, 2 all clear.                                                                          */
+int rt_debug_light_verdicts(rt_scene *s, rt_light_verdicts_info *out, unsigned long long *words, size_t cap);
+
 /* hipGraph-captured frame loop (config C4): `passes` samples per pixel + resolve + optional async copy of the packed
  * frame to pinned host memory, recorded once and replayed per frame. passes > 0: the samples are taken by ONE kernel
  * node (the sample loop runs inside the kernel); passes < 0: |passes| progressive one-sample nodes, each adding into

@@ -260,6 +260,12 @@ class ViewListsInfo(C.Structure):
                 ("blocks", C.c_int), ("overflowed", C.c_int), ("not_built", C.c_int), ("longest", C.c_int), ("mean", C.c_float)]
 
 
+class LightVerdictsInfo(C.Structure):
+    """rt_light_verdicts_info."""
+    _fields_ = [("state", C.c_int), ("slot", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("unwritten", C.c_int),
+                ("nothing", C.c_longlong), ("clear", C.c_longlong)]
+
+
 RT_VIEW_CAP = 64
 RT_VIEW_SLOT = 1 + RT_VIEW_CAP + RT_VIEW_CAP // 4 + RT_VIEW_CAP // 4    # 16-byte records per block
 RT_VIEW_OVERFLOW, RT_VIEW_NOT_BUILT = 1, 2
@@ -334,6 +340,8 @@ def load_library():
         "rt_scene_set_lights": (ci, [vp, C.POINTER(Light), ci]),
         "rt_scene_set_tile_order": (ci, [vp, ci]),
         "rt_scene_set_view_lists": (ci, [vp, ci]),
+        "rt_scene_set_light_verdicts": (ci, [vp, ci]),
+        "rt_debug_light_verdicts": (ci, [vp, C.POINTER(LightVerdictsInfo), C.POINTER(C.c_uint64), C.c_size_t]),
         "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
         "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
         "rt_debug_tile_order": (ci, [C.POINTER(C.c_uint), ci, ci, ci, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
@@ -827,6 +835,25 @@ class Scene:
     def set_view_lists(self, mode: int):
         """1 (default): the tiles of a frame walk their block's per-view candidate list; 0: every tile culls for itself."""
         _check(self.lib.rt_scene_set_view_lists(self.handle, mode), "rt_scene_set_view_lists")
+
+    def set_light_verdicts(self, mode: int):
+        """1 (default): launches of a resting view skip the lights an earlier launch of the same inputs found to add
+        nothing to a tile, and the occluder search of those it found clear; 0: every launch evaluates every light."""
+        _check(self.lib.rt_scene_set_light_verdicts(self.handle, mode), "rt_scene_set_light_verdicts")
+
+    def light_verdicts(self, want_words: bool = False) -> dict:
+        """What the last frame launch did with light verdicts (waits for the table's writer): state 0 nothing / 1 wrote
+        / 2 read, slot, tiles_x, tiles_y, unwritten, nothing, clear; with want_words also 'words', uint64 [tiles_y,
+        tiles_x]: two bits per (group, light) at 16 * group + 2 * light."""
+        info = LightVerdictsInfo()
+        _check(self.lib.rt_debug_light_verdicts(self.handle, C.byref(info), None, 0), "rt_debug_light_verdicts")
+        d = {k: getattr(info, k) for k, _ in LightVerdictsInfo._fields_}
+        if want_words and info.state:
+            buf = np.zeros(info.tiles_x * info.tiles_y, dtype=np.uint64)
+            _check(self.lib.rt_debug_light_verdicts(self.handle, C.byref(info), buf.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                    buf.size), "rt_debug_light_verdicts")
+            d["words"] = buf.reshape(info.tiles_y, info.tiles_x)
+        return d
 
     def view_lists_info(self, want_lists: bool = False) -> dict:
         """What the last launch read (waits for the lists' build): read, block size, blocks, overflowed and not-built

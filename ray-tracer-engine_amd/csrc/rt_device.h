@@ -264,4 +264,18 @@ struct RtFrameConsts {
     float *aov_normal;          // float4 per pixel
     int *aov_id;                // int2 per pixel
     float *aov_albedo;          // float4 per pixel
+
+    // Light verdicts: one word per tile of the launch's layout, at tile_y * tiles_x + tile_x (the
+    // tile's frame coordinates, after tile_perm). Two bits per (group, light) for the first RT_VERDICT_GROUPS groups of
+    // the tile, in the order the kernel forms them, and the first RT_VERDICT_LIGHTS lights, at 16 * group + 2 * light:
+    // 0 = evaluate, RT_VERDICT_NOTHING = the kernel left this iteration by one of its three "adds nothing" exits,
+    // RT_VERDICT_CLEAR = its all-clear test held. verdict_wr: this launch writes the words it finds; verdict_rd: it
+    // consumes the words an earlier launch of bit-identical inputs wrote (the host keeps the key). Either may be null;
+    // only the one-sample sphere-only product kernel (MODE 0, FEAT 0, CULL) looks at them.
+    const unsigned long long *verdict_rd;
+    unsigned long long *verdict_wr;
 };
+#define RT_VERDICT_GROUPS 4
+#define RT_VERDICT_LIGHTS 8
+#define RT_VERDICT_NOTHING 1u
+#define RT_VERDICT_CLEAR 2u

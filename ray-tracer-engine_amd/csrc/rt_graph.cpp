@@ -331,7 +331,7 @@ extern "C" int rt_graph_launch(rt_frame_graph *g, void *stream)
         if (rc != RT_OK) return rc;
     }
     RT_HIP(hipGraphLaunch(g->exec, (hipStream_t)stream));
-    return rt_scene_note_launch(g->scene, (hipStream_t)stream, nullptr, nullptr);
+    return rt_scene_note_launch(g->scene, (hipStream_t)stream, nullptr, nullptr, nullptr);   // a graph has tables of its own, and no light verdicts
 }
 
 extern "C" int rt_graph_set_camera(rt_frame_graph *g, const rt_camera *cam)

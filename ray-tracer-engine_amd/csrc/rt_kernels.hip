@@ -219,6 +219,8 @@ static RtTraceFn trace_fn(int tile_w, int cull, int mode, int feat, int multi)
 extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int feat,
                                           const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes)
 {
+    // a product launch that was handed a verdict table runs the instantiation that writes (7) or reads (6) it
+    if (mode == 0 && (fc->verdict_wr || fc->verdict_rd)) mode = fc->verdict_wr ? 7 : 6;
     const RtTraceFn fn = trace_fn(tile_w, cull, mode, feat, fc->spp > 1 ? 1 : 0);
     if (!fn) return hipErrorNotSupported;
     *lds_bytes = (unsigned)(RT_LIST_CAP * sizeof(float4) +   // survivor list
@@ -227,7 +229,8 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
                             64 * sizeof(int) +               // marked blocks of a culling pass
                             16 * sizeof(double) +            // atan(k/8)
                             192 * sizeof(float) +            // texel colours per pixel
-                            (feat == 2 ? (RT_BOX_CAP + 128) * sizeof(int) : 0));
+                            (feat == 2 ? (RT_BOX_CAP + 128) * sizeof(int)   // leaf boxes, marked blocks, staged vertices
+                                       : 2 * sizeof(unsigned)));            // the tile's light verdicts (same place)
     const int th = 64 / tile_w;
     *grid = dim3((fc->width + tile_w - 1) / tile_w, (fc->local_rows + th - 1) / th);
     *block = dim3(64);

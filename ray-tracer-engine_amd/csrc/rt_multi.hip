@@ -263,6 +263,9 @@ static int create_impl(rt_multi *m, const int *devices, int n, int transport)
         d.device = devices[i];
         RT_HIP(hipSetDevice(d.device));
         d.scene = rt_scene_create();
+        // (light verdicts stay with single-scene frames: a band or an interleaved share per device is not covered by them)
+        const int vrc = rt_scene_set_light_verdicts(d.scene, 0);
+        if (vrc != RT_OK) return vrc;
         RT_HIP(d.stream.create(hipStreamNonBlocking));
         for (HipEvent &e : d.rendered) RT_HIP(e.create());
         if (transport == RT_MULTI_PEER_COPY) {

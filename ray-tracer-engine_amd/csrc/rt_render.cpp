@@ -410,6 +410,11 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         rc = rt_scene_prepare_tile_order(s, kc, &fc, stream);
         if (rc != RT_OK) return rc;
     }
+    // light verdicts: the plain one-sample frame of a sphere scene (not a reflective frame, whose passes follow)
+    int verdict = -1;
+    rc = rt_scene_prepare_verdicts(s, kc, &fc, reflect_depth == 0 && kc.mode == 0 && kc.feat == 0 && kc.cull && fc.spp == 1, stream,
+                                   &verdict);
+    if (rc != RT_OK) return rc;
     if (samples) {   // the frame kernel per sample, the passes per group, the resolve pass
         rc = rt_reflect_launch_samples(s->refl.get(), &fc, &out, &kc, s->d_spheres.get(), s->n_spheres, reflect_depth, stream);
         if (rc != RT_OK) return rc;
@@ -425,7 +430,10 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         }
     }
     s->view_last = view;
-    return rt_scene_note_launch(s, stream, slot >= 0 ? &s->cones[slot] : nullptr, view >= 0 ? &s->views[view] : nullptr);
+    rc = rt_scene_end_verdicts(s, verdict, stream);
+    if (rc != RT_OK) return rc;
+    return rt_scene_note_launch(s, stream, slot >= 0 ? &s->cones[slot] : nullptr, view >= 0 ? &s->views[view] : nullptr,
+                                verdict >= 0 ? &s->verdicts[verdict] : nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -494,7 +502,7 @@ extern "C" int rt_scene_trace_rays(rt_scene *s, const rt_ray_query *q_in, void *
     fc.aux = s->d_aux.get();
     rc = rt_query_launch(&fc, bvh, s->d_spheres.get(), s->n_spheres, &q, stream);
     if (rc != RT_OK) return rc;
-    return rt_scene_note_launch(s, stream, nullptr, nullptr);   // a query in flight counts as a frame
+    return rt_scene_note_launch(s, stream, nullptr, nullptr, nullptr);   // a query in flight counts as a frame
 }
 
 extern "C" int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd_in, rt_ray *rays_dev, void *stream_)
@@ -526,7 +534,7 @@ extern "C" int rt_scene_primary_rays(rt_scene *s, const rt_frame_desc *fd_in, rt
     if (rc != RT_OK) return rc;
     rc = rt_query_launch_primary(&fc, rays_dev, stream);
     if (rc != RT_OK) return rc;
-    return rt_scene_note_launch(s, stream, nullptr, nullptr);   // it reads the raygen tables
+    return rt_scene_note_launch(s, stream, nullptr, nullptr, nullptr);   // it reads the raygen tables
 }
 
 // A buffer that a post pass reads or writes (p: 0 if the call does not use it).
@@ -1189,7 +1197,7 @@ static int indirect_call(rt_scene *s, const rt_indirect_desc *d_in, int bounces,
     if (s->ind_timing) s->ind_timed = n_ev;
     s->ind_counts = wavefront ? groups * bounces : 0;
     s->ind_bounces = bounces;
-    return rt_scene_note_launch(s, stream, nullptr, nullptr);   // the pass in flight counts as a frame
+    return rt_scene_note_launch(s, stream, nullptr, nullptr, nullptr);   // the pass in flight counts as a frame
 }
 
 extern "C" int rt_scene_indirect(rt_scene *s, const rt_indirect_desc *d, void *stream)

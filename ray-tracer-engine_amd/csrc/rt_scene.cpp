@@ -45,7 +45,7 @@ int rt_scene_wait_all_frames(rt_scene *s, hipStream_t stream)
 }
 
 // A frame has just been enqueued on `stream`: give it the next ring slot, and mark the slots it read with it.
-int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, RtTableSlot *views)
+int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, RtTableSlot *views, RtTableSlot *verdicts)
 {
     const int k = (int)(s->ring_seq % RT_RING);
     RT_HIP(s->ring[k].create());
@@ -53,7 +53,7 @@ int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, Rt
     if (s->ring_used[k]) RT_HIP(hipStreamWaitEvent(stream, s->ring[k].get(), 0));
     RT_HIP(hipEventRecord(s->ring[k].get(), stream));
     s->ring_used[k] = true;
-    for (RtTableSlot *c : {cones, views})
+    for (RtTableSlot *c : {cones, views, verdicts})
         if (c) {
             c->used = true;
             c->last_use = s->ring_seq;
@@ -539,6 +539,16 @@ extern "C" int rt_scene_set_tile_order(rt_scene *s, int mode)
 const float4 *rt_scene_sphere_table(const rt_scene *s) { return s->d_spheres.get(); }
 int rt_scene_sphere_count(const rt_scene *s) { return s->n_spheres; }
 unsigned long long rt_scene_epoch(const rt_scene *s) { return s->epoch; }
+
+extern "C" int rt_scene_set_light_verdicts(rt_scene *s, int mode)
+{
+    if (!s || (mode != 0 && mode != 1)) {
+        rt_set_error("rt_scene_set_light_verdicts: null scene or mode %d not in {0, 1}", mode);
+        return RT_ERR_INVALID;
+    }
+    s->light_verdicts_mode = mode;
+    return RT_OK;
+}
 
 extern "C" int rt_scene_set_view_lists(rt_scene *s, int mode)
 {

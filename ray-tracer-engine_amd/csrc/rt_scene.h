@@ -26,7 +26,11 @@
 //   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
 //       scratch;
 //   (g) whatever rewrites or re-allocates a buffer a recorded graph may point into bumps `epoch`, and nothing else
-//       does: of the hand-over functions only an rt_scene_begin_build whose buffer re-allocates.
+//       does: of the hand-over functions only an rt_scene_begin_build whose buffer re-allocates;
+//   (h) a light-verdict table is written by a frame launch on the frame's own stream, not by a build on the table
+//       stream: that stream is ordered behind the slot's last reader (through the frame ring) and its last writer, the
+//       slot's `built` is the writing launch's event, and readers on other streams wait for it on the device. Its
+//       buffer is in no graph, so growing it (after a quiesce) bumps no epoch.
 #pragma once
 #include <cstring>
 #include <memory>
@@ -38,6 +42,7 @@
 #define RT_RING 4
 #define RT_CONE_SLOTS 3
 #define RT_VIEW_SLOTS 4
+#define RT_VERDICT_SLOTS 4
 
 // One cached device table of a few: built on the table stream after the slot's last reader (through the frame ring),
 // read after `built` (on the device).
@@ -56,6 +61,19 @@ struct ConeSlot : RtTableSlot {
 struct ViewSlot : RtTableSlot {
     unsigned key[18] = {};                // compared by bits: sphere_gen, origin, rotation, eye_nz, aspect, frame size, sample total, block shape
     int nbx = 0, nby = 0, bw = 0, bh = 0;
+};
+
+// Light verdicts (RtFrameConsts::verdict_rd): one table per recent (view, layout), written by a
+// frame launch itself -- `built` is that launch's event on ITS stream -- and read by later launches of the same key.
+struct RtVerdictKey {
+    RtFrameConsts fc;                     // every field the kernel reads; outputs, tile order and the verdict pointers zeroed
+    unsigned long long epoch = 0;         // generation of every table behind fc's pointers that quiesce-and-rewrite mutations touch
+    unsigned long long sphere_gen = 0;    // ... and of the sphere list (tables built from it: cones, view lists, light tables)
+    int tile = 0, cull = 0, mode = 0, feat = 0;
+};
+struct VerdictSlot : RtTableSlot {       // buf: two 64-bit words per float4
+    RtVerdictKey key;
+    int tiles_x = 0, tiles_y = 0;
 };
 
 // The slot a new table replaces: a free one (is_free: it holds nothing a frame could ask for) before an occupied one;
@@ -171,6 +189,13 @@ struct rt_scene {
     ViewSlot views[RT_VIEW_SLOTS];
     int view_lists_mode = 1;                 // rt_scene_set_view_lists
     int view_last = -1;                      // the slot the last launch read, -1: it read none
+    // light verdicts of a resting view
+    VerdictSlot verdicts[RT_VERDICT_SLOTS];
+    int light_verdicts_mode = 1;             // rt_scene_set_light_verdicts
+    RtVerdictKey verdict_prev;               // the key of the previous frame launch ...
+    bool verdict_prev_valid = false;         // ... if that launch could have taken a table at all
+    int verdict_last = -1;                   // the slot the last launch wrote or read, -1: neither
+    int verdict_last_wrote = 0;              // 1: it wrote it
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
     std::unique_ptr<RtReflect, RtReflectDeleter> refl;
     // the two denoisers' scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand; `dn_done`
@@ -236,6 +261,11 @@ int rt_scene_prepare_eye(rt_scene *s, const float org[3], hipStream_t stream, in
 int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelChoice &kc, int cone_slot, RtFrameConsts *fc,
                           hipStream_t stream, int *view_out);
 int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, hipStream_t stream);
+// Light verdicts of a launch whose uniforms are otherwise complete. `eligible`: it runs the one-sample sphere-only
+// product kernel. Points fc at the table it reads or writes (slot index in *slot_out, -1: neither); after the launch
+// rt_scene_end_verdicts records a written table.
+int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out);
+int rt_scene_end_verdicts(rt_scene *s, int slot, hipStream_t stream);
 int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float aspect, int total);
 void rt_raygen_fill(int width, int height, float aspect, int total, float *h);   // the tables' values (host)
 void rt_build_frame_aux(const rt_scene *s, RtFrameAux *ax);

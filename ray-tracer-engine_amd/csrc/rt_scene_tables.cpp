@@ -460,6 +460,140 @@ int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelCh
     return RT_OK;
 }
 
+// Light verdicts (RtFrameConsts::verdict_rd). The key is, bit for bit, everything the frame kernel's
+// decisions depend on: its uniforms (outputs, tile order and the verdict pointers themselves excluded), which
+// instantiation runs, and the generation of what lies behind the uniforms' pointers -- `sphere_gen` for the sphere list
+// and everything built from it, `epoch` for every buffer that is rewritten or re-allocated after a quiesce (textures,
+// sky, RtFrameAux with its lights, light tables, occluder lists, raygen tables, a slot that grew); the cone table and the
+// view lists are rebuilt in place only for another origin, view or sphere list, all of which the key holds.
+// Policy: a launch whose key equals the previous launch's and has no table writes one (MODE 7); launches after that
+// read it (MODE 6); a launch with a new key does neither.
+static void verdict_key(const rt_scene *s, const RtKernelChoice &kc, const RtFrameConsts &fc, RtVerdictKey *k)
+{
+    memset(k, 0, sizeof *k);   // (padding too: the key is compared with memcmp)
+    k->fc = fc;
+    k->fc.rgba = nullptr; k->fc.packed = nullptr; k->fc.packed24 = nullptr; k->fc.stats = nullptr;
+    k->fc.tile_perm = nullptr; k->fc.tile_cost = nullptr;
+    k->fc.aov_depth = nullptr; k->fc.aov_normal = nullptr; k->fc.aov_id = nullptr; k->fc.aov_albedo = nullptr;
+    k->fc.verdict_rd = nullptr; k->fc.verdict_wr = nullptr;
+    k->epoch = s->epoch;
+    k->sphere_gen = s->sphere_gen;
+    k->tile = kc.tile; k->cull = kc.cull; k->mode = kc.mode; k->feat = kc.feat;
+}
+
+int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out)
+{
+    *slot_out = -1;
+    s->verdict_last = -1;
+    s->verdict_last_wrote = 0;
+    if (!eligible || !s->light_verdicts_mode) {
+        s->verdict_prev_valid = false;
+        return RT_OK;
+    }
+    RtVerdictKey key;
+    verdict_key(s, kc, *fc, &key);
+    const int th = 64 / kc.tile;
+    const int tiles_x = (fc->width + kc.tile - 1) / kc.tile, tiles_y = (fc->local_rows + th - 1) / th;   // the launch's grid
+    const size_t words = (size_t)tiles_x * (size_t)tiles_y;
+    int v = -1;
+    for (int i = 0; i < RT_VERDICT_SLOTS; ++i)
+        if (s->verdicts[i].valid && memcmp(&s->verdicts[i].key, &key, sizeof key) == 0) v = i;
+    if (v >= 0) {
+        VerdictSlot &c = s->verdicts[v];
+        if (c.tiles_x != tiles_x || c.tiles_y != tiles_y || c.buf.capacity() * 2 < words) {
+            rt_set_error("rt_scene_render: light verdicts of %d x %d tiles for a launch of %d x %d", c.tiles_x, c.tiles_y, tiles_x, tiles_y);
+            return RT_ERR_INVALID;
+        }
+        RT_HIP(rt_scene_order_reader(c, stream));   // the writing launch precedes its readers
+        fc->verdict_rd = reinterpret_cast<const unsigned long long *>(c.buf.get());
+        *slot_out = v;
+    } else if (s->verdict_prev_valid && memcmp(&s->verdict_prev, &key, sizeof key) == 0) {
+        VerdictSlot &c = rt_slot_victim(s->verdicts, [](const VerdictSlot &x) { return !x.valid; });
+        const size_t total = (words + 1) / 2;   // float4
+        if (total > c.buf.capacity()) {
+            const int rc = rt_scene_quiesce(s);   // nothing may still read or write the buffer that is freed
+            if (rc != RT_OK) return rc;
+            RT_HIP(c.built.host_wait());
+        }
+        c.valid = false;
+        RT_HIP(c.buf.reserve(total));
+        // on the frame's stream: behind the slot's last writer and, through the frame ring, its last reader
+        RT_HIP(c.built.order(stream));
+        if (c.used) {
+            if (s->ring_seq - c.last_use <= RT_RING) RT_HIP(hipStreamWaitEvent(stream, s->ring[c.last_use % RT_RING].get(), 0));
+            else {
+                const int rc = rt_scene_wait_all_frames(s, stream);
+                if (rc != RT_OK) return rc;
+            }
+        }
+        // all ones: a word no launch writes (code 3 is "evaluate" to a reader), so a read-back can count unwritten tiles
+        RT_HIP(hipMemsetAsync(c.buf.get(), 0xff, sizeof(float4) * total, stream));
+        c.key = key;
+        c.tiles_x = tiles_x;
+        c.tiles_y = tiles_y;
+        fc->verdict_wr = reinterpret_cast<unsigned long long *>(c.buf.get());
+        v = (int)(&c - s->verdicts);
+        *slot_out = v;
+        s->verdict_last_wrote = 1;
+    }
+    s->verdict_prev = key;
+    s->verdict_prev_valid = true;
+    s->verdict_last = v;
+    return RT_OK;
+}
+
+// After the launch: a table it wrote becomes readable behind the launch's event.
+int rt_scene_end_verdicts(rt_scene *s, int slot, hipStream_t stream)
+{
+    if (slot < 0 || !s->verdict_last_wrote) return RT_OK;
+    VerdictSlot &c = s->verdicts[slot];
+    RT_HIP(c.built.record(stream));
+    c.valid = true;
+    c.used = false;
+    return RT_OK;
+}
+
+// What the last frame launch on this scene did with light verdicts (waits for the launch that wrote the table).
+extern "C" int rt_debug_light_verdicts(rt_scene *s, rt_light_verdicts_info *out, unsigned long long *words, size_t cap)
+{
+    if (!s || !out) {
+        rt_set_error("rt_debug_light_verdicts: null argument");
+        return RT_ERR_INVALID;
+    }
+    memset(out, 0, sizeof *out);
+    out->slot = -1;
+    if (s->verdict_last < 0) return RT_OK;
+    VerdictSlot &c = s->verdicts[s->verdict_last];
+    if (!c.valid) return RT_OK;   // (a writing launch that failed)
+    RT_HIP(c.built.host_wait());
+    const size_t n = (size_t)c.tiles_x * (size_t)c.tiles_y;
+    std::vector<unsigned long long> h(n);
+    RT_HIP(hipMemcpy(h.data(), c.buf.get(), sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+    out->state = s->verdict_last_wrote ? 1 : 2;
+    out->slot = s->verdict_last;
+    out->tiles_x = c.tiles_x;
+    out->tiles_y = c.tiles_y;
+    for (unsigned long long w : h) {
+        if (w == ~0ull) {
+            out->unwritten++;
+            continue;
+        }
+        for (int b = 0; b < 64; b += 2) {
+            const unsigned code = (unsigned)(w >> b) & 3u;
+            if (code == RT_VERDICT_NOTHING) out->nothing++;
+            if (code == RT_VERDICT_CLEAR) out->clear++;
+        }
+    }
+    if (words) {
+        if (cap < n) {
+            rt_set_error("rt_debug_light_verdicts: room for %zu words, the table has %zu", cap, n);
+            return RT_ERR_INVALID;
+        }
+        memcpy(words, h.data(), sizeof(unsigned long long) * n);
+    }
+    return RT_OK;
+}
+
 void rt_view_lists_summary(const float4 *slots, int blocks, rt_view_lists_info *out)
 {
     long long sum = 0;

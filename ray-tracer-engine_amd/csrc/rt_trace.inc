@@ -1233,7 +1233,10 @@ __device__ __forceinline__ PreSure<N> presure_test(V3 o, const V3 (&dq)[N], floa
 // MODE: 0 = product kernel, 1 = work counters, 2 = every exactness-preserving shortcut off
 // (rt_launch_opts.force_slow_path: tests), 3 = per-phase cycle stamps (s_memtime; RT_TUNING
 // builds only, run time never quoted), 4 = opt-in approximate arithmetic (rt_launch_opts.fast),
-// 5 = the product kernel plus the G-buffer stores (rt_frame_desc.aov_*; one sample, default tile).
+// 5 = the product kernel plus the G-buffer stores (rt_frame_desc.aov_*; one sample, default tile),
+// 6 = the product kernel consuming light verdicts (RtFrameConsts::verdict_rd), 7 = the product kernel recording them
+// (verdict_wr): one-sample launches of sphere scenes, chosen by rt_dev_trace_config from the two pointers -- MODE 0
+// itself carries neither the code nor the registers of either.
 // FEAT: 0 = spheres only (the reference's default scene and every BASELINE config), 1 = with
 // the cube / plane branches of castRay and castLightRay, 2 = with those and the triangle mesh.
 // Each is its own instantiation so that the sphere-only kernel carries neither the code nor
@@ -1241,7 +1244,7 @@ __device__ __forceinline__ PreSure<N> presure_test(V3 o, const V3 (&dq)[N], floa
 // MULTI: the launch may take several samples per pixel (rt_launch_opts.spp > 1). The
 // one-sample kernel has no sample loop: 74 -> 22 spilled scalars and 15 fewer vector registers.
 template <int TW, bool CULL, int MODE, int FEAT = 0, bool MULTI = true>
-__global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_WAVES_MESH_MULTI : RT_MIN_WAVES_MESH) : (MODE == 1) ? 4 : !MULTI ? RT_MIN_WAVES_ONE_SAMPLE : RT_MIN_WAVES_PER_SIMD) void rt_trace_tiles(const RtFrameConsts fc,
+__global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_WAVES_MESH_MULTI : RT_MIN_WAVES_MESH) : (MODE == 1) ? 4 : (MODE == 7) ? RT_MIN_WAVES_PER_SIMD : !MULTI ? RT_MIN_WAVES_ONE_SAMPLE : RT_MIN_WAVES_PER_SIMD) void rt_trace_tiles(const RtFrameConsts fc,
                                                                      const float4 *__restrict__ spheres)
 {
     constexpr int STATS = (MODE == 1) ? 1 : (MODE == 3) ? 2 : 0;
@@ -1313,6 +1316,16 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         blk_y = p >> 16;
     }
     if (fc.tile_cost) t_start = (unsigned)__builtin_amdgcn_s_memtime();
+    // Light verdicts (RtFrameConsts::verdict_rd / verdict_wr). MODE 6: the tile's word of an earlier launch of
+    // bit-identical inputs is asked for here (lanes 0 and 1, a dword each, by the tile's frame coordinates), parked in
+    // the wave's LDS ahead of the light loop and consumed there two bits at a time. MODE 7: the word this launch finds
+    // is gathered in the same place and stored at the write-back. Nothing of it is held in a register across the light
+    // loop, whose scalar and vector files are full.
+    constexpr bool VD_USE = (MODE == 6), VD_REC = (MODE == 7), VERD = VD_USE || VD_REC;
+    static_assert(!VERD || (CULL && FEAT == 0), "light verdicts: the sphere-only culling kernels");
+    unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192)) + wave * 2;
+    unsigned vd_ld = 0;
+    if (VD_USE && lane < 2) vd_ld = reinterpret_cast<const unsigned *>(fc.verdict_rd)[2 * (size_t)(blk_y * tiles_x + blk_x) + lane];
     const int tile_x = blk_x * TW;
     // local row -> global row: a contiguous band, or row blocks dealt round-robin
     // to the ranks of a multi-GPU frame (il_rows is a multiple of the tile rows a
@@ -1752,6 +1765,10 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     reinterpret_cast<float4 *>(o_albedo)[o] = hit ? make_float4(tr, tg, tb, 1.f) : make_float4(fr, fg, fb, 1.f);
             }
         }
+        if (VERD) {   // the tile's word: the verdicts it was handed (MODE 6), or those it finds (MODE 7: none so far)
+            if (lane < 2) myvd[lane] = vd_ld;
+            wave_lds_sync();
+        }
         if (hit_m != 0 && !RT_ABL(16)) {
             // A tile that straddles a silhouette sees several spheres at different
             // depths; one beam around all of their shadow rays would be fat and its
@@ -1817,6 +1834,18 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 }
             }
             for (int li = 0; li < fc.n_lights; ++li) {
+                // An earlier launch of the same inputs left this iteration by one of the three exits marked below:
+                // so would this one, having added nothing -- the iteration is skipped whole.
+                // (groups beyond RT_VERDICT_GROUPS and lights beyond RT_VERDICT_LIGHTS have no bits: always evaluated)
+                const bool vd_has = VERD && g < RT_VERDICT_GROUPS && li < RT_VERDICT_LIGHTS;
+                const int vd_sh = 16 * (g & 1) + 2 * li;
+                unsigned vd = 0;
+                if (VD_USE && vd_has) vd = ((unsigned)__builtin_amdgcn_readfirstlane((int)myvd[g >> 1]) >> vd_sh) & 3u;
+                if (VD_USE && vd == RT_VERDICT_NOTHING) continue;
+                auto vd_note = [&](unsigned code) {
+                    if (VD_REC && vd_has && lane == 0)
+                        (void)__hip_atomic_fetch_or(&myvd[g >> 1], code << vd_sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                };
                 const RtLightDev L = ax->lights[li];
                 const V3 lpos{L.px, L.py, L.pz};
 
@@ -1846,7 +1875,10 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     // texel (checked once per pixel) are finite
                     zero_ok_m = (L.fin != 0.f) ? (tex_fin_m & LM(__builtin_fabsf(a0) < 1.0e30f)) : 0ull;
                     lit_m = inc_m & ~(LM(a0 < -1.0e-4f) & zero_ok_m);   // (facing away: takes no part)
-                    if (lit_m == 0) continue;
+                    if (lit_m == 0) {
+                        vd_note(RT_VERDICT_NOTHING);
+                        continue;
+                    }
                 }
                 const bool lit = lane_in(lit_m);
                 const bool all_zero_ok = (lit_m & ~zero_ok_m) == 0;   // every lit pixel may take a zero brightness as "adds nothing"
@@ -1857,7 +1889,8 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 bool sb_use_list = false;
                 int sbcount = MESH ? fc.n_boxes : 0;
                 float beam_k = 0.f;   // slope of the light's beam (valid when s_use_list)
-                if (CULL) {
+                // (a light whose all-clear test held for these inputs needs neither its list nor the test again)
+                if (CULL && !(VD_USE && vd == RT_VERDICT_CLEAR)) {
                     bool ok = true;
                     Beam b;
                     b.ux = L.ux; b.uy = L.uy; b.uz = L.uz;
@@ -1963,6 +1996,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                         if (may_skip && (cb & 0x40000000)) {
                             if (STATS == 1) hist[7] += 1;
                             wave_lds_sync();
+                            vd_note(RT_VERDICT_NOTHING);
                             continue;
                         }
                         if (MESH && RT_ABL(32768)) {
@@ -2002,7 +2036,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 // unshadowed without constructing one of them: only toL's evolution is
                 // needed for kernel.cu:1541. Typically the list is just the sphere the
                 // tile itself lies on.
-                bool all_clear = false;
+                bool all_clear = VD_USE && vd == RT_VERDICT_CLEAR;
                 if (CULL && (!MESH || (sb_use_list && sbcount == 0)) && s_use_list && scount <= 4 && !force_slow &&
                     !RT_ABL(128) && (!PRIMS || (fc.n_planes | fc.n_cubes) == 0)) {
                     lmask clear = ~0ull;
@@ -2023,6 +2057,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 if (all_clear) {
                     chain.settle();
                     us = (unsigned)RT_SHADOW_SAMPLES << 16;
+                    vd_note(RT_VERDICT_CLEAR);
                     if (STATS == 1) hist[6] += 1;
                 }
                 // The samples will be walked: put the likeliest occluders first -- the spheres that
@@ -2143,6 +2178,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     // zero brightness adds exactly nothing for all of them (finite light, texel and normal.toL: the
                     // condition of the full-occluder skip): b = 0 whatever toL turns out to be -- no chain at all.
                     dark = !RT_ABL(2097152) && all_zero_ok && (lit_m & ~LM(us == 0u)) == 0;
+                    if (dark) vd_note(RT_VERDICT_NOTHING);
                     if (!dark) {
                         chain.begin(lpos, start);   // toL = normalise(l.pos - start), kernel.cu:1438: the exact chain starts here
                         if (!any64((us & 0xffffu) != 0)) chain.settle();
@@ -2333,6 +2369,11 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         if (valid && i < 3) o_packed24[(size_t)(out_idx >> 2) * 3 + (size_t)i] = w24;
     }
 
+    if (VD_REC) {   // the tile's light verdicts as this launch found them (an all-sky tile: 0)
+        unsigned *const o_verdict = reinterpret_cast<unsigned *>(kargs->verdict_wr);
+        wave_lds_sync();
+        if (wb_lane < 2) o_verdict[2 * (size_t)(wb_y * wb_tiles_x + wb_x) + wb_lane] = myvd[wb_lane];
+    }
     if (o_cost) {   // this tile's wave duration, for the order of later frames (a plain store: an atomic maximum
         // per block of tiles here, 256 waves ending together on one address, slowed the whole launch down by 3 %)
         const unsigned dt = (unsigned)__builtin_amdgcn_s_memtime() - t_start;
@@ -2402,8 +2443,9 @@ template <int TW, bool CULL, bool MULTI, int MODE, int FEAT>
 static constexpr bool trace_exists()
 {
 #ifdef RT_QUICK   // kernel experiments (tools/variants.sh): the product instantiation and its brute-force twin only
-    if (TW != 8 || FEAT != 0 || (MODE != 0 && MODE != 1) || (MULTI && MODE != 0)) return false;
+    if (TW != 8 || FEAT != 0 || (MODE != 0 && MODE != 1 && MODE < 6) || (MULTI && MODE != 0)) return false;
 #endif
+    if (MODE >= 6) return CULL && FEAT == 0 && MULTI == (TW != 8);   // light verdicts: the one-sample kernel (other tiles: the sample loop, one pass)
     if (MODE == 4) return TW == 8 && CULL && FEAT < 2;   // fast mode: the product configuration only
     if (MODE == 5) return TW == 8 && !MULTI;             // G-buffer: the one-sample kernels of the default tile
     if (TW != 8 && FEAT >= 1 && MODE != 0) return false;
@@ -2441,6 +2483,8 @@ static RtTraceFn trace_fn_mode_feat(int mode, int feat)
     case 3: return trace_fn_feat<TW, CULL, MULTI, 3>(feat);
     case 4: return trace_fn_feat<TW, CULL, MULTI, 4>(feat);
     case 5: return trace_fn_feat<TW, CULL, MULTI, 5>(feat);
+    case 6: return feat == 0 ? trace_fn_one<TW, CULL, MULTI, 6, 0>() : nullptr;
+    case 7: return feat == 0 ? trace_fn_one<TW, CULL, MULTI, 7, 0>() : nullptr;
     default: return nullptr;
     }
 }

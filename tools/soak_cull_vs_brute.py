@@ -3,7 +3,9 @@
 the device, lean normalise / sqrt, fast texel index) against the brute-force instantiation (the
 reference's loops as written, IEEE forms everywhere), bit for bit. No oracle involved, so frames can
 be large. Every scene is rendered from two cameras in a row (the second one re-uses the scene's
-tables and rebuilds its eye cones), now and then with 4 spp or with the table staged in LDS.
+tables and rebuilds its eye cones), now and then with 4 spp or with the table staged in LDS. Every view is
+rendered --repeat times in a row (default 3) before the brute-force frame, so that the second launch records the
+view's light verdicts and the later ones read them; every one of those frames is compared.
 Prints the seeds that differ (none expected); --json writes a summary for profiles/."""
 import argparse, ctypes as C, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,13 +17,14 @@ ap.add_argument("--width", type=int, default=960)
 ap.add_argument("--height", type=int, default=540)
 ap.add_argument("--seed0", type=int, default=0)
 ap.add_argument("--json", default="")
+ap.add_argument("--repeat", type=int, default=3, help="culled launches per view (3: plain, recording, reading light verdicts)")
 a = ap.parse_args()
 rt = rt_amd.load()
 lib = rt.load_library()
 tex, sky = rt.synth_texture(0), rt.synth_texture(1)
 bad = []
 t0 = time.time()
-frames = pixels = 0
+frames = pixels = read_tables = wrote_tables = 0
 kinds = {"tile": {}, "spp4": 0, "mesh": 0, "prims": 0}
 for k in range(a.scenes):
     seed = a.seed0 + k
@@ -77,23 +80,32 @@ for k in range(a.scenes):
             cam.Org.z += 0.1
             cam.Org.x -= 0.1
             cam.Camyaw += 1.0
-        x = sc.render(a.width, a.height, cam=cam, cull=True, tile=tile, spp=spp)
+        xs = []
+        for rep in range(a.repeat):
+            xs.append(sc.render(a.width, a.height, cam=cam, cull=True, tile=tile, spp=spp))
+            state = sc.light_verdicts()["state"]
+            wrote_tables += state == 1
+            read_tables += state == 2
         y = sc.render(a.width, a.height, cam=cam, cull=False, spp=spp)
         torch.cuda.synchronize()
-        frames += 1
-        pixels += a.width * a.height
-        if not (torch.equal(x["rgba"].view(torch.int32), y["rgba"].view(torch.int32)) and torch.equal(x["packed"], y["packed"])):
-            nbad = int((x["rgba"].view(torch.int32) != y["rgba"].view(torch.int32)).any(dim=2).sum())
-            bad.append((seed, n, tile, view, nbad))
-            print("MISMATCH seed", seed, "spheres", n, "tile", tile, "view", view, "pixels", nbad, flush=True)
+        for rep, x in enumerate(xs):
+            frames += 1
+            pixels += a.width * a.height
+            if not (torch.equal(x["rgba"].view(torch.int32), y["rgba"].view(torch.int32)) and torch.equal(x["packed"], y["packed"])):
+                nbad = int((x["rgba"].view(torch.int32) != y["rgba"].view(torch.int32)).any(dim=2).sum())
+                bad.append((seed, n, tile, view, rep, nbad))
+                print("MISMATCH seed", seed, "spheres", n, "tile", tile, "view", view, "launch", rep, "pixels", nbad, flush=True)
     sc.close()
     if k % 25 == 24:
         print(f"{k + 1} scenes, {len(bad)} mismatches, {time.time() - t0:.0f} s", flush=True)
-print("soak done:", a.scenes, "scenes,", len(bad), "mismatches", bad[:10])
+print("soak done:", a.scenes, "scenes,", frames, "frames,", wrote_tables, "recorded and", read_tables, "read light verdicts,",
+      len(bad), "mismatching frames,", sum(b[-1] for b in bad), "differing pixels", bad[:10])
 if a.json:
     with open(a.json, "w") as f:
         json.dump({"tool": "tools/soak_cull_vs_brute.py", "what": "culled kernel (every shortcut) == brute-force kernel (reference loops, IEEE forms), "
                    "float4 and packed frames bit for bit", "scenes": a.scenes, "seed0": a.seed0, "frames_compared": frames,
-                   "width": a.width, "height": a.height, "pixels_compared": pixels, "mismatching_frames": len(bad),
+                   "width": a.width, "height": a.height, "pixels_compared": pixels, "launches_per_view": a.repeat,
+                   "frames_that_recorded_light_verdicts": int(wrote_tables), "frames_that_read_light_verdicts": int(read_tables),
+                   "mismatching_frames": len(bad), "differing_pixels": int(sum(b[-1] for b in bad)),
                    "mismatches": bad[:50], "mix": kinds, "seconds": round(time.time() - t0, 1)}, f, indent=1)
 sys.exit(1 if bad else 0)
