@@ -866,9 +866,10 @@ int rt_scene_view_lists_info(rt_scene *s, rt_view_lists_info *out, float *slots,
 int rt_debug_view_lists_host(const rt_sphere *spheres, int n, const rt_frame_desc *fd, rt_view_lists_info *out,
                              float *slots, size_t cap, float *beams);
 
-/* Light verdicts of a resting view. 1 (default): the second launch in a row with bit-identical inputs (camera, frame
+/* Light verdicts of a resting view. 1 (default): the second launch with bit-identical inputs (camera, frame
  * size, rows, tile shape, interleave, sphere list, lights, textures; the output buffers and the stream may differ)
- * also writes, per tile, which lights it found to add nothing to any pixel of the tile (all pixels facing away, a full
+ * among the scene's recent launches -- the one before it, or one of a repeating cycle of up to four layouts such as
+ * the row bands of a frame -- also writes, per tile, which lights it found to add nothing to any pixel of the tile (all pixels facing away, a full
  * occluder, every shadow sample of every pixel shadowed) and which it found clear of every occluder; the launches
  * after it skip the former and take the latter's brightness without looking for occluders. A launch with other inputs
  * does neither, so a moving camera renders as it did. One-sample frames of sphere scenes (no cubes, planes or mesh;
@@ -888,6 +889,9 @@ typedef struct rt_light_verdicts_info {
  * table, two bits per (group, light) at 16 * group + 2 * light for the tile's first 4 groups and the first 8 lights:
  * 0 evaluate, 1 adds nothing, 2 all clear.                                                                          */
 int rt_debug_light_verdicts(rt_scene *s, rt_light_verdicts_info *out, unsigned long long *words, size_t cap);
+/* Tests: the long-lived scene rt_launch_raytrace(_ex) and update() render through, for rt_debug_light_verdicts and
+ * rt_scene_view_lists_info; owned by the library, NULL before the first launch.                                     */
+rt_scene *rt_debug_shim_scene(void);
 
 /* hipGraph-captured frame loop (config C4): `passes` samples per pixel + resolve + optional async copy of the packed
  * frame to pinned host memory, recorded once and replayed per frame. passes > 0: the samples are taken by ONE kernel

@@ -342,6 +342,7 @@ def load_library():
         "rt_scene_set_view_lists": (ci, [vp, ci]),
         "rt_scene_set_light_verdicts": (ci, [vp, ci]),
         "rt_debug_light_verdicts": (ci, [vp, C.POINTER(LightVerdictsInfo), C.POINTER(C.c_uint64), C.c_size_t]),
+        "rt_debug_shim_scene": (vp, []),
         "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
         "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
         "rt_debug_tile_order": (ci, [C.POINTER(C.c_uint), ci, ci, ci, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),

@@ -192,8 +192,9 @@ struct rt_scene {
     // light verdicts of a resting view
     VerdictSlot verdicts[RT_VERDICT_SLOTS];
     int light_verdicts_mode = 1;             // rt_scene_set_light_verdicts
-    RtVerdictKey verdict_prev;               // the key of the previous frame launch ...
-    bool verdict_prev_valid = false;         // ... if that launch could have taken a table at all
+    RtVerdictKey verdict_seen[RT_VERDICT_SLOTS];   // keys of recent launches that found no table and wrote none, a ring:
+    bool verdict_seen_valid[RT_VERDICT_SLOTS] = {};   // a key leaves it when its table is written or the ring comes round
+    int verdict_seen_next = 0;               // the entry the next such key replaces
     int verdict_last = -1;                   // the slot the last launch wrote or read, -1: neither
     int verdict_last_wrote = 0;              // 1: it wrote it
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use

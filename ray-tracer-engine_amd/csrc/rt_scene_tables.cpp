@@ -466,8 +466,12 @@ int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelCh
 // and everything built from it, `epoch` for every buffer that is rewritten or re-allocated after a quiesce (textures,
 // sky, RtFrameAux with its lights, light tables, occluder lists, raygen tables, a slot that grew); the cone table and the
 // view lists are rebuilt in place only for another origin, view or sphere list, all of which the key holds.
-// Policy: a launch whose key equals the previous launch's and has no table writes one (MODE 7); launches after that
-// read it (MODE 6); a launch with a new key does neither.
+// Policy: a launch whose key has a table reads it (MODE 6). One whose key has none but is among the scene's last
+// RT_VERDICT_SLOTS table-less keys (verdict_seen) writes one (MODE 7) and leaves that history. A launch with any other
+// key does neither and enters the history in place of its oldest entry: a moving camera records nothing, a view at rest
+// records on its second launch, and so does every layout of a frame rendered as a repeating cycle of up to
+// RT_VERDICT_SLOTS launches (update()'s three row bands) on the cycle's second pass. A launch out of scope leaves the
+// history as it is (it changes nothing a key holds); switching verdicts off clears it.
 static void verdict_key(const rt_scene *s, const RtKernelChoice &kc, const RtFrameConsts &fc, RtVerdictKey *k)
 {
     memset(k, 0, sizeof *k);   // (padding too: the key is compared with memcmp)
@@ -486,18 +490,19 @@ int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameCons
     *slot_out = -1;
     s->verdict_last = -1;
     s->verdict_last_wrote = 0;
-    if (!eligible || !s->light_verdicts_mode) {
-        s->verdict_prev_valid = false;
-        return RT_OK;
-    }
+    if (!s->light_verdicts_mode)
+        for (bool &b : s->verdict_seen_valid) b = false;
+    if (!eligible || !s->light_verdicts_mode) return RT_OK;
     RtVerdictKey key;
     verdict_key(s, kc, *fc, &key);
     const int th = 64 / kc.tile;
     const int tiles_x = (fc->width + kc.tile - 1) / kc.tile, tiles_y = (fc->local_rows + th - 1) / th;   // the launch's grid
     const size_t words = (size_t)tiles_x * (size_t)tiles_y;
-    int v = -1;
-    for (int i = 0; i < RT_VERDICT_SLOTS; ++i)
+    int v = -1, seen = -1;
+    for (int i = 0; i < RT_VERDICT_SLOTS; ++i) {
         if (s->verdicts[i].valid && memcmp(&s->verdicts[i].key, &key, sizeof key) == 0) v = i;
+        if (s->verdict_seen_valid[i] && memcmp(&s->verdict_seen[i], &key, sizeof key) == 0) seen = i;
+    }
     if (v >= 0) {
         VerdictSlot &c = s->verdicts[v];
         if (c.tiles_x != tiles_x || c.tiles_y != tiles_y || c.buf.capacity() * 2 < words) {
@@ -507,7 +512,8 @@ int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameCons
         RT_HIP(rt_scene_order_reader(c, stream));   // the writing launch precedes its readers
         fc->verdict_rd = reinterpret_cast<const unsigned long long *>(c.buf.get());
         *slot_out = v;
-    } else if (s->verdict_prev_valid && memcmp(&s->verdict_prev, &key, sizeof key) == 0) {
+    } else if (seen >= 0) {
+        s->verdict_seen_valid[seen] = false;
         VerdictSlot &c = rt_slot_victim(s->verdicts, [](const VerdictSlot &x) { return !x.valid; });
         const size_t total = (words + 1) / 2;   // float4
         if (total > c.buf.capacity()) {
@@ -535,9 +541,11 @@ int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameCons
         v = (int)(&c - s->verdicts);
         *slot_out = v;
         s->verdict_last_wrote = 1;
+    } else {
+        s->verdict_seen[s->verdict_seen_next] = key;
+        s->verdict_seen_valid[s->verdict_seen_next] = true;
+        s->verdict_seen_next = (s->verdict_seen_next + 1) % RT_VERDICT_SLOTS;
     }
-    s->verdict_prev = key;
-    s->verdict_prev_valid = true;
     s->verdict_last = v;
     return RT_OK;
 }

@@ -15,6 +15,9 @@ struct ShimCache {
 };
 static ShimCache g_shim;
 
+// Tests: the scene rt_launch_raytrace and update() render through (null before the first launch).
+extern "C" rt_scene *rt_debug_shim_scene(void) { return g_shim.scene; }
+
 // memManager::operator delete on something the shim has mirrored: the next launch re-uploads.
 void rt_shim_forget(const void *ptr)
 {

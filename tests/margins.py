@@ -521,6 +521,84 @@ def prepass_guard(rt, oracle, seed):
     return m
 
 
+# ---------------------------------------------------------------------------------------------- row 6b: facing away
+FACING = -1.0e-4          # the kernel's `a0 < -1.0e-4f` (rt_trace.inc: "facing away: takes no part")
+
+
+def _amap(m, tr, a):
+    """Per hit pixel values `a` as a frame [h, w]; NaN where the closest hit is not sphere 0."""
+    out = np.full(m.w * m.h, np.nan)
+    on = _on_s(tr)
+    out[tr.hits[on]] = a[on]
+    return out.reshape(m.h, m.w)
+
+
+def facing_tiles(m, tr, a, lo=None, hi=None):
+    """(tx, ty) of the 8 x 8 tiles that lie wholly inside the frame, whose 64 pixels all hit sphere 0 and whose 64 values
+    of `a` (per hit pixel, as facing() returns them) all lie below `hi` / above `lo`."""
+    amap = _amap(m, tr, a)
+    out = []
+    for ty in range(m.h // 8):
+        for tx in range(m.w // 8):
+            t = amap[ty * 8:ty * 8 + 8, tx * 8:tx * 8 + 8]
+            if np.isnan(t).any():
+                continue
+            if (hi is None or (t < hi).all()) and (lo is None or (t > lo).all()):
+                out.append((tx, ty))
+    return out
+
+
+def facing_away(rt, oracle, seed):
+    """Ledger row "a light for lanes facing away" (normal.toL < -1e-4 with finite factors: the lane takes no part in the
+    light; a group all of whose lanes do leaves the light, which is the first of the three exits a light verdict records).
+    Light 0 is placed so that the binary64 a = normal.toL of the patch's centre pixel, from the reference's start and
+    normal, is -1e-4 x (1 + delta), and the patch is so narrow that a changes by a few 1e-6 per pixel: the bound crosses
+    the frame. Nothing but S and the far clutter: S hides no shadow ray that leaves it this flat (|a| < sqrt(2e-5 / R)).
+    Witness: hit pixels on S within 5e-6 of the bound on either side; 8 x 8 tiles of S-hits wholly 1e-5 below the bound
+    (ten times the 1e-6 the kernel's approximate toL is good for) and tiles wholly 1e-5 above it; `open`: every pixel of
+    S has a sample of light 0 that no sphere hits, so the light is not dark for any tile."""
+    rng = np.random.default_rng(650 + seed)
+    R = float(rng.uniform(0.4, 1.0))
+    target = FACING * (1 + _sweep(seed // 2))
+    w, h = 48, 36
+    m, tr, k0 = _patch(rt, oracle, rng, R, 3.0e-6 * w * R, FACING, w, h)
+    # light 0 again, from the reference's start and normal of the centre pixel: a(k0) = target
+    n0 = tr.normal[k0].astype(np.float64)
+    n0 /= np.linalg.norm(n0)
+    lp0 = np.array(m.lights[0][0], dtype=np.float64) - tr.starts[k0].astype(np.float64)
+    dist = float(np.linalg.norm(lp0))
+    t0 = lp0 - lp0.dot(n0) * n0
+    t0 /= np.linalg.norm(t0)
+    lp = tr.starts[k0].astype(np.float64) + (n0 * target + t0 * np.sqrt(1 - target * target)) * dist
+    size = (0.0, m.lights[0][1])[seed % 2]           # even seeds: a point light, ten identical samples
+    lights = [(tuple(lp), size, *m.lights[0][2:])] + m.lights[1:]
+    m = Margin("facing_away", seed, m.spheres, lights, m.cam, m.aspect, w, h, {})
+    tr = trace(rt, oracle, m)
+    a = facing(tr, np.array(lights[0][0], dtype=np.float32))
+    on = _on_s(tr)
+    below = on[(a[on] >= FACING - 5e-6) & (a[on] < FACING)]
+    above = on[(a[on] >= FACING) & (a[on] <= FACING + 5e-6)]
+    open_ = True
+    for k in on:
+        q = quad(tr.tab, np.repeat(tr.starts[k:k + 1], 10, axis=0), tr.dirs[k, 0])
+        open_ = open_ and bool((~q["hit"].any(axis=1)).any())
+    # the texel most pixels of the patch read (kernel.cu:1653: int(ty * height) * width + int(tx * width), clamped)
+    from query_ref import f2i
+    th, tw = tr.inp.tex[0].shape
+    ci = [min(max(int(f2i(f32(tr.rec["ty"][p] * f32(th)))) * tw + int(f2i(f32(tr.rec["tx"][p] * f32(tw)))), 0), tw * th - 1)
+          for p in tr.hits[on]]
+    vals, counts = np.unique(ci, return_counts=True)
+    texel = int(vals[np.argmax(counts)])
+    amap = _amap(m, tr, a)
+    with np.errstate(all="ignore"):
+        per_pixel = float(np.hypot(np.nanmedian(np.abs(np.diff(amap, axis=1))), np.nanmedian(np.abs(np.diff(amap, axis=0)))))
+    m.witness = {"pixels": [_pix(tr, m, k) for k in np.concatenate([below, above])],
+                 "below": len(below), "above": len(above), "centre": float(a[k0]), "target": target, "per_pixel": per_pixel,
+                 "away_tiles": facing_tiles(m, tr, a, hi=FACING - 1e-5), "lit_tiles": facing_tiles(m, tr, a, lo=FACING + 1e-5),
+                 "open": open_, "texel": (texel // tw, texel % tw), "texel_pixels": int(counts.max())}
+    return m
+
+
 # ---------------------------------------------------------------------------------------------- row 7: full occluder
 FULL_STEPS = 40
 
@@ -574,6 +652,30 @@ def full_occluder(rt, oracle, seed):
         (full if nh == 10 else part if nh > 0 else []).append(_pix(tr, m, k))
     eff = float(np.sqrt(np.float64(tr.tab[1, 3])))
     m.witness = {"pixels": full + part, "full": full, "partial": part, "centre_hits": centre, "rel": eff / r_edge - 1}
+    return m
+
+
+def full_occluder_inside(rt, oracle, seed):
+    """The same ledger row away from its edge: the base scenes of full_occluder with the occluder's radius 3 and 4 times
+    r_edge. The sweep above stays within 1e-2 of the edge, where the kernel's test of the whole group's beam against one
+    sphere (conservative: the group's ball, the padded slope) never holds -- measured: not below 1.5 r_edge, in every tile
+    only from about 3 r_edge on -- so that none of its scenes takes the exit that skips the light. These do. Witness: pixels
+    of S whose ten samples of light 0 all hit the occluder, and the 8 x 8 tiles that consist of such pixels only."""
+    base, big = seed % 2, (3.0, 4.0)[(seed // 2) % 2]
+    m = full_occluder(rt, oracle, base * FULL_STEPS + FULL_STEPS - 1)
+    x, y, z, r = m.spheres[1]
+    spheres = list(m.spheres)
+    spheres[1] = (x, y, z, float(np.sqrt(r * r * big)))
+    m = Margin("full_occluder_inside", seed, spheres, m.lights, m.cam, m.aspect, m.w, m.h, {})
+    tr = trace(rt, oracle, m)
+    on = _on_s(tr)
+    q = _samples(tr, on, 1)
+    full = [_pix(tr, m, k) for k, row in zip(on, q["hit"]) if row.all()]
+    fmap = np.zeros((m.h, m.w), dtype=bool)
+    for x_, y_ in full:
+        fmap[y_, x_] = True
+    tiles = sum(bool(fmap[ty:ty + 8, tx:tx + 8].all()) for ty in range(0, m.h - 7, 8) for tx in range(0, m.w - 7, 8))
+    m.witness = {"pixels": full, "full": len(full), "on_s": len(on), "full_tiles": tiles, "factor": big}
     return m
 
 
@@ -638,6 +740,8 @@ BUILDERS = {
     "shortcut_sure": (shortcut_sure, list(range(18))),
     "shortcut_behind": (shortcut_behind, list(range(9))),
     "prepass_guard": (prepass_guard, list(range(18))),
+    "facing_away": (facing_away, list(range(18))),
     "full_occluder": (full_occluder, list(range(2 * FULL_STEPS))),
+    "full_occluder_inside": (full_occluder_inside, list(range(4))),
     "front_to_back": (front_to_back, list(range(16))),
 }

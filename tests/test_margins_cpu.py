@@ -28,8 +28,15 @@ def test_witness_is_on_its_bound(rt, oracle, name, seed):
         assert w["above"] > 0 and w["below"] > 0
     elif name == "shortcut_behind":
         assert w["above"] > 0 and w["below"] > 0 and w["pre_above"] > 0 and w["pre_below"] > 0
+    elif name == "facing_away":
+        assert w["below"] >= 8 and w["above"] >= 8                # S-hits within 5e-6 of -1e-4, on either side
+        assert w["away_tiles"] and w["lit_tiles"]                 # whole tiles 1e-5 clear of the bound, on either side
+        assert abs(w["centre"] / w["target"] - 1) < 1e-3 and 1e-6 < w["per_pixel"] < 1e-5
+        assert w["open"]                                          # no pixel of S has all ten samples of light 0 shadowed
     elif name == "full_occluder":
         assert abs(w["rel"]) <= 1.0001e-2 and w["centre_hits"] is not None
+    elif name == "full_occluder_inside":
+        assert w["full"] > w["on_s"] // 2 and w["full_tiles"] >= 6 and w["factor"] >= 3   # whole tiles in full shadow
     elif name == "front_to_back":
         assert max(w["ulp_gaps"]) <= 1 and w["normals_differ"] > 0   # different spheres meet: the list position decides
 

@@ -1,0 +1,78 @@
+"""A resting view rendered through all three frame kernels: the first launch of a key runs the
+plain kernel (MODE 0), the second records the tile's light verdicts (MODE 7), every later one reads them (MODE 6).
+`resting` renders the same frame several times on one long-lived scene and holds every launch to the same expected
+frame, which the callers take from the oracle (or, where the oracle is too slow, from the brute-force kernel of a
+scene of its own with the switch off)."""
+import numpy as np
+
+from scenes import _bits
+
+GROUPS, LIGHTS = 4, 8         # RT_VERDICT_GROUPS, RT_VERDICT_LIGHTS: two bits per (group, light) at 16 * group + 2 * light
+NOTHING, CLEAR = 1, 2         # RT_VERDICT_NOTHING, RT_VERDICT_CLEAR
+
+
+def frame(scene, width, height, **kw):
+    """(float4 bits, packed words) of one launch."""
+    import torch
+    out = scene.render(width, height, **kw)
+    torch.cuda.synchronize()
+    return _bits(out["rgba"].cpu().numpy()), out["packed"].cpu().numpy().view(np.uint32)
+
+
+def oracle_frame(oracle, sc, width, height, y0=0, y1=None, nthreads=16):
+    """The oracle's (float4 bits, packed words) of rows [y0, y1) for a scenes.Scn / scenes.Inputs-like `sc`."""
+    rgba, packed, _ = oracle.render(sc.spheres, sc.n, sc.tex, sc.sky, sc.sky_box, sc.lights, sc.n_lights, sc.cam, width, height,
+                                    sc.aspect, y0=y0, y1=y1 if y1 else None, nthreads=nthreads)
+    return _bits(rgba), packed
+
+
+def differing(got, want, nan_equal=False):
+    """(pixels whose float4 differs, pixels whose packed word differs); nan_equal: a NaN matches any NaN."""
+    d = got[0] != want[0]
+    if nan_equal:
+        d &= ~(np.isnan(got[0].view(np.float32)) & np.isnan(want[0].view(np.float32)))
+    return int(d.any(axis=-1).sum()), int((got[1] != want[1]).sum())
+
+
+def assert_same(got, want, what, nan_equal=False):
+    assert got[0].shape == want[0].shape and got[1].shape == want[1].shape, (what, got[0].shape, want[0].shape)
+    assert differing(got, want, nan_equal) == (0, 0), (what, differing(got, want, nan_equal))
+
+
+def grid(width, height, kw):
+    """tiles_x, tiles_y of the launch: tiles are `tile` wide and 64 / tile high over the launch's own rows."""
+    from rt_amd import load
+    tile = kw.get("tile") or 8
+    rows = (kw.get("y1") or height) - kw.get("y0", 0)
+    if kw.get("interleave") is not None:
+        cnt, idx, blk = kw["interleave"]
+        rows = len(load().interleaved_rows(rows, idx, cnt, blk or 16))
+    th = 64 // tile
+    return (width + tile - 1) // tile, (rows + th - 1) // th
+
+
+def codes(words):
+    """uint64 [...] -> codes [..., GROUPS, LIGHTS]."""
+    sh = np.array([[16 * g + 2 * li for li in range(LIGHTS)] for g in range(GROUPS)], dtype=np.uint64)
+    return ((words[..., None, None] >> sh) & np.uint64(3)).astype(np.int64)
+
+
+def resting(scene, render_kwargs, want, launches=4, nan_equal=False, what="", allowed_states=None):
+    """Renders the frame `render_kwargs` (width, height and Scene.render's options) `launches` times on `scene`. Every
+    launch gives `want` = (float4 bits, packed words); the launches go nothing, write, read, read ... (allowed_states:
+    the sequences a caller accepts instead); the writing launch leaves no tile of its grid unwritten. -> the recorded
+    words, uint64 [tiles_y, tiles_x] (None if no launch wrote)."""
+    kw = dict(render_kwargs)
+    width, height = kw.pop("width"), kw.pop("height")
+    states, words = [], None
+    for k in range(launches):
+        got = frame(scene, width, height, **kw)
+        info = scene.light_verdicts(want_words=(k == 1))
+        assert_same(got, want, "%s launch %d (state %d)" % (what, k, info["state"]), nan_equal)
+        states.append(info["state"])
+        if k == 1 and info["state"] == 1:
+            assert info["unwritten"] == 0, (what, info)
+            assert (info["tiles_x"], info["tiles_y"]) == grid(width, height, kw), (what, info, grid(width, height, kw))
+            words = info["words"]
+    assert states in [list(s) for s in (allowed_states or [([0, 1] + [2] * launches)[:launches]])], (what, states)
+    return words
