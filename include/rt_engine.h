@@ -831,6 +831,93 @@ int rt_scene_upsample(rt_scene *s, const rt_upsample_desc *d, void *stream);
 int rt_scene_set_upsample_timing(rt_scene *s, int on);
 int rt_scene_upsample_times(rt_scene *s, float *ms, int cap, int *n);
 
+/* ------------------------------------------------------------------ *
+ * The display transform: the stage that ends the       *
+ * chain. A float colour of high dynamic range is metered, exposed,    *
+ * tone-mapped and packed, linearly or sRGB-encoded.                    *
+ * ------------------------------------------------------------------ */
+#define RT_DISPLAY_BINS 512            /* luminance bins: sixteen per octave from 2^-16 to 2^16 */
+#define RT_DISPLAY_METER_MANUAL 0
+#define RT_DISPLAY_METER_AUTO 1
+#define RT_DISPLAY_METER_LAGGED 2
+#define RT_DISPLAY_CLIP 0
+#define RT_DISPLAY_REINHARD 1
+#define RT_DISPLAY_ACES 2
+#define RT_DISPLAY_LINEAR 0
+#define RT_DISPLAY_SRGB 1
+
+typedef struct rt_display_desc {
+    uint32_t struct_size;         /* sizeof(rt_display_desc); 0 reads as this layout. Fields past a caller's size read as 0  */
+    int width, height;            /* whole frames, each in [1, RT_DENOISE_MAX_SIZE]                                          */
+    const float *rgba_in;         /* device, float4, 16-byte aligned: the colour to show                                     */
+    const int *id;                /* NULL, or device, int2 (kind, index), 8-byte aligned: read by the metering only          */
+    float *rgba_out;              /* NULL, or device, float4, 16-byte aligned: the display-linear colour after the curve,
+                                     alpha copied bit for bit; may be rgba_in itself                                         */
+    uint32_t *pixels;             /* NULL, or device: the packed words                                                       */
+    float *state;                 /* device, float[4], 16-byte aligned, kept by the caller from call to call like a temporal
+                                     history: {exposure, metered luminance, metered share of the pixels, valid}; all zero =
+                                     no state yet. Required unless meter is RT_DISPLAY_METER_MANUAL, which does not touch it  */
+    uint32_t *histogram_out;      /* NULL, or device, uint32[RT_DISPLAY_BINS]: the metered histogram (not with MANUAL)       */
+    int meter;                    /* RT_DISPLAY_METER_*                                                             [AUTO]   */
+    float exposure;               /* finite, > 0: the manual exposure, and the fallback where nothing can be metered   [1]   */
+    float key;                    /* finite, > 0: the metered luminance is brought to it                            [0.18]   */
+    float min_exposure;           /* finite, > 0, min <= max: the limits of a metered exposure              [2^-6]           */
+    float max_exposure;           /*                                                                          [2^6]          */
+    int meter_low, meter_high;    /* the window of the ranked luminances in 1/1024ths, 0 <= low < high <= 1024 [512] [973]   */
+    float adapt;                  /* in (0, 1]: the share of the way from the state's exposure to the metered one       [1]   */
+    int meter_sky;                /* non-zero: pixels without a hit (id kind < 0) are metered too                       [0]   */
+    int curve;                    /* RT_DISPLAY_CLIP, _REINHARD, _ACES                                               [ACES]   */
+    float white;                  /* finite, > 0: Reinhard's white point                                               [4]   */
+    int transfer;                 /* RT_DISPLAY_LINEAR (rgbToInt(c * 254), today's pack), RT_DISPLAY_SRGB            [SRGB]   */
+    int variant;                  /* 0: the product (a strided kernel, the histogram and the thresholds in LDS); 1: the
+                                     plain yardstick (a thread per pixel, global atomics, the table from global memory, a
+                                     serial resolve). The same bits                                                          */
+} rt_display_desc;
+
+/* The defaults in brackets above; sizes and pointers 0. */
+void rt_display_desc_init(rt_display_desc *d);
+
+/* T[0 .. 255], the thresholds of the sRGB encoding: T[0] = 0, T[v] = the binary32 nearest to EOTF((v - 0.5) / 255) with
+ * EOTF(c) = c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4), formed in binary64 on the host; strictly
+ * increasing. A channel's code is the number of v in 1 .. 255 with o >= T[v]. The kernels read this very table. */
+int rt_display_transfer_table(float out[256]);
+
+/* Shows rgba_in on `stream` (a hipStream_t; NULL = the null stream); (r, g, b, a) = rgba_in[p]. Binary32 + - * / and
+ * compares on colours, integers on the histogram, T for the encoding: defined to the bit, both variants the same bits.
+ * 1. Metering (AUTO, LAGGED): l = (0.2126 r + 0.7152 g) + 0.0722 b. p is metered iff l > 0, l is finite and (meter_sky
+ *    != 0, or id is NULL, or id[p].kind >= 0); its bin is k = clamp((bits(l) >> 19) - 1776, 0, 511); h[k] counts.
+ * 2. Resolve: N = sum h; e0 = state[0] and valid0 = (state[3] == 1) as they were on entry. N == 0: e = valid0 ? e0 :
+ *    exposure, the state becomes (e, 0, 0, 1) and histogram_out is not written. Otherwise, in 64-bit integers, lo =
+ *    (N meter_low) >> 10, hi = (N meter_high + 1023) >> 10; with cum the exclusive prefix sum of h, take_k = max(0,
+ *    min(cum[k + 1], hi) - max(cum[k], lo)); s = sum take_k k; m = (256 s) / (hi - lo); Lm = the float with the bits
+ *    (1776 << 19) + (m << 11) + (1 << 18); et = key / Lm, raised to min_exposure, then lowered to max_exposure; e =
+ *    (valid0 and adapt < 1) ? e0 + (et - e0) adapt : et; the state becomes (e, Lm, float(N) / float(width height), 1)
+ *    and histogram_out receives h.
+ * 3. The exposure applied, E: MANUAL: exposure; AUTO: the e this call resolved; LAGGED: valid0 ? e0 : exposure -- the
+ *    frame is shown with the exposure its predecessor resolved and read once.
+ * 4. The curve on c = (r E, g E, b E). CLIP: o = c. REINHARD: L = max(luma(c), 0), o = c ((1 + L / (white white)) /
+ *    (1 + L)). ACES, per channel: x = min(max(c, 0), 1024), o = (x (2.51 x + 0.03)) / (x (2.43 x + 0.59) + 0.14).
+ *    After REINHARD and ACES o = min(max(o, 0), 1) (a NaN gives 0). rgba_out[p] = (o, a).
+ * 5. The pack. LINEAR: rgbToInt(o * 254). SRGB: (code(o.r) << 16) + (code(o.g) << 8) + code(o.b) by T; a NaN gives 0.
+ * With MANUAL, exposure 1, CLIP and LINEAR the call returns rgba_in's own bits and the frame's own packed words.
+ * A call with both outputs NULL and a metering mode only meters. The call enqueues (AUTO: the metering, the resolve,
+ * the apply pass; LAGGED: one fused pass, the resolve; MANUAL: the apply pass) and returns; E is read from `state` on
+ * the device and there is no host wait. The histogram scratch is the scene's and is cleared at the head of every call;
+ * calls of one scene on different streams are ordered on the device, one after the other (an event). Ordering the call
+ * after the work that wrote rgba_in, id and state, and a reader of the outputs and of state after the call, is the
+ * caller's. Before anything is enqueued, and with nothing written: NULL or misaligned pointers (rgba_in, rgba_out and
+ * state 16 bytes, id 8, pixels and histogram_out 4), sizes, meter, curve, transfer or variant out of range, knobs
+ * that are not finite or out of range, no output with MANUAL, state missing with AUTO or LAGGED, an output that
+ * overlaps an input or another output (only rgba_out may be rgba_in itself) -> RT_ERR_INVALID; a stream that is being
+ * captured -> RT_ERR_UNSUPPORTED. */
+int rt_scene_display(rt_scene *s, const rt_display_desc *d, void *stream);
+
+/* Device time of every launch of the scene's later display calls (off by default). rt_scene_display_times waits for
+ * the last call and fills ms[0 .. *n - 1]: AUTO: metering, resolve, apply; LAGGED: the fused pass, resolve; MANUAL: the
+ * apply pass. cap: room in ms. */
+int rt_scene_set_display_timing(rt_scene *s, int on);
+int rt_scene_display_times(rt_scene *s, float *ms, int cap, int *n);
+
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
  * tile first -- the frame kernel records every tile's wave duration, and from the previous launch's durations the
  * blocks are sorted on the device (three small kernels, ~15 us): after 1, 2, 4, 8, 16, 32, 64, 96, ... launches of an

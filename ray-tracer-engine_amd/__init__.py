@@ -246,6 +246,26 @@ class IndirectDesc(C.Structure):
 RT_INDIRECT_MAX_RAYS = 16
 
 
+class DisplayDesc(C.Structure):
+    """rt_display_desc."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
+                ("rgba_in", C.c_void_p), ("id", C.c_void_p), ("rgba_out", C.c_void_p), ("pixels", C.c_void_p),
+                ("state", C.c_void_p), ("histogram_out", C.c_void_p),
+                ("meter", C.c_int), ("exposure", C.c_float), ("key", C.c_float), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("meter_low", C.c_int), ("meter_high", C.c_int), ("adapt", C.c_float),
+                ("meter_sky", C.c_int), ("curve", C.c_int), ("white", C.c_float), ("transfer", C.c_int),
+                ("variant", C.c_int)]
+
+
+RT_DISPLAY_BINS = 512
+RT_DISPLAY_METER_MANUAL, RT_DISPLAY_METER_AUTO, RT_DISPLAY_METER_LAGGED = 0, 1, 2
+RT_DISPLAY_CLIP, RT_DISPLAY_REINHARD, RT_DISPLAY_ACES = 0, 1, 2
+RT_DISPLAY_LINEAR, RT_DISPLAY_SRGB = 0, 1
+_DISPLAY_METERS = {"manual": RT_DISPLAY_METER_MANUAL, "auto": RT_DISPLAY_METER_AUTO, "lagged": RT_DISPLAY_METER_LAGGED}
+_DISPLAY_CURVES = {"clip": RT_DISPLAY_CLIP, "reinhard": RT_DISPLAY_REINHARD, "aces": RT_DISPLAY_ACES}
+_DISPLAY_TRANSFERS = {"linear": RT_DISPLAY_LINEAR, "srgb": RT_DISPLAY_SRGB}
+
+
 class IndirectPathsOpts(C.Structure):
     """rt_indirect_paths_opts."""
     _fields_ = [("struct_size", C.c_uint32), ("bounces", C.c_int)]
@@ -443,6 +463,11 @@ def load_library():
         "rt_debug_indirect_path_counts": (ci, [vp, C.POINTER(ci), ci, C.POINTER(ci)]),
         "rt_debug_indirect_path_key": (ci, [C.POINTER(C.c_uint), ci, ci, C.POINTER(C.c_uint)]),
         "rt_debug_reflect_dispatch": (ci, [vp, C.POINTER(ci), ci]),
+        "rt_display_desc_init": (None, [C.POINTER(DisplayDesc)]),
+        "rt_display_transfer_table": (ci, [fp]),
+        "rt_scene_display": (ci, [vp, C.POINTER(DisplayDesc), vp]),
+        "rt_scene_set_display_timing": (ci, [vp, ci]),
+        "rt_scene_display_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -1587,3 +1612,89 @@ class Scene:
         it): variant 1: the kernel; variant 0: per group of at most 4 rays the cast pass, the shade pass (bounces = 1)
         or one shade-and-continue pass per bounce, and the resolve pass."""
         return self._pass_times("indirect", (2 + RT_INDIRECT_MAX_BOUNCES) * ((RT_INDIRECT_MAX_RAYS + 3) // 4))
+
+    # ---------------------------------------------------------------- the display transform (DESIGN.md 6r)
+    def display_desc(self, width, height, *, rgba_in=0, id=0, rgba_out=0, pixels=0, state=0, histogram_out=0, meter=None,
+                     exposure=None, key=None, min_exposure=None, max_exposure=None, meter_low=None, meter_high=None,
+                     adapt=None, meter_sky=None, curve=None, white=None, transfer=None, variant=0) -> DisplayDesc:
+        """rt_display_desc with rt_display_desc_init's defaults where an argument is None."""
+        return self._desc(DisplayDesc, "rt_display_desc_init",
+                          dict(width=width, height=height, rgba_in=rgba_in, id=id, rgba_out=rgba_out, pixels=pixels,
+                               state=state, histogram_out=histogram_out),
+                          dict(meter=meter, exposure=exposure, key=key, min_exposure=min_exposure,
+                               max_exposure=max_exposure, meter_low=meter_low, meter_high=meter_high, adapt=adapt,
+                               curve=curve, white=white, transfer=transfer, variant=variant),
+                          dict(meter_sky=meter_sky))
+
+    def display_raw(self, d: DisplayDesc, stream=0) -> int:
+        """rt_scene_display as is: returns the status."""
+        return self.lib.rt_scene_display(self.handle, C.byref(d), stream)
+
+    def display(self, frame, state=None, *, meter="auto", exposure=None, key=None, window=None, limits=None, adapt=None,
+                meter_sky=None, curve="aces", white=None, transfer="srgb", want_rgba=True, want_packed=True,
+                want_histogram=False, variant=0, stream=None):
+        """Show a float colour: meter it, expose it, run it through a tone curve and pack it (rt_scene_display; None:
+        the default of rt_display_desc_init). `frame`: a frame dict (its "rgba", and its id guide where it has one: sky
+        pixels are then not metered unless meter_sky) or a bare CUDA float32 [H, W, 4] tensor. `state`: the "state" an
+        earlier call returned, or None for a zeroed one; it is updated in place. meter: "auto" (this frame's own
+        exposure), "lagged" (the state's exposure, the frame read once; its histogram resolves the next one) or
+        "manual" (`exposure`; no state). window: (meter_low, meter_high) in 1/1024ths; limits: (min_exposure,
+        max_exposure). Returns {'rgba': float32 [H, W, 4] or None, 'pixels': int32 [H, W] or None, 'state': float32
+        [4] or None, 'histogram': int32 [RT_DISPLAY_BINS] or None} as new tensors but the state; the frame is not
+        written. Enqueued on `stream` (default: the current stream); no host wait."""
+        for name, value, table in (("meter", meter, _DISPLAY_METERS), ("curve", curve, _DISPLAY_CURVES),
+                                   ("transfer", transfer, _DISPLAY_TRANSFERS)):
+            if value not in table:
+                raise RtError(f"display: {name} must be one of {sorted(table)}, not {value!r}")
+        for name, pair in (("window", window), ("limits", limits)):
+            if pair is not None and len(pair) != 2:
+                raise RtError(f"display: {name} must be a pair")
+        torch = self._need_gpu("the display transform")
+        rgba, ids = frame, None
+        if isinstance(frame, dict):
+            rgba, ids = frame.get("rgba"), (frame.get("aov") or {}).get("id")
+        if (not isinstance(rgba, torch.Tensor) or rgba.dim() != 3 or rgba.shape[2] != 4 or rgba.dtype != torch.float32
+                or not rgba.is_cuda):
+            raise RtError("display: the colour must be a CUDA float32 tensor of shape [H, W, 4] (or a frame with such an rgba)")
+        rgba = rgba.contiguous()
+        H, W = rgba.shape[0], rgba.shape[1]
+        metering = meter != "manual"
+        if ids is not None and metering:
+            if tuple(ids.shape) != (H, W, 2) or ids.dtype != torch.int32 or ids.device != rgba.device:
+                raise RtError("display: the id guide must be an int32 tensor of shape [H, W, 2] beside the colour")
+            ids = ids.contiguous()
+        st = self._stream(torch, stream)
+        if metering:
+            if state is None:
+                with torch.cuda.stream(st):           # cleared on the stream the pass runs on
+                    state = torch.zeros(4, dtype=torch.float32, device=rgba.device)
+            elif (not isinstance(state, torch.Tensor) or tuple(state.shape) != (4,) or state.dtype != torch.float32
+                  or state.device != rgba.device or not state.is_contiguous()):
+                raise RtError("display: state must be a contiguous float32 tensor of shape [4] beside the colour")
+        else:
+            state = None
+        out = self._new(torch, want_rgba, rgba, (H, W, 4), torch.float32)
+        packed = self._new(torch, want_packed, rgba, (H, W), torch.int32)
+        hist = None
+        if want_histogram and metering:               # a call that meters nothing writes none: zeros then
+            with torch.cuda.stream(st):
+                hist = torch.zeros(RT_DISPLAY_BINS, dtype=torch.int32, device=rgba.device)
+        low, high = window if window is not None else (None, None)
+        lo_e, hi_e = limits if limits is not None else (None, None)
+        d = self.display_desc(W, H, rgba_in=rgba.data_ptr(), id=self._ptr(ids) if metering else 0, rgba_out=self._ptr(out),
+                              pixels=self._ptr(packed), state=self._ptr(state), histogram_out=self._ptr(hist),
+                              meter=_DISPLAY_METERS[meter], exposure=exposure, key=key, min_exposure=lo_e,
+                              max_exposure=hi_e, meter_low=low, meter_high=high, adapt=adapt, meter_sky=meter_sky,
+                              curve=_DISPLAY_CURVES[curve], white=white, transfer=_DISPLAY_TRANSFERS[transfer],
+                              variant=variant)
+        _check(self.display_raw(d, st.cuda_stream), "rt_scene_display")
+        rgba.record_stream(st)            # a contiguous copy stays allocated until the stream has run the pass
+        return {"rgba": out, "pixels": packed, "state": state, "histogram": hist}
+
+    def set_display_timing(self, on: bool):
+        self._set_pass_timing("display", on)
+
+    def display_times(self):
+        """Device ms of every launch of the last timed display call (waits for it): "auto": metering, resolve, apply;
+        "lagged": the fused pass, resolve; "manual": the apply pass."""
+        return self._pass_times("display", 3)

@@ -257,6 +257,13 @@ int rt_temporal_launch(const rt_tmotion_desc *d, const float *dx_tab, const floa
 // rt_upsample.hip: guided upsampling (d: validated, in this build's layout; ev: null, or two timing events)
 int rt_upsample_launch(const rt_upsample_desc *d, hipEvent_t *ev, hipStream_t stream);
 
+// rt_display.hip: the display transform (d: validated, in this build's layout; hist: the scene's
+// RT_DISPLAY_BINS counters, cleared here on `stream`; table: rt_display_table() on the device; ev: null, or
+// RT_DISPLAY_MAX_EVENTS timing events, of which *n_ev are recorded)
+#define RT_DISPLAY_MAX_EVENTS 4
+int rt_display_launch(const rt_display_desc *d, uint32_t *hist, const float *table, hipEvent_t *ev, int *n_ev, hipStream_t stream);
+const float *rt_display_table();   // the 256 thresholds of the sRGB encoding (host)
+
 // rt_indirect.hip: the indirect pass. The product's scratch, all the scene's: per slot of a group of
 // at most RT_INDIRECT_GROUP rays a colour (slab) and a queue entry, a running sum per pixel when there are several
 // groups, and a counter per (group, bounce). Queue 0's entries are RT_INDIRECT_ENTRY_F4 float4; those of the later

@@ -1041,6 +1041,127 @@ extern "C" int rt_scene_upsample_times(rt_scene *s, float *ms, int cap, int *n)
 }
 
 // ---------------------------------------------------------------------------
+// the display transform (rt_display.hip)
+// ---------------------------------------------------------------------------
+extern "C" void rt_display_desc_init(rt_display_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->meter = RT_DISPLAY_METER_AUTO;
+    d->exposure = 1.f;
+    d->key = 0.18f;
+    d->min_exposure = 0.015625f;
+    d->max_exposure = 64.f;
+    d->meter_low = 512;
+    d->meter_high = 973;
+    d->adapt = 1.f;
+    d->curve = RT_DISPLAY_ACES;
+    d->white = 4.f;
+    d->transfer = RT_DISPLAY_SRGB;
+}
+
+extern "C" int rt_display_transfer_table(float out[256])
+{
+    if (!out) {
+        rt_set_error("rt_display_transfer_table: null table");
+        return RT_ERR_INVALID;
+    }
+    memcpy(out, rt_display_table(), 256 * sizeof(float));
+    return RT_OK;
+}
+
+extern "C" int rt_scene_display(rt_scene *s, const rt_display_desc *d_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_display: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_display_desc d;
+    as_built(d_in, &d);
+    auto positive = [](float v) { return v > 0.f && std::isfinite(v); };
+    const bool meter = d.meter != RT_DISPLAY_METER_MANUAL;
+    const char *bad = nullptr;
+    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
+        bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
+    else if (d.meter < RT_DISPLAY_METER_MANUAL || d.meter > RT_DISPLAY_METER_LAGGED) bad = "meter is not RT_DISPLAY_METER_MANUAL, _AUTO or _LAGGED";
+    else if (d.curve < RT_DISPLAY_CLIP || d.curve > RT_DISPLAY_ACES) bad = "curve is not RT_DISPLAY_CLIP, _REINHARD or _ACES";
+    else if (d.transfer < RT_DISPLAY_LINEAR || d.transfer > RT_DISPLAY_SRGB) bad = "transfer is not RT_DISPLAY_LINEAR or _SRGB";
+    else if (d.variant < 0 || d.variant > 1) bad = "variant is not 0 or 1";
+    else if (!d.rgba_in) bad = "rgba_in must not be NULL";
+    else if (meter && !d.state) bad = "state must not be NULL unless meter is RT_DISPLAY_METER_MANUAL";
+    else if (!meter && !d.rgba_out && !d.pixels) bad = "rgba_out and pixels are both NULL and meter is RT_DISPLAY_METER_MANUAL: nothing to do";
+    else if ((uintptr_t)d.rgba_in & 15u) bad = "rgba_in must be 16-byte aligned";
+    else if ((uintptr_t)d.rgba_out & 15u) bad = "rgba_out must be 16-byte aligned";
+    else if (meter && ((uintptr_t)d.state & 15u)) bad = "state must be 16-byte aligned";
+    else if (meter && ((uintptr_t)d.id & 7u)) bad = "id must be 8-byte aligned";
+    else if ((uintptr_t)d.pixels & 3u) bad = "pixels must be 4-byte aligned";
+    else if (meter && ((uintptr_t)d.histogram_out & 3u)) bad = "histogram_out must be 4-byte aligned";
+    else if (!positive(d.exposure)) bad = "exposure is not finite and > 0";
+    else if (!positive(d.key)) bad = "key is not finite and > 0";
+    else if (!positive(d.min_exposure)) bad = "min_exposure is not finite and > 0";
+    else if (!positive(d.max_exposure)) bad = "max_exposure is not finite and > 0";
+    else if (d.min_exposure > d.max_exposure) bad = "min_exposure exceeds max_exposure";
+    else if (d.meter_low < 0 || d.meter_low >= d.meter_high || d.meter_high > 1024) bad = "meter_low and meter_high are not 0 <= low < high <= 1024";
+    else if (!(d.adapt > 0.f && d.adapt <= 1.f)) bad = "adapt is not in (0, 1]";
+    else if (!positive(d.white)) bad = "white is not finite and > 0";
+    else {
+        // what MANUAL does not touch is in no one's way
+        const size_t npx = (size_t)d.width * d.height;
+        const Range outs[4] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.pixels, npx * 4},
+                               {meter ? (uintptr_t)d.state : 0, 16}, {meter ? (uintptr_t)d.histogram_out : 0, RT_DISPLAY_BINS * 4}};
+        const Range ins[2] = {{(uintptr_t)d.rgba_in, npx * 16}, {meter ? (uintptr_t)d.id : 0, npx * 8}};
+        bad = overlap_message(outs, ins, 0, "an output buffer (rgba_out, pixels, state, histogram_out) overlaps rgba_in or id (only rgba_out may be rgba_in itself)");
+        if (bad && !strncmp(bad, "two", 3)) bad = "two of rgba_out, pixels, state and histogram_out overlap";
+    }
+    if (bad) {
+        rt_set_error("rt_scene_display: %s (%d x %d, meter %d, curve %d, transfer %d, variant %d)", bad, d.width, d.height, d.meter,
+                     d.curve, d.transfer, d.variant);
+        return RT_ERR_INVALID;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_display: the stream is being captured (the pass is not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    // the scratch: the histogram's counters, then the thresholds, which never change
+    if (!s->dp_scratch.get()) {
+        RT_HIP(s->dp_scratch.reserve(RT_DISPLAY_BINS + 256));
+        const hipError_t e = hipMemcpy(s->dp_scratch.get() + RT_DISPLAY_BINS, rt_display_table(), 256 * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)s->dp_scratch.reset();
+            RT_HIP(e);
+        }
+    }
+    RT_HIP(s->dp_done.order(stream));   // one histogram: one call at a time
+    hipEvent_t ev[RT_DISPLAY_MAX_EVENTS];
+    s->dp_timed = 0;
+    if (s->dp_timing) {
+        for (int i = 0; i < RT_DISPLAY_MAX_EVENTS; ++i) {
+            RT_HIP(s->dp_ev[i].create(hipEventDefault));
+            ev[i] = s->dp_ev[i].get();
+        }
+    }
+    int n_ev = 0;
+    const int rc = rt_display_launch(&d, s->dp_scratch.get(), (const float *)(s->dp_scratch.get() + RT_DISPLAY_BINS),
+                                     s->dp_timing ? ev : nullptr, &n_ev, stream);
+    // also after a launch that failed half way: what was enqueued uses the histogram
+    RT_HIP(s->dp_done.record(stream));
+    if (rc == RT_OK && s->dp_timing) s->dp_timed = n_ev;
+    return rc;
+}
+
+extern "C" int rt_scene_set_display_timing(rt_scene *s, int on)
+{
+    return pass_set_timing(s, "rt_scene_set_display_timing", &rt_scene::dp_timing, on);
+}
+
+extern "C" int rt_scene_display_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    return pass_times(s, "rt_scene_display_times", &rt_scene::dp_done, s ? s->dp_ev : nullptr, s ? s->dp_timed : 0, ms, cap, n);
+}
+
+// ---------------------------------------------------------------------------
 // global illumination with a bounce budget (rt_indirect.hip)
 // ---------------------------------------------------------------------------
 extern "C" void rt_indirect_desc_init(rt_indirect_desc *d)

@@ -34,6 +34,7 @@ int rt_scene_quiesce(rt_scene *s)
     RT_HIP(s->tp_done.host_wait());                                                    // a temporal call still reading its ray tables
     RT_HIP(s->up_done.host_wait());                                                    // an upsample call in flight
     RT_HIP(s->ind_done.host_wait());                                                   // an indirect call still using its scratch
+    RT_HIP(s->dp_done.host_wait());                                                    // a display call still using its histogram
     return RT_OK;
 }
 

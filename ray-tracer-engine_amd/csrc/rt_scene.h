@@ -19,8 +19,8 @@
 //       build has finished;
 //   (c) a reader waits on the build event on the device only; the host never waits for a build, except in
 //       rt_scene_view_lists_info;
-//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's, the temporal pass's, the upsampler's
-//       and the indirect pass's events;
+//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's, the temporal pass's, the upsampler's,
+//       the indirect pass's and the display transform's events;
 //   (e) the tile order keeps one event for all layouts; a new layout or a re-sort first makes the launching stream
 //       wait for every ring event;
 //   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
@@ -226,6 +226,13 @@ struct rt_scene {
     HipEvent up_ev[2];                               // rt_scene_set_upsample_timing
     bool up_timing = false;
     int up_timed = 0;
+    // the display transform (rt_display.hip): the histogram's RT_DISPLAY_BINS counters and, behind them, the 256
+    // thresholds of the sRGB encoding, uploaded when the buffer is made; `dp_done` orders the scene's display calls
+    DevArray<uint32_t> dp_scratch;
+    HipPendingEvent dp_done;
+    HipEvent dp_ev[RT_DISPLAY_MAX_EVENTS];           // rt_scene_set_display_timing
+    bool dp_timing = false;
+    int dp_timed = 0;
     // the indirect pass (rt_indirect.hip): ray tables of its own, as the temporal pass has, and the product's scratch,
     // grown on demand; `ind_done` orders the scene's indirect calls
     DevArray<float> ind_raygen;                      // dx[width], dy[height] at one sample
