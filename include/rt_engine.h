@@ -976,6 +976,24 @@ typedef struct rt_light_verdicts_info {
  * table, two bits per (group, light) at 16 * group + 2 * light for the tile's first 4 groups and the first 8 lights:
  * 0 evaluate, 1 adds nothing, 2 all clear.                                                                          */
 int rt_debug_light_verdicts(rt_scene *s, rt_light_verdicts_info *out, unsigned long long *words, size_t cap);
+/* Shadow counts: the same table also remembers, for up to `records` lights per tile that the writing launch walked to the
+ * end (code 0: neither dark nor clear), every pixel's number of unshadowed samples; the reading launches take it in place
+ * of the occluder search and the ten samples. Same switch (rt_scene_set_light_verdicts), same key, same launches.    */
+typedef struct rt_shadow_counts_info {
+    int state, slot;           /* as in rt_light_verdicts_info */
+    int tiles_x, tiles_y;
+    int records;               /* records per tile (R) */
+    long long tagged;          /* records in use over the whole table */
+    long long tiles_tagged;    /* tiles with at least one */
+    long long tagged_all;      /* records in use over all of the scene's tables (a frame rendered in row bands has one per band) */
+} rt_shadow_counts_info;
+/* Tests and profiles; waits for the launch that wrote the table. tags (optional, `cap` tiles): a dword per tile, byte r =
+ * 0x80 | group << 3 | light of record r, 0 = free. counts (optional, `cap` tiles): records * 64 bytes per tile, record
+ * by record, a byte per lane of the tile's wave.                                                                       */
+int rt_debug_shadow_counts(rt_scene *s, rt_shadow_counts_info *out, unsigned *tags, unsigned char *counts, size_t cap);
+/* Tests: overwrites the tags and / or the records (null: left as they are) of the table that the last launch wrote or
+ * read; n = tiles_x * tiles_y. Waits for every launch in flight.                                                        */
+int rt_debug_set_shadow_counts(rt_scene *s, const unsigned *tags, const unsigned char *counts, size_t n);
 /* Tests: the long-lived scene rt_launch_raytrace(_ex) and update() render through, for rt_debug_light_verdicts and
  * rt_scene_view_lists_info; owned by the library, NULL before the first launch.                                     */
 rt_scene *rt_debug_shim_scene(void);

@@ -286,6 +286,12 @@ class LightVerdictsInfo(C.Structure):
                 ("nothing", C.c_longlong), ("clear", C.c_longlong)]
 
 
+class ShadowCountsInfo(C.Structure):
+    """rt_shadow_counts_info."""
+    _fields_ = [("state", C.c_int), ("slot", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("records", C.c_int),
+                ("tagged", C.c_longlong), ("tiles_tagged", C.c_longlong), ("tagged_all", C.c_longlong)]
+
+
 RT_VIEW_CAP = 64
 RT_VIEW_SLOT = 1 + RT_VIEW_CAP + RT_VIEW_CAP // 4 + RT_VIEW_CAP // 4    # 16-byte records per block
 RT_VIEW_OVERFLOW, RT_VIEW_NOT_BUILT = 1, 2
@@ -363,6 +369,8 @@ def load_library():
         "rt_scene_set_light_verdicts": (ci, [vp, ci]),
         "rt_debug_light_verdicts": (ci, [vp, C.POINTER(LightVerdictsInfo), C.POINTER(C.c_uint64), C.c_size_t]),
         "rt_debug_shim_scene": (vp, []),
+        "rt_debug_shadow_counts": (ci, [vp, C.POINTER(ShadowCountsInfo), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t]),
+        "rt_debug_set_shadow_counts": (ci, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t]),
         "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
         "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
         "rt_debug_tile_order": (ci, [C.POINTER(C.c_uint), ci, ci, ci, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
@@ -880,6 +888,38 @@ class Scene:
                                                     buf.size), "rt_debug_light_verdicts")
             d["words"] = buf.reshape(info.tiles_y, info.tiles_x)
         return d
+
+    def shadow_counts(self, want_tables: bool = False) -> dict:
+        """The shadow counts behind the last launch's light verdicts (waits for the table's writer): state, slot, tiles_x,
+        tiles_y, records (per tile), tagged, tiles_tagged, tagged_all (over all of the scene's tables); with want_tables also 'tags', uint8 [tiles_y, tiles_x, 4]
+        (byte r: 0x80 | group << 3 | light of record r, 0 = free) and 'counts', uint8 [tiles_y, tiles_x, records, 64]."""
+        info = ShadowCountsInfo()
+        _check(self.lib.rt_debug_shadow_counts(self.handle, C.byref(info), None, None, 0), "rt_debug_shadow_counts")
+        d = {k: getattr(info, k) for k, _ in ShadowCountsInfo._fields_}
+        if want_tables and info.state:
+            n = info.tiles_x * info.tiles_y
+            tags = np.zeros(n, dtype=np.uint32)
+            counts = np.zeros((n, info.records, 64), dtype=np.uint8)
+            _check(self.lib.rt_debug_shadow_counts(self.handle, C.byref(info), tags.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                   counts.ctypes.data_as(C.POINTER(C.c_uint8)), n), "rt_debug_shadow_counts")
+            d["tags"] = tags.view(np.uint8).reshape(info.tiles_y, info.tiles_x, 4)
+            d["counts"] = counts.reshape(info.tiles_y, info.tiles_x, info.records, 64)
+        return d
+
+    def set_shadow_counts(self, tags=None, counts=None):
+        """Tests: overwrites the record tags (uint8 [tiles_y, tiles_x, 4]) and / or the records (uint8 [tiles_y, tiles_x,
+        records, 64]) of the table that the last launch wrote or read."""
+        n = 0
+        tp = cp = None
+        if tags is not None:
+            tags = np.ascontiguousarray(tags, dtype=np.uint8)
+            n = tags.size // 4
+            tp = tags.ctypes.data_as(C.POINTER(C.c_uint32))
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.uint8)
+            n = counts.shape[0] * counts.shape[1]
+            cp = counts.ctypes.data_as(C.POINTER(C.c_uint8))
+        _check(self.lib.rt_debug_set_shadow_counts(self.handle, tp, cp, n), "rt_debug_set_shadow_counts")
 
     def view_lists_info(self, want_lists: bool = False) -> dict:
         """What the last launch read (waits for the lists' build): read, block size, blocks, overflowed and not-built

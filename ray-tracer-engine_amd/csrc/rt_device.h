@@ -272,6 +272,13 @@ struct RtFrameConsts {
     // RT_VERDICT_CLEAR = its all-clear test held. verdict_wr: this launch writes the words it finds; verdict_rd: it
     // consumes the words an earlier launch of bit-identical inputs wrote (the host keeps the key). Either may be null;
     // only the one-sample sphere-only product kernel (MODE 0, FEAT 0, CULL) looks at them.
+    //
+    // Shadow counts lie behind the words in the same allocation, so the kernel argument does not
+    // grow: with T = tiles of the launch's grid, a tag dword per tile at dword 2 T + tile, then RT_SHADOW_RECORDS records
+    // of 64 bytes per tile from byte 12 T (RT_SHADOW_COUNTS_OFFSET). A record holds, per lane, the number of unshadowed
+    // samples (0..RT_SHADOW_SAMPLES) that a walked light -- code 0, neither dark nor clear -- left; byte r of the tag
+    // dword says whose record r is, 0x80 | group << 3 | light, 0 = free. A light that found no free record has none and
+    // is walked by the reader as before.
     const unsigned long long *verdict_rd;
     unsigned long long *verdict_wr;
 };
@@ -279,3 +286,10 @@ struct RtFrameConsts {
 #define RT_VERDICT_LIGHTS 8
 #define RT_VERDICT_NOTHING 1u
 #define RT_VERDICT_CLEAR 2u
+#define RT_SHADOW_RECORDS 1      // R: the smallest count that gives a record to 95 % of C3's code-0 entries (96.6 %; profiles/shadow_counts_before.json)
+#define RT_SHADOW_TAG_UNWRITTEN 0xffffffffu   // the fill before a recording launch; every tile it renders stores its tags over it
+#define RT_SHADOW_TAG(g, li) (0x80u | ((unsigned)(g) << 3) | (unsigned)(li))
+// byte offsets, from the first verdict word, of the tag dwords and of the records of a table of `tiles` tiles; its size
+#define RT_SHADOW_TAGS_OFFSET(tiles) ((size_t)(tiles) * 8u)
+#define RT_SHADOW_COUNTS_OFFSET(tiles) ((size_t)(tiles) * 12u)
+#define RT_VERDICT_TABLE_BYTES(tiles) ((size_t)(tiles) * (12u + 64u * RT_SHADOW_RECORDS))

@@ -230,7 +230,7 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
                             16 * sizeof(double) +            // atan(k/8)
                             192 * sizeof(float) +            // texel colours per pixel
                             (feat == 2 ? (RT_BOX_CAP + 128) * sizeof(int)   // leaf boxes, marked blocks, staged vertices
-                                       : 2 * sizeof(unsigned)));            // the tile's light verdicts (same place)
+                                       : 4 * sizeof(unsigned)));            // the tile's light verdicts, record tags and index (same place)
     const int th = 64 / tile_w;
     *grid = dim3((fc->width + tile_w - 1) / tile_w, (fc->local_rows + th - 1) / th);
     *block = dim3(64);

@@ -505,7 +505,7 @@ int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameCons
     }
     if (v >= 0) {
         VerdictSlot &c = s->verdicts[v];
-        if (c.tiles_x != tiles_x || c.tiles_y != tiles_y || c.buf.capacity() * 2 < words) {
+        if (c.tiles_x != tiles_x || c.tiles_y != tiles_y || c.buf.capacity() * sizeof(float4) < RT_VERDICT_TABLE_BYTES(words)) {
             rt_set_error("rt_scene_render: light verdicts of %d x %d tiles for a launch of %d x %d", c.tiles_x, c.tiles_y, tiles_x, tiles_y);
             return RT_ERR_INVALID;
         }
@@ -515,7 +515,7 @@ int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameCons
     } else if (seen >= 0) {
         s->verdict_seen_valid[seen] = false;
         VerdictSlot &c = rt_slot_victim(s->verdicts, [](const VerdictSlot &x) { return !x.valid; });
-        const size_t total = (words + 1) / 2;   // float4
+        const size_t total = (RT_VERDICT_TABLE_BYTES(words) + sizeof(float4) - 1) / sizeof(float4);   // words, record tags, records
         if (total > c.buf.capacity()) {
             const int rc = rt_scene_quiesce(s);   // nothing may still read or write the buffer that is freed
             if (rc != RT_OK) return rc;
@@ -533,7 +533,11 @@ int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameCons
             }
         }
         // all ones: a word no launch writes (code 3 is "evaluate" to a reader), so a read-back can count unwritten tiles
-        RT_HIP(hipMemsetAsync(c.buf.get(), 0xff, sizeof(float4) * total, stream));
+        // The record tags behind the words take the same fill in the same call (a second one costs a recording launch
+        // another launch on its stream): every tile the launch renders stores its tag dword, 0 where it took no record,
+        // and an all-ones tag of a tile it did not render names group 15, which no iteration has -- RT_SHADOW_TAG_UNWRITTEN
+        // to the read-back. The records themselves are read only where a tag points and stay as they are.
+        RT_HIP(hipMemsetAsync(c.buf.get(), 0xff, RT_SHADOW_COUNTS_OFFSET(words), stream));
         c.key = key;
         c.tiles_x = tiles_x;
         c.tiles_y = tiles_y;
@@ -599,6 +603,76 @@ extern "C" int rt_debug_light_verdicts(rt_scene *s, rt_light_verdicts_info *out,
         }
         memcpy(words, h.data(), sizeof(unsigned long long) * n);
     }
+    return RT_OK;
+}
+
+// The shadow counts behind the last launch's verdict table (waits for the launch that wrote it).
+extern "C" int rt_debug_shadow_counts(rt_scene *s, rt_shadow_counts_info *out, unsigned *tags, unsigned char *counts, size_t cap)
+{
+    if (!s || !out) {
+        rt_set_error("rt_debug_shadow_counts: null argument");
+        return RT_ERR_INVALID;
+    }
+    memset(out, 0, sizeof *out);
+    out->slot = -1;
+    out->records = RT_SHADOW_RECORDS;
+    if (s->verdict_last < 0) return RT_OK;
+    VerdictSlot &c = s->verdicts[s->verdict_last];
+    if (!c.valid) return RT_OK;   // (a writing launch that failed)
+    RT_HIP(c.built.host_wait());
+    const size_t n = (size_t)c.tiles_x * (size_t)c.tiles_y;
+    const char *base = reinterpret_cast<const char *>(c.buf.get());
+    std::vector<unsigned> h(n);
+    RT_HIP(hipMemcpy(h.data(), base + RT_SHADOW_TAGS_OFFSET(n), sizeof(unsigned) * n, hipMemcpyDeviceToHost));
+    out->state = s->verdict_last_wrote ? 1 : 2;
+    out->slot = s->verdict_last;
+    out->tiles_x = c.tiles_x;
+    out->tiles_y = c.tiles_y;
+    for (unsigned &t : h) {
+        if (t == RT_SHADOW_TAG_UNWRITTEN) t = 0;   // (a tile the writing launch did not render: no record)
+        int k = 0;
+        for (int r = 0; r < 4; ++r) k += ((t >> (8 * r)) & 0x80u) ? 1 : 0;
+        out->tagged += k;
+        out->tiles_tagged += k ? 1 : 0;
+    }
+    for (VerdictSlot &o : s->verdicts) {   // every table the scene holds: a frame rendered in row bands has one per band
+        if (!o.valid) continue;
+        RT_HIP(o.built.host_wait());
+        const size_t m = (size_t)o.tiles_x * (size_t)o.tiles_y;
+        std::vector<unsigned> ht(m);
+        RT_HIP(hipMemcpy(ht.data(), reinterpret_cast<const char *>(o.buf.get()) + RT_SHADOW_TAGS_OFFSET(m), sizeof(unsigned) * m, hipMemcpyDeviceToHost));
+        for (unsigned t : ht)
+            for (int r = 0; r < 4 && t != RT_SHADOW_TAG_UNWRITTEN; ++r) out->tagged_all += ((t >> (8 * r)) & 0x80u) ? 1 : 0;
+    }
+    if (tags || counts) {
+        if (cap < n) {
+            rt_set_error("rt_debug_shadow_counts: room for %zu tiles, the table has %zu", cap, n);
+            return RT_ERR_INVALID;
+        }
+        if (tags) memcpy(tags, h.data(), sizeof(unsigned) * n);
+        if (counts) RT_HIP(hipMemcpy(counts, base + RT_SHADOW_COUNTS_OFFSET(n), (size_t)64 * RT_SHADOW_RECORDS * n, hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
+// Tests: overwrite the tags and / or the records of the table the last launch wrote or read (either may be null).
+extern "C" int rt_debug_set_shadow_counts(rt_scene *s, const unsigned *tags, const unsigned char *counts, size_t n)
+{
+    if (!s || s->verdict_last < 0 || !s->verdicts[s->verdict_last].valid) {
+        rt_set_error("rt_debug_set_shadow_counts: the last launch neither wrote nor read a table");
+        return RT_ERR_INVALID;
+    }
+    VerdictSlot &c = s->verdicts[s->verdict_last];
+    if (n != (size_t)c.tiles_x * (size_t)c.tiles_y) {
+        rt_set_error("rt_debug_set_shadow_counts: %zu tiles given, the table has %d x %d", n, c.tiles_x, c.tiles_y);
+        return RT_ERR_INVALID;
+    }
+    const int rc = rt_scene_quiesce(s);   // no launch still reads the table
+    if (rc != RT_OK) return rc;
+    RT_HIP(c.built.host_wait());
+    char *base = reinterpret_cast<char *>(c.buf.get());
+    if (tags) RT_HIP(hipMemcpy(base + RT_SHADOW_TAGS_OFFSET(n), tags, sizeof(unsigned) * n, hipMemcpyHostToDevice));
+    if (counts) RT_HIP(hipMemcpy(base + RT_SHADOW_COUNTS_OFFSET(n), counts, (size_t)64 * RT_SHADOW_RECORDS * n, hipMemcpyHostToDevice));
     return RT_OK;
 }
 

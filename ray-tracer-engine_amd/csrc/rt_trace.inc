@@ -1323,9 +1323,16 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
     // loop, whose scalar and vector files are full.
     constexpr bool VD_USE = (MODE == 6), VD_REC = (MODE == 7), VERD = VD_USE || VD_REC;
     static_assert(!VERD || (CULL && FEAT == 0), "light verdicts: the sphere-only culling kernels");
-    unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192)) + wave * 2;
+    // Shadow counts (step 5b) go the same way: the tile's tag dword is asked for by lane 2 and parked behind the word,
+    // and behind that the tile's index, which the light loop needs for a record's address and must not hold in a register.
+    unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192)) + wave * 4;
     unsigned vd_ld = 0;
-    if (VD_USE && lane < 2) vd_ld = reinterpret_cast<const unsigned *>(fc.verdict_rd)[2 * (size_t)(blk_y * tiles_x + blk_x) + lane];
+    if (VERD) {
+        const unsigned vd_tile = blk_y * tiles_x + blk_x, vd_tiles = tiles_x * ((unsigned)(fc.local_rows + TH - 1) / (unsigned)TH);   // T = the grid (rt_dev_trace_config)
+        // (dwords: the word's halves at 2 tile + lane, the tag at 2 T + tile)
+        if (VD_USE && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.verdict_rd)[lane < 2 ? 2 * (size_t)vd_tile + lane : 2 * (size_t)vd_tiles + vd_tile];
+        if (lane == 3) vd_ld = vd_tile;
+    }
     const int tile_x = blk_x * TW;
     // local row -> global row: a contiguous band, or row blocks dealt round-robin
     // to the ranks of a multi-GPU frame (il_rows is a multiple of the tile rows a
@@ -1766,7 +1773,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             }
         }
         if (VERD) {   // the tile's word: the verdicts it was handed (MODE 6), or those it finds (MODE 7: none so far)
-            if (lane < 2) myvd[lane] = vd_ld;
+            if (lane < 4) myvd[lane] = vd_ld;
             wave_lds_sync();
         }
         if (hit_m != 0 && !RT_ABL(16)) {
@@ -1846,6 +1853,18 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     if (VD_REC && vd_has && lane == 0)
                         (void)__hip_atomic_fetch_or(&myvd[g >> 1], code << vd_sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 };
+                // Shadow counts: a light that the recording launch walked to the end (code 0) and gave a record. Its lanes'
+                // numbers of unshadowed samples are what this launch would count again from the same bits, so the
+                // iteration takes the all-clear path -- the facing test (lit_m is still needed), then the chain's begin and
+                // settle for toL, no list header, beam, cull, all-clear test, list order, pre-pass or sample -- and the
+                // shading reads the lane's count from the record instead of RT_SHADOW_SAMPLES.
+                if (VD_USE && vd_has && vd == 0) {
+                    const unsigned tg = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[2]);
+#pragma unroll
+                    for (int r = 0; r < RT_SHADOW_RECORDS; ++r)
+                        if (((tg >> (8 * r)) & 0xffu) == RT_SHADOW_TAG(g, li)) vd = 4u + r;   // (neither code: record r)
+                }
+                const bool sc_use = VD_USE && vd >= 4u;
                 const RtLightDev L = ax->lights[li];
                 const V3 lpos{L.px, L.py, L.pz};
 
@@ -1890,7 +1909,8 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 int sbcount = MESH ? fc.n_boxes : 0;
                 float beam_k = 0.f;   // slope of the light's beam (valid when s_use_list)
                 // (a light whose all-clear test held for these inputs needs neither its list nor the test again)
-                if (CULL && !(VD_USE && vd == RT_VERDICT_CLEAR)) {
+                // (nor does a light whose counts are on record)
+                if (CULL && !(VD_USE && vd == RT_VERDICT_CLEAR) && !sc_use) {
                     bool ok = true;
                     Beam b;
                     b.ux = L.ux; b.uy = L.uy; b.uz = L.uz;
@@ -2036,7 +2056,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 // unshadowed without constructing one of them: only toL's evolution is
                 // needed for kernel.cu:1541. Typically the list is just the sphere the
                 // tile itself lies on.
-                bool all_clear = VD_USE && vd == RT_VERDICT_CLEAR;
+                bool all_clear = (VD_USE && vd == RT_VERDICT_CLEAR) || sc_use;   // (sc_use: no walk either; the counts differ)
                 if (CULL && (!MESH || (sb_use_list && sbcount == 0)) && s_use_list && scount <= 4 && !force_slow &&
                     !RT_ABL(128) && (!PRIMS || (fc.n_planes | fc.n_cubes) == 0)) {
                     lmask clear = ~0ull;
@@ -2266,6 +2286,27 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     phase(7);
                 }
                 if (CULL) wave_lds_sync();
+                // The recording launch: a light that was walked to the end (not clear, not dark) takes the tile's next free
+                // record -- every lane's count as a byte, 64 in a row -- and lane 0 notes whose it is in the tag dword.
+                if (VD_REC && vd_has && !all_clear && !dark) {
+                    const unsigned tg = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[2]);
+                    int slot = -1;
+#pragma unroll
+                    for (int r = RT_SHADOW_RECORDS - 1; r >= 0; --r)
+                        if (((tg >> (8 * r)) & 0xffu) == 0u) slot = r;
+                    if (slot >= 0) {
+                        FcPtr kg = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
+                        asm volatile("" : "+s"(kg));
+                        const unsigned tiles = ((unsigned)(kg->width + TW - 1) / (unsigned)TW) * ((unsigned)(kg->local_rows + TH - 1) / (unsigned)TH);   // = the grid
+                        const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[3]);
+                        unsigned char *rec = reinterpret_cast<unsigned char *>(kg->verdict_wr) + RT_SHADOW_COUNTS_OFFSET(tiles) +
+                                             ((size_t)tile * RT_SHADOW_RECORDS + (size_t)slot) * 64u;
+                        rec[lane] = (unsigned char)(us >> 16);
+                        if (lane == 0)
+                            (void)__hip_atomic_fetch_or(&myvd[2], RT_SHADOW_TAG(g, li) << (8 * slot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        wave_lds_sync();
+                    }
+                }
                 if (STATS == 1 && MESH && !all_clear) sm_slisted += (unsigned long long)sbcount;
                 if (STATS == 1 && !all_clear) {   // how many of the walked lights had a lane in a penumbra at all
                     const int unshadowed = (int)(us >> 16);
@@ -2280,7 +2321,25 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 
                 if (lit && !dark) {   // unlit lanes would add (0 * l.r) * r = +0, and so does a light that is dark for all of them
                     // b after `unshadowed` float+=double steps, then b *= max(normal.toL, 0)
-                    const int unshadowed = (int)(us >> 16);
+                    int unshadowed = (int)(us >> 16);
+                    // A light on record: the lane's count. The address is formed here, from the kernel-argument segment and
+                    // the tile index parked in LDS, so that nothing of it lives across the loop; and the load is issued
+                    // here, where the fewest registers are live -- asked for ahead of begin and settle, so that the chain
+                    // covers its latency, it costs the kernel four spilled vector registers and its scratch-free frame.
+                    if (sc_use) {
+                        FcPtr kg = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
+                        asm volatile("" : "+s"(kg));
+                        const unsigned tiles = ((unsigned)(kg->width + TW - 1) / (unsigned)TW) * ((unsigned)(kg->local_rows + TH - 1) / (unsigned)TH);   // = the grid
+                        const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[3]);
+                        const unsigned char *rec = reinterpret_cast<const unsigned char *>(kg->verdict_rd) + RT_SHADOW_COUNTS_OFFSET(tiles) +
+                                                   ((size_t)tile * RT_SHADOW_RECORDS + (size_t)(vd - 4u)) * 64u;
+                        // (a scalar base and a lane index formed on the spot, both opaque, and a global load said to be one:
+                        // as plain expressions the compiler keeps parts of the address in vector registers -- four spills)
+                        asm volatile("" : "+s"(rec));
+                        int sc_lane = (int)(threadIdx.x & 63u);
+                        asm volatile("" : "+v"(sc_lane));
+                        unshadowed = (int)((const __attribute__((address_space(1))) unsigned char *)rec)[sc_lane];
+                    }
                     float bsum = mybtab[unshadowed];
                     const float a = dot3(normal, chain.toL);                    // kernel.cu:1541
                     bsum = bsum * (a > 0.f ? a : 0.f);
@@ -2373,6 +2432,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         unsigned *const o_verdict = reinterpret_cast<unsigned *>(kargs->verdict_wr);
         wave_lds_sync();
         if (wb_lane < 2) o_verdict[2 * (size_t)(wb_y * wb_tiles_x + wb_x) + wb_lane] = myvd[wb_lane];
+        if (wb_lane == 2) o_verdict[2 * (size_t)(wb_tiles_x * ((unsigned)(kargs->local_rows + TH - 1) / (unsigned)TH)) + (wb_y * wb_tiles_x + wb_x)] = myvd[2];   // the tags of its records
     }
     if (o_cost) {   // this tile's wave duration, for the order of later frames (a plain store: an atomic maximum
         // per block of tiles here, 256 waves ending together on one address, slowed the whole launch down by 3 %)
