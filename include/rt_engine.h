@@ -994,6 +994,24 @@ int rt_debug_shadow_counts(rt_scene *s, rt_shadow_counts_info *out, unsigned *ta
 /* Tests: overwrites the tags and / or the records (null: left as they are) of the table that the last launch wrote or
  * read; n = tiles_x * tiles_y. Waits for every launch in flight.                                                        */
 int rt_debug_set_shadow_counts(rt_scene *s, const unsigned *tags, const unsigned char *counts, size_t n);
+/* Primary records: the third part of the same table. For every pixel of the writing launch's grid a dword -- bits 0-7 the
+ * entry of the tile's view list that is the pixel's closest hit (0xff: a miss, 0xfe: the tile has no record and reading
+ * launches walk its list as before), bits 8-31 the clamped texel index, of the object texture for a hit, of the sky for a
+ * miss. Reading launches evaluate that one entry and fetch that texel. Same switch, same key, same launches.          */
+typedef struct rt_primary_records_info {
+    int state, slot;           /* as in rt_light_verdicts_info */
+    int tiles_x, tiles_y;
+    int tile_w;                /* a tile is tile_w x 64 / tile_w pixels; lane = row in tile * tile_w + column in tile */
+    long long tiles_recorded;  /* tiles with a record (no valid pixel says 0xfe) */
+    long long hit_pixels, miss_pixels;   /* valid pixels of those tiles */
+} rt_primary_records_info;
+/* Tests and profiles; waits for the launch that wrote the table. dwords (optional, `cap` = 64 * tiles): the raw records at
+ * tile * 64 + lane. positions (optional, same size): the position in the sphere table that a pixel's entry resolves to
+ * through the view list the launch read, -1 for a miss, -2 where the tile has no record or the lane is outside the frame. */
+int rt_debug_primary_records(rt_scene *s, rt_primary_records_info *out, unsigned *dwords, int *positions, size_t cap);
+/* Tests: overwrites the records of the table that the last launch wrote or read; n = 64 * tiles_x * tiles_y. Waits for
+ * every launch in flight.                                                                                            */
+int rt_debug_set_primary_records(rt_scene *s, const unsigned *dwords, size_t n);
 /* Tests: the long-lived scene rt_launch_raytrace(_ex) and update() render through, for rt_debug_light_verdicts and
  * rt_scene_view_lists_info; owned by the library, NULL before the first launch.                                     */
 rt_scene *rt_debug_shim_scene(void);

@@ -292,6 +292,41 @@ class ShadowCountsInfo(C.Structure):
                 ("tagged", C.c_longlong), ("tiles_tagged", C.c_longlong), ("tagged_all", C.c_longlong)]
 
 
+class PrimaryRecordsInfo(C.Structure):
+    """rt_primary_records_info."""
+    _fields_ = [("state", C.c_int), ("slot", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("tile_w", C.c_int),
+                ("tiles_recorded", C.c_longlong), ("hit_pixels", C.c_longlong), ("miss_pixels", C.c_longlong)]
+
+
+RT_PRIMARY_MISS, RT_PRIMARY_NONE = 0xff, 0xfe
+
+
+def decode_primary_records(dwords):
+    """uint32 records -> (entry uint8: position in the tile's view list, RT_PRIMARY_MISS, RT_PRIMARY_NONE; texel int64)."""
+    d = np.asarray(dwords, dtype=np.uint32)
+    return (d & np.uint32(0xff)).astype(np.uint8), (d >> np.uint32(8)).astype(np.int64)
+
+
+def encode_primary_records(entry, texel):
+    """The inverse of decode_primary_records (texel < 2^24)."""
+    return (np.asarray(entry).astype(np.uint32) & np.uint32(0xff)) | (np.asarray(texel).astype(np.uint32) << np.uint32(8))
+
+
+def tiles_to_pixels(a, tile_w):
+    """[tiles_y, tiles_x, 64] (lane = row in tile * tile_w + column in tile) -> [tiles_y * 64 / tile_w, tiles_x * tile_w], the
+    launch's grid of pixels in local rows."""
+    ty, tx, _ = a.shape
+    th = 64 // tile_w
+    return a.reshape(ty, tx, th, tile_w).transpose(0, 2, 1, 3).reshape(ty * th, tx * tile_w)
+
+
+def pixels_to_tiles(a, tile_w):
+    """The inverse of tiles_to_pixels."""
+    th = 64 // tile_w
+    ty, tx = a.shape[0] // th, a.shape[1] // tile_w
+    return np.ascontiguousarray(a.reshape(ty, th, tx, tile_w).transpose(0, 2, 1, 3)).reshape(ty, tx, 64)
+
+
 RT_VIEW_CAP = 64
 RT_VIEW_SLOT = 1 + RT_VIEW_CAP + RT_VIEW_CAP // 4 + RT_VIEW_CAP // 4    # 16-byte records per block
 RT_VIEW_OVERFLOW, RT_VIEW_NOT_BUILT = 1, 2
@@ -371,6 +406,8 @@ def load_library():
         "rt_debug_shim_scene": (vp, []),
         "rt_debug_shadow_counts": (ci, [vp, C.POINTER(ShadowCountsInfo), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t]),
         "rt_debug_set_shadow_counts": (ci, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t]),
+        "rt_debug_primary_records": (ci, [vp, C.POINTER(PrimaryRecordsInfo), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_size_t]),
+        "rt_debug_set_primary_records": (ci, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
         "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
         "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
         "rt_debug_tile_order": (ci, [C.POINTER(C.c_uint), ci, ci, ci, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
@@ -920,6 +957,31 @@ class Scene:
             n = counts.shape[0] * counts.shape[1]
             cp = counts.ctypes.data_as(C.POINTER(C.c_uint8))
         _check(self.lib.rt_debug_set_shadow_counts(self.handle, tp, cp, n), "rt_debug_set_shadow_counts")
+
+    def primary_records(self, want_tables: bool = False) -> dict:
+        """The primary records behind the last launch's light verdicts (waits for the table's writer): state, slot, tiles_x,
+        tiles_y, tile_w, tiles_recorded, hit_pixels, miss_pixels; with want_tables also 'dwords', uint32 [tiles_y, tiles_x,
+        64] (see decode_primary_records; lane = row in tile * tile_w + column in tile) and 'positions', int32 of the same
+        shape: the sphere-table position a pixel's entry resolves to, -1 a miss, -2 no record or outside the frame."""
+        info = PrimaryRecordsInfo()
+        _check(self.lib.rt_debug_primary_records(self.handle, C.byref(info), None, None, 0), "rt_debug_primary_records")
+        d = {k: getattr(info, k) for k, _ in PrimaryRecordsInfo._fields_}
+        if want_tables and info.state:
+            n = 64 * info.tiles_x * info.tiles_y
+            dwords = np.zeros(n, dtype=np.uint32)
+            pos = np.zeros(n, dtype=np.int32)
+            _check(self.lib.rt_debug_primary_records(self.handle, C.byref(info), dwords.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                     pos.ctypes.data_as(C.POINTER(C.c_int32)), n), "rt_debug_primary_records")
+            d["dwords"] = dwords.reshape(info.tiles_y, info.tiles_x, 64)
+            d["positions"] = pos.reshape(info.tiles_y, info.tiles_x, 64)
+        return d
+
+    def set_primary_records(self, dwords):
+        """Tests: overwrites the primary records (uint32 [tiles_y, tiles_x, 64]) of the table that the last launch wrote or
+        read."""
+        dwords = np.ascontiguousarray(dwords, dtype=np.uint32)
+        _check(self.lib.rt_debug_set_primary_records(self.handle, dwords.ctypes.data_as(C.POINTER(C.c_uint32)), dwords.size),
+               "rt_debug_set_primary_records")
 
     def view_lists_info(self, want_lists: bool = False) -> dict:
         """What the last launch read (waits for the lists' build): read, block size, blocks, overflowed and not-built

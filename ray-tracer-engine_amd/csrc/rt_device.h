@@ -278,7 +278,8 @@ struct RtFrameConsts {
     // of 64 bytes per tile from byte 12 T (RT_SHADOW_COUNTS_OFFSET). A record holds, per lane, the number of unshadowed
     // samples (0..RT_SHADOW_SAMPLES) that a walked light -- code 0, neither dark nor clear -- left; byte r of the tag
     // dword says whose record r is, 0x80 | group << 3 | light, 0 = free. A light that found no free record has none and
-    // is walked by the reader as before.
+    // is walked by the reader as before. Primary records (step 5c) lie behind the counts: a dword per lane of every
+    // tile from RT_PRIMARY_RECORDS_OFFSET (below).
     const unsigned long long *verdict_rd;
     unsigned long long *verdict_wr;
 };
@@ -292,4 +293,14 @@ struct RtFrameConsts {
 // byte offsets, from the first verdict word, of the tag dwords and of the records of a table of `tiles` tiles; its size
 #define RT_SHADOW_TAGS_OFFSET(tiles) ((size_t)(tiles) * 8u)
 #define RT_SHADOW_COUNTS_OFFSET(tiles) ((size_t)(tiles) * 12u)
-#define RT_VERDICT_TABLE_BYTES(tiles) ((size_t)(tiles) * (12u + 64u * RT_SHADOW_RECORDS))
+// Primary records lie behind the shadow-count records: a dword per lane of every tile's wave, at
+// dword tile * 64 + lane from RT_PRIMARY_RECORDS_OFFSET. Bits 0-7: the entry of the tile's staged view list that is the
+// lane's closest hit, RT_PRIMARY_MISS = none, RT_PRIMARY_NONE = the tile has no record (it walked no view list, or a
+// texture has more than 2^24 texels); bits 8-31: the clamped texel index, of the object texture for a hit, of the sky for
+// a miss. The recording launch stores every lane of every tile it renders; a reader that finds RT_PRIMARY_NONE in a
+// valid lane takes the walk and the texel arithmetic for the whole tile.
+#define RT_PRIMARY_MISS 0xffu
+#define RT_PRIMARY_NONE 0xfeu
+#define RT_PRIMARY_TEXELS (1 << 24)
+#define RT_PRIMARY_RECORDS_OFFSET(tiles) ((size_t)(tiles) * (12u + 64u * RT_SHADOW_RECORDS))
+#define RT_VERDICT_TABLE_BYTES(tiles) (RT_PRIMARY_RECORDS_OFFSET(tiles) + (size_t)(tiles) * 256u)

@@ -71,7 +71,7 @@ struct RtVerdictKey {
     unsigned long long sphere_gen = 0;    // ... and of the sphere list (tables built from it: cones, view lists, light tables)
     int tile = 0, cull = 0, mode = 0, feat = 0;
 };
-struct VerdictSlot : RtTableSlot {       // buf: RT_VERDICT_TABLE_BYTES(tiles) -- the words, the record tags, the shadow-count records
+struct VerdictSlot : RtTableSlot {       // buf: RT_VERDICT_TABLE_BYTES(tiles) -- the words, the record tags, the shadow-count records, the primary records
     RtVerdictKey key;
     int tiles_x = 0, tiles_y = 0;
 };

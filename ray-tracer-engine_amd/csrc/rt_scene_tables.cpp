@@ -536,7 +536,9 @@ int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameCons
         // The record tags behind the words take the same fill in the same call (a second one costs a recording launch
         // another launch on its stream): every tile the launch renders stores its tag dword, 0 where it took no record,
         // and an all-ones tag of a tile it did not render names group 15, which no iteration has -- RT_SHADOW_TAG_UNWRITTEN
-        // to the read-back. The records themselves are read only where a tag points and stay as they are.
+        // to the read-back. The records themselves are read only where a tag points and stay as they are. The primary
+        // records behind them need no fill either: the launch stores every lane of every tile it renders, and a reader
+        // of the same key renders exactly those tiles.
         RT_HIP(hipMemsetAsync(c.buf.get(), 0xff, RT_SHADOW_COUNTS_OFFSET(words), stream));
         c.key = key;
         c.tiles_x = tiles_x;
@@ -673,6 +675,93 @@ extern "C" int rt_debug_set_shadow_counts(rt_scene *s, const unsigned *tags, con
     char *base = reinterpret_cast<char *>(c.buf.get());
     if (tags) RT_HIP(hipMemcpy(base + RT_SHADOW_TAGS_OFFSET(n), tags, sizeof(unsigned) * n, hipMemcpyHostToDevice));
     if (counts) RT_HIP(hipMemcpy(base + RT_SHADOW_COUNTS_OFFSET(n), counts, (size_t)64 * RT_SHADOW_RECORDS * n, hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// The primary records behind the last launch's verdict table (waits for the launch that wrote it). The tile's place in
+// the frame, and with it its block of the view lists, is formed as the kernel forms it, from the uniforms in the slot's key.
+extern "C" int rt_debug_primary_records(rt_scene *s, rt_primary_records_info *out, unsigned *dwords, int *positions, size_t cap)
+{
+    if (!s || !out) {
+        rt_set_error("rt_debug_primary_records: null argument");
+        return RT_ERR_INVALID;
+    }
+    memset(out, 0, sizeof *out);
+    out->slot = -1;
+    if (s->verdict_last < 0) return RT_OK;
+    VerdictSlot &c = s->verdicts[s->verdict_last];
+    if (!c.valid) return RT_OK;   // (a writing launch that failed)
+    RT_HIP(c.built.host_wait());
+    const size_t n = (size_t)c.tiles_x * (size_t)c.tiles_y;
+    std::vector<unsigned> h(64 * n);
+    RT_HIP(hipMemcpy(h.data(), reinterpret_cast<const char *>(c.buf.get()) + RT_PRIMARY_RECORDS_OFFSET(n), sizeof(unsigned) * 64 * n, hipMemcpyDeviceToHost));
+    const RtFrameConsts &fc = c.key.fc;
+    const int tw = c.key.tile, th = 64 / tw;
+    out->state = s->verdict_last_wrote ? 1 : 2;
+    out->slot = s->verdict_last;
+    out->tiles_x = c.tiles_x;
+    out->tiles_y = c.tiles_y;
+    out->tile_w = tw;
+    if ((dwords || positions) && cap < 64 * n) {
+        rt_set_error("rt_debug_primary_records: room for %zu records, the table has %zu", cap, 64 * n);
+        return RT_ERR_INVALID;
+    }
+    std::vector<float4> lists;   // the view lists the launch read (a tile with a record read one)
+    int nbx = 0;
+    if (positions && fc.view_lists && s->view_last >= 0 && reinterpret_cast<const float *>(s->views[s->view_last].buf.get()) == fc.view_lists) {
+        ViewSlot &v = s->views[s->view_last];
+        RT_HIP(v.built.host_wait());
+        lists.resize(rt_view_lists_size(v.nbx, v.nby));
+        RT_HIP(hipMemcpy(lists.data(), v.buf.get(), sizeof(float4) * lists.size(), hipMemcpyDeviceToHost));
+        nbx = v.nbx;
+    }
+    int il_sh = 0;
+    while ((1 << il_sh) < fc.il_rows) ++il_sh;
+    auto row_of = [&](int ly) { return fc.y0 + ((((ly >> il_sh) * fc.il_count + fc.il_index) << il_sh) | (ly & (fc.il_rows - 1))); };
+    for (int ty = 0; ty < c.tiles_y; ++ty)
+        for (int tx = 0; tx < c.tiles_x; ++tx) {
+            const size_t tile = (size_t)ty * c.tiles_x + tx;
+            bool valid[64], has = true, any = false;
+            for (int l = 0; l < 64; ++l) {
+                const int px = tx * tw + l % tw, ly = ty * th + l / tw;
+                valid[l] = px < fc.width && ly < fc.local_rows && row_of(ly) < fc.y1;
+                any = any || valid[l];
+                if (valid[l] && (h[tile * 64 + l] & 0xffu) == RT_PRIMARY_NONE) has = false;
+            }
+            has = has && any;
+            const int *keys = nullptr;
+            if (has && !lists.empty()) {
+                const int vblk = (row_of(ty * th) >> (fc.view_shift >> 8)) * nbx + ((tx * tw) >> (fc.view_shift & 255));
+                keys = reinterpret_cast<const int *>(lists.data() + (size_t)vblk * RT_VIEW_SLOT + 1 + RT_VIEW_CAP);
+            }
+            if (has) out->tiles_recorded++;
+            for (int l = 0; l < 64; ++l) {
+                const unsigned e = h[tile * 64 + l] & 0xffu;
+                if (has && valid[l]) (e == RT_PRIMARY_MISS ? out->miss_pixels : out->hit_pixels)++;
+                if (positions) positions[tile * 64 + l] = !(has && valid[l]) ? -2 : e == RT_PRIMARY_MISS ? -1 : (keys && e < RT_VIEW_CAP) ? keys[e] : -2;
+            }
+        }
+    if (dwords) memcpy(dwords, h.data(), sizeof(unsigned) * 64 * n);
+    return RT_OK;
+}
+
+// Tests: overwrite the primary records of the table the last launch wrote or read.
+extern "C" int rt_debug_set_primary_records(rt_scene *s, const unsigned *dwords, size_t n)
+{
+    if (!s || !dwords || s->verdict_last < 0 || !s->verdicts[s->verdict_last].valid) {
+        rt_set_error("rt_debug_set_primary_records: the last launch neither wrote nor read a table");
+        return RT_ERR_INVALID;
+    }
+    VerdictSlot &c = s->verdicts[s->verdict_last];
+    const size_t tiles = (size_t)c.tiles_x * (size_t)c.tiles_y;
+    if (n != 64 * tiles) {
+        rt_set_error("rt_debug_set_primary_records: %zu records given, the table has %d x %d tiles of 64", n, c.tiles_x, c.tiles_y);
+        return RT_ERR_INVALID;
+    }
+    const int rc = rt_scene_quiesce(s);   // no launch still reads the table
+    if (rc != RT_OK) return rc;
+    RT_HIP(c.built.host_wait());
+    RT_HIP(hipMemcpy(reinterpret_cast<char *>(c.buf.get()) + RT_PRIMARY_RECORDS_OFFSET(tiles), dwords, sizeof(unsigned) * n, hipMemcpyHostToDevice));
     return RT_OK;
 }
 

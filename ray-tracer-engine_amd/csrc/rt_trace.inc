@@ -1323,15 +1323,27 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
     // loop, whose scalar and vector files are full.
     constexpr bool VD_USE = (MODE == 6), VD_REC = (MODE == 7), VERD = VD_USE || VD_REC;
     static_assert(!VERD || (CULL && FEAT == 0), "light verdicts: the sphere-only culling kernels");
+    // A reading launch forms a group's ball (g_r2, the check against its sphere's ball: two wave reductions) only where a
+    // light of the group culls at all: 3.4 % of the 0.136 lights per tile that it still walks at C3. (RT_EAGER_BALL: the
+    // variant it was measured against, profiles/primary_records_ab.json.)
+#ifdef RT_EAGER_BALL
+    constexpr bool LAZY_BALL = false;
+#else
+    constexpr bool LAZY_BALL = VD_USE;
+#endif
     // Shadow counts (step 5b) go the same way: the tile's tag dword is asked for by lane 2 and parked behind the word,
     // and behind that the tile's index, which the light loop needs for a record's address and must not hold in a register.
     unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192)) + wave * 4;
     unsigned vd_ld = 0;
+    unsigned pr_rec = RT_PRIMARY_NONE;
     if (VERD) {
         const unsigned vd_tile = blk_y * tiles_x + blk_x, vd_tiles = tiles_x * ((unsigned)(fc.local_rows + TH - 1) / (unsigned)TH);   // T = the grid (rt_dev_trace_config)
         // (dwords: the word's halves at 2 tile + lane, the tag at 2 T + tile)
         if (VD_USE && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.verdict_rd)[lane < 2 ? 2 * (size_t)vd_tile + lane : 2 * (size_t)vd_tiles + vd_tile];
         if (lane == 3) vd_ld = vd_tile;
+        // Primary records (step 5c): the lane's dword -- which entry of the tile's view list is its closest hit, and its
+        // texel -- asked for here beside the word and used after the ray arithmetic.
+        if (VD_USE) pr_rec = reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(fc.verdict_rd) + RT_PRIMARY_RECORDS_OFFSET(vd_tiles))[(size_t)vd_tile * 64u + lane];
     }
     const int tile_x = blk_x * TW;
     // local row -> global row: a contiguous band, or row blocks dealt round-robin
@@ -1558,8 +1570,30 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         const float *plbs = reinterpret_cast<const float *>(myblks);
         const bool p_front_to_back = CULL && p_use_list && pcount > 1;
         int holder = -1;
+        int hent = 0;   // (MODE 7) the list entry that holds nt
+        // Primary records (step 5c): a reading launch whose tile has a record does not walk. Which entry each lane ends on
+        // is what the recording launch decided from the same list and the same rays; the lane evaluates that one entry, by
+        // the walk's own gate, functions and operands, and so arrives at the same nt, holder and centre. A lane on record
+        // as a miss keeps nt = +inf; the record is not trusted beyond that: hit_m below is formed from nt as ever.
+        // (wave-uniform: the tile read a view list, and no valid lane's record says "none")
+        const bool pr_use = VD_USE && v_use && (valid_m & LM((pr_rec & 0xffu) == RT_PRIMARY_NONE)) == 0;
+        if (VD_USE && pr_use) {
+            const unsigned e = pr_rec & 0xffu;
+            if (valid && e < (unsigned)RT_VIEW_CAP) {
+                const float4 s = mylist[e];
+                const int pos = mykeys[e];
+                const Quad q = quadratic(pr, s);
+                const bool need = q.disc >= 0.f && !(q.h > 0.f && q.disc < q.BB * RT_BEHIND_FACTOR);
+                float t;
+                if (need && intersect_tail_t<LEAN_PRIMARY_TAIL>(pr, q, t) && t < nt) {
+                    nt = t;
+                    holder = pos;
+                    hcx = s.x; hcy = s.y; hcz = s.z;
+                }
+            }
+        }
         float4 pcur = pcount > 0 ? primary_entry(0) : make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int e = 0; e < pcount; ++e) {
+        for (int e = 0; !(VD_USE && pr_use) && e < ((RT_ABL(262144) && pcount > 1) ? 1 : pcount); ++e) {   // (262144: the price of the walk -- entry 0 for every lane)
             const float4 s = pcur;
             const int pos = (CULL && p_use_list) ? mykeys[e] : e;
             pcur = primary_entry(e + 1 < pcount ? e + 1 : e);   // one entry in flight
@@ -1575,6 +1609,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                         if (t < nt || (t == nt && holder >= 0 && pos < holder)) {
                             nt = t;
                             holder = pos;
+                            if (VD_REC) hent = e;
                             hcx = s.x; hcy = s.y; hcz = s.z;
                             if (MESH) hkind = 1;
                         }
@@ -1621,7 +1656,16 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 
         // ================= miss: skybox::getFColor, kernel.cu:1147-1166 =================
         int sky_idx = -1;
-        if (valid && !hit) {
+        int pr_tex = 0;   // (MODE 7) the lane's clamped texel index, sky or object texture
+        if (VD_USE && pr_use) {
+            // the sky texel on record: no sky-sphere intersection, no normalise, no uv chain; the clamp stays
+            if (valid && !hit) {
+                int idx = (int)(pr_rec >> 8);
+                const int last = ax->sky_w * ax->sky_h - 1;
+                idx = idx < 0 ? 0 : (idx > last ? last : idx);
+                sky_idx = idx;
+            }
+        } else if (valid && !hit) {
             const float4 sk = make_float4(ax->sky_cx, ax->sky_cy, ax->sky_cz, ax->sky_r2);
             const Quad q = quadratic(pr, sk);
             float t;
@@ -1657,6 +1701,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             const int last = sky_w * sky_h - 1;
             idx = idx < 0 ? 0 : (idx > last ? last : idx);   // documented clamp (reference is UB there)
             sky_idx = idx;
+            if (VD_REC) pr_tex = idx;
         }
 
         // ================= hit: shade, kernel.cu:1396-1405, 1643-1677 =================
@@ -1699,6 +1744,8 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 normalise_t<LEAN>(normal);
                 if (RT_ABL(8)) {
                     tx = normal.x; ty = normal.y;
+                } else if (VD_USE && pr_use) {
+                    ci_fast = (int)(pr_rec >> 8);       // the texel on record (24 bits: never negative); clamped below
                 } else if (FAST) {
                     approx_sphere_uv(normal, tx, ty);   // no certainty test: a texel now and then is the neighbour
                 } else if (LEAN && !RT_ABL(4096)) {
@@ -1720,12 +1767,28 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             if (ci_fast >= 0) ci = ci_fast;
             const int last = t_w * t_h - 1;
             ci = ci < 0 ? 0 : (ci > last ? last : ci);       // documented clamp
+            if (VD_REC) pr_tex = ci;
             tr = kt->tex_r[ci];
             tg = kt->tex_g[ci];
             tb = kt->tex_b[ci];
             // start_O = normal * 0.00001 + new_org, kernel.cu:1647
             start = V3{normal.x * 0.00001f + hp.x, normal.y * 0.00001f + hp.y, normal.z * 0.00001f + hp.z};
             if (STATS == 1) st_hits += 1;
+        }
+        if (VD_REC) {
+            // The recording launch: every lane's primary record, one coalesced 256-byte store per wave. A tile that walked
+            // no view list (an overflowed block or one without cone, a tile shape that does not nest, a scene below 64
+            // spheres, the switch off) says so in all its lanes, and so does every tile when a texture's texel indices
+            // do not fit 24 bits -- decided here from the launch's own uniforms, wave-uniformly.
+            FcPtr kp = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kp));
+            const bool fits = (unsigned)(kp->tex_w * kp->tex_h) <= (unsigned)RT_PRIMARY_TEXELS && (unsigned)(ax->sky_w * ax->sky_h) <= (unsigned)RT_PRIMARY_TEXELS;
+            unsigned d = RT_PRIMARY_NONE;
+            if (v_use && fits) d = (hit ? (unsigned)hent : RT_PRIMARY_MISS) | ((unsigned)pr_tex << 8);
+            const unsigned p_tiles_x = (unsigned)(kp->width + TW - 1) / (unsigned)TW;
+            const unsigned p_tiles = p_tiles_x * ((unsigned)(kp->local_rows + TH - 1) / (unsigned)TH);   // = the grid
+            unsigned *const o_prim = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(kp->verdict_wr) + RT_PRIMARY_RECORDS_OFFSET(p_tiles));
+            o_prim[(size_t)(blk_y * p_tiles_x + blk_x) * 64u + lane] = d;
         }
 
         phase(3);
@@ -1824,6 +1887,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 g_ax = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, start.x), glead));
                 g_ay = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, start.y), glead));
                 g_az = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, start.z), glead));
+                if (!LAZY_BALL) {
                 const float ox = start.x - g_ax, oy = start.y - g_ay, oz = start.z - g_az;
                 g_r2 = uniform(wave_max(inc ? __builtin_fmaf(ox, ox, __builtin_fmaf(oy, oy, oz * oz)) : 0.f));
                 // The sphere's occluder lists and its kbeam (rt_tables.hip) hold for starts inside the ball of radius
@@ -1839,7 +1903,9 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     const float far2 = uniform(wave_max(inc ? __builtin_fmaf(cx, cx, __builtin_fmaf(cy, cy, cz * cz)) : 0.f));
                     if (!(far2 <= ball * ball * 0.99999f)) g_sphere = -1;   // (also for a NaN)
                 }
+                }
             }
+            bool ball_done = !LAZY_BALL;   // (LAZY_BALL: the two reductions wait for the group's first light that culls at all)
             for (int li = 0; li < fc.n_lights; ++li) {
                 // An earlier launch of the same inputs left this iteration by one of the three exits marked below:
                 // so would this one, having added nothing -- the iteration is skipped whole.
@@ -1911,6 +1977,18 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 // (a light whose all-clear test held for these inputs needs neither its list nor the test again)
                 // (nor does a light whose counts are on record)
                 if (CULL && !(VD_USE && vd == RT_VERDICT_CLEAR) && !sc_use) {
+                    if (LAZY_BALL && !ball_done) {   // the group's ball, as above
+                        const float ox = start.x - g_ax, oy = start.y - g_ay, oz = start.z - g_az;
+                        g_r2 = uniform(wave_max(inc ? __builtin_fmaf(ox, ox, __builtin_fmaf(oy, oy, oz * oz)) : 0.f));
+                        if (g_sphere >= 0) {
+                            const float4 sc = spheres[g_sphere];
+                            const float cx = start.x - sc.x, cy = start.y - sc.y, cz = start.z - sc.z;
+                            const float ball = __builtin_amdgcn_sqrtf(sc.w) * 1.001f + 1.0e-3f;
+                            const float far2 = uniform(wave_max(inc ? __builtin_fmaf(cx, cx, __builtin_fmaf(cy, cy, cz * cz)) : 0.f));
+                            if (!(far2 <= ball * ball * 0.99999f)) g_sphere = -1;
+                        }
+                        ball_done = true;
+                    }
                     bool ok = true;
                     Beam b;
                     b.ux = L.ux; b.uy = L.uy; b.uz = L.uz;
