@@ -912,36 +912,41 @@ class Scene:
         nothing to a tile, and the occluder search of those it found clear; 0: every launch evaluates every light."""
         _check(self.lib.rt_scene_set_light_verdicts(self.handle, mode), "rt_scene_set_light_verdicts")
 
+    def _read_back(self, fn: str, info_cls, wanted, make) -> dict:
+        """An 'info, then buffers' read-back: `fn` with null buffers fills the info struct, whose fields are the dict;
+        where wanted(info), make(info) gives the buffer arguments of a second call and a callable for the entries
+        they become."""
+        call = getattr(self.lib, fn)
+        info = info_cls()
+        _check(call(self.handle, C.byref(info), *[None] * (len(call.argtypes) - 3), 0), fn)
+        d = {k: getattr(info, k) for k, _ in info_cls._fields_}
+        if wanted(info):
+            args, entries = make(info)
+            _check(call(self.handle, C.byref(info), *args), fn)
+            d.update(entries())
+        return d
+
     def light_verdicts(self, want_words: bool = False) -> dict:
         """What the last frame launch did with light verdicts (waits for the table's writer): state 0 nothing / 1 wrote
         / 2 read, slot, tiles_x, tiles_y, unwritten, nothing, clear; with want_words also 'words', uint64 [tiles_y,
         tiles_x]: two bits per (group, light) at 16 * group + 2 * light."""
-        info = LightVerdictsInfo()
-        _check(self.lib.rt_debug_light_verdicts(self.handle, C.byref(info), None, 0), "rt_debug_light_verdicts")
-        d = {k: getattr(info, k) for k, _ in LightVerdictsInfo._fields_}
-        if want_words and info.state:
-            buf = np.zeros(info.tiles_x * info.tiles_y, dtype=np.uint64)
-            _check(self.lib.rt_debug_light_verdicts(self.handle, C.byref(info), buf.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                    buf.size), "rt_debug_light_verdicts")
-            d["words"] = buf.reshape(info.tiles_y, info.tiles_x)
-        return d
+        def make(i):
+            buf = np.zeros(i.tiles_x * i.tiles_y, dtype=np.uint64)
+            return (buf.ctypes.data_as(C.POINTER(C.c_uint64)), buf.size), lambda: {"words": buf.reshape(i.tiles_y, i.tiles_x)}
+        return self._read_back("rt_debug_light_verdicts", LightVerdictsInfo, lambda i: want_words and i.state, make)
 
     def shadow_counts(self, want_tables: bool = False) -> dict:
         """The shadow counts behind the last launch's light verdicts (waits for the table's writer): state, slot, tiles_x,
         tiles_y, records (per tile), tagged, tiles_tagged, tagged_all (over all of the scene's tables); with want_tables also 'tags', uint8 [tiles_y, tiles_x, 4]
         (byte r: 0x80 | group << 3 | light of record r, 0 = free) and 'counts', uint8 [tiles_y, tiles_x, records, 64]."""
-        info = ShadowCountsInfo()
-        _check(self.lib.rt_debug_shadow_counts(self.handle, C.byref(info), None, None, 0), "rt_debug_shadow_counts")
-        d = {k: getattr(info, k) for k, _ in ShadowCountsInfo._fields_}
-        if want_tables and info.state:
-            n = info.tiles_x * info.tiles_y
+        def make(i):
+            n = i.tiles_x * i.tiles_y
             tags = np.zeros(n, dtype=np.uint32)
-            counts = np.zeros((n, info.records, 64), dtype=np.uint8)
-            _check(self.lib.rt_debug_shadow_counts(self.handle, C.byref(info), tags.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                   counts.ctypes.data_as(C.POINTER(C.c_uint8)), n), "rt_debug_shadow_counts")
-            d["tags"] = tags.view(np.uint8).reshape(info.tiles_y, info.tiles_x, 4)
-            d["counts"] = counts.reshape(info.tiles_y, info.tiles_x, info.records, 64)
-        return d
+            counts = np.zeros((n, i.records, 64), dtype=np.uint8)
+            return ((tags.ctypes.data_as(C.POINTER(C.c_uint32)), counts.ctypes.data_as(C.POINTER(C.c_uint8)), n),
+                    lambda: {"tags": tags.view(np.uint8).reshape(i.tiles_y, i.tiles_x, 4),
+                             "counts": counts.reshape(i.tiles_y, i.tiles_x, i.records, 64)})
+        return self._read_back("rt_debug_shadow_counts", ShadowCountsInfo, lambda i: want_tables and i.state, make)
 
     def set_shadow_counts(self, tags=None, counts=None):
         """Tests: overwrites the record tags (uint8 [tiles_y, tiles_x, 4]) and / or the records (uint8 [tiles_y, tiles_x,
@@ -963,18 +968,13 @@ class Scene:
         tiles_y, tile_w, tiles_recorded, hit_pixels, miss_pixels; with want_tables also 'dwords', uint32 [tiles_y, tiles_x,
         64] (see decode_primary_records; lane = row in tile * tile_w + column in tile) and 'positions', int32 of the same
         shape: the sphere-table position a pixel's entry resolves to, -1 a miss, -2 no record or outside the frame."""
-        info = PrimaryRecordsInfo()
-        _check(self.lib.rt_debug_primary_records(self.handle, C.byref(info), None, None, 0), "rt_debug_primary_records")
-        d = {k: getattr(info, k) for k, _ in PrimaryRecordsInfo._fields_}
-        if want_tables and info.state:
-            n = 64 * info.tiles_x * info.tiles_y
+        def make(i):
+            n = 64 * i.tiles_x * i.tiles_y
             dwords = np.zeros(n, dtype=np.uint32)
             pos = np.zeros(n, dtype=np.int32)
-            _check(self.lib.rt_debug_primary_records(self.handle, C.byref(info), dwords.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                     pos.ctypes.data_as(C.POINTER(C.c_int32)), n), "rt_debug_primary_records")
-            d["dwords"] = dwords.reshape(info.tiles_y, info.tiles_x, 64)
-            d["positions"] = pos.reshape(info.tiles_y, info.tiles_x, 64)
-        return d
+            return ((dwords.ctypes.data_as(C.POINTER(C.c_uint32)), pos.ctypes.data_as(C.POINTER(C.c_int32)), n),
+                    lambda: {"dwords": dwords.reshape(i.tiles_y, i.tiles_x, 64), "positions": pos.reshape(i.tiles_y, i.tiles_x, 64)})
+        return self._read_back("rt_debug_primary_records", PrimaryRecordsInfo, lambda i: want_tables and i.state, make)
 
     def set_primary_records(self, dwords):
         """Tests: overwrites the primary records (uint32 [tiles_y, tiles_x, 64]) of the table that the last launch wrote or
@@ -986,14 +986,10 @@ class Scene:
     def view_lists_info(self, want_lists: bool = False) -> dict:
         """What the last launch read (waits for the lists' build): read, block size, blocks, overflowed and not-built
         blocks, longest and mean list; with want_lists also 'lists' (see unpack_view_lists)."""
-        info = ViewListsInfo()
-        _check(self.lib.rt_scene_view_lists_info(self.handle, C.byref(info), None, 0), "rt_scene_view_lists_info")
-        d = _view_info_dict(info)
-        if want_lists and info.read:
-            buf = np.zeros((info.blocks * RT_VIEW_SLOT, 4), dtype=np.float32)
-            _check(self.lib.rt_scene_view_lists_info(self.handle, C.byref(info), _fptr(buf), buf.shape[0]), "rt_scene_view_lists_info")
-            d["lists"] = unpack_view_lists(buf, info.blocks)
-        return d
+        def make(i):
+            buf = np.zeros((i.blocks * RT_VIEW_SLOT, 4), dtype=np.float32)
+            return (_fptr(buf), buf.shape[0]), lambda: {"lists": unpack_view_lists(buf, i.blocks)}
+        return self._read_back("rt_scene_view_lists_info", ViewListsInfo, lambda i: want_lists and i.read, make)
 
     @classmethod
     def default(cls, n_spheres: int = 1024, seed: int = 1) -> "Scene":

@@ -6,6 +6,7 @@
 // 1454, 1462-1463, 1538, 1629) and handed to the kernel by value, so it sits in
 // SGPRs instead of being recomputed by 64 lanes.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define RT_DEV_MAX_LIGHTS 8
@@ -265,24 +266,26 @@ struct RtFrameConsts {
     int *aov_id;                // int2 per pixel
     float *aov_albedo;          // float4 per pixel
 
-    // Light verdicts: one word per tile of the launch's layout, at tile_y * tiles_x + tile_x (the
-    // tile's frame coordinates, after tile_perm). Two bits per (group, light) for the first RT_VERDICT_GROUPS groups of
-    // the tile, in the order the kernel forms them, and the first RT_VERDICT_LIGHTS lights, at 16 * group + 2 * light:
-    // 0 = evaluate, RT_VERDICT_NOTHING = the kernel left this iteration by one of its three "adds nothing" exits,
-    // RT_VERDICT_CLEAR = its all-clear test held. verdict_wr: this launch writes the words it finds; verdict_rd: it
-    // consumes the words an earlier launch of bit-identical inputs wrote (the host keeps the key). Either may be null;
-    // only the one-sample sphere-only product kernel (MODE 0, FEAT 0, CULL) looks at them.
-    //
-    // Shadow counts lie behind the words in the same allocation, so the kernel argument does not
-    // grow: with T = tiles of the launch's grid, a tag dword per tile at dword 2 T + tile, then RT_SHADOW_RECORDS records
-    // of 64 bytes per tile from byte 12 T (RT_SHADOW_COUNTS_OFFSET). A record holds, per lane, the number of unshadowed
-    // samples (0..RT_SHADOW_SAMPLES) that a walked light -- code 0, neither dark nor clear -- left; byte r of the tag
-    // dword says whose record r is, 0x80 | group << 3 | light, 0 = free. A light that found no free record has none and
-    // is walked by the reader as before. Primary records (step 5c) lie behind the counts: a dword per lane of every
-    // tile from RT_PRIMARY_RECORDS_OFFSET (below).
-    const unsigned long long *verdict_rd;
-    unsigned long long *verdict_wr;
+    // The resting-view table (layout: the RT_REST_* block below). rest_wr: this launch
+    // records into it; rest_rd: it reads what an earlier launch of bit-identical inputs recorded (the host keeps the
+    // key). Either may be null; only the one-sample sphere-only product kernel (MODE 0, FEAT 0, CULL) looks at them.
+    const unsigned char *rest_rd;
+    unsigned char *rest_wr;
 };
+// The resting-view table: what a recording launch (MODE 7) leaves for the reading launches (MODE 6) of the same key, one
+// allocation of four sections, each an array over the T tiles of the launch's grid by the tile's frame coordinates
+// (tile_y * tiles_x + tile_x, after tile_perm). This block is the layout; nothing else states it.
+//   words    a 64-bit word per tile: two bits per (group, light) for the tile's first RT_VERDICT_GROUPS groups, in the
+//            order the kernel forms them, and the first RT_VERDICT_LIGHTS lights, at 16 * group + 2 * light: 0 = evaluate,
+//            RT_VERDICT_NOTHING = the kernel left by one of its three "adds nothing" exits, RT_VERDICT_CLEAR = all clear.
+//   tags     a dword per tile: byte r says whose shadow-count record r is, RT_SHADOW_TAG(group, light), 0 = free.
+//   counts   RT_SHADOW_RECORDS records of 64 bytes per tile: per lane, the number of unshadowed samples (0..RT_SHADOW_SAMPLES)
+//            that a walked light -- code 0 -- left. A light that found no free record is walked by the reader as before.
+//   primary  a dword per lane of every tile's wave. Bits 0-7: the entry of the tile's staged view list that is the lane's
+//            closest hit, RT_PRIMARY_MISS = none, RT_PRIMARY_NONE = the tile has no record (it walked no view list, or a
+//            texture has more than RT_PRIMARY_TEXELS texels); bits 8-31: the clamped texel index, of the object texture for
+//            a hit, of the sky for a miss. The recording launch stores every lane of every tile it renders; a reader that
+//            finds RT_PRIMARY_NONE in a valid lane takes the walk and the texel arithmetic for the whole tile.
 #define RT_VERDICT_GROUPS 4
 #define RT_VERDICT_LIGHTS 8
 #define RT_VERDICT_NOTHING 1u
@@ -290,17 +293,30 @@ struct RtFrameConsts {
 #define RT_SHADOW_RECORDS 1      // R: the smallest count that gives a record to 95 % of C3's code-0 entries (96.6 %; profiles/shadow_counts_before.json)
 #define RT_SHADOW_TAG_UNWRITTEN 0xffffffffu   // the fill before a recording launch; every tile it renders stores its tags over it
 #define RT_SHADOW_TAG(g, li) (0x80u | ((unsigned)(g) << 3) | (unsigned)(li))
-// byte offsets, from the first verdict word, of the tag dwords and of the records of a table of `tiles` tiles; its size
-#define RT_SHADOW_TAGS_OFFSET(tiles) ((size_t)(tiles) * 8u)
-#define RT_SHADOW_COUNTS_OFFSET(tiles) ((size_t)(tiles) * 12u)
-// Primary records lie behind the shadow-count records: a dword per lane of every tile's wave, at
-// dword tile * 64 + lane from RT_PRIMARY_RECORDS_OFFSET. Bits 0-7: the entry of the tile's staged view list that is the
-// lane's closest hit, RT_PRIMARY_MISS = none, RT_PRIMARY_NONE = the tile has no record (it walked no view list, or a
-// texture has more than 2^24 texels); bits 8-31: the clamped texel index, of the object texture for a hit, of the sky for
-// a miss. The recording launch stores every lane of every tile it renders; a reader that finds RT_PRIMARY_NONE in a
-// valid lane takes the walk and the texel arithmetic for the whole tile.
 #define RT_PRIMARY_MISS 0xffu
 #define RT_PRIMARY_NONE 0xfeu
 #define RT_PRIMARY_TEXELS (1 << 24)
-#define RT_PRIMARY_RECORDS_OFFSET(tiles) ((size_t)(tiles) * (12u + 64u * RT_SHADOW_RECORDS))
-#define RT_VERDICT_TABLE_BYTES(tiles) (RT_PRIMARY_RECORDS_OFFSET(tiles) + (size_t)(tiles) * 256u)
+
+// bytes per tile of each section, in the order they lie; a section's offset is the sum of those before it
+#define RT_REST_WORD_BYTES 8u
+#define RT_REST_TAG_BYTES 4u
+#define RT_REST_RECORD_BYTES 64u      // one shadow-count record: a byte per lane
+#define RT_REST_COUNT_BYTES (RT_REST_RECORD_BYTES * RT_SHADOW_RECORDS)
+#define RT_REST_PRIMARY_BYTES 256u
+#define RT_REST_TAGS_OFFSET(T) ((size_t)(T) * RT_REST_WORD_BYTES)
+#define RT_REST_COUNTS_OFFSET(T) (RT_REST_TAGS_OFFSET(T) + (size_t)(T) * RT_REST_TAG_BYTES)
+#define RT_REST_PRIMARY_OFFSET(T) (RT_REST_COUNTS_OFFSET(T) + (size_t)(T) * RT_REST_COUNT_BYTES)
+#define RT_REST_TABLE_BYTES(T) (RT_REST_PRIMARY_OFFSET(T) + (size_t)(T) * RT_REST_PRIMARY_BYTES)
+#define RT_REST_FILL_BYTES(T) RT_REST_COUNTS_OFFSET(T)   // filled with ones before a recording launch: the words and the tags
+// a tile's word (halves at + 0 and + 1) and its tags, in dwords from the table's first
+#define RT_REST_WORD_DWORD(tile) ((RT_REST_WORD_BYTES / 4u) * (size_t)(tile))
+#define RT_REST_TAG_DWORD(T, tile) (RT_REST_TAGS_OFFSET(T) / 4u + (tile))
+static_assert(RT_REST_TAGS_OFFSET(7) == 8u * 7, "resting-view table: the tags lie behind the words");
+static_assert(RT_REST_COUNTS_OFFSET(7) == 12u * 7 && RT_REST_FILL_BYTES(7) == RT_REST_COUNTS_OFFSET(7), "resting-view table: the fill ends where the counts begin");
+static_assert(RT_REST_PRIMARY_OFFSET(7) == (12u + 64u * RT_SHADOW_RECORDS) * 7, "resting-view table: the primary records lie behind the counts");
+static_assert(RT_REST_TABLE_BYTES(7) == RT_REST_PRIMARY_OFFSET(7) + 256u * 7, "resting-view table: a dword per lane ends it");
+
+// T and its factors: one 64-pixel tile of tile_w x 64 / tile_w per workgroup, over the launch's `width` x `local_rows`
+__host__ __device__ inline unsigned rt_rest_tiles_x(int width, int tile_w) { return (unsigned)(width + tile_w - 1) / (unsigned)tile_w; }
+__host__ __device__ inline unsigned rt_rest_tiles_y(int local_rows, int tile_w) { return (unsigned)(local_rows + 64 / tile_w - 1) / (unsigned)(64 / tile_w); }
+__host__ __device__ inline unsigned rt_rest_tiles(int width, int local_rows, int tile_w) { return rt_rest_tiles_x(width, tile_w) * rt_rest_tiles_y(local_rows, tile_w); }

@@ -138,9 +138,9 @@ int rt_build_frame_consts(const rt_scene *s, const rt_frame_desc *fd, const floa
 int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelChoice *kc);
 void rt_ray_origin(const rt_frame_desc *fd, float org[3]);
 // frames in flight (rt_scene.cpp): host wait for all of them; bookkeeping after a launch that read the scene's cached
-// eye-cone table `cones`, view lists `views` and light verdicts `verdicts` (null: it read none of its own)
+// eye-cone table `cones`, view lists `views` and resting-view table `rest` (null: it read none of its own)
 int rt_scene_quiesce(rt_scene *s);
-int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, RtTableSlot *views, RtTableSlot *verdicts);
+int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, RtTableSlot *views, RtTableSlot *rest);
 // what a graph node needs from the scene
 const float4 *rt_scene_sphere_table(const rt_scene *s);
 int rt_scene_sphere_count(const rt_scene *s);

@@ -219,8 +219,8 @@ static RtTraceFn trace_fn(int tile_w, int cull, int mode, int feat, int multi)
 extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int feat,
                                           const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes)
 {
-    // a product launch that was handed a verdict table runs the instantiation that writes (7) or reads (6) it
-    if (mode == 0 && (fc->verdict_wr || fc->verdict_rd)) mode = fc->verdict_wr ? 7 : 6;
+    // a product launch that was handed a resting-view table runs the instantiation that writes (7) or reads (6) it
+    if (mode == 0 && (fc->rest_wr || fc->rest_rd)) mode = fc->rest_wr ? 7 : 6;
     const RtTraceFn fn = trace_fn(tile_w, cull, mode, feat, fc->spp > 1 ? 1 : 0);
     if (!fn) return hipErrorNotSupported;
     *lds_bytes = (unsigned)(RT_LIST_CAP * sizeof(float4) +   // survivor list
@@ -231,8 +231,7 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
                             192 * sizeof(float) +            // texel colours per pixel
                             (feat == 2 ? (RT_BOX_CAP + 128) * sizeof(int)   // leaf boxes, marked blocks, staged vertices
                                        : 4 * sizeof(unsigned)));            // the tile's light verdicts, record tags and index (same place)
-    const int th = 64 / tile_w;
-    *grid = dim3((fc->width + tile_w - 1) / tile_w, (fc->local_rows + th - 1) / th);
+    *grid = dim3(rt_rest_tiles_x(fc->width, tile_w), rt_rest_tiles_y(fc->local_rows, tile_w));
     *block = dim3(64);
     *func = (const void *)fn;
     return hipSuccess;

@@ -410,10 +410,9 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         rc = rt_scene_prepare_tile_order(s, kc, &fc, stream);
         if (rc != RT_OK) return rc;
     }
-    // light verdicts: the plain one-sample frame of a sphere scene (not a reflective frame, whose passes follow)
-    int verdict = -1;
-    rc = rt_scene_prepare_verdicts(s, kc, &fc, reflect_depth == 0 && kc.mode == 0 && kc.feat == 0 && kc.cull && fc.spp == 1, stream,
-                                   &verdict);
+    // the resting-view table: the plain one-sample frame of a sphere scene (not a reflective frame, whose passes follow)
+    int rest = -1;
+    rc = rt_scene_prepare_rest(s, kc, &fc, reflect_depth == 0 && kc.mode == 0 && kc.feat == 0 && kc.cull && fc.spp == 1, stream, &rest);
     if (rc != RT_OK) return rc;
     if (samples) {   // the frame kernel per sample, the passes per group, the resolve pass
         rc = rt_reflect_launch_samples(s->refl.get(), &fc, &out, &kc, s->d_spheres.get(), s->n_spheres, reflect_depth, stream);
@@ -430,10 +429,10 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
         }
     }
     s->view_last = view;
-    rc = rt_scene_end_verdicts(s, verdict, stream);
+    rc = rt_scene_end_rest(s, rest, stream);
     if (rc != RT_OK) return rc;
     return rt_scene_note_launch(s, stream, slot >= 0 ? &s->cones[slot] : nullptr, view >= 0 ? &s->views[view] : nullptr,
-                                verdict >= 0 ? &s->verdicts[verdict] : nullptr);
+                                rest >= 0 ? &s->rest[rest] : nullptr);
 }
 
 // ---------------------------------------------------------------------------

@@ -46,7 +46,7 @@ int rt_scene_wait_all_frames(rt_scene *s, hipStream_t stream)
 }
 
 // A frame has just been enqueued on `stream`: give it the next ring slot, and mark the slots it read with it.
-int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, RtTableSlot *views, RtTableSlot *verdicts)
+int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, RtTableSlot *views, RtTableSlot *rest)
 {
     const int k = (int)(s->ring_seq % RT_RING);
     RT_HIP(s->ring[k].create());
@@ -54,7 +54,7 @@ int rt_scene_note_launch(rt_scene *s, hipStream_t stream, RtTableSlot *cones, Rt
     if (s->ring_used[k]) RT_HIP(hipStreamWaitEvent(stream, s->ring[k].get(), 0));
     RT_HIP(hipEventRecord(s->ring[k].get(), stream));
     s->ring_used[k] = true;
-    for (RtTableSlot *c : {cones, views, verdicts})
+    for (RtTableSlot *c : {cones, views, rest})
         if (c) {
             c->used = true;
             c->last_use = s->ring_seq;

@@ -1,5 +1,5 @@
 // rt_scene.h -- struct rt_scene and what its own translation units share (rt_scene.cpp, rt_scene_tables.cpp,
-// rt_render.cpp, rt_shim.cpp, rt_debug.cpp). Everything else goes through the functions of rt_internal.h.
+// rt_scene_rest.cpp, rt_render.cpp, rt_shim.cpp, rt_debug.cpp). Everything else goes through the functions of rt_internal.h.
 //
 // Frames in flight and the buffers they read. A frame is asynchronous work on the caller's stream; the scene's device
 // buffers may be read by frames on several streams at once (two frames in flight, a replaying graph). Whoever is about
@@ -27,7 +27,7 @@
 //       scratch;
 //   (g) whatever rewrites or re-allocates a buffer a recorded graph may point into bumps `epoch`, and nothing else
 //       does: of the hand-over functions only an rt_scene_begin_build whose buffer re-allocates;
-//   (h) a light-verdict table is written by a frame launch on the frame's own stream, not by a build on the table
+//   (h) a resting-view table is written by a frame launch on the frame's own stream, not by a build on the table
 //       stream: that stream is ordered behind the slot's last reader (through the frame ring) and its last writer, the
 //       slot's `built` is the writing launch's event, and readers on other streams wait for it on the device. Its
 //       buffer is in no graph, so growing it (after a quiesce) bumps no epoch.
@@ -42,7 +42,7 @@
 #define RT_RING 4
 #define RT_CONE_SLOTS 3
 #define RT_VIEW_SLOTS 4
-#define RT_VERDICT_SLOTS 4
+#define RT_REST_SLOTS 4
 
 // One cached device table of a few: built on the table stream after the slot's last reader (through the frame ring),
 // read after `built` (on the device).
@@ -63,16 +63,16 @@ struct ViewSlot : RtTableSlot {
     int nbx = 0, nby = 0, bw = 0, bh = 0;
 };
 
-// Light verdicts (RtFrameConsts::verdict_rd): one table per recent (view, layout), written by a
+// Resting-view tables (RtFrameConsts::rest_rd): one per recent (view, layout), written by a
 // frame launch itself -- `built` is that launch's event on ITS stream -- and read by later launches of the same key.
-struct RtVerdictKey {
-    RtFrameConsts fc;                     // every field the kernel reads; outputs, tile order and the verdict pointers zeroed
+struct RtRestKey {
+    RtFrameConsts fc;                     // every field the kernel reads; outputs, tile order and the table pointers zeroed
     unsigned long long epoch = 0;         // generation of every table behind fc's pointers that quiesce-and-rewrite mutations touch
     unsigned long long sphere_gen = 0;    // ... and of the sphere list (tables built from it: cones, view lists, light tables)
     int tile = 0, cull = 0, mode = 0, feat = 0;
 };
-struct VerdictSlot : RtTableSlot {       // buf: RT_VERDICT_TABLE_BYTES(tiles) -- the words, the record tags, the shadow-count records, the primary records
-    RtVerdictKey key;
+struct RestSlot : RtTableSlot {          // buf: RT_REST_TABLE_BYTES(tiles), the layout of rt_device.h
+    RtRestKey key;
     int tiles_x = 0, tiles_y = 0;
 };
 
@@ -189,14 +189,14 @@ struct rt_scene {
     ViewSlot views[RT_VIEW_SLOTS];
     int view_lists_mode = 1;                 // rt_scene_set_view_lists
     int view_last = -1;                      // the slot the last launch read, -1: it read none
-    // light verdicts of a resting view
-    VerdictSlot verdicts[RT_VERDICT_SLOTS];
+    // the tables of a resting view: light verdicts, shadow counts, primary records
+    RestSlot rest[RT_REST_SLOTS];
     int light_verdicts_mode = 1;             // rt_scene_set_light_verdicts
-    RtVerdictKey verdict_seen[RT_VERDICT_SLOTS];   // keys of recent launches that found no table and wrote none, a ring:
-    bool verdict_seen_valid[RT_VERDICT_SLOTS] = {};   // a key leaves it when its table is written or the ring comes round
-    int verdict_seen_next = 0;               // the entry the next such key replaces
-    int verdict_last = -1;                   // the slot the last launch wrote or read, -1: neither
-    int verdict_last_wrote = 0;              // 1: it wrote it
+    RtRestKey rest_seen[RT_REST_SLOTS];      // keys of recent launches that found no table and wrote none, a ring:
+    bool rest_seen_valid[RT_REST_SLOTS] = {};   // a key leaves it when its table is written or the ring comes round
+    int rest_seen_next = 0;                  // the entry the next such key replaces
+    int rest_last = -1;                      // the slot the last launch wrote or read, -1: neither
+    int rest_last_wrote = 0;                 // 1: it wrote it
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
     std::unique_ptr<RtReflect, RtReflectDeleter> refl;
     // the two denoisers' scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand; `dn_done`
@@ -269,11 +269,11 @@ int rt_scene_prepare_eye(rt_scene *s, const float org[3], hipStream_t stream, in
 int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelChoice &kc, int cone_slot, RtFrameConsts *fc,
                           hipStream_t stream, int *view_out);
 int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, hipStream_t stream);
-// Light verdicts of a launch whose uniforms are otherwise complete. `eligible`: it runs the one-sample sphere-only
+// rt_scene_rest.cpp: the resting-view table of a launch whose uniforms are otherwise complete. `eligible`: it runs the one-sample sphere-only
 // product kernel. Points fc at the table it reads or writes (slot index in *slot_out, -1: neither); after the launch
-// rt_scene_end_verdicts records a written table.
-int rt_scene_prepare_verdicts(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out);
-int rt_scene_end_verdicts(rt_scene *s, int slot, hipStream_t stream);
+// rt_scene_end_rest records a written table.
+int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out);
+int rt_scene_end_rest(rt_scene *s, int slot, hipStream_t stream);
 int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float aspect, int total);
 void rt_raygen_fill(int width, int height, float aspect, int total, float *h);   // the tables' values (host)
 void rt_build_frame_aux(const rt_scene *s, RtFrameAux *ax);

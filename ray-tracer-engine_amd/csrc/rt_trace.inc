@@ -1234,8 +1234,8 @@ __device__ __forceinline__ PreSure<N> presure_test(V3 o, const V3 (&dq)[N], floa
 // (rt_launch_opts.force_slow_path: tests), 3 = per-phase cycle stamps (s_memtime; RT_TUNING
 // builds only, run time never quoted), 4 = opt-in approximate arithmetic (rt_launch_opts.fast),
 // 5 = the product kernel plus the G-buffer stores (rt_frame_desc.aov_*; one sample, default tile),
-// 6 = the product kernel consuming light verdicts (RtFrameConsts::verdict_rd), 7 = the product kernel recording them
-// (verdict_wr): one-sample launches of sphere scenes, chosen by rt_dev_trace_config from the two pointers -- MODE 0
+// 6 = the product kernel consuming light verdicts (RtFrameConsts::rest_rd), 7 = the product kernel recording them
+// (rest_wr): one-sample launches of sphere scenes, chosen by rt_dev_trace_config from the two pointers -- MODE 0
 // itself carries neither the code nor the registers of either.
 // FEAT: 0 = spheres only (the reference's default scene and every BASELINE config), 1 = with
 // the cube / plane branches of castRay and castLightRay, 2 = with those and the triangle mesh.
@@ -1316,7 +1316,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         blk_y = p >> 16;
     }
     if (fc.tile_cost) t_start = (unsigned)__builtin_amdgcn_s_memtime();
-    // Light verdicts (RtFrameConsts::verdict_rd / verdict_wr). MODE 6: the tile's word of an earlier launch of
+    // Light verdicts (RtFrameConsts::rest_rd / rest_wr). MODE 6: the tile's word of an earlier launch of
     // bit-identical inputs is asked for here (lanes 0 and 1, a dword each, by the tile's frame coordinates), parked in
     // the wave's LDS ahead of the light loop and consumed there two bits at a time. MODE 7: the word this launch finds
     // is gathered in the same place and stored at the write-back. Nothing of it is held in a register across the light
@@ -1337,13 +1337,13 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
     unsigned vd_ld = 0;
     unsigned pr_rec = RT_PRIMARY_NONE;
     if (VERD) {
-        const unsigned vd_tile = blk_y * tiles_x + blk_x, vd_tiles = tiles_x * ((unsigned)(fc.local_rows + TH - 1) / (unsigned)TH);   // T = the grid (rt_dev_trace_config)
-        // (dwords: the word's halves at 2 tile + lane, the tag at 2 T + tile)
-        if (VD_USE && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.verdict_rd)[lane < 2 ? 2 * (size_t)vd_tile + lane : 2 * (size_t)vd_tiles + vd_tile];
+        const unsigned vd_tile = blk_y * tiles_x + blk_x, vd_tiles = tiles_x * rt_rest_tiles_y(fc.local_rows, TW);   // T = the grid
+        // (a dword each: the word's halves, the tag)
+        if (VD_USE && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.rest_rd)[lane < 2 ? RT_REST_WORD_DWORD(vd_tile) + lane : RT_REST_TAG_DWORD(vd_tiles, vd_tile)];
         if (lane == 3) vd_ld = vd_tile;
         // Primary records (step 5c): the lane's dword -- which entry of the tile's view list is its closest hit, and its
         // texel -- asked for here beside the word and used after the ray arithmetic.
-        if (VD_USE) pr_rec = reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(fc.verdict_rd) + RT_PRIMARY_RECORDS_OFFSET(vd_tiles))[(size_t)vd_tile * 64u + lane];
+        if (VD_USE) pr_rec = reinterpret_cast<const unsigned *>(fc.rest_rd + RT_REST_PRIMARY_OFFSET(vd_tiles))[(size_t)vd_tile * (RT_REST_PRIMARY_BYTES / 4u) + lane];
     }
     const int tile_x = blk_x * TW;
     // local row -> global row: a contiguous band, or row blocks dealt round-robin
@@ -1785,10 +1785,10 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             const bool fits = (unsigned)(kp->tex_w * kp->tex_h) <= (unsigned)RT_PRIMARY_TEXELS && (unsigned)(ax->sky_w * ax->sky_h) <= (unsigned)RT_PRIMARY_TEXELS;
             unsigned d = RT_PRIMARY_NONE;
             if (v_use && fits) d = (hit ? (unsigned)hent : RT_PRIMARY_MISS) | ((unsigned)pr_tex << 8);
-            const unsigned p_tiles_x = (unsigned)(kp->width + TW - 1) / (unsigned)TW;
-            const unsigned p_tiles = p_tiles_x * ((unsigned)(kp->local_rows + TH - 1) / (unsigned)TH);   // = the grid
-            unsigned *const o_prim = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(kp->verdict_wr) + RT_PRIMARY_RECORDS_OFFSET(p_tiles));
-            o_prim[(size_t)(blk_y * p_tiles_x + blk_x) * 64u + lane] = d;
+            const unsigned p_tiles_x = rt_rest_tiles_x(kp->width, TW);
+            const unsigned p_tiles = p_tiles_x * rt_rest_tiles_y(kp->local_rows, TW);   // = the grid
+            unsigned *const o_prim = reinterpret_cast<unsigned *>(kp->rest_wr + RT_REST_PRIMARY_OFFSET(p_tiles));
+            o_prim[(size_t)(blk_y * p_tiles_x + blk_x) * (RT_REST_PRIMARY_BYTES / 4u) + lane] = d;
         }
 
         phase(3);
@@ -2375,10 +2375,9 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     if (slot >= 0) {
                         FcPtr kg = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
                         asm volatile("" : "+s"(kg));
-                        const unsigned tiles = ((unsigned)(kg->width + TW - 1) / (unsigned)TW) * ((unsigned)(kg->local_rows + TH - 1) / (unsigned)TH);   // = the grid
+                        const unsigned tiles = rt_rest_tiles(kg->width, kg->local_rows, TW);
                         const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[3]);
-                        unsigned char *rec = reinterpret_cast<unsigned char *>(kg->verdict_wr) + RT_SHADOW_COUNTS_OFFSET(tiles) +
-                                             ((size_t)tile * RT_SHADOW_RECORDS + (size_t)slot) * 64u;
+                        unsigned char *rec = kg->rest_wr + RT_REST_COUNTS_OFFSET(tiles) + ((size_t)tile * RT_SHADOW_RECORDS + (size_t)slot) * RT_REST_RECORD_BYTES;
                         rec[lane] = (unsigned char)(us >> 16);
                         if (lane == 0)
                             (void)__hip_atomic_fetch_or(&myvd[2], RT_SHADOW_TAG(g, li) << (8 * slot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -2407,10 +2406,9 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     if (sc_use) {
                         FcPtr kg = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
                         asm volatile("" : "+s"(kg));
-                        const unsigned tiles = ((unsigned)(kg->width + TW - 1) / (unsigned)TW) * ((unsigned)(kg->local_rows + TH - 1) / (unsigned)TH);   // = the grid
+                        const unsigned tiles = rt_rest_tiles(kg->width, kg->local_rows, TW);
                         const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[3]);
-                        const unsigned char *rec = reinterpret_cast<const unsigned char *>(kg->verdict_rd) + RT_SHADOW_COUNTS_OFFSET(tiles) +
-                                                   ((size_t)tile * RT_SHADOW_RECORDS + (size_t)(vd - 4u)) * 64u;
+                        const unsigned char *rec = kg->rest_rd + RT_REST_COUNTS_OFFSET(tiles) + ((size_t)tile * RT_SHADOW_RECORDS + (size_t)(vd - 4u)) * RT_REST_RECORD_BYTES;
                         // (a scalar base and a lane index formed on the spot, both opaque, and a global load said to be one:
                         // as plain expressions the compiler keeps parts of the address in vector registers -- four spills)
                         asm volatile("" : "+s"(rec));
@@ -2507,10 +2505,10 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
     }
 
     if (VD_REC) {   // the tile's light verdicts as this launch found them (an all-sky tile: 0)
-        unsigned *const o_verdict = reinterpret_cast<unsigned *>(kargs->verdict_wr);
+        unsigned *const o_rest = reinterpret_cast<unsigned *>(kargs->rest_wr);
         wave_lds_sync();
-        if (wb_lane < 2) o_verdict[2 * (size_t)(wb_y * wb_tiles_x + wb_x) + wb_lane] = myvd[wb_lane];
-        if (wb_lane == 2) o_verdict[2 * (size_t)(wb_tiles_x * ((unsigned)(kargs->local_rows + TH - 1) / (unsigned)TH)) + (wb_y * wb_tiles_x + wb_x)] = myvd[2];   // the tags of its records
+        if (wb_lane < 2) o_rest[RT_REST_WORD_DWORD(wb_y * wb_tiles_x + wb_x) + wb_lane] = myvd[wb_lane];
+        if (wb_lane == 2) o_rest[RT_REST_TAG_DWORD(rt_rest_tiles(kargs->width, kargs->local_rows, TW), wb_y * wb_tiles_x + wb_x)] = myvd[2];   // the tags of its records
     }
     if (o_cost) {   // this tile's wave duration, for the order of later frames (a plain store: an atomic maximum
         // per block of tiles here, 256 waves ending together on one address, slowed the whole launch down by 3 %)

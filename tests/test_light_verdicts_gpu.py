@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import verdict_runs as R
 from scenes import Inputs, Scn, mixed_scene
 
 pytestmark = pytest.mark.gpu
@@ -35,13 +36,7 @@ def inputs(rt, gpu):
 
 def references(inp, w=W, h=H, **kw):
     """The frame with the switch off and the brute-force frame, from a scene of its own."""
-    ref = inp.scene()
-    ref.set_light_verdicts(0)
-    off = frame(ref, w, h, **kw)
-    assert ref.light_verdicts()["state"] == 0
-    brute = frame(ref, w, h, cull=False, **kw)
-    assert same(off, brute)
-    return off
+    return R.switched_off(inp, w, h, **kw)[0]
 
 
 LAYOUTS = {
@@ -85,13 +80,6 @@ def test_switch(inputs):
     assert [(same(frame(sc), off), sc.light_verdicts()["state"]) for _ in range(3)] == [(True, 0), (True, 1), (True, 2)]
 
 
-def _copy_lights(rt, lights, n):
-    arr = (rt.Light * n)()
-    for i in range(n):
-        arr[i] = rt.Light(rt.Vec3(lights[i].pos.x, lights[i].pos.y, lights[i].pos.z), lights[i].size, lights[i].r, lights[i].g, lights[i].b)
-    return arr
-
-
 def test_invalidation(rt, inputs):
     """Each change between launches of a warmed-up scene: the next frames equal a fresh scene's and the brute-force one."""
     inp = Inputs(rt, 1024)
@@ -111,7 +99,7 @@ def test_invalidation(rt, inputs):
 
     assert settle("start") == [0, 1, 2]
     # one light's position
-    inp.lights = _copy_lights(rt, inp.lights, 3)
+    inp.lights = R.copy_lights(rt, inp.lights, 3)
     inp.lights[0].pos.x = 14.0
     sc.set_lights(inp.lights, 3)
     assert settle("light position") == [0, 1, 2]
@@ -293,7 +281,7 @@ def test_meaning_of_nothing(rt, inputs):
     checked = 0
     for li in range(3):
         dark = Inputs(rt, 1024)
-        dark.lights = _copy_lights(rt, inp.lights, 3)
+        dark.lights = R.copy_lights(rt, inp.lights, 3)
         dark.lights[li].r = dark.lights[li].g = dark.lights[li].b = 0.0
         d = frame(dark.scene())
         for ty in range(words.shape[0]):

@@ -11,45 +11,23 @@ import pytest
 
 import verdict_runs as R
 from scenes import Inputs, Scn
-from test_verdict_app_gpu import _App
 
 pytestmark = pytest.mark.gpu
 
-SIZES = {1024: (160, 90), 256: (96, 54)}     # the scene of tests/golden/c3_160x90_n1024.npz, and a smaller one
+SIZES, layouts, rows_of = R.SIZES, R.layouts, R.rows_of
 LAYOUTS = ["tile8", "tile16", "tile32", "tile64", "band", "interleave"]
-
-
-def layouts(h):
-    return {"tile8": dict(), "tile16": dict(tile=16), "tile32": dict(tile=32), "tile64": dict(tile=64),
-            "band": dict(y0=16, y1=h - 18), "interleave": dict(interleave=(2, 1, 16))}
 
 
 @pytest.fixture(scope="module")
 def refs(rt, gpu, oracle):
-    """Per scene: its inputs and the oracle's whole frame (computed once, never changed)."""
-    out = {}
-    for n, (w, h) in SIZES.items():
-        inp = Inputs(rt, n)
-        out[n] = (inp, R.oracle_frame(oracle, inp, w, h))
-    return out
-
-
-def rows_of(rt, h, kw):
-    if kw.get("interleave"):
-        cnt, idx, blk = kw["interleave"]
-        return np.asarray(rt.interleaved_rows(h, idx, cnt, blk), dtype=np.int64)
-    return np.arange(kw.get("y0", 0), kw.get("y1") or h)
+    return R.oracle_refs(rt, oracle)
 
 
 def at_rest(inp, w, h, want, what, launches=5, **kw):
     """Switch off = brute force = `want`; then plain, recording and reading launches on one scene, all = `want`.
     -> (the scene, its primary-record info after the last launch)."""
-    ref = inp.scene()
-    ref.set_light_verdicts(0)
-    R.assert_same(R.frame(ref, w, h, **kw), want, what + ": switch off")
-    info = ref.primary_records()
-    assert info["state"] == 0 and info["tiles_recorded"] == 0, info
-    R.assert_same(R.frame(ref, w, h, cull=False, **kw), want, what + ": brute force")
+    _, info = R.switched_off(inp, w, h, want, what + ": ", read_back="primary_records", **kw)
+    assert info["tiles_recorded"] == 0, info
     sc = inp.scene()
     R.resting(sc, dict(width=w, height=h, **kw), want, launches=launches, what=what)
     info = sc.primary_records()
@@ -136,7 +114,7 @@ def test_two_identical_spheres(rt, gpu, oracle):
 
 def test_update_in_three_bands(rt, gpu, oracle):
     lib = rt.load_library()
-    with _App(rt, 256, 13, 64, 528) as app:
+    with R.App(rt, 256, 13, 64, 528) as app:
         want = R.oracle_frame(oracle, app.inp, 64, 528)[1]
         states = []
         for k in range(5):

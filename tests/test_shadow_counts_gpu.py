@@ -11,38 +11,15 @@ import pytest
 
 import verdict_runs as R
 from scenes import Inputs, Scn
-from test_verdict_app_gpu import _App
 
 pytestmark = pytest.mark.gpu
 
-SIZES = {1024: (160, 90), 256: (96, 54)}     # the scene of tests/golden/c3_160x90_n1024.npz, and a smaller one
-
-
-def layouts(h):
-    return {"tile8": dict(), "tile16": dict(tile=16), "tile32": dict(tile=32), "tile64": dict(tile=64),
-            "band": dict(y0=16, y1=h - 18), "interleave": dict(interleave=(2, 1, 16))}
+SIZES, layouts, rows_of, tagged_of = R.SIZES, R.layouts, R.rows_of, R.tagged_of
 
 
 @pytest.fixture(scope="module")
 def refs(rt, gpu, oracle):
-    """Per scene: its inputs and the oracle's whole frame (computed once, never changed)."""
-    out = {}
-    for n, (w, h) in SIZES.items():
-        inp = Inputs(rt, n)
-        out[n] = (inp, R.oracle_frame(oracle, inp, w, h))
-    return out
-
-
-def rows_of(rt, h, kw):
-    if kw.get("interleave"):
-        cnt, idx, blk = kw["interleave"]
-        return np.asarray(rt.interleaved_rows(h, idx, cnt, blk), dtype=np.int64)
-    return np.arange(kw.get("y0", 0), kw.get("y1") or h)
-
-
-def tagged_of(tags):
-    """tags uint8 [ty, tx, 4] -> (mask of used records, group, light)."""
-    return (tags & 0x80) != 0, (tags >> 3) & 0xf, tags & 7
+    return R.oracle_refs(rt, oracle)
 
 
 @pytest.mark.parametrize("n", sorted(SIZES))
@@ -53,11 +30,7 @@ def test_frames_at_rest(rt, refs, n, layout):
     inp, whole = refs[n]
     rows = rows_of(rt, h, kw)
     want = (whole[0][rows], whole[1][rows])
-    ref = inp.scene()
-    ref.set_light_verdicts(0)
-    R.assert_same(R.frame(ref, w, h, **kw), want, "switch off")
-    assert ref.shadow_counts()["state"] == 0
-    R.assert_same(R.frame(ref, w, h, cull=False, **kw), want, "brute force")
+    R.switched_off(inp, w, h, want, read_back="shadow_counts", **kw)
     sc = inp.scene()
     R.resting(sc, dict(width=w, height=h, **kw), want, launches=5, what="%d %s" % (n, layout))
     info = sc.shadow_counts()
@@ -149,13 +122,6 @@ def test_capacity(rt, gpu):
     assert (cd[..., 3, :] != 0).any()                        # tiles with at least four groups exist (test_light_verdicts: some have more)
 
 
-def _copy_lights(rt, lights, n):
-    arr = (rt.Light * n)()
-    for i in range(n):
-        arr[i] = rt.Light(rt.Vec3(lights[i].pos.x, lights[i].pos.y, lights[i].pos.z), lights[i].size, lights[i].r, lights[i].g, lights[i].b)
-    return arr
-
-
 def test_invalidation(rt, gpu):
     inp = Inputs(rt, 1024)
     sc = inp.scene()
@@ -174,7 +140,7 @@ def test_invalidation(rt, gpu):
         assert sc.shadow_counts()["tagged"] >= 1, tag
 
     settle("start")
-    inp.lights = _copy_lights(rt, inp.lights, 3)
+    inp.lights = R.copy_lights(rt, inp.lights, 3)
     inp.lights[0].pos.x = 14.0
     sc.set_lights(inp.lights, 3)
     settle("a light moved")
@@ -206,6 +172,25 @@ def test_two_views_alternating(rt, gpu):
     assert states[-2:] == [2, 2], states                     # both views end reading
 
 
+def test_tagged_all_sums_the_tables_of_both_views(rt, refs):
+    """The read-back walks the scene's tables once: `tagged` is the last launch's table, `tagged_all` every table's. With
+    one view at rest the two agree; once a second view has settled beside it, `tagged_all` is the sum of what `tagged`
+    said right after each view's own launches."""
+    inp, want = refs[256]
+    w, h = SIZES[256]
+    sc = inp.scene()
+    R.resting(sc, dict(width=w, height=h), want, launches=3)
+    a = sc.shadow_counts()
+    assert a["state"] == 2 and a["tagged"] >= 1 and a["tagged_all"] == a["tagged"], a
+    cam = rt.Camera(rt.Vec3(4.5, 3, 10), rt.Vec3(0, 0, 1), 0.0, 171.0, -20.0)
+    ref = inp.scene()
+    ref.set_light_verdicts(0)
+    R.resting(sc, dict(width=w, height=h, cam=cam), R.frame(ref, w, h, cam=cam, cull=False), launches=3, what="second view")
+    b = sc.shadow_counts()
+    assert b["state"] == 2 and b["slot"] != a["slot"], (a, b)
+    assert b["tagged_all"] >= b["tagged"] and b["tagged_all"] == a["tagged"] + b["tagged"], (a, b)
+
+
 def test_two_streams_after_the_recording_launch(refs):
     import torch
     inp, want = refs[1024]
@@ -227,7 +212,7 @@ def test_two_streams_after_the_recording_launch(refs):
 
 def test_update_in_three_bands(rt, gpu, oracle):
     lib = rt.load_library()
-    with _App(rt, 256, 11, 64, 528) as app:
+    with R.App(rt, 256, 11, 64, 528) as app:
         want = R.oracle_frame(oracle, app.inp, 64, 528)[1]
         states = []
         for k in range(5):

@@ -15,15 +15,6 @@ from test_gpu_parity import _managed_sprite
 pytestmark = pytest.mark.gpu
 
 
-def _shim_state(rt):
-    lib = rt.load_library()
-    s = lib.rt_debug_shim_scene()
-    assert s, "the shim has no scene yet"
-    info = rt.LightVerdictsInfo()
-    assert lib.rt_debug_light_verdicts(s, C.byref(info), None, 0) == 0, lib.rt_last_error()
-    return info.state
-
-
 def test_raytrace_launch_at_rest(rt, gpu, oracle):
     """rt_launch_raytrace four times with identical arguments at 160 x 90: the oracle's words every time, the shim's scene
     going nothing, write, read, read; one sphere changed in place: nothing again, and the new frame."""
@@ -51,7 +42,7 @@ def test_raytrace_launch_at_rest(rt, gpu, oracle):
         assert lib.rt_launch_raytrace(pixels.data_ptr(), w, h, inp.aspect, obj, inp.lights, 3, inp.cam, sky, None) == 0, \
             lib.rt_last_error()
         torch.cuda.synchronize()
-        return pixels.cpu().numpy().view(np.uint32), _shim_state(rt)
+        return pixels.cpu().numpy().view(np.uint32), R.shim_state(rt)
 
     want = R.oracle_frame(oracle, inp, w, h)[1]
     states = []
@@ -68,37 +59,6 @@ def test_raytrace_launch_at_rest(rt, gpu, oracle):
     assert np.array_equal(got, want2) and not np.array_equal(want2, want)
 
 
-class _App:
-    """onStart() with `n` spheres of `seed`, the offscreen window at w x h, the camera at its default; all put back."""
-
-    def __init__(self, rt, n, seed, w, h):
-        self.rt, self.lib, self.n, self.seed, self.w, self.h = rt, rt.load_library(), n, seed, w, h
-
-    def __enter__(self):
-        lib = self.lib
-        assert lib.rt_config_set_sphere_count(self.n) == 0 and lib.rt_config_set_seed(self.seed) == 0
-        assert lib.rt_config_set_gpus(0) == 0
-        lib.rt_on_start()
-        self.cam = lib.rt_config_camera()
-        self.saved = self.rt.Camera.from_buffer_copy(self.cam.contents)
-        d = self.rt.default_camera()
-        for f in ("Org", "Dir", "Camyaw", "Campitch"):
-            setattr(self.cam.contents, f, getattr(d, f))
-        assert lib.rt_offscreen_resize(self.w, self.h) == 0
-        self.inp = Inputs(self.rt, self.n, seed=self.seed)
-        return self
-
-    def __exit__(self, *exc):
-        C.memmove(self.cam, C.byref(self.saved), C.sizeof(self.rt.Camera))
-        self.lib.rt_config_set_sphere_count(256)
-        self.lib.rt_config_set_seed(1)
-        return False
-
-    def update(self):
-        self.lib.rt_update()
-        return np.ctypeslib.as_array(self.lib.rt_offscreen_pixels(), shape=(self.h, self.w)).copy(), _shim_state(self.rt)
-
-
 def test_update_at_rest_in_three_bands(rt, gpu, oracle):
     """update() at 64 x 528: three row bands per frame (rows 0-176, 176-352, 352-528), each a key of its own that comes
     round once per frame. Five frames at rest: the oracle's frame every time; the bands record on the second frame and
@@ -108,7 +68,7 @@ def test_update_at_rest_in_three_bands(rt, gpu, oracle):
     the history of recent keys: the bands A, B, C, A, B, C ... never meet that condition; the frames were right and the
     states [0, 0, 0, 0, 0], so a resting application never used its tables at 512 rows and more. With the history:
     [0, 1, 2, 2, 2]."""
-    with _App(rt, 256, 7, 64, 528) as app:
+    with R.App(rt, 256, 7, 64, 528) as app:
         want = R.oracle_frame(oracle, app.inp, 64, 528)[1]
         states = []
         for k in range(5):
@@ -122,7 +82,7 @@ def test_update_at_rest_in_three_bands(rt, gpu, oracle):
 def test_update_with_a_moving_camera_records_nothing(rt, gpu, oracle):
     """Org.z nudged before every one of six frames at 64 x 528: no launch writes or reads a table, every frame is the
     oracle's. (A moving camera pays nothing for the history of recent keys.)"""
-    with _App(rt, 256, 8, 64, 528) as app:
+    with R.App(rt, 256, 8, 64, 528) as app:
         for k in range(6):
             z = 10.0 + 0.03125 * (k + 1)
             app.cam.contents.Org.z = z
