@@ -918,6 +918,77 @@ int rt_scene_display(rt_scene *s, const rt_display_desc *d, void *stream);
 int rt_scene_set_display_timing(rt_scene *s, int on);
 int rt_scene_display_times(rt_scene *s, float *ms, int cap, int *n);
 
+/* ------------------------------------------------------------------ *
+ * The bloom pass: the stage ahead of the display       *
+ * transform that makes a bright source look bright. The part of a     *
+ * float colour above a luminance threshold is filtered down a pyramid *
+ * of half-resolution levels, walked back up and added to the frame,   *
+ * on the linear colour, before exposure and curve.                    *
+ * ------------------------------------------------------------------ */
+#define RT_BLOOM_MAX_LEVELS 8
+#define RT_BLOOM_MAX_EVENTS 16         /* timed launches of a call at most: 2 levels */
+
+typedef struct rt_bloom_desc {
+    uint32_t struct_size;         /* sizeof(rt_bloom_desc); 0 reads as this layout. Fields past a caller's size read as 0    */
+    int width, height;            /* whole frames, each in [1, RT_DENOISE_MAX_SIZE]                                          */
+    const float *rgba_in;         /* device, float4, 16-byte aligned: the linear colour of high dynamic range                */
+    const float *state;           /* NULL, or device, float[4], 16-byte aligned: the display transform's state, read only    */
+    float *rgba_out;              /* NULL, or device, float4, 16-byte aligned: the colour with its glare, alpha copied bit
+                                     for bit; may be rgba_in itself                                                          */
+    uint32_t *pixels;             /* NULL, or device: rgbToInt(rgba_out * 254), today's pack                                 */
+    float *glow_out;              /* NULL, or device, float4, 16-byte aligned: (T, 0), the glare alone before `strength`     */
+    int levels;                   /* in [1, RT_BLOOM_MAX_LEVELS]: the pyramid's levels                                 [5]   */
+    float threshold;              /* finite, >= 0: the luminance on the screen's scale above which light blooms        [1]   */
+    float limit;                  /* finite, > 0: the ceiling of a bright channel on the screen's scale               [64]   */
+    float spread;                 /* finite, in [0, 4]: the weight of every coarser level on the way up             [0.75]   */
+    float strength;               /* finite, >= 0: the weight of the glare in the frame                            [0.125]   */
+    int variant;                  /* 0: the product (LDS-staged tiles); 1: the plain yardstick (a thread per output pixel,
+                                     16 and 4 taps from global memory). The same bits                                        */
+} rt_bloom_desc;
+
+/* The defaults in brackets above; sizes and pointers 0. They are choices of taste, not measurements: five levels reach
+ * 32 pixels either way, a threshold of 1 is the screen's white, and the glare of a source far above it stays an
+ * eighth of what it spreads. */
+void rt_bloom_desc_init(rt_bloom_desc *d);
+
+/* Blooms rgba_in on `stream` (a hipStream_t; NULL = the null stream). Binary32 + - *, one / and compares, in the order
+ * written: defined to the bit, both variants the same bits. w_0 x h_0 is the frame, w_k = (w_{k-1} + 1) >> 1 and h_k
+ * likewise for k = 1 .. L = levels (a level may be one pixel wide or high); clampx clamps a column index to the
+ * source's [0, ws - 1], clampy a row index to [0, hs - 1]; luma(r, g, b) = (0.2126 r + 0.7152 g) + 0.0722 b.
+ * 1. Scale: E = 1 if state is NULL or state[3] != 1, else state[0]; t = threshold / E, lim = limit / E. A frame that
+ *    rt_scene_display exposes at E blooms what will end above `threshold` on the screen's scale. The state is read on
+ *    the device: no call waits on the host.
+ * 2. Bright pass, (r, g, b, a) = rgba_in[p]: l = luma(r, g, b). If l is finite and l > t: s = (l - t) / l and per
+ *    channel v = c s, v = v > 0 ? v : 0 (a NaN gives 0), v = v > lim ? lim : v. Otherwise v = 0. Br(p) = (v, 0) is
+ *    never stored: the first downsample evaluates it at each tap.
+ * 3. Down, from a source S of ws x hs to (x, y) of the next level, per channel: x0 = clampx(2x - 1), x1 = 2x, x2 =
+ *    clampx(2x + 1), x3 = clampx(2x + 2), rows y0 .. y3 likewise; H(j) = ((S(x0, j) + S(x3, j)) + 3 (S(x1, j) +
+ *    S(x2, j))) 0.125 for j = y0 .. y3; D = ((H(y0) + H(y3)) + 3 (H(y1) + H(y2))) 0.125. B_1 = Down(Br), B_k =
+ *    Down(B_{k-1}).
+ * 4. Up, from a source S of wc x hc to (x, y) of the level below: cx = x >> 1, nx = clampx(cx + ((x & 1) ? 1 : -1)),
+ *    cy and ny likewise; G(j) = 0.75 S(cx, j) + 0.25 S(nx, j) for j = cy, ny; U = 0.75 G(cy) + 0.25 G(ny).
+ * 5. Chain: A_L = B_L; A_k = B_k + spread Up(A_{k+1}) for k = L - 1 .. 1; T = Up(A_1) at w_0 x h_0.
+ * 6. Combine, per channel: o = (T == 0) ? c : c + strength T. rgba_out[p] = (o, a), pixels[p] = rgbToInt(o * 254),
+ *    glow_out[p] = (T, 0).
+ * A pixel that nothing bright reaches keeps its own bits, -0 and NaN included; a frame with nothing above t comes back
+ * as itself, its pixels the frame's own packed words. The call enqueues 2 levels launches (the downsamples, the
+ * upsamples, the combine) and returns. The pyramid is the scene's, sum of w_k h_k float4, grown on demand (only then
+ * the host waits for the scene's earlier bloom calls) and never shrunk; calls of one scene on different streams are
+ * ordered on the device, one after the other (an event). Ordering the call after the work that wrote rgba_in and
+ * state, and a reader of the outputs after the call, is the caller's. Before anything is enqueued, and with nothing
+ * written: NULL or misaligned pointers (rgba_in, state, rgba_out and glow_out 16 bytes, pixels 4), sizes, levels or
+ * variant out of range, threshold not finite or < 0, limit not finite or <= 0, spread not finite or outside [0, 4],
+ * strength not finite or < 0, no output at all, an output that overlaps an input or another output (only rgba_out may
+ * be rgba_in itself: the combine reads rgba_in[p] alone, after the first downsample has finished) -> RT_ERR_INVALID; a
+ * stream that is being captured -> RT_ERR_UNSUPPORTED. */
+int rt_scene_bloom(rt_scene *s, const rt_bloom_desc *d, void *stream);
+
+/* Device time of every launch of the scene's later bloom calls (off by default). rt_scene_bloom_times waits for the
+ * last call and fills ms[0 .. *n - 1], *n = 2 levels <= RT_BLOOM_MAX_EVENTS: the downsamples from the frame on, the
+ * upsamples from the coarsest level on, the combine. cap: room in ms. */
+int rt_scene_set_bloom_timing(rt_scene *s, int on);
+int rt_scene_bloom_times(rt_scene *s, float *ms, int cap, int *n);
+
 /* Order in which a launch starts its tiles. 1 (default): in blocks of 16 x 16 tiles, the block with the longest
  * tile first -- the frame kernel records every tile's wave duration, and from the previous launch's durations the
  * blocks are sorted on the device (three small kernels, ~15 us): after 1, 2, 4, 8, 16, 32, 64, 96, ... launches of an

@@ -266,6 +266,19 @@ _DISPLAY_CURVES = {"clip": RT_DISPLAY_CLIP, "reinhard": RT_DISPLAY_REINHARD, "ac
 _DISPLAY_TRANSFERS = {"linear": RT_DISPLAY_LINEAR, "srgb": RT_DISPLAY_SRGB}
 
 
+class BloomDesc(C.Structure):
+    """rt_bloom_desc."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int), ("height", C.c_int),
+                ("rgba_in", C.c_void_p), ("state", C.c_void_p), ("rgba_out", C.c_void_p), ("pixels", C.c_void_p),
+                ("glow_out", C.c_void_p),
+                ("levels", C.c_int), ("threshold", C.c_float), ("limit", C.c_float), ("spread", C.c_float),
+                ("strength", C.c_float), ("variant", C.c_int)]
+
+
+RT_BLOOM_MAX_LEVELS = 8
+RT_BLOOM_MAX_EVENTS = 16
+
+
 class IndirectPathsOpts(C.Structure):
     """rt_indirect_paths_opts."""
     _fields_ = [("struct_size", C.c_uint32), ("bounces", C.c_int)]
@@ -513,6 +526,10 @@ def load_library():
         "rt_scene_display": (ci, [vp, C.POINTER(DisplayDesc), vp]),
         "rt_scene_set_display_timing": (ci, [vp, ci]),
         "rt_scene_display_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
+        "rt_bloom_desc_init": (None, [C.POINTER(BloomDesc)]),
+        "rt_scene_bloom": (ci, [vp, C.POINTER(BloomDesc), vp]),
+        "rt_scene_set_bloom_timing": (ci, [vp, ci]),
+        "rt_scene_bloom_times": (ci, [vp, fp, ci, C.POINTER(ci)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
@@ -1594,6 +1611,67 @@ class Scene:
         """Device ms of every launch of the last timed denoise call (waits for it): variants 0 and 2: the pack pass, then
         the iterations; variant 1: the iterations."""
         return self._pass_times("denoise", RT_DENOISE_MAX_ITERATIONS + 1)
+
+    # ---------------------------------------------------------------- the bloom pass (DESIGN.md 6s)
+    def bloom_desc(self, width, height, *, rgba_in=0, state=0, rgba_out=0, pixels=0, glow_out=0, levels=None,
+                   threshold=None, limit=None, spread=None, strength=None, variant=0) -> BloomDesc:
+        """rt_bloom_desc with rt_bloom_desc_init's defaults where an argument is None."""
+        return self._desc(BloomDesc, "rt_bloom_desc_init",
+                          dict(width=width, height=height, rgba_in=rgba_in, state=state, rgba_out=rgba_out, pixels=pixels,
+                               glow_out=glow_out),
+                          dict(levels=levels, threshold=threshold, limit=limit, spread=spread, strength=strength,
+                               variant=variant))
+
+    def bloom_raw(self, d: BloomDesc, stream=0) -> int:
+        """rt_scene_bloom as is: returns the status."""
+        return self.lib.rt_scene_bloom(self.handle, C.byref(d), stream)
+
+    def bloom(self, frame, state=None, *, levels=None, threshold=None, limit=None, spread=None, strength=None,
+              want_rgba=True, want_packed=True, want_glow=False, variant=0, stream=None):
+        """Spread the light above a luminance threshold over its neighbourhood, on the linear colour ahead of `display`
+        (rt_scene_bloom; None: the default of rt_bloom_desc_init). `frame`: a frame dict (its "rgba") or a bare CUDA
+        float32 [H, W, 4] tensor. `state`: None, or the "state" a display call returned: threshold and limit are then
+        on the scale that call exposes at; it is read on the device and not written. Returns {'rgba': float32 [H, W, 4]
+        or None, 'pixels': int32 [H, W] or None, 'glow': float32 [H, W, 4] or None (the glare alone, before
+        `strength`)} as new tensors; the frame is not written. Enqueued on `stream` (default: the current stream); no
+        host wait."""
+        for name, value in (("levels", levels), ("variant", variant)):
+            if value is not None and (isinstance(value, bool) or not isinstance(value, int)):
+                raise RtError(f"bloom: {name} must be an int, not {value!r}")
+        for name, value in (("threshold", threshold), ("limit", limit), ("spread", spread), ("strength", strength)):
+            if value is not None and (isinstance(value, bool) or not isinstance(value, (int, float))):
+                raise RtError(f"bloom: {name} must be a number, not {value!r}")
+        if not (want_rgba or want_packed or want_glow):
+            raise RtError("bloom: want_rgba, want_packed and want_glow are all false: nothing to do")
+        torch = self._need_gpu("the bloom pass")
+        rgba = frame.get("rgba") if isinstance(frame, dict) else frame
+        if (not isinstance(rgba, torch.Tensor) or rgba.dim() != 3 or rgba.shape[2] != 4 or rgba.dtype != torch.float32
+                or not rgba.is_cuda):
+            raise RtError("bloom: the colour must be a CUDA float32 tensor of shape [H, W, 4] (or a frame with such an rgba)")
+        rgba = rgba.contiguous()
+        H, W = rgba.shape[0], rgba.shape[1]
+        if state is not None and (not isinstance(state, torch.Tensor) or tuple(state.shape) != (4,)
+                                  or state.dtype != torch.float32 or state.device != rgba.device
+                                  or not state.is_contiguous()):
+            raise RtError("bloom: state must be a contiguous float32 tensor of shape [4] beside the colour")
+        st = self._stream(torch, stream)
+        out = self._new(torch, want_rgba, rgba, (H, W, 4), torch.float32)
+        packed = self._new(torch, want_packed, rgba, (H, W), torch.int32)
+        glow = self._new(torch, want_glow, rgba, (H, W, 4), torch.float32)
+        d = self.bloom_desc(W, H, rgba_in=rgba.data_ptr(), state=self._ptr(state), rgba_out=self._ptr(out),
+                            pixels=self._ptr(packed), glow_out=self._ptr(glow), levels=levels, threshold=threshold,
+                            limit=limit, spread=spread, strength=strength, variant=variant)
+        _check(self.bloom_raw(d, st.cuda_stream), "rt_scene_bloom")
+        rgba.record_stream(st)            # a contiguous copy stays allocated until the stream has run the pass
+        return {"rgba": out, "pixels": packed, "glow": glow}
+
+    def set_bloom_timing(self, on: bool):
+        self._set_pass_timing("bloom", on)
+
+    def bloom_times(self):
+        """Device ms of every launch of the last timed bloom call (waits for it), 2 * levels of them: the downsamples
+        from the frame on, the upsamples from the coarsest level on, the combine."""
+        return self._pass_times("bloom", RT_BLOOM_MAX_EVENTS)
 
     # ---------------------------------------------------------------- one-bounce global illumination (DESIGN.md 6o)
     def indirect_desc(self, width, height, *, cam=None, aspect=None, depth=0, normal=0, id=0, albedo=0, rgba_in=0,

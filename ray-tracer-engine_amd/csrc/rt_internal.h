@@ -264,6 +264,12 @@ int rt_upsample_launch(const rt_upsample_desc *d, hipEvent_t *ev, hipStream_t st
 int rt_display_launch(const rt_display_desc *d, uint32_t *hist, const float *table, hipEvent_t *ev, int *n_ev, hipStream_t stream);
 const float *rt_display_table();   // the 256 thresholds of the sRGB encoding (host)
 
+// rt_bloom.hip: the bloom pass (d: validated, in this build's layout; pyramid: the scene's, room for
+// rt_bloom_pyramid_texels(width, height, levels) float4; ev: null, or RT_BLOOM_MAX_EVENTS + 1 timing events, of which
+// *n_ev are recorded: one ahead of the first launch, one behind each)
+size_t rt_bloom_pyramid_texels(int width, int height, int levels);
+int rt_bloom_launch(const rt_bloom_desc *d, float4 *pyramid, hipEvent_t *ev, int *n_ev, hipStream_t stream);
+
 // rt_indirect.hip: the indirect pass. The product's scratch, all the scene's: per slot of a group of
 // at most RT_INDIRECT_GROUP rays a colour (slab) and a queue entry, a running sum per pixel when there are several
 // groups, and a counter per (group, bounce). Queue 0's entries are RT_INDIRECT_ENTRY_F4 float4; those of the later

@@ -1161,6 +1161,94 @@ extern "C" int rt_scene_display_times(rt_scene *s, float *ms, int cap, int *n)
 }
 
 // ---------------------------------------------------------------------------
+// the bloom pass (rt_bloom.hip)
+// ---------------------------------------------------------------------------
+extern "C" void rt_bloom_desc_init(rt_bloom_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (uint32_t)sizeof *d;
+    d->levels = 5;
+    d->threshold = 1.f;
+    d->limit = 64.f;
+    d->spread = 0.75f;
+    d->strength = 0.125f;
+}
+
+extern "C" int rt_scene_bloom(rt_scene *s, const rt_bloom_desc *d_in, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!s || !d_in) {
+        rt_set_error("rt_scene_bloom: null scene or description");
+        return RT_ERR_INVALID;
+    }
+    rt_bloom_desc d;
+    as_built(d_in, &d);
+    const char *bad = nullptr;
+    if (d.width <= 0 || d.height <= 0 || d.width > RT_DENOISE_MAX_SIZE || d.height > RT_DENOISE_MAX_SIZE)
+        bad = "width and height must be in [1, RT_DENOISE_MAX_SIZE]";
+    else if (d.levels < 1 || d.levels > RT_BLOOM_MAX_LEVELS) bad = "levels is not in [1, RT_BLOOM_MAX_LEVELS]";
+    else if (d.variant < 0 || d.variant > 1) bad = "variant is not 0 or 1";
+    else if (!d.rgba_in) bad = "rgba_in must not be NULL";
+    else if (!d.rgba_out && !d.pixels && !d.glow_out) bad = "rgba_out, pixels and glow_out are all NULL: nothing to do";
+    else if ((uintptr_t)d.rgba_in & 15u) bad = "rgba_in must be 16-byte aligned";
+    else if ((uintptr_t)d.state & 15u) bad = "state must be 16-byte aligned";
+    else if ((uintptr_t)d.rgba_out & 15u) bad = "rgba_out must be 16-byte aligned";
+    else if ((uintptr_t)d.pixels & 3u) bad = "pixels must be 4-byte aligned";
+    else if ((uintptr_t)d.glow_out & 15u) bad = "glow_out must be 16-byte aligned";
+    else if (!(d.threshold >= 0.f) || !std::isfinite(d.threshold)) bad = "threshold is not finite and >= 0";
+    else if (!(d.limit > 0.f) || !std::isfinite(d.limit)) bad = "limit is not finite and > 0";
+    else if (!(d.spread >= 0.f && d.spread <= 4.f)) bad = "spread is not in [0, 4]";
+    else if (!(d.strength >= 0.f) || !std::isfinite(d.strength)) bad = "strength is not finite and >= 0";
+    else {
+        const size_t npx = (size_t)d.width * d.height;
+        const Range outs[3] = {{(uintptr_t)d.rgba_out, npx * 16}, {(uintptr_t)d.pixels, npx * 4}, {(uintptr_t)d.glow_out, npx * 16}};
+        const Range ins[2] = {{(uintptr_t)d.rgba_in, npx * 16}, {(uintptr_t)d.state, 16}};
+        bad = overlap_message(outs, ins, 0, "an output buffer (rgba_out, pixels, glow_out) overlaps rgba_in or state (only rgba_out may be rgba_in itself)");
+        if (bad && !strncmp(bad, "two", 3)) bad = "two of rgba_out, pixels and glow_out overlap";
+    }
+    if (bad) {
+        rt_set_error("rt_scene_bloom: %s (%d x %d, levels %d, variant %d)", bad, d.width, d.height, d.levels, d.variant);
+        return RT_ERR_INVALID;
+    }
+    if (stream_capturing(stream)) {
+        rt_set_error("rt_scene_bloom: the stream is being captured (the pass is not recorded into graphs)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    const size_t need = rt_bloom_pyramid_texels(d.width, d.height, d.levels);
+    if (need > s->bl_pyramid.capacity()) {
+        // growing releases the old pyramid: after the host has seen the last call that used it end
+        RT_HIP(s->bl_done.host_wait());
+        RT_HIP(s->bl_pyramid.reserve(need));
+    }
+    RT_HIP(s->bl_done.order(stream));   // one pyramid: one call at a time
+    hipEvent_t ev[RT_BLOOM_MAX_EVENTS + 1];
+    s->bl_timed = 0;
+    if (s->bl_timing) {
+        for (int i = 0; i < RT_BLOOM_MAX_EVENTS + 1; ++i) {
+            RT_HIP(s->bl_ev[i].create(hipEventDefault));
+            ev[i] = s->bl_ev[i].get();
+        }
+    }
+    int n_ev = 0;
+    const int rc = rt_bloom_launch(&d, s->bl_pyramid.get(), s->bl_timing ? ev : nullptr, &n_ev, stream);
+    // also after a launch that failed half way: what was enqueued uses the pyramid
+    RT_HIP(s->bl_done.record(stream));
+    if (rc == RT_OK && s->bl_timing) s->bl_timed = n_ev;
+    return rc;
+}
+
+extern "C" int rt_scene_set_bloom_timing(rt_scene *s, int on)
+{
+    return pass_set_timing(s, "rt_scene_set_bloom_timing", &rt_scene::bl_timing, on);
+}
+
+extern "C" int rt_scene_bloom_times(rt_scene *s, float *ms, int cap, int *n)
+{
+    return pass_times(s, "rt_scene_bloom_times", &rt_scene::bl_done, s ? s->bl_ev : nullptr, s ? s->bl_timed : 0, ms, cap, n);
+}
+
+// ---------------------------------------------------------------------------
 // global illumination with a bounce budget (rt_indirect.hip)
 // ---------------------------------------------------------------------------
 extern "C" void rt_indirect_desc_init(rt_indirect_desc *d)

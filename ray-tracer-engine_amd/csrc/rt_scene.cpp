@@ -35,6 +35,7 @@ int rt_scene_quiesce(rt_scene *s)
     RT_HIP(s->up_done.host_wait());                                                    // an upsample call in flight
     RT_HIP(s->ind_done.host_wait());                                                   // an indirect call still using its scratch
     RT_HIP(s->dp_done.host_wait());                                                    // a display call still using its histogram
+    RT_HIP(s->bl_done.host_wait());                                                    // a bloom call still using its pyramid
     return RT_OK;
 }
 

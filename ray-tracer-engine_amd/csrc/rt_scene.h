@@ -20,11 +20,11 @@
 //   (c) a reader waits on the build event on the device only; the host never waits for a build, except in
 //       rt_scene_view_lists_info;
 //   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's, the temporal pass's, the upsampler's,
-//       the indirect pass's and the display transform's events;
+//       the indirect pass's, the display transform's and the bloom pass's events;
 //   (e) the tile order keeps one event for all layouts; a new layout or a re-sort first makes the launching stream
 //       wait for every ring event;
 //   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
-//       scratch;
+//       scratch; the bloom pass does both for its pyramid;
 //   (g) whatever rewrites or re-allocates a buffer a recorded graph may point into bumps `epoch`, and nothing else
 //       does: of the hand-over functions only an rt_scene_begin_build whose buffer re-allocates;
 //   (h) a resting-view table is written by a frame launch on the frame's own stream, not by a build on the table
@@ -233,6 +233,13 @@ struct rt_scene {
     HipEvent dp_ev[RT_DISPLAY_MAX_EVENTS];           // rt_scene_set_display_timing
     bool dp_timing = false;
     int dp_timed = 0;
+    // the bloom pass (rt_bloom.hip): the pyramid's levels one behind the other, grown on demand and never shrunk;
+    // `bl_done` orders the scene's bloom calls
+    DevArray<float4> bl_pyramid;
+    HipPendingEvent bl_done;
+    HipEvent bl_ev[RT_BLOOM_MAX_EVENTS + 1];         // rt_scene_set_bloom_timing
+    bool bl_timing = false;
+    int bl_timed = 0;
     // the indirect pass (rt_indirect.hip): ray tables of its own, as the temporal pass has, and the product's scratch,
     // grown on demand; `ind_done` orders the scene's indirect calls
     DevArray<float> ind_raygen;                      // dx[width], dy[height] at one sample
