@@ -1083,6 +1083,23 @@ int rt_debug_primary_records(rt_scene *s, rt_primary_records_info *out, unsigned
 /* Tests: overwrites the records of the table that the last launch wrote or read; n = 64 * tiles_x * tiles_y. Waits for
  * every launch in flight.                                                                                            */
 int rt_debug_set_primary_records(rt_scene *s, const unsigned *dwords, size_t n);
+/* Tile summaries: the fourth part of the same table, a dword per tile of the writing launch's grid. Bit 0, settled: the
+ * tile has a primary record, at most 4 groups under at most 8 lights, and every (group, light) entry of its word is 1 --
+ * no light adds to any of its pixels (a tile without a hit pixel: trivially). Reading launches store 0 for its hit pixels
+ * and the sky texel of the record for the others, and evaluate nothing else of it. Bit 1: no valid pixel of the tile is a
+ * miss. Bits 8-15: the tile's group count, saturating at 255. Same switch, same key, same launches.                  */
+typedef struct rt_tile_summaries_info {
+    int state, slot;           /* as in rt_light_verdicts_info */
+    int tiles_x, tiles_y;
+    long long settled;         /* tiles with bit 0 */
+    long long settled_no_miss; /* of those, tiles with bit 1 as well */
+} rt_tile_summaries_info;
+/* Tests and profiles; waits for the launch that wrote the table. dwords (optional, `cap` = tiles): the raw summaries,
+ * row by row.                                                                                                        */
+int rt_debug_tile_summaries(rt_scene *s, rt_tile_summaries_info *out, unsigned *dwords, size_t cap);
+/* Tests: overwrites the summaries of the table that the last launch wrote or read; n = tiles_x * tiles_y. Waits for
+ * every launch in flight.                                                                                            */
+int rt_debug_set_tile_summaries(rt_scene *s, const unsigned *dwords, size_t n);
 /* Tests: the long-lived scene rt_launch_raytrace(_ex) and update() render through, for rt_debug_light_verdicts and
  * rt_scene_view_lists_info; owned by the library, NULL before the first launch.                                     */
 rt_scene *rt_debug_shim_scene(void);

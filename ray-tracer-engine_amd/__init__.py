@@ -311,7 +311,14 @@ class PrimaryRecordsInfo(C.Structure):
                 ("tiles_recorded", C.c_longlong), ("hit_pixels", C.c_longlong), ("miss_pixels", C.c_longlong)]
 
 
+class TileSummariesInfo(C.Structure):
+    """rt_tile_summaries_info."""
+    _fields_ = [("state", C.c_int), ("slot", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int),
+                ("settled", C.c_longlong), ("settled_no_miss", C.c_longlong)]
+
+
 RT_PRIMARY_MISS, RT_PRIMARY_NONE = 0xff, 0xfe
+RT_TILE_SETTLED, RT_TILE_NO_MISS, RT_TILE_GROUPS_SHIFT = 1, 2, 8
 
 
 def decode_primary_records(dwords):
@@ -421,6 +428,8 @@ def load_library():
         "rt_debug_set_shadow_counts": (ci, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t]),
         "rt_debug_primary_records": (ci, [vp, C.POINTER(PrimaryRecordsInfo), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_size_t]),
         "rt_debug_set_primary_records": (ci, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
+        "rt_debug_tile_summaries": (ci, [vp, C.POINTER(TileSummariesInfo), C.POINTER(C.c_uint32), C.c_size_t]),
+        "rt_debug_set_tile_summaries": (ci, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
         "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
         "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
         "rt_debug_tile_order": (ci, [C.POINTER(C.c_uint), ci, ci, ci, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
@@ -999,6 +1008,22 @@ class Scene:
         dwords = np.ascontiguousarray(dwords, dtype=np.uint32)
         _check(self.lib.rt_debug_set_primary_records(self.handle, dwords.ctypes.data_as(C.POINTER(C.c_uint32)), dwords.size),
                "rt_debug_set_primary_records")
+
+    def tile_summaries(self, want_tables: bool = False) -> dict:
+        """The tile summaries behind the last launch's light verdicts (waits for the table's writer): state, slot, tiles_x,
+        tiles_y, settled, settled_no_miss; with want_tables also 'dwords', uint32 [tiles_y, tiles_x]: RT_TILE_SETTLED,
+        RT_TILE_NO_MISS and the tile's group count (saturating) at RT_TILE_GROUPS_SHIFT."""
+        def make(i):
+            dwords = np.zeros(i.tiles_x * i.tiles_y, dtype=np.uint32)
+            return (dwords.ctypes.data_as(C.POINTER(C.c_uint32)), dwords.size), lambda: {"dwords": dwords.reshape(i.tiles_y, i.tiles_x)}
+        return self._read_back("rt_debug_tile_summaries", TileSummariesInfo, lambda i: want_tables and i.state, make)
+
+    def set_tile_summaries(self, dwords):
+        """Tests: overwrites the tile summaries (uint32 [tiles_y, tiles_x]) of the table that the last launch wrote or
+        read."""
+        dwords = np.ascontiguousarray(dwords, dtype=np.uint32)
+        _check(self.lib.rt_debug_set_tile_summaries(self.handle, dwords.ctypes.data_as(C.POINTER(C.c_uint32)), dwords.size),
+               "rt_debug_set_tile_summaries")
 
     def view_lists_info(self, want_lists: bool = False) -> dict:
         """What the last launch read (waits for the lists' build): read, block size, blocks, overflowed and not-built

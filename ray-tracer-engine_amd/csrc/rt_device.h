@@ -266,14 +266,14 @@ struct RtFrameConsts {
     int *aov_id;                // int2 per pixel
     float *aov_albedo;          // float4 per pixel
 
-    // The resting-view table (layout: the RT_REST_* block below; DESIGN.md 4, steps 5 / 5b / 5c). rest_wr: this launch
+    // The resting-view table (layout: the RT_REST_* block below; DESIGN.md 4, steps 5 / 5b / 5c / 5d). rest_wr: this launch
     // records into it; rest_rd: it reads what an earlier launch of bit-identical inputs recorded (the host keeps the
     // key). Either may be null; only the one-sample sphere-only product kernel (MODE 0, FEAT 0, CULL) looks at them.
     const unsigned char *rest_rd;
     unsigned char *rest_wr;
 };
 // The resting-view table: what a recording launch (MODE 7) leaves for the reading launches (MODE 6) of the same key, one
-// allocation of four sections, each an array over the T tiles of the launch's grid by the tile's frame coordinates
+// allocation of five sections, each an array over the T tiles of the launch's grid by the tile's frame coordinates
 // (tile_y * tiles_x + tile_x, after tile_perm). This block is the layout; nothing else states it.
 //   words    a 64-bit word per tile: two bits per (group, light) for the tile's first RT_VERDICT_GROUPS groups, in the
 //            order the kernel forms them, and the first RT_VERDICT_LIGHTS lights, at 16 * group + 2 * light: 0 = evaluate,
@@ -286,6 +286,14 @@ struct RtFrameConsts {
 //            texture has more than RT_PRIMARY_TEXELS texels); bits 8-31: the clamped texel index, of the object texture for
 //            a hit, of the sky for a miss. The recording launch stores every lane of every tile it renders; a reader that
 //            finds RT_PRIMARY_NONE in a valid lane takes the walk and the texel arithmetic for the whole tile.
+//   summary  a dword per tile, stored by the recording launch for every tile it renders. RT_TILE_SETTLED (bit 0): the tile
+//            has a primary record, at most RT_VERDICT_GROUPS groups under at most RT_VERDICT_LIGHTS lights, and every one
+//            of its (group, light) iterations left by an "adds nothing" exit (a tile without a hit lane: trivially) -- no
+//            light reaches a pixel of it, a reader stores 0 for its hit lanes and the sky texel on record for the others,
+//            and reads neither rays, lists, words, tags nor counts. RT_TILE_NO_MISS (bit 1): no valid lane is a miss -- a
+//            settled reader then does not load the primary records either. Bits 8-15: the tile's group count, saturating
+//            at 255 (for the read-back; no kernel reads it). A settled tile whose record says RT_PRIMARY_NONE in a valid
+//            lane (the setters only) takes the full path.
 #define RT_VERDICT_GROUPS 4
 #define RT_VERDICT_LIGHTS 8
 #define RT_VERDICT_NOTHING 1u
@@ -296,6 +304,9 @@ struct RtFrameConsts {
 #define RT_PRIMARY_MISS 0xffu
 #define RT_PRIMARY_NONE 0xfeu
 #define RT_PRIMARY_TEXELS (1 << 24)
+#define RT_TILE_SETTLED 1u
+#define RT_TILE_NO_MISS 2u
+#define RT_TILE_GROUPS_SHIFT 8
 
 // bytes per tile of each section, in the order they lie; a section's offset is the sum of those before it
 #define RT_REST_WORD_BYTES 8u
@@ -303,18 +314,22 @@ struct RtFrameConsts {
 #define RT_REST_RECORD_BYTES 64u      // one shadow-count record: a byte per lane
 #define RT_REST_COUNT_BYTES (RT_REST_RECORD_BYTES * RT_SHADOW_RECORDS)
 #define RT_REST_PRIMARY_BYTES 256u
+#define RT_REST_SUMMARY_BYTES 4u
 #define RT_REST_TAGS_OFFSET(T) ((size_t)(T) * RT_REST_WORD_BYTES)
 #define RT_REST_COUNTS_OFFSET(T) (RT_REST_TAGS_OFFSET(T) + (size_t)(T) * RT_REST_TAG_BYTES)
 #define RT_REST_PRIMARY_OFFSET(T) (RT_REST_COUNTS_OFFSET(T) + (size_t)(T) * RT_REST_COUNT_BYTES)
-#define RT_REST_TABLE_BYTES(T) (RT_REST_PRIMARY_OFFSET(T) + (size_t)(T) * RT_REST_PRIMARY_BYTES)
+#define RT_REST_SUMMARY_OFFSET(T) (RT_REST_PRIMARY_OFFSET(T) + (size_t)(T) * RT_REST_PRIMARY_BYTES)
+#define RT_REST_TABLE_BYTES(T) (RT_REST_SUMMARY_OFFSET(T) + (size_t)(T) * RT_REST_SUMMARY_BYTES)
 #define RT_REST_FILL_BYTES(T) RT_REST_COUNTS_OFFSET(T)   // filled with ones before a recording launch: the words and the tags
 // a tile's word (halves at + 0 and + 1) and its tags, in dwords from the table's first
 #define RT_REST_WORD_DWORD(tile) ((RT_REST_WORD_BYTES / 4u) * (size_t)(tile))
 #define RT_REST_TAG_DWORD(T, tile) (RT_REST_TAGS_OFFSET(T) / 4u + (tile))
+#define RT_REST_SUMMARY_DWORD(T, tile) (RT_REST_SUMMARY_OFFSET(T) / 4u + (tile))
 static_assert(RT_REST_TAGS_OFFSET(7) == 8u * 7, "resting-view table: the tags lie behind the words");
 static_assert(RT_REST_COUNTS_OFFSET(7) == 12u * 7 && RT_REST_FILL_BYTES(7) == RT_REST_COUNTS_OFFSET(7), "resting-view table: the fill ends where the counts begin");
 static_assert(RT_REST_PRIMARY_OFFSET(7) == (12u + 64u * RT_SHADOW_RECORDS) * 7, "resting-view table: the primary records lie behind the counts");
-static_assert(RT_REST_TABLE_BYTES(7) == RT_REST_PRIMARY_OFFSET(7) + 256u * 7, "resting-view table: a dword per lane ends it");
+static_assert(RT_REST_SUMMARY_OFFSET(7) == RT_REST_PRIMARY_OFFSET(7) + 256u * 7, "resting-view table: the tile summaries lie behind a dword per lane");
+static_assert(RT_REST_TABLE_BYTES(7) == RT_REST_SUMMARY_OFFSET(7) + 4u * 7, "resting-view table: a dword per tile ends it");
 
 // T and its factors: one 64-pixel tile of tile_w x 64 / tile_w per workgroup, over the launch's `width` x `local_rows`
 __host__ __device__ inline unsigned rt_rest_tiles_x(int width, int tile_w) { return (unsigned)(width + tile_w - 1) / (unsigned)tile_w; }

@@ -230,7 +230,7 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
                             16 * sizeof(double) +            // atan(k/8)
                             192 * sizeof(float) +            // texel colours per pixel
                             (feat == 2 ? (RT_BOX_CAP + 128) * sizeof(int)   // leaf boxes, marked blocks, staged vertices
-                                       : 4 * sizeof(unsigned)));            // the tile's light verdicts, record tags and index (same place)
+                                       : 8 * sizeof(unsigned)));            // the tile's light verdicts, record tags, index and summary (same place)
     *grid = dim3(rt_rest_tiles_x(fc->width, tile_w), rt_rest_tiles_y(fc->local_rows, tile_w));
     *block = dim3(64);
     *func = (const void *)fn;

@@ -1,4 +1,4 @@
-// rt_scene_rest.cpp -- the resting-view tables (RtFrameConsts::rest_rd / rest_wr, DESIGN.md 4 steps 5 / 5b / 5c; the
+// rt_scene_rest.cpp -- the resting-view tables (RtFrameConsts::rest_rd / rest_wr, DESIGN.md 4 steps 5 / 5b / 5c / 5d; the
 // layout is the RT_REST_* block of rt_device.h): the key a table is kept under, which launch records, reads or does
 // neither, and the rt_debug_* read-backs and setters of a table's sections. The hand-over is note (h) of rt_scene.h.
 #include "rt_scene.h"
@@ -80,7 +80,7 @@ int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *
         // and an all-ones tag of a tile it did not render names group 15, which no iteration has -- RT_SHADOW_TAG_UNWRITTEN
         // to the read-back. The records themselves are read only where a tag points and stay as they are. The primary
         // records behind them need no fill either: the launch stores every lane of every tile it renders, and a reader
-        // of the same key renders exactly those tiles.
+        // of the same key renders exactly those tiles. The same holds for the tile summaries behind those.
         RT_HIP(hipMemsetAsync(c.buf.get(), 0xff, RT_REST_FILL_BYTES(tiles), stream));
         c.key = key;
         c.tiles_x = tiles_x;
@@ -308,5 +308,39 @@ extern "C" int rt_debug_set_primary_records(rt_scene *s, const unsigned *dwords,
     const int rc = last_table_to_set(s, dwords != nullptr, "rt_debug_set_primary_records", n, 64, "records", " tiles of 64", &c);
     if (rc != RT_OK) return rc;
     RT_HIP(copy_section(*c, RT_REST_PRIMARY_OFFSET(tiles_of(*c)), sizeof(unsigned) * n, const_cast<unsigned *>(dwords), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// The tile summaries of the last launch's table (waits for the launch that wrote it).
+extern "C" int rt_debug_tile_summaries(rt_scene *s, rt_tile_summaries_info *out, unsigned *dwords, size_t cap)
+{
+    RestSlot *c;
+    const int rc = last_table(s, out, "rt_debug_tile_summaries", &c);
+    if (rc != RT_OK || !c) return rc;
+    const size_t n = tiles_of(*c);
+    std::vector<unsigned> h(n);
+    RT_HIP(copy_section(*c, RT_REST_SUMMARY_OFFSET(n), RT_REST_SUMMARY_BYTES * n, h.data(), hipMemcpyDeviceToHost));
+    for (unsigned d : h) {
+        if (!(d & RT_TILE_SETTLED)) continue;
+        out->settled++;
+        if (d & RT_TILE_NO_MISS) out->settled_no_miss++;
+    }
+    if (dwords) {
+        if (cap < n) {
+            rt_set_error("rt_debug_tile_summaries: room for %zu tiles, the table has %zu", cap, n);
+            return RT_ERR_INVALID;
+        }
+        memcpy(dwords, h.data(), sizeof(unsigned) * n);
+    }
+    return RT_OK;
+}
+
+// Tests: overwrite the tile summaries of the table the last launch wrote or read.
+extern "C" int rt_debug_set_tile_summaries(rt_scene *s, const unsigned *dwords, size_t n)
+{
+    RestSlot *c;
+    const int rc = last_table_to_set(s, dwords != nullptr, "rt_debug_set_tile_summaries", n, 1, "tiles", "", &c);
+    if (rc != RT_OK) return rc;
+    RT_HIP(copy_section(*c, RT_REST_SUMMARY_OFFSET(n), RT_REST_SUMMARY_BYTES * n, const_cast<unsigned *>(dwords), hipMemcpyHostToDevice));
     return RT_OK;
 }

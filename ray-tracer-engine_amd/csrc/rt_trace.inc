@@ -1300,11 +1300,30 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
     float *mytex = reinterpret_cast<float *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32)) + wave * 192;
     int *myboxes = reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192) + wave * (RT_BOX_CAP + 128);   // + marked leaf blocks + 64 staged floats
     float *mytri = reinterpret_cast<float *>(myboxes + RT_BOX_CAP + 64);   // staged vertices of a leaf (MESH launches only)
-    if (lane < 16) {
-        mybtab[lane] = kBrightnessSteps[lane];   // same values as brightness_steps()
-        myatan[lane] = kAtanEighth[lane];
+    // Tile summaries (step 5d, MODE 6): the tile's dword of the resting-view table is asked for first of all -- one scalar
+    // load by the tile's frame coordinates, formed here as below. A settled tile (RT_TILE_SETTLED) stages no table,
+    // loads no word, tag, list or ray table and, where no valid lane is a miss (RT_TILE_NO_MISS), no primary record:
+    // the head of the sample loop sends it to the write-back. The others go on from here as they always did, with the
+    // summary's latency in front of their loads: the flag is known before anything else is asked for.
+    unsigned ts = 0;
+    if (MODE == 6) {
+        unsigned h_x = blockIdx.x, h_y = blockIdx.y;
+        const unsigned h_tiles_x = (unsigned)(fc.width + TW - 1) / (unsigned)TW;
+        if (fc.tile_perm) {
+            const unsigned p = fc.tile_perm[blockIdx.y * h_tiles_x + blockIdx.x];
+            h_x = p & 0xffffu;
+            h_y = p >> 16;
+        }
+        ts = reinterpret_cast<const unsigned *>(fc.rest_rd)[RT_REST_SUMMARY_DWORD(h_tiles_x * rt_rest_tiles_y(fc.local_rows, TW), h_y * h_tiles_x + h_x)];
     }
-    wave_lds_sync();
+    bool settled = MODE == 6 && (ts & RT_TILE_SETTLED) != 0;   // wave-uniform
+    if (MODE != 6 || !settled) {
+        if (lane < 16) {
+            mybtab[lane] = kBrightnessSteps[lane];   // same values as brightness_steps()
+            myatan[lane] = kAtanEighth[lane];
+        }
+        wave_lds_sync();
+    }
 
     // which tile: the workgroup's own, or the one the frame's tile order puts at this place
     unsigned blk_x = blockIdx.x, blk_y = blockIdx.y;
@@ -1331,19 +1350,28 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 #else
     constexpr bool LAZY_BALL = VD_USE;
 #endif
+    // (RT_EAGER_REST_LOADS: the other order of a reading launch's head -- word, tags and primary records asked for before
+    // the summary is known and dropped by a settled tile -- which the order below was measured against,
+    // profiles/settled_tiles_ab.json.)
+#ifdef RT_EAGER_REST_LOADS
+    constexpr bool REST_EAGER = true;
+#else
+    constexpr bool REST_EAGER = false;
+#endif
     // Shadow counts (step 5b) go the same way: the tile's tag dword is asked for by lane 2 and parked behind the word,
     // and behind that the tile's index, which the light loop needs for a record's address and must not hold in a register.
-    unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192)) + wave * 4;
+    unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192)) + wave * 8;   // word, tags, tile index, summary (MODE 7)
     unsigned vd_ld = 0;
     unsigned pr_rec = RT_PRIMARY_NONE;
     if (VERD) {
         const unsigned vd_tile = blk_y * tiles_x + blk_x, vd_tiles = tiles_x * rt_rest_tiles_y(fc.local_rows, TW);   // T = the grid
         // (a dword each: the word's halves, the tag)
-        if (VD_USE && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.rest_rd)[lane < 2 ? RT_REST_WORD_DWORD(vd_tile) + lane : RT_REST_TAG_DWORD(vd_tiles, vd_tile)];
+        if (VD_USE && (REST_EAGER || !settled) && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.rest_rd)[lane < 2 ? RT_REST_WORD_DWORD(vd_tile) + lane : RT_REST_TAG_DWORD(vd_tiles, vd_tile)];
         if (lane == 3) vd_ld = vd_tile;
         // Primary records (step 5c): the lane's dword -- which entry of the tile's view list is its closest hit, and its
-        // texel -- asked for here beside the word and used after the ray arithmetic.
-        if (VD_USE) pr_rec = reinterpret_cast<const unsigned *>(fc.rest_rd + RT_REST_PRIMARY_OFFSET(vd_tiles))[(size_t)vd_tile * (RT_REST_PRIMARY_BYTES / 4u) + lane];
+        // texel -- asked for here beside the word and used after the ray arithmetic. (A settled tile without a miss lane
+        // has no use for them; one with miss lanes tells hit from miss by them and takes the sky texel.)
+        if (VD_USE && (REST_EAGER || (ts & (RT_TILE_SETTLED | RT_TILE_NO_MISS)) != (RT_TILE_SETTLED | RT_TILE_NO_MISS))) pr_rec = reinterpret_cast<const unsigned *>(fc.rest_rd + RT_REST_PRIMARY_OFFSET(vd_tiles))[(size_t)vd_tile * (RT_REST_PRIMARY_BYTES / 4u) + lane];
     }
     const int tile_x = blk_x * TW;
     // local row -> global row: a contiguous band, or row blocks dealt round-robin
@@ -1398,6 +1426,35 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 
     const int n_samples = MULTI ? fc.spp : 1;
     for (int sample = 0; sample < n_samples; ++sample) {
+        float fr = 0.f, fg = 0.f, fb = 0.f;   // this sample's colour (sky texel on a miss)
+        do {   // (left at its head by a settled tile, step 5d; by every other at its end)
+        if (VD_USE && settled) {
+            // A settled tile: by the verdicts on record no light adds to any of its pixels, so a hit lane's colour is
+            // the 0 it starts with and a miss lane's the sky texel of its record, through the clamp as ever. No ray, list,
+            // normal, texel or group is formed: none of them has a consumer left. Everything from here to the sample's
+            // sum and the write-back is wave-uniformly skipped.
+            const bool no_miss = (ts & RT_TILE_NO_MISS) != 0;
+            if (no_miss || (valid_m & LM((pr_rec & 0xffu) == RT_PRIMARY_NONE)) == 0) {
+                if (!no_miss && valid && (pr_rec & 0xffu) == RT_PRIMARY_MISS) {
+                    int idx = (int)(pr_rec >> 8);
+                    const int last = ax->sky_w * ax->sky_h - 1;
+                    idx = idx < 0 ? 0 : (idx > last ? last : idx);
+                    fr = ax->sky_r[idx];
+                    fg = ax->sky_g[idx];
+                    fb = ax->sky_b[idx];
+                }
+                break;
+            }
+            // A valid lane without a record (the setters only): the full path. The tables the head left out are staged
+            // here; the word and the tags it did not ask for stay 0, "evaluate" and "no record" for every light, which
+            // is the plain kernel's frame. (Asking for them again here costs the kernel a spilled vector register.)
+            settled = false;
+            if (lane < 16) {
+                mybtab[lane] = kBrightnessSteps[lane];
+                myatan[lane] = kAtanEighth[lane];
+            }
+            wave_lds_sync();
+        }
         // header (a scalar load) and this lane's entry of the block's list: asked for here, ahead of the ray
         // arithmetic, and consumed after it. The slot is whole whatever its count, so the entry does not wait for the
         // header. A multi-sample launch fetches the list again for every sample (the light loop re-uses its LDS).
@@ -1775,6 +1832,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             start = V3{normal.x * 0.00001f + hp.x, normal.y * 0.00001f + hp.y, normal.z * 0.00001f + hp.z};
             if (STATS == 1) st_hits += 1;
         }
+        unsigned ts_pre = 0;   // (MODE 7) the tile's summary before its groups are known
         if (VD_REC) {
             // The recording launch: every lane's primary record, one coalesced 256-byte store per wave. A tile that walked
             // no view list (an overflowed block or one without cone, a tile shape that does not nest, a scene below 64
@@ -1789,6 +1847,10 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             const unsigned p_tiles = p_tiles_x * rt_rest_tiles_y(kp->local_rows, TW);   // = the grid
             unsigned *const o_prim = reinterpret_cast<unsigned *>(kp->rest_wr + RT_REST_PRIMARY_OFFSET(p_tiles));
             o_prim[(size_t)(blk_y * p_tiles_x + blk_x) * (RT_REST_PRIMARY_BYTES / 4u) + lane] = d;
+            // The tile's summary (step 5d) so far: it can be settled at all -- it has a record, and every light has its
+            // bits in the word --, and whether a valid lane is a miss. Parked behind the tile index below; the groups
+            // have their say behind the light loop.
+            ts_pre = ((v_use && fits && kp->n_lights <= RT_VERDICT_LIGHTS) ? RT_TILE_SETTLED : 0u) | ((valid_m & ~hit_m) == 0 ? RT_TILE_NO_MISS : 0u);
         }
 
         phase(3);
@@ -1798,7 +1860,6 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         mytex[lane] = tr;
         mytex[64 + lane] = tg;
         mytex[128 + lane] = tb;
-        float fr = 0.f, fg = 0.f, fb = 0.f;   // this sample's colour (sky texel on a miss)
         if (sky_idx >= 0) {
             fr = ax->sky_r[sky_idx];
             fg = ax->sky_g[sky_idx];
@@ -1837,6 +1898,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         }
         if (VERD) {   // the tile's word: the verdicts it was handed (MODE 6), or those it finds (MODE 7: none so far)
             if (lane < 4) myvd[lane] = vd_ld;
+            if (VD_REC && lane == 4) myvd[4] = ts_pre;
             wave_lds_sync();
         }
         if (hit_m != 0 && !RT_ABL(16)) {
@@ -2426,7 +2488,22 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 }
             }
             }   // groups
+            if (VD_REC && lane == 0) {
+                // Settled (step 5d): every iteration the tile has left its code RT_VERDICT_NOTHING in the word -- lane 0
+                // made every note, so it reads its own -- and the word holds them all. What the word must then be: code
+                // 1 for each of the n_lights lights in each of the n_groups 16-bit fields, 0 elsewhere.
+                bool all_nothing = n_groups <= RT_VERDICT_GROUPS && fc.n_lights <= RT_VERDICT_LIGHTS;
+                if (all_nothing) {
+                    const unsigned pat = 0x5555u & ((1u << (2 * fc.n_lights)) - 1u);
+                    const unsigned lo = (n_groups > 0 ? pat : 0u) | (n_groups > 1 ? pat << 16 : 0u);
+                    const unsigned hi = (n_groups > 2 ? pat : 0u) | (n_groups > 3 ? pat << 16 : 0u);
+                    all_nothing = myvd[0] == lo && myvd[1] == hi;
+                }
+                myvd[4] = (myvd[4] & (all_nothing ? (RT_TILE_SETTLED | RT_TILE_NO_MISS) : RT_TILE_NO_MISS)) |
+                          ((unsigned)(n_groups < 255 ? n_groups : 255) << RT_TILE_GROUPS_SHIFT);
+            }
         }
+        } while (false);
         if (valid) {
             acc_r = acc_r + fr;
             acc_g = acc_g + fg;
@@ -2509,6 +2586,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         wave_lds_sync();
         if (wb_lane < 2) o_rest[RT_REST_WORD_DWORD(wb_y * wb_tiles_x + wb_x) + wb_lane] = myvd[wb_lane];
         if (wb_lane == 2) o_rest[RT_REST_TAG_DWORD(rt_rest_tiles(kargs->width, kargs->local_rows, TW), wb_y * wb_tiles_x + wb_x)] = myvd[2];   // the tags of its records
+        if (wb_lane == 3) o_rest[RT_REST_SUMMARY_DWORD(rt_rest_tiles(kargs->width, kargs->local_rows, TW), wb_y * wb_tiles_x + wb_x)] = myvd[4];   // its summary
     }
     if (o_cost) {   // this tile's wave duration, for the order of later frames (a plain store: an atomic maximum
         // per block of tiles here, 256 waves ending together on one address, slowed the whole launch down by 3 %)
