@@ -1,6 +1,7 @@
 // rt_engine.cpp -- the part of the C ABI (include/rt_engine.h) that belongs to no scene: status and errors, the
 // memManager surface, and the constants of a frame. The scene is rt_scene.cpp, its cached tables rt_scene_tables.cpp,
-// its resting-view tables rt_scene_rest.cpp, the launches rt_render.cpp, the rayTrace shim rt_shim.cpp, the rt_debug_* entry points rt_debug.cpp.
+// its resting-view tables rt_scene_rest.cpp, the launches rt_render.cpp, the post passes rt_post.cpp, the rayTrace shim
+// rt_shim.cpp, the rt_debug_* entry points rt_debug.cpp.
 //
 // Reference interface replaced here:
 //   memManager / check_cuda      /root/reference/memManager.h:11-18, memManager.cpp:3-22

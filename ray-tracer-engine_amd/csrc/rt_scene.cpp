@@ -30,12 +30,7 @@ int rt_scene_quiesce(rt_scene *s)
     for (int i = 0; i < RT_RING; ++i)
         if (s->ring_used[i]) RT_HIP(hipEventSynchronize(s->ring[i].get()));
     if (s->table_stream.get()) RT_HIP(hipStreamSynchronize(s->table_stream.get()));   // a table build still reading the list
-    RT_HIP(s->dn_done.host_wait());                                                    // a denoise call still using the scratch
-    RT_HIP(s->tp_done.host_wait());                                                    // a temporal call still reading its ray tables
-    RT_HIP(s->up_done.host_wait());                                                    // an upsample call in flight
-    RT_HIP(s->ind_done.host_wait());                                                   // an indirect call still using its scratch
-    RT_HIP(s->dp_done.host_wait());                                                    // a display call still using its histogram
-    RT_HIP(s->bl_done.host_wait());                                                    // a bloom call still using its pyramid
+    for (HipPendingEvent &done : s->post_event) RT_HIP(done.host_wait());              // a post pass still using its scratch
     return RT_OK;
 }
 
@@ -430,7 +425,7 @@ extern "C" int rt_scene_set_roughness(rt_scene *s, int kind, const float *rho, i
 }
 
 // Emission per primitive of one kind: host state under rt_scene_set_roughness' protocol; the next indirect
-// call uploads it (rt_render.cpp, indirect_call)
+// call uploads it (rt_post.cpp, indirect_call)
 extern "C" int rt_scene_set_emission(rt_scene *s, int kind, const float *rgb, int n)
 {
     if (!s) {

@@ -1,5 +1,6 @@
 // rt_scene.h -- struct rt_scene and what its own translation units share (rt_scene.cpp, rt_scene_tables.cpp,
-// rt_scene_rest.cpp, rt_render.cpp, rt_shim.cpp, rt_debug.cpp). Everything else goes through the functions of rt_internal.h.
+// rt_scene_rest.cpp, rt_render.cpp, rt_post.cpp, rt_shim.cpp, rt_debug.cpp). Everything else goes through the functions of
+// rt_internal.h.
 //
 // Frames in flight and the buffers they read. A frame is asynchronous work on the caller's stream; the scene's device
 // buffers may be read by frames on several streams at once (two frames in flight, a replaying graph). Whoever is about
@@ -19,12 +20,11 @@
 //       build has finished;
 //   (c) a reader waits on the build event on the device only; the host never waits for a build, except in
 //       rt_scene_view_lists_info;
-//   (d) rt_scene_quiesce waits for the ring, then the table stream, then the denoiser's, the temporal pass's, the upsampler's,
-//       the indirect pass's, the display transform's and the bloom pass's events;
+//   (d) rt_scene_quiesce waits for the ring, then the table stream, then every post pass's event (rt_scene::post_event);
 //   (e) the tile order keeps one event for all layouts; a new layout or a re-sort first makes the launching stream
 //       wait for every ring event;
-//   (f) the denoiser records its event also after a launch that failed half-way, and host-waits before growing its
-//       scratch; the bloom pass does both for its pyramid;
+//   (f) every post pass's event is recorded also after a launch that failed half-way, and a pass host-waits for it
+//       before it grows or rewrites the scratch the event guards (rt_post.cpp, PostCall);
 //   (g) whatever rewrites or re-allocates a buffer a recorded graph may point into bumps `epoch`, and nothing else
 //       does: of the hand-over functions only an rt_scene_begin_build whose buffer re-allocates;
 //   (h) a resting-view table is written by a frame launch on the frame's own stream, not by a build on the table
@@ -32,6 +32,7 @@
 //       slot's `built` is the writing launch's event, and readers on other streams wait for it on the device. Its
 //       buffer is in no graph, so growing it (after a quiesce) bumps no epoch.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -111,7 +112,8 @@ struct TileOrder {
 };
 
 // One kind's emission table: what the host last set, and a device copy that changes only in an indirect call, behind
-// the calls that may still read it (the protocol of rt_reflect.hip's RfTable, with `ind_done` for the frame ring).
+// the calls that may still read it (the protocol of rt_reflect.hip's RfTable, with the indirect pass's event for the
+// frame ring).
 // The passes are pointed by what the device holds (v_dev), never by v.
 struct RtEmitTable {
     std::vector<float4> v;               // (r, g, b, 0) per primitive; empty = no table
@@ -119,6 +121,38 @@ struct RtEmitTable {
     bool dirty = false;                  // v changed since the last upload
     DevArray<float4> d;
     const float4 *dev() const { return v_dev.empty() ? nullptr : d.get(); }
+};
+
+// The post passes (rt_post.cpp). Every owner of scratch has one event, which orders the scene's calls of that pass on
+// the device, whatever their streams, and which rt_scene_quiesce waits for; every timed entry has a timer of its own.
+// The two denoisers share their scratch, so their event. A new pass: one value in each enum, one line in the map.
+enum RtPostOwner { RT_OWNER_ATROUS, RT_OWNER_TEMPORAL, RT_OWNER_UPSAMPLE, RT_OWNER_DISPLAY, RT_OWNER_BLOOM, RT_OWNER_INDIRECT, RT_POST_OWNERS };
+enum RtPostEntry { RT_POST_DENOISE, RT_POST_VDENOISE, RT_POST_TEMPORAL, RT_POST_UPSAMPLE, RT_POST_DISPLAY, RT_POST_BLOOM, RT_POST_INDIRECT, RT_POST_ENTRIES };
+constexpr RtPostOwner kPostOwner[RT_POST_ENTRIES] = {RT_OWNER_ATROUS, RT_OWNER_ATROUS, RT_OWNER_TEMPORAL, RT_OWNER_UPSAMPLE,
+                                                     RT_OWNER_DISPLAY, RT_OWNER_BLOOM, RT_OWNER_INDIRECT};
+// One cap for every entry's events (a HipEvent is made on first use: a spare slot costs nothing). The denoisers: one
+// event per iteration, and before the first launch, after the pack, after the variance's spatial estimate.
+#define RT_POST_MAX_EVENTS RT_INDIRECT_MAX_EVENTS
+static_assert(RT_DENOISE_MAX_ITERATIONS + 3 <= RT_POST_MAX_EVENTS, "the denoisers' events");
+static_assert(2 <= RT_POST_MAX_EVENTS, "the temporal pass's and the upsampler's events");
+static_assert(RT_DISPLAY_MAX_EVENTS <= RT_POST_MAX_EVENTS, "the display transform's events");
+static_assert(RT_BLOOM_MAX_EVENTS + 1 <= RT_POST_MAX_EVENTS, "the bloom pass's events");
+struct RtPostTimer {
+    HipEvent ev[RT_POST_MAX_EVENTS];
+    bool on = false;                     // rt_scene_set_*_timing
+    int timed = 0;                       // events the entry's last timed call recorded
+};
+
+// A pass's own ray tables at one sample, dx[w] then dy[h]: its own, so that a call at another size than the frames'
+// (half resolution) does not rebuild their d_raygen.
+struct RtRayTables {
+    DevArray<float> tab;
+    int w = 0, h = 0;
+    float aspect = 0.f;                  // compared by bits
+    // The tables of this size and aspect; if they are others, new ones after the host has seen `done`, the pass's last call, end
+    int prepare(HipPendingEvent &done, int width, int height, float aspect_);
+    const float *dx() const { return tab.get(); }
+    const float *dy() const { return tab.get() + w; }
 };
 
 struct rt_scene {
@@ -199,62 +233,31 @@ struct rt_scene {
     int rest_last_wrote = 0;                 // 1: it wrote it
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
     std::unique_ptr<RtReflect, RtReflectDeleter> refl;
-    // the two denoisers' scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand; `dn_done`
-    // orders the scene's denoise calls on the device, whatever their streams
+    // the post passes: what orders each one's calls, and each timed entry's timing state (guided upsampling,
+    // rt_upsample.hip, has no more than these); below, each pass's scratch
+    HipPendingEvent post_event[RT_POST_OWNERS];
+    RtPostTimer post_timer[RT_POST_ENTRIES];
+    // the two denoisers' scratch (rt_denoise.hip): two irradiance buffers and the packed guides, grown on demand
     DevArray<float4> dn_col[2], dn_guide;
     DevArray<int> dn_key;
-    HipPendingEvent dn_done;
-    HipEvent dn_ev[RT_DENOISE_MAX_ITERATIONS + 2];   // rt_scene_set_denoise_timing
-    bool dn_timing = false;
-    int dn_timed = 0;                                // events the last timed call recorded
-    // the variance-guided denoiser uses the scratch above and `dn_done`, plus two variance arrays and timing state of its own
+    // the variance-guided denoiser uses the scratch above, plus two variance arrays
     DevArray<float> vd_var[2];
-    HipEvent vd_ev[RT_DENOISE_MAX_ITERATIONS + 3];   // rt_scene_set_vdenoise_timing
-    bool vd_timing = false;
-    int vd_timed = 0;
-    // temporal accumulation (rt_temporal.hip): the ray tables of the view its last call reprojected from (its own, so
-    // that a call of another size does not rebuild the frames' d_raygen); `tp_done` orders the scene's temporal calls
-    DevArray<float> tp_raygen;                       // dx[width], dy[height] at one sample
-    int tp_w = 0, tp_h = 0;
-    float tp_aspect = 0.f;
-    HipPendingEvent tp_done;
-    HipEvent tp_ev[2];                               // rt_scene_set_temporal_timing
-    bool tp_timing = false;
-    int tp_timed = 0;
-    // guided upsampling (rt_upsample.hip): no scratch; `up_done` orders the scene's upsample calls
-    HipPendingEvent up_done;
-    HipEvent up_ev[2];                               // rt_scene_set_upsample_timing
-    bool up_timing = false;
-    int up_timed = 0;
+    // temporal accumulation (rt_temporal.hip): the ray tables of the view its last call reprojected from
+    RtRayTables tp_rays;
     // the display transform (rt_display.hip): the histogram's RT_DISPLAY_BINS counters and, behind them, the 256
-    // thresholds of the sRGB encoding, uploaded when the buffer is made; `dp_done` orders the scene's display calls
+    // thresholds of the sRGB encoding, uploaded when the buffer is made
     DevArray<uint32_t> dp_scratch;
-    HipPendingEvent dp_done;
-    HipEvent dp_ev[RT_DISPLAY_MAX_EVENTS];           // rt_scene_set_display_timing
-    bool dp_timing = false;
-    int dp_timed = 0;
-    // the bloom pass (rt_bloom.hip): the pyramid's levels one behind the other, grown on demand and never shrunk;
-    // `bl_done` orders the scene's bloom calls
+    // the bloom pass (rt_bloom.hip): the pyramid's levels one behind the other, grown on demand and never shrunk
     DevArray<float4> bl_pyramid;
-    HipPendingEvent bl_done;
-    HipEvent bl_ev[RT_BLOOM_MAX_EVENTS + 1];         // rt_scene_set_bloom_timing
-    bool bl_timing = false;
-    int bl_timed = 0;
     // the indirect pass (rt_indirect.hip): ray tables of its own, as the temporal pass has, and the product's scratch,
-    // grown on demand; `ind_done` orders the scene's indirect calls
-    DevArray<float> ind_raygen;                      // dx[width], dy[height] at one sample
-    int ind_w = 0, ind_h = 0;
-    float ind_aspect = 0.f;
+    // grown on demand
+    RtRayTables ind_rays;
     DevArray<float4> ind_slab, ind_queue, ind_sum;
     DevArray<int> ind_count;
     DevArray<float4> ind_queue2;                     // bounces > 1: the second of the two queues
     int ind_counts = 0, ind_bounces = 1;             // the last call's counters (groups * bounces; plain: 0) and bounces
-    HipPendingEvent ind_done;
-    HipEvent ind_ev[RT_INDIRECT_MAX_EVENTS];         // rt_scene_set_indirect_timing
-    bool ind_timing = false;
-    int ind_timed = 0;
     // emission per primitive of a kind (rt_scene_set_emission; [kind - RT_HIT_SPHERE]): host state, which
-    // the next indirect call uploads on its stream behind `ind_done` -- the indirect calls are the tables' only readers
+    // the next indirect call uploads on its stream behind the pass's event -- the indirect calls are the tables' only readers
     RtEmitTable emit[3];
 #ifdef RT_TUNING
     int tune_no_eye_cones = 0, tune_no_light_columns = 0, tune_ablate = 0;
@@ -289,6 +292,24 @@ void rt_view_params_from_consts(const RtFrameConsts &fc, float aspect, RtViewPar
 void rt_view_lists_summary(const float4 *slots, int blocks, rt_view_lists_info *out);
 // rt_render.cpp
 void rt_view_rotation(const rt_frame_desc *fd, RtFrameConsts *fc);
+
+// For the entry points of rt_render.cpp and rt_post.cpp. A caller's versioned struct in this build's layout: what its
+// struct_size (0: `size0`) does not cover reads as 0. Returns the bytes taken from the caller.
+template <typename T>
+size_t as_built(const T *in, T *out, size_t size0 = sizeof(T))
+{
+    memset(out, 0, sizeof *out);
+    const size_t sz = std::min<size_t>(in->struct_size ? in->struct_size : size0, sizeof *out);
+    memcpy(out, in, sz);
+    out->struct_size = (uint32_t)sizeof *out;
+    return sz;
+}
+inline bool stream_capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream) (void)hipStreamIsCapturing(stream, &cs);
+    return cs != hipStreamCaptureStatusNone;
+}
 
 // margin of the fast texel-index path for a texture dimension of `size` texels (rt_kernels.hip:
 // sure_texel): approximation error RT_UV_DELTA plus the rounding of the two float products
