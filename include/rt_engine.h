@@ -1159,7 +1159,12 @@ int rt_multi_set_lights(rt_multi *m, const rt_light *lights, int n);
  * opts.y0 / y1 select a band of whole 16-row blocks, dealt to the devices from the band's first row;
  * its output pointers and interleave fields are ignored). The assembled rows land at their place in
  * `pixels_dev0` (the WHOLE frame's buffer in memory of the first device) or, if that is NULL, in an
- * internal buffer (rt_multi_frame). Asynchronous; two frames (or bands) may be in flight. */
+ * internal buffer (rt_multi_frame). There are two internal buffers: a call that begins a frame -- a whole
+ * frame, or a band with y0 == 0 -- takes the other one, and every later band of that frame lands in the same
+ * one, so after a frame's last band rt_multi_frame / rt_multi_download give the whole frame, and the frame
+ * before it stays readable meanwhile. Asynchronous; two frames (or bands) may be in flight. After a change of
+ * the frame's size there is no last frame until a render has succeeded (rt_multi_frame NULL, rt_multi_download
+ * and rt_multi_stream_wait fail). */
 int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *pixels_dev0);
 int rt_multi_sync(rt_multi *m);                              /* wait for every frame enqueued so far */
 int rt_multi_stream_wait(rt_multi *m, void *stream);         /* `stream` (first device) waits ON THE DEVICE for the frame /

@@ -112,7 +112,8 @@ struct rt_multi {
     HipEvent pulled[2];
     bool set_used[2] = {false, false};
     int width = 0, height = 0, slot_rows = 0;
-    unsigned long long frames = 0;
+    unsigned long long frames = 0;                     // calls enqueued: the receive / send set alternates per call
+    int frame_ix = 0;                                  // internal frame buffer of the frame begun last (internal_frame_of)
     uint32_t *last = nullptr;
     int last_set = -1;                                 // buffer set of the last enqueued frame / band
     unsigned long long gathers = 0;                    // ncclGather groups issued (rt_multi_gathers)
@@ -143,6 +144,9 @@ static int release_buffers(rt_multi *m)
         m->set_used[b] = false;
     }
     m->width = m->height = m->slot_rows = 0;
+    // nothing refers to the freed frames: until the next render succeeds there is no last frame
+    m->last = nullptr;
+    m->last_set = -1;
     return RT_OK;
 }
 
@@ -393,11 +397,17 @@ static int ensure_buffers(rt_multi *m, int width, int height)
     return RT_OK;
 }
 
+// The internal frame buffer of a call that starts at row y0: a whole frame or a band with y0 == 0 begins a frame and
+// takes the other buffer, every later band of that frame lands in the same one (the receive / send set alternates
+// per call, the frame buffer per frame). The caller stores the index in m->frame_ix once the call is enqueued.
+static int internal_frame_of(const rt_multi *m, int y0) { return y0 == 0 ? m->frame_ix ^ 1 : m->frame_ix; }
+
 // One frame, or one row band of it. fd: the whole frame's width, height, aspect, cam; opts.spp / cull / tile
 // honoured; opts.y0 / y1 (both multiples of 16 rows, or 0 / 0 for the whole frame) select a row band, whose
 // 16-row blocks are dealt to the devices from the band's first row; interleave and output pointers of fd are
 // ignored. The assembled 0x00RRGGBB rows land at their place in `pixels_dev0` (device memory of the first
-// device, the WHOLE frame's buffer) or, when that is null, in an internal frame buffer (rt_multi_frame).
+// device, the WHOLE frame's buffer) or, when that is null, in an internal frame buffer (rt_multi_frame): one buffer
+// for all bands of a frame, the other one from the next call that begins a frame (y0 == 0).
 // Asynchronous: returns when the work is enqueued; two frames (or bands) may be in flight.
 extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *pixels_dev0)
 {
@@ -428,7 +438,7 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
     if (n == 1 && (m->transport != RT_MULTI_RCCL || w % 4 != 0)) {
         rc = ensure_buffers(m, w, h);
         if (rc != RT_OK) return rc;
-        const int b = (int)(m->frames & 1);
+        const int b = (int)(m->frames & 1), fb = internal_frame_of(m, y0);
         RT_HIP(hipSetDevice(m->dev[0].device));
         if (m->set_used[b]) RT_HIP(hipStreamWaitEvent(m->dev[0].stream.get(), m->assembled[b].get(), 0));
         rt_frame_desc f = *fd;
@@ -438,7 +448,7 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
         f.opts.rgba = nullptr;
         f.opts.packed24 = nullptr;
         f.opts.stats = nullptr;
-        uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[b].get();
+        uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[fb].get();
         f.pixels = out + (size_t)y0 * (size_t)w;
         rc = rt_scene_render(m->dev[0].scene, &f, m->dev[0].stream.get());
         if (rc != RT_OK) return rc;
@@ -446,6 +456,7 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
         m->set_used[b] = true;
         m->last = out;
         m->last_set = b;
+        m->frame_ix = fb;
         m->frames++;
         return RT_OK;
     }
@@ -455,7 +466,7 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
     }
     rc = ensure_buffers(m, w, h);
     if (rc != RT_OK) return rc;
-    const int b = (int)(m->frames & 1);   // buffer set of this frame
+    const int b = (int)(m->frames & 1), fb = internal_frame_of(m, y0);   // buffer set of this call, frame buffer of its frame
     // slots of the receive buffer: the largest share of THIS band, whole blocks (a whole frame: m->slot_rows)
     const int blocks = (hb + RT_MULTI_BLOCK - 1) / RT_MULTI_BLOCK;
     const int slot_rows = ((blocks + n - 1) / n) * RT_MULTI_BLOCK;
@@ -514,7 +525,11 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
     }
     // rows home, 24 -> 32 bits
     RT_HIP(hipSetDevice(root.device));
-    uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[b].get();
+    uint32_t *out = pixels_dev0 ? pixels_dev0 : m->frame[fb].get();
+    // an internal frame buffer is written from both sets' copy streams: this scatter follows the previous call's
+    // (the root's one stream orders them under the RCCL transport)
+    if (!pixels_dev0 && m->transport != RT_MULTI_RCCL && m->set_used[b ^ 1])
+        RT_HIP(hipStreamWaitEvent(assemble_on, m->assembled[b ^ 1].get(), 0));
     const long long threads = (long long)(w / 4) * hb;
     hipLaunchKernelGGL(rt_scatter_rows24, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, assemble_on, m->recv[b].get(),
                        reinterpret_cast<uint4 *>(out + (size_t)y0 * (size_t)w), w, hb, n, slot_rows);
@@ -523,6 +538,7 @@ extern "C" int rt_multi_render(rt_multi *m, const rt_frame_desc *fd, uint32_t *p
     m->set_used[b] = true;
     m->last = out;
     m->last_set = b;
+    m->frame_ix = fb;
     m->frames++;
     return RT_OK;
 }
