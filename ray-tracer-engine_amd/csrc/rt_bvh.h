@@ -1,12 +1,13 @@
 // rt_bvh.h -- the sphere BVH and the per-ray pieces shared by the reflective passes (rt_reflect.hip) and the ray
 // queries (rt_query.hip): sphere::intersect on a table entry, the exact BVH walk (nearest and any-hit), the sky
-// lookup, the hit frame of a sphere hit and the primary ray of a pixel. Included after rt_trace.inc.
+// lookup, the hit frame of a sphere hit and the primary ray of a pixel. Stands on rt_exact.h (V3, AuxPtr, the primitive tests) and
+// takes neither the culling, the shadow chain nor the frame kernel: rt_sphere_bvh.cpp, a host unit, includes it.
 //
 // The BVH (host build in binary64, leaves of <= 4 spheres) is exact against the list: its traversal never drops a
 // sphere that sphere::intersect reports as hit, and the nearest hit is the lexicographic minimum of (t, index) --
 // what the reference's strict `t < nt` loop returns. The margin and the pruning rule are derived in DESIGN.md.
 #pragma once
-#include "rt_trace.inc"
+#include "rt_exact.h"
 #include "rt_internal.h"
 
 #include <vector>
@@ -45,7 +46,7 @@ struct RtReflectDev {              // the passes' uniforms (by value)
 // host & device: sphere::intersect, the BVH walk
 // ---------------------------------------------------------------------------
 // sphere::intersect, kernel.cu:293-354, on a table entry {cx,cy,cz,radius*radius}: the operations of quadratic() and
-// intersect_tail() in rt_trace.inc, in the same order (this file is compiled without contraction, both sides).
+// intersect_tail() in rt_exact.h, in the same order (this file is compiled without contraction, both sides).
 __host__ __device__ __forceinline__ bool rf_intersect(float ox, float oy, float oz, float dx, float dy, float dz,
                                                       float4 s, float &t)
 {
@@ -220,7 +221,7 @@ __device__ __forceinline__ void rf_sky(AuxPtr ax, V3 O, V3 D, float &r, float &g
     b = ax->sky_b[idx];
 }
 
-// normalise_inplace (rt_trace.inc) for host and device: the same operations (the host debug entries run them)
+// normalise_inplace (rt_exact.h) for host and device: the same operations (the host debug entries run them)
 __host__ __device__ __forceinline__ void rf_normalise(V3 &v)
 {
     const float l = __builtin_sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);

@@ -1,10 +1,11 @@
 // rt_cast.h -- the reference's casts over every kind of primitive, shared by the ray queries (rt_query.hip) and the
 // whole-scene reflective passes (rt_reflect.hip): castRay's nearest hit (q_nearest) and hit record
 // (q_hit_record), castLightRay's any-hit (q_occluded) and rayTrace's pixel body at a hit (q_shade_hit). One copy:
-// every primitive test is the frame kernel's own (rt_trace.inc), the spheres go through the BVH of rt_bvh.h.
+// every primitive test and the shadow chain are the frame kernel's own (rt_exact.h, rt_shadow.h), the spheres go through the BVH of rt_bvh.h.
 // Device only.
 #pragma once
 #include "rt_bvh.h"
+#include "rt_shadow.h"
 
 namespace {
 

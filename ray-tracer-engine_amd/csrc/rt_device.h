@@ -11,9 +11,9 @@
 
 #define RT_DEV_MAX_LIGHTS 8
 
-// Paddings of the conservative culling tests (rt_trace.inc: beam_keeps, beam_member_test, beam_keeps_block,
+// Paddings of the conservative culling tests (rt_cull.h: beam_keeps, beam_member_test, beam_keeps_block,
 // beam_keeps_column; rt_tables.hip: cone_entry). What they must cover is the rounding of the EXACT test. intersect()
-// (kernel.cu:332-336, `quadratic()` in rt_trace.inc) can only return true if its binary32 discriminant is >= 0. With
+// (kernel.cu:332-336, `quadratic()` in rt_exact.h) can only return true if its binary32 discriminant is >= 0. With
 // eps = 2^-24, d = |o - c| and |D| = 1 (to 2e-7): the dot product h carries at most 4 eps d (three products, two sums, the
 // rounded o - c), B*B at most 20 eps d^2, 4A*C at most 40 eps d^2 (C: 6 eps d^2; 4A: 4 eps relative on |C| <= d^2 ... with
 // R <= d, else read d as R), the final subtraction 4 eps d^2: |disc_float - disc| <= 64 eps d^2 = 3.8e-6 d^2, i.e. 9.5e-7 d^2
@@ -79,6 +79,54 @@
 #define RT_VIEW_SLOT (1 + RT_VIEW_CAP + RT_VIEW_CAP / 4 + RT_VIEW_CAP / 4)   // float4 per block: header, entries, positions, bounds
 #define RT_VIEW_OVERFLOW 1      // header flags: more than RT_VIEW_CAP survivors -- the tile culls for itself
 #define RT_VIEW_NOT_BUILT 2     // ... the block has no usable cone (degenerate or too wide) -- likewise
+
+// The frame kernel's MODE and FEAT (rt_trace.inc: rt_trace_tiles<TW, CULL, MODE, FEAT, MULTI>; RtKernelChoice::mode and
+// ::feat on the host). The template parameters are plain ints -- the kernels' mangled names carry the numbers, and
+// tools and committed profiles key on those -- so the lists are unscoped: a name is its number.
+enum RtTraceMode : int {
+    RT_MODE_PRODUCT = 0,      // the product kernel
+    RT_MODE_STATS = 1,        // ... with the work counters (rt_launch_opts.stats)
+    RT_MODE_FORCE_SLOW = 2,   // every exactness-preserving shortcut off (rt_launch_opts.force_slow_path: tests)
+    RT_MODE_PHASES = 3,       // per-phase cycle stamps (s_memtime; RT_TUNING builds only, run time never quoted)
+    RT_MODE_FAST = 4,         // opt-in approximate arithmetic (rt_launch_opts.fast)
+    RT_MODE_AOV = 5,          // the product kernel plus the G-buffer stores (rt_frame_desc.aov_*; one sample, default tile)
+    RT_MODE_REST_READ = 6,    // the product kernel consuming a resting view's table (RtFrameConsts::rest_rd)
+    RT_MODE_REST_WRITE = 7,   // ... recording it (rest_wr): one-sample launches of sphere scenes, chosen by
+                              // rt_dev_trace_config from the two pointers -- RT_MODE_PRODUCT itself carries neither the
+                              // code nor the registers of either
+};
+// Each FEAT is its own instantiation so that the sphere-only kernel carries neither the code nor the live scalars of
+// primitives that are not there.
+enum RtTraceFeat : int {
+    RT_FEAT_SPHERES = 0,      // spheres only (the reference's default scene and every BASELINE config)
+    RT_FEAT_PRIMS = 1,        // with the cube / plane branches of castRay and castLightRay
+    RT_FEAT_MESH = 2,         // with those and the triangle mesh
+};
+
+// The wave's LDS in the frame kernel: the survivor list of RT_LIST_CAP float4 entries, then the regions below, in dwords
+// from the list's end. rt_trace_tiles carves its pointers from these names and rt_dev_trace_config sizes the launch by
+// rt_trace_lds_bytes(); nothing else states the layout. The tail is the mesh's (RT_FEAT_MESH launches: the leaf-box list,
+// the marked leaf blocks of a culling pass, the staged vertices of a leaf) or, in the same place, the resting-view words
+// of the sphere-only launches (verdict word, tags, tile index, summary).
+constexpr int RT_LDS_KEYS = 0;                              // RT_LIST_CAP ints: list positions (primary order)
+constexpr int RT_LDS_BTAB = RT_LDS_KEYS + RT_LIST_CAP;      // 16 floats: the brightness table
+constexpr int RT_LDS_BLKS = RT_LDS_BTAB + 16;               // 64 ints: marked blocks of a culling pass
+constexpr int RT_LDS_ATAN = RT_LDS_BLKS + 64;               // 16 doubles: atan(k/8)
+constexpr int RT_LDS_TEX = RT_LDS_ATAN + 32;                // 192 floats: texel colours per pixel
+constexpr int RT_LDS_TAIL = RT_LDS_TEX + 192;
+constexpr int RT_LDS_MESH_BLKS = RT_BOX_CAP;                // within a mesh tail, behind the RT_BOX_CAP ints of the list: 64 ints
+constexpr int RT_LDS_MESH_TRI = RT_LDS_MESH_BLKS + 64;      // ... and 64 floats
+constexpr int RT_LDS_MESH_DWORDS = RT_LDS_MESH_TRI + 64;
+constexpr int RT_LDS_REST_DWORDS = 8;
+constexpr unsigned rt_trace_lds_bytes(int feat)
+{
+    return RT_LIST_CAP * 16u + 4u * (unsigned)(RT_LDS_TAIL + (feat == RT_FEAT_MESH ? RT_LDS_MESH_DWORDS : RT_LDS_REST_DWORDS));
+}
+static_assert((RT_LIST_CAP * 16 + 4 * RT_LDS_ATAN) % 8 == 0, "frame kernel's LDS: the atan table holds doubles");
+static_assert(RT_LDS_REST_DWORDS <= RT_LDS_MESH_DWORDS, "frame kernel's LDS: the resting-view words fit the tail every launch has");
+#if RT_LIST_CAP == 128 && RT_BOX_CAP == 128
+static_assert(rt_trace_lds_bytes(RT_FEAT_SPHERES) == 3808 && rt_trace_lds_bytes(RT_FEAT_MESH) == 4800, "frame kernel's LDS: the totals at the default capacities");
+#endif
 
 // Smallest binary32 >= 0.0001 (binary64): `t >= 0.0001` (kernel.cu:342) compares
 // the widened float with the double literal, which is equivalent to a float
@@ -259,7 +307,7 @@ struct RtFrameConsts {
     const unsigned *tile_perm;
     unsigned *tile_cost;
 
-    // G-buffer outputs (rt_frame_desc.aov_*; MODE 5 of the frame kernel only), band-local like `rgba`, may be null:
+    // G-buffer outputs (rt_frame_desc.aov_*; RT_MODE_AOV of the frame kernel only), band-local like `rgba`, may be null:
     // read from the kernel-argument segment where they are stored, after the primary hit's texel fetch
     float *aov_depth;           // float per pixel
     float *aov_normal;          // float4 per pixel
@@ -268,11 +316,11 @@ struct RtFrameConsts {
 
     // The resting-view table (layout: the RT_REST_* block below). rest_wr: this launch
     // records into it; rest_rd: it reads what an earlier launch of bit-identical inputs recorded (the host keeps the
-    // key). Either may be null; only the one-sample sphere-only product kernel (MODE 0, FEAT 0, CULL) looks at them.
+    // key). Either may be null; only the one-sample sphere-only product kernel (RT_MODE_PRODUCT, RT_FEAT_SPHERES, CULL) looks at them.
     const unsigned char *rest_rd;
     unsigned char *rest_wr;
 };
-// The resting-view table: what a recording launch (MODE 7) leaves for the reading launches (MODE 6) of the same key, one
+// The resting-view table: what a recording launch (RT_MODE_REST_WRITE) leaves for the reading launches (RT_MODE_REST_READ) of the same key, one
 // allocation of five sections, each an array over the T tiles of the launch's grid by the tile's frame coordinates
 // (tile_y * tiles_x + tile_x, after tile_perm). This block is the layout; nothing else states it.
 //   words    a 64-bit word per tile: two bits per (group, light) for the tile's first RT_VERDICT_GROUPS groups, in the

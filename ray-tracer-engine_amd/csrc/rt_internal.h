@@ -125,7 +125,7 @@ private:
 struct rt_scene;
 struct RtTableSlot;   // rt_scene.h
 
-// which instantiation of the frame kernel renders a frame (rt_kernels.hip: TW, CULL, MODE, FEAT)
+// which instantiation of the frame kernel renders a frame (rt_trace.inc: TW, CULL; rt_device.h: RtTraceMode, RtTraceFeat)
 struct RtKernelChoice {
     int tile, cull, mode, feat;
 };

@@ -205,7 +205,7 @@ RtTraceFn rt_trace_fn_cull8(int mode, int feat, int multi)
 // host-side launchers (called from rt_render.cpp / rt_debug.cpp / rt_graph.cpp)
 // ---------------------------------------------------------------------------
 // The instantiations that exist: trace_exists() in rt_trace.inc. Tile widths other than 8 are test dimensions, and
-// MODE 3 (phase stamps) exists in RT_TUNING builds only. Everything but the default tile's culling kernels lives in
+// RT_MODE_PHASES exists in RT_TUNING builds only. Everything but the default tile's culling kernels lives in
 // the other translation units.
 static RtTraceFn trace_fn(int tile_w, int cull, int mode, int feat, int multi)
 {
@@ -219,18 +219,11 @@ static RtTraceFn trace_fn(int tile_w, int cull, int mode, int feat, int multi)
 extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int feat,
                                           const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes)
 {
-    // a product launch that was handed a resting-view table runs the instantiation that writes (7) or reads (6) it
-    if (mode == 0 && (fc->rest_wr || fc->rest_rd)) mode = fc->rest_wr ? 7 : 6;
+    // a product launch that was handed a resting-view table runs the instantiation that writes or reads it
+    if (mode == RT_MODE_PRODUCT && (fc->rest_wr || fc->rest_rd)) mode = fc->rest_wr ? RT_MODE_REST_WRITE : RT_MODE_REST_READ;
     const RtTraceFn fn = trace_fn(tile_w, cull, mode, feat, fc->spp > 1 ? 1 : 0);
     if (!fn) return hipErrorNotSupported;
-    *lds_bytes = (unsigned)(RT_LIST_CAP * sizeof(float4) +   // survivor list
-                            RT_LIST_CAP * sizeof(int) +      // list positions (primary order)
-                            16 * sizeof(float) +             // brightness table
-                            64 * sizeof(int) +               // marked blocks of a culling pass
-                            16 * sizeof(double) +            // atan(k/8)
-                            192 * sizeof(float) +            // texel colours per pixel
-                            (feat == 2 ? (RT_BOX_CAP + 128) * sizeof(int)   // leaf boxes, marked blocks, staged vertices
-                                       : 8 * sizeof(unsigned)));            // the tile's light verdicts, record tags, index and summary (same place)
+    *lds_bytes = rt_trace_lds_bytes(feat);
     *grid = dim3(rt_rest_tiles_x(fc->width, tile_w), rt_rest_tiles_y(fc->local_rows, tile_w));
     *block = dim3(64);
     *func = (const void *)fn;

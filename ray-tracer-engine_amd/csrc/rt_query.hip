@@ -7,7 +7,7 @@
 //   OCCLUDED  castLightRay's per-sample any-hit over every kind of primitive (kernel.cu:1475-1536);
 //   SHADE     rayTrace's pixel body (kernel.cu:1633-1690): the texel, then per light the frame kernel's ShadowChain at
 //             brute-force precision with the all-kinds any-hit above; getFColor on a miss.
-// Every primitive test is the frame kernel's own (rt_trace.inc); the spheres go through rt_bvh.h. The casts themselves
+// Every primitive test is the frame kernel's own (rt_exact.h, rt_shadow.h); the spheres go through rt_bvh.h. The casts themselves
 // (q_nearest, q_hit_record, q_occluded, q_shade_hit) are in rt_cast.h, shared with the whole-scene reflective passes.
 // The brute-force variant (cull = 0) is the same kernels with the BVH replaced by the whole sphere list.
 #include "rt_cast.h"

@@ -186,16 +186,16 @@ int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelC
     int rc = tile_from_opts(fd->opts, &kc->tile);
     if (rc != RT_OK) return rc;
     kc->cull = (fd->opts.cull == 0) ? 0 : 1;
-    kc->mode = fd->opts.stats ? (fd->opts.profile ? 3 : 1) : (fd->opts.force_slow_path ? 2 : 0);
-    kc->feat = s->n_boxes > 0 ? 2 : ((s->n_planes > 0 || s->n_cubes > 0) ? 1 : 0);
+    kc->mode = fd->opts.stats ? (fd->opts.profile ? RT_MODE_PHASES : RT_MODE_STATS) : (fd->opts.force_slow_path ? RT_MODE_FORCE_SLOW : RT_MODE_PRODUCT);
+    kc->feat = s->n_boxes > 0 ? RT_FEAT_MESH : ((s->n_planes > 0 || s->n_cubes > 0) ? RT_FEAT_PRIMS : RT_FEAT_SPHERES);
     // the opt-in approximate mode exists for the product configuration only; anything else renders exactly
     // (a reflective frame is exact: `fast` is ignored there -- its L feeds the bounces; and so is
     // a launch with the table_lds field set: include/rt_engine.h)
-    if (fd->opts.fast == 1 && fd->opts.reflect_depth == 0 && kc->mode == 0 && kc->cull && kc->tile == 8 && kc->feat < 2 &&
+    if (fd->opts.fast == 1 && fd->opts.reflect_depth == 0 && kc->mode == RT_MODE_PRODUCT && kc->cull && kc->tile == 8 && kc->feat != RT_FEAT_MESH &&
         fd->opts.table_lds != 1)
-        kc->mode = 4;
+        kc->mode = RT_MODE_FAST;
 #ifndef RT_TUNING
-    if (kc->mode == 3) {
+    if (kc->mode == RT_MODE_PHASES) {
         rt_set_error("rt_scene_render: opts.profile (phase stamps) needs a tuning build of the library (make EXTRA=-DRT_TUNING)");
         return RT_ERR_UNSUPPORTED;
     }
@@ -206,7 +206,7 @@ int rt_frame_kernel_choice(const rt_scene *s, const rt_frame_desc *fd, RtKernelC
     }
     // the G-buffer kernel: the product kernel plus its stores (aov_supported has refused what it does not cover;
     // `fast` is ignored, as for reflective frames)
-    if (rt_fd_aov_field(fd)) kc->mode = 5;
+    if (rt_fd_aov_field(fd)) kc->mode = RT_MODE_AOV;
     return RT_OK;
 }
 
@@ -393,7 +393,7 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     }
     // the resting-view table: the plain one-sample frame of a sphere scene (not a reflective frame, whose passes follow)
     int rest = -1;
-    rc = rt_scene_prepare_rest(s, kc, &fc, reflect_depth == 0 && kc.mode == 0 && kc.feat == 0 && kc.cull && fc.spp == 1, stream, &rest);
+    rc = rt_scene_prepare_rest(s, kc, &fc, reflect_depth == 0 && kc.mode == RT_MODE_PRODUCT && kc.feat == RT_FEAT_SPHERES && kc.cull && fc.spp == 1, stream, &rest);
     if (rc != RT_OK) return rc;
     if (samples) {   // the frame kernel per sample, the passes per group, the resolve pass
         rc = rt_reflect_launch_samples(s->refl.get(), &fc, &out, &kc, s->d_spheres.get(), s->n_spheres, reflect_depth, stream);

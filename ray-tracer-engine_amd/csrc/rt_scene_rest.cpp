@@ -9,8 +9,8 @@
 // or re-allocated after a quiesce (textures, sky, RtFrameAux with its lights, light tables, occluder lists, raygen
 // tables, a slot that grew); the cone table and the view lists are rebuilt in place only for another origin, view or
 // sphere list, all of which the key holds.
-// Policy: a launch whose key has a table reads it (MODE 6). One whose key has none but is among the scene's last
-// RT_REST_SLOTS table-less keys (rest_seen) writes one (MODE 7) and leaves that history. A launch with any other
+// Policy: a launch whose key has a table reads it (RT_MODE_REST_READ). One whose key has none but is among the scene's last
+// RT_REST_SLOTS table-less keys (rest_seen) writes one (RT_MODE_REST_WRITE) and leaves that history. A launch with any other
 // key does neither and enters the history in place of its oldest entry: a moving camera records nothing, a view at rest
 // records on its second launch, and so does every layout of a frame rendered as a repeating cycle of up to
 // RT_REST_SLOTS launches (update()'s three row bands) on the cycle's second pass. A launch out of scope leaves the

@@ -421,7 +421,7 @@ int rt_scene_prepare_view(rt_scene *s, const rt_frame_desc *fd, const RtKernelCh
                           hipStream_t stream, int *view_out)
 {
     *view_out = -1;
-    if (!s->view_lists_mode || cone_slot < 0 || !kc.cull || kc.mode == 2) return RT_OK;
+    if (!s->view_lists_mode || cone_slot < 0 || !kc.cull || kc.mode == RT_MODE_FORCE_SLOW) return RT_OK;
     RtViewParams p;
     rt_view_params_from_consts(*fc, fd->aspect, &p);
     if (!view_tiles_nest(p, *fc, kc.tile)) return RT_OK;
@@ -508,5 +508,5 @@ extern "C" int rt_scene_view_lists_info(rt_scene *s, rt_view_lists_info *out, fl
 int rt_view_params_for_frame(const rt_scene *s, const RtFrameConsts *fc, float aspect, int tile_w, int cull, int mode, RtViewParams *p)
 {
     rt_view_params_from_consts(*fc, aspect, p);
-    return s->view_lists_mode && cull && mode != 2 && view_tiles_nest(*p, *fc, tile_w);
+    return s->view_lists_mode && cull && mode != RT_MODE_FORCE_SLOW && view_tiles_nest(*p, *fc, tile_w);
 }

@@ -2,7 +2,7 @@
 // table {cx,cy,cz,radius*radius} with conservative block bounds (see rt_device.h and DESIGN.md
 // section 4). None of them can change a pixel: a table only decides which spheres the exact
 // tests of rt_kernels.hip get to see, and every bound is padded so that a sphere left out is
-// one whose exact test (/root/reference/kernel.cu:293-354) would have returned false.
+// one whose exact test (kernel.cu:293-354) would have returned false.
 //
 //   build_sorted_blocks   3-D Morton order, bounding spheres      host, when the list changes
 //   build_light_columns   per light: order ACROSS its axis        host, when a light or the list changes
@@ -25,7 +25,7 @@
 
 #include "rt_device.h"
 #include "rt_tables.h"
-#include "rt_trace.inc"   // the view lists are built by the frame kernel's own cull (build_list2)
+#include "rt_cull.h"   // the view lists are built by the frame kernel's own cull (build_list2)
 
 // ---------------------------------------------------------------------------
 // shared host / device pieces
@@ -259,7 +259,7 @@ void rt_build_light_columns(const float4 *tab, int n, const float u_f[3], float4
 // runs within a few degrees of u = l.pos/|l.pos| WHATEVER its start (kernel.cu:1468 forms the direction relative to the
 // world origin). So the spheres such a ray can hit from anywhere on sphere S are those that reach into the cone of
 // slope kcap around u from a ball around S: a short list per (S, light), built here once per scene, of which a tile
-// then only has to cull the members against its own, much thinner beam (rt_trace.inc: build_list_cand) instead of
+// then only has to cull the members against its own, much thinner beam (rt_cull.h: build_list_cand) instead of
 // walking the light's column blocks. Conservative by the same member test the kernel applies (beam_member_test) with
 // the ball of S (radius R_S 1.001 + 1e-3) as the ray origins. Most starts lie in it (1e-5 above the surface), but not
 // all: a start is a float hit point, and at a grazing primary ray the rounding of the discriminant moves it along the ray

@@ -1,10 +1,15 @@
-// rt_kernels.hip -- gfx950 (MI355X) kernels for the ray-tracing hot path.
+// rt_trace.inc -- the frame kernel rt_trace_tiles for gfx950 (MI355X), the table of its instantiations
+// (trace_exists, the trace_fn_* ladders) and the declarations of the table's three parts. Included by the units that
+// instantiate the kernel and by no other: rt_kernels.hip (default tile, culling kernels, plus the launch
+// configuration and the diagnostics), rt_kernels_brute.hip (the same tile, brute-force loops) and
+// rt_kernels_tiles.hip (the other tile shapes) -- one code object, compiled in parallel. The device library the kernel
+// stands on is in four headers, each including the one before it: rt_wave.h (pointer types, V3, wave helpers),
+// rt_exact.h (exact and lean arithmetic, primitive tests), rt_cull.h (beams, list builders) and rt_shadow.h
+// (ShadowChain, shadow_test, the sample pre-pass). The other passes take those headers, never this file.
 //
-// What is computed is the reference's `rayTrace` kernel restricted to its
-// sphere path (/root/reference/kernel.cu:1614-1690 and callees: castRay
-// :1287-1431, castLightRay :1432-1544, sphere::intersect :292-354,
-// skybox::getFColor :1146-1166, rgbToInt :546-556). How it is computed is not
-// the reference's one-thread-per-pixel brute force:
+// What is computed is the reference's `rayTrace` kernel (kernel.cu:1614-1690 and callees: castRay :1287-1431,
+// castLightRay :1432-1544, sphere::intersect :292-354, skybox::getFColor :1146-1166, rgbToInt :546-556). How it is
+// computed is not the reference's one-thread-per-pixel brute force:
 //
 //   * one wave64 owns a TW x (64/TW) pixel tile and is its own workgroup; the sphere
 //     tables {cx,cy,cz,radius^2} stay in global memory (L2-resident) and only the
@@ -16,7 +21,7 @@
 //     reads the same list entry (LDS broadcast);
 //   * every value that decides a pixel (the quadratic, sqrt, divisions, the
 //     shadow-sample construction) is evaluated with exactly the reference's
-//     IEEE binary32/binary64 operations -- this file is compiled with
+//     IEEE binary32/binary64 operations -- the library is compiled with
 //     -ffp-contract=off and correctly rounded divide/sqrt; only the culling
 //     bounds use fast approximate math, and they are padded so that a culled
 //     sphere is one whose exact test would have returned false;
@@ -24,19 +29,10 @@
 //
 // A sphere skipped by culling can never change the closest hit (it is not hit)
 // nor an any-hit result, and survivors keep their list order, so first-index-
-//
-// This file is the DEVICE side of the frame kernel, included by the translation units that instantiate it
-// (rt_kernels.hip: default tile, tables in global memory, culling kernels + the diagnostics; rt_kernels_brute.hip:
-// the same tile, brute-force loops; rt_kernels_tiles.hip: the other tile shapes) -- one code object, compiled in
-// parallel.
-#pragma once
 // wins ties (kernel.cu:1335) resolve identically: the output is bit-identical
 // to the brute-force loops (template CULL=false), which tests check.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "rt_device.h"
-#include "rt_math.h"
+#pragma once
+#include "rt_shadow.h"
 
 // Timing experiments (RT_ABLATE) exist in tuning builds only (make EXTRA=-DRT_TUNING, tools/variants.sh):
 // the product kernel has no such switch and the product library reads no environment.
@@ -48,1211 +44,22 @@
 
 namespace {
 
-// RtFrameAux is read through the CONSTANT address space: the memory does not change while a
-// kernel runs, and a load from a wave-uniform address there is a scalar load (s_load into
-// SGPRs) wherever it stands -- as a plain global pointer the compiler has to assume the
-// kernel's own stores may alias it and uses per-lane vector loads into VGPRs.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const RtFrameAux __attribute__((address_space(4))) *AuxPtr;
-typedef const RtFrameConsts __attribute__((address_space(4))) *FcPtr;
-typedef const int __attribute__((address_space(4))) *ConstIntPtr;
-#else
-typedef const int *ConstIntPtr;
-typedef const RtFrameAux *AuxPtr;   // host pass over this translation unit (device functions are only parsed there)
-typedef const RtFrameConsts *FcPtr;
-#endif
-
-struct V3 {
-    float x, y, z;
-};
-
-// ---------------------------------------------------------------------------
-// wave64 helpers
-// ---------------------------------------------------------------------------
-// Wave-wide reductions on the VALU's DPP path (no LDS round trips): butterfly
-// inside each row of 16 lanes, then row_bcast:15 / row_bcast:31 carry the row
-// results upward so that lane 63 holds the reduction, which is broadcast back
-// through an SGPR (only lane 63 is meaningful after the broadcast steps, which run on all
-// rows: lanes without a source get `old`). All 64 lanes must be active (callers are in
-// uniform control flow). `old` is the operation's identity, so that the compiler folds each
-// move into the operation (one v_max_u32_dpp / v_add_f32_dpp per step, nothing to canonicalise).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_move0(int v)
-{
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false);
-}
-// max over the wave of NON-NEGATIVE floats, compared as unsigned integers (same order);
-// a NaN compares above +inf and therefore survives into the result.
-__device__ __forceinline__ float wave_max(float f)
-{
-    unsigned v = __builtin_bit_cast(unsigned, f);
-#define RT_STEP(CTRL, MASK) { const unsigned m = (unsigned)dpp_move0<CTRL, MASK>((int)v); v = v > m ? v : m; }
-    RT_STEP(0xB1, 0xf)    /* quad_perm [1,0,3,2]  */
-    RT_STEP(0x4E, 0xf)    /* quad_perm [2,3,0,1]  */
-    RT_STEP(0x141, 0xf)   /* row_half_mirror      */
-    RT_STEP(0x140, 0xf)   /* row_mirror           */
-    RT_STEP(0x142, 0xf)   /* row_bcast:15 -> rows 1,3 */
-    RT_STEP(0x143, 0xf)   /* row_bcast:31 -> rows 2,3 */
-#undef RT_STEP
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)v, 63));
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-#define RT_STEP(CTRL, MASK) v = v + __builtin_bit_cast(float, dpp_move0<CTRL, MASK>(__builtin_bit_cast(int, v)));
-    RT_STEP(0xB1, 0xf) RT_STEP(0x4E, 0xf) RT_STEP(0x141, 0xf) RT_STEP(0x140, 0xf) RT_STEP(0x142, 0xf) RT_STEP(0x143, 0xf)
-#undef RT_STEP
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-// three sums at once, their steps interleaved (a DPP read needs two wait states after the
-// write of its source: with three chains in flight no s_nop is needed)
-__device__ __forceinline__ void wave_sum3(float &a, float &b, float &c)
-{
-#define RT_STEP(CTRL, MASK)                                                                    \
-    {                                                                                          \
-        const float ta = __builtin_bit_cast(float, dpp_move0<CTRL, MASK>(__builtin_bit_cast(int, a))); \
-        const float tb = __builtin_bit_cast(float, dpp_move0<CTRL, MASK>(__builtin_bit_cast(int, b))); \
-        const float tc = __builtin_bit_cast(float, dpp_move0<CTRL, MASK>(__builtin_bit_cast(int, c))); \
-        a = a + ta; b = b + tb; c = c + tc;                                                    \
-    }
-    RT_STEP(0xB1, 0xf) RT_STEP(0x4E, 0xf) RT_STEP(0x141, 0xf) RT_STEP(0x140, 0xf) RT_STEP(0x142, 0xf) RT_STEP(0x143, 0xf)
-#undef RT_STEP
-    a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), 63));
-    b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, b), 63));
-    c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), 63));
-}
-// Votes on `bool` (an i1 for the compiler: the compare's own lane mask). HIP's __ballot / __any / __all take an `int`:
-// any predicate that is more than a single compare is first made a 0/1 vector register and compared against zero
-// again -- two instructions of the slow issue class per vote, and the frame kernel votes a hundred times per tile.
-// Cheaper still where it is hot: LM(one comparison) is that compare's own result register, masks combine with scalar
-// and/or/andn2, and lane_in(mask) hands a wave-uniform mask back to the lanes as a condition (selects and branches take
-// it as it is). The compiler lowers a ballot of anything BUT a single compare -- `a & b`, a flag carried round a loop --
-// through a 0/1 vector register (v_cndmask + v_cmp_ne, both of the half-rate issue class): thirty such pairs per tile.
-typedef unsigned long long lmask;
-#define LM(compare) __builtin_amdgcn_ballot_w64(compare)
-__device__ __forceinline__ bool lane_in(lmask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
-__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-__device__ __forceinline__ bool any64(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
-__device__ __forceinline__ bool all64(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; }   // (inactive lanes vote 0)
-__device__ __forceinline__ float uniform(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ int lane_prefix(unsigned long long mask)
-{
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-}
-// Lanes of one wave exchange data through LDS without a workgroup barrier.
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ---------------------------------------------------------------------------
-// exact (reference-order) vector helpers, kernel.cu:46-108
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float dot3(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-
-// normalise(vec3d&): l = sqrtf(dot); if (l != 0) v /= l (in place) and return it,
-// else return (0,0,0) leaving v alone. The reference divides in binary64 and
-// narrows; for binary32 operands that equals the correctly rounded binary32
-// quotient (53 >= 2*24+2), so a float division reproduces it bit for bit.
-__device__ __forceinline__ V3 normalise_inplace(V3 &v)
-{
-    const float l = __builtin_sqrtf(dot3(v, v));
-    if (l != 0.f) {
-        v.x = v.x / l;
-        v.y = v.y / l;
-        v.z = v.z / l;
-        return v;
-    }
-    return V3{0.f, 0.f, 0.f};
-}
-
-// ---------------------------------------------------------------------------
-// The same normalise() -- and the same correctly rounded binary32 square root --
-// without the instructions that only matter outside the ordinary range.
-//
-// hipcc expands an IEEE `a / b` into v_div_scale (x2), v_rcp, four FMAs, a multiply,
-// v_div_fmas and v_div_fixup, and an IEEE sqrtf into a pre-scaling select, v_sqrt, the
-// one-ulp-down / one-ulp-up residual test and a class fix-up (see the disassembly of
-// normalise_inplace above: 55 instructions). Pre-scaling and fix-up only act on
-// denormal, huge, zero, infinite or NaN operands; for operands in an ordinary range
-// v_div_scale returns its operand unchanged and clears VCC, v_div_fmas is then a plain
-// FMA and v_div_fixup returns its first operand. The division below is that expansion
-// with exactly these no-ops left out -- every remaining instruction is the one the full
-// expansion executes, on the same operands -- and the reciprocal refinement (which
-// depends on the divisor only) shared by the three quotients; lean_sqrt() is the
-// compiler's OTHER correctly rounded square root (see there), verified against sqrtf on
-// every float of its range. Lanes outside the safe range take the full IEEE expansion:
-//   every component >= 2^-48 in magnitude (so dot >= 2^-96, above sqrt's pre-scaling
-//   threshold, no quotient below 2^-68, no numerator the scaling would touch) and
-//   dot <= 2^40.
-// A zero component is "unsafe" (the lean sequence would lose the sign of -0).
-// tests/test_gpu_parity.py compares both functions with the IEEE ones exhaustively
-// (sqrt: every float of the range) and on 2^28 random vectors; the brute-force and
-// force-slow kernels keep the IEEE forms, so every cull-vs-brute comparison checks
-// them against each other as well.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float lean_sqrt(float x)   // x in [2^-96, 2^126]
-{
-    // The compiler's expansion of a correctly rounded binary32 square root for results that cannot be denormal:
-    // reciprocal square root, one coupled Newton step for the root and half its reciprocal, one residual correction --
-    // one transcendental and seven multiply(-add)s of the cheap issue class. (Round 2 used its other expansion -- v_sqrt,
-    // the neighbours one ulp down and up, two residuals, two compares, two selects -- whose compares and selects issue at
-    // half that rate.) Equal to sqrtf on EVERY float of [2^-96, 2^40]: rt_debug_shortcuts(1).
-    const float r = __builtin_amdgcn_rsqf(x);
-    float g = x * r;
-    float h = 0.5f * r;
-    const float e = __builtin_fmaf(-h, g, 0.5f);
-    h = __builtin_fmaf(h, e, h);
-    g = __builtin_fmaf(g, e, g);
-    const float d = __builtin_fmaf(-g, g, x);
-    return __builtin_fmaf(d, h, g);
-}
-
-struct LeanRcp {   // the divisor-only part of the division expansion
-    float d, r;
-    __device__ __forceinline__ explicit LeanRcp(float den) : d(den)
-    {
-        const float r0 = __builtin_amdgcn_rcpf(den);
-        const float e0 = __builtin_fmaf(-den, r0, 1.f);
-        r = __builtin_fmaf(e0, r0, r0);
-    }
-    __device__ __forceinline__ float divide(float n) const
-    {
-        const float q0 = n * r;
-        const float e1 = __builtin_fmaf(-d, q0, n);
-        const float q1 = __builtin_fmaf(e1, r, q0);
-        const float e2 = __builtin_fmaf(-d, q1, n);
-        return __builtin_fmaf(e2, r, q1);
-    }
-};
-
-// PREC: 0 = the IEEE forms as hipcc expands them, 1 = lean (the same bits, see above), 2 = FAST: the opt-in
-// approximate mode of rt_launch_opts.fast (hardware reciprocal square root / reciprocal / square root,
-// binary32 trigonometry, FMA contraction) -- NOT bit-exact; north_star's tolerance is 1e-5 relative per
-// channel away from the discrete decisions (a shadow sample, a texel, a silhouette), see DESIGN.md section 4c.
-template <int PREC>
-__device__ __forceinline__ V3 normalise_t(V3 &v)
-{
-    if constexpr (PREC == 0) {
-        return normalise_inplace(v);
-    } else if constexpr (PREC == 2) {
-        const float d2 = __builtin_fmaf(v.x, v.x, __builtin_fmaf(v.y, v.y, v.z * v.z));
-        if (d2 > 0.f) {   // a zero vector stays as it is and (0,0,0) is returned, as normalise() does
-            const float inv = __builtin_amdgcn_rsqf(d2);
-            v.x *= inv; v.y *= inv; v.z *= inv;
-            return v;
-        }
-        return V3{0.f, 0.f, 0.f};
-    } else {
-        const float d2 = dot3(v, v);
-        const float amin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), __builtin_fabsf(v.z));
-        const bool safe = (amin >= 0x1.0p-48f) & (d2 <= 0x1.0p40f);   // false for a NaN anywhere
-        if (__builtin_expect(!safe, 0)) return normalise_inplace(v);
-        const LeanRcp rl(lean_sqrt(d2));
-        v.x = rl.divide(v.x);
-        v.y = rl.divide(v.y);
-        v.z = rl.divide(v.z);
-        return v;
-    }
-}
-
-// normalise() of a vector whose z component is +-0 by construction (castLightRay's rotation axis cross((0,0,1), n),
-// kernel.cu:1465): the general lean form calls a zero component unsafe (it would lose the sign of -0) and such a vector
-// would take the IEEE expansion every time. Here z*z = +0 adds nothing to (x*x + y*y) -- the same dot bit for bit -- and
-// (+-0) / l = +-0 for the positive finite l of the safe range: z stays as it is, x and y take the lean division.
-template <int PREC>
-__device__ __forceinline__ V3 normalise_z0_t(V3 &v)
-{
-    if constexpr (PREC != 1) {
-        return normalise_t<PREC>(v);
-    } else {
-        const float d2 = dot3(v, v);
-        const float amin = __builtin_fminf(__builtin_fabsf(v.x), __builtin_fabsf(v.y));
-        const bool safe = (amin >= 0x1.0p-48f) & (d2 <= 0x1.0p40f) & (v.z == 0.f);   // false for a NaN anywhere
-        if (__builtin_expect(!safe, 0)) return normalise_inplace(v);
-        const LeanRcp rl(lean_sqrt(d2));
-        v.x = rl.divide(v.x);
-        v.y = rl.divide(v.y);
-        return v;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Texel index of a unit normal without binary64: castRay's (tx, ty) (kernel.cu:1402-1403)
-// only ever select a texel, c_index = (int)(ty*maxY)*maxX + (int)(tx*maxX) (kernel.cu:1653).
-// approx_sphere_uv() evaluates tx = (1 + atan2(n.z, n.x)/3.1415)/2 and ty = acos(n.y)/3.1415
-// in binary32 with absolute error below RT_UV_DELTA (budget: quotient after one Newton step
-// 0.5 ulp, degree-8 polynomial 1.2e-8 + ~1 ulp of evaluation, all quadrant reconstruction done
-// in units of the RESULT so that no step rounds at the magnitude of pi: 1.7e-7 for tx, 2.6e-7
-// for ty; rt_debug_uv measures it on the device and tests/test_gpu_parity.py asserts half of
-// RT_UV_DELTA). A lane is "sure" when both products tx*W, ty*H stay at least
-// mu = size * (RT_UV_DELTA + 2^-22) away from every integer (the second term covers the
-// rounding of the two float products): then truncation gives the same column and row as the
-// exact value would. Unsure lanes (about 5 % of the 8x8 tiles contain one at 512x512) -- and
-// anything negative or NaN -- take the exact binary64 path.
-// ---------------------------------------------------------------------------
-#define RT_UV_DELTA 5.0e-7f
-
-// atan(a) for a in [0, 1], absolute error < 1.0e-7 (Chebyshev fit of atan(sqrt(s))/sqrt(s), degree 8 in s)
-__device__ __forceinline__ float atan01(float a)
-{
-    const float s = a * a;
-    float p = 0x1.73776ap-9f;
-    p = __builtin_fmaf(p, s, -0x1.0639f6p-6f);
-    p = __builtin_fmaf(p, s, 0x1.5ce0b0p-5f);
-    p = __builtin_fmaf(p, s, -0x1.330372p-4f);
-    p = __builtin_fmaf(p, s, 0x1.b3ae74p-4f);
-    p = __builtin_fmaf(p, s, -0x1.22de60p-3f);
-    p = __builtin_fmaf(p, s, 0x1.997232p-3f);
-    p = __builtin_fmaf(p, s, -0x1.5554a2p-2f);
-    p = __builtin_fmaf(p, s, 1.0f);
-    return a * p;
-}
-
-// angle(y, x) * scale for y >= 0 given as magnitudes: returns scale * atan2(ay, x) in [0, scale*pi],
-// reconstructed in units of the result. k_half = scale*pi/2, k_full = scale*pi (both rounded once).
-__device__ __forceinline__ float scaled_angle(float ay, float x, float scale, float k_half, float k_full)
-{
-    const float ax = __builtin_fabsf(x);
-    const float mx = __builtin_fmaxf(ax, ay), mn = __builtin_fminf(ax, ay);
-    const float r = __builtin_amdgcn_rcpf(mx);
-    const float a0 = mn * r;
-    const float a = __builtin_fmaf(__builtin_fmaf(-mx, a0, mn), r, a0);   // mn / mx to half an ulp (NaN for 0/0)
-    float u = atan01(a) * scale;
-    u = (ay > ax) ? k_half - u : u;
-    u = (x < 0.f) ? k_full - u : u;
-    return u;
-}
-
-__device__ __forceinline__ void approx_sphere_uv(V3 n, float &tx, float &ty)
-{
-    constexpr double kC = 1.0 / 3.1415, kPiD = 3.14159265358979323846;
-    // tx = 0.5 + sign(n.z) * atan2(|n.z|, n.x) / (2 * 3.1415)
-    const float u = scaled_angle(__builtin_fabsf(n.z), n.x, (float)(0.5 * kC), (float)(0.25 * kPiD * kC), (float)(0.5 * kPiD * kC));
-    tx = __builtin_signbit(n.z) ? 0.5f - u : 0.5f + u;
-    // ty = atan2(sqrt((1 - y)(1 + y)), y) / 3.1415; the root to about an ulp (one Newton step)
-    const float q = (1.f - n.y) * (1.f + n.y);
-    const float s0 = __builtin_amdgcn_sqrtf(q);
-    const float rs = __builtin_amdgcn_rsqf(q);
-    const float sy = (q > 0.f) ? __builtin_fmaf(__builtin_fmaf(-s0, s0, q), 0.5f * rs, s0) : 0.f;
-    ty = scaled_angle(sy, n.y, (float)kC, (float)(0.5 * kPiD * kC), (float)(kPiD * kC));
-    if (!(__builtin_fabsf(n.y) <= 1.f)) ty = __builtin_nanf("");   // the exact function returns NaN there
-}
-
-// Column/row selection with certainty: returns the linear index row*w + col when both products are
-// clear of every integer by the margins, else -1 (the caller evaluates the exact expressions).
-__device__ __forceinline__ int sure_texel(float tx, float ty, int w, int h, float mu_x, float mu_y)
-{
-    const float px = tx * (float)w, py = ty * (float)h;
-    const float fx = __builtin_floorf(px), fy = __builtin_floorf(py);
-    const float rx = px - fx, ry = py - fy;
-    const bool sure = (rx > mu_x) & (rx < 1.f - mu_x) & (ry > mu_y) & (ry < 1.f - mu_y) & (fx >= 0.f) & (fy >= 0.f) &
-                      (fx <= 16384.f) & (fy <= 16384.f);
-    return sure ? (int)fy * w + (int)fx : -1;
-}
-
-// float -> int of the implicit conversions at kernel.cu:1653, 1157-1158, 1682:
-// truncation toward zero, NaN -> 0, saturating (v_cvt_i32_f32 semantics, which
-// are also CUDA's cvt.rzi.s32.f32).
-__device__ __forceinline__ int f2i(float v) { return (int)v; }
-
-// b after n executions of `b += 0.1` (float += double literal, kernel.cu:1538),
-// starting from 0: depends only on how many samples were unshadowed. Literals
-// instead of a table so that a per-lane n needs no memory (a kernarg array
-// indexed per lane would live in scratch); the host re-derives the sequence and
-// refuses to launch if it ever disagreed (rt_build_frame_consts).
-__device__ __forceinline__ float brightness_steps(int n)
-{
-    float b = 0x0.0p+0f;
-    b = n >= 1 ? 0x1.99999ap-4f : b;
-    b = n >= 2 ? 0x1.99999ap-3f : b;
-    b = n >= 3 ? 0x1.333334p-2f : b;
-    b = n >= 4 ? 0x1.99999ap-2f : b;
-    b = n >= 5 ? 0x1.000000p-1f : b;
-    b = n >= 6 ? 0x1.333334p-1f : b;
-    b = n >= 7 ? 0x1.666668p-1f : b;
-    b = n >= 8 ? 0x1.99999cp-1f : b;
-    b = n >= 9 ? 0x1.ccccd0p-1f : b;
-    b = n >= 10 ? 0x1.000002p+0f : b;
-    return b;
-}
-
-// The same eleven values for per-lane lookups (copied into LDS once per wave).
-__device__ const float kBrightnessSteps[16] = {0x0.0p+0f,      0x1.99999ap-4f, 0x1.99999ap-3f, 0x1.333334p-2f,
-                                               0x1.99999ap-2f, 0x1.000000p-1f, 0x1.333334p-1f, 0x1.666668p-1f,
-                                               0x1.99999cp-1f, 0x1.ccccd0p-1f, 0x1.000002p+0f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-// rtm::atan_eighth(0..8), for the same purpose (values checked against the function by
-// tests/test_gpu_parity.py through the math debug ops, which use the LDS copy as well).
-__device__ const double kAtanEighth[16] = {0x0.0p+0,
-                                           0x1.fd5ba9aac2f6ep-4,
-                                           0x1.f5b75f92c80ddp-3,
-                                           0x1.6f61941e4def1p-2,
-                                           0x1.dac670561bb4fp-2,
-                                           0x1.1e00babdefeb4p-1,
-                                           0x1.4978fa3269ee1p-1,
-                                           0x1.700a7c5784634p-1,
-                                           0x1.921fb54442d18p-1,
-                                           0, 0, 0, 0, 0, 0, 0};
-
-// rgbToInt, kernel.cu:547-556
-__device__ __forceinline__ unsigned rgb_to_int(int r, int g, int b)
-{
-    if (r > 255) r = 255;
-    if (g > 255) g = 255;
-    if (b > 255) b = 255;
-    return (unsigned)(((r & 0xff) << 16) + ((g & 0xff) << 8) + (b & 0xff));
-}
-
-// ---------------------------------------------------------------------------
-// sphere::intersect, kernel.cu:293-354, on a table entry {cx,cy,cz,radius*radius}
-// ---------------------------------------------------------------------------
-struct RayK {          // a ray plus the one per-ray constant of the quadratic that every test needs
-    float ox, oy, oz;
-    float dx, dy, dz;
-    float a4;          // 4*A (kernel.cu:334: B*B - 4*A*C)
-    // 2*A, the divisor of both roots, only where a root is actually formed (the same expression on the same operands)
-    __device__ __forceinline__ float a2() const { return 2.f * ((dx * dx + dy * dy) + dz * dz); }
-};
-
-__device__ __forceinline__ RayK make_ray(V3 o, V3 d)
-{
-    RayK r;
-    r.ox = o.x; r.oy = o.y; r.oz = o.z;
-    r.dx = d.x; r.dy = d.y; r.dz = d.z;
-    const float A = (d.x * d.x + d.y * d.y) + d.z * d.z;
-    r.a4 = 4.f * A;
-    return r;
-}
-
-struct Quad {  // B, B*B and the discriminant, in the reference's evaluation order
-    float h, B, BB, disc;
-};
-
-__device__ __forceinline__ Quad quadratic(const RayK &r, float4 s)
-{
-    const float ocx = r.ox - s.x, ocy = r.oy - s.y, ocz = r.oz - s.z;
-    Quad q;
-    q.h = (r.dx * ocx + r.dy * ocy) + r.dz * ocz;
-    q.B = 2.f * q.h;
-    const float C = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.w;
-    q.BB = q.B * q.B;
-    q.disc = q.BB - r.a4 * C;
-    return q;
-}
-
-// FAST mode: the same quadratic with fused multiply-adds (11 instructions instead of 17)
-__device__ __forceinline__ Quad quadratic_fast(const RayK &r, float4 s)
-{
-    const float ocx = r.ox - s.x, ocy = r.oy - s.y, ocz = r.oz - s.z;
-    Quad q;
-    q.h = __builtin_fmaf(r.dx, ocx, __builtin_fmaf(r.dy, ocy, r.dz * ocz));
-    q.B = 2.f * q.h;
-    const float C = __builtin_fmaf(ocx, ocx, __builtin_fmaf(ocy, ocy, __builtin_fmaf(ocz, ocz, -s.w)));
-    q.BB = q.B * q.B;
-    q.disc = __builtin_fmaf(-r.a4, C, q.BB);
-    return q;
-}
-
-// The tail of intersect once B and the discriminant are known.
-__device__ __forceinline__ bool intersect_tail(const RayK &r, const Quad &q, float &t)
-{
-    const float sq = __builtin_sqrtf(q.disc);
-    const float a2 = r.a2();
-    t = (-q.B + sq) / a2;
-    if (t == 0.f) return true;
-    if (t >= RT_T_MIN) {
-        const float t2 = (-q.B - sq) / a2;
-        if (t > t2) t = t2;
-        return true;
-    }
-    return false;
-}
-
-// The same tail with the lean square root and the lean divisions (see normalise_t above; both roots
-// divide by the same 2A, so the divisor's part of the expansion is shared). Safe range, per lane:
-// disc in [2^-96, 2^60], 2A in [2^-20, 2^20], both numerators between 2^-40 and 2^40 in magnitude --
-// anything else (a zero numerator in particular: the reference's `t == 0` clause) takes the IEEE forms.
-template <int PREC>
-__device__ __forceinline__ bool intersect_tail_t(const RayK &r, const Quad &q, float &t)
-{
-    if constexpr (PREC == 0) {
-        return intersect_tail(r, q, t);
-    } else if constexpr (PREC == 2) {
-        const float sq = __builtin_amdgcn_sqrtf(q.disc);
-        const float inv = __builtin_amdgcn_rcpf(r.a2());
-        t = (-q.B + sq) * inv;
-        if (t == 0.f) return true;
-        if (t >= RT_T_MIN) {
-            const float t2 = (-q.B - sq) * inv;
-            if (t > t2) t = t2;
-            return true;
-        }
-        return false;
-    } else {
-        const float nb = -q.B, a2 = r.a2();
-        const bool pre = (q.disc >= 0x1.0p-96f) & (q.disc <= 0x1.0p60f) & (a2 >= 0x1.0p-20f) & (a2 <= 0x1.0p20f);
-        if (__builtin_expect(!pre, 0)) return intersect_tail(r, q, t);
-        const float sq = lean_sqrt(q.disc);
-        const float n1 = nb + sq, n2 = nb - sq;
-        const bool safe = (__builtin_fminf(__builtin_fabsf(n1), __builtin_fabsf(n2)) >= 0x1.0p-40f) &
-                          (__builtin_fmaxf(__builtin_fabsf(n1), __builtin_fabsf(n2)) <= 0x1.0p40f);
-        if (__builtin_expect(!safe, 0)) return intersect_tail(r, q, t);
-        const LeanRcp ra(a2);
-        t = ra.divide(n1);
-        if (t >= RT_T_MIN) {           // t == 0 cannot happen here: |n1| >= 2^-40 and 2A <= 2^20
-            const float t2 = ra.divide(n2);
-            if (t > t2) t = t2;
-            return true;
-        }
-        return false;
-    }
-}
-
-
-// plane::intersect, kernel.cu:370-380
-__device__ __forceinline__ bool plane_intersect(const RtPlaneDev &p, V3 o, V3 d, float &t)
-{
-    const float denom = (p.nx * d.x + p.ny * d.y) + p.nz * d.z;
-    if (denom < 0.f) {
-        const V3 pl0{p.ox - o.x, p.oy - o.y, p.oz - o.z};
-        t = ((pl0.x * p.nx + pl0.y * p.ny) + pl0.z * p.nz) / denom;
-        return t >= 0.f;
-    }
-    return false;
-}
-
-// cube::intersect, kernel.cu:457-485. min/max are the reference's macros
-// (kernel.cu:16-26), whose NaN behaviour differs from fminf/fmaxf. `inv` is
-// 1.f / Dir per component, hoisted out of the per-cube call.
-#define RT_MAXM(a, b) (((a) > (b)) ? (a) : (b))
-#define RT_MINM(a, b) (((a) < (b)) ? (a) : (b))
-__device__ __forceinline__ bool cube_intersect(const RtCubeDev &c, V3 o, V3 inv, float &t)
-{
-    const float t1 = (c.ax - o.x) * inv.x, t2 = (c.bx - o.x) * inv.x;
-    const float t3 = (c.ay - o.y) * inv.y, t4 = (c.by - o.y) * inv.y;
-    const float t5 = (c.az - o.z) * inv.z, t6 = (c.bz - o.z) * inv.z;
-    const float tmin = RT_MAXM(RT_MAXM(RT_MINM(t1, t2), RT_MINM(t3, t4)), RT_MINM(t5, t6));
-    const float tmax = RT_MINM(RT_MINM(RT_MAXM(t1, t2), RT_MAXM(t3, t4)), RT_MAXM(t5, t6));
-    if (tmax < 0.f) { t = tmax; return false; }
-    if (tmax < tmin) { t = tmax; return false; }
-    t = tmin;
-    return true;
-}
-
-// mesh::rayIntersect (Moller-Trumbore), kernel.cu:1024-1059. The two double
-// literals there (`a < 0.0000001`, `t > 0.0000001`) compare the widened float
-// with 1e-7; 1e-7f is the smallest binary32 >= 1e-7, so `a < 1e-7f` and
-// `t >= 1e-7f` are the same predicates.
-__device__ __forceinline__ bool tri_intersect(V3 o, V3 d, const float *p0, const float *p1, const float *p2,
-                                              float &t, float &u, float &v)
-{
-    const V3 e1{p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-    const V3 e2{p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-    const V3 h{d.y * e2.z - d.z * e2.y, d.z * e2.x - d.x * e2.z, d.x * e2.y - d.y * e2.x};
-    const float a = dot3(e1, h);
-    if (a > -0.0000001f && a < 0.0000001f) return false;
-    const float f = 1.f / a;
-    const V3 s{o.x - p0[0], o.y - p0[1], o.z - p0[2]};
-    u = f * dot3(s, h);
-    if (u < 0.f || u > 1.f) return false;
-    const V3 q{s.y * e1.z - s.z * e1.y, s.z * e1.x - s.x * e1.z, s.x * e1.y - s.y * e1.x};
-    v = f * dot3(d, q);
-    if (v < 0.f || u + v > 1.f) return false;
-    t = f * dot3(e2, q);
-    return t >= 0.0000001f;
-}
-
-__device__ __forceinline__ bool box_intersect(const RtBoxDev &b, V3 o, V3 inv)
-{
-    RtCubeDev c;
-    c.ax = b.lo[0]; c.ay = b.lo[1]; c.az = b.lo[2];
-    c.bx = b.hi[0]; c.by = b.hi[1]; c.bz = b.hi[2];
-    float t;
-    return cube_intersect(c, o, inv, t);
-}
-
-// A ray that starts outside a sphere whose centre lies behind it has B > 0 and
-// disc < B*B; then sqrt(disc) < B, t < 0 strictly and intersect() is false. The
-// factor keeps sqrt(disc) below B even after rounding, so the `t == 0` clause
-// (kernel.cu:338) cannot fire. Purely a shortcut: when in doubt the full tail runs.
-#define RT_BEHIND_FACTOR 0.99999f
-
-// ---------------------------------------------------------------------------
-// conservative culling
-// ---------------------------------------------------------------------------
-struct Beam {        // all members wave-uniform
-    float ax, ay, az;   // a point on the axis
-    float ux, uy, uz;   // unit axis
-    float smin;         // rays start at axial coordinate >= smin
-    float smax;         // ... and <= smax (used only by the full-occluder test)
-    float r0;           // ... within r0 of the axis
-    float k;            // and spread with slope k = tan(theta)
-};
-
-// Keep sphere s unless no ray inside the beam can make intersect() return true.
-// intersect() is true only if the float discriminant is >= 0, which (rounding
-// included) needs the ray's line within sqrt(R^2 + eps*(1+|oc|^2)) of the centre
-// (R^2 = s.w is the squared effective radius), and a far root >= 0.
-__device__ __forceinline__ lmask beam_keeps(const Beam &b, float4 s)
-{
-    const float vx = s.x - b.ax, vy = s.y - b.ay, vz = s.z - b.az;
-    const float vv = __builtin_fmaf(vx, vx, __builtin_fmaf(vy, vy, vz * vz));
-    const float sa = __builtin_fmaf(vx, b.ux, __builtin_fmaf(vy, b.uy, vz * b.uz));
-    const float d2 = __builtin_fmaxf(__builtin_fmaf(-sa, sa, vv), 0.f);
-    // padded radius: rounding noise of the exact test + slack of this test
-    const float rc2 = s.w + __builtin_fmaf(RT_PAD_REL, vv, RT_PAD_ABS);
-    const float rc = __builtin_amdgcn_sqrtf(rc2) * 1.0001f;
-    const float reach = sa + rc - b.smin;
-    const float rad = __builtin_fmaf(b.k, __builtin_fmaxf(reach, 0.f), b.r0) + rc;
-    return LM(reach >= 0.f) & LM(d2 <= rad * rad * 1.0005f);
-}
-
-// A block of the Morton-ordered table: {centre, radius} of a sphere containing all
-// of its members (host side, rounded up). A member passes beam_keeps() only if
-// the block passes this test: the block's padded radius covers the member's
-// centre offset, its radius and its own padding sqrt(4e-5*|v|^2 + 1e-3)
-// (<= 6.4e-3*|v| + 0.032 with |v| <= |v_block| + r_block).
-__device__ __forceinline__ lmask beam_keeps_block(const Beam &b, float4 blk)
-{
-    const float vx = blk.x - b.ax, vy = blk.y - b.ay, vz = blk.z - b.az;
-    const float vv = __builtin_fmaf(vx, vx, __builtin_fmaf(vy, vy, vz * vz));
-    const float sa = __builtin_fmaf(vx, b.ux, __builtin_fmaf(vy, b.uy, vz * b.uz));
-    const float d2 = __builtin_fmaxf(__builtin_fmaf(-sa, sa, vv), 0.f);
-    const float dist = __builtin_amdgcn_sqrtf(vv) * 1.0001f;
-    const float rc = __builtin_fmaf(RT_BLK_PAD_REL, dist + blk.w, blk.w) + RT_BLK_PAD_ABS;
-    const float reach = sa + rc - b.smin;
-    const float rad = __builtin_fmaf(b.k, __builtin_fmaxf(reach, 0.f), b.r0) + rc;
-    return LM(!(reach < 0.f)) & LM(!(d2 > rad * rad * 1.0005f));   // NaN / inf bounds keep the block
-}
-
-// A column block of a light's table (RtFrameConsts::lsorted/lblocks): blkA = {point c on the
-// column's axis, lateral radius rho}, blkB = {s_hi, r3d, -, -}. A member j passes
-// beam_member_test() only if its block passes this test: its axial coordinate plus radius is
-// at most (c - a).u + s_hi, its centre lies within rho - R_j of the column's axis, and its
-// padding sqrt(4e-5 |v_j|^2 + 1e-3) <= 6.4e-3 |v_j| + 0.032 with |v_j| <= |c - a| + r3d.
-// Only valid for beams whose axis is the light's u (all shadow beams are).
-__device__ __forceinline__ lmask beam_keeps_column(const Beam &b, float4 blkA, float4 blkB)
-{
-    const float vx = blkA.x - b.ax, vy = blkA.y - b.ay, vz = blkA.z - b.az;
-    const float vv = __builtin_fmaf(vx, vx, __builtin_fmaf(vy, vy, vz * vz));
-    const float sa = __builtin_fmaf(vx, b.ux, __builtin_fmaf(vy, b.uy, vz * b.uz));
-    const float d2 = __builtin_fmaxf(__builtin_fmaf(-sa, sa, vv), 0.f);
-    const float dist = __builtin_amdgcn_sqrtf(vv) * 1.0001f;
-    const float pad = __builtin_fmaf(RT_BLK_PAD_REL, dist + blkB.y, RT_BLK_PAD_ABS);
-    const float reach = sa + blkB.x + pad - b.smin;
-    const float rad = __builtin_fmaf(b.k, __builtin_fmaxf(reach, 0.f), b.r0) + blkA.w + pad;
-    return LM(!(reach < 0.f)) & LM(!(d2 > rad * rad * 1.001f));   // NaN / inf bounds keep the block
-}
-
-// An entry of the list being walked: the wave's survivor list, or the whole table.
-__device__ __forceinline__ float4 entry_at(bool use_list, const float4 *list, const float4 *__restrict__ gl_tab, int e)
-{
-    if (use_list) return list[e];
-    return gl_tab[e];
-}
-
-// The member test of the culling loop: beam_keeps(), and with OCCL the question whether the
-// sphere occludes the whole beam, in one straight line -- the two share |v|^2, the axial
-// coordinate and the distance from the axis, and written with short-circuit conditions the
-// compiler wraps every clause in its own exec-mask region (a third of the loop's instructions).
-// `blocked`, only meaningful for kept entries:
-// Sphere s certainly occludes EVERY ray of the beam: it lies entirely ahead of all
-// ray origins, and the beam's cross-section at the centre's axial coordinate --
-// radius r0 + k*(sa - smin) around the axis, both already padded -- sits inside
-// the sphere shrunk by the same rounding allowance the cull test adds. Each ray
-// then passes within that shrunken radius of the centre in its forward direction,
-// so the exact float test has disc > 0 and h far below -h_sure: it returns true.
-template <bool OCCL>
-__device__ __forceinline__ lmask beam_member_test(const Beam &b, float4 s, lmask enable, lmask &blocked)
-{
-    const float vx = s.x - b.ax, vy = s.y - b.ay, vz = s.z - b.az;
-    const float vv = __builtin_fmaf(vx, vx, __builtin_fmaf(vy, vy, vz * vz));
-    const float sa = __builtin_fmaf(vx, b.ux, __builtin_fmaf(vy, b.uy, vz * b.uz));
-    const float d2 = __builtin_fmaxf(__builtin_fmaf(-sa, sa, vv), 0.f);
-    const float pad = __builtin_fmaf(RT_PAD_REL, vv, RT_PAD_ABS);
-    const float rc = __builtin_amdgcn_sqrtf(s.w + pad) * 1.0001f;
-    const float reach = sa + rc - b.smin;
-    const float rad = __builtin_fmaf(b.k, __builtin_fmaxf(reach, 0.f), b.r0) + rc;
-    const lmask keep = enable & LM(reach >= 0.f) & LM(d2 <= rad * rad * 1.0005f);
-    if (OCCL) {
-        const float r2b = s.w - pad;                                       // shrunken radius^2
-        const float rr = __builtin_amdgcn_sqrtf(s.w);
-        const lmask ahead = LM((sa - b.smax) >= __builtin_fmaf(rr, 1.001f, 0.01f));
-        const float rho = __builtin_fmaf(b.k, sa - b.smin, b.r0);
-        // (d2 = |v|^2 - (v.u)^2 carries a cancellation error of up to 3 eps |v|^2: its root is taken of an upper bound)
-        const float lhs = __builtin_fmaf(__builtin_amdgcn_sqrtf(__builtin_fmaf(2.0e-7f, vv, d2)) + rho, 1.001f, 1.0e-4f);
-        blocked |= keep & ahead & LM(r2b > 0.f) & LM(lhs * lhs <= r2b);
-    }
-    return keep;
-}
-
-// Two-level cull over an ordered copy of the table: the blocks of RT_BLOCK the beam can touch,
-// then their members (64/RT_BLOCK blocks per step). Survivors come out in the table's order,
-// which is fine for an any-hit; for the primary rays (ORDERED) their list positions are
-// carried along in keys[] and the short list is re-ordered front to back (see below), ties
-// between equal t being settled by those positions (kernel.cu:1335). Returns the survivor
-// count (with OCCL, bit 30 flags "one sphere occludes the whole beam"); a count above
-// RT_LIST_CAP tells the caller to walk the whole table instead.
-// BLOCKS selects the first level: 0 = cubes of the 3-D order (fc.sorted/fc.blocks), 1 = a
-// light's columns, 2 = eye cones (the last two: csorted/cblocks/corig, read from global memory).
-template <int STATS, bool OCCL, bool ORDERED, int BLOCKS = 0, typename FC = RtFrameConsts>
-__device__ __forceinline__ int build_list2(const FC &fc, int n, float4 *list, int *keys,
-                                           int *blist, const Beam &b, int lane, unsigned long long &n_cull,
-                                           const float4 *__restrict__ csorted = nullptr,
-                                           const float4 *__restrict__ cblocks = nullptr,
-                                           const int *__restrict__ corig = nullptr, bool stop_when_blocked = false)
-{
-    constexpr bool COLUMNS = BLOCKS != 0;   // two float4 per block, table in global memory
-    const float4 *__restrict__ gsorted = COLUMNS ? csorted : reinterpret_cast<const float4 *>(fc.sorted);
-    const float4 *__restrict__ gblocks = COLUMNS ? cblocks : reinterpret_cast<const float4 *>(fc.blocks);
-    const int *__restrict__ gorig = COLUMNS ? corig : fc.orig_idx;
-    // eye cones: cos and sin of the beam's own half-angle (slope padded as in the host's bound)
-    float cone_cw = 1.f, cone_sw = 0.f;
-    if (BLOCKS == 2) {
-        const float kw = b.k * 1.001f;
-        cone_cw = __builtin_amdgcn_rsqf(__builtin_fmaf(kw, kw, 1.f));
-        cone_sw = kw * cone_cw;
-    }
-    const int nb = fc.n_blocks;
-    int count = 0;
-    lmask blk = 0;
-    constexpr int G = 64 / RT_BLOCK;           // blocks examined side by side in one step
-    const int grp = lane / RT_BLOCK, sub = lane % RT_BLOCK;
-    for (int bbase = 0; bbase < nb; bbase += 64) {
-        const int bi = bbase + lane;
-        const int bc = bi < nb ? bi : nb - 1;
-        lmask bm;
-        if (BLOCKS == 2) {
-            // angle(axis, beam axis) <= theta + theta_beam, both below pi (build_eye_cones)
-            const float4 ba = gblocks[2 * bc], bbx = gblocks[2 * bc + 1];
-            const float dotp = __builtin_fmaf(ba.x, b.ux, __builtin_fmaf(ba.y, b.uy, ba.z * b.uz));
-            const float rhs = __builtin_fmaf(ba.w, cone_cw, -bbx.x * cone_sw) - 2.0e-5f;   // cos(theta + theta_beam)
-            const lmask inside = LM(!(dotp < rhs));                                            // NaN keeps the block
-            bm = LM(bi < nb) & LM(bbx.y >= 0.f) & (LM(bbx.y > 0.f) | inside);
-        } else if (BLOCKS == 1) {
-            const float4 ba = gblocks[2 * bc], bbx = gblocks[2 * bc + 1];
-            bm = LM(bi < nb) & LM(!(ba.w < 0.f)) & beam_keeps_column(b, ba, bbx);
-        } else {
-            const float4 bb = gblocks[bc];
-            bm = LM(bi < nb) & LM(!(bb.w < 0.f)) & beam_keeps_block(b, bb);   // w < 0: padding block
-        }
-        if (STATS == 1) n_cull += 64;
-        // the marked blocks, compacted into the wave's block list; then G of them per step,
-        // one per group of RT_BLOCK lanes (next step's block number read one step ahead)
-        const int marked = __popcll(bm);
-        if (lane_in(bm)) blist[lane_prefix(bm)] = bi;
-        wave_lds_sync();
-        int cur = (grp < marked) ? blist[grp] : -1;
-        for (int t = 0; t < marked; t += G) {
-            const int nslot = t + G + grp;
-            const int nxt = (nslot < marked) ? blist[nslot] : -1;
-            const int i = (cur < 0 ? 0 : cur) * RT_BLOCK + sub;   // inside the padded table
-            const float4 s = gsorted[i];
-            const lmask m = beam_member_test<OCCL>(b, s, LM(cur >= 0) & LM(i < n), blk);
-            const int pos = count + lane_prefix(m);
-            if (lane_in(m) && pos < RT_LIST_CAP) {
-                list[pos] = s;
-                if (ORDERED) keys[pos] = gorig[i];
-            }
-            count += __popcll(m);
-            if (STATS == 1) n_cull += 64;
-            cur = nxt;
-            // the caller only wants to know whether one sphere occludes the whole beam, and one does:
-            // the rest of the list is of no interest (the light adds nothing)
-            if (OCCL && stop_when_blocked && blk != 0) {
-                wave_lds_sync();
-                return count | 0x40000000;
-            }
-        }
-        if (bbase + 64 < nb) wave_lds_sync();   // the next 64 blocks reuse the block list
-    }
-    wave_lds_sync();
-    if (ORDERED) {
-        if (count > 64) {
-            count = RT_LIST_CAP + 1;     // too long to reorder in one step: caller walks the table
-        } else if (count > 1) {
-            // Front to back: the list is ordered by a LOWER BOUND of any t the entry can return
-            // to a ray from the apex (|D| = 1): dist - R outside the sphere, -(dist + R) inside
-            // (the near root is what intersect() returns), less an allowance for the float
-            // evaluation. That allowance is set by grazing rays: B^2 - 4AC is formed with an
-            // absolute error of about 12 ulp(dist^2) = 3e-6 dist^2, so sqrt(disc) -- and with it
-            // the near root -- can be off by sqrt(7.5e-7) dist = 8.7e-4 dist where the exact
-            // discriminant vanishes (where it does not, the error is far smaller and the exact
-            // root exceeds dist - R by up to R): 1e-3 + 1.5e-3 (dist + R) covers both cases.
-            // The caller stops as soon as every lane's nearest hit lies
-            // strictly below the next entry's bound; ties between equal t are resolved by the
-            // list positions in keys[] (first index wins, kernel.cu:1335), so the order of
-            // evaluation does not matter. The bounds go where the block list was (<= 64 entries).
-            float *lbs = reinterpret_cast<float *>(blist);
-            float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-            int key = 0, rank = 0;
-            float lb = 0.f;
-            if (lane < count) {
-                e = list[lane];
-                key = keys[lane];
-                const float vx = e.x - b.ax, vy = e.y - b.ay, vz = e.z - b.az;
-                const float vv = __builtin_fmaf(vx, vx, __builtin_fmaf(vy, vy, vz * vz));
-                const float dist = __builtin_amdgcn_sqrtf(vv), rr = __builtin_amdgcn_sqrtf(e.w);
-                const float slack = __builtin_fmaf(1.5e-3f, dist + rr, 1.0e-3f);
-                lb = (vv > e.w * 1.001f + 1.0e-6f) ? (dist - rr) - slack : -(dist + rr) - slack;
-                lb = (lb == lb) ? lb : -__builtin_inff();   // non-finite entries first: they never end the walk early
-                lbs[lane] = lb;
-            }
-            wave_lds_sync();
-            for (int j = 0; j < count; ++j) {
-                const float lj = lbs[j];
-                // (ties go to the lower slot: `j < lane` is the scalar mask of the lanes above j)
-                rank += lane_in(LM(lj < lb) | (LM(lj == lb) & (~1ull << j))) ? 1 : 0;
-            }
-            wave_lds_sync();
-            if (lane < count) {
-                list[rank] = e;
-                keys[rank] = key;
-                lbs[rank] = lb;
-            }
-            wave_lds_sync();
-        }
-    }
-    if (OCCL && blk != 0) count |= 0x40000000;
-    return count;
-}
-
-// The cull of a light's table for a group of pixels whose closest hit is ONE sphere S: the entries that a shadow ray
-// from S can hit at all were listed when the scene or the light last changed (RtFrameAux::cand_hdr / cand_ent,
-// rt_tables.hip: rt_occluder_lists_kernel -- a beam of slope kcap from a ball around S; the caller has checked its own
-// slope against kcap), in table order, and only those are put to the member test -- one step per 64 of them, where the walk over the light's column blocks takes
-// a block pass and three or four member steps. Same result convention as build_list2<OCCL = true>.
-template <int STATS>
-__device__ __forceinline__ int build_list_cand(const float4 *__restrict__ ents, int n, float4 *list, const Beam &b, int lane,
-                                               unsigned long long &n_cull, bool stop_when_blocked)
-{
-    int count = 0;
-    lmask blk = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const float4 s = ents[i];                       // the entry array is padded to whole steps
-        const lmask m = beam_member_test<true>(b, s, LM(i < n), blk);
-        const int pos = count + lane_prefix(m);
-        if (lane_in(m) && pos < RT_LIST_CAP) list[pos] = s;
-        count += __popcll(m);
-        if (STATS == 1) n_cull += 64;
-        if (stop_when_blocked && blk != 0) {
-            wave_lds_sync();
-            return count | 0x40000000;
-        }
-    }
-    wave_lds_sync();
-    if (blk != 0) count |= 0x40000000;
-    return count;
-}
-
-// One triangle of a leaf against the beam, by its bounding sphere ts = {centre, radius} and tn = {unit normal, kappa}
-// (host side: rt_scene_set_mesh). Moller-Trumbore (kernel.cu:1024-1059) accepts a ray when its computed barycentrics
-// lie in the unit simplex. Their rounding errors are those of two 3x3 determinants (absolute error <= gamma |s| |e|,
-// gamma ~ 10 eps, |s| the distance from the ray origin to the first vertex) divided by a = D . (e2 x e1) =
-// |e1| |e2| sin(phi0) cos(theta_n), theta_n the angle between the ray and the normal: in the triangle's plane they
-// displace the hit point by at most 2 gamma (|s| + |e|) / (sigma |cos(theta_n)|), sigma the smallest corner sine. For a
-// ray with |cos(theta_n)| >= kappa = 3e-3 / sigma that is below 4e-4 (|s| + |e|), inside pad = 2e-3 + 1e-3 (dist + r)
-// (|s| <= dist + r, |e| <= 2 r): such a ray can only be accepted if its line comes within pad of the triangle, hence
-// of its bounding sphere. A ray that GRAZES the triangle's plane is another matter: the error grows like
-// 1 / cos(theta_n) (float Moller-Trumbore does accept rays that pass the sphere at several radii once cos(theta_n)
-// drops below 3e-4: tools/mt_grazing.py), so a triangle is only culled when every ray of the beam keeps
-// |cos(theta_n)| >= kappa, i.e. |n . u| >= (kappa + k)(1 + k) for the beam's axis u and slope k. A well-shaped
-// triangle is "edge-on" to 0.5 % of the directions, a sliver (sigma -> 0, kappa >= 1; also anything degenerate or
-// non-finite: normal 0) to all of them: never culled.
-__device__ __forceinline__ bool beam_keeps_triangle(const Beam &b, float4 ts, float4 tn)
-{
-    const float vx = ts.x - b.ax, vy = ts.y - b.ay, vz = ts.z - b.az;
-    const float vv = __builtin_fmaf(vx, vx, __builtin_fmaf(vy, vy, vz * vz));
-    const float sa = __builtin_fmaf(vx, b.ux, __builtin_fmaf(vy, b.uy, vz * b.uz));
-    const float d2 = __builtin_fmaxf(__builtin_fmaf(-sa, sa, vv), 0.f);
-    const float dist = __builtin_amdgcn_sqrtf(vv) * 1.0001f;
-    const float rc = __builtin_fmaf(1.0e-3f, dist + ts.w, ts.w + 2.0e-3f) * 1.0001f;
-    const float reach = sa + rc - b.smin;
-    const float rad = __builtin_fmaf(b.k, __builtin_fmaxf(reach, 0.f), b.r0) + rc;
-    const float nu = __builtin_fabsf(__builtin_fmaf(tn.x, b.ux, __builtin_fmaf(tn.y, b.uy, tn.z * b.uz)));
-    const bool facing = nu >= (tn.w + b.k) * (1.f + b.k);              // false for a NaN anywhere
-    return !facing | (!(reach < 0.f) & !(d2 > rad * rad * 1.0005f));   // NaN / inf keep the triangle
-}
-
-// Leaf boxes of the mesh that the beam can touch, as indices in leaf order. A ray
-// tests a leaf's triangles only after passing the leaf's slab test, i.e. only if
-// it crosses the box, hence its bounding sphere: the sphere test with the usual
-// padding is conservative. Order is kept (first triangle wins ties, kernel.cu:1309):
-// two levels as for the spheres, but over blocks of RT_BLOCK CONSECUTIVE leaves (the host
-// appends their bounding spheres after the leaf spheres), marked blocks and their members
-// both taken in increasing order.
-__device__ __forceinline__ int build_box_list(const float4 *__restrict__ bsph, int nb, int *list, int *blist, const Beam &b,
-                                              int lane)
-{
-    const int nb_pad = (nb + RT_BLOCK - 1) / RT_BLOCK * RT_BLOCK, nblk = nb_pad / RT_BLOCK;
-    const float4 *__restrict__ blocks = bsph + nb_pad;
-    constexpr int G = 64 / RT_BLOCK;
-    const int grp = lane / RT_BLOCK, sub = lane % RT_BLOCK;
-    int count = 0;
-    for (int bbase = 0; bbase < nblk; bbase += 64) {
-        const int bi = bbase + lane;
-        const float4 bb = blocks[bi < nblk ? bi : nblk - 1];
-        const lmask bm = LM(bi < nblk) & beam_keeps_block(b, bb);
-        const int marked = __popcll(bm);
-        if (lane_in(bm)) blist[lane_prefix(bm)] = bi;
-        wave_lds_sync();
-        for (int t = 0; t < marked; t += G) {
-            const int slot = t + grp;
-            const int blk = (slot < marked) ? blist[slot] : -1;
-            const int i = (blk < 0 ? 0 : blk) * RT_BLOCK + sub;
-            const float4 s = bsph[i];
-            const lmask m = LM(blk >= 0) & LM(i < nb) & beam_keeps(b, s);
-            const int pos = count + lane_prefix(m);
-            if (lane_in(m) && pos < RT_BOX_CAP) list[pos] = i;
-            count += __popcll(m);
-        }
-        if (bbase + 64 < nblk) wave_lds_sync();
-    }
-    wave_lds_sync();
-    return count;
-}
-
-// ---------------------------------------------------------------------------
-// castLightRay's sample construction, kernel.cu:1438-1468 (exact)
-// ---------------------------------------------------------------------------
-template <int LEAN>
-struct ShadowChain {
-    V3 toL;            // keeps being re-normalised in place by the reference
-    // per-lane flags, kept as wave masks (scalar registers; see LM above)
-    lmask stable;      // an iteration leaves toL as it found it: every later iteration repeats this one
-    lmask fixed1;      // normalise() maps toL to itself: later iterations can only differ in `angle`
-    lmask settled;     // toL has its final value (advance()); says nothing about the cached angle / matrix
-    float angle;
-    float m00, m01, m02, m10, m11, m12, m20, m21, m22;
-
-    // FAST mode: toL itself is exact -- begin() and settle() run as in the exact kernel, because toL
-    // multiplies the brightness continuously (kernel.cu:1541) -- but everything that only shapes the
-    // sample directions (the angle to the light's edge, the rotation axis, angle and matrix of
-    // kernel.cu:1444-1466) is computed ONCE per light from the settled toL, in binary32 with hardware
-    // rsq / sqrt and fused multiply-adds, instead of being followed through the ten iterations.
-    __device__ __forceinline__ void setup_fast(const RtLightDev &L, V3 start)
-    {
-        const V3 lpos{L.px, L.py, L.pz};
-        const V3 P{-toL.z, 0.f, toL.x};                                     // cross(toL, (0,1,0))
-        V3 e0{__builtin_fmaf(P.x, L.size, lpos.x) - start.x, lpos.y - start.y, __builtin_fmaf(P.z, L.size, lpos.z) - start.z};
-        const V3 toEdge = normalise_t<2>(e0);
-        angle = __builtin_cosf(2.f * __builtin_fmaf(toL.x, toEdge.x, __builtin_fmaf(toL.y, toEdge.y, toL.z * toEdge.z)));
-        V3 ax0{-toL.y, toL.x, 0.f};                                         // cross((0,0,1), toL)
-        const V3 axis = normalise_t<2>(ax0);
-        const float cs = toL.z;                                             // cos(acos(toL.z))
-        const float sn = __builtin_amdgcn_sqrtf(__builtin_fmaxf(__builtin_fmaf(-cs, cs, 1.f), 0.f));
-        const float omc = 1.f - cs;
-        m00 = __builtin_fmaf(axis.x, axis.x, cs);
-        m01 = axis.x * axis.y * omc;
-        m02 = -axis.y * sn;
-        m10 = m01;
-        m11 = __builtin_fmaf(axis.y * axis.y, omc, cs);
-        m12 = -axis.x * sn;
-        m20 = -axis.y * sn;
-        m21 = axis.x * sn;
-        m22 = cs;
-        stable = ~0ull;
-        fixed1 = ~0ull;
-    }
-    __device__ __forceinline__ V3 direction_fast(AuxPtr ax, const RtLightDev &L, int j)
-    {
-        const float z = __builtin_fmaf(ax->jf[j], 1.0f - angle, angle);
-        const float sq = __builtin_amdgcn_sqrtf(__builtin_fmaf(-z, z, 1.f));   // NaN beyond |z| = 1, as the exact form
-        const float x = sq * ax->jcos[j], y = sq * ax->jsin[j];
-        V3 nd{L.px - __builtin_fmaf(x, m00, __builtin_fmaf(y, m10, z * m20)),
-              L.py - __builtin_fmaf(x, m01, __builtin_fmaf(y, m11, z * m21)),
-              L.pz - __builtin_fmaf(x, m02, __builtin_fmaf(y, m12, z * m22))};
-        return normalise_t<2>(nd);
-    }
-
-    __device__ __forceinline__ void begin(V3 lpos, V3 start)
-    {
-        // toL = normalise(l.pos - start), kernel.cu:1438
-        toL = V3{lpos.x - start.x, lpos.y - start.y, lpos.z - start.z};
-        normalise_t<LEAN>(toL);
-        stable = 0;
-        fixed1 = 0;
-        settled = 0;
-        angle = 0.f;
-        m00 = m01 = m02 = m10 = m11 = m12 = m20 = m21 = m22 = 0.f;
-    }
-
-    // One iteration's effect on toL alone (its two in-place normalisations, kernel.cu:1465-1466), for an iteration
-    // whose sample direction nobody needs: the next direction() then starts from the toL that iteration would have left.
-    // `stable` is not raised here -- the cached angle / matrix belong to whatever toL they were computed from, and
-    // direction() recomputes them unless it established itself that toL no longer moves.
-    __device__ __forceinline__ void advance()
-    {
-        const lmask act = LM(true);
-        if ((act & ~(settled | stable)) == 0) return;
-        if (LEAN) settled |= renormalise_is_identity();
-        if (LEAN && (act & ~(settled | stable)) == 0) return;
-        // (a wave mask is one value for the whole wave only in code every lane runs: the votes are taken AFTER the branch --
-        // inside it, the lanes that skip it would keep a stale copy. A lane that skips leaves toL == tin: its bit is set
-        // by the vote, as it already was.)
-        const V3 tin = toL;
-        V3 mid = toL;
-        if (!lane_in(settled | stable)) {
-            normalise_t<LEAN>(toL);
-            mid = toL;
-            normalise_t<LEAN>(toL);
-        }
-        settled |= (LM(toL.x == tin.x) & LM(toL.y == tin.y) & LM(toL.z == tin.z)) |
-                   (LM(toL.x == mid.x) & LM(toL.y == mid.y) & LM(toL.z == mid.z));
-    }
-
-    // normalise(toL) leaves toL as it is, for sure: the squared length as normalise() forms it (dot3, kernel.cu:56-58) is
-    // 1 or the next float, whose correctly rounded root is 1.0f (sqrt(1 + 2^-23) = 1 + 2^-24 - 2^-49 + ..., below the
-    // midpoint 1 + 2^-24), and x / 1.0f = x. Then every later normalisation repeats that: toL has its final value. Five
-    // multiply-adds and two compares where the pair of normalisations that would find it out takes eighty -- and half of
-    // the lanes leave begin() that way, nearly all of the others the first pair. (Culling kernels only: the brute-force
-    // and force-slow instantiations keep running the normalisations, so every cull-vs-brute comparison checks this.)
-    __device__ __forceinline__ lmask renormalise_is_identity() const
-    {
-        const float d2 = dot3(toL, toL);
-        return LM(d2 == 1.f) | LM(d2 == 0x1.000002p0f);   // false for a NaN
-    }
-
-    // The approximate sample frame of the pre-pass (see the frame kernel): from an approximate unit toL, binary32 with
-    // hardware reciprocal square roots and fused multiply-adds, cos(acos z) = z and sin(acos z) = sqrt(1 - z^2). The
-    // directions it yields differ from the exact chain's by less than RT_PRE_DELTA when the guards hold (returned flag;
-    // direction_approx's `ok`): derivation in the frame kernel.
-    __device__ __forceinline__ lmask setup_approx(const RtLightDev &L, V3 start, V3 t)
-    {
-        const V3 P{-t.z, 0.f, t.x};                                           // cross(toL, (0,1,0))
-        const V3 e0{__builtin_fmaf(P.x, L.size, L.px) - start.x, L.py - start.y, __builtin_fmaf(P.z, L.size, L.pz) - start.z};
-        const float e2 = __builtin_fmaf(e0.x, e0.x, __builtin_fmaf(e0.y, e0.y, e0.z * e0.z));
-        const float dte = __builtin_fmaf(t.x, e0.x, __builtin_fmaf(t.y, e0.y, t.z * e0.z)) * __builtin_amdgcn_rsqf(e2);
-        angle = __builtin_cosf(2.f * dte);
-        const float q2 = __builtin_fmaf(t.x, t.x, t.y * t.y);
-        const float rq = __builtin_amdgcn_rsqf(q2);
-        const float axx = -t.y * rq, axy = t.x * rq;                           // axis = (0,0,1) x toL, normalised; az = 0
-        const float cs = t.z;
-        const float sn = __builtin_amdgcn_sqrtf(__builtin_fmaxf(__builtin_fmaf(-cs, cs, 1.f), 0.f));
-        const float omc = 1.f - cs;
-        m00 = __builtin_fmaf(axx, axx, cs);
-        m01 = axx * axy * omc;
-        m02 = -axy * sn;
-        m10 = m01;
-        m11 = __builtin_fmaf(axy * axy, omc, cs);
-        m12 = -axx * sn;
-        m20 = -axy * sn;
-        m21 = axx * sn;
-        m22 = cs;
-        return LM(q2 >= 0.0025f) & LM(q2 <= 1.001f) & LM(e2 >= 1.0e-6f) & LM(e2 <= 1.0e30f) & LM(__builtin_fabsf(angle) <= 1.f);
-    }
-    __device__ __forceinline__ V3 direction_approx(AuxPtr ax, const RtLightDev &L, int j, bool &ok) const
-    {
-        const float z = __builtin_fmaf(ax->jf[j], 1.0f - angle, angle);
-        const float zz = __builtin_fmaf(-z, z, 1.f);
-        ok = zz >= 0.0025f;                                                    // sqrt(1 - z^2) >= 0.05: its slope in z stays below 20
-        const float sq = __builtin_amdgcn_sqrtf(zz);
-        const float x = sq * ax->jcos[j], y = sq * ax->jsin[j];
-        V3 nd{L.px - __builtin_fmaf(x, m00, __builtin_fmaf(y, m10, z * m20)),
-              L.py - __builtin_fmaf(x, m01, __builtin_fmaf(y, m11, z * m21)),
-              L.pz - __builtin_fmaf(x, m02, __builtin_fmaf(y, m12, z * m22))};
-        const float inv = __builtin_amdgcn_rsqf(__builtin_fmaf(nd.x, nd.x, __builtin_fmaf(nd.y, nd.y, nd.z * nd.z)));
-        return V3{nd.x * inv, nd.y * inv, nd.z * inv};
-    }
-
-    // Only the evolution of toL over the ten iterations (two in-place
-    // normalisations each, kernel.cu:1465-1466), for callers that need the final
-    // toL of kernel.cu:1541 but none of the sample directions.
-    __device__ __forceinline__ void settle()
-    {
-        const lmask act = LM(true);
-#pragma unroll 1
-        for (int j = 0; j < RT_SHADOW_SAMPLES; ++j) {
-            if (LEAN) stable |= renormalise_is_identity();
-            if ((act & ~stable) == 0) break;
-            const V3 tin = toL;
-            V3 mid = toL;
-            if (!lane_in(stable)) {
-                normalise_t<LEAN>(toL);
-                mid = toL;
-                normalise_t<LEAN>(toL);
-            }
-            // unchanged by the pair, or a fixed point of normalise(): toL has its final value (voted on after the branch,
-            // see advance())
-            stable |= (LM(toL.x == tin.x) & LM(toL.y == tin.y) & LM(toL.z == tin.z)) |
-                      (LM(toL.x == mid.x) & LM(toL.y == mid.y) & LM(toL.z == mid.z));
-        }
-    }
-
-    // Direction of sample j. Everything up to the rotation matrix depends on j
-    // only through toL, which normalise() keeps re-normalising in place
-    // (kernel.cu:1465-1466). Once two more normalisations leave toL
-    // bit-identical, every later iteration reproduces the same values, so the
-    // block is skipped (70 % of lanes are stable after j = 0, 99.6 % after j = 1).
-    __device__ __forceinline__ V3 direction(AuxPtr ax, bool force_slow, const RtLightDev &L,
-                                            V3 start, int j, const double *atab = nullptr)
-    {
-        const V3 lpos{L.px, L.py, L.pz};
-        // the flags as per-lane values while the branches below assign them; back into the wave masks after the join
-        bool st = lane_in(stable), f1 = lane_in(fixed1);
-        if (!st || force_slow) {
-            const V3 tin = toL;
-            // P = cross(toL, (0,1,0)), kernel.cu:1444
-            const V3 P{toL.y * 0.f - toL.z * 1.f, toL.z * 0.f - toL.x * 0.f, toL.x * 1.f - toL.y * 0.f};
-            V3 e0{(lpos.x + P.x * L.size) - start.x, (lpos.y + P.y * L.size) - start.y,
-                  (lpos.z + P.z * L.size) - start.z};
-            const V3 toEdge = normalise_t<LEAN>(e0);                       // kernel.cu:1450
-            angle = rtm::cosf_rt(dot3(toL, toEdge) * 2.f);                 // kernel.cu:1451
-            // The rest depends on toL only through its next two in-place normalisations. Once
-            // normalise() maps toL to itself (`fixed1`, 96 % of the lanes that are not `stable`
-            // after the first iteration) those leave it -- and the axis, nAngle and the matrix
-            // -- as they are: this iteration only had a new `angle` to compute, the next ones
-            // repeat it.
-            if (!f1 || force_slow) {
-                // axis = normalise(cross((0,0,1), normalise(toL))), kernel.cu:1465
-                const V3 n1 = normalise_t<LEAN>(toL);
-                const V3 mid = toL;
-                V3 ax0{0.f * n1.z - 1.f * n1.y, 1.f * n1.x - 0.f * n1.z, 0.f * n1.y - 0.f * n1.x};
-                const V3 axis = normalise_z0_t<LEAN>(ax0);
-                // nAngle = acosf(dot(normalise(toL), (0,0,1))), kernel.cu:1466
-                const V3 n2 = normalise_t<LEAN>(toL);
-                const float nAngle = rtm::acosf_rt((n2.x * 0.f + n2.y * 0.f) + n2.z * 1.f, atab);
-                float sn, cs;
-                rtm::sincosf_rt(nAngle, sn, cs);
-                const float omc = 1.f - cs;
-                // rotate(nAngle, axis), kernel.cu:1267-1277 (non-standard on purpose)
-                m00 = cs + axis.x * axis.x;
-                m01 = axis.x * axis.y * omc - axis.z * sn;
-                m02 = axis.x * axis.z * omc - axis.y * sn;
-                m10 = axis.y * axis.x * omc + axis.z * sn;
-                m11 = cs + axis.y * axis.y * omc;
-                m12 = axis.y * axis.z * omc - axis.x * sn;
-                m20 = axis.z * axis.x * omc - axis.y * sn;
-                m21 = axis.z * axis.y * omc + axis.x * sn;
-                m22 = cs + axis.z * axis.z * omc;
-                f1 = (toL.x == mid.x) && (toL.y == mid.y) && (toL.z == mid.z) &&
-                     (n1.x == n2.x) && (n1.y == n2.y) && (n1.z == n2.z);
-                st = (toL.x == tin.x) && (toL.y == tin.y) && (toL.z == tin.z);
-            } else {
-                st = true;
-            }
-        }
-        stable = ballot64(st);
-        fixed1 = ballot64(f1);
-        const float z = ax->jf[j] * (1.0f - angle) + angle;                // kernel.cu:1453
-        const float zz = 1.f - z * z;
-        float sq;                                                          // kernel.cu:1462-1463
-        if (LEAN && __builtin_expect(zz >= 0x1.0p-96f, 1)) sq = lean_sqrt(zz);   // zz <= 1
-        else sq = __builtin_sqrtf(zz);
-        const float x = sq * ax->jcos[j];
-        const float y = sq * ax->jsin[j];
-        // multiply(rot, {x,y,z}), kernel.cu:123-125
-        const V3 rv{(x * m00 + y * m10) + z * m20, (x * m01 + y * m11) + z * m21,
-                    (x * m02 + y * m12) + z * m22};
-        V3 nd{lpos.x - rv.x, lpos.y - rv.y, lpos.z - rv.z};
-        return normalise_t<LEAN>(nd);                                      // kernel.cu:1468
-    }
-};
-
-// One shadow ray against one table entry: updates `shadowed` (any-hit,
-// kernel.cu:1504-1508). Two shortcuts decide most entries without sqrt/div:
-// h < -h_sure puts t above RT_T_MIN (-B >= 2*h_sure and sqrt(disc) >= 0), and
-// "behind" (see RT_BEHIND_FACTOR) makes t strictly negative.
-template <int LEAN = 0>
-__device__ __forceinline__ void shadow_test(const RayK &sr, float4 s, bool &shadowed, bool force_slow)
-{
-    const Quad q = (LEAN == 2) ? quadratic_fast(sr, s) : quadratic(sr, s);
-    bool need;
-    if (force_slow) {
-        need = !shadowed;
-    } else {
-        const bool cand = (q.disc >= 0.f) && !shadowed;
-        // h < -2e-4*A puts t above RT_T_MIN (-B >= 4e-4*A, sqrt(disc) >= 0, divided by 2A); 5e-5 * (4A) is that
-        // bound up to a rounding the strict margins of the argument swallow many times over
-        const bool sure = cand && (q.h < -5.0e-5f * sr.a4);
-        const bool behind = (q.h > 0.f) && (q.disc < q.BB * RT_BEHIND_FACTOR);
-        shadowed = shadowed || sure;
-        need = cand && !sure && !behind;
-    }
-    if (any64(need)) {
-        if (need) {
-            float t;
-            if (intersect_tail_t<LEAN>(sr, q, t)) shadowed = true;
-        }
-    }
-}
-
-// The pre-pass of a light's ten samples (frame kernel): one shadow ray with an APPROXIMATE direction dq -- within
-// RT_PRE_DELTA of the exact chain's direction d -- against one list entry. Decides, where it can, what the exact test
-// (shadow_test above = intersect() of kernel.cu:293-354 for an any-hit) returns for d:
-//   hit   the exact test returns true:  the line passes the centre solidly inside the radius, ahead of the origin;
-//   miss  it returns false: no real root with margin, or the origin outside the sphere and the centre solidly behind.
-// C = |oc|^2 - R^2 is formed by the exact test's own operations (same bits); only h = d.oc differs, by at most
-// eta = (RT_PRE_DELTA + 2e-6) |oc| (the direction, and the rounding of either dot product), so |h| lies in
-// [hm, hp] = [|hq| - eta, |hq| + eta]. The exact test's discriminant B^2 - 4AC carries at most 3.8e-6 |oc|^2 of rounding
-// (rt_device.h), i.e. 9.5e-7 |oc|^2 on h^2 - C, and A = |d|^2 is 1 to 3e-7: 3e-6 |oc|^2 is the margin used.
-//   hit:  hq + eta < -2.1e-4 (so h < -5e-5 * 4A: the exact kernel's `sure` clause, t >= 1e-4) and hm^2 - C >= 3e-6 |oc|^2
-//         (so the float discriminant is >= 0);
-//   miss: hp^2 - C <= -3e-6 |oc|^2 (float discriminant < 0: the root is a NaN, every comparison false), or
-//         hq - eta > 0 and C > 1.002e-5 hp^2 (h > 0 and disc < 0.99999 B^2: the exact kernel's `behind` clause, t < 0).
-// A non-finite entry satisfies neither. Lanes that are neither `hit` by some entry nor `miss`ed by all are left to the
-// exact chain.
-#define RT_PRE_DELTA 1.0e-5f
-#ifndef RT_PRE_GROUP
-#define RT_PRE_GROUP 2   // samples per pass of the pre-pass over a light's list (measured: 2 and 3 alike, 4 +1 %, 5 +5 %: every
-                         // sample carries three wave masks, and a pass ends only when all of its samples are settled)
-#endif
-// N samples against one entry: oc, |oc|^2, C and the margins are the entry's and the pixel's, not the sample's -- 14 of a
-// single test's 35 instructions, formed once per entry for all N directions.
-template <int N>
-struct PreSure { lmask hit[N], miss[N]; };   // wave masks (see LM)
-template <int N>
-__device__ __forceinline__ PreSure<N> presure_test(V3 o, const V3 (&dq)[N], float4 s)
-{
-    const float ocx = o.x - s.x, ocy = o.y - s.y, ocz = o.z - s.z;
-    const float oc2 = (ocx * ocx + ocy * ocy) + ocz * ocz;
-    const float C = oc2 - s.w;                                    // as quadratic(): the same bits
-    const float eta = ((RT_PRE_DELTA + 2.0e-6f) * 1.0001f) * __builtin_amdgcn_sqrtf(oc2);
-    const float m = 3.0e-6f * oc2;
-    PreSure<N> r;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float hq = __builtin_fmaf(dq[i].x, ocx, __builtin_fmaf(dq[i].y, ocy, dq[i].z * ocz));
-        const float ah = __builtin_fabsf(hq);
-        const float hp = ah + eta, hm = __builtin_fmaxf(ah - eta, 0.f);
-        r.hit[i] = LM(hq + eta < -2.1e-4f) & LM(__builtin_fmaf(hm, hm, -C) >= m);
-        r.miss[i] = LM(__builtin_fmaf(hp, hp, -C) <= -m) | (LM(hq - eta > 0.f) & LM(C > 1.002e-5f * (hp * hp)));
-    }
-    return r;
-}
-
 // ---------------------------------------------------------------------------
 // the frame kernel
 // ---------------------------------------------------------------------------
-// MODE: 0 = product kernel, 1 = work counters, 2 = every exactness-preserving shortcut off
-// (rt_launch_opts.force_slow_path: tests), 3 = per-phase cycle stamps (s_memtime; RT_TUNING
-// builds only, run time never quoted), 4 = opt-in approximate arithmetic (rt_launch_opts.fast),
-// 5 = the product kernel plus the G-buffer stores (rt_frame_desc.aov_*; one sample, default tile),
-// 6 = the product kernel consuming light verdicts (RtFrameConsts::rest_rd), 7 = the product kernel recording them
-// (rest_wr): one-sample launches of sphere scenes, chosen by rt_dev_trace_config from the two pointers -- MODE 0
-// itself carries neither the code nor the registers of either.
-// FEAT: 0 = spheres only (the reference's default scene and every BASELINE config), 1 = with
-// the cube / plane branches of castRay and castLightRay, 2 = with those and the triangle mesh.
-// Each is its own instantiation so that the sphere-only kernel carries neither the code nor
-// the live scalars of primitives that are not there.
+// MODE, FEAT: RtTraceMode and RtTraceFeat (rt_device.h), which say what each value is.
 // MULTI: the launch may take several samples per pixel (rt_launch_opts.spp > 1). The
 // one-sample kernel has no sample loop: 74 -> 22 spilled scalars and 15 fewer vector registers.
-template <int TW, bool CULL, int MODE, int FEAT = 0, bool MULTI = true>
-__global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_WAVES_MESH_MULTI : RT_MIN_WAVES_MESH) : (MODE == 1) ? 4 : (MODE == 7) ? RT_MIN_WAVES_PER_SIMD : !MULTI ? RT_MIN_WAVES_ONE_SAMPLE : RT_MIN_WAVES_PER_SIMD) void rt_trace_tiles(const RtFrameConsts fc,
+template <int TW, bool CULL, int MODE, int FEAT = RT_FEAT_SPHERES, bool MULTI = true>
+__global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS ? 3 : MULTI ? RT_MIN_WAVES_MESH_MULTI : RT_MIN_WAVES_MESH) : (MODE == RT_MODE_STATS) ? 4 : (MODE == RT_MODE_REST_WRITE) ? RT_MIN_WAVES_PER_SIMD : !MULTI ? RT_MIN_WAVES_ONE_SAMPLE : RT_MIN_WAVES_PER_SIMD) void rt_trace_tiles(const RtFrameConsts fc,
                                                                      const float4 *__restrict__ spheres)
 {
-    constexpr int STATS = (MODE == 1) ? 1 : (MODE == 3) ? 2 : 0;
-    constexpr bool force_slow = (MODE == 2);
-    constexpr bool FAST = (MODE == 4);    // rt_launch_opts.fast: approximate arithmetic, never the default
-    constexpr bool AOV = (MODE == 5);     // rt_frame_desc.aov_*: MODE 0 plus the G-buffer stores after the texel fetch
-    constexpr bool MESH = (FEAT == 2);
-    constexpr bool PRIMS = (FEAT >= 1);   // cubes and planes may be present
+    constexpr int STATS = (MODE == RT_MODE_STATS) ? 1 : (MODE == RT_MODE_PHASES) ? 2 : 0;
+    constexpr bool force_slow = (MODE == RT_MODE_FORCE_SLOW);
+    constexpr bool FAST = (MODE == RT_MODE_FAST);    // rt_launch_opts.fast: approximate arithmetic, never the default
+    constexpr bool AOV = (MODE == RT_MODE_AOV);     // rt_frame_desc.aov_*: the product kernel plus the G-buffer stores after the texel fetch
+    constexpr bool MESH = (FEAT == RT_FEAT_MESH);
+    constexpr bool PRIMS = (FEAT == RT_FEAT_PRIMS || FEAT == RT_FEAT_MESH);   // cubes and planes may be present
     // the culling kernels take every exactness-preserving shortcut (lean normalise/sqrt, fast
     // texel index); the brute-force and force-slow ones evaluate everything the long way
 #ifdef RT_NO_LEAN
@@ -1283,30 +90,30 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
     const int n = fc.n_spheres;
     const AuxPtr ax = (AuxPtr)(uintptr_t)fc.aux;   // lights, sample constants, sky, planes/cubes, mesh (device memory)
 
-    // The wave's LDS, in the order rt_dev_trace_config sizes it. The `wave` terms are zero, but with them the compiler
-    // holds these addresses in registers; as plain constants it re-materialises them inside the loops, and the
-    // product kernel's code grows by 8 %.
+    // The wave's LDS, by the layout block of rt_device.h (RT_LDS_*), which also sizes the launch. The `wave` terms are
+    // zero, but with them the compiler holds these addresses in registers; as plain constants it re-materialises them
+    // inside the loops, and the product kernel's code grows by 8 %.
     float4 *mylist = lds + wave * RT_LIST_CAP;
-    int *mykeys = reinterpret_cast<int *>(lds + RT_LIST_CAP) + wave * RT_LIST_CAP;   // list positions (primary order)
+    int *mykeys = reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_KEYS + wave * RT_LIST_CAP;   // list positions (primary order)
     // b after n float+=double steps of 0.1 (brightness_steps), one 16-entry copy per wave: a
     // per-lane n then costs one LDS read instead of a ten-deep select chain per light
-    float *mybtab = reinterpret_cast<float *>(lds + RT_LIST_CAP) + RT_LIST_CAP + wave * 16;
+    float *mybtab = reinterpret_cast<float *>(lds + RT_LIST_CAP) + RT_LDS_BTAB + wave * 16;
     // marked blocks of one culling pass (at most 64 at a time)
-    int *myblks = reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16) + wave * 64;
+    int *myblks = reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_BLKS + wave * 64;
     // rtm::atan_eighth(0..8) for the binary64 arctangent (one LDS read instead of a select chain)
-    double *myatan = reinterpret_cast<double *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64)) + wave * 16;
+    double *myatan = reinterpret_cast<double *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_ATAN) + wave * 16;
     // the pixels' texel colours wait here for the shading at the end of a light (three registers that are live across
     // the whole light loop for one use per lit light; the compiler put them in scratch memory -- 0.4 GB per frame)
-    float *mytex = reinterpret_cast<float *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32)) + wave * 192;
-    int *myboxes = reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192) + wave * (RT_BOX_CAP + 128);   // + marked leaf blocks + 64 staged floats
-    float *mytri = reinterpret_cast<float *>(myboxes + RT_BOX_CAP + 64);   // staged vertices of a leaf (MESH launches only)
-    // Tile summaries (step 5d, MODE 6): the tile's dword of the resting-view table is asked for first of all -- one scalar
+    float *mytex = reinterpret_cast<float *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_TEX) + wave * 192;
+    int *myboxes = reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_TAIL + wave * RT_LDS_MESH_DWORDS;   // the mesh's tail: + marked leaf blocks + 64 staged floats
+    float *mytri = reinterpret_cast<float *>(myboxes + RT_LDS_MESH_TRI);   // staged vertices of a leaf (MESH launches only)
+    // Tile summaries (step 5d, RT_MODE_REST_READ): the tile's dword of the resting-view table is asked for first of all -- one scalar
     // load by the tile's frame coordinates, formed here as below. A settled tile (RT_TILE_SETTLED) stages no table,
     // loads no word, tag, list or ray table and, where no valid lane is a miss (RT_TILE_NO_MISS), no primary record:
     // the head of the sample loop sends it to the write-back. The others go on from here as they always did, with the
     // summary's latency in front of their loads: the flag is known before anything else is asked for.
     unsigned ts = 0;
-    if (MODE == 6) {
+    if (MODE == RT_MODE_REST_READ) {
         unsigned h_x = blockIdx.x, h_y = blockIdx.y;
         const unsigned h_tiles_x = (unsigned)(fc.width + TW - 1) / (unsigned)TW;
         if (fc.tile_perm) {
@@ -1316,8 +123,8 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         }
         ts = reinterpret_cast<const unsigned *>(fc.rest_rd)[RT_REST_SUMMARY_DWORD(h_tiles_x * rt_rest_tiles_y(fc.local_rows, TW), h_y * h_tiles_x + h_x)];
     }
-    bool settled = MODE == 6 && (ts & RT_TILE_SETTLED) != 0;   // wave-uniform
-    if (MODE != 6 || !settled) {
+    bool settled = MODE == RT_MODE_REST_READ && (ts & RT_TILE_SETTLED) != 0;   // wave-uniform
+    if (MODE != RT_MODE_REST_READ || !settled) {
         if (lane < 16) {
             mybtab[lane] = kBrightnessSteps[lane];   // same values as brightness_steps()
             myatan[lane] = kAtanEighth[lane];
@@ -1335,13 +142,13 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         blk_y = p >> 16;
     }
     if (fc.tile_cost) t_start = (unsigned)__builtin_amdgcn_s_memtime();
-    // Light verdicts (RtFrameConsts::rest_rd / rest_wr). MODE 6: the tile's word of an earlier launch of
+    // Light verdicts (RtFrameConsts::rest_rd / rest_wr). RT_MODE_REST_READ: the tile's word of an earlier launch of
     // bit-identical inputs is asked for here (lanes 0 and 1, a dword each, by the tile's frame coordinates), parked in
-    // the wave's LDS ahead of the light loop and consumed there two bits at a time. MODE 7: the word this launch finds
+    // the wave's LDS ahead of the light loop and consumed there two bits at a time. RT_MODE_REST_WRITE: the word this launch finds
     // is gathered in the same place and stored at the write-back. Nothing of it is held in a register across the light
     // loop, whose scalar and vector files are full.
-    constexpr bool VD_USE = (MODE == 6), VD_REC = (MODE == 7), VERD = VD_USE || VD_REC;
-    static_assert(!VERD || (CULL && FEAT == 0), "light verdicts: the sphere-only culling kernels");
+    constexpr bool VD_USE = (MODE == RT_MODE_REST_READ), VD_REC = (MODE == RT_MODE_REST_WRITE), VERD = VD_USE || VD_REC;
+    static_assert(!VERD || (CULL && FEAT == RT_FEAT_SPHERES), "light verdicts: the sphere-only culling kernels");
     // A reading launch forms a group's ball (g_r2, the check against its sphere's ball: two wave reductions) only where a
     // light of the group culls at all: 3.4 % of the 0.136 lights per tile that it still walks at C3. (RT_EAGER_BALL: the
     // variant it was measured against, profiles/primary_records_ab.json.)
@@ -1360,7 +167,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 #endif
     // Shadow counts (step 5b) go the same way: the tile's tag dword is asked for by lane 2 and parked behind the word,
     // and behind that the tile's index, which the light loop needs for a record's address and must not hold in a register.
-    unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + (RT_LIST_CAP + 16 + 64 + 32 + 192)) + wave * 8;   // word, tags, tile index, summary (MODE 7)
+    unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_TAIL) + wave * RT_LDS_REST_DWORDS;   // word, tags, tile index, summary (RT_MODE_REST_WRITE), in the tail's place
     unsigned vd_ld = 0;
     unsigned pr_rec = RT_PRIMARY_NONE;
     if (VERD) {
@@ -1550,7 +357,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                 if (STATS == 1) st_entries += (unsigned long long)(c <= RT_LIST_CAP ? c : n);
             }
             if (MESH && ok) {
-                const int cb = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_BOX_CAP, b, lane);
+                const int cb = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_LDS_MESH_BLKS, b, lane);
                 if (cb <= RT_BOX_CAP) {
                     pb_use_list = true;
                     pbcount = cb;
@@ -1627,7 +434,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
         const float *plbs = reinterpret_cast<const float *>(myblks);
         const bool p_front_to_back = CULL && p_use_list && pcount > 1;
         int holder = -1;
-        int hent = 0;   // (MODE 7) the list entry that holds nt
+        int hent = 0;   // (RT_MODE_REST_WRITE) the list entry that holds nt
         // Primary records (step 5c): a reading launch whose tile has a record does not walk. Which entry each lane ends on
         // is what the recording launch decided from the same list and the same rays; the lane evaluates that one entry, by
         // the walk's own gate, functions and operands, and so arrives at the same nt, holder and centre. A lane on record
@@ -1713,7 +520,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 
         // ================= miss: skybox::getFColor, kernel.cu:1147-1166 =================
         int sky_idx = -1;
-        int pr_tex = 0;   // (MODE 7) the lane's clamped texel index, sky or object texture
+        int pr_tex = 0;   // (RT_MODE_REST_WRITE) the lane's clamped texel index, sky or object texture
         if (VD_USE && pr_use) {
             // the sky texel on record: no sky-sphere intersection, no normalise, no uv chain; the clamp stays
             if (valid && !hit) {
@@ -1832,7 +639,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             start = V3{normal.x * 0.00001f + hp.x, normal.y * 0.00001f + hp.y, normal.z * 0.00001f + hp.z};
             if (STATS == 1) st_hits += 1;
         }
-        unsigned ts_pre = 0;   // (MODE 7) the tile's summary before its groups are known
+        unsigned ts_pre = 0;   // (RT_MODE_REST_WRITE) the tile's summary before its groups are known
         if (VD_REC) {
             // The recording launch: every lane's primary record, one coalesced 256-byte store per wave. A tile that walked
             // no view list (an overflowed block or one without cone, a tile shape that does not nest, a scene below 64
@@ -1896,7 +703,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     reinterpret_cast<float4 *>(o_albedo)[o] = hit ? make_float4(tr, tg, tb, 1.f) : make_float4(fr, fg, fb, 1.f);
             }
         }
-        if (VERD) {   // the tile's word: the verdicts it was handed (MODE 6), or those it finds (MODE 7: none so far)
+        if (VERD) {   // the tile's word: the verdicts it was handed (RT_MODE_REST_READ), or those it finds (RT_MODE_REST_WRITE: none so far)
             if (lane < 4) myvd[lane] = vd_ld;
             if (VD_REC && lane == 4) myvd[4] = ts_pre;
             wave_lds_sync();
@@ -2163,7 +970,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                             sb_use_list = true;
                             sbcount = 0;
                         } else if (MESH) {
-                            const int cbx = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_BOX_CAP, b, lane);
+                            const int cbx = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_LDS_MESH_BLKS, b, lane);
                             if (cbx <= RT_BOX_CAP) {
                                 sb_use_list = true;
                                 sbcount = cbx;
@@ -2212,7 +1019,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
                     all_clear = (lit_m & ~clear) == 0;
                 }
                 // (the chain begins after the pre-pass below, which borrows its registers for the approximate frame)
-                const bool will_prepass = CULL && !force_slow && !FAST && FEAT == 0 && !all_clear && s_use_list && !RT_ABL(131072);
+                const bool will_prepass = CULL && !force_slow && !FAST && FEAT == RT_FEAT_SPHERES && !all_clear && s_use_list && !RT_ABL(131072);
                 if (!will_prepass) chain.begin(lpos, start);
                 if (all_clear) {
                     chain.settle();
@@ -2624,7 +1431,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
             atomicAdd(&fc.stats[6], st_entries);
             atomicAdd(&fc.stats[7], st_overflow);
             for (int k = 0; k < 8; ++k) atomicAdd(&fc.stats[8 + k], hist[k]);
-            atomicAdd(&fc.stats[17], st_walks);               // (slots 17.. hold the wave-duration histogram in MODE 3)
+            atomicAdd(&fc.stats[17], st_walks);               // (slots 17.. hold the wave-duration histogram in RT_MODE_PHASES)
             if (MESH) {   // mesh launches: the mesh's work instead of the penumbra counters (tools/mesh_stats.py)
                 atomicAdd(&fc.stats[18], sm_plisted);
                 atomicAdd(&fc.stats[19], sm_pleaf);
@@ -2649,7 +1456,7 @@ __global__ __launch_bounds__(64, (FEAT == 2) ? (MODE == 1 ? 3 : MULTI ? RT_MIN_W
 typedef void (*RtTraceFn)(const RtFrameConsts, const float4 *);
 
 // Which (mode, feat) exist for a tile / cull / MULTI combination. The default tile has them all; the other tile
-// widths are test dimensions of the exact kernels (modes 0 and 2 on sphere scenes, mode 0 with cubes / planes / a
+// widths are test dimensions of the exact kernels (the product and force-slow modes on sphere scenes, the product mode with cubes / planes / a
 // mesh, the work counters on sphere scenes only): what no test, tool or bench launches is not compiled (build time
 // and code-object size, profiles/r03_build_and_first_launch.json). A missing combination makes the launch fail with
 // hipErrorNotSupported.
@@ -2657,14 +1464,14 @@ template <int TW, bool CULL, bool MULTI, int MODE, int FEAT>
 static constexpr bool trace_exists()
 {
 #ifdef RT_QUICK   // kernel experiments (tools/variants.sh): the product instantiation and its brute-force twin only
-    if (TW != 8 || FEAT != 0 || (MODE != 0 && MODE != 1 && MODE < 6) || (MULTI && MODE != 0)) return false;
+    if (TW != 8 || FEAT != RT_FEAT_SPHERES || (MODE != RT_MODE_PRODUCT && MODE != RT_MODE_STATS && MODE != RT_MODE_REST_READ && MODE != RT_MODE_REST_WRITE) || (MULTI && MODE != RT_MODE_PRODUCT)) return false;
 #endif
-    if (MODE >= 6) return CULL && FEAT == 0 && MULTI == (TW != 8);   // light verdicts: the one-sample kernel (other tiles: the sample loop, one pass)
-    if (MODE == 4) return TW == 8 && CULL && FEAT < 2;   // fast mode: the product configuration only
-    if (MODE == 5) return TW == 8 && !MULTI;             // G-buffer: the one-sample kernels of the default tile
-    if (TW != 8 && FEAT >= 1 && MODE != 0) return false;
+    if (MODE == RT_MODE_REST_READ || MODE == RT_MODE_REST_WRITE) return CULL && FEAT == RT_FEAT_SPHERES && MULTI == (TW != 8);   // light verdicts: the one-sample kernel (other tiles: the sample loop, one pass)
+    if (MODE == RT_MODE_FAST) return TW == 8 && CULL && FEAT != RT_FEAT_MESH;   // fast mode: the product configuration only
+    if (MODE == RT_MODE_AOV) return TW == 8 && !MULTI;   // G-buffer: the one-sample kernels of the default tile
+    if (TW != 8 && FEAT != RT_FEAT_SPHERES && MODE != RT_MODE_PRODUCT) return false;
 #ifndef RT_TUNING
-    if (MODE == 3) return false;
+    if (MODE == RT_MODE_PHASES) return false;
 #endif
     return true;
 }
@@ -2680,9 +1487,9 @@ template <int TW, bool CULL, bool MULTI, int MODE>
 static RtTraceFn trace_fn_feat(int feat)
 {
     switch (feat) {
-    case 0: return trace_fn_one<TW, CULL, MULTI, MODE, 0>();
-    case 1: return trace_fn_one<TW, CULL, MULTI, MODE, 1>();
-    case 2: return trace_fn_one<TW, CULL, MULTI, MODE, 2>();
+    case RT_FEAT_SPHERES: return trace_fn_one<TW, CULL, MULTI, MODE, RT_FEAT_SPHERES>();
+    case RT_FEAT_PRIMS: return trace_fn_one<TW, CULL, MULTI, MODE, RT_FEAT_PRIMS>();
+    case RT_FEAT_MESH: return trace_fn_one<TW, CULL, MULTI, MODE, RT_FEAT_MESH>();
     default: return nullptr;
     }
 }
@@ -2691,14 +1498,14 @@ template <int TW, bool CULL, bool MULTI>
 static RtTraceFn trace_fn_mode_feat(int mode, int feat)
 {
     switch (mode) {
-    case 0: return trace_fn_feat<TW, CULL, MULTI, 0>(feat);
-    case 1: return trace_fn_feat<TW, CULL, MULTI, 1>(feat);
-    case 2: return trace_fn_feat<TW, CULL, MULTI, 2>(feat);
-    case 3: return trace_fn_feat<TW, CULL, MULTI, 3>(feat);
-    case 4: return trace_fn_feat<TW, CULL, MULTI, 4>(feat);
-    case 5: return trace_fn_feat<TW, CULL, MULTI, 5>(feat);
-    case 6: return feat == 0 ? trace_fn_one<TW, CULL, MULTI, 6, 0>() : nullptr;
-    case 7: return feat == 0 ? trace_fn_one<TW, CULL, MULTI, 7, 0>() : nullptr;
+    case RT_MODE_PRODUCT: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_PRODUCT>(feat);
+    case RT_MODE_STATS: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_STATS>(feat);
+    case RT_MODE_FORCE_SLOW: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_FORCE_SLOW>(feat);
+    case RT_MODE_PHASES: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_PHASES>(feat);
+    case RT_MODE_FAST: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_FAST>(feat);
+    case RT_MODE_AOV: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_AOV>(feat);
+    case RT_MODE_REST_READ: return feat == RT_FEAT_SPHERES ? trace_fn_one<TW, CULL, MULTI, RT_MODE_REST_READ, RT_FEAT_SPHERES>() : nullptr;
+    case RT_MODE_REST_WRITE: return feat == RT_FEAT_SPHERES ? trace_fn_one<TW, CULL, MULTI, RT_MODE_REST_WRITE, RT_FEAT_SPHERES>() : nullptr;
     default: return nullptr;
     }
 }

@@ -449,7 +449,7 @@ def t_threshold(rt, oracle, seed):
 
 
 def shortcut_sure(rt, oracle, seed):
-    """Row 5a, the `sure` clause of the shadow test (h < -5e-5 * 4A, rt_trace.inc: shadow_test) and the pre-pass's
+    """Row 5a, the `sure` clause of the shadow test (h < -5e-5 * 4A, rt_shadow.h: shadow_test) and the pre-pass's
     hq + eta < -2.1e-4: a tiny occluder T whose centre projects 2e-4 x (1 + delta) (odd seeds: 2.1e-4) ahead of the patch's
     centre start on a sample ray, 1e-4 off it, radius 1.5e-4: the ray passes through T, the start stays outside. Witness,
     both sides: samples that pass T with h / A within 1e-5 of the threshold above it and below it."""
@@ -473,7 +473,7 @@ def shortcut_sure(rt, oracle, seed):
 
 
 def shortcut_behind(rt, oracle, seed):
-    """Row 5b, the `behind` clause (h > 0 and disc < RT_BEHIND_FACTOR B^2 = 0.99999 B^2, rt_trace.inc:581) and the
+    """Row 5b, the `behind` clause (h > 0 and disc < RT_BEHIND_FACTOR B^2 = 0.99999 B^2, rt_cull.h: RT_BEHIND_FACTOR) and the
     pre-pass's C > 1.002e-5 hp^2: S's own test of its shadow rays. A start 1e-5 above S has C ~ 2e-5 R and h ~ R cos,
     so disc / B^2 = 1 - AC / h^2 = 1 - 2e-5 / (R cos^2): with R cos^2 ~ 2 the patch's samples sit on 0.99999. Witness,
     both sides: samples of light 0 against S with h > 0 and disc / B^2 within 1e-6 of 0.99999, above and below."""
@@ -498,7 +498,7 @@ def shortcut_behind(rt, oracle, seed):
 
 
 def prepass_guard(rt, oracle, seed):
-    """Row 6, the pre-pass's guard (RT_PRE_DELTA, eta = (delta + 2e-6) |oc|, margin 3e-6 |oc|^2, rt_trace.inc): an occluder
+    """Row 6, the pre-pass's guard (RT_PRE_DELTA, eta = (delta + 2e-6) |oc|, margin 3e-6 |oc|^2, rt_shadow.h: presure_test): an occluder
     T (R_T 0.02-0.1) 0.5-2 units out whose surface a sample ray of the patch's centre start just grazes (distance of the
     line from the centre R_T x (1 + delta)). Witness: samples with |h^2 - C| below 3e-6 |oc|^2, some that the float test
     calls hit and some it calls a miss."""
@@ -681,7 +681,7 @@ def full_occluder_inside(rt, oracle, seed):
 
 # ---------------------------------------------------------------------------------------------- row 8: front to back
 def front_to_back(rt, oracle, seed):
-    """Ledger row of the front-to-back walk of the primary list (allowance 1e-3 + 1.5e-3 (dist + R), rt_trace.inc) and of
+    """Ledger row of the front-to-back walk of the primary list (allowance 1e-3 + 1.5e-3 (dist + R), rt_cull.h: build_list2) and of
     "first index wins" (kernel.cu:1335). Two DIFFERENT spheres whose near roots meet, seen through a frame zoomed onto
     where they meet: even seeds, two spheres whose surfaces cross (the camera aims at a point of the crossing circle);
     odd seeds, internally tangent at the point facing the camera. Their order in the list alternates every two seeds. Witness: pixels whose two nearest float near roots are equal or one ulp apart,

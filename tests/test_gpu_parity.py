@@ -164,7 +164,7 @@ def test_shortcuts_equal_the_long_forms(rt, gpu):
 
 
 def test_prepass_directions_stay_within_their_error_bound(rt, gpu):
-    """The sample pre-pass of the frame kernel (rt_trace.inc: setup_approx / direction_approx / presure_test)
+    """The sample pre-pass of the frame kernel (rt_shadow.h: setup_approx / direction_approx / presure_test)
     classifies shadow rays with APPROXIMATE directions and relies on |approximate - exact| < RT_PRE_DELTA = 1e-5
     wherever its guards let a direction through. Measured here on the device for 200 000 starts x 10 samples per
     light: starts in and around the scene for the three reference lights, and for random lights -- close ones, ones

@@ -188,7 +188,7 @@ ONE_TILE_FRAMES = ((8, 8, 8), (64, 1, 64))      # width, height, tile
 
 def beam_leaf_bounds(oracle, rt, om, inp, w, h):
     """(lower, upper) bounds of the leaves a tile that is the whole w x h frame lists for its primary rays, restated
-    in binary64 from build_box_list's test (rt_trace.inc): a leaf is kept when its bounding sphere comes within
+    in binary64 from build_box_list's test (rt_cull.h): a leaf is kept when its bounding sphere comes within
     k reach + r of the cone's axis, the axis the normalised sum of the tile's directions, k the tangent of their
     largest deviation. The kernel pads the deviation (x 1.01 + 1e-5), the radius (r^2 x 1.001 + 1e-6 on the host, then
     + 4e-6 |v|^2 + 8e-5) and the comparison (x 1.0005): `lower` drops every pad and shrinks the reach by a thousandth

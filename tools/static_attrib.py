@@ -6,7 +6,11 @@ rt_trace_tiles and asks llvm-symbolizer for the inline stack of every instructio
 outermost frame (a line of the kernel body) gets the instruction. Static counts only:
 loops are not weighted. Use together with the ablation timings (tools/ablate.sh).
 
-  python3 tools/static_attrib.py [--inst 'ILi8ELb1ELi0ELb1ELb0E'] [--by-callee]
+  python3 tools/static_attrib.py [--inst 'ILi8ELb1ELi1ELi0ELb0E'] [--by-callee]
+
+--inst is the mangled <TW, CULL, MODE, FEAT, MULTI> of an instantiation rt_kernels.hip holds in an RT_QUICK build;
+the default is the product kernel (8-wide tile, culling, RT_MODE_PRODUCT, RT_FEAT_SPHERES, one sample), the example
+its work-counter build. The line numbers are those of csrc/rt_trace.inc, where the kernel body is.
 """
 import argparse, collections, os, re, subprocess, sys, tempfile
 
@@ -18,7 +22,7 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--inst", default="ILi8ELb1ELi0ELb0ELi0ELb0E")
+    ap.add_argument("--inst", default="ILi8ELb1ELi0ELi0ELb0E")
     ap.add_argument("--by-callee", action="store_true")
     ap.add_argument("--top", type=int, default=60)
     a = ap.parse_args()
