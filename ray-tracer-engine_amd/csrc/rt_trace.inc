@@ -2,10 +2,13 @@
 // (trace_exists, the trace_fn_* ladders) and the declarations of the table's three parts. Included by the units that
 // instantiate the kernel and by no other: rt_kernels.hip (default tile, culling kernels, plus the launch
 // configuration and the diagnostics), rt_kernels_brute.hip (the same tile, brute-force loops) and
-// rt_kernels_tiles.hip (the other tile shapes) -- one code object, compiled in parallel. The device library the kernel
-// stands on is in four headers, each including the one before it: rt_wave.h (pointer types, V3, wave helpers),
-// rt_exact.h (exact and lean arithmetic, primitive tests), rt_cull.h (beams, list builders) and rt_shadow.h
-// (ShadowChain, shadow_test, the sample pre-pass). The other passes take those headers, never this file.
+// rt_kernels_tiles.hip (the other tile shapes) -- one code object, compiled in parallel. The configuration record
+// the kernel reads its switches from (TraceCfg), four helpers for blocks it held twice and the steps that stand on
+// their own are in rt_stages.h, which only this file includes. DESIGN.md section 4 maps the steps and says, for each
+// block that is still inline here, what cutting it out was measured to cost. The
+// device library both stand on is in four headers, each including the one before it: rt_wave.h (pointer types, V3,
+// wave helpers), rt_exact.h (exact and lean arithmetic, primitive tests), rt_cull.h (beams, list builders) and
+// rt_shadow.h (ShadowChain, shadow_test, the sample pre-pass). The other passes take those headers, never these two files.
 //
 // What is computed is the reference's `rayTrace` kernel (kernel.cu:1614-1690 and callees: castRay :1287-1431,
 // castLightRay :1432-1544, sphere::intersect :292-354, skybox::getFColor :1146-1166, rgbToInt :546-556). How it is
@@ -32,54 +35,19 @@
 // wins ties (kernel.cu:1335) resolve identically: the output is bit-identical
 // to the brute-force loops (template CULL=false), which tests check.
 #pragma once
-#include "rt_shadow.h"
-
-// Timing experiments (RT_ABLATE) exist in tuning builds only (make EXTRA=-DRT_TUNING, tools/variants.sh):
-// the product kernel has no such switch and the product library reads no environment.
-#ifdef RT_TUNING
-#define RT_ABL(bits) ((fc.ablate & (bits)) != 0)
-#else
-#define RT_ABL(bits) false
-#endif
+#include "rt_stages.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------
 // the frame kernel
 // ---------------------------------------------------------------------------
-// MODE, FEAT: RtTraceMode and RtTraceFeat (rt_device.h), which say what each value is.
-// MULTI: the launch may take several samples per pixel (rt_launch_opts.spp > 1). The
-// one-sample kernel has no sample loop: 74 -> 22 spilled scalars and 15 fewer vector registers.
+// The template parameters are TraceCfg's (rt_stages.h), which derives every switch from them.
 template <int TW, bool CULL, int MODE, int FEAT = RT_FEAT_SPHERES, bool MULTI = true>
-__global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS ? 3 : MULTI ? RT_MIN_WAVES_MESH_MULTI : RT_MIN_WAVES_MESH) : (MODE == RT_MODE_STATS) ? 4 : (MODE == RT_MODE_REST_WRITE) ? RT_MIN_WAVES_PER_SIMD : !MULTI ? RT_MIN_WAVES_ONE_SAMPLE : RT_MIN_WAVES_PER_SIMD) void rt_trace_tiles(const RtFrameConsts fc,
+__global__ __launch_bounds__(64, (TraceCfg<TW, CULL, MODE, FEAT, MULTI>::MIN_WAVES)) void rt_trace_tiles(const RtFrameConsts fc,
                                                                      const float4 *__restrict__ spheres)
 {
-    constexpr int STATS = (MODE == RT_MODE_STATS) ? 1 : (MODE == RT_MODE_PHASES) ? 2 : 0;
-    constexpr bool force_slow = (MODE == RT_MODE_FORCE_SLOW);
-    constexpr bool FAST = (MODE == RT_MODE_FAST);    // rt_launch_opts.fast: approximate arithmetic, never the default
-    constexpr bool AOV = (MODE == RT_MODE_AOV);     // rt_frame_desc.aov_*: the product kernel plus the G-buffer stores after the texel fetch
-    constexpr bool MESH = (FEAT == RT_FEAT_MESH);
-    constexpr bool PRIMS = (FEAT == RT_FEAT_PRIMS || FEAT == RT_FEAT_MESH);   // cubes and planes may be present
-    // the culling kernels take every exactness-preserving shortcut (lean normalise/sqrt, fast
-    // texel index); the brute-force and force-slow ones evaluate everything the long way
-#ifdef RT_NO_LEAN
-    constexpr int LEAN = 0;
-#else
-    constexpr int LEAN = (CULL && !force_slow) ? 1 : 0;   // precision class of normalise_t & co. (FAST: primary rays, normal and toL stay exact)
-#endif
-    // the lean tail of intersect(): for the primary rays; for the shadow rays it costs the one-sample
-    // kernel two spilled registers at its 6-waves-per-SIMD budget (measured: profiles/r02_variants.txt)
-#ifdef RT_NO_LEAN_PRIMARY_TAIL
-    constexpr int LEAN_PRIMARY_TAIL = 0;
-#else
-    constexpr int LEAN_PRIMARY_TAIL = LEAN;
-#endif
-#ifdef RT_LEAN_SHADOW_TAIL
-    constexpr int LEAN_SHADOW_TAIL = LEAN;
-#else
-    constexpr int LEAN_SHADOW_TAIL = FAST ? 2 : 0;
-#endif
-    constexpr int TH = 64 / TW;
+    using Cfg = TraceCfg<TW, CULL, MODE, FEAT, MULTI>;
     // One wave per workgroup: with the tables in global memory nothing is shared between waves, and one-wave
     // workgroups fill the SIMDs best (0.68 vs 0.71 ms at C3) and need no barrier.
     extern __shared__ float4 lds[];
@@ -93,6 +61,8 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     // The wave's LDS, by the layout block of rt_device.h (RT_LDS_*), which also sizes the launch. The `wave` terms are
     // zero, but with them the compiler holds these addresses in registers; as plain constants it re-materialises them
     // inside the loops, and the product kernel's code grows by 8 %.
+// (plain locals: held in one record handed to the steps by reference, the null test of the arctangent table is no
+// longer folded and the code grows by 8 %; formed again at each use, the tuning build's reading kernel spills 8 vector registers for 1)
     float4 *mylist = lds + wave * RT_LIST_CAP;
     int *mykeys = reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_KEYS + wave * RT_LIST_CAP;   // list positions (primary order)
     // b after n float+=double steps of 0.1 (brightness_steps), one 16-entry copy per wave: a
@@ -113,18 +83,22 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     // the head of the sample loop sends it to the write-back. The others go on from here as they always did, with the
     // summary's latency in front of their loads: the flag is known before anything else is asked for.
     unsigned ts = 0;
-    if (MODE == RT_MODE_REST_READ) {
+    if (Cfg::MODE == RT_MODE_REST_READ) {
+        // (the tile's place is formed four times -- here, below, at the G-buffer and at the write-back: as one function it
+        // changed 8 lines of the product kernel's machine code and 50 of the reading kernel's)
         unsigned h_x = blockIdx.x, h_y = blockIdx.y;
-        const unsigned h_tiles_x = (unsigned)(fc.width + TW - 1) / (unsigned)TW;
+        const unsigned h_tiles_x = (unsigned)(fc.width + Cfg::TW - 1) / (unsigned)Cfg::TW;
         if (fc.tile_perm) {
             const unsigned p = fc.tile_perm[blockIdx.y * h_tiles_x + blockIdx.x];
             h_x = p & 0xffffu;
             h_y = p >> 16;
         }
-        ts = reinterpret_cast<const unsigned *>(fc.rest_rd)[RT_REST_SUMMARY_DWORD(h_tiles_x * rt_rest_tiles_y(fc.local_rows, TW), h_y * h_tiles_x + h_x)];
+        ts = reinterpret_cast<const unsigned *>(fc.rest_rd)[RT_REST_SUMMARY_DWORD(h_tiles_x * rt_rest_tiles_y(fc.local_rows, Cfg::TW), h_y * h_tiles_x + h_x)];
     }
-    bool settled = MODE == RT_MODE_REST_READ && (ts & RT_TILE_SETTLED) != 0;   // wave-uniform
-    if (MODE != RT_MODE_REST_READ || !settled) {
+    bool settled = Cfg::MODE == RT_MODE_REST_READ && (ts & RT_TILE_SETTLED) != 0;   // wave-uniform
+    if (Cfg::MODE != RT_MODE_REST_READ || !settled) {
+        // (twice, here and where a settled tile falls back: as one function of (mybtab, myatan, lane) it changed 12 lines of the
+        // product kernel's machine code and 22 of the multi-sample kernel's)
         if (lane < 16) {
             mybtab[lane] = kBrightnessSteps[lane];   // same values as brightness_steps()
             myatan[lane] = kAtanEighth[lane];
@@ -135,58 +109,35 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     // which tile: the workgroup's own, or the one the frame's tile order puts at this place
     unsigned blk_x = blockIdx.x, blk_y = blockIdx.y;
     unsigned t_start = 0;
-    const unsigned tiles_x = (unsigned)(fc.width + TW - 1) / (unsigned)TW;   // = gridDim.x
+    const unsigned tiles_x = (unsigned)(fc.width + Cfg::TW - 1) / (unsigned)Cfg::TW;   // = gridDim.x
     if (fc.tile_perm) {
         const unsigned p = fc.tile_perm[blockIdx.y * tiles_x + blockIdx.x];
         blk_x = p & 0xffffu;
         blk_y = p >> 16;
     }
     if (fc.tile_cost) t_start = (unsigned)__builtin_amdgcn_s_memtime();
-    // Light verdicts (RtFrameConsts::rest_rd / rest_wr). RT_MODE_REST_READ: the tile's word of an earlier launch of
-    // bit-identical inputs is asked for here (lanes 0 and 1, a dword each, by the tile's frame coordinates), parked in
-    // the wave's LDS ahead of the light loop and consumed there two bits at a time. RT_MODE_REST_WRITE: the word this launch finds
-    // is gathered in the same place and stored at the write-back. Nothing of it is held in a register across the light
-    // loop, whose scalar and vector files are full.
-    constexpr bool VD_USE = (MODE == RT_MODE_REST_READ), VD_REC = (MODE == RT_MODE_REST_WRITE), VERD = VD_USE || VD_REC;
-    static_assert(!VERD || (CULL && FEAT == RT_FEAT_SPHERES), "light verdicts: the sphere-only culling kernels");
-    // A reading launch forms a group's ball (g_r2, the check against its sphere's ball: two wave reductions) only where a
-    // light of the group culls at all: 3.4 % of the 0.136 lights per tile that it still walks at C3. (RT_EAGER_BALL: the
-    // variant it was measured against, profiles/primary_records_ab.json.)
-#ifdef RT_EAGER_BALL
-    constexpr bool LAZY_BALL = false;
-#else
-    constexpr bool LAZY_BALL = VD_USE;
-#endif
-    // (RT_EAGER_REST_LOADS: the other order of a reading launch's head -- word, tags and primary records asked for before
-    // the summary is known and dropped by a settled tile -- which the order below was measured against,
-    // profiles/settled_tiles_ab.json.)
-#ifdef RT_EAGER_REST_LOADS
-    constexpr bool REST_EAGER = true;
-#else
-    constexpr bool REST_EAGER = false;
-#endif
     // Shadow counts (step 5b) go the same way: the tile's tag dword is asked for by lane 2 and parked behind the word,
     // and behind that the tile's index, which the light loop needs for a record's address and must not hold in a register.
     unsigned *myvd = reinterpret_cast<unsigned *>(reinterpret_cast<int *>(lds + RT_LIST_CAP) + RT_LDS_TAIL) + wave * RT_LDS_REST_DWORDS;   // word, tags, tile index, summary (RT_MODE_REST_WRITE), in the tail's place
     unsigned vd_ld = 0;
     unsigned pr_rec = RT_PRIMARY_NONE;
-    if (VERD) {
-        const unsigned vd_tile = blk_y * tiles_x + blk_x, vd_tiles = tiles_x * rt_rest_tiles_y(fc.local_rows, TW);   // T = the grid
+    if (Cfg::VERD) {
+        const unsigned vd_tile = blk_y * tiles_x + blk_x, vd_tiles = tiles_x * rt_rest_tiles_y(fc.local_rows, Cfg::TW);   // T = the grid
         // (a dword each: the word's halves, the tag)
-        if (VD_USE && (REST_EAGER || !settled) && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.rest_rd)[lane < 2 ? RT_REST_WORD_DWORD(vd_tile) + lane : RT_REST_TAG_DWORD(vd_tiles, vd_tile)];
+        if (Cfg::VD_USE && (Cfg::REST_EAGER || !settled) && lane < 3) vd_ld = reinterpret_cast<const unsigned *>(fc.rest_rd)[lane < 2 ? RT_REST_WORD_DWORD(vd_tile) + lane : RT_REST_TAG_DWORD(vd_tiles, vd_tile)];
         if (lane == 3) vd_ld = vd_tile;
         // Primary records (step 5c): the lane's dword -- which entry of the tile's view list is its closest hit, and its
         // texel -- asked for here beside the word and used after the ray arithmetic. (A settled tile without a miss lane
         // has no use for them; one with miss lanes tells hit from miss by them and takes the sky texel.)
-        if (VD_USE && (REST_EAGER || (ts & (RT_TILE_SETTLED | RT_TILE_NO_MISS)) != (RT_TILE_SETTLED | RT_TILE_NO_MISS))) pr_rec = reinterpret_cast<const unsigned *>(fc.rest_rd + RT_REST_PRIMARY_OFFSET(vd_tiles))[(size_t)vd_tile * (RT_REST_PRIMARY_BYTES / 4u) + lane];
+        if (Cfg::VD_USE && (Cfg::REST_EAGER || (ts & (RT_TILE_SETTLED | RT_TILE_NO_MISS)) != (RT_TILE_SETTLED | RT_TILE_NO_MISS))) pr_rec = reinterpret_cast<const unsigned *>(fc.rest_rd + RT_REST_PRIMARY_OFFSET(vd_tiles))[(size_t)vd_tile * (RT_REST_PRIMARY_BYTES / 4u) + lane];
     }
-    const int tile_x = blk_x * TW;
+    const int tile_x = blk_x * Cfg::TW;
     // local row -> global row: a contiguous band, or row blocks dealt round-robin
     // to the ranks of a multi-GPU frame (il_rows is a multiple of the tile rows a
     // workgroup covers, so a tile never straddles two blocks)
     // (`+ wave` adds 0; without it the 64x1-tile kernels compile to different code, the others do not change)
-    const int ly = (blk_y + wave) * TH + (lane / TW);
-    const int px = tile_x + (lane % TW);
+    const int ly = (blk_y + wave) * Cfg::TH + (lane / Cfg::TW);
+    const int px = tile_x + (lane % Cfg::TW);
     // (il_rows is a power of two -- the host checks -- and il_count = 1, il_index = 0 for a contiguous band: shifts and a
     // mask, where a division by a run-time il_rows is thirty vector instructions at the head of every wave)
     const int il_sh = __builtin_ctz((unsigned)fc.il_rows);
@@ -195,6 +146,8 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     if (valid_m == 0) return;   // wave-uniform
     const bool valid = lane_in(valid_m);
 
+// (plain locals: as one record with phase() and the flushes as members they moved registers and spills of the
+// work-counter mesh kernels and the phase-stamp kernels, 119 -> 135 vector registers in one; a run-time-indexed hist[] member put the record in scratch)
     unsigned long long st_primary = 0, st_shadow = 0, st_cull = 0, st_slots = 0, st_entries = 0,
                        st_overflow = 0, st_hits = 0, st_unshadowed = 0, st_clusters = 0;
 
@@ -205,9 +158,9 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long t_prev = 0;
     const bool span_only = RT_ABL(512);   // no inner stamps: near-real wave durations
-    const unsigned long long rt_begin = (STATS == 2) ? __builtin_amdgcn_s_memrealtime() : 0ull;   // 100 MHz
+    const unsigned long long rt_begin = (Cfg::STATS == 2) ? __builtin_amdgcn_s_memrealtime() : 0ull;   // 100 MHz
     auto phase = [&](int k, bool last = false) {   // charge the cycles since the previous stamp to phase k
-        if (STATS == 2 && (k < 0 || last || !span_only)) {
+        if (Cfg::STATS == 2 && (k < 0 || last || !span_only)) {
             __builtin_amdgcn_sched_barrier(0);
             const unsigned long long now = __builtin_amdgcn_s_memtime();
             __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): s_memtime returns through it
@@ -222,20 +175,19 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
 
     // The view list of the block of the frame this tile lies in (RtFrameConsts::view_lists), by the tile's frame
     // coordinates alone: what the primary cull below would compute, built once per view (rt_tables.hip).
-    constexpr bool VIEW = CULL && !force_slow;
     const float4 *vslot = nullptr;
-    if (VIEW && fc.view_lists) {
-        const int ly0 = (int)blk_y * TH;
+    if (Cfg::VIEW && fc.view_lists) {
+        const int ly0 = (int)blk_y * Cfg::TH;
         const int py0 = fc.y0 + ((((ly0 >> il_sh) * fc.il_count + fc.il_index) << il_sh) | (ly0 & (fc.il_rows - 1)));
         const int vblk = __builtin_amdgcn_readfirstlane((py0 >> (fc.view_shift >> 8)) * fc.view_nbx + (tile_x >> (fc.view_shift & 255)));
         vslot = reinterpret_cast<const float4 *>(fc.view_lists) + (size_t)vblk * RT_VIEW_SLOT;
     }
 
-    const int n_samples = MULTI ? fc.spp : 1;
+    const int n_samples = Cfg::MULTI ? fc.spp : 1;
     for (int sample = 0; sample < n_samples; ++sample) {
         float fr = 0.f, fg = 0.f, fb = 0.f;   // this sample's colour (sky texel on a miss)
         do {   // (left at its head by a settled tile, step 5d; by every other at its end)
-        if (VD_USE && settled) {
+        if (Cfg::VD_USE && settled) {
             // A settled tile: by the verdicts on record no light adds to any of its pixels, so a hit lane's colour is
             // the 0 it starts with and a miss lane's the sky texel of its record, through the clamp as ever. No ray, list,
             // normal, texel or group is formed: none of them has a consumer left. Everything from here to the sample's
@@ -243,9 +195,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
             const bool no_miss = (ts & RT_TILE_NO_MISS) != 0;
             if (no_miss || (valid_m & LM((pr_rec & 0xffu) == RT_PRIMARY_NONE)) == 0) {
                 if (!no_miss && valid && (pr_rec & 0xffu) == RT_PRIMARY_MISS) {
-                    int idx = (int)(pr_rec >> 8);
-                    const int last = ax->sky_w * ax->sky_h - 1;
-                    idx = idx < 0 ? 0 : (idx > last ? last : idx);
+                    const int idx = clamp_texel((int)(pr_rec >> 8), ax->sky_w * ax->sky_h - 1);
                     fr = ax->sky_r[idx];
                     fg = ax->sky_g[idx];
                     fb = ax->sky_b[idx];
@@ -270,7 +220,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         float4 v_ent = make_float4(0.f, 0.f, 0.f, 0.f);
         int v_key = 0;
         float v_lb = 0.f;
-        if (VIEW && vslot) {
+        if (Cfg::VIEW && vslot) {
             const ConstIntPtr vh = (ConstIntPtr)(uintptr_t)vslot;
             v_count = vh[0];
             v_use = vh[1] == 0;
@@ -278,6 +228,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
             v_key = reinterpret_cast<const int *>(vslot + 1 + RT_VIEW_CAP)[lane];
             v_lb = reinterpret_cast<const float *>(vslot + 1 + RT_VIEW_CAP + RT_VIEW_CAP / 4)[lane];
         }
+        // (inline: as a function returning D it changed 6 lines of the product kernel's machine code)
         // ================= primary ray, kernel.cu:1624-1631 =================
         // dx, dy of kernel.cu:1624-1625 (binary64 expressions of the column resp. the row) come
         // from the frame's tables, evaluated by the host with the reference's operations; lanes
@@ -286,7 +237,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         const float dx = fc.dx_tab[sidx * fc.width + (px < fc.width ? px : fc.width - 1)];
         const float dy = fc.dy_tab[sidx * fc.height + (py < fc.height ? py : fc.height - 1)];
         V3 dir{dx, dy, fc.eye_nz};   // (dx,dy,0) - (0,0,-1/aspect)
-        normalise_t<LEAN>(dir);
+        normalise_t<Cfg::LEAN>(dir);
         // camera::rotateDir, kernel.cu:252-257 (cos/sin hoisted to the host)
         V3 D;
         {
@@ -304,13 +255,13 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         bool p_use_list = false;   // false: walk the whole table
         int pcount = n;
         bool pb_use_list = false;  // leaf boxes of the mesh: false = all of them
-        int pbcount = MESH ? fc.n_boxes : 0;
+        int pbcount = Cfg::MESH ? fc.n_boxes : 0;
         Beam pbeam;                // the tile's primary beam, kept for the per-triangle cull of the mesh leaves
         bool pbeam_ok = false;
-        if (CULL) {
+        if (Cfg::CULL) {
             Beam b;
             bool ok = false;
-            if (!v_use || MESH) {
+            if (!v_use || Cfg::MESH) {
                 // cone around the tile's mean direction, apex at the (shared) origin
                 float sx = D.x, sy = D.y, sz = D.z;
                 wave_sum3(sx, sy, sz);
@@ -339,32 +290,32 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 wave_lds_sync();
                 p_use_list = true;
                 pcount = v_count;
-                if (STATS == 1) st_entries += (unsigned long long)v_count;
+                if (Cfg::STATS == 1) st_entries += (unsigned long long)v_count;
             } else if (ok) {
                 // eye cones when the scene has them and the tile's beam is within their slope limit
                 const float4 *csorted = reinterpret_cast<const float4 *>(fc.csorted);
                 const int c = (csorted && b.k <= fc.cone_kcap)
-                                  ? build_list2<STATS, false, true, 2>(fc, n, mylist, mykeys, myblks, b, lane, st_cull,
+                                  ? build_list2<Cfg::STATS, false, true, 2>(fc, n, mylist, mykeys, myblks, b, lane, st_cull,
                                                                               csorted, reinterpret_cast<const float4 *>(fc.cblocks),
                                                                               fc.corig)
-                                  : build_list2<STATS, false, true>(fc, n, mylist, mykeys, myblks, b, lane, st_cull);
+                                  : build_list2<Cfg::STATS, false, true>(fc, n, mylist, mykeys, myblks, b, lane, st_cull);
                 if (c <= RT_LIST_CAP) {
                     p_use_list = true;
                     pcount = c;
-                } else if (STATS == 1) {
+                } else if (Cfg::STATS == 1) {
                     st_overflow += 1;
                 }
-                if (STATS == 1) st_entries += (unsigned long long)(c <= RT_LIST_CAP ? c : n);
+                if (Cfg::STATS == 1) st_entries += (unsigned long long)(c <= RT_LIST_CAP ? c : n);
             }
-            if (MESH && ok) {
+            if (Cfg::MESH && ok) {
                 const int cb = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_LDS_MESH_BLKS, b, lane);
                 if (cb <= RT_BOX_CAP) {
                     pb_use_list = true;
                     pbcount = cb;
                 }
                 pbeam = b;
-                pbeam_ok = !force_slow;
-                if (STATS == 1) sm_plisted += (unsigned long long)pbcount;
+                pbeam_ok = !Cfg::force_slow;
+                if (Cfg::STATS == 1) sm_plisted += (unsigned long long)pbcount;
             }
         }
 
@@ -374,7 +325,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         int hkind = 1;                           // 0 triangle, 1 sphere, 2 plane, 3 cube (kernel.cu:1376)
         int htri = 0;
         int hprim = 0;                           // list position of the closest plane or cube (AOV only)
-        if (MESH) {
+        if (Cfg::MESH) {
             // triangles through the flat list of leaf boxes, kernel.cu:1293-1328 (before
             // the spheres, as there): a lane tests a leaf's triangles iff its ray hits the box
             const V3 inv{1.f / D.x, 1.f / D.y, 1.f / D.z};
@@ -383,14 +334,14 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 const RtBoxDev bx = ax->boxes[j];
                 const bool bh = box_intersect(bx, O, inv);
                 if (any64(bh) && !RT_ABL(1024)) {
-                    if (STATS == 1) sm_pleaf += 1;
+                    if (Cfg::STATS == 1) sm_pleaf += 1;
                     // which of the leaf's triangles the tile's beam can touch at all (a leaf of the reference's
                     // ten-pass split holds triangles far larger than a tile: about a third survive), 63 triangles
                     // -- nine loads of seven -- at a time: the split leaves a few leaves of a hundred and more
                     for (int c0 = 0; c0 < bx.len; c0 += 63) {
                         const int clen = bx.len - c0 < 63 ? bx.len - c0 : 63;
                         unsigned long long tmask = ~0ull;
-                        if (CULL && pbeam_ok) {
+                        if (Cfg::CULL && pbeam_ok) {
                             const int ti = bx.start + c0 + (lane < clen ? lane : 0);
                             const float4 ts = reinterpret_cast<const float4 *>(ax->tri_bs)[ti];
                             const float4 tn = reinterpret_cast<const float4 *>(ax->tri_nrm)[ti];
@@ -409,7 +360,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                                 if (!((tmask >> (base + i)) & 1ull)) continue;
                                 const float *tv = mytri + 9 * i;
                                 float t, u, v;
-                                if (STATS == 1) sm_ptri += 1;
+                                if (Cfg::STATS == 1) sm_ptri += 1;
                                 if (bh && tri_intersect(O, D, tv, tv + 3, tv + 6, t, u, v) && t < nt) {
                                     nt = t;
                                     htri = bx.start + c0 + base + i;   // position in tri_idx; resolved when shading (u, v too)
@@ -424,7 +375,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         }
         // without a list the table is walked in list order, from global memory
         auto primary_entry = [&](int e) -> float4 {
-            if (CULL) return p_use_list ? mylist[e] : spheres[e];
+            if (Cfg::CULL) return p_use_list ? mylist[e] : spheres[e];
             return spheres[e];
         };
         // A culled list comes front to back (build_list2): entry e carries its list position in
@@ -432,7 +383,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         // position of the sphere that currently holds nt (-1: none, e.g. a triangle does), so
         // that "first index wins ties" (kernel.cu:1335) holds in any order of evaluation.
         const float *plbs = reinterpret_cast<const float *>(myblks);
-        const bool p_front_to_back = CULL && p_use_list && pcount > 1;
+        const bool p_front_to_back = Cfg::CULL && p_use_list && pcount > 1;
         int holder = -1;
         int hent = 0;   // (RT_MODE_REST_WRITE) the list entry that holds nt
         // Primary records (step 5c): a reading launch whose tile has a record does not walk. Which entry each lane ends on
@@ -440,8 +391,8 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         // the walk's own gate, functions and operands, and so arrives at the same nt, holder and centre. A lane on record
         // as a miss keeps nt = +inf; the record is not trusted beyond that: hit_m below is formed from nt as ever.
         // (wave-uniform: the tile read a view list, and no valid lane's record says "none")
-        const bool pr_use = VD_USE && v_use && (valid_m & LM((pr_rec & 0xffu) == RT_PRIMARY_NONE)) == 0;
-        if (VD_USE && pr_use) {
+        const bool pr_use = Cfg::VD_USE && v_use && (valid_m & LM((pr_rec & 0xffu) == RT_PRIMARY_NONE)) == 0;
+        if (Cfg::VD_USE && pr_use) {
             const unsigned e = pr_rec & 0xffu;
             if (valid && e < (unsigned)RT_VIEW_CAP) {
                 const float4 s = mylist[e];
@@ -449,7 +400,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 const Quad q = quadratic(pr, s);
                 const bool need = q.disc >= 0.f && !(q.h > 0.f && q.disc < q.BB * RT_BEHIND_FACTOR);
                 float t;
-                if (need && intersect_tail_t<LEAN_PRIMARY_TAIL>(pr, q, t) && t < nt) {
+                if (need && intersect_tail_t<Cfg::LEAN_PRIMARY_TAIL>(pr, q, t) && t < nt) {
                     nt = t;
                     holder = pos;
                     hcx = s.x; hcy = s.y; hcz = s.z;
@@ -457,40 +408,40 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
             }
         }
         float4 pcur = pcount > 0 ? primary_entry(0) : make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int e = 0; !(VD_USE && pr_use) && e < ((RT_ABL(262144) && pcount > 1) ? 1 : pcount); ++e) {   // (262144: the price of the walk -- entry 0 for every lane)
+        for (int e = 0; !(Cfg::VD_USE && pr_use) && e < ((RT_ABL(262144) && pcount > 1) ? 1 : pcount); ++e) {   // (262144: the price of the walk -- entry 0 for every lane)
             const float4 s = pcur;
-            const int pos = (CULL && p_use_list) ? mykeys[e] : e;
+            const int pos = (Cfg::CULL && p_use_list) ? mykeys[e] : e;
             pcur = primary_entry(e + 1 < pcount ? e + 1 : e);   // one entry in flight
             const Quad q = quadratic(pr, s);
             lmask need = LM(q.disc >= 0.f);
-            if (!force_slow) need &= ~(LM(q.h > 0.f) & LM(q.disc < q.BB * RT_BEHIND_FACTOR));
-            if (force_slow) need = ~0ull;
+            if (!Cfg::force_slow) need &= ~(LM(q.h > 0.f) & LM(q.disc < q.BB * RT_BEHIND_FACTOR));
+            if (Cfg::force_slow) need = ~0ull;
             if (need != 0) {
                 if (lane_in(need)) {
                     float t;
-                    if (intersect_tail_t<LEAN_PRIMARY_TAIL>(pr, q, t)) {
+                    if (intersect_tail_t<Cfg::LEAN_PRIMARY_TAIL>(pr, q, t)) {
                         // strict, and among equal t the lower list position: first index wins ties
                         if (t < nt || (t == nt && holder >= 0 && pos < holder)) {
                             nt = t;
                             holder = pos;
-                            if (VD_REC) hent = e;
+                            if (Cfg::VD_REC) hent = e;
                             hcx = s.x; hcy = s.y; hcz = s.z;
-                            if (MESH) hkind = 1;
+                            if (Cfg::MESH) hkind = 1;
                         }
                     }
                 }
             }
-            if (STATS == 1) { st_primary += __popcll(valid_m); st_slots += 64; }
+            if (Cfg::STATS == 1) { st_primary += __popcll(valid_m); st_slots += 64; }
             // every remaining entry returns t >= its bound >= the next entry's bound
-            if (p_front_to_back && e + 1 < pcount && !force_slow) {
+            if (p_front_to_back && e + 1 < pcount && !Cfg::force_slow) {
                 const float lb_next = plbs[e + 1];
                 if ((valid_m & ~LM(nt < lb_next)) == 0) break;
             }
         }
-        if (CULL) wave_lds_sync();   // the list is rebuilt below
+        if (Cfg::CULL) wave_lds_sync();   // the list is rebuilt below
         // cubes (kernel.cu:1344-1356) then planes (:1359-1372): few, tested exhaustively;
         // for a plane hit hc* carries the plane's normal instead of a centre
-        if (PRIMS && fc.n_cubes > 0) {
+        if (Cfg::PRIMS && fc.n_cubes > 0) {
             const V3 inv{1.f / D.x, 1.f / D.y, 1.f / D.z};
             for (int i = 0; i < fc.n_cubes; ++i) {
                 const RtCubeDev c = ax->cubes[i];
@@ -499,18 +450,18 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     nt = t;
                     hkind = 3;
                     hcx = c.cx; hcy = c.cy; hcz = c.cz;
-                    if (AOV) hprim = i;
+                    if (Cfg::AOV) hprim = i;
                 }
             }
         }
-        for (int i = 0; i < (PRIMS ? fc.n_planes : 0); ++i) {
+        for (int i = 0; i < (Cfg::PRIMS ? fc.n_planes : 0); ++i) {
             const RtPlaneDev p = ax->planes[i];
             float t;
             if (plane_intersect(p, O, D, t) && t < nt) {
                 nt = t;
                 hkind = 2;
                 hcx = p.nx; hcy = p.ny; hcz = p.nz;
-                if (AOV) hprim = i;
+                if (Cfg::AOV) hprim = i;
             }
         }
         phase(2);
@@ -521,32 +472,29 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         // ================= miss: skybox::getFColor, kernel.cu:1147-1166 =================
         int sky_idx = -1;
         int pr_tex = 0;   // (RT_MODE_REST_WRITE) the lane's clamped texel index, sky or object texture
-        if (VD_USE && pr_use) {
+        if (Cfg::VD_USE && pr_use) {
             // the sky texel on record: no sky-sphere intersection, no normalise, no uv chain; the clamp stays
             if (valid && !hit) {
-                int idx = (int)(pr_rec >> 8);
-                const int last = ax->sky_w * ax->sky_h - 1;
-                idx = idx < 0 ? 0 : (idx > last ? last : idx);
-                sky_idx = idx;
+                sky_idx = clamp_texel((int)(pr_rec >> 8), ax->sky_w * ax->sky_h - 1);
             }
         } else if (valid && !hit) {
             const float4 sk = make_float4(ax->sky_cx, ax->sky_cy, ax->sky_cz, ax->sky_r2);
             const Quad q = quadratic(pr, sk);
             float t;
-            intersect_tail_t<LEAN_PRIMARY_TAIL>(pr, q, t);   // the boolean is ignored there, t is used as left
+            intersect_tail_t<Cfg::LEAN_PRIMARY_TAIL>(pr, q, t);   // the boolean is ignored there, t is used as left
             const V3 hp{O.x + D.x * t, O.y + D.y * t, O.z + D.z * t};
             V3 nrm{hp.x - sk.x, hp.y - sk.y, hp.z - sk.z};
-            normalise_t<LEAN>(nrm);
+            normalise_t<Cfg::LEAN>(nrm);
             const int sky_w = ax->sky_w, sky_h = ax->sky_h;
             int ix, iy;
             int sky_fast = -1;
-            if (FAST) {
+            if (Cfg::FAST) {
                 float ux, uy;
                 approx_sphere_uv(nrm, ux, uy);
                 ix = f2i(ux * (float)sky_w);
                 iy = f2i(uy * (float)sky_h);
             } else {
-                if (LEAN) {
+                if (Cfg::LEAN) {
                     // the same certainty test as for the object texture (approx_sphere_uv / sure_texel above); here
                     // the exact expressions are binary32 chains of their own -- atan2f and acosf rounded to float, a
                     // float division, 1.f + ..., two products -- which stay within 1.7e-7 of the real value, so the
@@ -561,11 +509,8 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     iy = f2i(rtm::acosf_rt(nrm.y, myatan) / 3.1415f * (float)sky_h);
                 }
             }
-            int idx = sky_fast >= 0 ? sky_fast : iy * sky_w + ix;
-            const int last = sky_w * sky_h - 1;
-            idx = idx < 0 ? 0 : (idx > last ? last : idx);   // documented clamp (reference is UB there)
-            sky_idx = idx;
-            if (VD_REC) pr_tex = idx;
+            sky_idx = clamp_texel(sky_fast >= 0 ? sky_fast : iy * sky_w + ix, sky_w * sky_h - 1);   // documented clamp (reference is UB there)
+            if (Cfg::VD_REC) pr_tex = sky_idx;
         }
 
         // ================= hit: shade, kernel.cu:1396-1405, 1643-1677 =================
@@ -574,14 +519,13 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         if (hit) {
             // the texture's uniforms: read from the kernel-argument segment here (see the write-back), not carried through
             // the primary cull and tests
-            FcPtr kt = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(kt));
+            FcPtr kt = kargs_again();
             const int t_w = kt->tex_w, t_h = kt->tex_h;
             const V3 new_org{O.x + D.x * nt, O.y + D.y * nt, O.z + D.z * nt};
             float tx = 0.5f, ty = 0.5f;   // plane, kernel.cu:1413-1414
             int ci_fast = -1;             // texel index already known for sure (sphere / cube hits of the culling kernels)
             V3 hp = new_org;              // what start_O is offset from
-            if (MESH && hkind == 0) {     // triangle, kernel.cu:1378-1393
+            if (Cfg::MESH && hkind == 0) {     // triangle, kernel.cu:1378-1393
                 const RtTriDev *tp = ax->tris + ax->tri_idx[htri];
                 // the barycentrics of the winning triangle: the same operations on the same operands as
                 // in the loop above (which does not carry them along)
@@ -592,7 +536,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     normal = V3{(tp->vn[0] * w0 + tp->vn[3] * hnu) + tp->vn[6] * hnv,
                                 (tp->vn[1] * w0 + tp->vn[4] * hnu) + tp->vn[7] * hnv,
                                 (tp->vn[2] * w0 + tp->vn[5] * hnu) + tp->vn[8] * hnv};
-                    normalise_t<LEAN>(normal);
+                    normalise_t<Cfg::LEAN>(normal);
                 } else {
                     normal = V3{tp->n[0], tp->n[1], tp->n[2]};
                 }
@@ -601,64 +545,39 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 // new_org = add(normal, add(Org, Dir * nt)): displaced by the whole normal
                 hp = V3{normal.x + new_org.x, normal.y + new_org.y, normal.z + new_org.z};
                 hcx = hcy = hcz = 0.f;    // one group for all triangle hits of the tile
-            } else if (PRIMS && hkind == 2) {      // plane, kernel.cu:1407-1416: the normal as stored
+            } else if (Cfg::PRIMS && hkind == 2) {      // plane, kernel.cu:1407-1416: the normal as stored
                 normal = V3{hcx, hcy, hcz};
             } else {                      // sphere / cube, kernel.cu:1396-1405, 1418-1425
                 normal = V3{new_org.x - hcx, new_org.y - hcy, new_org.z - hcz};
-                normalise_t<LEAN>(normal);
+                normalise_t<Cfg::LEAN>(normal);
                 if (RT_ABL(8)) {
                     tx = normal.x; ty = normal.y;
-                } else if (VD_USE && pr_use) {
+                } else if (Cfg::VD_USE && pr_use) {
                     ci_fast = (int)(pr_rec >> 8);       // the texel on record (24 bits: never negative); clamped below
-                } else if (FAST) {
+                } else if (Cfg::FAST) {
                     approx_sphere_uv(normal, tx, ty);   // no certainty test: a texel now and then is the neighbour
-                } else if (LEAN && !RT_ABL(4096)) {
+                } else if (Cfg::LEAN && !RT_ABL(4096)) {
                     float ux, uy;
                     approx_sphere_uv(normal, ux, uy);
                     ci_fast = sure_texel(ux, uy, t_w, t_h, kt->tex_mu_x, kt->tex_mu_y);
-                    if (__builtin_expect(ci_fast < 0, 0)) {
-                        tx = (float)((1.0 + rtm::div_by_3p1415((double)rtm::atan2f_rt(normal.z, normal.x, myatan))) * 0.5);
-                        ty = (float)rtm::div_by_3p1415((double)rtm::acosf_rt(normal.y, myatan));
-                    }
+                    if (__builtin_expect(ci_fast < 0, 0)) exact_uv(normal, myatan, tx, ty);
                 } else {
-                    // the literals 1, 3.1415, 0.5 make these binary64 expressions
-                    // kernel.cu:1402-1403; "/ 3.1415" in binary64 through div_by_3p1415 (same bits)
-                    tx = (float)((1.0 + rtm::div_by_3p1415((double)rtm::atan2f_rt(normal.z, normal.x, myatan))) * 0.5);
-                    ty = (float)rtm::div_by_3p1415((double)rtm::acosf_rt(normal.y, myatan));
+                    exact_uv(normal, myatan, tx, ty);
                 }
             }
             int ci = f2i(ty * (float)t_h) * t_w + f2i(tx * (float)t_w);
             if (ci_fast >= 0) ci = ci_fast;
-            const int last = t_w * t_h - 1;
-            ci = ci < 0 ? 0 : (ci > last ? last : ci);       // documented clamp
-            if (VD_REC) pr_tex = ci;
+            ci = clamp_texel(ci, t_w * t_h - 1);       // documented clamp
+            if (Cfg::VD_REC) pr_tex = ci;
             tr = kt->tex_r[ci];
             tg = kt->tex_g[ci];
             tb = kt->tex_b[ci];
             // start_O = normal * 0.00001 + new_org, kernel.cu:1647
             start = V3{normal.x * 0.00001f + hp.x, normal.y * 0.00001f + hp.y, normal.z * 0.00001f + hp.z};
-            if (STATS == 1) st_hits += 1;
+            if (Cfg::STATS == 1) st_hits += 1;
         }
         unsigned ts_pre = 0;   // (RT_MODE_REST_WRITE) the tile's summary before its groups are known
-        if (VD_REC) {
-            // The recording launch: every lane's primary record, one coalesced 256-byte store per wave. A tile that walked
-            // no view list (an overflowed block or one without cone, a tile shape that does not nest, a scene below 64
-            // spheres, the switch off) says so in all its lanes, and so does every tile when a texture's texel indices
-            // do not fit 24 bits -- decided here from the launch's own uniforms, wave-uniformly.
-            FcPtr kp = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(kp));
-            const bool fits = (unsigned)(kp->tex_w * kp->tex_h) <= (unsigned)RT_PRIMARY_TEXELS && (unsigned)(ax->sky_w * ax->sky_h) <= (unsigned)RT_PRIMARY_TEXELS;
-            unsigned d = RT_PRIMARY_NONE;
-            if (v_use && fits) d = (hit ? (unsigned)hent : RT_PRIMARY_MISS) | ((unsigned)pr_tex << 8);
-            const unsigned p_tiles_x = rt_rest_tiles_x(kp->width, TW);
-            const unsigned p_tiles = p_tiles_x * rt_rest_tiles_y(kp->local_rows, TW);   // = the grid
-            unsigned *const o_prim = reinterpret_cast<unsigned *>(kp->rest_wr + RT_REST_PRIMARY_OFFSET(p_tiles));
-            o_prim[(size_t)(blk_y * p_tiles_x + blk_x) * (RT_REST_PRIMARY_BYTES / 4u) + lane] = d;
-            // The tile's summary (step 5d) so far: it can be settled at all -- it has a record, and every light has its
-            // bits in the word --, and whether a valid lane is a miss. Parked behind the tile index below; the groups
-            // have their say behind the light loop.
-            ts_pre = ((v_use && fits && kp->n_lights <= RT_VERDICT_LIGHTS) ? RT_TILE_SETTLED : 0u) | ((valid_m & ~hit_m) == 0 ? RT_TILE_NO_MISS : 0u);
-        }
+        if (Cfg::VD_REC) ts_pre = store_primary_record<Cfg>(ax, lane, blk_x, blk_y, v_use, hit, hent, pr_tex, valid_m, hit_m);
 
         phase(3);
         // finite: x - x is 0 (inf - inf and NaN - NaN are NaNs); written as a comparison of its own -- `fabs(x) < inf` becomes
@@ -672,80 +591,25 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
             fg = ax->sky_g[sky_idx];
             fb = ax->sky_b[sky_idx];
         }
-        if (AOV) {
-            // ================= G-buffer (rt_frame_desc.aov_*, DESIGN.md 6e) =================
-            // Every value is live here and nothing new is held across the light loop below, whose register peak is
-            // what the budget is cut to: the output pointers come from the kernel-argument segment at this point,
-            // and the pixel's place is formed again as the write-back forms it.
-            FcPtr ka = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(ka));
-            float *const o_depth = ka->aov_depth, *const o_normal = ka->aov_normal, *const o_albedo = ka->aov_albedo;
-            int *const o_id = ka->aov_id;
-            unsigned a_x = blockIdx.x, a_y = blockIdx.y;
-            const unsigned a_tiles_x = (unsigned)(ka->width + TW - 1) / (unsigned)TW;
-            if (ka->tile_perm) {
-                const unsigned p = ka->tile_perm[blockIdx.y * a_tiles_x + blockIdx.x];
-                a_x = p & 0xffffu;
-                a_y = p >> 16;
-            }
-            const size_t o = (size_t)((unsigned)((a_y + wave) * TH + lane / TW) * (unsigned)ka->width + (unsigned)(a_x * TW + lane % TW));
-            if (valid) {
-                if (o_depth) o_depth[o] = nt;   // +inf on a miss
-                if (o_normal)
-                    reinterpret_cast<float4 *>(o_normal)[o] = hit ? make_float4(normal.x, normal.y, normal.z, 0.f)
-                                                                  : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (o_id) {
-                    int idx = -1;
-                    if (hit) idx = (MESH && hkind == 0) ? ax->tri_idx[htri] : (PRIMS && hkind >= 2) ? hprim : holder;
-                    reinterpret_cast<int2 *>(o_id)[o] = make_int2(hit ? hkind : -1, idx);
-                }
-                if (o_albedo)
-                    reinterpret_cast<float4 *>(o_albedo)[o] = hit ? make_float4(tr, tg, tb, 1.f) : make_float4(fr, fg, fb, 1.f);
-            }
-        }
-        if (VERD) {   // the tile's word: the verdicts it was handed (RT_MODE_REST_READ), or those it finds (RT_MODE_REST_WRITE: none so far)
-            if (lane < 4) myvd[lane] = vd_ld;
-            if (VD_REC && lane == 4) myvd[4] = ts_pre;
-            wave_lds_sync();
-        }
+        if (Cfg::AOV) store_gbuffer<Cfg>(ax, lane, wave, valid, hit, nt, normal, hkind, htri, hprim, holder, tr, tg, tb, fr, fg, fb);
+        if (Cfg::VERD) park_verdicts<Cfg>(myvd, lane, vd_ld, ts_pre);
         if (hit_m != 0 && !RT_ABL(16)) {
-            // A tile that straddles a silhouette sees several spheres at different
-            // depths; one beam around all of their shadow rays would be fat and its
-            // survivor list long. So the hit lanes are processed in groups that share
-            // the closest sphere (3.5 % of the 8x8 tiles at 4K see more than one):
-            // each group's origins lie on one small patch, its beam is thin, its
-            // list short -- and no wave runs orders of magnitude longer than the rest.
-            // group ids first (the sphere centres / kinds they are derived from are
-            // not needed afterwards, which frees four registers for the light loop)
-            int gid = -1, n_groups = 0;
-            {
-                lmask rem = hit_m;
-                while (rem) {
-                    const int first = __builtin_ctzll(rem);
-                    const float gx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hcx), first));
-                    const float gy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hcy), first));
-                    const float gz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hcz), first));
-                    const int gk = __builtin_amdgcn_readlane(hkind, first);
-                    const lmask in = rem & ((1ull << first) | ((PRIMS ? LM(hkind == gk) : ~0ull) & LM(hcx == gx) & LM(hcy == gy) & LM(hcz == gz)));
-                    if (lane_in(in)) gid = n_groups;
-                    rem &= ~in;
-                    ++n_groups;
-                }
-            }
+            int gid = -1;
+            const int n_groups = form_groups<Cfg>(hit_m, hcx, hcy, hcz, hkind, gid);
             for (int g = 0; g < n_groups; ++g) {
             const lmask inc_m = LM(gid == g);   // (gid is -1 where nothing was hit)
             const bool inc = lane_in(inc_m);
-            if (STATS == 1) st_clusters += 1;
+            if (Cfg::STATS == 1) st_clusters += 1;
             // The group's ray origins, bounded once for all lights: a ball around the first
             // member's `start`. (Per-light axial and perpendicular extents would be a little
             // tighter, for three more wave reductions per light; the patch a tile sees of one
             // primitive is small against the spheres it is culled against.)
             float g_ax = 0.f, g_ay = 0.f, g_az = 0.f, g_r2 = 0.f;
             int g_sphere = -1;     // list position of the sphere the group lies on (-1: a plane, cube or triangle)
-            if (CULL) {
+            if (Cfg::CULL) {
                 const int glead = __builtin_ctzll(inc_m);
                 g_sphere = __builtin_amdgcn_readlane(holder, glead);
-                if (PRIMS && __builtin_amdgcn_readlane(hkind, glead) != 1) g_sphere = -1;
+                if (Cfg::PRIMS && __builtin_amdgcn_readlane(hkind, glead) != 1) g_sphere = -1;
                 // (Groups are formed by the CENTRE of the closest sphere, so two concentric spheres would share one. They
                 // never do where it matters: intersect() returns the near root even when it is negative, and of two
                 // concentric spheres the larger has the smaller C, hence the larger discriminant and the smaller near
@@ -756,7 +620,9 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 g_ax = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, start.x), glead));
                 g_ay = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, start.y), glead));
                 g_az = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, start.z), glead));
-                if (!LAZY_BALL) {
+                if (!Cfg::LAZY_BALL) {
+                // (twice, here and at LAZY_BALL's first culling light: as one function with g_r2 and g_sphere by reference it moved four
+                // kernels' spilled scalars, 11 -> 14 in the product one; as two that return them, 24 lines of its machine code)
                 const float ox = start.x - g_ax, oy = start.y - g_ay, oz = start.z - g_az;
                 g_r2 = uniform(wave_max(inc ? __builtin_fmaf(ox, ox, __builtin_fmaf(oy, oy, oz * oz)) : 0.f));
                 // The sphere's occluder lists and its kbeam (rt_tables.hip) hold for starts inside the ball of radius
@@ -774,18 +640,18 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 }
                 }
             }
-            bool ball_done = !LAZY_BALL;   // (LAZY_BALL: the two reductions wait for the group's first light that culls at all)
+            bool ball_done = !Cfg::LAZY_BALL;   // (LAZY_BALL: the two reductions wait for the group's first light that culls at all)
             for (int li = 0; li < fc.n_lights; ++li) {
                 // An earlier launch of the same inputs left this iteration by one of the three exits marked below:
                 // so would this one, having added nothing -- the iteration is skipped whole.
                 // (groups beyond RT_VERDICT_GROUPS and lights beyond RT_VERDICT_LIGHTS have no bits: always evaluated)
-                const bool vd_has = VERD && g < RT_VERDICT_GROUPS && li < RT_VERDICT_LIGHTS;
+                const bool vd_has = Cfg::VERD && g < RT_VERDICT_GROUPS && li < RT_VERDICT_LIGHTS;
                 const int vd_sh = 16 * (g & 1) + 2 * li;
                 unsigned vd = 0;
-                if (VD_USE && vd_has) vd = ((unsigned)__builtin_amdgcn_readfirstlane((int)myvd[g >> 1]) >> vd_sh) & 3u;
-                if (VD_USE && vd == RT_VERDICT_NOTHING) continue;
+                if (Cfg::VD_USE && vd_has) vd = ((unsigned)__builtin_amdgcn_readfirstlane((int)myvd[g >> 1]) >> vd_sh) & 3u;
+                if (Cfg::VD_USE && vd == RT_VERDICT_NOTHING) continue;
                 auto vd_note = [&](unsigned code) {
-                    if (VD_REC && vd_has && lane == 0)
+                    if (Cfg::VD_REC && vd_has && lane == 0)
                         (void)__hip_atomic_fetch_or(&myvd[g >> 1], code << vd_sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 };
                 // Shadow counts: a light that the recording launch walked to the end (code 0) and gave a record. Its lanes'
@@ -793,13 +659,13 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 // iteration takes the all-clear path -- the facing test (lit_m is still needed), then the chain's begin and
                 // settle for toL, no list header, beam, cull, all-clear test, list order, pre-pass or sample -- and the
                 // shading reads the lane's count from the record instead of RT_SHADOW_SAMPLES.
-                if (VD_USE && vd_has && vd == 0) {
+                if (Cfg::VD_USE && vd_has && vd == 0) {
                     const unsigned tg = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[2]);
 #pragma unroll
                     for (int r = 0; r < RT_SHADOW_RECORDS; ++r)
                         if (((tg >> (8 * r)) & 0xffu) == RT_SHADOW_TAG(g, li)) vd = 4u + r;   // (neither code: record r)
                 }
-                const bool sc_use = VD_USE && vd >= 4u;
+                const bool sc_use = Cfg::VD_USE && vd >= 4u;
                 const RtLightDev L = ax->lights[li];
                 const V3 lpos{L.px, L.py, L.pz};
 
@@ -823,7 +689,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 // runs the reference's loops as written and is what tests compare with.)
                 lmask lit_m = inc_m;
                 lmask zero_ok_m = 0;   // brightness 0 adds exactly nothing for this lane
-                if (CULL && !force_slow) {
+                if (Cfg::CULL && !Cfg::force_slow) {
                     const float a0 = dot3(normal, toL);
                     // (0 * l.r) * r is 0 iff the light's colour (frame constant, checked by the host) and the
                     // texel (checked once per pixel) are finite
@@ -841,12 +707,12 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 bool s_use_list = false;
                 int scount = n;
                 bool sb_use_list = false;
-                int sbcount = MESH ? fc.n_boxes : 0;
+                int sbcount = Cfg::MESH ? fc.n_boxes : 0;
                 float beam_k = 0.f;   // slope of the light's beam (valid when s_use_list)
                 // (a light whose all-clear test held for these inputs needs neither its list nor the test again)
                 // (nor does a light whose counts are on record)
-                if (CULL && !(VD_USE && vd == RT_VERDICT_CLEAR) && !sc_use) {
-                    if (LAZY_BALL && !ball_done) {   // the group's ball, as above
+                if (Cfg::CULL && !(Cfg::VD_USE && vd == RT_VERDICT_CLEAR) && !sc_use) {
+                    if (Cfg::LAZY_BALL && !ball_done) {   // the group's ball, as above
                         const float ox = start.x - g_ax, oy = start.y - g_ay, oz = start.z - g_az;
                         g_r2 = uniform(wave_max(inc ? __builtin_fmaf(ox, ox, __builtin_fmaf(oy, oy, oz * oz)) : 0.f));
                         if (g_sphere >= 0) {
@@ -941,35 +807,34 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                         // One sphere in front of the whole beam shadows all 10 samples of
                         // every lit lane: unshadowed = 0, b = 0, and the light adds exactly
                         // nothing -- the sample construction and the tests are skipped.
-                        const bool may_skip = !force_slow && !RT_ABL(64) && all_zero_ok;
+                        const bool may_skip = !Cfg::force_slow && !RT_ABL(64) && all_zero_ok;
                         const float4 *lsorted = reinterpret_cast<const float4 *>(ax->lsorted[li]);
                         // the fallback culls read the table pointers and block count from the kernel-argument segment
                         // HERE (see the write-back): they are rarely needed once the occluder lists exist, and held in
                         // scalar registers from the kernel's entry they are spilled around every loop in between
-                        FcPtr kl = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
-                        asm volatile("" : "+s"(kl));
+                        FcPtr kl = kargs_again();
                         // the group's own sphere has a list of what can shadow it from this light: cull that
                         int cand_n = ch.count;
                         const int cand_off = ch.offset;
                         if (!(uniform(b.k) <= ch.kcap)) cand_n = -1;   // (also for a NaN)
-                        const int cb = cand_n >= 0 ? build_list_cand<STATS>(reinterpret_cast<const float4 *>(ax->cand_ent[li]) + cand_off, cand_n,
+                        const int cb = cand_n >= 0 ? build_list_cand<Cfg::STATS>(reinterpret_cast<const float4 *>(ax->cand_ent[li]) + cand_off, cand_n,
                                                                             mylist, b, lane, st_cull, may_skip)
-                                     : lsorted ? build_list2<STATS, true, false, 1>(
+                                     : lsorted ? build_list2<Cfg::STATS, true, false, 1>(
                                                      *kl, n, mylist, mykeys, myblks, b, lane, st_cull, lsorted,
                                                      reinterpret_cast<const float4 *>(ax->lblocks[li]), nullptr, may_skip)
-                                               : build_list2<STATS, true, false>(*kl, n, mylist, mykeys, myblks, b,
+                                               : build_list2<Cfg::STATS, true, false>(*kl, n, mylist, mykeys, myblks, b,
                                                                                          lane, st_cull, nullptr, nullptr, nullptr, may_skip);
                         const int c = cb & 0x3fffffff;
                         if (may_skip && (cb & 0x40000000)) {
-                            if (STATS == 1) hist[7] += 1;
+                            if (Cfg::STATS == 1) hist[7] += 1;
                             wave_lds_sync();
                             vd_note(RT_VERDICT_NOTHING);
                             continue;
                         }
-                        if (MESH && RT_ABL(32768)) {
+                        if (Cfg::MESH && RT_ABL(32768)) {
                             sb_use_list = true;
                             sbcount = 0;
-                        } else if (MESH) {
+                        } else if (Cfg::MESH) {
                             const int cbx = build_box_list(reinterpret_cast<const float4 *>(ax->box_spheres), fc.n_boxes, myboxes, myboxes + RT_LDS_MESH_BLKS, b, lane);
                             if (cbx <= RT_BOX_CAP) {
                                 sb_use_list = true;
@@ -980,11 +845,11 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                             s_use_list = true;
                             scount = c;
                             beam_k = b.k;
-                        } else if (STATS == 1) {
+                        } else if (Cfg::STATS == 1) {
                             st_overflow += 1;
                         }
-                        if (STATS == 1) st_entries += (unsigned long long)(c <= RT_LIST_CAP ? c : n);
-                        if (STATS == 1) {
+                        if (Cfg::STATS == 1) st_entries += (unsigned long long)(c <= RT_LIST_CAP ? c : n);
+                        if (Cfg::STATS == 1) {
                             const int bin = c <= 1 ? 0 : c <= 2 ? 1 : c <= 4 ? 2 : c <= 8 ? 3 : c <= 16 ? 4 : c <= RT_LIST_CAP ? 5 : 6;
                             hist[bin] += 1;
                         }
@@ -993,9 +858,10 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
 
                 phase(5);
                 // ---------- the 10 samples, kernel.cu:1442-1540 (exact) ----------
-                ShadowChain<LEAN> chain;
+                ShadowChain<Cfg::LEAN> chain;
                 // one register for both: bits 0..15 = samples left to the exact chain (pre-pass), bits 16.. = unshadowed samples so far
                 unsigned us = 0;
+                // (inline: as a function returning all_clear this test moved the spilled-scalar counts of four kernels, 14 -> 18 in the reading one)
                 // A short list whose every sphere lies behind every ray of the beam (for
                 // each lit lane: start outside the sphere by more than the `behind`
                 // shortcut needs, C > 2e-5*|oc|^2, and the whole cone of directions on the
@@ -1003,9 +869,9 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                 // unshadowed without constructing one of them: only toL's evolution is
                 // needed for kernel.cu:1541. Typically the list is just the sphere the
                 // tile itself lies on.
-                bool all_clear = (VD_USE && vd == RT_VERDICT_CLEAR) || sc_use;   // (sc_use: no walk either; the counts differ)
-                if (CULL && (!MESH || (sb_use_list && sbcount == 0)) && s_use_list && scount <= 4 && !force_slow &&
-                    !RT_ABL(128) && (!PRIMS || (fc.n_planes | fc.n_cubes) == 0)) {
+                bool all_clear = (Cfg::VD_USE && vd == RT_VERDICT_CLEAR) || sc_use;   // (sc_use: no walk either; the counts differ)
+                if (Cfg::CULL && (!Cfg::MESH || (sb_use_list && sbcount == 0)) && s_use_list && scount <= 4 && !Cfg::force_slow &&
+                    !RT_ABL(128) && (!Cfg::PRIMS || (fc.n_planes | fc.n_cubes) == 0)) {
                     lmask clear = ~0ull;
                     for (int e = 0; e < scount; ++e) {
                         const float4 sp = mylist[e];
@@ -1019,18 +885,20 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     all_clear = (lit_m & ~clear) == 0;
                 }
                 // (the chain begins after the pre-pass below, which borrows its registers for the approximate frame)
-                const bool will_prepass = CULL && !force_slow && !FAST && FEAT == RT_FEAT_SPHERES && !all_clear && s_use_list && !RT_ABL(131072);
+                const bool will_prepass = Cfg::CULL && !Cfg::force_slow && !Cfg::FAST && Cfg::FEAT == RT_FEAT_SPHERES && !all_clear && s_use_list && !RT_ABL(131072);
                 if (!will_prepass) chain.begin(lpos, start);
                 if (all_clear) {
                     chain.settle();
                     us = (unsigned)RT_SHADOW_SAMPLES << 16;
                     vd_note(RT_VERDICT_CLEAR);
-                    if (STATS == 1) hist[6] += 1;
+                    if (Cfg::STATS == 1) hist[6] += 1;
                 }
+                // (inline: as a function of the list, the group's origin and the light it changed 13 lines of the product kernel's machine
+                // code and 31 of the multi-sample kernel's)
                 // The samples will be walked: put the likeliest occluders first -- the spheres that
                 // reach farthest across the beam's axis (distance from the axis minus radius) -- so
                 // that the any-hit loops end sooner. An any-hit does not depend on the order.
-                if (CULL && s_use_list && !all_clear && scount > 2 && scount <= 64 && !force_slow &&
+                if (Cfg::CULL && s_use_list && !all_clear && scount > 2 && scount <= 64 && !Cfg::force_slow &&
                     !RT_ABL(256)) {
                     float *kbuf = reinterpret_cast<float *>(myblks);
                     float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1054,7 +922,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     if (lane < scount) mylist[rank] = e;
                     wave_lds_sync();
                 }
-                if (FAST && !all_clear) {   // toL as the reference leaves it (exact), then the sample frame once, approximately
+                if (Cfg::FAST && !all_clear) {   // toL as the reference leaves it (exact), then the sample frame once, approximately
                     chain.settle();
                     chain.setup_fast(L, start);
                 }
@@ -1104,12 +972,12 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                             lmask all_hit = ~0ull;
 #pragma unroll
                             for (int i = 0; i < N; ++i) {
-                                if (STATS == 1 && (lit_m & ~h[i]) != 0 && (lit_m & ~r.hit[i]) == 0) n_single += 1;
+                                if (Cfg::STATS == 1 && (lit_m & ~h[i]) != 0 && (lit_m & ~r.hit[i]) == 0) n_single += 1;
                                 h[i] |= r.hit[i];
                                 m[i] &= r.miss[i];
                                 all_hit &= h[i];
                             }
-                            if (STATS == 1) { st_shadow += N * __popcll(lit_m); st_slots += 64 * N; }
+                            if (Cfg::STATS == 1) { st_shadow += N * __popcll(lit_m); st_slots += 64 * N; }
                             if ((lit_m & ~all_hit) == 0) { broke = true; break; }
                         }
                         // the entry that completed "every lit pixel hit" goes to the front: the next samples' rays are
@@ -1136,7 +1004,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                         for (; j + G <= RT_SHADOW_SAMPLES; j += G) group(std::integral_constant<int, G>{}, j);
                         if constexpr (R != 0) group(std::integral_constant<int, R>{}, j);
                     }
-                    if (STATS == 1) {   // pre-pass outcome: walks that need the exact chain, and how many of their samples
+                    if (Cfg::STATS == 1) {   // pre-pass outcome: walks that need the exact chain, and how many of their samples
                         unsigned long long need = 0;
                         for (int j = 0; j < RT_SHADOW_SAMPLES; ++j) need += any64((us >> j) & 1u) ? 1 : 0;
                         st_pre += need + ((need ? 1ull : 0ull) << 24) + ((n_single == RT_SHADOW_SAMPLES ? 1ull : 0ull) << 44);
@@ -1164,35 +1032,34 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     }
                     const bool want = lane_in(want_m);
                     const V3 new_dir = RT_ABL(2) ? chain.toL
-                                       : FAST   ? chain.direction_fast(ax, L, j)
-                                                : chain.direction(ax, force_slow, L, start, j, myatan);
+                                       : Cfg::FAST   ? chain.direction_fast(ax, L, j)
+                                                : chain.direction(ax, Cfg::force_slow, L, start, j, myatan);
                     const RayK sr = make_ray(start, new_dir);
                     phase(6);
                     // any-hit over the list, kernel.cu:1501-1510
                     bool shadowed = !want;   // lanes outside the group, unlit or already decided are simply done
                     const int scount_j = RT_ABL(1) ? 0 : scount;
                     if (scount_j > 0) {
-                        FcPtr kg = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
-                        asm volatile("" : "+s"(kg));
-                        const float4 *gtab = CULL ? reinterpret_cast<const float4 *>(kg->sorted) : spheres;
+                        FcPtr kg = kargs_again();
+                        const float4 *gtab = Cfg::CULL ? reinterpret_cast<const float4 *>(kg->sorted) : spheres;
                         // (no entry kept in flight: at 7 waves per SIMD the LDS latency is covered by the other
                         // waves, and the four registers are what lets the kernel run at 7)
                         for (int e = 0; e < scount_j; ++e) {
                             const float4 cur = entry_at(s_use_list, mylist, gtab, e);
-                            shadow_test<LEAN_SHADOW_TAIL>(sr, cur, shadowed, force_slow);
-                            if (STATS == 1) { st_shadow += __popcll(ballot64(lit)); st_slots += 64; }
+                            shadow_test<Cfg::LEAN_SHADOW_TAIL>(sr, cur, shadowed, Cfg::force_slow);
+                            if (Cfg::STATS == 1) { st_shadow += __popcll(ballot64(lit)); st_slots += 64; }
                             if (all64(shadowed)) break;
                         }
                     }
                     // triangles, kernel.cu:1475-1497 (the reference tests them first; an
                     // any-hit does not depend on the order)
-                    if (MESH && !all64(shadowed) && !RT_ABL(8192)) {
+                    if (Cfg::MESH && !all64(shadowed) && !RT_ABL(8192)) {
                         const V3 inv{1.f / new_dir.x, 1.f / new_dir.y, 1.f / new_dir.z};
                         for (int bjj = 0; bjj < sbcount; ++bjj) {
                             const int bj = sb_use_list ? myboxes[bjj] : bjj;
                             const RtBoxDev bx = ax->boxes[bj];
                             const bool bh = !shadowed && box_intersect(bx, start, inv);
-                            if (STATS == 1) sm_sslab += 1;
+                            if (Cfg::STATS == 1) sm_sslab += 1;
                             if (any64(bh) && !RT_ABL(16384)) {
                                 // (a per-triangle cull against the light's beam, as for the primary rays, was measured:
                                 // -1.7 % at 4K, +2.8 % at 1080p, one more spilled register -- not kept)
@@ -1203,7 +1070,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                                     for (int i = 0; i < cnt; ++i) {
                                         const float *tv = mytri + 9 * i;
                                         float t, u, v;
-                                        if (STATS == 1) sm_stri += 1;
+                                        if (Cfg::STATS == 1) sm_stri += 1;
                                         if (bh && !shadowed && tri_intersect(start, new_dir, tv, tv + 3, tv + 6, t, u, v))
                                             shadowed = true;
                                     }
@@ -1214,7 +1081,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                         }
                     }
                     // planes (kernel.cu:1511-1523) then cubes (:1524-1536), any-hit
-                    if (PRIMS && (fc.n_planes | fc.n_cubes) != 0 && !all64(shadowed)) {
+                    if (Cfg::PRIMS && (fc.n_planes | fc.n_cubes) != 0 && !all64(shadowed)) {
                         for (int i = 0; i < fc.n_planes; ++i) {
                             float t;
                             if (!shadowed && plane_intersect(ax->planes[i], start, new_dir, t)) shadowed = true;
@@ -1232,29 +1099,10 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     if (!shadowed) us += 1u << 16;   // b += 0.1, kernel.cu:1537-1539
                     phase(7);
                 }
-                if (CULL) wave_lds_sync();
-                // The recording launch: a light that was walked to the end (not clear, not dark) takes the tile's next free
-                // record -- every lane's count as a byte, 64 in a row -- and lane 0 notes whose it is in the tag dword.
-                if (VD_REC && vd_has && !all_clear && !dark) {
-                    const unsigned tg = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[2]);
-                    int slot = -1;
-#pragma unroll
-                    for (int r = RT_SHADOW_RECORDS - 1; r >= 0; --r)
-                        if (((tg >> (8 * r)) & 0xffu) == 0u) slot = r;
-                    if (slot >= 0) {
-                        FcPtr kg = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
-                        asm volatile("" : "+s"(kg));
-                        const unsigned tiles = rt_rest_tiles(kg->width, kg->local_rows, TW);
-                        const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[3]);
-                        unsigned char *rec = kg->rest_wr + RT_REST_COUNTS_OFFSET(tiles) + ((size_t)tile * RT_SHADOW_RECORDS + (size_t)slot) * RT_REST_RECORD_BYTES;
-                        rec[lane] = (unsigned char)(us >> 16);
-                        if (lane == 0)
-                            (void)__hip_atomic_fetch_or(&myvd[2], RT_SHADOW_TAG(g, li) << (8 * slot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        wave_lds_sync();
-                    }
-                }
-                if (STATS == 1 && MESH && !all_clear) sm_slisted += (unsigned long long)sbcount;
-                if (STATS == 1 && !all_clear) {   // how many of the walked lights had a lane in a penumbra at all
+                if (Cfg::CULL) wave_lds_sync();
+                if (Cfg::VD_REC && vd_has && !all_clear && !dark) record_counts<Cfg>(myvd, g, li, lane, us);
+                if (Cfg::STATS == 1 && Cfg::MESH && !all_clear) sm_slisted += (unsigned long long)sbcount;
+                if (Cfg::STATS == 1 && !all_clear) {   // how many of the walked lights had a lane in a penumbra at all
                     const int unshadowed = (int)(us >> 16);
                     const bool pen = lit && unshadowed != 0 && unshadowed != RT_SHADOW_SAMPLES;
                     st_walks += 1;
@@ -1273,9 +1121,8 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     // here, where the fewest registers are live -- asked for ahead of begin and settle, so that the chain
                     // covers its latency, it costs the kernel four spilled vector registers and its scratch-free frame.
                     if (sc_use) {
-                        FcPtr kg = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();
-                        asm volatile("" : "+s"(kg));
-                        const unsigned tiles = rt_rest_tiles(kg->width, kg->local_rows, TW);
+                        FcPtr kg = kargs_again();
+                        const unsigned tiles = rt_rest_tiles(kg->width, kg->local_rows, Cfg::TW);
                         const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)myvd[3]);
                         const unsigned char *rec = kg->rest_rd + RT_REST_COUNTS_OFFSET(tiles) + ((size_t)tile * RT_SHADOW_RECORDS + (size_t)(vd - 4u)) * RT_REST_RECORD_BYTES;
                         // (a scalar base and a lane index formed on the spot, both opaque, and a global load said to be one:
@@ -1291,24 +1138,11 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
                     fr = fr + bsum * L.r * mytex[lane];                         // kernel.cu:1673-1675
                     fg = fg + bsum * L.g * mytex[64 + lane];
                     fb = fb + bsum * L.b * mytex[128 + lane];
-                    if (STATS == 1) st_unshadowed += (unsigned long long)unshadowed;
+                    if (Cfg::STATS == 1) st_unshadowed += (unsigned long long)unshadowed;
                 }
             }
             }   // groups
-            if (VD_REC && lane == 0) {
-                // Settled (step 5d): every iteration the tile has left its code RT_VERDICT_NOTHING in the word -- lane 0
-                // made every note, so it reads its own -- and the word holds them all. What the word must then be: code
-                // 1 for each of the n_lights lights in each of the n_groups 16-bit fields, 0 elsewhere.
-                bool all_nothing = n_groups <= RT_VERDICT_GROUPS && fc.n_lights <= RT_VERDICT_LIGHTS;
-                if (all_nothing) {
-                    const unsigned pat = 0x5555u & ((1u << (2 * fc.n_lights)) - 1u);
-                    const unsigned lo = (n_groups > 0 ? pat : 0u) | (n_groups > 1 ? pat << 16 : 0u);
-                    const unsigned hi = (n_groups > 2 ? pat : 0u) | (n_groups > 3 ? pat << 16 : 0u);
-                    all_nothing = myvd[0] == lo && myvd[1] == hi;
-                }
-                myvd[4] = (myvd[4] & (all_nothing ? (RT_TILE_SETTLED | RT_TILE_NO_MISS) : RT_TILE_NO_MISS)) |
-                          ((unsigned)(n_groups < 255 ? n_groups : 255) << RT_TILE_GROUPS_SHIFT);
-            }
+            if (Cfg::VD_REC && lane == 0) tile_summary(fc, myvd, n_groups);
         }
         } while (false);
         if (valid) {
@@ -1318,12 +1152,14 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         }
     }
 
+    // (inline: as a function of (myvd, lane, wave, valid, t_start, acc, n_samples) it changed 38 lines of the product kernel's
+    // machine code and 40 of the multi-sample kernel's; with it and the five blocks marked likewise above cut out, the multi-sample
+    // frame measured 0.7777 ms against the parent's 0.7760, every round above every round of the parent's)
     // ================= write-back =================
     // The frame uniforms of this part -- output pointers, flags, the divisor -- are read from the kernel-argument
     // segment HERE: taken from `fc` they are loaded at the kernel's entry and held in scalar registers across the whole
     // kernel, whose scalar file is full (each one more is a v_writelane / v_readlane pair in the loops above).
-    FcPtr kargs = (FcPtr)__builtin_amdgcn_kernarg_segment_ptr();   // `fc` is the first kernel argument
-    asm volatile("" : "+s"(kargs));                                // opaque: not merged with the loads at the entry
+    FcPtr kargs = kargs_again();
     float *const o_rgba = kargs->rgba;
     uint32_t *const o_packed = kargs->packed, *const o_packed24 = kargs->packed24;
     unsigned *const o_cost = kargs->tile_cost;
@@ -1334,7 +1170,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     // coordinates are then dead between the primary ray and this point instead of occupying vector registers -- or a
     // scratch slot -- across the light loop, whose register peak is what the seven-waves-per-SIMD budget is cut to.
     unsigned wb_x = blockIdx.x, wb_y = blockIdx.y;
-    const unsigned wb_tiles_x = (unsigned)(kargs->width + TW - 1) / (unsigned)TW;
+    const unsigned wb_tiles_x = (unsigned)(kargs->width + Cfg::TW - 1) / (unsigned)Cfg::TW;
     const uint32_t *perm = kargs->tile_perm;
     if (perm) {
         const unsigned p = perm[blockIdx.y * wb_tiles_x + blockIdx.x];
@@ -1343,8 +1179,8 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     }
     int wb_lane = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(wb_lane));
-    const int wb_px = (int)(wb_x * TW) + (wb_lane % TW);
-    const int wb_ly = (int)((wb_y + wave) * TH) + (wb_lane / TW);
+    const int wb_px = (int)(wb_x * Cfg::TW) + (wb_lane % Cfg::TW);
+    const int wb_ly = (int)((wb_y + wave) * Cfg::TH) + (wb_lane / Cfg::TW);
     const unsigned out_idx = (unsigned)wb_ly * (unsigned)kargs->width + (unsigned)wb_px;   // band-local pixel index
     if (valid) {
         const size_t o = out_idx;
@@ -1361,25 +1197,11 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
             *dst = make_float4(acc_r, acc_g, acc_b, w);
         }
         if (o_packed && (o_flags & RT_FLAG_RESOLVE)) {
-            // mean over the frame's samples (x/1.0f is exact, so 1 spp is the
-            // reference's rgbToInt(fr*254, fg*254, fb*254), kernel.cu:1682/1688)
-            float mr = acc_r, mg = acc_g, mb = acc_b;
-            if (o_total != 1.f) {   // wave-uniform; three IEEE divisions saved at 1 spp
-                mr = acc_r / o_total;
-                mg = acc_g / o_total;
-                mb = acc_b / o_total;
-            }
-            o_packed[o] = rgb_to_int(f2i(mr * 254.f), f2i(mg * 254.f), f2i(mb * 254.f));
+            o_packed[o] = resolve_pixel(acc_r, acc_g, acc_b, o_total);
         }
     }
     if (o_packed24 && (o_flags & RT_FLAG_RESOLVE)) {   // wave-uniform; all lanes take part in the quad exchange
-        float mr = acc_r, mg = acc_g, mb = acc_b;
-        if (o_total != 1.f) {
-            mr = acc_r / o_total;
-            mg = acc_g / o_total;
-            mb = acc_b / o_total;
-        }
-        const unsigned p = rgb_to_int(f2i(mr * 254.f), f2i(mg * 254.f), f2i(mb * 254.f));
+        const unsigned p = resolve_pixel(acc_r, acc_g, acc_b, o_total);
         // the next pixel of the quad (lanes 4q..4q+3 hold four consecutive pixels of a row)
         const unsigned pn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)p, 0xF9 /* quad_perm [1,2,3,3] */, 0xf, 0xf, true);
         const int i = lane & 3;
@@ -1388,12 +1210,12 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
         if (valid && i < 3) o_packed24[(size_t)(out_idx >> 2) * 3 + (size_t)i] = w24;
     }
 
-    if (VD_REC) {   // the tile's light verdicts as this launch found them (an all-sky tile: 0)
+    if (Cfg::VD_REC) {   // the tile's light verdicts as this launch found them (an all-sky tile: 0)
         unsigned *const o_rest = reinterpret_cast<unsigned *>(kargs->rest_wr);
         wave_lds_sync();
         if (wb_lane < 2) o_rest[RT_REST_WORD_DWORD(wb_y * wb_tiles_x + wb_x) + wb_lane] = myvd[wb_lane];
-        if (wb_lane == 2) o_rest[RT_REST_TAG_DWORD(rt_rest_tiles(kargs->width, kargs->local_rows, TW), wb_y * wb_tiles_x + wb_x)] = myvd[2];   // the tags of its records
-        if (wb_lane == 3) o_rest[RT_REST_SUMMARY_DWORD(rt_rest_tiles(kargs->width, kargs->local_rows, TW), wb_y * wb_tiles_x + wb_x)] = myvd[4];   // its summary
+        if (wb_lane == 2) o_rest[RT_REST_TAG_DWORD(rt_rest_tiles(kargs->width, kargs->local_rows, Cfg::TW), wb_y * wb_tiles_x + wb_x)] = myvd[2];   // the tags of its records
+        if (wb_lane == 3) o_rest[RT_REST_SUMMARY_DWORD(rt_rest_tiles(kargs->width, kargs->local_rows, Cfg::TW), wb_y * wb_tiles_x + wb_x)] = myvd[4];   // its summary
     }
     if (o_cost) {   // this tile's wave duration, for the order of later frames (a plain store: an atomic maximum
         // per block of tiles here, 256 waves ending together on one address, slowed the whole launch down by 3 %)
@@ -1402,7 +1224,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
     }
 
     phase(3, true);
-    if (STATS == 2 && fc.stats) {
+    if (Cfg::STATS == 2 && fc.stats) {
         if (lane == 0) {
             unsigned long long tot = 0;
             for (int k = 0; k < 8; ++k) {
@@ -1417,7 +1239,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
             (void)tot;
         }
     }
-    if (STATS == 1 && fc.stats) {
+    if (Cfg::STATS == 1 && fc.stats) {
         // per-lane counters were kept wave-uniform except hits/unshadowed
         const unsigned long long h = (unsigned long long)wave_sum((float)st_hits);
         const unsigned long long u = (unsigned long long)wave_sum((float)st_unshadowed);
@@ -1432,7 +1254,7 @@ __global__ __launch_bounds__(64, (FEAT == RT_FEAT_MESH) ? (MODE == RT_MODE_STATS
             atomicAdd(&fc.stats[7], st_overflow);
             for (int k = 0; k < 8; ++k) atomicAdd(&fc.stats[8 + k], hist[k]);
             atomicAdd(&fc.stats[17], st_walks);               // (slots 17.. hold the wave-duration histogram in RT_MODE_PHASES)
-            if (MESH) {   // mesh launches: the mesh's work instead of the penumbra counters (tools/mesh_stats.py)
+            if (Cfg::MESH) {   // mesh launches: the mesh's work instead of the penumbra counters (tools/mesh_stats.py)
                 atomicAdd(&fc.stats[18], sm_plisted);
                 atomicAdd(&fc.stats[19], sm_pleaf);
                 atomicAdd(&fc.stats[20], sm_ptri);
