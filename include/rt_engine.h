@@ -1100,6 +1100,35 @@ int rt_debug_tile_summaries(rt_scene *s, rt_tile_summaries_info *out, unsigned *
 /* Tests: overwrites the summaries of the table that the last launch wrote or read; n = tiles_x * tiles_y. Waits for
  * every launch in flight.                                                                                            */
 int rt_debug_set_tile_summaries(rt_scene *s, const unsigned *dwords, size_t n);
+/* The compact reading launch of a resting view. 1 (default): once a view's table has a run list -- built on the device
+ * from the tile summaries and primary records after the recording launch, and again after every re-sort of the tile
+ * order and every rt_debug_set_tile_summaries / rt_debug_set_primary_records -- and the builder's two counts have
+ * reached the host (the launches never wait for them: until then they keep the full grid) and say that at least a
+ * quarter of the tiles can be streamed, a reading launch starts
+ * one workgroup per run of R settled tiles, which it streams, and behind those one per tile that still computes,
+ * instead of one per tile. 0: the full grid. Both give the same frame, bit for bit. Frames recorded by rt_graph_capture, and callers of the
+ * launch configuration that have no list, keep the full grid. */
+int rt_scene_set_compact_launch(rt_scene *s, int on);
+typedef struct rt_compact_launch_info {
+    int compact;                      /* 1: the last frame launch was a compact one */
+    unsigned n_unsettled, n_streamed; /* ... its tiles with a wave of their own, and streamed in runs */
+    unsigned run, workgroups;         /* ... R, and its grid: n_unsettled + ceil(n_streamed / R) */
+    int ahead;                        /* ... 1: the runs' workgroups ahead of the others (rt_debug_set_compact_run) */
+    unsigned long long rebuilds;      /* run lists built on this scene so far */
+    int list_built;                   /* 1: the table the last launch wrote or read has a run list; then: */
+    int tiles_x, tiles_y;
+    unsigned list_n_unsettled, list_n_streamed;   /* its header */
+} rt_compact_launch_info;
+/* Tests and profiles; waits for the list's build. list (optional, `cap` = tiles): the list's entries (tile_y << 16) | tile_x,
+ * the n_unsettled tiles that keep their wave first, in the launch's order, then the streamed ones in theirs. */
+int rt_debug_compact_launch(rt_scene *s, rt_compact_launch_info *out, unsigned *list, size_t cap);
+/* Profiles and tests: R of the run lists built from now on (1 ... 64; default 64), where their runs lie in the grid
+ * (0 behind the tiles that keep their wave, 1 (default) ahead of them; a list built otherwise is rebuilt) and the share
+ * of streamed tiles, in percent of the launch's tiles, below which a launch keeps the full grid (default 25). Same frames. */
+int rt_debug_set_compact_run(rt_scene *s, int run, int ahead, int min_percent);
+/* Tests: the order that run list was built from -- the tile order at that build, or grid order -- `cap` = tiles entries
+ * (tile_y << 16) | tile_x. Waits for every launch in flight. */
+int rt_debug_compact_order(rt_scene *s, unsigned *order, size_t cap);
 /* Tests: the long-lived scene rt_launch_raytrace(_ex) and update() render through, for rt_debug_light_verdicts and
  * rt_scene_view_lists_info; owned by the library, NULL before the first launch.                                     */
 rt_scene *rt_debug_shim_scene(void);
@@ -1195,6 +1224,13 @@ int rt_debug_math(int op, const float *a, const float *b, float *out, int n);
 /* A float4 copy kernel over n16 float4s (16-byte aligned, disjoint device buffers): the copy the denoiser's traffic
  * floor is measured with (tools/bench_denoise.py). */
 int rt_debug_copy16(const void *src, void *dst, size_t n16, void *stream);
+/* What a launch of the resting-view reader's geometry costs before it computes anything (tools/launch_floor_probe.py):
+ * one-wave workgroups with the reader's LDS bytes and 72 registers. cfgs: n_cfgs triples {what, workgroups, run} --
+ * what 0: empty workgroups; 1: one scalar load each, waited for; 2: each stores the float4 and the packed word of `run`
+ * consecutive 8x8 tiles of a width x height frame (grid order; tiles beyond the frame are not written); 3: a linear
+ * float4 fill of the frame's bytes (width * height * 20; workgroups and run ignored). `rounds` interleaved rounds after
+ * `preroll` fills, `reps` launches per timing; ms[c * rounds + r] = milliseconds per launch. */
+int rt_debug_launch_floor(int width, int height, const int *cfgs, int n_cfgs, int rounds, int reps, int preroll, float *ms);
 /* sphere::intersect on the device: hit[i], t[i] for rays[i] vs spheres[i].      */
 int rt_debug_intersect(const rt_sphere *spheres, const rt_ray *rays, int n, int *hit, float *t);
 /* The 10 shadow-sample directions of castLightRay (kernel.cu:1442-1468) and its

@@ -311,6 +311,13 @@ class PrimaryRecordsInfo(C.Structure):
                 ("tiles_recorded", C.c_longlong), ("hit_pixels", C.c_longlong), ("miss_pixels", C.c_longlong)]
 
 
+class CompactLaunchInfo(C.Structure):
+    """rt_compact_launch_info."""
+    _fields_ = [("compact", C.c_int), ("n_unsettled", C.c_uint), ("n_streamed", C.c_uint), ("run", C.c_uint), ("workgroups", C.c_uint), ("ahead", C.c_int),
+                ("rebuilds", C.c_ulonglong), ("list_built", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int),
+                ("list_n_unsettled", C.c_uint), ("list_n_streamed", C.c_uint)]
+
+
 class TileSummariesInfo(C.Structure):
     """rt_tile_summaries_info."""
     _fields_ = [("state", C.c_int), ("slot", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int),
@@ -430,6 +437,10 @@ def load_library():
         "rt_debug_set_primary_records": (ci, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
         "rt_debug_tile_summaries": (ci, [vp, C.POINTER(TileSummariesInfo), C.POINTER(C.c_uint32), C.c_size_t]),
         "rt_debug_set_tile_summaries": (ci, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
+        "rt_scene_set_compact_launch": (ci, [vp, ci]),
+        "rt_debug_compact_launch": (ci, [vp, C.POINTER(CompactLaunchInfo), C.POINTER(C.c_uint32), C.c_size_t]),
+        "rt_debug_set_compact_run": (ci, [vp, ci, ci, ci]),
+        "rt_debug_compact_order": (ci, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
         "rt_scene_view_lists_info": (ci, [vp, C.POINTER(ViewListsInfo), fp, C.c_size_t]),
         "rt_debug_view_lists_host": (ci, [C.POINTER(Sphere), ci, C.POINTER(FrameDesc), C.POINTER(ViewListsInfo), fp, C.c_size_t, fp]),
         "rt_debug_tile_order": (ci, [C.POINTER(C.c_uint), ci, ci, ci, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
@@ -439,6 +450,7 @@ def load_library():
         "rt_graph_set_camera": (ci, [vp, C.POINTER(Camera)]),
         "rt_graph_destroy": (None, [vp]),
         "rt_debug_math": (ci, [ci, fp, fp, fp, ci]),
+        "rt_debug_launch_floor": (ci, [ci, ci, C.POINTER(ci), ci, ci, ci, ci, fp]),
         "rt_debug_intersect": (ci, [C.POINTER(Sphere), C.POINTER(Ray), ci, C.POINTER(ci), fp]),
         "rt_debug_light": (ci, [C.POINTER(Sphere), ci, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(Light), ci, fp, fp]),
         "rt_debug_shortcuts": (ci, [ci, C.c_uint, C.c_longlong, C.POINTER(C.c_ulonglong)]),
@@ -1024,6 +1036,38 @@ class Scene:
         dwords = np.ascontiguousarray(dwords, dtype=np.uint32)
         _check(self.lib.rt_debug_set_tile_summaries(self.handle, dwords.ctypes.data_as(C.POINTER(C.c_uint32)), dwords.size),
                "rt_debug_set_tile_summaries")
+
+    def set_compact_launch(self, on: int):
+        """1 (default): a resting view's reading launches start one workgroup per tile that still computes and one per run
+        of settled tiles, once the table's run list is built and its counts have arrived; 0: one per tile. Same frames."""
+        _check(self.lib.rt_scene_set_compact_launch(self.handle, on), "rt_scene_set_compact_launch")
+
+    def set_compact_run(self, run: int = 64, ahead: int = 1, min_percent: int = 0):
+        """Profiles and tests: settled tiles per workgroup of the compact launches whose run lists are built from now on,
+        whether those workgroups lie behind (0) or ahead of (1) the tiles that keep their wave, and the share of streamed
+        tiles (percent) below which a launch keeps the full grid -- the library's default is 25, this call's is 0."""
+        _check(self.lib.rt_debug_set_compact_run(self.handle, run, ahead, min_percent), "rt_debug_set_compact_run")
+
+    def compact_order(self, tiles: int):
+        """Tests: the order the last launch's run list was built from, uint32 [tiles]: (tile_y << 16) | tile_x."""
+        order = np.zeros(tiles, dtype=np.uint32)
+        _check(self.lib.rt_debug_compact_order(self.handle, order.ctypes.data_as(C.POINTER(C.c_uint32)), order.size), "rt_debug_compact_order")
+        return order
+
+    def compact_launch(self, want_list: bool = False) -> dict:
+        """The last frame launch's geometry (compact, n_unsettled, n_streamed, run, workgroups), the run lists built so far
+        (rebuilds) and, where the table that launch wrote or read has a run list (list_built; waits for its build), the
+        list's header (tiles_x, tiles_y, list_n_unsettled, list_n_streamed) and with want_list its entries 'list',
+        uint32 [tiles]: (tile_y << 16) | tile_x."""
+        info = CompactLaunchInfo()
+        _check(self.lib.rt_debug_compact_launch(self.handle, C.byref(info), None, 0), "rt_debug_compact_launch")
+        out = {name: getattr(info, name) for name, _ in CompactLaunchInfo._fields_}
+        if want_list and info.list_built:
+            lst = np.zeros(info.tiles_x * info.tiles_y, dtype=np.uint32)
+            _check(self.lib.rt_debug_compact_launch(self.handle, C.byref(info), lst.ctypes.data_as(C.POINTER(C.c_uint32)), lst.size),
+                   "rt_debug_compact_launch")
+            out["list"] = lst
+        return out
 
     def view_lists_info(self, want_lists: bool = False) -> dict:
         """What the last launch read (waits for the lists' build): read, block size, blocks, overflowed and not-built

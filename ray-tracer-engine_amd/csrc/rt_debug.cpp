@@ -8,6 +8,8 @@
 extern "C" hipError_t rt_dev_launch_dbg_shortcuts(int what, unsigned seed, long long n, unsigned long long *out, hipStream_t stream);
 extern "C" hipError_t rt_dev_launch_dbg_math(int op, const float *a, const float *b, float *out, int n,
                                              hipStream_t stream);
+extern "C" hipError_t rt_dev_launch_dbg_floor(int what, int workgroups, int run, const unsigned *table, float4 *rgba, unsigned *packed,
+                                              int width, int height, hipStream_t stream);
 extern "C" hipError_t rt_dev_launch_dbg_intersect(const float4 *tab, const float *rays, int n, int *hit,
                                                   float *t, hipStream_t stream);
 extern "C" hipError_t rt_dev_launch_dbg_light(const RtFrameConsts *fc, const float4 *tab, const float *starts,
@@ -330,6 +332,55 @@ extern "C" int rt_debug_view_lists_host(const rt_sphere *spheres, int n, const r
         for (int b = 0; b < p.nbx * p.nby; ++b) {
             const RtViewBeam vb = rt_view_block_beam(p, b % p.nbx, b / p.nbx);
             beams[4 * b + 0] = vb.ux; beams[4 * b + 1] = vb.uy; beams[4 * b + 2] = vb.uz; beams[4 * b + 3] = vb.ok ? vb.k : -1.f;
+        }
+    return RT_OK;
+}
+
+// What a launch of the reading kernel's geometry costs before it computes anything (tools/launch_floor_probe.py,
+// DESIGN.md 6a). cfgs: n_cfgs triples {what, workgroups, run} (rt_dev_launch_dbg_floor in rt_kernels.hip says what each
+// is). After `preroll` launches of the linear fill, `rounds` rounds; a round times every configuration once, in the
+// order given -- the rounds are interleaved, so a drift of the clock meets all of them alike --, `reps` launches
+// back to back between two events. ms[c * rounds + r]: milliseconds per launch.
+extern "C" int rt_debug_launch_floor(int width, int height, const int *cfgs, int n_cfgs, int rounds, int reps, int preroll, float *ms)
+{
+    if (width < 1 || height < 1 || width > 16384 || height > 16384 || ((size_t)width * (size_t)height) % 4 != 0 || !cfgs || n_cfgs < 1 ||
+        rounds < 1 || reps < 1 || preroll < 0 || !ms) {
+        rt_set_error("rt_debug_launch_floor: bad argument");
+        return RT_ERR_INVALID;
+    }
+    const size_t pixels = (size_t)width * (size_t)height;
+    int max_wg = 1;
+    for (int c = 0; c < n_cfgs; ++c) {
+        const int what = cfgs[3 * c], wg = cfgs[3 * c + 1], run = cfgs[3 * c + 2];
+        if (what < 0 || what > 3 || wg < 1 || wg > (1 << 22) || run < 1 || run > 4096) {
+            rt_set_error("rt_debug_launch_floor: configuration %d is {%d, %d, %d}", c, what, wg, run);
+            return RT_ERR_INVALID;
+        }
+        if (wg > max_wg) max_wg = wg;
+    }
+    DevArray<unsigned> table, packed;
+    DevArray<float4> rgba;
+    RT_HIP(table.reserve((size_t)max_wg));
+    RT_HIP(packed.reserve(pixels));
+    RT_HIP(rgba.reserve(pixels * 5 / 4));   // the linear fill writes the packed words' bytes behind the float4
+    RT_HIP(hipMemset(table.get(), 0, sizeof(unsigned) * (size_t)max_wg));
+    HipEvent e0, e1;
+    RT_HIP(e0.create(hipEventDefault));
+    RT_HIP(e1.create(hipEventDefault));
+    for (int i = 0; i < preroll; ++i)
+        RT_HIP(rt_dev_launch_dbg_floor(3, 1, 1, table.get(), rgba.get(), packed.get(), width, height, nullptr));
+    RT_HIP(hipDeviceSynchronize());
+    for (int r = 0; r < rounds; ++r)
+        for (int c = 0; c < n_cfgs; ++c) {
+            RT_HIP(rt_dev_launch_dbg_floor(cfgs[3 * c], cfgs[3 * c + 1], cfgs[3 * c + 2], table.get(), rgba.get(), packed.get(), width, height, nullptr));
+            RT_HIP(hipEventRecord(e0.get(), nullptr));
+            for (int i = 0; i < reps; ++i)
+                RT_HIP(rt_dev_launch_dbg_floor(cfgs[3 * c], cfgs[3 * c + 1], cfgs[3 * c + 2], table.get(), rgba.get(), packed.get(), width, height, nullptr));
+            RT_HIP(hipEventRecord(e1.get(), nullptr));
+            RT_HIP(hipEventSynchronize(e1.get()));
+            float t = 0.f;
+            RT_HIP(hipEventElapsedTime(&t, e0.get(), e1.get()));
+            ms[(size_t)c * rounds + r] = t / (float)reps;
         }
     return RT_OK;
 }

@@ -94,6 +94,8 @@ enum RtTraceMode : int {
     RT_MODE_REST_WRITE = 7,   // ... recording it (rest_wr): one-sample launches of sphere scenes, chosen by
                               // rt_dev_trace_config from the two pointers -- RT_MODE_PRODUCT itself carries neither the
                               // code nor the registers of either
+    RT_MODE_REST_COMPACT = 8, // RT_MODE_REST_READ with the head of a compact launch (RT_FLAG_COMPACT; rt_dev_launch_trace_grid picks it):
+                              // an instantiation of its own, so that a reading launch with the full grid runs the code it always ran
 };
 // Each FEAT is its own instantiation so that the sphere-only kernel carries neither the code nor the live scalars of
 // primitives that are not there.
@@ -230,6 +232,11 @@ enum {                          // RtFrameConsts::flags
     RT_FLAG_RESOLVE = 2,
     RT_FLAG_FORCE_SLOW = 4,
     RT_FLAG_MESH_NORMALS = 8,
+    RT_FLAG_COMPACT = 16,       // a compact reading launch (RT_MODE_REST_COMPACT; the run list of the RT_REST_* block below). The
+                                // grid is 1-D over the table's run list: the first n_ahead workgroups (list header) each stream a
+                                // run of settled tiles, the next n_unsettled render one tile each, the rest stream runs again
+                                // (n_ahead = 0: all runs behind). tile_perm points n_ahead entries in front of the list, so that
+                                // tile_perm[blockIdx.x] is a one-wave tile's entry. Set by rt_scene_prepare_rest, never part of a key.
 };
 
 // Frame uniforms used all over the kernel, by value (kernel argument -> SGPRs).
@@ -321,7 +328,7 @@ struct RtFrameConsts {
     unsigned char *rest_wr;
 };
 // The resting-view table: what a recording launch (RT_MODE_REST_WRITE) leaves for the reading launches (RT_MODE_REST_READ) of the same key, one
-// allocation of five sections, each an array over the T tiles of the launch's grid by the tile's frame coordinates
+// allocation of six sections, the first five each an array over the T tiles of the launch's grid by the tile's frame coordinates
 // (tile_y * tiles_x + tile_x, after tile_perm). This block is the layout; nothing else states it.
 //   words    a 64-bit word per tile: two bits per (group, light) for the tile's first RT_VERDICT_GROUPS groups, in the
 //            order the kernel forms them, and the first RT_VERDICT_LIGHTS lights, at 16 * group + 2 * light: 0 = evaluate,
@@ -342,6 +349,14 @@ struct RtFrameConsts {
 //            settled reader then does not load the primary records either. Bits 8-15: the tile's group count, saturating
 //            at 255 (for the read-back; no kernel reads it). A settled tile whose record says RT_PRIMARY_NONE in a valid
 //            lane (the setters only) takes the full path.
+//   list     the run list of a compact reading launch (RT_FLAG_COMPACT): RT_REST_LIST_HEADER dwords
+//            {n_unsettled, n_streamed, R, n_ahead}, then T dwords (tile_y << 16) | tile_x: a stable partition of the launch's order
+//            (tile_perm, or grid order without it). First the n_unsettled tiles that keep a wave of their own, in that
+//            order; behind them the n_streamed streamable ones -- settled, and either RT_TILE_NO_MISS or without a valid
+//            lane whose primary record says RT_PRIMARY_NONE --, which the launch's last ceil(n_streamed / R) workgroups
+//            take R at a time, or -- n_ahead = ceil(n_streamed / R), the variant the placement was measured against -- its
+//            first n_ahead. Built by rt_rest_list_launch (rt_tables.hip) from the summaries and records, not by a
+//            recording launch; rebuilt whenever those or the order change (rt_scene_rest.cpp).
 #define RT_VERDICT_GROUPS 4
 #define RT_VERDICT_LIGHTS 8
 #define RT_VERDICT_NOTHING 1u
@@ -367,7 +382,10 @@ struct RtFrameConsts {
 #define RT_REST_COUNTS_OFFSET(T) (RT_REST_TAGS_OFFSET(T) + (size_t)(T) * RT_REST_TAG_BYTES)
 #define RT_REST_PRIMARY_OFFSET(T) (RT_REST_COUNTS_OFFSET(T) + (size_t)(T) * RT_REST_COUNT_BYTES)
 #define RT_REST_SUMMARY_OFFSET(T) (RT_REST_PRIMARY_OFFSET(T) + (size_t)(T) * RT_REST_PRIMARY_BYTES)
-#define RT_REST_TABLE_BYTES(T) (RT_REST_SUMMARY_OFFSET(T) + (size_t)(T) * RT_REST_SUMMARY_BYTES)
+#define RT_REST_LIST_HEADER 4u           // dwords in front of the list's T entries
+#define RT_REST_LIST_RUN_MAX 64u        // R <= a wave's lanes: a run's entries are one load
+#define RT_REST_LIST_OFFSET(T) (RT_REST_SUMMARY_OFFSET(T) + (size_t)(T) * RT_REST_SUMMARY_BYTES)
+#define RT_REST_TABLE_BYTES(T) (RT_REST_LIST_OFFSET(T) + 4u * (RT_REST_LIST_HEADER + (size_t)(T)))
 #define RT_REST_FILL_BYTES(T) RT_REST_COUNTS_OFFSET(T)   // filled with ones before a recording launch: the words and the tags
 // a tile's word (halves at + 0 and + 1) and its tags, in dwords from the table's first
 #define RT_REST_WORD_DWORD(tile) ((RT_REST_WORD_BYTES / 4u) * (size_t)(tile))
@@ -377,7 +395,8 @@ static_assert(RT_REST_TAGS_OFFSET(7) == 8u * 7, "resting-view table: the tags li
 static_assert(RT_REST_COUNTS_OFFSET(7) == 12u * 7 && RT_REST_FILL_BYTES(7) == RT_REST_COUNTS_OFFSET(7), "resting-view table: the fill ends where the counts begin");
 static_assert(RT_REST_PRIMARY_OFFSET(7) == (12u + 64u * RT_SHADOW_RECORDS) * 7, "resting-view table: the primary records lie behind the counts");
 static_assert(RT_REST_SUMMARY_OFFSET(7) == RT_REST_PRIMARY_OFFSET(7) + 256u * 7, "resting-view table: the tile summaries lie behind a dword per lane");
-static_assert(RT_REST_TABLE_BYTES(7) == RT_REST_SUMMARY_OFFSET(7) + 4u * 7, "resting-view table: a dword per tile ends it");
+static_assert(RT_REST_LIST_OFFSET(7) == RT_REST_SUMMARY_OFFSET(7) + 4u * 7, "resting-view table: the run list lies behind a dword per tile");
+static_assert(RT_REST_TABLE_BYTES(7) == RT_REST_LIST_OFFSET(7) + 4u * (4 + 7), "resting-view table: a header and a dword per tile end it");
 
 // T and its factors: one 64-pixel tile of tile_w x 64 / tile_w per workgroup, over the launch's `width` x `local_rows`
 __host__ __device__ inline unsigned rt_rest_tiles_x(int width, int tile_w) { return (unsigned)(width + tile_w - 1) / (unsigned)tile_w; }

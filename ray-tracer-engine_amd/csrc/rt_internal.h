@@ -116,6 +116,19 @@ public:
         return e;
     }
     bool pending() const { return pending_; }
+    // *done: whether the last record() has completed; never waits. "Not ready" is the only answer taken for "no":
+    // any other error of the query (or an earlier asynchronous one it reports) is returned.
+    hipError_t complete(bool *done)
+    {
+        if (pending_) {
+            const hipError_t e = hipEventQuery(ev_.get());
+            if (e == hipSuccess) pending_ = false;
+            else if (e == hipErrorNotReady) (void)hipGetLastError();
+            else return e;
+        }
+        *done = !pending_;
+        return hipSuccess;
+    }
 
 private:
     HipEvent ev_;
@@ -173,6 +186,10 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
                                           const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes);
 extern "C" hipError_t rt_dev_launch_trace(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
                                           int feat, hipStream_t stream);
+// ... with the 1-D grid of a compact reading launch (workgroups > 0: fc carries RT_FLAG_COMPACT and a table with a run
+// list; rt_dev_trace_config knows no list and always gives the full grid)
+extern "C" hipError_t rt_dev_launch_trace_grid(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
+                                               int feat, unsigned workgroups, hipStream_t stream);
 
 // rt_sphere_bvh.cpp: the scene's sphere BVH (rt_bvh.h), shared by reflective frames and ray queries
 struct RtSphereBvh;

@@ -193,6 +193,44 @@ __global__ void rt_dbg_shortcuts(int what, unsigned seed, long long n, unsigned 
     }
 }
 
+// What a launch of the reading kernel's geometry costs before it computes anything (rt_debug_launch_floor,
+// tools/launch_floor_probe.py): one-wave workgroups with the frame kernel's LDS and a register
+// allocation of 72 (the clobber of v71 is what allocates them: the wave then takes the reader's share of a SIMD).
+//   what 0  nothing
+//   what 1  one scalar load per workgroup, waited for
+//   what 2  the float4 and the packed word of `run` consecutive 8x8 tiles (grid order) per workgroup
+template <int WHAT>
+__global__ __launch_bounds__(64, RT_MIN_WAVES_ONE_SAMPLE) void rt_dbg_launch_floor(const unsigned *__restrict__ table, float4 *rgba, unsigned *packed,
+                                                                                int width, int height, int run)
+{
+    asm volatile("" ::: "v71");
+    if (WHAT == 1) {
+        const unsigned d = table[blockIdx.x];   // wave-uniform: a scalar load
+        asm volatile("" ::"s"(d));              // ... and its wait
+    }
+    if (WHAT == 2) {
+        const int lane = threadIdx.x & 63;
+        const unsigned tiles_x = rt_rest_tiles_x(width, 8), tiles = tiles_x * rt_rest_tiles_y(height, 8);
+        for (int r = 0; r < run; ++r) {
+            const unsigned tile = blockIdx.x * (unsigned)run + (unsigned)r;
+            if (tile >= tiles) break;
+            const int px = (int)(tile % tiles_x) * 8 + (lane & 7), py = (int)(tile / tiles_x) * 8 + (lane >> 3);
+            if (px < width && py < height) {
+                const size_t o = (size_t)py * (size_t)width + (size_t)px;
+                rgba[o] = make_float4(0.f, 0.f, 0.f, 1.f);
+                packed[o] = 0u;
+            }
+        }
+    }
+}
+
+// what 3: the ceiling -- `n` float4 stored linearly, 16 bytes per lane and 1 KiB per wave-instruction
+__global__ __launch_bounds__(256) void rt_dbg_linear_fill(float4 *out, size_t n)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = make_float4(0.f, 0.f, 0.f, 1.f);
+}
+
 }  // namespace
 
 RtTraceFn rt_trace_fn_cull8(int mode, int feat, int multi)
@@ -216,6 +254,7 @@ static RtTraceFn trace_fn(int tile_w, int cull, int mode, int feat, int multi)
 
 // Everything a launch of the frame kernel needs besides its two arguments: one 64-thread
 // workgroup per tile. hipErrorNotSupported: no such instantiation.
+// (The full grid always: this function has no run list. The compact grid of a reading launch is rt_dev_launch_trace_grid's.)
 extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, int cull, int mode, int feat,
                                           const void **func, dim3 *grid, dim3 *block, unsigned *lds_bytes)
 {
@@ -230,15 +269,45 @@ extern "C" hipError_t rt_dev_trace_config(const RtFrameConsts *fc, int tile_w, i
     return hipSuccess;
 }
 
-extern "C" hipError_t rt_dev_launch_trace(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
-                                          int feat, hipStream_t stream)
+extern "C" hipError_t rt_dev_launch_trace_grid(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
+                                               int feat, unsigned workgroups, hipStream_t stream)
 {
     const void *func = nullptr;
     dim3 grid, block;
     unsigned lds_bytes = 0;
     const hipError_t ce = rt_dev_trace_config(fc, tile_w, cull, mode, feat, &func, &grid, &block, &lds_bytes);
     if (ce != hipSuccess) return ce;
+    // a compact reading launch: RT_FLAG_COMPACT and the 1-D grid go together, and only with a table to read
+    if (((fc->flags & RT_FLAG_COMPACT) != 0) != (workgroups > 0) || (workgroups > 0 && (!fc->rest_rd || fc->rest_wr || !fc->tile_perm))) return hipErrorInvalidValue;
+    if (workgroups > 0) {   // the reader with the compact head: an instantiation of its own
+        func = (const void *)trace_fn(tile_w, cull, RT_MODE_REST_COMPACT, feat, fc->spp > 1 ? 1 : 0);
+        if (!func) return hipErrorNotSupported;
+        grid = dim3(workgroups);
+    }
     hipLaunchKernelGGL((RtTraceFn)func, grid, block, lds_bytes, stream, *fc, spheres);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rt_dev_launch_trace(const RtFrameConsts *fc, const float4 *spheres, int tile_w, int cull, int mode,
+                                          int feat, hipStream_t stream)
+{
+    return rt_dev_launch_trace_grid(fc, spheres, tile_w, cull, mode, feat, 0, stream);
+}
+
+// One launch of the probe: `workgroups` one-wave workgroups with the reader's block size and LDS bytes (what 0 - 2; the
+// caller sizes the grid so that workgroups * run covers the tiles it wants written), or the linear fill of the
+// frame's bytes, float4 and packed word together: width * height * 5 / 4 float4 from `rgba` on (what 3).
+extern "C" hipError_t rt_dev_launch_dbg_floor(int what, int workgroups, int run, const unsigned *table, float4 *rgba, unsigned *packed,
+                                              int width, int height, hipStream_t stream)
+{
+    const unsigned lds_bytes = rt_trace_lds_bytes(RT_FEAT_SPHERES);
+    switch (what) {
+    case 0: hipLaunchKernelGGL(rt_dbg_launch_floor<0>, dim3(workgroups), dim3(64), lds_bytes, stream, table, rgba, packed, width, height, run); break;
+    case 1: hipLaunchKernelGGL(rt_dbg_launch_floor<1>, dim3(workgroups), dim3(64), lds_bytes, stream, table, rgba, packed, width, height, run); break;
+    case 2: hipLaunchKernelGGL(rt_dbg_launch_floor<2>, dim3(workgroups), dim3(64), lds_bytes, stream, table, rgba, packed, width, height, run); break;
+    case 3: hipLaunchKernelGGL(rt_dbg_linear_fill, dim3(2048), dim3(256), 0, stream, rgba, (size_t)width * (size_t)height * 5 / 4); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

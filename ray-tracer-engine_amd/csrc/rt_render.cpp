@@ -393,7 +393,9 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
     }
     // the resting-view table: the plain one-sample frame of a sphere scene (not a reflective frame, whose passes follow)
     int rest = -1;
-    rc = rt_scene_prepare_rest(s, kc, &fc, reflect_depth == 0 && kc.mode == RT_MODE_PRODUCT && kc.feat == RT_FEAT_SPHERES && kc.cull && fc.spp == 1, stream, &rest);
+    unsigned compact_wgs = 0;   // the 1-D grid of a compact reading launch, 0: the full grid
+    rc = rt_scene_prepare_rest(s, kc, &fc, reflect_depth == 0 && kc.mode == RT_MODE_PRODUCT && kc.feat == RT_FEAT_SPHERES && kc.cull && fc.spp == 1, stream, &rest,
+                               samples ? nullptr : &compact_wgs);
     if (rc != RT_OK) return rc;
     if (samples) {   // the frame kernel per sample, the passes per group, the resolve pass
         rc = rt_reflect_launch_samples(s->refl.get(), &fc, &out, &kc, s->d_spheres.get(), s->n_spheres, reflect_depth, stream);
@@ -403,7 +405,7 @@ extern "C" int rt_scene_render(rt_scene *s, const rt_frame_desc *fd_in, void *st
             rc = rt_reflect_mark_frame_start(s->refl.get(), stream);
             if (rc != RT_OK) return rc;
         }
-        RT_HIP(rt_dev_launch_trace(&fc, s->d_spheres.get(), kc.tile, kc.cull, kc.mode, kc.feat, stream));
+        RT_HIP(rt_dev_launch_trace_grid(&fc, s->d_spheres.get(), kc.tile, kc.cull, kc.mode, kc.feat, compact_wgs, stream));
         if (reflect_depth > 0) {
             rc = rt_reflect_launch(s->refl.get(), &fc, s->d_spheres.get(), s->n_spheres, reflect_depth, kc.cull == 0, stream);
             if (rc != RT_OK) return rc;

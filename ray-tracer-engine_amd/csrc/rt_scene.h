@@ -72,9 +72,32 @@ struct RtRestKey {
     unsigned long long sphere_gen = 0;    // ... and of the sphere list (tables built from it: cones, view lists, light tables)
     int tile = 0, cull = 0, mode = 0, feat = 0;
 };
+// The run list of a compact reading launch (the table's list section) is built by rt_rest_list_launch on the stream of the
+// reading launch that finds it stale -- never built, or built from another order than the launch's (list_perm,
+// list_order_serial) or with another R, or from sections a setter has rewritten since -- behind every frame launched so
+// far, as a tile-order sort is; `list_done` is that build, and compact launches on other streams wait for it on the
+// device. The host needs the list's two counts for the grid. They depend on the summaries and records alone -- another
+// order re-orders the list and leaves them as they are --, so they are fetched once per content of those sections:
+// the build copies the header into `list_counts` (pinned), and the first launch that finds list_done complete adopts
+// them; no launch waits for that on the host, and until then reading launches keep the full grid and do not look at the list.
 struct RestSlot : RtTableSlot {          // buf: RT_REST_TABLE_BYTES(tiles), the layout of rt_device.h
     RtRestKey key;
     int tiles_x = 0, tiles_y = 0;
+    bool list_built = false;              // a build from the table's present sections is enqueued or done
+    bool list_adopted = false;            // the counts of the table's present sections are in list_n
+    const unsigned *list_perm = nullptr;  // the order the list was built from (null: grid order)
+    unsigned long long list_order_serial = 0;   // TileOrder::serial of that order at that build
+    unsigned list_run = 0;                // R of that build
+    unsigned list_ahead = 0;              // ... and where it put the runs (RtRestListParams::ahead)
+    unsigned list_n[2] = {0, 0};          // n_unsettled, n_streamed
+    PinnedArray<unsigned> list_counts;    // RT_REST_LIST_HEADER dwords, copied behind every build
+    DevArray<unsigned> list_scratch;      // the builder's (rt_rest_list_scratch)
+    HipPendingEvent list_done;            // the last build and its copy
+};
+// What the last launch's geometry was (rt_debug_compact_launch).
+struct RtCompactLast {
+    int compact = 0, ahead = 0;
+    unsigned n_unsettled = 0, n_streamed = 0, run = 0, workgroups = 0;
 };
 
 // The slot a new table replaces: a free one (is_free: it holds nothing a frame could ask for) before an occupied one;
@@ -94,6 +117,9 @@ struct RtReflectDeleter {
     void operator()(RtReflect *r) const { rt_reflect_destroy(r); }
 };
 
+#define RT_COMPACT_RUN 64           // settled tiles per workgroup of a compact reading launch, and (RT_COMPACT_AHEAD) those
+#define RT_COMPACT_MIN_PERCENT 25   // ... and only where at least this share of the tiles is streamed (C3: 68 %, 18 % faster; C5: 8 %, 3.5 % slower)
+#define RT_COMPACT_AHEAD 1          // workgroups ahead of the one-wave tiles': both by measurement, DESIGN.md 4, step 5e
 #define RT_ORDER_SLOTS 4
 #define RT_ORDER_EVERY 32            // an unchanged view: the order is sorted again from fresh durations every so many launches
 #ifndef RT_ORDER_MOVING
@@ -109,6 +135,7 @@ struct TileOrder {
     int since_sort = 0;                          // launches (all of which recorded durations) since the order was sorted / reset
     bool have_perm = false;
     unsigned long long last_use = 0;
+    unsigned long long serial = 0;               // of its last sort or reset: a run list built from an earlier one is stale
 };
 
 // One kind's emission table: what the host last set, and a device copy that changes only in an indirect call, behind
@@ -219,6 +246,8 @@ struct rt_scene {
     unsigned long long order_clock = 0;      // for least-recently-used replacement
     int tile_order_mode = 1;                 // rt_scene_set_tile_order
     HipPendingEvent order_built;             // the last rebuild; launches on other streams wait for it on the device
+    unsigned long long order_serial = 0;     // counts the sorts and resets of all orders; TileOrder::serial takes its values
+    unsigned long long order_cur_serial = 0; // the serial of the order the launch being prepared starts its tiles in
     // per-view candidate lists of the primary rays
     ViewSlot views[RT_VIEW_SLOTS];
     int view_lists_mode = 1;                 // rt_scene_set_view_lists
@@ -231,6 +260,12 @@ struct rt_scene {
     int rest_seen_next = 0;                  // the entry the next such key replaces
     int rest_last = -1;                      // the slot the last launch wrote or read, -1: neither
     int rest_last_wrote = 0;                 // 1: it wrote it
+    int compact_mode = 1;                    // rt_scene_set_compact_launch
+    unsigned compact_run = RT_COMPACT_RUN;   // R of the lists built from now on (rt_debug_set_compact_run)
+    unsigned compact_min_percent = RT_COMPACT_MIN_PERCENT;   // ... and the share of streamed tiles below which a launch keeps the full grid
+    unsigned compact_ahead = RT_COMPACT_AHEAD;   // ... and the runs' place: 0 behind the one-wave tiles, 1 ahead of them
+    unsigned long long list_rebuilds = 0;    // run lists built so far, all slots
+    RtCompactLast compact_last;              // the last frame launch's geometry
     // mirror reflections (rt_reflect.hip): materials, sphere BVH, queues; created on first use
     std::unique_ptr<RtReflect, RtReflectDeleter> refl;
     // the post passes: what orders each one's calls, and each timed entry's timing state (guided upsampling,
@@ -282,7 +317,8 @@ int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameCo
 // rt_scene_rest.cpp: the resting-view table of a launch whose uniforms are otherwise complete. `eligible`: it runs the one-sample sphere-only
 // product kernel. Points fc at the table it reads or writes (slot index in *slot_out, -1: neither); after the launch
 // rt_scene_end_rest records a written table.
-int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out);
+// *workgroups_out: the 1-D grid of a compact reading launch (fc then carries RT_FLAG_COMPACT and the run list in tile_perm), 0: the full grid.
+int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out, unsigned *workgroups_out);
 int rt_scene_end_rest(rt_scene *s, int slot, hipStream_t stream);
 int rt_scene_prepare_raygen(rt_scene *s, int width, int height, float aspect, int total);
 void rt_raygen_fill(int width, int height, float aspect, int total, float *h);   // the tables' values (host)

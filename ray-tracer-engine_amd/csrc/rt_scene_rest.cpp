@@ -28,9 +28,91 @@ static void rest_key(const rt_scene *s, const RtKernelChoice &kc, const RtFrameC
     k->tile = kc.tile; k->cull = kc.cull; k->mode = kc.mode; k->feat = kc.feat;
 }
 
-int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out)
+// The compact reading launch of a launch that reads table c: rebuilds the table's run list when
+// it is stale, adopts the builder's counts once they have arrived, and then points the launch at the list. The rules
+// are beside RestSlot (rt_scene.h). *workgroups: the 1-D grid, 0 = the full grid, which gives the same frame.
+static int rest_run_list(rt_scene *s, RestSlot &c, const RtKernelChoice &kc, RtFrameConsts *fc, hipStream_t stream, unsigned *workgroups)
+{
+    const size_t tiles = (size_t)c.tiles_x * (size_t)c.tiles_y;
+    if (!s->compact_mode || c.tiles_x > 0xffff || c.tiles_y > 0xffff || !rt_rest_list_fits(tiles)) return RT_OK;
+    unsigned char *table = reinterpret_cast<unsigned char *>(c.buf.get());
+    const unsigned long long serial = fc->tile_perm ? s->order_cur_serial : 0;
+    // A build costs three small launches and a copy on the frame's stream, and a view that rests for a dozen frames
+    // while the host runs ahead of the device would pay for it and never see a compact frame (bench.py's held positions:
+    // 9 % slower with a build at every first read and re-sort). So: no first build before the device has finished the
+    // recording launch -- a host that is further ahead than that is not looking at a view known to rest --, and no
+    // rebuild for another order before the counts of the build before have arrived, i.e. before compact launches can
+    // follow it at all.
+    bool stale = c.list_perm != fc->tile_perm || c.list_order_serial != serial || c.list_run != s->compact_run || c.list_ahead != s->compact_ahead;
+    bool arrived = false;
+    if (!c.list_built) RT_HIP(c.built.complete(&arrived));
+    else if (!c.list_adopted) RT_HIP(c.list_done.complete(&arrived));
+    if (!c.list_built ? !arrived : (stale && !c.list_adopted && !arrived)) return RT_OK;   // this launch keeps the full grid
+    if (c.list_built && !c.list_adopted && arrived) {
+        c.list_n[0] = c.list_counts.get()[0];
+        c.list_n[1] = c.list_counts.get()[1];
+        c.list_adopted = true;
+    }
+    // The reader with the compact head (MODE 8) renders a one-wave tile some 4 % slower than MODE 6 does: with few tiles
+    // to stream the full grid is the faster launch, and nothing is rebuilt for it.
+    if (c.list_adopted && (unsigned long long)c.list_n[1] * 100ull < (unsigned long long)s->compact_min_percent * tiles) return RT_OK;
+    if (!c.list_built || stale) {
+        const int rc = rt_scene_wait_all_frames(s, stream);   // frames in flight read the list that is rewritten
+        if (rc != RT_OK) return rc;
+        RT_HIP(c.list_counts.reserve(RT_REST_LIST_HEADER));
+        RT_HIP(c.list_scratch.reserve(rt_rest_list_scratch(tiles)));
+        RtRestListParams p;
+        p.table = table;
+        p.perm = fc->tile_perm;
+        p.scratch = c.list_scratch.get();
+        p.tile_w = kc.tile; p.width = fc->width; p.local_rows = fc->local_rows; p.y0 = fc->y0; p.y1 = fc->y1;
+        p.il_count = fc->il_count; p.il_index = fc->il_index; p.il_rows = fc->il_rows;
+        p.run = s->compact_run;
+        p.ahead = s->compact_ahead;
+        RT_HIP(rt_rest_list_launch(p, stream));
+        RT_HIP(hipMemcpyAsync(c.list_counts.get(), table + RT_REST_LIST_OFFSET(tiles), sizeof(unsigned) * RT_REST_LIST_HEADER, hipMemcpyDeviceToHost, stream));
+        RT_HIP(c.list_done.record(stream));
+        c.list_built = true;
+        c.list_perm = fc->tile_perm;
+        c.list_order_serial = serial;
+        c.list_run = s->compact_run;
+        c.list_ahead = s->compact_ahead;
+        s->list_rebuilds++;
+    }
+    if (!c.list_adopted) {
+        bool done = false;
+        RT_HIP(c.list_done.complete(&done));
+        if (!done) return RT_OK;   // this launch keeps the full grid
+        c.list_n[0] = c.list_counts.get()[0];
+        c.list_n[1] = c.list_counts.get()[1];
+        c.list_adopted = true;
+    }
+    RT_HIP(c.list_done.order(stream));   // a build for another order that is still under way (another stream's: a device-side wait)
+    if ((size_t)c.list_n[0] + (size_t)c.list_n[1] != tiles) {
+        rt_set_error("rt_scene_render: a run list of %u + %u tiles for a table of %zu", c.list_n[0], c.list_n[1], tiles);
+        return RT_ERR_INVALID;
+    }
+    // The one-wave tiles' workgroups find their entry at tile_perm[blockIdx.x]: with the runs ahead of them (the measured
+    // variant) the pointer is set back by the runs' workgroups, and no workgroup reads in front of the list.
+    const unsigned n_runs = (c.list_n[1] + c.list_run - 1) / c.list_run;
+    const uintptr_t list = reinterpret_cast<uintptr_t>(table + RT_REST_LIST_OFFSET(tiles)) + sizeof(unsigned) * RT_REST_LIST_HEADER;
+    fc->tile_perm = reinterpret_cast<const unsigned *>(list - (c.list_ahead ? sizeof(unsigned) * (size_t)n_runs : 0));
+    fc->flags |= RT_FLAG_COMPACT;
+    *workgroups = c.list_n[0] + n_runs;
+    s->compact_last.compact = 1;
+    s->compact_last.n_unsettled = c.list_n[0];
+    s->compact_last.n_streamed = c.list_n[1];
+    s->compact_last.run = c.list_run;
+    s->compact_last.ahead = (int)c.list_ahead;
+    s->compact_last.workgroups = *workgroups;
+    return RT_OK;
+}
+
+int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *fc, bool eligible, hipStream_t stream, int *slot_out, unsigned *workgroups_out)
 {
     *slot_out = -1;
+    if (workgroups_out) *workgroups_out = 0;
+    s->compact_last = RtCompactLast();
     s->rest_last = -1;
     s->rest_last_wrote = 0;
     if (!s->light_verdicts_mode)
@@ -54,6 +136,10 @@ int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *
         RT_HIP(rt_scene_order_reader(c, stream));   // the writing launch precedes its readers
         fc->rest_rd = reinterpret_cast<const unsigned char *>(c.buf.get());
         *slot_out = v;
+        if (workgroups_out) {
+            const int rc = rest_run_list(s, c, kc, fc, stream, workgroups_out);
+            if (rc != RT_OK) return rc;
+        }
     } else if (seen >= 0) {
         s->rest_seen_valid[seen] = false;
         RestSlot &c = rt_slot_victim(s->rest, [](const RestSlot &x) { return !x.valid; });
@@ -64,6 +150,8 @@ int rt_scene_prepare_rest(rt_scene *s, const RtKernelChoice &kc, RtFrameConsts *
             RT_HIP(c.built.host_wait());
         }
         c.valid = false;
+        c.list_built = false;   // the run list of what the slot held
+        c.list_adopted = false;
         RT_HIP(c.buf.reserve(total));
         // on the frame's stream: behind the slot's last writer and, through the frame ring, its last reader
         RT_HIP(c.built.order(stream));
@@ -308,6 +396,7 @@ extern "C" int rt_debug_set_primary_records(rt_scene *s, const unsigned *dwords,
     const int rc = last_table_to_set(s, dwords != nullptr, "rt_debug_set_primary_records", n, 64, "records", " tiles of 64", &c);
     if (rc != RT_OK) return rc;
     RT_HIP(copy_section(*c, RT_REST_PRIMARY_OFFSET(tiles_of(*c)), sizeof(unsigned) * n, const_cast<unsigned *>(dwords), hipMemcpyHostToDevice));
+    c->list_built = c->list_adopted = false;   // the run list was built from the records
     return RT_OK;
 }
 
@@ -342,5 +431,86 @@ extern "C" int rt_debug_set_tile_summaries(rt_scene *s, const unsigned *dwords, 
     const int rc = last_table_to_set(s, dwords != nullptr, "rt_debug_set_tile_summaries", n, 1, "tiles", "", &c);
     if (rc != RT_OK) return rc;
     RT_HIP(copy_section(*c, RT_REST_SUMMARY_OFFSET(n), RT_REST_SUMMARY_BYTES * n, const_cast<unsigned *>(dwords), hipMemcpyHostToDevice));
+    c->list_built = c->list_adopted = false;   // the run list was built from the summaries
+    return RT_OK;
+}
+
+// The compact reading launch: the switch, R, and what the last frame launch did.
+extern "C" int rt_scene_set_compact_launch(rt_scene *s, int on)
+{
+    if (!s || (on != 0 && on != 1)) {
+        rt_set_error("rt_scene_set_compact_launch: null scene or %d not in {0, 1}", on);
+        return RT_ERR_INVALID;
+    }
+    s->compact_mode = on;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_set_compact_run(rt_scene *s, int run, int ahead, int min_percent)
+{
+    if (!s || run < 1 || run > (int)RT_REST_LIST_RUN_MAX || (ahead != 0 && ahead != 1) || min_percent < 0 || min_percent > 100) {
+        rt_set_error("rt_debug_set_compact_run: null scene, %d not in 1 ... %u, %d not in {0, 1} or %d not in 0 ... 100", run, RT_REST_LIST_RUN_MAX, ahead, min_percent);
+        return RT_ERR_INVALID;
+    }
+    s->compact_run = (unsigned)run;
+    s->compact_ahead = (unsigned)ahead;
+    s->compact_min_percent = (unsigned)min_percent;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_compact_launch(rt_scene *s, rt_compact_launch_info *out, unsigned *list, size_t cap)
+{
+    if (!s || !out) {
+        rt_set_error("rt_debug_compact_launch: null argument");
+        return RT_ERR_INVALID;
+    }
+    memset(out, 0, sizeof *out);
+    out->compact = s->compact_last.compact;
+    out->n_unsettled = s->compact_last.n_unsettled;
+    out->n_streamed = s->compact_last.n_streamed;
+    out->run = s->compact_last.run;
+    out->ahead = s->compact_last.ahead;
+    out->workgroups = s->compact_last.workgroups;
+    out->rebuilds = s->list_rebuilds;
+    if (s->rest_last < 0 || !s->rest[s->rest_last].valid || !s->rest[s->rest_last].list_built) return RT_OK;
+    RestSlot &c = s->rest[s->rest_last];
+    RT_HIP(c.list_done.host_wait());
+    out->list_built = 1;
+    out->tiles_x = c.tiles_x;
+    out->tiles_y = c.tiles_y;
+    out->list_n_unsettled = c.list_counts.get()[0];
+    out->list_n_streamed = c.list_counts.get()[1];
+    if (list) {
+        const size_t n = tiles_of(c);
+        if (cap < n) {
+            rt_set_error("rt_debug_compact_launch: room for %zu tiles, the list has %zu", cap, n);
+            return RT_ERR_INVALID;
+        }
+        RT_HIP(copy_section(c, RT_REST_LIST_OFFSET(n) + 4u * RT_REST_LIST_HEADER, sizeof(unsigned) * n, list, hipMemcpyDeviceToHost));
+    }
+    return RT_OK;
+}
+
+// The order the last launch's run list was built from, (tile_y << 16) | tile_x per place: the tile order's perm[] at that
+// build, or grid order where the launch had none. Waits for the list's build. (Tests: the list must be a stable
+// partition of exactly this.)
+extern "C" int rt_debug_compact_order(rt_scene *s, unsigned *order, size_t cap)
+{
+    if (!s || !order || s->rest_last < 0 || !s->rest[s->rest_last].valid || !s->rest[s->rest_last].list_built) {
+        rt_set_error("rt_debug_compact_order: null argument, or the last launch's table has no run list");
+        return RT_ERR_INVALID;
+    }
+    RestSlot &c = s->rest[s->rest_last];
+    const size_t n = tiles_of(c);
+    if (cap < n) {
+        rt_set_error("rt_debug_compact_order: room for %zu tiles, the order has %zu", cap, n);
+        return RT_ERR_INVALID;
+    }
+    const int rc = rt_scene_quiesce(s);   // (no sort under way)
+    if (rc != RT_OK) return rc;
+    RT_HIP(c.list_done.host_wait());
+    if (c.list_perm) RT_HIP(hipMemcpy(order, c.list_perm, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
+    else
+        for (size_t i = 0; i < n; ++i) order[i] = (unsigned)((i / (size_t)c.tiles_x) << 16) | (unsigned)(i % (size_t)c.tiles_x);
     return RT_OK;
 }

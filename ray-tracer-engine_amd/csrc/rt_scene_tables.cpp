@@ -362,6 +362,7 @@ int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameCo
         t->same_view = 0;
         t->since_sort = 0;
         t->have_perm = false;
+        t->serial = ++s->order_serial;
         RT_HIP(s->order_built.record(stream));   // launches on other streams: after the reset
     } else {
         if (memcmp(t->view, view, sizeof view) != 0) {
@@ -378,6 +379,7 @@ int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameCo
             RT_HIP(rt_tile_order_launch(t->buf.cost(), t->buf.key(), t->buf.start(), t->buf.perm(), t->grid.tiles_x, t->grid.tiles_y,
                                         stream));
             RT_HIP(s->order_built.record(stream));
+            t->serial = ++s->order_serial;   // a run list built from the order before is stale (rt_scene_rest.cpp)
             t->have_perm = true;
             t->since_sort = 0;
         }
@@ -387,6 +389,7 @@ int rt_scene_prepare_tile_order(rt_scene *s, const RtKernelChoice &kc, RtFrameCo
     t->last_use = ++s->order_clock;
     fc->tile_cost = t->buf.cost();
     fc->tile_perm = t->have_perm ? t->buf.perm() : nullptr;
+    s->order_cur_serial = t->serial;
     return RT_OK;
 }
 

@@ -58,7 +58,8 @@ struct TraceCfg {
     // the wave's LDS ahead of the light loop and consumed there two bits at a time. RT_MODE_REST_WRITE: the word this launch finds
     // is gathered in the same place and stored at the write-back. Nothing of it is held in a register across the light
     // loop, whose scalar and vector files are full.
-    static constexpr bool VD_USE = (MODE == RT_MODE_REST_READ), VD_REC = (MODE == RT_MODE_REST_WRITE), VERD = VD_USE || VD_REC;
+    static constexpr bool COMPACT = (MODE == RT_MODE_REST_COMPACT);   // the reader with the compact launch's head (step 5e)
+    static constexpr bool VD_USE = (MODE == RT_MODE_REST_READ || COMPACT), VD_REC = (MODE == RT_MODE_REST_WRITE), VERD = VD_USE || VD_REC;
     static_assert(!VERD || (CULL && FEAT == RT_FEAT_SPHERES), "light verdicts: the sphere-only culling kernels");
     // A reading launch forms a group's ball (g_r2, the check against its sphere's ball: two wave reductions) only where a
     // light of the group culls at all: 3.4 % of the 0.136 lights per tile that it still walks at C3. (RT_EAGER_BALL: the
@@ -119,6 +120,94 @@ __device__ __forceinline__ unsigned resolve_pixel(float acc_r, float acc_g, floa
         mb = acc_b / o_total;
     }
     return rgb_to_int(f2i(mr * 254.f), f2i(mg * 254.f), f2i(mb * 254.f));
+}
+
+// ---------------------------------------------------------------------------
+// the compact reading launch: a run of streamable tiles (step 5e)
+// ---------------------------------------------------------------------------
+// Entries [first, first + count) of the table's run list `list` (count <= RT_REST_LIST_RUN_MAX, wave-uniform), each of them a
+// settled tile that needs neither the full path nor a table staged. Per tile what a settled tile's wave does in
+// rt_trace_tiles, by the same expressions: its place, the valid lanes, the sample's sum (0 for a hit lane, the sky texel
+// on record through the clamp for a miss lane), one write-back, its own duration into tile_cost. The entries and their
+// summaries are asked for once for the whole run, a lane each. No LDS; the frame uniforms of the write-back come from
+// the kernel-argument segment here, so that the one-wave path beside this one holds none of them.
+template <class Cfg>
+__device__ __forceinline__ void stream_settled_run(const RtFrameConsts &fc, AuxPtr ax, const unsigned *list, int lane, unsigned first, unsigned count)
+{
+    const unsigned s_tiles_x = (unsigned)(fc.width + Cfg::TW - 1) / (unsigned)Cfg::TW;
+    const unsigned s_tiles = s_tiles_x * rt_rest_tiles_y(fc.local_rows, Cfg::TW);
+    unsigned my_p = 0, my_ts = 0;
+    if ((unsigned)lane < count) {
+        my_p = list[first + (unsigned)lane];
+        my_ts = reinterpret_cast<const unsigned *>(fc.rest_rd)[RT_REST_SUMMARY_DWORD(s_tiles, (my_p >> 16) * s_tiles_x + (my_p & 0xffffu))];
+    }
+    FcPtr kargs = kargs_again();
+    float *const o_rgba = kargs->rgba;
+    uint32_t *const o_packed = kargs->packed, *const o_packed24 = kargs->packed24;
+    unsigned *const o_cost = kargs->tile_cost;
+    const int o_flags = kargs->flags;
+    const float o_total = kargs->sample_total;
+    const int il_sh = __builtin_ctz((unsigned)fc.il_rows);
+    // (The other tile shapes' readers are the sample-loop kernels, MULTI, and a launch that reads a table takes one sample:
+    // the count is 1 in every launch there is. It is spelt as the kernel spells it so that the two cannot drift apart.)
+    const int n_samples = Cfg::MULTI ? fc.spp : 1;
+    for (unsigned r = 0; r < count; ++r) {
+        const unsigned t_start = o_cost ? (unsigned)__builtin_amdgcn_s_memtime() : 0u;
+        const unsigned p = (unsigned)__builtin_amdgcn_readlane((int)my_p, (int)r), ts = (unsigned)__builtin_amdgcn_readlane((int)my_ts, (int)r);
+        const unsigned blk_x = p & 0xffffu, blk_y = p >> 16;
+        const int ly = (int)blk_y * Cfg::TH + (lane / Cfg::TW);
+        const int px = (int)blk_x * Cfg::TW + (lane % Cfg::TW);
+        const int py = fc.y0 + ((((ly >> il_sh) * fc.il_count + fc.il_index) << il_sh) | (ly & (fc.il_rows - 1)));
+        const lmask valid_m = LM(px < fc.width) & LM(ly < fc.local_rows) & LM(py < fc.y1);
+        if (valid_m == 0) continue;   // (as its own wave such a tile stores nothing either, its duration included: the kernel returns before)
+        const bool valid = lane_in(valid_m);
+        float fr = 0.f, fg = 0.f, fb = 0.f;
+        if ((ts & RT_TILE_NO_MISS) == 0) {   // wave-uniform
+            const unsigned pr_rec = reinterpret_cast<const unsigned *>(fc.rest_rd + RT_REST_PRIMARY_OFFSET(s_tiles))[(size_t)(blk_y * s_tiles_x + blk_x) * (RT_REST_PRIMARY_BYTES / 4u) + lane];
+            if (valid && (pr_rec & 0xffu) == RT_PRIMARY_MISS) {
+                const int idx = clamp_texel((int)(pr_rec >> 8), ax->sky_w * ax->sky_h - 1);
+                fr = ax->sky_r[idx];
+                fg = ax->sky_g[idx];
+                fb = ax->sky_b[idx];
+            }
+        }
+        float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f;
+        for (int sample = 0; sample < n_samples; ++sample)   // (a settled tile's samples are all this one)
+            if (valid) {
+                acc_r = acc_r + fr;
+                acc_g = acc_g + fg;
+                acc_b = acc_b + fb;
+            }
+        // the write-back of rt_trace_tiles
+        const unsigned out_idx = (unsigned)ly * (unsigned)fc.width + (unsigned)px;   // band-local pixel index
+        if (valid) {
+            const size_t o = out_idx;
+            float w = (float)n_samples;
+            if (o_rgba) {
+                float4 *dst = reinterpret_cast<float4 *>(o_rgba) + o;
+                if (o_flags & RT_FLAG_ACCUMULATE) {
+                    const float4 old = *dst;
+                    acc_r = old.x + acc_r;
+                    acc_g = old.y + acc_g;
+                    acc_b = old.z + acc_b;
+                    w = old.w + w;
+                }
+                *dst = make_float4(acc_r, acc_g, acc_b, w);
+            }
+            if (o_packed && (o_flags & RT_FLAG_RESOLVE)) o_packed[o] = resolve_pixel(acc_r, acc_g, acc_b, o_total);
+        }
+        if (o_packed24 && (o_flags & RT_FLAG_RESOLVE)) {   // wave-uniform; all lanes take part in the quad exchange
+            const unsigned q = resolve_pixel(acc_r, acc_g, acc_b, o_total);
+            const unsigned qn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)q, 0xF9 /* quad_perm [1,2,3,3] */, 0xf, 0xf, true);
+            const int i = lane & 3;
+            const unsigned w24 = (q >> (8 * i)) | (qn << (24 - 8 * i));
+            if (valid && i < 3) o_packed24[(size_t)(out_idx >> 2) * 3 + (size_t)i] = w24;
+        }
+        if (o_cost) {
+            const unsigned dt = (unsigned)__builtin_amdgcn_s_memtime() - t_start;
+            if (lane == 0) o_cost[blk_y * s_tiles_x + blk_x] = dt;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -125,3 +125,21 @@ struct RtTileOrderBuf {
     }
 };
 void rt_tile_order_kernel_configs(int tiles_x, int tiles_y, const void *func[3], dim3 grid[3], dim3 block[3]);
+
+// The run list of a compact reading launch (the list section of the RT_REST_* layout block, rt_device.h): a stable
+// partition of the launch's order -- perm[], or grid order when it is null -- into the tiles that keep a wave of their
+// own and, behind them, the streamable ones, with the header {n_unsettled, n_streamed, run, n_ahead} in front. Three small
+// launches on `stream`; they read the table's summaries and, for settled tiles with miss lanes, their primary records.
+#define RT_REST_LIST_BLOCK 256
+#define RT_REST_LIST_MAX_BLOCKS 4096          // what the one-workgroup sum of the blocks' counts holds: 2^20 tiles
+struct RtRestListParams {
+    unsigned char *table;      // the resting-view table of the launch's T tiles
+    const unsigned *perm;      // T entries (tile_y << 16) | tile_x, or null
+    unsigned *scratch;         // rt_rest_list_scratch(T) dwords: a flag per place of the order, a count per block
+    int tile_w, width, local_rows, y0, y1, il_count, il_index, il_rows;   // the launch's geometry, as in RtFrameConsts
+    unsigned run;              // R, 1 ... RT_REST_LIST_RUN_MAX
+    unsigned ahead;            // 1: the runs' workgroups in front of the one-wave tiles' (header: n_ahead), 0: behind them
+};
+inline size_t rt_rest_list_scratch(size_t tiles) { return tiles + (tiles + RT_REST_LIST_BLOCK - 1) / RT_REST_LIST_BLOCK; }
+inline bool rt_rest_list_fits(size_t tiles) { return tiles > 0 && (tiles + RT_REST_LIST_BLOCK - 1) / RT_REST_LIST_BLOCK <= RT_REST_LIST_MAX_BLOCKS; }
+hipError_t rt_rest_list_launch(const RtRestListParams &p, hipStream_t stream);

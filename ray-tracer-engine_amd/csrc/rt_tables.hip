@@ -1123,3 +1123,95 @@ void rt_tile_order_kernel_configs(int tiles_x, int tiles_y, const void *func[3],
     func[1] = (const void *)rt_tile_order_sort_kernel;   grid[1] = dim3(1); block[1] = dim3(1024);
     func[2] = (const void *)rt_tile_order_expand_kernel; grid[2] = dim3((tiles_x * tiles_y + 255) / 256); block[2] = dim3(256);
 }
+
+// ---------------------------------------------------------------------------
+// the run list of a compact reading launch (RT_REST_* layout block of rt_device.h)
+// ---------------------------------------------------------------------------
+// Whether a tile may be streamed: settled, and either without a miss lane or without a valid lane whose primary record
+// says RT_PRIMARY_NONE (such a tile takes the full path, which only a wave of its own has). The valid lanes are formed
+// as the frame kernel forms them.
+__device__ static bool rest_tile_streamable(const RtRestListParams &p, unsigned tiles_x, unsigned tiles, unsigned xy)
+{
+    const unsigned tx = xy & 0xffffu, ty = xy >> 16, tile = ty * tiles_x + tx;
+    const unsigned ts = reinterpret_cast<const unsigned *>(p.table)[RT_REST_SUMMARY_DWORD(tiles, tile)];
+    if (!(ts & RT_TILE_SETTLED)) return false;
+    if (ts & RT_TILE_NO_MISS) return true;
+    const unsigned *rec = reinterpret_cast<const unsigned *>(p.table + RT_REST_PRIMARY_OFFSET(tiles)) + (size_t)tile * (RT_REST_PRIMARY_BYTES / 4u);
+    const int th = 64 / p.tile_w, il_sh = __builtin_ctz((unsigned)p.il_rows);
+    bool none = false;   // (no early exit: the tile's 64 records are asked for together)
+#pragma unroll 16
+    for (int lane = 0; lane < 64; ++lane) {
+        const int ly = (int)ty * th + lane / p.tile_w, px = (int)tx * p.tile_w + lane % p.tile_w;
+        const int py = p.y0 + ((((ly >> il_sh) * p.il_count + p.il_index) << il_sh) | (ly & (p.il_rows - 1)));
+        none = none || (px < p.width && ly < p.local_rows && py < p.y1 && (rec[lane] & 0xffu) == RT_PRIMARY_NONE);
+    }
+    if (none) return false;
+    return true;
+}
+
+// A stable partition of the launch's order in three launches. Classify: a thread per place of the order says whether
+// its tile is streamable (flags[]) and every block of RT_REST_LIST_BLOCK places counts its own (counts[]). Offsets: one
+// workgroup sums the blocks' counts -- how many streamable tiles lie ahead of each block -- and writes the header.
+// Scatter: a thread per place again; a tile that keeps its wave goes to its place less the streamable ones ahead of
+// it, a streamable one behind all of those, to the number of streamable ones ahead of it.
+__global__ __launch_bounds__(RT_REST_LIST_BLOCK) void rt_rest_list_classify_kernel(const RtRestListParams p)
+{
+    const unsigned tiles_x = rt_rest_tiles_x(p.width, p.tile_w), tiles = tiles_x * rt_rest_tiles_y(p.local_rows, p.tile_w);
+    const unsigned i = blockIdx.x * RT_REST_LIST_BLOCK + threadIdx.x;
+    bool f = false;
+    if (i < tiles) {
+        f = rest_tile_streamable(p, tiles_x, tiles, p.perm ? p.perm[i] : ((i / tiles_x) << 16) | (i % tiles_x));
+        p.scratch[i] = f ? 1u : 0u;
+    }
+    const int c = __syncthreads_count(f ? 1 : 0);
+    if (threadIdx.x == 0) p.scratch[tiles + blockIdx.x] = (unsigned)c;
+}
+
+__global__ __launch_bounds__(1024) void rt_rest_list_offsets_kernel(const RtRestListParams p)
+{
+    __shared__ unsigned cnt[RT_REST_LIST_MAX_BLOCKS], tmp[RT_REST_LIST_MAX_BLOCKS];
+    const unsigned tiles = rt_rest_tiles(p.width, p.local_rows, p.tile_w), nb = (tiles + RT_REST_LIST_BLOCK - 1) / RT_REST_LIST_BLOCK;
+    unsigned *const counts = p.scratch + tiles;
+    for (unsigned b = threadIdx.x; b < nb; b += 1024) cnt[b] = counts[b];
+    __syncthreads();
+    scan_inclusive_lds(cnt, tmp, (int)nb);
+    const unsigned n_streamed = cnt[nb - 1];
+    __syncthreads();
+    for (unsigned b = threadIdx.x; b < nb; b += 1024) counts[b] = b ? cnt[b - 1] : 0u;   // streamable tiles ahead of block b
+    if (threadIdx.x == 0) {
+        unsigned *const hdr = reinterpret_cast<unsigned *>(p.table + RT_REST_LIST_OFFSET(tiles));
+        hdr[0] = tiles - n_streamed;
+        hdr[1] = n_streamed;
+        hdr[2] = p.run;
+        hdr[3] = p.ahead ? (n_streamed + p.run - 1u) / p.run : 0u;
+    }
+}
+
+__global__ __launch_bounds__(RT_REST_LIST_BLOCK) void rt_rest_list_scatter_kernel(const RtRestListParams p)
+{
+    __shared__ unsigned wsum[RT_REST_LIST_BLOCK / 64];
+    const unsigned tiles_x = rt_rest_tiles_x(p.width, p.tile_w), tiles = tiles_x * rt_rest_tiles_y(p.local_rows, p.tile_w);
+    unsigned *const hdr = reinterpret_cast<unsigned *>(p.table + RT_REST_LIST_OFFSET(tiles)), *const list = hdr + RT_REST_LIST_HEADER;
+    const unsigned i = blockIdx.x * RT_REST_LIST_BLOCK + threadIdx.x;
+    const bool f = i < tiles && p.scratch[i] != 0u;
+    const unsigned long long m = __ballot(f);
+    const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (lane == 0) wsum[w] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned before = p.scratch[tiles + blockIdx.x] + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+    for (unsigned k = 0; k < w; ++k) before += wsum[k];
+    if (i < tiles) {
+        const unsigned xy = p.perm ? p.perm[i] : ((i / tiles_x) << 16) | (i % tiles_x);
+        list[f ? hdr[0] + before : i - before] = xy;
+    }
+}
+
+hipError_t rt_rest_list_launch(const RtRestListParams &p, hipStream_t stream)
+{
+    const unsigned tiles = rt_rest_tiles(p.width, p.local_rows, p.tile_w), nb = (tiles + RT_REST_LIST_BLOCK - 1) / RT_REST_LIST_BLOCK;
+    if (tiles == 0 || nb > RT_REST_LIST_MAX_BLOCKS || !p.scratch || !p.table || p.run < 1 || p.run > RT_REST_LIST_RUN_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_rest_list_classify_kernel, dim3(nb), dim3(RT_REST_LIST_BLOCK), 0, stream, p);
+    hipLaunchKernelGGL(rt_rest_list_offsets_kernel, dim3(1), dim3(1024), 0, stream, p);
+    hipLaunchKernelGGL(rt_rest_list_scatter_kernel, dim3(nb), dim3(RT_REST_LIST_BLOCK), 0, stream, p);
+    return hipGetLastError();
+}

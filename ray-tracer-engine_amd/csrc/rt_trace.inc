@@ -83,7 +83,21 @@ __global__ __launch_bounds__(64, (TraceCfg<TW, CULL, MODE, FEAT, MULTI>::MIN_WAV
     // the head of the sample loop sends it to the write-back. The others go on from here as they always did, with the
     // summary's latency in front of their loads: the flag is known before anything else is asked for.
     unsigned ts = 0;
-    if (Cfg::MODE == RT_MODE_REST_READ) {
+    if (Cfg::VD_USE) {
+        // The compact launch (step 5e, RT_MODE_REST_COMPACT): a 1-D grid over the table's run list. n_unsettled workgroups take
+        // their tile from it wherever this kernel forms a tile's place -- tile_perm points at the list so that their
+        // blockIdx.x finds their entry -- and go on below as ever; each of the others streams a run of R settled tiles and
+        // ends here. The runs lie behind the one-wave tiles, or (n_ahead > 0) all of them ahead.
+        if (Cfg::COMPACT) {
+            const unsigned *c_hdr = reinterpret_cast<const unsigned *>(fc.rest_rd + RT_REST_LIST_OFFSET(rt_rest_tiles(fc.width, fc.local_rows, Cfg::TW)));
+            const unsigned n_unsettled = c_hdr[0], n_ahead = c_hdr[3];
+            if (blockIdx.x < n_ahead || blockIdx.x >= n_ahead + n_unsettled) {
+                const unsigned c_end = n_unsettled + c_hdr[1], c_run = c_hdr[2];
+                const unsigned c_first = n_unsettled + (blockIdx.x < n_ahead ? blockIdx.x : blockIdx.x - n_unsettled) * c_run;
+                if (c_first < c_end) stream_settled_run<Cfg>(fc, ax, c_hdr + RT_REST_LIST_HEADER, lane, c_first, c_end - c_first < c_run ? c_end - c_first : c_run);
+                return;
+            }
+        }
         // (the tile's place is formed four times -- here, below, at the G-buffer and at the write-back: as one function it
         // changed 8 lines of the product kernel's machine code and 50 of the reading kernel's)
         unsigned h_x = blockIdx.x, h_y = blockIdx.y;
@@ -95,8 +109,8 @@ __global__ __launch_bounds__(64, (TraceCfg<TW, CULL, MODE, FEAT, MULTI>::MIN_WAV
         }
         ts = reinterpret_cast<const unsigned *>(fc.rest_rd)[RT_REST_SUMMARY_DWORD(h_tiles_x * rt_rest_tiles_y(fc.local_rows, Cfg::TW), h_y * h_tiles_x + h_x)];
     }
-    bool settled = Cfg::MODE == RT_MODE_REST_READ && (ts & RT_TILE_SETTLED) != 0;   // wave-uniform
-    if (Cfg::MODE != RT_MODE_REST_READ || !settled) {
+    bool settled = Cfg::VD_USE && (ts & RT_TILE_SETTLED) != 0;   // wave-uniform
+    if (!Cfg::VD_USE || !settled) {
         // (twice, here and where a settled tile falls back: as one function of (mybtab, myatan, lane) it changed 12 lines of the
         // product kernel's machine code and 22 of the multi-sample kernel's)
         if (lane < 16) {
@@ -1286,9 +1300,9 @@ template <int TW, bool CULL, bool MULTI, int MODE, int FEAT>
 static constexpr bool trace_exists()
 {
 #ifdef RT_QUICK   // kernel experiments (tools/variants.sh): the product instantiation and its brute-force twin only
-    if (TW != 8 || FEAT != RT_FEAT_SPHERES || (MODE != RT_MODE_PRODUCT && MODE != RT_MODE_STATS && MODE != RT_MODE_REST_READ && MODE != RT_MODE_REST_WRITE) || (MULTI && MODE != RT_MODE_PRODUCT)) return false;
+    if (TW != 8 || FEAT != RT_FEAT_SPHERES || (MODE != RT_MODE_PRODUCT && MODE != RT_MODE_STATS && MODE != RT_MODE_REST_READ && MODE != RT_MODE_REST_COMPACT && MODE != RT_MODE_REST_WRITE) || (MULTI && MODE != RT_MODE_PRODUCT)) return false;
 #endif
-    if (MODE == RT_MODE_REST_READ || MODE == RT_MODE_REST_WRITE) return CULL && FEAT == RT_FEAT_SPHERES && MULTI == (TW != 8);   // light verdicts: the one-sample kernel (other tiles: the sample loop, one pass)
+    if (MODE == RT_MODE_REST_READ || MODE == RT_MODE_REST_COMPACT || MODE == RT_MODE_REST_WRITE) return CULL && FEAT == RT_FEAT_SPHERES && MULTI == (TW != 8);   // light verdicts: the one-sample kernel (other tiles: the sample loop, one pass)
     if (MODE == RT_MODE_FAST) return TW == 8 && CULL && FEAT != RT_FEAT_MESH;   // fast mode: the product configuration only
     if (MODE == RT_MODE_AOV) return TW == 8 && !MULTI;   // G-buffer: the one-sample kernels of the default tile
     if (TW != 8 && FEAT != RT_FEAT_SPHERES && MODE != RT_MODE_PRODUCT) return false;
@@ -1327,6 +1341,7 @@ static RtTraceFn trace_fn_mode_feat(int mode, int feat)
     case RT_MODE_FAST: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_FAST>(feat);
     case RT_MODE_AOV: return trace_fn_feat<TW, CULL, MULTI, RT_MODE_AOV>(feat);
     case RT_MODE_REST_READ: return feat == RT_FEAT_SPHERES ? trace_fn_one<TW, CULL, MULTI, RT_MODE_REST_READ, RT_FEAT_SPHERES>() : nullptr;
+    case RT_MODE_REST_COMPACT: return feat == RT_FEAT_SPHERES ? trace_fn_one<TW, CULL, MULTI, RT_MODE_REST_COMPACT, RT_FEAT_SPHERES>() : nullptr;
     case RT_MODE_REST_WRITE: return feat == RT_FEAT_SPHERES ? trace_fn_one<TW, CULL, MULTI, RT_MODE_REST_WRITE, RT_FEAT_SPHERES>() : nullptr;
     default: return nullptr;
     }
